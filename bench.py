@@ -12,7 +12,11 @@ clip_grad_value_(1.0) + Adam, the reference's `unpack_input_data_and_predict` + 
 Inputs are resident in HBM before the timed region. One rank per GPU; every rank holds its own
 32 graphs (weak scaling), graphs never cross ranks, the only collective is the gradient all-reduce.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0. A plain run sets up, warms up, times K steps and prints that line
+(`ms_per_step` = milliseconds of one timed step). `--full` adds what the headline figure does not need:
+the roofline and per-kernel breakdown, the CPU baseline and, for the default cfg2 run, the secondary
+configurations. `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy
+(inputs and initial weights are seeded: the same arguments give the same inputs in every run).
 """
 import argparse
 import ctypes as C
@@ -74,6 +78,29 @@ def _kernel_each(lib, name, cap=4096):
     buf, cnt = (C.c_double * cap)(), C.c_int64(0)
     rc = lib.pvs_profile_read_each(name.encode(), buf, cap, C.byref(cnt))
     return [buf[k] for k in range(min(cnt.value, cap))] if rc == 0 else []
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array of `arrays` (name -> tensor) as out_dir/<name>.npy, float64 kept, every other dtype
+    as float32. Should the files exceed 64 MB in all, each array above an even share of that is replaced by a fixed
+    sample of its flattened entries (seeded, in index order), so that two runs still compare entry for entry."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    host = {}
+    for name, v in arrays.items():
+        a = v.detach().cpu().numpy() if hasattr(v, 'detach') else np.asarray(v)
+        host[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    if sum(a.nbytes for a in host.values()) > DUMP_LIMIT_BYTES:
+        share = DUMP_LIMIT_BYTES // len(host)
+        for name, a in host.items():
+            if a.nbytes > share:
+                idx = np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False)
+                host[name] = a.reshape(-1)[np.sort(idx)]
+    for name, a in host.items():
+        np.save(out_dir / f'{name}.npy', a)
 
 
 def scaling_note(args, world, strong):
@@ -395,18 +422,21 @@ def screening_bench(args, rank, world, dev):
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    n_lines = sum(1 for _ in open(pred_file))
-    assert n_lines == timed.shape[0], (n_lines, timed.shape[0])
-
-    # kernel timings of the same step, eager (HIP events cannot be read out of a replayed graph)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {'scores': scores})
     screen = sweep.buckets[n_lig]
-    lib.pvs_profile_reset()
-    lib.pvs_profile_enable(1)
-    prof_steps = 5
-    for k in range(prof_steps):
-        screen(timed[k * args.batch:(k + 1) * args.batch].contiguous())
-    torch.cuda.synchronize(dev)
-    lib.pvs_profile_enable(0)
+    if args.full:
+        n_lines = sum(1 for _ in open(pred_file))
+        assert n_lines == timed.shape[0], (n_lines, timed.shape[0])
+
+        # kernel timings of the same step, eager (HIP events cannot be read out of a replayed graph)
+        lib.pvs_profile_reset()
+        lib.pvs_profile_enable(1)
+        prof_steps = 5
+        for k in range(prof_steps):
+            screen(timed[k * args.batch:(k + 1) * args.batch].contiguous())
+        torch.cuda.synchronize(dev)
+        lib.pvs_profile_enable(0)
 
     def kernel_ms(name):
         tot, cnt = C.c_double(0.0), C.c_int64(0)
@@ -418,14 +448,6 @@ def screening_bench(args, rank, world, dev):
         n_nodes = args.batch * (n_lig + rec.shape[0])
         n_edges = int(screen._fast['rowptr'][n_nodes].item()) if screen._fast else screen.batcher.batch.prepared.n_edges
         n_edges_lig = int(screen._fast['rowptr_l'][n_nodes].item()) if screen._fast else 0
-        fwd_ms, fwd_n = kernel_ms('edge_fwd')
-        part_ms, part_n = kernel_ms('edge_fwd_partial')
-        prep_ms, _ = kernel_ms('graph_prepare')
-        dom_avg_ms = fwd_ms / max(fwd_n, 1)
-        dom_bytes = algorithmic_bytes_edge_fwd(n_nodes, n_edges, h)
-        achieved = dom_bytes / (dom_avg_ms * 1e-3) / 1e9 if dom_avg_ms > 0 else 0.0
-        dom_tflops = (4.0 * h * h + 2 * h) * n_edges / (dom_avg_ms * 1e-3) / 1e12 if dom_avg_ms > 0 else 0.0
-        traffic, traffic_src = measured_traffic('cfg5', 'k_edge_fwd_mfma')
         ms_step = elapsed / args.steps * 1e3
         out = {
             'metric': 'ligand poses/sec, forward only (virtual-screening sweep), 3-layer EGNN ch=32, one '
@@ -437,21 +459,32 @@ def screening_bench(args, rank, world, dev):
                                    f'ligand + 1970-atom receptor, N={n_nodes} nodes E={n_edges} edges per batch '
                                    f'({n_edges_lig} touch the ligand), radius graph from coordinates every step, '
                                    f'first-layer receptor-receptor sums reused: {screen.reuse}, hipGraph replay: '
-                                   f'{bool(screen._captured)}, predictions streamed to a file ({n_lines} lines)',
+                                   f'{bool(screen._captured)}, predictions streamed to a file'
+                                   + (f' ({n_lines} lines)' if args.full else ''),
                        'graphs_per_gpu': args.batch, 'global_batch': world * args.batch, 'parallelism': f'dp{world}',
                        'mean_score': round(float(scores.mean()), 6)},
-            'roofline': {
-                'bound': 'hbm', 'kernel': f'k_edge_fwd_mfma (H={h} edge forward over the full pose-batch graph, '
-                                          f'{layers - 1} launches per step; the first layer runs over the ligand edges only)',
-                'achieved': round(achieved, 2), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-                'frac': round(achieved / HBM_PEAK_GBS, 5), 'traffic': traffic, 'traffic_source': traffic_src,
-                'algorithmic_bytes_per_launch': dom_bytes, 'avg_launch_ms': round(dom_avg_ms, 4), 'launches': fwd_n,
-                'kernel_exec_fp32': {'achieved': round(dom_tflops, 2), 'peak': FP32_PEAK_TFLOPS, 'unit': 'TFLOP/s',
-                                     'frac': round(dom_tflops / FP32_PEAK_TFLOPS, 5)},
-                'kernel_ms_per_step': {'edge_fwd_full_layers': round(fwd_ms / prof_steps, 3),
-                                       'edge_fwd_first_layer_ligand_edges': round(part_ms / prof_steps, 3),
-                                       'graph_build': round(prep_ms / prof_steps, 3)}},
         }
+        if not args.full:
+            return out
+        fwd_ms, fwd_n = kernel_ms('edge_fwd')
+        part_ms, part_n = kernel_ms('edge_fwd_partial')
+        prep_ms, _ = kernel_ms('graph_prepare')
+        dom_avg_ms = fwd_ms / max(fwd_n, 1)
+        dom_bytes = algorithmic_bytes_edge_fwd(n_nodes, n_edges, h)
+        achieved = dom_bytes / (dom_avg_ms * 1e-3) / 1e9 if dom_avg_ms > 0 else 0.0
+        dom_tflops = (4.0 * h * h + 2 * h) * n_edges / (dom_avg_ms * 1e-3) / 1e12 if dom_avg_ms > 0 else 0.0
+        traffic, traffic_src = measured_traffic('cfg5', 'k_edge_fwd_mfma')
+        out['roofline'] = {
+            'bound': 'hbm', 'kernel': f'k_edge_fwd_mfma (H={h} edge forward over the full pose-batch graph, '
+                                      f'{layers - 1} launches per step; the first layer runs over the ligand edges only)',
+            'achieved': round(achieved, 2), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+            'frac': round(achieved / HBM_PEAK_GBS, 5), 'traffic': traffic, 'traffic_source': traffic_src,
+            'algorithmic_bytes_per_launch': dom_bytes, 'avg_launch_ms': round(dom_avg_ms, 4), 'launches': fwd_n,
+            'kernel_exec_fp32': {'achieved': round(dom_tflops, 2), 'peak': FP32_PEAK_TFLOPS, 'unit': 'TFLOP/s',
+                                 'frac': round(dom_tflops / FP32_PEAK_TFLOPS, 5)},
+            'kernel_ms_per_step': {'edge_fwd_full_layers': round(fwd_ms / prof_steps, 3),
+                                   'edge_fwd_first_layer_ligand_edges': round(part_ms / prof_steps, 3),
+                                   'graph_build': round(prep_ms / prof_steps, 3)}}
         if world == 1 and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline_screening(cfg, lig, rec, feats)
         return out
@@ -480,11 +513,21 @@ def main():
     ap.add_argument('--skip-dead-coords', action='store_true',
                     help='let the model skip the last layer\'s coordinate update, whose result nothing reads '
                          '(the library default); the bench evaluates it by default, like the reference does')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline figure does not need: the per-kernel breakdown and roofline '
+                         'of the timed configuration (HIP events around the dominant kernel inside the timed steps, '
+                         'profiled eager steps behind them), the CPU baseline and, for the default cfg2 run, the '
+                         'secondary configurations. Without it a run sets up, warms up, times --steps steps and prints '
+                         'the line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed (logits, loss, parameters '
+                         'and their gradients; cfg5: the pose scores) as DIR/<name>.npy in float32 / float64, '
+                         'at most 64 MB in all')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: no CPU baseline')
     ap.add_argument('--no-secondary', action='store_true',
-                    help='default cfg2 run only: do not also time BASELINE configs 3 and 5 behind the headline (the '
-                         '"secondary" object of the line); implied by --no-cpu-baseline, the flag of every profiling and '
-                         'A/B invocation under tools/ (a kernel trace of ONE configuration)')
+                    help='with --full, default cfg2 run only: do not also time BASELINE configs 3 and 5 behind the '
+                         'headline (the "secondary" object of the line); implied by --no-cpu-baseline, the flag of every '
+                         'profiling and A/B invocation under tools/ (a kernel trace of ONE configuration)')
     ap.add_argument('--model-flags', default='',
                     help='NOT a BASELINE configuration: extra model keywords on top of --config, e.g. '
                          '"edge_residual=True,tanh=True" (profiles of kernel instantiations no BASELINE config uses); '
@@ -565,7 +608,8 @@ def main():
         out = training_bench(args, rank, world, dev)
         plain = not (args.infer or args.model_flags or args.build_graph or args.host_inputs or strong or args.force_dist
                      or args.graph or args.skip_dead_coords or args.batch != 32)
-        if args.config == 'cfg2' and world == 1 and plain and not (args.no_secondary or args.no_cpu_baseline):
+        if (args.full and args.config == 'cfg2' and world == 1 and plain
+                and not (args.no_secondary or args.no_cpu_baseline)):
             sec = secondary_configs(args, rank, world, dev)
             if out is not None:
                 out['secondary'] = sec
@@ -595,6 +639,7 @@ def secondary_configs(args, rank, world, dev):
         for k, v in changes.items():
             setattr(a, k, v)
         a.no_cpu_baseline = True
+        a.dump_outputs = None         # (the dumped outputs are the headline's)
         rec = screening_bench(a, rank, world, dev) if name == 'cfg5' else training_bench(a, rank, world, dev)
         if rec is None:
             continue
@@ -660,9 +705,12 @@ def training_bench(args, rank, world, dev):
     # kernels), so off by default
     prefetch = int(os.environ.get('PVS_BENCH_PREFETCH', '0')) and not use_graph
 
+    last = {}       # the logits of the most recent step (--dump-outputs; under a graph: the captured step's output)
+
     def infer_step():
         with torch.no_grad():
-            return model(batch).reshape(-1).sum()
+            last['y_pred'] = model(batch).reshape(-1)
+            return last['y_pred'].sum()
 
     if args.build_graph:
         from pointvs_amd.radius_graph import attach_radius_graph
@@ -675,7 +723,7 @@ def training_bench(args, rank, world, dev):
             attach_radius_graph(batch, cfg['graph']['edge_radius'])
         if args.infer:
             return infer_step()
-        y_pred = model(batch).reshape(-1)
+        y_pred = last['y_pred'] = model(batch).reshape(-1)
         if prefetch:   # the next batch's CSR/CSC build (here: the same tensors) runs on a side
             # stream under this batch's backward, as a data loader's look-ahead would arrange it
             pgraph.prefetch_graph(batch.edge_index, batch.edge_attr, n_nodes, layout=pgraph.runs_layout(batch))
@@ -711,13 +759,14 @@ def training_bench(args, rank, world, dev):
                 hip_graph.replay()
                 return static_loss
             step()
-        # HIP events around the DOMINANT kernel only inside the timed region (roofline.avg_launch_ms is measured live, as
-        # the contract asks); an event pair costs the stream a ~6 us bubble per launch (tools/step_timeline.py), so the
-        # other groups of the per-step breakdown are timed in three more steps behind the timed region
+        # --full: HIP events around the DOMINANT kernel only inside the timed region (roofline.avg_launch_ms is measured
+        # live, as the contract asks); an event pair costs the stream a ~6 us bubble per launch (tools/step_timeline.py),
+        # so the other groups of the per-step breakdown are timed in three more steps behind the timed region. Without
+        # --full nothing is recorded: the timed steps are the step and nothing else
         prof_ids = {'edge_fwd': 0, 'edge_bwd': 1, 'col_gather': 2, 'graph_prepare': 3}
         dom_group = 'edge_fwd' if args.infer else 'edge_bwd'
         lib.pvs_profile_reset()
-        lib.pvs_profile_enable(0 if use_graph else 1 << (prof_ids[dom_group] + 1))
+        lib.pvs_profile_enable(0 if use_graph or not args.full else 1 << (prof_ids[dom_group] + 1))
         # (as train_model does, point_neural_network_base.long_lived_heap_frozen: Python's first full collection walks the
         # ~170,000 objects `import torch` leaves behind - 60-170 ms, once, wherever the allocation count puts it: in a
         # 0.1 s timed region that is luck, not throughput. PVS_GC_FREEZE=0 leaves the collector alone.)
@@ -760,16 +809,26 @@ def training_bench(args, rank, world, dev):
         if freeze:
             gc.unfreeze()
         lib.pvs_profile_enable(0)
-        dom_live = None if use_graph else _kernel_ms(lib, dom_group)      # (total ms, launches) of the timed region
-        dom_each = [] if use_graph else _kernel_each(lib, dom_group)
-        # the per-step breakdown (every group), eager, behind the timed region
-        lib.pvs_profile_reset()
-        lib.pvs_profile_enable(1)
+        if args.dump_outputs and rank == 0:      # what the last timed step computed, before anything else runs a step
+            outputs = {'y_pred': last['y_pred']}
+            if not args.infer:
+                outputs['loss'] = loss
+                for name, p in model.named_parameters():
+                    outputs[f'param.{name}'] = p
+                    if p.grad is not None:
+                        outputs[f'grad.{name}'] = p.grad
+            dump_outputs(args.dump_outputs, outputs)
         prof_steps = 3
-        for _ in range(prof_steps):
-            eager_step()
-        torch.cuda.synchronize(dev)
-        lib.pvs_profile_enable(0)
+        if args.full:
+            dom_live = None if use_graph else _kernel_ms(lib, dom_group)      # (total ms, launches) of the timed region
+            dom_each = [] if use_graph else _kernel_each(lib, dom_group)
+            # the per-step breakdown (every group), eager, behind the timed region
+            lib.pvs_profile_reset()
+            lib.pvs_profile_enable(1)
+            for _ in range(prof_steps):
+                eager_step()
+            torch.cuda.synchronize(dev)
+            lib.pvs_profile_enable(0)
     rank_ms = [elapsed / args.steps * 1e3]
     if distributed:     # the contract's value uses the MAX over ranks; min / max per rank make a straggler visible
         every = [torch.zeros(1, dtype=torch.float64, device=dev) for _ in range(world)]
@@ -789,38 +848,6 @@ def training_bench(args, rank, world, dev):
         training = not args.infer
         ms_step = elapsed / args.steps * 1e3
         graphs_per_s = world * args.batch * args.steps / elapsed
-        bwd_ms, bwd_n = kernel_ms('edge_bwd')
-        fwd_ms, fwd_n = kernel_ms('edge_fwd')
-        col_ms, col_n = kernel_ms('col_gather')
-        prep_ms, prep_n = kernel_ms('graph_prepare')
-        if training:     # dominant kernel: the edge backward (one launch per layer)
-            dom_ms, dom_n = dom_live if dom_live and dom_live[1] > 0 else (bwd_ms, bwd_n)
-            dom_bytes = algorithmic_bytes_edge_bwd(n_nodes, n_edges, h)
-            dom_flops = (12.0 * h * h + 4 * h) * n_edges     # 2 recompute + 2 dgrad + 2 wgrad products
-            fp32_family = os.environ.get('PVS_EGNN_BF16X3') == '0'
-            dom_symbol = (('k_edge_bwd_mfma' if fp32_family else 'k_edge_bwd_f16') if h == 32
-                          else ('k_edge_bwd_team' if fp32_family else 'k_edge_bwd_h64'))
-            dom_name = (f'{dom_symbol} (H={h} edge backward, one launch per layer)')
-            step_bytes = layers * algorithmic_bytes_per_layer(n_nodes, n_edges, h)
-        else:            # forward only: the edge forward
-            dom_ms, dom_n = dom_live if dom_live and dom_live[1] > 0 else (fwd_ms, fwd_n)
-            dom_bytes = algorithmic_bytes_edge_fwd(n_nodes, n_edges, h)
-            dom_flops = (4.0 * h * h + 2 * h) * n_edges
-            dom_symbol = 'k_edge_fwd_mfma'
-            dom_name = f'k_edge_fwd_mfma (H={h} edge forward, one launch per layer)'
-            step_bytes = layers * dom_bytes
-        dom_avg_ms = dom_ms / max(dom_n, 1)
-        achieved = dom_bytes / (dom_avg_ms * 1e-3) / 1e9 if dom_avg_ms > 0 else 0.0
-        dom_tflops = dom_flops / (dom_avg_ms * 1e-3) / 1e12 if dom_avg_ms > 0 else 0.0
-        # The launches of one step do not do the same work: the backward runs the layers last to first, and nothing
-        # differentiates the last layer's coordinate update (its x is dead: SURVEY Q3, the reference's autograd skips
-        # it too), so the FIRST backward launch of every step has no coordinate branch. `avg_launch_ms` is over all
-        # launches (the contract's definition); `avg_launch_ms_full_work` leaves those lighter launches out.
-        full = [ms for k, ms in enumerate(dom_each) if k % layers != 0] if (training and layers > 1) else []
-        full_avg_ms = sum(full) / len(full) if full else None
-        ref_flops = algorithmic_flops_per_step(n_nodes, n_edges, h, 3, layers, eatt, natt, training)
-        exec_flops = executed_flops_per_step(n_nodes, n_edges, h, layers, eatt, natt, training)
-        traffic, traffic_src = measured_traffic(args.config, dom_symbol)
         what = 'forward only (inference)' if args.infer else 'fwd+bwd (+Adam step)'
         shape = {'cfg2': '3-layer EGNN ch=32, ~2k nodes r=10A',
                  'cfg3': '12-layer EGNN ch=64 edge+node attention, ~2k nodes r=6A',
@@ -867,32 +894,66 @@ def training_bench(args, rank, world, dev):
                                          'counting (verified on the device)'
                                          if pgraph.runs_layout(batch) is not None else
                                          'int64 COO + one-hot parsed every step (two radix sorts)')},
-            'roofline': {
-                'bound': 'hbm', 'kernel': dom_name,
-                'achieved': round(achieved, 2), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-                'frac': round(achieved / HBM_PEAK_GBS, 5), 'traffic': traffic, 'traffic_source': traffic_src,
-                **measured_limiter(args.config, dom_symbol),
-                'algorithmic_bytes_per_launch': dom_bytes,
-                'avg_launch_ms': round(dom_avg_ms, 4), 'launches': dom_n,
-                'avg_launch_ms_full_work': None if full_avg_ms is None else round(full_avg_ms, 4),
-                'frac_full_work': None if not full_avg_ms else round(dom_bytes / (full_avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
-                # the kernel is ALU-bound, not HBM-bound: its EXECUTED products against the
-                # fp32 matrix peak, beside the HBM fraction north_star asks for. The products run as three fp16
-                # terms (H = 32) or six bf16 terms (H = 64 backward) on the 16-bit matrix pipes, so this is an
-                # effective fp32 rate, not a utilisation: the PMC busy figures in profiles/ are the utilisation
-                'kernel_exec_fp32': {'achieved': round(dom_tflops, 2), 'peak': FP32_PEAK_TFLOPS, 'unit': 'TFLOP/s',
-                                     'frac': round(dom_tflops / FP32_PEAK_TFLOPS, 5)},
-                'step_hbm_frac': round(step_bytes / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
-                # executed FLOPs of the step (the P/Q split removes 4H^2 per edge per pass of the
-                # reference formulation) and, for comparison, the reference formulation's count
-                'step_exec_fp32_frac': round(exec_flops / (ms_step * 1e-3) / 1e12 / FP32_PEAK_TFLOPS, 5),
-                'step_ref_formulation_fp32_frac': round(ref_flops / (ms_step * 1e-3) / 1e12 / FP32_PEAK_TFLOPS, 5),
-                'kernel_ms_per_step': {
-                    'edge_fwd': round(fwd_ms / prof_steps, 3),
-                    'edge_bwd': round(bwd_ms / prof_steps, 3),
-                    'col_gather': round(col_ms / prof_steps, 3),
-                    'graph_prepare': round(prep_ms / prof_steps, 3)}},
         }
+        if not args.full:
+            return out
+        bwd_ms, bwd_n = kernel_ms('edge_bwd')
+        fwd_ms, fwd_n = kernel_ms('edge_fwd')
+        col_ms, col_n = kernel_ms('col_gather')
+        prep_ms, prep_n = kernel_ms('graph_prepare')
+        if training:     # dominant kernel: the edge backward (one launch per layer)
+            dom_ms, dom_n = dom_live if dom_live and dom_live[1] > 0 else (bwd_ms, bwd_n)
+            dom_bytes = algorithmic_bytes_edge_bwd(n_nodes, n_edges, h)
+            dom_flops = (12.0 * h * h + 4 * h) * n_edges     # 2 recompute + 2 dgrad + 2 wgrad products
+            fp32_family = os.environ.get('PVS_EGNN_BF16X3') == '0'
+            dom_symbol = (('k_edge_bwd_mfma' if fp32_family else 'k_edge_bwd_f16') if h == 32
+                          else ('k_edge_bwd_team' if fp32_family else 'k_edge_bwd_h64'))
+            dom_name = (f'{dom_symbol} (H={h} edge backward, one launch per layer)')
+            step_bytes = layers * algorithmic_bytes_per_layer(n_nodes, n_edges, h)
+        else:            # forward only: the edge forward
+            dom_ms, dom_n = dom_live if dom_live and dom_live[1] > 0 else (fwd_ms, fwd_n)
+            dom_bytes = algorithmic_bytes_edge_fwd(n_nodes, n_edges, h)
+            dom_flops = (4.0 * h * h + 2 * h) * n_edges
+            dom_symbol = 'k_edge_fwd_mfma'
+            dom_name = f'k_edge_fwd_mfma (H={h} edge forward, one launch per layer)'
+            step_bytes = layers * dom_bytes
+        dom_avg_ms = dom_ms / max(dom_n, 1)
+        achieved = dom_bytes / (dom_avg_ms * 1e-3) / 1e9 if dom_avg_ms > 0 else 0.0
+        dom_tflops = dom_flops / (dom_avg_ms * 1e-3) / 1e12 if dom_avg_ms > 0 else 0.0
+        # The launches of one step do not do the same work: the backward runs the layers last to first, and nothing
+        # differentiates the last layer's coordinate update (its x is dead: SURVEY Q3, the reference's autograd skips
+        # it too), so the FIRST backward launch of every step has no coordinate branch. `avg_launch_ms` is over all
+        # launches (the contract's definition); `avg_launch_ms_full_work` leaves those lighter launches out.
+        full = [ms for k, ms in enumerate(dom_each) if k % layers != 0] if (training and layers > 1) else []
+        full_avg_ms = sum(full) / len(full) if full else None
+        ref_flops = algorithmic_flops_per_step(n_nodes, n_edges, h, 3, layers, eatt, natt, training)
+        exec_flops = executed_flops_per_step(n_nodes, n_edges, h, layers, eatt, natt, training)
+        traffic, traffic_src = measured_traffic(args.config, dom_symbol)
+        out['roofline'] = {
+            'bound': 'hbm', 'kernel': dom_name,
+            'achieved': round(achieved, 2), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+            'frac': round(achieved / HBM_PEAK_GBS, 5), 'traffic': traffic, 'traffic_source': traffic_src,
+            **measured_limiter(args.config, dom_symbol),
+            'algorithmic_bytes_per_launch': dom_bytes,
+            'avg_launch_ms': round(dom_avg_ms, 4), 'launches': dom_n,
+            'avg_launch_ms_full_work': None if full_avg_ms is None else round(full_avg_ms, 4),
+            'frac_full_work': None if not full_avg_ms else round(dom_bytes / (full_avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
+            # the kernel is ALU-bound, not HBM-bound: its EXECUTED products against the
+            # fp32 matrix peak, beside the HBM fraction north_star asks for. The products run as three fp16
+            # terms (H = 32) or six bf16 terms (H = 64 backward) on the 16-bit matrix pipes, so this is an
+            # effective fp32 rate, not a utilisation: the PMC busy figures in profiles/ are the utilisation
+            'kernel_exec_fp32': {'achieved': round(dom_tflops, 2), 'peak': FP32_PEAK_TFLOPS, 'unit': 'TFLOP/s',
+                                 'frac': round(dom_tflops / FP32_PEAK_TFLOPS, 5)},
+            'step_hbm_frac': round(step_bytes / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
+            # executed FLOPs of the step (the P/Q split removes 4H^2 per edge per pass of the
+            # reference formulation) and, for comparison, the reference formulation's count
+            'step_exec_fp32_frac': round(exec_flops / (ms_step * 1e-3) / 1e12 / FP32_PEAK_TFLOPS, 5),
+            'step_ref_formulation_fp32_frac': round(ref_flops / (ms_step * 1e-3) / 1e12 / FP32_PEAK_TFLOPS, 5),
+            'kernel_ms_per_step': {
+                'edge_fwd': round(fwd_ms / prof_steps, 3),
+                'edge_bwd': round(bwd_ms / prof_steps, 3),
+                'col_gather': round(col_ms / prof_steps, 3),
+                'graph_prepare': round(prep_ms / prof_steps, 3)}}
         if world == 1 and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(cfg)
         return out

@@ -144,11 +144,27 @@ def rccl_single_rank_bench(out_path):
         sys.path.insert(0, str(ROOT))
     import bench
     sys.argv = ['bench.py', '--gpus', '1', '--steps', '3', '--warmup', '2', '--batch', '2', '--force-dist',
-                '--no-cpu-baseline']
+                '--full', '--no-cpu-baseline']
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
         bench.main()
     Path(out_path).write_text(buf.getvalue())
+
+
+def bench_plain_dump(out_dir):
+    """A plain `bench.py --dump-outputs` run (no --full) in a process of its own: the result line goes to
+    out_dir/line.txt, the last timed step's outputs to out_dir/dump/."""
+    import contextlib
+    import io
+    if str(ROOT) not in sys.path:
+        sys.path.insert(0, str(ROOT))
+    import bench
+    sys.argv = ['bench.py', '--gpus', '1', '--steps', '3', '--warmup', '1', '--batch', '2',
+                '--dump-outputs', str(Path(out_dir) / 'dump')]
+    buf = io.StringIO()
+    with contextlib.redirect_stdout(buf):
+        bench.main()
+    (Path(out_dir) / 'line.txt').write_text(buf.getvalue())
 
 
 def rccl_single_rank_reducer(out_path):

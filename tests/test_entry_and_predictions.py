@@ -186,3 +186,22 @@ def test_bench_limiter_label_follows_the_parsed_shares(tmp_path, monkeypatch):
     assert bench.measured_limiter('cfg2', 'k_c')['limiter'] == 'matrix_pipe'
     assert bench.measured_limiter('cfg2', 'k_d')['limiter'] == 'wave_stalls'         # nothing over a threshold: the largest share
     assert bench.measured_limiter('cfg9', 'k_a')['limiter'] is None
+
+
+def test_bench_dump_outputs_dtypes_and_size_cap(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float64 stays float64, every other dtype is written as float32; above the size cap each
+    array larger than its even share becomes a fixed sample of its entries, the same sample in every run."""
+    import bench
+    big = torch.arange(4000, dtype=torch.float32).reshape(40, 100)
+    bench.dump_outputs(tmp_path / 'a', {'loss': torch.tensor(0.25, dtype=torch.float16), 'w': big,
+                                        'd': np.arange(3, dtype=np.float64)})
+    assert np.load(tmp_path / 'a' / 'loss.npy').dtype == np.float32 and float(np.load(tmp_path / 'a' / 'loss.npy')) == 0.25
+    assert np.array_equal(np.load(tmp_path / 'a' / 'w.npy'), big.numpy())
+    assert np.load(tmp_path / 'a' / 'd.npy').dtype == np.float64
+    monkeypatch.setattr(bench, 'DUMP_LIMIT_BYTES', 2 * 1024)
+    for run in ('b', 'c'):
+        bench.dump_outputs(tmp_path / run, {'w': big, 'small': np.ones(4, dtype=np.float32)})
+    w_b, w_c = np.load(tmp_path / 'b' / 'w.npy'), np.load(tmp_path / 'c' / 'w.npy')
+    assert w_b.shape == (256,) and np.array_equal(w_b, w_c)
+    assert np.all(np.diff(w_b) > 0) and set(w_b.tolist()) <= set(range(4000))        # entries of `big`, in index order
+    assert np.array_equal(np.load(tmp_path / 'b' / 'small.npy'), np.ones(4, dtype=np.float32))

@@ -152,3 +152,32 @@ def test_bench_multi_rank_path_runs_on_rccl_with_one_rank(tmp_path):
     rec = json.loads(line)
     assert rec['n_gpus'] == 1 and rec['value'] > 0 and rec['config']['launch'] == 'eager'
     assert rec['config']['arithmetic']          # says how the fp32 products are formed; wording not pinned
+    assert rec['roofline']['launches'] > 0      # --full: the dominant kernel timed inside the timed steps
+
+
+def test_bench_plain_run_times_the_steps_asked_for_and_dumps_the_last_one_reproducibly(tmp_path):
+    """`bench.py --steps K --dump-outputs DIR` without --full: the line carries the headline fields and nothing that needs
+    runs of its own; two fresh processes with the same arguments write the same last-step outputs, bit for bit."""
+    import json
+    runs = []
+    for k in range(2):
+        (tmp_path / f'run{k}').mkdir()
+        _run_one(W.bench_plain_dump, tmp_path / f'run{k}')
+        line = [ln for ln in (tmp_path / f'run{k}' / 'line.txt').read_text().splitlines() if ln.startswith('{')][-1]
+        runs.append(json.loads(line))
+    rec = runs[0]
+    for key in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+        assert key in rec, key
+    assert rec['steps'] == 3 and rec['warmup'] == 1 and rec['ms_per_step'] > 0
+    assert not {'roofline', 'cpu_baseline', 'secondary'} & set(rec), sorted(rec)
+    d0, d1 = tmp_path / 'run0' / 'dump', tmp_path / 'run1' / 'dump'
+    names = sorted(f.name for f in d0.glob('*.npy'))
+    assert names == sorted(f.name for f in d1.glob('*.npy'))
+    assert {'y_pred.npy', 'loss.npy'} <= set(names)
+    assert any(n.startswith('param.') for n in names) and any(n.startswith('grad.') for n in names)
+    for n in names:
+        a, b = np.load(d0 / n), np.load(d1 / n)
+        assert a.dtype == np.float32 and np.all(np.isfinite(a)), n
+        assert np.array_equal(a, b), n
+    assert np.load(d0 / 'y_pred.npy').shape == (2,)
+    assert round(float(np.load(d0 / 'loss.npy')), 6) == rec['config']['final_loss']

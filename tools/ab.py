@@ -14,7 +14,7 @@ for r in range(rounds):
     for name, path in libs:
         e = dict(os.environ, PVS_EGNN_LIB=str(Path(path).resolve()))
         try:
-            out = subprocess.run([sys.executable, str(ROOT / 'bench.py'), '--steps', '4', '--warmup', '2',
+            out = subprocess.run([sys.executable, str(ROOT / 'bench.py'), '--full', '--steps', '4', '--warmup', '2',
                                   '--no-cpu-baseline'] + os.environ.get('AB_ARGS', '').split(), env=e, capture_output=True,
                                  text=True, timeout=float(os.environ.get('AB_TIMEOUT', '240')))
         except subprocess.TimeoutExpired:

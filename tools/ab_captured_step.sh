@@ -8,7 +8,7 @@ mkdir -p gpurun_out
 for cfg in cfg2 cfg3; do
   for r in $(seq 1 $rounds); do
     for g in 0 1; do
-      line=$(python3 bench.py --config $cfg --graph $g --steps $steps --warmup 5 --no-cpu-baseline 2>/dev/null | grep '^{' | tail -1)
+      line=$(python3 bench.py --full --config $cfg --graph $g --steps $steps --warmup 5 --no-cpu-baseline 2>/dev/null | grep '^{' | tail -1)
       python3 - "$cfg" "$r" "$g" "$line" >> $out <<'PY'
 import json, sys
 cfg, r, g, line = sys.argv[1:5]

@@ -20,7 +20,7 @@ res = {n: [] for n, _ in variants}
 for r in range(3):
     for name, env in variants:
         e = dict(os.environ, **env)
-        out = subprocess.run([sys.executable, str(ROOT / 'bench.py'), '--steps', '4', '--warmup', '2',
+        out = subprocess.run([sys.executable, str(ROOT / 'bench.py'), '--full', '--steps', '4', '--warmup', '2',
                               '--no-cpu-baseline'] + extra, env=e, capture_output=True, text=True)
         line = [l for l in out.stdout.splitlines() if l.startswith('{')]
         if not line:

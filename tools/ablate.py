@@ -19,7 +19,7 @@ VARIANTS = [('baseline', {}), ('no_mfma', {'PVS_ABLATE': '1'}), ('no_reduce', {'
 
 for name, env in VARIANTS:
     e = dict(os.environ, **env)
-    out = subprocess.run([sys.executable, str(ROOT / 'bench.py'), '--steps', '3', '--warmup', '1',
+    out = subprocess.run([sys.executable, str(ROOT / 'bench.py'), '--full', '--steps', '3', '--warmup', '1',
                           '--no-cpu-baseline'], env=e, capture_output=True, text=True)
     line = [l for l in out.stdout.splitlines() if l.startswith('{')]
     if not line:

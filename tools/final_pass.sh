@@ -6,15 +6,15 @@ out=gpurun_out/final_$tag
 mkdir -p $out
 export TMPDIR=/tmp
 line() { grep '^{' | tail -1; }          # keep the JSON line only ([Gloo] / library chatter goes to stdout too)
-python3 bench.py --steps 20 --warmup 5 2> $out/bench_cfg2.err | line > $out/bench_cfg2.json
-python3 bench.py --config cfg3 2>/dev/null | line > $out/bench_cfg3.json        # (with cpu_baseline since round 4)
-python3 bench.py --infer --no-cpu-baseline 2>/dev/null | line > $out/bench_cfg2_infer.json
-python3 bench.py --config cfg5 --sweep 12800 2>/dev/null | line > $out/bench_cfg5.json
-python3 bench.py --skip-dead-coords --no-cpu-baseline 2>/dev/null | line > $out/bench_cfg2_skip.json
-PVS_BENCH_BACKEND=gloo python3 bench.py --gpus 2 --steps 5 --warmup 2 2>/dev/null | line > $out/bench_cfg2_gpus2_gloo_shared_gpu.json
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_cfg2 -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline > $out/prof_cfg2.json 2> $out/prof_cfg2.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_cfg3 -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --config cfg3 > $out/prof_cfg3.json 2> $out/prof_cfg3.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_cfg5 -- python3 bench.py --config cfg5 --steps 50 --warmup 5 --graph 0 --no-cpu-baseline > $out/prof_cfg5.json 2> $out/prof_cfg5.err
+python3 bench.py --full --steps 20 --warmup 5 2> $out/bench_cfg2.err | line > $out/bench_cfg2.json
+python3 bench.py --full --config cfg3 2>/dev/null | line > $out/bench_cfg3.json        # (with cpu_baseline since round 4)
+python3 bench.py --full --infer --no-cpu-baseline 2>/dev/null | line > $out/bench_cfg2_infer.json
+python3 bench.py --full --config cfg5 --sweep 12800 2>/dev/null | line > $out/bench_cfg5.json
+python3 bench.py --full --skip-dead-coords --no-cpu-baseline 2>/dev/null | line > $out/bench_cfg2_skip.json
+PVS_BENCH_BACKEND=gloo python3 bench.py --full --gpus 2 --steps 5 --warmup 2 2>/dev/null | line > $out/bench_cfg2_gpus2_gloo_shared_gpu.json
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_cfg2 -- python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline > $out/prof_cfg2.json 2> $out/prof_cfg2.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_cfg3 -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --config cfg3 > $out/prof_cfg3.json 2> $out/prof_cfg3.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_cfg5 -- python3 bench.py --full --config cfg5 --steps 50 --warmup 5 --graph 0 --no-cpu-baseline > $out/prof_cfg5.json 2> $out/prof_cfg5.err
 # one step's launches in order (round 6: kept for cfg2 and cfg3 too), then keep only the summaries (the traces are large)
 python3 tools/step_timeline.py $out/prof_cfg2 > $out/step_timeline_cfg2.txt 2>&1
 python3 tools/step_timeline.py $out/prof_cfg3 > $out/step_timeline_cfg3.txt 2>&1
@@ -35,7 +35,7 @@ python3 tools/soak.py --repeats 40 --states nan,garbage --out $out/soak_poison.j
 tools/pmc_lat.sh ${tag} > $out/pmc_lat.txt 2>&1
 find gpurun_out/pmc_lat_${tag} -name '*.csv' -size +1M -delete
 tools/variants_r3b.sh $out/variants.txt > /dev/null 2>&1
-python3 bench.py --config cfg5 --sweep 100000 --no-cpu-baseline 2>/dev/null | line > $out/bench_cfg5_sweep100000.json
+python3 bench.py --full --config cfg5 --sweep 100000 --no-cpu-baseline 2>/dev/null | line > $out/bench_cfg5_sweep100000.json
 # round 4 additions: sustained clocks, strong-scaling legs, the 1-rank RCCL all-reduce, strict-parity margins, dynamic range
 tools/sustained.sh ${tag} > $out/sustained_summary.txt 2>&1
 tools/strong_scaling_legs.sh > $out/strong_scaling_one_gpu_legs.txt 2>&1
@@ -43,9 +43,9 @@ python3 tools/allreduce_microbench.py 2>/dev/null | line > $out/allreduce_one_ra
 python3 tools/dynamic_range_probe.py 2>/dev/null | grep -v amdgpu.ids > $out/dynamic_range.txt
 python3 -m pytest tests/test_gpu_parity.py tests/test_gpu_baseline_parity.py -q -m gpu > $out/parity.log 2>&1; cp gpurun_out/parity_margins.txt $out/parity_margins.txt
 # round 5 additions: the launch-bound shape (the reference's CLI defaults), eager and captured, with one step's timeline
-python3 bench.py --config real4A --steps 200 --warmup 30 --graph 0 --no-cpu-baseline 2>/dev/null | line > $out/real_shape_eager.json
-python3 bench.py --config real4A --steps 200 --warmup 30 --graph 1 --no-cpu-baseline 2>/dev/null | line > $out/real_shape_graph.json
-rocprofv3 --kernel-trace --output-format csv -d $out/trace_real4A -- python3 bench.py --config real4A --steps 3 --warmup 2 --graph 0 --no-cpu-baseline > /dev/null 2>&1
+python3 bench.py --full --config real4A --steps 200 --warmup 30 --graph 0 --no-cpu-baseline 2>/dev/null | line > $out/real_shape_eager.json
+python3 bench.py --full --config real4A --steps 200 --warmup 30 --graph 1 --no-cpu-baseline 2>/dev/null | line > $out/real_shape_graph.json
+rocprofv3 --kernel-trace --output-format csv -d $out/trace_real4A -- python3 bench.py --full --config real4A --steps 3 --warmup 2 --graph 0 --no-cpu-baseline > /dev/null 2>&1
 python3 tools/step_timeline.py $out/trace_real4A > $out/step_timeline_real4A.txt 2>&1
 find $out/trace_real4A -name '*.csv' -size +1M -delete
 python3 -m pytest tests/test_gpu_lazy_scales.py tests/test_gpu_properties.py -q -m gpu -k "lazy or tile_magnitudes or bias_sums or dynamic_range or binades" > $out/lazy_tests.log 2>&1
@@ -57,4 +57,4 @@ tools/micro/valu_issue_bench.bin sigmoid > $out/micro_sigmoid.txt 2>&1
 
 # round 6 additions: which host operation launches the torch-side kernels of a step; the gloo two-rank line under an RCCL protocol flag (recorded only)
 python3 tools/launch_origins.py cfg2 2>&1 | grep -v "amdgpu.ids\|Warning\|_warn_once" > $out/launch_origins_cfg2.txt
-python3 bench.py --gpus 1 --force-dist --rccl-proto LL --steps 5 --warmup 2 --no-cpu-baseline 2>/dev/null | line > $out/bench_cfg2_one_rank_rccl_ll.json
+python3 bench.py --full --gpus 1 --force-dist --rccl-proto LL --steps 5 --warmup 2 --no-cpu-baseline 2>/dev/null | line > $out/bench_cfg2_one_rank_rccl_ll.json

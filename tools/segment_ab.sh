@@ -7,7 +7,7 @@
 out=$1; : > $out
 for b in 32 16 8 4 2 1; do
   steps=$(( 640 / b )); [ $steps -gt 120 ] && steps=120
-  line=$(python3 bench.py --batch $b --graph 1 --steps $steps --warmup 5 --no-cpu-baseline 2>/dev/null | grep '^{' | tail -1)
+  line=$(python3 bench.py --full --batch $b --graph 1 --steps $steps --warmup 5 --no-cpu-baseline 2>/dev/null | grep '^{' | tail -1)
   python3 - "$b" "$line" <<'PY' >> $out
 import json,sys
 b=int(sys.argv[1]); d=json.loads(sys.argv[2]); k=d['roofline']['kernel_ms_per_step']

@@ -2,7 +2,7 @@
 # Per-launch times of the non-default instantiations of the edge backward (NOT BASELINE configurations): cfg2 (H = 32)
 # and cfg3 (H = 64) + model flags, one library build.   usage: tools/variants_r3b.sh <outfile> [lib.so]
 out=$1; lib=$2
-run() { cfg=$1; flags=$2; line=$(env ${lib:+PVS_EGNN_LIB=$lib} python3 bench.py --config $cfg --steps 8 --warmup 3 --no-cpu-baseline --model-flags "$flags" 2>/dev/null | grep '^{' | tail -1);
+run() { cfg=$1; flags=$2; line=$(env ${lib:+PVS_EGNN_LIB=$lib} python3 bench.py --full --config $cfg --steps 8 --warmup 3 --no-cpu-baseline --model-flags "$flags" 2>/dev/null | grep '^{' | tail -1);
   python3 - "$cfg $flags" "$line" <<'PY' >> $out
 import json,sys
 d=json.loads(sys.argv[2]); r=d['roofline']
