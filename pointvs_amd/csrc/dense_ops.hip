@@ -1067,12 +1067,10 @@ int pvs_launch_linear(hipStream_t s, float* y, int ldy, const float* x, int ldx,
     if (aligned16 && K % 32 == 0 && K2 % 32 == 0 && C % 32 == 0 && C <= 64 && (KK == 32 || KK == 64 || KK == 128)) {
         const int kb = KK / 32, cb = C / 32;
         const size_t lds_m = (size_t)(C * (KK + 1) + C) * sizeof(float);
-#ifndef PVS_LIN_ROWS
-#define PVS_LIN_ROWS 256   // rows per block: 2 tiles per wave amortise the weight staging (cfg3 step -0.4 %)
-#endif
+        constexpr int kLinRows = 256;   // rows per block: 2 tiles per wave amortise the weight staging (cfg3 step -0.4 %)
         // (few rows - 4-graph batches of the wide layers, 8000 nodes: 32 blocks of 256 rows leave 7/8 of the chip idle
         // behind the weight staging - one 32-row tile per wave)
-        const int rows_m = N >= 32768 ? PVS_LIN_ROWS : 128;
+        const int rows_m = N >= 32768 ? kLinRows : 128;
         int blocks_m = (N + rows_m - 1) / rows_m;
         if (blocks_m > 1024) blocks_m = 1024;
 #define PVS_LIN(KBV, CBV)                                                                          \

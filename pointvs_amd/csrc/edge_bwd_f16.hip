@@ -15,57 +15,13 @@
 // the weight gradients accumulate in the MFMA accumulators at the images' scale (below: wgrad_tile_f16_acc); with edge
 // attention every tile takes its own scale from the wave-wide maximum and the products go through a temporary
 // accumulator (wgrad_tile_f16). Elementwise work (SiLU and SiLU', descales, the split's scale) is written on register
-// pairs (common.h pvs_f2). What bounds the kernel, measured phase by phase: DESIGN.md §5 / §8 item 1,
-// tools/tile_trace.py.
+// pairs (common.h pvs_f2). What bounds the kernel, measured phase by phase: DESIGN.md §5 / §8 item 1.
 //
 // Reference semantics: autograd of EGNNLayer.edge_model / coord_model / node_model's aggregation,
 // /root/reference/point_vs/models/geometric/egnn_satorras.py:123-206 (SURVEY.md §8a "Backward spec").
 #include "edge_mfma_common.h"
-#ifndef PVS_SA_IDX
-#define PVS_SA_IDX 0
-#endif
-#ifndef PVS_SA_GATHER
-#define PVS_SA_GATHER 0
-#endif
-#ifndef PVS_SA_ROW
-#define PVS_SA_ROW 0
-#endif
-#ifndef PVS_SA_STORE
-#define PVS_SA_STORE 0
-#endif
 
 namespace {
-
-// timing-only ablation (tools/variant_obj.sh -DPVS_ABL_F_SCATTER): the per-edge outputs at scattered positions of a
-// 256k-edge region, the access pattern of a by-column layout
-#ifdef PVS_ABL_F_SCATTER
-#define PVS_ABL_SCR(e) pvs_abl_scr((e), g.n_edges)
-__device__ __forceinline__ int pvs_abl_scr(int e, int E) {
-    const int r = (e & ~262143) + (int)(((unsigned)(e & 262143) * 40503u) & 262143u);
-    return r < E ? r : e;
-}
-#else
-#define PVS_ABL_SCR(e) (e)
-#endif
-
-// timing-only instrumentation (tools/variant_obj.sh -DPVS_TILE_TRACE, tools/tile_trace.py): workgroup 0 writes the shader
-// clock at phase boundaries of its first tiles; every point is a scheduling barrier, so the traced kernel is the
-// phase-by-phase form of the shipped one (the tool reports both tile times)
-#ifdef PVS_TILE_TRACE
-constexpr int kTraceTiles = 128, kTracePoints = 24;
-__device__ unsigned long long pvs_trace_buf[8 * kTraceTiles * kTracePoints];
-#define PVS_TP(k)                                                                                        \
-    do {                                                                                                 \
-        __builtin_amdgcn_sched_barrier(0);                                                               \
-        if ((k) == 1 || (k) == 21) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   /* 1: the gather has landed; 21: the previous tile's stores have */ \
-        const unsigned long long t_ = __builtin_readcyclecounter();                                      \
-        if (blockIdx.x == 0 && lane == 0 && tile_no < kTraceTiles)                                       \
-            pvs_trace_buf[(wv * kTraceTiles + tile_no) * kTracePoints + (k)] = t_;                       \
-        __builtin_amdgcn_sched_barrier(0);                                                               \
-    } while (0)
-#else
-#define PVS_TP(k) ((void)0)
-#endif
 
 constexpr int kH = 32;
 constexpr int kPartShorts = 32 * kH;              // one fp16 part image of a [32 edges][32 channels] tensor
@@ -96,13 +52,9 @@ __device__ __forceinline__ void write_part_f16(unsigned short* __restrict__ part
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
         const uint4 u = __builtin_bit_cast(uint4, p[s]);
-        // registers 8s..8s+3 hold channels 16s + 4hh + (0..3), registers 8s+4..8s+7 channels 16s + 8 + 4hh + (0..3)
-#if PVS_IMG_PAIRED      // (the two chunks are neighbours in the image: img_off<1>)
+        // registers 8s..8s+3 hold channels 16s + 4hh + (0..3), registers 8s+4..8s+7 channels 16s + 8 + 4hh + (0..3):
+        // neighbours in the image (img_off<1>)
         *reinterpret_cast<uint4*>(part + img_off<1>(j, 16 * s + 4 * hh)) = u;
-#else
-        *reinterpret_cast<uint2*>(part + img_off<1>(j, 16 * s + 4 * hh)) = make_uint2(u.x, u.y);
-        *reinterpret_cast<uint2*>(part + img_off<1>(j, 16 * s + 8 + 4 * hh)) = make_uint2(u.z, u.w);
-#endif
     }
 }
 
@@ -143,7 +95,7 @@ __device__ __forceinline__ void wgrad_tile_f16(const unsigned short* __restrict_
     }
 }
 
-// ---- weight gradients accumulated IN the matrix core's accumulator (PVS_LAZY_WSCALE, round 4) ----------------------
+// ---- weight gradients accumulated IN the matrix core's accumulator (lazy tile scales, round 4) ----------------------
 // wgrad_tile_f16 sums a tile into 32 temporary registers and folds them into the running sums with the tile's scales:
 // 64 v_fma + 32 live registers per tile in a kernel whose register file is full. Here the running sums ARE the MFMA
 // accumulators, kept at the scale of the operand images, and the images' scales move LAZILY: an operand keeps its
@@ -175,16 +127,6 @@ __device__ __forceinline__ void wgrad_tile_f16_acc(const unsigned short* __restr
     }
 }
 
-// timing-only ablations (tools/variant_obj.sh builds; never in the shipped library)
-#ifdef PVS_ABL_F_NOWGRAD
-#define F16_WGRAD(...) ((void)0)
-#define F16_WGRAD_ACC(...) ((void)0)
-#else
-#define F16_WGRAD(...) wgrad_tile_f16(__VA_ARGS__)
-#define F16_WGRAD_ACC(...) wgrad_tile_f16_acc(__VA_ARGS__)
-#endif
-
-
 struct F16Cfg {
     static constexpr int kThreadsPerBlock = 512;                          // two waves per SIMD
     static constexpr int kWavesPerBlock = kThreadsPerBlock / 64;
@@ -199,8 +141,8 @@ struct F16Cfg {
 };
 
 // ERK: edge residual kind - 0 none; 1 the plain sum m + m_prev (nothing of the residual has to survive the tile's
-// coordinate branch); 2 rezero (the gate's gradient needs the pre-residual message at the end); 3 gated (... and m_prev);
-// 4 rezero or gated by the run-time flags (every kind >= 2 before round 4). Compile-time kinds took rezero from 18 / 31
+// coordinate branch); 2 rezero (the gate's gradient needs the pre-residual message at the end); 3 gated (... and m_prev).
+// (Before round 4 one kind read rezero or gated from the run-time flags.) Compile-time kinds took rezero from 18 / 31
 // spilled VGPRs (without / with edge attention) to 2 / 9 and -11 % / -19 % per launch, gated + attention from 31 to 26 and
 // -4 %; gated without attention is faster the old way (profiles/r04_variants_gated_rezero.txt).
 template <int ERK, bool EATT>
@@ -270,17 +212,12 @@ k_edge_bwd_f16(PvsGraph g, PvsEdgeW w, uint32_t flags, int att_act, PvsEdgeBwdIO
 
     const float bac = EATT ? w.ba[0] : 0.f;
     float gate_raw = 0.f, gate = 1.f;
-    // (kind 4: the kind is read from the flags at run time, as all of them were before round 4 - the same source)
-    if (ERK == 4 && (flags & (PVS_REZERO | PVS_GATED_RESIDUAL))) {
-        gate_raw = w.edge_gate[0];
-        gate = (flags & PVS_GATED_RESIDUAL) ? fmaxf(gate_raw, 0.f) : gate_raw;
-    }
     if constexpr (ERK == 2 || ERK == 3) {
         gate_raw = w.edge_gate[0];
         gate = ERK == 3 ? fmaxf(gate_raw, 0.f) : gate_raw;
     }
-    const float res_a = ERK == 4 ? ((flags & (PVS_REZERO | PVS_GATED_RESIDUAL)) ? gate : 1.f) : (ERK >= 2 ? gate : 1.f);
-    const float res_b = ERK == 4 ? ((flags & PVS_GATED_RESIDUAL) ? 1.f - gate : 1.f) : (ERK == 3 ? 1.f - gate : 1.f);
+    const float res_a = ERK >= 2 ? gate : 1.f;
+    const float res_b = ERK == 3 ? 1.f - gate : 1.f;
 
     // ---- accumulators that live for the whole kernel ----
     f32x16 gW2, gWc1;                          // D layout: [c = ch(r,hh)][k = j]
@@ -296,10 +233,10 @@ k_edge_bwd_f16(PvsGraph g, PvsEdgeW w, uint32_t flags, int att_act, PvsEdgeBwdIO
     for (int r = 0; r < 16; ++r) { gB[r] = 0.f; g_wc2x[r] = 0.f; gW2[r] = 0.f; gWc1[r] = 0.f; }
     float g_ba = 0.f, g_gate = 0.f;
     // (LAZY) scale exponents of the four operand images and what the accumulators carry
-    constexpr bool LAZY = PVS_LAZY_WSCALE && !EATT;
+    constexpr bool LAZY = !EATT;
     // elementwise work on register pairs (common.h pvs_f2): everywhere but gated residual + attention, the instantiation
     // with the most live values per tile (30 spilled registers instead of 26 with it, +7 % per launch)
-    constexpr bool PAIR = PVS_PAIR_MATH && !(ERK == 3 && EATT);
+    constexpr bool PAIR = !(ERK == 3 && EATT);
     // (the four exponents share ONE scalar register, a byte each, 0 = not set yet: the kernel has no scalar register to
     // spare, and a spilled one costs a v_readlane / v_writelane pair per use)
     unsigned lazy_pack = 0u;
@@ -315,9 +252,6 @@ k_edge_bwd_f16(PvsGraph g, PvsEdgeW w, uint32_t flags, int att_act, PvsEdgeBwdIO
     AccUnits u_w2{-1}, u_b2{-1}, u_wc1{-1}, u_bc1{-1};
 
     const int total_waves = gridDim.x * NW;
-#ifdef PVS_TILE_TRACE
-    int tile_no = 0;
-#endif
     for (int chunk = pvs_xcd_block(blockIdx.x, gridDim.x) * NW + wv; chunk < n_chunks; chunk += total_waves) {
         // (wave-uniform values that come out of global loads: into scalar registers, the vector file is full)
         const int e_begin = __builtin_amdgcn_readfirstlane(chunk_begin(g, chunk, n_chunks, e_lo, e_hi));
@@ -329,7 +263,7 @@ k_edge_bwd_f16(PvsGraph g, PvsEdgeW w, uint32_t flags, int att_act, PvsEdgeBwdIO
         auto flush = [&](int row_id) {
             if (row_id >= 0) {
                 const float4 tot = sum_row_slots<1>(acc);
-                if (rsub == 0) *reinterpret_cast<float4*>(PVS_SA_STORE ? pvs_off(io.gPQ + (size_t)row_id * 2 * H, 16u * quad) : io.gPQ + (size_t)row_id * 2 * H + 4 * quad) = tot;
+                if (rsub == 0) *reinterpret_cast<float4*>(io.gPQ + (size_t)row_id * 2 * H + 4 * quad) = tot;
                 const float4 tx4 = sum_row_slots<1>(accx);
                 if (lane == 0) {
                     io.gx_row[3 * row_id] = tx4.x;
@@ -358,20 +292,18 @@ k_edge_bwd_f16(PvsGraph g, PvsEdgeW w, uint32_t flags, int att_act, PvsEdgeBwdIO
         // only what comes out of memory is carried from tile to tile (4 registers); e / ee / valid are recomputed
         struct Loaded { int i, jn, ty, prev_row; };
         auto load_idx = [&](int start, int end) {
-            const TileIdx t = PVS_SA_IDX ? load_tile_idx32(g, w.n_attr, start, e_begin, end, j) : load_tile_idx(g, w.n_attr, start, e_begin, end, j);
+            const TileIdx t = load_tile_idx(g, w.n_attr, start, e_begin, end, j);
             return Loaded{t.i, t.jn, t.ty, t.prev_row};
         };
         Loaded I = load_idx(e_begin, t_end);
         for (int e0 = e_begin; e0 < e_end;) {
             const int e_this_end = t_end;
-            PVS_TP(21);
             // the next tile: starts where this one ends; past a graph boundary the next boundary applies
             if (g.graph_eptr)    // (empty graphs repeat a boundary)
                 while (gk < g.n_graphs && gb <= e_this_end) { ++gk; gb = __builtin_amdgcn_readfirstlane(g.graph_eptr[gk]); }
             const int e_next = e_this_end < e_end ? e_this_end : e0;
             const int n_end = e_this_end < e_end ? tile_end(e_this_end, gb) : e_this_end;
             const Loaded In = load_idx(e_next, n_end);
-            PVS_TP(0);
             const int e = e0 + j, i = I.i, ty = I.ty;
             const bool valid = e < e_this_end;
             const int ee = min(max(valid ? e : e_this_end - 1, 0), g.n_edges - 1);   // (as load_tile_idx clamps)
@@ -387,15 +319,11 @@ k_edge_bwd_f16(PvsGraph g, PvsEdgeW w, uint32_t flags, int att_act, PvsEdgeBwdIO
                 TileGather<1> G;
                 TileIdx Ig;
                 Ig.i = I.i; Ig.jn = I.jn;
-#ifdef PVS_ABL_F_QHOT          // timing-only: the column-side rows come from a 256 KB window (what hiding their latency could give)
-                Ig.jn &= 1023;
-#endif
-                if (PVS_SA_GATHER) gather_tile32<1>(io.PQ, io.x, Ig, hh, G); else gather_tile<1>(io.PQ, io.x, Ig, hh, G);
+                gather_tile<1>(io.PQ, io.x, Ig, hh, G);
                 d0 = G.d0; d1 = G.d1; d2 = G.d2;
                 rho = d0 * d0 + d1 * d1 + d2 * d2;
                 float a1[1][16];
                 assemble_z1<1>(G, attrt, wrhot, ty, hh, rho, a1);
-                PVS_TP(1);
 #pragma unroll
                 for (int gq = 0; gq < 4; ++gq) {
                     float dd[4];
@@ -419,13 +347,9 @@ k_edge_bwd_f16(PvsGraph g, PvsEdgeW w, uint32_t flags, int att_act, PvsEdgeBwdIO
                     }
                     *reinterpret_cast<float4*>(d1b + (gq * 64 + lane) * 4) = make_float4(dd[0], dd[1], dd[2], dd[3]);
                 }
-                PVS_TP(18);
                 const float sa1 = LAZY ? lazy_scale(a1[0], kXa1, &inv_sa1) : pvs_tile_scale(a1[0], &inv_sa1);
-                PVS_TP(19);
                 split_f16x2<PAIR>(a1[0], sa1, pb);
-                PVS_TP(20);
                 write_image_f16(A1I, j, hh, pb);
-                PVS_TP(2);
                 f32x16 acc2;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc2[r] = 0.f;
@@ -443,7 +367,6 @@ k_edge_bwd_f16(PvsGraph g, PvsEdgeW w, uint32_t flags, int att_act, PvsEdgeBwdIO
 #pragma unroll
                     for (int r = 0; r < 16; ++r) z2[r] = fmaf(acc2[r], k2, bias[0][r]);
                 }
-                PVS_TP(3);
             }
             float dz2[16], m[1][16];          // SiLU'(z2) and the message
             float m_new[ERK >= 2 ? 16 : 1], mp[1][16];
@@ -475,12 +398,11 @@ k_edge_bwd_f16(PvsGraph g, PvsEdgeW w, uint32_t flags, int att_act, PvsEdgeBwdIO
             // ---- gradient wrt m: the coordinate branch's term comes from the matrix core first; the external,
             // aggregated-message and attention terms are added AFTER it (g_m is then not live across the
             // coordinate branch) ----
-            PVS_TP(4);
             float gm[16];
 #pragma unroll
             for (int r = 0; r < 16; ++r) gm[r] = 0.f;
             float gMi[1][16];
-            auto load_row_terms = [&]() { if (PVS_SA_ROW) load_x<1>(pvs_off(io.gM, (unsigned)i * (4u * H) + 16u * hh), 0, gMi); else load_x<1>(io.gM + (size_t)i * H, hh, gMi); };
+            auto load_row_terms = [&]() { load_x<1>(io.gM + (size_t)i * H, hh, gMi); };
             // Edge attention: everything that needs the message itself - the logit, m . g_M, the gate's gradient g_l
             // and its weight gradient g_wa += g_l m - is evaluated HERE, while m is live anyway; two scalars (the gate
             // value and g_l) cross the coordinate branch and m dies with its split, as in the plain kernel. The g_M
@@ -536,14 +458,11 @@ k_edge_bwd_f16(PvsGraph g, PvsEdgeW w, uint32_t flags, int att_act, PvsEdgeBwdIO
             float s_coord = 0.f, nrm = 1.f;
             float gT0 = 0.f, gT1 = 0.f, gT2 = 0.f;
             if (upd) {
-                const float* gT = PVS_SA_ROW ? pvs_off(io.gxagg, 12u * (unsigned)i) : io.gxagg + 3 * i;
+                const float* gT = io.gxagg + 3 * i;
                 gT0 = gT[0]; gT1 = gT[1]; gT2 = gT[2];
                 const float sm = LAZY ? lazy_scale(m[0], kXm, &inv_sm) : pvs_tile_scale(m[0], &inv_sm);
-                PVS_TP(16);
                 split_f16x2<PAIR>(m[0], sm, pb);
-                PVS_TP(17);
                 write_image_f16(MI, j, hh, pb);
-                PVS_TP(5);
                 f32x16 accc;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) accc[r] = 0.f;
@@ -587,12 +506,10 @@ k_edge_bwd_f16(PvsGraph g, PvsEdgeW w, uint32_t flags, int att_act, PvsEdgeBwdIO
                     g_zc[r] = g_s * wc2x[0][r] * dq[r];
                     g_wc2x[r] = fmaf(g_s, q[r], g_wc2x[r]);
                 }
-                PVS_TP(6);
                 float inv_sg;
                 const float sg_ = LAZY ? lazy_scale(g_zc, kXg, &inv_sg) : pvs_tile_scale(g_zc, &inv_sg);
                 split_f16x2<PAIR>(g_zc, sg_, pb);
                 write_image_f16(GI, j, hh, pb);
-                PVS_TP(7);
                 f32x16 accg;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) accg[r] = 0.f;
@@ -600,22 +517,20 @@ k_edge_bwd_f16(PvsGraph g, PvsEdgeW w, uint32_t flags, int att_act, PvsEdgeBwdIO
                 const float kg = inv_sg * inv_swc1;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) gm[r] = accg[r] * kg;
-                PVS_TP(8);
                 pvs_wave_lds_sync();                                  // the m and g_zc images are complete
                 // gWc1 += g_zc (x) m ; g_bc1 += sum_e g_zc
                 if constexpr (LAZY) {
                     const int what = pvs_rescale_acc(gWc1, gB, j == 0, u_wc1, u_bc1, lazy_e(kXg), lazy_e(kXm));
                     // (an operand whose product is not to be added is read from the all-zero image instead: the product
                     // itself is never inside a branch, so that its MFMAs can be scheduled among the vector work behind it)
-                    F16_WGRAD_ACC(GI, (what & 1) ? MI : ZI, (what & 2) ? ones0 : reinterpret_cast<unsigned*>(ZI), lane, gWc1, gB);
+                    wgrad_tile_f16_acc(GI, (what & 1) ? MI : ZI, (what & 2) ? ones0 : reinterpret_cast<unsigned*>(ZI), lane, gWc1, gB);
                 } else {
-                    F16_WGRAD(GI, MI, ones0, lane, inv_sg * inv_sm, inv_sg, gWc1, gB);
+                    wgrad_tile_f16(GI, MI, ones0, lane, inv_sg * inv_sm, inv_sg, gWc1, gB);
                 }
                 load_row_terms();
             } else {
                 load_row_terms();
             }
-            PVS_TP(9);
             add_row_terms();
             // ---- edge residual; g_z2 = g_m_new * SiLU'(z2) ----
             float g_z2[16];
@@ -634,30 +549,12 @@ k_edge_bwd_f16(PvsGraph g, PvsEdgeW w, uint32_t flags, int att_act, PvsEdgeBwdIO
                     if (gate_raw > 0.f) g_gate = fmaf(gmv, m_new[r] - mp[0][r], g_gate);
                     mp[0][r] = (1.f - gate) * gmv;
                 }
-                if constexpr (ERK == 4) {
-                    if (flags & PVS_REZERO) {
-                        gnew = gate * gmv;
-                        g_gate = fmaf(gmv, m_new[r], g_gate);
-                        mp[0][r] = gmv;
-                    } else if (flags & PVS_GATED_RESIDUAL) {
-                        gnew = gate * gmv;
-                        if (gate_raw > 0.f) g_gate = fmaf(gmv, m_new[r] - mp[0][r], g_gate);
-                        mp[0][r] = (1.f - gate) * gmv;
-                    } else {
-                        mp[0][r] = gmv;
-                    }
-                }
-#ifdef PVS_MASK_GZ2          // (A/B only: what the lanes past a tile's end hold - profiles/r06_gated_residual_backward_defect.txt)
-                g_z2[r] = valid ? gnew * dz2[r] : 0.f;
-#else
                 g_z2[r] = gnew * dz2[r];
-#endif
             }
             if constexpr (ERES) {
                 if (valid) store_x<1>(io.g_m_prev + (size_t)e * H, hh, mp);
             }
             // ---- g_a1 = W2^T g_z2 ; gW2 += g_z2 (x) a1 ; g_b2 += sum_e g_z2 ; g_z1 = g_a1 * SiLU'(z1) ----
-            PVS_TP(10);
             float inv_sg2;
             const float sg2 = LAZY ? lazy_scale(g_z2, kXg2, &inv_sg2) : pvs_tile_scale(g_z2, &inv_sg2);
             split_f16x2<PAIR>(g_z2, sg2, pb);
@@ -667,15 +564,13 @@ k_edge_bwd_f16(PvsGraph g, PvsEdgeW w, uint32_t flags, int att_act, PvsEdgeBwdIO
 #pragma unroll
             for (int r = 0; r < 16; ++r) ga1[r] = 0.f;
             chain_f16<true>(W2i, lane, pb, ga1);
-            PVS_TP(11);
             pvs_wave_lds_sync();                                      // the a1 and g_z2 images are complete
             if constexpr (LAZY) {
                 const int what = pvs_rescale_acc(gW2, gB, j == 1, u_w2, u_b2, lazy_e(kXg2), lazy_e(kXa1));
-                F16_WGRAD_ACC(GI, (what & 1) ? A1I : ZI, (what & 2) ? ones1 : reinterpret_cast<unsigned*>(ZI), lane, gW2, gB);
+                wgrad_tile_f16_acc(GI, (what & 1) ? A1I : ZI, (what & 2) ? ones1 : reinterpret_cast<unsigned*>(ZI), lane, gW2, gB);
             } else {
-                F16_WGRAD(GI, A1I, ones1, lane, inv_sg2 * inv_sa1, inv_sg2, gW2, gB);
+                wgrad_tile_f16(GI, A1I, ones1, lane, inv_sg2 * inv_sa1, inv_sg2, gW2, gB);
             }
-            PVS_TP(12);
             float g_z1[1][16];
             const float k1g = inv_sg2 * inv_sw2;
 #pragma unroll
@@ -691,21 +586,14 @@ k_edge_bwd_f16(PvsGraph g, PvsEdgeW w, uint32_t flags, int att_act, PvsEdgeBwdIO
             const float gd0 = fmaf(k1, gT0, 2.f * d0 * g_rho);
             const float gd1 = fmaf(k1, gT1, 2.f * d1 * g_rho);
             const float gd2 = fmaf(k1, gT2, 2.f * d2 * g_rho);
-            PVS_TP(13);
             pvs_wave_lds_sync();          // every read of the m / gradient images (their slots become the g_z1 tile) is done
             // per edge: grad wrt (x_row - x_col) and rho, 16 B, for the node gather kernel
             if (hh == 0) {
                 *reinterpret_cast<float4*>(tx + j * 4) = make_float4(gd0, gd1, gd2, 0.f);
                 rowbuf[j] = i;
                 if (valid) {
-#if defined(PVS_ABL_F_SCATTER) || !PVS_SA_STORE
-                    float* gd_at = io.gd + (size_t)PVS_ABL_SCR(e) * 4;
-#else
-                    float* gd_at = pvs_off(io.gd + (size_t)e0 * 4, 16u * j);       // (e0 is wave-uniform: a scalar base)
-#endif
-#ifndef PVS_ABL_F_NOGZ1      // timing-only: no per-edge outputs (what a column side fused into this kernel would not write)
+                    float* gd_at = io.gd + (size_t)e * 4;
                     pvs_store_nt(gd_at, make_float4(gd0, gd1, gd2, pvs_pack_rho_type(rho, ty)));
-#endif
                 }
             }
             // ---- g_z1 edge-major, then whole rows to HBM + the row-side sums from the same reads ----
@@ -714,30 +602,17 @@ k_edge_bwd_f16(PvsGraph g, PvsEdgeW w, uint32_t flags, int att_act, PvsEdgeBwdIO
                 *reinterpret_cast<float4*>(T1 + (TSWZ ? pvs_tile_quad_off<1>(j, 2 * gq + hh) : j * Cfg::kTS + 8 * gq + 4 * hh)) =
                     make_float4(g_z1[0][4 * gq], g_z1[0][4 * gq + 1], g_z1[0][4 * gq + 2], g_z1[0][4 * gq + 3]);
             pvs_wave_lds_sync();
-            PVS_TP(14);
-#ifndef PVS_ABL_F_NOREDUCE
             reduce_rows_tile<1, false, true, TSWZ>(T1, tx, rowbuf, bmask, lane, acc, accx, cur_row, flush,
                                 [&](int rl, int q, const float4& v) {
                                     if (e0 + rl < e_this_end) {  // streamed once: non-temporal
-#if defined(PVS_ABL_F_SCATTER) || !PVS_SA_STORE
-                                        float* at = io.gz1 + (size_t)PVS_ABL_SCR(e0 + rl) * H + 4 * q;
-#else
-                                        float* at = pvs_off(io.gz1 + (size_t)e0 * H, (unsigned)rl * (4u * H) + 16u * q);
-#endif
-#ifndef PVS_ABL_F_NOGZ1
+                                        float* at = io.gz1 + (size_t)(e0 + rl) * H + 4 * q;
                                         pvs_store_nt(at, v);
-#endif
                                     }
                                 });
-#endif
             I = In;
             e0 = e_this_end;
             t_end = n_end;
             pvs_wave_lds_sync();
-            PVS_TP(15);
-#ifdef PVS_TILE_TRACE
-            ++tile_no;
-#endif
         }
         flush(cur_row);
     }
@@ -808,16 +683,6 @@ k_edge_bwd_f16(PvsGraph g, PvsEdgeW w, uint32_t flags, int att_act, PvsEdgeBwdIO
 
 }  // namespace
 
-#ifdef PVS_PAIR_PROBE
-#include "probe_pair_bwd.h"
-#endif
-
-#ifdef PVS_TILE_TRACE
-extern "C" int pvs_debug_tile_trace(unsigned long long* dst, size_t count) {
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(pvs_trace_buf), count * sizeof(unsigned long long));
-}
-#endif
-
 // Same contract as pvs_launch_edge_bwd_mfma (edge_mfma.hip). H = 32 only.
 int pvs_launch_edge_bwd_f16(hipStream_t s, int H, const PvsGraph& g, const PvsEdgeW& w, uint32_t flags, int att_act,
                             const PvsEdgeBwdIO& io, int e_lo, int e_hi, int* n_slabs) {
@@ -848,18 +713,6 @@ int pvs_launch_edge_bwd_f16(hipStream_t s, int H, const PvsGraph& g, const PvsEd
     if (lds < (size_t)L.total * 4) lds = (size_t)L.total * 4;
     const bool eres = (flags & PVS_EDGE_RESIDUAL) && io.m_prev != nullptr;
     const bool eatt = flags & PVS_EDGE_ATTENTION;
-#ifdef PVS_PAIR_PROBE       // timing-only: the channel-split wave-pair kernel in place of <0, false> (probe_pair_bwd.h)
-    if (!eres && !eatt) {
-        const int pblocks = 256 * PVS_PAIR_PROBE_OCC, ppairs = 2 * pblocks;
-        long long per = ((long long)(e_hi - e_lo) + (long long)ppairs * 2048 - 1) / ((long long)ppairs * 2048);
-        if (per < 1) per = 1;
-        *n_slabs = pblocks;
-        if (set_lds(pairprobe::k_edge_bwd_pair_probe, (size_t)pairprobe::kLds)) return -2;
-        pairprobe::k_edge_bwd_pair_probe<<<pblocks, 256, pairprobe::kLds, s>>>(g, w, flags, io, (int)(ppairs * per), e_lo, e_hi);
-        PVS_CHECK_LAUNCH();
-        return 0;
-    }
-#endif
 #define PVS_BWD_F16_LAUNCH(ER, EA)                                                                          \
     do {                                                                                                   \
         if (set_lds(k_edge_bwd_f16<ER, EA>, lds)) return -2;                                               \
@@ -880,11 +733,7 @@ int pvs_launch_edge_bwd_f16(hipStream_t s, int H, const PvsGraph& g, const PvsEd
     // instantiation was not found (no asm-related hazard in its ISA, spills outside the tile loop); the kind-4 code path is
     // no longer instantiated. tools/backward_instantiations_probe.py and the GPU test of the same name run all 24
     // instantiations of the H = 32 / 64 backward twice on a multi-tile graph.
-#ifdef PVS_GATED_KIND4          // (A/B only: the defective run-time kind, for whoever looks for the cause; never shipped)
-    else if (eres && gated) PVS_BWD_F16_LAUNCH(4, false);
-#else
     else if (eres && gated) PVS_BWD_F16_LAUNCH(3, false);
-#endif
     else if (eres && eatt) PVS_BWD_F16_LAUNCH(1, true);
     else if (eres) PVS_BWD_F16_LAUNCH(1, false);
     else if (eatt) PVS_BWD_F16_LAUNCH(0, true);

@@ -27,9 +27,6 @@
 // issues one instruction per ~5 cycles whatever it is, so two results per instruction is two issue slots for one
 // (cfg3: -1...1.7 % per launch). NOT in the block woven beside the gW2 product (wgrad16_beside): paired there, the
 // pinned units no longer fill the MFMAs' shadows evenly (23 more s_nop, +0.5 % instead of -1 %).
-#ifndef PVS_PAIR_H64
-#define PVS_PAIR_H64 1
-#endif
 
 namespace {
 
@@ -198,11 +195,7 @@ __device__ __forceinline__ void chain16(const unsigned short* __restrict__ img, 
 // split first and then issues the 48 MFMAs back to back with the vector ALU idle). Product order: every group of
 // four MFMAs needs only parts that are ready - (lo,0)hi (lo,1)hi (mid,0)hi (mid,0)mid (mid,1)hi (hi,0)hi (mid,1)mid
 // (hi,0)mid (hi,0)lo (hi,1)hi (hi,1)mid (hi,1)lo; fragment loads stay two groups ahead as in chain16.
-// GLOBAL (timing-only probe, -DPVS_ABL_H64_WC1_GLOBAL, profiles/r06_ab_h64_lds_residency.txt): the weight's operand
-// fragments as PRE-ARRANGED 16-byte words in global memory - fragment (part, s, b) of lane l at word
-// ((part * 2 + s) * 4 + b) * 64 + l, one fully coalesced 1 KB load per fragment, what csrc/edge_bwd_wide.hip does for
-// coord_mlp.0 - instead of reads of the LDS image: what freeing that weight's 24.5 KB of LDS would cost.
-template <bool TRANSPOSE, bool GLOBAL = false>
+template <bool TRANSPOSE>
 __device__ __forceinline__ void chain16s(const unsigned short* __restrict__ img, int lane, const float (&x)[16],
                                          Bf16Parts& pb, f32x4 (&acc)[4]) {
     const unsigned short* lo = img + 2 * kH * kH;
@@ -213,15 +206,7 @@ __device__ __forceinline__ void chain16s(const unsigned short* __restrict__ img,
     float r[16], t[16];
     auto ld = [&](const unsigned short* part, int s, bf16x8 (&f)[4]) {
 #pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            if constexpr (GLOBAL) {
-                const int pi = (int)((part - img) / (kH * kH));
-                // (a wave-uniform base + the lane's 32-bit byte offset: one address register for all 24 fragments)
-                f[b] = __builtin_bit_cast(bf16x8, *pvs_off(reinterpret_cast<const uint4*>(img) + (((pi * 2 + (TRANSPOSE ? 1 : 0)) * 2 + s) * 4 + b) * 64, 16u * (unsigned)lane));
-            } else {
-                f[b] = frag16<TRANSPOSE>(part, lane, b, s);
-            }
-        }
+        for (int b = 0; b < 4; ++b) f[b] = frag16<TRANSPOSE>(part, lane, b, s);
     };
     auto res = [](float v) { return v - __uint_as_float(__float_as_uint(v) & 0xffff0000u); };
     auto part = [](const unsigned (&p)[8], int s) {
@@ -438,12 +423,8 @@ __device__ __forceinline__ void reduce_rows16(const float* __restrict__ T, const
         seg[k] = __popc(bmask & ((2u << rl) - 1u));
     }
     auto add4 = [](float4& a, const float4& b) {
-#if PVS_PAIR_H64
         const pvs_f2 lo = pvs_f2{a.x, a.y} + pvs_f2{b.x, b.y}, hi = pvs_f2{a.z, a.w} + pvs_f2{b.z, b.w};
         a.x = lo.x; a.y = lo.y; a.z = hi.x; a.w = hi.y;
-#else
-        a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
-#endif
     };
     if (bmask == 0u) {
 #pragma unroll
@@ -468,17 +449,6 @@ __device__ __forceinline__ void reduce_rows16(const float* __restrict__ T, const
     }
 }
 
-// timing-only ablations (tools/ab.py variants; never built into the shipped library)
-#ifdef PVS_ABL_H_NOWGRAD
-#define H64_WGRAD(...) ((void)0)
-#else
-#define H64_WGRAD(...) wgrad16(__VA_ARGS__)
-#endif
-#ifdef PVS_ABL_H_NOCHAIN
-#define H64_CHAIN(T, img, lane, v, acc) do { for (int b_ = 0; b_ < 4; ++b_) acc[b_][0] += __builtin_bit_cast(uint4, v.hi[0]).x * 1e-30f; } while (0)
-#define H64_CHAINS(T, img, lane, x, pb, acc) do { split_bf16x3(x, pb); H64_CHAIN(T, img, lane, pb, acc); } while (0)
-#else
-#define H64_CHAIN(T, img, lane, v, acc) chain16<T>(img, lane, v, acc)
 // (the pinned form costs registers: with an edge residual - m_prev and, for the gates, the pre-residual message
 // live through the tile - it spills 8-22 VGPRs where split + chain16 spills 0-10; those instantiations keep the
 // two-step form)
@@ -487,16 +457,6 @@ __device__ __forceinline__ void reduce_rows16(const float* __restrict__ T, const
         if constexpr (ERK == 0) chain16s<T>(img, lane, x, pb, acc);                 \
         else { split_bf16x3(x, pb); chain16<T>(img, lane, pb, acc); }               \
     } while (0)
-#endif
-#ifdef PVS_ABL_H64_WC1_GLOBAL      // timing only (wrong numbers: the words read are node rows, not weight fragments)
-#define H64_CHAINS_WC1(T, img, lane, x, pb, acc)                                                                        \
-    do {                                                                                                                \
-        if constexpr (ERK == 0) chain16s<T, true>(reinterpret_cast<const unsigned short*>(io.PQ), lane, x, pb, acc);    \
-        else H64_CHAINS(T, img, lane, x, pb, acc);                                                                      \
-    } while (0)
-#else
-#define H64_CHAINS_WC1(T, img, lane, x, pb, acc) H64_CHAINS(T, img, lane, x, pb, acc)
-#endif
 
 // ERK: edge residual kind - 0 none; 1 the plain sum m + m_prev (nothing of the residual has to survive the tile's
 // coordinate branch); 2 rezero / gated (the gate's gradient needs the pre-residual message and m_prev at the end).
@@ -610,14 +570,12 @@ k_edge_bwd_h64(PvsGraph g, PvsEdgeW w, uint32_t flags, int att_act, PvsEdgeBwdIO
         auto store_phase = [&]() {
             if (gr == 0 && pend_e0 + n < e_end)       // per edge: grad wrt (x_row - x_col), rho and class: 16 B
                 pvs_store_nt(io.gd + (size_t)(pend_e0 + n) * 4, *reinterpret_cast<const float4*>(tx + n * 4));
-#ifndef PVS_ABL_H_NOSEG
             const int pe0 = pend_e0;
             reduce_rows16(T1, tx, rowbuf, pend_bmask, lane, acc, accx, cur_row, flush,
                           [&](int rl, int q, const float4& v) {
                               if (pe0 + rl < e_end)   // streamed once: non-temporal
                                   pvs_store_nt(io.gz1 + (size_t)(pe0 + rl) * H + 4 * q, v);
                           });
-#endif
             pvs_wave_lds_sync();
         };
         for (int e0 = e_begin; e0 < e_end; e0 += kT16) {
@@ -644,7 +602,6 @@ k_edge_bwd_h64(PvsGraph g, PvsEdgeW w, uint32_t flags, int att_act, PvsEdgeBwdIO
                 float a1[16], aa[16], rr[16];
                 load_y(attrt + ty * H, gr, aa);
                 load_y(wrhot, gr, rr);
-#ifndef PVS_ABL_H_NOWGRAD
                 {
                     float z[16], ex[16];
                     wgrad16_beside(GI, A1I, lane, gW2,
@@ -666,16 +623,6 @@ k_edge_bwd_h64(PvsGraph g, PvsEdgeW w, uint32_t flags, int att_act, PvsEdgeBwdIO
                                        asm volatile("" : "+v"(d1r[r]), "+v"(a1[r]));
                                    });
                 }
-#else
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const float z = G.P[r] + G.Q[r] + fmaf(rr[r], rho, aa[r]);
-                    const float sg = pvs_sigmoid(z);
-                    const float av = z * sg;
-                    d1r[r] = fmaf(av, 1.0f - sg, sg);
-                    a1[r] = av;
-                }
-#endif
                 float bias[16];
                 load_y(b2t, gr, bias);
 #pragma unroll
@@ -688,19 +635,10 @@ k_edge_bwd_h64(PvsGraph g, PvsEdgeW w, uint32_t flags, int att_act, PvsEdgeBwdIO
             float m_new[ERK == 2 ? 16 : 1];
 #pragma unroll
             for (int r = 0; r < 16; r += 2) {
-#if PVS_PAIR_H64
                 pvs_f2 mv, dv;
                 pvs_silu_grad2(pvs_f2{acc2[r >> 2][r & 3], acc2[r >> 2][(r & 3) + 1]}, mv, dv);
                 m[r] = mv.x; m[r + 1] = mv.y;
                 dz2[r] = dv.x; dz2[r + 1] = dv.y;
-#else
-                for (int t = r; t < r + 2; ++t) {
-                    const float z2 = acc2[t >> 2][t & 3];
-                    const float sg = pvs_sigmoid(z2);
-                    m[t] = z2 * sg;
-                    dz2[t] = fmaf(m[t], 1.0f - sg, sg);
-                }
-#endif
                 if constexpr (ERK == 2) { m_new[r] = m[r]; m_new[r + 1] = m[r + 1]; }
             }
             if constexpr (ERES) {
@@ -727,13 +665,12 @@ k_edge_bwd_h64(PvsGraph g, PvsEdgeW w, uint32_t flags, int att_act, PvsEdgeBwdIO
 #pragma unroll
                     for (int r = 0; r < 16; ++r) accc[r >> 2][r & 3] = bias2[r];
                 }
-                H64_CHAINS_WC1(false, Wc1i, lane, m, pb, accc);        // zc = Wc1 m + bc1
+                H64_CHAINS(false, Wc1i, lane, m, pb, accc);            // zc = Wc1 m + bc1
                 write_image16(MI, n, gr, pb);
                 float wc2y[16];
                 load_y(wc2t, gr, wc2y);
                 float q[16], dq[16];
                 float s = 0.f;
-#if PVS_PAIR_H64
                 pvs_f2 s2{0.f, 0.f};
 #pragma unroll
                 for (int r = 0; r < 16; r += 2) {
@@ -744,16 +681,6 @@ k_edge_bwd_h64(PvsGraph g, PvsEdgeW w, uint32_t flags, int att_act, PvsEdgeBwdIO
                     s2 = pvs_fma2(pvs_f2{wc2y[r], wc2y[r + 1]}, qv, s2);
                 }
                 s = s2.x + s2.y;
-#else
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const float zc = accc[r >> 2][r & 3];
-                    const float sg = pvs_sigmoid(zc);
-                    q[r] = zc * sg;
-                    dq[r] = fmaf(q[r], 1.0f - sg, sg);
-                    s = fmaf(wc2y[r], q[r], s);
-                }
-#endif
                 s = sum_groups(s);
                 float dact = 1.f;
                 if (flags & PVS_TANH) { s = pvs_tanh(s); dact = 1.f - s * s; }
@@ -763,26 +690,18 @@ k_edge_bwd_h64(PvsGraph g, PvsEdgeW w, uint32_t flags, int att_act, PvsEdgeBwdIO
                 float g_zc[16];
 #pragma unroll
                 for (int r = 0; r < 16; r += 2) {
-#if PVS_PAIR_H64
                     const pvs_f2 gz = pvs_f2{wc2y[r], wc2y[r + 1]} * g_s * pvs_f2{dq[r], dq[r + 1]};
                     const pvs_f2 gw = pvs_fma2(pvs_f2{q[r], q[r + 1]}, pvs_f2{g_s, g_s}, pvs_f2{g_wc2y[r], g_wc2y[r + 1]});
                     const pvs_f2 gb = pvs_f2{g_bc1y[r], g_bc1y[r + 1]} + gz;
                     g_zc[r] = gz.x; g_zc[r + 1] = gz.y;
                     g_wc2y[r] = gw.x; g_wc2y[r + 1] = gw.y;
                     g_bc1y[r] = gb.x; g_bc1y[r + 1] = gb.y;
-#else
-                    for (int t = r; t < r + 2; ++t) {
-                        g_zc[t] = g_s * wc2y[t] * dq[t];
-                        g_wc2y[t] = fmaf(g_s, q[t], g_wc2y[t]);
-                        g_bc1y[t] += g_zc[t];
-                    }
-#endif
                 }
                 load_y(io.gM + (size_t)i * H, gr, gMi);               // (in flight behind the two products below)
-                H64_CHAINS_WC1(true, Wc1i, lane, g_zc, pb, gm);        // g_m += Wc1^T g_zc
+                H64_CHAINS(true, Wc1i, lane, g_zc, pb, gm);            // g_m += Wc1^T g_zc
                 write_image16(GI, n, gr, pb);
                 pvs_wave_lds_sync();                                  // the m and g_zc images are complete
-                H64_WGRAD(GI, MI, lane, gWc1);                          // gWc1 += g_zc (x) m
+                wgrad16(GI, MI, lane, gWc1);                            // gWc1 += g_zc (x) m
             } else {
                 load_y(io.gM + (size_t)i * H, gr, gMi);
             }
@@ -797,7 +716,6 @@ k_edge_bwd_h64(PvsGraph g, PvsEdgeW w, uint32_t flags, int att_act, PvsEdgeBwdIO
                     float way[16];
                     load_y(wat, gr, way);
                     float logit = 0.f, dot = 0.f;
-#if PVS_PAIR_H64
                     pvs_f2 l2{0.f, 0.f}, d2p{0.f, 0.f};
 #pragma unroll
                     for (int r = 0; r < 16; r += 2) {
@@ -807,13 +725,6 @@ k_edge_bwd_h64(PvsGraph g, PvsEdgeW w, uint32_t flags, int att_act, PvsEdgeBwdIO
                     }
                     logit = l2.x + l2.y;
                     dot = d2p.x + d2p.y;
-#else
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        logit = fmaf(way[r], m[r], logit);
-                        dot = fmaf(m[r], gMi[r], dot);
-                    }
-#endif
                     logit = sum_groups(logit) + bac;
                     dot = sum_groups(dot);
                     const float g_l = (flags & PVS_SOFTMAX_ATT) ? aval * (dot - softd) * vm     // softD = M_i . g_M_i
@@ -821,28 +732,16 @@ k_edge_bwd_h64(PvsGraph g, PvsEdgeW w, uint32_t flags, int att_act, PvsEdgeBwdIO
                     if (gr == 0) g_ba += g_l;
 #pragma unroll
                     for (int r = 0; r < 16; r += 2) {
-#if PVS_PAIR_H64
                         const pvs_f2 t = pvs_fma2(pvs_f2{gMi[r], gMi[r + 1]}, pvs_f2{aval * vm, aval * vm}, pvs_f2{way[r], way[r + 1]} * g_l);
                         const pvs_f2 gw = pvs_fma2(pvs_f2{m[r], m[r + 1]}, pvs_f2{g_l, g_l}, pvs_f2{g_way[r], g_way[r + 1]});
                         gm[r >> 2][r & 3] += t.x; gm[r >> 2][(r & 3) + 1] += t.y;
                         g_way[r] = gw.x; g_way[r + 1] = gw.y;
-#else
-                        for (int t = r; t < r + 2; ++t) {
-                            gm[t >> 2][t & 3] += (aval * vm) * gMi[t] + g_l * way[t];
-                            g_way[t] = fmaf(g_l, m[t], g_way[t]);
-                        }
-#endif
                     }
                 } else {
 #pragma unroll
                     for (int r = 0; r < 16; r += 2) {
-#if PVS_PAIR_H64
                         const pvs_f2 t = pvs_fma2(pvs_f2{gMi[r], gMi[r + 1]}, pvs_f2{vm, vm}, pvs_f2{gm[r >> 2][r & 3], gm[r >> 2][(r & 3) + 1]});
                         gm[r >> 2][r & 3] = t.x; gm[r >> 2][(r & 3) + 1] = t.y;
-#else
-                        gm[r >> 2][r & 3] = fmaf(vm, gMi[r], gm[r >> 2][r & 3]);
-                        gm[(r + 1) >> 2][(r + 1) & 3] = fmaf(vm, gMi[r + 1], gm[(r + 1) >> 2][(r + 1) & 3]);
-#endif
                     }
                 }
             }
@@ -873,9 +772,9 @@ k_edge_bwd_h64(PvsGraph g, PvsEdgeW w, uint32_t flags, int att_act, PvsEdgeBwdIO
                     }
                 }
                 g_z2[r] = gnew * dz2[r];
-                if (!(PVS_PAIR_H64 && ERK == 0)) g_b2y[r] += g_z2[r];
+                if (ERK != 0) g_b2y[r] += g_z2[r];
             }
-            if constexpr (PVS_PAIR_H64 && ERK == 0) {      // (g_z2 = g_m * SiLU'(z2) again, two at a time: the loop above folds away)
+            if constexpr (ERK == 0) {      // (g_z2 = g_m * SiLU'(z2) again, two at a time: the loop above folds away)
 #pragma unroll
                 for (int r = 0; r < 16; r += 2) {
                     const pvs_f2 z = pvs_f2{gm[r >> 2][r & 3], gm[r >> 2][(r & 3) + 1]} * pvs_f2{dz2[r], dz2[r + 1]};
@@ -900,28 +799,18 @@ k_edge_bwd_h64(PvsGraph g, PvsEdgeW w, uint32_t flags, int att_act, PvsEdgeBwdIO
             float g_z1[16];
 #pragma unroll
             for (int r = 0; r < 16; r += 2) {
-#if PVS_PAIR_H64
                 const pvs_f2 z = pvs_f2{ga1[r >> 2][r & 3], ga1[r >> 2][(r & 3) + 1]} * pvs_f2{d1r[r], d1r[r + 1]};
                 g_z1[r] = z.x; g_z1[r + 1] = z.y;
-#else
-                g_z1[r] = ga1[r >> 2][r & 3] * d1r[r];
-                g_z1[r + 1] = ga1[(r + 1) >> 2][(r + 1) & 3] * d1r[r + 1];
-#endif
             }
             float g_rho;
             {
                 float rr[16];
                 load_y(wrhot, gr, rr);
                 float s = 0.f;
-#if PVS_PAIR_H64
                 pvs_f2 s2{0.f, 0.f};
 #pragma unroll
                 for (int r = 0; r < 16; r += 2) s2 = pvs_fma2(pvs_f2{rr[r], rr[r + 1]}, pvs_f2{g_z1[r], g_z1[r + 1]}, s2);
                 s = s2.x + s2.y;
-#else
-#pragma unroll
-                for (int r = 0; r < 16; ++r) s = fmaf(rr[r], g_z1[r], s);
-#endif
                 g_rho = sum_groups(s);
             }
             const float k1 = s_coord * nrm * vm;
@@ -946,7 +835,7 @@ k_edge_bwd_h64(PvsGraph g, PvsEdgeW w, uint32_t flags, int att_act, PvsEdgeBwdIO
         }
         if (pend_e0 >= 0) {
             pvs_wave_lds_sync();
-            H64_WGRAD(GI, A1I, lane, gW2);                              // the last tile's product
+            wgrad16(GI, A1I, lane, gW2);                                // the last tile's product
             store_phase();
         }
         flush(cur_row);

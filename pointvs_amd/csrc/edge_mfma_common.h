@@ -15,9 +15,9 @@ constexpr int kThreads = 256;
 constexpr int kWaves = 4;
 constexpr int kTile = 32;
 
-// Timing-only ablation switches (PVS_ABLATE env, tools/ablate.py): results are wrong when set.
 // internal: the forward writes the raw coordinate sums (no x, no 1/deg) into x_out (edge_sums)
 constexpr uint32_t kFwdRawXsum = 1u << 23;
+// Timing-only ablation switches (PVS_ABLATE env, layer_api.hip): results are wrong when set.
 constexpr uint32_t kAblNoMfma = 1u << 24, kAblNoSilu = 1u << 25, kAblNoReduce = 1u << 26,
                    kAblNoGather = 1u << 27;
 
@@ -128,15 +128,9 @@ __device__ __forceinline__ float pvs_xor_sum(float v) {
 }
 
 // Pair arithmetic (common.h pvs_f2): the elementwise work of the edge kernels on two adjacent registers per instruction.
-#ifndef PVS_PAIR_MATH
-#define PVS_PAIR_MATH 1
-#endif
 // H = 32 only. At 128 channels register pairs cost the softmax forward its second wave per SIMD; the 64-channel forward
-// (768 threads, 168 registers) is 1 % slower with them (profiles/r05_ab_pair_math.txt; -DPVS_PAIR_MAX_HB=2 builds it).
-#ifndef PVS_PAIR_MAX_HB
-#define PVS_PAIR_MAX_HB 1
-#endif
-template <int HB> constexpr bool pvs_pair_math = PVS_PAIR_MATH && HB <= PVS_PAIR_MAX_HB;
+// (768 threads, 168 registers) is 1 % slower with them (profiles/r05_ab_pair_math.txt).
+template <int HB> constexpr bool pvs_pair_math = HB <= 1;
 
 template <int HB>
 __device__ __forceinline__ float dot_tab(const float* __restrict__ tab, int hh, const float (&v)[HB][16]) {
@@ -171,9 +165,6 @@ __device__ __forceinline__ int chunk_begin(const PvsGraph& g, int k, int n_chunk
     if (k <= 0) return e_lo;
     if (k >= n_chunks) return e_hi;
     const long long t = e_lo + (long long)k * (e_hi - e_lo) / n_chunks;
-#ifdef PVS_ABL_UNALIGNED_CHUNKS       // timing only (rows that straddle a boundary are summed wrongly): what perfectly equal chunks would give
-    return (int)t;
-#endif
     return max(e_lo, g.rowptr[g.row[t]]);
 }
 
@@ -207,12 +198,8 @@ __device__ __forceinline__ TileIdx load_tile_idx(const PvsGraph& g, int n_attr, 
 // formed in scalar registers) plus an UNSIGNED 32-bit byte offset selects the `global_load v, v_off, s[base:base+1]`
 // form instead: one register and at most one instruction per address. Callers bound the offsets: node tables below
 // 2^32 bytes (the launchers check N), per-edge arrays addressed relative to the tile's first edge.
-#ifndef PVS_SADDR
-#define PVS_SADDR 1
-#endif
 template <class T>
 __device__ __forceinline__ T* pvs_off(T* base, unsigned bytes) {
-    if (!PVS_SADDR) return reinterpret_cast<T*>(reinterpret_cast<char*>(const_cast<typename std::remove_const<T>::type*>(base)) + (long long)(int)bytes);
     return reinterpret_cast<T*>(reinterpret_cast<char*>(const_cast<typename std::remove_const<T>::type*>(base)) + bytes);
 }
 
@@ -447,14 +434,10 @@ typedef short pvs_v4s __attribute__((ext_vector_type(4)));
 // and their swizzle. swz(r) = bits (r2, r3, r1 ^ r4) of the row is a bijection of (r1, r2, r3) for every r4 (the writes:
 // 16 rows of one group) AND of (r2, r3, r4) for every r1 (the row reads: 32 rows, 64 banks); the transposed reads take
 // four consecutive rows whole and do not care. All three conflict-free.
-#ifndef PVS_IMG_PAIRED
-#define PVS_IMG_PAIRED 1
-#endif
 template <int HB>
 __device__ __forceinline__ int img_off(int r, int c) {
     constexpr int H = 32 * HB, NCH = H / 4, RPC = 128 / H;
     if constexpr (HB == 1) {
-#if PVS_IMG_PAIRED
         // The two 8-byte chunks one lane's fragment is made of (channels 16 s + 4 hh + 0..3 and 16 s + 8 + 4 hh + 0..3: chunk
         // numbers q and q + 2) sit SIDE BY SIDE: a row fragment is one ds_read_b128 and a part write one ds_write_b128
         // instead of two 8-byte accesses each (and hipcc no longer pairs a row read with the other part image's, which cost
@@ -464,9 +447,6 @@ __device__ __forceinline__ int img_off(int r, int c) {
         const int q = c >> 2, pair = ((q >> 2) << 1) | (q & 1), t = (q >> 1) & 1;
         const int f = ((r >> 2) & 1) | ((((r >> 1) ^ (r >> 3)) & 1) << 1);
         return r * H + 8 * (pair ^ f) + 4 * t + (c & 3);
-#else
-        return r * H + 4 * ((c >> 2) ^ (((r >> 2) & 3) | ((((r >> 1) ^ (r >> 4)) & 1) << 2))) + (c & 3);
-#endif
     }
     return r * H + 4 * ((c >> 2) ^ ((r / RPC) & (NCH - 1))) + (c & 3);
 }
@@ -480,7 +460,7 @@ __device__ __forceinline__ uint4 img_fragment_bits(const unsigned short* __restr
     uint2 a, b;
     if constexpr (!TRANSPOSE) {
         const int r = 32 * bo + (lane & 31), c0 = 32 * bi + 16 * s + 4 * hh;
-        if constexpr (HB == 1 && PVS_IMG_PAIRED) return *reinterpret_cast<const uint4*>(part + img_off<HB>(r, c0));
+        if constexpr (HB == 1) return *reinterpret_cast<const uint4*>(part + img_off<HB>(r, c0));
         a = *reinterpret_cast<const uint2*>(part + img_off<HB>(r, c0));
         b = *reinterpret_cast<const uint2*>(part + img_off<HB>(r, c0 + 8));
     } else {
@@ -613,13 +593,7 @@ __device__ __forceinline__ void split_f16x2(const float (&v)[16], float s, F16Pa
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const float x0 = v[8 * ks + 2 * q], x1 = v[8 * ks + 2 * q + 1];
-#ifdef PVS_SPLIT_MIXLO      // (A/B only: round 3's first form. Its parts are written by asm statements, i.e. NOT guarded against the
-            // VALU-write -> MFMA-read hazard, see pvs_f16_split2: never ship a build with this defined)
-            h[q] = pvs_f16_hi2(x0, x1, s);
-            l[q] = pvs_f16_lo2(x0, x1, s, h[q]);
-#else
             pvs_f16_split2<PAIR>(x0, x1, s, h[q], l[q]);
-#endif
         }
         out.hi[ks] = __builtin_bit_cast(f16x8, ph);
         out.lo[ks] = __builtin_bit_cast(f16x8, pl);
@@ -696,9 +670,6 @@ __device__ __forceinline__ void mfma_chain_f16x2_blocks(const unsigned* __restri
 // weight-gradient accumulators live in the accumulator half of the register file, and the rescaling branch - vector
 // instructions that touch them inside the tile loop - makes the allocator move them out of it: the wide backward went
 // from 25-163 to 145-237 spilled VGPRs with this scheme (the same wall as profiles/r03_h64_backward_f16x2_rejected.txt) ----
-#ifndef PVS_LAZY_WSCALE
-#define PVS_LAZY_WSCALE 1
-#endif
 constexpr int kLazyWindow = 2;
 struct LazyExp { int e; };                 // exponent of the scale's ceiling (scale = 2^(140 - e)); < 0: not set yet
 
@@ -719,10 +690,7 @@ __device__ __forceinline__ float pvs_lazy_tile_scale(const float (&v)[16], LazyE
     const unsigned m = __float_as_uint(pvs_absmax16(v));
     const unsigned hi = (unsigned)(st.e + 1) << 23;
     const unsigned lo = st.e - kLazyWindow <= 16 ? 0u : (unsigned)(st.e - kLazyWindow) << 23;
-#ifndef PVS_WINDOW_CHECK
-#define PVS_WINDOW_CHECK 1
-#endif
-    if (!PVS_WINDOW_CHECK || st.e < 0 || __ballot(m >= hi) != 0ull || __ballot(m >= lo) == 0ull)
+    if (st.e < 0 || __ballot(m >= hi) != 0ull || __ballot(m >= lo) == 0ull)
         return pvs_lazy_scale_from_max(pvs_wave_max_u32(m), st, inv);
     *inv = __uint_as_float((unsigned)(st.e - 13) << 23);
     return __uint_as_float((unsigned)(267 - st.e) << 23);
@@ -851,8 +819,8 @@ inline int pvs_edges_per_wave() {
 // Edges per chunk above which a wave's share is cut into several chunks (PVS_CHUNK_EDGES overrides it: A/B only).
 // Chunk ends are row-aligned, so a wave's share is uneven by up to a row per chunk end (157 edges at cfg2) and the launch
 // waits for the largest share: FEWER, larger chunks per wave balance better (round 6, H = 32 backward at cfg2: two chunks
-// of 2.5 k edges per wave -> one of 5 k: -2.5 % per launch; perfectly equal shares - timing-only, -DPVS_ABL_UNALIGNED_CHUNKS
-// - would give -3.3 %: profiles/r06_ab_chunk_balance.txt).
+// of 2.5 k edges per wave -> one of 5 k: -2.5 % per launch; perfectly equal shares - a timing-only build - would give
+// -3.3 %: profiles/r06_ab_chunk_balance.txt).
 inline long long pvs_chunk_edges(long long dflt = 4096) {
     static const long long v = [] { const char* e = getenv("PVS_CHUNK_EDGES"); return e ? atoll(e) : 0ll; }();
     return v > 0 ? v : dflt;

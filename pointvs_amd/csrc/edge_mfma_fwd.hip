@@ -20,9 +20,6 @@
 // allocation of the H = 64 instantiation returned NaN rows; that was the unprotected inline-asm -> MFMA hazard of the
 // operand split (pvs_f16_split2 has the story, tools/asm_mfma_hazard_scan.py finds such places), which any change of
 // schedule could expose - with the conversions back in the compiler's hands the same build is green.
-#ifndef PVS_FWD_SADDR
-#define PVS_FWD_SADDR 1
-#endif
 
 namespace {
 
@@ -34,7 +31,7 @@ namespace {
 // io.m_out; 2 the coordinate branch alone, with only Wc1 staged - it reads the messages back from io.m_out.
 // SA32: node rows and index arrays addressed as a scalar base + a 32-bit lane offset (pvs_off: -2.6 % at H = 32); the
 // launcher takes the 64-bit instantiation when a table outgrows 32-bit byte offsets (N * 8H >= 2^32 or E >= 2^30)
-template <int HB, int NT = kThreads, bool SOFT = false, bool F16X2 = false, int MODE = 0, bool SA32 = PVS_FWD_SADDR>
+template <int HB, int NT = kThreads, bool SOFT = false, bool F16X2 = false, int MODE = 0, bool SA32 = true>
 __global__ void __launch_bounds__(NT, (F16X2 && HB == 1) ? 4 : (F16X2 && NT == 768) ? 3 : 1)
 k_edge_fwd_mfma(PvsGraph g, PvsEdgeW w, uint32_t flags, int att_act, PvsEdgeFwdIO io, int n_chunks,
                 int e_lo, int e_hi) {
@@ -394,7 +391,7 @@ int pvs_launch_edge_fwd_mfma(hipStream_t s, int H, const PvsGraph& g, const PvsE
     // instantiation of the same kernel runs: PVS_FWD_SADDR=0 at run time forces it for the test)
     const char* sa_env = getenv("PVS_FWD_SADDR");
     const bool force64 = sa_env && sa_env[0] == '0';
-    const bool sa32 = PVS_FWD_SADDR && !force64 && (long long)g.n_nodes * 8 * H < (1ll << 32) && g.n_edges < (1 << 30);
+    const bool sa32 = !force64 && (long long)g.n_nodes * 8 * H < (1ll << 32) && g.n_edges < (1 << 30);
     // rows without edges are never flushed: M = 0, x_out = x
     if (!io.init_done) {
         const long long threads = (long long)g.n_nodes * (H / 4);

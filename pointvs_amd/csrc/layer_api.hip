@@ -17,7 +17,7 @@ static bool pvs_use_mfma() {
     return !(v && v[0] == 'g');
 }
 
-// PVS_ABLATE=<hex bits>: timing-only switches of the MFMA edge kernels (tools/ablate.py)
+// PVS_ABLATE=<hex bits>: timing-only switches of the MFMA edge kernels (kAbl*, edge_mfma_common.h)
 static uint32_t pvs_ablate_bits() {
     const char* v = getenv("PVS_ABLATE");
     return v ? (uint32_t)strtoul(v, nullptr, 16) << 24 : 0u;
