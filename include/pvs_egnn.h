@@ -11,7 +11,8 @@
  * Conventions
  *   - every pointer is a DEVICE pointer to caller-owned memory (torch allocations); the library
  *     never allocates, frees or synchronises; all work is enqueued on `stream` (hipGraph-capturable)
- *   - floating point is fp32, indices int32 inside the library (the int64 COO / int64 one-hot the
+ *   - floating point is fp32, except the *_f64 entries (the reference's --double: fp64 throughout, same
+ *     layouts); indices int32 inside the library (the int64 COO / int64 one-hot the
  *     reference hands over is converted once per batch by pvs_graph_prepare)
  *   - row-major, dense; "[E,H] sorted" means edge rows in the CSR order produced by
  *     pvs_graph_prepare (use pvs_rows_to_input_order to get the reference's input edge order)
@@ -413,6 +414,71 @@ int pvs_segment_reduce_fwd(const float* data, const int64_t* ids, int32_t n_rows
                            pvs_stream_t stream);
 int pvs_segment_reduce_bwd(const float* g_out, const int64_t* ids, const int32_t* ptr, int32_t n_rows,
                            int32_t width, int32_t n_segments, int32_t mean, float* g_data, pvs_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * fp64 (the reference's --double, point_vs.py: torch.set_default_dtype(torch.float64)).
+ * The same operations, layouts and conventions as the fp32 entries above, on double tensors; graphs
+ * (PvsGraph, pvs_graph_prepare) have no dtype and are shared. Every result is summed in one fixed
+ * order (no floating-point atomics): bitwise reproducible from run to run. The mean aggregation's
+ * 1 / max(deg, 1) is formed in fp64 from rowptr (PvsGraph.inv_deg is not read).
+ * Layer: H = 16, 32, 64 (callers pad other widths up to 64), 0..3 edge classes, every PVS_* flag;
+ * n_edges_dev graphs are refused. saved: pvs_egnn_layer_saved_doubles_f64() doubles.
+ */
+typedef struct PvsLayerParamsF64 {
+    const double *edge_w1, *edge_b1, *edge_w2, *edge_b2;
+    const double *coord_w1, *coord_b1, *coord_w2;
+    const double *att_w, *att_b;
+    const double *node_w1, *node_b1, *node_w2, *node_b2;
+    const double *gn_weight, *gn_bias, *gn_mean_scale;
+    const double *node_att_w, *node_att_b;
+    const double *edge_gate, *node_gate;
+} PvsLayerParamsF64;
+
+typedef struct PvsLayerGradsF64 {
+    double *edge_w1, *edge_b1, *edge_w2, *edge_b2;
+    double *coord_w1, *coord_b1, *coord_w2;
+    double *att_w, *att_b;
+    double *node_w1, *node_b1, *node_w2, *node_b2;
+    double *gn_weight, *gn_bias, *gn_mean_scale;
+    double *node_att_w, *node_att_b;
+    double *edge_gate, *node_gate;
+} PvsLayerGradsF64;
+
+size_t pvs_egnn_layer_saved_doubles_f64(const PvsLayerDesc* desc, int32_t n_nodes, int32_t n_edges);
+size_t pvs_egnn_layer_workspace_bytes_f64(const PvsLayerDesc* desc, int32_t n_nodes, int32_t n_edges,
+                                          int32_t backward);
+int pvs_egnn_layer_fwd_f64(const PvsLayerDesc* desc, const PvsGraph* graph, const PvsLayerParamsF64* params,
+                           const double* h, const double* x, const double* m_prev,
+                           double* h_out, double* x_out, double* m_out, double* att_out,
+                           double* node_att_out, double* saved,
+                           void* workspace, size_t workspace_bytes, pvs_stream_t stream);
+int pvs_egnn_layer_bwd_f64(const PvsLayerDesc* desc, const PvsGraph* graph, const PvsLayerParamsF64* params,
+                           const double* h, const double* x, const double* m_prev, const double* att,
+                           const double* saved,
+                           const double* g_h_out, const double* g_x_out, const double* g_m_out,
+                           double* g_h, double* g_x, double* g_m_prev, const PvsLayerGradsF64* grads,
+                           void* workspace, size_t workspace_bytes, pvs_stream_t stream);
+
+/* The model-level ops in fp64 (row permutations are bit copies: pvs_rows_to_*_order at twice the width). */
+int pvs_linear_fwd_f64(const double* x, const double* w, const double* b /*NULL if no bias*/, double* y,
+                       int32_t n_rows, int32_t n_in, int32_t n_out, pvs_stream_t stream);
+size_t pvs_linear_bwd_workspace_bytes_f64(int32_t n_rows, int32_t n_in, int32_t n_out);
+int pvs_linear_bwd_f64(const double* x, const double* w, const double* g_y,
+                       double* g_x /*NULL to skip*/, double* g_w, double* g_b /*NULL if no bias*/,
+                       int32_t n_rows, int32_t n_in, int32_t n_out,
+                       void* workspace, size_t workspace_bytes, pvs_stream_t stream);
+int pvs_mean_pool_fwd_f64(const double* h, const int32_t* graph_ptr, double* pooled,
+                          int32_t n_graphs, int32_t width, pvs_stream_t stream);
+int pvs_mean_pool_bwd_f64(const double* g_pooled, const int32_t* graph_ptr, double* g_h,
+                          int32_t n_graphs, int32_t n_nodes, int32_t width, pvs_stream_t stream);
+size_t pvs_segment_workspace_bytes_f64(int32_t n_rows, int32_t n_segments);
+int pvs_segment_reduce_fwd_f64(const double* data, const int64_t* ids, int32_t n_rows, int32_t width,
+                               int32_t n_segments, int32_t mean, double* out, int32_t* ptr_out,
+                               int32_t* status, void* workspace, size_t workspace_bytes,
+                               pvs_stream_t stream);
+int pvs_segment_reduce_bwd_f64(const double* g_out, const int64_t* ids, const int32_t* ptr, int32_t n_rows,
+                               int32_t width, int32_t n_segments, int32_t mean, double* g_data,
+                               pvs_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Measurement hook (no reference counterpart): when enabled, the library brackets its dominant

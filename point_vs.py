@@ -175,6 +175,9 @@ def main(argv=None):
     problems = unsupported_in_use(args)
     if problems:
         raise NotImplementedError('not available on the HIP path: ' + '; '.join(problems))
+    # --double (reference point_vs.py: "only use if precision is an issue"): the model is built in fp64, so that a seeded
+    # init matches the reference's, and runs on the fp64 kernels; the loader's features follow the model's dtype
+    torch.set_default_dtype(torch.float64 if args.double else torch.float32)
     if args.wandb_project is not None and args.wandb_run is None:
         raise SystemExit('wandb_run must be specified if wandb_project is specified.')
     save_path = Path(args.save_path, *(p for p in (args.wandb_project, args.wandb_run) if p)).expanduser()

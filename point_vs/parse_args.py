@@ -79,7 +79,7 @@ FLAGS = (
     (('--regression_loss',), STR, 'mse', 'mse | huber'),
     (('--use_1cycle',), ON, False, '1cycle learning-rate schedule'),
     (('--warm_restarts',), ON, False, 'cosine annealing with warm restarts'),
-    (('--double',), ON, False, 'fp64 (not available on the HIP path: raises)'),
+    (('--double',), ON, False, 'fp64 throughout (torch default dtype float64, fp64 kernels)'),
     # --- run control / bookkeeping ---
     (('--load_weights', '-l'), STR, None, 'checkpoint (or model directory) to start from'),
     (('--load_args',), STR, None, 'yaml of argument values that override the command line'),
@@ -122,8 +122,6 @@ def unsupported_in_use(args):
     """Flags set on the command line that this entry cannot honour (it raises on them rather than
     silently training something else)."""
     bad = []
-    if args.double:
-        bad.append('--double (the HIP kernels are fp32)')
     if args.model == 'lucid':
         bad.append('model lucid (outside the hot path)')
     if args.include_strain_info:

@@ -39,6 +39,14 @@ class PvsLayerGrads(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in PARAM_FIELDS]
 
 
+class PvsLayerParamsF64(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in PARAM_FIELDS]
+
+
+class PvsLayerGradsF64(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in PARAM_FIELDS]
+
+
 class PvsStackStrides(C.Structure):
     _fields_ = [(name, C.c_int64) for name in ('h_mid', 'x_mid', 'att', 'node_att', 'saved')]
 
@@ -118,6 +126,23 @@ _PROTOTYPES = {
                                      C.c_double, C.c_double, C.c_float, C.c_void_p]),
     'pvs_adam_clip_step_dev': (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_float, C.c_float,
                                          C.c_void_p, C.c_float, C.c_void_p]),
+    # fp64 (--double)
+    'pvs_egnn_layer_saved_doubles_f64': (C.c_size_t, [C.POINTER(PvsLayerDesc), C.c_int32, C.c_int32]),
+    'pvs_egnn_layer_workspace_bytes_f64': (C.c_size_t, [C.POINTER(PvsLayerDesc), C.c_int32, C.c_int32, C.c_int32]),
+    'pvs_egnn_layer_fwd_f64': (C.c_int, [C.POINTER(PvsLayerDesc), C.POINTER(PvsGraph), C.POINTER(PvsLayerParamsF64)] +
+                               [C.c_void_p] * 9 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    'pvs_egnn_layer_bwd_f64': (C.c_int, [C.POINTER(PvsLayerDesc), C.POINTER(PvsGraph), C.POINTER(PvsLayerParamsF64)] +
+                               [C.c_void_p] * 11 + [C.POINTER(PvsLayerGradsF64), C.c_void_p, C.c_size_t, C.c_void_p]),
+    'pvs_linear_fwd_f64': (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 3 + [C.c_void_p]),
+    'pvs_linear_bwd_workspace_bytes_f64': (C.c_size_t, [C.c_int32] * 3),
+    'pvs_linear_bwd_f64': (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 3 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    'pvs_mean_pool_fwd_f64': (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 2 + [C.c_void_p]),
+    'pvs_mean_pool_bwd_f64': (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 3 + [C.c_void_p]),
+    'pvs_segment_workspace_bytes_f64': (C.c_size_t, [C.c_int32, C.c_int32]),
+    'pvs_segment_reduce_fwd_f64': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'pvs_segment_reduce_bwd_f64': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                             C.c_int32, C.c_void_p, C.c_void_p]),
     'pvs_profile_enable': (C.c_int, [C.c_int]),
     'pvs_profile_reset': (C.c_int, []),
     'pvs_profile_read': (C.c_int, [C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),

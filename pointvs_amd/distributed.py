@@ -21,6 +21,14 @@ import torch
 import torch.distributed as dist
 
 
+def _refuse_fp64(params, group):
+    """The flat buckets are fp32: fp64 gradients would be rounded on the way through. Refused with more than one rank."""
+    if (dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
+            and any(p.dtype == torch.float64 for p in params)):
+        raise NotImplementedError('multi-rank gradient exchange of fp64 parameters is not built (the fp32 flat '
+                                  'buffers would round them): train fp64 models on one rank')
+
+
 def _active(group, alone=False):
     """A process group exists and has someone to exchange with. alone=True: also a group of ONE rank runs
     its collectives (an RCCL smoke on a one-GPU box walks the very code of the multi-rank path)."""
@@ -79,6 +87,7 @@ class GradAllReducer:
 
     def __init__(self, params, process_group=None, exchange_when_alone=False):
         self.params = list(params)
+        _refuse_fp64(self.params, process_group)
         self.group = process_group
         self.alone = bool(exchange_when_alone)
         self._live = None
@@ -162,6 +171,7 @@ class OverlappedGradAllReducer:
 
     def __init__(self, params, n_buckets=2, process_group=None, exchange_when_alone=False):
         self.params = list(params)
+        _refuse_fp64(self.params, process_group)
         self.group = process_group
         self.alone = bool(exchange_when_alone)
         self._flat_fallback = GradAllReducer(self.params, process_group, exchange_when_alone)

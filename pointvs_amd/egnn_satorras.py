@@ -218,11 +218,14 @@ class EGNNLayer(nn.Module):
             else:
                 return params, pstruct
         params = self._params()
-        ok = all(p is None or (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()) for p in params)
+        dtype = params[0].dtype     # fp64 layers (model.double(), --double) get the fp64 struct
+        ok = dtype in (torch.float32, torch.float64) and all(
+            p is None or (p.is_cuda and p.dtype == dtype and p.is_contiguous()) for p in params)
         if not ok:
             self.__dict__.pop('_pcache', None)
             return params, None
-        pstruct = _lib.PvsLayerParams(*[_lib.ptr(p) for p in params])
+        struct = _lib.PvsLayerParams if dtype == torch.float32 else _lib.PvsLayerParamsF64
+        pstruct = struct(*[_lib.ptr(p) for p in params])
         probes = self._slot_probes(params)
         if probes is None:            # computed weights (parametrizations): a fresh struct per call
             self.__dict__.pop('_pcache', None)
@@ -259,6 +262,8 @@ class EGNNLayer(nn.Module):
         the public sub-methods instead."""
         if self.hidden_nf <= 64:
             return True
+        if self.edge_mlp[0].weight.dtype == torch.float64:      # fp64 is built up to 64 channels
+            return False
         return (self.hidden_nf <= 128 and self.edges_in_d <= 3 and os.environ.get('PVS_WIDE') != 'decomposed'
                 and os.environ.get('PVS_EGNN_KERNELS', '')[:1] != 'g')
 
@@ -401,7 +406,7 @@ class EGNNLayer(nn.Module):
     def _mlp(seq, x):
         for mod in seq:
             if isinstance(mod, nn.Linear):
-                if min(mod.in_features, mod.out_features) > 64 or mod.out_features > 64:
+                if x.dtype == torch.float32 and (min(mod.in_features, mod.out_features) > 64 or mod.out_features > 64):
                     # a plain GEMM wider than the MFMA linear kernels are built for (hidden sizes above 64):
                     # the library GEMM (hipBLASLt through torch) instead of the generic one-row-per-lane kernel
                     _lib.require_hip(x)
@@ -621,7 +626,7 @@ class SartorrasEGNN(PNNGeometricBase):
         pstructs, param_tuples = [], []
         for layer in egnn_layers:
             params, pstruct = layer._params_cached()
-            if pstruct is None:
+            if pstruct is None or isinstance(pstruct, _lib.PvsLayerParamsF64):     # (no fused fp64 stack)
                 return None
             pstructs.append(pstruct)
             param_tuples.append(params)

@@ -18,12 +18,37 @@ def _ws(nbytes, dev):
     return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)
 
 
+def _fc(t, dtype):
+    """`t` contiguous, checked to be of `dtype` (the dtype of the call's primary input): the kernels never cast."""
+    if t is None:
+        return None
+    if t.dtype != dtype:
+        raise TypeError(f'pointvs_amd: a {t.dtype} tensor in a {dtype} call (mixed dtypes are not cast)')
+    return t.contiguous()
+
+
 def _f32c(t):
     if t is None:
         return None
     if t.dtype != torch.float32:
-        raise TypeError(f'pointvs_amd kernels are fp32 (got {t.dtype}); --double is not supported')
+        raise TypeError(f'pointvs_amd: this op is fp32 only (got {t.dtype}); fp64 runs per-layer ops')
     return t.contiguous()
+
+
+_F64 = torch.float64
+
+
+def _call_dtype(what, primary, **others):
+    """The dtype of a call: its primary input's, fp32 or fp64. Any other floating tensor of another dtype is a
+    TypeError that names them all (fp64 parameters with fp32 features, say): never cast silently."""
+    dtype = primary.dtype
+    if dtype not in (torch.float32, _F64):
+        raise TypeError(f'{what}: pointvs_amd kernels are float32 or float64 (got {dtype})')
+    bad = [f'{k}: {t.dtype}' for k, t in others.items() if t is not None and t.dtype != dtype]
+    if bad:
+        raise TypeError(f'{what}: mixed dtypes - the primary input is {dtype}, but ' + ', '.join(bad) +
+                        ' (convert the model and its inputs to one dtype: model.double() / .float())')
+    return dtype
 
 
 class _PermuteRows(torch.autograd.Function):
@@ -31,10 +56,12 @@ class _PermuteRows(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, src, perm, to_input):
-        src = _f32c(src)
+        src = _f32c(src) if src.dtype != _F64 else src.contiguous()
         _lib.require_hip(src)
         ctx.perm, ctx.to_input = perm, to_input
         width = src.shape[1] if src.dim() > 1 else 1
+        if src.dtype == _F64:       # a bit copy: the fp32 kernel moves 2 x width words per row
+            width *= 2
         dst = torch.empty_like(src)
         fn = _lib.lib().pvs_rows_to_input_order if to_input else _lib.lib().pvs_rows_to_sorted_order
         _lib.check(fn(_lib.ptr(src), _lib.ptr(dst), _lib.ptr(perm), src.shape[0], width,
@@ -149,8 +176,90 @@ class _EGNNLayerFn(torch.autograd.Function):
         return (g_h, g_x, g_m_prev, None, None, None, None, *grads)
 
 
+class _EGNNLayerF64Fn(torch.autograd.Function):
+    """The fp64 layer (pvs_egnn_layer_fwd_f64 / _bwd_f64): same contract as _EGNNLayerFn, double tensors."""
+
+    @staticmethod
+    def forward(ctx, h, x, m_prev, pg, desc_tuple, need_m, pstruct, *params):
+        lib = _lib.lib()
+        hidden, n_attr, flags, act = desc_tuple
+        h, x, m_prev = h.contiguous(), x.contiguous(), None if m_prev is None else m_prev.contiguous()
+        if pstruct is None:
+            params = tuple(None if p is None else p.contiguous() for p in params)
+            _lib.require_hip(h, x, m_prev, *params)
+            pstruct = _lib.PvsLayerParamsF64(*[_lib.ptr(p) for p in params])
+        else:
+            _lib.require_hip(h, x, m_prev)
+        dev = h.device
+        n, e = pg.n_nodes, pg.n_edges
+        if h.shape != (n, hidden) or x.shape != (n, 3):
+            raise ValueError(f'h {tuple(h.shape)} / coord {tuple(x.shape)} do not match N={n}, H={hidden}')
+        if n_attr != pg.n_edge_attr:
+            raise ValueError(f'layer built with edges_in_d={n_attr} but edge_attr has {pg.n_edge_attr} columns')
+        desc = _lib.PvsLayerDesc(hidden, n_attr, flags, act)
+        eres = bool(flags & _lib.EDGE_RESIDUAL) and m_prev is not None
+        f64 = dict(dtype=_F64, device=dev)
+        h_out, x_out = torch.empty_like(h), torch.empty_like(x)
+        m_out = torch.empty((max(e, 0), hidden), **f64) if need_m else None
+        att = torch.empty((max(e, 1),), **f64) if flags & _lib.EDGE_ATTENTION else None
+        node_att = torch.empty((n,), **f64) if flags & _lib.NODE_ATTENTION else None
+        saved = torch.empty(lib.pvs_egnn_layer_saved_doubles_f64(C.byref(desc), n, e), **f64)
+        ws_bytes = lib.pvs_egnn_layer_workspace_bytes_f64(C.byref(desc), n, e, 0)
+        ws = _ws(ws_bytes, dev)
+        _lib.check(lib.pvs_egnn_layer_fwd_f64(
+            C.byref(desc), C.byref(pg.c), C.byref(pstruct), _lib.ptr(h), _lib.ptr(x),
+            _lib.ptr(m_prev if eres else None), _lib.ptr(h_out), _lib.ptr(x_out), _lib.ptr(m_out),
+            _lib.ptr(att), _lib.ptr(node_att), _lib.ptr(saved), _lib.ptr(ws), ws_bytes, _stream(dev)),
+            'pvs_egnn_layer_fwd_f64')
+        ctx.pg, ctx.desc_tuple, ctx.eres, ctx.pstruct = pg, desc_tuple, eres, pstruct
+        ctx.save_for_backward(h, x, m_prev if eres else None, att, saved, *params)
+        ctx.set_materialize_grads(False)
+        if att is not None or node_att is not None:
+            ctx.mark_non_differentiable(*[t for t in (att, node_att) if t is not None])
+        return h_out, x_out, m_out, att, node_att
+
+    @staticmethod
+    def backward(ctx, g_h_out, g_x_out, g_m_out, _g_att, _g_natt):
+        lib = _lib.lib()
+        h, x, m_prev, att, saved, *params = ctx.saved_tensors
+        pg = ctx.pg
+        hidden, n_attr, flags, act = ctx.desc_tuple
+        dev = h.device
+        n, e = pg.n_nodes, pg.n_edges
+        desc = _lib.PvsLayerDesc(hidden, n_attr, flags, act)
+        g_h_out = torch.zeros_like(h) if g_h_out is None else _fc(g_h_out, _F64)
+        g_x_out = _fc(g_x_out, _F64)
+        g_m_out = _fc(g_m_out, _F64) if (g_m_out is not None and g_m_out.numel()) else None
+        g_h = torch.empty_like(h)
+        g_x = torch.empty_like(x) if ctx.needs_input_grad[1] else None
+        g_m_prev = torch.empty_like(m_prev) if ctx.eres else None
+        coord_live = bool(flags & _lib.UPDATE_COORDS) and g_x_out is not None
+        live = {'coord_w1': coord_live, 'coord_b1': coord_live, 'coord_w2': coord_live,
+                'edge_gate': ctx.eres and bool(flags & (_lib.REZERO | _lib.GATED_RESIDUAL))}
+        grads = [None if (p is None or not live.get(name, True)) else torch.empty_like(p)
+                 for name, p in zip(_lib.PARAM_FIELDS, params)]
+        gstruct = _lib.PvsLayerGradsF64(*[_lib.ptr(g) for g in grads])
+        ws_bytes = lib.pvs_egnn_layer_workspace_bytes_f64(C.byref(desc), n, e, 1)
+        ws = _ws(ws_bytes, dev)
+        _lib.check(lib.pvs_egnn_layer_bwd_f64(
+            C.byref(desc), C.byref(pg.c), C.byref(ctx.pstruct), _lib.ptr(h), _lib.ptr(x),
+            _lib.ptr(m_prev), _lib.ptr(att), _lib.ptr(saved), _lib.ptr(g_h_out), _lib.ptr(g_x_out),
+            _lib.ptr(g_m_out), _lib.ptr(g_h), _lib.ptr(g_x), _lib.ptr(g_m_prev), C.byref(gstruct),
+            _lib.ptr(ws), ws_bytes, _stream(dev)), 'pvs_egnn_layer_bwd_f64')
+        return (g_h, g_x, g_m_prev, None, None, None, None, *grads)
+
+
 def egnn_layer(h, x, m_prev_sorted, pg, desc_tuple, need_m, params, pstruct=None):
-    """Returns (h_out, x_out, m_sorted|None, att_sorted|None, node_att|None). pstruct: see _EGNNLayerFn.forward."""
+    """Returns (h_out, x_out, m_sorted|None, att_sorted|None, node_att|None). pstruct: see _EGNNLayerFn.forward.
+    fp64 (h float64, or a layer whose cached parameter struct is fp64) runs the fp64 kernels; mixed dtypes raise."""
+    if h.dtype == _F64 or isinstance(pstruct, _lib.PvsLayerParamsF64):
+        _call_dtype('EGNNLayer', h, coord=x, edge_messages=m_prev_sorted,
+                    **{name: p for name, p in zip(_lib.PARAM_FIELDS, params)})
+        if pg.c.n_edges_dev:
+            raise NotImplementedError('fp64 layers need a graph with a host-known edge count')
+        return _EGNNLayerF64Fn.apply(h, x, m_prev_sorted, pg, desc_tuple, need_m, pstruct, *params)
+    if pstruct is None and params and params[0] is not None and params[0].dtype == _F64:
+        _call_dtype('EGNNLayer', h, coord=x, **{name: p for name, p in zip(_lib.PARAM_FIELDS, params)})
     return _EGNNLayerFn.apply(h, x, m_prev_sorted, pg, desc_tuple, need_m, pstruct, *params)
 
 
@@ -325,6 +434,20 @@ class _LinearFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w, b):
+        if x.dtype == _F64:
+            _call_dtype('linear', x, weight=w, bias=b)
+            x, w, b = _fc(x, _F64), _fc(w, _F64), _fc(b, _F64)
+            _lib.require_hip(x, w, b)
+            n, k = x.shape
+            c = w.shape[0]
+            y = torch.empty((n, c), dtype=_F64, device=x.device)
+            _lib.check(_lib.lib().pvs_linear_fwd_f64(_lib.ptr(x), _lib.ptr(w), _lib.ptr(b), _lib.ptr(y),
+                                                     n, k, c, _stream(x.device)), 'pvs_linear_fwd_f64')
+            ctx.save_for_backward(x, w)
+            ctx.has_bias = b is not None
+            return y
+        if w.dtype != torch.float32 or (b is not None and b.dtype != torch.float32):
+            _call_dtype('linear', x, weight=w, bias=b)
         x, w, b = _f32c(x), _f32c(w), _f32c(b)
         _lib.require_hip(x, w, b)
         n, k = x.shape
@@ -339,6 +462,8 @@ class _LinearFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_y):
         x, w = ctx.saved_tensors
+        if x.dtype == _F64:
+            return _LinearFn._backward_f64(ctx, x, w, _fc(g_y, _F64))
         g_y = _f32c(g_y)
         n, k = x.shape
         c = w.shape[0]
@@ -353,6 +478,21 @@ class _LinearFn(torch.autograd.Function):
                                       _stream(x.device)), 'pvs_linear_bwd')
         return g_x, g_w, g_b
 
+    @staticmethod
+    def _backward_f64(ctx, x, w, g_y):
+        n, k = x.shape
+        c = w.shape[0]
+        lib = _lib.lib()
+        g_x = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        g_w = torch.empty_like(w)
+        g_b = torch.empty((c,), dtype=_F64, device=x.device) if ctx.has_bias else None
+        ws_bytes = lib.pvs_linear_bwd_workspace_bytes_f64(n, k, c)
+        ws = _ws(ws_bytes, x.device)
+        _lib.check(lib.pvs_linear_bwd_f64(_lib.ptr(x), _lib.ptr(w), _lib.ptr(g_y), _lib.ptr(g_x), _lib.ptr(g_w),
+                                          _lib.ptr(g_b), n, k, c, _lib.ptr(ws), ws_bytes, _stream(x.device)),
+                   'pvs_linear_bwd_f64')
+        return g_x, g_w, g_b
+
 
 def linear(x, weight, bias=None):
     squeeze = x.dim() == 1
@@ -365,6 +505,15 @@ class _MeanPoolFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, h, graph_ptr):
+        if h.dtype == _F64:
+            h = _fc(h, _F64)
+            _lib.require_hip(h, graph_ptr)
+            b = graph_ptr.numel() - 1
+            pooled = torch.empty((b, h.shape[1]), dtype=_F64, device=h.device)
+            _lib.check(_lib.lib().pvs_mean_pool_fwd_f64(_lib.ptr(h), _lib.ptr(graph_ptr), _lib.ptr(pooled),
+                                                        b, h.shape[1], _stream(h.device)), 'pvs_mean_pool_fwd_f64')
+            ctx.graph_ptr, ctx.n = graph_ptr, h.shape[0]
+            return pooled
         h = _f32c(h)
         _lib.require_hip(h, graph_ptr)
         b = graph_ptr.numel() - 1
@@ -377,6 +526,13 @@ class _MeanPoolFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
+        if g.dtype == _F64:
+            g = _fc(g, _F64)
+            b, width = g.shape
+            g_h = torch.empty((ctx.n, width), dtype=_F64, device=g.device)
+            _lib.check(_lib.lib().pvs_mean_pool_bwd_f64(_lib.ptr(g), _lib.ptr(ctx.graph_ptr), _lib.ptr(g_h),
+                                                        b, ctx.n, width, _stream(g.device)), 'pvs_mean_pool_bwd_f64')
+            return g_h, None
         g = _f32c(g)
         b, width = g.shape
         g_h = torch.empty((ctx.n, width), dtype=torch.float32, device=g.device)
@@ -534,24 +690,34 @@ class _SegmentReduceFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, data, segment_ids, num_segments, mean):
-        data = _f32c(data)
+        f64 = data.dtype == _F64
+        data = _fc(data, _F64) if f64 else _f32c(data)
         _lib.require_hip(data, segment_ids)
         lib = _lib.lib()
+        ctx.f64 = f64
         ids = segment_ids.long().contiguous()
         e, c = data.shape
         dev = data.device
         capturing = torch.cuda.is_current_stream_capturing()
         if not capturing:
             _SegmentStatus.poll()           # an earlier call's out-of-range ids raise here
-        out = torch.empty((num_segments, c), dtype=torch.float32, device=dev)
+        out = torch.empty((num_segments, c), dtype=data.dtype, device=dev)
         ptr = torch.empty(num_segments + 1, dtype=torch.int32, device=dev)
         status = torch.empty(1, dtype=torch.int32, device=dev)
-        ws_bytes = lib.pvs_segment_workspace_bytes(e, num_segments)
-        ws = _ws(ws_bytes, dev)
-        _lib.check(lib.pvs_segment_reduce_fwd(
-            _lib.ptr(data), _lib.ptr(ids), e, c, num_segments, 1 if mean else 0, _lib.ptr(out),
-            _lib.ptr(ptr), _lib.ptr(status), _lib.ptr(ws), ws_bytes, _stream(dev)),
-            'pvs_segment_reduce_fwd')
+        if f64:
+            ws_bytes = lib.pvs_segment_workspace_bytes_f64(e, num_segments)
+            ws = _ws(ws_bytes, dev)
+            _lib.check(lib.pvs_segment_reduce_fwd_f64(
+                _lib.ptr(data), _lib.ptr(ids), e, c, num_segments, 1 if mean else 0, _lib.ptr(out),
+                _lib.ptr(ptr), _lib.ptr(status), _lib.ptr(ws), ws_bytes, _stream(dev)),
+                'pvs_segment_reduce_fwd_f64')
+        else:
+            ws_bytes = lib.pvs_segment_workspace_bytes(e, num_segments)
+            ws = _ws(ws_bytes, dev)
+            _lib.check(lib.pvs_segment_reduce_fwd(
+                _lib.ptr(data), _lib.ptr(ids), e, c, num_segments, 1 if mean else 0, _lib.ptr(out),
+                _lib.ptr(ptr), _lib.ptr(status), _lib.ptr(ws), ws_bytes, _stream(dev)),
+                'pvs_segment_reduce_fwd')
         ctx.status = None if capturing else _SegmentStatus(status)      # (no host-visible validation inside a capture)
         ctx.save_for_backward(ids, ptr)
         ctx.mean, ctx.shape, ctx.n_segments = mean, (e, c), num_segments
@@ -562,8 +728,15 @@ class _SegmentReduceFn(torch.autograd.Function):
         ids, ptr = ctx.saved_tensors
         if ctx.status is not None and not torch.cuda.is_current_stream_capturing():
             ctx.status.settle(wait=True)
-        g_out = _f32c(g_out)
         e, c = ctx.shape
+        if ctx.f64:
+            g_out = _fc(g_out, _F64)
+            g_data = torch.empty((e, c), dtype=_F64, device=g_out.device)
+            _lib.check(_lib.lib().pvs_segment_reduce_bwd_f64(
+                _lib.ptr(g_out), _lib.ptr(ids), _lib.ptr(ptr), e, c, ctx.n_segments, 1 if ctx.mean else 0,
+                _lib.ptr(g_data), _stream(g_out.device)), 'pvs_segment_reduce_bwd_f64')
+            return g_data, None, None, None
+        g_out = _f32c(g_out)
         g_data = torch.empty((e, c), dtype=torch.float32, device=g_out.device)
         _lib.check(_lib.lib().pvs_segment_reduce_bwd(
             _lib.ptr(g_out), _lib.ptr(ids), _lib.ptr(ptr), e, c, ctx.n_segments, 1 if ctx.mean else 0,

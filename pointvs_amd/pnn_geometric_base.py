@@ -28,9 +28,19 @@ class PNNGeometricBase(PointNeuralNetworkBase):
     def unpack_graph(self, graph):
         edges = getattr(graph, 'edge_index', None)      # None when the graph was built on the GPU
         attrs = getattr(graph, 'edge_attr', None)
+        if self._model_dtype() == torch.float64:      # --double: features and coordinates in the model's dtype
+            return (graph.x.to(DEVICE, torch.float64), None if edges is None else edges.to(DEVICE),
+                    graph.pos.to(DEVICE, torch.float64), None if attrs is None else attrs.to(DEVICE),
+                    graph.batch.to(DEVICE))
         return (graph.x.float().to(DEVICE), None if edges is None else edges.to(DEVICE),
                 graph.pos.float().to(DEVICE), None if attrs is None else attrs.to(DEVICE),
                 graph.batch.to(DEVICE))
+
+    def _model_dtype(self):
+        """float64 for a model built or moved to fp64 (the embedding's weight decides), else float32."""
+        embed = self.layers[0] if getattr(self, 'layers', None) is not None and len(self.layers) else None
+        w = getattr(getattr(embed, 'm', None), 'weight', None)
+        return torch.float32 if w is None else w.dtype
 
     def _embed_graph(self, graph):
         feats, edges, coords, edge_attributes, batch = self.unpack_graph(graph)
@@ -93,6 +103,7 @@ class PNNGeometricBase(PointNeuralNetworkBase):
         op (PF.pool_head: one launch forward, one backward)."""
         mods = list(head)
         if (not mods or not isinstance(mods[0], nn.Linear) or feats.size(1) > PF.POOL_HEAD_MAX_WIDTH
+                or feats.dtype != torch.float32                    # (fp64: mean_pool + linear)
                 or os.environ.get('PVS_FUSED_HEAD') == '0'):       # (=0: the two ops apart, for A/B)
             return cls._run_head(head, cls._pool(feats, graph_ptr, n_graphs))
         if n_graphs == 1:

@@ -83,6 +83,8 @@ class _StepReplayer:
                                       'into the captured optimiser step)')
         if not isinstance(model.optimiser, torch.optim.Adam):
             raise NotImplementedError('train_model(capture=True) needs the Adam optimiser')
+        if any(p.dtype == torch.float64 for p in model.parameters()):
+            raise NotImplementedError('train_model(capture=True) is fp32 only (fp64 trains eagerly)')
         self.model, self.max_graphs = model, max_graphs
         # one side stream per model, kept across calls (AccumulateGrad nodes remember the stream of their first backward)
         if getattr(model, '_capture_stream', None) is None:
@@ -249,9 +251,10 @@ class PointNeuralNetworkBase(nn.Module):
             if (y_pred.is_cuda and y_pred.dtype == torch.float32      # nn.BCEWithLogitsLoss() as one launch each way
                     and os.environ.get('PVS_FUSED_HEAD') != '0'):
                 return PF.bce_with_logits_mean(y_pred, y_true.to(device=y_pred.device, dtype=torch.float32))
-            return self.bce(y_pred, y_true.to(y_pred.device))
+            # (labels arrive as fp32; an fp64 model's logits want fp64 targets)
+            return self.bce(y_pred, y_true.to(device=y_pred.device, dtype=y_pred.dtype))
         if self.model_task == 'regression':
-            return self.regression_loss(y_pred, y_true.to(y_pred.device))
+            return self.regression_loss(y_pred, y_true.to(device=y_pred.device, dtype=y_pred.dtype))
         y_pred[torch.where(y_true == -1)] = -1
         return 3 * self.regression_loss(y_pred, y_true.to(y_pred.device))
 

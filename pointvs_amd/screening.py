@@ -29,6 +29,9 @@ class ReceptorScreen:
     lig_poses [batch_size, n_lig, 3] on the device. Returns the model's raw outputs [batch_size, ...]."""
 
     def __init__(self, model, rec_pos, feats, n_lig, batch_size, edge_radius, intra_radius=None):
+        if any(p.dtype == torch.float64 for p in model.parameters()):
+            raise NotImplementedError('ReceptorScreen and its pose-batch builder are fp32 only (no fp64 screening '
+                                      'kernels): score fp64 models through the model forward')
         layers = list(model.layers)
         self.model, self.embed, self.egnn = model, layers[0], layers[1:]
         first = self.egnn[0] if self.egnn else None
