@@ -287,6 +287,29 @@ int pvs_screen_graph_build(const float* lig_pos, const float* rec_pos, const int
                            int32_t* rowptr_lig, int32_t* row_lig, int32_t* col_lig, uint8_t* etype_lig,
                            int32_t* status, void* state, size_t state_bytes, pvs_stream_t stream);
 
+/* Leave-out graph batch of masking attribution (the reference's atom_masking / bond_masking loops,
+ * attribution/attribution_fns.py:39-115, 356-456, which rebuild one masked edge list per atom on the host).
+ * `parent`: the prepared graph of ONE complex (rowptr / col / etype; host-side edge count); drop [n_masks, 2] int32:
+ * the node(s) each copy leaves out, drop[b][1] = -1 (or = drop[b][0]) for a single node. Output: the PvsGraph arrays of
+ * the disjoint union of n_masks copies, copy b without its dropped nodes and every edge touching them, node ids
+ * renumbered densely. The arrays equal what pvs_graph_prepare makes of the masked COO lists (same order inside a row,
+ * duplicate edges kept); no sort is run: a row-sorted list with rows removed is row-sorted. Forward-only (no perm, no
+ * by-column lists).
+ *   total_nodes: the caller's count of output nodes (n_masks * N less one or two per copy), the size of the node arrays
+ *   capacity:    room for edges in row / col / etype, <= n_masks * E; exact_edges != 0: the caller has counted the
+ *                surviving edges on the host and `capacity` IS that count (any other count is an error, bit 4)
+ *   rowptr [total_nodes + 1] (its last entry = the edge count, usable as PvsGraph.n_edges_dev), row / col / etype
+ *   [capacity] (etype NULL exactly when the parent has none), inv_deg [total_nodes],
+ *   src_node [total_nodes]: the parent node each output node is (gather features and coordinates with it),
+ *   graph_ptr / graph_eptr [n_masks + 1]: first node / first edge of every copy (PvsGraph.graph_eptr).
+ * *status: bit 0 = a node id outside [0, N) (second id: [-1, N)), bit 2 = more than `capacity` edges, bit 3 =
+ * total_nodes does not match the table, bit 4 = exact_edges and another edge count; no edge is written then. Bitwise reproducible; no host synchronisation. */
+size_t pvs_mask_graph_workspace_bytes(int32_t n_nodes, int32_t n_masks);
+int pvs_mask_graph_build(const PvsGraph* parent, const int32_t* drop, int32_t n_masks, int32_t total_nodes,
+                         int32_t capacity, int32_t exact_edges, int32_t* rowptr, int32_t* row, int32_t* col,
+                         uint8_t* etype, float* inv_deg, int32_t* src_node, int32_t* graph_ptr, int32_t* graph_eptr,
+                         int32_t* status, void* workspace, size_t workspace_bytes, pvs_stream_t stream);
+
 /* Backward of the above (what autograd replays for the reference, SURVEY.md §8a "Backward spec").
  *   g_h_out [N,H]; g_x_out [N,3] or NULL (=0: the last layer's x is unused);
  *   g_m_out [E,H] sorted or NULL (=0); att [E] sorted as written by the forward.
@@ -482,10 +505,10 @@ int pvs_segment_reduce_bwd_f64(const double* g_out, const int64_t* ids, const in
 
 /* ---------------------------------------------------------------------------------------------
  * Measurement hook (no reference counterpart): when enabled, the library brackets its dominant
- * kernels ("edge_fwd", "edge_bwd", "col_gather", "graph_prepare") with HIP events on the launch
+ * kernels ("edge_fwd", "edge_bwd", "col_gather", "graph_prepare", "edge_fwd_partial", "mask_graph") with HIP events on the launch
  * stream; pvs_profile_read waits for those events and returns the summed kernel time. Used by
  * bench.py for the roofline figure; off by default (no events are created).
- * on: 0 = off; 1 = all four groups; otherwise a mask, bit (k + 1) = group k in the order above (an event pair costs the
+ * on: 0 = off; 1 = all groups; otherwise a mask, bit (k + 1) = group k in the order above (an event pair costs the
  * stream a ~6 us bubble per launch, so bench.py brackets only the dominant kernel inside its timed region).
  */
 int pvs_profile_enable(int on);

@@ -9,7 +9,8 @@ struct Rec { int id; hipEvent_t a, b; };
 std::mutex g_mu;
 unsigned g_mask = 0;      // bit 0: every category; bit (id + 1): category id
 std::vector<Rec*> g_recs;
-const char* kNames[PVS_PROF_COUNT] = {"edge_fwd", "edge_bwd", "col_gather", "graph_prepare", "edge_fwd_partial"};
+const char* kNames[PVS_PROF_COUNT] = {"edge_fwd", "edge_bwd", "col_gather", "graph_prepare", "edge_fwd_partial",
+                                      "mask_graph"};
 thread_local int t_fwd_tag = PVS_PROF_EDGE_FWD;
 }  // namespace
 
