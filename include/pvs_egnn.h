@@ -510,6 +510,10 @@ int pvs_segment_reduce_bwd_f64(const double* g_out, const int64_t* ids, const in
  * bench.py for the roofline figure; off by default (no events are created).
  * on: 0 = off; 1 = all groups; otherwise a mask, bit (k + 1) = group k in the order above (an event pair costs the
  * stream a ~6 us bubble per launch, so bench.py brackets only the dominant kernel inside its timed region).
+ * Behind those six, one group per dispatch route of the dense launchers, for tests that pin a shape to its route:
+ * "linear_mfma", "linear_chunk64", "linear_chunk256", "linear_generic", "tsgemm_mfma", "tsgemm_wide",
+ * "tsgemm_colchunk", "tsgemm_narrow", "tsgemm_tn8", "tsgemm_tn32", "colreduce4", "colreduce", "colreduce_chunk"
+ * (groups 6 .. 18). These are recorded only when their own mask bit is set; on = 1 leaves them out.
  */
 int pvs_profile_enable(int on);
 int pvs_profile_reset(void);

@@ -1,5 +1,6 @@
 #include "dense_ops.h"
 #include "mfma_common.h"
+#include "profile.h"
 
 namespace {
 
@@ -629,6 +630,7 @@ __global__ void k_mean_pool_bwd(const float* __restrict__ gp, const int32_t* __r
             int mid = (lo + hi) >> 1;
             if (gptr[mid] <= n) lo = mid; else hi = mid;
         }
+        if (n < gptr[0] || n >= gptr[B]) { gh[i] = 0.f; continue; }     // a row outside every graph's range fed no mean
         int cnt = gptr[lo + 1] - gptr[lo];
         gh[i] = gp[(size_t)lo * width + c] / (float)(cnt > 1 ? cnt : 1);
     }
@@ -1033,6 +1035,7 @@ int pvs_launch_linear(hipStream_t s, float* y, int ldy, const float* x, int ldx,
         // more output channels than one pass holds (one per thread): chunks of the output dimension (the input
         // gradient of a layer whose input is wider than 256: edge_mlp.0 at hidden size 128 on the decomposed path)
         PVS_REQUIRE(epi == 0 && !x2, "linear: n_out %d > %d needs the plain form", C, kThreads);
+        PvsProfScope prof(s, PVS_PROF_LIN_CHUNK256);
         for (int c0 = 0; c0 < C; c0 += kThreads) {
             const int rc = pvs_launch_linear(s, y + c0, ldy, x, ldx, W + (size_t)c0 * swc, swc, swk, b ? b + c0 : nullptr,
                                              nullptr, 0, nullptr, 0, 0, N, K, 0, C - c0 < kThreads ? C - c0 : kThreads,
@@ -1052,6 +1055,7 @@ int pvs_launch_linear(hipStream_t s, float* y, int ldy, const float* x, int ldx,
     auto mfma_k = [](int k) { return k == 32 || k == 64 || k == 128; };
     if (aligned16 && epi == 0 && C > 64 && C % 64 == 0 && mfma_k(K) && (K2 == 0 || mfma_k(K2)) &&
         (KK > 128 || C > 64)) {
+        PvsProfScope prof(s, PVS_PROF_LIN_CHUNK64);
         for (int c0 = 0; c0 < C; c0 += 64) {
             int rc = pvs_launch_linear(s, y + c0, ldy, x, ldx, W + (size_t)c0 * swc, swc, swk, b ? b + c0 : nullptr,
                                        nullptr, 0, nullptr, 0, 0, N, K, 0, 64, accumulate, 0, nullptr, 0, nullptr, 0);
@@ -1073,6 +1077,7 @@ int pvs_launch_linear(hipStream_t s, float* y, int ldy, const float* x, int ldx,
         const int rows_m = N >= 32768 ? kLinRows : 128;
         int blocks_m = (N + rows_m - 1) / rows_m;
         if (blocks_m > 1024) blocks_m = 1024;
+        PvsProfScope prof(s, PVS_PROF_LIN_MFMA);
 #define PVS_LIN(KBV, CBV)                                                                          \
     k_linear_mfma<KBV, CBV><<<blocks_m, kThreads, lds_m, s>>>(y, ldy, x, ldx, K / 32, x2, ldx2, W, swc, \
                                                               swk, W2, swc2, swk2, b, N, accumulate ? 1 : 0, \
@@ -1096,6 +1101,7 @@ int pvs_launch_linear(hipStream_t s, float* y, int ldy, const float* x, int ldx,
         PVS_CHECK_HIP(hipFuncSetAttribute((const void*)k_linear,
                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     int blocks = grid_for(N, NB * 4);
+    PvsProfScope prof(s, PVS_PROF_LIN_GENERIC);
     k_linear<<<blocks, kThreads, lds, s>>>(y, ldy, x, ldx, W, swc, swk, b, x2, ldx2, W2, swc2, swk2,
                                            N, K, K2, C, accumulate ? 1 : 0, NB);
     PVS_CHECK_LAUNCH();
@@ -1201,6 +1207,7 @@ int pvs_launch_tsgemm_tn(hipStream_t s, float* out, int ldo, const float* A, int
         if (blocks > kMaxBlocks) blocks = kMaxBlocks;
         if (blocks < 1) blocks = 1;
         const int rpb = rows_per_block_for(N, blocks);
+        PvsProfScope prof(s, PVS_PROF_TS_WIDE);
         for (int c0 = 0; c0 < C; c0 += 64)
             for (int k0 = 0; k0 < K; k0 += 64) {
                 k_tsgemm_mfma<2, 2><<<blocks, kThreads, 0, s>>>(slabs, A + c0, lda, B + k0, ldb, N, rpb, 64);
@@ -1215,6 +1222,7 @@ int pvs_launch_tsgemm_tn(hipStream_t s, float* out, int ldo, const float* A, int
         // product of its own (hidden sizes above 64 on the decomposed layer path; A is re-read per chunk)
         const int kc = (32 * kThreads / C) & ~3;
         PVS_REQUIRE(kc >= 4, "tsgemm: %d x %d outputs unsupported", C, K);
+        PvsProfScope prof(s, PVS_PROF_TS_COLCHUNK);
         for (int k0 = 0; k0 < K; k0 += kc) {
             const int rc = pvs_launch_tsgemm_tn(s, out + k0, ldo, A, lda, B + k0, ldb, N, C, K - k0 < kc ? K - k0 : kc,
                                                 slabs, accumulate);
@@ -1226,6 +1234,7 @@ int pvs_launch_tsgemm_tn(hipStream_t s, float* out, int ldo, const float* A, int
     const int rpb = rows_per_block_for(N, blocks);
     if (C % 32 == 0 && K % 32 == 0 && C <= 64 && K <= 64) {
         const int cb = C / 32, kb = K / 32;
+        PvsProfScope prof(s, PVS_PROF_TS_MFMA);
         if (cb == 1 && kb == 1) k_tsgemm_mfma<1, 1><<<blocks, kThreads, 0, s>>>(slabs, A, lda, B, ldb, N, rpb, K);
         else if (cb == 1 && kb == 2) k_tsgemm_mfma<1, 2><<<blocks, kThreads, 0, s>>>(slabs, A, lda, B, ldb, N, rpb, K);
         else if (cb == 2 && kb == 1) k_tsgemm_mfma<2, 1><<<blocks, kThreads, 0, s>>>(slabs, A, lda, B, ldb, N, rpb, K);
@@ -1237,6 +1246,7 @@ int pvs_launch_tsgemm_tn(hipStream_t s, float* out, int ldo, const float* A, int
         // narrow right operand (the input embedding: K = 12 atom features): zero-padded to one
         // 32-column MFMA block; the slabs keep the padded [C][32] layout, the reduction skips the pad
         const int ones = colsum_out ? 1 : 0;      // (column K of the padded right operand = 1: column sums of A for free)
+        PvsProfScope prof(s, PVS_PROF_TS_NARROW);
         if (C == 32) k_tsgemm_mfma<1, 1><<<blocks, kThreads, 0, s>>>(slabs, A, lda, B, ldb, N, rpb, K, ones);
         else k_tsgemm_mfma<2, 1><<<blocks, kThreads, 0, s>>>(slabs, A, lda, B, ldb, N, rpb, K, ones);
         PVS_CHECK_LAUNCH();
@@ -1246,6 +1256,7 @@ int pvs_launch_tsgemm_tn(hipStream_t s, float* out, int ldo, const float* A, int
         return 0;
     }
     size_t lds = (size_t)16 * (C + K) * sizeof(float);
+    PvsProfScope prof(s, CK <= 8 * kThreads ? PVS_PROF_TS_TN8 : PVS_PROF_TS_TN32);
     if (CK <= 8 * kThreads)
         k_tsgemm_tn<8><<<blocks, kThreads, lds, s>>>(slabs, A, lda, B, ldb, N, C, K, rpb);
     else
@@ -1309,6 +1320,7 @@ int pvs_launch_colreduce(hipStream_t s, int mode, float* out, const float* A, in
                          bool accumulate) {
     PVS_REQUIRE(C >= 1, "colreduce: width %d unsupported", C);
     if (C > kThreads) {      // one thread per column: wider inputs in chunks of 256 columns (the slabs are reused in stream order)
+        PvsProfScope prof(s, PVS_PROF_COLREDUCE_CHUNK);
         for (int c0 = 0; c0 < C; c0 += kThreads) {
             const int rc = pvs_launch_colreduce(s, mode, out + c0, A + c0, lda, B ? B + c0 : nullptr, ldb,
                                                 shift ? shift + c0 : nullptr, N, C - c0 < kThreads ? C - c0 : kThreads,
@@ -1321,6 +1333,7 @@ int pvs_launch_colreduce(hipStream_t s, int mode, float* out, const float* A, in
     const int rpb = rows_per_block_for(N, blocks);
     const bool vec4 = C % 4 == 0 && lda % 4 == 0 && (B == nullptr || ldb % 4 == 0) &&
                       (((uintptr_t)A | (uintptr_t)B | (uintptr_t)shift | (uintptr_t)slabs) & 15) == 0;
+    PvsProfScope prof(s, vec4 ? PVS_PROF_COLREDUCE4 : PVS_PROF_COLREDUCE);
     if (vec4) k_colreduce4<<<blocks, kThreads, 0, s>>>(mode, slabs, A, lda, B, ldb, shift, N, C, rpb);
     else k_colreduce<<<blocks, kThreads, 0, s>>>(mode, slabs, A, lda, B, ldb, shift, N, C, rpb);
     PVS_CHECK_LAUNCH();

@@ -7,10 +7,13 @@
 namespace {
 struct Rec { int id; hipEvent_t a, b; };
 std::mutex g_mu;
-unsigned g_mask = 0;      // bit 0: every category; bit (id + 1): category id
+unsigned g_mask = 0;      // bit 0: every kernel-group category (id < PVS_PROF_DENSE_FIRST); bit (id + 1): category id
 std::vector<Rec*> g_recs;
 const char* kNames[PVS_PROF_COUNT] = {"edge_fwd", "edge_bwd", "col_gather", "graph_prepare", "edge_fwd_partial",
-                                      "mask_graph"};
+                                      "mask_graph",
+                                      "linear_mfma", "linear_chunk64", "linear_chunk256", "linear_generic",
+                                      "tsgemm_mfma", "tsgemm_wide", "tsgemm_colchunk", "tsgemm_narrow", "tsgemm_tn8",
+                                      "tsgemm_tn32", "colreduce4", "colreduce", "colreduce_chunk"};
 thread_local int t_fwd_tag = PVS_PROF_EDGE_FWD;
 }  // namespace
 
@@ -18,7 +21,7 @@ void pvs_prof_set_fwd_tag(int id) { t_fwd_tag = id; }
 int pvs_prof_fwd_tag() { return t_fwd_tag; }
 
 PvsProfScope::PvsProfScope(hipStream_t stream, int id) : s(stream), rec(nullptr) {
-    if (!((g_mask & 1u) || ((g_mask >> (id + 1)) & 1u))) return;
+    if (!(((g_mask & 1u) && id < PVS_PROF_DENSE_FIRST) || ((g_mask >> (id + 1)) & 1u))) return;
     Rec* r = new Rec{id, nullptr, nullptr};
     if (hipEventCreate(&r->a) != hipSuccess || hipEventCreate(&r->b) != hipSuccess) { delete r; return; }
     (void)hipEventRecord(r->a, s);

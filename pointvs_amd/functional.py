@@ -543,6 +543,8 @@ class _MeanPoolFn(torch.autograd.Function):
 
 
 def mean_pool(h, graph_ptr):
+    """Mean of the rows [graph_ptr[g], graph_ptr[g + 1]) per graph (an empty graph gives zeros); a row outside
+    [graph_ptr[0], graph_ptr[-1]) belongs to no graph: the forward ignores it, the backward gives it a zero gradient."""
     return _MeanPoolFn.apply(h, graph_ptr)
 
 
