@@ -29,6 +29,12 @@ void pvs_set_error(const char* fmt, ...);
         }                                     \
     } while (0)
 
+#define PVS_TRY(...)                \
+    do {                            \
+        int _rc = (__VA_ARGS__);    \
+        if (_rc) return _rc;        \
+    } while (0)
+
 static inline size_t pvs_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // 16-byte store / load of data that is written once and read once by a later kernel (per-edge

@@ -683,7 +683,7 @@ k_edge_bwd_f16(PvsGraph g, PvsEdgeW w, uint32_t flags, int att_act, PvsEdgeBwdIO
 
 }  // namespace
 
-// Same contract as pvs_launch_edge_bwd_mfma (edge_mfma.hip). H = 32 only.
+// The MFMA backward contract of edge_kernels.h. H = 32 only.
 int pvs_launch_edge_bwd_f16(hipStream_t s, int H, const PvsGraph& g, const PvsEdgeW& w, uint32_t flags, int att_act,
                             const PvsEdgeBwdIO& io, int e_lo, int e_hi, int* n_slabs) {
     PVS_REQUIRE(w.n_attr <= 3, "MFMA edge backward supports up to 3 edge classes (got %d)", w.n_attr);
@@ -692,53 +692,26 @@ int pvs_launch_edge_bwd_f16(hipStream_t s, int H, const PvsGraph& g, const PvsEd
     if (e_hi <= e_lo) return 0;
     using Cfg = F16Cfg;
     constexpr int nw = Cfg::kWavesPerBlock;
-    int blocks, n_chunks;
-    {
-        const int E = e_hi - e_lo;
-        const long long per = pvs_edges_per_wave();
-        long long b = ((long long)E + (long long)nw * per - 1) / ((long long)nw * per);   // fill the chip first
-        if (b < 1) b = 1;
-        if (b > 256) b = 256;                      // one workgroup per CU (LDS)
-        const long long waves = b * nw;
-        const long long ce = pvs_chunk_edges(8192);     // (one chunk per wave at cfg2: edge_mfma_common.h)
-        long long per_wave = ((long long)E + waves * ce - 1) / (waves * ce);
-        if (per_wave < 1) per_wave = 1;
-        blocks = (int)b;
-        n_chunks = (int)(waves * per_wave);
-    }
-    *n_slabs = blocks;
+    // (chunks of 8192 edges: one chunk per wave at cfg2, pvs_chunk_edges)
+    const PvsEdgeGrid grid = pvs_edge_grid(e_hi - e_lo, nw, kPvsBwdF16MaxBlocks, pvs_edges_per_wave(), pvs_chunk_edges(8192));
+    PVS_TRY(pvs_report_slabs(grid.blocks, n_slabs));
     PvsProfScope prof(s, PVS_PROF_EDGE_BWD);
     const PvsSlabLayout L = pvs_slab_layout(kH);
     size_t lds = (size_t)Cfg::kSharedBytes + (size_t)nw * Cfg::kWaveBytes;
     if (lds < (size_t)L.total * 4) lds = (size_t)L.total * 4;
-    const bool eres = (flags & PVS_EDGE_RESIDUAL) && io.m_prev != nullptr;
-    const bool eatt = flags & PVS_EDGE_ATTENTION;
-#define PVS_BWD_F16_LAUNCH(ER, EA)                                                                          \
-    do {                                                                                                   \
-        if (set_lds(k_edge_bwd_f16<ER, EA>, lds)) return -2;                                               \
-        k_edge_bwd_f16<ER, EA><<<blocks, Cfg::kThreadsPerBlock, lds, s>>>(g, w, flags, att_act, io, n_chunks, \
-                                                                          e_lo, e_hi);                   \
-    } while (0)
-    // (as the reference orders them: rezero wins over gated, egnn_satorras.py:194-202)
-    const bool rezero = flags & PVS_REZERO, gated = !rezero && (flags & PVS_GATED_RESIDUAL);
-    if (eres && rezero && eatt) PVS_BWD_F16_LAUNCH(2, true);
-    else if (eres && rezero) PVS_BWD_F16_LAUNCH(2, false);
-    else if (eres && gated && eatt) PVS_BWD_F16_LAUNCH(3, true);
-    // Gated residual without attention runs the COMPILE-TIME kind 3 since round 6. Until then it ran kind 4 (the kind read
-    // from the flags at run time: 11 spilled VGPRs against 13) - and kind 4 with BOTH the lazy scales and
-    // the pair arithmetic compiled in gave g_z2-derived outputs (g_h, g_x, the edge_mlp gradients) that were 1e-3 ... 1e-1 off
-    // and changed from run to run, while g_m_prev and the coordinate branch stayed right; either feature off, or kind 3,
-    // and it is bit-reproducible and within 1e-6 of the exact family (profiles/r06_gated_residual_backward_defect.txt:
-    // found by fuzz seed 116; no golden case ran that instantiation on more than a few tiles). The cause inside the
-    // instantiation was not found (no asm-related hazard in its ISA, spills outside the tile loop); the kind-4 code path is
-    // no longer instantiated. tools/backward_instantiations_probe.py and the GPU test of the same name run all 24
-    // instantiations of the H = 32 / 64 backward twice on a multi-tile graph.
-    else if (eres && gated) PVS_BWD_F16_LAUNCH(3, false);
-    else if (eres && eatt) PVS_BWD_F16_LAUNCH(1, true);
-    else if (eres) PVS_BWD_F16_LAUNCH(1, false);
-    else if (eatt) PVS_BWD_F16_LAUNCH(0, true);
-    else PVS_BWD_F16_LAUNCH(0, false);
-#undef PVS_BWD_F16_LAUNCH
-    PVS_CHECK_LAUNCH();
-    return 0;
+    // ERK = the residual kind itself: 0 none, 1 sum, 2 rezero, 3 gated, all COMPILE-TIME. Until round 6 gated residual
+    // without attention ran kind 4 (the kind read from the flags at run time: 11 spilled VGPRs against 13) - and kind 4 with
+    // BOTH the lazy scales and the pair arithmetic compiled in gave g_z2-derived outputs that were 1e-3 ... 1e-1 off and
+    // changed from run to run; either feature off, or kind 3, and it is bit-reproducible and within 1e-6 of the exact
+    // family (profiles/r06_gated_residual_backward_defect.txt). The cause inside the instantiation was not found; the kind-4
+    // code path is no longer instantiated. tools/backward_instantiations_probe.py and the GPU test of the same name run all
+    // 24 instantiations of the H = 32 / 64 backward twice on a multi-tile graph.
+    const int erk = pvs_edge_residual_kind(flags, io.m_prev != nullptr);
+    return pvs_dispatch<4>(erk, (flags & PVS_EDGE_ATTENTION) != 0, [&](auto ERK, auto EATT) {
+        auto kernel = k_edge_bwd_f16<decltype(ERK)::value, decltype(EATT)::value>;
+        if (set_lds(kernel, lds)) return -2;
+        kernel<<<grid.blocks, Cfg::kThreadsPerBlock, lds, s>>>(g, w, flags, att_act, io, grid.n_chunks, e_lo, e_hi);
+        PVS_CHECK_LAUNCH();
+        return 0;
+    });
 }

@@ -899,46 +899,26 @@ k_edge_bwd_h64(PvsGraph g, PvsEdgeW w, uint32_t flags, int att_act, PvsEdgeBwdIO
 
 }  // namespace
 
-// Same contract as pvs_launch_edge_bwd_mfma (edge_mfma.hip), H = 64 only.
+// The MFMA backward contract of edge_kernels.h, H = 64 only.
 int pvs_launch_edge_bwd_h64(hipStream_t s, const PvsGraph& g, const PvsEdgeW& w, uint32_t flags, int att_act,
                             const PvsEdgeBwdIO& io, int e_lo, int e_hi, int* n_slabs) {
     PVS_REQUIRE(w.n_attr <= 3, "MFMA edge backward supports up to 3 edge classes (got %d)", w.n_attr);
     *n_slabs = 0;
     if (e_hi <= e_lo) return 0;
     constexpr int nw = 4;
-    int blocks, n_chunks;
-    {
-        const int E = e_hi - e_lo;
-        const long long per = pvs_edges_per_wave();
-        long long b = ((long long)E + (long long)nw * per - 1) / ((long long)nw * per);   // fill the chip first
-        if (b < 1) b = 1;
-        if (b > 256) b = 256;                      // one workgroup per CU (registers: one wave per SIMD)
-        const long long waves = b * nw;
-        long long per_wave = ((long long)E + waves * 4096 - 1) / (waves * 4096);
-        if (per_wave < 1) per_wave = 1;
-        blocks = (int)b;
-        n_chunks = (int)(waves * per_wave);
-    }
-    *n_slabs = blocks;
+    const PvsEdgeGrid grid = pvs_edge_grid(e_hi - e_lo, nw, kPvsBwdH64MaxBlocks, pvs_edges_per_wave(), 4096);
+    PVS_TRY(pvs_report_slabs(grid.blocks, n_slabs));
     PvsProfScope prof(s, PVS_PROF_EDGE_BWD);
     const PvsSlabLayout L = pvs_slab_layout(kH);
     size_t lds = (size_t)kSharedBytes64 + (size_t)nw * kWaveBytes64;
     if (lds < (size_t)L.total * 4) lds = (size_t)L.total * 4;
-    const bool eres = (flags & PVS_EDGE_RESIDUAL) && io.m_prev != nullptr;
-    const bool eatt = flags & PVS_EDGE_ATTENTION;
-#define PVS_BWD_H64_LAUNCH(ER, EA)                                                                      \
-    do {                                                                                               \
-        if (set_lds(k_edge_bwd_h64<ER, EA>, lds)) return -2;                                           \
-        k_edge_bwd_h64<ER, EA><<<blocks, 256, lds, s>>>(g, w, flags, att_act, io, n_chunks, e_lo, e_hi); \
-    } while (0)
-    const bool gated = flags & (PVS_REZERO | PVS_GATED_RESIDUAL);
-    if (eres && gated && eatt) PVS_BWD_H64_LAUNCH(2, true);
-    else if (eres && gated) PVS_BWD_H64_LAUNCH(2, false);
-    else if (eres && eatt) PVS_BWD_H64_LAUNCH(1, true);
-    else if (eres) PVS_BWD_H64_LAUNCH(1, false);
-    else if (eatt) PVS_BWD_H64_LAUNCH(0, true);
-    else PVS_BWD_H64_LAUNCH(0, false);
-#undef PVS_BWD_H64_LAUNCH
-    PVS_CHECK_LAUNCH();
-    return 0;
+    const PvsEdgeResidual res = pvs_edge_residual_kind(flags, io.m_prev != nullptr);
+    const int erk = res == PVS_ERES_GATED ? 2 : (int)res;      // ERK: 0 none, 1 sum, 2 rezero / gated
+    return pvs_dispatch<3>(erk, (flags & PVS_EDGE_ATTENTION) != 0, [&](auto ERK, auto EATT) {
+        auto kernel = k_edge_bwd_h64<decltype(ERK)::value, decltype(EATT)::value>;
+        if (set_lds(kernel, lds)) return -2;
+        kernel<<<grid.blocks, 256, lds, s>>>(g, w, flags, att_act, io, grid.n_chunks, e_lo, e_hi);
+        PVS_CHECK_LAUNCH();
+        return 0;
+    });
 }

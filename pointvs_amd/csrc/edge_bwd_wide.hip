@@ -703,38 +703,24 @@ int launch_wide(hipStream_t s, const PvsGraph& g, const PvsEdgeW& w, uint32_t fl
     const PvsSlabLayout L = pvs_slab_layout(H);
     size_t lds = Cfg::kBytes;
     if (lds < (size_t)L.total * 4) lds = (size_t)L.total * 4;
-    const int per_cu = (int)((160 * 1024) / lds) > 0 ? (int)((160 * 1024) / lds) : 1;     // teams resident per CU
-    const int E = e_hi - e_lo;
-    long long b = ((long long)E + 511) / 512;          // fill the chip first: >= 16 tiles per team
-    if (b < 1) b = 1;
-    if (b > 256LL * per_cu) b = 256LL * per_cu;
-    long long per_team = ((long long)E + b * 4096 - 1) / (b * 4096);
-    if (per_team < 1) per_team = 1;
-    const int blocks = (int)b, n_chunks = (int)(b * per_team);
-    *n_slabs = blocks;
+    // fill the chip first: >= 16 tiles per team (a team is the unit the planner calls a wave), one team resident per CU
+    static_assert(2 * Cfg::kBytes > 160 * 1024, "two teams fit a CU: kPvsBwdWideMaxBlocks (and the slab capacity) can double");
+    const PvsEdgeGrid grid = pvs_edge_grid(e_hi - e_lo, 1, kPvsBwdWideMaxBlocks, 512, 4096);
+    PVS_TRY(pvs_report_slabs(grid.blocks, n_slabs));
     PvsProfScope prof(s, PVS_PROF_EDGE_BWD);
-    const bool eres = (flags & PVS_EDGE_RESIDUAL) && io.m_prev != nullptr;
-    const bool eatt = flags & PVS_EDGE_ATTENTION;
-#define PVS_BWD_WIDE_LAUNCH(ER, EA)                                                                            \
-    do {                                                                                                      \
-        if (set_lds(k_edge_bwd_wide<HB, ER, EA>, lds)) return -2;                                             \
-        k_edge_bwd_wide<HB, ER, EA><<<blocks, Cfg::kThreads, lds, s>>>(g, w, flags, att_act, io, n_chunks, e_lo, \
-                                                                       e_hi, wglob);                        \
-    } while (0)
-    const bool gated = flags & (PVS_REZERO | PVS_GATED_RESIDUAL);
-    if (eres && gated && eatt) PVS_BWD_WIDE_LAUNCH(2, true);
-    else if (eres && gated) PVS_BWD_WIDE_LAUNCH(2, false);
-    else if (eres && eatt) PVS_BWD_WIDE_LAUNCH(1, true);
-    else if (eres) PVS_BWD_WIDE_LAUNCH(1, false);
-    else if (eatt) PVS_BWD_WIDE_LAUNCH(0, true);
-    else PVS_BWD_WIDE_LAUNCH(0, false);
-#undef PVS_BWD_WIDE_LAUNCH
-    PVS_CHECK_LAUNCH();
-    return 0;
+    const PvsEdgeResidual res = pvs_edge_residual_kind(flags, io.m_prev != nullptr);
+    const int erk = res == PVS_ERES_GATED ? 2 : (int)res;      // ERK: 0 none, 1 sum, 2 rezero / gated
+    return pvs_dispatch<3>(erk, (flags & PVS_EDGE_ATTENTION) != 0, [&](auto ERK, auto EATT) {
+        auto kernel = k_edge_bwd_wide<HB, decltype(ERK)::value, decltype(EATT)::value>;
+        if (set_lds(kernel, lds)) return -2;
+        kernel<<<grid.blocks, Cfg::kThreads, lds, s>>>(g, w, flags, att_act, io, grid.n_chunks, e_lo, e_hi, wglob);
+        PVS_CHECK_LAUNCH();
+        return 0;
+    });
 }
 }  // namespace
 
-// Same contract as pvs_launch_edge_bwd_mfma (edge_mfma.hip). H = 128; io.wpair: pvs_edge_bwd_wide_scratch_floats()
+// The MFMA backward contract of edge_kernels.h. H = 128; io.wpair: pvs_edge_bwd_wide_scratch_floats()
 // floats of scratch. (The kernel is written for H = 32 HB; its HB = 2 form - two waves per tile, both weight matrices in
 // LDS, two teams per CU - is correct, 138 GPU tests, but 50 % slower than the one-wave-per-16-edge-tile kernel of
 // edge_bwd_h64.hip at cfg3: 1.51 against 1.01 ms per launch, profiles/r03_ab_h64_team_f16_rejected.txt. Not built.)

@@ -1,6 +1,7 @@
 // Per-edge kernels of the EGNN layer (internal interface between layer_api.hip and the kernels).
 #pragma once
 #include "common.h"
+#include "edge_dispatch.h"
 
 // Pointers the edge kernels need, by value in the kernel arguments.
 struct PvsEdgeW {
@@ -72,13 +73,21 @@ __host__ __device__ static inline PvsSlabLayout pvs_slab_layout(int H) {
     return L;
 }
 
-int pvs_edge_mfma_supported(int H, uint32_t flags);
-int pvs_launch_edge_fwd_mfma(hipStream_t s, int H, const PvsGraph& g, const PvsEdgeW& w, uint32_t flags,
+// MFMA edge forward of the family `fam` (split, exact or wide: pvs_edge_family, edge_dispatch.h)
+int pvs_launch_edge_fwd_mfma(hipStream_t s, int H, PvsEdgeFamily fam, const PvsGraph& g, const PvsEdgeW& w, uint32_t flags,
                              int att_act, const PvsEdgeFwdIO& io);
-int pvs_edge_bwd_mfma_supported(int H, uint32_t flags, int n_attr);
-int pvs_edge_bwd_mfma_max_blocks(int H);
-int pvs_launch_edge_bwd_mfma(hipStream_t s, int H, const PvsGraph& g, const PvsEdgeW& w, uint32_t flags,
-                             int att_act, const PvsEdgeBwdIO& io, int e_lo, int e_hi, int* n_slabs);
+// The MFMA edge backward launchers share one contract: the CSR edge range [e_lo, e_hi) (row-aligned: the whole batch or
+// one segment of whole graphs); gPQ's row part and gx_row zeroed by the caller (rows without edges are never written);
+// *n_slabs (<= kPvsEdgeSlabCapacity) per-block weight-gradient partials at io.slabs. layer_api.hip picks one by family.
+static inline int pvs_report_slabs(int blocks, int* n_slabs) {
+    PVS_REQUIRE(blocks <= kPvsEdgeSlabCapacity, "edge backward: %d workgroups for %d weight-gradient slabs", blocks,
+                kPvsEdgeSlabCapacity);
+    *n_slabs = blocks;
+    return 0;
+}
+// Exact fp32 MFMAs, H = 32 / 64 / 128 (edge_mfma.hip): the cross-check family; H = 128: io.wpair = 2 H H floats of scratch
+int pvs_launch_edge_bwd_exact(hipStream_t s, int H, const PvsGraph& g, const PvsEdgeW& w, uint32_t flags, int att_act,
+                              const PvsEdgeBwdIO& io, int e_lo, int e_hi, int* n_slabs);
 // H = 32 backward with every product as three fp16 terms (f16x2 split with tile scales), both weight-gradient
 // operands through transposing LDS reads (edge_bwd_f16.hip, round 3); same contract
 int pvs_launch_edge_bwd_f16(hipStream_t s, int H, const PvsGraph& g, const PvsEdgeW& w, uint32_t flags, int att_act,

@@ -992,142 +992,53 @@ __global__ void k_stage_weight_pair(const float* __restrict__ W, int H, float* _
 
 }  // namespace
 
-int pvs_edge_bwd_mfma_max_blocks(int H) { (void)H; return 512; }
-
-// Edge backward over the CSR edge range [e_lo, e_hi) (row-aligned: the whole batch or one segment
-// of whole graphs). gPQ's row part and gx_row must have been zeroed by the caller (rows without
-// edges are never written). Writes *n_slabs per-block weight-gradient partials at io.slabs.
-int pvs_launch_edge_bwd_mfma(hipStream_t s, int H, const PvsGraph& g, const PvsEdgeW& w, uint32_t flags,
-                             int att_act, const PvsEdgeBwdIO& io, int e_lo, int e_hi, int* n_slabs) {
+// The MFMA backward contract of edge_kernels.h with every product as an exact fp32 MFMA (v_mfma_f32_32x32x2_f32): the
+// arithmetic cross-check family of the tests (PVS_EGNN_BF16X3=0; tests/test_gpu_properties.py). H = 32: one wave per tile;
+// H = 64: one team of 2 waves per 128-thread block, two blocks per CU - one wave per SIMD with the whole register file;
+// H = 128 (the wide layer): one team of 4 waves per 256-thread block, one block per CU, W2 in LDS and Wc1 in both
+// orientations from global memory (two fp32 128x128 matrices do not fit beside the team's 51 KB of tiles).
+int pvs_launch_edge_bwd_exact(hipStream_t s, int H, const PvsGraph& g, const PvsEdgeW& w, uint32_t flags, int att_act,
+                              const PvsEdgeBwdIO& io, int e_lo, int e_hi, int* n_slabs) {
     PVS_REQUIRE(w.n_attr <= 3, "MFMA edge backward supports up to 3 edge classes (got %d)", w.n_attr);
     PVS_REQUIRE(H == 32 || H == 64 || H == 128, "MFMA edge backward is built for H = 32, 64, 128 (got %d)", H);
     *n_slabs = 0;
     if (e_hi <= e_lo) return 0;
-    if (H == 128) {
-        // The wide layer (64 < hidden <= 128, padded to 128). Default: the four-wave team on three-term fp16 products
-        // (edge_bwd_wide.hip). PVS_EGNN_BF16X3=0: the same team layout on exact fp32 MFMAs - the cross-check family -
-        // with W2 in LDS and Wc1 in both orientations from global memory (two fp32 128x128 matrices do not fit beside
-        // the team's 51 KB of tiles). One team per 256-thread block, one block per CU.
-        {
-            const char* bfw = getenv("PVS_EGNN_BF16X3");
-            if (!(bfw && bfw[0] == '0'))
-                return pvs_launch_edge_bwd_wide(s, H, g, w, flags, att_act, io, e_lo, e_hi, n_slabs);
-        }
+    const int E = e_hi - e_lo, HB = H / 32;
+    if (HB == 4) {
         PVS_REQUIRE(io.wpair, "H = 128 edge backward needs the weight-pair scratch");
-        const bool upd = (flags & PVS_UPDATE_COORDS) && io.gxagg != nullptr;
-        if (upd) {
+        if ((flags & PVS_UPDATE_COORDS) && io.gxagg != nullptr) {
             k_stage_weight_pair<<<64, 256, 0, s>>>(w.wc1, H, io.wpair);
             PVS_CHECK_LAUNCH();
         }
-        const int E = e_hi - e_lo;
-        long long b = ((long long)E + 511) / 512;
-        if (b < 1) b = 1;
-        if (b > 256) b = 256;
-        long long per_team = ((long long)E + b * 4096 - 1) / (b * 4096);
-        if (per_team < 1) per_team = 1;
-        const int blocks = (int)b, n_chunks = (int)(b * per_team);
-        *n_slabs = blocks;
-        PvsProfScope prof(s, PVS_PROF_EDGE_BWD);
-        const PvsSlabLayout L = pvs_slab_layout(H);
-        size_t tw = (size_t)H * (H + 1) + (5 + PVS_MAX_EDGE_ATTR) * H + 16 +
-                    (size_t)(3 * kTile * (H + 4) + kTile * 4 + 2 * kTile + 2 * 4 * kTile);
-        if (tw < (size_t)L.total) tw = L.total;
-        const size_t tlds = tw * sizeof(float);
-        const bool eres = (flags & PVS_EDGE_RESIDUAL) && io.m_prev != nullptr;
-        const bool eatt = flags & PVS_EDGE_ATTENTION;
-#define PVS_WIDE_LAUNCH(ER, EA)                                                                    \
-    do {                                                                                          \
-        if (set_lds(k_edge_bwd_team<4, ER, EA>, tlds)) return -2;                          \
-        k_edge_bwd_team<4, ER, EA><<<blocks, 256, tlds, s>>>(g, w, flags, att_act, io, n_chunks, e_lo, e_hi, io.wpair); \
-    } while (0)
-        if (eres && eatt) PVS_WIDE_LAUNCH(true, true);
-        else if (eres) PVS_WIDE_LAUNCH(true, false);
-        else if (eatt) PVS_WIDE_LAUNCH(false, true);
-        else PVS_WIDE_LAUNCH(false, false);
-#undef PVS_WIDE_LAUNCH
+    }
+    // (the team kernels: one team per block, >= 16 tiles per team)
+    const PvsEdgeGrid grid = HB == 1   ? pvs_edge_grid(E, kWaves, kPvsBwdExactMaxBlocks, pvs_edges_per_wave(), 4096)
+                             : HB == 2 ? pvs_edge_grid(E, 1, kPvsBwdExactMaxBlocks, 512, 4096)
+                                       : pvs_edge_grid(E, 1, kPvsBwdExactWideMaxBlocks, 512, 4096);
+    PVS_TRY(pvs_report_slabs(grid.blocks, n_slabs));
+    PvsProfScope prof(s, PVS_PROF_EDGE_BWD);
+    // weights (Wc1 from global memory at H = 128), tables, per wave or team: three tiles, tx, gl, rowbuf (+ the team's
+    // lens and partial dots); the slab is reduced in the same memory
+    size_t words = HB == 1 ? (size_t)2 * H * (H + 1) + (5 + PVS_MAX_EDGE_ATTR) * H +
+                                 (size_t)kWaves * (3 * kTile * (H + 4) + kTile * 4 + 2 * kTile)
+                           : (size_t)(HB == 4 ? 1 : 2) * H * (H + 1) + (5 + PVS_MAX_EDGE_ATTR) * H + 16 +
+                                 (size_t)(3 * kTile * (H + 4) + kTile * 4 + 2 * kTile + 2 * HB * kTile);
+    if (words < (size_t)pvs_slab_layout(H).total) words = pvs_slab_layout(H).total;
+    const size_t lds = words * sizeof(float);
+    const bool eres = pvs_edge_residual_kind(flags, io.m_prev != nullptr) != PVS_ERES_NONE;      // ERES: any kind
+    return pvs_dispatch<2>(eres, (flags & PVS_EDGE_ATTENTION) != 0, [&](auto ER, auto EATT) {
+        constexpr bool ERES = decltype(ER)::value != 0, EA = decltype(EATT)::value;
+        if (HB == 1) {
+            if (set_lds(k_edge_bwd_mfma<1, ERES, EA>, lds)) return -2;
+            k_edge_bwd_mfma<1, ERES, EA><<<grid.blocks, kThreads, lds, s>>>(g, w, flags, att_act, io, grid.n_chunks, e_lo, e_hi);
+        } else if (HB == 2) {
+            if (set_lds(k_edge_bwd_team<2, ERES, EA>, lds)) return -2;
+            k_edge_bwd_team<2, ERES, EA><<<grid.blocks, 128, lds, s>>>(g, w, flags, att_act, io, grid.n_chunks, e_lo, e_hi, nullptr);
+        } else {
+            if (set_lds(k_edge_bwd_team<4, ERES, EA>, lds)) return -2;
+            k_edge_bwd_team<4, ERES, EA><<<grid.blocks, 256, lds, s>>>(g, w, flags, att_act, io, grid.n_chunks, e_lo, e_hi, io.wpair);
+        }
         PVS_CHECK_LAUNCH();
         return 0;
-    }
-    // Default: H = 32 as three-term fp16 products (edge_bwd_f16.hip), H = 64 as one wave per 16-edge tile with
-    // six-term bf16 products (edge_bwd_h64.hip). PVS_EGNN_BF16X3=0: every product as an exact fp32 MFMA
-    // (v_mfma_f32_32x32x2_f32) - the kernels below, kept as the arithmetic cross-check family of the tests
-    // (tests/test_gpu_properties.py); the round-1/2 split kernels they replaced are gone from the library.
-    const char* bf = getenv("PVS_EGNN_BF16X3");
-    const char* bf64 = getenv("PVS_EGNN_BF16X3_H64");       // (=0: the fp32 family for H = 64 only)
-    if (!(bf && bf[0] == '0') && (H == 32 || !(bf64 && bf64[0] == '0'))) {
-        if (H == 32) return pvs_launch_edge_bwd_f16(s, H, g, w, flags, att_act, io, e_lo, e_hi, n_slabs);
-        return pvs_launch_edge_bwd_h64(s, g, w, flags, att_act, io, e_lo, e_hi, n_slabs);
-    }
-    const int nt = kThreads, nw = nt / 64;
-    int blocks, n_chunks;
-    {
-        const int E = e_hi - e_lo;
-        const int max_blocks = pvs_edge_bwd_mfma_max_blocks(H);       // H = 32: 2 x 256 threads per CU
-        const long long per = pvs_edges_per_wave();
-        long long b = ((long long)E + (long long)nw * per - 1) / ((long long)nw * per);   // fill the chip first
-        if (b < 1) b = 1;
-        if (b > max_blocks) b = max_blocks;
-        const long long waves = b * nw;
-        long long per_wave = ((long long)E + waves * 4096 - 1) / (waves * 4096);
-        if (per_wave < 1) per_wave = 1;
-        blocks = (int)b;
-        n_chunks = (int)(waves * per_wave);
-    }
-    *n_slabs = blocks;
-    PvsProfScope prof(s, PVS_PROF_EDGE_BWD);
-    const PvsSlabLayout L = pvs_slab_layout(H);
-    size_t words = (size_t)2 * H * (H + 1) + (5 + PVS_MAX_EDGE_ATTR) * H +
-                   (size_t)nw * (3 * kTile * (H + 4) + kTile * 4 + 2 * kTile);
-    if (words < (size_t)L.total) words = L.total;
-    const size_t lds = words * sizeof(float);
-    const bool eres = (flags & PVS_EDGE_RESIDUAL) && io.m_prev != nullptr;
-    const bool eatt = flags & PVS_EDGE_ATTENTION;
-    if (H == 32) {
-#define PVS_BWD_LAUNCH(ER, EA)                                                                      \
-    do {                                                                                           \
-        if (set_lds(k_edge_bwd_mfma<1, ER, EA>, lds)) return -2;                            \
-        k_edge_bwd_mfma<1, ER, EA><<<blocks, nt, lds, s>>>(g, w, flags, att_act, io, n_chunks, e_lo, e_hi); \
-    } while (0)
-        if (eres && eatt) PVS_BWD_LAUNCH(true, true);
-        else if (eres) PVS_BWD_LAUNCH(true, false);
-        else if (eatt) PVS_BWD_LAUNCH(false, true);
-        else PVS_BWD_LAUNCH(false, false);
-#undef PVS_BWD_LAUNCH
-    } else {
-        // team kernel: one team of 2 waves per 128-thread block, two blocks per CU: one wave per SIMD
-        // with the whole register file
-        constexpr int kTeams = 1;
-        const int E = e_hi - e_lo;
-        long long b = ((long long)E + 511) / 512;
-        if (b < 1) b = 1;
-        if (b > 512) b = 512;
-        const long long teams = b * kTeams;
-        long long per_team = ((long long)E + teams * 4096 - 1) / (teams * 4096);
-        if (per_team < 1) per_team = 1;
-        blocks = (int)b;
-        n_chunks = (int)(teams * per_team);
-        *n_slabs = blocks;
-        size_t tw = (size_t)2 * H * (H + 1) + (5 + PVS_MAX_EDGE_ATTR) * H + 16 +
-                    (size_t)kTeams * (3 * kTile * (H + 4) + kTile * 4 + 2 * kTile + 2 * 2 * kTile);
-        if (tw < (size_t)L.total) tw = L.total;
-        const size_t tlds = tw * sizeof(float);
-#define PVS_TEAM_LAUNCH(ER, EA)                                                                    \
-    do {                                                                                          \
-        if (set_lds(k_edge_bwd_team<2, ER, EA>, tlds)) return -2;                          \
-        k_edge_bwd_team<2, ER, EA><<<blocks, 128, tlds, s>>>(g, w, flags, att_act, io, n_chunks, e_lo, e_hi, nullptr); \
-    } while (0)
-        if (eres && eatt) PVS_TEAM_LAUNCH(true, true);
-        else if (eres) PVS_TEAM_LAUNCH(true, false);
-        else if (eatt) PVS_TEAM_LAUNCH(false, true);
-        else PVS_TEAM_LAUNCH(false, false);
-#undef PVS_TEAM_LAUNCH
-    }
-    PVS_CHECK_LAUNCH();
-    return 0;
-}
-
-int pvs_edge_bwd_mfma_supported(int H, uint32_t flags, int n_attr) {
-    if ((H != 32 && H != 64 && H != 128) || n_attr > 3) return 0;
-    (void)flags;
-    return 1;
+    });
 }

@@ -17,9 +17,11 @@ constexpr int kTile = 32;
 
 // internal: the forward writes the raw coordinate sums (no x, no 1/deg) into x_out (edge_sums)
 constexpr uint32_t kFwdRawXsum = 1u << 23;
-// Timing-only ablation switches (PVS_ABLATE env, layer_api.hip): results are wrong when set.
-constexpr uint32_t kAblNoMfma = 1u << 24, kAblNoSilu = 1u << 25, kAblNoReduce = 1u << 26,
-                   kAblNoGather = 1u << 27;
+// Dead flag bits. They were the timing-only switches of a PVS_ABLATE environment variable that is gone: no caller can
+// set them. The wave-uniform branches on them stay in the kernels (forward, exact-fp32 backward, and `n_attr & 0x100` in
+// load_tile_idx*): the compiler schedules the kernels worse without them - edge forward +1.5 % at cfg2, +0.5 % at cfg3,
+// +2.7 % at cfg5, H = 32 backward +1.6 % (profiles/edge_dispatch_refactor.txt).
+constexpr uint32_t kAblNoMfma = 1u << 24, kAblNoReduce = 1u << 26, kAblNoGather = 1u << 27;
 
 // Stage W[H][H] (row-major, W[out][in]) for  Z = W V  (transpose=false)  or  Z = W^T V  (true)
 // in A-operand order: dst[((bo*HB + bi)*16 + t)*64 + l] = Wx[32bo + (l&31)][32bi + ch(t, l>>5)].
@@ -39,7 +41,7 @@ template <int HB>
 __device__ __forceinline__ void mfma_chain(const float* __restrict__ Ws, int lane,
                                            const float (&v)[HB][16], f32x16 (&acc)[HB],
                                            bool skip = false) {
-    if (skip) {   // ablation: keep the operands live, issue no MFMA
+    if (skip) {   // (kAblNoMfma: dead, see above)
 #pragma unroll
         for (int b = 0; b < HB; ++b) acc[b][0] += v[b][0];
         return;
@@ -69,7 +71,7 @@ __device__ __forceinline__ void mfma_chain_nat(const float* __restrict__ Wn, int
                                                const float (&v)[HB][16], f32x16 (&acc)[HB],
                                                bool skip = false) {
     constexpr int H = 32 * HB, LD = H + 1;
-    if (skip) {
+    if (skip) {   // (kAblNoMfma: dead, see above)
 #pragma unroll
         for (int b = 0; b < HB; ++b) acc[b][0] += v[b][0];
         return;
@@ -185,7 +187,7 @@ __device__ __forceinline__ TileIdx load_tile_idx(const PvsGraph& g, int n_attr, 
     t.ee = min(max(t.ee, 0), g.n_edges - 1);
     t.i = g.row[t.ee];
     t.jn = g.col[t.ee];
-    if (n_attr & 0x100) { t.i &= 7; t.jn &= 7; }   // ablation: every gather hits 8 hot rows
+    if (n_attr & 0x100) { t.i &= 7; t.jn &= 7; }   // (kAblNoGather: dead, see above)
     t.ty = (n_attr & 0xff) ? (int)g.etype[t.ee] : 0;
     t.prev_row = (t.ee == e_begin || t.ee == 0) ? -1 : g.row[t.ee - 1];
     return t;
@@ -213,7 +215,7 @@ __device__ __forceinline__ TileIdx load_tile_idx32(const PvsGraph& g, int n_attr
     const unsigned o = 4u * (unsigned)t.ee;
     t.i = *pvs_off(g.row, o);
     t.jn = *pvs_off(g.col, o);
-    if (n_attr & 0x100) { t.i &= 7; t.jn &= 7; }   // ablation: every gather hits 8 hot rows
+    if (n_attr & 0x100) { t.i &= 7; t.jn &= 7; }   // (kAblNoGather: dead, see above)
     t.ty = (n_attr & 0xff) ? (int)*pvs_off(g.etype, (unsigned)t.ee) : 0;
     t.prev_row = (t.ee == e_begin || t.ee == 0) ? -1 : *pvs_off(g.row, o - 4u);
     return t;
@@ -805,40 +807,5 @@ int set_lds(K kernel, size_t lds) {
                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     return 0;
 }
-
-// Edges a wave gets before the grid grows by another workgroup. 512 until round 5 (sixteen tiles amortise a workgroup's
-// weight staging): right for BASELINE-size batches, whose grids are capped by the CU count anyway, and wrong for small ones
-// - at the reference's default shape (32 graphs of 500 atoms, r = 4 A: 176k edges) the backward ran on 43 of 256 CUs.
-// Two tiles per wave: edge forward 0.62 -> 0.20 ms, edge backward 0.81 -> 0.28 ms per 6-layer step there (32: 0.19 / 0.28;
-// profiles/r05_ab_small_batch_grid.txt). PVS_EDGES_PER_WAVE overrides it (A/B).
-inline int pvs_edges_per_wave() {
-    static const int v = [] { const char* e = getenv("PVS_EDGES_PER_WAVE"); const int x = e ? atoi(e) : 0; return x > 0 ? x : 64; }();
-    return v;
-}
-
-// Edges per chunk above which a wave's share is cut into several chunks (PVS_CHUNK_EDGES overrides it: A/B only).
-// Chunk ends are row-aligned, so a wave's share is uneven by up to a row per chunk end (157 edges at cfg2) and the launch
-// waits for the largest share: FEWER, larger chunks per wave balance better (round 6, H = 32 backward at cfg2: two chunks
-// of 2.5 k edges per wave -> one of 5 k: -2.5 % per launch; perfectly equal shares - a timing-only build - would give
-// -3.3 %: profiles/r06_ab_chunk_balance.txt).
-inline long long pvs_chunk_edges(long long dflt = 4096) {
-    static const long long v = [] { const char* e = getenv("PVS_CHUNK_EDGES"); return e ? atoll(e) : 0ll; }();
-    return v > 0 ? v : dflt;
-}
-
-void pick_grid(int E, int* blocks, int* n_chunks, int nw = kWaves, int max_blocks = 1024) {
-    // fill the chip first: a wave gets >= pvs_edges_per_wave() edges where the range allows; chunks of <= ~4096 edges; every wave gets the same number of chunks
-    const long long per = pvs_edges_per_wave();
-    long long b = ((long long)E + (long long)nw * per - 1) / ((long long)nw * per);
-    if (b < 1) b = 1;
-    if (b > max_blocks) b = max_blocks;
-    const long long waves = b * nw;
-    const long long ce = pvs_chunk_edges();
-    long long per_wave = ((long long)E + waves * ce - 1) / (waves * ce);
-    if (per_wave < 1) per_wave = 1;
-    *blocks = (int)b;
-    *n_chunks = (int)(waves * per_wave);
-}
-
 
 }  // namespace

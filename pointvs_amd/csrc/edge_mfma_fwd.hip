@@ -376,17 +376,28 @@ __global__ void k_init_fwd(float* __restrict__ Magg, const float* __restrict__ x
     if (q == 0 && raw_xsum) { x_out[3 * n] = 0.f; x_out[3 * n + 1] = 0.f; x_out[3 * n + 2] = 0.f; }
     else if (q == 0 && x) { x_out[3 * n] = x[3 * n]; x_out[3 * n + 1] = x[3 * n + 1]; x_out[3 * n + 2] = x[3 * n + 2]; }
 }
+
+// One launch of k_edge_fwd_mfma<HB, NT, SOFT, F16X2, MODE, SA32>: the softmax form and the offset width picked at run time
+// (MODE 2, the coordinate branch alone, has no attention: only its SOFT = false form exists)
+template <int HB, int NT, bool F16X2, int MODE>
+int launch_fwd(hipStream_t s, bool soft, bool sa32, PvsEdgeGrid grid, size_t lds, const PvsGraph& g, const PvsEdgeW& w,
+               uint32_t flags, int att_act, const PvsEdgeFwdIO& io) {
+    return pvs_dispatch<MODE == 2 ? 1 : 2>(soft, sa32, [&](auto SF, auto SA) {
+        auto kernel = k_edge_fwd_mfma<HB, NT, decltype(SF)::value != 0, F16X2, MODE, decltype(SA)::value>;
+        if (set_lds(kernel, lds)) return -2;
+        kernel<<<grid.blocks, NT, lds, s>>>(g, w, flags, att_act, io, grid.n_chunks, 0, g.n_edges);
+        PVS_CHECK_LAUNCH();
+        return 0;
+    });
+}
 }  // namespace
 
-int pvs_edge_mfma_supported(int H, uint32_t flags) {
-    if (H != 32 && H != 64 && H != 128) return 0;
-    return 1;
-}
-
-int pvs_launch_edge_fwd_mfma(hipStream_t s, int H, const PvsGraph& g, const PvsEdgeW& w, uint32_t flags,
+int pvs_launch_edge_fwd_mfma(hipStream_t s, int H, PvsEdgeFamily fam, const PvsGraph& g, const PvsEdgeW& w, uint32_t flags,
                              int att_act, const PvsEdgeFwdIO& io) {
     PVS_REQUIRE(w.n_attr <= PVS_MAX_EDGE_ATTR, "edge_attr classes %d > %d", w.n_attr,
                 PVS_MAX_EDGE_ATTR);
+    PVS_REQUIRE(fam == PVS_EDGE_WIDE ? H == 128 : ((fam == PVS_EDGE_SPLIT || fam == PVS_EDGE_EXACT) && (H == 32 || H == 64)),
+                "MFMA edge forward: no kernel of family %d for H = %d", (int)fam, H);
     // (32-bit byte offsets into the node tables [N, 2H] fp32 and the edge index arrays: pvs_off; beyond them the 64-bit
     // instantiation of the same kernel runs: PVS_FWD_SADDR=0 at run time forces it for the test)
     const char* sa_env = getenv("PVS_FWD_SADDR");
@@ -402,82 +413,44 @@ int pvs_launch_edge_fwd_mfma(hipStream_t s, int H, const PvsGraph& g, const PvsE
     if (g.n_edges == 0) return 0;
     PvsProfScope prof(s, pvs_prof_fwd_tag());
     const int HB = H / 32;
-    if (HB == 4) {
+    const int attr_rows = w.n_attr > 1 ? w.n_attr : 1;
+    const bool soft = (flags & PVS_EDGE_ATTENTION) && (flags & PVS_SOFTMAX_ATT);
+    if (fam == PVS_EDGE_WIDE) {
         // The wide layer (64 < hidden <= 128, padded to 128): two launches of the f16x2 kernel, one split weight matrix
         // (64 KB) in LDS each - everything but the coordinate branch, messages to m_out (or the scratch); then the
         // coordinate branch alone, reading the messages back. 256 threads, one workgroup per CU (138 KB of LDS).
         float* mbuf = io.m_out ? io.m_out : io.m_scratch;
         const bool upd = flags & PVS_UPDATE_COORDS;
         PVS_REQUIRE(mbuf || !upd, "H = 128 edge forward needs m_out or the message scratch");
-        const int attr_rows = w.n_attr > 1 ? w.n_attr : 1;
-        int blocks, n_chunks;
-        pick_grid(g.n_edges, &blocks, &n_chunks, kWaves, 256);
+        const PvsEdgeGrid grid = pvs_edge_grid(g.n_edges, kWaves, kPvsFwdLargeMaxBlocks, pvs_edges_per_wave(), pvs_chunk_edges());
         const size_t words = (size_t)16 * 4 * 64 * 4 + 4 + (5 + attr_rows) * H +
                              (size_t)kWaves * (kTile * (H + 4) + kTile * 4 + kTile);
         const size_t lds = words * sizeof(float);
-        const bool soft = (flags & PVS_EDGE_ATTENTION) && (flags & PVS_SOFTMAX_ATT);
         PvsEdgeFwdIO io1 = io;
         io1.m_out = upd ? mbuf : io.m_out;
-#define PVS_FWD_WIDE(SF, MD, SA)                                                                       \
-    do {                                                                                              \
-        if (set_lds(k_edge_fwd_mfma<4, kThreads, SF, true, MD, SA>, lds)) return -2;                  \
-        k_edge_fwd_mfma<4, kThreads, SF, true, MD, SA><<<blocks, kThreads, lds, s>>>(g, w, flags, att_act, io1, n_chunks, 0, g.n_edges); \
-    } while (0)
-        if (soft && sa32) PVS_FWD_WIDE(true, 1, true);
-        else if (soft) PVS_FWD_WIDE(true, 1, false);
-        else if (sa32) PVS_FWD_WIDE(false, 1, true);
-        else PVS_FWD_WIDE(false, 1, false);
-        PVS_CHECK_LAUNCH();
-        if (upd) {
-            if (sa32) PVS_FWD_WIDE(false, 2, true);
-            else PVS_FWD_WIDE(false, 2, false);
-            PVS_CHECK_LAUNCH();
-        }
-#undef PVS_FWD_WIDE
-        if (soft) return pvs_launch_softmax_finalize(s, g, io.smax, io.ssum, io.att_out);
-        return 0;
+        PVS_TRY(launch_fwd<4, kThreads, true, 1>(s, soft, sa32, grid, lds, g, w, flags, att_act, io1));
+        if (upd) PVS_TRY(launch_fwd<4, kThreads, true, 2>(s, false, sa32, grid, lds, g, w, flags, att_act, io1));
+    } else {
+        // split (default): the two chain products as three-term fp16 products with tile scales ("f16x2", round 3);
+        // exact: fp32 MFMAs - the cross-check family of the tests. (The six-term bf16 form of rounds 1-2 is gone from
+        // the library: same accuracy, twice the MFMAs, a dearer split.)
+        const bool f16x2 = fam == PVS_EDGE_SPLIT;
+        // H = 64: 32 KB of weight operands, one workgroup per CU: 768 threads = three waves per SIMD where the edge-class
+        // table leaves room in the 160 KB of LDS (up to 3 classes), 512 threads otherwise
+        const int nw = (HB == 2 && f16x2) ? (attr_rows <= 3 ? 12 : 8) : kWaves;
+        const PvsEdgeGrid grid = pvs_edge_grid(g.n_edges, nw, nw >= 8 ? kPvsFwdLargeMaxBlocks : kPvsFwdMaxBlocks,
+                                               pvs_edges_per_wave(), pvs_chunk_edges());
+        const size_t words = (f16x2 ? (size_t)2 * HB * HB * 4 * 64 * 4 + 4 : (size_t)2 * H * H) +
+                             (5 + attr_rows) * H +
+                             (size_t)nw * (kTile * (H + 4) + kTile * 4 + kTile);
+        const size_t lds = words * sizeof(float);
+        if (HB == 2 && f16x2 && nw == 12) PVS_TRY(launch_fwd<2, 768, true, 0>(s, soft, sa32, grid, lds, g, w, flags, att_act, io));
+        else if (HB == 2 && f16x2) PVS_TRY(launch_fwd<2, 512, true, 0>(s, soft, sa32, grid, lds, g, w, flags, att_act, io));
+        else if (HB == 1 && f16x2) PVS_TRY(launch_fwd<1, kThreads, true, 0>(s, soft, sa32, grid, lds, g, w, flags, att_act, io));
+        else if (HB == 1) PVS_TRY(launch_fwd<1, kThreads, false, 0>(s, soft, sa32, grid, lds, g, w, flags, att_act, io));
+        else PVS_TRY(launch_fwd<2, kThreads, false, 0>(s, soft, sa32, grid, lds, g, w, flags, att_act, io));
     }
-    const char* bf = getenv("PVS_EGNN_BF16X3");
-    const char* bf64 = getenv("PVS_EGNN_BF16X3_H64");
-    // default: the two chain products as three-term fp16 products with tile scales ("f16x2", round 3);
-    // PVS_EGNN_BF16X3=0: exact fp32 MFMAs (PVS_EGNN_BF16X3_H64=0: only for H = 64) - the cross-check family of the
-    // tests. (The six-term bf16 form of rounds 1-2 is gone from the library: same accuracy, twice the MFMAs, a
-    // dearer split.)
-    const bool f16x2 = !(bf && bf[0] == '0') && (H == 32 || !(bf64 && bf64[0] == '0'));
-    // H = 64: 32 KB of weight operands, one workgroup per CU: 768 threads = three waves per SIMD where the edge-class
-    // table leaves room in the 160 KB of LDS (up to 3 classes), 512 threads otherwise
-    const int attr_rows = w.n_attr > 1 ? w.n_attr : 1;
-    const int nw = (HB == 2 && f16x2) ? (attr_rows <= 3 ? 12 : 8) : kWaves;
-    int blocks, n_chunks;
-    pick_grid(g.n_edges, &blocks, &n_chunks, nw, nw >= 8 ? 256 : 1024);
-    const size_t words = (f16x2 ? (size_t)2 * HB * HB * 4 * 64 * 4 + 4 : (size_t)2 * H * H) +
-                         (5 + attr_rows) * H +
-                         (size_t)nw * (kTile * (H + 4) + kTile * 4 + kTile);
-    const size_t lds = words * sizeof(float);
-    const bool soft = (flags & PVS_EDGE_ATTENTION) && (flags & PVS_SOFTMAX_ATT);
-#define PVS_FWD_LAUNCH(HBV, NTV, SF, F16, SA)                                                         \
-    do {                                                                                            \
-        if (set_lds(k_edge_fwd_mfma<HBV, NTV, SF, F16, 0, SA>, lds)) return -2;                     \
-        k_edge_fwd_mfma<HBV, NTV, SF, F16, 0, SA><<<blocks, NTV, lds, s>>>(g, w, flags, att_act, io, n_chunks, 0, g.n_edges); \
-    } while (0)
-#define PVS_FWD_PICK(HBV, NTV, F16)                                   \
-    do {                                                              \
-        if (soft && sa32) PVS_FWD_LAUNCH(HBV, NTV, true, F16, true);  \
-        else if (soft) PVS_FWD_LAUNCH(HBV, NTV, true, F16, false);    \
-        else if (sa32) PVS_FWD_LAUNCH(HBV, NTV, false, F16, true);    \
-        else PVS_FWD_LAUNCH(HBV, NTV, false, F16, false);             \
-    } while (0)
-    if (HB == 2 && f16x2 && nw == 12) PVS_FWD_PICK(2, 768, true);
-    else if (HB == 2 && f16x2) PVS_FWD_PICK(2, 512, true);
-    else if (HB == 1 && f16x2) PVS_FWD_PICK(1, kThreads, true);
-    else if (HB == 1) PVS_FWD_PICK(1, kThreads, false);
-    else PVS_FWD_PICK(2, kThreads, false);
-#undef PVS_FWD_PICK
-#undef PVS_FWD_LAUNCH
-    PVS_CHECK_LAUNCH();
     // softmax attention: att_out holds the logits, the rows' maxima and sums are complete now
-    if ((flags & PVS_EDGE_ATTENTION) && (flags & PVS_SOFTMAX_ATT))
-        return pvs_launch_softmax_finalize(s, g, io.smax, io.ssum, io.att_out);
+    if (soft) return pvs_launch_softmax_finalize(s, g, io.smax, io.ssum, io.att_out);
     return 0;
 }
-

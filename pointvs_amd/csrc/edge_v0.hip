@@ -600,8 +600,8 @@ int pvs_launch_edge_bwd_v0(hipStream_t s, int H, const PvsGraph& g, const PvsEdg
     PVS_REQUIRE(w.n_attr <= PVS_MAX_EDGE_ATTR, "edge_attr classes %d > %d", w.n_attr,
                 PVS_MAX_EDGE_ATTR);
     int blocks = pvs_edge_v0_blocks(g.n_nodes);
-    if (blocks > 512) blocks = 512;
-    *n_slabs = blocks;
+    if (blocks > kPvsBwdGenericMaxBlocks) blocks = kPvsBwdGenericMaxBlocks;
+    PVS_TRY(pvs_report_slabs(blocks, n_slabs));
     PvsProfScope prof(s, PVS_PROF_EDGE_BWD);
     PVS_DISPATCH_H(H, {
         const PvsSlabLayout L = pvs_slab_layout(HH);

@@ -10,26 +10,7 @@
 
 static constexpr uint32_t kFwdRawXsumFlag = 1u << 23;   // == kFwdRawXsum of edge_mfma_common.h
 
-// PVS_EGNN_KERNELS=generic forces the generic (VALU/LDS) edge kernels everywhere: used by the
-// tests to cross-check the MFMA path against the generic one on the same inputs.
-static bool pvs_use_mfma() {
-    const char* v = getenv("PVS_EGNN_KERNELS");
-    return !(v && v[0] == 'g');
-}
-
-// PVS_ABLATE=<hex bits>: timing-only switches of the MFMA edge kernels (kAbl*, edge_mfma_common.h)
-static uint32_t pvs_ablate_bits() {
-    const char* v = getenv("PVS_ABLATE");
-    return v ? (uint32_t)strtoul(v, nullptr, 16) << 24 : 0u;
-}
-
 namespace {
-
-static size_t edge_slab_capacity(int H, int E) {
-    (void)E;
-    const size_t cap = (size_t)pvs_edge_bwd_mfma_max_blocks(H);
-    return cap < 512 ? 512 : cap;     // one slab per workgroup of the edge backward
-}
 
 struct Dims {
     int N, E, H, A, ld1, off_rho, off_q;
@@ -72,7 +53,7 @@ int check_desc(const PvsLayerDesc* d, const PvsGraph* g, const PvsLayerParams* p
     // 16 / 32 / 64: every kernel family; 128 (the wide layer: 64 < hidden <= 128 zero-padded by the caller): the MFMA
     // edge kernels only (up to 3 edge classes, no PVS_EGNN_KERNELS=generic)
     PVS_REQUIRE(pvs_edge_v0_supported(d->hidden) ||
-                    (d->hidden == 128 && pvs_use_mfma() && pvs_edge_bwd_mfma_supported(128, d->flags, d->n_edge_attr)),
+                    (d->hidden == 128 && pvs_edge_family(128, d->flags, d->n_edge_attr, PVS_EDGE_BWD) != PVS_EDGE_GENERIC),
                 "hidden size %d unsupported by this build (16, 32, 64; 128 on the MFMA kernels with <= 3 edge classes)",
                 d->hidden);
     PVS_REQUIRE(d->n_edge_attr >= 0 && d->n_edge_attr <= PVS_MAX_EDGE_ATTR,
@@ -144,7 +125,7 @@ size_t carve_bwd(PvsArena& a, const Dims& m, BwdWs* w) {
     t.gz1 = a.take<float>((size_t)(m.E > 0 ? m.E : 1) * m.H);
     t.gd = a.take<float>(4 * (size_t)(m.E > 0 ? m.E : 1));
     t.gx_row = a.take<float>(3 * (size_t)m.N);
-    t.eslabs = a.take<float>(edge_slab_capacity(m.H, m.E) * L.total);
+    t.eslabs = a.take<float>((size_t)kPvsEdgeSlabCapacity * L.total);      // one slab per workgroup of the edge backward
     t.gsum = a.take<float>(L.total);
     t.dslabs = a.take<float>((size_t)pvs_reduce_blocks(m.N) * m.H * m.H);
     t.S1 = a.take<float>(m.H);
@@ -200,11 +181,21 @@ k_finalize_edge_grads(const float* __restrict__ gsum, PvsSlabLayout L, int H, in
     }
 }
 
-#define PVS_TRY(call)             \
-    do {                          \
-        int _rc = (call);         \
-        if (_rc) return _rc;      \
-    } while (0)
+// The MFMA edge backward of the family `fam` (the launchers' contract: edge_kernels.h)
+int pvs_launch_edge_bwd_mfma(hipStream_t s, int H, PvsEdgeFamily fam, const PvsGraph& g, const PvsEdgeW& w, uint32_t flags,
+                             int att_act, const PvsEdgeBwdIO& io, int e_lo, int e_hi, int* n_slabs) {
+    switch (fam) {
+        case PVS_EDGE_SPLIT:
+            if (H == 32) return pvs_launch_edge_bwd_f16(s, H, g, w, flags, att_act, io, e_lo, e_hi, n_slabs);
+            PVS_REQUIRE(H == 64, "split-product edge backward is built for H = 32, 64 (got %d)", H);
+            return pvs_launch_edge_bwd_h64(s, g, w, flags, att_act, io, e_lo, e_hi, n_slabs);
+        case PVS_EDGE_EXACT: return pvs_launch_edge_bwd_exact(s, H, g, w, flags, att_act, io, e_lo, e_hi, n_slabs);
+        case PVS_EDGE_WIDE: return pvs_launch_edge_bwd_wide(s, H, g, w, flags, att_act, io, e_lo, e_hi, n_slabs);
+        default: break;      // (generic: pvs_launch_edge_bwd_v0, another contract)
+    }
+    pvs_set_error("pvs_launch_edge_bwd_mfma: family %d is not an MFMA family", (int)fam);
+    return -1;
+}
 
 // y1 = [h | Magg] Wn1^T + bn1 ; (graphnorm stats) ; u = SiLU(GN(y1)) ; o = u Wn2^T + bn2 ; h_out
 // = node_out(o, h). Without GraphNorm the SiLU rides on the first product's epilogue, and the plain
@@ -325,7 +316,9 @@ extern "C" int pvs_egnn_layer_fwd(const PvsLayerDesc* d, const PvsGraph* g, cons
                                   pvs_stream_t stream_) {
     hipStream_t s = (hipStream_t)stream_;
     PVS_TRY(check_desc(d, g, p, /*allow_dev_count=*/true));
-    PVS_REQUIRE(!g->n_edges_dev || (pvs_use_mfma() && pvs_edge_mfma_supported(d->hidden, d->flags) && !m_out),
+    const PvsEdgeFamily fam = pvs_edge_family(d->hidden, d->flags, d->n_edge_attr, PVS_EDGE_FWD);
+    const bool mfma_fwd = fam != PVS_EDGE_GENERIC;
+    PVS_REQUIRE(!g->n_edges_dev || (mfma_fwd && !m_out),
                 "pvs_egnn_layer_fwd: a graph with a device-side edge count needs the MFMA edge kernel and m_out = NULL");
     PVS_REQUIRE(h && x && h_out && x_out && saved, "pvs_egnn_layer_fwd: NULL tensor");
     PVS_REQUIRE(x_out != x, "pvs_egnn_layer_fwd: x_out must not alias x");
@@ -349,10 +342,9 @@ extern "C" int pvs_egnn_layer_fwd(const PvsLayerDesc* d, const PvsGraph* g, cons
     PvsEdgeFwdIO io;
     io.PQ = sPQ; io.x = x; io.m_prev = m_prev; io.Magg = Magg; io.x_out = x_out; io.m_out = m_out;
     io.att_out = att_out; io.smax = w.smax; io.ssum = w.ssum; io.m_scratch = w.m_scratch;
-    const bool mfma_fwd = pvs_use_mfma() && pvs_edge_mfma_supported(H, d->flags);
     PVS_TRY(node_pre_forward(s, m, p, h, sPQ, mfma_fwd ? &io : nullptr, d->flags));
     if (mfma_fwd)
-        PVS_TRY(pvs_launch_edge_fwd_mfma(s, H, *g, ew, d->flags | pvs_ablate_bits(), d->att_act, io));
+        PVS_TRY(pvs_launch_edge_fwd_mfma(s, H, fam, *g, ew, d->flags, d->att_act, io));
     else
         PVS_TRY(pvs_launch_edge_fwd_v0(s, H, *g, ew, d->flags, d->att_act, io));
     if (!(d->flags & PVS_UPDATE_COORDS))
@@ -394,9 +386,10 @@ __global__ void k_combine_partial(float* __restrict__ Magg, float* __restrict__ 
     }
 }
 
-int partial_checks(const PvsLayerDesc* d, const PvsGraph* g, const PvsLayerParams* p) {
+int partial_checks(const PvsLayerDesc* d, const PvsGraph* g, const PvsLayerParams* p, PvsEdgeFamily* fam) {
     PVS_TRY(check_desc(d, g, p, true));
-    PVS_REQUIRE(pvs_use_mfma() && pvs_edge_mfma_supported(d->hidden, d->flags),
+    *fam = pvs_edge_family(d->hidden, d->flags, d->n_edge_attr, PVS_EDGE_FWD);
+    PVS_REQUIRE(*fam != PVS_EDGE_GENERIC,
                 "partial-sum forward needs the MFMA edge kernel (H = 32 or 64)");
     PVS_REQUIRE(!((d->flags & PVS_EDGE_ATTENTION) && (d->flags & PVS_SOFTMAX_ATT)),
                 "partial-sum forward: softmax attention is not supported (row sums of two edge sets do not add)");
@@ -410,7 +403,8 @@ extern "C" int pvs_egnn_layer_edge_sums(const PvsLayerDesc* d, const PvsGraph* g
                                         const float* h, const float* x, float* magg, float* xsum,
                                         void* workspace, size_t workspace_bytes, pvs_stream_t stream_) {
     hipStream_t s = (hipStream_t)stream_;
-    PVS_TRY(partial_checks(d, g, p));
+    PvsEdgeFamily fam;
+    PVS_TRY(partial_checks(d, g, p, &fam));
     PVS_REQUIRE(h && x && magg && xsum, "pvs_egnn_layer_edge_sums: NULL tensor");
     const Dims m = make_dims(d, g);
     PvsArena arena(workspace, workspace_bytes);
@@ -423,7 +417,7 @@ extern "C" int pvs_egnn_layer_edge_sums(const PvsLayerDesc* d, const PvsGraph* g
     io.PQ = w.PQ; io.x = x; io.m_prev = nullptr; io.Magg = magg; io.x_out = xsum; io.m_out = nullptr;
     io.att_out = att; io.smax = w.smax; io.ssum = w.ssum; io.m_scratch = w.m_scratch;
     PVS_TRY(node_pre_forward(s, m, p, h, w.PQ, &io, d->flags | kFwdRawXsumFlag));
-    PVS_TRY(pvs_launch_edge_fwd_mfma(s, m.H, *g, ew, d->flags | kFwdRawXsumFlag, d->att_act, io));
+    PVS_TRY(pvs_launch_edge_fwd_mfma(s, m.H, fam, *g, ew, d->flags | kFwdRawXsumFlag, d->att_act, io));
     if (!(d->flags & PVS_UPDATE_COORDS))
         PVS_CHECK_HIP(hipMemsetAsync(xsum, 0, sizeof(float) * 3 * (size_t)m.N, s));
     return 0;
@@ -435,7 +429,8 @@ extern "C" int pvs_egnn_layer_fwd_partial(const PvsLayerDesc* d, const PvsGraph*
                                           float* x_out, float* node_att_out, float* saved, void* workspace,
                                           size_t workspace_bytes, pvs_stream_t stream_) {
     hipStream_t s = (hipStream_t)stream_;
-    PVS_TRY(partial_checks(d, g, p));
+    PvsEdgeFamily fam;
+    PVS_TRY(partial_checks(d, g, p, &fam));
     PVS_REQUIRE(h && x && base_magg && base_xsum && base_deg && h_out && x_out && saved,
                 "pvs_egnn_layer_fwd_partial: NULL tensor");
     PVS_REQUIRE(x_out != x, "pvs_egnn_layer_fwd_partial: x_out must not alias x");
@@ -458,7 +453,7 @@ extern "C" int pvs_egnn_layer_fwd_partial(const PvsLayerDesc* d, const PvsGraph*
     io.att_out = att; io.smax = w.smax; io.ssum = w.ssum; io.m_scratch = w.m_scratch;
     PVS_TRY(node_pre_forward(s, m, p, h, sPQ, &io, d->flags | kFwdRawXsumFlag));
     pvs_prof_set_fwd_tag(PVS_PROF_EDGE_FWD_PARTIAL);      // timed apart from the full-graph layers (bench.py)
-    const int rc_partial = pvs_launch_edge_fwd_mfma(s, H, *g, ew, d->flags | kFwdRawXsumFlag, d->att_act, io);
+    const int rc_partial = pvs_launch_edge_fwd_mfma(s, H, fam, *g, ew, d->flags | kFwdRawXsumFlag, d->att_act, io);
     pvs_prof_set_fwd_tag(PVS_PROF_EDGE_FWD);
     PVS_TRY(rc_partial);
     const long long threads = (long long)m.N * (H / 4);
@@ -514,7 +509,8 @@ extern "C" int pvs_egnn_layer_bwd(const PvsLayerDesc* d, const PvsGraph* g, cons
 
     // ---- node_model backward ----
     const bool split_small = getenv("PVS_EGNN_SPLIT_SMALL") != nullptr;     // (the launches apart, for A/B)
-    const bool mfma_bwd = pvs_use_mfma() && pvs_edge_bwd_mfma_supported(H, F, m.A);
+    const PvsEdgeFamily fam = pvs_edge_family(H, F, m.A, PVS_EDGE_BWD);
+    const bool mfma_bwd = fam != PVS_EDGE_GENERIC;
     // Layers without GraphNorm and without rezero / gated residual: the output stage (node gate, residual), g_y1 and
     // [g_h | gM] as ONE launch that also carries the per-node preparation of the edge backward (dense_ops.hip:
     // k_node_mlp_bwd). Without a node gate g_o is g_h_out itself and nothing is written for it.
@@ -626,8 +622,7 @@ extern "C" int pvs_egnn_layer_bwd(const PvsLayerDesc* d, const PvsGraph* g, cons
     const PvsSlabLayout L = pvs_slab_layout(H);
     int n_nslabs = 0;
     if (mfma_bwd) {
-        const uint32_t Fk = F | pvs_ablate_bits();
-        PVS_TRY(pvs_launch_edge_bwd_mfma(s, H, *g, ew, Fk, d->att_act, io, 0, m.E, &n_slabs));
+        PVS_TRY(pvs_launch_edge_bwd_mfma(s, H, fam, *g, ew, F, d->att_act, io, 0, m.E, &n_slabs));
         PVS_TRY(pvs_launch_node_gather(s, H, *g, true, w.gz1, w.gd, w.gx_row, g_x_out, w.gPQ, g_x,
                                        w.nslabs, 0, N, &n_nslabs));
     } else {

@@ -26,7 +26,9 @@ for r in range(rounds):
             continue
         d = json.loads(line[0])
         k = d['roofline']['kernel_ms_per_step']
-        res[name].append((d['ms_per_step'], k['edge_fwd'], k['edge_bwd'], k['col_gather']))
+        # (cfg5 is forward only: its record has the full-graph layers' edge forward and no backward)
+        res[name].append((d['ms_per_step'], k.get('edge_fwd', k.get('edge_fwd_full_layers', 0.0)), k.get('edge_bwd', 0.0),
+                          k.get('col_gather', 0.0)))
 for name, rows in res.items():
     for row in rows:
         print(f'{name:16s} step {row[0]:7.3f}  fwd {row[1]:.3f}  bwd {row[2]:.3f}  col {row[3]:.3f}')
