@@ -287,6 +287,39 @@ int pvs_screen_graph_build(const float* lig_pos, const float* rec_pos, const int
                            int32_t* rowptr_lig, int32_t* row_lig, int32_t* col_lig, uint8_t* etype_lig,
                            int32_t* status, void* state, size_t state_bytes, pvs_stream_t stream);
 
+/* Library batches: the same graphs for a batch whose n_slots slots hold one pose each of DIFFERENT ligands
+ * (0..64 atoms per slot, 0 = the receptor alone) against the one receptor. No host argument depends on the
+ * batch's composition, so one captured step serves every batch of a library.
+ *   lig_pos [lig_cap,3]: the ligand atoms of all slots, packed; lig_ptr [n_slots+1] (device, int32, lig_ptr[0] = 0):
+ *     slot p holds the atoms lig_ptr[p] .. lig_ptr[p+1]; lig_ptr[n_slots] <= lig_cap <= 64 * n_slots.
+ *   Node layout (compact): slot p owns the nodes node_ptr[p] .. node_ptr[p+1], node_ptr[p] = lig_ptr[p] + p * n_rec,
+ *     its ligand atoms first, then the n_rec receptor atoms. The nodes from node_ptr[n_slots] up to
+ *     N_cap = lig_cap + n_slots * n_rec are padding: degree 0, inv_deg 1, graph id -1, zero rows in every table.
+ *   Outputs as the call above over N_cap nodes (rowptr / rowptr_lig [N_cap+1], inv_deg [N_cap]; edges, classes and
+ *     in-row order per slot those of generate_edges; both edge counts on the device), plus the node tables of the layer
+ *     stack: node_ptr [n_slots+1] (= the batch's graph ptr), node_graph [N_cap], pos [N_cap,3] and, where `tables` is
+ *     given, feats [N_cap,n_feats] (ligand rows from lig_feats [lig_cap,n_feats], receptor rows from rec_feats
+ *     [n_rec,n_feats]; feats may be NULL) and the first-layer receptor sums base_magg [N_cap,hidden], base_xsum
+ *     [N_cap,3], base_deg [N_cap] expanded from rec_magg / rec_xsum / rec_deg [n_rec,.] with zeros on ligand and
+ *     padding rows (base_magg may be NULL: none of the three is written).
+ *   *status: bit 2 = a capacity was too small (no edge is written then); bit 3 = lig_ptr is not such a table (the
+ *     outputs then describe N_cap padding nodes and no edge). */
+typedef struct {
+    int32_t n_feats, hidden;
+    const float *lig_feats, *rec_feats;
+    const float *rec_magg, *rec_xsum, *rec_deg;
+    float *feats, *base_magg, *base_xsum, *base_deg;
+} PvsRaggedNodeTables;
+size_t pvs_screen_graph_ragged_state_bytes(int32_t n_slots, int32_t lig_cap, int32_t n_rec);
+int pvs_screen_graph_build_ragged(const float* lig_pos, const int32_t* lig_ptr, const float* rec_pos,
+                                  const int32_t* rr_rowptr, const int32_t* rr_col, int32_t n_slots, int32_t lig_cap,
+                                  int32_t n_rec, double inter_radius, double intra_radius, int32_t capacity,
+                                  int32_t capacity_lig, int32_t* rowptr, int32_t* row, int32_t* col, uint8_t* etype,
+                                  float* inv_deg, int32_t* rowptr_lig, int32_t* row_lig, int32_t* col_lig,
+                                  uint8_t* etype_lig, int32_t* node_ptr, int32_t* node_graph, float* pos,
+                                  const PvsRaggedNodeTables* tables, int32_t* status, void* state,
+                                  size_t state_bytes, pvs_stream_t stream);
+
 /* Leave-out graph batch of masking attribution (the reference's atom_masking / bond_masking loops,
  * attribution/attribution_fns.py:39-115, 356-456, which rebuild one masked edge list per atom on the host).
  * `parent`: the prepared graph of ONE complex (rowptr / col / etype; host-side edge count); drop [n_masks, 2] int32:

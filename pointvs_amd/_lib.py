@@ -47,6 +47,11 @@ class PvsLayerGradsF64(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in PARAM_FIELDS]
 
 
+class PvsRaggedNodeTables(C.Structure):
+    _fields_ = [('n_feats', C.c_int32), ('hidden', C.c_int32)] + [(name, C.c_void_p) for name in (
+        'lig_feats', 'rec_feats', 'rec_magg', 'rec_xsum', 'rec_deg', 'feats', 'base_magg', 'base_xsum', 'base_deg')]
+
+
 class PvsStackStrides(C.Structure):
     _fields_ = [(name, C.c_int64) for name in ('h_mid', 'x_mid', 'att', 'node_att', 'saved')]
 
@@ -88,6 +93,10 @@ _PROTOTYPES = {
     'pvs_screen_graph_build': (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 3 + [C.c_double, C.c_double, C.c_int32,
                                                                               C.c_int32] + [C.c_void_p] * 10 +
                                [C.c_void_p, C.c_size_t, C.c_void_p]),
+    'pvs_screen_graph_ragged_state_bytes': (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    'pvs_screen_graph_build_ragged': (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 3 + [C.c_double, C.c_double, C.c_int32,
+                                                                                     C.c_int32] + [C.c_void_p] * 12 +
+                                      [C.POINTER(PvsRaggedNodeTables), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     'pvs_mask_graph_workspace_bytes': (C.c_size_t, [C.c_int32, C.c_int32]),
     'pvs_mask_graph_build': (C.c_int, [C.POINTER(PvsGraph), C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32] +
                              [C.c_void_p] * 9 + [C.c_void_p, C.c_size_t, C.c_void_p]),

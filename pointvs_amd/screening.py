@@ -292,6 +292,373 @@ class ReceptorScreen:
         return model._pool_and_head(model.feats_linear_layers, h, self._graph_ptr, self.b)
 
 
+def plan_library(pose_counts, lig_sizes, batch_size, max_lig_atoms=64):
+    """Batches of a library sweep: a list of batches, each a list of up to `batch_size` pairs (ligand index, pose
+    index), in library order then pose order, slots filled densely (only the last batch may have empty slots).
+    Pure host logic. Raises ValueError for a ligand that has poses and no atoms or more than `max_lig_atoms`."""
+    batch_size = int(batch_size)
+    if batch_size < 1:
+        raise ValueError(f'batch_size must be positive (got {batch_size})')
+    if len(pose_counts) != len(lig_sizes):
+        raise ValueError('pose_counts and lig_sizes differ in length')
+    batches, cur = [], []
+    for lig, (count, size) in enumerate(zip(pose_counts, lig_sizes)):
+        if int(count) > 0 and not 1 <= int(size) <= max_lig_atoms:
+            raise ValueError(f'ligand {lig} has {int(size)} atoms: a library batch slot holds 1..{max_lig_atoms}')
+        for pose in range(int(count)):
+            cur.append((lig, pose))
+            if len(cur) == batch_size:
+                batches.append(cur)
+                cur = []
+    if cur:
+        batches.append(cur)
+    return batches
+
+
+class LibraryScreen:
+    """Library screening: every one of the `batch_size` slots of a batch holds one pose of ANY ligand of up to
+    `max_lig_atoms` (<= 64) atoms against the one receptor, or nothing (the last batch of a library).
+
+        screen = LibraryScreen(model, rec_pos, rec_feats, batch_size, max_lig_atoms, edge_radius)
+        scores = screen([(lig_feats [n,F], pose [n,3]), ...])        # [batch_size, ...] raw outputs
+
+    What ReceptorScreen reuses across the poses of one ligand is reused across ligands: the receptor-receptor
+    template CSR and the first layer's receptor-receptor sums (kept once, [n_rec, .]), the ligand-touching first
+    layer, device-side edge counts. The mixed batch's graph and node tables come from pvs_screen_graph_build_ragged
+    in a compact layout (slot p: its ligand atoms, then the receptor); no host argument of a step depends on the
+    batch's composition, so ONE captured step (`capture`) serves every batch. Models without graphnorm always run
+    at the padded shape N_cap = batch_size * (max_lig_atoms + n_rec) (padding nodes have no edges and belong to no
+    graph), eager and captured alike; graphnorm normalises over the batch's nodes, so such models run eager at the
+    exact node count. Models the first-layer reuse does not cover (edge_residual, softmax attention, hidden size not
+    32 / 64) take the plain forward on the same mixed batch. fp32 only."""
+
+    def __init__(self, model, rec_pos, rec_feats, batch_size, max_lig_atoms, edge_radius, intra_radius=None):
+        if any(p.dtype == torch.float64 for p in model.parameters()):
+            raise NotImplementedError('LibraryScreen and its pose-batch builder are fp32 only (no fp64 screening '
+                                      'kernels): score fp64 models through the model forward')
+        if not 1 <= int(max_lig_atoms) <= 64:
+            raise ValueError(f'max_lig_atoms must be 1..64 (got {max_lig_atoms}); larger ligands go through '
+                             'ReceptorScreen')
+        _lib.require_hip(rec_pos)
+        layers = list(model.layers)
+        self.model, self.embed, self.egnn = model, layers[0], layers[1:]
+        first = self.egnn[0] if self.egnn else None
+        self.reuse = (first is not None and first.hidden_nf in (32, 64) and not first.softmax_attention
+                      and not any(l.edge_residual for l in self.egnn))
+        self.graphnorm = any(getattr(l, 'graphnorm', False) for l in self.egnn)
+        dev = rec_pos.device
+        self.b, self.max_lig_atoms = int(batch_size), int(max_lig_atoms)
+        self.n_rec = int(rec_pos.shape[0])
+        self.l_cap = self.b * self.max_lig_atoms
+        self.n_cap = self.l_cap + self.b * self.n_rec
+        self.r_inter = edge_radius
+        self.r_intra = edge_radius if intra_radius is None else intra_radius
+        self._rec_pos = rec_pos.float().contiguous()
+        self._rec_feats = rec_feats.to(dev).float().contiguous()
+        n_feats = int(self._rec_feats.shape[1])
+        i32 = dict(dtype=torch.int32, device=dev)
+        self.lig_pos = torch.zeros((self.l_cap, 3), dtype=torch.float32, device=dev)
+        self.lig_feats = torch.zeros((self.l_cap, n_feats), dtype=torch.float32, device=dev)
+        self.lig_ptr = torch.zeros(self.b + 1, **i32)
+        self.n_atoms = 0             # host copies of what load() was given
+        self._sizes = [0] * self.b
+        self._stage, self._stage_at = [], 0
+        self._pending, self._f, self._l1_ws, self._graph = None, None, None, None
+        if self.reuse:
+            self._cache_receptor_sums()
+
+    _weights_fingerprint = ReceptorScreen._weights_fingerprint
+    stale = ReceptorScreen.stale
+
+    def _cache_receptor_sums(self):
+        """Receptor-receptor template and the first layer's receptor-receptor sums, [n_rec, .] (pose and
+        ligand independent)."""
+        lib = _lib.lib()
+        rec_pos, first, n_rec = self._rec_pos, self.egnn[0], self.n_rec
+        dev = rec_pos.device
+        self._fingerprint = self._weights_fingerprint()
+        with torch.no_grad():
+            h_rec = self.embed.embed(self._rec_feats, rec_pos)
+            pg = radius_graph(rec_pos, torch.ones(n_rec, dtype=torch.uint8, device=dev), None,
+                              self.r_inter, self.r_intra, need_backward=False)
+            desc = _lib.PvsLayerDesc(*first._desc())
+            params = [None if p is None else p.detach().float().contiguous() for p in first._params()]
+            pstruct = _lib.PvsLayerParams(*[_lib.ptr(p) for p in params])
+            self.rec_magg = torch.empty((n_rec, first.hidden_nf), dtype=torch.float32, device=dev)
+            self.rec_xsum = torch.empty((n_rec, 3), dtype=torch.float32, device=dev)
+            ws_bytes = lib.pvs_egnn_layer_workspace_bytes(C.byref(desc), n_rec, pg.n_edges, 2)
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            _lib.check(lib.pvs_egnn_layer_edge_sums(
+                C.byref(desc), C.byref(pg.c), C.byref(pstruct), _lib.ptr(h_rec.contiguous()), _lib.ptr(rec_pos),
+                _lib.ptr(self.rec_magg), _lib.ptr(self.rec_xsum), _lib.ptr(ws), ws_bytes, _stream(dev)),
+                'pvs_egnn_layer_edge_sums')
+            self.rec_deg = (pg.t['rowptr'][1:] - pg.t['rowptr'][:-1]).float().contiguous()
+            self._rr = pg
+            torch.cuda.current_stream(dev).synchronize()    # ws goes out of scope
+
+    # ---- inputs ----
+    def load_packed(self, lig_pos, lig_feats, lig_ptr, sizes):
+        """One batch from packed device (or pinned host) tensors: lig_pos [L,3], lig_feats [L,F] (L = sum of
+        sizes), lig_ptr [batch_size+1] int32; `sizes`: the host's copy of the slots' atom counts. Three
+        asynchronous copies into the step's static inputs."""
+        sizes = [int(n) for n in sizes]
+        if len(sizes) > self.b or any(not 0 <= n <= self.max_lig_atoms for n in sizes):
+            raise ValueError(f'a batch holds up to {self.b} slots of 0..{self.max_lig_atoms} atoms (got {sizes})')
+        total = sum(sizes)
+        if lig_pos.shape[0] != total or lig_feats.shape[0] != total or lig_ptr.numel() != self.b + 1:
+            raise ValueError('packed ligand tensors do not match the slot sizes')
+        self.lig_pos[:total].copy_(lig_pos, non_blocking=True)
+        self.lig_feats[:total].copy_(lig_feats, non_blocking=True)
+        self.lig_ptr.copy_(lig_ptr, non_blocking=True)
+        self._sizes = sizes + [0] * (self.b - len(sizes))
+        self.n_atoms = total
+        return self
+
+    def load(self, slots):
+        """slots: up to batch_size pairs (lig_feats [n,F], pose [n,3]), n = 0..max_lig_atoms (host or device
+        tensors); the slots after them are empty. Host tensors are packed into pinned staging."""
+        slots = list(slots)
+        sizes = [int(pose.shape[0]) for _, pose in slots]
+        if len(sizes) > self.b or any(not 0 <= n <= self.max_lig_atoms for n in sizes):
+            raise ValueError(f'a batch holds up to {self.b} slots of 0..{self.max_lig_atoms} atoms (got {sizes})')
+        total = sum(sizes)
+        if len(self._stage) < 2:      # two staging sets: the previous batch's copies may still be in flight
+            self._stage.append(dict(
+                pos=torch.zeros((self.l_cap, 3), dtype=torch.float32).pin_memory(),
+                feats=torch.zeros((self.l_cap, self.lig_feats.shape[1]), dtype=torch.float32).pin_memory(),
+                ptr=torch.zeros(self.b + 1, dtype=torch.int32).pin_memory(), event=None))
+            st = self._stage[-1]
+        else:
+            self._stage_at ^= 1
+            st = self._stage[self._stage_at]
+        if st['event'] is not None:
+            st['event'].synchronize()
+        at = 0
+        for k in range(self.b):
+            st['ptr'][k] = at
+            if k < len(slots) and sizes[k]:
+                feats, pose = slots[k]
+                st['pos'][at:at + sizes[k]].copy_(pose)
+                st['feats'][at:at + sizes[k]].copy_(feats)
+                at += sizes[k]
+        st['ptr'][self.b] = at
+        self.load_packed(st['pos'][:total], st['feats'][:total], st['ptr'], sizes)
+        st['event'] = torch.cuda.Event()
+        st['event'].record(torch.cuda.current_stream(self.lig_pos.device))
+        return self
+
+    # ---- the graph and the node tables ----
+    def _buffers(self, cap, cap_l):
+        lib = _lib.lib()
+        dev, n_cap = self.lig_pos.device, self.n_cap
+        i32 = dict(dtype=torch.int32, device=dev)
+        f32 = dict(dtype=torch.float32, device=dev)
+        hid = self.egnn[0].hidden_nf
+        f = dict(cap=cap, cap_l=cap_l, status=torch.zeros(1, **i32),
+                 host=torch.zeros(1, dtype=torch.int32).pin_memory(),
+                 state=torch.empty(lib.pvs_screen_graph_ragged_state_bytes(self.b, self.l_cap, self.n_rec),
+                                   dtype=torch.uint8, device=dev),
+                 node_ptr=torch.zeros(self.b + 1, **i32), node_graph=torch.empty(n_cap, **i32),
+                 pos=torch.empty((n_cap, 3), **f32), x=torch.empty((n_cap, self.lig_feats.shape[1]), **f32),
+                 base_magg=torch.empty((n_cap, hid), **f32), base_xsum=torch.empty((n_cap, 3), **f32),
+                 base_deg=torch.empty(n_cap, **f32), inv_deg=torch.empty(n_cap, **f32),
+                 ones=torch.ones(n_cap, **f32), pgs={})
+        for tag, c in (('', cap), ('_l', cap_l)):
+            f['rowptr' + tag] = torch.empty(n_cap + 1, **i32)
+            f['row' + tag] = torch.empty(c, **i32)
+            f['col' + tag] = torch.empty(c, **i32)
+            f['etype' + tag] = torch.empty(c, dtype=torch.uint8, device=dev)
+        f['tables'] = _lib.PvsRaggedNodeTables(
+            f['x'].shape[1], hid, _lib.ptr(self.lig_feats), _lib.ptr(self._rec_feats), _lib.ptr(self.rec_magg),
+            _lib.ptr(self.rec_xsum), _lib.ptr(self.rec_deg), _lib.ptr(f['x']), _lib.ptr(f['base_magg']),
+            _lib.ptr(f['base_xsum']), _lib.ptr(f['base_deg']))
+        return f
+
+    def _launch_builder(self, f):
+        lib = _lib.lib()
+        _lib.check(lib.pvs_screen_graph_build_ragged(
+            _lib.ptr(self.lig_pos), _lib.ptr(self.lig_ptr), _lib.ptr(self._rec_pos), _lib.ptr(self._rr.t['rowptr']),
+            _lib.ptr(self._rr.t['col']), self.b, self.l_cap, self.n_rec, float(self.r_inter), float(self.r_intra),
+            f['cap'], f['cap_l'], _lib.ptr(f['rowptr']), _lib.ptr(f['row']), _lib.ptr(f['col']), _lib.ptr(f['etype']),
+            _lib.ptr(f['inv_deg']), _lib.ptr(f['rowptr_l']), _lib.ptr(f['row_l']), _lib.ptr(f['col_l']),
+            _lib.ptr(f['etype_l']), _lib.ptr(f['node_ptr']), _lib.ptr(f['node_graph']), _lib.ptr(f['pos']),
+            C.byref(f['tables']), _lib.ptr(f['status']), _lib.ptr(f['state']), f['state'].numel(),
+            _stream(self.lig_pos.device)), 'pvs_screen_graph_build_ragged')
+
+    def _probe_capacities(self):
+        """One synchronous probe: the builder with no room for edges leaves both exact edge counts in its row
+        pointers. Room for the ligand-touching edges: twice the loaded batch's contacts per ligand atom at a full
+        batch of L_cap atoms, at most what L_cap atoms can have."""
+        probe = self._buffers(1, 1)
+        probe['cap'] = probe['cap_l'] = 0
+        self._launch_builder(probe)
+        n_lig_edges = int(probe['rowptr_l'][self.n_cap].item())
+        per_atom = -(-n_lig_edges // max(self.n_atoms, 1))
+        cap_l = min(self.l_cap * (4 * self.n_rec + 64), 2 * per_atom * self.l_cap + 4096)
+        cap = self.b * self._rr.n_edges + cap_l
+        if cap >= 2 ** 31:
+            raise ValueError(f'a batch of {self.b} slots can have {cap} edges (>= 2^31): use a smaller batch_size')
+        return cap, cap_l
+
+    def _graphs(self, n):
+        """(PreparedGraph of the full CSR, PvsGraph of the ligand-touching CSR) over the first n nodes."""
+        from .graph import PreparedGraph
+        f = self._f
+        got = f['pgs'].get(n)
+        if got is None:
+            pg = PreparedGraph(n, f['cap'], 3, dict(rowptr=f['rowptr'], row=f['row'], col=f['col'],
+                                                    etype=f['etype'], inv_deg=f['inv_deg'], status=f['status']))
+            pg._status_checked = True
+            # (the nodes after n are padding, without edges: rowptr[n] == rowptr[N_cap] == the edge count)
+            pg.c.n_edges_dev = f['rowptr'][self.n_cap:].data_ptr()
+            gl = _lib.PvsGraph()
+            gl.n_nodes, gl.n_edges = n, f['cap_l']
+            gl.rowptr, gl.row, gl.col, gl.etype = (_lib.ptr(f[k + '_l']) for k in ('rowptr', 'row', 'col', 'etype'))
+            gl.inv_deg = _lib.ptr(f['ones'])
+            gl.n_edges_dev = f['rowptr_l'][self.n_cap:].data_ptr()
+            got = f['pgs'][n] = (pg, gl)
+        return got
+
+    def _build(self, capacities=None):
+        """The loaded batch's graph and node tables (pvs_screen_graph_build_ragged). capacities: (full, ligand-
+        touching) edge room instead of the probe's."""
+        capturing = torch.cuda.is_current_stream_capturing()
+        if self._f is None:
+            cap, cap_l = capacities or self._probe_capacities()
+            self._f = self._buffers(cap, cap_l)
+        if not capturing:
+            self.check()
+        self._launch_builder(self._f)
+        if not capturing:
+            self._poll_status()
+        return self._f
+
+    def _poll_status(self):
+        f = self._f
+        f['host'].copy_(f['status'], non_blocking=True)
+        self._pending = torch.cuda.Event()
+        self._pending.record(torch.cuda.current_stream(f['status'].device))
+
+    def check(self):
+        """Raises if the edge buffers of an earlier batch were too small (checked one batch late so that the loop
+        never waits for the device; call once more after the last batch)."""
+        if self._pending is not None:
+            self._pending.synchronize()
+            self._pending = None
+            code = int(self._f['host'].item())
+            if code & 8:
+                raise ValueError('LibraryScreen: lig_ptr is not a table of 0..64-atom slots')
+            if code & 4:
+                raise RuntimeError('LibraryScreen: edge buffer overflow (more ligand contacts per atom than twice '
+                                   'the first batch); rebuild the screen with a denser first batch')
+
+    # ---- the step ----
+    def _first_layer(self, g, h, x, n):
+        lib = _lib.lib()
+        first, f, dev = self.egnn[0], self._f, h.device
+        desc = _lib.PvsLayerDesc(*first._desc())
+        params = [None if p is None else p.detach().float().contiguous() for p in first._params()]
+        pstruct = _lib.PvsLayerParams(*[_lib.ptr(p) for p in params])
+        h_out, x_out = torch.empty_like(h), torch.empty_like(x)
+        natt = torch.empty(n, dtype=torch.float32, device=dev) if first.node_attention else None
+        if self._l1_ws is None:
+            self._l1_ws = (
+                torch.empty(lib.pvs_egnn_layer_saved_floats(C.byref(desc), self.n_cap, f['cap_l']),
+                            dtype=torch.float32, device=dev),
+                torch.empty(lib.pvs_egnn_layer_workspace_bytes(C.byref(desc), self.n_cap, f['cap_l'], 2),
+                            dtype=torch.uint8, device=dev))
+        saved, ws = self._l1_ws
+        _lib.check(lib.pvs_egnn_layer_fwd_partial(
+            C.byref(desc), C.byref(g), C.byref(pstruct), _lib.ptr(h), _lib.ptr(x), _lib.ptr(f['base_magg']),
+            _lib.ptr(f['base_xsum']), _lib.ptr(f['base_deg']), _lib.ptr(h_out), _lib.ptr(x_out), _lib.ptr(natt),
+            _lib.ptr(saved), _lib.ptr(ws), ws.numel(), _stream(dev)), 'pvs_egnn_layer_fwd_partial')
+        return h_out, x_out
+
+    def _plain_forward(self):
+        """The models the first-layer reuse does not cover: the same mixed batch, graph from the general builder."""
+        from .graph import Batch
+        from .radius_graph import attach_radius_graph
+        dev = self.lig_pos.device
+        pos, x, counts, at = [], [], [], 0
+        for n in self._sizes:
+            pos += [self.lig_pos[at:at + n], self._rec_pos]
+            x += [self.lig_feats[at:at + n], self._rec_feats]
+            counts.append(n + self.n_rec)
+            at += n
+        ptr = torch.tensor([0] + counts, dtype=torch.int64).cumsum(0)
+        batch = Batch(x=torch.cat(x, 0), pos=torch.cat(pos, 0), edge_index=None, edge_attr=None,
+                      batch=torch.arange(self.b, device=dev).repeat_interleave(torch.tensor(counts, device=dev)),
+                      ptr=ptr, y=torch.zeros(self.b, device=dev), lig_fname=['pose'] * self.b,
+                      rec_fname=['receptor'] * self.b, num_graphs=self.b, graph_node_counts=counts)
+        return self.model(attach_radius_graph(batch, self.r_inter, self.r_intra))
+
+    @torch.no_grad()
+    def __call__(self, slots=None):
+        if slots is not None:
+            self.load(slots)
+        model = self.model
+        if not self.reuse:
+            return self._plain_forward()
+        if self._fingerprint != self._weights_fingerprint():
+            if torch.cuda.is_current_stream_capturing() or self._graph is not None:
+                raise RuntimeError('LibraryScreen: the model\'s weights changed after capture(); build a new screen')
+            self._cache_receptor_sums()
+            if self._f is not None:         # (the node-table struct points at the receptor sums)
+                t = self._f['tables']
+                t.rec_magg, t.rec_xsum, t.rec_deg = (_lib.ptr(v) for v in (self.rec_magg, self.rec_xsum, self.rec_deg))
+        f = self._build()
+        # graphnorm's statistics run over the batch's nodes: no padding rows there (the host knows the count)
+        n = self.n_atoms + self.b * self.n_rec if self.graphnorm else self.n_cap
+        pg_full, g_lig = self._graphs(n)
+        x = f['pos'][:n]
+        h = self.embed.embed(f['x'][:n], x).contiguous()
+        h, x = self._first_layer(g_lig, h, x, n)
+        for layer in self.egnn[1:]:
+            h, x, _ = layer.forward_prepared(pg_full, h, x, None, need_m=False,
+                                             need_coords=layer is not self.egnn[-1])
+        if model.feats_linear_layers is None:
+            return h
+        if self.b == 1:     # (one slot: the pooling still ends at node_ptr[1], not at the padded shape)
+            return model._run_head(model.feats_linear_layers, PF.mean_pool(h, f['node_ptr']))
+        return model._pool_and_head(model.feats_linear_layers, h, f['node_ptr'], self.b)
+
+    def capture(self, example_slots=None):
+        """Captures one whole step (builder + layer stack + head) in a hipGraph; `replay(slots)` then serves every
+        batch of a library, whatever its composition."""
+        if not self.reuse:
+            raise RuntimeError('capture needs the first-layer reuse (no edge_residual, no softmax attention, '
+                               'hidden size 32 or 64)')
+        if self.graphnorm:
+            raise RuntimeError('a graphnorm model normalises over the batch\'s nodes and runs at the exact node '
+                               'count: it cannot be captured at the padded shape; call the screen eagerly')
+        if example_slots is not None:
+            self.load(example_slots)
+        dev = self.lig_pos.device
+        stream = torch.cuda.Stream(dev)
+        stream.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(stream):
+            for _ in range(2):
+                self()                         # warm-up: probe, buffers, lazy allocations
+            self.check()
+            torch.cuda.synchronize(dev)
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph, stream=stream):
+                self._static_out = self()
+        self._graph = graph
+        torch.cuda.current_stream(dev).wait_stream(stream)
+        return self
+
+    def replay(self, slots=None):
+        if self.stale():           # host-only comparison of version counters
+            raise RuntimeError('LibraryScreen: the model\'s weights changed after capture(); build a new screen')
+        self.check()
+        if slots is not None:
+            self.load(slots)
+        self._graph.replay()
+        self._poll_status()
+        return self._static_out
+
+
 class ScreeningSweep:
     """Virtual-screening sweep (BASELINE config 5; the reference's `val` / inference.py loop,
     point_neural_network_base.py:208-360, inference.py:77-146): many ligands, each with many rigid
@@ -339,6 +706,30 @@ class ScreeningSweep:
         x = screen.batcher.batch.x
         x.view(screen.b, screen.batcher.n, -1)[:, :screen.n_lig] = lig_feats.to(x.device, x.dtype)
 
+    def _run_ligand(self, name, lig_feats, poses, sigmoid, writer):
+        """All poses of one ligand through its size bucket; returns its scores [P, ...]."""
+        n_poses, n_lig = int(poses.shape[0]), int(poses.shape[1])
+        pad = (-n_poses) % self.b
+        if pad:
+            poses = torch.cat([poses, poses[-1:].expand(pad, -1, -1)], 0)
+        screen = self._bucket(n_lig, lig_feats, poses[:self.b].contiguous())
+        self._set_ligand_feats(screen, lig_feats)
+        scores = []
+        for k in range(0, poses.shape[0], self.b):
+            chunk = poses[k:k + self.b]
+            y = screen.replay(chunk).clone() if screen._captured else screen(chunk.contiguous())
+            y = y.reshape(self.b, -1)
+            if sigmoid:
+                y = torch.sigmoid(y)
+            keep = min(self.b, n_poses - k)
+            scores.append(y[:keep])
+            if writer is not None:
+                writer.submit(y[:keep, 0], None, [self.receptor_name] * keep,
+                              [f'{name}_pose{k + i}' for i in range(keep)])
+            self.batches_run += 1
+        screen.check()
+        return torch.cat(scores, 0)
+
     @torch.no_grad()
     def run(self, ligands, predictions_file=None, sigmoid=None):
         """ligands: iterable of (name, lig_feats [n_lig,F], poses [P,n_lig,3] on the device).
@@ -354,31 +745,99 @@ class ScreeningSweep:
         frozen.__enter__()
         try:
             for name, lig_feats, poses in ligands:
-                n_poses, n_lig = int(poses.shape[0]), int(poses.shape[1])
-                if n_poses == 0:
+                if int(poses.shape[0]) == 0:
                     continue
-                pad = (-n_poses) % self.b
-                if pad:
-                    poses = torch.cat([poses, poses[-1:].expand(pad, -1, -1)], 0)
-                screen = self._bucket(n_lig, lig_feats, poses[:self.b].contiguous())
-                self._set_ligand_feats(screen, lig_feats)
-                scores = []
-                for k in range(0, poses.shape[0], self.b):
-                    chunk = poses[k:k + self.b]
-                    y = screen.replay(chunk).clone() if screen._captured else screen(chunk.contiguous())
-                    y = y.reshape(self.b, -1)
-                    if sigmoid:
-                        y = torch.sigmoid(y)
-                    keep = min(self.b, n_poses - k)
-                    scores.append(y[:keep])
-                    if writer is not None:
-                        writer.submit(y[:keep, 0], None, [self.receptor_name] * keep,
-                                      [f'{name}_pose{k + i}' for i in range(keep)])
-                    self.batches_run += 1
-                out[name] = torch.cat(scores, 0)
-                screen.check()
+                out[name] = self._run_ligand(name, lig_feats, poses, sigmoid, writer)
         finally:
             frozen.__exit__(None, None, None)
             if writer is not None:
                 writer.close()
         return out
+
+    def _library_screen(self, max_atoms):
+        screen = getattr(self, 'library', None)
+        if screen is None or screen.stale() or screen.max_lig_atoms < max_atoms:
+            screen = LibraryScreen(self.model, self.rec_pos, self.rec_feats, self.b, max_atoms, self.edge_radius,
+                                   self.intra_radius)
+            screen._captured = False
+            self.library = screen
+        return screen
+
+    @torch.no_grad()
+    def run_library(self, ligands, predictions_file=None, sigmoid=None):
+        """`run` for a docking library (many ligands of different sizes with a few poses each): the poses of all
+        ligands of up to 64 atoms are streamed through ONE LibraryScreen in dense mixed batches (`plan_library`:
+        library order, then pose order; ceil(total poses / batch_size) batches, one captured step for all of them),
+        larger ligands through their size bucket as in `run`. Same arguments, return value and predictions lines
+        as `run`; the lines are in library order, then pose order."""
+        from .point_neural_network_base import long_lived_heap_frozen
+        from .predictions import PredictionsWriter
+        if sigmoid is None:
+            sigmoid = getattr(self.model, 'model_task', 'classification') == 'classification'
+        ligands = [item for item in ligands if int(item[2].shape[0]) > 0]
+        dev = self.rec_pos.device
+        small = [k for k, (_, _, poses) in enumerate(ligands) if int(poses.shape[1]) <= 64]
+        large = [k for k in range(len(ligands)) if int(ligands[k][2].shape[1]) > 64]
+        sizes = [int(ligands[k][2].shape[1]) for k in small]
+        counts = [int(ligands[k][2].shape[0]) for k in small]
+        plan = plan_library(counts, sizes, self.b, 64)
+        writer = PredictionsWriter(predictions_file, 'regression', flush_every=10) if predictions_file else None
+        out, kept = {}, []
+        frozen = long_lived_heap_frozen()
+        frozen.__enter__()
+        try:
+            if plan:
+                # the whole library packed once, in plan order: a batch is a contiguous range of it
+                all_pos = torch.cat([ligands[k][2].to(dev).float().reshape(-1, 3) for k in small], 0)
+                all_feats = torch.cat([ligands[k][1].to(dev).float().repeat(c, 1) for k, c in zip(small, counts)], 0)
+                ptrs = torch.zeros((len(plan), self.b + 1), dtype=torch.int32)
+                for b, batch in enumerate(plan):
+                    ptrs[b, 1:len(batch) + 1] = torch.tensor([sizes[lig] for lig, _ in batch], dtype=torch.int32)
+                ptrs = ptrs.cumsum(1, dtype=torch.int32)
+                ptrs_dev = ptrs.to(dev)
+                screen = self._library_screen(max(sizes))
+            next_large, at = 0, 0
+
+            def run_large_before(k):       # the larger ligands whose place in the library is before ligand k
+                nonlocal next_large
+                while next_large < len(large) and large[next_large] < k:
+                    name, lig_feats, poses = ligands[large[next_large]]
+                    out[name] = self._run_ligand(name, lig_feats, poses, sigmoid, writer)
+                    next_large += 1
+
+            for b, batch in enumerate(plan):
+                batch_sizes = [sizes[lig] for lig, _ in batch]
+                total = int(ptrs[b, -1])
+                screen.load_packed(all_pos[at:at + total], all_feats[at:at + total], ptrs_dev[b], batch_sizes)
+                at += total
+                if self.capture and screen.reuse and not screen.graphnorm and not screen._captured:
+                    screen.capture()
+                    screen._captured = True
+                y = (screen.replay().clone() if screen._captured else screen()).reshape(self.b, -1)
+                if sigmoid:
+                    y = torch.sigmoid(y)
+                kept.append(y[:len(batch)])
+                self.batches_run += 1
+                if writer is not None:
+                    lo = 0
+                    while lo < len(batch):      # one submit per run of slots that no larger ligand interrupts
+                        run_large_before(small[batch[lo][0]])
+                        hi = lo + 1
+                        stop = large[next_large] if next_large < len(large) else len(ligands)
+                        while hi < len(batch) and small[batch[hi][0]] < stop:
+                            hi += 1
+                        writer.submit(y[lo:hi, 0], None, [self.receptor_name] * (hi - lo),
+                                      [f'{ligands[small[lig]][0]}_pose{pose}' for lig, pose in batch[lo:hi]])
+                        lo = hi
+            run_large_before(len(ligands))
+            if plan:
+                screen.check()
+                scores, at = torch.cat(kept, 0), 0
+                for k, c in zip(small, counts):
+                    out[ligands[k][0]] = scores[at:at + c]
+                    at += c
+        finally:
+            frozen.__exit__(None, None, None)
+            if writer is not None:
+                writer.close()
+        return {name: out[name] for name, _, _ in ligands}
