@@ -453,6 +453,40 @@ int pvs_adam_clip_step(const PvsAdamEntry* table, int32_t n_tensors, double lr, 
 int pvs_adam_clip_step_dev(const PvsAdamEntry* table, int32_t n_tensors, double lr, double beta1, double beta2,
                            float eps, float weight_decay, const float* step, float clip, pvs_stream_t stream);
 
+/* Hyper-parameters that change from step to step (a learning-rate scheduler; OneCycleLR also cycles Adam's beta1 / SGD's
+ * momentum) live in a small block of doubles in DEVICE memory, so that a captured optimiser step can be replayed at other
+ * values: Adam {lr, beta1, beta2}, SGD {lr, momentum}. pvs_hyper_write stores n (1..4) doubles into such a block on the
+ * stream; the values travel BY VALUE as kernel arguments - no staging buffer, no host synchronisation, and a host that
+ * runs several steps ahead of the device cannot overwrite what an earlier write still has to deliver. Call it outside
+ * the capture and before every replay. */
+int pvs_hyper_write(double* dst, int32_t n, double v0, double v1, double v2, double v3, pvs_stream_t stream);
+/* pvs_adam_clip_step_dev with lr, beta1 and beta2 read from hyper[0..2]: lr / bias_correction1, sqrt(bias_correction2),
+ * 1 - beta1 and 1 - beta2 are formed in double from those doubles and rounded once, as both forms above do: with the same
+ * values in the block the update is bit for bit theirs. */
+int pvs_adam_clip_step_hyper(const PvsAdamEntry* table, int32_t n_tensors, const double* hyper, float eps,
+                             float weight_decay, const float* step, float clip, pvs_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * clip_grad_value_(params, clip) + torch.optim.SGD.step() for all parameters in ONE launch, for the settings the
+ * reference constructs (point_neural_network_base.py: momentum 0.9, nesterov, weight decay; dampening 0, not maximize).
+ * The gradients are clamped in place to [-clip, clip] (clip <= 0: no clamp), then, every product rounded to fp32
+ * before its sum,
+ *   d = g + weight_decay * p;  buf = first ? d : momentum * buf + d;  d = nesterov ? d + momentum * buf : buf;
+ *   p -= lr * d
+ * `first`: the tensors of this table have no momentum history yet (torch clones the gradient into a new buffer): the
+ * buffers are written, not read. momentum == 0 (or a NULL momentum_buf): no buffer is touched, d = g + weight_decay * p.
+ * _hyper reads lr and momentum from hyper[0..1] (pvs_hyper_write) and has no `first`: a replayed step has buffers. */
+typedef struct PvsSgdEntry {
+    float* param;
+    float* grad;
+    float* momentum_buf;
+    int64_t numel;
+} PvsSgdEntry;
+int pvs_sgd_clip_step(const PvsSgdEntry* table, int32_t n_tensors, double lr, double momentum, float weight_decay,
+                      int32_t nesterov, int32_t first, float clip, pvs_stream_t stream);
+int pvs_sgd_clip_step_hyper(const PvsSgdEntry* table, int32_t n_tensors, const double* hyper, float weight_decay,
+                            int32_t nesterov, float clip, pvs_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * unsorted_segment_sum / unsorted_segment_mean (egnn_satorras.py:332-337 / :340-347) as standalone
  * operators (inside the layers these sums are fused into the edge kernels).

@@ -138,6 +138,12 @@ _PROTOTYPES = {
                                      C.c_double, C.c_double, C.c_float, C.c_void_p]),
     'pvs_adam_clip_step_dev': (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_float, C.c_float,
                                          C.c_void_p, C.c_float, C.c_void_p]),
+    'pvs_hyper_write': (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p]),
+    'pvs_adam_clip_step_hyper': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_float,
+                                           C.c_void_p]),
+    'pvs_sgd_clip_step': (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_float, C.c_int32, C.c_int32,
+                                    C.c_float, C.c_void_p]),
+    'pvs_sgd_clip_step_hyper': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_float, C.c_int32, C.c_float, C.c_void_p]),
     # fp64 (--double)
     'pvs_egnn_layer_saved_doubles_f64': (C.c_size_t, [C.POINTER(PvsLayerDesc), C.c_int32, C.c_int32]),
     'pvs_egnn_layer_workspace_bytes_f64': (C.c_size_t, [C.POINTER(PvsLayerDesc), C.c_int32, C.c_int32, C.c_int32]),
@@ -162,6 +168,7 @@ _PROTOTYPES = {
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)
+MIN_VERSION = 104       # pvs_version() of the library these prototypes describe (104: device hyper-parameters, fused SGD)
 _lib = None
 
 
@@ -179,6 +186,12 @@ def lib():
         # ("no ROCm-capable device is detected" from the first launch; seen when build() and smoke() ran in one process).
         import torch  # noqa: F401
         handle = C.CDLL(str(LIB_PATH))
+        handle.pvs_version.restype, handle.pvs_version.argtypes = _PROTOTYPES['pvs_version']
+        if handle.pvs_version() < MIN_VERSION:
+            raise RuntimeError(
+                f'{LIB_PATH} is version {handle.pvs_version()}, this package needs {MIN_VERSION} or newer: it was built '
+                f'from older sources - rebuild it (`python -c "import __graft_entry__ as g; g.build()"` or '
+                f'`make -C pointvs_amd/csrc`)')
         for name, (restype, argtypes) in _PROTOTYPES.items():
             fn = getattr(handle, name)
             fn.restype, fn.argtypes = restype, argtypes

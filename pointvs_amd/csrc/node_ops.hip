@@ -449,13 +449,25 @@ namespace {
 // and rounded once, as torch's Adam forms them (Python floats handed to lerp_ / addcmul_ / addcdiv_ as scalars: adam.py
 // `_single_tensor_adam`). Until round 6 the kernel took 1 - beta in fp32 - 1.f - 0.999f is 1.3e-5 below float(0.001) - and
 // exp_avg_sq ran 1.3e-5 (relative) below torch's, the updates 6e-6 (tools/fuzz_adam.py found it with gradients of 30).
-template <bool STEP_DEV>
+// HYPER: lr and the betas too are on the device (three doubles, `pvs_hyper_write`): a replayed step runs at whatever the
+// host wrote there before the replay (a learning-rate scheduler; OneCycleLR also cycles beta1). The same doubles through the
+// same double expressions as the host forms', rounded once: bit for bit their update.
+template <bool STEP_DEV, bool HYPER = false>
 __global__ void __launch_bounds__(256)
 k_adam_clip(const PvsAdamEntry* __restrict__ table, float step_size, float beta2, float omb1, float omb2, float eps, float wd,
-            float bc2_sqrt, float clip, const float* __restrict__ step_dev, double lr_d, double beta1_d, double beta2_d) {
+            float bc2_sqrt, float clip, const float* __restrict__ step_dev, double lr_d, double beta1_d, double beta2_d,
+            const double* __restrict__ hyper = nullptr) {
     if constexpr (STEP_DEV) {
-        __shared__ float bc[2];
+        __shared__ float bc[5];
         if (threadIdx.x == 0) {      // (from the betas as the caller holds them - doubles in Python - like `1 - beta ** step` there)
+            if constexpr (HYPER) {
+                lr_d = hyper[0];
+                beta1_d = hyper[1];
+                beta2_d = hyper[2];
+                bc[2] = (float)beta2_d;
+                bc[3] = (float)(1.0 - beta1_d);
+                bc[4] = (float)(1.0 - beta2_d);
+            }
             // (a counter below 1 - a state restored by hand, a step skipped - would make both corrections 0 and the
             // update a division by zero: treated as the first step)
             const double t = fmax((double)step_dev[0], 1.0);
@@ -465,6 +477,11 @@ k_adam_clip(const PvsAdamEntry* __restrict__ table, float step_size, float beta2
         __syncthreads();
         step_size = bc[0];
         bc2_sqrt = bc[1];
+        if constexpr (HYPER) {
+            beta2 = bc[2];
+            omb1 = bc[3];
+            omb2 = bc[4];
+        }
     }
     const PvsAdamEntry e = table[blockIdx.y];
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < e.numel;
@@ -484,6 +501,50 @@ k_adam_clip(const PvsAdamEntry* __restrict__ table, float step_size, float beta2
         e.exp_avg[i] = m;
         e.exp_avg_sq[i] = v;
         e.param[i] = __fadd_rn(p, __fmul_rn(-step_size, __fdiv_rn(m, denom)));   // addcdiv_(m, denom, value=-step_size)
+    }
+}
+
+// One thread stores up to four doubles that arrived as kernel arguments: no staging buffer whose lifetime a host running
+// ahead of the device would have to mind, and nothing for the host to wait for.
+__global__ void k_hyper_write(double* __restrict__ dst, int n, double v0, double v1, double v2, double v3) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    if (n > 0) dst[0] = v0;
+    if (n > 1) dst[1] = v1;
+    if (n > 2) dst[2] = v2;
+    if (n > 3) dst[3] = v3;
+}
+
+// clip + torch.optim.SGD (dampening 0, L2 weight decay, not maximize) for every tensor of a table: the launch shape of
+// k_adam_clip. The scalars reach the arithmetic as fp32 (torch hands Python floats to add / mul_ / add_ on fp32 tensors
+// as fp32 `alpha`s); every product is rounded before its sum, as separate torch ops round it.
+// HYPER: lr and momentum are read from two doubles on the device (pvs_hyper_write), and every buffer exists.
+template <bool HYPER>
+__global__ void __launch_bounds__(256)
+k_sgd_clip(const PvsSgdEntry* __restrict__ table, float lr, float momentum, float wd, float clip, int first, int nesterov,
+           const double* __restrict__ hyper) {
+    if constexpr (HYPER) {
+        lr = (float)hyper[0];
+        momentum = (float)hyper[1];
+    }
+    const PvsSgdEntry e = table[blockIdx.y];
+    const bool with_buf = momentum != 0.f && e.momentum_buf != nullptr;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < e.numel;
+         i += (long long)gridDim.x * blockDim.x) {
+        float g = e.grad[i];
+        if (clip > 0.f) {
+            g = (g != g) ? g : fminf(fmaxf(g, -clip), clip);   // torch.clamp propagates NaN (fminf/fmaxf drop it)
+            e.grad[i] = g;                       // clip_grad_value_ is in place
+        }
+        const float p = e.param[i];
+        float d = g;
+        if (wd != 0.f) d = __fadd_rn(g, __fmul_rn(wd, p));                        // grad.add(param, alpha=wd)
+        if (with_buf) {
+            float buf = d;                                                        // first: buf = clone(grad)
+            if (!first) buf = __fadd_rn(__fmul_rn(e.momentum_buf[i], momentum), d);   // buf.mul_(momentum).add_(grad)
+            e.momentum_buf[i] = buf;
+            d = nesterov ? __fadd_rn(d, __fmul_rn(momentum, buf)) : buf;          // grad.add(buf, alpha=momentum)
+        }
+        e.param[i] = __fadd_rn(p, __fmul_rn(-lr, d));                             // param.add_(grad, alpha=-lr)
     }
 }
 }  // namespace
@@ -506,6 +567,43 @@ extern "C" int pvs_adam_clip_step_dev(const PvsAdamEntry* table, int32_t n, doub
     if (n == 0) return 0;
     k_adam_clip<true><<<dim3(8, n), 256, 0, (hipStream_t)stream>>>(table, 0.f, (float)beta2, (float)(1.0 - beta1),
                                                                    (float)(1.0 - beta2), eps, wd, 1.f, clip, step, lr, beta1, beta2);
+    PVS_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int pvs_adam_clip_step_hyper(const PvsAdamEntry* table, int32_t n, const double* hyper, float eps, float wd,
+                                        const float* step, float clip, pvs_stream_t stream) {
+    PVS_REQUIRE(table && hyper && step && n >= 0, "pvs_adam_clip_step_hyper: bad arguments");
+    if (n == 0) return 0;
+    k_adam_clip<true, true><<<dim3(8, n), 256, 0, (hipStream_t)stream>>>(table, 0.f, 0.f, 0.f, 0.f, eps, wd, 1.f, clip, step,
+                                                                         0.0, 0.0, 0.0, hyper);
+    PVS_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int pvs_hyper_write(double* dst, int32_t n, double v0, double v1, double v2, double v3, pvs_stream_t stream) {
+    PVS_REQUIRE(dst && n >= 1 && n <= 4, "pvs_hyper_write: needs a destination and 1..4 values");
+    k_hyper_write<<<1, 64, 0, (hipStream_t)stream>>>(dst, n, v0, v1, v2, v3);
+    PVS_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int pvs_sgd_clip_step(const PvsSgdEntry* table, int32_t n, double lr, double momentum, float wd, int32_t nesterov,
+                                 int32_t first, float clip, pvs_stream_t stream) {
+    PVS_REQUIRE(table && n >= 0, "pvs_sgd_clip_step: bad arguments");
+    PVS_REQUIRE(!nesterov || momentum > 0.0, "pvs_sgd_clip_step: Nesterov momentum needs a momentum");
+    if (n == 0) return 0;
+    k_sgd_clip<false><<<dim3(8, n), 256, 0, (hipStream_t)stream>>>(table, (float)lr, (float)momentum, wd, clip, first != 0,
+                                                                   nesterov != 0, nullptr);
+    PVS_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int pvs_sgd_clip_step_hyper(const PvsSgdEntry* table, int32_t n, const double* hyper, float wd, int32_t nesterov,
+                                       float clip, pvs_stream_t stream) {
+    PVS_REQUIRE(table && hyper && n >= 0, "pvs_sgd_clip_step_hyper: bad arguments");
+    if (n == 0) return 0;
+    k_sgd_clip<true><<<dim3(8, n), 256, 0, (hipStream_t)stream>>>(table, 0.f, 0.f, wd, clip, 0, nesterov != 0, hyper);
     PVS_CHECK_LAUNCH();
     return 0;
 }

@@ -1,24 +1,24 @@
-"""`torch.optim.Adam` whose step (and the `clip_grad_value_` the reference runs just before it,
+"""`torch.optim.Adam` and `torch.optim.SGD` whose step (and the `clip_grad_value_` the reference runs just before it,
 /root/reference/point_vs/models/point_neural_network_base.py:421-422) is ONE kernel launch for all
-parameters (`pvs_adam_clip_step`) instead of torch's dozen multi-tensor
-launches. Same update rule, same `state_dict` layout (`step`, `exp_avg`, `exp_avg_sq`), so
-checkpoints stay interchangeable with the reference's Adam."""
+parameters (`pvs_adam_clip_step` / `pvs_sgd_clip_step`) instead of torch's dozen multi-tensor
+launches. Same update rules, same `state_dict` layouts (`step`, `exp_avg`, `exp_avg_sq`; `momentum_buffer`), so
+checkpoints stay interchangeable with the reference's optimisers.
+
+Both have a capturable form for hipGraph replay: what a learning-rate scheduler changes from step to step (lr; OneCycleLR
+also cycles Adam's beta1 / SGD's momentum) is then read by the kernel from a few doubles in device memory, which
+`push_hyperparameters()` writes from the groups' current Python floats (`pvs_hyper_write`)."""
 import torch
 
 from . import _lib
 
 
-class FusedClipAdam(torch.optim.Adam):
-    """Drop-in `torch.optim.Adam`; `step(clip_value=c)` first clamps every gradient to [-c, c] in
-    place. Falls back to torch's own implementation whenever a feature the kernel does not cover is
-    on (amsgrad, maximize, differentiable, a tensor learning rate, non-CUDA / non-fp32 parameters).
-    `capturable=True` (round 5) keeps the step counters on the device exactly as torch's capturable Adam does (same
-    `state_dict`), advances them with one foreach launch and lets the kernel form the bias corrections from them
-    (`pvs_adam_clip_step_dev`): the whole step is then two launches that a hipGraph can replay."""
+class _PointerTables:
+    """What the fused optimisers share: the pointer tables of a launch (one row per tensor) travel to the device through a
+    small ring of pinned buffers or, under capture, through pinned tables that belong to the capture; the device blocks of
+    hyper-parameters of the capturable forms. None of it is optimiser state: `state_dict` stays torch's."""
 
-    def __init__(self, params, **kwargs):
-        super().__init__(params, **kwargs)
-        self._reset_transients()
+    _ROW = 5                # int64 columns of a table row
+    _NAME = 'optimiser'
 
     def _reset_transients(self):
         # pointer tables travel through a small ring of pinned buffers: a slot is only rewritten once
@@ -26,13 +26,139 @@ class FusedClipAdam(torch.optim.Adam):
         self._ring, self._slot = [], 0
         self._capture_pool, self._capture_next, self._captured_tables = None, 0, []
         self._recent = {}              # (device, the table's rows) -> ring slot that holds that table on the device
+        self._hyper = {}               # (group index, device) -> 4 doubles on that device (made with the plan)
         self._fast = None
 
     def __setstate__(self, state):
         """copy.deepcopy / pickle of an optimiser carry `defaults`, `state` and `param_groups` only (Optimizer.__getstate__):
-        the copy starts with its own empty upload ring and no work list."""
+        the copy starts with its own empty upload ring, no hyper-parameter blocks and no work list."""
         super().__setstate__(state)
         self._reset_transients()
+
+    def reserve_capture_tables(self, k):
+        """Pinned pointer tables for `k` more captured steps (pinned memory cannot be allocated while a capture is open,
+        and a captured upload must keep its source for as long as the graph is replayed)."""
+        rows = max(64, sum(len(g['params']) for g in self.param_groups))
+        left = 0 if self._capture_pool is None else self._capture_pool.shape[0] - self._capture_next
+        if left < k:
+            self._capture_pool = torch.empty((k, rows, self._ROW), dtype=torch.int64).pin_memory()   # (tables handed out
+            self._capture_next = 0                                                    # stay alive in _captured_tables)
+
+    def zero_grad(self, set_to_none=True):
+        """torch's zero_grad walks hooks, profiler ranges and foreach groups (~100 us on the host for 34 parameters);
+        with set_to_none this is all it does."""
+        if not set_to_none:
+            return super().zero_grad(set_to_none=False)
+        for group in self.param_groups:
+            for p in group['params']:
+                p.grad = None
+
+    def _group_capturable(self, group):
+        return bool(group.get('capturable'))
+
+    def _hyper_block(self, gi, dev):
+        """The device block of group `gi` on `dev` (allocated when the plan is made: never under capture)."""
+        block = self._hyper.get((gi, dev))
+        if block is None:
+            block = self._hyper[(gi, dev)] = torch.zeros(4, dtype=torch.float64, device=dev)
+        return block
+
+    def push_hyperparameters(self):
+        """Writes every capturable group's CURRENT hyper-parameters (Python floats: schedulers keep writing them into
+        `param_groups` as ever) into its device block, on the current stream, with the values as kernel arguments: no
+        staging buffer, nothing to wait for. step() does this itself unless it is being captured - a capture must not
+        contain the write, it would replay the captured values - so whoever replays a captured step calls this before
+        the capture and before every replay."""
+        if not self._hyper:
+            return
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f'{self._NAME}.push_hyperparameters() inside a capture: the write would be replayed with '
+                               f'the captured values - call it before the capture and before every replay')
+        lib = _lib.lib()
+        for (gi, dev), block in self._hyper.items():
+            group = self.param_groups[gi]
+            if not self._group_capturable(group) or isinstance(group['lr'], torch.Tensor):
+                continue
+            vals = self._hyper_values(group)
+            _lib.check(lib.pvs_hyper_write(block.data_ptr(), len(vals), *vals, *([0.0] * (4 - len(vals))), _lib.stream(dev)),
+                       'pvs_hyper_write')
+
+    def _clip_and_torch_step(self, clip_value):
+        """What the kernels do not cover: clip_grad_value_ + torch's own step."""
+        self._fast = None
+        if clip_value is not None:
+            torch.nn.utils.clip_grad_value_([p for g in self.param_groups for p in g['params']], clip_value)
+        super().step()
+
+    def _table(self, key, rows, n, dev, capturing):
+        """The device table of this launch: `rows()` lists its n rows when they have to be uploaded."""
+        if not self._ring or self._ring[0][0].shape[0] < n:
+            cap = max(n, 64)
+            self._ring = [[torch.empty((cap, self._ROW), dtype=torch.int64).pin_memory(),
+                           torch.empty((cap, self._ROW), dtype=torch.int64, device=dev), None] for _ in range(8)]
+            self._recent = {}
+        hit = None if capturing else self._recent.get(key)
+        if hit is not None:
+            # addresses seen before (the caching allocator hands the gradients the same few sets of blocks,
+            # alternating from step to step): that table is still on the device - no upload, and nothing about
+            # these very tensors has to be checked or listed again
+            return self._ring[hit][1]
+        if capturing:
+            # a captured upload is replayed from its pinned source: that buffer belongs to the capture and is
+            # never rewritten (a ring slot would be, by the next eager step)
+            if self._capture_pool is None or self._capture_next >= self._capture_pool.shape[0]:
+                raise RuntimeError(f'{self._NAME}: no pinned table left for this capture - call '
+                                   'reserve_capture_tables(k) (or run one eager capturable step) before capturing')
+            table_host = self._capture_pool[self._capture_next]
+            self._capture_next += 1
+            table_host[:n] = torch.tensor(rows(), dtype=torch.int64)
+            table_dev = torch.empty((n, self._ROW), dtype=torch.int64, device=dev)
+            table_dev.copy_(table_host[:n], non_blocking=True)
+            self._captured_tables.append((table_host, table_dev))
+            return table_dev
+        idx = self._slot
+        slot = self._ring[idx]
+        self._slot = (self._slot + 1) % len(self._ring)
+        if slot[2] is not None:
+            slot[2].synchronize()
+        # (the slot's previous table is forgotten before it is overwritten)
+        self._recent = {k: v for k, v in self._recent.items() if v != idx}
+        table_host, table_dev = slot[0], slot[1]
+        table_host[:n] = torch.tensor(rows(), dtype=torch.int64)
+        table_dev[:n].copy_(table_host[:n], non_blocking=True)
+        slot[2] = torch.cuda.Event()
+        slot[2].record(torch.cuda.current_stream(dev))
+        self._recent[key] = idx
+        return table_dev
+
+    @staticmethod
+    def _tensors_fusable(work):
+        for p in work['params']:
+            g = p.grad
+            if (not p.is_cuda or not g.is_cuda or g.is_sparse or g.layout is not torch.strided
+                    or not g.is_contiguous() or not p.is_contiguous()):
+                return False
+        return True
+
+
+class FusedClipAdam(_PointerTables, torch.optim.Adam):
+    """Drop-in `torch.optim.Adam`; `step(clip_value=c)` first clamps every gradient to [-c, c] in
+    place. Falls back to torch's own implementation whenever a feature the kernel does not cover is
+    on (amsgrad, maximize, differentiable, a tensor learning rate, non-CUDA / non-fp32 parameters).
+    `capturable=True` (round 5) keeps the step counters on the device exactly as torch's capturable Adam does (same
+    `state_dict`), advances them with one foreach launch and lets the kernel form the bias corrections from them, and
+    from the lr and betas that `push_hyperparameters()` wrote to the device (`pvs_adam_clip_step_hyper`): the step
+    itself is then two launches that a hipGraph can replay, under a scheduler too."""
+
+    _NAME = 'FusedClipAdam'
+
+    def __init__(self, params, **kwargs):
+        super().__init__(params, **kwargs)
+        self._reset_transients()
+
+    @staticmethod
+    def _hyper_values(group):
+        return (float(group['lr']), float(group['betas'][0]), float(group['betas'][1]))
 
     def _fusable(self):
         for group in self.param_groups:
@@ -45,24 +171,6 @@ class FusedClipAdam(torch.optim.Adam):
                                            or not p.is_contiguous() or not p.grad.is_contiguous()):
                     return False
         return True
-
-    def reserve_capture_tables(self, k):
-        """Pinned pointer tables for `k` more captured steps (pinned memory cannot be allocated while a capture is open,
-        and a captured upload must keep its source for as long as the graph is replayed)."""
-        rows = max(64, sum(len(g['params']) for g in self.param_groups))
-        left = 0 if self._capture_pool is None else self._capture_pool.shape[0] - self._capture_next
-        if left < k:
-            self._capture_pool = torch.empty((k, rows, 5), dtype=torch.int64).pin_memory()   # (tables handed out stay alive
-            self._capture_next = 0                                                            # in _captured_tables)
-
-    def zero_grad(self, set_to_none=True):
-        """torch's zero_grad walks hooks, profiler ranges and foreach groups (~100 us on the host for 34 parameters);
-        with set_to_none this is all it does."""
-        if not set_to_none:
-            return super().zero_grad(set_to_none=False)
-        for group in self.param_groups:
-            for p in group['params']:
-                p.grad = None
 
     def load_state_dict(self, state_dict):
         """torch's own, then the step counters where THIS optimiser keeps them: on the host for a non-capturable group
@@ -103,22 +211,18 @@ class FusedClipAdam(torch.optim.Adam):
             fast = self._plan(live)
         keys = self._address_keys(fast) if fast['fusable'] else None
         if keys is None:
-            self._fast = None
-            if clip_value is not None:
-                torch.nn.utils.clip_grad_value_([p for g in self.param_groups for p in g['params']], clip_value)
-            super().step()
+            self._clip_and_torch_step(clip_value)
             return loss
         lib = _lib.lib()
         all_works = [work for works in fast['groups'] for work in works]
         # tensors at addresses not seen before are looked at (device, layout, sparsity) BEFORE anything is launched
         if any(self._recent.get(key) is None and not self._tensors_fusable(work) for work, key in zip(all_works, keys)):
-            self._fast = None
-            if clip_value is not None:
-                torch.nn.utils.clip_grad_value_([p for g in self.param_groups for p in g['params']], clip_value)
-            super().step()
+            self._clip_and_torch_step(clip_value)
             return loss
+        if self._hyper and not torch.cuda.is_current_stream_capturing():
+            self.push_hyperparameters()        # (a captured step reads what its caller pushes before each replay)
         keys = iter(keys)
-        for group, works in zip(self.param_groups, fast['groups']):
+        for gi, (group, works) in enumerate(zip(self.param_groups, fast['groups'])):
             beta1, beta2 = group['betas']
             for work in works:            # one launch per distinct step count (one, unless the gradient set changed mid-run)
                 key = next(keys)
@@ -129,54 +233,16 @@ class FusedClipAdam(torch.optim.Adam):
                 work['step'] += 1
                 step, n, dev = work['step'], work['n'], work['dev']
                 capturing = work['on_device'] and torch.cuda.is_current_stream_capturing()
-                if not self._ring or self._ring[0][0].shape[0] < n:
-                    cap = max(n, 64)
-                    self._ring = [[torch.empty((cap, 5), dtype=torch.int64).pin_memory(),
-                                   torch.empty((cap, 5), dtype=torch.int64, device=dev), None] for _ in range(8)]
-                    self._recent = {}
                 if work['on_device'] and not capturing and self._capture_pool is None:
                     self.reserve_capture_tables(8)
-                hit = None if capturing else self._recent.get(key)
-                if hit is not None:
-                    # addresses seen before (the caching allocator hands the gradients the same few sets of blocks,
-                    # alternating from step to step): that table is still on the device - no upload, and nothing about
-                    # these very tensors has to be checked or listed again
-                    table_dev = self._ring[hit][1]
-                else:
-                    rows = [[p.data_ptr(), p.grad.data_ptr(), ea.data_ptr(), es.data_ptr(), p.numel()]
-                            for p, ea, es in work['items']]
-                    if capturing:
-                        # a captured upload is replayed from its pinned source: that buffer belongs to the capture and is
-                        # never rewritten (a ring slot would be, by the next eager step)
-                        if self._capture_pool is None or self._capture_next >= self._capture_pool.shape[0]:
-                            raise RuntimeError('FusedClipAdam: no pinned table left for this capture - call '
-                                               'reserve_capture_tables(k) (or run one eager capturable step) before capturing')
-                        table_host = self._capture_pool[self._capture_next]
-                        self._capture_next += 1
-                        table_host[:n] = torch.tensor(rows, dtype=torch.int64)
-                        table_dev = torch.empty((n, 5), dtype=torch.int64, device=dev)
-                        table_dev.copy_(table_host[:n], non_blocking=True)
-                        self._captured_tables.append((table_host, table_dev))
-                    else:
-                        idx = self._slot
-                        slot = self._ring[idx]
-                        self._slot = (self._slot + 1) % len(self._ring)
-                        if slot[2] is not None:
-                            slot[2].synchronize()
-                        # (the slot's previous table is forgotten before it is overwritten)
-                        self._recent = {k: v for k, v in self._recent.items() if v != idx}
-                        table_host, table_dev = slot[0], slot[1]
-                        table_host[:n] = torch.tensor(rows, dtype=torch.int64)
-                        table_dev[:n].copy_(table_host[:n], non_blocking=True)
-                        slot[2] = torch.cuda.Event()
-                        slot[2].record(torch.cuda.current_stream(dev))
-                        self._recent[key] = idx
+                table_dev = self._table(key, lambda: [[p.data_ptr(), p.grad.data_ptr(), ea.data_ptr(), es.data_ptr(), p.numel()]
+                                                      for p, ea, es in work['items']], n, dev, capturing)
                 if work['on_device']:
-                    _lib.check(lib.pvs_adam_clip_step_dev(
-                        _lib.ptr(table_dev), n, float(group['lr']), float(beta1), float(beta2),
+                    _lib.check(lib.pvs_adam_clip_step_hyper(
+                        _lib.ptr(table_dev), n, work['hyper'].data_ptr(),
                         float(group['eps']), float(group['weight_decay']), work['steps'][0].data_ptr(),
                         float(clip_value) if clip_value is not None else 0.0,
-                        _lib.stream(dev)), 'pvs_adam_clip_step_dev')
+                        _lib.stream(dev)), 'pvs_adam_clip_step_hyper')
                 else:
                     _lib.check(lib.pvs_adam_clip_step(
                         _lib.ptr(table_dev), n, float(group['lr']), float(beta1), float(beta2),
@@ -197,7 +263,7 @@ class FusedClipAdam(torch.optim.Adam):
             self._fast = {'live': live, 'capt': [bool(g.get('capturable')) for g in self.param_groups], 'groups': [],
                           'fusable': False}
             return self._fast
-        for group in self.param_groups:
+        for gi, group in enumerate(self.param_groups):
             by_step = {}
             for p in group['params']:
                 if p.grad is None:
@@ -229,7 +295,8 @@ class FusedClipAdam(torch.optim.Adam):
                 works.append({'items': [(p, st['exp_avg'], st['exp_avg_sq']) for p, st in members],
                               'steps': [st['step'] for _, st in members], 'step': int(count), 'n': len(members),
                               'dev': members[0][0].device, 'params': [p for p, _ in members], 'on_device': on_device,
-                              'steps_base': base})
+                              'steps_base': base,
+                              'hyper': self._hyper_block(gi, members[0][0].device) if on_device else None})
             groups.append(works)
         self._fast = {'live': live, 'capt': [bool(g.get('capturable')) for g in self.param_groups], 'groups': groups,
                       'fusable': fusable}
@@ -259,11 +326,165 @@ class FusedClipAdam(torch.optim.Adam):
                 keys.append(tuple(key))
         return keys
 
+
+class FusedClipSGD(_PointerTables, torch.optim.SGD):
+    """Drop-in `torch.optim.SGD`; `step(clip_value=c)` first clamps every gradient to [-c, c] in place, and clip + step
+    are ONE launch for all parameters (`pvs_sgd_clip_step`): momentum, Nesterov, L2 weight decay - what the reference
+    constructs (point_neural_network_base.py: momentum 0.9, nesterov). The state is torch's (`momentum_buffer`). Falls back
+    to `clip_grad_value_` + torch's own step for whatever the kernel does not cover: CPU or non-fp32 parameters, sparse
+    gradients, maximize, dampening, a tensor learning rate or weight decay, differentiable, torch's `fused` flavour or a
+    gradient scaler's `grad_scale` / `found_inf`.
+    `capturable=True`: lr and momentum are read by the kernel from the device (`pvs_sgd_clip_step_hyper`, written by
+    `push_hyperparameters()`), so that a hipGraph of the step can be replayed under a scheduler. The switch is an
+    attribute of the optimiser, not a group option: `param_groups` and `state_dict()` stay torch's SGD's."""
+
+    _ROW = 4
+    _NAME = 'FusedClipSGD'
+
+    def __init__(self, params, capturable=False, **kwargs):
+        super().__init__(params, **kwargs)
+        self.capturable = bool(capturable)
+        self._reset_transients()
+
+    def __getstate__(self):
+        state = super().__getstate__()
+        state['capturable'] = self.capturable
+        return state
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        self.capturable = bool(self.__dict__.get('capturable', False))
+
+    def load_state_dict(self, state_dict):
+        self._fast = None              # new momentum buffers
+        return super().load_state_dict(state_dict)
+
+    def _group_capturable(self, group):
+        return self.capturable
+
     @staticmethod
-    def _tensors_fusable(work):
-        for p in work['params']:
-            g = p.grad
-            if (not p.is_cuda or not g.is_cuda or g.is_sparse or g.layout is not torch.strided
-                    or not g.is_contiguous() or not p.is_contiguous()):
+    def _hyper_values(group):
+        return (float(group['lr']), float(group['momentum']))
+
+    def _groups_fusable(self):
+        if getattr(self, 'grad_scale', None) is not None or getattr(self, 'found_inf', None) is not None:
+            return False
+        for group in self.param_groups:
+            if group.get('maximize') or group.get('differentiable') or group.get('fused') or group['dampening'] != 0 \
+                    or isinstance(group['lr'], torch.Tensor) or isinstance(group['weight_decay'], torch.Tensor) \
+                    or (group['nesterov'] and group['momentum'] <= 0):
                 return False
         return True
+
+    def _signature(self):
+        return [(self.capturable, group['momentum'] != 0) for group in self.param_groups]
+
+    @torch.no_grad()
+    def step(self, closure=None, clip_value=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        # (the work list is kept from step to step, as FusedClipAdam keeps its own: see there)
+        live = [p.grad is not None for group in self.param_groups for p in group['params']]
+        fast = self._fast
+        if fast is None or fast['live'] != live or fast['sig'] != self._signature():
+            fast = self._plan(live)
+        keys = self._address_keys(fast) if fast['fusable'] else None
+        if keys is None:
+            self._clip_and_torch_step(clip_value)
+            return loss
+        lib = _lib.lib()
+        all_works = [work for works in fast['groups'] for work in works]
+        # tensors at addresses not seen before are looked at (device, layout, sparsity) BEFORE anything is launched
+        if any(self._recent.get(key) is None and not self._tensors_fusable(work) for work, key in zip(all_works, keys)):
+            self._clip_and_torch_step(clip_value)
+            return loss
+        capturing = self.capturable and torch.cuda.is_current_stream_capturing()
+        if self._hyper and not capturing:
+            self.push_hyperparameters()        # (a captured step reads what its caller pushes before each replay)
+        clip = float(clip_value) if clip_value is not None else 0.0
+        keys = iter(keys)
+        replan = False
+        for group, works in zip(self.param_groups, fast['groups']):
+            for work in works:            # one launch, or two while some parameters have no momentum history yet
+                key = next(keys)
+                n, dev = work['n'], work['dev']
+                if work['first'] and capturing:
+                    raise RuntimeError('FusedClipSGD: a parameter takes its first step inside a capture (its momentum '
+                                       'buffer does not exist yet) - run one eager step before capturing')
+                if self.capturable and not capturing and self._capture_pool is None:
+                    self.reserve_capture_tables(8)
+                table_dev = self._table(key, lambda: [[p.data_ptr(), p.grad.data_ptr(), 0 if buf is None else buf.data_ptr(),
+                                                       p.numel()] for p, buf in work['items']], n, dev, capturing)
+                if work['hyper'] is not None and not work['first']:
+                    _lib.check(lib.pvs_sgd_clip_step_hyper(
+                        _lib.ptr(table_dev), n, work['hyper'].data_ptr(), float(group['weight_decay']),
+                        int(bool(group['nesterov'])), clip, _lib.stream(dev)), 'pvs_sgd_clip_step_hyper')
+                else:
+                    _lib.check(lib.pvs_sgd_clip_step(
+                        _lib.ptr(table_dev), n, float(group['lr']), float(group['momentum']), float(group['weight_decay']),
+                        int(bool(group['nesterov'])), int(work['first']), clip, _lib.stream(dev)), 'pvs_sgd_clip_step')
+                if work['first']:          # the launch filled the new buffers: they are state from here on
+                    for p, buf in work['items']:
+                        self.state[p]['momentum_buffer'] = buf
+                    replan = True
+                # the kernel wrote through raw pointers: tell autograd (and anything that caches by
+                # version, e.g. ReceptorScreen) that the parameters changed, as an in-place op would
+                torch.autograd.graph.increment_version(work['params'])
+        if replan:
+            self._fast = None
+        return loss
+
+    def _plan(self, live):
+        """The work list of step(): per group the parameters with gradients, those that have a momentum buffer apart
+        from those that get one in this step (`first`: torch clones the gradient into it)."""
+        groups, fusable = [], self._groups_fusable()
+        self._recent = {}      # (remembered tables hold the OLD plan's buffer addresses: they are not in the key)
+        for gi, group in enumerate(self.param_groups):
+            works = []
+            if fusable:
+                with_momentum = group['momentum'] != 0
+                old, new = [], []
+                for p in group['params']:
+                    if p.grad is None:
+                        continue
+                    if p.dtype != torch.float32 or not p.is_cuda:
+                        fusable = False
+                        break
+                    buf = self.state[p].get('momentum_buffer') if with_momentum else None
+                    if with_momentum and buf is None:
+                        new.append((p, torch.empty_like(p, memory_format=torch.preserve_format)))
+                    elif buf is not None and (buf.dtype != torch.float32 or buf.device != p.device
+                                              or not buf.is_contiguous()):
+                        fusable = False
+                        break
+                    else:
+                        old.append((p, buf))
+                for first, members in ((False, old), (True, new)):
+                    if members and fusable:
+                        dev = members[0][0].device
+                        works.append({'items': members, 'params': [p for p, _ in members], 'n': len(members), 'dev': dev,
+                                      'first': first, 'hyper': self._hyper_block(gi, dev) if self.capturable else None})
+            groups.append(works)
+        self._fast = {'live': live, 'sig': self._signature(), 'groups': groups if fusable else [], 'fusable': fusable}
+        return self._fast
+
+    def _address_keys(self, fast):
+        """Per work item the tuple of (parameter, gradient) addresses of this step - what the pointer table on the device
+        is remembered by - or None when the fused kernel must not run (FusedClipAdam._address_keys)."""
+        if not self._groups_fusable():
+            return None
+        f32 = torch.float32
+        keys = []
+        for works in fast['groups']:
+            for work in works:
+                key = [work['dev'], work['first']]
+                for p in work['params']:
+                    g = p.grad
+                    if p.dtype is not f32 or g.dtype is not f32:
+                        return None
+                    key.append(p.data_ptr())
+                    key.append(g.data_ptr())
+                keys.append(tuple(key))
+        return keys

@@ -26,7 +26,7 @@ from torch import nn
 
 from . import functional as PF
 from .global_objects import DEVICE
-from .optim import FusedClipAdam
+from .optim import FusedClipAdam, FusedClipSGD
 
 
 def _rank_world():
@@ -64,25 +64,32 @@ def long_lived_heap_frozen():
 _FROZEN_DEPTH = 0
 
 class _StepReplayer:
-    """train_model(capture=True): whole training steps (graph preparation, forward, loss, backward, clip + Adam) as
+    """train_model(capture=True): whole training steps (graph preparation, forward, loss, backward, clip + optimiser) as
     hipGraphs, one per batch that comes back with the same device tensors. A batch runs eagerly on its first visit
     (which also warms up whatever its shapes need), is captured and replayed on its second, replayed from then on; at
     most `max_graphs` batches are captured, the rest stay eager. Everything - eager steps too - runs on ONE side stream:
     autograd's AccumulateGrad nodes remember the stream of their first backward, and a capture on another stream than
     earlier eager steps faults in hipStreamEndCapture (ROCm 7.2 / torch 2.10; bench.py --graph 1 does the same).
-    The optimiser runs in its capturable form for the duration (step counters on the device, as torch's capturable Adam
-    keeps them; FusedClipAdam then forms the bias corrections in its kernel: optim.py) and is restored on close()."""
+    The optimiser runs in its capturable form for the duration (Adam: step counters on the device, as torch's capturable
+    Adam keeps them; FusedClipAdam then forms the bias corrections in its kernel: optim.py) and is restored on close().
+    What a learning-rate scheduler changes between steps (lr; OneCycleLR: beta1 / momentum too) is no part of a capture:
+    the fused optimisers' kernels read it from device memory, and step() has the groups' current values written there
+    (`push_hyperparameters`, on the replayer's stream) before the capture and before every replay - an eager step does
+    that itself. `scheduler.step()` stays on the host, after the optimiser step (_train_epochs): a captured run's
+    rates are the eager run's, double for double."""
 
     def __init__(self, model, max_graphs=64):
         if not torch.cuda.is_available():
             raise RuntimeError('train_model(capture=True) needs a GPU')
         if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
             raise NotImplementedError('train_model(capture=True) is single-process (the gradient exchange is not captured)')
-        if model.scheduler is not None:
-            raise NotImplementedError('train_model(capture=True) with a learning-rate scheduler (the rate is baked '
-                                      'into the captured optimiser step)')
-        if not isinstance(model.optimiser, torch.optim.Adam):
-            raise NotImplementedError('train_model(capture=True) needs the Adam optimiser')
+        if not isinstance(model.optimiser, (torch.optim.Adam, FusedClipSGD)):
+            raise TypeError(f'train_model(capture=True) replays FusedClipAdam, FusedClipSGD or torch.optim.Adam steps, '
+                            f'not {type(model.optimiser).__name__}')
+        self._push = getattr(model.optimiser, 'push_hyperparameters', None)
+        if model.scheduler is not None and self._push is None:
+            raise TypeError("train_model(capture=True) with a learning-rate scheduler needs one of the project's fused "
+                            'optimisers (torch.optim.Adam bakes a float rate into the captured step)')
         if any(p.dtype == torch.float64 for p in model.parameters()):
             raise NotImplementedError('train_model(capture=True) is fp32 only (fp64 trains eagerly)')
         self.model, self.max_graphs = model, max_graphs
@@ -93,15 +100,19 @@ class _StepReplayer:
         self.seen, self.graphs = {}, {}
         self.stats = {'eager': 0, 'captured': 0, 'replayed': 0}
         model.last_capture_stats = self.stats
-        self._was = []
-        model._capturable_was = self._was       # save() writes the optimiser's OWN form, not the replayer's
-        for group in model.optimiser.param_groups:
-            self._was.append(group.get('capturable', False))
-            group['capturable'] = True
-            for p in group['params']:
-                st = model.optimiser.state.get(p)
-                if st and isinstance(st.get('step'), torch.Tensor) and not st['step'].is_cuda:
-                    st['step'] = st['step'].to(device=p.device, dtype=torch.float32)
+        self._was, self._sgd_was = [], None
+        if isinstance(model.optimiser, FusedClipSGD):
+            # (a switch on the optimiser - no group option, no state: checkpoints written meanwhile need no care)
+            self._sgd_was, model.optimiser.capturable = model.optimiser.capturable, True
+        else:
+            model._capturable_was = self._was       # save() writes the optimiser's OWN form, not the replayer's
+            for group in model.optimiser.param_groups:
+                self._was.append(group.get('capturable', False))
+                group['capturable'] = True
+                for p in group['params']:
+                    st = model.optimiser.state.get(p)
+                    if st and isinstance(st.get('step'), torch.Tensor) and not st['step'].is_cuda:
+                        st['step'] = st['step'].to(device=p.device, dtype=torch.float32)
         model.optimiser._fast = None
         if hasattr(model.optimiser, 'reserve_capture_tables'):
             model.optimiser.reserve_capture_tables(max_graphs)
@@ -110,6 +121,8 @@ class _StepReplayer:
         torch.cuda.current_stream(DEVICE).wait_stream(self.stream)
         self.graphs.clear()
         opt = self.model.optimiser
+        if self._sgd_was is not None:
+            opt.capturable = self._sgd_was
         for group, was in zip(opt.param_groups, self._was):
             group['capturable'] = was
             if not was:
@@ -166,6 +179,8 @@ class _StepReplayer:
         key = self._key(graph, self.model.model_task)
         hit = self.graphs.get(key) if key is not None else None
         if hit is not None:
+            if self._push is not None:
+                self._push()
             hit[0].replay()
             self.stats['replayed'] += 1
             return hit[1].clone()
@@ -181,6 +196,8 @@ class _StepReplayer:
         cache_was, pgraph.CACHE_ENABLED = pgraph.CACHE_ENABLED, False
         try:
             self.stream.synchronize()
+            if self._push is not None:
+                self._push()                 # (outside the capture: what the replay just below runs at)
             hip_graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(hip_graph, stream=self.stream):
                 static_loss = self._eager(graph)
@@ -221,8 +238,9 @@ class PointNeuralNetworkBase(nn.Module):
             # torch.optim.Adam subclass: same rule and state_dict, one launch for clip + step on the GPU
             self.optimiser = FusedClipAdam(self.parameters(), lr=self.lr, weight_decay=weight_decay or 0)
         elif optimiser == 'sgd':
-            self.optimiser = torch.optim.SGD(self.parameters(), lr=self.lr, momentum=0.9,
-                                             weight_decay=weight_decay or 0, nesterov=True)
+            # torch.optim.SGD subclass, likewise (the reference's arguments)
+            self.optimiser = FusedClipSGD(self.parameters(), lr=self.lr, momentum=0.9,
+                                          weight_decay=weight_decay or 0, nesterov=True)
         else:
             raise NotImplementedError(f'{optimiser} not recognised optimiser.')
         assert not (use_1cycle and warm_restarts), '1cycle and warm restarts are mutually exclusive'
@@ -271,7 +289,7 @@ class PointNeuralNetworkBase(nn.Module):
             loss.backward()
         if self.grad_sync is not None:
             self.grad_sync()
-        if isinstance(self.optimiser, FusedClipAdam):
+        if isinstance(self.optimiser, (FusedClipAdam, FusedClipSGD)):
             self.optimiser.step(clip_value=1.0)
         else:
             torch.nn.utils.clip_grad_value_(self.parameters(), 1.0)
@@ -313,8 +331,10 @@ class PointNeuralNetworkBase(nn.Module):
         epoch, e.g. a list of pre-collated batches resident on the GPU - are replayed from a hipGraph of their whole
         step from their third visit on (`_StepReplayer`). For small graphs the eager step is bound by the host
         (~70 launches of a few microseconds: 16.8k -> 25.7k graphs/s at the reference's default shape,
-        profiles/r05_real_shape.txt); for BASELINE-size batches it buys nothing. Single process, no learning-rate
-        scheduler, Adam; anything else raises."""
+        profiles/r05_real_shape.txt); for BASELINE-size batches it buys nothing. Works with either optimiser the
+        constructor builds (Adam, SGD) and under either scheduler (`use_1cycle`, `warm_restarts`): the fused optimisers
+        read lr, betas / momentum from device memory, rewritten from the host's values before every replay, so the rates
+        of a captured run are the eager run's. Single process, fp32; anything else raises."""
         init_epoch, _ = self.training_setup(data_loader=data_loader, epochs=epochs)
         if capture:
             replayer = _StepReplayer(self)
