@@ -320,6 +320,52 @@ int pvs_screen_graph_build_ragged(const float* lig_pos, const int32_t* lig_ptr, 
                                   const PvsRaggedNodeTables* tables, int32_t* status, void* state,
                                   size_t state_bytes, pvs_stream_t stream);
 
+/* Complex batches: the node tables of B protein-ligand complexes built from a device-resident pool of structure
+ * files, as the reference loader builds one sample on the host (data_loaders.py:259-309: ligand then receptor, crop of
+ * the receptor to the atoms closer than `radius` to some ligand atom - fp64, scipy's cdist decision -, hydrogen filter
+ * after the crop, make_bit_vector features, fp32 coordinates).
+ *   pool: every unique receptor / ligand file once. *_xyz [atoms,3] fp64 as stored, *_types (smina type) and *_z
+ *     (atomic number) [atoms] int32, rec_ptr [n_rec+1] / lig_ptr [n_lig+1] int32 atom offsets of the files.
+ *   pairs [B,3] int32: receptor id, ligand id, offset of the sample's flags in the workspace (the running sum of
+ *     ligand + receptor atom counts of the samples before it; n_atoms_in = that sum over the whole batch).
+ *   lig_xform [B,3,3] fp64 or NULL: ligand coordinates become x @ M before anything else (augmented actives; products
+ *     and sums rounded one by one, x0*M0j + x1*M1j, then + x2*M2j). rot [B,3,3] fp64 or NULL: applied the same way
+ *     to `pos` only.
+ * _count: counts [B,2] = kept ligand atoms, kept receptor atoms of every sample; one flag per input atom in the
+ *   workspace. *status is reset, then bit 0 = a pair outside the pool or the workspace, bit 1 = a ligand of more than
+ *   1024 atoms (the counts of such a sample are 0).
+ * _fill (same pool, pairs, lig_xform, workspace; graph_ptr [B+1] = the running sum of the counts, total_nodes its
+ *   last entry): x [N,F] (F = n_features + 1 compact, else 2 n_features; class = smina type, or class_of_z
+ *   [128][atomic number] with numbers outside the table in class n_features; receptor classes + n_features), pos [N,3],
+ *   pos_graph [N,3] or NULL (the coordinates before `rot`: what the edge list is built from), bp [N] (0 ligand,
+ *   1 receptor), batch [N] int64. Node order per sample: ligand atoms in file order, then the surviving receptor atoms
+ *   in file order. *status: bit 2 = a class outside the encoding (one_hot of the reference raises), bit 3 = graph_ptr
+ *   does not match the counts (nothing is written outside a sample's rows).
+ * pvs_complex_edges: the arrays of pvs_radius_graph_fill over the batch -> the loader's edge list, graph by graph the
+ *   inter block then the intra block, each row-major (the 'generate_edges' layout): edge_index [2,E] int64, edge_attr
+ *   [E,3] int64 one-hot. *status bit 4 = inconsistent tables. Bitwise reproducible; no host synchronisation in any. */
+typedef struct {
+    const double *rec_xyz, *lig_xyz;
+    const int32_t *rec_types, *lig_types, *rec_z, *lig_z;
+    const int32_t *rec_ptr, *lig_ptr;
+    int32_t n_rec, n_lig;
+} PvsComplexPool;
+size_t pvs_complex_batch_workspace_bytes(int32_t n_samples, int32_t n_atoms_in);
+int pvs_complex_batch_count(const PvsComplexPool* pool, const int32_t* pairs, const double* lig_xform,
+                            int32_t n_samples, int32_t n_atoms_in, double radius, int32_t keep_hydrogens,
+                            int32_t* counts, int32_t* status, void* workspace, size_t workspace_bytes,
+                            pvs_stream_t stream);
+int pvs_complex_batch_fill(const PvsComplexPool* pool, const int32_t* pairs, const double* lig_xform,
+                           const double* rot, int32_t n_samples, int32_t n_atoms_in, int32_t total_nodes,
+                           int32_t use_atomic_numbers, int32_t n_features, int32_t compact, const int32_t* class_of_z,
+                           const int32_t* counts, const int32_t* graph_ptr, float* x, float* pos, float* pos_graph,
+                           uint8_t* bp, int64_t* batch, int32_t* status, const void* workspace,
+                           size_t workspace_bytes, pvs_stream_t stream);
+int pvs_complex_edges(int32_t n_nodes, int32_t n_edges, int32_t n_graphs, const int32_t* graph_ptr,
+                      const int32_t* rowptr, const int32_t* inter_ptr, const int32_t* intra_ptr, const int32_t* row,
+                      const int32_t* col, const uint8_t* etype, const int32_t* perm, int64_t* edge_index,
+                      int64_t* edge_attr, int32_t* status, pvs_stream_t stream);
+
 /* Leave-out graph batch of masking attribution (the reference's atom_masking / bond_masking loops,
  * attribution/attribution_fns.py:39-115, 356-456, which rebuild one masked edge list per atom on the host).
  * `parent`: the prepared graph of ONE complex (rowptr / col / etype; host-side edge count); drop [n_masks, 2] int32:

@@ -8,14 +8,22 @@ checkpoints/, predictions files).
     python point_vs.py multitask /tmp/run --model_task both -ea 1 -ep 1 --layers 3 \\
         --train_data_root_pose graphs/pose --train_data_root_affinity graphs/affinity ...
 
-Data sources. Turning parquet structure files into graphs is the reference's CPU data layer and is
-outside the hot-path scope; this entry reads
+Data sources. This entry reads
+  * a PointVS data root, as the reference does: parquet structure files (`receptors/*.parquet`,
+    `ligands/**/*.parquet`, or any layout the types file names) below --*_data_root_* and the types file of
+    --*_types_*. Every unique file is read once into a pool in device memory and the complexes of a batch are built on
+    the GPU (pointvs_amd/parquet_data.py, csrc/complex_build.hip: crop to --radius around the ligand, hydrogen filter,
+    one-hot features, the --edge_radius graph), honouring --radius, --hydrogens, --use_atomic_numbers, --compact,
+    --extended_atom_types, --estimate_bonds, --augmented_actives, --min_aug_angle, --max_active_rmsd,
+    --min_inactive_rmsd, --max_inactive_rmsd and --p_noise. Not built there, and refused by name: --prune,
+    --p_remove_entity > 0, --include_strain_info, --synthpharm, and --hydrogens without --use_atomic_numbers;
   * a data root holding one `.npz` per graph: `x [N,F]`, `pos [N,3]`, `y`, and either
     `edge_index [2,E]` + `edge_type [E]` (as the reference's loader emits them; an optional
     `edge_layout = 'generate_edges'` entry promises that order and selects the sort-free preparation) or, without edges,
     the ligand/receptor bit in the last column of `x` - the radius graph is then built on the GPU
     with --edge_radius (pvs_radius_graph_*); a types file, when given, lists the files to use
-    (last column = file name relative to the root, first column = label);
+    (last column = file name relative to the root, first column = label); a root is read this way when it holds
+    `.npz` files or no parquet file;
   * `--synthetic_graphs N`: N synthetic protein-ligand radius graphs (SURVEY.md §8d generator).
 One process per GPU under `python -m torch.distributed.run`: ranks draw disjoint shares of one
 seeded sample sequence (pointvs_amd/data_loaders.py) and exchange gradients over RCCL
@@ -76,8 +84,8 @@ class NpzGraphs:
             self.files = sorted(self.root.glob(f'**/*.{suffix}'))
             self.labels = None
         if not self.files:
-            raise FileNotFoundError(f'no .{suffix} graphs under {self.root} (parquet structure files are '
-                                    f'the reference\'s CPU data layer, outside this entry: see the docstring)')
+            raise FileNotFoundError(f'no .{suffix} graphs and no parquet structure files under {self.root} (see the '
+                                    f'docstring for the two kinds of data root)')
         self.feature_dim = int(np.load(self.files[0])['x'].shape[1])
 
     def __len__(self):
@@ -139,12 +147,43 @@ class _WithRadiusGraph:
             yield batch
 
 
+def is_parquet_root(root, suffix='parquet'):
+    """A PointVS data root: structure files with the --input_suffix (parquet) somewhere below it and no `.npz` graph."""
+    root = Path(root).expanduser()
+    suffix = suffix.lstrip('.')
+    if not suffix.endswith('parquet') or not root.is_dir():
+        return False
+    return next(root.glob(f'**/*.{suffix}'), None) is not None and next(root.glob('**/*.npz'), None) is None
+
+
+def make_parquet_loader(args, root, types_fname, mode, task, rank, world, seed0):
+    """The reference's get_data_loader calls (/root/reference/point_vs.py:108-185): the data flags go to every loader,
+    the augmentation / RMSD-labelling / noise flags to the training loaders only; rot=False as there."""
+    from pointvs_amd.global_objects import DEVICE
+    from pointvs_amd.parquet_data import PygPointCloudDataset, SynthPharmDataset, get_data_loader
+    kwargs = dict(batch_size=args.batch_size, compact=args.compact, radius=args.radius,
+                  use_atomic_numbers=args.use_atomic_numbers, rot=False, polar_hydrogens=args.hydrogens,
+                  fname_suffix=args.input_suffix, edge_radius=args.edge_radius, estimate_bonds=args.estimate_bonds,
+                  prune=args.prune, extended_atom_types=args.extended_atom_types,
+                  include_strain_info=args.include_strain_info)
+    if mode == 'train':
+        kwargs.update(augmented_actives=args.augmented_actives, min_aug_angle=args.min_aug_angle,
+                      max_active_rms_distance=args.max_active_rmsd, min_inactive_rms_distance=args.min_inactive_rmsd,
+                      max_inactive_rms_distance=args.max_inactive_rmsd, p_noise=args.p_noise,
+                      p_remove_entity=args.p_remove_entity)
+    dataset_class = SynthPharmDataset if (args.synthpharm or args.synth_pharm) else PygPointCloudDataset
+    return get_data_loader(root, dataset_class, types_fname=types_fname, mode=mode, model_task=task, rank=rank,
+                           world=world, seed=seed0, device=DEVICE, **kwargs)
+
+
 def make_loader(args, root, types_fname, mode, task, rank, world, seed0):
     from pointvs_amd.data_loaders import GraphLoader, RankWeightedSampler, class_balance_weights
     from pointvs_amd.distributed import shard_range
     from pointvs_amd.global_objects import DEVICE
     if args.synthetic_graphs:
         ds = SyntheticGraphs(args.synthetic_graphs, args.synthetic_atoms, args.edge_radius, task, seed0)
+    elif root is not None and is_parquet_root(root, args.input_suffix):
+        return make_parquet_loader(args, root, types_fname, mode, task, rank, world, seed0)
     elif root is not None:
         ds = NpzGraphs(root, types_fname, task, 'npz')
     else:
@@ -213,7 +252,7 @@ def main(argv=None):
                            regression_task, rank, world, 4000) if args.model_task != 'classification' else None
     first = train_pose or train_aff or test_pose or test_aff
     if first is None:
-        raise SystemExit('no data: give a data root of .npz graphs or --synthetic_graphs N')
+        raise SystemExit('no data: give a data root (parquet structure files or .npz graphs) or --synthetic_graphs N')
 
     model_kwargs = model_kwargs_from_args(args, first.dataset.feature_dim, regression_task)
     if args.model_task == 'both':

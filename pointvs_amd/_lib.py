@@ -52,6 +52,11 @@ class PvsRaggedNodeTables(C.Structure):
         'lig_feats', 'rec_feats', 'rec_magg', 'rec_xsum', 'rec_deg', 'feats', 'base_magg', 'base_xsum', 'base_deg')]
 
 
+class PvsComplexPool(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in ('rec_xyz', 'lig_xyz', 'rec_types', 'lig_types', 'rec_z', 'lig_z',
+                                                'rec_ptr', 'lig_ptr')] + [('n_rec', C.c_int32), ('n_lig', C.c_int32)]
+
+
 class PvsStackStrides(C.Structure):
     _fields_ = [(name, C.c_int64) for name in ('h_mid', 'x_mid', 'att', 'node_att', 'saved')]
 
@@ -100,6 +105,13 @@ _PROTOTYPES = {
     'pvs_mask_graph_workspace_bytes': (C.c_size_t, [C.c_int32, C.c_int32]),
     'pvs_mask_graph_build': (C.c_int, [C.POINTER(PvsGraph), C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32] +
                              [C.c_void_p] * 9 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    'pvs_complex_batch_workspace_bytes': (C.c_size_t, [C.c_int32, C.c_int32]),
+    'pvs_complex_batch_count': (C.c_int, [C.POINTER(PvsComplexPool), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                          C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                          C.c_void_p]),
+    'pvs_complex_batch_fill': (C.c_int, [C.POINTER(PvsComplexPool), C.c_void_p, C.c_void_p, C.c_void_p] +
+                               [C.c_int32] * 6 + [C.c_void_p] * 9 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    'pvs_complex_edges': (C.c_int, [C.c_int32] * 3 + [C.c_void_p] * 12),
     'pvs_graph_filter_workspace_bytes': (C.c_size_t, [C.c_int32]),
     'pvs_graph_filter_ligand_edges': (C.c_int, [C.POINTER(PvsGraph), C.c_void_p, C.c_int32] + [C.c_void_p] * 5 +
                                       [C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -168,7 +180,7 @@ _PROTOTYPES = {
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)
-MIN_VERSION = 104       # pvs_version() of the library these prototypes describe (104: device hyper-parameters, fused SGD)
+MIN_VERSION = 105       # pvs_version() of the library these prototypes describe (105: complex batches from a structure pool)
 _lib = None
 
 
