@@ -2,12 +2,19 @@
 #pragma once
 #include "common.h"
 
-// y[n*ldy + c] (=|+=) b[c] + sum_k x[n*ldx+k] * W[c*swc + k*swk] + sum_k2 x2[n*ldx2+k2] * W2[c*swc2 + k2*swk2]
-int pvs_launch_linear(hipStream_t s, float* y, int ldy, const float* x, int ldx, const float* W,
-                      int swc, int swk, const float* b, const float* x2, int ldx2, const float* W2,
-                      int swc2, int swk2, int N, int K, int K2, int C, bool accumulate, int epi = 0,
-                      const float* aux_in = nullptr, int ld_in = 0, float* aux_out = nullptr, int ld_out = 0,
-                      const struct PvsLinearExt* ext = nullptr);
+// One (input, weight) pair of a node-level product: its term of output (n, c) is sum_k x[n*ldx + k] * W[c*swc + k*swk], k < K.
+struct PvsLinearOperand {
+    const float* x = nullptr;
+    int ldx = 0;
+    const float* W = nullptr;
+    int swc = 0, swk = 0;
+    int K = 0;                    // 0: no such operand
+};
+// x times the weight as stored, W = [C][K] in rows of stride ld (y = x W^T: a Linear's forward)
+inline PvsLinearOperand pvs_operand(const float* x, int ldx, const float* W, int ld, int K) { return {x, ldx, W, ld, 1, K}; }
+// x times the weight transposed, W = [K][C] in rows of stride ld (y = x W: a Linear's input gradient)
+inline PvsLinearOperand pvs_operand_t(const float* x, int ldx, const float* W, int ld, int K) { return {x, ldx, W, 1, ld, K}; }
+
 // Extras of the MFMA linear (shapes of pvs_linear_epilogue_supported only; launches folded into a product that deals
 // the node rows to its lanes anyway):
 struct PvsLinearExt {
@@ -32,8 +39,33 @@ struct PvsLinearExt {
 // elementwise epilogue on the product (only on the MFMA path: check first):
 //   1: aux_out = SiLU(y)   2: aux_out = aux_in + y   3: y *= SiLU'(aux_in)   4: aux_out = y
 enum { PVS_EPI_NONE = 0, PVS_EPI_SILU_OUT = 1, PVS_EPI_ADD_OUT = 2, PVS_EPI_MUL_SILU_GRAD = 3, PVS_EPI_COPY_OUT = 4 };
-bool pvs_linear_epilogue_supported(int ldy, int ldx, int ldx2, int K, int K2, int C, const void* y,
-                                   const void* x, const void* x2);
+
+// A node-level product as a job description:
+//   y[n*ldy + c] (=|+=) bias[c] + (term of a) + (term of b),  n < N, c < C
+struct PvsLinearJob {
+    float* y = nullptr;
+    int ldy = 0;
+    PvsLinearOperand a, b;        // b.K == 0: one operand
+    const float* bias = nullptr;
+    int N = 0, C = 0;
+    bool accumulate = false;
+    int epi = PVS_EPI_NONE;
+    const float* aux_in = nullptr;
+    int ld_in = 0;
+    float* aux_out = nullptr;
+    int ld_out = 0;
+    const PvsLinearExt* ext = nullptr;
+};
+// the fields every job has (and the bias most have); the others by name
+inline PvsLinearJob pvs_linear_job(float* y, int ldy, const PvsLinearOperand& a, int N, int C, const float* bias = nullptr) {
+    PvsLinearJob j;
+    j.y = y; j.ldy = ldy; j.a = a; j.N = N; j.C = C; j.bias = bias;
+    return j;
+}
+int pvs_launch_linear(hipStream_t s, const PvsLinearJob& job);
+// Does the MFMA path (the only one with epilogues and extras) take this job? Asked of the very job that is launched; of a
+// grouped job (ext->groups > 1) it is the question for one group's C / groups columns.
+bool pvs_linear_epilogue_supported(const PvsLinearJob& job);
 
 // The node MLP of a layer as one launch each way (H = 32, 64; layers without GraphNorm and without rezero / gated
 // residual; node attention (natt_w != NULL) and the plain residual are part of the chain):
@@ -167,6 +199,13 @@ struct PvsNodeWgradSlabs { const float* slabs = nullptr; int n_slabs = 0, width 
 // (W1 = edge_mlp.0's weight, row stride ld1) - the product of this point of the backward that does not depend on the
 // weight gradients - as further workgroups.
 struct PvsGhJob { float* g_h = nullptr; const float* gPQ = nullptr; const float* W1 = nullptr; int ld1 = 0, off_q = 0, blocks = 0; };
+// the same product as a launch of its own: one job with the two (input, weight) pairs
+inline PvsLinearJob pvs_gh_linear_job(const PvsGhJob& gh, int N, int H) {
+    PvsLinearJob j = pvs_linear_job(gh.g_h, H, pvs_operand_t(gh.gPQ, 2 * H, gh.W1, gh.ld1, H), N, H);
+    j.b = pvs_operand_t(gh.gPQ + H, 2 * H, gh.W1 + gh.off_q, gh.ld1, H);
+    j.accumulate = true;
+    return j;
+}
 int pvs_launch_node_wgrads(hipStream_t s, int H, int N, const PvsNodeWgradIn& in, const PvsNodeWgradOut& out,
                            float* slabs, bool scatter = true, const float** gsum_out = nullptr,
                            const PvsReduce2Args* extra = nullptr, PvsNodeWgradSlabs* slabs_out = nullptr,

@@ -986,24 +986,31 @@ int pvs_colreduce_blocks(int N) {
 
 static int rows_per_block_for(int N, int blocks) { return (N + blocks - 1) / blocks; }
 
-bool pvs_linear_epilogue_supported(int ldy, int ldx, int ldx2, int K, int K2, int C, const void* y,
-                                   const void* x, const void* x2) {
-    const int KK = K + K2;
-    const bool aligned16 = ((ldx | ldy | ldx2) & 3) == 0 && (((uintptr_t)x | (uintptr_t)y | (uintptr_t)x2) & 15) == 0;
+bool pvs_linear_epilogue_supported(const PvsLinearJob& j) {
+    const int groups = j.ext && j.ext->groups > 1 ? j.ext->groups : 1;
+    const int K = j.a.K, K2 = j.b.K, KK = K + K2, C = j.C / groups, ldx2 = j.b.x ? j.b.ldx : 0;
+    const bool aligned16 = ((j.a.ldx | j.ldy | ldx2) & 3) == 0 &&
+                           (((uintptr_t)j.a.x | (uintptr_t)j.y | (uintptr_t)j.b.x) & 15) == 0;
     return aligned16 && K % 32 == 0 && K2 % 32 == 0 && C % 32 == 0 && C <= 64 && (KK == 32 || KK == 64 || KK == 128);
 }
 
-int pvs_launch_linear(hipStream_t s, float* y, int ldy, const float* x, int ldx, const float* W,
-                      int swc, int swk, const float* b, const float* x2, int ldx2, const float* W2,
-                      int swc2, int swk2, int N, int K, int K2, int C, bool accumulate, int epi,
-                      const float* aux_in, int ld_in, float* aux_out, int ld_out, const PvsLinearExt* ext) {
+int pvs_launch_linear(hipStream_t s, const PvsLinearJob& j) {
+    float* const y = j.y;
+    const float *const x = j.a.x, *const W = j.a.W, *const x2 = j.b.x, *const W2 = j.b.W, *const b = j.bias;
+    const int ldy = j.ldy, ldx = j.a.ldx, swc = j.a.swc, swk = j.a.swk, K = j.a.K;
+    const int ldx2 = j.b.ldx, swc2 = j.b.swc, swk2 = j.b.swk, K2 = j.b.K;
+    const int N = j.N, C = j.C, epi = j.epi, ld_in = j.ld_in, ld_out = j.ld_out;
+    const bool accumulate = j.accumulate;
+    const float* const aux_in = j.aux_in;
+    float* const aux_out = j.aux_out;
+    const PvsLinearExt* const ext = j.ext;
     PVS_REQUIRE(C >= 1, "linear: n_out %d unsupported", C);
     if (ext && ext->groups > 1) {
         // `groups` sets of workgroups, each the product for its own C / groups output columns (one launch, grid.y)
         const int G = ext->groups, Cg = C / G;
         PVS_REQUIRE(C % G == 0 && epi == 0 && !ext->y1 && !x2 && K2 == 0 &&
                     ext->zero_w % 4 == 0 && (ext->zero_ld & 3) == 0 && ((uintptr_t)ext->zero_rows & 15) == 0 &&
-                    pvs_linear_epilogue_supported(ldy, ldx, 0, K, 0, Cg, y, x, nullptr),
+                    pvs_linear_epilogue_supported(j),
                     "linear: grouped launch of %d x %d outputs unsupported", G, Cg);
         if (N <= 0) return 0;
         const int rows_g = N >= 32768 ? 256 : 128;
@@ -1026,25 +1033,30 @@ int pvs_launch_linear(hipStream_t s, float* y, int ldy, const float* x, int ldx,
         PVS_CHECK_LAUNCH();
         return 0;
     }
-    PVS_REQUIRE(!ext || (pvs_linear_epilogue_supported(ldy, ldx, x2 ? ldx2 : 0, K, K2, C, y, x, x2) &&
+    PVS_REQUIRE(!ext || (pvs_linear_epilogue_supported(j) &&
                          ext->zero_w % 8 == 0 && (ext->zero_ld & 3) == 0 && ((uintptr_t)ext->zero_rows & 15) == 0 &&
                          (!ext->y1 || (C == 64 && (ext->ldy1 & 3) == 0 && ((uintptr_t)ext->y1 & 15) == 0))),
                 "linear: the extras need the MFMA path");
     const PvsLinearExt ext_v = ext ? *ext : PvsLinearExt{};
+    // output columns [c0, c0 + width) of one operand's term as a plain job of its own
+    auto chunk = [&](PvsLinearOperand op, int c0, int width, const float* bias, bool acc) {
+        op.W += (size_t)c0 * op.swc;
+        PvsLinearJob c = pvs_linear_job(y + c0, ldy, op, N, width, bias ? bias + c0 : nullptr);
+        c.accumulate = acc;
+        return c;
+    };
     if (C > kThreads) {
         // more output channels than one pass holds (one per thread): chunks of the output dimension (the input
         // gradient of a layer whose input is wider than 256: edge_mlp.0 at hidden size 128 on the decomposed path)
         PVS_REQUIRE(epi == 0 && !x2, "linear: n_out %d > %d needs the plain form", C, kThreads);
         PvsProfScope prof(s, PVS_PROF_LIN_CHUNK256);
         for (int c0 = 0; c0 < C; c0 += kThreads) {
-            const int rc = pvs_launch_linear(s, y + c0, ldy, x, ldx, W + (size_t)c0 * swc, swc, swk, b ? b + c0 : nullptr,
-                                             nullptr, 0, nullptr, 0, 0, N, K, 0, C - c0 < kThreads ? C - c0 : kThreads,
-                                             accumulate, 0, nullptr, 0, nullptr, 0);
+            const int rc = pvs_launch_linear(s, chunk(j.a, c0, C - c0 < kThreads ? C - c0 : kThreads, b, accumulate));
             if (rc) return rc;
         }
         return 0;
     }
-    PVS_REQUIRE(epi == 0 || pvs_linear_epilogue_supported(ldy, ldx, x2 ? ldx2 : 0, K, K2, C, y, x, x2),
+    PVS_REQUIRE(epi == 0 || pvs_linear_epilogue_supported(j),
                 "linear: the epilogue needs the MFMA path");
     if (N <= 0) return 0;
     const int KK = K + K2;
@@ -1057,12 +1069,10 @@ int pvs_launch_linear(hipStream_t s, float* y, int ldy, const float* x, int ldx,
         (KK > 128 || C > 64)) {
         PvsProfScope prof(s, PVS_PROF_LIN_CHUNK64);
         for (int c0 = 0; c0 < C; c0 += 64) {
-            int rc = pvs_launch_linear(s, y + c0, ldy, x, ldx, W + (size_t)c0 * swc, swc, swk, b ? b + c0 : nullptr,
-                                       nullptr, 0, nullptr, 0, 0, N, K, 0, 64, accumulate, 0, nullptr, 0, nullptr, 0);
+            int rc = pvs_launch_linear(s, chunk(j.a, c0, 64, b, accumulate));
             if (rc) return rc;
             if (K2 > 0) {
-                rc = pvs_launch_linear(s, y + c0, ldy, x2, ldx2, W2 + (size_t)c0 * swc2, swc2, swk2, nullptr, nullptr, 0,
-                                       nullptr, 0, 0, N, K2, 0, 64, true, 0, nullptr, 0, nullptr, 0);
+                rc = pvs_launch_linear(s, chunk(j.b, c0, 64, nullptr, true));
                 if (rc) return rc;
             }
         }
@@ -1297,8 +1307,7 @@ int pvs_launch_node_wgrads(hipStream_t s, int H, int N, const PvsNodeWgradIn& in
         k_node_wgrads<1, true><<<dim3(rb + ex.blocks() + gh.blocks, 1), kThreads, 0, s>>>(slabs, in, N, rb, ex, gh);
     } else {
         if (gh_job)     // (H = 64: the product as its own launch, see k_node_wgrads)
-            PVS_TRY_RC(pvs_launch_linear(s, gh.g_h, H, gh.gPQ, 2 * H, gh.W1, 1, gh.ld1, nullptr, gh.gPQ + H, 2 * H,
-                                         gh.W1 + gh.off_q, 1, gh.ld1, N, H, H, H, true));
+            PVS_TRY_RC(pvs_launch_linear(s, pvs_gh_linear_job(gh, N, H)));
         k_node_wgrads<2, false><<<dim3(rb + ex.blocks(), 4), kThreads, 0, s>>>(slabs, in, N, rb, ex, gh);
     }
     PVS_CHECK_LAUNCH();
@@ -1346,8 +1355,7 @@ int pvs_launch_colreduce(hipStream_t s, int mode, float* out, const float* A, in
 // ------------------------------------------------------------------------------------------------
 extern "C" int pvs_linear_fwd(const float* x, const float* w, const float* b, float* y, int32_t N,
                               int32_t K, int32_t C, pvs_stream_t stream) {
-    return pvs_launch_linear((hipStream_t)stream, y, C, x, K, w, K, 1, b, nullptr, 0, nullptr, 0, 0,
-                             N, K, 0, C, false);
+    return pvs_launch_linear((hipStream_t)stream, pvs_linear_job(y, C, pvs_operand(x, K, w, K, K), N, C, b));
 }
 
 extern "C" size_t pvs_linear_bwd_workspace_bytes(int32_t N, int32_t K, int32_t C) {
@@ -1364,8 +1372,7 @@ extern "C" int pvs_linear_bwd(const float* x, const float* w, const float* g_y, 
     float* slabs = (float*)workspace;
     int rc;
     if (g_x) {  // g_x[n,k] = sum_c g_y[n,c] W[c,k]
-        rc = pvs_launch_linear(s, g_x, K, g_y, C, w, 1, K, nullptr, nullptr, 0, nullptr, 0, 0, N, C,
-                               0, K, false);
+        rc = pvs_launch_linear(s, pvs_linear_job(g_x, K, pvs_operand_t(g_y, C, w, K, C), N, K));
         if (rc) return rc;
     }
     const bool bias_in_product = g_w && g_b && pvs_tsgemm_colsum_supported(N, C, K);

@@ -3,6 +3,10 @@
 #include "common.h"
 #include "edge_dispatch.h"
 
+// Internal flag beside the PVS_* layer flags: the forward writes the raw coordinate sums (no x, no 1/deg) into x_out
+// (pvs_egnn_layer_edge_sums / _fwd_partial)
+constexpr uint32_t kFwdRawXsum = 1u << 23;
+
 // Pointers the edge kernels need, by value in the kernel arguments.
 struct PvsEdgeW {
     const float* w1;     // edge_mlp.0.weight [H, ld1]

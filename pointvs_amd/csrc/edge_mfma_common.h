@@ -15,8 +15,6 @@ constexpr int kThreads = 256;
 constexpr int kWaves = 4;
 constexpr int kTile = 32;
 
-// internal: the forward writes the raw coordinate sums (no x, no 1/deg) into x_out (edge_sums)
-constexpr uint32_t kFwdRawXsum = 1u << 23;
 // Dead flag bits. They were the timing-only switches of a PVS_ABLATE environment variable that is gone: no caller can
 // set them. The wave-uniform branches on them stay in the kernels (forward, exact-fp32 backward, and `n_attr & 0x100` in
 // load_tile_idx*): the compiler schedules the kernels worse without them - edge forward +1.5 % at cfg2, +0.5 % at cfg3,

@@ -15,6 +15,11 @@ size_t pvs64_atb_slab_doubles(int R, int C, int K);
 int pvs64_atb(hipStream_t s, double* G, int ldg, const double* A, int lda, const double* B, int ldb, int R, int C,
               int K, double* slabs, bool accumulate);
 
+// out[c] = sum_r A[r*lda + c], c < C: the column sums (bias gradients and the like) as pvs64_atb without a right operand.
+inline int pvs64_colsum(hipStream_t s, double* out, const double* A, int lda, int R, int C, double* slabs) {
+    return pvs64_atb(s, out, 1, A, lda, nullptr, 0, R, C, 1, slabs, false);
+}
+
 // Largest C*K the layer hands to pvs64_atb (the slab scratch it reserves).
 #define PVS64_MAX_ATB_OUT (64 * 64)
 

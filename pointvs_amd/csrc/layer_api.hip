@@ -8,8 +8,6 @@
 
 #include <stdlib.h>
 
-static constexpr uint32_t kFwdRawXsumFlag = 1u << 23;   // == kFwdRawXsum of edge_mfma_common.h
-
 namespace {
 
 struct Dims {
@@ -98,6 +96,26 @@ size_t carve_fwd(PvsArena& a, const Dims& m, FwdWs* w) {
     t.m_scratch = a.take<float>(m.H > 64 ? (size_t)(m.E > 0 ? m.E : 1) * m.H : 4);
     if (w) *w = t;
     return a.off;
+}
+
+// What a layer's forward keeps for its backward in the caller's `saved` buffer: the node-level forward (N rows: small)
+// instead of recomputing it.
+struct SavedLayout {
+    float *Magg, *stats, *PQ, *y1, *o, *u;   // [N,H] | graphnorm stats [2H] | [N,2H] | [N,H] | [N,H] | SiLU(GN(y1)) [N,H]
+    static size_t floats(size_t N, size_t H) { return 6 * N * H + 2 * H; }
+};
+SavedLayout saved_layout(float* saved, int N, int H) {
+    const size_t NH = (size_t)N * H, S = 2 * (size_t)H;
+    return {saved, saved + NH, saved + NH + S, saved + 3 * NH + S, saved + 4 * NH + S, saved + 5 * NH + S};
+}
+
+// The edge forward's tensors; m_prev / m_out / att_out as the entry point has them (NULL: none)
+PvsEdgeFwdIO make_fwd_io(const FwdWs& w, const float* PQ, const float* x, const float* m_prev, float* Magg, float* x_out,
+                         float* m_out, float* att_out) {
+    PvsEdgeFwdIO io;
+    io.PQ = PQ; io.x = x; io.m_prev = m_prev; io.Magg = Magg; io.x_out = x_out; io.m_out = m_out;
+    io.att_out = att_out; io.smax = w.smax; io.ssum = w.ssum; io.m_scratch = w.m_scratch;
+    return io;
 }
 
 struct BwdWs {
@@ -206,8 +224,12 @@ int node_mlp_forward(hipStream_t s, const Dims& m, const PvsLayerDesc* d, const 
                      float* h_out, float* node_att_out) {
     const int H = m.H;
     const uint32_t F = d->flags;
-    const bool can_epi = pvs_linear_epilogue_supported(H, H, H, H, H, H, y1, h, Magg) &&
-                         pvs_linear_epilogue_supported(H, H, 0, H, 0, H, o, u, nullptr) &&
+    PvsLinearJob first = pvs_linear_job(y1, H, pvs_operand(h, H, p->node_w1, 2 * H, H), m.N, H, p->node_b1);
+    first.b = pvs_operand(Magg, H, p->node_w1 + H, 2 * H, H);
+    first.aux_out = u; first.ld_out = H;
+    PvsLinearJob second = pvs_linear_job(o, H, pvs_operand(u, H, p->node_w2, H, H), m.N, H, p->node_b2);
+    second.aux_in = h; second.ld_in = H; second.aux_out = h_out; second.ld_out = H;
+    const bool can_epi = pvs_linear_epilogue_supported(first) && pvs_linear_epilogue_supported(second) &&
                          (((uintptr_t)h_out | (uintptr_t)u) & 15) == 0;
     const bool fuse_silu = can_epi && !(F & PVS_GRAPHNORM);
     const bool gated = (F & PVS_RESIDUAL) && (F & (PVS_REZERO | PVS_GATED_RESIDUAL));
@@ -225,16 +247,13 @@ int node_mlp_forward(hipStream_t s, const Dims& m, const PvsLayerDesc* d, const 
                                        (F & PVS_RESIDUAL) != 0, natt ? nw.natt_w : nullptr, natt ? nw.natt_b : nullptr,
                                        d->att_act, y1, u, o, h_out, node_att_out);
     }
-    PVS_TRY(pvs_launch_linear(s, y1, H, h, H, p->node_w1, 2 * H, 1, p->node_b1, Magg, H,
-                              p->node_w1 + H, 2 * H, 1, m.N, H, H, H, false,
-                              fuse_silu ? PVS_EPI_SILU_OUT : PVS_EPI_NONE, nullptr, 0, u, H));
+    first.epi = fuse_silu ? PVS_EPI_SILU_OUT : PVS_EPI_NONE;
+    PVS_TRY(pvs_launch_linear(s, first));
     if ((F & PVS_GRAPHNORM) && compute_stats)
         PVS_TRY(pvs_graphnorm_stats(s, y1, p->gn_mean_scale, m.N, H, stats, shift_tmp, slabs));
     if (!fuse_silu) PVS_TRY(pvs_node_tail_fwd(s, y1, stats, nw, m.N, H, u));
-    PVS_TRY(pvs_launch_linear(s, o, H, u, H, p->node_w2, H, 1, p->node_b2, nullptr, 0, nullptr, 0, 0,
-                              m.N, H, 0, H, false,
-                              !fuse_out ? PVS_EPI_NONE : (F & PVS_RESIDUAL) ? PVS_EPI_ADD_OUT : PVS_EPI_COPY_OUT,
-                              h, H, h_out, H));
+    second.epi = !fuse_out ? PVS_EPI_NONE : (F & PVS_RESIDUAL) ? PVS_EPI_ADD_OUT : PVS_EPI_COPY_OUT;
+    PVS_TRY(pvs_launch_linear(s, second));
     if (!fuse_out) PVS_TRY(pvs_node_out_fwd(s, H, o, h, nw, F, d->att_act, m.N, h_out, node_att_out));
     return 0;
 }
@@ -251,40 +270,30 @@ int node_pre_forward(hipStream_t s, const Dims& m, const PvsLayerParams* p, cons
     PvsLinearExt e;
     if (init) {
         e.zero_rows = init->Magg; e.zero_w = H; e.zero_ld = H;
-        if (init_flags & kFwdRawXsumFlag) e.zero3 = init->x_out;
+        if (init_flags & kFwdRawXsum) e.zero3 = init->x_out;
         else if (init_flags & PVS_UPDATE_COORDS) { e.copy3_src = init->x; e.copy3_dst = init->x_out; }
     }
     const bool side_ok = init && !split_small && ((uintptr_t)init->Magg & 15) == 0;
-    if (H == 32 && !split_small && pvs_linear_epilogue_supported(2 * H, H, 0, H, 0, 2 * H, PQ, h, nullptr) &&
-        (!init || side_ok)) {
-        // P | Q in one launch: 64 outputs, the second column block (group) on the Q slice of edge_mlp.0's weight, no bias
-        e.w_shift1 = (long long)m.off_q - 32LL * m.ld1;
-        e.bias_blocks = 1;
-        // (as two groups of one-column-block workgroups, the clears as a third group: 12 us against 15-16 for
-        // workgroups twice as long that also do the clears)
-        e.groups = 2; e.side_group = init ? 1 : 0;
-        PVS_TRY(pvs_launch_linear(s, PQ, 2 * H, h, H, p->edge_w1, m.ld1, 1, p->edge_b1, nullptr, 0, nullptr, 0, 0, m.N,
-                                  H, 0, 2 * H, false, PVS_EPI_NONE, nullptr, 0, nullptr, 0, &e));
-        if (init) init->init_done = true;
-        return 0;
+    // P = h W1[:, 0:H]^T + b1 (row part), Q = h W1[:, off_q:off_q+H]^T (col part)
+    const PvsLinearOperand row_part = pvs_operand(h, H, p->edge_w1, m.ld1, H);
+    if ((H == 32 || H == 64) && !split_small && (H == 64 || !init || side_ok)) {
+        // P | Q as two groups of workgroups of ONE launch (H outputs each; the second group on the Q slice of the weight, no
+        // bias), the forward's clears as a third group: at H = 32, 12 us against 15-16 for workgroups twice as long that
+        // also do the clears; at H = 64, as side jobs of the P workgroups they cost 11 us against 6 for a launch of their
+        // own (profiles/r03_ab_small_launch_folding.txt). H = 32 with clears that cannot ride takes the two launches below.
+        PvsLinearExt g2 = side_ok ? e : PvsLinearExt{};
+        g2.groups = 2; g2.shift_block = H / 32; g2.bias_blocks = H / 32; g2.side_group = side_ok ? 1 : 0;
+        g2.w_shift1 = (long long)m.off_q - (long long)H * m.ld1;
+        PvsLinearJob pq = pvs_linear_job(PQ, 2 * H, row_part, m.N, 2 * H, p->edge_b1);
+        pq.ext = &g2;
+        if (pvs_linear_epilogue_supported(pq)) {
+            PVS_TRY(pvs_launch_linear(s, pq));
+            if (side_ok) init->init_done = true;
+            return 0;
+        }
     }
-    if (H == 64 && !split_small && pvs_linear_epilogue_supported(2 * H, H, 0, H, 0, H, PQ, h, nullptr)) {
-        // H = 64: P and Q as two groups of workgroups of ONE launch (64 outputs each; the second group on the Q slice of
-        // the weight, no bias), the forward's clears as a third group (as side jobs of the P workgroups they cost 11 us
-        // against 6 for a launch of their own, profiles/r03_ab_small_launch_folding.txt).
-        PvsLinearExt g2 = side_ok ? e : PvsLinearExt{};      // (with the forward's clears as a third group of their own)
-        g2.groups = 2; g2.shift_block = 2; g2.bias_blocks = 2; g2.side_group = side_ok ? 1 : 0;
-        g2.w_shift1 = (long long)m.off_q - 64LL * m.ld1;
-        PVS_TRY(pvs_launch_linear(s, PQ, 2 * H, h, H, p->edge_w1, m.ld1, 1, p->edge_b1, nullptr, 0, nullptr, 0, 0, m.N, H, 0,
-                                  2 * H, false, PVS_EPI_NONE, nullptr, 0, nullptr, 0, &g2));
-        if (side_ok) init->init_done = true;
-        return 0;
-    }
-    // P = W1[:, 0:H] h + b1 (row part), Q = W1[:, off_q:off_q+H] h (col part)
-    PVS_TRY(pvs_launch_linear(s, PQ, 2 * H, h, H, p->edge_w1, m.ld1, 1, p->edge_b1, nullptr, 0,
-                              nullptr, 0, 0, m.N, H, 0, H, false));
-    PVS_TRY(pvs_launch_linear(s, PQ + H, 2 * H, h, H, p->edge_w1 + m.off_q, m.ld1, 1, nullptr,
-                              nullptr, 0, nullptr, 0, 0, m.N, H, 0, H, false));
+    PVS_TRY(pvs_launch_linear(s, pvs_linear_job(PQ, 2 * H, row_part, m.N, H, p->edge_b1)));
+    PVS_TRY(pvs_launch_linear(s, pvs_linear_job(PQ + H, 2 * H, pvs_operand(h, H, p->edge_w1 + m.off_q, m.ld1, H), m.N, H)));
     return 0;
 }
 
@@ -292,10 +301,7 @@ int node_pre_forward(hipStream_t s, const Dims& m, const PvsLayerParams* p, cons
 
 extern "C" size_t pvs_egnn_layer_saved_floats(const PvsLayerDesc* d, int32_t N, int32_t E) {
     (void)E;
-    // Magg [N,H] | graphnorm stats [2H] | PQ [N,2H] | y1 [N,H] | o [N,H] | u [N,H]: the node-level forward is
-    // kept for the backward (N rows: small) instead of being recomputed
-    // (+ u = SiLU(GN(y1)) [N,H]: one small launch less in the backward)
-    return 6 * (size_t)N * d->hidden + 2 * (size_t)d->hidden;
+    return SavedLayout::floats((size_t)N, (size_t)d->hidden);
 }
 
 extern "C" size_t pvs_egnn_layer_workspace_bytes(const PvsLayerDesc* d, int32_t N, int32_t E,
@@ -331,18 +337,12 @@ extern "C" int pvs_egnn_layer_fwd(const PvsLayerDesc* d, const PvsGraph* g, cons
     PVS_REQUIRE(arena.ok(), "pvs_egnn_layer_fwd: workspace too small (%zu < %zu)", workspace_bytes,
                 arena.off);
     const int H = m.H;
-    float* Magg = saved;
-    float* stats = saved + (size_t)m.N * H;
-    float* sPQ = stats + 2 * H;
-    float* sy1 = sPQ + 2 * (size_t)m.N * H;
-    float* so = sy1 + (size_t)m.N * H;
+    const SavedLayout sv = saved_layout(saved, m.N, H);
     const PvsEdgeW ew = make_edge_w(m, p);
     const PvsNodeW nw = make_node_w(d, p);
 
-    PvsEdgeFwdIO io;
-    io.PQ = sPQ; io.x = x; io.m_prev = m_prev; io.Magg = Magg; io.x_out = x_out; io.m_out = m_out;
-    io.att_out = att_out; io.smax = w.smax; io.ssum = w.ssum; io.m_scratch = w.m_scratch;
-    PVS_TRY(node_pre_forward(s, m, p, h, sPQ, mfma_fwd ? &io : nullptr, d->flags));
+    PvsEdgeFwdIO io = make_fwd_io(w, sv.PQ, x, m_prev, sv.Magg, x_out, m_out, att_out);
+    PVS_TRY(node_pre_forward(s, m, p, h, sv.PQ, mfma_fwd ? &io : nullptr, d->flags));
     if (mfma_fwd)
         PVS_TRY(pvs_launch_edge_fwd_mfma(s, H, fam, *g, ew, d->flags, d->att_act, io));
     else
@@ -350,8 +350,8 @@ extern "C" int pvs_egnn_layer_fwd(const PvsLayerDesc* d, const PvsGraph* g, cons
     if (!(d->flags & PVS_UPDATE_COORDS))
         PVS_CHECK_HIP(hipMemcpyAsync(x_out, x, sizeof(float) * 3 * (size_t)m.N,
                                      hipMemcpyDeviceToDevice, s));
-    PVS_TRY(node_mlp_forward(s, m, d, p, nw, h, Magg, sy1, so + (size_t)m.N * H, so, stats, true, w.shift, w.slabs,
-                             h_out, node_att_out));
+    PVS_TRY(node_mlp_forward(s, m, d, p, nw, h, sv.Magg, sv.y1, sv.u, sv.o, sv.stats, true, w.shift, w.slabs, h_out,
+                             node_att_out));
     return 0;
 }
 
@@ -413,11 +413,9 @@ extern "C" int pvs_egnn_layer_edge_sums(const PvsLayerDesc* d, const PvsGraph* g
     float* att = arena.take<float>((size_t)(m.E > 0 ? m.E : 1));
     PVS_REQUIRE(arena.ok(), "pvs_egnn_layer_edge_sums: workspace too small (%zu < %zu)", workspace_bytes, arena.off);
     const PvsEdgeW ew = make_edge_w(m, p);
-    PvsEdgeFwdIO io;
-    io.PQ = w.PQ; io.x = x; io.m_prev = nullptr; io.Magg = magg; io.x_out = xsum; io.m_out = nullptr;
-    io.att_out = att; io.smax = w.smax; io.ssum = w.ssum; io.m_scratch = w.m_scratch;
-    PVS_TRY(node_pre_forward(s, m, p, h, w.PQ, &io, d->flags | kFwdRawXsumFlag));
-    PVS_TRY(pvs_launch_edge_fwd_mfma(s, m.H, fam, *g, ew, d->flags | kFwdRawXsumFlag, d->att_act, io));
+    PvsEdgeFwdIO io = make_fwd_io(w, w.PQ, x, nullptr, magg, xsum, nullptr, att);
+    PVS_TRY(node_pre_forward(s, m, p, h, w.PQ, &io, d->flags | kFwdRawXsum));
+    PVS_TRY(pvs_launch_edge_fwd_mfma(s, m.H, fam, *g, ew, d->flags | kFwdRawXsum, d->att_act, io));
     if (!(d->flags & PVS_UPDATE_COORDS))
         PVS_CHECK_HIP(hipMemsetAsync(xsum, 0, sizeof(float) * 3 * (size_t)m.N, s));
     return 0;
@@ -441,28 +439,22 @@ extern "C" int pvs_egnn_layer_fwd_partial(const PvsLayerDesc* d, const PvsGraph*
     float* att = arena.take<float>((size_t)(m.E > 0 ? m.E : 1));
     PVS_REQUIRE(arena.ok(), "pvs_egnn_layer_fwd_partial: workspace too small (%zu < %zu)", workspace_bytes, arena.off);
     const int H = m.H;
-    float* Magg = saved;
-    float* stats = saved + (size_t)m.N * H;
-    float* sPQ = stats + 2 * H;
-    float* sy1 = sPQ + 2 * (size_t)m.N * H;
-    float* so = sy1 + (size_t)m.N * H;
+    const SavedLayout sv = saved_layout(saved, m.N, H);
     const PvsEdgeW ew = make_edge_w(m, p);
     const PvsNodeW nw = make_node_w(d, p);
-    PvsEdgeFwdIO io;
-    io.PQ = sPQ; io.x = x; io.m_prev = nullptr; io.Magg = Magg; io.x_out = x_out; io.m_out = nullptr;
-    io.att_out = att; io.smax = w.smax; io.ssum = w.ssum; io.m_scratch = w.m_scratch;
-    PVS_TRY(node_pre_forward(s, m, p, h, sPQ, &io, d->flags | kFwdRawXsumFlag));
+    PvsEdgeFwdIO io = make_fwd_io(w, sv.PQ, x, nullptr, sv.Magg, x_out, nullptr, att);
+    PVS_TRY(node_pre_forward(s, m, p, h, sv.PQ, &io, d->flags | kFwdRawXsum));
     pvs_prof_set_fwd_tag(PVS_PROF_EDGE_FWD_PARTIAL);      // timed apart from the full-graph layers (bench.py)
-    const int rc_partial = pvs_launch_edge_fwd_mfma(s, H, fam, *g, ew, d->flags | kFwdRawXsumFlag, d->att_act, io);
+    const int rc_partial = pvs_launch_edge_fwd_mfma(s, H, fam, *g, ew, d->flags | kFwdRawXsum, d->att_act, io);
     pvs_prof_set_fwd_tag(PVS_PROF_EDGE_FWD);
     PVS_TRY(rc_partial);
     const long long threads = (long long)m.N * (H / 4);
-    k_combine_partial<<<(int)((threads + 255) / 256), 256, 0, s>>>(Magg, x_out, x, base_magg, base_xsum, base_deg,
+    k_combine_partial<<<(int)((threads + 255) / 256), 256, 0, s>>>(sv.Magg, x_out, x, base_magg, base_xsum, base_deg,
                                                                    g->rowptr, m.N, H,
                                                                    (d->flags & PVS_UPDATE_COORDS) ? 1 : 0);
     PVS_CHECK_LAUNCH();
-    PVS_TRY(node_mlp_forward(s, m, d, p, nw, h, Magg, sy1, so + (size_t)m.N * H, so, stats, true, w.shift, w.slabs,
-                             h_out, node_att_out));
+    PVS_TRY(node_mlp_forward(s, m, d, p, nw, h, sv.Magg, sv.y1, sv.u, sv.o, sv.stats, true, w.shift, w.slabs, h_out,
+                             node_att_out));
     return 0;
 }
 
@@ -490,11 +482,9 @@ extern "C" int pvs_egnn_layer_bwd(const PvsLayerDesc* d, const PvsGraph* g, cons
     PVS_REQUIRE(arena.ok(), "pvs_egnn_layer_bwd: workspace too small (%zu < %zu)", workspace_bytes,
                 arena.off);
     const int H = m.H, N = m.N;
-    const float* Magg = saved;
-    float* stats = const_cast<float*>(saved) + (size_t)N * H;   // read-only here
-    const float* sPQ = stats + 2 * H;
-    const float* sy1 = sPQ + 2 * (size_t)N * H;
-    const float* so = sy1 + (size_t)N * H;
+    const SavedLayout sv = saved_layout(const_cast<float*>(saved), N, H);      // read-only here
+    const float *Magg = sv.Magg, *sPQ = sv.PQ, *sy1 = sv.y1, *so = sv.o, *su = sv.u;
+    float* stats = sv.stats;
     const PvsEdgeW ew = make_edge_w(m, p);
     const PvsNodeW nw = make_node_w(d, p);
     const bool gn = F & PVS_GRAPHNORM, natt = F & PVS_NODE_ATTENTION;
@@ -504,8 +494,7 @@ extern "C" int pvs_egnn_layer_bwd(const PvsLayerDesc* d, const PvsGraph* g, cons
     const bool fused_wgrads = pvs_node_wgrads_supported(H) && gr.node_w2 && gr.node_w1 && gr.edge_w1 &&
                               !getenv("PVS_EGNN_SPLIT_WGRADS");
 
-    // ---- node-level forward: PQ, y1, o were kept by the forward; u = SiLU(GN(y1)) is elementwise ----
-    const float* su = so + (size_t)N * H;      // u = SiLU(GN(y1)) kept by the forward
+    // ---- node-level forward: PQ, y1, o and u = SiLU(GN(y1)) were kept by the forward ----
 
     // ---- node_model backward ----
     const bool split_small = getenv("PVS_EGNN_SPLIT_SMALL") != nullptr;     // (the launches apart, for A/B)
@@ -547,12 +536,11 @@ extern "C" int pvs_egnn_layer_bwd(const PvsLayerDesc* d, const PvsGraph* g, cons
     }
     // o = u Wn2^T + bn2
     // (without GraphNorm g_y1 = g_u * SiLU'(y1) rides on this product's epilogue)
-    const bool fuse_tail_bwd = !gn && pvs_linear_epilogue_supported(H, H, 0, H, 0, H, w.g_u, g_o, nullptr) &&
-                               ((uintptr_t)sy1 & 15) == 0;
-    if (!chain_bwd)
-        PVS_TRY(pvs_launch_linear(s, w.g_u, H, g_o, H, p->node_w2, 1, H, nullptr, nullptr, 0, nullptr, 0,
-                                  0, N, H, 0, H, false, fuse_tail_bwd ? PVS_EPI_MUL_SILU_GRAD : PVS_EPI_NONE, sy1, H,
-                                  nullptr, 0));
+    PvsLinearJob gu = pvs_linear_job(w.g_u, H, pvs_operand_t(g_o, H, p->node_w2, H, H), N, H);
+    gu.aux_in = sy1; gu.ld_in = H;
+    const bool fuse_tail_bwd = !gn && pvs_linear_epilogue_supported(gu) && ((uintptr_t)sy1 & 15) == 0;
+    gu.epi = fuse_tail_bwd ? PVS_EPI_MUL_SILU_GRAD : PVS_EPI_NONE;
+    if (!chain_bwd) PVS_TRY(pvs_launch_linear(s, gu));
     if (gr.node_w2 && !fused_wgrads)
         PVS_TRY(pvs_launch_tsgemm_tn(s, gr.node_w2, H, g_o, H, su, H, N, H, H, w.dslabs, false));
     if (gr.node_b2 && !fused_wgrads)
@@ -574,24 +562,26 @@ extern "C" int pvs_egnn_layer_bwd(const PvsLayerDesc* d, const PvsGraph* g, cons
     // The per-node preparation of the edge backward (clear the row part of gPQ and gx_row - rows without edges are
     // never written by the MFMA edge backward -, g_x_out / deg) rides on these products as side jobs of the node rows
     // where the MFMA linear takes the shape; the softmax row dots need the finished gM and keep their own launch.
-    const bool prep_side = !split_small && ((uintptr_t)w.gPQ & 15) == 0 &&
-                           pvs_linear_epilogue_supported(H, H, 0, H, 0, H, w.gM, g_y1, nullptr);
+    PvsLinearJob gh1 = pvs_linear_job(g_h, H, pvs_operand_t(g_y1, H, p->node_w1, 2 * H, H), N, H);
+    gh1.accumulate = !plain_out;
+    PvsLinearJob gm = pvs_linear_job(w.gM, H, pvs_operand_t(g_y1, H, p->node_w1 + H, 2 * H, H), N, H);
+    const bool prep_side = !split_small && ((uintptr_t)w.gPQ & 15) == 0 && pvs_linear_epilogue_supported(gm);
+    // g_h (+)= and gM = in one launch: 64 outputs over the two halves of node_mlp.0's weight, the second column block
+    // to gM
+    PvsLinearJob both = gh1;
+    both.C = 2 * H;
+    both.ext = &prep;
     bool prep_done = false;
     if (chain_bwd) {
         prep_done = true;       // (launched above)
-    } else if (H == 32 && prep_side && pvs_linear_epilogue_supported(H, H, 0, H, 0, 2 * H, g_h, g_y1, nullptr)) {
-        // g_h (+)= and gM = in one launch: 64 outputs over the two halves of node_mlp.0's weight, the second column
-        // block to gM
+    } else if (H == 32 && prep_side && pvs_linear_epilogue_supported(both)) {
         prep.y1 = w.gM; prep.ldy1 = H; prep.acc1 = 0;
-        PVS_TRY(pvs_launch_linear(s, g_h, H, g_y1, H, p->node_w1, 1, 2 * H, nullptr, nullptr, 0, nullptr, 0, 0, N, H, 0,
-                                  2 * H, !plain_out, PVS_EPI_NONE, nullptr, 0, nullptr, 0, &prep));
+        PVS_TRY(pvs_launch_linear(s, both));
         prep_done = true;
     } else {
-        PVS_TRY(pvs_launch_linear(s, g_h, H, g_y1, H, p->node_w1, 1, 2 * H, nullptr, nullptr, 0, nullptr,
-                                  0, 0, N, H, 0, H, !plain_out));
-        PVS_TRY(pvs_launch_linear(s, w.gM, H, g_y1, H, p->node_w1 + H, 1, 2 * H, nullptr, nullptr, 0,
-                                  nullptr, 0, 0, N, H, 0, H, false, PVS_EPI_NONE, nullptr, 0, nullptr, 0,
-                                  prep_side ? &prep : nullptr));
+        PVS_TRY(pvs_launch_linear(s, gh1));
+        if (prep_side) gm.ext = &prep;
+        PVS_TRY(pvs_launch_linear(s, gm));
         prep_done = prep_side;
     }
     if (gr.node_w1 && !fused_wgrads) {
@@ -650,9 +640,9 @@ extern "C" int pvs_egnn_layer_bwd(const PvsLayerDesc* d, const PvsGraph* g, cons
     // g_h += g_P W1a + g_Q W1b: one launch with the two (input, weight) pairs
     // (with the folded tail it is a role of the weight-gradient launch below)
     const bool gh_folded = tail_folded && (((uintptr_t)g_h | (uintptr_t)w.gPQ) & 15) == 0;
-    if (!gh_folded)
-        PVS_TRY(pvs_launch_linear(s, g_h, H, w.gPQ, 2 * H, p->edge_w1, 1, m.ld1, nullptr, w.gPQ + H, 2 * H,
-                                  p->edge_w1 + m.off_q, 1, m.ld1, N, H, H, H, true));
+    PvsGhJob ghj;
+    ghj.g_h = g_h; ghj.gPQ = w.gPQ; ghj.W1 = p->edge_w1; ghj.ld1 = m.ld1; ghj.off_q = m.off_q;
+    if (!gh_folded) PVS_TRY(pvs_launch_linear(s, pvs_gh_linear_job(ghj, N, H)));
     const float* node_gsum = nullptr;
     PvsNodeWgradSlabs node_slabs;
     PvsNodeWgradOut node_out{};
@@ -664,8 +654,6 @@ extern "C" int pvs_egnn_layer_bwd(const PvsLayerDesc* d, const PvsGraph* g, cons
         wo.node_b2 = gr.node_b2; wo.node_b1 = gr.node_b1; wo.edge_b1 = gr.edge_b1;
         wo.ld1 = m.ld1; wo.off_q = m.off_q; wo.perm = m.perm ? 1 : 0;
         if (gate_in_wgrads) { wi.t1 = w.t1; wi.gl = w.gl; wo.natt_w = gr.node_att_w; wo.natt_b = gr.node_att_b; }
-        PvsGhJob ghj;
-        ghj.g_h = g_h; ghj.gPQ = w.gPQ; ghj.W1 = p->edge_w1; ghj.ld1 = m.ld1; ghj.off_q = m.off_q;
         if (tail_folded)
             PVS_TRY(pvs_launch_node_wgrads(s, H, N, wi, wo, w.wslabs, /*scatter=*/false, nullptr, &edge_red, &node_slabs,
                                            gh_folded ? &ghj : nullptr));

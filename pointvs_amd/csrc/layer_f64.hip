@@ -632,6 +632,26 @@ E64Args edge_args(const PvsLayerDesc* d, const PvsGraph* g, const PvsLayerParams
     return a;
 }
 
+// the node tail's arguments both directions share; the caller adds its outputs (forward) or gradients (backward)
+NodeArgs node_args(const PvsLayerDesc* d, const PvsLayerParamsF64* p, int N, const double* h, const Saved64& sv) {
+    NodeArgs na = {};
+    const uint32_t f = d->flags;
+    na.N = N;
+    na.H = d->hidden;
+    na.natt = (f & PVS_NODE_ATTENTION) ? 1 : 0;
+    na.act = d->att_act;
+    na.residual = (f & PVS_RESIDUAL) ? 1 : 0;
+    na.rezero = (f & PVS_REZERO) ? 1 : 0;
+    na.gated = (f & PVS_GATED_RESIDUAL) ? 1 : 0;
+    na.h = h;
+    na.out = sv.out;
+    na.naw = p->node_att_w;
+    na.nab = p->node_att_b;
+    na.ngate = p->node_gate;
+    na.nl = sv.nl;
+    return na;
+}
+
 int check_params(const PvsLayerDesc* d, const PvsLayerParamsF64* p, const char* who) {
     const uint32_t f = d->flags;
     PVS_REQUIRE(p && p->edge_w1 && p->edge_b1 && p->edge_w2 && p->edge_b2 && p->node_w1 && p->node_b1 &&
@@ -704,13 +724,13 @@ extern "C" int pvs_egnn_layer_fwd_f64(const PvsLayerDesc* desc, const PvsGraph* 
     if ((rc = pvs64_gemm(s, sv.u, H, sv.agg, H, params->node_w1 + H, 2 * H, 1, nullptr, N, H, H, true))) return rc;
     const long long NH = (long long)N * H;
     if (f & PVS_GRAPHNORM) {
-        if ((rc = pvs64_atb(s, w.vec0, 1, sv.u, H, nullptr, 0, N, H, 1, w.slabs, false))) return rc;
+        if ((rc = pvs64_colsum(s, w.vec0, sv.u, H, N, H, w.slabs))) return rc;
         hipLaunchKernelGGL(k64_scale_vec, dim3(1), dim3(64), 0, s, w.vec0, sv.mu, H, (double)N);
         PVS_CHECK_LAUNCH();
         hipLaunchKernelGGL(k64_gn_center, dim3(blocks_for(NH)), dim3(256), 0, s, sv.u, sv.mu, params->gn_mean_scale,
                            w.o, w.o2, N, H);
         PVS_CHECK_LAUNCH();
-        if ((rc = pvs64_atb(s, w.vec1, 1, w.o2, H, nullptr, 0, N, H, 1, w.slabs, false))) return rc;
+        if ((rc = pvs64_colsum(s, w.vec1, w.o2, H, N, H, w.slabs))) return rc;
         hipLaunchKernelGGL(k64_gn_sq, dim3(1), dim3(64), 0, s, w.vec1, sv.sq, H, (double)N);
         PVS_CHECK_LAUNCH();
         hipLaunchKernelGGL(k64_gn_apply, dim3(blocks_for(NH)), dim3(256), 0, s, w.o, sv.sq, params->gn_weight,
@@ -721,20 +741,7 @@ extern "C" int pvs_egnn_layer_fwd_f64(const PvsLayerDesc* desc, const PvsGraph* 
         PVS_CHECK_LAUNCH();
     }
     if ((rc = pvs64_gemm(s, sv.out, H, sv.a, H, params->node_w2, H, 1, params->node_b2, N, H, H, false))) return rc;
-    NodeArgs na = {};
-    na.N = N;
-    na.H = H;
-    na.natt = (f & PVS_NODE_ATTENTION) ? 1 : 0;
-    na.act = desc->att_act;
-    na.residual = (f & PVS_RESIDUAL) ? 1 : 0;
-    na.rezero = (f & PVS_REZERO) ? 1 : 0;
-    na.gated = (f & PVS_GATED_RESIDUAL) ? 1 : 0;
-    na.h = h;
-    na.out = sv.out;
-    na.naw = params->node_att_w;
-    na.nab = params->node_att_b;
-    na.ngate = params->node_gate;
-    na.nl = sv.nl;
+    NodeArgs na = node_args(desc, params, N, h, sv);
     na.node_att_out = node_att_out;
     na.h_out = h_out;
     PVS_REQUIRE(!(na.residual && (na.rezero || na.gated)) || na.ngate, "%s: missing node_gate_parameter", who);
@@ -771,20 +778,7 @@ extern "C" int pvs_egnn_layer_bwd_f64(const PvsLayerDesc* desc, const PvsGraph* 
     int rc;
 
     // node tail: residual and node attention
-    NodeArgs na = {};
-    na.N = N;
-    na.H = H;
-    na.natt = (f & PVS_NODE_ATTENTION) ? 1 : 0;
-    na.act = desc->att_act;
-    na.residual = (f & PVS_RESIDUAL) ? 1 : 0;
-    na.rezero = (f & PVS_REZERO) ? 1 : 0;
-    na.gated = (f & PVS_GATED_RESIDUAL) ? 1 : 0;
-    na.h = h;
-    na.out = sv.out;
-    na.naw = params->node_att_w;
-    na.nab = params->node_att_b;
-    na.ngate = params->node_gate;
-    na.nl = sv.nl;
+    NodeArgs na = node_args(desc, params, N, h, sv);
     na.g_hout = g_h_out;
     na.g_out = w.g_out;
     na.g_h = g_h;
@@ -793,19 +787,16 @@ extern "C" int pvs_egnn_layer_bwd_f64(const PvsLayerDesc* desc, const PvsGraph* 
     hipLaunchKernelGGL(k64_node_tail_bwd, dim3(blocks_for(N)), dim3(256), 0, s, na);
     PVS_CHECK_LAUNCH();
     if (na.natt && grads->node_att_w)
-        if ((rc = pvs64_atb(s, grads->node_att_w, 1, w.np, H + 2, nullptr, 0, N, H, 1, w.slabs, false))) return rc;
+        if ((rc = pvs64_colsum(s, grads->node_att_w, w.np, H + 2, N, H, w.slabs))) return rc;
     if (na.natt && grads->node_att_b)
-        if ((rc = pvs64_atb(s, grads->node_att_b, 1, w.np + H, H + 2, nullptr, 0, N, 1, 1, w.slabs, false)))
-            return rc;
+        if ((rc = pvs64_colsum(s, grads->node_att_b, w.np + H, H + 2, N, 1, w.slabs))) return rc;
     if (na.residual && (na.rezero || na.gated) && grads->node_gate)
-        if ((rc = pvs64_atb(s, grads->node_gate, 1, w.np + H + 1, H + 2, nullptr, 0, N, 1, 1, w.slabs, false)))
-            return rc;
+        if ((rc = pvs64_colsum(s, grads->node_gate, w.np + H + 1, H + 2, N, 1, w.slabs))) return rc;
 
     // node_mlp.3
     if (grads->node_w2 && (rc = pvs64_atb(s, grads->node_w2, H, w.g_out, H, sv.a, H, N, H, H, w.slabs, false)))
         return rc;
-    if (grads->node_b2 && (rc = pvs64_atb(s, grads->node_b2, 1, w.g_out, H, nullptr, 0, N, H, 1, w.slabs, false)))
-        return rc;
+    if (grads->node_b2 && (rc = pvs64_colsum(s, grads->node_b2, w.g_out, H, N, H, w.slabs))) return rc;
     if ((rc = pvs64_gemm(s, w.g_a, H, w.g_out, H, params->node_w2, 1, H, nullptr, N, H, H, false))) return rc;
 
     // SiLU and GraphNorm
@@ -813,16 +804,14 @@ extern "C" int pvs_egnn_layer_bwd_f64(const PvsLayerDesc* desc, const PvsGraph* 
         hipLaunchKernelGGL(k64_gn_bwd1, dim3(blocks_for(NH)), dim3(256), 0, s, sv.u, sv.mu, params->gn_mean_scale,
                            sv.sq, params->gn_weight, params->gn_bias, w.g_a, w.g_o, w.t1, w.t2, N, H);
         PVS_CHECK_LAUNCH();
-        if (grads->gn_bias && (rc = pvs64_atb(s, grads->gn_bias, 1, w.g_o, H, nullptr, 0, N, H, 1, w.slabs, false)))
-            return rc;
-        if (grads->gn_weight && (rc = pvs64_atb(s, grads->gn_weight, 1, w.t1, H, nullptr, 0, N, H, 1, w.slabs, false)))
-            return rc;
-        if ((rc = pvs64_atb(s, w.vec0, 1, w.t2, H, nullptr, 0, N, H, 1, w.slabs, false))) return rc;
+        if (grads->gn_bias && (rc = pvs64_colsum(s, grads->gn_bias, w.g_o, H, N, H, w.slabs))) return rc;
+        if (grads->gn_weight && (rc = pvs64_colsum(s, grads->gn_weight, w.t1, H, N, H, w.slabs))) return rc;
+        if ((rc = pvs64_colsum(s, w.vec0, w.t2, H, N, H, w.slabs))) return rc;
         // g_o (into t1, free now)
         hipLaunchKernelGGL(k64_gn_bwd2, dim3(blocks_for(NH)), dim3(256), 0, s, sv.u, sv.mu, params->gn_mean_scale,
                            sv.sq, params->gn_weight, w.g_o, w.vec0, w.t1, N, H);
         PVS_CHECK_LAUNCH();
-        if ((rc = pvs64_atb(s, w.vec1, 1, w.t1, H, nullptr, 0, N, H, 1, w.slabs, false))) return rc;
+        if ((rc = pvs64_colsum(s, w.vec1, w.t1, H, N, H, w.slabs))) return rc;
         hipLaunchKernelGGL(k64_gn_bwd3, dim3(blocks_for(NH)), dim3(256), 0, s, w.t1, params->gn_mean_scale, w.vec1,
                            w.g_u, N, H);
         PVS_CHECK_LAUNCH();
@@ -840,8 +829,7 @@ extern "C" int pvs_egnn_layer_bwd_f64(const PvsLayerDesc* desc, const PvsGraph* 
         if ((rc = pvs64_atb(s, grads->node_w1, 2 * H, w.g_u, H, h, H, N, H, H, w.slabs, false))) return rc;
         if ((rc = pvs64_atb(s, grads->node_w1 + H, 2 * H, w.g_u, H, sv.agg, H, N, H, H, w.slabs, false))) return rc;
     }
-    if (grads->node_b1 && (rc = pvs64_atb(s, grads->node_b1, 1, w.g_u, H, nullptr, 0, N, H, 1, w.slabs, false)))
-        return rc;
+    if (grads->node_b1 && (rc = pvs64_colsum(s, grads->node_b1, w.g_u, H, N, H, w.slabs))) return rc;
     if ((rc = pvs64_gemm(s, g_h, H, w.g_u, H, params->node_w1, 1, 2 * H, nullptr, N, H, H, true))) return rc;
     if ((rc = pvs64_gemm(s, w.g_agg, H, w.g_u, H, params->node_w1 + H, 1, 2 * H, nullptr, N, H, H, false))) return rc;
 
@@ -895,31 +883,24 @@ extern "C" int pvs_egnn_layer_bwd_f64(const PvsLayerDesc* desc, const PvsGraph* 
                                 w.slabs, false)))
                 return rc;
     }
-    if (grads->edge_b1 && (rc = pvs64_atb(s, grads->edge_b1, 1, w.gP, H, nullptr, 0, N, H, 1, w.slabs, false)))
-        return rc;
+    if (grads->edge_b1 && (rc = pvs64_colsum(s, grads->edge_b1, w.gP, H, N, H, w.slabs))) return rc;
     // edge_mlp.2
     if (grads->edge_w2 && (rc = pvs64_atb(s, grads->edge_w2, H, w.gz2s, H, w.a1s, H, E, H, H, w.slabs, false)))
         return rc;
-    if (grads->edge_b2 && (rc = pvs64_atb(s, grads->edge_b2, 1, w.gz2s, H, nullptr, 0, E, H, 1, w.slabs, false)))
-        return rc;
+    if (grads->edge_b2 && (rc = pvs64_colsum(s, grads->edge_b2, w.gz2s, H, E, H, w.slabs))) return rc;
     // coord_mlp (live when the coordinates were updated and a gradient arrived for them)
     if ((f & PVS_UPDATE_COORDS) && g_x_out) {
         if (grads->coord_w1 && (rc = pvs64_atb(s, grads->coord_w1, H, w.gc1s, H, w.ms, H, E, H, H, w.slabs, false)))
             return rc;
-        if (grads->coord_b1 && (rc = pvs64_atb(s, grads->coord_b1, 1, w.gc1s, H, nullptr, 0, E, H, 1, w.slabs, false)))
-            return rc;
-        if (grads->coord_w2 && (rc = pvs64_atb(s, grads->coord_w2, 1, w.rp, KP, nullptr, 0, N, H, 1, w.slabs, false)))
-            return rc;
+        if (grads->coord_b1 && (rc = pvs64_colsum(s, grads->coord_b1, w.gc1s, H, E, H, w.slabs))) return rc;
+        if (grads->coord_w2 && (rc = pvs64_colsum(s, grads->coord_w2, w.rp, KP, N, H, w.slabs))) return rc;
     }
     // attention and the edge gate
     if (f & PVS_EDGE_ATTENTION) {
-        if (grads->att_w && (rc = pvs64_atb(s, grads->att_w, 1, w.rp + H, KP, nullptr, 0, N, H, 1, w.slabs, false)))
-            return rc;
-        if (grads->att_b && (rc = pvs64_atb(s, grads->att_b, 1, w.rp + 6 * H, KP, nullptr, 0, N, 1, 1, w.slabs, false)))
-            return rc;
+        if (grads->att_w && (rc = pvs64_colsum(s, grads->att_w, w.rp + H, KP, N, H, w.slabs))) return rc;
+        if (grads->att_b && (rc = pvs64_colsum(s, grads->att_b, w.rp + 6 * H, KP, N, 1, w.slabs))) return rc;
     }
     if (a.eres && (a.rezero || a.gated) && grads->edge_gate)
-        if ((rc = pvs64_atb(s, grads->edge_gate, 1, w.rp + 6 * H + 1, KP, nullptr, 0, N, 1, 1, w.slabs, false)))
-            return rc;
+        if ((rc = pvs64_colsum(s, grads->edge_gate, w.rp + 6 * H + 1, KP, N, 1, w.slabs))) return rc;
     return 0;
 }

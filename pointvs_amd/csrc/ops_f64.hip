@@ -107,7 +107,7 @@ extern "C" int pvs_linear_bwd_f64(const double* x, const double* w, const double
         if (rc) return rc;
     }
     if (g_b) {
-        int rc = pvs64_atb(s, g_b, 1, g_y, C, nullptr, 0, N, C, 1, slabs, false);
+        int rc = pvs64_colsum(s, g_b, g_y, C, N, C, slabs);
         if (rc) return rc;
     }
     return 0;

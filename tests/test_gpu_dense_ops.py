@@ -201,6 +201,63 @@ def test_route_groups_stay_out_of_the_every_group_switch():
     lib.pvs_profile_reset()
 
 
+def test_two_operand_generic_linear_in_a_hidden_16_layer_exact():
+    """node_mlp.0 of a layer is ONE product over two (input, weight) pairs, y1 = h W1[:, :H]^T + Magg W1[:, H:]^T + b1.
+    At hidden size 16 the MFMA linear refuses the shape and the generic kernel takes both pairs (at 32 / 64 the fused
+    node MLP does, at 128 two accumulating passes). Through pvs_egnn_layer_fwd with every value an integer: edge_mlp.2
+    = 0 * z + b2e with b2e >= 32, where SiLU(v) = v * rcp(1 + exp(-v)) is v itself, so Magg = deg (x) b2e; h, W1 >= 0
+    and b1 = 32 keep y1 >= 32, so u = y1; W2, b2 in [-4, 4]. h_out = (y1) W2^T + b2 is then exact in fp32 in any order
+    (|sums| < 2**24, asserted): one dropped, doubled or swapped row, column or operand shows. 70 rows: one full pass
+    of the kernel's rows plus a ragged remainder; some rows without edges."""
+    from pointvs_amd import _lib
+    from pointvs_amd.functional import _stream, _ws
+    from pointvs_amd.graph import prepare_graph
+    lib = _lib.lib()
+    rng = np.random.default_rng(16)
+    n, H = 70, 16
+    ei = rng.integers(0, n - 6, size=(2, 230))                      # rows n-6 .. n-1 have no edges
+    ei = ei[:, ei[0] != ei[1]]
+    deg = np.bincount(ei[0], minlength=n).astype(F64)
+    h = rng.integers(0, 5, size=(n, H)).astype(F32)
+    p = dict(edge_w1=rng.standard_normal((H, 2 * H + 1)).astype(F32), edge_b1=rng.standard_normal(H).astype(F32),
+             edge_w2=np.zeros((H, H), F32), edge_b2=rng.integers(32, 41, size=H).astype(F32),
+             node_w1=rng.integers(0, 5, size=(H, 2 * H)).astype(F32), node_b1=np.full(H, 32, F32),
+             node_w2=rng.integers(-4, 5, size=(H, H)).astype(F32), node_b2=rng.integers(-4, 5, size=H).astype(F32))
+    magg = deg[:, None] * p['edge_b2'].astype(F64)[None, :]
+    y1 = h.astype(F64) @ p['node_w1'][:, :H].astype(F64).T + magg @ p['node_w1'][:, H:].astype(F64).T + p['node_b1']
+    want = y1 @ p['node_w2'].astype(F64).T + p['node_b2']
+    assert y1.min() >= 32 and np.abs(y1).max() * 4 * H < 2 ** 24 and np.abs(want).max() < 2 ** 24
+    pg = prepare_graph(torch.from_numpy(ei).cuda(), None, n, need_backward=False)
+    tp = {k: dev(v) for k, v in p.items()}
+    pstruct = _lib.PvsLayerParams(*[_lib.ptr(tp.get(name)) for name in _lib.PARAM_FIELDS])
+    desc = _lib.PvsLayerDesc(H, 0, 0, _lib.ACT_CODES['sigmoid'])
+    th, tx = dev(h), dev(rng.standard_normal((n, 3)).astype(F32) * 3)
+    h_out, x_out = torch.empty_like(th), torch.empty_like(tx)
+    saved = torch.empty(lib.pvs_egnn_layer_saved_floats(C.byref(desc), n, pg.n_edges), dtype=torch.float32, device='cuda')
+    ws_bytes = lib.pvs_egnn_layer_workspace_bytes(C.byref(desc), n, pg.n_edges, 0)
+    ws = _ws(ws_bytes, th.device)
+    lib.pvs_profile_reset()
+    lib.pvs_profile_enable(sum(1 << (ROUTE_FIRST_ID + k + 1) for k in range(len(ROUTE_NAMES))))
+    try:
+        rc = lib.pvs_egnn_layer_fwd(C.byref(desc), C.byref(pg.c), C.byref(pstruct), _lib.ptr(th), _lib.ptr(tx), None,
+                                    _lib.ptr(h_out), _lib.ptr(x_out), None, None, None, _lib.ptr(saved), _lib.ptr(ws),
+                                    ws_bytes, _stream(th.device))
+        _lib.check(rc, 'pvs_egnn_layer_fwd')
+        torch.cuda.synchronize()
+    finally:
+        lib.pvs_profile_enable(0)
+    routes = {}
+    for name in ROUTE_NAMES:
+        ms, cnt = C.c_double(0.0), C.c_int64(0)
+        assert lib.pvs_profile_read(name.encode(), C.byref(ms), C.byref(cnt)) == 0
+        if cnt.value:
+            routes[name] = cnt.value
+    lib.pvs_profile_reset()
+    assert routes == {'linear_generic': 4}, routes          # P, Q, node_mlp.0 (two operands), node_mlp.3
+    R.assert_exact(host(h_out), R.Ref(want, 2 * H, None), 'h_out of the hidden-16 layer')
+    assert np.array_equal(host(x_out), host(tx))
+
+
 # ---- PF.linear, fp64 ------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('integer', [True, False], ids=['exact', 'rounded'])
 @pytest.mark.parametrize('bias', [True, False], ids=['bias', 'nobias'])

@@ -1,0 +1,56 @@
+"""(GPU) The kernels a layer enqueues, in order, with their grids: the record that a host-side change left every launch alone.
+Runs one training step through the per-layer calls and one through the stack calls for each hidden size 16 / 32 / 64 /
+128 and four flag sets (plain; GraphNorm + both attentions + residual; gated residual; node attention + residual) on one
+small two-graph batch. Under a kernel trace, once per library and once more with PVS_EGNN_SPLIT_SMALL=1:
+    PVS_EGNN_LIB=<library> rocprofv3 --kernel-trace --output-format csv -d DIR -- python tools/launch_sequence.py
+    python tools/launch_sequence.py --parse DIR OUT.txt      # one line per launch: name, grid, workgroup, LDS
+Two libraries enqueue the same work when their OUT.txt files are equal (profiles/linear_job_refactor.txt)."""
+import csv
+import glob
+import os
+import sys
+from pathlib import Path
+
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+
+FLAGS = {
+    'plain': dict(),
+    'attn_gn': dict(graphnorm=True, node_attention=True, edge_attention=True, residual=True),
+    'gated': dict(residual=True, gated_residual=True),
+    'natt_res': dict(node_attention=True, residual=True),
+}
+
+
+def parse(trace_dir, out_path):
+    files = glob.glob(trace_dir + '/**/*kernel_trace.csv', recursive=True)
+    assert len(files) == 1, files
+    rows = list(csv.DictReader(open(files[0])))
+    rows.sort(key=lambda r: (int(r.get('Dispatch_Id', 0) or 0), int(r['Start_Timestamp'])))
+    with open(out_path, 'w') as out:
+        for r in rows:
+            grid, wg = ('x'.join(r[f'{what}_{a}'] for a in 'XYZ') for what in ('Grid_Size', 'Workgroup_Size'))
+            out.write(f"{r['Kernel_Name']} grid {grid} wg {wg} lds {r.get('LDS_Block_Size', '?')}\n")
+    print(out_path, len(rows), 'launches')
+
+
+def run():
+    import torch
+    from tests.test_gpu_properties import make_model, random_graph
+    g = random_graph(300, 5000, seed=3, n_graphs=2).to('cuda')
+    for hidden in (16, 32, 64, 128):
+        for kw in FLAGS.values():
+            model, _ = make_model(seed=5, k=hidden, num_layers=2, **kw)
+            model.train()
+            for stack in ('0', '1'):
+                os.environ['PVS_EGNN_STACK'] = stack
+                model.optimiser.zero_grad()
+                y = model(g).reshape(-1)
+                model.get_loss(torch.ones_like(y), y).backward()
+                torch.cuda.synchronize()
+
+
+if __name__ == '__main__':
+    if len(sys.argv) == 4 and sys.argv[1] == '--parse':
+        parse(sys.argv[2], sys.argv[3])
+    else:
+        run()
