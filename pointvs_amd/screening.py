@@ -9,6 +9,7 @@ the edges that touch a ligand atom (`pvs_egnn_layer_fwd_partial`), the other lay
 graph. Graphs are built on the GPU from the coordinates (radius_graph.py). Scores equal the plain
 `model(batch)` forward up to fp32 summation order.
 """
+import contextlib
 import ctypes as C
 
 import torch
@@ -22,35 +23,63 @@ def _stream(dev):
     return _lib.stream(dev)
 
 
-class ReceptorScreen:
-    """scores = ReceptorScreen(model, rec_pos, feats, n_lig, batch_size, edge_radius)(lig_poses)
+def _csr_buffers(dev, n_nodes, cap_l, cap=None, **extra):
+    """Buffers of a device-built pose-batch graph over n_nodes nodes: the ligand-touching CSR (`*_l`, room for cap_l
+    edges) and, with `cap`, the full CSR and its inv_deg; the builder's status word and its pinned host copy; `ones`
+    (the ligand-touching graph's inv_deg). The builders read f['cap'] / f['cap_l'] at every launch."""
+    i32 = dict(dtype=torch.int32, device=dev)
+    f = dict(cap=cap, cap_l=cap_l, status=torch.zeros(1, **i32), host=torch.zeros(1, dtype=torch.int32).pin_memory(),
+             **extra)
+    for tag, c in (('', cap), ('_l', cap_l)):
+        if c is not None:
+            f['rowptr' + tag] = torch.empty(n_nodes + 1, **i32)
+            f['row' + tag] = torch.empty(c, **i32)
+            f['col' + tag] = torch.empty(c, **i32)
+            f['etype' + tag] = torch.empty(c, dtype=torch.uint8, device=dev)
+    if cap is not None:
+        f['inv_deg'] = torch.empty(n_nodes, dtype=torch.float32, device=dev)
+    f['ones'] = torch.ones(n_nodes, dtype=torch.float32, device=dev)
+    return f
 
-    feats [n_lig + n_rec, F]: ligand rows first, last column = bp (preprocessing.make_bit_vector);
-    lig_poses [batch_size, n_lig, 3] on the device. Returns the model's raw outputs [batch_size, ...]."""
 
-    def __init__(self, model, rec_pos, feats, n_lig, batch_size, edge_radius, intra_radius=None):
+def _ligand_csr(f, n_nodes, n_end):
+    """PvsGraph of f's ligand-touching CSR over the first n_nodes nodes; its edge count stays on the device, in
+    rowptr_l[n_end] (the rows from n_nodes to n_end are padding, without edges)."""
+    gl = _lib.PvsGraph()
+    gl.n_nodes, gl.n_edges = n_nodes, f['cap_l']
+    gl.rowptr, gl.row, gl.col, gl.etype = (_lib.ptr(f[k + '_l']) for k in ('rowptr', 'row', 'col', 'etype'))
+    gl.inv_deg = _lib.ptr(f['ones'])
+    gl.n_edges_dev = f['rowptr_l'][n_end:].data_ptr()
+    return gl
+
+
+def _graph_pair(f, n_nodes, n_end):
+    """(PreparedGraph of f's full CSR, PvsGraph of its ligand-touching CSR) over the first n_nodes nodes, both with
+    device-side edge counts (rowptr[n_end])."""
+    from .graph import PreparedGraph
+    pg = PreparedGraph(n_nodes, f['cap'], 3, dict(rowptr=f['rowptr'], row=f['row'], col=f['col'], etype=f['etype'],
+                                                   inv_deg=f['inv_deg'], status=f['status']))
+    pg._status_checked = True
+    pg.c.n_edges_dev = f['rowptr'][n_end:].data_ptr()
+    return pg, _ligand_csr(f, n_nodes, n_end)
+
+
+class _ReceptorSideScreen:
+    """What ReceptorScreen and LibraryScreen do alike, once: the receptor-receptor sums of the first layer and their
+    weights fingerprint, the ligand-touching first layer, the layers after it, the deferred status word and the
+    capture / replay scaffolding. A subclass provides `_cache_receptor_sums()` (where the sums are kept),
+    `_raise_for(code)` (its status bits), `_head(h)` (pooling + head) and, once its builder has run, `_fast` (the
+    live buffer dict with `status` / `host`)."""
+
+    def __init__(self, model, edge_radius, intra_radius):
         if any(p.dtype == torch.float64 for p in model.parameters()):
-            raise NotImplementedError('ReceptorScreen and its pose-batch builder are fp32 only (no fp64 screening '
-                                      'kernels): score fp64 models through the model forward')
+            raise NotImplementedError(f'{type(self).__name__} and its pose-batch builder are fp32 only (no fp64 '
+                                      'screening kernels): score fp64 models through the model forward')
         layers = list(model.layers)
         self.model, self.embed, self.egnn = model, layers[0], layers[1:]
-        first = self.egnn[0] if self.egnn else None
-        self.reuse = (first is not None and first.hidden_nf in (32, 64) and not first.softmax_attention
-                      and not first.edge_residual)
-        dev = rec_pos.device
-        self.batcher = PoseBatcher(rec_pos, feats, n_lig, batch_size, edge_radius, intra_radius)
-        self.n_lig, self.b = n_lig, batch_size
         self.r_inter = edge_radius
         self.r_intra = edge_radius if intra_radius is None else intra_radius
-        self._lig_buf, self._pending, self._l1_ws = None, None, None
-        self._fast = None
-        self._graph_ptr = self.batcher.batch.ptr.to(device=dev, dtype=torch.int32)
-        # the specialised pose-batch builder (pvs_screen_graph_build) leaves the edge counts on the
-        # device; layers that return edge messages (edge_residual) need them on the host
-        self.fast_graph = self.reuse and n_lig <= 64 and not any(l.edge_residual for l in self.egnn)
-        self._rec_pos, self._feats = rec_pos, feats
-        if self.reuse:
-            self._cache_receptor_sums()
+        self._graph, self._captured, self._pending, self._l1_ws, self._fast = None, False, None, None, None
 
     def _weights_fingerprint(self):
         """Version counters of everything the cached receptor-receptor sums were computed from (the
@@ -58,23 +87,41 @@ class ReceptorScreen:
         mods = [self.embed.m, self.egnn[0]]
         return tuple((p.data_ptr(), p._version) for m in mods for p in m.parameters())
 
-    def _cache_receptor_sums(self):
-        """Per-node sums of the first layer's receptor-receptor messages (pose independent)."""
+    def stale(self):
+        """True when the weights the cached receptor-receptor sums came from have changed since
+        (load_weights(), an optimiser step): a captured step has those sums baked in."""
+        return self.reuse and self._fingerprint != self._weights_fingerprint()
+
+    def _weights_changed(self):
+        return RuntimeError(f'{type(self).__name__}: the model\'s weights changed after capture(); build a new screen')
+
+    def _refresh_if_stale(self):
+        """The weights changed under the screen (load_weights(), a training step): the cached sums are recomputed
+        once - never inside a captured graph, which bakes them in."""
+        if self._fingerprint != self._weights_fingerprint():
+            if torch.cuda.is_current_stream_capturing() or self._graph is not None:
+                raise self._weights_changed()
+            self._cache_receptor_sums()
+
+    def _first_layer_args(self):
+        first = self.egnn[0]
+        desc = _lib.PvsLayerDesc(*first._desc())
+        params = [None if p is None else p.detach().float().contiguous() for p in first._params()]
+        return desc, params, _lib.PvsLayerParams(*[_lib.ptr(p) for p in params])
+
+    def _receptor_sums(self, rec_feats, rec_pos):
+        """Per-node sums of the first layer's receptor-receptor messages (pose and ligand independent):
+        (magg [n_rec,H], xsum [n_rec,3], deg [n_rec]). Keeps the receptor-receptor template CSR (`_rr`: rowptr /
+        col, receptor-local ids) and the fingerprint of the weights used."""
         lib = _lib.lib()
-        rec_pos, feats, first = self._rec_pos, self._feats, self.egnn[0]
-        n_lig, batch_size = self.n_lig, self.b
-        dev = rec_pos.device
-        n_rec = rec_pos.shape[0]
+        dev, n_rec = rec_pos.device, rec_pos.shape[0]
         self._fingerprint = self._weights_fingerprint()
         with torch.no_grad():
-            feats_rec = feats[n_lig:].to(dev).float()
-            h_rec = self.embed.embed(feats_rec, rec_pos)
+            h_rec = self.embed.embed(rec_feats, rec_pos)
             pg = radius_graph(rec_pos, torch.ones(n_rec, dtype=torch.uint8, device=dev), None,
                               self.r_inter, self.r_intra, need_backward=False)
-            desc = _lib.PvsLayerDesc(*first._desc())
-            params = [None if p is None else p.detach().float().contiguous() for p in first._params()]
-            pstruct = _lib.PvsLayerParams(*[_lib.ptr(p) for p in params])
-            magg = torch.empty((n_rec, first.hidden_nf), dtype=torch.float32, device=dev)
+            desc, params, pstruct = self._first_layer_args()
+            magg = torch.empty((n_rec, self.egnn[0].hidden_nf), dtype=torch.float32, device=dev)
             xsum = torch.empty((n_rec, 3), dtype=torch.float32, device=dev)
             ws_bytes = lib.pvs_egnn_layer_workspace_bytes(C.byref(desc), n_rec, pg.n_edges, 2)
             ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
@@ -83,16 +130,125 @@ class ReceptorScreen:
                 _lib.ptr(rec_pos.contiguous()), _lib.ptr(magg), _lib.ptr(xsum), _lib.ptr(ws), ws_bytes,
                 _stream(dev)), 'pvs_egnn_layer_edge_sums')
             deg = (pg.t['rowptr'][1:] - pg.t['rowptr'][:-1]).float()
-            self._rr = pg          # receptor-receptor template (rowptr / col, receptor-local ids)
-            n = n_lig + n_rec
-            # batch layout: [ligand rows (no base) | receptor rows] per pose
-            self.base_magg = torch.zeros((batch_size, n, first.hidden_nf), dtype=torch.float32, device=dev)
-            self.base_xsum = torch.zeros((batch_size, n, 3), dtype=torch.float32, device=dev)
-            self.base_deg = torch.zeros((batch_size, n), dtype=torch.float32, device=dev)
-            self.base_magg[:, n_lig:] = magg
-            self.base_xsum[:, n_lig:] = xsum
-            self.base_deg[:, n_lig:] = deg
-            torch.cuda.current_stream(dev).synchronize()    # ws / pg go out of scope
+            self._rr = pg
+            torch.cuda.current_stream(dev).synchronize()    # ws / params go out of scope
+        return magg, xsum, deg
+
+    def _partial_first_layer(self, g, h, x, base_magg, base_xsum, base_deg, ws_nodes, ws_edges):
+        """First layer over the ligand-touching edges `g` on top of the receptor-receptor sums `base_*` (one row
+        per node). ws_nodes / ws_edges size the saved / workspace pair, allocated at the first call."""
+        lib = _lib.lib()
+        dev = h.device
+        desc, params, pstruct = self._first_layer_args()
+        h_out, x_out = torch.empty_like(h), torch.empty_like(x)
+        natt = torch.empty(h.shape[0], dtype=torch.float32, device=dev) if self.egnn[0].node_attention else None
+        if self._l1_ws is None:
+            self._l1_ws = (
+                torch.empty(lib.pvs_egnn_layer_saved_floats(C.byref(desc), ws_nodes, ws_edges), dtype=torch.float32,
+                            device=dev),
+                torch.empty(lib.pvs_egnn_layer_workspace_bytes(C.byref(desc), ws_nodes, ws_edges, 2),
+                            dtype=torch.uint8, device=dev))
+        saved, ws = self._l1_ws
+        _lib.check(lib.pvs_egnn_layer_fwd_partial(
+            C.byref(desc), C.byref(g), C.byref(pstruct), _lib.ptr(h), _lib.ptr(x), _lib.ptr(base_magg),
+            _lib.ptr(base_xsum), _lib.ptr(base_deg), _lib.ptr(h_out), _lib.ptr(x_out), _lib.ptr(natt),
+            _lib.ptr(saved), _lib.ptr(ws), ws.numel(), _stream(dev)), 'pvs_egnn_layer_fwd_partial')
+        return h_out, x_out
+
+    def _tail(self, pg_full, h, x):
+        """The layers after the first over the full graph, then the head."""
+        m_sorted = None
+        for layer in self.egnn[1:]:
+            h, x, m_sorted = layer.forward_prepared(pg_full, h, x, m_sorted, need_m=layer.edge_residual,
+                                                    need_coords=layer is not self.egnn[-1])
+        return h if self.model.feats_linear_layers is None else self._head(h)
+
+    def _queue_status(self, status, host):
+        """Queues the copy of a builder's status word into its pinned host copy; check() reads it later."""
+        host.copy_(status, non_blocking=True)
+        event = torch.cuda.Event()
+        event.record(torch.cuda.current_stream(status.device))
+        self._pending = (event, host)
+
+    def check(self):
+        """Raises if the edge buffers of an earlier batch were too small (checked one batch late so that the loop
+        never waits for the device; call once more after the last batch)."""
+        if self._pending is not None:
+            (event, host), self._pending = self._pending, None
+            event.synchronize()
+            self._raise_for(int(host.item()))
+
+    def _capture(self, step, dev):
+        """Captures step() (builder + layer stack + head) in a hipGraph on `dev` after two eager warm-up calls."""
+        stream = torch.cuda.Stream(dev)
+        stream.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(stream):
+            for _ in range(2):
+                step()                         # warm-up: probe, buffers, lazy allocations
+            self.check()
+            torch.cuda.synchronize(dev)
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph, stream=stream):
+                self._static_out = step()
+        self._graph, self._captured = graph, True
+        torch.cuda.current_stream(dev).wait_stream(stream)
+        return self
+
+    def _replay(self, load):
+        if self.stale():           # host-only comparison of version counters
+            raise self._weights_changed()
+        self.check()
+        load()
+        self._graph.replay()
+        self._queue_status(self._fast['status'], self._fast['host'])
+        return self._static_out
+
+
+class ReceptorScreen(_ReceptorSideScreen):
+    """scores = ReceptorScreen(model, rec_pos, feats, n_lig, batch_size, edge_radius)(lig_poses)
+
+    feats [n_lig + n_rec, F]: ligand rows first, last column = bp (preprocessing.make_bit_vector);
+    lig_poses [batch_size, n_lig, 3] on the device. Returns the model's raw outputs [batch_size, ...]."""
+
+    def __init__(self, model, rec_pos, feats, n_lig, batch_size, edge_radius, intra_radius=None):
+        super().__init__(model, edge_radius, intra_radius)
+        first = self.egnn[0] if self.egnn else None
+        self.reuse = (first is not None and first.hidden_nf in (32, 64) and not first.softmax_attention
+                      and not first.edge_residual)
+        dev = rec_pos.device
+        self.batcher = PoseBatcher(rec_pos, feats, n_lig, batch_size, edge_radius, intra_radius)
+        self.n_lig, self.b = n_lig, batch_size
+        self._lig_buf = None
+        self._graph_ptr = self.batcher.batch.ptr.to(device=dev, dtype=torch.int32)
+        # the specialised pose-batch builder (pvs_screen_graph_build) leaves the edge counts on the
+        # device; layers that return edge messages (edge_residual) need them on the host
+        self.fast_graph = self.reuse and n_lig <= 64 and not any(l.edge_residual for l in self.egnn)
+        self._rec_pos, self._feats = rec_pos, feats
+        if self.reuse:
+            self._cache_receptor_sums()
+
+    def _cache_receptor_sums(self):
+        """The receptor sums tiled into the batch layout: [ligand rows (no base) | receptor rows] per pose."""
+        dev, n_lig = self._rec_pos.device, self.n_lig
+        magg, xsum, deg = self._receptor_sums(self._feats[n_lig:].to(dev).float(), self._rec_pos)
+        n = n_lig + self._rec_pos.shape[0]
+        self.base_magg = torch.zeros((self.b, n, magg.shape[1]), dtype=torch.float32, device=dev)
+        self.base_xsum = torch.zeros((self.b, n, 3), dtype=torch.float32, device=dev)
+        self.base_deg = torch.zeros((self.b, n), dtype=torch.float32, device=dev)
+        self.base_magg[:, n_lig:] = magg
+        self.base_xsum[:, n_lig:] = xsum
+        self.base_deg[:, n_lig:] = deg
+        # the tiling copies are done before magg / xsum / deg are released and before a capture opens its side
+        # stream; without this wait a sweep over 57 size buckets read corrupted status words
+        # (profiles/screening_refactor.txt, 7)
+        torch.cuda.current_stream(dev).synchronize()
+
+    def _probe_cap_l(self, batch):
+        """One synchronous probe of the loaded batch sizes the ligand-edge buffers; later batches are checked
+        asynchronously."""
+        probe = radius_graph(batch.pos, batch.x[:, -1], batch.ptr, self.r_inter, self.r_intra,
+                             max_graph_nodes=self.batcher.n, need_backward=False, ligand_pairs_only=True)
+        return min(4 * self.n_lig * self.batcher.n * self.b, 2 * probe.n_edges + 4096)
 
     def _ligand_graph(self, batch):
         """CSR of the full graph's ligand-touching edges, filtered on the device (no host round trip);
@@ -102,106 +258,37 @@ class ReceptorScreen:
         dev = batch.pos.device
         n = full.n_nodes
         if self._lig_buf is None:
-            # one synchronous probe sizes the buffers; later batches are checked asynchronously
-            probe = radius_graph(batch.pos, batch.x[:, -1], batch.ptr, self.r_inter, self.r_intra,
-                                 max_graph_nodes=self.batcher.n, need_backward=False, ligand_pairs_only=True)
-            cap = min(4 * self.n_lig * self.batcher.n * self.b, 2 * probe.n_edges + 4096)
-            i32 = dict(dtype=torch.int32, device=dev)
-            self._lig_buf = dict(
-                cap=cap, rowptr=torch.empty(n + 1, **i32), row=torch.empty(cap, **i32), col=torch.empty(cap, **i32),
-                etype=torch.empty(cap, dtype=torch.uint8, device=dev), status=torch.zeros(1, **i32),
-                ones=torch.ones(n, dtype=torch.float32, device=dev),
-                ws=torch.empty(lib.pvs_graph_filter_workspace_bytes(n), dtype=torch.uint8, device=dev),
-                bp=batch.x[:, -1].to(torch.uint8).contiguous(),
-                host=torch.zeros(1, dtype=torch.int32).pin_memory())
+            b = _csr_buffers(dev, n, self._probe_cap_l(batch))
+            b['ws'] = torch.empty(lib.pvs_graph_filter_workspace_bytes(n), dtype=torch.uint8, device=dev)
+            b['bp'] = batch.x[:, -1].to(torch.uint8).contiguous()
+            b['gl'] = _ligand_csr(b, n, n)
+            self._lig_buf = b
         b = self._lig_buf
         self.check()      # the previous batch's overflow flag has landed by now
         _lib.check(lib.pvs_graph_filter_ligand_edges(
-            C.byref(full.c), _lib.ptr(b['bp']), b['cap'], _lib.ptr(b['rowptr']), _lib.ptr(b['row']),
-            _lib.ptr(b['col']), _lib.ptr(b['etype']), _lib.ptr(b['status']), _lib.ptr(b['ws']), b['ws'].numel(),
+            C.byref(full.c), _lib.ptr(b['bp']), b['cap_l'], _lib.ptr(b['rowptr_l']), _lib.ptr(b['row_l']),
+            _lib.ptr(b['col_l']), _lib.ptr(b['etype_l']), _lib.ptr(b['status']), _lib.ptr(b['ws']), b['ws'].numel(),
             _stream(dev)), 'pvs_graph_filter_ligand_edges')
-        b['host'].copy_(b['status'], non_blocking=True)
-        self._pending = torch.cuda.Event()
-        self._pending.record(torch.cuda.current_stream(dev))
-        g = _lib.PvsGraph()
-        g.n_nodes, g.n_edges = n, b['cap']
-        g.rowptr, g.row, g.col, g.etype = (_lib.ptr(b[k]) for k in ('rowptr', 'row', 'col', 'etype'))
-        g.inv_deg = _lib.ptr(b['ones'])
-        g.n_edges_dev = b['rowptr'][n:].data_ptr()
-        return g
+        self._queue_status(b['status'], b['host'])
+        return b['gl']
 
-    def check(self):
-        """Raises if the ligand-edge buffers of an earlier batch were too small (checked one batch
-        late so that the loop never waits for the device; call once more after the last batch)."""
-        if self._pending is not None:
-            self._pending.synchronize()
-            self._pending = None
-            if int(self._lig_buf['host'].item()) & 4:
-                raise RuntimeError('ReceptorScreen: ligand-edge buffer overflow (more ligand contacts than '
-                                   'twice the first batch); rebuild the screen with a larger probe')
-
-    def _first_layer(self, batch, h, x, g=None):
-        lib = _lib.lib()
-        first = self.egnn[0]
-        dev = h.device
-        if g is None:
-            g = self._ligand_graph(batch)
-        desc = _lib.PvsLayerDesc(*first._desc())
-        params = [None if p is None else p.detach().float().contiguous() for p in first._params()]
-        pstruct = _lib.PvsLayerParams(*[_lib.ptr(p) for p in params])
-        n = h.shape[0]
-        h_out, x_out = torch.empty_like(h), torch.empty_like(x)
-        natt = torch.empty(n, dtype=torch.float32, device=dev) if first.node_attention else None
-        if self._l1_ws is None:
-            self._l1_ws = (
-                torch.empty(lib.pvs_egnn_layer_saved_floats(C.byref(desc), n, g.n_edges), dtype=torch.float32,
-                            device=dev),
-                torch.empty(lib.pvs_egnn_layer_workspace_bytes(C.byref(desc), n, g.n_edges, 2), dtype=torch.uint8,
-                            device=dev))
-        saved, ws = self._l1_ws
-        _lib.check(lib.pvs_egnn_layer_fwd_partial(
-            C.byref(desc), C.byref(g), C.byref(pstruct), _lib.ptr(h), _lib.ptr(x),
-            _lib.ptr(self.base_magg), _lib.ptr(self.base_xsum), _lib.ptr(self.base_deg), _lib.ptr(h_out),
-            _lib.ptr(x_out), _lib.ptr(natt), _lib.ptr(saved), _lib.ptr(ws), ws.numel(), _stream(dev)),
-            'pvs_egnn_layer_fwd_partial')
-        return h_out, x_out
+    def _raise_for(self, code):
+        if code & 4:
+            raise RuntimeError('ReceptorScreen: ligand-edge buffer overflow (more ligand contacts than '
+                               'twice the first batch); rebuild the screen with a larger probe')
 
     def _build_fast(self, lig_poses):
         """Full graph + ligand-touching subgraph of the pose batch from the receptor template
         (pvs_screen_graph_build): no receptor-receptor distance tests, no host round trip."""
-        from .graph import PreparedGraph
         lib = _lib.lib()
         dev = lig_poses.device
         n, b_, n_rec = self.batcher.n, self.b, self.batcher.n - self.n_lig
-        big_n = n * b_
         if self._fast is None:
-            batch = self.batcher.load(lig_poses)       # one synchronous probe sizes the buffers
-            probe = radius_graph(batch.pos, batch.x[:, -1], batch.ptr, self.r_inter, self.r_intra,
-                                 max_graph_nodes=n, need_backward=False, ligand_pairs_only=True)
-            cap_l = min(4 * self.n_lig * n * b_, 2 * probe.n_edges + 4096)
-            cap = b_ * self._rr.n_edges + cap_l
-            i32 = dict(dtype=torch.int32, device=dev)
-            f = dict(cap=cap, cap_l=cap_l, status=torch.zeros(1, **i32),
-                     host=torch.zeros(1, dtype=torch.int32).pin_memory(),
-                     state=torch.empty(lib.pvs_screen_graph_state_bytes(b_, self.n_lig, n_rec), dtype=torch.uint8,
-                                       device=dev))
-            for tag, c in (('', cap), ('_l', cap_l)):
-                f['rowptr' + tag] = torch.empty(big_n + 1, **i32)
-                f['row' + tag] = torch.empty(c, **i32)
-                f['col' + tag] = torch.empty(c, **i32)
-                f['etype' + tag] = torch.empty(c, dtype=torch.uint8, device=dev)
-            f['inv_deg'] = torch.empty(big_n, dtype=torch.float32, device=dev)
-            f['ones'] = torch.ones(big_n, dtype=torch.float32, device=dev)
-            pg = PreparedGraph(big_n, cap, 3, dict(rowptr=f['rowptr'], row=f['row'], col=f['col'],
-                                                    etype=f['etype'], inv_deg=f['inv_deg'], status=f['status']))
-            pg._status_checked = True
-            pg.c.n_edges_dev = f['rowptr'][big_n:].data_ptr()
-            gl = _lib.PvsGraph()
-            gl.n_nodes, gl.n_edges = big_n, cap_l
-            gl.rowptr, gl.row, gl.col, gl.etype = (_lib.ptr(f[k + '_l']) for k in ('rowptr', 'row', 'col', 'etype'))
-            gl.inv_deg = _lib.ptr(f['ones'])
-            gl.n_edges_dev = f['rowptr_l'][big_n:].data_ptr()
-            f['pg'], f['gl'] = pg, gl
+            cap_l = self._probe_cap_l(self.batcher.load(lig_poses))
+            f = _csr_buffers(dev, n * b_, cap_l, b_ * self._rr.n_edges + cap_l,
+                             state=torch.empty(lib.pvs_screen_graph_state_bytes(b_, self.n_lig, n_rec),
+                                               dtype=torch.uint8, device=dev))
+            f['pg'], f['gl'] = _graph_pair(f, n * b_, n * b_)
             self._fast = f
         f = self._fast
         capturing = torch.cuda.is_current_stream_capturing()
@@ -216,16 +303,9 @@ class ReceptorScreen:
             _lib.ptr(f['inv_deg']), _lib.ptr(f['rowptr_l']), _lib.ptr(f['row_l']), _lib.ptr(f['col_l']),
             _lib.ptr(f['etype_l']), _lib.ptr(f['status']), _lib.ptr(f['state']), f['state'].numel(),
             _stream(dev)), 'pvs_screen_graph_build')
-        self._lig_buf = dict(host=f['host'])       # check() reads the overflow flag from here
         if not capturing:
-            self._poll_status()
+            self._queue_status(f['status'], f['host'])
         return f['pg'], f['gl']
-
-    def _poll_status(self):
-        f = self._fast
-        f['host'].copy_(f['status'], non_blocking=True)
-        self._pending = torch.cuda.Event()
-        self._pending.record(torch.cuda.current_stream(f['status'].device))
 
     def capture(self, example_poses):
         """Captures one whole screening step (graph build + layer stack + head) in a hipGraph; after
@@ -234,46 +314,20 @@ class ReceptorScreen:
         (self.fast_graph)."""
         if not self.fast_graph:
             raise RuntimeError('capture needs the pose-batch builder (<= 64 ligand atoms, no edge_residual)')
-        dev = example_poses.device
         self._static_in = example_poses.clone()
-        stream = torch.cuda.Stream(dev)
-        stream.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(stream):
-            for _ in range(2):
-                self(self._static_in)          # warm-up: probe, buffers, lazy allocations
-            self.check()
-            torch.cuda.synchronize(dev)
-            self._graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self._graph, stream=stream):
-                self._static_out = self(self._static_in)
-        torch.cuda.current_stream(dev).wait_stream(stream)
-        return self
-
-    def stale(self):
-        """True when the weights the cached receptor-receptor sums came from have changed since
-        (load_weights(), an optimiser step): a captured step has those sums baked in."""
-        return self.reuse and self._fingerprint != self._weights_fingerprint()
+        return self._capture(lambda: self(self._static_in), example_poses.device)
 
     def replay(self, lig_poses):
-        if self.stale():           # host-only comparison of version counters
-            raise RuntimeError('ReceptorScreen: the model\'s weights changed after capture(); build a new screen')
-        self.check()
-        self._static_in.copy_(lig_poses)
-        self._graph.replay()
-        self._poll_status()
-        return self._static_out
+        return self._replay(lambda: self._static_in.copy_(lig_poses))
+
+    def _head(self, h):
+        return self.model._pool_and_head(self.model.feats_linear_layers, h, self._graph_ptr, self.b)
 
     @torch.no_grad()
     def __call__(self, lig_poses):
-        model = self.model
         if not self.reuse:
-            return model(self.batcher.load(lig_poses))
-        if self._fingerprint != self._weights_fingerprint():
-            # the weights changed under the screen (load_weights(), a training step): the cached sums
-            # are stale - recompute them once (never inside a captured graph, which bakes them in)
-            if torch.cuda.is_current_stream_capturing() or getattr(self, '_graph', None) is not None:
-                raise RuntimeError('ReceptorScreen: the model\'s weights changed after capture(); build a new screen')
-            self._cache_receptor_sums()
+            return self.model(self.batcher.load(lig_poses))
+        self._refresh_if_stale()
         if self.fast_graph:
             pg_full, g_lig = self._build_fast(lig_poses)
             batch = self.batcher.batch
@@ -282,14 +336,11 @@ class ReceptorScreen:
             pg_full, g_lig = batch.prepared, None
         h = self.embed.embed(batch.x.float(), batch.pos).contiguous()
         x = batch.pos.contiguous()
-        h, x = self._first_layer(batch, h, x, g_lig)
-        m_sorted = None
-        for layer in self.egnn[1:]:
-            h, x, m_sorted = layer.forward_prepared(pg_full, h, x, m_sorted, need_m=layer.edge_residual,
-                                                    need_coords=layer is not self.egnn[-1])
-        if model.feats_linear_layers is None:
-            return h
-        return model._pool_and_head(model.feats_linear_layers, h, self._graph_ptr, self.b)
+        if g_lig is None:
+            g_lig = self._ligand_graph(batch)
+        h, x = self._partial_first_layer(g_lig, h, x, self.base_magg, self.base_xsum, self.base_deg,
+                                         h.shape[0], g_lig.n_edges)
+        return self._tail(pg_full, h, x)
 
 
 def plan_library(pose_counts, lig_sizes, batch_size, max_lig_atoms=64):
@@ -315,7 +366,7 @@ def plan_library(pose_counts, lig_sizes, batch_size, max_lig_atoms=64):
     return batches
 
 
-class LibraryScreen:
+class LibraryScreen(_ReceptorSideScreen):
     """Library screening: every one of the `batch_size` slots of a batch holds one pose of ANY ligand of up to
     `max_lig_atoms` (<= 64) atoms against the one receptor, or nothing (the last batch of a library).
 
@@ -333,15 +384,11 @@ class LibraryScreen:
     32 / 64) take the plain forward on the same mixed batch. fp32 only."""
 
     def __init__(self, model, rec_pos, rec_feats, batch_size, max_lig_atoms, edge_radius, intra_radius=None):
-        if any(p.dtype == torch.float64 for p in model.parameters()):
-            raise NotImplementedError('LibraryScreen and its pose-batch builder are fp32 only (no fp64 screening '
-                                      'kernels): score fp64 models through the model forward')
+        super().__init__(model, edge_radius, intra_radius)
         if not 1 <= int(max_lig_atoms) <= 64:
             raise ValueError(f'max_lig_atoms must be 1..64 (got {max_lig_atoms}); larger ligands go through '
                              'ReceptorScreen')
         _lib.require_hip(rec_pos)
-        layers = list(model.layers)
-        self.model, self.embed, self.egnn = model, layers[0], layers[1:]
         first = self.egnn[0] if self.egnn else None
         self.reuse = (first is not None and first.hidden_nf in (32, 64) and not first.softmax_attention
                       and not any(l.edge_residual for l in self.egnn))
@@ -351,50 +398,24 @@ class LibraryScreen:
         self.n_rec = int(rec_pos.shape[0])
         self.l_cap = self.b * self.max_lig_atoms
         self.n_cap = self.l_cap + self.b * self.n_rec
-        self.r_inter = edge_radius
-        self.r_intra = edge_radius if intra_radius is None else intra_radius
         self._rec_pos = rec_pos.float().contiguous()
         self._rec_feats = rec_feats.to(dev).float().contiguous()
         n_feats = int(self._rec_feats.shape[1])
-        i32 = dict(dtype=torch.int32, device=dev)
         self.lig_pos = torch.zeros((self.l_cap, 3), dtype=torch.float32, device=dev)
         self.lig_feats = torch.zeros((self.l_cap, n_feats), dtype=torch.float32, device=dev)
-        self.lig_ptr = torch.zeros(self.b + 1, **i32)
+        self.lig_ptr = torch.zeros(self.b + 1, dtype=torch.int32, device=dev)
         self.n_atoms = 0             # host copies of what load() was given
         self._sizes = [0] * self.b
         self._stage, self._stage_at = [], 0
-        self._pending, self._f, self._l1_ws, self._graph = None, None, None, None
         if self.reuse:
             self._cache_receptor_sums()
 
-    _weights_fingerprint = ReceptorScreen._weights_fingerprint
-    stale = ReceptorScreen.stale
-
     def _cache_receptor_sums(self):
-        """Receptor-receptor template and the first layer's receptor-receptor sums, [n_rec, .] (pose and
-        ligand independent)."""
-        lib = _lib.lib()
-        rec_pos, first, n_rec = self._rec_pos, self.egnn[0], self.n_rec
-        dev = rec_pos.device
-        self._fingerprint = self._weights_fingerprint()
-        with torch.no_grad():
-            h_rec = self.embed.embed(self._rec_feats, rec_pos)
-            pg = radius_graph(rec_pos, torch.ones(n_rec, dtype=torch.uint8, device=dev), None,
-                              self.r_inter, self.r_intra, need_backward=False)
-            desc = _lib.PvsLayerDesc(*first._desc())
-            params = [None if p is None else p.detach().float().contiguous() for p in first._params()]
-            pstruct = _lib.PvsLayerParams(*[_lib.ptr(p) for p in params])
-            self.rec_magg = torch.empty((n_rec, first.hidden_nf), dtype=torch.float32, device=dev)
-            self.rec_xsum = torch.empty((n_rec, 3), dtype=torch.float32, device=dev)
-            ws_bytes = lib.pvs_egnn_layer_workspace_bytes(C.byref(desc), n_rec, pg.n_edges, 2)
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            _lib.check(lib.pvs_egnn_layer_edge_sums(
-                C.byref(desc), C.byref(pg.c), C.byref(pstruct), _lib.ptr(h_rec.contiguous()), _lib.ptr(rec_pos),
-                _lib.ptr(self.rec_magg), _lib.ptr(self.rec_xsum), _lib.ptr(ws), ws_bytes, _stream(dev)),
-                'pvs_egnn_layer_edge_sums')
-            self.rec_deg = (pg.t['rowptr'][1:] - pg.t['rowptr'][:-1]).float().contiguous()
-            self._rr = pg
-            torch.cuda.current_stream(dev).synchronize()    # ws goes out of scope
+        """The receptor sums kept once, [n_rec, .]; the builder's node-table struct points at them."""
+        self.rec_magg, self.rec_xsum, self.rec_deg = self._receptor_sums(self._rec_feats, self._rec_pos)
+        if self._fast is not None:
+            t = self._fast['tables']
+            t.rec_magg, t.rec_xsum, t.rec_deg = (_lib.ptr(v) for v in (self.rec_magg, self.rec_xsum, self.rec_deg))
 
     # ---- inputs ----
     def load_packed(self, lig_pos, lig_feats, lig_ptr, sizes):
@@ -454,20 +475,14 @@ class LibraryScreen:
         i32 = dict(dtype=torch.int32, device=dev)
         f32 = dict(dtype=torch.float32, device=dev)
         hid = self.egnn[0].hidden_nf
-        f = dict(cap=cap, cap_l=cap_l, status=torch.zeros(1, **i32),
-                 host=torch.zeros(1, dtype=torch.int32).pin_memory(),
-                 state=torch.empty(lib.pvs_screen_graph_ragged_state_bytes(self.b, self.l_cap, self.n_rec),
-                                   dtype=torch.uint8, device=dev),
-                 node_ptr=torch.zeros(self.b + 1, **i32), node_graph=torch.empty(n_cap, **i32),
-                 pos=torch.empty((n_cap, 3), **f32), x=torch.empty((n_cap, self.lig_feats.shape[1]), **f32),
-                 base_magg=torch.empty((n_cap, hid), **f32), base_xsum=torch.empty((n_cap, 3), **f32),
-                 base_deg=torch.empty(n_cap, **f32), inv_deg=torch.empty(n_cap, **f32),
-                 ones=torch.ones(n_cap, **f32), pgs={})
-        for tag, c in (('', cap), ('_l', cap_l)):
-            f['rowptr' + tag] = torch.empty(n_cap + 1, **i32)
-            f['row' + tag] = torch.empty(c, **i32)
-            f['col' + tag] = torch.empty(c, **i32)
-            f['etype' + tag] = torch.empty(c, dtype=torch.uint8, device=dev)
+        f = _csr_buffers(
+            dev, n_cap, cap_l, cap,
+            state=torch.empty(lib.pvs_screen_graph_ragged_state_bytes(self.b, self.l_cap, self.n_rec),
+                              dtype=torch.uint8, device=dev),
+            node_ptr=torch.zeros(self.b + 1, **i32), node_graph=torch.empty(n_cap, **i32),
+            pos=torch.empty((n_cap, 3), **f32), x=torch.empty((n_cap, self.lig_feats.shape[1]), **f32),
+            base_magg=torch.empty((n_cap, hid), **f32), base_xsum=torch.empty((n_cap, 3), **f32),
+            base_deg=torch.empty(n_cap, **f32), pgs={})
         f['tables'] = _lib.PvsRaggedNodeTables(
             f['x'].shape[1], hid, _lib.ptr(self.lig_feats), _lib.ptr(self._rec_feats), _lib.ptr(self.rec_magg),
             _lib.ptr(self.rec_xsum), _lib.ptr(self.rec_deg), _lib.ptr(f['x']), _lib.ptr(f['base_magg']),
@@ -501,79 +516,35 @@ class LibraryScreen:
         return cap, cap_l
 
     def _graphs(self, n):
-        """(PreparedGraph of the full CSR, PvsGraph of the ligand-touching CSR) over the first n nodes."""
-        from .graph import PreparedGraph
-        f = self._f
-        got = f['pgs'].get(n)
-        if got is None:
-            pg = PreparedGraph(n, f['cap'], 3, dict(rowptr=f['rowptr'], row=f['row'], col=f['col'],
-                                                    etype=f['etype'], inv_deg=f['inv_deg'], status=f['status']))
-            pg._status_checked = True
-            # (the nodes after n are padding, without edges: rowptr[n] == rowptr[N_cap] == the edge count)
-            pg.c.n_edges_dev = f['rowptr'][self.n_cap:].data_ptr()
-            gl = _lib.PvsGraph()
-            gl.n_nodes, gl.n_edges = n, f['cap_l']
-            gl.rowptr, gl.row, gl.col, gl.etype = (_lib.ptr(f[k + '_l']) for k in ('rowptr', 'row', 'col', 'etype'))
-            gl.inv_deg = _lib.ptr(f['ones'])
-            gl.n_edges_dev = f['rowptr_l'][self.n_cap:].data_ptr()
-            got = f['pgs'][n] = (pg, gl)
-        return got
+        """(PreparedGraph of the full CSR, PvsGraph of the ligand-touching CSR) over the first n nodes (the nodes
+        after n are padding, without edges: rowptr[n] == rowptr[N_cap] == the edge count)."""
+        pgs = self._fast['pgs']
+        if n not in pgs:
+            pgs[n] = _graph_pair(self._fast, n, self.n_cap)
+        return pgs[n]
 
     def _build(self, capacities=None):
         """The loaded batch's graph and node tables (pvs_screen_graph_build_ragged). capacities: (full, ligand-
         touching) edge room instead of the probe's."""
         capturing = torch.cuda.is_current_stream_capturing()
-        if self._f is None:
-            cap, cap_l = capacities or self._probe_capacities()
-            self._f = self._buffers(cap, cap_l)
+        if self._fast is None:
+            self._fast = self._buffers(*(capacities or self._probe_capacities()))
+        f = self._fast
         if not capturing:
             self.check()
-        self._launch_builder(self._f)
+        self._launch_builder(f)
         if not capturing:
-            self._poll_status()
-        return self._f
+            self._queue_status(f['status'], f['host'])
+        return f
 
-    def _poll_status(self):
-        f = self._f
-        f['host'].copy_(f['status'], non_blocking=True)
-        self._pending = torch.cuda.Event()
-        self._pending.record(torch.cuda.current_stream(f['status'].device))
-
-    def check(self):
-        """Raises if the edge buffers of an earlier batch were too small (checked one batch late so that the loop
-        never waits for the device; call once more after the last batch)."""
-        if self._pending is not None:
-            self._pending.synchronize()
-            self._pending = None
-            code = int(self._f['host'].item())
-            if code & 8:
-                raise ValueError('LibraryScreen: lig_ptr is not a table of 0..64-atom slots')
-            if code & 4:
-                raise RuntimeError('LibraryScreen: edge buffer overflow (more ligand contacts per atom than twice '
-                                   'the first batch); rebuild the screen with a denser first batch')
+    def _raise_for(self, code):
+        if code & 8:
+            raise ValueError('LibraryScreen: lig_ptr is not a table of 0..64-atom slots')
+        if code & 4:
+            raise RuntimeError('LibraryScreen: edge buffer overflow (more ligand contacts per atom than twice '
+                               'the first batch); rebuild the screen with a denser first batch')
 
     # ---- the step ----
-    def _first_layer(self, g, h, x, n):
-        lib = _lib.lib()
-        first, f, dev = self.egnn[0], self._f, h.device
-        desc = _lib.PvsLayerDesc(*first._desc())
-        params = [None if p is None else p.detach().float().contiguous() for p in first._params()]
-        pstruct = _lib.PvsLayerParams(*[_lib.ptr(p) for p in params])
-        h_out, x_out = torch.empty_like(h), torch.empty_like(x)
-        natt = torch.empty(n, dtype=torch.float32, device=dev) if first.node_attention else None
-        if self._l1_ws is None:
-            self._l1_ws = (
-                torch.empty(lib.pvs_egnn_layer_saved_floats(C.byref(desc), self.n_cap, f['cap_l']),
-                            dtype=torch.float32, device=dev),
-                torch.empty(lib.pvs_egnn_layer_workspace_bytes(C.byref(desc), self.n_cap, f['cap_l'], 2),
-                            dtype=torch.uint8, device=dev))
-        saved, ws = self._l1_ws
-        _lib.check(lib.pvs_egnn_layer_fwd_partial(
-            C.byref(desc), C.byref(g), C.byref(pstruct), _lib.ptr(h), _lib.ptr(x), _lib.ptr(f['base_magg']),
-            _lib.ptr(f['base_xsum']), _lib.ptr(f['base_deg']), _lib.ptr(h_out), _lib.ptr(x_out), _lib.ptr(natt),
-            _lib.ptr(saved), _lib.ptr(ws), ws.numel(), _stream(dev)), 'pvs_egnn_layer_fwd_partial')
-        return h_out, x_out
-
     def _plain_forward(self):
         """The models the first-layer reuse does not cover: the same mixed batch, graph from the general builder."""
         from .graph import Batch
@@ -592,35 +563,28 @@ class LibraryScreen:
                       rec_fname=['receptor'] * self.b, num_graphs=self.b, graph_node_counts=counts)
         return self.model(attach_radius_graph(batch, self.r_inter, self.r_intra))
 
+    def _head(self, h):
+        model, node_ptr = self.model, self._fast['node_ptr']
+        if self.b == 1:     # (one slot: the pooling still ends at node_ptr[1], not at the padded shape)
+            return model._run_head(model.feats_linear_layers, PF.mean_pool(h, node_ptr))
+        return model._pool_and_head(model.feats_linear_layers, h, node_ptr, self.b)
+
     @torch.no_grad()
     def __call__(self, slots=None):
         if slots is not None:
             self.load(slots)
-        model = self.model
         if not self.reuse:
             return self._plain_forward()
-        if self._fingerprint != self._weights_fingerprint():
-            if torch.cuda.is_current_stream_capturing() or self._graph is not None:
-                raise RuntimeError('LibraryScreen: the model\'s weights changed after capture(); build a new screen')
-            self._cache_receptor_sums()
-            if self._f is not None:         # (the node-table struct points at the receptor sums)
-                t = self._f['tables']
-                t.rec_magg, t.rec_xsum, t.rec_deg = (_lib.ptr(v) for v in (self.rec_magg, self.rec_xsum, self.rec_deg))
+        self._refresh_if_stale()
         f = self._build()
         # graphnorm's statistics run over the batch's nodes: no padding rows there (the host knows the count)
         n = self.n_atoms + self.b * self.n_rec if self.graphnorm else self.n_cap
         pg_full, g_lig = self._graphs(n)
         x = f['pos'][:n]
         h = self.embed.embed(f['x'][:n], x).contiguous()
-        h, x = self._first_layer(g_lig, h, x, n)
-        for layer in self.egnn[1:]:
-            h, x, _ = layer.forward_prepared(pg_full, h, x, None, need_m=False,
-                                             need_coords=layer is not self.egnn[-1])
-        if model.feats_linear_layers is None:
-            return h
-        if self.b == 1:     # (one slot: the pooling still ends at node_ptr[1], not at the padded shape)
-            return model._run_head(model.feats_linear_layers, PF.mean_pool(h, f['node_ptr']))
-        return model._pool_and_head(model.feats_linear_layers, h, f['node_ptr'], self.b)
+        h, x = self._partial_first_layer(g_lig, h, x, f['base_magg'], f['base_xsum'], f['base_deg'],
+                                         self.n_cap, f['cap_l'])
+        return self._tail(pg_full, h, x)
 
     def capture(self, example_slots=None):
         """Captures one whole step (builder + layer stack + head) in a hipGraph; `replay(slots)` then serves every
@@ -633,30 +597,10 @@ class LibraryScreen:
                                'count: it cannot be captured at the padded shape; call the screen eagerly')
         if example_slots is not None:
             self.load(example_slots)
-        dev = self.lig_pos.device
-        stream = torch.cuda.Stream(dev)
-        stream.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(stream):
-            for _ in range(2):
-                self()                         # warm-up: probe, buffers, lazy allocations
-            self.check()
-            torch.cuda.synchronize(dev)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph, stream=stream):
-                self._static_out = self()
-        self._graph = graph
-        torch.cuda.current_stream(dev).wait_stream(stream)
-        return self
+        return self._capture(lambda: self(), self.lig_pos.device)
 
     def replay(self, slots=None):
-        if self.stale():           # host-only comparison of version counters
-            raise RuntimeError('LibraryScreen: the model\'s weights changed after capture(); build a new screen')
-        self.check()
-        if slots is not None:
-            self.load(slots)
-        self._graph.replay()
-        self._poll_status()
-        return self._static_out
+        return self._replay(lambda: None if slots is None else self.load(slots))
 
 
 class ScreeningSweep:
@@ -682,6 +626,7 @@ class ScreeningSweep:
         self.edge_radius, self.intra_radius, self.b = edge_radius, intra_radius, int(batch_size)
         self.capture, self.receptor_name = capture, receptor_name
         self.buckets = {}          # n_lig -> ReceptorScreen (captured when possible)
+        self.library = None        # the LibraryScreen of run_library
         self.batches_run = 0
 
     def _bucket(self, n_lig, lig_feats, example_poses):
@@ -693,10 +638,8 @@ class ScreeningSweep:
         if screen is None:
             feats = torch.cat([lig_feats.to(self.rec_feats.device), self.rec_feats], 0)
             screen = ReceptorScreen(self.model, self.rec_pos, feats, n_lig, self.b, self.edge_radius, self.intra_radius)
-            screen._captured = False
             if self.capture and screen.fast_graph:
                 screen.capture(example_poses)
-                screen._captured = True
             self.buckets[n_lig] = screen
         return screen
 
@@ -730,37 +673,41 @@ class ScreeningSweep:
         screen.check()
         return torch.cat(scores, 0)
 
+    @contextlib.contextmanager
+    def _sweeping(self, predictions_file, sigmoid):
+        """What a sweep runs inside: yields (sigmoid, writer) - sigmoid defaults to what `val` does for the model's
+        task, writer is the PredictionsWriter of predictions_file (or None), closed at the end - with the
+        long-lived heap frozen (no full-heap collection pause inside the sweep: see its docstring)."""
+        from .point_neural_network_base import long_lived_heap_frozen
+        from .predictions import PredictionsWriter
+        if sigmoid is None:
+            sigmoid = getattr(self.model, 'model_task', 'classification') == 'classification'
+        writer = PredictionsWriter(predictions_file, 'regression', flush_every=10) if predictions_file else None
+        try:
+            with long_lived_heap_frozen():
+                yield sigmoid, writer
+        finally:
+            if writer is not None:
+                writer.close()
+
     @torch.no_grad()
     def run(self, ligands, predictions_file=None, sigmoid=None):
         """ligands: iterable of (name, lig_feats [n_lig,F], poses [P,n_lig,3] on the device).
         Returns {name: scores [P, ...] on the device} (raw model outputs; sigmoid-ed like `val` does for
         classification models when sigmoid is None/True). predictions_file: optional path."""
-        from .predictions import PredictionsWriter
-        if sigmoid is None:
-            sigmoid = getattr(self.model, 'model_task', 'classification') == 'classification'
-        writer = PredictionsWriter(predictions_file, 'regression', flush_every=10) if predictions_file else None
         out = {}
-        from .point_neural_network_base import long_lived_heap_frozen
-        frozen = long_lived_heap_frozen()       # (no full-heap collection pause inside the sweep: see its docstring)
-        frozen.__enter__()
-        try:
+        with self._sweeping(predictions_file, sigmoid) as (sigmoid, writer):
             for name, lig_feats, poses in ligands:
                 if int(poses.shape[0]) == 0:
                     continue
                 out[name] = self._run_ligand(name, lig_feats, poses, sigmoid, writer)
-        finally:
-            frozen.__exit__(None, None, None)
-            if writer is not None:
-                writer.close()
         return out
 
     def _library_screen(self, max_atoms):
-        screen = getattr(self, 'library', None)
+        screen = self.library
         if screen is None or screen.stale() or screen.max_lig_atoms < max_atoms:
-            screen = LibraryScreen(self.model, self.rec_pos, self.rec_feats, self.b, max_atoms, self.edge_radius,
-                                   self.intra_radius)
-            screen._captured = False
-            self.library = screen
+            screen = self.library = LibraryScreen(self.model, self.rec_pos, self.rec_feats, self.b, max_atoms,
+                                                  self.edge_radius, self.intra_radius)
         return screen
 
     @torch.no_grad()
@@ -770,10 +717,6 @@ class ScreeningSweep:
         library order, then pose order; ceil(total poses / batch_size) batches, one captured step for all of them),
         larger ligands through their size bucket as in `run`. Same arguments, return value and predictions lines
         as `run`; the lines are in library order, then pose order."""
-        from .point_neural_network_base import long_lived_heap_frozen
-        from .predictions import PredictionsWriter
-        if sigmoid is None:
-            sigmoid = getattr(self.model, 'model_task', 'classification') == 'classification'
         ligands = [item for item in ligands if int(item[2].shape[0]) > 0]
         dev = self.rec_pos.device
         small = [k for k, (_, _, poses) in enumerate(ligands) if int(poses.shape[1]) <= 64]
@@ -781,11 +724,8 @@ class ScreeningSweep:
         sizes = [int(ligands[k][2].shape[1]) for k in small]
         counts = [int(ligands[k][2].shape[0]) for k in small]
         plan = plan_library(counts, sizes, self.b, 64)
-        writer = PredictionsWriter(predictions_file, 'regression', flush_every=10) if predictions_file else None
         out, kept = {}, []
-        frozen = long_lived_heap_frozen()
-        frozen.__enter__()
-        try:
+        with self._sweeping(predictions_file, sigmoid) as (sigmoid, writer):
             if plan:
                 # the whole library packed once, in plan order: a batch is a contiguous range of it
                 all_pos = torch.cat([ligands[k][2].to(dev).float().reshape(-1, 3) for k in small], 0)
@@ -812,7 +752,6 @@ class ScreeningSweep:
                 at += total
                 if self.capture and screen.reuse and not screen.graphnorm and not screen._captured:
                     screen.capture()
-                    screen._captured = True
                 y = (screen.replay().clone() if screen._captured else screen()).reshape(self.b, -1)
                 if sigmoid:
                     y = torch.sigmoid(y)
@@ -836,8 +775,4 @@ class ScreeningSweep:
                 for k, c in zip(small, counts):
                     out[ligands[k][0]] = scores[at:at + c]
                     at += c
-        finally:
-            frozen.__exit__(None, None, None)
-            if writer is not None:
-                writer.close()
         return {name: out[name] for name, _, _ in ligands}

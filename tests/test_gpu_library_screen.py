@@ -265,3 +265,61 @@ def test_run_library_end_to_end(tmp_path):
             assert abs(float(got[name][k, 0]) - float(want)) < 1e-5 * max(1.0, abs(float(want))), (name, k)
             assert lines[at] == f'{float(got[name][k, 0]):.3f} | receptor {name}_pose{k}'
             at += 1
+
+
+def _stale_case(kind, model, rec, rec_feats, lig, lig_feats):
+    """(screen factory, batch) at the smallest shape with three contact-mask words and several ligand rows."""
+    from pointvs_amd.screening import LibraryScreen, ReceptorScreen
+    from pointvs_amd.synthetic import random_poses
+    if kind == 'receptor':
+        feats = torch.cat([lig_feats[:12], rec_feats], 0)
+        return (lambda: ReceptorScreen(model, rec.cuda(), feats, 12, 3, 7.0),
+                random_poses(lig[:12], 3, seed=5, max_shift=3.0).cuda())
+    return (lambda: LibraryScreen(model, rec.cuda(), rec_feats, 3, 20, 7.0),
+            _slots(lig, lig_feats, (7, 20, 3), seed=90, special=False))
+
+
+def _change_first_layer(model):
+    with torch.no_grad():
+        model.layers[1].edge_mlp[0].weight.mul_(1.5)         # (in place: bumps the version counter)
+
+
+@pytest.mark.parametrize('kind', ['receptor', 'library'])
+def test_weights_changed_under_an_eager_screen_recomputes_the_sums(kind):
+    """The first layer's weights change between two eager calls: the screen is stale, the next call recomputes the
+    receptor-receptor sums (LibraryScreen: and re-points the builder's node-table struct at them) and equals a
+    screen built on the changed model bit for bit (same kernels, inputs and order; no atomics)."""
+    lig, rec, lig_feats, rec_feats = _set(6006)
+    model = _model(3)
+    make, batch = _stale_case(kind, model, rec, rec_feats, lig, lig_feats)
+    screen = make()
+    y0 = screen(batch).clone()
+    assert not screen.stale()
+    _change_first_layer(model)
+    assert screen.stale()
+    y1 = screen(batch).clone()
+    assert not screen.stale()
+    screen.check()
+    fresh = make()
+    y2 = fresh(batch).clone()
+    fresh.check()
+    assert torch.equal(y1, y2)
+    assert not torch.equal(y0, y1)
+
+
+@needs_caching_allocator
+@pytest.mark.parametrize('kind', ['receptor', 'library'])
+def test_weights_changed_under_a_captured_screen_is_refused(kind):
+    """A captured step has the sums baked in: replay and the eager call both refuse once the weights changed."""
+    lig, rec, lig_feats, rec_feats = _set(6006)
+    model = _model(3)
+    make, batch = _stale_case(kind, model, rec, rec_feats, lig, lig_feats)
+    screen = make().capture(batch)
+    screen.replay(batch)
+    screen.check()
+    _change_first_layer(model)
+    assert screen.stale()
+    with pytest.raises(RuntimeError, match='weights changed'):
+        screen.replay(batch)
+    with pytest.raises(RuntimeError, match='weights changed'):
+        screen(batch)

@@ -4,7 +4,10 @@ Runs one training step through the per-layer calls and one through the stack cal
 small two-graph batch. Under a kernel trace, once per library and once more with PVS_EGNN_SPLIT_SMALL=1:
     PVS_EGNN_LIB=<library> rocprofv3 --kernel-trace --output-format csv -d DIR -- python tools/launch_sequence.py
     python tools/launch_sequence.py --parse DIR OUT.txt      # one line per launch: name, grid, workgroup, LDS
-Two libraries enqueue the same work when their OUT.txt files are equal (profiles/linear_job_refactor.txt)."""
+Two libraries enqueue the same work when their OUT.txt files are equal (profiles/linear_job_refactor.txt).
+`--screening` traces instead one eager step of each screen (ReceptorScreen on the pose-batch builder and on the filter
+path, LibraryScreen) at a small shape (130-atom receptor, batch of 3): the record that a change of the screens'
+host code left every launch alone (profiles/screening_refactor.txt)."""
 import csv
 import glob
 import os
@@ -49,8 +52,33 @@ def run():
                 torch.cuda.synchronize()
 
 
+def run_screening():
+    import tempfile
+    import torch
+    from pointvs_amd.egnn_satorras import SartorrasEGNN
+    from pointvs_amd.screening import LibraryScreen, ReceptorScreen
+    from pointvs_amd.synthetic import CONFIGS, random_poses, screening_set
+    lig, rec, feats = screening_set(seed=6006, n_nodes=470, n_lig=70)
+    near = torch.argsort((rec - lig.mean(0)).norm(dim=1))[:130].sort().values      # 130 atoms: three contact-mask words
+    rec, lig_feats, rec_feats = rec[near].contiguous().cuda(), feats[:70], feats[70:][near].contiguous()
+    torch.manual_seed(3)
+    kw = dict(CONFIGS['cfg2']['model'], num_layers=2)
+    model = SartorrasEGNN(tempfile.mkdtemp(), 2e-3, 1e-4, silent=True, **kw).eval()
+    for n_lig in (12, 70):         # 70 atoms: no pose-batch builder, the ligand edges are filtered from the full graph
+        screen = ReceptorScreen(model, rec, torch.cat([lig_feats[:n_lig], rec_feats], 0), n_lig, 3, 7.0)
+        screen(random_poses(lig[:n_lig], 3, seed=5, max_shift=3.0).cuda())
+        screen.check()
+    screen = LibraryScreen(model, rec, rec_feats, 3, 20, 7.0)
+    screen([(lig_feats[:n].roll(k, 0).contiguous(), random_poses(lig[:n], 1, seed=90 + k, max_shift=3.0)[0])
+            for k, n in enumerate((7, 20, 3))])
+    screen.check()
+    torch.cuda.synchronize()
+
+
 if __name__ == '__main__':
     if len(sys.argv) == 4 and sys.argv[1] == '--parse':
         parse(sys.argv[2], sys.argv[3])
+    elif sys.argv[1:] == ['--screening']:
+        run_screening()
     else:
         run()
