@@ -210,11 +210,7 @@ __global__ void k_complex_edges(int n_nodes, int n_edges, int n_graphs, const in
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= n_edges) return;
     const int i = row[p];
-    int lo = 0, hi = n_graphs;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (graph_ptr[mid] <= i) lo = mid; else hi = mid;
-    }
+    const int lo = pvs_last_le(graph_ptr, n_graphs, i);      // (a row outside every graph fails the range check below)
     const int n0 = graph_ptr[lo], n1 = graph_ptr[lo + 1];
     bool ok = i >= 0 && i < n_nodes && n0 >= 0 && n0 <= i && i < n1 && n1 <= n_nodes;
     int dst = -1;

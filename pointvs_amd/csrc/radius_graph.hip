@@ -105,10 +105,7 @@ k_radius_masks(const float* __restrict__ pos, const uint8_t* __restrict__ bp,
         const int bpj = bp[jj];
         for (int t = 0; t < n_rows; ++t) {
             const int li = wv * kRowsPerWave + t;
-            const double d0 = rx[li] - xj, d1 = ry[li] - yj, d2 = rz[li] - zj;
-            double s = __dmul_rn(d0, d0);
-            s = __dadd_rn(s, __dmul_rn(d1, d1));
-            s = __dadd_rn(s, __dmul_rn(d2, d2));
+            const double s = pvs_sqdist(rx[li], ry[li], rz[li], xj, yj, zj);
             bool e_inter = false, e_intra = false;
             // pair_filter 1: only pairs that touch a ligand atom (bp == 0)
             const bool wanted = pair_filter == 0 || rbp[li] == 0 || bpj == 0;
@@ -142,13 +139,7 @@ k_radius_fill(const uint8_t* __restrict__ bp, const int32_t* __restrict__ gptr, 
     const int lane = threadIdx.x & 63;
     const int i = (blockIdx.x * kThreads + threadIdx.x) >> 6;
     if (i >= n_nodes) return;
-    // graph of the row: binary search over graph_ptr
-    int lo = 0, hi = n_graphs;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (gptr[mid] <= i) lo = mid; else hi = mid;
-    }
-    const int g = lo, n0 = gptr[g], n1 = gptr[g + 1];
+    const int g = pvs_last_le(gptr, n_graphs, i), n0 = gptr[g], n1 = gptr[g + 1];      // graph of the row
     const int n_chunks = (n1 - n0 + 63) / 64;
     const unsigned long long* mrow = masks + 2 * mask_off[g] + (size_t)(i - n0) * 2 * n_chunks;
     const int n_inter_total = inter_ptr[n_nodes];
@@ -162,30 +153,14 @@ k_radius_fill(const uint8_t* __restrict__ bp, const int32_t* __restrict__ gptr, 
     for (int kind = 0; kind < 2; ++kind) {
         const int base = kind == 0 ? seg0 : seg0 + n_int;
         const int pbase = kind == 0 ? inter_ptr[i] : n_inter_total + intra_ptr[i];
-        int done = 0;      // entries of this kind already written (wave-uniform)
-        for (int c0 = 0; c0 < n_chunks; c0 += 64) {
-            const int c = c0 + lane;
-            unsigned long long m = c < n_chunks ? mrow[(size_t)kind * n_chunks + c] : 0ull;
-            const int cnt = __popcll(m);
-            int scan = cnt;
-            for (int o = 1; o < 64; o <<= 1) {
-                const int t = __shfl_up(scan, o, 64);
-                if (lane >= o) scan += t;
-            }
-            int k = done + scan - cnt;
-            while (m) {
-                const int bit = __builtin_ctzll(m);
-                m &= m - 1ull;
-                const int j = n0 + 64 * c + bit;
-                const int p = base + k;
-                row[p] = i;
-                col[p] = j;
-                etype[p] = kind == 0 ? 1 : ((bpi == 1 && bp[j] == 1) ? 2 : 0);
-                perm[p] = pbase + k;
-                ++k;
-            }
-            done += __shfl(scan, 63, 64);
-        }
+        pvs_expand_mask_row(mrow + (size_t)kind * n_chunks, n_chunks, lane, [&](int k, int b) {
+            const int j = n0 + b;
+            const int p = base + k;
+            row[p] = i;
+            col[p] = j;
+            etype[p] = kind == 0 ? 1 : ((bpi == 1 && bp[j] == 1) ? 2 : 0);
+            perm[p] = pbase + k;
+        });
     }
 }
 

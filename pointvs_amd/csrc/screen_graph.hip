@@ -14,296 +14,25 @@
 #include "common.h"
 #include "profile.h"
 #include "radius_common.h"
+#include "screen_slots.h"
 #include <hipcub/hipcub.hpp>
 
 namespace {
 
 typedef unsigned long long u64;
 
-// wave per (pose, ligand atom): contact masks against the receptor (64 atoms per word) and the ligand
+// wave per packed ligand atom q: contact masks against the receptor (64 atoms per word) and the atom's own ligand
+template <class Slots>
 __global__ void __launch_bounds__(256)
-k_contacts(const float* __restrict__ lig_pos, const float* __restrict__ rec_pos, int B, int n_lig, int n_rec,
-           Radius r_inter, Radius r_intra, Radius r_zero, u64* __restrict__ m_inter, u64* __restrict__ m_intra,
+k_contacts(const float* __restrict__ lig_pos, const float* __restrict__ rec_pos, Slots L, Radius r_inter,
+           Radius r_intra, Radius r_zero, u64* __restrict__ m_inter, u64* __restrict__ m_intra,
            u64* __restrict__ m_ll) {
     const int lane = threadIdx.x & 63;
-    const int w = (blockIdx.x * 256 + threadIdx.x) >> 6;
-    if (w >= B * n_lig) return;
-    const int p = w / n_lig, a = w - p * n_lig;
-    const int n_chunks = (n_rec + 63) / 64;
-    const float* la = lig_pos + ((size_t)p * n_lig + a) * 3;
-    const double xa = la[0], ya = la[1], za = la[2];
-    for (int c = 0; c < n_chunks; ++c) {
-        const int i = 64 * c + lane;
-        bool ei = false, ea = false;
-        if (i < n_rec) {
-            const double s = pvs_sqdist(xa, ya, za, (double)rec_pos[3 * i], (double)rec_pos[3 * i + 1],
-                                        (double)rec_pos[3 * i + 2]);
-            if (above(s, r_zero)) {
-                ei = below(s, r_inter);
-                ea = below(s, r_intra);
-            }
-        }
-        const u64 bi = __ballot(ei), ba = __ballot(ea);
-        if (lane == 0) {
-            m_inter[(size_t)w * n_chunks + c] = bi;
-            m_intra[(size_t)w * n_chunks + c] = ba;
-        }
-    }
-    bool ell = false;
-    if (lane < n_lig) {
-        const float* lb = lig_pos + ((size_t)p * n_lig + lane) * 3;
-        const double s = pvs_sqdist(xa, ya, za, (double)lb[0], (double)lb[1], (double)lb[2]);
-        ell = above(s, r_zero) && below(s, r_intra);
-    }
-    const u64 bl = __ballot(ell);
-    if (lane == 0) m_ll[w] = bl;
-}
-
-__device__ __forceinline__ int row_popc(const u64* __restrict__ m, int n_chunks) {
-    int c = 0;
-    for (int k = 0; k < n_chunks; ++k) c += __popcll(m[k]);
-    return c;
-}
-
-// thread per node: degree in the full graph and in the ligand-touching subgraph
-__global__ void k_degrees(const u64* __restrict__ m_inter, const u64* __restrict__ m_intra,
-                          const u64* __restrict__ m_ll, const int32_t* __restrict__ rr_rowptr, int B, int n_lig,
-                          int n_rec, int32_t* __restrict__ deg, int32_t* __restrict__ deg_l) {
-    const int g = blockIdx.x * blockDim.x + threadIdx.x;
-    const int n = n_lig + n_rec, N = B * n;
-    if (g > N) return;
-    if (g == N) { deg[g] = 0; deg_l[g] = 0; return; }
-    const int p = g / n, local = g - p * n;
-    const int n_chunks = (n_rec + 63) / 64;
-    if (local < n_lig) {
-        const size_t w = (size_t)p * n_lig + local;
-        const int d = row_popc(m_inter + w * n_chunks, n_chunks) + __popcll(m_ll[w]) +
-                      row_popc(m_intra + w * n_chunks, n_chunks);
-        deg[g] = d;
-        deg_l[g] = d;
-    } else {
-        const int i = local - n_lig, c = i >> 6;
-        const u64 bit = 1ull << (i & 63);
-        int nl = 0;
-        for (int a = 0; a < n_lig; ++a) {
-            const size_t w = (size_t)p * n_lig + a;
-            nl += (m_inter[w * n_chunks + c] & bit) ? 1 : 0;
-            nl += (m_intra[w * n_chunks + c] & bit) ? 1 : 0;
-        }
-        deg_l[g] = nl;
-        deg[g] = nl + (rr_rowptr[i + 1] - rr_rowptr[i]);
-    }
-}
-
-struct OutCsr {
-    const int32_t* rowptr;
-    int32_t *row, *col;
-    uint8_t* etype;
-    int capacity;
-};
-
-// wave per row: writes the row's segment of the full CSR and of the ligand-touching CSR
-__global__ void __launch_bounds__(256)
-k_fill(const u64* __restrict__ m_inter, const u64* __restrict__ m_intra, const u64* __restrict__ m_ll,
-       const int32_t* __restrict__ rr_rowptr, const int32_t* __restrict__ rr_col, int B, int n_lig, int n_rec,
-       OutCsr full, OutCsr lig, float* __restrict__ inv_deg, int32_t* __restrict__ status) {
-    const int lane = threadIdx.x & 63;
-    const int g = (blockIdx.x * 256 + threadIdx.x) >> 6;
-    const int n = n_lig + n_rec, N = B * n;
-    if (g >= N) return;
-    if (full.rowptr[N] > full.capacity || lig.rowptr[N] > lig.capacity) {
-        if (g == 0 && lane == 0) atomicOr(status, 4);
-        return;
-    }
-    const int p = g / n, local = g - p * n, node0 = p * n;
-    const int n_chunks = (n_rec + 63) / 64;
-    const u64 lower = (1ull << lane) - 1ull;
-    int pf = full.rowptr[g], pl = lig.rowptr[g];
-    if (lane == 0) {
-        const int d = full.rowptr[g + 1] - pf;
-        inv_deg[g] = 1.0f / (float)(d > 1 ? d : 1);
-    }
-    auto emit = [&](int off, int column, int cls, bool also_lig) {
-        full.row[pf + off] = g; full.col[pf + off] = column; full.etype[pf + off] = (uint8_t)cls;
-        if (also_lig) { lig.row[pl + off] = g; lig.col[pl + off] = column; lig.etype[pl + off] = (uint8_t)cls; }
-    };
-    // one mask row (n_chunks words) expanded by the wave: lane c takes word c, offsets by a wave scan
-    auto expand_words = [&](const u64* __restrict__ m, int col0, int cls) {
-        int done = 0;
-        for (int c0 = 0; c0 < n_chunks; c0 += 64) {
-            const int c = c0 + lane;
-            u64 word = c < n_chunks ? m[c] : 0ull;
-            const int cnt = __popcll(word);
-            int scan = cnt;
-            for (int o = 1; o < 64; o <<= 1) {
-                const int t = __shfl_up(scan, o, 64);
-                if (lane >= o) scan += t;
-            }
-            int k = done + scan - cnt;
-            while (word) {
-                const int bit = __builtin_ctzll(word);
-                word &= word - 1ull;
-                emit(k, col0 + 64 * c + bit, cls, true);
-                ++k;
-            }
-            done += __shfl(scan, 63, 64);
-        }
-        pf += done;
-        pl += done;
-    };
-    if (local < n_lig) {
-        const size_t w = (size_t)p * n_lig + local;
-        expand_words(m_inter + w * n_chunks, node0 + n_lig, 1);             // inter block: receptor atoms
-        {                                                                     // intra block: ligand atoms ...
-            const u64 mll = m_ll[w];
-            const bool on = (mll >> lane) & 1ull;
-            if (on) emit(__popcll(mll & lower), node0 + lane, 0, true);
-            const int c = __popcll(mll);
-            pf += c; pl += c;
-        }
-        expand_words(m_intra + w * n_chunks, node0 + n_lig, 0);              // ... then receptor atoms
-    } else {
-        const int i = local - n_lig, c = i >> 6;
-        const u64 bit = 1ull << (i & 63);
-        for (int kind = 0; kind < 2; ++kind) {                                // inter block, then intra: ligand atoms
-            const u64* m = kind == 0 ? m_inter : m_intra;
-            const bool on = lane < n_lig && (m[((size_t)p * n_lig + lane) * n_chunks + c] & bit);
-            const u64 b = __ballot(on);
-            if (on) emit(__popcll(b & lower), node0 + lane, kind == 0 ? 1 : 0, true);
-            const int cnt = __popcll(b);
-            pf += cnt; pl += cnt;
-        }
-        const int r0 = rr_rowptr[i], r1 = rr_rowptr[i + 1];                   // intra block: receptor atoms
-        for (int k = lane; k < r1 - r0; k += 64) emit(k, node0 + n_lig + rr_col[r0 + k], 2, false);
-    }
-}
-
-struct ScreenState {
-    u64 *m_inter, *m_intra, *m_ll;
-    int32_t *deg, *deg_l;
-    void* scan_tmp;
-    size_t scan_bytes;
-};
-
-size_t carve_screen(PvsArena& a, int B, int n_lig, int n_rec, ScreenState* out) {
-    ScreenState t;
-    const size_t n_chunks = (size_t)(n_rec + 63) / 64, rows = (size_t)B * n_lig;
-    const int N = B * (n_lig + n_rec);
-    t.m_inter = a.take<u64>(rows * n_chunks);
-    t.m_intra = a.take<u64>(rows * n_chunks);
-    t.m_ll = a.take<u64>(rows);
-    t.deg = a.take<int32_t>((size_t)N + 1);
-    t.deg_l = a.take<int32_t>((size_t)N + 1);
-    size_t sb = 0;
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, sb, (const int32_t*)nullptr, (int32_t*)nullptr, N + 1);
-    t.scan_bytes = sb;
-    t.scan_tmp = a.take<char>(sb);
-    if (out) *out = t;
-    return a.off;
-}
-
-}  // namespace
-
-extern "C" size_t pvs_screen_graph_state_bytes(int32_t B, int32_t n_lig, int32_t n_rec) {
-    PvsArena a(nullptr, 0);
-    return carve_screen(a, B, n_lig, n_rec, nullptr) + 256;
-}
-
-extern "C" int pvs_screen_graph_build(const float* lig_pos, const float* rec_pos, const int32_t* rr_rowptr,
-                                      const int32_t* rr_col, int32_t B, int32_t n_lig, int32_t n_rec,
-                                      double inter_radius, double intra_radius, int32_t capacity,
-                                      int32_t capacity_lig, int32_t* rowptr, int32_t* row, int32_t* col,
-                                      uint8_t* etype, float* inv_deg, int32_t* rowptr_lig, int32_t* row_lig,
-                                      int32_t* col_lig, uint8_t* etype_lig, int32_t* status, void* state,
-                                      size_t state_bytes, pvs_stream_t stream_) {
-    hipStream_t s = (hipStream_t)stream_;
-    PVS_REQUIRE(lig_pos && rec_pos && rr_rowptr && rr_col && rowptr && row && col && etype && inv_deg &&
-                rowptr_lig && row_lig && col_lig && etype_lig && status && state, "pvs_screen_graph_build: NULL");
-    PVS_REQUIRE(B > 0 && n_lig > 0 && n_lig <= 64 && n_rec > 0, "pvs_screen_graph_build: needs 1..64 ligand atoms "
-                "(got %d) and a receptor", n_lig);
-    PvsArena arena(state, state_bytes);
-    ScreenState w;
-    carve_screen(arena, B, n_lig, n_rec, &w);
-    PVS_REQUIRE(arena.ok(), "pvs_screen_graph_build: state too small (%zu < %zu)", state_bytes, arena.off);
-    PvsProfScope prof(s, PVS_PROF_PREPARE);
-    const int N = B * (n_lig + n_rec);
-    PVS_CHECK_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), s));
-    k_contacts<<<(B * n_lig + 3) / 4, 256, 0, s>>>(lig_pos, rec_pos, B, n_lig, n_rec, make_radius(inter_radius),
-                                                   make_radius(intra_radius), make_radius(1e-7), w.m_inter,
-                                                   w.m_intra, w.m_ll);
-    PVS_CHECK_LAUNCH();
-    k_degrees<<<(N + 1 + 255) / 256, 256, 0, s>>>(w.m_inter, w.m_intra, w.m_ll, rr_rowptr, B, n_lig, n_rec, w.deg,
-                                                  w.deg_l);
-    PVS_CHECK_LAUNCH();
-    size_t sb = w.scan_bytes;
-    PVS_CHECK_HIP(hipcub::DeviceScan::ExclusiveSum(w.scan_tmp, sb, w.deg, rowptr, N + 1, s));
-    sb = w.scan_bytes;
-    PVS_CHECK_HIP(hipcub::DeviceScan::ExclusiveSum(w.scan_tmp, sb, w.deg_l, rowptr_lig, N + 1, s));
-    OutCsr full{rowptr, row, col, etype, capacity}, lig{rowptr_lig, row_lig, col_lig, etype_lig, capacity_lig};
-    k_fill<<<(N + 3) / 4, 256, 0, s>>>(w.m_inter, w.m_intra, w.m_ll, rr_rowptr, rr_col, B, n_lig, n_rec, full, lig,
-                                       inv_deg, status);
-    PVS_CHECK_LAUNCH();
-    return 0;
-}
-
-// ---- library batches: every slot of the batch holds one pose of ANY ligand of 0..64 atoms ----
-// pvs_screen_graph_build_ragged: the same graphs for a batch whose B slots hold poses of different
-// ligands (a docking library: thousands of ligands of 8-60 atoms with ~10 poses each). The ligand atoms
-// come packed, lig_pos [L_cap,3] with the device table lig_ptr [B+1]; slot p has lig_ptr[p+1]-lig_ptr[p]
-// atoms (0 = receptor only). Compact node layout: slot p owns nodes node_ptr[p] .. node_ptr[p+1],
-// node_ptr[p] = lig_ptr[p] + p * n_rec, ligand atoms first, then the receptor; the nodes from node_ptr[B]
-// up to N_cap = L_cap + B * n_rec are padding (degree 0, inv_deg 1, graph id -1). No host argument depends
-// on the batch's composition, so one captured step serves every batch of a library. The masks are indexed by
-// the packed atom (same words as above), node -> slot by bisection of node_ptr, atom -> slot by a table that
-// the first kernel fills; the node tables of the layer stack (graph id, pos, features, first-layer receptor
-// sums) are expanded by a sibling kernel of the same call.
-namespace {
-
-constexpr int kBadTable = 8;     // *status bit 3: lig_ptr is not a table of 0..64-atom slots inside L_cap
-
-// thread per slot: validates the slot, node_ptr, atom -> slot table
-__global__ void k_slots(const int32_t* __restrict__ lig_ptr, int B, int L_cap, int n_rec,
-                        int32_t* __restrict__ node_ptr, int32_t* __restrict__ slot_of,
-                        int32_t* __restrict__ status) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p > B) return;
-    if (p == B) {
-        const int t = lig_ptr[B];
-        node_ptr[B] = (t >= 0 && t <= L_cap) ? t + B * n_rec : B * n_rec;
-        if (lig_ptr[0] != 0) atomicOr(status, kBadTable);
-        return;
-    }
-    const int a0 = lig_ptr[p], a1 = lig_ptr[p + 1];
-    if (a0 < 0 || a1 < a0 || a1 - a0 > 64 || a1 > L_cap) {
-        atomicOr(status, kBadTable);
-        node_ptr[p] = p * n_rec;
-        return;
-    }
-    node_ptr[p] = a0 + p * n_rec;
-    for (int q = a0; q < a1; ++q) slot_of[q] = p;
-}
-
-// the slot that owns node g (g < node_ptr[B]): the last p with node_ptr[p] <= g
-__device__ __forceinline__ int slot_of_node(const int32_t* __restrict__ node_ptr, int B, int g) {
-    int lo = 0, hi = B - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (node_ptr[mid] <= g) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
-// wave per packed ligand atom: contact masks against the receptor and the atom's own ligand
-__global__ void __launch_bounds__(256)
-k_contacts_ragged(const float* __restrict__ lig_pos, const int32_t* __restrict__ lig_ptr,
-                  const int32_t* __restrict__ slot_of, const float* __restrict__ rec_pos, int B, int L_cap, int n_rec,
-                  Radius r_inter, Radius r_intra, Radius r_zero, const int32_t* __restrict__ status,
-                  u64* __restrict__ m_inter, u64* __restrict__ m_intra, u64* __restrict__ m_ll) {
-    const int lane = threadIdx.x & 63;
     const int q = (blockIdx.x * 256 + threadIdx.x) >> 6;
-    if (q >= L_cap || (*status & kBadTable) || q >= lig_ptr[B]) return;
-    const int p = slot_of[q], a0 = lig_ptr[p], n_lig = lig_ptr[p + 1] - a0;
-    const int n_chunks = (n_rec + 63) / 64;
+    if (q >= L.atoms()) return;
+    const PvsSlotAtom slot = L.atom(q);
+    if (!slot.valid) return;
+    const int n_rec = L.n_rec, n_chunks = (n_rec + 63) / 64;
     const float* la = lig_pos + (size_t)q * 3;
     const double xa = la[0], ya = la[1], za = la[2];
     for (int c = 0; c < n_chunks; ++c) {
@@ -324,8 +53,8 @@ k_contacts_ragged(const float* __restrict__ lig_pos, const int32_t* __restrict__
         }
     }
     bool ell = false;
-    if (lane < n_lig) {
-        const float* lb = lig_pos + (size_t)(a0 + lane) * 3;
+    if (lane < slot.n_lig) {
+        const float* lb = lig_pos + (size_t)(slot.a0 + lane) * 3;
         const double s = pvs_sqdist(xa, ya, za, (double)lb[0], (double)lb[1], (double)lb[2]);
         ell = above(s, r_zero) && below(s, r_intra);
     }
@@ -333,30 +62,35 @@ k_contacts_ragged(const float* __restrict__ lig_pos, const int32_t* __restrict__
     if (lane == 0) m_ll[q] = bl;
 }
 
-// thread per node (and one past the end): degree in the full graph and in the ligand-touching subgraph
-__global__ void k_degrees_ragged(const u64* __restrict__ m_inter, const u64* __restrict__ m_intra,
-                                 const u64* __restrict__ m_ll, const int32_t* __restrict__ rr_rowptr,
-                                 const int32_t* __restrict__ lig_ptr, const int32_t* __restrict__ node_ptr, int B,
-                                 int N_cap, int n_rec, const int32_t* __restrict__ status,
-                                 int32_t* __restrict__ deg, int32_t* __restrict__ deg_l) {
+__device__ __forceinline__ int row_popc(const u64* __restrict__ m, int n_chunks) {
+    int c = 0;
+    for (int k = 0; k < n_chunks; ++k) c += __popcll(m[k]);
+    return c;
+}
+
+// thread per row (and one past the end): degree in the full graph and in the ligand-touching subgraph
+template <class Slots>
+__global__ void k_degrees(const u64* __restrict__ m_inter, const u64* __restrict__ m_intra,
+                          const u64* __restrict__ m_ll, const int32_t* __restrict__ rr_rowptr, Slots L,
+                          int32_t* __restrict__ deg, int32_t* __restrict__ deg_l) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g > N_cap) return;
-    if (g >= node_ptr[B] || (*status & kBadTable)) { deg[g] = 0; deg_l[g] = 0; return; }
-    const int p = slot_of_node(node_ptr, B, g);
-    const int a0 = lig_ptr[p], n_lig = lig_ptr[p + 1] - a0, local = g - node_ptr[p];
-    const int n_chunks = (n_rec + 63) / 64;
-    if (local < n_lig) {
-        const size_t w = (size_t)a0 + local;
+    if (g > L.rows()) return;
+    PvsSlotRow r = {};
+    if (g < L.rows()) r = L.row(g);
+    if (!r.valid) { deg[g] = 0; deg_l[g] = 0; return; }
+    const int n_chunks = (L.n_rec + 63) / 64;
+    if (r.local < r.n_lig) {
+        const size_t w = (size_t)r.a0 + r.local;
         const int d = row_popc(m_inter + w * n_chunks, n_chunks) + __popcll(m_ll[w]) +
                       row_popc(m_intra + w * n_chunks, n_chunks);
         deg[g] = d;
         deg_l[g] = d;
     } else {
-        const int i = local - n_lig, c = i >> 6;
+        const int i = r.local - r.n_lig, c = i >> 6;
         const u64 bit = 1ull << (i & 63);
         int nl = 0;
-        for (int a = 0; a < n_lig; ++a) {
-            const size_t w = (size_t)a0 + a;
+        for (int a = 0; a < r.n_lig; ++a) {
+            const size_t w = (size_t)r.a0 + a;
             nl += (m_inter[w * n_chunks + c] & bit) ? 1 : 0;
             nl += (m_intra[w * n_chunks + c] & bit) ? 1 : 0;
         }
@@ -365,26 +99,34 @@ __global__ void k_degrees_ragged(const u64* __restrict__ m_inter, const u64* __r
     }
 }
 
-// wave per row: writes the row's segment of the full CSR and of the ligand-touching CSR (k_fill's scheme)
+struct OutCsr {
+    const int32_t* rowptr;
+    int32_t *row, *col;
+    uint8_t* etype;
+    int capacity;
+};
+
+// wave per row: writes the row's segment of the full CSR and of the ligand-touching CSR
+template <class Slots>
 __global__ void __launch_bounds__(256)
-k_fill_ragged(const u64* __restrict__ m_inter, const u64* __restrict__ m_intra, const u64* __restrict__ m_ll,
-              const int32_t* __restrict__ rr_rowptr, const int32_t* __restrict__ rr_col,
-              const int32_t* __restrict__ lig_ptr, const int32_t* __restrict__ node_ptr, int B, int N_cap, int n_rec,
-              OutCsr full, OutCsr lig, float* __restrict__ inv_deg, int32_t* __restrict__ status) {
+k_fill(const u64* __restrict__ m_inter, const u64* __restrict__ m_intra, const u64* __restrict__ m_ll,
+       const int32_t* __restrict__ rr_rowptr, const int32_t* __restrict__ rr_col, Slots L, OutCsr full, OutCsr lig,
+       float* __restrict__ inv_deg, int32_t* __restrict__ status) {
     const int lane = threadIdx.x & 63;
     const int g = (blockIdx.x * 256 + threadIdx.x) >> 6;
-    if (g >= N_cap) return;
-    if (full.rowptr[N_cap] > full.capacity || lig.rowptr[N_cap] > lig.capacity) {
+    const int N = L.rows();
+    if (g >= N) return;
+    if (full.rowptr[N] > full.capacity || lig.rowptr[N] > lig.capacity) {
         if (g == 0 && lane == 0) atomicOr(status, 4);
         return;
     }
-    if (g >= node_ptr[B] || (*status & kBadTable)) {      // padding row (or no valid table: an empty graph)
+    const PvsSlotRow r = L.row(g);
+    if (!r.valid) {                                       // padding row (or no valid table: an empty graph)
         if (lane == 0) inv_deg[g] = 1.0f;
         return;
     }
-    const int p = slot_of_node(node_ptr, B, g);
-    const int a0 = lig_ptr[p], n_lig = lig_ptr[p + 1] - a0, node0 = node_ptr[p], local = g - node0;
-    const int n_chunks = (n_rec + 63) / 64;
+    const int n_lig = r.n_lig, node0 = r.node0;
+    const int n_chunks = (L.n_rec + 63) / 64;
     const u64 lower = (1ull << lane) - 1ull;
     int pf = full.rowptr[g], pl = lig.rowptr[g];
     if (lane == 0) {
@@ -396,30 +138,12 @@ k_fill_ragged(const u64* __restrict__ m_inter, const u64* __restrict__ m_intra, 
         if (also_lig) { lig.row[pl + off] = g; lig.col[pl + off] = column; lig.etype[pl + off] = (uint8_t)cls; }
     };
     auto expand_words = [&](const u64* __restrict__ m, int col0, int cls) {
-        int done = 0;
-        for (int c0 = 0; c0 < n_chunks; c0 += 64) {
-            const int c = c0 + lane;
-            u64 word = c < n_chunks ? m[c] : 0ull;
-            const int cnt = __popcll(word);
-            int scan = cnt;
-            for (int o = 1; o < 64; o <<= 1) {
-                const int t = __shfl_up(scan, o, 64);
-                if (lane >= o) scan += t;
-            }
-            int k = done + scan - cnt;
-            while (word) {
-                const int bit = __builtin_ctzll(word);
-                word &= word - 1ull;
-                emit(k, col0 + 64 * c + bit, cls, true);
-                ++k;
-            }
-            done += __shfl(scan, 63, 64);
-        }
+        const int done = pvs_expand_mask_row(m, n_chunks, lane, [&](int k, int b) { emit(k, col0 + b, cls, true); });
         pf += done;
         pl += done;
     };
-    if (local < n_lig) {
-        const size_t w = (size_t)a0 + local;
+    if (r.local < n_lig) {
+        const size_t w = (size_t)r.a0 + r.local;
         expand_words(m_inter + w * n_chunks, node0 + n_lig, 1);             // inter block: receptor atoms
         {                                                                     // intra block: ligand atoms ...
             const u64 mll = m_ll[w];
@@ -430,11 +154,11 @@ k_fill_ragged(const u64* __restrict__ m_inter, const u64* __restrict__ m_intra, 
         }
         expand_words(m_intra + w * n_chunks, node0 + n_lig, 0);              // ... then receptor atoms
     } else {
-        const int i = local - n_lig, c = i >> 6;
+        const int i = r.local - n_lig, c = i >> 6;
         const u64 bit = 1ull << (i & 63);
         for (int kind = 0; kind < 2; ++kind) {                                // inter block, then intra: ligand atoms
             const u64* m = kind == 0 ? m_inter : m_intra;
-            const bool on = lane < n_lig && (m[((size_t)a0 + lane) * n_chunks + c] & bit);
+            const bool on = lane < n_lig && (m[((size_t)r.a0 + lane) * n_chunks + c] & bit);
             const u64 b = __ballot(on);
             if (on) emit(__popcll(b & lower), node0 + lane, kind == 0 ? 1 : 0, true);
             const int cnt = __popcll(b);
@@ -445,23 +169,135 @@ k_fill_ragged(const u64* __restrict__ m_inter, const u64* __restrict__ m_intra, 
     }
 }
 
+// the builder's scratch: contact masks per packed atom, degrees per row; slot_of (atom -> slot) for the ragged layout
+struct ScreenState {
+    u64 *m_inter, *m_intra, *m_ll;
+    int32_t *deg, *deg_l, *slot_of;
+    void* scan_tmp;
+    size_t scan_bytes;
+};
+
+size_t carve_screen(PvsArena& a, size_t atoms, int rows, int n_rec, bool ragged, ScreenState* out) {
+    ScreenState t;
+    const size_t n_chunks = (size_t)(n_rec + 63) / 64;
+    t.m_inter = a.take<u64>(atoms * n_chunks);
+    t.m_intra = a.take<u64>(atoms * n_chunks);
+    t.m_ll = a.take<u64>(atoms);
+    t.slot_of = ragged ? a.take<int32_t>(atoms) : nullptr;
+    t.deg = a.take<int32_t>((size_t)rows + 1);
+    t.deg_l = a.take<int32_t>((size_t)rows + 1);
+    size_t sb = 0;
+    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, sb, (const int32_t*)nullptr, (int32_t*)nullptr, rows + 1);
+    t.scan_bytes = sb;
+    t.scan_tmp = a.take<char>(sb);
+    if (out) *out = t;
+    return a.off;
+}
+
+// contacts -> degrees -> the two row pointers (rowptr, rowptr_lig: what full.rowptr / lig.rowptr read) -> fill, for
+// either layout
+template <class Slots>
+int build_csrs(const Slots& L, const float* lig_pos, const float* rec_pos, const int32_t* rr_rowptr,
+               const int32_t* rr_col, double inter_radius, double intra_radius, int32_t* rowptr, int32_t* rowptr_lig,
+               OutCsr full, OutCsr lig, float* inv_deg, int32_t* status, const ScreenState& w, hipStream_t s) {
+    const int N = L.rows();
+    k_contacts<<<(L.atoms() + 3) / 4, 256, 0, s>>>(lig_pos, rec_pos, L, make_radius(inter_radius),
+                                                   make_radius(intra_radius), make_radius(1e-7), w.m_inter,
+                                                   w.m_intra, w.m_ll);
+    PVS_CHECK_LAUNCH();
+    k_degrees<<<(N + 1 + 255) / 256, 256, 0, s>>>(w.m_inter, w.m_intra, w.m_ll, rr_rowptr, L, w.deg, w.deg_l);
+    PVS_CHECK_LAUNCH();
+    size_t sb = w.scan_bytes;
+    PVS_CHECK_HIP(hipcub::DeviceScan::ExclusiveSum(w.scan_tmp, sb, w.deg, rowptr, N + 1, s));
+    sb = w.scan_bytes;
+    PVS_CHECK_HIP(hipcub::DeviceScan::ExclusiveSum(w.scan_tmp, sb, w.deg_l, rowptr_lig, N + 1, s));
+    k_fill<<<(N + 3) / 4, 256, 0, s>>>(w.m_inter, w.m_intra, w.m_ll, rr_rowptr, rr_col, L, full, lig, inv_deg, status);
+    PVS_CHECK_LAUNCH();
+    return 0;
+}
+
+}  // namespace
+
+extern "C" size_t pvs_screen_graph_state_bytes(int32_t B, int32_t n_lig, int32_t n_rec) {
+    PvsArena a(nullptr, 0);
+    const PvsUniformSlots L{B, n_lig, n_rec};
+    return carve_screen(a, (size_t)L.atoms(), L.rows(), n_rec, false, nullptr) + 256;
+}
+
+extern "C" int pvs_screen_graph_build(const float* lig_pos, const float* rec_pos, const int32_t* rr_rowptr,
+                                      const int32_t* rr_col, int32_t B, int32_t n_lig, int32_t n_rec,
+                                      double inter_radius, double intra_radius, int32_t capacity,
+                                      int32_t capacity_lig, int32_t* rowptr, int32_t* row, int32_t* col,
+                                      uint8_t* etype, float* inv_deg, int32_t* rowptr_lig, int32_t* row_lig,
+                                      int32_t* col_lig, uint8_t* etype_lig, int32_t* status, void* state,
+                                      size_t state_bytes, pvs_stream_t stream_) {
+    hipStream_t s = (hipStream_t)stream_;
+    PVS_REQUIRE(lig_pos && rec_pos && rr_rowptr && rr_col && rowptr && row && col && etype && inv_deg &&
+                rowptr_lig && row_lig && col_lig && etype_lig && status && state, "pvs_screen_graph_build: NULL");
+    PVS_REQUIRE(B > 0 && n_lig > 0 && n_lig <= 64 && n_rec > 0, "pvs_screen_graph_build: needs 1..64 ligand atoms "
+                "(got %d) and a receptor", n_lig);
+    const PvsUniformSlots L{B, n_lig, n_rec};
+    PvsArena arena(state, state_bytes);
+    ScreenState w;
+    carve_screen(arena, (size_t)L.atoms(), L.rows(), n_rec, false, &w);
+    PVS_REQUIRE(arena.ok(), "pvs_screen_graph_build: state too small (%zu < %zu)", state_bytes, arena.off);
+    PvsProfScope prof(s, PVS_PROF_PREPARE);
+    PVS_CHECK_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), s));
+    return build_csrs(L, lig_pos, rec_pos, rr_rowptr, rr_col, inter_radius, intra_radius, rowptr, rowptr_lig,
+                      OutCsr{rowptr, row, col, etype, capacity},
+                      OutCsr{rowptr_lig, row_lig, col_lig, etype_lig, capacity_lig}, inv_deg, status, w, s);
+}
+
+// ---- library batches: every slot of the batch holds one pose of ANY ligand of 0..64 atoms ----
+// pvs_screen_graph_build_ragged: the same graphs for a batch whose B slots hold poses of different
+// ligands (a docking library: thousands of ligands of 8-60 atoms with ~10 poses each). The ligand atoms
+// come packed, lig_pos [L_cap,3] with the device table lig_ptr [B+1]; slot p has lig_ptr[p+1]-lig_ptr[p]
+// atoms (0 = receptor only). Compact node layout: slot p owns nodes node_ptr[p] .. node_ptr[p+1],
+// node_ptr[p] = lig_ptr[p] + p * n_rec, ligand atoms first, then the receptor; the nodes from node_ptr[B]
+// up to N_cap = L_cap + B * n_rec are padding (degree 0, inv_deg 1, graph id -1). No host argument depends
+// on the batch's composition, so one captured step serves every batch of a library. The masks are indexed by
+// the packed atom (same words as above), node -> slot by bisection of node_ptr, atom -> slot by a table that
+// the first kernel fills; the node tables of the layer stack (graph id, pos, features, first-layer receptor
+// sums) are expanded by a sibling kernel of the same call. The kernels above run on either layout (screen_slots.h:
+// PvsUniformSlots, PvsRaggedSlots); only k_slots and k_node_tables_ragged are the ragged builder's own.
+namespace {
+
+// thread per slot: validates the slot, node_ptr, atom -> slot table
+__global__ void k_slots(const int32_t* __restrict__ lig_ptr, int B, int L_cap, int n_rec,
+                        int32_t* __restrict__ node_ptr, int32_t* __restrict__ slot_of,
+                        int32_t* __restrict__ status) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p > B) return;
+    if (p == B) {
+        const int t = lig_ptr[B];
+        node_ptr[B] = (t >= 0 && t <= L_cap) ? t + B * n_rec : B * n_rec;
+        if (lig_ptr[0] != 0) atomicOr(status, kPvsBadTable);
+        return;
+    }
+    const int a0 = lig_ptr[p], a1 = lig_ptr[p + 1];
+    if (a0 < 0 || a1 < a0 || a1 - a0 > 64 || a1 > L_cap) {
+        atomicOr(status, kPvsBadTable);
+        node_ptr[p] = p * n_rec;
+        return;
+    }
+    node_ptr[p] = a0 + p * n_rec;
+    for (int q = a0; q < a1; ++q) slot_of[q] = p;
+}
+
 // wave per node: graph id, coordinates and (with tables) the feature row and the first-layer receptor sums
 __global__ void __launch_bounds__(256)
-k_node_tables_ragged(const float* __restrict__ lig_pos, const float* __restrict__ rec_pos,
-                     const int32_t* __restrict__ lig_ptr, const int32_t* __restrict__ node_ptr, int B, int N_cap,
-                     const int32_t* __restrict__ status, int32_t* __restrict__ node_graph, float* __restrict__ pos,
-                     PvsRaggedNodeTables t) {
+k_node_tables_ragged(const float* __restrict__ lig_pos, const float* __restrict__ rec_pos, PvsRaggedSlots L,
+                     int32_t* __restrict__ node_graph, float* __restrict__ pos, PvsRaggedNodeTables t) {
     const int lane = threadIdx.x & 63;
     const int g = (blockIdx.x * 256 + threadIdx.x) >> 6;
-    if (g >= N_cap) return;
+    if (g >= L.rows()) return;
     const int F = t.n_feats, H = t.hidden;
-    int p = -1, lig_row = -1, rec_row = -1;                // padding: every table zero
-    if (g < node_ptr[B] && !(*status & kBadTable)) {
-        p = slot_of_node(node_ptr, B, g);
-        const int a0 = lig_ptr[p], n_lig = lig_ptr[p + 1] - a0, local = g - node_ptr[p];
-        if (local < n_lig) lig_row = a0 + local; else rec_row = local - n_lig;
+    const PvsSlotRow r = L.row(g);
+    int lig_row = -1, rec_row = -1;                        // padding: every table zero
+    if (r.valid) {
+        if (r.local < r.n_lig) lig_row = r.a0 + r.local; else rec_row = r.local - r.n_lig;
     }
-    if (lane == 0) node_graph[g] = p;
+    if (lane == 0) node_graph[g] = r.slot;
     if (lane < 3) {
         pos[(size_t)g * 3 + lane] = lig_row >= 0 ? lig_pos[(size_t)lig_row * 3 + lane]
                                   : rec_row >= 0 ? rec_pos[(size_t)rec_row * 3 + lane] : 0.0f;
@@ -479,36 +315,11 @@ k_node_tables_ragged(const float* __restrict__ lig_pos, const float* __restrict_
     }
 }
 
-struct RaggedState {
-    u64 *m_inter, *m_intra, *m_ll;
-    int32_t *deg, *deg_l, *slot_of;
-    void* scan_tmp;
-    size_t scan_bytes;
-};
-
-size_t carve_ragged(PvsArena& a, int B, int L_cap, int n_rec, RaggedState* out) {
-    RaggedState t;
-    const size_t n_chunks = (size_t)(n_rec + 63) / 64, rows = (size_t)L_cap;
-    const int N_cap = L_cap + B * n_rec;
-    t.m_inter = a.take<u64>(rows * n_chunks);
-    t.m_intra = a.take<u64>(rows * n_chunks);
-    t.m_ll = a.take<u64>(rows);
-    t.slot_of = a.take<int32_t>(rows);
-    t.deg = a.take<int32_t>((size_t)N_cap + 1);
-    t.deg_l = a.take<int32_t>((size_t)N_cap + 1);
-    size_t sb = 0;
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, sb, (const int32_t*)nullptr, (int32_t*)nullptr, N_cap + 1);
-    t.scan_bytes = sb;
-    t.scan_tmp = a.take<char>(sb);
-    if (out) *out = t;
-    return a.off;
-}
-
 }  // namespace
 
 extern "C" size_t pvs_screen_graph_ragged_state_bytes(int32_t B, int32_t L_cap, int32_t n_rec) {
     PvsArena a(nullptr, 0);
-    return carve_ragged(a, B, L_cap, n_rec, nullptr) + 256;
+    return carve_screen(a, (size_t)L_cap, L_cap + B * n_rec, n_rec, true, nullptr) + 256;
 }
 
 extern "C" int pvs_screen_graph_build_ragged(const float* lig_pos, const int32_t* lig_ptr, const float* rec_pos,
@@ -537,31 +348,18 @@ extern "C" int pvs_screen_graph_build_ragged(const float* lig_pos, const int32_t
                     "%s: receptor sums incomplete", who);
     }
     PvsArena arena(state, state_bytes);
-    RaggedState w;
-    carve_ragged(arena, B, L_cap, n_rec, &w);
+    ScreenState w;
+    carve_screen(arena, (size_t)L_cap, L_cap + B * n_rec, n_rec, true, &w);
     PVS_REQUIRE(arena.ok(), "%s: state too small (%zu < %zu)", who, state_bytes, arena.off);
     PvsProfScope prof(s, PVS_PROF_PREPARE);
-    const int N_cap = L_cap + B * n_rec;
+    const PvsRaggedSlots L{lig_ptr, node_ptr, w.slot_of, status, B, L_cap, n_rec};
     PVS_CHECK_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), s));
     k_slots<<<(B + 1 + 255) / 256, 256, 0, s>>>(lig_ptr, B, L_cap, n_rec, node_ptr, w.slot_of, status);
     PVS_CHECK_LAUNCH();
-    k_contacts_ragged<<<(L_cap + 3) / 4, 256, 0, s>>>(lig_pos, lig_ptr, w.slot_of, rec_pos, B, L_cap, n_rec,
-                                                      make_radius(inter_radius), make_radius(intra_radius),
-                                                      make_radius(1e-7), status, w.m_inter, w.m_intra, w.m_ll);
-    PVS_CHECK_LAUNCH();
-    k_degrees_ragged<<<(N_cap + 1 + 255) / 256, 256, 0, s>>>(w.m_inter, w.m_intra, w.m_ll, rr_rowptr, lig_ptr, node_ptr,
-                                                             B, N_cap, n_rec, status, w.deg, w.deg_l);
-    PVS_CHECK_LAUNCH();
-    size_t sb = w.scan_bytes;
-    PVS_CHECK_HIP(hipcub::DeviceScan::ExclusiveSum(w.scan_tmp, sb, w.deg, rowptr, N_cap + 1, s));
-    sb = w.scan_bytes;
-    PVS_CHECK_HIP(hipcub::DeviceScan::ExclusiveSum(w.scan_tmp, sb, w.deg_l, rowptr_lig, N_cap + 1, s));
-    OutCsr full{rowptr, row, col, etype, capacity}, lig{rowptr_lig, row_lig, col_lig, etype_lig, capacity_lig};
-    k_fill_ragged<<<(N_cap + 3) / 4, 256, 0, s>>>(w.m_inter, w.m_intra, w.m_ll, rr_rowptr, rr_col, lig_ptr, node_ptr, B,
-                                                  N_cap, n_rec, full, lig, inv_deg, status);
-    PVS_CHECK_LAUNCH();
-    k_node_tables_ragged<<<(N_cap + 3) / 4, 256, 0, s>>>(lig_pos, rec_pos, lig_ptr, node_ptr, B, N_cap, status,
-                                                         node_graph, pos, t);
+    PVS_TRY(build_csrs(L, lig_pos, rec_pos, rr_rowptr, rr_col, inter_radius, intra_radius, rowptr, rowptr_lig,
+                       OutCsr{rowptr, row, col, etype, capacity},
+                       OutCsr{rowptr_lig, row_lig, col_lig, etype_lig, capacity_lig}, inv_deg, status, w, s));
+    k_node_tables_ragged<<<(L.rows() + 3) / 4, 256, 0, s>>>(lig_pos, rec_pos, L, node_graph, pos, t);
     PVS_CHECK_LAUNCH();
     return 0;
 }

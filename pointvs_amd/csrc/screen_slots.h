@@ -1,0 +1,70 @@
+// Where the slots of a pose batch live (screen_graph.hip), and the table bisection the graph builders share.
+// A slot holds one pose: its ligand atoms, then the receptor's n_rec atoms. Two layouts answer the same questions
+// (how many packed ligand atoms and node rows there are; which slot a packed atom or a row belongs to), so that the
+// builder's kernels exist once: uniform (B poses of one n_lig-atom ligand, by arithmetic) and ragged (one pose of any
+// 0..64-atom ligand per slot, from the device tables lig_ptr / node_ptr / slot_of). No HIP header: the host compiler
+// builds this file alone (tests/test_screen_slots_host.py).
+#pragma once
+#include <stdint.h>
+
+#ifdef __HIPCC__
+#define PVS_SLOTS_FN __host__ __device__ inline
+#else
+#define PVS_SLOTS_FN inline
+#endif
+
+// The last k in [0, n) with table[k] <= i, for an ascending table with table[0] <= i (0 otherwise; of equal entries
+// the last one wins, so empty slots / graphs never own a row).
+PVS_SLOTS_FN int pvs_last_le(const int32_t* table, int n, int i) {
+    int lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (table[mid] <= i) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+constexpr int kPvsBadTable = 8;     // *status bit 3: lig_ptr is not a table of 0..64-atom slots inside L_cap
+
+// What a layout says about a packed ligand atom or a node row. Not valid: the other fields are zero (a row's slot: -1).
+struct PvsSlotAtom {
+    bool valid;
+    int a0, n_lig;                  // the slot's first packed atom and its atom count
+};
+struct PvsSlotRow {
+    bool valid;
+    int slot, a0, n_lig;
+    int node0, local;               // the slot's first row; this row inside the slot (< n_lig: ligand atom, else receptor)
+};
+
+// B poses of one ligand: slot p owns the atoms p * n_lig .. and the rows p * (n_lig + n_rec) ..; every row is valid.
+struct PvsUniformSlots {
+    int B, n_lig, n_rec;
+    PVS_SLOTS_FN int atoms() const { return B * n_lig; }
+    PVS_SLOTS_FN int rows() const { return B * (n_lig + n_rec); }
+    PVS_SLOTS_FN PvsSlotAtom atom(int q) const { return {true, q / n_lig * n_lig, n_lig}; }
+    PVS_SLOTS_FN PvsSlotRow row(int g) const {
+        const int n = n_lig + n_rec, p = g / n;
+        return {true, p, p * n_lig, n_lig, p * n, g - p * n};
+    }
+};
+
+// One pose of any ligand per slot: slot p owns the atoms lig_ptr[p] .. lig_ptr[p+1] and the rows node_ptr[p] ..
+// node_ptr[p+1] (node_ptr[p] = lig_ptr[p] + p * n_rec). Not valid: the atoms from lig_ptr[B], the rows from
+// node_ptr[B] (padding up to L_cap / L_cap + B * n_rec), and everything while *status has kPvsBadTable.
+struct PvsRaggedSlots {
+    const int32_t *lig_ptr, *node_ptr, *slot_of, *status;
+    int B, L_cap, n_rec;
+    PVS_SLOTS_FN int atoms() const { return L_cap; }
+    PVS_SLOTS_FN int rows() const { return L_cap + B * n_rec; }
+    PVS_SLOTS_FN PvsSlotAtom atom(int q) const {
+        if ((*status & kPvsBadTable) || q >= lig_ptr[B]) return {false, 0, 0};
+        const int p = slot_of[q], a0 = lig_ptr[p];
+        return {true, a0, lig_ptr[p + 1] - a0};
+    }
+    PVS_SLOTS_FN PvsSlotRow row(int g) const {
+        if (g >= node_ptr[B] || (*status & kPvsBadTable)) return {false, -1, 0, 0, 0, 0};
+        const int p = pvs_last_le(node_ptr, B, g), a0 = lig_ptr[p], node0 = node_ptr[p];
+        return {true, p, a0, lig_ptr[p + 1] - a0, node0, g - node0};
+    }
+};

@@ -323,3 +323,92 @@ def test_weights_changed_under_a_captured_screen_is_refused(kind):
         screen.replay(batch)
     with pytest.raises(RuntimeError, match='weights changed'):
         screen(batch)
+
+
+def _fill_canaries(f):
+    for k in ('row', 'col', 'row_l', 'col_l'):
+        f[k].fill_(-77)
+    for k in ('etype', 'etype_l'):
+        f[k].fill_(77)
+
+
+def _canaries_intact(f):
+    return (all(bool((f[k] == -77).all()) for k in ('row', 'col', 'row_l', 'col_l')) and
+            all(bool((f[k] == 77).all()) for k in ('etype', 'etype_l')))
+
+
+def test_pose_batch_builder_at_capacity_reports_overflow_and_writes_nothing():
+    """pvs_screen_graph_build (the uniform builder) at its capacities: one edge short in either CSR, or half of
+    both, sets the overflow bit, keeps both edge counts and writes no entry; with exactly enough room there is no
+    flag, every entry below the count is written and nothing behind it."""
+    from pointvs_amd.screening import ReceptorScreen
+    from pointvs_amd.synthetic import random_poses
+    lig, rec, lig_feats, rec_feats = _set(6007, n_lig=5)
+    poses = random_poses(lig, 2, seed=3, max_shift=2.0).cuda()
+    screen = ReceptorScreen(_model(), rec.cuda(), torch.cat([lig_feats, rec_feats], 0), 5, 2, 6.0, 2.5)
+    assert screen.fast_graph
+    screen._build_fast(poses)
+    screen.check()
+    f, n = screen._fast, 2 * (5 + N_REC)
+    e, el = int(f['rowptr'][n]), int(f['rowptr_l'][n])
+    assert 0 < el < e
+    for cap, cap_l in ((e - 1, el), (e, el - 1), (e // 2, el // 2)):
+        f['cap'], f['cap_l'] = cap, cap_l
+        _fill_canaries(f)
+        screen._build_fast(poses)
+        with pytest.raises(RuntimeError, match='overflow'):
+            screen.check()
+        assert int(f['rowptr'][n]) == e and int(f['rowptr_l'][n]) == el
+        assert _canaries_intact(f)
+    f['cap'], f['cap_l'] = e, el                          # exactly enough room: no flag
+    _fill_canaries(f)
+    screen._build_fast(poses)
+    screen.check()
+    for tag, count in (('', e), ('_l', el)):
+        for k in ('row', 'col'):
+            assert bool((f[k + tag][:count] >= 0).all()) and bool((f[k + tag][count:] == -77).all()), k + tag
+        assert bool((f['etype' + tag][:count] <= 2).all()) and bool((f['etype' + tag][count:] == 77).all()), tag
+
+
+BAD_LIG_PTR = [([1, 64, 64, 65, 129], 'first entry not 0'), ([0, 64, 60, 65, 129], 'descending'),
+               ([0, 65, 65, 66, 129], 'a 65-atom slot'), ([0, 64, 64, 65, 257], 'beyond L_cap')]
+
+
+def test_a_lig_ptr_that_is_no_table_gives_an_empty_graph():
+    """Status bit 3 of pvs_screen_graph_build_ragged: a lig_ptr that is not a table of 0..64-atom slots inside L_cap
+    (validated on the device) is reported as ValueError, the batch comes out as an empty graph of padding rows and
+    no edge entry is written; the valid table afterwards reproduces the first build array for array."""
+    from pointvs_amd.screening import LibraryScreen
+    lig, rec, lig_feats, rec_feats = _set(6008)
+    rec, rec_feats = rec[:65].contiguous(), rec_feats[:65].contiguous()
+    sizes = (64, 0, 1, 64)
+    slots = _slots(lig, lig_feats, sizes, seed=20, special=False)
+    screen = LibraryScreen(_model(), rec.cuda(), rec_feats, 4, 64, 7.0).load(slots)
+    assert screen.l_cap == 256
+    f = screen._build()
+    screen.check()
+    torch.cuda.synchronize()
+    names = ('rowptr', 'row', 'col', 'etype', 'rowptr_l', 'row_l', 'col_l', 'etype_l', 'inv_deg', 'node_ptr',
+             'node_graph', 'pos', 'x', 'base_magg', 'base_xsum', 'base_deg')
+    e, el = int(f['rowptr'][screen.n_cap]), int(f['rowptr_l'][screen.n_cap])
+    assert 0 < el < e
+    count = {'row': e, 'col': e, 'etype': e, 'row_l': el, 'col_l': el, 'etype_l': el}
+    first = {k: f[k][:count.get(k)].clone() for k in names}
+    good = screen.lig_ptr.clone()
+    assert good.tolist() == [0, 64, 64, 65, 129]
+    for table, what in BAD_LIG_PTR:
+        screen.lig_ptr.copy_(torch.tensor(table, dtype=torch.int32))
+        _fill_canaries(f)
+        screen._build()
+        with pytest.raises(ValueError, match='lig_ptr'):
+            screen.check()
+        assert bool((f['rowptr'] == 0).all()) and bool((f['rowptr_l'] == 0).all()), what
+        assert _canaries_intact(f), what
+        assert bool((f['inv_deg'] == 1).all()) and bool((f['node_graph'] == -1).all()), what
+        for k in ('pos', 'x', 'base_magg', 'base_xsum', 'base_deg'):
+            assert bool((f[k] == 0).all()), (what, k)
+    screen.lig_ptr.copy_(good)
+    screen._build()
+    screen.check()
+    for k in names:
+        assert torch.equal(f[k][:count.get(k)], first[k]), k
