@@ -218,14 +218,14 @@ class EGNNLayer(nn.Module):
             else:
                 return params, pstruct
         params = self._params()
-        dtype = params[0].dtype     # fp64 layers (model.double(), --double) get the fp64 struct
-        ok = dtype in (torch.float32, torch.float64) and all(
+        dtype = params[0].dtype
+        kind = PF.KINDS.get(dtype)  # fp64 layers (model.double(), --double) get the fp64 struct
+        ok = kind is not None and all(
             p is None or (p.is_cuda and p.dtype == dtype and p.is_contiguous()) for p in params)
         if not ok:
             self.__dict__.pop('_pcache', None)
             return params, None
-        struct = _lib.PvsLayerParams if dtype == torch.float32 else _lib.PvsLayerParamsF64
-        pstruct = struct(*[_lib.ptr(p) for p in params])
+        pstruct = kind.params_t(*[_lib.ptr(p) for p in params])
         probes = self._slot_probes(params)
         if probes is None:            # computed weights (parametrizations): a fresh struct per call
             self.__dict__.pop('_pcache', None)
@@ -626,7 +626,7 @@ class SartorrasEGNN(PNNGeometricBase):
         pstructs, param_tuples = [], []
         for layer in egnn_layers:
             params, pstruct = layer._params_cached()
-            if pstruct is None or isinstance(pstruct, _lib.PvsLayerParamsF64):     # (no fused fp64 stack)
+            if not isinstance(pstruct, PF.STACK_KIND.params_t):     # (None, or fp64: no fused fp64 stack)
                 return None
             pstructs.append(pstruct)
             param_tuples.append(params)

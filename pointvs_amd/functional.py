@@ -18,32 +18,80 @@ def _ws(nbytes, dev):
     return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)
 
 
-def _fc(t, dtype):
-    """`t` contiguous, checked to be of `dtype` (the dtype of the call's primary input): the kernels never cast."""
+_F32, _F64 = torch.float32, torch.float64
+
+
+class _Kind:
+    """What distinguishes the fp32 and the fp64 family of this binding, said once: the torch dtype, the parameter and
+    gradient struct classes of the layer, the 32-bit words per value (the row permutation is a bit copy) and, per
+    operator, the C entry point. Every wrapper below has ONE body and reads these from the kind of its call.
+    The entry points become attributes (bound ctypes functions) the first time one of them is asked for: the library is
+    loaded by then and not at import, and a call pays a plain attribute look-up."""
+
+    def __init__(self, dtype, params_t, grads_t, words, **entry):
+        self.dtype, self.params_t, self.grads_t, self.words, self.entry = dtype, params_t, grads_t, words, entry
+
+    def __getattr__(self, op):      # (reached only while the entry points are unbound: binds them all)
+        entry = self.__dict__.get('entry')      # (absent on an instance made without __init__: copy / pickle probes)
+        if entry is None or op not in entry:
+            raise AttributeError(op)
+        lib = _lib.lib()
+        # (the one write after __init__: from here on the record is only read)
+        self.__dict__.update({name: getattr(lib, symbol) for name, symbol in self.entry.items()})
+        return self.__dict__[op]
+
+    def check(self, rc, op):
+        if rc != 0:
+            _lib.check(rc, self.entry[op])
+
+
+KINDS = {
+    _F32: _Kind(_F32, _lib.PvsLayerParams, _lib.PvsLayerGrads, 1,
+                rows_to_input='pvs_rows_to_input_order', rows_to_sorted='pvs_rows_to_sorted_order',
+                layer_saved='pvs_egnn_layer_saved_floats', layer_ws='pvs_egnn_layer_workspace_bytes',
+                layer_fwd='pvs_egnn_layer_fwd', layer_bwd='pvs_egnn_layer_bwd',
+                linear_fwd='pvs_linear_fwd', linear_bwd_ws='pvs_linear_bwd_workspace_bytes', linear_bwd='pvs_linear_bwd',
+                mean_pool_fwd='pvs_mean_pool_fwd', mean_pool_bwd='pvs_mean_pool_bwd',
+                segment_ws='pvs_segment_workspace_bytes', segment_fwd='pvs_segment_reduce_fwd',
+                segment_bwd='pvs_segment_reduce_bwd'),
+    # (the row permutation has no fp64 entry: the fp32 one moves 2 x width words per row)
+    _F64: _Kind(_F64, _lib.PvsLayerParamsF64, _lib.PvsLayerGradsF64, 2,
+                rows_to_input='pvs_rows_to_input_order', rows_to_sorted='pvs_rows_to_sorted_order',
+                layer_saved='pvs_egnn_layer_saved_doubles_f64', layer_ws='pvs_egnn_layer_workspace_bytes_f64',
+                layer_fwd='pvs_egnn_layer_fwd_f64', layer_bwd='pvs_egnn_layer_bwd_f64',
+                linear_fwd='pvs_linear_fwd_f64', linear_bwd_ws='pvs_linear_bwd_workspace_bytes_f64',
+                linear_bwd='pvs_linear_bwd_f64',
+                mean_pool_fwd='pvs_mean_pool_fwd_f64', mean_pool_bwd='pvs_mean_pool_bwd_f64',
+                segment_ws='pvs_segment_workspace_bytes_f64', segment_fwd='pvs_segment_reduce_fwd_f64',
+                segment_bwd='pvs_segment_reduce_bwd_f64'),
+}
+_K32, _K64 = KINDS[_F32], KINDS[_F64]
+STACK_KIND = _K32        # the one-call layer stack (pvs_egnn_stack_fwd / _bwd) is built for fp32 only
+
+
+def _kind_of(what, t):
+    kind = KINDS.get(t.dtype)
+    if kind is None:
+        raise TypeError(f'{what}: pointvs_amd kernels are float32 or float64 (got {t.dtype})')
+    return kind
+
+
+def _c(t, dtype, note=''):
+    """`t` contiguous, checked to be of `dtype` (the dtype of the call): the kernels never cast."""
     if t is None:
         return None
     if t.dtype != dtype:
-        raise TypeError(f'pointvs_amd: a {t.dtype} tensor in a {dtype} call (mixed dtypes are not cast)')
+        raise TypeError(f'pointvs_amd: a {t.dtype} tensor in a {dtype} call (mixed dtypes are not cast){note}')
     return t.contiguous()
 
 
-def _f32c(t):
-    if t is None:
-        return None
-    if t.dtype != torch.float32:
-        raise TypeError(f'pointvs_amd: this op is fp32 only (got {t.dtype}); fp64 runs per-layer ops')
-    return t.contiguous()
-
-
-_F64 = torch.float64
+_FP32_ONLY = ': this op is fp32 only, fp64 runs per-layer ops'
 
 
 def _call_dtype(what, primary, **others):
     """The dtype of a call: its primary input's, fp32 or fp64. Any other floating tensor of another dtype is a
     TypeError that names them all (fp64 parameters with fp32 features, say): never cast silently."""
-    dtype = primary.dtype
-    if dtype not in (torch.float32, _F64):
-        raise TypeError(f'{what}: pointvs_amd kernels are float32 or float64 (got {dtype})')
+    dtype = _kind_of(what, primary).dtype
     bad = [f'{k}: {t.dtype}' for k, t in others.items() if t is not None and t.dtype != dtype]
     if bad:
         raise TypeError(f'{what}: mixed dtypes - the primary input is {dtype}, but ' + ', '.join(bad) +
@@ -56,21 +104,20 @@ class _PermuteRows(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, src, perm, to_input):
-        src = _f32c(src) if src.dtype != _F64 else src.contiguous()
+        kind = _kind_of('rows_to_input_order / rows_to_sorted_order', src)
+        src = src.contiguous()
         _lib.require_hip(src)
-        ctx.perm, ctx.to_input = perm, to_input
-        width = src.shape[1] if src.dim() > 1 else 1
-        if src.dtype == _F64:       # a bit copy: the fp32 kernel moves 2 x width words per row
-            width *= 2
+        ctx.perm, ctx.to_input, ctx.dtype = perm, to_input, kind.dtype
+        width = (src.shape[1] if src.dim() > 1 else 1) * kind.words
         dst = torch.empty_like(src)
-        fn = _lib.lib().pvs_rows_to_input_order if to_input else _lib.lib().pvs_rows_to_sorted_order
-        _lib.check(fn(_lib.ptr(src), _lib.ptr(dst), _lib.ptr(perm), src.shape[0], width,
-                      _stream(src.device)), 'pvs_rows_permute')
+        fn = kind.rows_to_input if to_input else kind.rows_to_sorted
+        kind.check(fn(_lib.ptr(src), _lib.ptr(dst), _lib.ptr(perm), src.shape[0], width, _stream(src.device)),
+                   'rows_to_input' if to_input else 'rows_to_sorted')
         return dst
 
     @staticmethod
     def backward(ctx, g):
-        return _PermuteRows.apply(g, ctx.perm, not ctx.to_input), None, None
+        return _PermuteRows.apply(_c(g, ctx.dtype), ctx.perm, not ctx.to_input), None, None
 
 
 def rows_to_input_order(src_sorted, pg):
@@ -81,22 +128,36 @@ def rows_to_sorted_order(src_input, pg):
     return _PermuteRows.apply(src_input, pg.perm, False)
 
 
+_COORD_MLP = ('coord_w1', 'coord_b1', 'coord_w2')
+
+
+def dead_grads(flags, coords_fed, edge_res):
+    """The slots of `_lib.PARAM_FIELDS` that get NO gradient in a layer's backward (every other parameter the layer has
+    gets one): the coord MLP unless the layer updates coordinates and a gradient arrived for them (`coords_fed`), the
+    edge gate unless messages came from the layer before (`edge_res`) through a rezero / gated residual."""
+    dead = () if flags & _lib.UPDATE_COORDS and coords_fed else _COORD_MLP
+    if not (edge_res and flags & (_lib.REZERO | _lib.GATED_RESIDUAL)):
+        dead += ('edge_gate',)
+    return dead
+
+
 class _EGNNLayerFn(torch.autograd.Function):
-    """One EGNNLayer.forward (egnn_satorras.py:189-206) and its backward, sorted edge order."""
+    """One EGNNLayer.forward (egnn_satorras.py:189-206) and its backward, sorted edge order, in the dtype of `kind`."""
 
     @staticmethod
-    def forward(ctx, h, x, m_prev, pg, desc_tuple, need_m, pstruct, *params):
-        # pstruct: the layer's PvsLayerParams built ONCE for these very parameter tensors (EGNNLayer._params_cached:
-        # fp32, contiguous, on the device - checked when it was built), or None (padded / ad-hoc parameter tensors).
-        # Host time matters here: at the reference's default shape (32 graphs of 500 atoms) a training step is ~70
-        # launches of a few microseconds and the step is bound by this Python (tools/host_profile.py).
-        lib = _lib.lib()
+    def forward(ctx, kind, h, x, m_prev, pg, desc_tuple, need_m, pstruct, *params):
+        # pstruct: the layer's parameter struct built ONCE for these very parameter tensors (EGNNLayer._params_cached:
+        # of the kind's dtype, contiguous, on the device - checked when it was built), or None (padded / ad-hoc
+        # parameter tensors). Host time matters here: at the reference's default shape (32 graphs of 500 atoms) a
+        # training step is ~70 launches of a few microseconds and the step is bound by this Python
+        # (tools/host_profile.py).
         hidden, n_attr, flags, act = desc_tuple
-        h, x, m_prev = _f32c(h), _f32c(x), _f32c(m_prev)
+        dtype = kind.dtype
+        h, x, m_prev = _c(h, dtype), _c(x, dtype), _c(m_prev, dtype)
         if pstruct is None:
-            params = tuple(_f32c(p) for p in params)
+            params = tuple(_c(p, dtype) for p in params)
             _lib.require_hip(h, x, m_prev, *params)
-            pstruct = _lib.PvsLayerParams(*[_lib.ptr(p) for p in params])
+            pstruct = kind.params_t(*[_lib.ptr(p) for p in params])
         else:
             _lib.require_hip(h, x, m_prev)
         dev = h.device
@@ -113,20 +174,18 @@ class _EGNNLayerFn(torch.autograd.Function):
         eres = bool(flags & _lib.EDGE_RESIDUAL) and m_prev is not None
         h_out = torch.empty_like(h)
         x_out = torch.empty_like(x)
-        m_out = torch.empty((max(e, 0), hidden), dtype=torch.float32, device=dev) if need_m else None
-        att = torch.empty((max(e, 1),), dtype=torch.float32, device=dev) if eatt else None
-        node_att = torch.empty((n,), dtype=torch.float32, device=dev) if natt else None
-        saved = torch.empty(lib.pvs_egnn_layer_saved_floats(C.byref(desc), n, e),
-                            dtype=torch.float32, device=dev)
-        ws_bytes = lib.pvs_egnn_layer_workspace_bytes(C.byref(desc), n, e, 0)
+        m_out = torch.empty((max(e, 0), hidden), dtype=dtype, device=dev) if need_m else None
+        att = torch.empty((max(e, 1),), dtype=dtype, device=dev) if eatt else None
+        node_att = torch.empty((n,), dtype=dtype, device=dev) if natt else None
+        saved = torch.empty(kind.layer_saved(C.byref(desc), n, e), dtype=dtype, device=dev)
+        ws_bytes = kind.layer_ws(C.byref(desc), n, e, 0)
         ws = _ws(ws_bytes, dev)
-        rc = lib.pvs_egnn_layer_fwd(
+        rc = kind.layer_fwd(
             C.byref(desc), C.byref(pg.c), C.byref(pstruct), _lib.ptr(h), _lib.ptr(x),
             _lib.ptr(m_prev if eres else None), _lib.ptr(h_out), _lib.ptr(x_out), _lib.ptr(m_out),
             _lib.ptr(att), _lib.ptr(node_att), _lib.ptr(saved), _lib.ptr(ws), ws_bytes, _stream(dev))
-        _lib.check(rc, 'pvs_egnn_layer_fwd')
-        ctx.pg, ctx.desc_tuple, ctx.eres = pg, desc_tuple, eres
-        ctx.n_params = len(params)
+        kind.check(rc, 'layer_fwd')
+        ctx.pg, ctx.desc_tuple, ctx.eres, ctx.kind = pg, desc_tuple, eres, kind
         ctx.pstruct = pstruct      # (the backward reads the same parameter tensors: saved below, so they cannot have moved)
         ctx.save_for_backward(h, x, m_prev if eres else None, att, saved, *params)
         ctx.set_materialize_grads(False)
@@ -138,129 +197,48 @@ class _EGNNLayerFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_h_out, g_x_out, g_m_out, _g_att, _g_natt):
-        lib = _lib.lib()
         h, x, m_prev, att, saved, *params = ctx.saved_tensors
-        pg = ctx.pg
+        pg, kind = ctx.pg, ctx.kind
         hidden, n_attr, flags, act = ctx.desc_tuple
-        dev = h.device
+        dev, dtype = h.device, kind.dtype
         n, e = pg.n_nodes, pg.n_edges
         desc = _lib.PvsLayerDesc(hidden, n_attr, flags, act)
         pstruct = ctx.pstruct
-        g_h_out = torch.zeros_like(h) if g_h_out is None else _f32c(g_h_out)
-        g_x_out = _f32c(g_x_out)       # None => the caller never used x_out (last layer)
-        g_m_out = _f32c(g_m_out) if (g_m_out is not None and g_m_out.numel()) else None
+        g_h_out = torch.zeros_like(h) if g_h_out is None else _c(g_h_out, dtype)
+        g_x_out = _c(g_x_out, dtype)       # None => the caller never used x_out (last layer)
+        g_m_out = _c(g_m_out, dtype) if (g_m_out is not None and g_m_out.numel()) else None
         need = ctx.needs_input_grad
         g_h = torch.empty_like(h)
-        g_x = torch.empty_like(x) if need[1] else None
+        g_x = torch.empty_like(x) if need[2] else None
         g_m_prev = torch.empty_like(m_prev) if ctx.eres else None
-        coord_live = bool(flags & _lib.UPDATE_COORDS) and g_x_out is not None
-        live = {
-            'coord_w1': coord_live, 'coord_b1': coord_live, 'coord_w2': coord_live,
-            'edge_gate': ctx.eres and bool(flags & (_lib.REZERO | _lib.GATED_RESIDUAL)),
-        }
-        grads = []
-        for name, p in zip(_lib.PARAM_FIELDS, params):
-            if p is None or not live.get(name, True):
-                grads.append(None)
-            else:
-                grads.append(torch.empty_like(p))
-        gstruct = _lib.PvsLayerGrads(*[_lib.ptr(g) for g in grads])
-        ws_bytes = lib.pvs_egnn_layer_workspace_bytes(C.byref(desc), n, e, 1)
+        dead = dead_grads(flags, g_x_out is not None, ctx.eres)
+        grads = [None if (p is None or name in dead) else torch.empty_like(p)
+                 for name, p in zip(_lib.PARAM_FIELDS, params)]
+        gstruct = kind.grads_t(*[_lib.ptr(g) for g in grads])
+        ws_bytes = kind.layer_ws(C.byref(desc), n, e, 1)
         ws = _ws(ws_bytes, dev)
-        rc = lib.pvs_egnn_layer_bwd(
+        rc = kind.layer_bwd(
             C.byref(desc), C.byref(pg.c), C.byref(pstruct), _lib.ptr(h), _lib.ptr(x),
             _lib.ptr(m_prev), _lib.ptr(att), _lib.ptr(saved), _lib.ptr(g_h_out), _lib.ptr(g_x_out),
             _lib.ptr(g_m_out), _lib.ptr(g_h), _lib.ptr(g_x), _lib.ptr(g_m_prev), C.byref(gstruct),
             _lib.ptr(ws), ws_bytes, _stream(dev))
-        _lib.check(rc, 'pvs_egnn_layer_bwd')
-        return (g_h, g_x, g_m_prev, None, None, None, None, *grads)
-
-
-class _EGNNLayerF64Fn(torch.autograd.Function):
-    """The fp64 layer (pvs_egnn_layer_fwd_f64 / _bwd_f64): same contract as _EGNNLayerFn, double tensors."""
-
-    @staticmethod
-    def forward(ctx, h, x, m_prev, pg, desc_tuple, need_m, pstruct, *params):
-        lib = _lib.lib()
-        hidden, n_attr, flags, act = desc_tuple
-        h, x, m_prev = h.contiguous(), x.contiguous(), None if m_prev is None else m_prev.contiguous()
-        if pstruct is None:
-            params = tuple(None if p is None else p.contiguous() for p in params)
-            _lib.require_hip(h, x, m_prev, *params)
-            pstruct = _lib.PvsLayerParamsF64(*[_lib.ptr(p) for p in params])
-        else:
-            _lib.require_hip(h, x, m_prev)
-        dev = h.device
-        n, e = pg.n_nodes, pg.n_edges
-        if h.shape != (n, hidden) or x.shape != (n, 3):
-            raise ValueError(f'h {tuple(h.shape)} / coord {tuple(x.shape)} do not match N={n}, H={hidden}')
-        if n_attr != pg.n_edge_attr:
-            raise ValueError(f'layer built with edges_in_d={n_attr} but edge_attr has {pg.n_edge_attr} columns')
-        desc = _lib.PvsLayerDesc(hidden, n_attr, flags, act)
-        eres = bool(flags & _lib.EDGE_RESIDUAL) and m_prev is not None
-        f64 = dict(dtype=_F64, device=dev)
-        h_out, x_out = torch.empty_like(h), torch.empty_like(x)
-        m_out = torch.empty((max(e, 0), hidden), **f64) if need_m else None
-        att = torch.empty((max(e, 1),), **f64) if flags & _lib.EDGE_ATTENTION else None
-        node_att = torch.empty((n,), **f64) if flags & _lib.NODE_ATTENTION else None
-        saved = torch.empty(lib.pvs_egnn_layer_saved_doubles_f64(C.byref(desc), n, e), **f64)
-        ws_bytes = lib.pvs_egnn_layer_workspace_bytes_f64(C.byref(desc), n, e, 0)
-        ws = _ws(ws_bytes, dev)
-        _lib.check(lib.pvs_egnn_layer_fwd_f64(
-            C.byref(desc), C.byref(pg.c), C.byref(pstruct), _lib.ptr(h), _lib.ptr(x),
-            _lib.ptr(m_prev if eres else None), _lib.ptr(h_out), _lib.ptr(x_out), _lib.ptr(m_out),
-            _lib.ptr(att), _lib.ptr(node_att), _lib.ptr(saved), _lib.ptr(ws), ws_bytes, _stream(dev)),
-            'pvs_egnn_layer_fwd_f64')
-        ctx.pg, ctx.desc_tuple, ctx.eres, ctx.pstruct = pg, desc_tuple, eres, pstruct
-        ctx.save_for_backward(h, x, m_prev if eres else None, att, saved, *params)
-        ctx.set_materialize_grads(False)
-        if att is not None or node_att is not None:
-            ctx.mark_non_differentiable(*[t for t in (att, node_att) if t is not None])
-        return h_out, x_out, m_out, att, node_att
-
-    @staticmethod
-    def backward(ctx, g_h_out, g_x_out, g_m_out, _g_att, _g_natt):
-        lib = _lib.lib()
-        h, x, m_prev, att, saved, *params = ctx.saved_tensors
-        pg = ctx.pg
-        hidden, n_attr, flags, act = ctx.desc_tuple
-        dev = h.device
-        n, e = pg.n_nodes, pg.n_edges
-        desc = _lib.PvsLayerDesc(hidden, n_attr, flags, act)
-        g_h_out = torch.zeros_like(h) if g_h_out is None else _fc(g_h_out, _F64)
-        g_x_out = _fc(g_x_out, _F64)
-        g_m_out = _fc(g_m_out, _F64) if (g_m_out is not None and g_m_out.numel()) else None
-        g_h = torch.empty_like(h)
-        g_x = torch.empty_like(x) if ctx.needs_input_grad[1] else None
-        g_m_prev = torch.empty_like(m_prev) if ctx.eres else None
-        coord_live = bool(flags & _lib.UPDATE_COORDS) and g_x_out is not None
-        live = {'coord_w1': coord_live, 'coord_b1': coord_live, 'coord_w2': coord_live,
-                'edge_gate': ctx.eres and bool(flags & (_lib.REZERO | _lib.GATED_RESIDUAL))}
-        grads = [None if (p is None or not live.get(name, True)) else torch.empty_like(p)
-                 for name, p in zip(_lib.PARAM_FIELDS, params)]
-        gstruct = _lib.PvsLayerGradsF64(*[_lib.ptr(g) for g in grads])
-        ws_bytes = lib.pvs_egnn_layer_workspace_bytes_f64(C.byref(desc), n, e, 1)
-        ws = _ws(ws_bytes, dev)
-        _lib.check(lib.pvs_egnn_layer_bwd_f64(
-            C.byref(desc), C.byref(pg.c), C.byref(ctx.pstruct), _lib.ptr(h), _lib.ptr(x),
-            _lib.ptr(m_prev), _lib.ptr(att), _lib.ptr(saved), _lib.ptr(g_h_out), _lib.ptr(g_x_out),
-            _lib.ptr(g_m_out), _lib.ptr(g_h), _lib.ptr(g_x), _lib.ptr(g_m_prev), C.byref(gstruct),
-            _lib.ptr(ws), ws_bytes, _stream(dev)), 'pvs_egnn_layer_bwd_f64')
-        return (g_h, g_x, g_m_prev, None, None, None, None, *grads)
+        kind.check(rc, 'layer_bwd')
+        return (None, g_h, g_x, g_m_prev, None, None, None, None, *grads)
 
 
 def egnn_layer(h, x, m_prev_sorted, pg, desc_tuple, need_m, params, pstruct=None):
     """Returns (h_out, x_out, m_sorted|None, att_sorted|None, node_att|None). pstruct: see _EGNNLayerFn.forward.
     fp64 (h float64, or a layer whose cached parameter struct is fp64) runs the fp64 kernels; mixed dtypes raise."""
-    if h.dtype == _F64 or isinstance(pstruct, _lib.PvsLayerParamsF64):
+    kind = _K32
+    if h.dtype == _F64 or isinstance(pstruct, _K64.params_t):
+        kind = _K64
         _call_dtype('EGNNLayer', h, coord=x, edge_messages=m_prev_sorted,
                     **{name: p for name, p in zip(_lib.PARAM_FIELDS, params)})
         if pg.c.n_edges_dev:
             raise NotImplementedError('fp64 layers need a graph with a host-known edge count')
-        return _EGNNLayerF64Fn.apply(h, x, m_prev_sorted, pg, desc_tuple, need_m, pstruct, *params)
-    if pstruct is None and params and params[0] is not None and params[0].dtype == _F64:
+    elif pstruct is None and params and params[0] is not None and params[0].dtype == _F64:
         _call_dtype('EGNNLayer', h, coord=x, **{name: p for name, p in zip(_lib.PARAM_FIELDS, params)})
-    return _EGNNLayerFn.apply(h, x, m_prev_sorted, pg, desc_tuple, need_m, pstruct, *params)
+    return _EGNNLayerFn.apply(kind, h, x, m_prev_sorted, pg, desc_tuple, need_m, pstruct, *params)
 
 
 def _align(count, to=64):
@@ -279,7 +257,7 @@ class StackPlan:
         self.n_layers, self.hidden = n, desc_tuples[0][0]
         self.desc_tuples, self.pstructs = tuple(desc_tuples), tuple(pstructs)
         self.descs = (_lib.PvsLayerDesc * n)(*[_lib.PvsLayerDesc(*d) for d in desc_tuples])
-        self.params_c = (_lib.PvsLayerParams * n)(*pstructs)       # (copies of the structs: plain pointers)
+        self.params_c = (STACK_KIND.params_t * n)(*pstructs)       # (copies of the structs: plain pointers)
         self.any_eatt = any(d[2] & _lib.EDGE_ATTENTION for d in desc_tuples)
         self.any_natt = any(d[2] & _lib.NODE_ATTENTION for d in desc_tuples)
         self.index, flat = [], []
@@ -292,9 +270,9 @@ class StackPlan:
         self._sizes, self._layouts = {}, {}
 
     def grad_layout(self, last_coords_live):
-        """Where every parameter gradient of a backward sits in ONE flat buffer. Which gradients exist follows
-        _EGNNLayerFn.backward: a layer's coord_mlp only when its coordinates fed something (every layer but the last; the
-        last one when a gradient arrives for x_L), never the edge gate (no edge residual in a stack)."""
+        """Where every parameter gradient of a backward sits in ONE flat buffer. Which gradients exist is `dead_grads`, as
+        in _EGNNLayerFn.backward: a layer's coordinates fed something in every layer but the last, and in the last one
+        when a gradient arrives for x_L; a stack has no edge residual."""
         got = self._layouts.get(last_coords_live)
         if got is None:
             got = self._layouts[last_coords_live] = _GradLayout(self, last_coords_live)
@@ -305,7 +283,7 @@ class StackPlan:
         got = self._sizes.get((n, e))
         if got is None:
             lib = _lib.lib()
-            saved = lib.pvs_egnn_layer_saved_floats(self.descs, n, e)
+            saved = STACK_KIND.layer_saved(self.descs, n, e)
             st = _lib.PvsStackStrides(_align(n * self.hidden), _align(3 * n), _align(max(e, 1)), _align(n), _align(saved))
             got = (st, lib.pvs_egnn_stack_workspace_bytes(self.descs, self.n_layers, n, e, 0),
                    lib.pvs_egnn_stack_workspace_bytes(self.descs, self.n_layers, n, e, 1))
@@ -325,14 +303,9 @@ class _GradLayout:
         fields, nl = _lib.PARAM_FIELDS, plan.n_layers
         self.sizes, self.take, self._offsets, self._by_base = [], [], [], {}
         off = 0
+        dead = [dead_grads(d[2], layer < nl - 1 or last_coords_live, False) for layer, d in enumerate(plan.desc_tuples)]
         for (layer, slot), p in zip(plan.index, plan.params):
-            name = fields[slot]
-            on = True
-            if name in ('coord_w1', 'coord_b1', 'coord_w2'):
-                on = bool(plan.desc_tuples[layer][2] & _lib.UPDATE_COORDS) and (layer < nl - 1 or last_coords_live)
-            elif name == 'edge_gate':
-                on = False
-            if not on:
+            if fields[slot] in dead[layer]:
                 self.take.append((-1, None))
                 continue
             k = p.numel()
@@ -351,7 +324,7 @@ class _GradLayout:
             rows = [[None] * self.n_fields for _ in range(self.n_layers)]
             for layer, slot, byte_off in self._offsets:
                 rows[layer][slot] = base + byte_off
-            got = (_lib.PvsLayerGrads * self.n_layers)(*[_lib.PvsLayerGrads(*r) for r in rows])
+            got = (STACK_KIND.grads_t * self.n_layers)(*[STACK_KIND.grads_t(*r) for r in rows])
             if len(self._by_base) > 32:
                 self._by_base.clear()
             self._by_base[base] = got
@@ -366,7 +339,7 @@ class _EGNNStackFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, h0, x0, pg, plan, *params):
         lib = _lib.lib()
-        h0, x0 = _f32c(h0), _f32c(x0)
+        h0, x0 = _c(h0, _F32, _FP32_ONLY), _c(x0, _F32, _FP32_ONLY)
         _lib.require_hip(h0, x0)
         n, e, hidden, nl = pg.n_nodes, pg.n_edges, plan.hidden, plan.n_layers
         if h0.shape != (n, hidden) or x0.shape != (n, 3):
@@ -401,8 +374,8 @@ class _EGNNStackFn(torch.autograd.Function):
         pg, plan = ctx.pg, ctx.plan
         n, e, nl = pg.n_nodes, pg.n_edges, plan.n_layers
         dev = h0.device
-        g_h_out = torch.zeros_like(h0) if g_h_out is None else _f32c(g_h_out)
-        g_x_out = _f32c(g_x_out)        # None => nothing read the last layer's coordinates
+        g_h_out = torch.zeros_like(h0) if g_h_out is None else _c(g_h_out, _F32, _FP32_ONLY)
+        g_x_out = _c(g_x_out, _F32, _FP32_ONLY)        # None => nothing read the last layer's coordinates
         g_h0 = torch.empty_like(h0)
         g_x0 = torch.empty_like(x0) if ctx.needs_input_grad[1] else None
         # ONE allocation for all parameter gradients, handed out as views (16-byte aligned): 78 allocations less per step
@@ -434,63 +407,33 @@ class _LinearFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w, b):
-        if x.dtype == _F64:
-            _call_dtype('linear', x, weight=w, bias=b)
-            x, w, b = _fc(x, _F64), _fc(w, _F64), _fc(b, _F64)
-            _lib.require_hip(x, w, b)
-            n, k = x.shape
-            c = w.shape[0]
-            y = torch.empty((n, c), dtype=_F64, device=x.device)
-            _lib.check(_lib.lib().pvs_linear_fwd_f64(_lib.ptr(x), _lib.ptr(w), _lib.ptr(b), _lib.ptr(y),
-                                                     n, k, c, _stream(x.device)), 'pvs_linear_fwd_f64')
-            ctx.save_for_backward(x, w)
-            ctx.has_bias = b is not None
-            return y
-        if w.dtype != torch.float32 or (b is not None and b.dtype != torch.float32):
-            _call_dtype('linear', x, weight=w, bias=b)
-        x, w, b = _f32c(x), _f32c(w), _f32c(b)
+        kind = _kind_of('linear', x)
+        dtype = kind.dtype
+        x, w, b = _c(x, dtype), _c(w, dtype), _c(b, dtype)
         _lib.require_hip(x, w, b)
         n, k = x.shape
         c = w.shape[0]
-        y = torch.empty((n, c), dtype=torch.float32, device=x.device)
-        _lib.check(_lib.lib().pvs_linear_fwd(_lib.ptr(x), _lib.ptr(w), _lib.ptr(b), _lib.ptr(y),
-                                             n, k, c, _stream(x.device)), 'pvs_linear_fwd')
+        y = torch.empty((n, c), dtype=dtype, device=x.device)
+        kind.check(kind.linear_fwd(_lib.ptr(x), _lib.ptr(w), _lib.ptr(b), _lib.ptr(y), n, k, c, _stream(x.device)),
+                   'linear_fwd')
         ctx.save_for_backward(x, w)
-        ctx.has_bias = b is not None
+        ctx.has_bias, ctx.kind = b is not None, kind
         return y
 
     @staticmethod
     def backward(ctx, g_y):
         x, w = ctx.saved_tensors
-        if x.dtype == _F64:
-            return _LinearFn._backward_f64(ctx, x, w, _fc(g_y, _F64))
-        g_y = _f32c(g_y)
+        kind = ctx.kind
+        g_y = _c(g_y, kind.dtype)
         n, k = x.shape
         c = w.shape[0]
-        lib = _lib.lib()
         g_x = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         g_w = torch.empty_like(w)
-        g_b = torch.empty((c,), dtype=torch.float32, device=x.device) if ctx.has_bias else None
-        ws_bytes = lib.pvs_linear_bwd_workspace_bytes(n, k, c)
+        g_b = torch.empty((c,), dtype=kind.dtype, device=x.device) if ctx.has_bias else None
+        ws_bytes = kind.linear_bwd_ws(n, k, c)
         ws = _ws(ws_bytes, x.device)
-        _lib.check(lib.pvs_linear_bwd(_lib.ptr(x), _lib.ptr(w), _lib.ptr(g_y), _lib.ptr(g_x),
-                                      _lib.ptr(g_w), _lib.ptr(g_b), n, k, c, _lib.ptr(ws), ws_bytes,
-                                      _stream(x.device)), 'pvs_linear_bwd')
-        return g_x, g_w, g_b
-
-    @staticmethod
-    def _backward_f64(ctx, x, w, g_y):
-        n, k = x.shape
-        c = w.shape[0]
-        lib = _lib.lib()
-        g_x = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        g_w = torch.empty_like(w)
-        g_b = torch.empty((c,), dtype=_F64, device=x.device) if ctx.has_bias else None
-        ws_bytes = lib.pvs_linear_bwd_workspace_bytes_f64(n, k, c)
-        ws = _ws(ws_bytes, x.device)
-        _lib.check(lib.pvs_linear_bwd_f64(_lib.ptr(x), _lib.ptr(w), _lib.ptr(g_y), _lib.ptr(g_x), _lib.ptr(g_w),
-                                          _lib.ptr(g_b), n, k, c, _lib.ptr(ws), ws_bytes, _stream(x.device)),
-                   'pvs_linear_bwd_f64')
+        kind.check(kind.linear_bwd(_lib.ptr(x), _lib.ptr(w), _lib.ptr(g_y), _lib.ptr(g_x), _lib.ptr(g_w), _lib.ptr(g_b),
+                                   n, k, c, _lib.ptr(ws), ws_bytes, _stream(x.device)), 'linear_bwd')
         return g_x, g_w, g_b
 
 
@@ -505,40 +448,24 @@ class _MeanPoolFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, h, graph_ptr):
-        if h.dtype == _F64:
-            h = _fc(h, _F64)
-            _lib.require_hip(h, graph_ptr)
-            b = graph_ptr.numel() - 1
-            pooled = torch.empty((b, h.shape[1]), dtype=_F64, device=h.device)
-            _lib.check(_lib.lib().pvs_mean_pool_fwd_f64(_lib.ptr(h), _lib.ptr(graph_ptr), _lib.ptr(pooled),
-                                                        b, h.shape[1], _stream(h.device)), 'pvs_mean_pool_fwd_f64')
-            ctx.graph_ptr, ctx.n = graph_ptr, h.shape[0]
-            return pooled
-        h = _f32c(h)
+        kind = _kind_of('mean_pool', h)
+        h = h.contiguous()
         _lib.require_hip(h, graph_ptr)
         b = graph_ptr.numel() - 1
-        pooled = torch.empty((b, h.shape[1]), dtype=torch.float32, device=h.device)
-        _lib.check(_lib.lib().pvs_mean_pool_fwd(_lib.ptr(h), _lib.ptr(graph_ptr), _lib.ptr(pooled),
-                                                b, h.shape[1], _stream(h.device)),
-                   'pvs_mean_pool_fwd')
-        ctx.graph_ptr, ctx.n = graph_ptr, h.shape[0]
+        pooled = torch.empty((b, h.shape[1]), dtype=kind.dtype, device=h.device)
+        kind.check(kind.mean_pool_fwd(_lib.ptr(h), _lib.ptr(graph_ptr), _lib.ptr(pooled), b, h.shape[1],
+                                      _stream(h.device)), 'mean_pool_fwd')
+        ctx.graph_ptr, ctx.n, ctx.kind = graph_ptr, h.shape[0], kind
         return pooled
 
     @staticmethod
     def backward(ctx, g):
-        if g.dtype == _F64:
-            g = _fc(g, _F64)
-            b, width = g.shape
-            g_h = torch.empty((ctx.n, width), dtype=_F64, device=g.device)
-            _lib.check(_lib.lib().pvs_mean_pool_bwd_f64(_lib.ptr(g), _lib.ptr(ctx.graph_ptr), _lib.ptr(g_h),
-                                                        b, ctx.n, width, _stream(g.device)), 'pvs_mean_pool_bwd_f64')
-            return g_h, None
-        g = _f32c(g)
+        kind = ctx.kind
+        g = _c(g, kind.dtype)
         b, width = g.shape
-        g_h = torch.empty((ctx.n, width), dtype=torch.float32, device=g.device)
-        _lib.check(_lib.lib().pvs_mean_pool_bwd(_lib.ptr(g), _lib.ptr(ctx.graph_ptr), _lib.ptr(g_h),
-                                                b, ctx.n, width, _stream(g.device)),
-                   'pvs_mean_pool_bwd')
+        g_h = torch.empty((ctx.n, width), dtype=kind.dtype, device=g.device)
+        kind.check(kind.mean_pool_bwd(_lib.ptr(g), _lib.ptr(ctx.graph_ptr), _lib.ptr(g_h), b, ctx.n, width,
+                                      _stream(g.device)), 'mean_pool_bwd')
         return g_h, None
 
 
@@ -554,7 +481,7 @@ class _PoolHeadFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, h, graph_ptr, w, b):
-        h, w, b = _f32c(h), _f32c(w), _f32c(b)
+        h, w, b = _c(h, _F32, _FP32_ONLY), _c(w, _F32, _FP32_ONLY), _c(b, _F32, _FP32_ONLY)
         _lib.require_hip(h, graph_ptr, w, b)
         n_graphs, width, n_out = graph_ptr.numel() - 1, h.shape[1], w.shape[0]
         pooled = torch.empty((n_graphs, width), dtype=torch.float32, device=h.device)
@@ -569,7 +496,7 @@ class _PoolHeadFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_y):
         pooled, w = ctx.saved_tensors
-        g_y = _f32c(g_y)
+        g_y = _c(g_y, _F32, _FP32_ONLY)
         n_graphs, width = pooled.shape
         n_out = w.shape[0]
         dev = g_y.device
@@ -596,7 +523,7 @@ class _BceLogitsMeanFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, target):
         shape = x.shape
-        x, target = _f32c(x).reshape(-1), _f32c(target).reshape(-1)
+        x, target = _c(x, _F32, _FP32_ONLY).reshape(-1), _c(target, _F32, _FP32_ONLY).reshape(-1)
         _lib.require_hip(x, target)
         n = x.numel()
         loss = torch.empty((), dtype=torch.float32, device=x.device)
@@ -615,7 +542,7 @@ class _BceLogitsMeanFn(torch.autograd.Function):
             # constant 1, so the factor saved by the forward IS the gradient - no scaling launch (and autograd did not
             # have to fill a ones tensor either)
             return grad.reshape(ctx.shape), None
-        g_loss = _f32c(g_loss)
+        g_loss = _c(g_loss, _F32, _FP32_ONLY)
         out = torch.empty_like(grad)
         _lib.check(_lib.lib().pvs_scale_by_device_scalar(_lib.ptr(grad), _lib.ptr(g_loss), grad.numel(), _lib.ptr(out),
                                                          _stream(grad.device)), 'pvs_scale_by_device_scalar')
@@ -692,37 +619,26 @@ class _SegmentReduceFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, data, segment_ids, num_segments, mean):
-        f64 = data.dtype == _F64
-        data = _fc(data, _F64) if f64 else _f32c(data)
+        kind = _kind_of('segment_reduce', data)
+        data = data.contiguous()
         _lib.require_hip(data, segment_ids)
-        lib = _lib.lib()
-        ctx.f64 = f64
         ids = segment_ids.long().contiguous()
         e, c = data.shape
         dev = data.device
         capturing = torch.cuda.is_current_stream_capturing()
         if not capturing:
             _SegmentStatus.poll()           # an earlier call's out-of-range ids raise here
-        out = torch.empty((num_segments, c), dtype=data.dtype, device=dev)
+        out = torch.empty((num_segments, c), dtype=kind.dtype, device=dev)
         ptr = torch.empty(num_segments + 1, dtype=torch.int32, device=dev)
         status = torch.empty(1, dtype=torch.int32, device=dev)
-        if f64:
-            ws_bytes = lib.pvs_segment_workspace_bytes_f64(e, num_segments)
-            ws = _ws(ws_bytes, dev)
-            _lib.check(lib.pvs_segment_reduce_fwd_f64(
-                _lib.ptr(data), _lib.ptr(ids), e, c, num_segments, 1 if mean else 0, _lib.ptr(out),
-                _lib.ptr(ptr), _lib.ptr(status), _lib.ptr(ws), ws_bytes, _stream(dev)),
-                'pvs_segment_reduce_fwd_f64')
-        else:
-            ws_bytes = lib.pvs_segment_workspace_bytes(e, num_segments)
-            ws = _ws(ws_bytes, dev)
-            _lib.check(lib.pvs_segment_reduce_fwd(
-                _lib.ptr(data), _lib.ptr(ids), e, c, num_segments, 1 if mean else 0, _lib.ptr(out),
-                _lib.ptr(ptr), _lib.ptr(status), _lib.ptr(ws), ws_bytes, _stream(dev)),
-                'pvs_segment_reduce_fwd')
+        ws_bytes = kind.segment_ws(e, num_segments)
+        ws = _ws(ws_bytes, dev)
+        kind.check(kind.segment_fwd(
+            _lib.ptr(data), _lib.ptr(ids), e, c, num_segments, 1 if mean else 0, _lib.ptr(out),
+            _lib.ptr(ptr), _lib.ptr(status), _lib.ptr(ws), ws_bytes, _stream(dev)), 'segment_fwd')
         ctx.status = None if capturing else _SegmentStatus(status)      # (no host-visible validation inside a capture)
         ctx.save_for_backward(ids, ptr)
-        ctx.mean, ctx.shape, ctx.n_segments = mean, (e, c), num_segments
+        ctx.mean, ctx.shape, ctx.n_segments, ctx.kind = mean, (e, c), num_segments, kind
         return out
 
     @staticmethod
@@ -731,18 +647,12 @@ class _SegmentReduceFn(torch.autograd.Function):
         if ctx.status is not None and not torch.cuda.is_current_stream_capturing():
             ctx.status.settle(wait=True)
         e, c = ctx.shape
-        if ctx.f64:
-            g_out = _fc(g_out, _F64)
-            g_data = torch.empty((e, c), dtype=_F64, device=g_out.device)
-            _lib.check(_lib.lib().pvs_segment_reduce_bwd_f64(
-                _lib.ptr(g_out), _lib.ptr(ids), _lib.ptr(ptr), e, c, ctx.n_segments, 1 if ctx.mean else 0,
-                _lib.ptr(g_data), _stream(g_out.device)), 'pvs_segment_reduce_bwd_f64')
-            return g_data, None, None, None
-        g_out = _f32c(g_out)
-        g_data = torch.empty((e, c), dtype=torch.float32, device=g_out.device)
-        _lib.check(_lib.lib().pvs_segment_reduce_bwd(
+        kind = ctx.kind
+        g_out = _c(g_out, kind.dtype)
+        g_data = torch.empty((e, c), dtype=kind.dtype, device=g_out.device)
+        kind.check(kind.segment_bwd(
             _lib.ptr(g_out), _lib.ptr(ids), _lib.ptr(ptr), e, c, ctx.n_segments, 1 if ctx.mean else 0,
-            _lib.ptr(g_data), _stream(g_out.device)), 'pvs_segment_reduce_bwd')
+            _lib.ptr(g_data), _stream(g_out.device)), 'segment_bwd')
         return g_data, None, None, None
 
 

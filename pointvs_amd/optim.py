@@ -19,6 +19,7 @@ class _PointerTables:
 
     _ROW = 5                # int64 columns of a table row
     _NAME = 'optimiser'
+    _KEY_FIELDS = ('dev',)  # what of a work item, besides its tensors' addresses, a remembered table depends on
 
     def _reset_transients(self):
         # pointer tables travel through a small ring of pinned buffers: a slot is only rewritten once
@@ -131,6 +132,59 @@ class _PointerTables:
         self._recent[key] = idx
         return table_dev
 
+    def _fused_work(self, closure, clip_value):
+        """The opening of step(): runs the closure, refreshes the plan and returns (loss, the plan, an iterator over the
+        address keys of its work items in order, whether the stream is being captured) - or (loss, None, None, None) when
+        the kernel does not cover this step, and then `_clip_and_torch_step` HAS RUN: the caller only returns the loss.
+        Host time counts (small batches are bound by it: tools/host_profile.py): the work list - which parameters have
+        gradients, their state tensors, the fusability verdict - is kept from step to step and re-derived only when the
+        set of parameters with gradients (or `_signature()`: the groups' flavour, or the state) changes; a pointer table
+        already on the device is found again by the (parameter, gradient) addresses alone."""
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        live = [p.grad is not None for group in self.param_groups for p in group['params']]
+        fast = self._fast
+        if fast is None or fast['live'] != live or fast['sig'] != self._signature():
+            fast = self._plan(live)
+        keys = self._address_keys(fast) if fast['fusable'] else None
+        # tensors at addresses not seen before are looked at (device, layout, sparsity) BEFORE anything is launched
+        if keys is None or any(self._recent.get(key) is None and not self._tensors_fusable(work)
+                               for work, key in zip([work for works in fast['groups'] for work in works], keys)):
+            self._clip_and_torch_step(clip_value)
+            return loss, None, None, None
+        capturing = torch.cuda.is_current_stream_capturing()
+        # (any capture skips the push - also that of a FusedClipSGD whose `capturable` was cleared after its blocks had been
+        # made: not a supported use; its step() used to raise from push_hyperparameters() there)
+        if self._hyper and not capturing:
+            self.push_hyperparameters()        # (a captured step reads what its caller pushes before each replay)
+        return loss, fast, iter(keys), capturing
+
+    def _address_keys(self, fast):
+        """Per work item the tuple of its `_KEY_FIELDS` and the (parameter, gradient) addresses of this step - what the
+        pointer table on the device is remembered by - or None when the fused kernel must not run: a group option it
+        does not cover switched on mid-run (`_groups_fusable`: amsgrad, maximize, ... or a tensor learning rate), or a
+        parameter / gradient that is not fp32 any more (`model.half()` / `.double()` after the first step: the kernel
+        takes raw pointers as fp32 device memory). What else can change under an unchanged plan (device, layout,
+        sparsity) is checked by `_tensors_fusable` whenever the addresses are new; tensors at addresses seen before ARE
+        the tensors that passed it."""
+        if not self._groups_fusable():
+            return None
+        f32 = torch.float32
+        keys = []
+        for works in fast['groups']:
+            for work in works:
+                key = [work[field] for field in self._KEY_FIELDS]
+                for p in work['params']:
+                    g = p.grad
+                    if p.dtype is not f32 or g.dtype is not f32:
+                        return None
+                    key.append(p.data_ptr())
+                    key.append(g.data_ptr())
+                keys.append(tuple(key))
+        return keys
+
     @staticmethod
     def _tensors_fusable(work):
         for p in work['params']:
@@ -160,12 +214,21 @@ class FusedClipAdam(_PointerTables, torch.optim.Adam):
     def _hyper_values(group):
         return (float(group['lr']), float(group['betas'][0]), float(group['betas'][1]))
 
-    def _fusable(self):
+    def _groups_fusable(self):
         for group in self.param_groups:
             if group.get('amsgrad') or group.get('maximize') \
                     or group.get('differentiable') or group.get('decoupled_weight_decay') \
                     or isinstance(group['lr'], torch.Tensor):
                 return False
+        return True
+
+    def _signature(self):
+        return [bool(g.get('capturable')) for g in self.param_groups]
+
+    def _fusable(self):
+        if not self._groups_fusable():
+            return False
+        for group in self.param_groups:
             for p in group['params']:
                 if p.grad is not None and (not p.is_cuda or p.dtype != torch.float32 or p.grad.is_sparse
                                            or not p.is_contiguous() or not p.grad.is_contiguous()):
@@ -194,34 +257,12 @@ class FusedClipAdam(_PointerTables, torch.optim.Adam):
 
     @torch.no_grad()
     def step(self, closure=None, clip_value=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        # Host time counts (small batches are bound by it: tools/host_profile.py): the work list - which parameters
-        # have gradients, their state tensors, their common step count, the fusability verdict - is kept from step to
-        # step and re-derived only when the set of parameters with gradients (or the groups, or the state) changes;
-        # the step counters (one 0-dim CPU tensor per parameter: torch's state_dict layout) are views of one tensor and
-        # advance with one add_; a pointer table already on the device is found again by the (parameter, gradient)
-        # addresses alone.
-        live = [p.grad is not None for group in self.param_groups for p in group['params']]
-        fast = getattr(self, '_fast', None)
-        capt = [bool(g.get('capturable')) for g in self.param_groups]
-        if fast is None or fast['live'] != live or fast['capt'] != capt:
-            fast = self._plan(live)
-        keys = self._address_keys(fast) if fast['fusable'] else None
-        if keys is None:
-            self._clip_and_torch_step(clip_value)
+        # (the step counters - one 0-dim CPU tensor per parameter: torch's state_dict layout - are views of one tensor and
+        # advance with one add_: `_plan`)
+        loss, fast, keys, stream_capturing = self._fused_work(closure, clip_value)
+        if fast is None:
             return loss
         lib = _lib.lib()
-        all_works = [work for works in fast['groups'] for work in works]
-        # tensors at addresses not seen before are looked at (device, layout, sparsity) BEFORE anything is launched
-        if any(self._recent.get(key) is None and not self._tensors_fusable(work) for work, key in zip(all_works, keys)):
-            self._clip_and_torch_step(clip_value)
-            return loss
-        if self._hyper and not torch.cuda.is_current_stream_capturing():
-            self.push_hyperparameters()        # (a captured step reads what its caller pushes before each replay)
-        keys = iter(keys)
         for gi, (group, works) in enumerate(zip(self.param_groups, fast['groups'])):
             beta1, beta2 = group['betas']
             for work in works:            # one launch per distinct step count (one, unless the gradient set changed mid-run)
@@ -232,7 +273,7 @@ class FusedClipAdam(_PointerTables, torch.optim.Adam):
                     torch._foreach_add_(work['steps'], 1)    # (capturable: one device launch)
                 work['step'] += 1
                 step, n, dev = work['step'], work['n'], work['dev']
-                capturing = work['on_device'] and torch.cuda.is_current_stream_capturing()
+                capturing = work['on_device'] and stream_capturing
                 if work['on_device'] and not capturing and self._capture_pool is None:
                     self.reserve_capture_tables(8)
                 table_dev = self._table(key, lambda: [[p.data_ptr(), p.grad.data_ptr(), ea.data_ptr(), es.data_ptr(), p.numel()]
@@ -260,8 +301,7 @@ class FusedClipAdam(_PointerTables, torch.optim.Adam):
         groups, fusable = [], self._fusable()
         self._recent = {}      # (remembered tables hold the OLD plan's state-tensor addresses: exp_avg / exp_avg_sq are not in the key)
         if not fusable:       # (torch's own step creates whatever state its flavour - capturable, amsgrad ... - needs)
-            self._fast = {'live': live, 'capt': [bool(g.get('capturable')) for g in self.param_groups], 'groups': [],
-                          'fusable': False}
+            self._fast = {'live': live, 'sig': self._signature(), 'groups': [], 'fusable': False}
             return self._fast
         for gi, group in enumerate(self.param_groups):
             by_step = {}
@@ -298,33 +338,8 @@ class FusedClipAdam(_PointerTables, torch.optim.Adam):
                               'steps_base': base,
                               'hyper': self._hyper_block(gi, members[0][0].device) if on_device else None})
             groups.append(works)
-        self._fast = {'live': live, 'capt': [bool(g.get('capturable')) for g in self.param_groups], 'groups': groups,
-                      'fusable': fusable}
+        self._fast = {'live': live, 'sig': self._signature(), 'groups': groups, 'fusable': fusable}
         return self._fast
-
-    def _address_keys(self, fast):
-        """Per work item the tuple of (parameter, gradient) addresses of this step - what the pointer table on the device
-        is remembered by - or None when the fused kernel must not run: a group option it does not cover switched on
-        mid-run (amsgrad, maximize, ... or a tensor learning rate), or a parameter / gradient that is not fp32 any more
-        (`model.half()` / `.double()` after the first step: the kernel takes raw pointers as fp32 device memory). What
-        else can change under an unchanged plan (device, layout, sparsity) is checked by `_tensors_fusable` whenever the
-        addresses are new; tensors at addresses seen before ARE the tensors that passed it."""
-        f32 = torch.float32
-        keys = []
-        for group, works in zip(self.param_groups, fast['groups']):
-            if group.get('amsgrad') or group.get('maximize') or group.get('differentiable') \
-                    or group.get('decoupled_weight_decay') or isinstance(group['lr'], torch.Tensor):
-                return None
-            for work in works:
-                key = [work['dev']]
-                for p in work['params']:
-                    g = p.grad
-                    if p.dtype is not f32 or g.dtype is not f32:
-                        return None
-                    key.append(p.data_ptr())
-                    key.append(g.data_ptr())
-                keys.append(tuple(key))
-        return keys
 
 
 class FusedClipSGD(_PointerTables, torch.optim.SGD):
@@ -340,6 +355,7 @@ class FusedClipSGD(_PointerTables, torch.optim.SGD):
 
     _ROW = 4
     _NAME = 'FusedClipSGD'
+    _KEY_FIELDS = ('dev', 'first')
 
     def __init__(self, params, capturable=False, **kwargs):
         super().__init__(params, **kwargs)
@@ -381,30 +397,12 @@ class FusedClipSGD(_PointerTables, torch.optim.SGD):
 
     @torch.no_grad()
     def step(self, closure=None, clip_value=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        # (the work list is kept from step to step, as FusedClipAdam keeps its own: see there)
-        live = [p.grad is not None for group in self.param_groups for p in group['params']]
-        fast = self._fast
-        if fast is None or fast['live'] != live or fast['sig'] != self._signature():
-            fast = self._plan(live)
-        keys = self._address_keys(fast) if fast['fusable'] else None
-        if keys is None:
-            self._clip_and_torch_step(clip_value)
+        loss, fast, keys, capturing = self._fused_work(closure, clip_value)
+        if fast is None:
             return loss
         lib = _lib.lib()
-        all_works = [work for works in fast['groups'] for work in works]
-        # tensors at addresses not seen before are looked at (device, layout, sparsity) BEFORE anything is launched
-        if any(self._recent.get(key) is None and not self._tensors_fusable(work) for work, key in zip(all_works, keys)):
-            self._clip_and_torch_step(clip_value)
-            return loss
-        capturing = self.capturable and torch.cuda.is_current_stream_capturing()
-        if self._hyper and not capturing:
-            self.push_hyperparameters()        # (a captured step reads what its caller pushes before each replay)
+        capturing = self.capturable and capturing
         clip = float(clip_value) if clip_value is not None else 0.0
-        keys = iter(keys)
         replan = False
         for group, works in zip(self.param_groups, fast['groups']):
             for work in works:            # one launch, or two while some parameters have no momentum history yet
@@ -469,22 +467,3 @@ class FusedClipSGD(_PointerTables, torch.optim.SGD):
             groups.append(works)
         self._fast = {'live': live, 'sig': self._signature(), 'groups': groups if fusable else [], 'fusable': fusable}
         return self._fast
-
-    def _address_keys(self, fast):
-        """Per work item the tuple of (parameter, gradient) addresses of this step - what the pointer table on the device
-        is remembered by - or None when the fused kernel must not run (FusedClipAdam._address_keys)."""
-        if not self._groups_fusable():
-            return None
-        f32 = torch.float32
-        keys = []
-        for works in fast['groups']:
-            for work in works:
-                key = [work['dev'], work['first']]
-                for p in work['params']:
-                    g = p.grad
-                    if p.dtype is not f32 or g.dtype is not f32:
-                        return None
-                    key.append(p.data_ptr())
-                    key.append(g.data_ptr())
-                keys.append(tuple(key))
-        return keys

@@ -44,3 +44,48 @@ def test_fp64_workspace_and_saved_sizes():
         bwd = lib.pvs_egnn_layer_workspace_bytes_f64(ctypes.byref(desc), n, e, 1)
         assert 2 * n * hidden * 8 < fwd < bwd
         assert bwd >= 5 * e * hidden * 8
+
+
+def test_both_dtype_kinds_name_the_same_operators():
+    """functional.KINDS: an operator added to one kind only, an entry that is not exported or not in the built library, or
+    an fp64 entry whose argument count differs from its fp32 twin's fails here, without a GPU."""
+    import ctypes
+    import torch
+    from pointvs_amd import _lib
+    from pointvs_amd import functional as PF
+    assert set(PF.KINDS) == {torch.float32, torch.float64}
+    k32, k64 = PF.KINDS[torch.float32], PF.KINDS[torch.float64]
+    assert (k32.dtype, k32.words, k64.dtype, k64.words) == (torch.float32, 1, torch.float64, 2)
+    assert list(k32.entry) == list(k64.entry) and len(k32.entry) >= 14
+    handle = ctypes.CDLL(str(_lib.LIB_PATH))
+    for kind in (k32, k64):
+        for op, symbol in kind.entry.items():
+            assert symbol in _lib.EXPORTED_SYMBOLS, (op, symbol)
+            assert hasattr(handle, symbol), (op, symbol)
+            assert getattr(kind, op).argtypes == _lib._PROTOTYPES[symbol][1], (op, symbol)      # (bound on first use)
+        for struct in (kind.params_t, kind.grads_t):
+            assert [f for f, _ in struct._fields_] == list(_lib.PARAM_FIELDS), struct
+    for op in k32.entry:
+        r32, a32 = _lib._PROTOTYPES[k32.entry[op]]
+        r64, a64 = _lib._PROTOTYPES[k64.entry[op]]
+        assert len(a32) == len(a64) and r32 is r64, op
+    assert set(k64.entry.values()) - set(k32.entry.values()) == set(F64_SYMBOLS)
+    assert (k32.params_t, k32.grads_t) == (_lib.PvsLayerParams, _lib.PvsLayerGrads)
+    assert (k64.params_t, k64.grads_t) == (_lib.PvsLayerParamsF64, _lib.PvsLayerGradsF64)
+    assert PF.STACK_KIND is k32
+    assert not hasattr(k32, 'no_such_operator')
+
+
+def test_dead_gradients_follow_one_rule():
+    """functional.dead_grads, the rule shared by _EGNNLayerFn.backward and the stack's _GradLayout."""
+    from pointvs_amd import _lib
+    from pointvs_amd.functional import dead_grads
+    coord = {'coord_w1', 'coord_b1', 'coord_w2'}
+    uc, rz, gr = _lib.UPDATE_COORDS, _lib.REZERO, _lib.GATED_RESIDUAL
+    assert set(dead_grads(uc, True, False)) == {'edge_gate'}
+    assert set(dead_grads(uc, False, False)) == coord | {'edge_gate'}
+    assert set(dead_grads(0, True, True)) == coord | {'edge_gate'}
+    assert set(dead_grads(uc | rz, True, True)) == set()
+    assert set(dead_grads(uc | gr, False, True)) == coord
+    assert set(dead_grads(uc | gr, True, False)) == {'edge_gate'}
+    assert set(dead_grads(rz | _lib.EDGE_RESIDUAL, True, True)) == coord

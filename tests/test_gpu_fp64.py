@@ -282,3 +282,77 @@ def test_point_vs_entry_trains_and_predicts_in_fp64(tmp_path):
     floats = [v for v in state['model_state_dict'].values() if v.is_floating_point()]
     assert floats and all(v.dtype == torch.float64 for v in floats)
     assert (tmp_path / 'run' / 'pose_predictions.txt').read_text().count('\n') == 12
+
+
+@pytest.mark.parametrize('call, other', [(torch.float32, torch.float64), (torch.float64, torch.float32)],
+                         ids=['f64_into_f32', 'f32_into_f64'])
+def test_each_operator_refuses_the_other_dtype_forward_and_backward(call, other, tmp_path):
+    """One wrapper per operator over functional.KINDS: a tensor of the `other` dtype in a `call`-dtype call is a TypeError
+    from the one contiguity-and-dtype helper, in the forward and - called directly, as autograd itself would cast the
+    gradient first - in every backward: never a launch on memory of the wrong width."""
+    from pointvs_amd import functional as PF
+    from pointvs_amd.graph import prepared_for
+    data = _graphs([(20, _random_graph(20, 0.3, 41))])
+    model = _model(dict(ALL_ON, k=16), save_path=tmp_path).to(call)
+    feats, edges, coords, eattr, _ = model.unpack_graph(_batch_fn(*data)())
+    first, second = model.layers[1], model.layers[2]
+    h = model.layers[0].embed(feats, coords)
+    assert h.dtype == call and coords.dtype == call
+    h1, x1, _, m1 = first(h, edges, coords, edge_attr=eattr)
+    assert (h1.dtype, x1.dtype, m1.dtype) == (call, call, call)
+
+    def refused():
+        return pytest.raises(TypeError, match='mixed dtypes')
+
+    # forward: the layer's coordinates and previous messages, linear's weight and bias
+    with refused():
+        first(h, edges, coords.to(other), edge_attr=eattr)
+    with refused():
+        second(h1, edges, x1, edge_attr=eattr, edge_messages=m1.to(other))
+    gen = torch.Generator().manual_seed(5)
+    x = torch.randn(20, 8, generator=gen).to('cuda', call).requires_grad_()
+    w = torch.randn(8, 8, generator=gen).to('cuda', call).requires_grad_()
+    bias = torch.randn(8, generator=gen).to('cuda', call).requires_grad_()
+    with refused():
+        PF.linear(x, w.to(other))
+    with refused():
+        PF.linear(x, w, bias.to(other))
+    # either dtype is taken and returned
+    graph_ptr = torch.tensor([0, 7, 20], dtype=torch.int32, device='cuda')
+    ids = torch.randint(0, 5, (20,), generator=gen).cuda()
+    pg = prepared_for(edges, eattr, feats.size(0))
+    rows = torch.randn(edges.shape[1], 8, generator=gen).to('cuda', call).requires_grad_()
+    outs = {'linear': PF.linear(x, w, bias), 'mean_pool': PF.mean_pool(x, graph_ptr),
+            'segment_sum': PF.segment_reduce(x, ids, 5), 'segment_mean': PF.segment_reduce(x, ids, 5, mean=True),
+            'rows_to_sorted_order': PF.rows_to_sorted_order(rows, pg), 'rows_to_input_order': PF.rows_to_input_order(rows, pg)}
+    for name, y in outs.items():
+        assert y.dtype == call, name
+    assert torch.equal(PF.rows_to_input_order(outs['rows_to_sorted_order'], pg), rows)
+    # fp32 only
+    if call == torch.float64:
+        with pytest.raises(TypeError, match='fp32 only'):
+            PF.pool_head(x, graph_ptr, w, bias)
+        with pytest.raises(TypeError, match='fp32 only'):
+            PF.bce_with_logits_mean(x[:, 0], torch.ones(20, device='cuda', dtype=call))
+    else:
+        assert PF.pool_head(x, graph_ptr, w, bias).dtype == call
+        assert PF.bce_with_logits_mean(x[:, 0], torch.ones(20, device='cuda')).dtype == call
+        with pytest.raises(TypeError, match='fp32 only'):
+            PF.pool_head(x.to(other), graph_ptr, w, bias)
+        with pytest.raises(TypeError, match='fp32 only'):
+            PF.bce_with_logits_mean(x[:, 0].to(other), torch.ones(20, device='cuda', dtype=other))
+    # backward: a correct forward in `call`, its backward handed a gradient of `other`
+    for name, y in outs.items():
+        with refused():
+            y.grad_fn.apply(torch.ones_like(y, dtype=other))
+    node = h1.grad_fn                   # the layer's own node: (h_out, x_out, m_out, att, node_att)
+    assert type(node).__name__ == '_EGNNLayerFnBackward'
+    with refused():
+        node.apply(torch.ones_like(h1, dtype=other), None, None, None, None)
+    with refused():
+        node.apply(torch.ones_like(h1), torch.ones_like(x1, dtype=other), None, None, None)
+    # ... and the right dtype still runs, after all the refusals
+    g_in = node.apply(torch.ones_like(h1), None, None, None, None)
+    assert g_in[0] is None and g_in[1].dtype == call and g_in[1].shape == h.shape
+    g_x, g_w, g_b = outs['linear'].grad_fn.apply(torch.ones_like(outs['linear']))
+    assert (g_x.dtype, g_w.dtype, g_b.dtype) == (call, call, call)

@@ -7,7 +7,9 @@ small two-graph batch. Under a kernel trace, once per library and once more with
 Two libraries enqueue the same work when their OUT.txt files are equal (profiles/linear_job_refactor.txt).
 `--screening` traces instead one eager step of each screen (ReceptorScreen on the pose-batch builder and on the filter
 path, LibraryScreen) at a small shape (130-atom receptor, batch of 3): the record that a change of the screens'
-host code left every launch alone (profiles/screening_refactor.txt)."""
+host code left every launch alone (profiles/screening_refactor.txt). `--fp64` runs the loop of the default mode with model
+and batch in double (hidden 16 / 32 / 64, the per-layer path: there is no fp64 stack), for a change of the binding's
+fp64 side (profiles/functional_dtype_refactor.txt)."""
 import csv
 import glob
 import os
@@ -36,15 +38,17 @@ def parse(trace_dir, out_path):
     print(out_path, len(rows), 'launches')
 
 
-def run():
+def run(fp64=False):
     import torch
     from tests.test_gpu_properties import make_model, random_graph
     g = random_graph(300, 5000, seed=3, n_graphs=2).to('cuda')
-    for hidden in (16, 32, 64, 128):
+    for hidden in (16, 32, 64) if fp64 else (16, 32, 64, 128):
         for kw in FLAGS.values():
             model, _ = make_model(seed=5, k=hidden, num_layers=2, **kw)
             model.train()
-            for stack in ('0', '1'):
+            if fp64:
+                model.double()
+            for stack in ('0',) if fp64 else ('0', '1'):
                 os.environ['PVS_EGNN_STACK'] = stack
                 model.optimiser.zero_grad()
                 y = model(g).reshape(-1)
@@ -81,4 +85,4 @@ if __name__ == '__main__':
     elif sys.argv[1:] == ['--screening']:
         run_screening()
     else:
-        run()
+        run(fp64=sys.argv[1:] == ['--fp64'])
