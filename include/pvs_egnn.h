@@ -273,8 +273,9 @@ int pvs_graph_filter_ligand_edges(const PvsGraph* full, const uint8_t* bp, int32
 
 /* The radius graphs of B rigid poses of one ligand against one receptor without re-testing the
  * receptor-receptor pairs (they are pose independent: rr_rowptr [n_rec+1] / rr_col, receptor-local
- * ids, from pvs_radius_graph_* on the receptor alone). Node layout per pose: n_lig (<= 64) ligand
- * atoms first, then the n_rec receptor atoms; lig_pos [B,n_lig,3], rec_pos [n_rec,3]. Same edges,
+ * ids, from pvs_radius_graph_* on the receptor alone). Node layout per pose: n_lig (1..1024) ligand
+ * atoms first, then the n_rec receptor atoms; lig_pos [B,n_lig,3], rec_pos [n_rec,3]. A ligand atom's contacts
+ * with its own ligand are kept in ceil(n_lig / 64) mask words (the state grows by that much). Same edges,
  * classes and in-row order as generate_edges per pose. Outputs: the full CSR (rowptr [N+1], row,
  * col, etype with room for `capacity` edges, inv_deg [N]) and the CSR of its ligand-touching edges
  * (`_lig`), both with the edge count only on the device (rowptr[N]; pass it as PvsGraph.n_edges_dev:
@@ -303,7 +304,9 @@ int pvs_screen_graph_build(const float* lig_pos, const float* rec_pos, const int
  *     [N_cap,3], base_deg [N_cap] expanded from rec_magg / rec_xsum / rec_deg [n_rec,.] with zeros on ligand and
  *     padding rows (base_magg may be NULL: none of the three is written).
  *   *status: bit 2 = a capacity was too small (no edge is written then); bit 3 = lig_ptr is not such a table (the
- *     outputs then describe N_cap padding nodes and no edge). */
+ *     outputs then describe N_cap padding nodes and no edge).
+ * The _cap pair is the same builder for slots of 0..slot_cap atoms, slot_cap = 1..1024 (lig_cap <= slot_cap * n_slots;
+ * ceil(slot_cap / 64) ligand-ligand mask words per packed atom in the state); the pair without it is slot_cap = 64. */
 typedef struct {
     int32_t n_feats, hidden;
     const float *lig_feats, *rec_feats;
@@ -319,6 +322,16 @@ int pvs_screen_graph_build_ragged(const float* lig_pos, const int32_t* lig_ptr, 
                                   uint8_t* etype_lig, int32_t* node_ptr, int32_t* node_graph, float* pos,
                                   const PvsRaggedNodeTables* tables, int32_t* status, void* state,
                                   size_t state_bytes, pvs_stream_t stream);
+size_t pvs_screen_graph_ragged_cap_state_bytes(int32_t n_slots, int32_t lig_cap, int32_t n_rec, int32_t slot_cap);
+int pvs_screen_graph_build_ragged_cap(const float* lig_pos, const int32_t* lig_ptr, const float* rec_pos,
+                                      const int32_t* rr_rowptr, const int32_t* rr_col, int32_t n_slots,
+                                      int32_t lig_cap, int32_t n_rec, int32_t slot_cap, double inter_radius,
+                                      double intra_radius, int32_t capacity, int32_t capacity_lig, int32_t* rowptr,
+                                      int32_t* row, int32_t* col, uint8_t* etype, float* inv_deg,
+                                      int32_t* rowptr_lig, int32_t* row_lig, int32_t* col_lig, uint8_t* etype_lig,
+                                      int32_t* node_ptr, int32_t* node_graph, float* pos,
+                                      const PvsRaggedNodeTables* tables, int32_t* status, void* state,
+                                      size_t state_bytes, pvs_stream_t stream);
 
 /* Complex batches: the node tables of B protein-ligand complexes built from a device-resident pool of structure
  * files, as the reference loader builds one sample on the host (data_loaders.py:259-309: ligand then receptor, crop of

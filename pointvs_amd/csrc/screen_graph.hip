@@ -8,7 +8,9 @@
 //   intra block: all pairs with 1e-7 < d < intra_radius: ligand-ligand and ligand-receptor (class 0),
 //                receptor-receptor (class 2, from the template)
 // Only the B * n_lig * n_rec ligand-receptor and B * n_lig^2 ligand-ligand distances are evaluated
-// (fp64, cdist operation order). Two CSRs come out, both with the edge count left on the device
+// (fp64, cdist operation order). A ligand has 1..1024 atoms: its ligand-ligand contacts are W = ceil(n_lig / 64) mask
+// words per atom, and every lane-per-ligand-atom step runs as W trips of the wave (one trip up to 64 atoms, the same
+// instructions as when one word was all there was). Two CSRs come out, both with the edge count left on the device
 // (their rowptr[N]; PvsGraph.n_edges_dev): the full graph, and its ligand-touching edges only (what
 // the first layer runs over when the receptor-receptor sums are cached, pvs_egnn_layer_fwd_partial).
 #include "common.h"
@@ -22,6 +24,7 @@ namespace {
 typedef unsigned long long u64;
 
 // wave per packed ligand atom q: contact masks against the receptor (64 atoms per word) and the atom's own ligand
+// (W words per atom; trip w, lane l: the slot's atom 64 w + l)
 template <class Slots>
 __global__ void __launch_bounds__(256)
 k_contacts(const float* __restrict__ lig_pos, const float* __restrict__ rec_pos, Slots L, Radius r_inter,
@@ -52,14 +55,18 @@ k_contacts(const float* __restrict__ lig_pos, const float* __restrict__ rec_pos,
             m_intra[(size_t)q * n_chunks + c] = ba;
         }
     }
-    bool ell = false;
-    if (lane < slot.n_lig) {
-        const float* lb = lig_pos + (size_t)(slot.a0 + lane) * 3;
-        const double s = pvs_sqdist(xa, ya, za, (double)lb[0], (double)lb[1], (double)lb[2]);
-        ell = above(s, r_zero) && below(s, r_intra);
+    const int W = L.words();
+    for (int w = 0; w < W; ++w) {
+        const int b = 64 * w + lane;
+        bool ell = false;
+        if (b < slot.n_lig) {
+            const float* lb = lig_pos + (size_t)(slot.a0 + b) * 3;
+            const double s = pvs_sqdist(xa, ya, za, (double)lb[0], (double)lb[1], (double)lb[2]);
+            ell = above(s, r_zero) && below(s, r_intra);
+        }
+        const u64 bl = __ballot(ell);
+        if (lane == 0) m_ll[(size_t)q * W + w] = bl;
     }
-    const u64 bl = __ballot(ell);
-    if (lane == 0) m_ll[q] = bl;
 }
 
 __device__ __forceinline__ int row_popc(const u64* __restrict__ m, int n_chunks) {
@@ -68,7 +75,8 @@ __device__ __forceinline__ int row_popc(const u64* __restrict__ m, int n_chunks)
     return c;
 }
 
-// thread per row (and one past the end): degree in the full graph and in the ligand-touching subgraph
+// thread per row (and one past the end): degree in the full graph and in the ligand-touching subgraph (a receptor
+// row walks the slot's ligand atoms one by one: linear in n_lig)
 template <class Slots>
 __global__ void k_degrees(const u64* __restrict__ m_inter, const u64* __restrict__ m_intra,
                           const u64* __restrict__ m_ll, const int32_t* __restrict__ rr_rowptr, Slots L,
@@ -81,7 +89,8 @@ __global__ void k_degrees(const u64* __restrict__ m_inter, const u64* __restrict
     const int n_chunks = (L.n_rec + 63) / 64;
     if (r.local < r.n_lig) {
         const size_t w = (size_t)r.a0 + r.local;
-        const int d = row_popc(m_inter + w * n_chunks, n_chunks) + __popcll(m_ll[w]) +
+        const int W = L.words();
+        const int d = row_popc(m_inter + w * n_chunks, n_chunks) + row_popc(m_ll + w * W, W) +
                       row_popc(m_intra + w * n_chunks, n_chunks);
         deg[g] = d;
         deg_l[g] = d;
@@ -126,7 +135,8 @@ k_fill(const u64* __restrict__ m_inter, const u64* __restrict__ m_intra, const u
         return;
     }
     const int n_lig = r.n_lig, node0 = r.node0;
-    const int n_chunks = (L.n_rec + 63) / 64;
+    const int n_chunks = (L.n_rec + 63) / 64, W = L.words();
+    const int trips = pvs_slot_words(n_lig);               // the words that this slot's atoms reach (<= W)
     const u64 lower = (1ull << lane) - 1ull;
     int pf = full.rowptr[g], pl = lig.rowptr[g];
     if (lane == 0) {
@@ -146,10 +156,11 @@ k_fill(const u64* __restrict__ m_inter, const u64* __restrict__ m_intra, const u
         const size_t w = (size_t)r.a0 + r.local;
         expand_words(m_inter + w * n_chunks, node0 + n_lig, 1);             // inter block: receptor atoms
         {                                                                     // intra block: ligand atoms ...
-            const u64 mll = m_ll[w];
-            const bool on = (mll >> lane) & 1ull;
-            if (on) emit(__popcll(mll & lower), node0 + lane, 0, true);
-            const int c = __popcll(mll);
+            const u64* mll = m_ll + w * W;
+            for (int t = 0; t < trips; ++t) {
+                if ((mll[t] >> lane) & 1ull) emit(pvs_mask_rank(mll, t, lane), node0 + 64 * t + lane, 0, true);
+            }
+            const int c = row_popc(mll, W);
             pf += c; pl += c;
         }
         expand_words(m_intra + w * n_chunks, node0 + n_lig, 0);              // ... then receptor atoms
@@ -158,10 +169,14 @@ k_fill(const u64* __restrict__ m_inter, const u64* __restrict__ m_intra, const u
         const u64 bit = 1ull << (i & 63);
         for (int kind = 0; kind < 2; ++kind) {                                // inter block, then intra: ligand atoms
             const u64* m = kind == 0 ? m_inter : m_intra;
-            const bool on = lane < n_lig && (m[((size_t)r.a0 + lane) * n_chunks + c] & bit);
-            const u64 b = __ballot(on);
-            if (on) emit(__popcll(b & lower), node0 + lane, kind == 0 ? 1 : 0, true);
-            const int cnt = __popcll(b);
+            int cnt = 0;
+            for (int t = 0; t < trips; ++t) {                                 // (trip t: the slot's atoms 64 t ..)
+                const int a = 64 * t + lane;
+                const bool on = a < n_lig && (m[((size_t)r.a0 + a) * n_chunks + c] & bit);
+                const u64 b = __ballot(on);
+                if (on) emit(cnt + __popcll(b & lower), node0 + a, kind == 0 ? 1 : 0, true);
+                cnt += __popcll(b);
+            }
             pf += cnt; pl += cnt;
         }
         const int r0 = rr_rowptr[i], r1 = rr_rowptr[i + 1];                   // intra block: receptor atoms
@@ -169,7 +184,8 @@ k_fill(const u64* __restrict__ m_inter, const u64* __restrict__ m_intra, const u
     }
 }
 
-// the builder's scratch: contact masks per packed atom, degrees per row; slot_of (atom -> slot) for the ragged layout
+// the builder's scratch: contact masks per packed atom (n_chunks receptor words each, `words` ligand words), degrees
+// per row; slot_of (atom -> slot) for the ragged layout
 struct ScreenState {
     u64 *m_inter, *m_intra, *m_ll;
     int32_t *deg, *deg_l, *slot_of;
@@ -177,12 +193,12 @@ struct ScreenState {
     size_t scan_bytes;
 };
 
-size_t carve_screen(PvsArena& a, size_t atoms, int rows, int n_rec, bool ragged, ScreenState* out) {
+size_t carve_screen(PvsArena& a, size_t atoms, int rows, int n_rec, int words, bool ragged, ScreenState* out) {
     ScreenState t;
     const size_t n_chunks = (size_t)(n_rec + 63) / 64;
     t.m_inter = a.take<u64>(atoms * n_chunks);
     t.m_intra = a.take<u64>(atoms * n_chunks);
-    t.m_ll = a.take<u64>(atoms);
+    t.m_ll = a.take<u64>(atoms * (size_t)words);
     t.slot_of = ragged ? a.take<int32_t>(atoms) : nullptr;
     t.deg = a.take<int32_t>((size_t)rows + 1);
     t.deg_l = a.take<int32_t>((size_t)rows + 1);
@@ -221,7 +237,7 @@ int build_csrs(const Slots& L, const float* lig_pos, const float* rec_pos, const
 extern "C" size_t pvs_screen_graph_state_bytes(int32_t B, int32_t n_lig, int32_t n_rec) {
     PvsArena a(nullptr, 0);
     const PvsUniformSlots L{B, n_lig, n_rec};
-    return carve_screen(a, (size_t)L.atoms(), L.rows(), n_rec, false, nullptr) + 256;
+    return carve_screen(a, (size_t)L.atoms(), L.rows(), n_rec, L.words(), false, nullptr) + 256;
 }
 
 extern "C" int pvs_screen_graph_build(const float* lig_pos, const float* rec_pos, const int32_t* rr_rowptr,
@@ -234,12 +250,12 @@ extern "C" int pvs_screen_graph_build(const float* lig_pos, const float* rec_pos
     hipStream_t s = (hipStream_t)stream_;
     PVS_REQUIRE(lig_pos && rec_pos && rr_rowptr && rr_col && rowptr && row && col && etype && inv_deg &&
                 rowptr_lig && row_lig && col_lig && etype_lig && status && state, "pvs_screen_graph_build: NULL");
-    PVS_REQUIRE(B > 0 && n_lig > 0 && n_lig <= 64 && n_rec > 0, "pvs_screen_graph_build: needs 1..64 ligand atoms "
-                "(got %d) and a receptor", n_lig);
+    PVS_REQUIRE(B > 0 && n_lig > 0 && n_lig <= kPvsMaxSlotCap && n_rec > 0, "pvs_screen_graph_build: needs 1..%d "
+                "ligand atoms (n_lig: got %d) and a receptor", kPvsMaxSlotCap, n_lig);
     const PvsUniformSlots L{B, n_lig, n_rec};
     PvsArena arena(state, state_bytes);
     ScreenState w;
-    carve_screen(arena, (size_t)L.atoms(), L.rows(), n_rec, false, &w);
+    carve_screen(arena, (size_t)L.atoms(), L.rows(), n_rec, L.words(), false, &w);
     PVS_REQUIRE(arena.ok(), "pvs_screen_graph_build: state too small (%zu < %zu)", state_bytes, arena.off);
     PvsProfScope prof(s, PVS_PROF_PREPARE);
     PVS_CHECK_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), s));
@@ -248,8 +264,8 @@ extern "C" int pvs_screen_graph_build(const float* lig_pos, const float* rec_pos
                       OutCsr{rowptr_lig, row_lig, col_lig, etype_lig, capacity_lig}, inv_deg, status, w, s);
 }
 
-// ---- library batches: every slot of the batch holds one pose of ANY ligand of 0..64 atoms ----
-// pvs_screen_graph_build_ragged: the same graphs for a batch whose B slots hold poses of different
+// ---- library batches: every slot of the batch holds one pose of ANY ligand of 0..slot_cap atoms ----
+// pvs_screen_graph_build_ragged_cap (and pvs_screen_graph_build_ragged: the same with slot_cap = 64): the same graphs for a batch whose B slots hold poses of different
 // ligands (a docking library: thousands of ligands of 8-60 atoms with ~10 poses each). The ligand atoms
 // come packed, lig_pos [L_cap,3] with the device table lig_ptr [B+1]; slot p has lig_ptr[p+1]-lig_ptr[p]
 // atoms (0 = receptor only). Compact node layout: slot p owns nodes node_ptr[p] .. node_ptr[p+1],
@@ -263,7 +279,7 @@ extern "C" int pvs_screen_graph_build(const float* lig_pos, const float* rec_pos
 namespace {
 
 // thread per slot: validates the slot, node_ptr, atom -> slot table
-__global__ void k_slots(const int32_t* __restrict__ lig_ptr, int B, int L_cap, int n_rec,
+__global__ void k_slots(const int32_t* __restrict__ lig_ptr, int B, int L_cap, int n_rec, int slot_cap,
                         int32_t* __restrict__ node_ptr, int32_t* __restrict__ slot_of,
                         int32_t* __restrict__ status) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
@@ -275,7 +291,7 @@ __global__ void k_slots(const int32_t* __restrict__ lig_ptr, int B, int L_cap, i
         return;
     }
     const int a0 = lig_ptr[p], a1 = lig_ptr[p + 1];
-    if (a0 < 0 || a1 < a0 || a1 - a0 > 64 || a1 > L_cap) {
+    if (a0 < 0 || a1 < a0 || a1 - a0 > slot_cap || a1 > L_cap) {
         atomicOr(status, kPvsBadTable);
         node_ptr[p] = p * n_rec;
         return;
@@ -317,27 +333,32 @@ k_node_tables_ragged(const float* __restrict__ lig_pos, const float* __restrict_
 
 }  // namespace
 
-extern "C" size_t pvs_screen_graph_ragged_state_bytes(int32_t B, int32_t L_cap, int32_t n_rec) {
+extern "C" size_t pvs_screen_graph_ragged_cap_state_bytes(int32_t B, int32_t L_cap, int32_t n_rec,
+                                                          int32_t slot_cap) {
+    if (slot_cap < 1 || slot_cap > kPvsMaxSlotCap) return 0;
     PvsArena a(nullptr, 0);
-    return carve_screen(a, (size_t)L_cap, L_cap + B * n_rec, n_rec, true, nullptr) + 256;
+    return carve_screen(a, (size_t)L_cap, L_cap + B * n_rec, n_rec, pvs_slot_words(slot_cap), true, nullptr) + 256;
 }
 
-extern "C" int pvs_screen_graph_build_ragged(const float* lig_pos, const int32_t* lig_ptr, const float* rec_pos,
-                                             const int32_t* rr_rowptr, const int32_t* rr_col, int32_t B,
-                                             int32_t L_cap, int32_t n_rec, double inter_radius, double intra_radius,
-                                             int32_t capacity, int32_t capacity_lig, int32_t* rowptr, int32_t* row,
-                                             int32_t* col, uint8_t* etype, float* inv_deg, int32_t* rowptr_lig,
-                                             int32_t* row_lig, int32_t* col_lig, uint8_t* etype_lig,
-                                             int32_t* node_ptr, int32_t* node_graph, float* pos,
-                                             const PvsRaggedNodeTables* tables, int32_t* status, void* state,
-                                             size_t state_bytes, pvs_stream_t stream_) {
+extern "C" int pvs_screen_graph_build_ragged_cap(const float* lig_pos, const int32_t* lig_ptr, const float* rec_pos,
+                                                 const int32_t* rr_rowptr, const int32_t* rr_col, int32_t B,
+                                                 int32_t L_cap, int32_t n_rec, int32_t slot_cap, double inter_radius,
+                                                 double intra_radius, int32_t capacity, int32_t capacity_lig,
+                                                 int32_t* rowptr, int32_t* row, int32_t* col, uint8_t* etype,
+                                                 float* inv_deg, int32_t* rowptr_lig, int32_t* row_lig,
+                                                 int32_t* col_lig, uint8_t* etype_lig, int32_t* node_ptr,
+                                                 int32_t* node_graph, float* pos, const PvsRaggedNodeTables* tables,
+                                                 int32_t* status, void* state, size_t state_bytes,
+                                                 pvs_stream_t stream_) {
     hipStream_t s = (hipStream_t)stream_;
-    const char* who = "pvs_screen_graph_build_ragged";
+    const char* who = "pvs_screen_graph_build_ragged_cap";
     PVS_REQUIRE(lig_pos && lig_ptr && rec_pos && rr_rowptr && rr_col && rowptr && row && col && etype && inv_deg &&
                 rowptr_lig && row_lig && col_lig && etype_lig && node_ptr && node_graph && pos && status && state,
                 "%s: NULL", who);
-    PVS_REQUIRE(B > 0 && L_cap > 0 && L_cap <= 64 * (int64_t)B && n_rec > 0, "%s: needs slots, 1..64 * slots packed "
-                "ligand atoms (got %d for %d) and a receptor", who, L_cap, B);
+    PVS_REQUIRE(slot_cap >= 1 && slot_cap <= kPvsMaxSlotCap, "%s: slot_cap must be 1..%d (got %d)", who,
+                kPvsMaxSlotCap, slot_cap);
+    PVS_REQUIRE(B > 0 && L_cap > 0 && L_cap <= slot_cap * (int64_t)B && n_rec > 0, "%s: needs slots, 1..%d * slots "
+                "packed ligand atoms (got %d for %d) and a receptor", who, slot_cap, L_cap, B);
     PVS_REQUIRE((int64_t)L_cap + (int64_t)B * n_rec < INT32_MAX, "%s: more than 2^31 nodes", who);
     PvsRaggedNodeTables t = {};
     if (tables) {
@@ -349,12 +370,12 @@ extern "C" int pvs_screen_graph_build_ragged(const float* lig_pos, const int32_t
     }
     PvsArena arena(state, state_bytes);
     ScreenState w;
-    carve_screen(arena, (size_t)L_cap, L_cap + B * n_rec, n_rec, true, &w);
+    carve_screen(arena, (size_t)L_cap, L_cap + B * n_rec, n_rec, pvs_slot_words(slot_cap), true, &w);
     PVS_REQUIRE(arena.ok(), "%s: state too small (%zu < %zu)", who, state_bytes, arena.off);
     PvsProfScope prof(s, PVS_PROF_PREPARE);
-    const PvsRaggedSlots L{lig_ptr, node_ptr, w.slot_of, status, B, L_cap, n_rec};
+    const PvsRaggedSlots L{lig_ptr, node_ptr, w.slot_of, status, B, L_cap, n_rec, slot_cap};
     PVS_CHECK_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), s));
-    k_slots<<<(B + 1 + 255) / 256, 256, 0, s>>>(lig_ptr, B, L_cap, n_rec, node_ptr, w.slot_of, status);
+    k_slots<<<(B + 1 + 255) / 256, 256, 0, s>>>(lig_ptr, B, L_cap, n_rec, slot_cap, node_ptr, w.slot_of, status);
     PVS_CHECK_LAUNCH();
     PVS_TRY(build_csrs(L, lig_pos, rec_pos, rr_rowptr, rr_col, inter_radius, intra_radius, rowptr, rowptr_lig,
                        OutCsr{rowptr, row, col, etype, capacity},
@@ -362,4 +383,24 @@ extern "C" int pvs_screen_graph_build_ragged(const float* lig_pos, const int32_t
     k_node_tables_ragged<<<(L.rows() + 3) / 4, 256, 0, s>>>(lig_pos, rec_pos, L, node_graph, pos, t);
     PVS_CHECK_LAUNCH();
     return 0;
+}
+
+// the pair from before slots could be wider than one mask word: slots of 0..64 atoms
+extern "C" size_t pvs_screen_graph_ragged_state_bytes(int32_t B, int32_t L_cap, int32_t n_rec) {
+    return pvs_screen_graph_ragged_cap_state_bytes(B, L_cap, n_rec, 64);
+}
+
+extern "C" int pvs_screen_graph_build_ragged(const float* lig_pos, const int32_t* lig_ptr, const float* rec_pos,
+                                             const int32_t* rr_rowptr, const int32_t* rr_col, int32_t B,
+                                             int32_t L_cap, int32_t n_rec, double inter_radius, double intra_radius,
+                                             int32_t capacity, int32_t capacity_lig, int32_t* rowptr, int32_t* row,
+                                             int32_t* col, uint8_t* etype, float* inv_deg, int32_t* rowptr_lig,
+                                             int32_t* row_lig, int32_t* col_lig, uint8_t* etype_lig,
+                                             int32_t* node_ptr, int32_t* node_graph, float* pos,
+                                             const PvsRaggedNodeTables* tables, int32_t* status, void* state,
+                                             size_t state_bytes, pvs_stream_t stream_) {
+    return pvs_screen_graph_build_ragged_cap(lig_pos, lig_ptr, rec_pos, rr_rowptr, rr_col, B, L_cap, n_rec, 64,
+                                             inter_radius, intra_radius, capacity, capacity_lig, rowptr, row, col,
+                                             etype, inv_deg, rowptr_lig, row_lig, col_lig, etype_lig, node_ptr,
+                                             node_graph, pos, tables, status, state, state_bytes, stream_);
 }

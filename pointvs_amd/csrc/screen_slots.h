@@ -2,8 +2,10 @@
 // A slot holds one pose: its ligand atoms, then the receptor's n_rec atoms. Two layouts answer the same questions
 // (how many packed ligand atoms and node rows there are; which slot a packed atom or a row belongs to), so that the
 // builder's kernels exist once: uniform (B poses of one n_lig-atom ligand, by arithmetic) and ragged (one pose of any
-// 0..64-atom ligand per slot, from the device tables lig_ptr / node_ptr / slot_of). No HIP header: the host compiler
-// builds this file alone (tests/test_screen_slots_host.py).
+// ligand of 0..slot_cap atoms per slot, from the device tables lig_ptr / node_ptr / slot_of). A ligand atom's contacts
+// with the other atoms of its slot are a bit mask of words() 64-bit words (atom k of the slot: bit k % 64 of word
+// k / 64); the word and bit arithmetic of those masks lives here too. No HIP header: the host compiler builds this
+// file alone (tests/test_screen_slots_host.py, tests/test_screen_words_host.py).
 #pragma once
 #include <stdint.h>
 
@@ -24,7 +26,22 @@ PVS_SLOTS_FN int pvs_last_le(const int32_t* table, int n, int i) {
     return lo;
 }
 
-constexpr int kPvsBadTable = 8;     // *status bit 3: lig_ptr is not a table of 0..64-atom slots inside L_cap
+constexpr int kPvsBadTable = 8;     // *status bit 3: lig_ptr is not a table of 0..slot_cap-atom slots inside L_cap
+constexpr int kPvsMaxSlotCap = 1024;        // the most ligand atoms a slot holds: 16 mask words
+
+// Ligand-side masks: how many 64-bit words hold one bit per atom of a slot of up to `cap` atoms, and where the slot's
+// k-th atom has its bit.
+PVS_SLOTS_FN int pvs_slot_words(int cap) { return (cap + 63) >> 6; }
+PVS_SLOTS_FN int pvs_slot_word(int k) { return k >> 6; }
+PVS_SLOTS_FN int pvs_slot_bit(int k) { return k & 63; }
+
+// The number of set bits of the multi-word mask m before bit `bit` (0..63) of word `word`: where the wave's lane `bit`
+// of trip `word` writes its entry when every set bit of m becomes one entry, ascending (k_fill).
+PVS_SLOTS_FN int pvs_mask_rank(const unsigned long long* m, int word, int bit) {
+    int rank = 0;
+    for (int w = 0; w < word; ++w) rank += __builtin_popcountll(m[w]);
+    return rank + __builtin_popcountll(m[word] & ((1ull << bit) - 1ull));
+}
 
 // What a layout says about a packed ligand atom or a node row. Not valid: the other fields are zero (a row's slot: -1).
 struct PvsSlotAtom {
@@ -40,6 +57,7 @@ struct PvsSlotRow {
 // B poses of one ligand: slot p owns the atoms p * n_lig .. and the rows p * (n_lig + n_rec) ..; every row is valid.
 struct PvsUniformSlots {
     int B, n_lig, n_rec;
+    PVS_SLOTS_FN int words() const { return pvs_slot_words(n_lig); }
     PVS_SLOTS_FN int atoms() const { return B * n_lig; }
     PVS_SLOTS_FN int rows() const { return B * (n_lig + n_rec); }
     PVS_SLOTS_FN PvsSlotAtom atom(int q) const { return {true, q / n_lig * n_lig, n_lig}; }
@@ -51,10 +69,13 @@ struct PvsUniformSlots {
 
 // One pose of any ligand per slot: slot p owns the atoms lig_ptr[p] .. lig_ptr[p+1] and the rows node_ptr[p] ..
 // node_ptr[p+1] (node_ptr[p] = lig_ptr[p] + p * n_rec). Not valid: the atoms from lig_ptr[B], the rows from
-// node_ptr[B] (padding up to L_cap / L_cap + B * n_rec), and everything while *status has kPvsBadTable.
+// node_ptr[B] (padding up to L_cap / L_cap + B * n_rec), and everything while *status has kPvsBadTable. slot_cap: the
+// most atoms a slot of a valid table holds (k_slots checks it).
 struct PvsRaggedSlots {
     const int32_t *lig_ptr, *node_ptr, *slot_of, *status;
     int B, L_cap, n_rec;
+    int slot_cap = 64;
+    PVS_SLOTS_FN int words() const { return pvs_slot_words(slot_cap); }
     PVS_SLOTS_FN int atoms() const { return L_cap; }
     PVS_SLOTS_FN int rows() const { return L_cap + B * n_rec; }
     PVS_SLOTS_FN PvsSlotAtom atom(int q) const {

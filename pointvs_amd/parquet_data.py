@@ -28,7 +28,8 @@ from . import _lib
 from .data_loaders import RankWeightedSampler, class_balance_weights
 from .graph import Batch
 
-MAX_LIGAND_ATOMS = 1024     # csrc/complex_build.hip keeps a sample's ligand in LDS
+MAX_LIGAND_ATOMS = 1024     # csrc/complex_build.hip keeps a sample's ligand in LDS; the screening paths accept the
+                            # same number (screening.MAX_SCREEN_LIGAND_ATOMS)
 
 
 def classification_types_to_lists(types_fname):

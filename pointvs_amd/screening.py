@@ -19,6 +19,11 @@ from . import functional as PF
 from .radius_graph import PoseBatcher, radius_graph
 
 
+# The most ligand atoms a pose-batch slot holds (the builders keep a ligand atom's ligand-ligand contacts in
+# ceil(n / 64) mask words); the same number as parquet_data.MAX_LIGAND_ATOMS, the data-root path's limit.
+MAX_SCREEN_LIGAND_ATOMS = 1024
+
+
 def _stream(dev):
     return _lib.stream(dev)
 
@@ -222,7 +227,8 @@ class ReceptorScreen(_ReceptorSideScreen):
         self._graph_ptr = self.batcher.batch.ptr.to(device=dev, dtype=torch.int32)
         # the specialised pose-batch builder (pvs_screen_graph_build) leaves the edge counts on the
         # device; layers that return edge messages (edge_residual) need them on the host
-        self.fast_graph = self.reuse and n_lig <= 64 and not any(l.edge_residual for l in self.egnn)
+        self.fast_graph = (self.reuse and n_lig <= MAX_SCREEN_LIGAND_ATOMS
+                           and not any(l.edge_residual for l in self.egnn))
         self._rec_pos, self._feats = rec_pos, feats
         if self.reuse:
             self._cache_receptor_sums()
@@ -313,7 +319,8 @@ class ReceptorScreen(_ReceptorSideScreen):
         graph (BASELINE config 5: "hipGraph-captured layer stack"). Needs the device-side edge counts
         (self.fast_graph)."""
         if not self.fast_graph:
-            raise RuntimeError('capture needs the pose-batch builder (<= 64 ligand atoms, no edge_residual)')
+            raise RuntimeError(f'capture needs the pose-batch builder (<= {MAX_SCREEN_LIGAND_ATOMS} ligand atoms, '
+                               'no edge_residual)')
         self._static_in = example_poses.clone()
         return self._capture(lambda: self(self._static_in), example_poses.device)
 
@@ -368,16 +375,18 @@ def plan_library(pose_counts, lig_sizes, batch_size, max_lig_atoms=64):
 
 class LibraryScreen(_ReceptorSideScreen):
     """Library screening: every one of the `batch_size` slots of a batch holds one pose of ANY ligand of up to
-    `max_lig_atoms` (<= 64) atoms against the one receptor, or nothing (the last batch of a library).
+    `max_lig_atoms` (<= MAX_SCREEN_LIGAND_ATOMS = 1024) atoms against the one receptor, or nothing (the last batch of
+    a library).
 
         screen = LibraryScreen(model, rec_pos, rec_feats, batch_size, max_lig_atoms, edge_radius)
         scores = screen([(lig_feats [n,F], pose [n,3]), ...])        # [batch_size, ...] raw outputs
 
     What ReceptorScreen reuses across the poses of one ligand is reused across ligands: the receptor-receptor
     template CSR and the first layer's receptor-receptor sums (kept once, [n_rec, .]), the ligand-touching first
-    layer, device-side edge counts. The mixed batch's graph and node tables come from pvs_screen_graph_build_ragged
-    in a compact layout (slot p: its ligand atoms, then the receptor); no host argument of a step depends on the
-    batch's composition, so ONE captured step (`capture`) serves every batch. Models without graphnorm always run
+    layer, device-side edge counts. The mixed batch's graph and node tables come from
+    pvs_screen_graph_build_ragged_cap (slot cap max(max_lig_atoms, 64): ceil(cap / 64) ligand-ligand mask words per
+    atom, one word for a screen of up to 64 atoms) in a compact layout (slot p: its ligand atoms, then the
+    receptor); no host argument of a step depends on the batch's composition, so ONE captured step (`capture`) serves every batch. Models without graphnorm always run
     at the padded shape N_cap = batch_size * (max_lig_atoms + n_rec) (padding nodes have no edges and belong to no
     graph), eager and captured alike; graphnorm normalises over the batch's nodes, so such models run eager at the
     exact node count. Models the first-layer reuse does not cover (edge_residual, softmax attention, hidden size not
@@ -385,9 +394,8 @@ class LibraryScreen(_ReceptorSideScreen):
 
     def __init__(self, model, rec_pos, rec_feats, batch_size, max_lig_atoms, edge_radius, intra_radius=None):
         super().__init__(model, edge_radius, intra_radius)
-        if not 1 <= int(max_lig_atoms) <= 64:
-            raise ValueError(f'max_lig_atoms must be 1..64 (got {max_lig_atoms}); larger ligands go through '
-                             'ReceptorScreen')
+        if not 1 <= int(max_lig_atoms) <= MAX_SCREEN_LIGAND_ATOMS:
+            raise ValueError(f'max_lig_atoms must be 1..{MAX_SCREEN_LIGAND_ATOMS} (got {max_lig_atoms})')
         _lib.require_hip(rec_pos)
         first = self.egnn[0] if self.egnn else None
         self.reuse = (first is not None and first.hidden_nf in (32, 64) and not first.softmax_attention
@@ -395,6 +403,7 @@ class LibraryScreen(_ReceptorSideScreen):
         self.graphnorm = any(getattr(l, 'graphnorm', False) for l in self.egnn)
         dev = rec_pos.device
         self.b, self.max_lig_atoms = int(batch_size), int(max_lig_atoms)
+        self.slot_cap = max(self.max_lig_atoms, 64)      # what the builder validates lig_ptr against
         self.n_rec = int(rec_pos.shape[0])
         self.l_cap = self.b * self.max_lig_atoms
         self.n_cap = self.l_cap + self.b * self.n_rec
@@ -477,7 +486,8 @@ class LibraryScreen(_ReceptorSideScreen):
         hid = self.egnn[0].hidden_nf
         f = _csr_buffers(
             dev, n_cap, cap_l, cap,
-            state=torch.empty(lib.pvs_screen_graph_ragged_state_bytes(self.b, self.l_cap, self.n_rec),
+            state=torch.empty(lib.pvs_screen_graph_ragged_cap_state_bytes(self.b, self.l_cap, self.n_rec,
+                                                                          self.slot_cap),
                               dtype=torch.uint8, device=dev),
             node_ptr=torch.zeros(self.b + 1, **i32), node_graph=torch.empty(n_cap, **i32),
             pos=torch.empty((n_cap, 3), **f32), x=torch.empty((n_cap, self.lig_feats.shape[1]), **f32),
@@ -491,25 +501,27 @@ class LibraryScreen(_ReceptorSideScreen):
 
     def _launch_builder(self, f):
         lib = _lib.lib()
-        _lib.check(lib.pvs_screen_graph_build_ragged(
+        _lib.check(lib.pvs_screen_graph_build_ragged_cap(
             _lib.ptr(self.lig_pos), _lib.ptr(self.lig_ptr), _lib.ptr(self._rec_pos), _lib.ptr(self._rr.t['rowptr']),
-            _lib.ptr(self._rr.t['col']), self.b, self.l_cap, self.n_rec, float(self.r_inter), float(self.r_intra),
+            _lib.ptr(self._rr.t['col']), self.b, self.l_cap, self.n_rec, self.slot_cap, float(self.r_inter),
+            float(self.r_intra),
             f['cap'], f['cap_l'], _lib.ptr(f['rowptr']), _lib.ptr(f['row']), _lib.ptr(f['col']), _lib.ptr(f['etype']),
             _lib.ptr(f['inv_deg']), _lib.ptr(f['rowptr_l']), _lib.ptr(f['row_l']), _lib.ptr(f['col_l']),
             _lib.ptr(f['etype_l']), _lib.ptr(f['node_ptr']), _lib.ptr(f['node_graph']), _lib.ptr(f['pos']),
             C.byref(f['tables']), _lib.ptr(f['status']), _lib.ptr(f['state']), f['state'].numel(),
-            _stream(self.lig_pos.device)), 'pvs_screen_graph_build_ragged')
+            _stream(self.lig_pos.device)), 'pvs_screen_graph_build_ragged_cap')
 
     def _probe_capacities(self):
         """One synchronous probe: the builder with no room for edges leaves both exact edge counts in its row
         pointers. Room for the ligand-touching edges: twice the loaded batch's contacts per ligand atom at a full
-        batch of L_cap atoms, at most what L_cap atoms can have."""
+        batch of L_cap atoms, at most what L_cap atoms can have (per atom: inter and intra contacts with the receptor,
+        both directions, and the slot's other ligand atoms)."""
         probe = self._buffers(1, 1)
         probe['cap'] = probe['cap_l'] = 0
         self._launch_builder(probe)
         n_lig_edges = int(probe['rowptr_l'][self.n_cap].item())
         per_atom = -(-n_lig_edges // max(self.n_atoms, 1))
-        cap_l = min(self.l_cap * (4 * self.n_rec + 64), 2 * per_atom * self.l_cap + 4096)
+        cap_l = min(self.l_cap * (4 * self.n_rec + self.slot_cap), 2 * per_atom * self.l_cap + 4096)
         cap = self.b * self._rr.n_edges + cap_l
         if cap >= 2 ** 31:
             raise ValueError(f'a batch of {self.b} slots can have {cap} edges (>= 2^31): use a smaller batch_size')
@@ -524,7 +536,7 @@ class LibraryScreen(_ReceptorSideScreen):
         return pgs[n]
 
     def _build(self, capacities=None):
-        """The loaded batch's graph and node tables (pvs_screen_graph_build_ragged). capacities: (full, ligand-
+        """The loaded batch's graph and node tables (pvs_screen_graph_build_ragged_cap). capacities: (full, ligand-
         touching) edge room instead of the probe's."""
         capturing = torch.cuda.is_current_stream_capturing()
         if self._fast is None:
@@ -539,7 +551,7 @@ class LibraryScreen(_ReceptorSideScreen):
 
     def _raise_for(self, code):
         if code & 8:
-            raise ValueError('LibraryScreen: lig_ptr is not a table of 0..64-atom slots')
+            raise ValueError(f'LibraryScreen: lig_ptr is not a table of 0..{self.slot_cap}-atom slots')
         if code & 4:
             raise RuntimeError('LibraryScreen: edge buffer overflow (more ligand contacts per atom than twice '
                                'the first batch); rebuild the screen with a denser first batch')
@@ -711,19 +723,22 @@ class ScreeningSweep:
         return screen
 
     @torch.no_grad()
-    def run_library(self, ligands, predictions_file=None, sigmoid=None):
+    def run_library(self, ligands, predictions_file=None, sigmoid=None, max_lig_atoms=64):
         """`run` for a docking library (many ligands of different sizes with a few poses each): the poses of all
-        ligands of up to 64 atoms are streamed through ONE LibraryScreen in dense mixed batches (`plan_library`:
+        ligands of up to `max_lig_atoms` (1..MAX_SCREEN_LIGAND_ATOMS) atoms are streamed through ONE LibraryScreen in dense mixed batches (`plan_library`:
         library order, then pose order; ceil(total poses / batch_size) batches, one captured step for all of them),
         larger ligands through their size bucket as in `run`. Same arguments, return value and predictions lines
         as `run`; the lines are in library order, then pose order."""
+        max_lig_atoms = int(max_lig_atoms)
+        if not 1 <= max_lig_atoms <= MAX_SCREEN_LIGAND_ATOMS:
+            raise ValueError(f'max_lig_atoms must be 1..{MAX_SCREEN_LIGAND_ATOMS} (got {max_lig_atoms})')
         ligands = [item for item in ligands if int(item[2].shape[0]) > 0]
         dev = self.rec_pos.device
-        small = [k for k, (_, _, poses) in enumerate(ligands) if int(poses.shape[1]) <= 64]
-        large = [k for k in range(len(ligands)) if int(ligands[k][2].shape[1]) > 64]
+        small = [k for k, (_, _, poses) in enumerate(ligands) if int(poses.shape[1]) <= max_lig_atoms]
+        large = [k for k in range(len(ligands)) if int(ligands[k][2].shape[1]) > max_lig_atoms]
         sizes = [int(ligands[k][2].shape[1]) for k in small]
         counts = [int(ligands[k][2].shape[0]) for k in small]
-        plan = plan_library(counts, sizes, self.b, 64)
+        plan = plan_library(counts, sizes, self.b, max_lig_atoms)
         out, kept = {}, []
         with self._sweeping(predictions_file, sigmoid) as (sigmoid, writer):
             if plan:

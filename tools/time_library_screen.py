@@ -4,13 +4,16 @@
   mixed    512 ligands, sizes uniform in 8..64 (fixed seed), 9 poses each: `ScreeningSweep.run` launches one padded
            batch per ligand (512), `run_library` ceil(4608 / 128) = 36 dense mixed batches
   control  36 ligands of 30 atoms with exactly 128 poses each: both paths launch 36 full batches of the same work
+  wide     (--wide) 128 ligands, sizes uniform in 65..200 (fixed seed), 9 poses each: `run_library` at its default
+           boundary of 64 atoms sends every ligand through its size bucket (128 padded batches, a captured step per
+           size), `run_library(max_lig_atoms=200)` streams them in ceil(1152 / 128) = 9 dense mixed batches
 
 Each path: one untimed run (buckets built, steps captured), then 3 timed runs, the two paths alternating; a run is
 timed by the host clock from the call to a device synchronise after it (the predictions file is complete by then:
 the writer is closed inside the call). Reports the median poses/s of both paths, their ratio and the batches
 launched, and the largest difference between the two paths' scores.
 
-    python tools/time_library_screen.py [--out profiles/library_screen_time.txt]
+    python tools/time_library_screen.py [--wide] [--out profiles/library_screen_time.txt]
 """
 import argparse
 import statistics
@@ -43,14 +46,16 @@ def timed(fn, dev):
     return time.perf_counter() - t0, out
 
 
-def measure(name, work, model, rec, rec_feats, radius, batch, out_dir, dev, repeats=3):
+def measure(name, work, model, rec, rec_feats, radius, batch, out_dir, dev, repeats=3, paths=None):
+    """paths: {label: (ScreeningSweep method name, its keyword arguments)}, two of them: the baseline first."""
     from pointvs_amd.screening import ScreeningSweep
     n_poses = sum(int(p.shape[0]) for _, _, p in work)
-    sweeps = {'run': ScreeningSweep(model, rec, rec_feats, radius, batch),
-              'run_library': ScreeningSweep(model, rec, rec_feats, radius, batch)}
-    calls = {'run': lambda: sweeps['run'].run(work, predictions_file=out_dir / f'{name}_run.txt'),
-             'run_library': lambda: sweeps['run_library'].run_library(
-                 work, predictions_file=out_dir / f'{name}_library.txt')}
+    paths = paths or {'run': ('run', {}), 'run_library': ('run_library', {})}
+    base, other = paths
+    sweeps = {key: ScreeningSweep(model, rec, rec_feats, radius, batch) for key in paths}
+    files = {key: out_dir / f'{name}_{k}.txt' for k, key in enumerate(paths)}
+    calls = {key: (lambda key=key, method=method, kw=kw: getattr(sweeps[key], method)(
+        work, predictions_file=files[key], **kw)) for key, (method, kw) in paths.items()}
     times, scores, batches = {k: [] for k in calls}, {}, {}
     for key, call in calls.items():                    # untimed: buckets, probes, captures
         timed(call, dev)
@@ -60,15 +65,15 @@ def measure(name, work, model, rec, rec_feats, radius, batch, out_dir, dev, repe
             t, scores[key] = timed(call, dev)
             times[key].append(t)
             batches[key] = sweeps[key].batches_run - before
-    diff = max(float((scores['run'][n] - scores['run_library'][n]).abs().max()) for n, _, _ in work)
-    lines_equal = (out_dir / f'{name}_run.txt').read_text() == (out_dir / f'{name}_library.txt').read_text()
+    diff = max(float((scores[base][n] - scores[other][n]).abs().max()) for n, _, _ in work)
+    lines_equal = files[base].read_text() == files[other].read_text()
     rate = {k: n_poses / statistics.median(v) for k, v in times.items()}
     lines = [f'## {name}: {len(work)} ligands, {n_poses} poses, batch {batch}']
     for key in calls:
         runs = ' '.join(f'{t:.3f}' for t in times[key])
-        lines.append(f'{key:12s} {rate[key]:10.0f} poses/s (median of {repeats}; runs {runs} s)  '
+        lines.append(f'{key:{max(12, *map(len, paths))}s} {rate[key]:10.0f} poses/s (median of {repeats}; runs {runs} s)  '
                      f'{batches[key]:4d} batches launched')
-    lines.append(f'ratio run_library / run = {rate["run_library"] / rate["run"]:.2f}')
+    lines.append(f'ratio {other} / {base} = {rate[other] / rate[base]:.2f}')
     lines.append(f'max |score difference| between the paths = {diff:.2e}; predictions files identical: {lines_equal}')
     return lines
 
@@ -78,6 +83,7 @@ def main():
     ap.add_argument('--out', default=str(ROOT / 'profiles' / 'library_screen_time.txt'))
     ap.add_argument('--ligands', type=int, default=512)
     ap.add_argument('--batch', type=int, default=128)
+    ap.add_argument('--wide', action='store_true', help='also the leg with ligands of 65..200 atoms')
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('time_library_screen.py measures on the GPU; none found')
@@ -103,6 +109,14 @@ def main():
     del mixed
     control = make_library(lig, lig_feats, [30] * 36, args.batch, dev, seed=9000)
     text += measure('control', control, model, rec, rec_feats, radius, args.batch, out_dir, dev) + ['']
+    if args.wide:
+        del control
+        wide_lig, _, wide_feats = screening_set(seed=5200, n_lig=200)
+        wide_sizes = torch.randint(65, 201, (max(args.ligands // 4, 1),), generator=gen).tolist()
+        wide = make_library(wide_lig, wide_feats[:200], wide_sizes, 9, dev, seed=20000)
+        text += measure('wide', wide, model, rec, rec_feats, radius, args.batch, out_dir, dev,
+                        paths={'run_library': ('run_library', {}),
+                               'run_library(max_lig_atoms=200)': ('run_library', dict(max_lig_atoms=200))}) + ['']
     text = '\n'.join(text)
     print(text)
     Path(args.out).parent.mkdir(parents=True, exist_ok=True)
