@@ -476,6 +476,38 @@ int pvs_pool_head_bwd(const float* g_y, const float* pooled, const float* w, con
                       float* g_h, float* g_w, float* g_b, int32_t n_graphs, int32_t n_nodes, int32_t width,
                       int32_t n_out, pvs_stream_t stream);
 
+/* The pooling once and up to PVS_MAX_POOL_HEADS heads on the pooled row in one launch, forward only (screening a
+ * two-headed model: egnn_multitask.py:141-166 evaluates one head per pass, `feats_linear_layers_pose` or
+ * `feats_linear_layers_affinity`, over the same pooled embedding). A head is one nn.Linear, W [n_out, width] and b [n_out]
+ * (NULL: no bias), followed by nothing, nn.ReLU() or nn.Softplus() with its defaults (beta 1, threshold 20: the input
+ * itself above 20); it writes the columns [col, col + n_out) of y [n_graphs, ld_y]:
+ *   y[g, col + o] = act(b[o] + sum_k pooled[g, k] W[o, k]),  k ascending, one fused multiply-add per term.
+ * The pooled row is formed by the code of the single-head forward above, so with PVS_HEAD_NONE a head's columns are bit
+ * for bit what that entry gives with the head's weights. `heads` is a HOST array, copied into the kernel's arguments
+ * (no device table: a captured launch keeps them). pooled [n_graphs, width]: NULL to skip. width <= 1024; the column
+ * ranges must lie inside ld_y and must not overlap. */
+enum { PVS_HEAD_NONE = 0, PVS_HEAD_RELU = 1, PVS_HEAD_SOFTPLUS = 2 };
+enum { PVS_MAX_POOL_HEADS = 4 };
+typedef struct PvsHead {
+    const float* w;
+    const float* b;
+    int32_t n_out;
+    int32_t act;     /* PVS_HEAD_* */
+    int32_t col;     /* first column of y this head writes */
+} PvsHead;
+int pvs_pool_heads_fwd(const float* h, const int32_t* graph_ptr, const PvsHead* heads, int32_t n_heads, float* pooled,
+                       float* y, int32_t n_graphs, int32_t width, int32_t ld_y, pvs_stream_t stream);
+
+/* Best row of every segment (the best pose of every ligand of a sweep): scores [P, n_cols], segment s = the rows
+ * [seg_ptr[s], seg_ptr[s + 1]) (seg_ptr: DEVICE, ascending, inside [0, P]). best[s] = the row, counted from the
+ * segment's first, whose entry in `column` is largest; best_rows[s, :] = that row of scores. Equal values go to the
+ * lower row (-0.0 and +0.0 are equal), a NaN never beats a number, -inf is a score like any other. A segment without
+ * rows or with nothing but NaNs in `column` gets best = -1 and a row of NaNs. No atomics, no workspace: the result
+ * does not depend on the order in which candidates meet (csrc/pose_select.h holds the relation) and is the same bits
+ * every time. */
+int pvs_segment_argmax(const float* scores, int32_t n_cols, int32_t column, const int32_t* seg_ptr, int32_t n_segments,
+                       int32_t* best, float* best_rows, pvs_stream_t stream);
+
 /* nn.BCEWithLogitsLoss() with its default mean reduction (point_neural_network_base.py:74, used at :365) over n logits:
  * loss[0] = mean(max(x, 0) - x t + log1p(exp(-|x|))), grad[i] = (sigmoid(x_i) - t_i) / n (what the backward scales by
  * the upstream gradient: pvs_scale_by_device_scalar, out[i] = a[i] * scalar[0] with the scalar in device memory). */

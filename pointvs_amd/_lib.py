@@ -57,6 +57,14 @@ class PvsComplexPool(C.Structure):
                                                 'rec_ptr', 'lig_ptr')] + [('n_rec', C.c_int32), ('n_lig', C.c_int32)]
 
 
+class PvsHead(C.Structure):
+    _fields_ = [('w', C.c_void_p), ('b', C.c_void_p), ('n_out', C.c_int32), ('act', C.c_int32), ('col', C.c_int32)]
+
+
+HEAD_NONE, HEAD_RELU, HEAD_SOFTPLUS = 0, 1, 2       # PVS_HEAD_* (pvs_egnn.h)
+MAX_POOL_HEADS = 4
+
+
 class PvsStackStrides(C.Structure):
     _fields_ = [(name, C.c_int64) for name in ('h_mid', 'x_mid', 'att', 'node_att', 'saved')]
 
@@ -143,6 +151,10 @@ _PROTOTYPES = {
     'pvs_mean_pool_bwd': (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 3 + [C.c_void_p]),
     'pvs_pool_head_fwd': (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 3 + [C.c_void_p]),
     'pvs_pool_head_bwd': (C.c_int, [C.c_void_p] * 7 + [C.c_int32] * 4 + [C.c_void_p]),
+    'pvs_pool_heads_fwd': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(PvsHead), C.c_int32, C.c_void_p, C.c_void_p] +
+                           [C.c_int32] * 3 + [C.c_void_p]),
+    'pvs_segment_argmax': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                     C.c_void_p]),
     'pvs_bce_logits_fwd': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     'pvs_scale_by_device_scalar': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     'pvs_segment_workspace_bytes': (C.c_size_t, [C.c_int32, C.c_int32]),
@@ -185,7 +197,7 @@ _PROTOTYPES = {
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)
-MIN_VERSION = 105       # pvs_version() of the library these prototypes describe (105: complex batches from a structure pool)
+MIN_VERSION = 106       # pvs_version() of the library these prototypes describe (106: several heads on one pooled row, best row per segment)
 _lib = None
 
 

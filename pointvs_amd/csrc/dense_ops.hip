@@ -490,13 +490,11 @@ k_mean_pool_fwd(const float* __restrict__ h, const int32_t* __restrict__ gptr,
     }
 }
 
-// global_mean_pool + the first Linear of the head in one launch (one workgroup per graph): the pooled row stays in LDS
-// for the product; y[g, c] = b[c] + sum_k W[c, k] pooled[g, k], k ascending (the order of k_linear).
-__global__ void __launch_bounds__(kPoolThreads)
-k_pool_head_fwd(const float* __restrict__ h, const int32_t* __restrict__ gptr, const float* __restrict__ W,
-                const float* __restrict__ b, float* __restrict__ pooled, float* __restrict__ y, int width, int C) {
-    __shared__ float part[kPoolThreads];
-    __shared__ float pl[kPoolThreads];
+// The pooled row of graph g (width <= 1024 channels) into pl[0, width) (LDS) and, unless pooled is NULL, into
+// pooled[g, :]; ends with the workgroup's barrier. The ONE place the pool-and-head kernels form the row: whatever reads
+// pl afterwards sees the same bits in k_pool_head_fwd and k_pool_heads_fwd.
+__device__ __forceinline__ void pool_row_to_lds(const float* __restrict__ h, const int32_t* __restrict__ gptr,
+                                                float* __restrict__ pooled, float* part, float* pl, int width) {
     const int g = blockIdx.x, tid = threadIdx.x;
     const int n0 = gptr[g], n1 = gptr[g + 1];
     const int R = kPoolThreads / width;
@@ -520,14 +518,60 @@ k_pool_head_fwd(const float* __restrict__ h, const int32_t* __restrict__ gptr, c
         const int cnt = n1 - n0;
         s = s / (float)(cnt > 1 ? cnt : 1);
         pl[tid] = s;
-        pooled[(size_t)g * width + tid] = s;
+        if (pooled) pooled[(size_t)g * width + tid] = s;
     }
     __syncthreads();
-    for (int o = tid; o < C; o += kPoolThreads) {
-        float acc = b ? b[o] : 0.f;
-        const float* wr = W + (size_t)o * width;
-        for (int k = 0; k < width; ++k) acc = fmaf(pl[k], wr[k], acc);
-        y[(size_t)g * C + o] = acc;
+}
+
+// b[o] + sum_k W[o, k] pl[k], k ascending (the order of k_linear), one fmaf per term
+__device__ __forceinline__ float head_dot(const float* pl, const float* __restrict__ W, const float* __restrict__ b,
+                                          int o, int width) {
+    float acc = b ? b[o] : 0.f;
+    const float* wr = W + (size_t)o * width;
+    for (int k = 0; k < width; ++k) acc = fmaf(pl[k], wr[k], acc);
+    return acc;
+}
+
+// global_mean_pool + the first Linear of the head in one launch (one workgroup per graph): the pooled row stays in LDS
+// for the product; y[g, c] = b[c] + sum_k W[c, k] pooled[g, k].
+__global__ void __launch_bounds__(kPoolThreads)
+k_pool_head_fwd(const float* __restrict__ h, const int32_t* __restrict__ gptr, const float* __restrict__ W,
+                const float* __restrict__ b, float* __restrict__ pooled, float* __restrict__ y, int width, int C) {
+    __shared__ float part[kPoolThreads];
+    __shared__ float pl[kPoolThreads];
+    pool_row_to_lds(h, gptr, pooled, part, pl, width);
+    const int g = blockIdx.x;
+    for (int o = threadIdx.x; o < C; o += kPoolThreads) y[(size_t)g * C + o] = head_dot(pl, W, b, o, width);
+}
+
+// The same pooled row under up to four heads (screening a two-headed model: pose logit and affinity from one pass):
+// y[g, col + o] = act(b[o] + sum_k W[o, k] pooled[g, k]) per head. The head descriptors are kernel arguments (no device
+// table: the launch captures as it stands); the loop over them is unrolled so that they stay in scalar registers.
+struct PoolHeads {
+    PvsHead head[PVS_MAX_POOL_HEADS];
+    int n;
+};
+
+// nn.Softplus() with its defaults (beta 1, threshold 20): the input itself above the threshold
+__device__ __forceinline__ float head_act(int act, float v) {
+    if (act == PVS_HEAD_RELU) return v > 0.f ? v : 0.f;
+    if (act == PVS_HEAD_SOFTPLUS) return v > 20.f ? v : log1pf(expf(v));
+    return v;
+}
+
+__global__ void __launch_bounds__(kPoolThreads)
+k_pool_heads_fwd(const float* __restrict__ h, const int32_t* __restrict__ gptr, const PoolHeads heads,
+                 float* __restrict__ pooled, float* __restrict__ y, int width, int ld_y) {
+    __shared__ float part[kPoolThreads];
+    __shared__ float pl[kPoolThreads];
+    pool_row_to_lds(h, gptr, pooled, part, pl, width);
+    float* yr = y + (size_t)blockIdx.x * ld_y;
+#pragma unroll
+    for (int i = 0; i < PVS_MAX_POOL_HEADS; ++i) {
+        if (i >= heads.n) break;
+        const PvsHead hd = heads.head[i];
+        for (int o = threadIdx.x; o < hd.n_out; o += kPoolThreads)
+            yr[hd.col + o] = head_act(hd.act, head_dot(pl, hd.w, hd.b, o, width));
     }
 }
 
@@ -1413,6 +1457,30 @@ extern "C" int pvs_pool_head_fwd(const float* h, const int32_t* graph_ptr, const
                 n_out);
     if (B <= 0) return 0;
     k_pool_head_fwd<<<B, kPoolThreads, 0, (hipStream_t)stream>>>(h, graph_ptr, w, b, pooled, y, width, n_out);
+    PVS_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int pvs_pool_heads_fwd(const float* h, const int32_t* graph_ptr, const PvsHead* heads, int32_t n_heads,
+                                  float* pooled, float* y, int32_t B, int32_t width, int32_t ld_y, pvs_stream_t stream) {
+    PVS_REQUIRE(width >= 1 && width <= kPoolThreads, "pool_heads: width %d unsupported", width);
+    PVS_REQUIRE(heads && n_heads >= 1 && n_heads <= PVS_MAX_POOL_HEADS, "pool_heads: %d heads (1..%d in one launch)",
+                n_heads, PVS_MAX_POOL_HEADS);
+    PoolHeads args = {};
+    args.n = n_heads;
+    for (int i = 0; i < n_heads; ++i) {
+        const PvsHead& hd = heads[i];
+        PVS_REQUIRE(hd.w && hd.n_out >= 1 && hd.act >= PVS_HEAD_NONE && hd.act <= PVS_HEAD_SOFTPLUS,
+                    "pool_heads: head %d: weights missing, n_out %d or activation %d unsupported", i, hd.n_out, hd.act);
+        PVS_REQUIRE(hd.col >= 0 && hd.col <= ld_y - hd.n_out, "pool_heads: head %d: columns [%d, %d + %d) outside the %d of y",
+                    i, hd.col, hd.col, hd.n_out, ld_y);
+        for (int j = 0; j < i; ++j)
+            PVS_REQUIRE(hd.col >= heads[j].col + heads[j].n_out || heads[j].col >= hd.col + hd.n_out,
+                        "pool_heads: heads %d and %d write overlapping columns", j, i);
+        args.head[i] = hd;
+    }
+    if (B <= 0) return 0;
+    k_pool_heads_fwd<<<B, kPoolThreads, 0, (hipStream_t)stream>>>(h, graph_ptr, args, pooled, y, width, ld_y);
     PVS_CHECK_LAUNCH();
     return 0;
 }

@@ -29,9 +29,13 @@ template <class Slots>
 __global__ void __launch_bounds__(256)
 k_contacts(const float* __restrict__ lig_pos, const float* __restrict__ rec_pos, Slots L, Radius r_inter,
            Radius r_intra, Radius r_zero, u64* __restrict__ m_inter, u64* __restrict__ m_intra,
-           u64* __restrict__ m_ll) {
+           u64* __restrict__ m_ll, int32_t* __restrict__ clear_status) {
     const int lane = threadIdx.x & 63;
     const int q = (blockIdx.x * 256 + threadIdx.x) >> 6;
+    // (the status word of this build is cleared here, by a plain store of the call's first kernel, and not by a 4-byte
+    // memset ahead of it: in a replayed hipGraph that memset node has left the word filled with one arbitrary byte,
+    // 0x14141414 or 0x2c2c2c2c, which check() then read as an overflow or a bad table)
+    if (clear_status && blockIdx.x == 0 && threadIdx.x == 0) *clear_status = 0;
     if (q >= L.atoms()) return;
     const PvsSlotAtom slot = L.atom(q);
     if (!slot.valid) return;
@@ -215,11 +219,12 @@ size_t carve_screen(PvsArena& a, size_t atoms, int rows, int n_rec, int words, b
 template <class Slots>
 int build_csrs(const Slots& L, const float* lig_pos, const float* rec_pos, const int32_t* rr_rowptr,
                const int32_t* rr_col, double inter_radius, double intra_radius, int32_t* rowptr, int32_t* rowptr_lig,
-               OutCsr full, OutCsr lig, float* inv_deg, int32_t* status, const ScreenState& w, hipStream_t s) {
+               OutCsr full, OutCsr lig, float* inv_deg, int32_t* status, bool clear_status, const ScreenState& w,
+               hipStream_t s) {
     const int N = L.rows();
     k_contacts<<<(L.atoms() + 3) / 4, 256, 0, s>>>(lig_pos, rec_pos, L, make_radius(inter_radius),
                                                    make_radius(intra_radius), make_radius(1e-7), w.m_inter,
-                                                   w.m_intra, w.m_ll);
+                                                   w.m_intra, w.m_ll, clear_status ? status : nullptr);
     PVS_CHECK_LAUNCH();
     k_degrees<<<(N + 1 + 255) / 256, 256, 0, s>>>(w.m_inter, w.m_intra, w.m_ll, rr_rowptr, L, w.deg, w.deg_l);
     PVS_CHECK_LAUNCH();
@@ -258,10 +263,9 @@ extern "C" int pvs_screen_graph_build(const float* lig_pos, const float* rec_pos
     carve_screen(arena, (size_t)L.atoms(), L.rows(), n_rec, L.words(), false, &w);
     PVS_REQUIRE(arena.ok(), "pvs_screen_graph_build: state too small (%zu < %zu)", state_bytes, arena.off);
     PvsProfScope prof(s, PVS_PROF_PREPARE);
-    PVS_CHECK_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), s));
     return build_csrs(L, lig_pos, rec_pos, rr_rowptr, rr_col, inter_radius, intra_radius, rowptr, rowptr_lig,
                       OutCsr{rowptr, row, col, etype, capacity},
-                      OutCsr{rowptr_lig, row_lig, col_lig, etype_lig, capacity_lig}, inv_deg, status, w, s);
+                      OutCsr{rowptr_lig, row_lig, col_lig, etype_lig, capacity_lig}, inv_deg, status, true, w, s);
 }
 
 // ---- library batches: every slot of the batch holds one pose of ANY ligand of 0..slot_cap atoms ----
@@ -278,7 +282,9 @@ extern "C" int pvs_screen_graph_build(const float* lig_pos, const float* rec_pos
 // PvsUniformSlots, PvsRaggedSlots); only k_slots and k_node_tables_ragged are the ragged builder's own.
 namespace {
 
-// thread per slot: validates the slot, node_ptr, atom -> slot table
+// thread per slot: validates the slot, node_ptr, atom -> slot table. The thread behind the last slot walks the whole
+// table once more and STORES the build's status word (0 or kPvsBadTable): the word's one writer in this kernel, so no
+// clearing launch or memset has to come before it (k_contacts: why not a memset).
 __global__ void k_slots(const int32_t* __restrict__ lig_ptr, int B, int L_cap, int n_rec, int slot_cap,
                         int32_t* __restrict__ node_ptr, int32_t* __restrict__ slot_of,
                         int32_t* __restrict__ status) {
@@ -287,12 +293,16 @@ __global__ void k_slots(const int32_t* __restrict__ lig_ptr, int B, int L_cap, i
     if (p == B) {
         const int t = lig_ptr[B];
         node_ptr[B] = (t >= 0 && t <= L_cap) ? t + B * n_rec : B * n_rec;
-        if (lig_ptr[0] != 0) atomicOr(status, kPvsBadTable);
+        bool bad = lig_ptr[0] != 0;
+        for (int k = 0; k < B; ++k) {
+            const int a0 = lig_ptr[k], a1 = lig_ptr[k + 1];
+            bad = bad || a0 < 0 || a1 < a0 || a1 - a0 > slot_cap || a1 > L_cap;
+        }
+        *status = bad ? kPvsBadTable : 0;
         return;
     }
     const int a0 = lig_ptr[p], a1 = lig_ptr[p + 1];
     if (a0 < 0 || a1 < a0 || a1 - a0 > slot_cap || a1 > L_cap) {
-        atomicOr(status, kPvsBadTable);
         node_ptr[p] = p * n_rec;
         return;
     }
@@ -374,12 +384,11 @@ extern "C" int pvs_screen_graph_build_ragged_cap(const float* lig_pos, const int
     PVS_REQUIRE(arena.ok(), "%s: state too small (%zu < %zu)", who, state_bytes, arena.off);
     PvsProfScope prof(s, PVS_PROF_PREPARE);
     const PvsRaggedSlots L{lig_ptr, node_ptr, w.slot_of, status, B, L_cap, n_rec, slot_cap};
-    PVS_CHECK_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), s));
     k_slots<<<(B + 1 + 255) / 256, 256, 0, s>>>(lig_ptr, B, L_cap, n_rec, slot_cap, node_ptr, w.slot_of, status);
     PVS_CHECK_LAUNCH();
     PVS_TRY(build_csrs(L, lig_pos, rec_pos, rr_rowptr, rr_col, inter_radius, intra_radius, rowptr, rowptr_lig,
                        OutCsr{rowptr, row, col, etype, capacity},
-                       OutCsr{rowptr_lig, row_lig, col_lig, etype_lig, capacity_lig}, inv_deg, status, w, s));
+                       OutCsr{rowptr_lig, row_lig, col_lig, etype_lig, capacity_lig}, inv_deg, status, false, w, s));
     k_node_tables_ragged<<<(L.rows() + 3) / 4, 256, 0, s>>>(lig_pos, rec_pos, L, node_graph, pos, t);
     PVS_CHECK_LAUNCH();
     return 0;

@@ -55,6 +55,15 @@ class MultitaskSatorrasEGNN(SartorrasEGNN):
         self.feats_linear_layers_affinity = nn.Sequential(*affinity)
         return nn.Sequential(*layers)
 
+    def task_heads(self, tasks):
+        """The head modules of 'pose', 'affinity' or 'both' (pose first), whatever model_task says: what the screens
+        evaluate on one pooled embedding (PNNGeometricBase._pool_and_heads)."""
+        heads = {'pose': [self.feats_linear_layers_pose], 'affinity': [self.feats_linear_layers_affinity],
+                 'both': [self.feats_linear_layers_pose, self.feats_linear_layers_affinity]}
+        if tasks not in heads:
+            raise ValueError(f"tasks={tasks!r}: one of 'pose', 'affinity' or 'both'")
+        return heads[tasks]
+
     def forward(self, graph):
         feats, pg, graph_ptr, n_graphs = self._embed_graph(graph)
         if 'classification' in self.model_task:

@@ -543,6 +543,13 @@ class SartorrasEGNN(PNNGeometricBase):
         self.feats_linear_layers = nn.Sequential(*head)
         return nn.Sequential(*layers)
 
+    def task_heads(self, tasks=None):
+        """The heads a screen evaluates: this model has one, so only None is accepted (MultitaskSatorrasEGNN names
+        its two)."""
+        if tasks is not None:
+            raise ValueError(f'tasks={tasks!r}: {type(self).__name__} has one head')
+        return [self.feats_linear_layers]
+
     def edge_dropout(self, edges, edge_attributes):
         """egnn_satorras.py:320-323: dropout_adj(edges, edge_attributes, dropout, force_undirected=True,
         training=self.training) ahead of the layer stack; identity when dropout == 0 or in eval mode. The draw

@@ -517,6 +517,62 @@ def pool_head(h, graph_ptr, weight, bias=None):
     return _PoolHeadFn.apply(h, graph_ptr, weight, bias)
 
 
+MAX_POOL_HEADS = _lib.MAX_POOL_HEADS
+HEAD_ACTS = {None: _lib.HEAD_NONE, 'relu': _lib.HEAD_RELU, 'softplus': _lib.HEAD_SOFTPLUS}
+
+
+def pool_heads(h, graph_ptr, heads, return_pooled=False):
+    """Several heads on ONE pooled row per graph, in one launch, forward only (screening a two-headed model):
+    heads = [(weight [C_i, width], bias [C_i] or None, act), ...], act None, 'relu' or 'softplus' (nn.Softplus()
+    with its defaults). Returns y [B, sum C_i], the heads' columns side by side in the order given (and the pooled rows
+    [B, width] with return_pooled). With act None a head's columns are bit for bit pool_head(h, graph_ptr, weight,
+    bias). fp32 only; raises when autograd is recording and an input requires grad (there is no backward)."""
+    heads = [(w, b, act) for w, b, act in heads]
+    tensors = [h] + [t for w, b, _ in heads for t in (w, b) if t is not None]
+    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+        raise RuntimeError('pool_heads is forward only: call it under torch.no_grad() (training takes pool_head)')
+    h = _c(h, _F32, _FP32_ONLY)
+    _lib.require_hip(h, graph_ptr, *tensors)
+    n_graphs, width = graph_ptr.numel() - 1, h.shape[1]
+    table, keep, col = (_lib.PvsHead * max(len(heads), 1))(), [], 0
+    for i, (w, b, act) in enumerate(heads):
+        if act not in HEAD_ACTS:
+            raise ValueError(f'pool_heads: activation {act!r} (one of {sorted(k for k in HEAD_ACTS if k)} or None)')
+        w, b = _c(w.detach(), _F32, _FP32_ONLY), _c(None if b is None else b.detach(), _F32, _FP32_ONLY)
+        if w.dim() != 2 or w.shape[1] != width or (b is not None and b.numel() != w.shape[0]):
+            raise ValueError(f'pool_heads: head {i}: weight {tuple(w.shape)} / bias on features of width {width}')
+        keep += [w, b]
+        table[i] = _lib.PvsHead(_lib.ptr(w), _lib.ptr(b), w.shape[0], HEAD_ACTS[act], col)
+        col += w.shape[0]
+    y = torch.empty((n_graphs, col), dtype=torch.float32, device=h.device)
+    pooled = torch.empty((n_graphs, width), dtype=torch.float32, device=h.device) if return_pooled else None
+    _lib.check(_lib.lib().pvs_pool_heads_fwd(_lib.ptr(h), _lib.ptr(graph_ptr), table, len(heads), _lib.ptr(pooled),
+                                             _lib.ptr(y), n_graphs, width, col, _stream(h.device)),
+               'pvs_pool_heads_fwd')
+    return (y, pooled) if return_pooled else y
+
+
+def segment_argmax(scores, seg_ptr, column=0):
+    """The best row of every segment: scores [P, C] fp32, seg_ptr [L + 1] int32 on the device (ascending, inside
+    [0, P]). Returns (best int32 [L], rows [L, C]): best[s] = the row of segment s, counted from its first, with the
+    largest scores[:, column] (equal values: the lower row; a NaN never beats a number; -inf is a score), rows[s] =
+    that row of scores; best = -1 and a row of NaNs for a segment without rows or with NaNs only. One launch, no
+    atomics: the same bits every time."""
+    scores = _c(scores, _F32, _FP32_ONLY)
+    if scores.dim() != 2 or seg_ptr.dtype != torch.int32 or seg_ptr.dim() != 1 or seg_ptr.numel() < 1:
+        raise ValueError('segment_argmax: scores [P, C] and an int32 seg_ptr [L + 1]')
+    _lib.require_hip(scores, seg_ptr)
+    n_cols, n_seg = scores.shape[1], seg_ptr.numel() - 1
+    if scores.shape[0] == 0:        # (no rows: every segment is empty, the kernel reads none - but wants a pointer)
+        scores = scores.new_zeros((1, n_cols))
+    best = torch.empty(n_seg, dtype=torch.int32, device=scores.device)
+    rows = torch.empty((n_seg, n_cols), dtype=torch.float32, device=scores.device)
+    _lib.check(_lib.lib().pvs_segment_argmax(_lib.ptr(scores), n_cols, int(column), _lib.ptr(seg_ptr.contiguous()), n_seg,
+                                             _lib.ptr(best), _lib.ptr(rows), _stream(scores.device)),
+               'pvs_segment_argmax')
+    return best, rows
+
+
 class _BceLogitsMeanFn(torch.autograd.Function):
     """nn.BCEWithLogitsLoss() (mean) as one launch forward (loss + the gradient factor), one backward."""
 

@@ -113,6 +113,37 @@ class PNNGeometricBase(PointNeuralNetworkBase):
             out = PF.pool_head(feats, graph_ptr, mods[0].weight, mods[0].bias)
         return cls._run_head(mods[1:], out)
 
+    @staticmethod
+    def _fused_head(head):
+        """(weight, bias, act) when `head` is a Linear followed by nothing, ReLU or a default Softplus - what
+        PF.pool_heads evaluates - else None."""
+        mods = list(head)
+        if not mods or len(mods) > 2 or not isinstance(mods[0], nn.Linear):
+            return None
+        act = None
+        if len(mods) == 2:
+            if isinstance(mods[1], nn.ReLU):
+                act = 'relu'
+            elif isinstance(mods[1], nn.Softplus) and mods[1].beta == 1 and mods[1].threshold == 20:
+                act = 'softplus'
+            else:
+                return None
+        return mods[0].weight, mods[0].bias, act
+
+    @classmethod
+    def _pool_and_heads(cls, heads, feats, graph_ptr, n_graphs):
+        """Several heads on the same pooled embedding, forward only (the screens): [n_graphs, sum of the heads'
+        outputs], the heads' columns side by side. One launch (PF.pool_heads) when every head is a Linear followed by
+        nothing, ReLU or a default Softplus and the features are fp32 and at most POOL_HEAD_MAX_WIDTH wide; else (and
+        with PVS_FUSED_HEAD=0, the A/B switch of _pool_and_head) one pooling, then each head."""
+        fused = [cls._fused_head(head) for head in heads]
+        if (heads and all(f is not None for f in fused) and len(fused) <= PF.MAX_POOL_HEADS
+                and feats.dtype == torch.float32 and feats.size(1) <= PF.POOL_HEAD_MAX_WIDTH
+                and os.environ.get('PVS_FUSED_HEAD') != '0'):
+            return PF.pool_heads(feats, graph_ptr, fused)
+        pooled = PF.mean_pool(feats, graph_ptr)
+        return torch.cat([cls._run_head(head, pooled).reshape(n_graphs, -1) for head in heads], 1)
+
     def forward(self, x):
         feats, _, graph_ptr, n_graphs = self._embed_graph(x)
         if self.feats_linear_layers is not None:

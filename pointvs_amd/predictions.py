@@ -48,6 +48,25 @@ def format_lines(task, y_pred, y_true, receptors, ligands):
             for i in range(n)]
 
 
+def task_files(path, tasks):
+    """The predictions files of a screen: {task: path}. One task writes `path` itself; 'both' writes `pose_<name>` and
+    `affinity_<name>` beside it, `val`'s naming (point_neural_network_base.py: f'{model_task_for_fnames}_' +
+    predictions_file.name), and not `path`."""
+    path = Path(path).expanduser()
+    if tasks == 'both':
+        return {task: path.with_name(f'{task}_{path.name}') for task in ('pose', 'affinity')}
+    return {tasks: path}
+
+
+def format_hit_lines(best, rows, receptor, names):
+    """The hits file of a sweep, one line per ligand that has a best pose (best[i] >= 0), in the order given:
+    '{c0:.3f} {c1:.3f} ... | {receptor} {name}_pose{best}' - the columns of the best pose's row, then which pose it
+    is. best: L ints, rows: [L, C] numbers, names: L ligand names."""
+    return ['{0} | {1} {2}_pose{3}'.format(' '.join(f'{v:.3f}' for v in np.asarray(rows[i]).reshape(-1)), receptor,
+                                           names[i], int(best[i]))
+            for i in range(len(names)) if int(best[i]) >= 0]
+
+
 def rank_part(path, rank):
     """Part file of one rank of a data-parallel validation run (joined by merge_rank_files)."""
     path = Path(path)

@@ -69,14 +69,36 @@ def _graph_pair(f, n_nodes, n_end):
     return pg, _ligand_csr(f, n_nodes, n_end)
 
 
+TASKS = ('pose', 'affinity', 'both')
+
+
+def _resolve_tasks(model, tasks):
+    """Which heads a screen of `model` evaluates. A model with one head (`feats_linear_layers`) takes only None and
+    gives None: the screen's single-head path. A two-headed model (`feats_linear_layers_pose` / `_affinity`) gives
+    'pose', 'affinity' or 'both' (pose first): `tasks` itself, or for None the head its current task selects
+    ('classification' in model_task: pose, as its forward decides). Pure host logic; ValueError for anything else."""
+    two_headed = hasattr(model, 'feats_linear_layers_pose') and hasattr(model, 'feats_linear_layers_affinity')
+    if not two_headed:
+        if tasks is not None:
+            raise ValueError(f'tasks={tasks!r}: {type(model).__name__} has one head; tasks selects the heads of a '
+                             'two-headed model (leave it None)')
+        return None
+    if tasks is None:
+        return 'pose' if 'classification' in model.model_task else 'affinity'
+    if tasks not in TASKS:
+        raise ValueError(f"tasks={tasks!r}: one of 'pose', 'affinity', 'both' or None")
+    return tasks
+
+
 class _ReceptorSideScreen:
     """What ReceptorScreen and LibraryScreen do alike, once: the receptor-receptor sums of the first layer and their
     weights fingerprint, the ligand-touching first layer, the layers after it, the deferred status word and the
     capture / replay scaffolding. A subclass provides `_cache_receptor_sums()` (where the sums are kept),
-    `_raise_for(code)` (its status bits), `_head(h)` (pooling + head) and, once its builder has run, `_fast` (the
-    live buffer dict with `status` / `host`)."""
+    `_raise_for(code)` (its status bits), `_head(h)` (pooling + head of a single-head model), `_pool_ptr()` (the
+    batch's node offsets, for the heads of a two-headed model) and, once its builder has run, `_fast` (the live buffer
+    dict with `status` / `host`)."""
 
-    def __init__(self, model, edge_radius, intra_radius):
+    def __init__(self, model, edge_radius, intra_radius, tasks=None):
         if any(p.dtype == torch.float64 for p in model.parameters()):
             raise NotImplementedError(f'{type(self).__name__} and its pose-batch builder are fp32 only (no fp64 '
                                       'screening kernels): score fp64 models through the model forward')
@@ -84,6 +106,10 @@ class _ReceptorSideScreen:
         self.model, self.embed, self.egnn = model, layers[0], layers[1:]
         self.r_inter = edge_radius
         self.r_intra = edge_radius if intra_radius is None else intra_radius
+        # None: a single-head model, the path below as it always was; else the heads of a two-headed model, resolved
+        # here (a captured step has them baked in) and never by changing model.model_task
+        self.tasks = _resolve_tasks(model, tasks)
+        self.heads = None if self.tasks is None else model.task_heads(self.tasks)
         self._graph, self._captured, self._pending, self._l1_ws, self._fast = None, False, None, None, None
 
     def _weights_fingerprint(self):
@@ -166,7 +192,22 @@ class _ReceptorSideScreen:
         for layer in self.egnn[1:]:
             h, x, m_sorted = layer.forward_prepared(pg_full, h, x, m_sorted, need_m=layer.edge_residual,
                                                     need_coords=layer is not self.egnn[-1])
+        if self.tasks is not None:
+            return self._heads_out(h, self._pool_ptr())
         return h if self.model.feats_linear_layers is None else self._head(h)
+
+    def _heads_out(self, feats, graph_ptr):
+        """[batch_size, sum of the heads' outputs] of a two-headed model: one pooling, every selected head
+        (PF.pool_heads: one launch)."""
+        return self.model._pool_and_heads(self.heads, feats, graph_ptr, self.b)
+
+    def _plain(self, batch):
+        """The model's plain forward on `batch`, for the routes the first-layer reuse does not cover: the model's own
+        forward (single head), or its trunk and then the same head code as the reuse route."""
+        if self.tasks is None:
+            return self.model(batch)
+        feats, _, graph_ptr, _ = self.model._embed_graph(batch)
+        return self._heads_out(feats, graph_ptr)
 
     def _queue_status(self, status, host):
         """Queues the copy of a builder's status word into its pinned host copy; check() reads it later."""
@@ -213,10 +254,12 @@ class ReceptorScreen(_ReceptorSideScreen):
     """scores = ReceptorScreen(model, rec_pos, feats, n_lig, batch_size, edge_radius)(lig_poses)
 
     feats [n_lig + n_rec, F]: ligand rows first, last column = bp (preprocessing.make_bit_vector);
-    lig_poses [batch_size, n_lig, 3] on the device. Returns the model's raw outputs [batch_size, ...]."""
+    lig_poses [batch_size, n_lig, 3] on the device. Returns the model's raw outputs [batch_size, ...].
+    tasks (two-headed models, `_resolve_tasks`): 'pose', 'affinity' or 'both' - [batch_size, 1 + A], pose logit first,
+    from one trunk pass."""
 
-    def __init__(self, model, rec_pos, feats, n_lig, batch_size, edge_radius, intra_radius=None):
-        super().__init__(model, edge_radius, intra_radius)
+    def __init__(self, model, rec_pos, feats, n_lig, batch_size, edge_radius, intra_radius=None, tasks=None):
+        super().__init__(model, edge_radius, intra_radius, tasks)
         first = self.egnn[0] if self.egnn else None
         self.reuse = (first is not None and first.hidden_nf in (32, 64) and not first.softmax_attention
                       and not first.edge_residual)
@@ -330,10 +373,13 @@ class ReceptorScreen(_ReceptorSideScreen):
     def _head(self, h):
         return self.model._pool_and_head(self.model.feats_linear_layers, h, self._graph_ptr, self.b)
 
+    def _pool_ptr(self):
+        return self._graph_ptr
+
     @torch.no_grad()
     def __call__(self, lig_poses):
         if not self.reuse:
-            return self.model(self.batcher.load(lig_poses))
+            return self._plain(self.batcher.load(lig_poses))
         self._refresh_if_stale()
         if self.fast_graph:
             pg_full, g_lig = self._build_fast(lig_poses)
@@ -390,10 +436,11 @@ class LibraryScreen(_ReceptorSideScreen):
     at the padded shape N_cap = batch_size * (max_lig_atoms + n_rec) (padding nodes have no edges and belong to no
     graph), eager and captured alike; graphnorm normalises over the batch's nodes, so such models run eager at the
     exact node count. Models the first-layer reuse does not cover (edge_residual, softmax attention, hidden size not
-    32 / 64) take the plain forward on the same mixed batch. fp32 only."""
+    32 / 64) take the plain forward on the same mixed batch. fp32 only. tasks: as for ReceptorScreen."""
 
-    def __init__(self, model, rec_pos, rec_feats, batch_size, max_lig_atoms, edge_radius, intra_radius=None):
-        super().__init__(model, edge_radius, intra_radius)
+    def __init__(self, model, rec_pos, rec_feats, batch_size, max_lig_atoms, edge_radius, intra_radius=None,
+                 tasks=None):
+        super().__init__(model, edge_radius, intra_radius, tasks)
         if not 1 <= int(max_lig_atoms) <= MAX_SCREEN_LIGAND_ATOMS:
             raise ValueError(f'max_lig_atoms must be 1..{MAX_SCREEN_LIGAND_ATOMS} (got {max_lig_atoms})')
         _lib.require_hip(rec_pos)
@@ -573,13 +620,16 @@ class LibraryScreen(_ReceptorSideScreen):
                       batch=torch.arange(self.b, device=dev).repeat_interleave(torch.tensor(counts, device=dev)),
                       ptr=ptr, y=torch.zeros(self.b, device=dev), lig_fname=['pose'] * self.b,
                       rec_fname=['receptor'] * self.b, num_graphs=self.b, graph_node_counts=counts)
-        return self.model(attach_radius_graph(batch, self.r_inter, self.r_intra))
+        return self._plain(attach_radius_graph(batch, self.r_inter, self.r_intra))
 
     def _head(self, h):
         model, node_ptr = self.model, self._fast['node_ptr']
         if self.b == 1:     # (one slot: the pooling still ends at node_ptr[1], not at the padded shape)
             return model._run_head(model.feats_linear_layers, PF.mean_pool(h, node_ptr))
         return model._pool_and_head(model.feats_linear_layers, h, node_ptr, self.b)
+
+    def _pool_ptr(self):
+        return self._fast['node_ptr']
 
     @torch.no_grad()
     def __call__(self, slots=None):
@@ -615,6 +665,63 @@ class LibraryScreen(_ReceptorSideScreen):
         return self._replay(lambda: None if slots is None else self.load(slots))
 
 
+class _SweepSink:
+    """What a sweep does with a batch's raw outputs: the sigmoid (every column of a single-head classification model,
+    as `val` does; the pose column alone of a two-headed one), the predictions file(s) - one PredictionsWriter each,
+    so the loop never waits for the host - and, for a hits file, the raw rows per ligand."""
+
+    def __init__(self, sweep, predictions_file, sigmoid, keep_raw):
+        from .predictions import PredictionsWriter, task_files
+        tasks, model = sweep.tasks, sweep.model
+        if tasks is None:
+            if sigmoid is None:
+                sigmoid = getattr(model, 'model_task', 'classification') == 'classification'
+            self.sig_cols = None if sigmoid else 0          # (None: all of them)
+        else:
+            has_pose = tasks != 'affinity'
+            self.sig_cols = 1 if has_pose and (sigmoid is None or sigmoid) else 0
+        self.receptor = sweep.receptor_name
+        self.raw = {} if keep_raw else None
+        self.writers = []          # (writer, first column, columns)
+        if predictions_file:
+            at = 0
+            for task, path in task_files(predictions_file, tasks).items():
+                width = model.task_heads('affinity')[0][0].out_features if task == 'affinity' else 1
+                if width not in (1, 3):      # (the reference has line formats for one affinity and for three)
+                    raise ValueError(f'predictions_file: no line format for an affinity head of {width} outputs '
+                                     '(1 or 3); the returned scores hold them all')
+                # three affinity columns: format_lines' unlabelled multi_regression form
+                form = 'multi_regression' if width == 3 else 'regression'
+                self.writers.append((PredictionsWriter(path, form, flush_every=10), at, width))
+                at += width
+
+    def scored(self, y):
+        """y [n, C] raw -> what the sweep returns and writes."""
+        if self.sig_cols == 0:
+            return y
+        if self.sig_cols is None or y.shape[1] == 1:
+            return torch.sigmoid(y)
+        return torch.cat([torch.sigmoid(y[:, :1]), y[:, 1:]], 1)
+
+    def write(self, y, ligands):
+        for writer, at, cols in self.writers:
+            writer.submit(y[:, at] if cols == 1 else y[:, at:at + cols], None, [self.receptor] * len(ligands), ligands)
+
+    def keep_raw(self, name, raw):
+        if self.raw is not None:
+            self.raw.setdefault(name, []).append(raw)
+
+    def close(self):
+        error = None
+        for writer, _, _ in self.writers:
+            try:
+                writer.close()
+            except Exception as exc:     # (the other file is still closed)
+                error = error or exc
+        if error is not None:
+            raise error
+
+
 class ScreeningSweep:
     """Virtual-screening sweep (BASELINE config 5; the reference's `val` / inference.py loop,
     point_neural_network_base.py:208-360, inference.py:77-146): many ligands, each with many rigid
@@ -630,11 +737,21 @@ class ScreeningSweep:
 
         sweep = ScreeningSweep(model, rec_pos, rec_feats, edge_radius=10.0, batch_size=32)
         scores = sweep.run([(name, lig_feats [n_lig,F], poses [P,n_lig,3]), ...], 'predictions.txt')
+
+    A two-headed model (MultitaskSatorrasEGNN) is screened on the heads `tasks` names: None (the head its current
+    task selects), 'pose', 'affinity', or 'both' - pose logit in column 0, the affinity head's outputs behind it, from
+    ONE trunk pass and one pooling (PF.pool_heads); model.model_task is never changed. With 'both' the predictions go
+    to `pose_<name>` and `affinity_<name>` beside the path given (`val`'s naming), same line order. `hits_file` (any
+    model): after the sweep the best pose of every ligand is picked on the device (PF.segment_argmax on the raw
+    column 0: larger wins, ties to the lower pose, NaN never wins) and written one line per ligand; `sweep.hits`
+    keeps {name: (best pose or -1, its row)}.
     """
 
     def __init__(self, model, rec_pos, rec_feats, edge_radius, batch_size=32, intra_radius=None, capture=True,
-                 receptor_name='receptor'):
+                 receptor_name='receptor', tasks=None):
         self.model, self.rec_pos, self.rec_feats = model, rec_pos, rec_feats
+        self.tasks = _resolve_tasks(model, tasks)
+        self.hits = {}
         self.edge_radius, self.intra_radius, self.b = edge_radius, intra_radius, int(batch_size)
         self.capture, self.receptor_name = capture, receptor_name
         self.buckets = {}          # n_lig -> ReceptorScreen (captured when possible)
@@ -649,7 +766,8 @@ class ScreeningSweep:
             screen = None
         if screen is None:
             feats = torch.cat([lig_feats.to(self.rec_feats.device), self.rec_feats], 0)
-            screen = ReceptorScreen(self.model, self.rec_pos, feats, n_lig, self.b, self.edge_radius, self.intra_radius)
+            screen = ReceptorScreen(self.model, self.rec_pos, feats, n_lig, self.b, self.edge_radius, self.intra_radius,
+                                    tasks=self.tasks)
             if self.capture and screen.fast_graph:
                 screen.capture(example_poses)
             self.buckets[n_lig] = screen
@@ -661,7 +779,7 @@ class ScreeningSweep:
         x = screen.batcher.batch.x
         x.view(screen.b, screen.batcher.n, -1)[:, :screen.n_lig] = lig_feats.to(x.device, x.dtype)
 
-    def _run_ligand(self, name, lig_feats, poses, sigmoid, writer):
+    def _run_ligand(self, name, lig_feats, poses, sink):
         """All poses of one ligand through its size bucket; returns its scores [P, ...]."""
         n_poses, n_lig = int(poses.shape[0]), int(poses.shape[1])
         pad = (-n_poses) % self.b
@@ -673,57 +791,79 @@ class ScreeningSweep:
         for k in range(0, poses.shape[0], self.b):
             chunk = poses[k:k + self.b]
             y = screen.replay(chunk).clone() if screen._captured else screen(chunk.contiguous())
-            y = y.reshape(self.b, -1)
-            if sigmoid:
-                y = torch.sigmoid(y)
+            raw = y.reshape(self.b, -1)
+            y = sink.scored(raw)
             keep = min(self.b, n_poses - k)
             scores.append(y[:keep])
-            if writer is not None:
-                writer.submit(y[:keep, 0], None, [self.receptor_name] * keep,
-                              [f'{name}_pose{k + i}' for i in range(keep)])
+            sink.keep_raw(name, raw[:keep])
+            if sink.writers:
+                sink.write(y[:keep], [f'{name}_pose{k + i}' for i in range(keep)])
             self.batches_run += 1
         screen.check()
         return torch.cat(scores, 0)
 
     @contextlib.contextmanager
-    def _sweeping(self, predictions_file, sigmoid):
-        """What a sweep runs inside: yields (sigmoid, writer) - sigmoid defaults to what `val` does for the model's
-        task, writer is the PredictionsWriter of predictions_file (or None), closed at the end - with the
+    def _sweeping(self, predictions_file, sigmoid, hits_file):
+        """What a sweep runs inside: yields its _SweepSink - sigmoid defaults to what `val` does for the model's task
+        (two-headed: on whenever there is a pose column), the predictions writers are closed at the end - with the
         long-lived heap frozen (no full-heap collection pause inside the sweep: see its docstring)."""
         from .point_neural_network_base import long_lived_heap_frozen
-        from .predictions import PredictionsWriter
-        if sigmoid is None:
-            sigmoid = getattr(self.model, 'model_task', 'classification') == 'classification'
-        writer = PredictionsWriter(predictions_file, 'regression', flush_every=10) if predictions_file else None
+        sink = _SweepSink(self, predictions_file, sigmoid, hits_file is not None)
         try:
             with long_lived_heap_frozen():
-                yield sigmoid, writer
+                yield sink
         finally:
-            if writer is not None:
-                writer.close()
+            sink.close()
+
+    def _pick_hits(self, names, sink, hits_file):
+        """The best pose of every ligand of `names` (library order; a ligand without poses is an empty segment): one
+        PF.segment_argmax over the raw scores on column 0 - before the sigmoid, which saturates into ties - one
+        device-to-host copy, `self.hits` and the hits file (predictions.format_hit_lines)."""
+        if hits_file is None:
+            return
+        from pathlib import Path
+        from .predictions import format_hit_lines
+        raw = {name: torch.cat(parts, 0) for name, parts in sink.raw.items()}
+        lines, self.hits = [], {name: (-1, None) for name in names}
+        if raw:
+            counts = [int(raw[name].shape[0]) if name in raw else 0 for name in names]
+            scores = torch.cat([raw[name] for name in names if name in raw], 0)
+            seg_ptr = torch.tensor([0] + counts).cumsum(0).to(device=scores.device, dtype=torch.int32)
+            best, rows = PF.segment_argmax(scores, seg_ptr, 0)
+            # (best beside its row: ONE copy to the host; a pose index is exact in fp32 below 2^24)
+            packed = torch.cat([best.to(rows.dtype).unsqueeze(1), sink.scored(rows)], 1).cpu()
+            best, rows = packed[:, 0].long().tolist(), packed[:, 1:]
+            self.hits = {name: (best[i], rows[i]) for i, name in enumerate(names)}
+            lines = format_hit_lines(best, rows.numpy(), self.receptor_name, names)
+        path = Path(hits_file).expanduser()
+        path.parent.mkdir(parents=True, exist_ok=True)
+        path.write_text(''.join(line + '\n' for line in lines))
 
     @torch.no_grad()
-    def run(self, ligands, predictions_file=None, sigmoid=None):
+    def run(self, ligands, predictions_file=None, sigmoid=None, hits_file=None):
         """ligands: iterable of (name, lig_feats [n_lig,F], poses [P,n_lig,3] on the device).
-        Returns {name: scores [P, ...] on the device} (raw model outputs; sigmoid-ed like `val` does for
-        classification models when sigmoid is None/True). predictions_file: optional path."""
-        out = {}
-        with self._sweeping(predictions_file, sigmoid) as (sigmoid, writer):
+        Returns {name: scores [P, C] on the device} (raw model outputs; sigmoid-ed like `val` does for
+        classification models when sigmoid is None/True - the pose column alone of a two-headed model).
+        predictions_file, hits_file: optional paths (class docstring)."""
+        out, names = {}, []
+        with self._sweeping(predictions_file, sigmoid, hits_file) as sink:
             for name, lig_feats, poses in ligands:
+                names.append(name)
                 if int(poses.shape[0]) == 0:
                     continue
-                out[name] = self._run_ligand(name, lig_feats, poses, sigmoid, writer)
+                out[name] = self._run_ligand(name, lig_feats, poses, sink)
+            self._pick_hits(names, sink, hits_file)
         return out
 
     def _library_screen(self, max_atoms):
         screen = self.library
         if screen is None or screen.stale() or screen.max_lig_atoms < max_atoms:
             screen = self.library = LibraryScreen(self.model, self.rec_pos, self.rec_feats, self.b, max_atoms,
-                                                  self.edge_radius, self.intra_radius)
+                                                  self.edge_radius, self.intra_radius, tasks=self.tasks)
         return screen
 
     @torch.no_grad()
-    def run_library(self, ligands, predictions_file=None, sigmoid=None, max_lig_atoms=64):
+    def run_library(self, ligands, predictions_file=None, sigmoid=None, max_lig_atoms=64, hits_file=None):
         """`run` for a docking library (many ligands of different sizes with a few poses each): the poses of all
         ligands of up to `max_lig_atoms` (1..MAX_SCREEN_LIGAND_ATOMS) atoms are streamed through ONE LibraryScreen in dense mixed batches (`plan_library`:
         library order, then pose order; ceil(total poses / batch_size) batches, one captured step for all of them),
@@ -732,6 +872,8 @@ class ScreeningSweep:
         max_lig_atoms = int(max_lig_atoms)
         if not 1 <= max_lig_atoms <= MAX_SCREEN_LIGAND_ATOMS:
             raise ValueError(f'max_lig_atoms must be 1..{MAX_SCREEN_LIGAND_ATOMS} (got {max_lig_atoms})')
+        ligands = list(ligands)
+        names = [item[0] for item in ligands]
         ligands = [item for item in ligands if int(item[2].shape[0]) > 0]
         dev = self.rec_pos.device
         small = [k for k, (_, _, poses) in enumerate(ligands) if int(poses.shape[1]) <= max_lig_atoms]
@@ -739,8 +881,8 @@ class ScreeningSweep:
         sizes = [int(ligands[k][2].shape[1]) for k in small]
         counts = [int(ligands[k][2].shape[0]) for k in small]
         plan = plan_library(counts, sizes, self.b, max_lig_atoms)
-        out, kept = {}, []
-        with self._sweeping(predictions_file, sigmoid) as (sigmoid, writer):
+        out, kept, kept_raw = {}, [], []
+        with self._sweeping(predictions_file, sigmoid, hits_file) as sink:
             if plan:
                 # the whole library packed once, in plan order: a batch is a contiguous range of it
                 all_pos = torch.cat([ligands[k][2].to(dev).float().reshape(-1, 3) for k in small], 0)
@@ -757,7 +899,7 @@ class ScreeningSweep:
                 nonlocal next_large
                 while next_large < len(large) and large[next_large] < k:
                     name, lig_feats, poses = ligands[large[next_large]]
-                    out[name] = self._run_ligand(name, lig_feats, poses, sigmoid, writer)
+                    out[name] = self._run_ligand(name, lig_feats, poses, sink)
                     next_large += 1
 
             for b, batch in enumerate(plan):
@@ -767,12 +909,13 @@ class ScreeningSweep:
                 at += total
                 if self.capture and screen.reuse and not screen.graphnorm and not screen._captured:
                     screen.capture()
-                y = (screen.replay().clone() if screen._captured else screen()).reshape(self.b, -1)
-                if sigmoid:
-                    y = torch.sigmoid(y)
+                raw = (screen.replay().clone() if screen._captured else screen()).reshape(self.b, -1)
+                y = sink.scored(raw)
                 kept.append(y[:len(batch)])
+                if sink.raw is not None:
+                    kept_raw.append(raw[:len(batch)])
                 self.batches_run += 1
-                if writer is not None:
+                if sink.writers:
                     lo = 0
                     while lo < len(batch):      # one submit per run of slots that no larger ligand interrupts
                         run_large_before(small[batch[lo][0]])
@@ -780,14 +923,17 @@ class ScreeningSweep:
                         stop = large[next_large] if next_large < len(large) else len(ligands)
                         while hi < len(batch) and small[batch[hi][0]] < stop:
                             hi += 1
-                        writer.submit(y[lo:hi, 0], None, [self.receptor_name] * (hi - lo),
-                                      [f'{ligands[small[lig]][0]}_pose{pose}' for lig, pose in batch[lo:hi]])
+                        sink.write(y[lo:hi], [f'{ligands[small[lig]][0]}_pose{pose}' for lig, pose in batch[lo:hi]])
                         lo = hi
             run_large_before(len(ligands))
             if plan:
                 screen.check()
                 scores, at = torch.cat(kept, 0), 0
+                raw_scores = torch.cat(kept_raw, 0) if kept_raw else None
                 for k, c in zip(small, counts):
                     out[ligands[k][0]] = scores[at:at + c]
+                    if raw_scores is not None:
+                        sink.keep_raw(ligands[k][0], raw_scores[at:at + c])
                     at += c
+            self._pick_hits(names, sink, hits_file)
         return {name: out[name] for name, _, _ in ligands}
