@@ -508,6 +508,26 @@ int pvs_pool_heads_fwd(const float* h, const int32_t* graph_ptr, const PvsHead* 
 int pvs_segment_argmax(const float* scores, int32_t n_cols, int32_t column, const int32_t* seg_ptr, int32_t n_segments,
                        int32_t* best, float* best_rows, pvs_stream_t stream);
 
+/* Leave-one-atom-out copies of a set of ligands as the slots of a pose batch (atom masking of a sweep's hits through
+ * pvs_screen_graph_build_ragged_cap: attribution_fns.py:365-431 removes an atom together with its edges, which is the
+ * radius graph of the atoms that remain). lig_pos [n_rows, 3], lig_feats [n_rows, n_feats], lig_ptr [n_ligands + 1]
+ * (DEVICE): ligand s has n_s = lig_ptr[s + 1] - lig_ptr[s] atoms and owns n_s + 1 consecutive copies - the whole
+ * ligand, then the ligand without atom 0, without atom 1, ... (the remaining rows keep their order). Its first copy is
+ * number lig_ptr[s] + s; there are lig_ptr[n_ligands] + n_ligands copies in all.
+ * Slot k of the batch holds copy first_copy[0] + k (first_copy: ONE int32 in DEVICE memory, so that the host advances
+ * it without a launch argument changing); a slot whose copy number is not one of the copies holds nothing. out_ptr
+ * [n_slots + 1] = the prefix sum of the slots' atom counts, the rows [out_ptr[k], out_ptr[k + 1]) of out_pos / out_feats
+ * = the copy's atoms; out_pos and out_feats have room for n_slots * slot_cap rows, those from out_ptr[n_slots] on are
+ * left as they are.
+ *   *status is stored by every launch: 0, or bit 3 (the screen builders' "not such a table") when lig_ptr does not
+ *   ascend from 0 to at most n_rows or a ligand has more than slot_cap (1..1024) atoms; out_ptr is all zeros then and
+ *   no row is written.
+ * One launch, no atomics, no workspace: the same bits every time. */
+int pvs_leave_out_ligand_pack(const float* lig_pos, const float* lig_feats, const int32_t* lig_ptr, int32_t n_ligands,
+                              int32_t n_rows, int32_t n_feats, const int32_t* first_copy, int32_t n_slots,
+                              int32_t slot_cap, float* out_pos, float* out_feats, int32_t* out_ptr, int32_t* status,
+                              pvs_stream_t stream);
+
 /* nn.BCEWithLogitsLoss() with its default mean reduction (point_neural_network_base.py:74, used at :365) over n logits:
  * loss[0] = mean(max(x, 0) - x t + log1p(exp(-|x|))), grad[i] = (sigmoid(x_i) - t_i) / n (what the backward scales by
  * the upstream gradient: pvs_scale_by_device_scalar, out[i] = a[i] * scalar[0] with the scalar in device memory). */

@@ -155,6 +155,8 @@ _PROTOTYPES = {
                            [C.c_int32] * 3 + [C.c_void_p]),
     'pvs_segment_argmax': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                      C.c_void_p]),
+    'pvs_leave_out_ligand_pack': (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 3 + [C.c_void_p, C.c_int32, C.c_int32] +
+                                  [C.c_void_p] * 4 + [C.c_void_p]),
     'pvs_bce_logits_fwd': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     'pvs_scale_by_device_scalar': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     'pvs_segment_workspace_bytes': (C.c_size_t, [C.c_int32, C.c_int32]),
@@ -197,7 +199,7 @@ _PROTOTYPES = {
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)
-MIN_VERSION = 106       # pvs_version() of the library these prototypes describe (106: several heads on one pooled row, best row per segment)
+MIN_VERSION = 107       # pvs_version() of the library these prototypes describe (107: leave-one-atom-out pose-batch slots)
 _lib = None
 
 

@@ -573,6 +573,47 @@ def segment_argmax(scores, seg_ptr, column=0):
     return best, rows
 
 
+def leave_out_ligand_pack(lig_pos, lig_feats, lig_ptr, first_copy, n_slots, slot_cap, out=None):
+    """Leave-one-atom-out copies of a set of ligands as the slots of a pose batch (pvs_leave_out_ligand_pack).
+    lig_pos [L, 3], lig_feats [L, F] fp32, lig_ptr [S + 1] int32, first_copy: one int32, all on the device. Ligand s owns
+    the copies lig_ptr[s] + s ..: the whole ligand, then the ligand without atom 0, 1, ...; slot k of the batch holds
+    copy first_copy + k (nothing past the last copy). Returns (out_pos [n_slots * slot_cap, 3], out_feats [.., F],
+    out_ptr [n_slots + 1] int32, status [1] int32): the rows [out_ptr[k], out_ptr[k + 1]) are slot k's atoms, the rows
+    from out_ptr[n_slots] on are not written. `out`: those four tensors to write into (at least that large). status:
+    8 when lig_ptr does not ascend from 0 inside L or a ligand has more than slot_cap atoms (out_ptr all zeros, no
+    row written). One launch, no atomics, no host synchronisation."""
+    lig_pos, lig_feats = _c(lig_pos, _F32, _FP32_ONLY), _c(lig_feats, _F32, _FP32_ONLY)
+    n_slots, slot_cap = int(n_slots), int(slot_cap)
+    if (lig_pos.dim() != 2 or lig_pos.shape[1] != 3 or lig_feats.dim() != 2 or lig_feats.shape[0] != lig_pos.shape[0]
+            or lig_feats.shape[1] < 1):
+        raise ValueError('leave_out_ligand_pack: lig_pos [L, 3] and lig_feats [L, F] of the same L')
+    if lig_ptr.dtype != torch.int32 or lig_ptr.dim() != 1 or lig_ptr.numel() < 1:
+        raise ValueError('leave_out_ligand_pack: an int32 lig_ptr [S + 1]')
+    if first_copy.dtype != torch.int32 or first_copy.numel() < 1:
+        raise ValueError('leave_out_ligand_pack: first_copy is one int32 on the device')
+    if n_slots < 1 or slot_cap < 1:
+        raise ValueError(f'leave_out_ligand_pack: {n_slots} slots of up to {slot_cap} atoms')
+    _lib.require_hip(lig_pos, lig_feats, lig_ptr, first_copy)
+    dev, n_feats, rows = lig_pos.device, lig_feats.shape[1], n_slots * slot_cap
+    if out is None:
+        out = (torch.empty((rows, 3), dtype=torch.float32, device=dev),
+               torch.empty((rows, n_feats), dtype=torch.float32, device=dev),
+               torch.empty(n_slots + 1, dtype=torch.int32, device=dev), torch.empty(1, dtype=torch.int32, device=dev))
+    out_pos, out_feats, out_ptr, status = out
+    _lib.require_hip(*out)
+    if (out_pos.dtype != torch.float32 or out_feats.dtype != torch.float32 or out_pos.dim() != 2 or out_feats.dim() != 2
+            or out_pos.shape[0] < rows or out_pos.shape[1] != 3 or out_feats.shape[0] < rows
+            or out_feats.shape[1] != n_feats or out_ptr.dtype != torch.int32 or out_ptr.numel() != n_slots + 1
+            or status.dtype != torch.int32 or status.numel() < 1):
+        raise ValueError(f'leave_out_ligand_pack: out = (pos [>= {rows}, 3], feats [>= {rows}, {n_feats}], int32 ptr '
+                         f'[{n_slots + 1}], int32 status [1])')
+    _lib.check(_lib.lib().pvs_leave_out_ligand_pack(
+        _lib.ptr(lig_pos), _lib.ptr(lig_feats), _lib.ptr(lig_ptr), lig_ptr.numel() - 1, lig_pos.shape[0], n_feats,
+        _lib.ptr(first_copy), n_slots, slot_cap, _lib.ptr(out_pos), _lib.ptr(out_feats), _lib.ptr(out_ptr),
+        _lib.ptr(status), _stream(dev)), 'pvs_leave_out_ligand_pack')
+    return out_pos, out_feats, out_ptr, status
+
+
 class _BceLogitsMeanFn(torch.autograd.Function):
     """nn.BCEWithLogitsLoss() (mean) as one launch forward (loss + the gradient factor), one backward."""
 

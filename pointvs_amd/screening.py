@@ -419,6 +419,23 @@ def plan_library(pose_counts, lig_sizes, batch_size, max_lig_atoms=64):
     return batches
 
 
+def leave_out_plan(sizes, batch_size):
+    """Slot sizes of the batches that hold every leave-one-atom-out copy of ligands of `sizes` atoms: ligand s owns
+    sizes[s] + 1 consecutive copies (the whole ligand: sizes[s] atoms; then one copy per atom left out: sizes[s] - 1),
+    sum(sizes) + len(sizes) copies in all, `batch_size` per batch in that order. A list of batches, each a list of
+    `batch_size` atom counts; the slots after the last copy are empty (0). What pvs_leave_out_ligand_pack lays out on
+    the device, as pure host arithmetic."""
+    batch_size = int(batch_size)
+    if batch_size < 1:
+        raise ValueError(f'batch_size must be positive (got {batch_size})')
+    sizes = [int(n) for n in sizes]
+    if any(n < 0 for n in sizes):
+        raise ValueError(f'ligand sizes must not be negative (got {sizes})')
+    copies = [m for n in sizes for m in [n] + [n - 1] * n]
+    copies += [0] * ((-len(copies)) % batch_size)
+    return [copies[k:k + batch_size] for k in range(0, len(copies), batch_size)]
+
+
 class LibraryScreen(_ReceptorSideScreen):
     """Library screening: every one of the `batch_size` slots of a batch holds one pose of ANY ligand of up to
     `max_lig_atoms` (<= MAX_SCREEN_LIGAND_ATOMS = 1024) atoms against the one receptor, or nothing (the last batch of
@@ -463,6 +480,7 @@ class LibraryScreen(_ReceptorSideScreen):
         self.n_atoms = 0             # host copies of what load() was given
         self._sizes = [0] * self.b
         self._stage, self._stage_at = [], 0
+        self._pack_status = None     # load_leave_out's status word
         if self.reuse:
             self._cache_receptor_sums()
 
@@ -523,6 +541,30 @@ class LibraryScreen(_ReceptorSideScreen):
         st['event'] = torch.cuda.Event()
         st['event'].record(torch.cuda.current_stream(self.lig_pos.device))
         return self
+
+    def load_leave_out(self, lig_pos, lig_feats, lig_ptr, sizes, first_copy):
+        """One batch of leave-one-atom-out copies (PF.leave_out_ligand_pack: slot k holds copy first_copy + k of the
+        ligands lig_pos [L,3] / lig_feats [L,F] / lig_ptr [S+1] int32, all on the device; first_copy: one int32 on the
+        device), packed by one launch straight into the step's static inputs. `sizes`: the host's copy of the slots'
+        atom counts (a batch of `leave_out_plan`); nothing is copied back. `check_leave_out()` reads the packer's
+        verdict on lig_ptr."""
+        sizes = [int(n) for n in sizes]
+        if len(sizes) > self.b or any(not 0 <= n <= self.max_lig_atoms for n in sizes):
+            raise ValueError(f'a batch holds up to {self.b} slots of 0..{self.max_lig_atoms} atoms (got {sizes})')
+        if self._pack_status is None:
+            self._pack_status = torch.zeros(1, dtype=torch.int32, device=self.lig_pos.device)
+        PF.leave_out_ligand_pack(lig_pos, lig_feats, lig_ptr, first_copy, self.b, self.max_lig_atoms,
+                                 out=(self.lig_pos, self.lig_feats, self.lig_ptr, self._pack_status))
+        self._sizes = sizes + [0] * (self.b - len(sizes))
+        self.n_atoms = sum(sizes)
+        return self
+
+    def check_leave_out(self):
+        """Raises if the last load_leave_out() was given a lig_ptr that is no table of 0..max_lig_atoms-atom ligands
+        (its batch was empty then). Waits for the device."""
+        if self._pack_status is not None and int(self._pack_status.item()) & 8:
+            raise ValueError(f'LibraryScreen.load_leave_out: lig_ptr is not a table of 0..{self.max_lig_atoms}-atom '
+                             'ligands inside lig_pos')
 
     # ---- the graph and the node tables ----
     def _buffers(self, cap, cap_l):
@@ -744,7 +786,8 @@ class ScreeningSweep:
     to `pose_<name>` and `affinity_<name>` beside the path given (`val`'s naming), same line order. `hits_file` (any
     model): after the sweep the best pose of every ligand is picked on the device (PF.segment_argmax on the raw
     column 0: larger wins, ties to the lower pose, NaN never wins) and written one line per ligand; `sweep.hits`
-    keeps {name: (best pose or -1, its row)}.
+    keeps {name: (best pose or -1, its row)}. `ligand_atom_masking(best_poses(ligands))` then says which ligand atoms
+    carry each hit's score: every leave-one-atom-out copy of every hit as a LibraryScreen slot.
     """
 
     def __init__(self, model, rec_pos, rec_feats, edge_radius, batch_size=32, intra_radius=None, capture=True,
@@ -752,10 +795,12 @@ class ScreeningSweep:
         self.model, self.rec_pos, self.rec_feats = model, rec_pos, rec_feats
         self.tasks = _resolve_tasks(model, tasks)
         self.hits = {}
+        self.atom_masking_raw = {}     # ligand_atom_masking: {name: raw rows [n + 1, C], whole ligand first}
         self.edge_radius, self.intra_radius, self.b = edge_radius, intra_radius, int(batch_size)
         self.capture, self.receptor_name = capture, receptor_name
         self.buckets = {}          # n_lig -> ReceptorScreen (captured when possible)
         self.library = None        # the LibraryScreen of run_library
+        self.masking = None        # the LibraryScreen of ligand_atom_masking (its edge room is sized for whole ligands)
         self.batches_run = 0
 
     def _bucket(self, n_lig, lig_feats, example_poses):
@@ -855,12 +900,20 @@ class ScreeningSweep:
             self._pick_hits(names, sink, hits_file)
         return out
 
-    def _library_screen(self, max_atoms):
-        screen = self.library
+    def _library_screen(self, max_atoms, which='library'):
+        screen = getattr(self, which)
         if screen is None or screen.stale() or screen.max_lig_atoms < max_atoms:
-            screen = self.library = LibraryScreen(self.model, self.rec_pos, self.rec_feats, self.b, max_atoms,
-                                                  self.edge_radius, self.intra_radius, tasks=self.tasks)
+            screen = LibraryScreen(self.model, self.rec_pos, self.rec_feats, self.b, max_atoms, self.edge_radius,
+                                   self.intra_radius, tasks=self.tasks)
+            setattr(self, which, screen)
         return screen
+
+    def _library_step(self, screen):
+        """The raw outputs [batch_size, C] of the batch loaded into `screen`: the captured step where one can be had
+        (captured at the first batch), the eager one otherwise."""
+        if self.capture and screen.reuse and not screen.graphnorm and not screen._captured:
+            screen.capture()
+        return (screen.replay().clone() if screen._captured else screen()).reshape(self.b, -1)
 
     @torch.no_grad()
     def run_library(self, ligands, predictions_file=None, sigmoid=None, max_lig_atoms=64, hits_file=None):
@@ -907,9 +960,7 @@ class ScreeningSweep:
                 total = int(ptrs[b, -1])
                 screen.load_packed(all_pos[at:at + total], all_feats[at:at + total], ptrs_dev[b], batch_sizes)
                 at += total
-                if self.capture and screen.reuse and not screen.graphnorm and not screen._captured:
-                    screen.capture()
-                raw = (screen.replay().clone() if screen._captured else screen()).reshape(self.b, -1)
+                raw = self._library_step(screen)
                 y = sink.scored(raw)
                 kept.append(y[:len(batch)])
                 if sink.raw is not None:
@@ -937,3 +988,83 @@ class ScreeningSweep:
                     at += c
             self._pick_hits(names, sink, hits_file)
         return {name: out[name] for name, _, _ in ligands}
+
+    def best_poses(self, ligands):
+        """(name, lig_feats, poses[best]) of every ligand of `ligands` - what `run` / `run_library(hits_file=...)` was
+        given - that has a best pose in `self.hits`; a ligand without one (no poses, NaN scores only) is skipped. What
+        `ligand_atom_masking` takes."""
+        for name, lig_feats, poses in ligands:
+            best = self.hits.get(name, (-1, None))[0]
+            if best >= 0:
+                yield name, lig_feats, poses[best]
+
+    @torch.no_grad()
+    def ligand_atom_masking(self, items, scores_file=None, sigmoid=None, column=0):
+        """Atom masking (the reference's attribution_fns.atom_masking, :365-431) of the LIGAND atoms of many complexes
+        with this receptor: items = iterable of (name, lig_feats [n,F], pose [n,3]), n <= MAX_SCREEN_LIGAND_ATOMS,
+        unique names. A complex without ligand atom a is a pose of an (n - 1)-atom ligand, and its radius graph is what
+        the reference's masking leaves (the atom goes together with its edges): every item's n + 1 copies - the whole
+        ligand, then one per atom left out - stream through ONE LibraryScreen in dense batches, laid out on the device
+        (LibraryScreen.load_leave_out: one packer launch per batch, then the one captured step), ceil((sum n +
+        len(items)) / batch_size) steps in all (and, for a new screen, one batch of the batch_size largest whole ligands
+        before them, from which the screen sizes its edge buffers).
+        Returns {name: scores [n] on the device}, scores[a] = s(y_whole[column]) - s(y_without_a[column]), s = the
+        sigmoid where a sweep applies it to that column (`sigmoid` as in `run`; False: raw differences);
+        `self.atom_masking_raw[name]` keeps the raw rows [n + 1, C], whole ligand first. scores_file: one line per
+        ligand atom, item order then atom order, '{score:.6f} | {receptor} {name}_atom{a}'."""
+        from .predictions import PredictionsWriter
+        items = [(name, lig_feats, pose) for name, lig_feats, pose in items]
+        names = [name for name, _, _ in items]
+        if len(set(names)) != len(names):
+            raise ValueError(f'ligand_atom_masking: names must be unique (repeated: '
+                             f'{sorted({n for n in names if names.count(n) > 1})})')
+        ns = []
+        for name, lig_feats, pose in items:
+            n = int(pose.shape[0])
+            if n > MAX_SCREEN_LIGAND_ATOMS:
+                raise ValueError(f'ligand_atom_masking: ligand {name!r} has {n} atoms: a pose-batch slot holds up to '
+                                 f'{MAX_SCREEN_LIGAND_ATOMS}')
+            if pose.dim() != 2 or pose.shape[1] != 3 or lig_feats.dim() != 2 or int(lig_feats.shape[0]) != n:
+                raise ValueError(f'ligand_atom_masking: ligand {name!r}: lig_feats [n, F] and ONE pose [n, 3]')
+            ns.append(n)
+        self.atom_masking_raw = {}
+        if not items:
+            return {}
+        dev = self.rec_pos.device
+        screen = self._library_screen(max(max(ns), 1), 'masking')
+        if screen.reuse and screen._fast is None:
+            # a new screen sizes its edge buffers from its first batch, and the first leave-out batch may hold the
+            # copies of one small ligand: it is shown a batch of the largest whole ligands first (a copy has no more
+            # contacts per atom than its whole ligand)
+            big = sorted(range(len(items)), key=lambda i: -ns[i])[:self.b]
+            screen([(items[i][1], items[i][2]) for i in big])
+            self.batches_run += 1
+        all_pos = torch.cat([pose.to(dev).float() for _, _, pose in items], 0).contiguous()
+        all_feats = torch.cat([lig_feats.to(dev).float() for _, lig_feats, _ in items], 0).contiguous()
+        lig_ptr = torch.tensor([0] + ns).cumsum(0).to(device=dev, dtype=torch.int32)
+        plan = leave_out_plan(ns, self.b)
+        total = sum(ns) + len(ns)
+        firsts = (torch.arange(len(plan), dtype=torch.int32) * self.b).to(dev)     # batch k starts at copy k * b
+        kept = []
+        with self._sweeping(None, sigmoid, None) as sink:
+            for k, batch_sizes in enumerate(plan):
+                screen.load_leave_out(all_pos, all_feats, lig_ptr, batch_sizes, firsts[k:k + 1])
+                kept.append(self._library_step(screen))
+                self.batches_run += 1
+            screen.check()
+            screen.check_leave_out()
+            raw = torch.cat(kept, 0)[:total]
+            if not 0 <= int(column) < raw.shape[1]:
+                raise ValueError(f'ligand_atom_masking: column {column} of {raw.shape[1]} outputs')
+            scored = sink.scored(raw)[:, int(column)]
+        out, at = {}, 0
+        for name, n in zip(names, ns):
+            self.atom_masking_raw[name] = raw[at:at + n + 1]
+            out[name] = scored[at] - scored[at + 1:at + n + 1]
+            at += n + 1
+        if scores_file:
+            with PredictionsWriter(scores_file, 'atom_masking') as writer:
+                if sum(ns):
+                    writer.submit(torch.cat([out[name] for name in names], 0), None, [self.receptor_name] * sum(ns),
+                                  [f'{name}_atom{a}' for name, n in zip(names, ns) for a in range(n)])
+        return out
