@@ -261,6 +261,15 @@ int pvs_egnn_layer_fwd_partial(const PvsLayerDesc* desc, const PvsGraph* graph, 
                                const float* h, const float* x, const float* base_magg, const float* base_xsum,
                                const float* base_deg, float* h_out, float* x_out, float* node_att_out,
                                float* saved, void* workspace, size_t workspace_bytes, pvs_stream_t stream);
+/* pvs_egnn_layer_fwd_partial that also hands out the layer's edge attention: att_out [>= max(E, 1)], CSR-sorted over
+ * `graph` (entry e belongs to edge e of graph->row / col; with a device-side edge count the entries from that count
+ * on are left as they are), or NULL: the attention stays in the workspace, which is pvs_egnn_layer_fwd_partial -
+ * the same launches, the same h_out / x_out bits either way. Meaningful for a layer with PVS_EDGE_ATTENTION. */
+int pvs_egnn_layer_fwd_partial_att(const PvsLayerDesc* desc, const PvsGraph* graph, const PvsLayerParams* params,
+                                   const float* h, const float* x, const float* base_magg, const float* base_xsum,
+                                   const float* base_deg, float* h_out, float* x_out, float* node_att_out,
+                                   float* att_out, float* saved, void* workspace, size_t workspace_bytes,
+                                   pvs_stream_t stream);
 
 /* The edges of `full` that touch a ligand atom (bp == 0), as a CSR over the same nodes, without a
  * host round trip: rowptr_out [N+1] (its last entry = the edge count, pass it as
@@ -527,6 +536,30 @@ int pvs_leave_out_ligand_pack(const float* lig_pos, const float* lig_feats, cons
                               int32_t n_rows, int32_t n_feats, const int32_t* first_copy, int32_t n_slots,
                               int32_t slot_cap, float* out_pos, float* out_feats, int32_t* out_ptr, int32_t* status,
                               pvs_stream_t stream);
+
+/* Contact attention of a pose batch (the reference's attribution/hotspot.py over attribution_fns.edge_attention,
+ * :278-295: per atom the largest attention value over its ligand-receptor edges, per receptor atom the mean of these
+ * over the binding events in which it has a contact), reduced on the device over the compact pose-batch layout of
+ * pvs_screen_graph_build_ragged_cap: slot p owns the rows node_ptr[p] .. node_ptr[p + 1] (node_ptr[p] = lig_ptr[p] +
+ * p * n_rec; node_ptr, lig_ptr: DEVICE, [n_slots + 1]), its lig_ptr[p + 1] - lig_ptr[p] ligand atoms first, then the
+ * n_rec receptor atoms. rowptr [n_nodes + 1] / etype [n_edges] are either CSR of such a batch (the ligand-touching one
+ * or the full one) and att [n_edges] one attention value per edge in THAT CSR's order. An edge counts when its class
+ * is 1 (ligand-receptor) wherever it stands in its row; a NaN value is skipped.
+ *   lig_att [>= lig_ptr[n_slots]]: per packed ligand atom the largest counted value of its row, NaN for a row without
+ *     one; the entries from lig_ptr[n_slots] on are left as they are.
+ *   slot_rec_att [n_slots, n_rec]: the same for every receptor atom of every slot (an empty slot: NaN).
+ *   rec_sum [n_rec] double, rec_count [n_rec] int32, rec_max [n_rec] float are READ AND UPDATED, so that a captured
+ *     step accumulates over its replays: rec_sum += the slot values that are not NaN, added in slot order; rec_count +=
+ *     how many there were; rec_max = the largest value so far (a NaN in rec_max means none so far: start it there).
+ * Equal values are one value (+0.0 above -0.0), so no result depends on the order in which the edges of a row meet;
+ * no atomics: the same bits every time, whatever the launch geometry. A slot whose two tables disagree, that has more
+ * than 1024 ligand atoms or whose rows end beyond n_nodes - n_slots * n_rec ligand rows is no slot (NaN, nothing
+ * accumulated); edge ranges are clamped to [0, n_edges), so a rowptr of a build that overflowed its edge buffers
+ * reads nothing outside them. n_slots == 0 or n_rec == 0: nothing to do, returns 0 without a launch. Two launches. */
+int pvs_contact_attention(const int32_t* rowptr, const uint8_t* etype, const float* att, int32_t n_nodes,
+                          int32_t n_edges, const int32_t* node_ptr, const int32_t* lig_ptr, int32_t n_slots,
+                          int32_t n_rec, float* lig_att, float* slot_rec_att, double* rec_sum, int32_t* rec_count,
+                          float* rec_max, pvs_stream_t stream);
 
 /* nn.BCEWithLogitsLoss() with its default mean reduction (point_neural_network_base.py:74, used at :365) over n logits:
  * loss[0] = mean(max(x, 0) - x t + log1p(exp(-|x|))), grad[i] = (sigmoid(x_i) - t_i) / n (what the backward scales by

@@ -134,7 +134,10 @@ _PROTOTYPES = {
     'pvs_egnn_layer_fwd_partial': (C.c_int, [C.POINTER(PvsLayerDesc), C.POINTER(PvsGraph),
                                              C.POINTER(PvsLayerParams)] + [C.c_void_p] * 9 +
                                    [C.c_void_p, C.c_size_t, C.c_void_p]),
-    'pvs_egnn_layer_bwd': (C.c_int, [C.POINTER(PvsLayerDesc), C.POINTER(PvsGraph),
+    'pvs_egnn_layer_fwd_partial_att': (C.c_int, [C.POINTER(PvsLayerDesc), C.POINTER(PvsGraph),
+                                                 C.POINTER(PvsLayerParams)] + [C.c_void_p] * 10 +
+                                       [C.c_void_p, C.c_size_t, C.c_void_p]),
+    'pvs_egnn_layer_bwd':(C.c_int, [C.POINTER(PvsLayerDesc), C.POINTER(PvsGraph),
                                      C.POINTER(PvsLayerParams)] + [C.c_void_p] * 11 +
                            [C.POINTER(PvsLayerGrads), C.c_void_p, C.c_size_t, C.c_void_p]),
     'pvs_egnn_stack_workspace_bytes': (C.c_size_t, [C.POINTER(PvsLayerDesc), C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
@@ -157,6 +160,8 @@ _PROTOTYPES = {
                                      C.c_void_p]),
     'pvs_leave_out_ligand_pack': (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 3 + [C.c_void_p, C.c_int32, C.c_int32] +
                                   [C.c_void_p] * 4 + [C.c_void_p]),
+    'pvs_contact_attention': (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 2 + [C.c_void_p] * 2 + [C.c_int32] * 2 +
+                              [C.c_void_p] * 5 + [C.c_void_p]),
     'pvs_bce_logits_fwd': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     'pvs_scale_by_device_scalar': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     'pvs_segment_workspace_bytes': (C.c_size_t, [C.c_int32, C.c_int32]),
@@ -199,7 +204,7 @@ _PROTOTYPES = {
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)
-MIN_VERSION = 107       # pvs_version() of the library these prototypes describe (107: leave-one-atom-out pose-batch slots)
+MIN_VERSION = 108       # pvs_version() of the library these prototypes describe (108: contact attention of a pose batch)
 _lib = None
 
 

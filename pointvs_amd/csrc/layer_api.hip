@@ -421,11 +421,11 @@ extern "C" int pvs_egnn_layer_edge_sums(const PvsLayerDesc* d, const PvsGraph* g
     return 0;
 }
 
-extern "C" int pvs_egnn_layer_fwd_partial(const PvsLayerDesc* d, const PvsGraph* g, const PvsLayerParams* p,
-                                          const float* h, const float* x, const float* base_magg,
-                                          const float* base_xsum, const float* base_deg, float* h_out,
-                                          float* x_out, float* node_att_out, float* saved, void* workspace,
-                                          size_t workspace_bytes, pvs_stream_t stream_) {
+extern "C" int pvs_egnn_layer_fwd_partial_att(const PvsLayerDesc* d, const PvsGraph* g, const PvsLayerParams* p,
+                                              const float* h, const float* x, const float* base_magg,
+                                              const float* base_xsum, const float* base_deg, float* h_out,
+                                              float* x_out, float* node_att_out, float* att_out, float* saved,
+                                              void* workspace, size_t workspace_bytes, pvs_stream_t stream_) {
     hipStream_t s = (hipStream_t)stream_;
     PvsEdgeFamily fam;
     PVS_TRY(partial_checks(d, g, p, &fam));
@@ -436,8 +436,9 @@ extern "C" int pvs_egnn_layer_fwd_partial(const PvsLayerDesc* d, const PvsGraph*
     PvsArena arena(workspace, workspace_bytes);
     FwdWs w;
     carve_fwd(arena, m, &w);
-    float* att = arena.take<float>((size_t)(m.E > 0 ? m.E : 1));
+    float* att = arena.take<float>((size_t)(m.E > 0 ? m.E : 1));      // (carved either way: one workspace size)
     PVS_REQUIRE(arena.ok(), "pvs_egnn_layer_fwd_partial: workspace too small (%zu < %zu)", workspace_bytes, arena.off);
+    if (att_out) att = att_out;       // the caller keeps the layer's attention (CSR-sorted over g)
     const int H = m.H;
     const SavedLayout sv = saved_layout(saved, m.N, H);
     const PvsEdgeW ew = make_edge_w(m, p);
@@ -456,6 +457,15 @@ extern "C" int pvs_egnn_layer_fwd_partial(const PvsLayerDesc* d, const PvsGraph*
     PVS_TRY(node_mlp_forward(s, m, d, p, nw, h, sv.Magg, sv.y1, sv.u, sv.o, sv.stats, true, w.shift, w.slabs, h_out,
                              node_att_out));
     return 0;
+}
+
+extern "C" int pvs_egnn_layer_fwd_partial(const PvsLayerDesc* d, const PvsGraph* g, const PvsLayerParams* p,
+                                          const float* h, const float* x, const float* base_magg,
+                                          const float* base_xsum, const float* base_deg, float* h_out,
+                                          float* x_out, float* node_att_out, float* saved, void* workspace,
+                                          size_t workspace_bytes, pvs_stream_t stream_) {
+    return pvs_egnn_layer_fwd_partial_att(d, g, p, h, x, base_magg, base_xsum, base_deg, h_out, x_out, node_att_out,
+                                          nullptr, saved, workspace, workspace_bytes, stream_);
 }
 
 extern "C" int pvs_egnn_layer_bwd(const PvsLayerDesc* d, const PvsGraph* g, const PvsLayerParams* p,

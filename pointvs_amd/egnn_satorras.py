@@ -77,6 +77,9 @@ class EGNNLayer(nn.Module):
             'sigmoid': nn.Sigmoid, 'tanh': nn.Tanh, 'relu': nn.ReLU, 'silu': nn.SiLU,
             'identity': nn.Identity}[self.attention_activation_name]
         self._att_src = self._natt_src = self._coords_src = None
+        # the edge attention of the last forward_prepared call as the kernel wrote it: a device tensor in the prepared
+        # graph's CSR-sorted edge order (what _att_src permutes on demand), or None
+        self._att_sorted = None
 
         # construction order follows the reference so a given torch seed yields the same init
         self.edge_mlp = nn.Sequential(
@@ -248,7 +251,7 @@ class EGNNLayer(nn.Module):
         over device tensors of the last call; `att_val` etc. read None on the copy until its own first forward)."""
         state = self.__dict__.copy()
         state.pop('_pcache', None)
-        for k in ('_att_src', '_natt_src', '_coords_src'):
+        for k in ('_att_src', '_att_sorted', '_natt_src', '_coords_src'):
             if k in state:
                 state[k] = None
         return state
@@ -326,6 +329,7 @@ class EGNNLayer(nn.Module):
                 h, coord, m_prev_sorted, pg, desc, need_m, params, pstruct)
         # (plain attributes through __dict__: nn.Module.__setattr__ costs 2-3 us a piece on the host, three per layer call)
         d = self.__dict__
+        d['_att_sorted'] = att
         d['_att_src'] = None if att is None else (
             lambda: PF.rows_to_input_order(att.detach()[:pg.n_edges].reshape(-1, 1), pg))
         d['_natt_src'] = None if natt is None else (lambda: natt.detach().reshape(-1, 1))
@@ -361,7 +365,7 @@ class EGNNLayer(nn.Module):
                 m = gate * m + (1 - gate) * m_prev_sorted
             else:
                 m = m + m_prev_sorted
-        self._att_src = self._natt_src = None
+        self._att_src = self._att_sorted = self._natt_src = None
         if skip_coords:
             x_out = coord
             self._coords_src = lambda h=h.detach(), coord=coord.detach(), mp=(

@@ -614,6 +614,54 @@ def leave_out_ligand_pack(lig_pos, lig_feats, lig_ptr, first_copy, n_slots, slot
     return out_pos, out_feats, out_ptr, status
 
 
+def new_contact_accumulators(n_rec, device):
+    """Fresh accumulators of `contact_attention`: (rec_sum [n_rec] float64 zeros, rec_count [n_rec] int32 zeros,
+    rec_max [n_rec] float32 NaN: none so far)."""
+    return (torch.zeros(n_rec, dtype=torch.float64, device=device), torch.zeros(n_rec, dtype=torch.int32, device=device),
+            torch.full((n_rec,), float('nan'), dtype=torch.float32, device=device))
+
+
+def contact_attention(rowptr, etype, att, node_ptr, lig_ptr, n_rec, out=None):
+    """Contact attention of a pose batch (pvs_contact_attention): rowptr [N + 1] int32 / etype [E] uint8 - either CSR
+    of a compact pose batch (slot p: the rows node_ptr[p] .. node_ptr[p + 1], its lig_ptr[p + 1] - lig_ptr[p] ligand
+    atoms, then the n_rec receptor atoms; node_ptr, lig_ptr [n_slots + 1] int32) - and att [>= E] fp32, one value per
+    edge in that CSR's order, all on the device. Returns (lig_att [N - n_slots * n_rec], slot_rec_att [n_slots, n_rec],
+    rec_sum [n_rec] float64, rec_count [n_rec] int32, rec_max [n_rec]): per packed ligand atom and per (slot, receptor
+    atom) the largest att over the row's class-1 (ligand-receptor) edges, NaN without one (NaN values are skipped; the
+    lig_att rows from lig_ptr[n_slots] on are not written); rec_sum / rec_count / rec_max are UPDATED with the slot
+    values that are not NaN, in slot order (fresh ones: new_contact_accumulators). `out`: those five tensors to write
+    into and accumulate on. Two launches, no atomics, no host synchronisation: the same bits every time."""
+    att = _c(att, _F32, _FP32_ONLY)
+    n_rec = int(n_rec)
+    if (rowptr.dtype != torch.int32 or rowptr.dim() != 1 or rowptr.numel() < 1 or etype.dtype != torch.uint8
+            or etype.dim() != 1 or att.dim() != 1 or att.numel() < etype.numel()):
+        raise ValueError('contact_attention: an int32 rowptr [N + 1], a uint8 etype [E] and att [>= E]')
+    if (node_ptr.dtype != torch.int32 or lig_ptr.dtype != torch.int32 or node_ptr.dim() != 1 or node_ptr.numel() < 1
+            or lig_ptr.shape != node_ptr.shape):
+        raise ValueError('contact_attention: int32 node_ptr and lig_ptr [n_slots + 1]')
+    n_nodes, n_edges, n_slots = rowptr.numel() - 1, etype.numel(), node_ptr.numel() - 1
+    if n_rec < 0 or n_slots * n_rec > n_nodes:
+        raise ValueError(f'contact_attention: {n_nodes} rows cannot hold {n_slots} slots of {n_rec} receptor atoms')
+    _lib.require_hip(rowptr, etype, att, node_ptr, lig_ptr)
+    dev, n_lig = att.device, n_nodes - n_slots * n_rec
+    if out is None:
+        out = (torch.full((n_lig,), float('nan'), dtype=torch.float32, device=dev),
+               torch.empty((n_slots, n_rec), dtype=torch.float32, device=dev)) + new_contact_accumulators(n_rec, dev)
+    lig_att, slot_rec_att, rec_sum, rec_count, rec_max = out
+    _lib.require_hip(*out)
+    if (lig_att.dtype != torch.float32 or slot_rec_att.dtype != torch.float32 or rec_sum.dtype != torch.float64
+            or rec_count.dtype != torch.int32 or rec_max.dtype != torch.float32 or lig_att.dim() != 1
+            or lig_att.numel() < n_lig or slot_rec_att.shape != (n_slots, n_rec) or rec_sum.shape != (n_rec,)
+            or rec_count.shape != (n_rec,) or rec_max.shape != (n_rec,)):
+        raise ValueError(f'contact_attention: out = (lig_att [>= {n_lig}], slot_rec_att [{n_slots}, {n_rec}], float64 '
+                         f'rec_sum [{n_rec}], int32 rec_count [{n_rec}], rec_max [{n_rec}])')
+    _lib.check(_lib.lib().pvs_contact_attention(
+        _lib.ptr(rowptr), _lib.ptr(etype), _lib.ptr(att), n_nodes, n_edges, _lib.ptr(node_ptr), _lib.ptr(lig_ptr),
+        n_slots, n_rec, _lib.ptr(lig_att), _lib.ptr(slot_rec_att), _lib.ptr(rec_sum), _lib.ptr(rec_count),
+        _lib.ptr(rec_max), _stream(dev)), 'pvs_contact_attention')
+    return lig_att, slot_rec_att, rec_sum, rec_count, rec_max
+
+
 class _BceLogitsMeanFn(torch.autograd.Function):
     """nn.BCEWithLogitsLoss() (mean) as one launch forward (loss + the gradient factor), one backward."""
 

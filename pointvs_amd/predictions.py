@@ -13,6 +13,7 @@ Line formats (point_neural_network_base.py:287-325):
     multi_regression    '{label:.3f} | {prediction:.3f} {receptor} {ligand} | {metric}'   (labelled targets > -0.5)
                         '{p0:.3f} {p1:.3f} {p2:.3f} | {receptor} {ligand}'        (unlabelled)
     atom_masking        '{score:.6f} | {receptor} {ligand}_atom{a}'               (no reference format: per-atom scores)
+    hotspot             '{mean:.6f} {count} | {receptor} atom{j}'                 (no reference format: receptor atoms)
 """
 import queue
 import threading
@@ -40,6 +41,10 @@ def format_lines(task, y_pred, y_true, receptors, ligands):
         y_pred, y_true = y_pred[keep], y_true[keep]
         return ['{0:.3f} | {1:.3f} {2} {3} | {4}'.format(float(y_true[i]), y_pred[i], receptors[i], ligands[i],
                                                         metrics[i]) for i in range(n)]
+    if task == 'hotspot':            # (ScreeningSweep.receptor_hotspots: y_pred [n, 2] = mean, count; ligands = the atoms)
+        y_pred = np.asarray(y_pred).reshape(-1, 2)
+        return ['{0:.6f} {1} | {2} {3}'.format(y_pred[i, 0], int(y_pred[i, 1]), receptors[i], ligands[i])
+                for i in range(n)]
     y_pred = np.asarray(y_pred).reshape(-1)
     if task == 'atom_masking':       # (ScreeningSweep.ligand_atom_masking: score differences, six decimals)
         return ['{0:.6f} | {1} {2}'.format(y_pred[i], receptors[i], ligands[i]) for i in range(n)]

@@ -90,6 +90,21 @@ def _resolve_tasks(model, tasks):
     return tasks
 
 
+def resolve_attention_layer(model, layer):
+    """The index into model.layers (>= 1: layer 0 is the embedding) that `layer` names, the reference's attribution
+    `--layer` (negative: from the end); None stays None. ValueError, listing the layers that qualify, for an index
+    outside the model or a layer without edge attention. Pure host logic."""
+    if layer is None:
+        return None
+    layers = list(model.layers)
+    have = [k for k, l in enumerate(layers) if getattr(l, 'edge_attention', False)]
+    at = int(layer) + len(layers) if int(layer) < 0 else int(layer)
+    if at not in have:
+        raise ValueError(f'contact attention of layer {layer}: model.layers[{layer}] has no edge attention (the layers '
+                         f'that have it: {have}, of {len(layers)})')
+    return at
+
+
 class _ReceptorSideScreen:
     """What ReceptorScreen and LibraryScreen do alike, once: the receptor-receptor sums of the first layer and their
     weights fingerprint, the ligand-touching first layer, the layers after it, the deferred status word and the
@@ -165,9 +180,10 @@ class _ReceptorSideScreen:
             torch.cuda.current_stream(dev).synchronize()    # ws / params go out of scope
         return magg, xsum, deg
 
-    def _partial_first_layer(self, g, h, x, base_magg, base_xsum, base_deg, ws_nodes, ws_edges):
+    def _partial_first_layer(self, g, h, x, base_magg, base_xsum, base_deg, ws_nodes, ws_edges, att_out=None):
         """First layer over the ligand-touching edges `g` on top of the receptor-receptor sums `base_*` (one row
-        per node). ws_nodes / ws_edges size the saved / workspace pair, allocated at the first call."""
+        per node). ws_nodes / ws_edges size the saved / workspace pair, allocated at the first call. att_out
+        [>= g's edge room]: receives the layer's edge attention in g's edge order (pvs_egnn_layer_fwd_partial_att)."""
         lib = _lib.lib()
         dev = h.device
         desc, params, pstruct = self._first_layer_args()
@@ -180,10 +196,17 @@ class _ReceptorSideScreen:
                 torch.empty(lib.pvs_egnn_layer_workspace_bytes(C.byref(desc), ws_nodes, ws_edges, 2),
                             dtype=torch.uint8, device=dev))
         saved, ws = self._l1_ws
-        _lib.check(lib.pvs_egnn_layer_fwd_partial(
-            C.byref(desc), C.byref(g), C.byref(pstruct), _lib.ptr(h), _lib.ptr(x), _lib.ptr(base_magg),
-            _lib.ptr(base_xsum), _lib.ptr(base_deg), _lib.ptr(h_out), _lib.ptr(x_out), _lib.ptr(natt),
-            _lib.ptr(saved), _lib.ptr(ws), ws.numel(), _stream(dev)), 'pvs_egnn_layer_fwd_partial')
+        if att_out is None:
+            _lib.check(lib.pvs_egnn_layer_fwd_partial(
+                C.byref(desc), C.byref(g), C.byref(pstruct), _lib.ptr(h), _lib.ptr(x), _lib.ptr(base_magg),
+                _lib.ptr(base_xsum), _lib.ptr(base_deg), _lib.ptr(h_out), _lib.ptr(x_out), _lib.ptr(natt),
+                _lib.ptr(saved), _lib.ptr(ws), ws.numel(), _stream(dev)), 'pvs_egnn_layer_fwd_partial')
+        else:
+            _lib.check(lib.pvs_egnn_layer_fwd_partial_att(
+                C.byref(desc), C.byref(g), C.byref(pstruct), _lib.ptr(h), _lib.ptr(x), _lib.ptr(base_magg),
+                _lib.ptr(base_xsum), _lib.ptr(base_deg), _lib.ptr(h_out), _lib.ptr(x_out), _lib.ptr(natt),
+                _lib.ptr(att_out), _lib.ptr(saved), _lib.ptr(ws), ws.numel(), _stream(dev)),
+                'pvs_egnn_layer_fwd_partial_att')
         return h_out, x_out
 
     def _tail(self, pg_full, h, x):
@@ -453,10 +476,17 @@ class LibraryScreen(_ReceptorSideScreen):
     at the padded shape N_cap = batch_size * (max_lig_atoms + n_rec) (padding nodes have no edges and belong to no
     graph), eager and captured alike; graphnorm normalises over the batch's nodes, so such models run eager at the
     exact node count. Models the first-layer reuse does not cover (edge_residual, softmax attention, hidden size not
-    32 / 64) take the plain forward on the same mixed batch. fp32 only. tasks: as for ReceptorScreen."""
+    32 / 64) take the plain forward on the same mixed batch. fp32 only. tasks: as for ReceptorScreen.
+
+    contact_attention: None, or a layer index into model.layers as the reference's attribution `--layer` (1: the first
+    EGNN layer; negative: from the end) whose edge attention every step reduces on the device (PF.contact_attention,
+    inside the captured step) into the static buffers `screen.contact`: lig_att [batch_size * max_lig_atoms] (packed
+    atom order of the loaded batch) and slot_rec_att [batch_size, n_rec] - the largest attention over each atom's
+    ligand-receptor edges, NaN without one - of the LAST step, and rec_sum / rec_count / rec_max [n_rec], accumulated
+    over every step since reset_contact_attention(). Needs the first-layer reuse."""
 
     def __init__(self, model, rec_pos, rec_feats, batch_size, max_lig_atoms, edge_radius, intra_radius=None,
-                 tasks=None):
+                 tasks=None, contact_attention=None):
         super().__init__(model, edge_radius, intra_radius, tasks)
         if not 1 <= int(max_lig_atoms) <= MAX_SCREEN_LIGAND_ATOMS:
             raise ValueError(f'max_lig_atoms must be 1..{MAX_SCREEN_LIGAND_ATOMS} (got {max_lig_atoms})')
@@ -481,8 +511,35 @@ class LibraryScreen(_ReceptorSideScreen):
         self._sizes = [0] * self.b
         self._stage, self._stage_at = [], 0
         self._pack_status = None     # load_leave_out's status word
+        self.contact_attention = resolve_attention_layer(model, contact_attention)       # (index into model.layers)
+        self.contact = None
+        if self.contact_attention is not None:
+            if not self.reuse:
+                raise NotImplementedError(
+                    f'LibraryScreen(contact_attention={contact_attention}): the contact-attention reduction runs in '
+                    'the step of the first-layer reuse, which this model does not have (softmax attention, '
+                    'edge_residual or a hidden size other than 32 / 64 take the plain forward)')
+            f32 = dict(dtype=torch.float32, device=dev)
+            rec_sum, rec_count, rec_max = PF.new_contact_accumulators(self.n_rec, dev)
+            self.contact = dict(lig_att=torch.full((self.l_cap,), float('nan'), **f32),
+                                slot_rec_att=torch.full((self.b, self.n_rec), float('nan'), **f32),
+                                rec_sum=rec_sum, rec_count=rec_count, rec_max=rec_max)
         if self.reuse:
             self._cache_receptor_sums()
+
+    def reset_contact_attention(self):
+        """The accumulators of `contact` as before the first step: sums and counts zero, maxima NaN (none so far)."""
+        if self.contact is None:
+            raise RuntimeError('reset_contact_attention: the screen was built without contact_attention')
+        self.contact['rec_sum'].zero_()
+        self.contact['rec_count'].zero_()
+        self.contact['rec_max'].fill_(float('nan'))
+
+    def _reduce_contacts(self, f, tag, att):
+        """PF.contact_attention over f's CSR `tag` ('_l': ligand-touching, '': full) with `att` in its edge order."""
+        c = self.contact
+        PF.contact_attention(f['rowptr' + tag], f['etype' + tag], att, f['node_ptr'], self.lig_ptr, self.n_rec,
+                             out=(c['lig_att'], c['slot_rec_att'], c['rec_sum'], c['rec_count'], c['rec_max']))
 
     def _cache_receptor_sums(self):
         """The receptor sums kept once, [n_rec, .]; the builder's node-table struct points at them."""
@@ -582,6 +639,8 @@ class LibraryScreen(_ReceptorSideScreen):
             pos=torch.empty((n_cap, 3), **f32), x=torch.empty((n_cap, self.lig_feats.shape[1]), **f32),
             base_magg=torch.empty((n_cap, hid), **f32), base_xsum=torch.empty((n_cap, 3), **f32),
             base_deg=torch.empty(n_cap, **f32), pgs={})
+        if self.contact_attention == 1:      # the first EGNN layer's attention, in the ligand-touching CSR's order
+            f['att_l'] = torch.empty(max(cap_l, 1), **f32)
         f['tables'] = _lib.PvsRaggedNodeTables(
             f['x'].shape[1], hid, _lib.ptr(self.lig_feats), _lib.ptr(self._rec_feats), _lib.ptr(self.rec_magg),
             _lib.ptr(self.rec_xsum), _lib.ptr(self.rec_deg), _lib.ptr(f['x']), _lib.ptr(f['base_magg']),
@@ -687,8 +746,13 @@ class LibraryScreen(_ReceptorSideScreen):
         x = f['pos'][:n]
         h = self.embed.embed(f['x'][:n], x).contiguous()
         h, x = self._partial_first_layer(g_lig, h, x, f['base_magg'], f['base_xsum'], f['base_deg'],
-                                         self.n_cap, f['cap_l'])
-        return self._tail(pg_full, h, x)
+                                         self.n_cap, f['cap_l'], f.get('att_l'))
+        y = self._tail(pg_full, h, x)
+        if self.contact_attention == 1:
+            self._reduce_contacts(f, '_l', f['att_l'])
+        elif self.contact_attention is not None:      # (a later layer: what its forward_prepared left, full CSR order)
+            self._reduce_contacts(f, '', self.model.layers[self.contact_attention]._att_sorted)
+        return y
 
     def capture(self, example_slots=None):
         """Captures one whole step (builder + layer stack + head) in a hipGraph; `replay(slots)` then serves every
@@ -787,7 +851,9 @@ class ScreeningSweep:
     model): after the sweep the best pose of every ligand is picked on the device (PF.segment_argmax on the raw
     column 0: larger wins, ties to the lower pose, NaN never wins) and written one line per ligand; `sweep.hits`
     keeps {name: (best pose or -1, its row)}. `ligand_atom_masking(best_poses(ligands))` then says which ligand atoms
-    carry each hit's score: every leave-one-atom-out copy of every hit as a LibraryScreen slot.
+    carry each hit's score: every leave-one-atom-out copy of every hit as a LibraryScreen slot;
+    `receptor_hotspots(best_poses(ligands))` says which receptor atoms the hits bind to: one layer's edge attention
+    reduced per atom inside the screening step and averaged over the hits on the device.
     """
 
     def __init__(self, model, rec_pos, rec_feats, edge_radius, batch_size=32, intra_radius=None, capture=True,
@@ -801,6 +867,7 @@ class ScreeningSweep:
         self.buckets = {}          # n_lig -> ReceptorScreen (captured when possible)
         self.library = None        # the LibraryScreen of run_library
         self.masking = None        # the LibraryScreen of ligand_atom_masking (its edge room is sized for whole ligands)
+        self.hotspot = None        # the LibraryScreen of receptor_hotspots (it reduces one layer's edge attention)
         self.batches_run = 0
 
     def _bucket(self, n_lig, lig_feats, example_poses):
@@ -900,19 +967,27 @@ class ScreeningSweep:
             self._pick_hits(names, sink, hits_file)
         return out
 
-    def _library_screen(self, max_atoms, which='library'):
+    def _library_screen(self, max_atoms, which='library', contact_attention=None):
+        """The sweep's LibraryScreen `which`, built anew when there is none, when the weights changed under it, when it
+        is too narrow for `max_atoms` or when it reduces another layer's attention than `contact_attention`."""
         screen = getattr(self, which)
-        if screen is None or screen.stale() or screen.max_lig_atoms < max_atoms:
+        layer = resolve_attention_layer(self.model, contact_attention)
+        if (screen is None or screen.stale() or screen.max_lig_atoms < max_atoms
+                or screen.contact_attention != layer):
             screen = LibraryScreen(self.model, self.rec_pos, self.rec_feats, self.b, max_atoms, self.edge_radius,
-                                   self.intra_radius, tasks=self.tasks)
+                                   self.intra_radius, tasks=self.tasks, contact_attention=layer)
             setattr(self, which, screen)
         return screen
+
+    def _capture_if_wanted(self, screen):
+        """Captures the step of `screen` on the batch loaded into it, where a captured step can be had."""
+        if self.capture and screen.reuse and not screen.graphnorm and not screen._captured:
+            screen.capture()
 
     def _library_step(self, screen):
         """The raw outputs [batch_size, C] of the batch loaded into `screen`: the captured step where one can be had
         (captured at the first batch), the eager one otherwise."""
-        if self.capture and screen.reuse and not screen.graphnorm and not screen._captured:
-            screen.capture()
+        self._capture_if_wanted(screen)
         return (screen.replay().clone() if screen._captured else screen()).reshape(self.b, -1)
 
     @torch.no_grad()
@@ -998,6 +1073,26 @@ class ScreeningSweep:
             if best >= 0:
                 yield name, lig_feats, poses[best]
 
+    @staticmethod
+    def _checked_hits(items, who):
+        """(items as a list, names, atom counts) of an iterable of (name, lig_feats [n,F], pose [n,3]): unique names,
+        n <= MAX_SCREEN_LIGAND_ATOMS, one pose each - or a ValueError that begins with `who`."""
+        items = [(name, lig_feats, pose) for name, lig_feats, pose in items]
+        names = [name for name, _, _ in items]
+        if len(set(names)) != len(names):
+            raise ValueError(f'{who}: names must be unique (repeated: '
+                             f'{sorted({n for n in names if names.count(n) > 1})})')
+        ns = []
+        for name, lig_feats, pose in items:
+            n = int(pose.shape[0])
+            if n > MAX_SCREEN_LIGAND_ATOMS:
+                raise ValueError(f'{who}: ligand {name!r} has {n} atoms: a pose-batch slot holds up to '
+                                 f'{MAX_SCREEN_LIGAND_ATOMS}')
+            if pose.dim() != 2 or pose.shape[1] != 3 or lig_feats.dim() != 2 or int(lig_feats.shape[0]) != n:
+                raise ValueError(f'{who}: ligand {name!r}: lig_feats [n, F] and ONE pose [n, 3]')
+            ns.append(n)
+        return items, names, ns
+
     @torch.no_grad()
     def ligand_atom_masking(self, items, scores_file=None, sigmoid=None, column=0):
         """Atom masking (the reference's attribution_fns.atom_masking, :365-431) of the LIGAND atoms of many complexes
@@ -1013,20 +1108,7 @@ class ScreeningSweep:
         `self.atom_masking_raw[name]` keeps the raw rows [n + 1, C], whole ligand first. scores_file: one line per
         ligand atom, item order then atom order, '{score:.6f} | {receptor} {name}_atom{a}'."""
         from .predictions import PredictionsWriter
-        items = [(name, lig_feats, pose) for name, lig_feats, pose in items]
-        names = [name for name, _, _ in items]
-        if len(set(names)) != len(names):
-            raise ValueError(f'ligand_atom_masking: names must be unique (repeated: '
-                             f'{sorted({n for n in names if names.count(n) > 1})})')
-        ns = []
-        for name, lig_feats, pose in items:
-            n = int(pose.shape[0])
-            if n > MAX_SCREEN_LIGAND_ATOMS:
-                raise ValueError(f'ligand_atom_masking: ligand {name!r} has {n} atoms: a pose-batch slot holds up to '
-                                 f'{MAX_SCREEN_LIGAND_ATOMS}')
-            if pose.dim() != 2 or pose.shape[1] != 3 or lig_feats.dim() != 2 or int(lig_feats.shape[0]) != n:
-                raise ValueError(f'ligand_atom_masking: ligand {name!r}: lig_feats [n, F] and ONE pose [n, 3]')
-            ns.append(n)
+        items, names, ns = self._checked_hits(items, 'ligand_atom_masking')
         self.atom_masking_raw = {}
         if not items:
             return {}
@@ -1067,4 +1149,76 @@ class ScreeningSweep:
                 if sum(ns):
                     writer.submit(torch.cat([out[name] for name in names], 0), None, [self.receptor_name] * sum(ns),
                                   [f'{name}_atom{a}' for name, n in zip(names, ns) for a in range(n)])
+        return out
+
+    @torch.no_grad()
+    def receptor_hotspots(self, items, gnn_layer=1, scores_file=None, per_hit=False):
+        """Which receptor atoms the hits of a sweep bind to (the reference's attribution/hotspot.py with its default
+        attribution, edge_attention): items as for `ligand_atom_masking` - (name, lig_feats [n,F], pose [n,3]), unique
+        names, e.g. `best_poses(ligands)` - are the binding events; per event every atom gets the largest attention
+        value of layer `gnn_layer` (an index into model.layers as the reference's `--layer`: 1 = the first EGNN layer,
+        negative from the end) over its ligand-receptor edges, and a receptor atom's score is the mean of these over
+        the events in which it has such an edge. The whole ligands stream through ONE LibraryScreen (`self.hotspot`,
+        built with contact_attention=gnn_layer) in ceil(len(items) / batch_size) steps - and, for a new screen, one
+        batch of the batch_size largest ligands before them, from which it sizes its edge buffers; that batch and the
+        warm-up steps of the capture are not part of the result. The reduction runs inside the step on the device
+        (PF.contact_attention); nothing is copied to the host per hit.
+        Returns a dict of device tensors: mean [n_rec] float64 (NaN for an atom without a contact), count [n_rec]
+        int32 (the events in which the atom has a contact), max [n_rec] (its largest value over them, NaN without),
+        ligand {name: [n]} (the same per ligand atom of each hit, NaN without a contact) and, with per_hit, per_hit
+        [len(items), n_rec] (every event's values, item order). scores_file: one line per receptor atom that has a
+        contact, atom order, '{mean:.6f} {count} | {receptor} atom{j}'."""
+        from pathlib import Path
+        from .predictions import PredictionsWriter
+        items, names, ns = self._checked_hits(items, 'receptor_hotspots')
+        dev, n_rec = self.rec_pos.device, int(self.rec_pos.shape[0])
+        ligand, hit_rows = {}, []
+        if items:
+            screen = self._library_screen(max(max(ns), 1), 'hotspot', contact_attention=gnn_layer)
+            if screen._fast is None:
+                # (a new screen sizes its edge buffers from its first batch: the largest ligands, as ligand_atom_masking)
+                big = sorted(range(len(items)), key=lambda i: -ns[i])[:self.b]
+                screen([(items[i][1], items[i][2]) for i in big])
+                self.batches_run += 1
+            self._capture_if_wanted(screen)
+            screen.reset_contact_attention()      # (behind the sizing batch and the capture's warm-up steps)
+            all_pos = torch.cat([pose.to(dev).float() for _, _, pose in items], 0).contiguous()
+            all_feats = torch.cat([lig_feats.to(dev).float() for _, lig_feats, _ in items], 0).contiguous()
+            n_batches = -(-len(items) // self.b)
+            ptrs = torch.zeros((n_batches, self.b + 1), dtype=torch.int32)
+            for k in range(n_batches):
+                batch_ns = ns[k * self.b:(k + 1) * self.b]
+                ptrs[k, 1:len(batch_ns) + 1] = torch.tensor(batch_ns, dtype=torch.int32)
+            ptrs = ptrs.cumsum(1, dtype=torch.int32)
+            ptrs_dev = ptrs.to(dev)
+            at, lig_rows = 0, []
+            for k in range(n_batches):
+                batch_ns = ns[k * self.b:(k + 1) * self.b]
+                total = sum(batch_ns)
+                screen.load_packed(all_pos[at:at + total], all_feats[at:at + total], ptrs_dev[k], batch_ns)
+                at += total
+                self._library_step(screen)
+                self.batches_run += 1
+                lig_rows.append(screen.contact['lig_att'][:total].clone())
+                if per_hit:
+                    hit_rows.append(screen.contact['slot_rec_att'][:len(batch_ns)].clone())
+            screen.check()
+            rec_sum, count, top = (screen.contact[key].clone() for key in ('rec_sum', 'rec_count', 'rec_max'))
+            lig_rows, at = torch.cat(lig_rows, 0), 0
+            for name, n in zip(names, ns):
+                ligand[name] = lig_rows[at:at + n]
+                at += n
+        else:
+            rec_sum, count, top = PF.new_contact_accumulators(n_rec, dev)
+        out = dict(mean=rec_sum / count, count=count, max=top, ligand=ligand)      # (0 / 0: NaN)
+        if per_hit:
+            out['per_hit'] = torch.cat(hit_rows, 0) if hit_rows else torch.empty((0, n_rec), dtype=torch.float32,
+                                                                                 device=dev)
+        if scores_file:
+            packed = torch.stack([out['mean'], count.double()], 1).cpu().numpy()      # the one copy to the host
+            atoms = [j for j in range(n_rec) if packed[j, 1] > 0]
+            with PredictionsWriter(scores_file, 'hotspot') as writer:
+                if atoms:
+                    writer.submit(packed[atoms], None, [self.receptor_name] * len(atoms), [f'atom{j}' for j in atoms])
+            Path(scores_file).expanduser().touch()       # (no contact at all: an empty file)
         return out
