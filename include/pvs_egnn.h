@@ -561,6 +561,36 @@ int pvs_contact_attention(const int32_t* rowptr, const uint8_t* etype, const flo
                           int32_t n_rec, float* lig_att, float* slot_rec_att, double* rec_sum, int32_t* rec_count,
                           float* rec_max, pvs_stream_t stream);
 
+/* The heads of pvs_pool_heads_fwd on EVERY row of h [n_rows, width] instead of on a pooled row (the reference's
+ * attribution_fns.cam, :312-362: the head applied to each node's final embedding), forward only:
+ *   y[n, col + o] = act(b[o] + sum_k h[n, k] W[o, k]),  k ascending, one fused multiply-add per term
+ * - the arithmetic of the pooled heads, instruction for instruction (csrc/head_ops.h), so a row of y is bit for bit what
+ * pvs_pool_heads_fwd gives for a graph that consists of that row alone. `heads`: a HOST array of 1..PVS_MAX_POOL_HEADS
+ * heads, copied into the kernel's arguments; their column ranges must lie inside ld_y and must not overlap; the other
+ * columns of y [n_rows, ld_y] are left as they are. width 1..1024. n_rows == 0: returns 0 without a launch. One launch,
+ * no workspace, no atomics: the same bits every time. */
+int pvs_node_heads_fwd(const float* h, const PvsHead* heads, int32_t n_heads, float* y, int32_t n_rows, int32_t width,
+                       int32_t ld_y, pvs_stream_t stream);
+
+/* pvs_contact_attention's reduction over a value that every node has (the class-activation map of a pose batch), over
+ * the same compact layout (node_ptr, lig_ptr: DEVICE, [n_slots + 1]; slot p: its ligand atoms, then the n_rec receptor
+ * atoms). y [n_nodes, ld_y]; the value of node row r is y[r, col] with n_mean == 1 and
+ * ((y[r, col] + y[r, col + 1]) + y[r, col + 2]) / 3.0f with n_mean == 3 (the reference's "three outputs are averaged",
+ * in that order, an IEEE division); any other n_mean is refused, as are columns outside ld_y.
+ *   lig_val [>= lig_ptr[n_slots]]: the value of every packed ligand atom; the entries from lig_ptr[n_slots] on are left
+ *     as they are.
+ *   slot_rec_val [n_slots, n_rec]: the value of every receptor atom of every slot that has at least one ligand atom; a
+ *     row of NaN for an empty slot and for one that is no slot (pvs_contact_attention's rule: the tables disagree, more
+ *     than 1024 ligand atoms, rows beyond n_nodes - n_slots * n_rec ligand rows), which writes nothing to lig_val.
+ *   rec_sum / rec_count / rec_max [n_rec]: READ AND UPDATED from slot_rec_val by pvs_contact_attention's accumulation
+ *     kernel itself (slot order, NaN skipped, the same order relation).
+ * Nothing read from the device decides an address unchecked; every output element has one writer, no atomics: the same
+ * bits every time. n_slots == 0 or n_rec == 0: returns 0 without a launch. Two launches. */
+int pvs_slot_node_values(const float* y, int32_t ld_y, int32_t col, int32_t n_mean, int32_t n_nodes,
+                         const int32_t* node_ptr, const int32_t* lig_ptr, int32_t n_slots, int32_t n_rec,
+                         float* lig_val, float* slot_rec_val, double* rec_sum, int32_t* rec_count, float* rec_max,
+                         pvs_stream_t stream);
+
 /* nn.BCEWithLogitsLoss() with its default mean reduction (point_neural_network_base.py:74, used at :365) over n logits:
  * loss[0] = mean(max(x, 0) - x t + log1p(exp(-|x|))), grad[i] = (sigmoid(x_i) - t_i) / n (what the backward scales by
  * the upstream gradient: pvs_scale_by_device_scalar, out[i] = a[i] * scalar[0] with the scalar in device memory). */

@@ -162,6 +162,10 @@ _PROTOTYPES = {
                                   [C.c_void_p] * 4 + [C.c_void_p]),
     'pvs_contact_attention': (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 2 + [C.c_void_p] * 2 + [C.c_int32] * 2 +
                               [C.c_void_p] * 5 + [C.c_void_p]),
+    'pvs_node_heads_fwd': (C.c_int, [C.c_void_p, C.POINTER(PvsHead), C.c_int32, C.c_void_p] + [C.c_int32] * 3 +
+                           [C.c_void_p]),
+    'pvs_slot_node_values': (C.c_int, [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p] * 2 + [C.c_int32] * 2 +
+                             [C.c_void_p] * 5 + [C.c_void_p]),
     'pvs_bce_logits_fwd': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     'pvs_scale_by_device_scalar': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     'pvs_segment_workspace_bytes': (C.c_size_t, [C.c_int32, C.c_int32]),
@@ -204,7 +208,7 @@ _PROTOTYPES = {
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)
-MIN_VERSION = 108       # pvs_version() of the library these prototypes describe (108: contact attention of a pose batch)
+MIN_VERSION = 109       # pvs_version() of the library these prototypes describe (109: per-node heads, slot node values)
 _lib = None
 
 

@@ -1,4 +1,5 @@
 #include "dense_ops.h"
+#include "head_ops.h"
 #include "mfma_common.h"
 #include "profile.h"
 
@@ -523,15 +524,6 @@ __device__ __forceinline__ void pool_row_to_lds(const float* __restrict__ h, con
     __syncthreads();
 }
 
-// b[o] + sum_k W[o, k] pl[k], k ascending (the order of k_linear), one fmaf per term
-__device__ __forceinline__ float head_dot(const float* pl, const float* __restrict__ W, const float* __restrict__ b,
-                                          int o, int width) {
-    float acc = b ? b[o] : 0.f;
-    const float* wr = W + (size_t)o * width;
-    for (int k = 0; k < width; ++k) acc = fmaf(pl[k], wr[k], acc);
-    return acc;
-}
-
 // global_mean_pool + the first Linear of the head in one launch (one workgroup per graph): the pooled row stays in LDS
 // for the product; y[g, c] = b[c] + sum_k W[c, k] pooled[g, k].
 __global__ void __launch_bounds__(kPoolThreads)
@@ -547,20 +539,9 @@ k_pool_head_fwd(const float* __restrict__ h, const int32_t* __restrict__ gptr, c
 // The same pooled row under up to four heads (screening a two-headed model: pose logit and affinity from one pass):
 // y[g, col + o] = act(b[o] + sum_k W[o, k] pooled[g, k]) per head. The head descriptors are kernel arguments (no device
 // table: the launch captures as it stands); the loop over them is unrolled so that they stay in scalar registers.
-struct PoolHeads {
-    PvsHead head[PVS_MAX_POOL_HEADS];
-    int n;
-};
-
-// nn.Softplus() with its defaults (beta 1, threshold 20): the input itself above the threshold
-__device__ __forceinline__ float head_act(int act, float v) {
-    if (act == PVS_HEAD_RELU) return v > 0.f ? v : 0.f;
-    if (act == PVS_HEAD_SOFTPLUS) return v > 20.f ? v : log1pf(expf(v));
-    return v;
-}
-
+// head_dot / head_act: head_ops.h, shared with the per-node heads (node_heads.hip).
 __global__ void __launch_bounds__(kPoolThreads)
-k_pool_heads_fwd(const float* __restrict__ h, const int32_t* __restrict__ gptr, const PoolHeads heads,
+k_pool_heads_fwd(const float* __restrict__ h, const int32_t* __restrict__ gptr, const PvsHeadArgs heads,
                  float* __restrict__ pooled, float* __restrict__ y, int width, int ld_y) {
     __shared__ float part[kPoolThreads];
     __shared__ float pl[kPoolThreads];
@@ -1464,21 +1445,8 @@ extern "C" int pvs_pool_head_fwd(const float* h, const int32_t* graph_ptr, const
 extern "C" int pvs_pool_heads_fwd(const float* h, const int32_t* graph_ptr, const PvsHead* heads, int32_t n_heads,
                                   float* pooled, float* y, int32_t B, int32_t width, int32_t ld_y, pvs_stream_t stream) {
     PVS_REQUIRE(width >= 1 && width <= kPoolThreads, "pool_heads: width %d unsupported", width);
-    PVS_REQUIRE(heads && n_heads >= 1 && n_heads <= PVS_MAX_POOL_HEADS, "pool_heads: %d heads (1..%d in one launch)",
-                n_heads, PVS_MAX_POOL_HEADS);
-    PoolHeads args = {};
-    args.n = n_heads;
-    for (int i = 0; i < n_heads; ++i) {
-        const PvsHead& hd = heads[i];
-        PVS_REQUIRE(hd.w && hd.n_out >= 1 && hd.act >= PVS_HEAD_NONE && hd.act <= PVS_HEAD_SOFTPLUS,
-                    "pool_heads: head %d: weights missing, n_out %d or activation %d unsupported", i, hd.n_out, hd.act);
-        PVS_REQUIRE(hd.col >= 0 && hd.col <= ld_y - hd.n_out, "pool_heads: head %d: columns [%d, %d + %d) outside the %d of y",
-                    i, hd.col, hd.col, hd.n_out, ld_y);
-        for (int j = 0; j < i; ++j)
-            PVS_REQUIRE(hd.col >= heads[j].col + heads[j].n_out || heads[j].col >= hd.col + hd.n_out,
-                        "pool_heads: heads %d and %d write overlapping columns", j, i);
-        args.head[i] = hd;
-    }
+    PvsHeadArgs args;
+    PVS_TRY(pvs_head_args("pool_heads", heads, n_heads, ld_y, &args));
     if (B <= 0) return 0;
     k_pool_heads_fwd<<<B, kPoolThreads, 0, (hipStream_t)stream>>>(h, graph_ptr, args, pooled, y, width, ld_y);
     PVS_CHECK_LAUNCH();

@@ -521,35 +521,61 @@ MAX_POOL_HEADS = _lib.MAX_POOL_HEADS
 HEAD_ACTS = {None: _lib.HEAD_NONE, 'relu': _lib.HEAD_RELU, 'softplus': _lib.HEAD_SOFTPLUS}
 
 
+def _head_table(what, h, heads):
+    """(h contiguous, the PvsHead table of `heads`, the tensors it points at, the columns they write in all) of
+    `pool_heads` / `node_heads`; their refusals, worded with `what`."""
+    heads = [(w, b, act) for w, b, act in heads]
+    tensors = [h] + [t for w, b, _ in heads for t in (w, b) if t is not None]
+    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+        raise RuntimeError(f'{what} is forward only: call it under torch.no_grad() (training takes pool_head)')
+    h = _c(h, _F32, _FP32_ONLY)
+    _lib.require_hip(*tensors)
+    width = h.shape[1]
+    table, keep, col = (_lib.PvsHead * max(len(heads), 1))(), [], 0
+    for i, (w, b, act) in enumerate(heads):
+        if act not in HEAD_ACTS:
+            raise ValueError(f'{what}: activation {act!r} (one of {sorted(k for k in HEAD_ACTS if k)} or None)')
+        w, b = _c(w.detach(), _F32, _FP32_ONLY), _c(None if b is None else b.detach(), _F32, _FP32_ONLY)
+        if w.dim() != 2 or w.shape[1] != width or (b is not None and b.numel() != w.shape[0]):
+            raise ValueError(f'{what}: head {i}: weight {tuple(w.shape)} / bias on features of width {width}')
+        keep += [w, b]
+        table[i] = _lib.PvsHead(_lib.ptr(w), _lib.ptr(b), w.shape[0], HEAD_ACTS[act], col)
+        col += w.shape[0]
+    return h, table, len(heads), keep, col
+
+
 def pool_heads(h, graph_ptr, heads, return_pooled=False):
     """Several heads on ONE pooled row per graph, in one launch, forward only (screening a two-headed model):
     heads = [(weight [C_i, width], bias [C_i] or None, act), ...], act None, 'relu' or 'softplus' (nn.Softplus()
     with its defaults). Returns y [B, sum C_i], the heads' columns side by side in the order given (and the pooled rows
     [B, width] with return_pooled). With act None a head's columns are bit for bit pool_head(h, graph_ptr, weight,
     bias). fp32 only; raises when autograd is recording and an input requires grad (there is no backward)."""
-    heads = [(w, b, act) for w, b, act in heads]
-    tensors = [h] + [t for w, b, _ in heads for t in (w, b) if t is not None]
-    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
-        raise RuntimeError('pool_heads is forward only: call it under torch.no_grad() (training takes pool_head)')
-    h = _c(h, _F32, _FP32_ONLY)
-    _lib.require_hip(h, graph_ptr, *tensors)
+    h, table, n_heads, keep, col = _head_table('pool_heads', h, heads)
+    _lib.require_hip(graph_ptr)
     n_graphs, width = graph_ptr.numel() - 1, h.shape[1]
-    table, keep, col = (_lib.PvsHead * max(len(heads), 1))(), [], 0
-    for i, (w, b, act) in enumerate(heads):
-        if act not in HEAD_ACTS:
-            raise ValueError(f'pool_heads: activation {act!r} (one of {sorted(k for k in HEAD_ACTS if k)} or None)')
-        w, b = _c(w.detach(), _F32, _FP32_ONLY), _c(None if b is None else b.detach(), _F32, _FP32_ONLY)
-        if w.dim() != 2 or w.shape[1] != width or (b is not None and b.numel() != w.shape[0]):
-            raise ValueError(f'pool_heads: head {i}: weight {tuple(w.shape)} / bias on features of width {width}')
-        keep += [w, b]
-        table[i] = _lib.PvsHead(_lib.ptr(w), _lib.ptr(b), w.shape[0], HEAD_ACTS[act], col)
-        col += w.shape[0]
     y = torch.empty((n_graphs, col), dtype=torch.float32, device=h.device)
     pooled = torch.empty((n_graphs, width), dtype=torch.float32, device=h.device) if return_pooled else None
-    _lib.check(_lib.lib().pvs_pool_heads_fwd(_lib.ptr(h), _lib.ptr(graph_ptr), table, len(heads), _lib.ptr(pooled),
+    _lib.check(_lib.lib().pvs_pool_heads_fwd(_lib.ptr(h), _lib.ptr(graph_ptr), table, n_heads, _lib.ptr(pooled),
                                              _lib.ptr(y), n_graphs, width, col, _stream(h.device)),
                'pvs_pool_heads_fwd')
     return (y, pooled) if return_pooled else y
+
+
+def node_heads(h, heads, out=None):
+    """The heads of `pool_heads` on EVERY row of h [n, width] (pvs_node_heads_fwd; the class-activation map: the head
+    applied to each node's final embedding): y [n, sum C_i], y[r] bit for bit what pool_heads gives for a graph that
+    is row r alone. Same argument forms and refusals as pool_heads. `out`: an fp32 tensor [>= n, sum C_i] to write the
+    first n rows of (a static buffer of a captured step). One launch, forward only, fp32 only."""
+    h, table, n_heads, keep, col = _head_table('node_heads', h, heads)
+    n, width = h.shape
+    if out is None:
+        out = torch.empty((n, col), dtype=torch.float32, device=h.device)
+    _lib.require_hip(out)
+    if out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] < n or out.shape[1] != col:
+        raise ValueError(f'node_heads: out = an fp32 tensor [>= {n}, {col}]')
+    _lib.check(_lib.lib().pvs_node_heads_fwd(_lib.ptr(h), table, n_heads, _lib.ptr(out), n, width, col,
+                                             _stream(h.device)), 'pvs_node_heads_fwd')
+    return out[:n]
 
 
 def segment_argmax(scores, seg_ptr, column=0):
@@ -660,6 +686,50 @@ def contact_attention(rowptr, etype, att, node_ptr, lig_ptr, n_rec, out=None):
         n_slots, n_rec, _lib.ptr(lig_att), _lib.ptr(slot_rec_att), _lib.ptr(rec_sum), _lib.ptr(rec_count),
         _lib.ptr(rec_max), _stream(dev)), 'pvs_contact_attention')
     return lig_att, slot_rec_att, rec_sum, rec_count, rec_max
+
+
+def slot_node_values(y, node_ptr, lig_ptr, n_rec, column=0, n_mean=1, out=None):
+    """`contact_attention`'s reduction over a value that every node has (pvs_slot_node_values): y [N, C] fp32 holds one
+    row per node of a compact pose batch (slot p: the rows node_ptr[p] .. node_ptr[p + 1], its lig_ptr[p + 1] -
+    lig_ptr[p] ligand atoms, then the n_rec receptor atoms; node_ptr, lig_ptr [n_slots + 1] int32), all on the device.
+    A node's value is y[r, column] (n_mean 1) or ((y[r, column] + y[r, column + 1]) + y[r, column + 2]) / 3 (n_mean 3).
+    Returns (lig_val [N - n_slots * n_rec], slot_rec_val [n_slots, n_rec], rec_sum [n_rec] float64, rec_count [n_rec]
+    int32, rec_max [n_rec]): the value of every packed ligand atom (the rows from lig_ptr[n_slots] on are not
+    written) and of every (slot, receptor atom) - a row of NaN for a slot without ligand atoms or with broken tables;
+    rec_sum / rec_count / rec_max are UPDATED with the slot values that are not NaN, in slot order (fresh ones:
+    new_contact_accumulators). `out`: those five tensors to write into and accumulate on. Two launches, no atomics, no
+    host synchronisation: the same bits every time."""
+    y = _c(y, _F32, _FP32_ONLY)
+    n_rec, column, n_mean = int(n_rec), int(column), int(n_mean)
+    if y.dim() != 2 or y.shape[1] < 1:
+        raise ValueError('slot_node_values: y [N, C]')
+    if n_mean not in (1, 3) or not 0 <= column <= y.shape[1] - n_mean:
+        raise ValueError(f'slot_node_values: column {column}, n_mean {n_mean}: one column or the mean of three, inside '
+                         f'the {y.shape[1]} of y')
+    if (node_ptr.dtype != torch.int32 or lig_ptr.dtype != torch.int32 or node_ptr.dim() != 1 or node_ptr.numel() < 1
+            or lig_ptr.shape != node_ptr.shape):
+        raise ValueError('slot_node_values: int32 node_ptr and lig_ptr [n_slots + 1]')
+    n_nodes, n_slots = y.shape[0], node_ptr.numel() - 1
+    if n_rec < 0 or n_slots * n_rec > n_nodes:
+        raise ValueError(f'slot_node_values: {n_nodes} rows cannot hold {n_slots} slots of {n_rec} receptor atoms')
+    _lib.require_hip(y, node_ptr, lig_ptr)
+    dev, n_lig = y.device, n_nodes - n_slots * n_rec
+    if out is None:
+        out = (torch.full((n_lig,), float('nan'), dtype=torch.float32, device=dev),
+               torch.empty((n_slots, n_rec), dtype=torch.float32, device=dev)) + new_contact_accumulators(n_rec, dev)
+    lig_val, slot_rec_val, rec_sum, rec_count, rec_max = out
+    _lib.require_hip(*out)
+    if (lig_val.dtype != torch.float32 or slot_rec_val.dtype != torch.float32 or rec_sum.dtype != torch.float64
+            or rec_count.dtype != torch.int32 or rec_max.dtype != torch.float32 or lig_val.dim() != 1
+            or lig_val.numel() < n_lig or slot_rec_val.shape != (n_slots, n_rec) or rec_sum.shape != (n_rec,)
+            or rec_count.shape != (n_rec,) or rec_max.shape != (n_rec,)):
+        raise ValueError(f'slot_node_values: out = (lig_val [>= {n_lig}], slot_rec_val [{n_slots}, {n_rec}], float64 '
+                         f'rec_sum [{n_rec}], int32 rec_count [{n_rec}], rec_max [{n_rec}])')
+    _lib.check(_lib.lib().pvs_slot_node_values(
+        _lib.ptr(y), y.shape[1], column, n_mean, n_nodes, _lib.ptr(node_ptr.contiguous()), _lib.ptr(lig_ptr.contiguous()),
+        n_slots, n_rec, _lib.ptr(lig_val), _lib.ptr(slot_rec_val), _lib.ptr(rec_sum), _lib.ptr(rec_count),
+        _lib.ptr(rec_max), _stream(dev)), 'pvs_slot_node_values')
+    return lig_val, slot_rec_val, rec_sum, rec_count, rec_max
 
 
 class _BceLogitsMeanFn(torch.autograd.Function):

@@ -13,6 +13,7 @@ import contextlib
 import ctypes as C
 
 import torch
+from torch import nn
 
 from . import _lib
 from . import functional as PF
@@ -105,6 +106,37 @@ def resolve_attention_layer(model, layer):
     return at
 
 
+def resolve_cam(model, heads, tasks, cam):
+    """What `cam=` of a LibraryScreen selects: None for None, else (the head modules evaluated per node, their output
+    widths, first column, columns averaged). The heads are the ones the screen evaluates (`heads` of a two-headed
+    model, else model.feats_linear_layers). True follows the reference's rule (attribution_fns.cam): one output column
+    is the value, three are averaged, anything else - the two heads of tasks='both' included - is a ValueError that
+    asks for a column; an int selects that column of the raw outputs."""
+    if cam is None:
+        return None
+    heads = list(heads) if heads is not None else [model.feats_linear_layers]
+    if any(head is None for head in heads):
+        raise ValueError('cam: the model has no head (feats_linear_layers is None): there is nothing to apply per node')
+    widths = []
+    for head in heads:
+        linears = [m for m in head if isinstance(m, nn.Linear)]
+        if not linears:
+            raise ValueError('cam: a head without a Linear has no known output width')
+        widths.append(int(linears[-1].out_features))
+    total = sum(widths)
+    if cam is True:
+        if tasks == 'both' or total not in (1, 3):
+            raise ValueError(f"cam=True: the reference's rule covers one output column (itself) or three (their mean); "
+                             f"the heads evaluated here (tasks={tasks!r}) give {total} - name a column: cam=<int> / "
+                             'column=<int>')
+        return heads, widths, 0, total
+    if isinstance(cam, bool) or not isinstance(cam, int):
+        raise ValueError(f'cam={cam!r}: None, True or a column of the raw outputs')
+    if not 0 <= cam < total:
+        raise ValueError(f'cam: column {cam} of {total} outputs')
+    return heads, widths, int(cam), 1
+
+
 class _ReceptorSideScreen:
     """What ReceptorScreen and LibraryScreen do alike, once: the receptor-receptor sums of the first layer and their
     weights fingerprint, the ligand-touching first layer, the layers after it, the deferred status word and the
@@ -126,6 +158,7 @@ class _ReceptorSideScreen:
         self.tasks = _resolve_tasks(model, tasks)
         self.heads = None if self.tasks is None else model.task_heads(self.tasks)
         self._graph, self._captured, self._pending, self._l1_ws, self._fast = None, False, None, None, None
+        self.cam, self._h_final = None, None      # (LibraryScreen(cam=...): per-node heads of the final embedding)
 
     def _weights_fingerprint(self):
         """Version counters of everything the cached receptor-receptor sums were computed from (the
@@ -215,6 +248,8 @@ class _ReceptorSideScreen:
         for layer in self.egnn[1:]:
             h, x, m_sorted = layer.forward_prepared(pg_full, h, x, m_sorted, need_m=layer.edge_residual,
                                                     need_coords=layer is not self.egnn[-1])
+        if self.cam is not None:
+            self._h_final = h
         if self.tasks is not None:
             return self._heads_out(h, self._pool_ptr())
         return h if self.model.feats_linear_layers is None else self._head(h)
@@ -226,10 +261,16 @@ class _ReceptorSideScreen:
 
     def _plain(self, batch):
         """The model's plain forward on `batch`, for the routes the first-layer reuse does not cover: the model's own
-        forward (single head), or its trunk and then the same head code as the reuse route."""
-        if self.tasks is None:
+        forward (single head), or its trunk and then the same head code as the reuse route. With `cam` the trunk's
+        final embedding and the batch's node offsets are kept (`_h_final`, `_plain_ptr`)."""
+        if self.tasks is None and self.cam is None:
             return self.model(batch)
-        feats, _, graph_ptr, _ = self.model._embed_graph(batch)
+        feats, _, graph_ptr, n_graphs = self.model._embed_graph(batch)
+        if self.cam is not None:
+            self._h_final, self._plain_ptr = feats, graph_ptr
+        if self.tasks is None:      # (the model's own forward, said out)
+            head = self.model.feats_linear_layers
+            return feats if head is None else self.model._pool_and_head(head, feats, graph_ptr, n_graphs)
         return self._heads_out(feats, graph_ptr)
 
     def _queue_status(self, status, host):
@@ -478,6 +519,13 @@ class LibraryScreen(_ReceptorSideScreen):
     exact node count. Models the first-layer reuse does not cover (edge_residual, softmax attention, hidden size not
     32 / 64) take the plain forward on the same mixed batch. fp32 only. tasks: as for ReceptorScreen.
 
+    cam: None, True or a column (`resolve_cam`): the class-activation map of every step - the heads the screen
+    evaluates, applied to every node's final embedding (PF.node_heads) and gathered per slot (PF.slot_node_values),
+    inside the captured step - in the static buffers `screen.cam`: node_y [N_cap, C] (the heads' raw outputs per node),
+    lig_val [batch_size * max_lig_atoms] (packed atom order of the loaded batch) and slot_rec_val [batch_size, n_rec]
+    (NaN for an empty slot) of the LAST step, and rec_sum / rec_count / rec_max [n_rec], accumulated over every step
+    since reset_cam(). Needs no attention layer and no first-layer reuse: the plain route runs it eagerly.
+
     contact_attention: None, or a layer index into model.layers as the reference's attribution `--layer` (1: the first
     EGNN layer; negative: from the end) whose edge attention every step reduces on the device (PF.contact_attention,
     inside the captured step) into the static buffers `screen.contact`: lig_att [batch_size * max_lig_atoms] (packed
@@ -486,8 +534,10 @@ class LibraryScreen(_ReceptorSideScreen):
     over every step since reset_contact_attention(). Needs the first-layer reuse."""
 
     def __init__(self, model, rec_pos, rec_feats, batch_size, max_lig_atoms, edge_radius, intra_radius=None,
-                 tasks=None, contact_attention=None):
+                 tasks=None, contact_attention=None, cam=None):
         super().__init__(model, edge_radius, intra_radius, tasks)
+        self.cam_request = cam
+        self._cam_plan = resolve_cam(model, self.heads, self.tasks, cam)
         if not 1 <= int(max_lig_atoms) <= MAX_SCREEN_LIGAND_ATOMS:
             raise ValueError(f'max_lig_atoms must be 1..{MAX_SCREEN_LIGAND_ATOMS} (got {max_lig_atoms})')
         _lib.require_hip(rec_pos)
@@ -524,8 +574,41 @@ class LibraryScreen(_ReceptorSideScreen):
             self.contact = dict(lig_att=torch.full((self.l_cap,), float('nan'), **f32),
                                 slot_rec_att=torch.full((self.b, self.n_rec), float('nan'), **f32),
                                 rec_sum=rec_sum, rec_count=rec_count, rec_max=rec_max)
+        if self._cam_plan is not None:
+            f32 = dict(dtype=torch.float32, device=dev)
+            rec_sum, rec_count, rec_max = PF.new_contact_accumulators(self.n_rec, dev)
+            self.cam = dict(node_y=torch.zeros((self.n_cap, sum(self._cam_plan[1])), **f32),
+                            lig_val=torch.full((self.l_cap,), float('nan'), **f32),
+                            slot_rec_val=torch.full((self.b, self.n_rec), float('nan'), **f32),
+                            rec_sum=rec_sum, rec_count=rec_count, rec_max=rec_max)
         if self.reuse:
             self._cache_receptor_sums()
+
+    def reset_cam(self):
+        """The accumulators of `cam` as before the first step: sums and counts zero, maxima NaN (none so far)."""
+        if self.cam is None:
+            raise RuntimeError('reset_cam: the screen was built without cam')
+        self.cam['rec_sum'].zero_()
+        self.cam['rec_count'].zero_()
+        self.cam['rec_max'].fill_(float('nan'))
+
+    def _reduce_cam(self, h, node_ptr, lig_ptr):
+        """The heads on every row of the final embedding h [n, H] into cam['node_y'][:n] - one launch (PF.node_heads)
+        when every head is one that PF.pool_heads takes, else each head per node on the linear op - then the slots'
+        values and the accumulators (PF.slot_node_values)."""
+        heads, widths, column, n_mean = self._cam_plan
+        c, n = self.cam, h.shape[0]
+        node_y = c['node_y'][:n]
+        fused = [self.model._fused_head(head) for head in heads]
+        if all(f is not None for f in fused) and len(fused) <= PF.MAX_POOL_HEADS and h.shape[1] <= PF.POOL_HEAD_MAX_WIDTH:
+            PF.node_heads(h, fused, out=node_y)
+        else:
+            at = 0
+            for head, width in zip(heads, widths):
+                node_y[:, at:at + width].copy_(self.model._run_head(head, h).reshape(n, width))
+                at += width
+        PF.slot_node_values(node_y, node_ptr, lig_ptr, self.n_rec, column, n_mean,
+                            out=(c['lig_val'], c['slot_rec_val'], c['rec_sum'], c['rec_count'], c['rec_max']))
 
     def reset_contact_attention(self):
         """The accumulators of `contact` as before the first step: sums and counts zero, maxima NaN (none so far)."""
@@ -721,7 +804,11 @@ class LibraryScreen(_ReceptorSideScreen):
                       batch=torch.arange(self.b, device=dev).repeat_interleave(torch.tensor(counts, device=dev)),
                       ptr=ptr, y=torch.zeros(self.b, device=dev), lig_fname=['pose'] * self.b,
                       rec_fname=['receptor'] * self.b, num_graphs=self.b, graph_node_counts=counts)
-        return self._plain(attach_radius_graph(batch, self.r_inter, self.r_intra))
+        y = self._plain(attach_radius_graph(batch, self.r_inter, self.r_intra))
+        if self.cam is not None:      # (eager: the offsets come from the host-known sizes)
+            lig_ptr = torch.tensor([0] + list(self._sizes), dtype=torch.int64).cumsum(0).to(device=dev, dtype=torch.int32)
+            self._reduce_cam(self._h_final.contiguous(), self._plain_ptr, lig_ptr)
+        return y
 
     def _head(self, h):
         model, node_ptr = self.model, self._fast['node_ptr']
@@ -752,6 +839,8 @@ class LibraryScreen(_ReceptorSideScreen):
             self._reduce_contacts(f, '_l', f['att_l'])
         elif self.contact_attention is not None:      # (a later layer: what its forward_prepared left, full CSR order)
             self._reduce_contacts(f, '', self.model.layers[self.contact_attention]._att_sorted)
+        if self.cam is not None:
+            self._reduce_cam(self._h_final, f['node_ptr'], self.lig_ptr)
         return y
 
     def capture(self, example_slots=None):
@@ -853,7 +942,8 @@ class ScreeningSweep:
     keeps {name: (best pose or -1, its row)}. `ligand_atom_masking(best_poses(ligands))` then says which ligand atoms
     carry each hit's score: every leave-one-atom-out copy of every hit as a LibraryScreen slot;
     `receptor_hotspots(best_poses(ligands))` says which receptor atoms the hits bind to: one layer's edge attention
-    reduced per atom inside the screening step and averaged over the hits on the device.
+    reduced per atom inside the screening step and averaged over the hits on the device - or, with attribution='cam',
+    the class-activation map (the heads applied to every atom's final embedding), which needs no attention layer.
     """
 
     def __init__(self, model, rec_pos, rec_feats, edge_radius, batch_size=32, intra_radius=None, capture=True,
@@ -868,6 +958,7 @@ class ScreeningSweep:
         self.library = None        # the LibraryScreen of run_library
         self.masking = None        # the LibraryScreen of ligand_atom_masking (its edge room is sized for whole ligands)
         self.hotspot = None        # the LibraryScreen of receptor_hotspots (it reduces one layer's edge attention)
+        self.cam_screen = None     # the LibraryScreen of receptor_hotspots(attribution='cam') (per-node heads)
         self.batches_run = 0
 
     def _bucket(self, n_lig, lig_feats, example_poses):
@@ -967,15 +1058,17 @@ class ScreeningSweep:
             self._pick_hits(names, sink, hits_file)
         return out
 
-    def _library_screen(self, max_atoms, which='library', contact_attention=None):
+    def _library_screen(self, max_atoms, which='library', contact_attention=None, cam=None):
         """The sweep's LibraryScreen `which`, built anew when there is none, when the weights changed under it, when it
-        is too narrow for `max_atoms` or when it reduces another layer's attention than `contact_attention`."""
+        is too narrow for `max_atoms`, when it reduces another layer's attention than `contact_attention` or maps
+        another value than `cam`."""
         screen = getattr(self, which)
         layer = resolve_attention_layer(self.model, contact_attention)
         if (screen is None or screen.stale() or screen.max_lig_atoms < max_atoms
-                or screen.contact_attention != layer):
+                or screen.contact_attention != layer
+                or (type(screen.cam_request), screen.cam_request) != (type(cam), cam)):      # (True is not column 1)
             screen = LibraryScreen(self.model, self.rec_pos, self.rec_feats, self.b, max_atoms, self.edge_radius,
-                                   self.intra_radius, tasks=self.tasks, contact_attention=layer)
+                                   self.intra_radius, tasks=self.tasks, contact_attention=layer, cam=cam)
             setattr(self, which, screen)
         return screen
 
@@ -1152,7 +1245,8 @@ class ScreeningSweep:
         return out
 
     @torch.no_grad()
-    def receptor_hotspots(self, items, gnn_layer=1, scores_file=None, per_hit=False):
+    def receptor_hotspots(self, items, gnn_layer=1, scores_file=None, per_hit=False, attribution='edge_attention',
+                          column=None, ligand_scores_file=None):
         """Which receptor atoms the hits of a sweep bind to (the reference's attribution/hotspot.py with its default
         attribution, edge_attention): items as for `ligand_atom_masking` - (name, lig_feats [n,F], pose [n,3]), unique
         names, e.g. `best_poses(ligands)` - are the binding events; per event every atom gets the largest attention
@@ -1167,21 +1261,40 @@ class ScreeningSweep:
         int32 (the events in which the atom has a contact), max [n_rec] (its largest value over them, NaN without),
         ligand {name: [n]} (the same per ligand atom of each hit, NaN without a contact) and, with per_hit, per_hit
         [len(items), n_rec] (every event's values, item order). scores_file: one line per receptor atom that has a
-        contact, atom order, '{mean:.6f} {count} | {receptor} atom{j}'."""
+        contact, atom order, '{mean:.6f} {count} | {receptor} atom{j}'.
+        attribution='cam' (the reference's `--scoring_method cam`): the value of an atom is the class-activation map
+        instead - the heads the sweep evaluates, applied to the atom's final embedding; `column`: None for the
+        reference's rule (one output: itself, three: their mean), else a column of the raw outputs (required with
+        tasks='both'). Every atom has a value, so count is the number of hits that have atoms, for every receptor
+        atom, and scores_file gets a line for each; `gnn_layer` is ignored. The hits stream through `self.cam_screen`
+        (LibraryScreen(cam=...)), which needs neither an attention layer nor the first-layer reuse. Same keys.
+        ligand_scores_file: one line per ligand atom of every hit, item order then atom order, '{value:.6f} |
+        {receptor} {name}_atom{a}'."""
         from pathlib import Path
         from .predictions import PredictionsWriter
+        if attribution not in ('edge_attention', 'cam'):
+            raise ValueError(f"receptor_hotspots: attribution={attribution!r}: 'edge_attention' or 'cam'")
+        by_cam = attribution == 'cam'
+        if column is not None and not by_cam:
+            raise ValueError("receptor_hotspots: column selects a head output of attribution='cam'")
         items, names, ns = self._checked_hits(items, 'receptor_hotspots')
         dev, n_rec = self.rec_pos.device, int(self.rec_pos.shape[0])
         ligand, hit_rows = {}, []
+        lig_key, slot_key = ('lig_val', 'slot_rec_val') if by_cam else ('lig_att', 'slot_rec_att')
         if items:
-            screen = self._library_screen(max(max(ns), 1), 'hotspot', contact_attention=gnn_layer)
-            if screen._fast is None:
+            if by_cam:
+                screen = self._library_screen(max(max(ns), 1), 'cam_screen', cam=True if column is None else int(column))
+            else:
+                screen = self._library_screen(max(max(ns), 1), 'hotspot', contact_attention=gnn_layer)
+            values = screen.cam if by_cam else screen.contact
+            if screen.reuse and screen._fast is None:
                 # (a new screen sizes its edge buffers from its first batch: the largest ligands, as ligand_atom_masking)
                 big = sorted(range(len(items)), key=lambda i: -ns[i])[:self.b]
                 screen([(items[i][1], items[i][2]) for i in big])
                 self.batches_run += 1
             self._capture_if_wanted(screen)
-            screen.reset_contact_attention()      # (behind the sizing batch and the capture's warm-up steps)
+            # (behind the sizing batch and the capture's warm-up steps)
+            screen.reset_cam() if by_cam else screen.reset_contact_attention()
             all_pos = torch.cat([pose.to(dev).float() for _, _, pose in items], 0).contiguous()
             all_feats = torch.cat([lig_feats.to(dev).float() for _, lig_feats, _ in items], 0).contiguous()
             n_batches = -(-len(items) // self.b)
@@ -1199,11 +1312,11 @@ class ScreeningSweep:
                 at += total
                 self._library_step(screen)
                 self.batches_run += 1
-                lig_rows.append(screen.contact['lig_att'][:total].clone())
+                lig_rows.append(values[lig_key][:total].clone())
                 if per_hit:
-                    hit_rows.append(screen.contact['slot_rec_att'][:len(batch_ns)].clone())
+                    hit_rows.append(values[slot_key][:len(batch_ns)].clone())
             screen.check()
-            rec_sum, count, top = (screen.contact[key].clone() for key in ('rec_sum', 'rec_count', 'rec_max'))
+            rec_sum, count, top = (values[key].clone() for key in ('rec_sum', 'rec_count', 'rec_max'))
             lig_rows, at = torch.cat(lig_rows, 0), 0
             for name, n in zip(names, ns):
                 ligand[name] = lig_rows[at:at + n]
@@ -1221,4 +1334,10 @@ class ScreeningSweep:
                 if atoms:
                     writer.submit(packed[atoms], None, [self.receptor_name] * len(atoms), [f'atom{j}' for j in atoms])
             Path(scores_file).expanduser().touch()       # (no contact at all: an empty file)
+        if ligand_scores_file:
+            with PredictionsWriter(ligand_scores_file, 'atom_masking') as writer:
+                if sum(ns):
+                    writer.submit(torch.cat([ligand[name] for name in names], 0), None, [self.receptor_name] * sum(ns),
+                                  [f'{name}_atom{a}' for name, n in zip(names, ns) for a in range(n)])
+            Path(ligand_scores_file).expanduser().touch()
         return out

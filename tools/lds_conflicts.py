@@ -130,7 +130,34 @@ def h32_backward(ts=36, swz_t1=False, paired=False):
     return tot, conf
 
 
+def node_heads_stride(width, vec=None):
+    """Row stride (floats) of the per-node heads' LDS tile (csrc/node_heads.h: pvs_node_heads_stride), restated."""
+    vec = width % 4 == 0 if vec is None else vec
+    if not vec:
+        return width | 1
+    return width if (width // 4) % 2 else width + 4
+
+
+def node_heads(width, stride=None, rows=128, quiet=False):
+    """k_node_heads_fwd: lane = row of the tile; every lane reads channel chunk q of its own row (ds_read_b128 when
+    width % 4 == 0, else ds_read_b32 of channel q). Returns (cycles, conflict cycles) summed over one chunk per wave
+    of the tile - the pattern is the same for every q."""
+    stride = node_heads_stride(width) if stride is None else stride
+    kind = 'r128' if width % 4 == 0 and stride % 4 == 0 else 'r32'
+    tot = conf = 0
+    for wave in range(max(rows // 64, 1)):
+        c, ideal = cycles(kind, lambda l: 4 * ((64 * wave + l) * stride + (4 if kind == 'r128' else 1)))
+        tot, conf = tot + c, conf + c - ideal
+    if not quiet:
+        print(f'node heads, width {width:4d}, stride {stride:4d} floats, {kind}: {tot} cycles, {conf} in conflicts')
+    return tot, conf
+
+
 if __name__ == '__main__':
+    print('== per-node heads (k_node_heads_fwd): the unpadded row stride against the shipped one ==')
+    for w in (20, 32, 64, 128, 1024, 33):
+        node_heads(w, stride=w)
+        node_heads(w)
     print('== H = 32 backward (k_edge_bwd_f16) as of round 4: image swizzle (r / 4) & 7, g_z1 tile stride 36 floats ==')
     h32_backward(36)
     print('== round 5: image swizzle bits (r2, r3, r1 ^ r4), g_z1 tile unpadded with the quads of row r rotated by r & 7 ==')
