@@ -342,6 +342,28 @@ int pvs_screen_graph_build_ragged_cap(const float* lig_pos, const int32_t* lig_p
                                       const PvsRaggedNodeTables* tables, int32_t* status, void* state,
                                       size_t state_bytes, pvs_stream_t stream);
 
+/* Struck slots: pvs_screen_graph_build_ragged_cap plus rec_drop [n_slots] (int32, DEVICE): -1, or the receptor atom
+ * r in 0..n_rec-1 that the slot's receptor lacks (receptor-atom and contact masking of a sweep's hits:
+ * attribution_fns.py atom_masking / bond_masking remove atoms together with their edges). A struck slot owns
+ * n_lig + n_rec - 1 rows - its ligand atoms, then the receptor atoms in order without r - so node_ptr[p] = lig_ptr[p] +
+ * p * n_rec - (struck slots before p) and the rows from node_ptr[n_slots] on are padding. Its full CSR is the unstruck
+ * slot's without every edge that touches r, ids above r moved down by one, classes and in-row order kept; inv_deg from
+ * the new degrees. A receptor row that had r in its template row cannot start from the cached receptor sums: its
+ * base_magg / base_xsum / base_deg are zero and its row of the ligand-touching CSR is its WHOLE row (ligand entries,
+ * then the class-2 entries that remain); every other row is as without rec_drop. With every entry -1 all outputs are
+ * those of pvs_screen_graph_build_ragged_cap. *status as there; bit 3 also for an entry of rec_drop outside
+ * -1..n_rec-1 (an edgeless batch). capacity_lig needs room for the whole rows of the touched receptor rows. */
+size_t pvs_screen_graph_struck_state_bytes(int32_t n_slots, int32_t lig_cap, int32_t n_rec, int32_t slot_cap);
+int pvs_screen_graph_build_struck(const float* lig_pos, const int32_t* lig_ptr, const int32_t* rec_drop,
+                                  const float* rec_pos, const int32_t* rr_rowptr, const int32_t* rr_col,
+                                  int32_t n_slots, int32_t lig_cap, int32_t n_rec, int32_t slot_cap,
+                                  double inter_radius, double intra_radius, int32_t capacity, int32_t capacity_lig,
+                                  int32_t* rowptr, int32_t* row, int32_t* col, uint8_t* etype, float* inv_deg,
+                                  int32_t* rowptr_lig, int32_t* row_lig, int32_t* col_lig, uint8_t* etype_lig,
+                                  int32_t* node_ptr, int32_t* node_graph, float* pos,
+                                  const PvsRaggedNodeTables* tables, int32_t* status, void* state, size_t state_bytes,
+                                  pvs_stream_t stream);
+
 /* Complex batches: the node tables of B protein-ligand complexes built from a device-resident pool of structure
  * files, as the reference loader builds one sample on the host (data_loaders.py:259-309: ligand then receptor, crop of
  * the receptor to the atoms closer than `radius` to some ligand atom - fp64, scipy's cdist decision -, hydrogen filter
@@ -536,6 +558,36 @@ int pvs_leave_out_ligand_pack(const float* lig_pos, const float* lig_feats, cons
                               int32_t n_rows, int32_t n_feats, const int32_t* first_copy, int32_t n_slots,
                               int32_t slot_cap, float* out_pos, float* out_feats, int32_t* out_ptr, int32_t* status,
                               pvs_stream_t stream);
+
+/* The ligand-receptor contacts of packed hits: lig_pos [n_rows, 3] / lig_ptr [n_hits + 1] (DEVICE) against rec_pos
+ * [n_rec, 3]. (a, r) - ligand atom a counted inside its hit, receptor atom r - is a contact exactly when the pose-batch
+ * builders write a class-1 edge for it: 1e-7 < d < inter_radius on the same fp64 squared distance and compares.
+ * _count: pair_ptr [n_hits + 1] = the exclusive scan of the hits' contact counts (the host reads pair_ptr[n_hits], the
+ * one copy back); a lig_ptr that does not ascend from 0 inside n_rows gives zeros and pair_ptr[n_hits] = -1.
+ * _fill: pairs [n_pairs, 2] int32, the rows pair_ptr[s] .. pair_ptr[s + 1] = hit s's contacts sorted by a, then by r;
+ * nothing is written from row n_pairs on. No atomics: the same bits every time. */
+int pvs_contact_pairs_count(const float* lig_pos, const int32_t* lig_ptr, int32_t n_hits, int32_t n_rows,
+                            const float* rec_pos, int32_t n_rec, double inter_radius, int32_t* pair_ptr,
+                            pvs_stream_t stream);
+int pvs_contact_pairs_fill(const float* lig_pos, const int32_t* lig_ptr, int32_t n_hits, int32_t n_rows,
+                           const float* rec_pos, int32_t n_rec, double inter_radius, const int32_t* pair_ptr,
+                           int32_t n_pairs, int32_t* pairs, pvs_stream_t stream);
+
+/* pvs_leave_out_ligand_pack for copies that leave out one ligand-receptor pair, the slots of
+ * pvs_screen_graph_build_struck (attribution_fns.py bond_masking; with a = -1 or r = -1 a single atom). Hit s owns the
+ * rows pair_ptr[s] .. pair_ptr[s + 1] of pairs [n_pairs, 2] (a: ligand atom counted inside the hit or -1; r: receptor
+ * atom or -1) and one copy more than rows: the whole ligand, then one copy per row. Its first copy is number
+ * pair_ptr[s] + s. Slot k holds copy first_copy[0] + k: the hit's rows without atom a in out_pos / out_feats, out_ptr as
+ * above, and rec_drop[k] = r (-1 for a whole ligand and for a slot that holds nothing).
+ *   *status: 0, or bit 3 with out_ptr all zeros, rec_drop all -1 and no row written when lig_ptr or pair_ptr does not
+ *   ascend from 0 (to at most n_rows / n_pairs), a ligand has more than slot_cap atoms, or a pair row of one of THIS
+ *   batch's copies has a outside -1..n_s-1 or r outside -1..n_rec-1.
+ * One launch, no atomics, no workspace: the same bits every time. */
+int pvs_leave_out_pair_pack(const float* lig_pos, const float* lig_feats, const int32_t* lig_ptr, const int32_t* pairs,
+                            const int32_t* pair_ptr, int32_t n_hits, int32_t n_rows, int32_t n_pairs, int32_t n_feats,
+                            int32_t n_rec, const int32_t* first_copy, int32_t n_slots, int32_t slot_cap, float* out_pos,
+                            float* out_feats, int32_t* out_ptr, int32_t* rec_drop, int32_t* status,
+                            pvs_stream_t stream);
 
 /* Contact attention of a pose batch (the reference's attribution/hotspot.py over attribution_fns.edge_attention,
  * :278-295: per atom the largest attention value over its ligand-receptor edges, per receptor atom the mean of these

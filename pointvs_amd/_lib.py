@@ -115,6 +115,11 @@ _PROTOTYPES = {
                                                                                          C.c_int32, C.c_int32] +
                                           [C.c_void_p] * 12 + [C.POINTER(PvsRaggedNodeTables), C.c_void_p, C.c_void_p,
                                                                C.c_size_t, C.c_void_p]),
+    'pvs_screen_graph_struck_state_bytes': (C.c_size_t, [C.c_int32] * 4),
+    'pvs_screen_graph_build_struck': (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 4 + [C.c_double, C.c_double, C.c_int32,
+                                                                                     C.c_int32] +
+                                      [C.c_void_p] * 12 + [C.POINTER(PvsRaggedNodeTables), C.c_void_p, C.c_void_p,
+                                                           C.c_size_t, C.c_void_p]),
     'pvs_mask_graph_workspace_bytes': (C.c_size_t, [C.c_int32, C.c_int32]),
     'pvs_mask_graph_build': (C.c_int, [C.POINTER(PvsGraph), C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32] +
                              [C.c_void_p] * 9 + [C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -160,6 +165,12 @@ _PROTOTYPES = {
                                      C.c_void_p]),
     'pvs_leave_out_ligand_pack': (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 3 + [C.c_void_p, C.c_int32, C.c_int32] +
                                   [C.c_void_p] * 4 + [C.c_void_p]),
+    'pvs_contact_pairs_count': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                                          C.c_double, C.c_void_p, C.c_void_p]),
+    'pvs_contact_pairs_fill': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                                         C.c_double, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    'pvs_leave_out_pair_pack': (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 5 + [C.c_void_p, C.c_int32, C.c_int32] +
+                                [C.c_void_p] * 5 + [C.c_void_p]),
     'pvs_contact_attention': (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 2 + [C.c_void_p] * 2 + [C.c_int32] * 2 +
                               [C.c_void_p] * 5 + [C.c_void_p]),
     'pvs_node_heads_fwd': (C.c_int, [C.c_void_p, C.POINTER(PvsHead), C.c_int32, C.c_void_p] + [C.c_int32] * 3 +
@@ -208,7 +219,7 @@ _PROTOTYPES = {
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)
-MIN_VERSION = 109       # pvs_version() of the library these prototypes describe (109: per-node heads, slot node values)
+MIN_VERSION = 110       # pvs_version() of the library these prototypes describe (110: struck slots, contact pairs)
 _lib = None
 
 

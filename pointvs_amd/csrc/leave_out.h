@@ -41,3 +41,35 @@ PVS_LEAVE_OUT_FN bool pvs_leave_out_table_ok(const int32_t* lig_ptr, int S, int 
     const long long n = (long long)lig_ptr[t + 1] - lig_ptr[t];
     return n >= 0 && n <= slot_cap;
 }
+
+// ---- copies that leave out one ligand-receptor pair (pvs_leave_out_pair_pack) ----
+// Hit s owns the rows pair_ptr[s] .. pair_ptr[s + 1] of a pair table [K, 2] (ligand atom a counted inside the hit or -1,
+// receptor atom r or -1) and pair_ptr[s + 1] - pair_ptr[s] + 1 consecutive copies: the whole ligand first, then one per
+// row of its table. Its first copy is number pair_ptr[s] + s: the arithmetic above with pair_ptr in the place of
+// lig_ptr, and pair_ptr[S] + S copies in all.
+struct PvsPairCopy {
+    int32_t hit;        // -1: a copy number outside [0, pair_ptr[S] + S) holds nothing
+    int32_t pair;       // the row of the pair table that the copy leaves out; -1: the whole ligand
+};
+
+// pair_ptr must be ascending from 0 (pvs_pair_table_ok of every entry).
+PVS_LEAVE_OUT_FN PvsPairCopy pvs_pair_copy(const int32_t* pair_ptr, int S, long long copy) {
+    if (S < 1 || copy < 0 || copy >= (long long)pair_ptr[S] + S) return PvsPairCopy{-1, -1};
+    int lo = 0, hi = S;         // the last s with pair_ptr[s] + s <= copy
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if ((long long)pair_ptr[mid] + mid <= copy) lo = mid; else hi = mid;
+    }
+    const int32_t which = (int32_t)(copy - ((long long)pair_ptr[lo] + lo));      // 0 .. the hit's pair count
+    return PvsPairCopy{lo, which == 0 ? -1 : pair_ptr[lo] + which - 1};
+}
+
+// Entry t (0 .. S) of a table of pair rows inside K.
+PVS_LEAVE_OUT_FN bool pvs_pair_table_ok(const int32_t* pair_ptr, int S, int t, int K) {
+    if (t == 0 && pair_ptr[0] != 0) return false;
+    if (t == S) return pair_ptr[S] <= K;
+    return pair_ptr[t + 1] >= pair_ptr[t];
+}
+
+// One row (a, r) of the table of a hit of n atoms against n_rec receptor atoms.
+PVS_LEAVE_OUT_FN bool pvs_pair_ok(int a, int r, int n, int n_rec) { return a >= -1 && a < n && r >= -1 && r < n_rec; }

@@ -18,10 +18,15 @@
 #include "radius_common.h"
 #include "screen_slots.h"
 #include <hipcub/hipcub.hpp>
+#include <type_traits>
 
 namespace {
 
 typedef unsigned long long u64;
+
+// Struck slots (PvsStruckSlots: a slot's receptor may lack one atom) run through the same kernels; what they do
+// differently is compiled only for that layout.
+template <class Slots> constexpr bool kStruck = std::is_same<Slots, PvsStruckSlots>::value;
 
 // wave per packed ligand atom q: contact masks against the receptor (64 atoms per word) and the atom's own ligand
 // (W words per atom; trip w, lane l: the slot's atom 64 w + l)
@@ -40,12 +45,14 @@ k_contacts(const float* __restrict__ lig_pos, const float* __restrict__ rec_pos,
     const PvsSlotAtom slot = L.atom(q);
     if (!slot.valid) return;
     const int n_rec = L.n_rec, n_chunks = (n_rec + 63) / 64;
+    int drop = -1;                                       // the receptor atom this atom's slot lacks: no contact with it
+    if constexpr (kStruck<Slots>) drop = L.drop_of_atom(q);
     const float* la = lig_pos + (size_t)q * 3;
     const double xa = la[0], ya = la[1], za = la[2];
     for (int c = 0; c < n_chunks; ++c) {
         const int i = 64 * c + lane;
         bool ei = false, ea = false;
-        if (i < n_rec) {
+        if (i < n_rec && (!kStruck<Slots> || i != drop)) {
             const double s = pvs_sqdist(xa, ya, za, (double)rec_pos[3 * i], (double)rec_pos[3 * i + 1],
                                         (double)rec_pos[3 * i + 2]);
             if (above(s, r_zero)) {
@@ -83,8 +90,9 @@ __device__ __forceinline__ int row_popc(const u64* __restrict__ m, int n_chunks)
 // row walks the slot's ligand atoms one by one: linear in n_lig)
 template <class Slots>
 __global__ void k_degrees(const u64* __restrict__ m_inter, const u64* __restrict__ m_intra,
-                          const u64* __restrict__ m_ll, const int32_t* __restrict__ rr_rowptr, Slots L,
-                          int32_t* __restrict__ deg, int32_t* __restrict__ deg_l) {
+                          const u64* __restrict__ m_ll, const int32_t* __restrict__ rr_rowptr,
+                          const int32_t* __restrict__ rr_col, Slots L, int32_t* __restrict__ deg,
+                          int32_t* __restrict__ deg_l) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g > L.rows()) return;
     PvsSlotRow r = {};
@@ -99,7 +107,9 @@ __global__ void k_degrees(const u64* __restrict__ m_inter, const u64* __restrict
         deg[g] = d;
         deg_l[g] = d;
     } else {
-        const int i = r.local - r.n_lig, c = i >> 6;
+        int i = r.local - r.n_lig;
+        if constexpr (kStruck<Slots>) i = pvs_struck_receptor(i, r.drop);
+        const int c = i >> 6;
         const u64 bit = 1ull << (i & 63);
         int nl = 0;
         for (int a = 0; a < r.n_lig; ++a) {
@@ -107,8 +117,14 @@ __global__ void k_degrees(const u64* __restrict__ m_inter, const u64* __restrict
             nl += (m_inter[w * n_chunks + c] & bit) ? 1 : 0;
             nl += (m_intra[w * n_chunks + c] & bit) ? 1 : 0;
         }
-        deg_l[g] = nl;
-        deg[g] = nl + (rr_rowptr[i + 1] - rr_rowptr[i]);
+        int rr = rr_rowptr[i + 1] - rr_rowptr[i];
+        bool touched = false;           // a struck slot's row that had the struck atom as a neighbour: the whole row
+        if constexpr (kStruck<Slots>) {  // goes through the ligand-touching CSR too
+            touched = r.drop >= 0 && pvs_find_ascending(rr_col + rr_rowptr[i], rr, r.drop) >= 0;
+            rr -= touched ? 1 : 0;
+        }
+        deg_l[g] = touched ? nl + rr : nl;
+        deg[g] = nl + rr;
     }
 }
 
@@ -152,7 +168,10 @@ k_fill(const u64* __restrict__ m_inter, const u64* __restrict__ m_intra, const u
         if (also_lig) { lig.row[pl + off] = g; lig.col[pl + off] = column; lig.etype[pl + off] = (uint8_t)cls; }
     };
     auto expand_words = [&](const u64* __restrict__ m, int col0, int cls) {
-        const int done = pvs_expand_mask_row(m, n_chunks, lane, [&](int k, int b) { emit(k, col0 + b, cls, true); });
+        const int done = pvs_expand_mask_row(m, n_chunks, lane, [&](int k, int b) {
+            if constexpr (kStruck<Slots>) b = pvs_struck_row(b, r.drop);
+            emit(k, col0 + b, cls, true);
+        });
         pf += done;
         pl += done;
     };
@@ -169,7 +188,9 @@ k_fill(const u64* __restrict__ m_inter, const u64* __restrict__ m_intra, const u
         }
         expand_words(m_intra + w * n_chunks, node0 + n_lig, 0);              // ... then receptor atoms
     } else {
-        const int i = r.local - n_lig, c = i >> 6;
+        int i = r.local - n_lig;
+        if constexpr (kStruck<Slots>) i = pvs_struck_receptor(i, r.drop);
+        const int c = i >> 6;
         const u64 bit = 1ull << (i & 63);
         for (int kind = 0; kind < 2; ++kind) {                                // inter block, then intra: ligand atoms
             const u64* m = kind == 0 ? m_inter : m_intra;
@@ -184,7 +205,16 @@ k_fill(const u64* __restrict__ m_inter, const u64* __restrict__ m_intra, const u
             pf += cnt; pl += cnt;
         }
         const int r0 = rr_rowptr[i], r1 = rr_rowptr[i + 1];                   // intra block: receptor atoms
-        for (int k = lane; k < r1 - r0; k += 64) emit(k, node0 + n_lig + rr_col[r0 + k], 2, false);
+        if (!kStruck<Slots> || r.drop < 0) {
+            for (int k = lane; k < r1 - r0; k += 64) emit(k, node0 + n_lig + rr_col[r0 + k], 2, false);
+        } else {                        // without the struck atom; a row that had it is written to both CSRs
+            const int at = pvs_find_ascending(rr_col + r0, r1 - r0, r.drop);
+            for (int k = lane; k < r1 - r0; k += 64) {
+                if (k == at) continue;
+                emit(k - ((at >= 0 && k > at) ? 1 : 0), node0 + n_lig + pvs_struck_row(rr_col[r0 + k], r.drop), 2,
+                     at >= 0);
+            }
+        }
     }
 }
 
@@ -226,7 +256,7 @@ int build_csrs(const Slots& L, const float* lig_pos, const float* rec_pos, const
                                                    make_radius(intra_radius), make_radius(1e-7), w.m_inter,
                                                    w.m_intra, w.m_ll, clear_status ? status : nullptr);
     PVS_CHECK_LAUNCH();
-    k_degrees<<<(N + 1 + 255) / 256, 256, 0, s>>>(w.m_inter, w.m_intra, w.m_ll, rr_rowptr, L, w.deg, w.deg_l);
+    k_degrees<<<(N + 1 + 255) / 256, 256, 0, s>>>(w.m_inter, w.m_intra, w.m_ll, rr_rowptr, rr_col, L, w.deg, w.deg_l);
     PVS_CHECK_LAUNCH();
     size_t sb = w.scan_bytes;
     PVS_CHECK_HIP(hipcub::DeviceScan::ExclusiveSum(w.scan_tmp, sb, w.deg, rowptr, N + 1, s));
@@ -310,9 +340,42 @@ __global__ void k_slots(const int32_t* __restrict__ lig_ptr, int B, int L_cap, i
     for (int q = a0; q < a1; ++q) slot_of[q] = p;
 }
 
-// wave per node: graph id, coordinates and (with tables) the feature row and the first-layer receptor sums
+// k_slots for struck slots: the same with rec_drop [B]. A struck slot has one row less, so node_ptr[p] also counts the
+// struck slots before p (a walk over the table per thread: B is a batch size); an entry of rec_drop outside
+// -1..n_rec-1 makes the whole table bad.
+__global__ void k_slots_struck(const int32_t* __restrict__ lig_ptr, const int32_t* __restrict__ rec_drop, int B,
+                               int L_cap, int n_rec, int slot_cap, int32_t* __restrict__ node_ptr,
+                               int32_t* __restrict__ slot_of, int32_t* __restrict__ status) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p > B) return;
+    int struck = 0;
+    for (int k = 0; k < p; ++k) struck += rec_drop[k] >= 0 ? 1 : 0;
+    if (p == B) {
+        const int t = lig_ptr[B];
+        bool bad = lig_ptr[0] != 0;
+        for (int k = 0; k < B; ++k) {
+            const int a0 = lig_ptr[k], a1 = lig_ptr[k + 1];
+            bad = bad || a0 < 0 || a1 < a0 || a1 - a0 > slot_cap || a1 > L_cap || !pvs_rec_drop_ok(rec_drop[k], n_rec);
+        }
+        node_ptr[B] = bad ? B * n_rec : t + B * n_rec - struck;
+        *status = bad ? kPvsBadTable : 0;
+        return;
+    }
+    const int a0 = lig_ptr[p], a1 = lig_ptr[p + 1];
+    if (a0 < 0 || a1 < a0 || a1 - a0 > slot_cap || a1 > L_cap) {
+        node_ptr[p] = p * n_rec;
+        return;
+    }
+    node_ptr[p] = a0 + p * n_rec - struck;
+    for (int q = a0; q < a1; ++q) slot_of[q] = p;
+}
+
+// wave per node: graph id, coordinates and (with tables) the feature row and the first-layer receptor sums (zero for
+// a struck slot's row that had the struck atom as a neighbour: its whole row is in the ligand-touching CSR)
+template <class Slots>
 __global__ void __launch_bounds__(256)
-k_node_tables_ragged(const float* __restrict__ lig_pos, const float* __restrict__ rec_pos, PvsRaggedSlots L,
+k_node_tables_ragged(const float* __restrict__ lig_pos, const float* __restrict__ rec_pos, Slots L,
+                     const int32_t* __restrict__ rr_rowptr, const int32_t* __restrict__ rr_col,
                      int32_t* __restrict__ node_graph, float* __restrict__ pos, PvsRaggedNodeTables t) {
     const int lane = threadIdx.x & 63;
     const int g = (blockIdx.x * 256 + threadIdx.x) >> 6;
@@ -322,6 +385,14 @@ k_node_tables_ragged(const float* __restrict__ lig_pos, const float* __restrict_
     int lig_row = -1, rec_row = -1;                        // padding: every table zero
     if (r.valid) {
         if (r.local < r.n_lig) lig_row = r.a0 + r.local; else rec_row = r.local - r.n_lig;
+    }
+    bool based = rec_row >= 0;                            // the row starts from the receptor's cached sums
+    if constexpr (kStruck<Slots>) {
+        if (rec_row >= 0) rec_row = pvs_struck_receptor(rec_row, r.drop);
+        if (rec_row >= 0 && r.drop >= 0 && t.base_magg) {
+            const int r0 = rr_rowptr[rec_row];
+            based = pvs_find_ascending(rr_col + r0, rr_rowptr[rec_row + 1] - r0, r.drop) < 0;
+        }
     }
     if (lane == 0) node_graph[g] = r.slot;
     if (lane < 3) {
@@ -335,9 +406,9 @@ k_node_tables_ragged(const float* __restrict__ lig_pos, const float* __restrict_
     }
     if (t.base_magg) {
         for (int c = lane; c < H; c += 64)
-            t.base_magg[(size_t)g * H + c] = rec_row >= 0 ? t.rec_magg[(size_t)rec_row * H + c] : 0.0f;
-        if (lane < 3) t.base_xsum[(size_t)g * 3 + lane] = rec_row >= 0 ? t.rec_xsum[(size_t)rec_row * 3 + lane] : 0.0f;
-        if (lane == 0) t.base_deg[g] = rec_row >= 0 ? t.rec_deg[rec_row] : 0.0f;
+            t.base_magg[(size_t)g * H + c] = based ? t.rec_magg[(size_t)rec_row * H + c] : 0.0f;
+        if (lane < 3) t.base_xsum[(size_t)g * 3 + lane] = based ? t.rec_xsum[(size_t)rec_row * 3 + lane] : 0.0f;
+        if (lane == 0) t.base_deg[g] = based ? t.rec_deg[rec_row] : 0.0f;
     }
 }
 
@@ -350,18 +421,16 @@ extern "C" size_t pvs_screen_graph_ragged_cap_state_bytes(int32_t B, int32_t L_c
     return carve_screen(a, (size_t)L_cap, L_cap + B * n_rec, n_rec, pvs_slot_words(slot_cap), true, nullptr) + 256;
 }
 
-extern "C" int pvs_screen_graph_build_ragged_cap(const float* lig_pos, const int32_t* lig_ptr, const float* rec_pos,
-                                                 const int32_t* rr_rowptr, const int32_t* rr_col, int32_t B,
-                                                 int32_t L_cap, int32_t n_rec, int32_t slot_cap, double inter_radius,
-                                                 double intra_radius, int32_t capacity, int32_t capacity_lig,
-                                                 int32_t* rowptr, int32_t* row, int32_t* col, uint8_t* etype,
-                                                 float* inv_deg, int32_t* rowptr_lig, int32_t* row_lig,
-                                                 int32_t* col_lig, uint8_t* etype_lig, int32_t* node_ptr,
-                                                 int32_t* node_graph, float* pos, const PvsRaggedNodeTables* tables,
-                                                 int32_t* status, void* state, size_t state_bytes,
-                                                 pvs_stream_t stream_) {
+namespace {
+// the ragged builder; with rec_drop (a device table [B]) its slots are struck slots
+int build_ragged(const char* who, const float* lig_pos, const int32_t* lig_ptr, const int32_t* rec_drop,
+                 const float* rec_pos, const int32_t* rr_rowptr, const int32_t* rr_col, int32_t B, int32_t L_cap,
+                 int32_t n_rec, int32_t slot_cap, double inter_radius, double intra_radius, int32_t capacity,
+                 int32_t capacity_lig, int32_t* rowptr, int32_t* row, int32_t* col, uint8_t* etype, float* inv_deg,
+                 int32_t* rowptr_lig, int32_t* row_lig, int32_t* col_lig, uint8_t* etype_lig, int32_t* node_ptr,
+                 int32_t* node_graph, float* pos, const PvsRaggedNodeTables* tables, int32_t* status, void* state,
+                 size_t state_bytes, pvs_stream_t stream_) {
     hipStream_t s = (hipStream_t)stream_;
-    const char* who = "pvs_screen_graph_build_ragged_cap";
     PVS_REQUIRE(lig_pos && lig_ptr && rec_pos && rr_rowptr && rr_col && rowptr && row && col && etype && inv_deg &&
                 rowptr_lig && row_lig && col_lig && etype_lig && node_ptr && node_graph && pos && status && state,
                 "%s: NULL", who);
@@ -383,15 +452,70 @@ extern "C" int pvs_screen_graph_build_ragged_cap(const float* lig_pos, const int
     carve_screen(arena, (size_t)L_cap, L_cap + B * n_rec, n_rec, pvs_slot_words(slot_cap), true, &w);
     PVS_REQUIRE(arena.ok(), "%s: state too small (%zu < %zu)", who, state_bytes, arena.off);
     PvsProfScope prof(s, PVS_PROF_PREPARE);
-    const PvsRaggedSlots L{lig_ptr, node_ptr, w.slot_of, status, B, L_cap, n_rec, slot_cap};
-    k_slots<<<(B + 1 + 255) / 256, 256, 0, s>>>(lig_ptr, B, L_cap, n_rec, slot_cap, node_ptr, w.slot_of, status);
-    PVS_CHECK_LAUNCH();
-    PVS_TRY(build_csrs(L, lig_pos, rec_pos, rr_rowptr, rr_col, inter_radius, intra_radius, rowptr, rowptr_lig,
-                       OutCsr{rowptr, row, col, etype, capacity},
-                       OutCsr{rowptr_lig, row_lig, col_lig, etype_lig, capacity_lig}, inv_deg, status, false, w, s));
-    k_node_tables_ragged<<<(L.rows() + 3) / 4, 256, 0, s>>>(lig_pos, rec_pos, L, node_graph, pos, t);
+    const OutCsr full{rowptr, row, col, etype, capacity}, lig{rowptr_lig, row_lig, col_lig, etype_lig, capacity_lig};
+    const int n_rows = L_cap + B * n_rec;
+    if (rec_drop) {
+        const PvsStruckSlots L{lig_ptr, node_ptr, w.slot_of, status, rec_drop, B, L_cap, n_rec, slot_cap};
+        k_slots_struck<<<(B + 1 + 255) / 256, 256, 0, s>>>(lig_ptr, rec_drop, B, L_cap, n_rec, slot_cap, node_ptr,
+                                                           w.slot_of, status);
+        PVS_CHECK_LAUNCH();
+        PVS_TRY(build_csrs(L, lig_pos, rec_pos, rr_rowptr, rr_col, inter_radius, intra_radius, rowptr, rowptr_lig, full,
+                           lig, inv_deg, status, false, w, s));
+        k_node_tables_ragged<<<(n_rows + 3) / 4, 256, 0, s>>>(lig_pos, rec_pos, L, rr_rowptr, rr_col, node_graph, pos, t);
+    } else {
+        const PvsRaggedSlots L{lig_ptr, node_ptr, w.slot_of, status, B, L_cap, n_rec, slot_cap};
+        k_slots<<<(B + 1 + 255) / 256, 256, 0, s>>>(lig_ptr, B, L_cap, n_rec, slot_cap, node_ptr, w.slot_of, status);
+        PVS_CHECK_LAUNCH();
+        PVS_TRY(build_csrs(L, lig_pos, rec_pos, rr_rowptr, rr_col, inter_radius, intra_radius, rowptr, rowptr_lig, full,
+                           lig, inv_deg, status, false, w, s));
+        k_node_tables_ragged<<<(n_rows + 3) / 4, 256, 0, s>>>(lig_pos, rec_pos, L, rr_rowptr, rr_col, node_graph, pos, t);
+    }
     PVS_CHECK_LAUNCH();
     return 0;
+}
+}  // namespace
+
+extern "C" int pvs_screen_graph_build_ragged_cap(const float* lig_pos, const int32_t* lig_ptr, const float* rec_pos,
+                                                 const int32_t* rr_rowptr, const int32_t* rr_col, int32_t B,
+                                                 int32_t L_cap, int32_t n_rec, int32_t slot_cap, double inter_radius,
+                                                 double intra_radius, int32_t capacity, int32_t capacity_lig,
+                                                 int32_t* rowptr, int32_t* row, int32_t* col, uint8_t* etype,
+                                                 float* inv_deg, int32_t* rowptr_lig, int32_t* row_lig,
+                                                 int32_t* col_lig, uint8_t* etype_lig, int32_t* node_ptr,
+                                                 int32_t* node_graph, float* pos, const PvsRaggedNodeTables* tables,
+                                                 int32_t* status, void* state, size_t state_bytes,
+                                                 pvs_stream_t stream_) {
+    return build_ragged("pvs_screen_graph_build_ragged_cap", lig_pos, lig_ptr, nullptr, rec_pos, rr_rowptr, rr_col, B,
+                        L_cap, n_rec, slot_cap, inter_radius, intra_radius, capacity, capacity_lig, rowptr, row, col,
+                        etype, inv_deg, rowptr_lig, row_lig, col_lig, etype_lig, node_ptr, node_graph, pos, tables,
+                        status, state, state_bytes, stream_);
+}
+
+// ---- struck slots: pvs_screen_graph_build_ragged_cap plus rec_drop [B] (int32, on the device): -1, or the receptor
+// atom that the slot's receptor lacks (screen_slots.h: PvsStruckSlots). The slot's graph is what the reference's masking
+// leaves of the unstruck slot's graph: the atom and every edge that touches it are gone, the ids above it move down by
+// one, classes and in-row order stay. A receptor row that had the atom as a template neighbour can no longer start from
+// the receptor's cached first-layer sums: its base is zero and its WHOLE row (ligand entries, then the class-2 entries
+// that remain) is in the ligand-touching CSR, which is all pvs_egnn_layer_fwd_partial needs. An entry outside
+// -1..n_rec-1: *status bit 3 and an edgeless batch, as for a bad lig_ptr. ----
+extern "C" size_t pvs_screen_graph_struck_state_bytes(int32_t B, int32_t L_cap, int32_t n_rec, int32_t slot_cap) {
+    return pvs_screen_graph_ragged_cap_state_bytes(B, L_cap, n_rec, slot_cap);
+}
+
+extern "C" int pvs_screen_graph_build_struck(const float* lig_pos, const int32_t* lig_ptr, const int32_t* rec_drop,
+                                             const float* rec_pos, const int32_t* rr_rowptr, const int32_t* rr_col,
+                                             int32_t B, int32_t L_cap, int32_t n_rec, int32_t slot_cap,
+                                             double inter_radius, double intra_radius, int32_t capacity,
+                                             int32_t capacity_lig, int32_t* rowptr, int32_t* row, int32_t* col,
+                                             uint8_t* etype, float* inv_deg, int32_t* rowptr_lig, int32_t* row_lig,
+                                             int32_t* col_lig, uint8_t* etype_lig, int32_t* node_ptr,
+                                             int32_t* node_graph, float* pos, const PvsRaggedNodeTables* tables,
+                                             int32_t* status, void* state, size_t state_bytes, pvs_stream_t stream_) {
+    PVS_REQUIRE(rec_drop, "pvs_screen_graph_build_struck: NULL rec_drop");
+    return build_ragged("pvs_screen_graph_build_struck", lig_pos, lig_ptr, rec_drop, rec_pos, rr_rowptr, rr_col, B,
+                        L_cap, n_rec, slot_cap, inter_radius, intra_radius, capacity, capacity_lig, rowptr, row, col,
+                        etype, inv_deg, rowptr_lig, row_lig, col_lig, etype_lig, node_ptr, node_graph, pos, tables,
+                        status, state, state_bytes, stream_);
 }
 
 // the pair from before slots could be wider than one mask word: slots of 0..64 atoms

@@ -1,5 +1,6 @@
 // Where the slots of a pose batch live (screen_graph.hip), and the table bisection the graph builders share.
-// A slot holds one pose: its ligand atoms, then the receptor's n_rec atoms. Two layouts answer the same questions
+// A slot holds one pose: its ligand atoms, then the receptor's n_rec atoms (struck slots, at the end of this file: all
+// but one of them). The layouts answer the same questions
 // (how many packed ligand atoms and node rows there are; which slot a packed atom or a row belongs to), so that the
 // builder's kernels exist once: uniform (B poses of one n_lig-atom ligand, by arithmetic) and ragged (one pose of any
 // ligand of 0..slot_cap atoms per slot, from the device tables lig_ptr / node_ptr / slot_of). A ligand atom's contacts
@@ -52,6 +53,7 @@ struct PvsSlotRow {
     bool valid;
     int slot, a0, n_lig;
     int node0, local;               // the slot's first row; this row inside the slot (< n_lig: ligand atom, else receptor)
+    int drop = -1;                  // the receptor atom that the slot's receptor lacks (PvsStruckSlots); -1: none
 };
 
 // B poses of one ligand: slot p owns the atoms p * n_lig .. and the rows p * (n_lig + n_rec) ..; every row is valid.
@@ -87,5 +89,51 @@ struct PvsRaggedSlots {
         if (g >= node_ptr[B] || (*status & kPvsBadTable)) return {false, -1, 0, 0, 0, 0};
         const int p = pvs_last_le(node_ptr, B, g), a0 = lig_ptr[p], node0 = node_ptr[p];
         return {true, p, a0, lig_ptr[p + 1] - a0, node0, g - node0};
+    }
+};
+
+// ---- struck slots: a slot's receptor may lack one atom (rec_drop[p] = r in 0..n_rec-1; -1: the whole receptor) ----
+// The receptor atoms of a struck slot keep their order with r left out, so the slot owns n_lig + n_rec - 1 rows and
+// node_ptr[p] = lig_ptr[p] + p * n_rec - (struck slots before p). A row's `local` counts the slot's rows as they are
+// (compact); pvs_struck_receptor turns the receptor part of it back into the receptor's own numbering.
+
+// A valid entry of rec_drop.
+PVS_SLOTS_FN bool pvs_rec_drop_ok(int drop, int n_rec) { return drop >= -1 && drop < n_rec; }
+
+// The receptor atom behind the k-th receptor row of a slot without atom `drop`, and the row of receptor atom i (i !=
+// drop) in such a slot.
+PVS_SLOTS_FN int pvs_struck_receptor(int k, int drop) { return k + ((drop >= 0 && k >= drop) ? 1 : 0); }
+PVS_SLOTS_FN int pvs_struck_row(int i, int drop) { return i - ((drop >= 0 && i > drop) ? 1 : 0); }
+
+// Where `v` stands in the ascending row col[0 .. n); -1 when it is not there (a receptor row of the template CSR: is
+// the struck atom one of its neighbours, and at which place).
+PVS_SLOTS_FN int pvs_find_ascending(const int32_t* col, int n, int v) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (col[mid] < v) lo = mid + 1; else hi = mid;
+    }
+    return (lo < n && col[lo] == v) ? lo : -1;
+}
+
+// The ragged layout with rec_drop [B]: the same questions, and per row the atom its slot lacks. Not valid: as for
+// PvsRaggedSlots (kPvsBadTable also stands for a rec_drop entry outside -1..n_rec-1; k_slots_struck checks it).
+struct PvsStruckSlots {
+    const int32_t *lig_ptr, *node_ptr, *slot_of, *status, *rec_drop;
+    int B, L_cap, n_rec;
+    int slot_cap = 64;
+    PVS_SLOTS_FN int words() const { return pvs_slot_words(slot_cap); }
+    PVS_SLOTS_FN int atoms() const { return L_cap; }
+    PVS_SLOTS_FN int rows() const { return L_cap + B * n_rec; }
+    PVS_SLOTS_FN PvsSlotAtom atom(int q) const {
+        if ((*status & kPvsBadTable) || q >= lig_ptr[B]) return {false, 0, 0};
+        const int p = slot_of[q], a0 = lig_ptr[p];
+        return {true, a0, lig_ptr[p + 1] - a0};
+    }
+    PVS_SLOTS_FN int drop_of_atom(int q) const { return rec_drop[slot_of[q]]; }       // (of a valid atom)
+    PVS_SLOTS_FN PvsSlotRow row(int g) const {
+        if (g >= node_ptr[B] || (*status & kPvsBadTable)) return {false, -1, 0, 0, 0, 0};
+        const int p = pvs_last_le(node_ptr, B, g), a0 = lig_ptr[p], node0 = node_ptr[p];
+        return {true, p, a0, lig_ptr[p + 1] - a0, node0, g - node0, rec_drop[p]};
     }
 };

@@ -640,6 +640,90 @@ def leave_out_ligand_pack(lig_pos, lig_feats, lig_ptr, first_copy, n_slots, slot
     return out_pos, out_feats, out_ptr, status
 
 
+def contact_pairs(lig_pos, lig_ptr, rec_pos, radius, host_ptr=False):
+    """The ligand-receptor contacts of packed hits (pvs_contact_pairs_count / _fill): lig_pos [L, 3] fp32, lig_ptr
+    [S + 1] int32 (hit s: the rows lig_ptr[s] .. lig_ptr[s + 1]) and rec_pos [n_rec, 3] fp32, all on the device. A pair
+    (a, r) - ligand atom a counted inside its hit, receptor atom r - is a contact exactly when the pose-batch builders
+    write a class-1 edge for it at inter radius `radius` (the same fp64 distance and compares). Returns (pairs [K, 2]
+    int32, pair_ptr [S + 1] int32): the rows pair_ptr[s] .. pair_ptr[s + 1] are hit s's contacts, sorted by a then r.
+    K = pair_ptr[S] is read back once (the call's one wait for the device); ValueError when lig_ptr does not ascend
+    from 0 inside L. host_ptr: that one copy brings the whole pair_ptr, returned third (a host int32 tensor)."""
+    lig_pos, rec_pos = _c(lig_pos, _F32, _FP32_ONLY), _c(rec_pos, _F32, _FP32_ONLY)
+    if lig_pos.dim() != 2 or lig_pos.shape[1] != 3 or rec_pos.dim() != 2 or rec_pos.shape[1] != 3 or rec_pos.shape[0] < 1:
+        raise ValueError('contact_pairs: lig_pos [L, 3] and rec_pos [n_rec >= 1, 3]')
+    if lig_ptr.dtype != torch.int32 or lig_ptr.dim() != 1 or lig_ptr.numel() < 1:
+        raise ValueError('contact_pairs: an int32 lig_ptr [S + 1]')
+    if not float(radius) > 0:
+        raise ValueError(f'contact_pairs: radius must be positive (got {radius})')
+    if lig_pos.shape[0] * rec_pos.shape[0] >= 2 ** 31:
+        raise ValueError('contact_pairs: L * n_rec passes 2^31')
+    _lib.require_hip(lig_pos, lig_ptr, rec_pos)
+    dev, n_hits = lig_pos.device, lig_ptr.numel() - 1
+    lig_ptr = lig_ptr.contiguous()
+    pair_ptr = torch.empty(n_hits + 1, dtype=torch.int32, device=dev)
+    args = (_lib.ptr(lig_pos), _lib.ptr(lig_ptr), n_hits, lig_pos.shape[0], _lib.ptr(rec_pos), rec_pos.shape[0],
+            float(radius), _lib.ptr(pair_ptr))
+    _lib.check(_lib.lib().pvs_contact_pairs_count(*args, _stream(dev)), 'pvs_contact_pairs_count')
+    on_host = pair_ptr.cpu() if host_ptr else pair_ptr[n_hits:].cpu()
+    n_pairs = int(on_host[-1])
+    if n_pairs < 0:
+        raise ValueError('contact_pairs: lig_ptr is not an ascending table from 0 inside lig_pos')
+    pairs = torch.empty((n_pairs, 2), dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().pvs_contact_pairs_fill(*args, n_pairs, _lib.ptr(pairs), _stream(dev)),
+               'pvs_contact_pairs_fill')
+    return (pairs, pair_ptr, on_host) if host_ptr else (pairs, pair_ptr)
+
+
+def leave_out_pair_pack(lig_pos, lig_feats, lig_ptr, pairs, pair_ptr, n_rec, first_copy, n_slots, slot_cap, out=None):
+    """Copies of a set of hits that leave out one ligand-receptor pair each, as the slots of a struck pose batch
+    (pvs_leave_out_pair_pack). lig_pos [L, 3], lig_feats [L, F] fp32, lig_ptr [S + 1] int32, pairs [K, 2] int32 (ligand
+    atom a counted inside its hit or -1, receptor atom r or -1), pair_ptr [S + 1] int32 (hit s: the rows pair_ptr[s] ..
+    pair_ptr[s + 1] of pairs), first_copy: one int32, all on the device. Hit s owns the copies pair_ptr[s] + s ..: the
+    whole ligand, then one per row of its pairs; slot k of the batch holds copy first_copy + k (nothing past the last
+    copy). Returns (out_pos [n_slots * slot_cap, 3], out_feats [.., F], out_ptr [n_slots + 1] int32, rec_drop [n_slots]
+    int32, status [1] int32): the hit's rows without atom a, and rec_drop[k] = r (-1: the whole receptor). `out`: those
+    five tensors to write into. status: 8 when lig_ptr or pair_ptr does not ascend from 0 inside L / K, a ligand has
+    more than slot_cap atoms or a pair of one of the batch's copies is outside its hit or the receptor (out_ptr all
+    zeros, rec_drop all -1, no row written). One launch, no atomics, no host synchronisation."""
+    lig_pos, lig_feats = _c(lig_pos, _F32, _FP32_ONLY), _c(lig_feats, _F32, _FP32_ONLY)
+    n_slots, slot_cap, n_rec = int(n_slots), int(slot_cap), int(n_rec)
+    if (lig_pos.dim() != 2 or lig_pos.shape[1] != 3 or lig_feats.dim() != 2 or lig_feats.shape[0] != lig_pos.shape[0]
+            or lig_feats.shape[1] < 1):
+        raise ValueError('leave_out_pair_pack: lig_pos [L, 3] and lig_feats [L, F] of the same L')
+    if lig_ptr.dtype != torch.int32 or lig_ptr.dim() != 1 or lig_ptr.numel() < 1:
+        raise ValueError('leave_out_pair_pack: an int32 lig_ptr [S + 1]')
+    if pair_ptr.dtype != torch.int32 or pair_ptr.dim() != 1 or pair_ptr.numel() != lig_ptr.numel():
+        raise ValueError('leave_out_pair_pack: an int32 pair_ptr [S + 1], as long as lig_ptr')
+    if pairs.dtype != torch.int32 or pairs.dim() != 2 or pairs.shape[1] != 2 or not pairs.is_contiguous():
+        raise ValueError('leave_out_pair_pack: contiguous int32 pairs [K, 2]')
+    if first_copy.dtype != torch.int32 or first_copy.numel() < 1:
+        raise ValueError('leave_out_pair_pack: first_copy is one int32 on the device')
+    if n_slots < 1 or slot_cap < 1 or n_rec < 1:
+        raise ValueError(f'leave_out_pair_pack: {n_slots} slots of up to {slot_cap} atoms against {n_rec} receptor atoms')
+    _lib.require_hip(lig_pos, lig_feats, lig_ptr, pairs, pair_ptr, first_copy)
+    dev, n_feats, rows = lig_pos.device, lig_feats.shape[1], n_slots * slot_cap
+    if out is None:
+        out = (torch.empty((rows, 3), dtype=torch.float32, device=dev),
+               torch.empty((rows, n_feats), dtype=torch.float32, device=dev),
+               torch.empty(n_slots + 1, dtype=torch.int32, device=dev),
+               torch.empty(n_slots, dtype=torch.int32, device=dev), torch.empty(1, dtype=torch.int32, device=dev))
+    out_pos, out_feats, out_ptr, rec_drop, status = out
+    _lib.require_hip(*out)
+    if (out_pos.dtype != torch.float32 or out_feats.dtype != torch.float32 or out_pos.dim() != 2 or out_feats.dim() != 2
+            or out_pos.shape[0] < rows or out_pos.shape[1] != 3 or out_feats.shape[0] < rows
+            or out_feats.shape[1] != n_feats or out_ptr.dtype != torch.int32 or out_ptr.numel() != n_slots + 1
+            or rec_drop.dtype != torch.int32 or rec_drop.numel() != n_slots
+            or status.dtype != torch.int32 or status.numel() < 1):
+        raise ValueError(f'leave_out_pair_pack: out = (pos [>= {rows}, 3], feats [>= {rows}, {n_feats}], int32 ptr '
+                         f'[{n_slots + 1}], int32 rec_drop [{n_slots}], int32 status [1])')
+    _lib.check(_lib.lib().pvs_leave_out_pair_pack(
+        _lib.ptr(lig_pos), _lib.ptr(lig_feats), _lib.ptr(lig_ptr), _lib.ptr(pairs), _lib.ptr(pair_ptr),
+        lig_ptr.numel() - 1, lig_pos.shape[0], pairs.shape[0], n_feats, n_rec, _lib.ptr(first_copy), n_slots, slot_cap,
+        _lib.ptr(out_pos), _lib.ptr(out_feats), _lib.ptr(out_ptr), _lib.ptr(rec_drop), _lib.ptr(status), _stream(dev)),
+        'pvs_leave_out_pair_pack')
+    return out_pos, out_feats, out_ptr, rec_drop, status
+
+
 def new_contact_accumulators(n_rec, device):
     """Fresh accumulators of `contact_attention`: (rec_sum [n_rec] float64 zeros, rec_count [n_rec] int32 zeros,
     rec_max [n_rec] float32 NaN: none so far)."""

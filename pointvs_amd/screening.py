@@ -500,6 +500,31 @@ def leave_out_plan(sizes, batch_size):
     return [copies[k:k + batch_size] for k in range(0, len(copies), batch_size)]
 
 
+def leave_out_pair_plan(pair_counts, sizes, batch_size, ligand_atom=True, receptor_atom=True):
+    """The batches that hold every copy of hits of `sizes` atoms that leaves out one row of the hit's pair table
+    (`pair_counts[s]` rows): hit s owns pair_counts[s] + 1 consecutive copies (the whole ligand: sizes[s] atoms, the
+    whole receptor; then one copy per row: sizes[s] - 1 atoms when the rows name a ligand atom, `ligand_atom`, and a
+    receptor without one atom when they name a receptor atom, `receptor_atom`), sum(pair_counts) + len(sizes) copies in
+    all, `batch_size` per batch in that order. A list of batches, each (a list of `batch_size` atom counts, the number
+    of its slots that lack a receptor atom); the slots after the last copy are empty (0). What
+    pvs_leave_out_pair_pack lays out on the device, as pure host arithmetic."""
+    batch_size = int(batch_size)
+    if batch_size < 1:
+        raise ValueError(f'batch_size must be positive (got {batch_size})')
+    sizes, pair_counts = [int(n) for n in sizes], [int(k) for k in pair_counts]
+    if len(sizes) != len(pair_counts):
+        raise ValueError('pair_counts and sizes differ in length')
+    if any(n < 0 for n in sizes) or any(k < 0 for k in pair_counts):
+        raise ValueError(f'sizes and pair counts must not be negative (got {sizes}, {pair_counts})')
+    if ligand_atom and any(k > 0 and n == 0 for k, n in zip(pair_counts, sizes)):
+        raise ValueError('a hit without atoms has no ligand atom to leave out')
+    less = 1 if ligand_atom else 0
+    copies = [c for n, k in zip(sizes, pair_counts) for c in [(n, 0)] + [(n - less, 1 if receptor_atom else 0)] * k]
+    copies += [(0, 0)] * ((-len(copies)) % batch_size)
+    return [([n for n, _ in copies[k:k + batch_size]], sum(d for _, d in copies[k:k + batch_size]))
+            for k in range(0, len(copies), batch_size)]
+
+
 class LibraryScreen(_ReceptorSideScreen):
     """Library screening: every one of the `batch_size` slots of a batch holds one pose of ANY ligand of up to
     `max_lig_atoms` (<= MAX_SCREEN_LIGAND_ATOMS = 1024) atoms against the one receptor, or nothing (the last batch of
@@ -531,11 +556,25 @@ class LibraryScreen(_ReceptorSideScreen):
     inside the captured step) into the static buffers `screen.contact`: lig_att [batch_size * max_lig_atoms] (packed
     atom order of the loaded batch) and slot_rec_att [batch_size, n_rec] - the largest attention over each atom's
     ligand-receptor edges, NaN without one - of the LAST step, and rec_sum / rec_count / rec_max [n_rec], accumulated
-    over every step since reset_contact_attention(). Needs the first-layer reuse."""
+    over every step since reset_contact_attention(). Needs the first-layer reuse.
+
+    struck: None, or True for a screen whose slots may lack one receptor atom each (receptor-atom and contact masking:
+    the reference's atom_masking / bond_masking remove atoms together with their edges). The screen then owns a static
+    `rec_drop [batch_size]` int32 (-1: the whole receptor; r: the slot's receptor is without atom r, so the slot has
+    n_rec - 1 receptor rows) and launches pvs_screen_graph_build_struck: the rows that had r as a receptor-receptor
+    neighbour take their whole first-layer row through the ligand-touching CSR with a zero base, every other row and
+    every kernel is as without it. `load(slots, rec_drop=[...])` and `load_leave_out_pairs` fill it. Needs the
+    first-layer reuse, and goes with neither `cam` nor `contact_attention` (their reductions assume n_rec receptor rows
+    per slot). A screen without it launches exactly what it always launched."""
 
     def __init__(self, model, rec_pos, rec_feats, batch_size, max_lig_atoms, edge_radius, intra_radius=None,
-                 tasks=None, contact_attention=None, cam=None):
+                 tasks=None, contact_attention=None, cam=None, struck=None):
         super().__init__(model, edge_radius, intra_radius, tasks)
+        self.struck = bool(struck)
+        if self.struck and (cam is not None or contact_attention is not None):
+            which = 'cam' if cam is not None else 'contact_attention'
+            raise ValueError(f'LibraryScreen(struck=True, {which}=...): the {which} reduction assumes n_rec receptor '
+                             'rows in every slot, and a struck slot has one less; use two screens')
         self.cam_request = cam
         self._cam_plan = resolve_cam(model, self.heads, self.tasks, cam)
         if not 1 <= int(max_lig_atoms) <= MAX_SCREEN_LIGAND_ATOMS:
@@ -549,6 +588,11 @@ class LibraryScreen(_ReceptorSideScreen):
         self.b, self.max_lig_atoms = int(batch_size), int(max_lig_atoms)
         self.slot_cap = max(self.max_lig_atoms, 64)      # what the builder validates lig_ptr against
         self.n_rec = int(rec_pos.shape[0])
+        if self.struck and not self.reuse:
+            raise ValueError(
+                'LibraryScreen(struck=True): struck slots are built for the step of the first-layer reuse, which this '
+                'model does not have (softmax attention, edge_residual or a hidden size other than 32 / 64); mask it '
+                'one complex at a time with pointvs_amd.attribution.bond_masking / atom_masking')
         self.l_cap = self.b * self.max_lig_atoms
         self.n_cap = self.l_cap + self.b * self.n_rec
         self._rec_pos = rec_pos.float().contiguous()
@@ -561,6 +605,8 @@ class LibraryScreen(_ReceptorSideScreen):
         self._sizes = [0] * self.b
         self._stage, self._stage_at = [], 0
         self._pack_status = None     # load_leave_out's status word
+        self.rec_drop = torch.full((self.b,), -1, dtype=torch.int32, device=dev) if self.struck else None
+        self._n_struck = 0           # host copy: how many slots of the loaded batch lack a receptor atom
         self.contact_attention = resolve_attention_layer(model, contact_attention)       # (index into model.layers)
         self.contact = None
         if self.contact_attention is not None:
@@ -632,13 +678,31 @@ class LibraryScreen(_ReceptorSideScreen):
             t.rec_magg, t.rec_xsum, t.rec_deg = (_lib.ptr(v) for v in (self.rec_magg, self.rec_xsum, self.rec_deg))
 
     # ---- inputs ----
-    def load_packed(self, lig_pos, lig_feats, lig_ptr, sizes):
+    def _load_rec_drop(self, rec_drop, n_slots):
+        """The static rec_drop of a struck screen <- a host list (None: every slot has the whole receptor)."""
+        if rec_drop is None:
+            if self.struck:
+                self.rec_drop.fill_(-1)
+            self._n_struck = 0
+            return
+        if not self.struck:
+            raise ValueError('rec_drop: the screen was built without struck=True')
+        drops = [int(r) for r in rec_drop]
+        if len(drops) > self.b or len(drops) != n_slots or any(not -1 <= r < self.n_rec for r in drops):
+            raise ValueError(f'rec_drop: one entry of -1..{self.n_rec - 1} per slot ({n_slots}; got {drops})')
+        drops += [-1] * (self.b - len(drops))
+        self.rec_drop.copy_(torch.tensor(drops, dtype=torch.int32))
+        self._n_struck = sum(r >= 0 for r in drops)
+
+    def load_packed(self, lig_pos, lig_feats, lig_ptr, sizes, rec_drop=None):
         """One batch from packed device (or pinned host) tensors: lig_pos [L,3], lig_feats [L,F] (L = sum of
         sizes), lig_ptr [batch_size+1] int32; `sizes`: the host's copy of the slots' atom counts. Three
-        asynchronous copies into the step's static inputs."""
+        asynchronous copies into the step's static inputs. rec_drop (a struck screen): a host list, one entry per
+        slot of `sizes`."""
         sizes = [int(n) for n in sizes]
         if len(sizes) > self.b or any(not 0 <= n <= self.max_lig_atoms for n in sizes):
             raise ValueError(f'a batch holds up to {self.b} slots of 0..{self.max_lig_atoms} atoms (got {sizes})')
+        self._load_rec_drop(rec_drop, len(sizes))
         total = sum(sizes)
         if lig_pos.shape[0] != total or lig_feats.shape[0] != total or lig_ptr.numel() != self.b + 1:
             raise ValueError('packed ligand tensors do not match the slot sizes')
@@ -649,9 +713,10 @@ class LibraryScreen(_ReceptorSideScreen):
         self.n_atoms = total
         return self
 
-    def load(self, slots):
+    def load(self, slots, rec_drop=None):
         """slots: up to batch_size pairs (lig_feats [n,F], pose [n,3]), n = 0..max_lig_atoms (host or device
-        tensors); the slots after them are empty. Host tensors are packed into pinned staging."""
+        tensors); the slots after them are empty. Host tensors are packed into pinned staging. rec_drop (a struck
+        screen, hand-built batches): a host list with one entry per slot, -1 or the receptor atom the slot lacks."""
         slots = list(slots)
         sizes = [int(pose.shape[0]) for _, pose in slots]
         if len(sizes) > self.b or any(not 0 <= n <= self.max_lig_atoms for n in sizes):
@@ -677,7 +742,7 @@ class LibraryScreen(_ReceptorSideScreen):
                 st['feats'][at:at + sizes[k]].copy_(feats)
                 at += sizes[k]
         st['ptr'][self.b] = at
-        self.load_packed(st['pos'][:total], st['feats'][:total], st['ptr'], sizes)
+        self.load_packed(st['pos'][:total], st['feats'][:total], st['ptr'], sizes, rec_drop)
         st['event'] = torch.cuda.Event()
         st['event'].record(torch.cuda.current_stream(self.lig_pos.device))
         return self
@@ -695,8 +760,33 @@ class LibraryScreen(_ReceptorSideScreen):
             self._pack_status = torch.zeros(1, dtype=torch.int32, device=self.lig_pos.device)
         PF.leave_out_ligand_pack(lig_pos, lig_feats, lig_ptr, first_copy, self.b, self.max_lig_atoms,
                                  out=(self.lig_pos, self.lig_feats, self.lig_ptr, self._pack_status))
+        self._load_rec_drop(None, len(sizes))
         self._sizes = sizes + [0] * (self.b - len(sizes))
         self.n_atoms = sum(sizes)
+        return self
+
+    def load_leave_out_pairs(self, lig_pos, lig_feats, lig_ptr, pairs, pair_ptr, sizes, n_struck, first_copy):
+        """One batch of copies that leave out one ligand-receptor pair each (PF.leave_out_pair_pack: slot k holds copy
+        first_copy + k of the hits lig_pos [L,3] / lig_feats [L,F] / lig_ptr [S+1] with the pair table pairs [K,2] /
+        pair_ptr [S+1], all on the device), packed by one launch straight into the step's static inputs, rec_drop
+        among them. `sizes`, `n_struck`: the host's copy of the slots' atom counts and of how many of them lack a
+        receptor atom (a batch of `leave_out_pair_plan`); nothing is copied back. `check_leave_out()` reads the
+        packer's verdict on the tables."""
+        if not self.struck:
+            raise ValueError('load_leave_out_pairs: the screen was built without struck=True')
+        sizes = [int(n) for n in sizes]
+        if len(sizes) > self.b or any(not 0 <= n <= self.max_lig_atoms for n in sizes):
+            raise ValueError(f'a batch holds up to {self.b} slots of 0..{self.max_lig_atoms} atoms (got {sizes})')
+        if not 0 <= int(n_struck) <= len(sizes):
+            raise ValueError(f'n_struck: 0..{len(sizes)} of the batch\'s slots (got {n_struck})')
+        if self._pack_status is None:
+            self._pack_status = torch.zeros(1, dtype=torch.int32, device=self.lig_pos.device)
+        PF.leave_out_pair_pack(lig_pos, lig_feats, lig_ptr, pairs, pair_ptr, self.n_rec, first_copy, self.b,
+                               self.max_lig_atoms,
+                               out=(self.lig_pos, self.lig_feats, self.lig_ptr, self.rec_drop, self._pack_status))
+        self._sizes = sizes + [0] * (self.b - len(sizes))
+        self.n_atoms = sum(sizes)
+        self._n_struck = int(n_struck)
         return self
 
     def check_leave_out(self):
@@ -704,7 +794,8 @@ class LibraryScreen(_ReceptorSideScreen):
         (its batch was empty then). Waits for the device."""
         if self._pack_status is not None and int(self._pack_status.item()) & 8:
             raise ValueError(f'LibraryScreen.load_leave_out: lig_ptr is not a table of 0..{self.max_lig_atoms}-atom '
-                             'ligands inside lig_pos')
+                             'ligands inside lig_pos'
+                             + (', or the pair table is not one of pairs inside them' if self.struck else ''))
 
     # ---- the graph and the node tables ----
     def _buffers(self, cap, cap_l):
@@ -715,8 +806,9 @@ class LibraryScreen(_ReceptorSideScreen):
         hid = self.egnn[0].hidden_nf
         f = _csr_buffers(
             dev, n_cap, cap_l, cap,
-            state=torch.empty(lib.pvs_screen_graph_ragged_cap_state_bytes(self.b, self.l_cap, self.n_rec,
-                                                                          self.slot_cap),
+            state=torch.empty((lib.pvs_screen_graph_struck_state_bytes if self.struck else
+                               lib.pvs_screen_graph_ragged_cap_state_bytes)(self.b, self.l_cap, self.n_rec,
+                                                                            self.slot_cap),
                               dtype=torch.uint8, device=dev),
             node_ptr=torch.zeros(self.b + 1, **i32), node_graph=torch.empty(n_cap, **i32),
             pos=torch.empty((n_cap, 3), **f32), x=torch.empty((n_cap, self.lig_feats.shape[1]), **f32),
@@ -732,6 +824,17 @@ class LibraryScreen(_ReceptorSideScreen):
 
     def _launch_builder(self, f):
         lib = _lib.lib()
+        if self.struck:
+            _lib.check(lib.pvs_screen_graph_build_struck(
+                _lib.ptr(self.lig_pos), _lib.ptr(self.lig_ptr), _lib.ptr(self.rec_drop), _lib.ptr(self._rec_pos),
+                _lib.ptr(self._rr.t['rowptr']), _lib.ptr(self._rr.t['col']), self.b, self.l_cap, self.n_rec,
+                self.slot_cap, float(self.r_inter), float(self.r_intra),
+                f['cap'], f['cap_l'], _lib.ptr(f['rowptr']), _lib.ptr(f['row']), _lib.ptr(f['col']),
+                _lib.ptr(f['etype']), _lib.ptr(f['inv_deg']), _lib.ptr(f['rowptr_l']), _lib.ptr(f['row_l']),
+                _lib.ptr(f['col_l']), _lib.ptr(f['etype_l']), _lib.ptr(f['node_ptr']), _lib.ptr(f['node_graph']),
+                _lib.ptr(f['pos']), C.byref(f['tables']), _lib.ptr(f['status']), _lib.ptr(f['state']),
+                f['state'].numel(), _stream(self.lig_pos.device)), 'pvs_screen_graph_build_struck')
+            return
         _lib.check(lib.pvs_screen_graph_build_ragged_cap(
             _lib.ptr(self.lig_pos), _lib.ptr(self.lig_ptr), _lib.ptr(self._rec_pos), _lib.ptr(self._rr.t['rowptr']),
             _lib.ptr(self._rr.t['col']), self.b, self.l_cap, self.n_rec, self.slot_cap, float(self.r_inter),
@@ -746,7 +849,8 @@ class LibraryScreen(_ReceptorSideScreen):
         """One synchronous probe: the builder with no room for edges leaves both exact edge counts in its row
         pointers. Room for the ligand-touching edges: twice the loaded batch's contacts per ligand atom at a full
         batch of L_cap atoms, at most what L_cap atoms can have (per atom: inter and intra contacts with the receptor,
-        both directions, and the slot's other ligand atoms)."""
+        both directions, and the slot's other ligand atoms). A struck screen adds the whole rows of the receptor rows
+        that the struck atom can touch (`_struck_room`) for every slot."""
         probe = self._buffers(1, 1)
         probe['cap'] = probe['cap_l'] = 0
         self._launch_builder(probe)
@@ -754,9 +858,24 @@ class LibraryScreen(_ReceptorSideScreen):
         per_atom = -(-n_lig_edges // max(self.n_atoms, 1))
         cap_l = min(self.l_cap * (4 * self.n_rec + self.slot_cap), 2 * per_atom * self.l_cap + 4096)
         cap = self.b * self._rr.n_edges + cap_l
+        if self.struck:
+            cap_l += self.b * self._struck_room()
         if cap >= 2 ** 31:
             raise ValueError(f'a batch of {self.b} slots can have {cap} edges (>= 2^31): use a smaller batch_size')
         return cap, cap_l
+
+    def _struck_room(self):
+        """The most receptor-receptor entries that one struck atom moves into a slot's ligand-touching CSR: max over r
+        of the sum over r's template neighbours j of deg_rr(j) - 1. From the template on the device, one number back
+        (at construction of the buffers)."""
+        n_edges = int(self._rr.n_edges)
+        if n_edges == 0:
+            return 0
+        rowptr, col = self._rr.t['rowptr'].long(), self._rr.t['col'][:n_edges].long()
+        deg = rowptr[1:] - rowptr[:-1]
+        rows = torch.repeat_interleave(torch.arange(self.n_rec, device=deg.device), deg)
+        moved = torch.zeros(self.n_rec, dtype=torch.int64, device=deg.device).index_add_(0, rows, deg[col] - 1)
+        return int(moved.max().item())
 
     def _graphs(self, n):
         """(PreparedGraph of the full CSR, PvsGraph of the ligand-touching CSR) over the first n nodes (the nodes
@@ -782,7 +901,8 @@ class LibraryScreen(_ReceptorSideScreen):
 
     def _raise_for(self, code):
         if code & 8:
-            raise ValueError(f'LibraryScreen: lig_ptr is not a table of 0..{self.slot_cap}-atom slots')
+            raise ValueError(f'LibraryScreen: lig_ptr is not a table of 0..{self.slot_cap}-atom slots'
+                             + (f', or rec_drop has an entry outside -1..{self.n_rec - 1}' if self.struck else ''))
         if code & 4:
             raise RuntimeError('LibraryScreen: edge buffer overflow (more ligand contacts per atom than twice '
                                'the first batch); rebuild the screen with a denser first batch')
@@ -828,7 +948,7 @@ class LibraryScreen(_ReceptorSideScreen):
         self._refresh_if_stale()
         f = self._build()
         # graphnorm's statistics run over the batch's nodes: no padding rows there (the host knows the count)
-        n = self.n_atoms + self.b * self.n_rec if self.graphnorm else self.n_cap
+        n = self.n_atoms + self.b * self.n_rec - self._n_struck if self.graphnorm else self.n_cap
         pg_full, g_lig = self._graphs(n)
         x = f['pos'][:n]
         h = self.embed.embed(f['x'][:n], x).contiguous()
@@ -858,6 +978,15 @@ class LibraryScreen(_ReceptorSideScreen):
 
     def replay(self, slots=None):
         return self._replay(lambda: None if slots is None else self.load(slots))
+
+
+def _starts(counts):
+    """The exclusive prefix sums of a host list."""
+    out, at = [], 0
+    for k in counts:
+        out.append(at)
+        at += k
+    return out
 
 
 class _SweepSink:
@@ -959,6 +1088,9 @@ class ScreeningSweep:
         self.masking = None        # the LibraryScreen of ligand_atom_masking (its edge room is sized for whole ligands)
         self.hotspot = None        # the LibraryScreen of receptor_hotspots (it reduces one layer's edge attention)
         self.cam_screen = None     # the LibraryScreen of receptor_hotspots(attribution='cam') (per-node heads)
+        self.struck = None         # the LibraryScreen(struck=True) of contact_masking and receptor_atom_masking
+        self.contact_masking_raw = {}          # contact_masking: {name: raw rows [K + 1, C], whole complex first}
+        self.receptor_atom_masking_raw = {}    # receptor_atom_masking: {name: raw rows [M + 1, C]}
         self.batches_run = 0
 
     def _bucket(self, n_lig, lig_feats, example_poses):
@@ -1058,7 +1190,7 @@ class ScreeningSweep:
             self._pick_hits(names, sink, hits_file)
         return out
 
-    def _library_screen(self, max_atoms, which='library', contact_attention=None, cam=None):
+    def _library_screen(self, max_atoms, which='library', contact_attention=None, cam=None, struck=None):
         """The sweep's LibraryScreen `which`, built anew when there is none, when the weights changed under it, when it
         is too narrow for `max_atoms`, when it reduces another layer's attention than `contact_attention` or maps
         another value than `cam`."""
@@ -1068,7 +1200,7 @@ class ScreeningSweep:
                 or screen.contact_attention != layer
                 or (type(screen.cam_request), screen.cam_request) != (type(cam), cam)):      # (True is not column 1)
             screen = LibraryScreen(self.model, self.rec_pos, self.rec_feats, self.b, max_atoms, self.edge_radius,
-                                   self.intra_radius, tasks=self.tasks, contact_attention=layer, cam=cam)
+                                   self.intra_radius, tasks=self.tasks, contact_attention=layer, cam=cam, struck=struck)
             setattr(self, which, screen)
         return screen
 
@@ -1242,6 +1374,152 @@ class ScreeningSweep:
                 if sum(ns):
                     writer.submit(torch.cat([out[name] for name in names], 0), None, [self.receptor_name] * sum(ns),
                                   [f'{name}_atom{a}' for name, n in zip(names, ns) for a in range(n)])
+        return out
+
+    def _pair_copies(self, items, ns, pairs, counts, ligand_atom, sigmoid):
+        """Every hit's copies - the whole complex, then one per row of its pair table (pairs [K,2] int32 on the device:
+        ligand atom inside the hit or -1, receptor atom; counts: the host's rows per hit) - streamed through the one
+        struck LibraryScreen `self.struck` in dense batches (load_leave_out_pairs: one packer launch per batch, then
+        the one captured step). Returns (raw [K + hits, C], the same with the sweep's sigmoid)."""
+        dev = self.rec_pos.device
+        screen = self._library_screen(max(max(ns), 1), 'struck', struck=True)
+        if screen._fast is None:
+            # a new screen sizes its edge buffers from its first batch: the largest whole ligands (a copy has no more
+            # contacts per atom than its whole complex; the struck rows' room is the screen's own addition)
+            big = sorted(range(len(items)), key=lambda i: -ns[i])[:self.b]
+            screen([(items[i][1], items[i][2]) for i in big])
+            self.batches_run += 1
+        all_pos = torch.cat([pose.to(dev).float() for _, _, pose in items], 0).contiguous()
+        all_feats = torch.cat([lig_feats.to(dev).float() for _, lig_feats, _ in items], 0).contiguous()
+        lig_ptr = torch.tensor([0] + ns).cumsum(0).to(device=dev, dtype=torch.int32)
+        pair_ptr = torch.tensor([0] + list(counts)).cumsum(0).to(device=dev, dtype=torch.int32)
+        plan = leave_out_pair_plan(counts, ns, self.b, ligand_atom=ligand_atom)
+        total = sum(counts) + len(ns)
+        firsts = (torch.arange(len(plan), dtype=torch.int32) * self.b).to(dev)     # batch k starts at copy k * b
+        kept = []
+        with self._sweeping(None, sigmoid, None) as sink:
+            for k, (batch_sizes, n_struck) in enumerate(plan):
+                screen.load_leave_out_pairs(all_pos, all_feats, lig_ptr, pairs, pair_ptr, batch_sizes, n_struck,
+                                            firsts[k:k + 1])
+                kept.append(self._library_step(screen))
+                self.batches_run += 1
+            screen.check()
+            screen.check_leave_out()
+            raw = torch.cat(kept, 0)[:total]
+            return raw, sink.scored(raw)
+
+    @staticmethod
+    def _split_pair_scores(names, counts, raw, scored, column):
+        """({name: raw rows [K + 1, C]}, {name: s(whole) - s(copy k) [K]}) from the copies' rows in copy order."""
+        raws, out, at = {}, {}, 0
+        for name, k in zip(names, counts):
+            raws[name] = raw[at:at + k + 1]
+            out[name] = scored[at, column] - scored[at + 1:at + k + 1, column]
+            at += k + 1
+        return raws, out
+
+    def _hit_contacts(self, items):
+        """(pairs [K,2] int32 on the device, the host's pair counts per hit): PF.contact_pairs of the hits against the
+        receptor at the sweep's edge radius; the whole pair_ptr comes back in the method's one copy to the host."""
+        dev = self.rec_pos.device
+        ns = [int(pose.shape[0]) for _, _, pose in items]
+        all_pos = torch.cat([pose.to(dev).float() for _, _, pose in items], 0).contiguous()
+        lig_ptr = torch.tensor([0] + ns).cumsum(0).to(device=dev, dtype=torch.int32)
+        pairs, _, host_ptr = PF.contact_pairs(all_pos, lig_ptr, self.rec_pos.float().contiguous(), self.edge_radius,
+                                              host_ptr=True)
+        return pairs, [int(k) for k in (host_ptr[1:] - host_ptr[:-1]).tolist()]
+
+    @torch.no_grad()
+    def contact_masking(self, items, scores_file=None, sigmoid=None, column=None):
+        """Bond masking (the reference's attribution_fns.bond_masking, its default way to rank interactions) of the
+        ligand-receptor contacts of many complexes with this receptor: items as for `ligand_atom_masking`. A contact is
+        a pair (ligand atom a, receptor atom r) with a class-1 edge at the sweep's edge radius (PF.contact_pairs, on the
+        device); the complex without both atoms is a struck pose-batch slot - the (n - 1)-atom ligand against the
+        receptor without r - whose graph is what the reference's masking leaves. Every item's K + 1 copies (the whole
+        complex, then one per contact, by a then r) stream through ONE LibraryScreen(struck=True), `self.struck`, in
+        dense batches: ceil((sum K + len(items)) / batch_size) steps (and the sizing batch of a new screen).
+        Returns {name: (pairs [K,2] int32, scores [K])} on the device, scores[k] = s(y_whole[column]) -
+        s(y_without_pair_k[column]); column None: the reference's rule, column 1 of more than one output, else column 0
+        (tasks='both': name it). One value per unordered pair (the reference lists a contact once per direction, with
+        equal scores). `self.contact_masking_raw[name]`: the raw rows [K + 1, C]. scores_file: one line per contact,
+        item order then pair order, '{score:.6f} | {receptor} {name}_atom{a} atom{r}'."""
+        from .predictions import PredictionsWriter
+        items, names, ns = self._checked_hits(items, 'contact_masking')
+        self.contact_masking_raw = {}
+        if column is None and self.tasks == 'both':
+            raise ValueError("contact_masking: with tasks='both' the column must be named (0: pose, 1..: affinity)")
+        if not items:
+            return {}
+        pairs, counts = self._hit_contacts(items)
+        raw, scored = self._pair_copies(items, ns, pairs, counts, True, sigmoid)
+        if column is None:
+            column = 1 if raw.shape[1] > 1 else 0
+        if not 0 <= int(column) < raw.shape[1]:
+            raise ValueError(f'contact_masking: column {column} of {raw.shape[1]} outputs')
+        self.contact_masking_raw, scores = self._split_pair_scores(names, counts, raw, scored, int(column))
+        out, at = {}, 0
+        for name, k in zip(names, counts):
+            out[name] = (pairs[at:at + k], scores[name])
+            at += k
+        if scores_file:
+            with PredictionsWriter(scores_file, 'atom_masking') as writer:
+                if sum(counts):
+                    host = pairs.cpu().tolist()
+                    labels = [f'{name}_atom{a} atom{r}' for name, k, lo in zip(names, counts, _starts(counts))
+                              for a, r in host[lo:lo + k]]
+                    writer.submit(torch.cat([scores[name] for name in names], 0), None,
+                                  [self.receptor_name] * len(labels), labels)
+        return out
+
+    @torch.no_grad()
+    def receptor_atom_masking(self, items, atoms='contacts', scores_file=None, sigmoid=None, column=0):
+        """Atom masking (the reference's attribution_fns.atom_masking) of RECEPTOR atoms of many complexes with this
+        receptor, through the same struck screen as `contact_masking`: a copy keeps the whole ligand and lacks one
+        receptor atom. atoms: 'contacts' (per hit, the receptor atoms in at least one of its contacts, ascending),
+        'all' (every receptor atom) or a 1-D index tensor that applies to every hit. Returns {name: (atoms [M] int32,
+        scores [M])} on the device, scores[m] = s(y_whole[column]) - s(y_without_atom_m[column]);
+        `self.receptor_atom_masking_raw[name]`: the raw rows [M + 1, C]. scores_file: one line per atom, item order
+        then atom order, '{score:.6f} | {receptor} {name} atom{r}'."""
+        from .predictions import PredictionsWriter
+        items, names, ns = self._checked_hits(items, 'receptor_atom_masking')
+        self.receptor_atom_masking_raw = {}
+        if not items:
+            return {}
+        dev, n_rec = self.rec_pos.device, int(self.rec_pos.shape[0])
+        if isinstance(atoms, str) and atoms == 'contacts':
+            pairs, counts = self._hit_contacts(items)
+            hit = torch.repeat_interleave(torch.arange(len(items), device=dev), torch.tensor(counts, device=dev))
+            keys = torch.unique(hit * n_rec + pairs[:, 1].long())         # ascending: by hit, then by receptor atom
+            which = (keys % n_rec).to(torch.int32)
+            counts = torch.bincount(keys // n_rec, minlength=len(items)).tolist()
+        elif isinstance(atoms, str) and atoms == 'all':
+            which = torch.arange(n_rec, dtype=torch.int32, device=dev).repeat(len(items))
+            counts = [n_rec] * len(items)
+        elif torch.is_tensor(atoms) and atoms.dim() == 1 and not atoms.is_floating_point():
+            host = [int(r) for r in atoms.tolist()]
+            if any(not 0 <= r < n_rec for r in host):
+                raise ValueError(f'receptor_atom_masking: atoms must be receptor atoms 0..{n_rec - 1}')
+            which = torch.tensor(host, dtype=torch.int32, device=dev).repeat(len(items))
+            counts = [len(host)] * len(items)
+        else:
+            raise ValueError(f"receptor_atom_masking: atoms={atoms!r}: 'contacts', 'all' or a 1-D index tensor")
+        table = torch.stack([torch.full_like(which, -1), which], 1).contiguous()
+        raw, scored = self._pair_copies(items, ns, table, counts, False, sigmoid)
+        if not 0 <= int(column) < raw.shape[1]:
+            raise ValueError(f'receptor_atom_masking: column {column} of {raw.shape[1]} outputs')
+        self.receptor_atom_masking_raw, scores = self._split_pair_scores(names, counts, raw, scored, int(column))
+        out, at = {}, 0
+        for name, k in zip(names, counts):
+            out[name] = (which[at:at + k], scores[name])
+            at += k
+        if scores_file:
+            with PredictionsWriter(scores_file, 'atom_masking') as writer:
+                if sum(counts):
+                    host = which.cpu().tolist()
+                    labels = [f'{name} atom{r}' for name, k, lo in zip(names, counts, _starts(counts))
+                              for r in host[lo:lo + k]]
+                    writer.submit(torch.cat([scores[name] for name in names], 0), None,
+                                  [self.receptor_name] * len(labels), labels)
         return out
 
     @torch.no_grad()
