@@ -906,7 +906,7 @@ int pvs_launch_edge_bwd_h64(hipStream_t s, const PvsGraph& g, const PvsEdgeW& w,
     *n_slabs = 0;
     if (e_hi <= e_lo) return 0;
     constexpr int nw = 4;
-    const PvsEdgeGrid grid = pvs_edge_grid(e_hi - e_lo, nw, kPvsBwdH64MaxBlocks, pvs_edges_per_wave(), 4096);
+    const PvsEdgeGrid grid = pvs_edge_grid(e_hi - e_lo, nw, kPvsBwdH64MaxBlocks, pvs_edges_per_wave(), pvs_chunk_edges(4096));
     PVS_TRY(pvs_report_slabs(grid.blocks, n_slabs));
     PvsProfScope prof(s, PVS_PROF_EDGE_BWD);
     const PvsSlabLayout L = pvs_slab_layout(kH);

@@ -705,7 +705,7 @@ int launch_wide(hipStream_t s, const PvsGraph& g, const PvsEdgeW& w, uint32_t fl
     if (lds < (size_t)L.total * 4) lds = (size_t)L.total * 4;
     // fill the chip first: >= 16 tiles per team (a team is the unit the planner calls a wave), one team resident per CU
     static_assert(2 * Cfg::kBytes > 160 * 1024, "two teams fit a CU: kPvsBwdWideMaxBlocks (and the slab capacity) can double");
-    const PvsEdgeGrid grid = pvs_edge_grid(e_hi - e_lo, 1, kPvsBwdWideMaxBlocks, 512, 4096);
+    const PvsEdgeGrid grid = pvs_edge_grid(e_hi - e_lo, 1, kPvsBwdWideMaxBlocks, 512, pvs_chunk_edges(4096));
     PVS_TRY(pvs_report_slabs(grid.blocks, n_slabs));
     PvsProfScope prof(s, PVS_PROF_EDGE_BWD);
     const PvsEdgeResidual res = pvs_edge_residual_kind(flags, io.m_prev != nullptr);

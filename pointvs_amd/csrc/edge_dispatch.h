@@ -40,21 +40,24 @@ inline PvsEdgeFamily pvs_edge_family(int H, uint32_t flags, int n_attr, PvsEdgeD
 // weight staging): right for BASELINE-size batches, whose grids are capped by the CU count anyway, and wrong for small ones
 // - at the reference's default shape (32 graphs of 500 atoms, r = 4 A: 176k edges) the backward ran on 43 of 256 CUs.
 // Two tiles per wave: edge forward 0.62 -> 0.20 ms, edge backward 0.81 -> 0.28 ms per 6-layer step there (32: 0.19 / 0.28;
-// profiles/r05_ab_small_batch_grid.txt). PVS_EDGES_PER_WAVE overrides it (A/B; read once per process). The team kernels
-// (H = 128 backward, exact H = 64 backward) keep 512 per team whatever it says.
+// profiles/r05_ab_small_batch_grid.txt). PVS_EDGES_PER_WAVE overrides it (A/B, and the tests' way to other work partitions:
+// read at every call, like the family switches; 0 or below counts as unset). The team kernels (H = 128 backward, exact
+// H = 64 backward) keep 512 per team whatever it says.
 inline int pvs_edges_per_wave() {
-    static const int v = [] { const char* e = getenv("PVS_EDGES_PER_WAVE"); const int x = e ? atoi(e) : 0; return x > 0 ? x : 64; }();
-    return v;
+    const char* e = getenv("PVS_EDGES_PER_WAVE");
+    const int x = e ? atoi(e) : 0;
+    return x > 0 ? x : 64;
 }
 
-// Edges per chunk above which a wave's share is cut into several chunks (PVS_CHUNK_EDGES overrides it: A/B only; read once
-// per process; it reaches the forward and the H = 32 split backward, the other launchers pass 4096).
+// Edges per chunk above which a wave's share is cut into several chunks (PVS_CHUNK_EDGES overrides it: A/B and tests; read
+// at every call; 0 or below counts as unset; it reaches every MFMA edge launcher, each with its own default).
 // Chunk ends are row-aligned, so a wave's share is uneven by up to a row per chunk end (157 edges at cfg2) and the launch
 // waits for the largest share: FEWER, larger chunks per wave balance better (round 6, H = 32 backward at cfg2: two chunks
 // of 2.5 k edges per wave -> one of 5 k: -2.5 % per launch; perfectly equal shares - a timing-only build - would give
 // -3.3 %: profiles/r06_ab_chunk_balance.txt).
 inline long long pvs_chunk_edges(long long dflt = 4096) {
-    static const long long v = [] { const char* e = getenv("PVS_CHUNK_EDGES"); return e ? atoll(e) : 0ll; }();
+    const char* e = getenv("PVS_CHUNK_EDGES");
+    const long long v = e ? atoll(e) : 0ll;
     return v > 0 ? v : dflt;
 }
 

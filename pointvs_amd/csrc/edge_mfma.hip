@@ -1012,9 +1012,10 @@ int pvs_launch_edge_bwd_exact(hipStream_t s, int H, const PvsGraph& g, const Pvs
         }
     }
     // (the team kernels: one team per block, >= 16 tiles per team)
-    const PvsEdgeGrid grid = HB == 1   ? pvs_edge_grid(E, kWaves, kPvsBwdExactMaxBlocks, pvs_edges_per_wave(), 4096)
-                             : HB == 2 ? pvs_edge_grid(E, 1, kPvsBwdExactMaxBlocks, 512, 4096)
-                                       : pvs_edge_grid(E, 1, kPvsBwdExactWideMaxBlocks, 512, 4096);
+    const long long ce = pvs_chunk_edges(4096);
+    const PvsEdgeGrid grid = HB == 1   ? pvs_edge_grid(E, kWaves, kPvsBwdExactMaxBlocks, pvs_edges_per_wave(), ce)
+                             : HB == 2 ? pvs_edge_grid(E, 1, kPvsBwdExactMaxBlocks, 512, ce)
+                                       : pvs_edge_grid(E, 1, kPvsBwdExactWideMaxBlocks, 512, ce);
     PVS_TRY(pvs_report_slabs(grid.blocks, n_slabs));
     PvsProfScope prof(s, PVS_PROF_EDGE_BWD);
     // weights (Wc1 from global memory at H = 128), tables, per wave or team: three tiles, tx, gl, rowbuf (+ the team's

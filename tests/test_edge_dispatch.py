@@ -3,7 +3,9 @@
 The header is the one place that decides which kernel family runs a layer, on what grid and as which edge-residual
 kind. These tests compare it with the rules the launchers carried inline before they shared it, restated here in Python
 from that source: the same (blocks, n_chunks) for every launcher's parameter set, the same family for every
-(H, n_attr, direction, environment), the same residual kind for every flag combination."""
+(H, n_attr, direction, environment), the same residual kind for every flag combination. The last part checks the two
+grid overrides (PVS_CHUNK_EDGES, PVS_EDGES_PER_WAVE: read at every call, reaching every launcher) and the grids they give
+under the work partitions of tests/test_gpu_edge_partitions.py."""
 import itertools
 import os
 import shutil
@@ -47,6 +49,38 @@ int main(int argc, char** argv) {
                kPvsBwdF16MaxBlocks, kPvsBwdH64MaxBlocks, kPvsBwdWideMaxBlocks, kPvsBwdExactMaxBlocks,
                kPvsBwdExactWideMaxBlocks, kPvsBwdGenericMaxBlocks);
         printf("capacity %d\n", kPvsEdgeSlabCapacity);
+    } else if (argc > 1 && !strcmp(argv[1], "launchers")) {
+        // the calls as the launchers make them: every chunk size through pvs_chunk_edges(its default), the floor
+        // through pvs_edges_per_wave() except in the team kernels
+        const Site sites[] = {
+            {"fwd_256", 4, kPvsFwdMaxBlocks, pvs_edges_per_wave(), pvs_chunk_edges()},
+            {"fwd_512", 8, kPvsFwdLargeMaxBlocks, pvs_edges_per_wave(), pvs_chunk_edges()},
+            {"fwd_768", 12, kPvsFwdLargeMaxBlocks, pvs_edges_per_wave(), pvs_chunk_edges()},
+            {"fwd_wide", 4, kPvsFwdLargeMaxBlocks, pvs_edges_per_wave(), pvs_chunk_edges()},
+            {"bwd_f16", 8, kPvsBwdF16MaxBlocks, pvs_edges_per_wave(), pvs_chunk_edges(8192)},
+            {"bwd_h64", 4, kPvsBwdH64MaxBlocks, pvs_edges_per_wave(), pvs_chunk_edges(4096)},
+            {"bwd_wide", 1, kPvsBwdWideMaxBlocks, 512, pvs_chunk_edges(4096)},
+            {"exact_wide", 1, kPvsBwdExactWideMaxBlocks, 512, pvs_chunk_edges(4096)},
+            {"exact_h32", 4, kPvsBwdExactMaxBlocks, pvs_edges_per_wave(), pvs_chunk_edges(4096)},
+            {"exact_h64", 1, kPvsBwdExactMaxBlocks, 512, pvs_chunk_edges(4096)},
+        };
+        for (const Site& s : sites)
+            for (int i = 2; i < argc; ++i) {
+                const long long E = atoll(argv[i]);
+                const PvsEdgeGrid g = pvs_edge_grid(E, s.nw, s.cap, s.min_edges, s.chunk);
+                printf("%s %lld %d %d\n", s.name, E, g.blocks, g.n_chunks);
+            }
+    } else if (argc > 1 && !strcmp(argv[1], "reread")) {
+        // both overrides inside ONE process: set, set to values that count as unset, removed
+        const char* steps[] = {nullptr, "16", "0", "-3", "48", nullptr};
+        const char* vars[] = {"PVS_CHUNK_EDGES", "PVS_EDGES_PER_WAVE"};
+        for (int i = 0; i < 6; ++i) {
+            for (const char* name : vars) {
+                if (steps[i]) setenv(name, steps[i], 1); else unsetenv(name);
+            }
+            printf("%s %lld %lld %d\n", steps[i] ? steps[i] : "unset", pvs_chunk_edges(), pvs_chunk_edges(8192),
+                   pvs_edges_per_wave());
+        }
     } else if (argc > 1 && !strcmp(argv[1], "family")) {
         static const char* names[] = {"generic", "split", "exact", "wide"};
         const int Hs[] = {16, 32, 48, 64, 128};
@@ -175,3 +209,67 @@ def test_residual_kind_orders_rezero_before_gated(program):
     for eres, rezero, gated, has_m_prev, kind in rows:
         want = 0 if not (eres and has_m_prev) else 2 if rezero else 3 if gated else 1
         assert kind == want, (eres, rezero, gated, has_m_prev)
+
+
+# ---- the work partitions of tests/test_gpu_edge_partitions.py ------------------------------------------------------------
+def _site_lines(text):
+    return [line for line in text.splitlines() if line.split()[0] in SITES]
+
+
+def test_launchers_plan_as_before_when_nothing_is_set(program):
+    """The calls as the launchers make them now (every chunk size through pvs_chunk_edges) give the grids of the
+    SITES table when no override is set, and when one is set to a value that counts as unset."""
+    want = _site_lines(program('grid', *edge_counts()))
+    assert len(want) == len(SITES) * len(edge_counts())
+    assert _site_lines(program('launchers', *edge_counts())) == want
+    for value in ('0', '-7', ''):
+        env = {'PVS_CHUNK_EDGES': value, 'PVS_EDGES_PER_WAVE': value}
+        assert _site_lines(program('launchers', *edge_counts(), env=env)) == want, value
+
+
+def test_overrides_are_read_at_every_call(program):
+    rows = [line.split() for line in program('reread').splitlines()]
+    assert rows == [['unset', '4096', '8192', '64'], ['16', '16', '16', '16'], ['0', '4096', '8192', '64'],
+                    ['-3', '4096', '8192', '64'], ['48', '48', '48', '48'], ['unset', '4096', '8192', '64']]
+
+
+def test_no_launcher_passes_a_literal_chunk_size():
+    """PVS_CHUNK_EDGES reaches every MFMA edge launcher: no call of pvs_edge_grid ends in a literal."""
+    import re
+    calls = []
+    for path in sorted(CSRC.glob('*.hip')):
+        calls += re.findall(r'pvs_edge_grid\((?:[^()]|\([^()]*\))*\)', path.read_text())
+    assert len(calls) == 8, calls        # forward 2 (its three block sizes share one), split 2, wide 1, exact 3
+    for call in calls:
+        assert not re.search(r',\s*\d+\s*\)$', call), call
+
+
+@pytest.mark.parametrize('partition', ['many_chunks', 'one_block', 'fine'])
+def test_partitions_of_the_gpu_tests_reach_every_site(program, partition):
+    """(blocks, n_chunks) of every launch site under each partition of tests/_edge_partition_cases.py, at the edge
+    count of its graphs: the overridden chunk size, the overridden floor where the site honours it and 512 for the
+    team sites - and what keeps the GPU tests from being vacuous: two or more chunks per wave (team), a single
+    workgroup, a grid at its cap."""
+    from tests import _edge_partition_cases as epc
+    E = epc.N_EDGES
+    rows = [line.split() for line in _site_lines(program('launchers', E, env=epc.PARTITIONS[partition]))]
+    assert [r[0] for r in rows] == list(SITES) == list(epc.SITES)
+    for name, e, blocks, n_chunks in rows:
+        blocks, n_chunks = int(blocks), int(n_chunks)
+        nw, cap, floor, chunk = epc.site_parameters(name, partition)
+        team = SITES[name][2] == 512
+        assert team == (not epc.SITES[name][2]) and (nw, cap) == SITES[name][:2] and epc.SITES[name][3] == SITES[name][3]
+        assert floor == (512 if team else int(epc.PARTITIONS[partition].get('PVS_EDGES_PER_WAVE', SITES[name][2])))
+        assert int(e) == E and (blocks, n_chunks) == parent_grid(E, nw, cap, floor, chunk), name
+        assert n_chunks % (blocks * nw) == 0 and blocks <= cap
+        if partition in ('many_chunks', 'one_block'):
+            assert n_chunks // (blocks * nw) >= 2, name
+        if partition == 'one_block' and not team:
+            assert blocks == 1, name
+        # (the team sites keep 512 edges per team, so a floor of one edge never drives them to their cap)
+        if partition == 'fine' and cap <= E // (nw * floor):
+            assert blocks == cap, name
+    if partition == 'fine':
+        at_cap = {r[0] for r in rows if int(r[2]) == SITES[r[0]][1]}
+        assert at_cap == {'fwd_512', 'fwd_768', 'fwd_wide', 'bwd_f16', 'bwd_h64', 'exact_h32'}
+        assert dict((r[0], int(r[2])) for r in rows)['exact_h32'] == 512      # every slab of the workspace

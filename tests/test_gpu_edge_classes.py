@@ -119,11 +119,12 @@ def _new_layer(A, hid, flags, seed):
 
 class Problem:
     """Inputs and oracle references of a chain of `depth` layers on the A-class graph: built once per (A, hid, flags,
-    depth) and shared, unchanged, by every test that needs it."""
+    depth) and shared, unchanged, by every test that needs it. `graph`: another graph with A classes in its place
+    (tests/test_gpu_edge_partitions.py)."""
 
-    def __init__(self, A, hid, flags_name, depth=1):
+    def __init__(self, A, hid, flags_name, depth=1, graph=None):
         self.A, self.hid, self.flags, self.depth = A, hid, FLAGS[flags_name], depth
-        self.g = ecc.class_graph(A, seed=100 + A)
+        self.g = ecc.class_graph(A, seed=100 + A) if graph is None else graph
         n, e = self.g.n_nodes, int(self.g.edge_index.shape[1])
         self.sds = [{k: v.detach().clone() for k, v in _new_layer(A, hid, self.flags, 11 + 7 * d).state_dict().items()}
                     for d in range(depth)]
