@@ -806,7 +806,10 @@ int pvs_segment_reduce_bwd_f64(const double* g_out, const int64_t* ids, const in
  * Behind those six, one group per dispatch route of the dense launchers, for tests that pin a shape to its route:
  * "linear_mfma", "linear_chunk64", "linear_chunk256", "linear_generic", "tsgemm_mfma", "tsgemm_wide",
  * "tsgemm_colchunk", "tsgemm_narrow", "tsgemm_tn8", "tsgemm_tn32", "colreduce4", "colreduce", "colreduce_chunk"
- * (groups 6 .. 18). These are recorded only when their own mask bit is set; on = 1 leaves them out.
+ * (groups 6 .. 18), and one group per node-level launcher of a layer, for tests that pin a layer to its node route (the
+ * folded node MLP or the separate tail and output stage; the fused weight-gradient pass): "node_mlp_fwd", "node_mlp_bwd",
+ * "node_out_fwd", "node_out_bwd", "node_tail" (the three tail launchers), "node_wgrads" (groups 19 .. 24).
+ * Groups 6 .. 24 are recorded only when their own mask bit is set; on = 1 leaves them out.
  */
 int pvs_profile_enable(int on);
 int pvs_profile_reset(void);

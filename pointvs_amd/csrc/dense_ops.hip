@@ -1161,6 +1161,7 @@ int pvs_launch_node_mlp_fwd(hipStream_t s, int H, int N, const float* h, const f
                 "node_mlp_fwd: H = %d or the alignment is unsupported", H);
     PVS_REQUIRE(!natt_w || natt_b, "node_mlp_fwd: node attention bias missing");
     if (N <= 0) return 0;
+    PvsProfScope prof(s, PVS_PROF_NODE_MLP_FWD);
     const size_t lds = (size_t)(H * (2 * H + 1) + H * (H + 1) + 3 * H) * sizeof(float);
     if (H == 32) {
         k_node_mlp_fwd<1><<<node_mlp_blocks(N), kThreads, lds, s>>>(h, Magg, W1, b1, W2, b2, N, residual ? 1 : 0, natt_w,
@@ -1189,6 +1190,7 @@ int pvs_launch_node_mlp_bwd(hipStream_t s, int H, int N, const float* g_hout, co
     PVS_REQUIRE(!ext || (ext->zero_w % 8 == 0 && (ext->zero_ld & 3) == 0 && ((uintptr_t)ext->zero_rows & 15) == 0),
                 "node_mlp_bwd: bad side job");
     if (N <= 0) return 0;
+    PvsProfScope prof(s, PVS_PROF_NODE_MLP_BWD);
     const PvsLinearExt e = ext ? *ext : PvsLinearExt{};
     const size_t lds = (size_t)(3 * H * (H + 1) + H) * sizeof(float);
     if (H == 32) {
@@ -1328,6 +1330,7 @@ int pvs_launch_node_wgrads(hipStream_t s, int H, int N, const PvsNodeWgradIn& in
         gh.blocks = (N + rows_m - 1) / rows_m;
         if (gh.blocks > 1024) gh.blocks = 1024;
     }
+    PvsProfScope prof(s, PVS_PROF_NODE_WGRADS);
     if (hb == 1) {
         k_node_wgrads<1, true><<<dim3(rb + ex.blocks() + gh.blocks, 1), kThreads, 0, s>>>(slabs, in, N, rb, ex, gh);
     } else {

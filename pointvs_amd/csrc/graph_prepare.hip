@@ -113,7 +113,8 @@ extern "C" int pvs_graph_prepare(const int64_t* edge_index, const int64_t* edge_
     PVS_REQUIRE(N > 0 && E >= 0, "pvs_graph_prepare: bad sizes N=%d E=%d", N, E);
     PVS_REQUIRE(n_edge_attr >= 0 && n_edge_attr <= 255, "pvs_graph_prepare: bad n_edge_attr %d",
                 n_edge_attr);
-    PVS_REQUIRE(n_edge_attr == 0 || (edge_attr && etype), "pvs_graph_prepare: edge_attr/etype NULL");
+    // (a list without edges has no attribute rows: an empty tensor has no device pointer to hand over)
+    PVS_REQUIRE(n_edge_attr == 0 || E == 0 || (edge_attr && etype), "pvs_graph_prepare: edge_attr/etype NULL");
     PVS_REQUIRE((colptr == nullptr) == (cedge == nullptr), "pvs_graph_prepare: colptr and cedge go together");
     PvsArena arena(workspace, workspace_bytes);
     PrepWs w;

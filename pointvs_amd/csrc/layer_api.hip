@@ -681,9 +681,12 @@ extern "C" int pvs_egnn_layer_bwd(const PvsLayerDesc* d, const PvsGraph* g, cons
         PVS_TRY(pvs_launch_colreduce(s, PVS_COL_SUM_A, gr.edge_b1, w.gPQ, 2 * H, nullptr, 0, nullptr,
                                      N, H, 1.f, w.dslabs, false));
     const int node_blocks = node_slabs.slabs ? (node_slabs.width + 31) / 32 : 0;
+    // (a graph without edges: the caller's [0, H] m_prev has no device pointer, yet the edge gate is a parameter of the
+    // layer and its gradient - the sum over no edges - is 0, not whatever the caller's buffer held)
+    const bool gate_grad = eres || ((F & PVS_EDGE_RESIDUAL) && m.E == 0);
     k_finalize_edge_grads<<<node_blocks + (H * H / 256 > 4 ? H * H / 256 : 4), 256, 0, s>>>(
         w.gsum, L, H, m.A, m.ld1, m.off_rho, gr, coord_bwd ? 1 : 0, eatt ? (soft ? 2 : 1) : 0,
-        (eres && (F & (PVS_REZERO | PVS_GATED_RESIDUAL))) ? 1 : 0, node_gsum, node_out, node_slabs, node_blocks);
+        (gate_grad && (F & (PVS_REZERO | PVS_GATED_RESIDUAL))) ? 1 : 0, node_gsum, node_out, node_slabs, node_blocks);
     PVS_CHECK_LAUNCH();
     // GraphNorm: node_mlp.0.bias from the closed form of k_gn_bwd_coefs instead of the column sum of g_y1
     if (gn && gr.node_b1) PVS_TRY(pvs_copy_small(s, w.coefs + 3 * H, gr.node_b1, H));

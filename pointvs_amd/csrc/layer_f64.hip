@@ -902,5 +902,8 @@ extern "C" int pvs_egnn_layer_bwd_f64(const PvsLayerDesc* desc, const PvsGraph* 
     }
     if (a.eres && (a.rezero || a.gated) && grads->edge_gate)
         if ((rc = pvs64_colsum(s, grads->edge_gate, w.rp + 6 * H + 1, KP, N, 1, w.slabs))) return rc;
+    // (a graph without edges: the caller's [0, H] m_prev has no device pointer; the gate's gradient is the sum over no edges)
+    if (E == 0 && !a.eres && (f & PVS_EDGE_RESIDUAL) && (a.rezero || a.gated) && grads->edge_gate)
+        PVS_CHECK_HIP(hipMemsetAsync(grads->edge_gate, 0, sizeof(double), s));
     return 0;
 }

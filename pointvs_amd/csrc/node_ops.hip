@@ -1,4 +1,5 @@
 #include "node_ops.h"
+#include "profile.h"
 
 namespace {
 
@@ -350,6 +351,7 @@ int pvs_graphnorm_stats(hipStream_t s, const float* y1, const float* gn_ms, int 
 
 int pvs_node_tail_fwd(hipStream_t s, const float* y1, const float* stats, const PvsNodeW& w, int N,
                       int H, float* u) {
+    PvsProfScope prof(s, PVS_PROF_NODE_TAIL);
     k_node_tail_fwd<<<ew_grid((long long)N * H), 256, 0, s>>>(y1, stats, w, N, H, u);
     PVS_CHECK_LAUNCH();
     return 0;
@@ -365,6 +367,7 @@ int pvs_node_tail_fwd(hipStream_t s, const float* y1, const float* stats, const 
 
 int pvs_node_out_fwd(hipStream_t s, int H, const float* o, const float* h, const PvsNodeW& w,
                      uint32_t flags, int att_act, int N, float* h_out, float* natt_out) {
+    PvsProfScope prof(s, PVS_PROF_NODE_OUT_FWD);
     const int blocks = ew_grid((long long)N * H);
     if (H == 128) {
         k_node_out_fwd_wide<2><<<blocks, 256, 0, s>>>(o, h, w, flags, att_act, N, h_out, natt_out);
@@ -381,6 +384,7 @@ int pvs_node_out_fwd(hipStream_t s, int H, const float* o, const float* h, const
 int pvs_node_out_bwd(hipStream_t s, int H, const float* g_hout, const float* o, const float* h,
                      const PvsNodeW& w, uint32_t flags, int att_act, int N, float* g_o, float* g_h,
                      float* gl, float* t1, float* tg) {
+    PvsProfScope prof(s, PVS_PROF_NODE_OUT_BWD);
     const int blocks = ew_grid((long long)N * H);
     if (H == 128) {
         k_node_out_bwd_wide<2><<<blocks, 256, 0, s>>>(g_hout, o, h, w, flags, att_act, N, g_o, g_h, gl, t1, tg);
@@ -397,6 +401,7 @@ int pvs_node_out_bwd(hipStream_t s, int H, const float* g_hout, const float* o, 
 
 int pvs_node_tail_bwd1(hipStream_t s, const float* g_u, const float* y1, const float* stats,
                        const PvsNodeW& w, int N, int H, float* g_yn) {
+    PvsProfScope prof(s, PVS_PROF_NODE_TAIL);
     k_node_tail_bwd1<<<ew_grid((long long)N * H), 256, 0, s>>>(g_u, y1, stats, w, N, H, g_yn);
     PVS_CHECK_LAUNCH();
     return 0;
@@ -412,6 +417,7 @@ int pvs_graphnorm_bwd_coefs(hipStream_t s, const float* S1, const float* S2, con
 
 int pvs_node_tail_bwd2(hipStream_t s, const float* g_yn, const float* y1, const float* stats,
                        const PvsNodeW& w, const float* coefs, int N, int H, float* g_y1) {
+    PvsProfScope prof(s, PVS_PROF_NODE_TAIL);
     k_node_tail_bwd2<<<ew_grid((long long)N * H), 256, 0, s>>>(g_yn, y1, stats, w, coefs, N, H, g_y1);
     PVS_CHECK_LAUNCH();
     return 0;

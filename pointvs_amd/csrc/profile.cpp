@@ -13,7 +13,9 @@ const char* kNames[PVS_PROF_COUNT] = {"edge_fwd", "edge_bwd", "col_gather", "gra
                                       "mask_graph",
                                       "linear_mfma", "linear_chunk64", "linear_chunk256", "linear_generic",
                                       "tsgemm_mfma", "tsgemm_wide", "tsgemm_colchunk", "tsgemm_narrow", "tsgemm_tn8",
-                                      "tsgemm_tn32", "colreduce4", "colreduce", "colreduce_chunk"};
+                                      "tsgemm_tn32", "colreduce4", "colreduce", "colreduce_chunk",
+                                      "node_mlp_fwd", "node_mlp_bwd", "node_out_fwd", "node_out_bwd", "node_tail",
+                                      "node_wgrads"};
 thread_local int t_fwd_tag = PVS_PROF_EDGE_FWD;
 }  // namespace
 

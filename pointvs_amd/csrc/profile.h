@@ -12,7 +12,13 @@ enum { PVS_PROF_EDGE_FWD = 0, PVS_PROF_EDGE_BWD = 1, PVS_PROF_COL_GATHER = 2, PV
        PVS_PROF_TS_MFMA = 10, PVS_PROF_TS_WIDE = 11, PVS_PROF_TS_COLCHUNK = 12, PVS_PROF_TS_NARROW = 13,
        PVS_PROF_TS_TN8 = 14, PVS_PROF_TS_TN32 = 15,
        PVS_PROF_COLREDUCE4 = 16, PVS_PROF_COLREDUCE = 17, PVS_PROF_COLREDUCE_CHUNK = 18,
-       PVS_PROF_COUNT = 19 };
+       // The node-level launchers of a layer (dense_ops.hip: the folded node MLP and the fused weight-gradient pass;
+       // node_ops.hip: the separate tail and output stage), one id per launcher, the three tail launchers under one: which
+       // of the two node routes a layer call took. Recorded like the dense routes, under their own mask bit only.
+       PVS_PROF_NODE_MLP_FWD = 19, PVS_PROF_NODE_MLP_BWD = 20, PVS_PROF_NODE_OUT_FWD = 21, PVS_PROF_NODE_OUT_BWD = 22,
+       PVS_PROF_NODE_TAIL = 23, PVS_PROF_NODE_WGRADS = 24,
+       PVS_PROF_COUNT = 25 };
+static_assert(PVS_PROF_COUNT + 1 <= 32, "the profile mask is an unsigned with bit (id + 1) per category");
 
 // tag the edge forward launches of the calling thread carry (layer_api: full layer vs partial layer)
 void pvs_prof_set_fwd_tag(int id);

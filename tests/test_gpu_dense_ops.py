@@ -153,6 +153,8 @@ ROUTE_NAMES = ('linear_mfma', 'linear_chunk64', 'linear_chunk256', 'linear_gener
                'tsgemm_colchunk', 'tsgemm_narrow', 'tsgemm_tn8', 'tsgemm_tn32', 'colreduce4', 'colreduce',
                'colreduce_chunk')
 ROUTE_FIRST_ID = 6          # PVS_PROF_DENSE_FIRST: the route groups follow the six kernel groups, in ROUTE_NAMES order
+# the node-level launchers of a layer (csrc/profile.h), after the dense routes; tests/test_gpu_node_side.py reads them
+NODE_ROUTE_NAMES = ('node_mlp_fwd', 'node_mlp_bwd', 'node_out_fwd', 'node_out_bwd', 'node_tail', 'node_wgrads')
 
 
 @pytest.mark.parametrize('shape', list(ROUTES), ids=lambda s: 'x'.join(map(str, s)))
@@ -184,20 +186,37 @@ def test_dispatch_routes(shape):
 
 
 def test_route_groups_stay_out_of_the_every_group_switch():
-    """pvs_profile_enable(1) (what the benchmark's profile legs pass) records the kernel groups only."""
+    """pvs_profile_enable(1) (what the benchmark's profile legs pass) records the kernel groups only: neither the dense
+    routes of a linear nor the dense and node-level routes of a layer's forward and backward - hidden 32 without a gate
+    (the folded chain, the fused weight gradients) and hidden 16 with GraphNorm, node attention and a gated residual
+    (the separate stages, tsgemm, the column reductions) -, while the layer's edge kernels are recorded."""
     from pointvs_amd import _lib
+    from pointvs_amd.egnn_satorras import EGNNLayer
     lib = _lib.lib()
     x, w, b, g_y = R.linear_case((33, 32, 32), True, integer=True)
+    gen = torch.Generator().manual_seed(3)
+    n = 70
+    ei = torch.randint(0, n, (2, 400), generator=gen)
+    ei = ei[:, ei[0] != ei[1]].cuda()
     lib.pvs_profile_reset()
     lib.pvs_profile_enable(1)
     try:
         run_linear(x, w, b, g_y)
+        for hid, flags in ((32, dict()), (16, dict(graphnorm=True, node_attention=True, gated_residual=True))):
+            layer = EGNNLayer(hid, hid, hid, **flags).cuda()
+            h = torch.randn(n, hid, generator=gen).cuda().requires_grad_(True)
+            pos = torch.randn(n, 3, generator=gen).cuda()
+            h_out, x_out, _, m = layer(h, ei, pos)
+            (h_out.sum() + x_out.sum() + m.sum()).backward()
         torch.cuda.synchronize()
     finally:
         lib.pvs_profile_enable(0)
-    for name in ROUTE_NAMES:
+    for name in ROUTE_NAMES + NODE_ROUTE_NAMES:
         ms, cnt = C.c_double(0.0), C.c_int64(-1)
         assert lib.pvs_profile_read(name.encode(), C.byref(ms), C.byref(cnt)) == 0 and cnt.value == 0, name
+    for name in ('edge_fwd', 'edge_bwd'):
+        ms, cnt = C.c_double(0.0), C.c_int64(-1)
+        assert lib.pvs_profile_read(name.encode(), C.byref(ms), C.byref(cnt)) == 0 and cnt.value == 2, name
     lib.pvs_profile_reset()
 
 

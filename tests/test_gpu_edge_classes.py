@@ -28,6 +28,21 @@ FLAGS = {
                  normalize=True, tanh=True, graphnorm=True),
     'soft': dict(edge_attention=True, softmax_attention=True, residual=True),
     'perm': dict(permutation_invariance=True),            # ld1 = H + 1 + A
+    # the node-side kinds of tests/test_gpu_node_side.py (`node_gate`: the value _new_layer gives node_gate_parameter)
+    'nores': dict(residual=False),
+    'gn': dict(graphnorm=True),
+    'natt-sigmoid': dict(node_attention=True, attention_activation_fn='sigmoid'),
+    'natt-tanh': dict(node_attention=True, attention_activation_fn='tanh'),
+    'natt-relu': dict(node_attention=True, attention_activation_fn='relu'),
+    'natt-silu': dict(node_attention=True, attention_activation_fn='silu'),
+    'rezero0': dict(residual=True, rezero=True, node_attention=True, node_gate=0.0),     # what every rezero model starts from
+    'rezero': dict(residual=True, rezero=True, node_attention=True, node_gate=0.35),
+    'gated+': dict(residual=True, gated_residual=True, node_gate=0.6),
+    'gated0': dict(residual=True, gated_residual=True, node_gate=0.0),
+    'gated-': dict(residual=True, gated_residual=True, node_gate=-0.3),
+    'eatt-tanh': dict(edge_attention=True, node_attention=True, attention_activation_fn='tanh'),
+    'eatt-relu': dict(edge_attention=True, node_attention=True, attention_activation_fn='relu'),
+    'eatt-silu': dict(edge_attention=True, node_attention=True, attention_activation_fn='silu'),
 }
 FAMILY_ENV = {'default': {}, 'exact': {'PVS_EGNN_BF16X3': '0'}, 'generic': {'PVS_EGNN_KERNELS': 'generic'}}
 
@@ -97,11 +112,15 @@ def _environment(cell):
                 os.environ[k] = v
 
 
-def _new_layer(A, hid, flags, seed):
+def _new_layer(A, hid, flags, seed, node_gate=None):
     """A layer with every parameter away from its symmetric initial value: gates 0.7 / 0.6 instead of 0.5 (a swap of
     gate and 1 - gate would not show), GraphNorm's (1, 0, 1) perturbed, the last coordinate weight (Xavier gain 0.001)
-    a hundred times larger so that the coordinate update is not lost beside the coordinates."""
+    a hundred times larger so that the coordinate update is not lost beside the coordinates.
+    node_gate: another value for node_gate_parameter (default: the flag set's `node_gate` entry, else 0.6)."""
     from pointvs_amd.egnn_satorras import EGNNLayer
+    flags = dict(flags)
+    gate = flags.pop('node_gate', 0.6)
+    node_gate = gate if node_gate is None else node_gate
     torch.manual_seed(seed)
     layer = EGNNLayer(hid, hid, hid, edges_in_d=A, **flags)
     gen = torch.Generator().manual_seed(seed + 1)
@@ -113,7 +132,7 @@ def _new_layer(A, hid, flags, seed):
         if hasattr(layer, 'edge_gate_parameter'):
             layer.edge_gate_parameter.fill_(0.7)
         if hasattr(layer, 'node_gate_parameter'):
-            layer.node_gate_parameter.fill_(0.6)
+            layer.node_gate_parameter.fill_(node_gate)
     return layer
 
 
