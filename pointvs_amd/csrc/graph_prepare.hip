@@ -182,81 +182,91 @@ __device__ __forceinline__ int graph_of_edge(const int32_t* __restrict__ edge_pt
     return g;
 }
 
-// One thread per PAIR of consecutive edges. The reference's format costs 40 bytes per edge here (int64 COO + int64
-// one-hot [E, 3]) against 9 written, so the pass is a stream of loads: VEC = 16-byte loads (two int64 per request:
-// rows, columns and the pair's 2A one-hot words; needs E even and 16-byte aligned arrays - the launcher checks).
-template <bool VEC>
-__global__ void k_extract_runs(const int64_t* __restrict__ ei, const int64_t* __restrict__ ea, int A, int N, int E,
-                               int n_graphs, const int32_t* __restrict__ node_ptr, const int32_t* __restrict__ edge_ptr,
-                               int32_t* __restrict__ row32, int32_t* __restrict__ col32, uint8_t* __restrict__ etype_in,
-                               int32_t* __restrict__ split, int32_t* __restrict__ status) {
-    const int e0 = 2 * (blockIdx.x * blockDim.x + threadIdx.x);
-    int g = graph_of_edge(edge_ptr, n_graphs, min(e0, E - 1), E, 2);
-    if (e0 >= E) return;
-    const int n_here = e0 + 1 < E ? 2 : 1;
-    int64_t rr[2], cc[2];
-    if (VEC) {
-        const longlong2 r2 = *reinterpret_cast<const longlong2*>(ei + e0);
-        const longlong2 c2 = *reinterpret_cast<const longlong2*>(ei + (size_t)E + e0);
-        rr[0] = r2.x; rr[1] = r2.y; cc[0] = c2.x; cc[1] = c2.y;
-    } else {
-        rr[0] = ei[e0]; cc[0] = ei[(size_t)E + e0];
-        rr[1] = n_here > 1 ? ei[e0 + 1] : 0; cc[1] = n_here > 1 ? ei[(size_t)E + e0 + 1] : 0;
+// ---- the row side as two streams over the int64 inputs (round 7) -----------------------------------------------------
+// The reference's format costs 40 bytes per edge (int64 COO + int64 one-hot [E, 3]) against 13 written, so the passes
+// over the edges are streams of loads, and every input byte is read once by the pass that needs it: a rows-only
+// pre-pass (k_scan_rows: 8 bytes per edge) finds each graph's descent and decides everything that rows and tables
+// decide; the placement pass (k_place_stream) reads rows, columns and one-hot words and writes row / col / etype /
+// perm at their final positions. No narrowed copy of the inputs in between.
+// A wave takes 64 * K consecutive edges (K = kScanEdges / kPlaceEdges) and lane l owns edges l, 64 + l, 128 + l, ... of
+// them: every load instruction of the wave covers one contiguous run, so does every store while the wave stays inside
+// one row's slots, and a lane has K independent loads per array in flight. Measured at cfg2 (10.2 M edges, MI355X):
+// k_scan_rows 16.1 us (81.5 MB: 5.1 TB/s), k_place_stream 98.2 us (407.6 MB read + 132.5 MB written: 5.5 TB/s, against
+// 6.29 TB/s for a float4 copy); 2 / 4 / 8 edges per thread in the placement pass: 101 / 106 / 124.5 us without the
+// non-temporal loads - more waves per SIMD beat more loads per lane.
+constexpr int kScanEdges = 8;                                   // edges per thread of k_scan_rows
+constexpr int kPlaceEdges = 4;                                  // ... of k_place_stream (even: the one-hot words go by 128 edges)
+constexpr int kPrepThreads = 256;
+constexpr int kPrepWaves = kPrepThreads / 64;
+
+typedef long long pvs_ll2 __attribute__((ext_vector_type(2)));
+// The placement pass is the last reader of its inputs: non-temporal loads, so that the 408 MB do not push `col` and the
+// tables of the by-column kernels behind it out of the caches (cfg2, 4 edges per thread: 0.265 -> 0.256 ms per
+// preparation, k_place_stream 104 -> 96 us, k_csc_pass<false> 18.8 -> 15.3 us; in k_scan_rows they cost k_run_starts,
+// which searches the same rows, 8 us: profiles/r07_ab_prepare_streams.txt).
+template <class T> __device__ __forceinline__ T prep_load_once(const T* p) { return __builtin_nontemporal_load(p); }
+
+// the graph of the edge at hand and its slices of the two tables: reloaded only when the walk moves on
+struct PrepSeg { int g, n_lo, n_hi, e_lo, e_hi; };
+
+__device__ __forceinline__ void prep_seg_load(PrepSeg& s, const int32_t* __restrict__ node_ptr,
+                                              const int32_t* __restrict__ edge_ptr) {
+    s.n_lo = node_ptr[s.g]; s.n_hi = node_ptr[s.g + 1];
+    s.e_lo = edge_ptr[s.g]; s.e_hi = edge_ptr[s.g + 1];
+}
+
+// (the walk of graph_of_edge, continued: the last g with edge_ptr[g] <= e as seen from the previous edge's graph)
+__device__ __forceinline__ bool prep_seg_advance(PrepSeg& s, int e, int n_graphs, const int32_t* __restrict__ node_ptr,
+                                                 const int32_t* __restrict__ edge_ptr) {
+    if (s.g + 1 >= n_graphs || s.e_hi > e) return false;
+    do ++s.g; while (s.g + 1 < n_graphs && edge_ptr[s.g + 1] <= e);
+    prep_seg_load(s, node_ptr, edge_ptr);
+    return true;
+}
+
+// Pre-pass over edge_index[0, :]. Status bit 1: a row outside [0, N). Status bit 4: a row outside its graph's node
+// range, tables that do not cover exactly [0, E) / [0, N), more than one descent in a graph. split[g] = the graph's
+// descent (k_init_split: edge_ptr[g + 1] where there is none). The row in front of a lane's edge is the neighbouring
+// lane's (a lane move); lane 0 takes lane 63's of the step before, and the wave's first edge one load of its own.
+__global__ void __launch_bounds__(kPrepThreads)
+k_scan_rows(const int64_t* __restrict__ rows, int N, int E, int n_graphs, const int32_t* __restrict__ node_ptr,
+            const int32_t* __restrict__ edge_ptr, int32_t* __restrict__ split, int32_t* __restrict__ status) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const long long cb = ((long long)blockIdx.x * kPrepWaves + wv) * (64 * kScanEdges);      // the wave's first edge
+    PrepSeg s;
+    s.g = graph_of_edge(edge_ptr, n_graphs, (int)min(cb + lane, (long long)E - 1), E, kScanEdges);
+    if (cb >= E) return;                                    // (wave-uniform)
+    long long r[kScanEdges];
+#pragma unroll
+    for (int j = 0; j < kScanEdges; ++j) {
+        const long long e = cb + 64 * j + lane;
+        r[j] = e < E ? (long long)rows[e] : 0;
     }
-    int64_t prev = e0 > 0 ? ei[e0 - 1] : 0;      // (the neighbouring thread's line: a cache hit)
-    int hot[2] = {-1, -1}, attr_bad[2] = {0, 0};
-    if (A > 0) {
-        int ones[2] = {0, 0};
-        if (VEC) {       // the pair's 2A words as A 16-byte loads: word w belongs to edge w / A, class w % A
-            const longlong2* src = reinterpret_cast<const longlong2*>(ea + (size_t)e0 * A);
-            for (int q = 0; q < A; ++q) {
-                const longlong2 v = src[q];
-                const int w0 = 2 * q, w1 = 2 * q + 1;
-                const int ed0 = w0 >= A, ed1 = w1 >= A;
-                if (v.x == 1) { ones[ed0]++; hot[ed0] = w0 - ed0 * A; } else if (v.x != 0) attr_bad[ed0] = 1;
-                if (v.y == 1) { ones[ed1]++; hot[ed1] = w1 - ed1 * A; } else if (v.y != 0) attr_bad[ed1] = 1;
-            }
-        } else {
-            for (int i = 0; i < n_here; ++i)
-                for (int a = 0; a < A; ++a) {
-                    const int64_t v = ea[(size_t)(e0 + i) * A + a];
-                    if (v == 1) { ones[i]++; hot[i] = a; } else if (v != 0) attr_bad[i] = 1;
-                }
-        }
-        for (int i = 0; i < 2; ++i) if (ones[i] != 1) attr_bad[i] = 1;
-    }
+    long long before = 0;
+    if (lane == 0 && cb > 0) before = rows[cb - 1];
+    prep_seg_load(s, node_ptr, edge_ptr);
     int bad = 0;
-    int32_t r32[2] = {0, 0}, c32[2] = {0, 0};
-    uint8_t ty[2] = {0, 0};
-    for (int i = 0; i < n_here; ++i) {
-        const int e = e0 + i;
-        while (g + 1 < n_graphs && edge_ptr[g + 1] <= e) ++g;
-        int64_t r = rr[i], c = cc[i];
-        if (r < 0 || r >= N || c < 0 || c >= N) { bad |= 1; r = 0; c = 0; }
-        if (r < node_ptr[g] || r >= node_ptr[g + 1] || c < node_ptr[g] || c >= node_ptr[g + 1]) bad |= 4;
+#pragma unroll
+    for (int j = 0; j < kScanEdges; ++j) {
+        long long prev = __shfl_up(r[j], 1, 64);
+        const long long carry = j ? __shfl(r[j ? j - 1 : 0], 63, 64) : before;
+        if (lane == 0) prev = carry;
+        const long long el = cb + 64 * j + lane;
+        if (el >= E) continue;
+        const int e = (int)el;
+        prep_seg_advance(s, e, n_graphs, node_ptr, edge_ptr);
+        long long v = r[j];
+        if (v < 0 || v >= N) { bad |= 1; v = 0; }
+        if (v < s.n_lo || v >= s.n_hi) bad |= 4;
         // the tables themselves: they must cover exactly [0, E) and [0, N) (an edge list edited after collation with
         // stale per-graph counts would otherwise be placed outside its rows' slots); monotone segments follow from
-        // the per-edge range checks above, because every edge is tested against the segment the walk assigns it
-        if (e < edge_ptr[g] || e >= edge_ptr[g + 1]) bad |= 4;
+        // the per-edge range checks, because every edge is tested against the segment the walk assigns it
+        if (e < s.e_lo || e >= s.e_hi) bad |= 4;
         if (e == 0 && (edge_ptr[0] != 0 || edge_ptr[n_graphs] != E || node_ptr[0] != 0 || node_ptr[n_graphs] != N)) bad |= 4;
-        if (e > edge_ptr[g] && prev > rr[i]) {         // a descent inside the graph: the second run starts here
-            const int old = atomicMin(&split[g], e);
-            if (old != edge_ptr[g + 1]) bad |= 4;          // more than one descent: not two sorted runs
+        if (e > s.e_lo && prev > r[j]) {               // a descent inside the graph: the second run starts here
+            const int old = atomicMin(&split[s.g], e);
+            if (old != s.e_hi) bad |= 4;                   // more than one descent: not two sorted runs
         }
-        prev = rr[i];
-        r32[i] = (int32_t)r; c32[i] = (int32_t)c;
-        if (A > 0) {
-            if (attr_bad[i]) { bad |= 2; if (hot[i] < 0) hot[i] = 0; }
-            ty[i] = (uint8_t)hot[i];
-        }
-    }
-    if (n_here == 2) {
-        *reinterpret_cast<int2*>(row32 + e0) = make_int2(r32[0], r32[1]);
-        *reinterpret_cast<int2*>(col32 + e0) = make_int2(c32[0], c32[1]);
-        if (A > 0) *reinterpret_cast<uchar2*>(etype_in + e0) = make_uchar2(ty[0], ty[1]);
-    } else {
-        row32[e0] = r32[0]; col32[e0] = c32[0];
-        if (A > 0) etype_in[e0] = ty[0];
     }
     if (bad) atomicOr(status, bad);
 }
@@ -273,18 +283,25 @@ __global__ void k_init_split(int n_graphs, const int32_t* __restrict__ edge_ptr,
     if (g < n_graphs) split[g] = edge_ptr[g + 1];      // no descent: the second run is empty
 }
 
-// per node: where its edges start in the first / second run of its graph, how many the first run has, degree
-__global__ void k_run_starts(const int32_t* __restrict__ row32, int N, int E, int n_graphs,
+// per node: where its edges start in the first / second run of its graph, how many the first run has, degree. The
+// searches read the caller's int64 rows. What the placement needs of a row is ONE 8-byte record: the sorted position of
+// edge e of the first run is  rowptr[r] + (e - start_a[r])  and of the second  rowptr[r] + cnt_a[r] + (e - start_b[r]),
+// so rec[r] = (rowptr - start_a, rowptr + cnt_a - start_b) and the position is e + rec[r].x or e + rec[r].y.
+__global__ void k_run_starts(const int64_t* __restrict__ rows, int N, int E, int n_graphs,
                              const int32_t* __restrict__ status, const int32_t* __restrict__ node_ptr,
                              const int32_t* __restrict__ edge_ptr, const int32_t* __restrict__ split,
-                             int32_t* __restrict__ start_a, int32_t* __restrict__ start_b, int32_t* __restrict__ cnt_a,
+                             int2* __restrict__ rec, int32_t* __restrict__ unsafe,
                              int32_t* __restrict__ rowptr, float* __restrict__ inv_deg) {
     const int n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= N) return;
     if (n == N - 1) rowptr[N] = E;
-    if (*status & 4) {      // broken contract (all of it is known after k_extract_runs): a SAFE graph - every
+    // everything rows and tables decide is known after k_scan_rows; the placement pass (which adds the columns' and the
+    // one-hot words' bits to the status word while it runs) takes the verdict from a word of its own
+    const bool broken = (*status & 5) != 0;
+    if (n == 0) *unsafe = broken;
+    if (broken) {           // broken contract or a row outside [0, N): a SAFE graph - every
         // edge a self-edge of node 0 - so that nothing downstream indexes out of bounds before the host raises
-        start_a[n] = 0; start_b[n] = 0; cnt_a[n] = 0;
+        rec[n] = make_int2(0, 0);
         rowptr[n] = n == 0 ? 0 : E;
         inv_deg[n] = 1.0f;
         return;
@@ -301,57 +318,135 @@ __global__ void k_run_starts(const int32_t* __restrict__ row32, int N, int E, in
     int f0 = a0, l0 = a1, f1 = a0, l1 = a1, f2 = a1, l2 = b1, f3 = a1, l3 = b1;
     while (f0 < l0 || f1 < l1 || f2 < l2 || f3 < l3) {
         const int m0 = (f0 + l0) >> 1, m1 = (f1 + l1) >> 1, m2 = (f2 + l2) >> 1, m3 = (f3 + l3) >> 1;
-        const int v0 = f0 < l0 ? row32[m0] : 0, v1 = f1 < l1 ? row32[m1] : 0;
-        const int v2 = f2 < l2 ? row32[m2] : 0, v3 = f3 < l3 ? row32[m3] : 0;
+        const int64_t v0 = f0 < l0 ? rows[m0] : 0, v1 = f1 < l1 ? rows[m1] : 0;
+        const int64_t v2 = f2 < l2 ? rows[m2] : 0, v3 = f3 < l3 ? rows[m3] : 0;
         if (f0 < l0) { if (v0 < n) f0 = m0 + 1; else l0 = m0; }
         if (f1 < l1) { if (v1 < n + 1) f1 = m1 + 1; else l1 = m1; }
         if (f2 < l2) { if (v2 < n) f2 = m2 + 1; else l2 = m2; }
         if (f3 < l3) { if (v3 < n + 1) f3 = m3 + 1; else l3 = m3; }
     }
     const int sa = f0, sa_next = f1, sb = f2, sb_next = f3;
-    start_a[n] = sa;
-    start_b[n] = sb;
-    cnt_a[n] = sa_next - sa;
     const int d = (sa_next - sa) + (sb_next - sb);
     // rowptr WITHOUT a prefix sum (round 5): the graph's edges fill [edge_ptr[g], edge_ptr[g + 1]) of the sorted list, and
     // those in front of row n are the (sa - a0) edges of run A and the (sb - a1) edges of run B with a smaller row
-    rowptr[n] = a0 + (sa - a0) + (sb - a1);
+    const int first = a0 + (sa - a0) + (sb - a1);
+    rowptr[n] = first;
+    rec[n] = make_int2(first - sa, first + (sa_next - sa) - sb);
     inv_deg[n] = 1.0f / (float)(d > 1 ? d : 1);
 }
 
-__global__ void k_place_runs(const int32_t* __restrict__ row32, const int32_t* __restrict__ col32,
-                             const uint8_t* __restrict__ etype_in, int E, int n_graphs,
-                             const int32_t* __restrict__ edge_ptr, const int32_t* __restrict__ split,
-                             const int32_t* __restrict__ rowptr, const int32_t* __restrict__ start_a,
-                             const int32_t* __restrict__ start_b, const int32_t* __restrict__ cnt_a,
-                             int32_t* __restrict__ row, int32_t* __restrict__ col, uint8_t* __restrict__ etype,
-                             int32_t* __restrict__ perm, const int32_t* __restrict__ status) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    const int g = graph_of_edge(edge_ptr, n_graphs, min(e, E - 1), E);
-    if (e >= E) return;
-    if (*status & 4) {      // the safe graph of k_run_starts
-        row[e] = 0; col[e] = 0; perm[e] = e;
-        if (etype) etype[e] = 0;
-        return;
-    }
-    // (two sorted runs per graph with rows inside the graph's range - verified by k_extract_runs - make the
-    // positions below a bijection onto [0, E): every slot is written exactly once)
-    const int r = row32[e];
-    const bool second = e >= split[g];
-    const int off = second ? e - start_b[r] : e - start_a[r];
-    const int local = second ? cnt_a[r] + off : off;
-    const int pos = rowptr[r] + local;
-    row[pos] = r;
-    col[pos] = col32[e];
-    if (etype) etype[pos] = etype_in[e];
-    perm[pos] = e;
-}
+__device__ __forceinline__ int prep_code(long long v) { return v == 0 ? 0 : v == 1 ? 1 : 2; }
 
+// Placement pass: rows, columns and one-hot words are read once and row / col / etype / perm written at their final
+// positions. Status bit 1: a column outside [0, N); bit 2: a row of edge_attr that is not one-hot; bit 4: a column
+// outside its graph's node range. A column can only be judged here, after the positions are fixed: a bad one is
+// replaced by the edge's row (in range: k_scan_rows passed), and rows alone decide positions, so the placement stays a
+// bijection onto [0, E) - every slot is written exactly once (two sorted runs per graph with rows inside the graph's
+// range) - and nothing downstream indexes out of bounds before the host raises.
+// The one-hot words of 128 consecutive edges are 128 * A consecutive int64: the wave loads them as A contiguous runs of
+// 64 16-byte pieces (VEC; two 8-byte loads per piece where edge_attr is not 16-byte aligned), turns every word into a
+// byte code (0, 1, other) and hands the codes to the owning lanes through LDS. A <= AMAX takes this route; more
+// classes than that are read word by word by the owning lane.
+template <bool VEC, int AMAX>
+__global__ void __launch_bounds__(kPrepThreads)
+k_place_stream(const int64_t* __restrict__ ei, const int64_t* __restrict__ ea, int A, int N, int E, int n_graphs,
+               const int32_t* __restrict__ node_ptr, const int32_t* __restrict__ edge_ptr,
+               const int32_t* __restrict__ split, const int2* __restrict__ rec, const int32_t* __restrict__ unsafe,
+               int32_t* __restrict__ row, int32_t* __restrict__ col, uint8_t* __restrict__ etype,
+               int32_t* __restrict__ perm, int32_t* __restrict__ status) {
+    __shared__ unsigned short codes[kPrepWaves][kPlaceEdges / 2][64 * AMAX];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const long long cb = ((long long)blockIdx.x * kPrepWaves + wv) * (64 * kPlaceEdges);      // the wave's first edge
+    PrepSeg s;
+    s.g = graph_of_edge(edge_ptr, n_graphs, (int)min(cb + lane, (long long)E - 1), E, kPlaceEdges);
+    if (cb >= E) return;                                    // (wave-uniform)
+    const int64_t* cols = ei + (size_t)E;
+    long long r[kPlaceEdges], c[kPlaceEdges];
+#pragma unroll
+    for (int j = 0; j < kPlaceEdges; ++j) {
+        const long long e = cb + 64 * j + lane;
+        r[j] = e < E ? (long long)prep_load_once(ei + e) : 0;
+        c[j] = e < E ? (long long)prep_load_once(cols + e) : 0;
+    }
+    const bool by_pieces = A > 0 && A <= AMAX;              // (wave-uniform)
+    if (by_pieces) {
+        const size_t words = (size_t)E * A;
+        pvs_ll2 av[kPlaceEdges / 2][AMAX];
+#pragma unroll
+        for (int jj = 0; jj < kPlaceEdges / 2; ++jj)
+#pragma unroll
+            for (int q = 0; q < AMAX; ++q) {
+                av[jj][q] = pvs_ll2{0, 0};
+                if (q >= A) continue;
+                // (even: 128 * A words per step pair, two per piece - a 16-byte aligned array keeps every piece aligned)
+                const size_t w0 = (size_t)(cb + 128 * jj) * A + 2 * (size_t)(q * 64 + lane);
+                if (VEC && w0 + 1 < words) {
+                    av[jj][q] = prep_load_once(reinterpret_cast<const pvs_ll2*>(ea + w0));
+                } else {
+                    if (w0 < words) av[jj][q].x = ea[w0];
+                    if (w0 + 1 < words) av[jj][q].y = ea[w0 + 1];
+                }
+            }
+#pragma unroll
+        for (int jj = 0; jj < kPlaceEdges / 2; ++jj)
+#pragma unroll
+            for (int q = 0; q < AMAX; ++q)
+                if (q < A) codes[wv][jj][q * 64 + lane] = (unsigned short)(prep_code(av[jj][q].x) | prep_code(av[jj][q].y) << 8);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+    const bool safe_graph = *unsafe != 0;
+    prep_seg_load(s, node_ptr, edge_ptr);
+    int second_from = split[s.g];
+    int bad = 0;
+#pragma unroll
+    for (int j = 0; j < kPlaceEdges; ++j) {
+        const long long el = cb + 64 * j + lane;
+        if (el >= E) continue;
+        const int e = (int)el;
+        if (prep_seg_advance(s, e, n_graphs, node_ptr, edge_ptr)) second_from = split[s.g];
+        long long cc = c[j];
+        bool col_bad = false;
+        if (cc < 0 || cc >= N) { bad |= 1; cc = 0; col_bad = true; }
+        if (cc < s.n_lo || cc >= s.n_hi) { bad |= 4; col_bad = true; }
+        int hot = -1;
+        if (A > 0) {
+            int ones = 0, other = 0;
+            if (by_pieces) {
+                const unsigned char* mine = reinterpret_cast<const unsigned char*>(codes[wv][j >> 1]) + ((j & 1) * 64 + lane) * A;
+                for (int a = 0; a < A; ++a) {
+                    const int k = mine[a];
+                    if (k == 1) { ones++; hot = a; } else if (k != 0) other = 1;
+                }
+            } else {
+                for (int a = 0; a < A; ++a) {
+                    const int64_t v = ea[(size_t)e * A + a];
+                    if (v == 1) { ones++; hot = a; } else if (v != 0) other = 1;
+                }
+            }
+            if (ones != 1 || other) { bad |= 2; if (hot < 0) hot = 0; }
+        }
+        if (safe_graph) {       // the safe graph of k_run_starts
+            row[e] = 0; col[e] = 0; perm[e] = e;
+            if (etype) etype[e] = 0;
+            continue;
+        }
+        const int rr = (int)r[j];
+        const int2 t = rec[rr];
+        const int pos = e + (e >= second_from ? t.y : t.x);
+        row[pos] = rr;
+        col[pos] = col_bad ? rr : (int)cc;
+        if (etype) etype[pos] = (uint8_t)hot;
+        perm[pos] = e;
+    }
+    if (bad) atomicOr(status, bad);
+}
 
 // ---- by-column lists of a batch of disjoint graphs WITHOUT a sort ("counting transpose", round 3) ----------
 // cedge = the sorted positions grouped by column, ascending inside a column (what a stable sort by column of the
 // row-sorted list gives). The columns of a graph's edges lie inside the graph's node range (verified by
-// k_extract_runs), so a column has at most max_graph_nodes distinct keys RELATIVE to its graph: a counting sort
+// k_place_stream, which writes them), so a column has at most max_graph_nodes distinct keys RELATIVE to its graph: a counting sort
 // with one LDS table per wave. Every graph's positions are cut into `cpg` contiguous chunks, one wave per chunk:
 //   pass 1  counts the chunk's edges per column                       (cnt[chunk][column], LDS atomics: integer
 //           sums do not depend on their order)
@@ -374,8 +469,8 @@ constexpr int kCscAhead = 8;              // steps of 64 positions whose columns
 
 struct CscChunk { int begin, end, node_lo, width, g; };
 
-// The caller's edge_ptr / node_ptr are CLAMPED into [0, E] / [0, N] and made monotone here: k_extract_runs verifies the
-// layout on the device and sets status bit 4, but these passes run before the host reads the status word, and a
+// The caller's edge_ptr / node_ptr are CLAMPED into [0, E] / [0, N] and made monotone here: k_scan_rows and k_place_stream verify the
+// layout on the device and set status bit 4, but these passes run before the host reads the status word, and a
 // direct C-ABI caller may pass tables that do not even end at E. With consistent tables the clamps do nothing.
 __device__ __forceinline__ CscChunk csc_chunk(int wid, int cpg, int stride, int n_graphs, int N, int E,
                                               const int32_t* __restrict__ node_ptr,
@@ -640,42 +735,38 @@ int csc_stride(int max_graph_nodes) { return (max_graph_nodes + 63) & ~63; }
 bool csc_counting_ok(int max_graph_nodes) { return max_graph_nodes > 0 && max_graph_nodes <= kCscMaxCols; }
 
 struct RunsWs {
-    int32_t *row32, *col32, *iota, *keys_tmp, *split, *start_a, *start_b, *cnt_a, *deg, *csc_cnt, *indeg;
-    uint8_t* etype_in;
-    void *sort_tmp, *scan_tmp;
-    size_t sort_bytes, scan_bytes;
+    int32_t *iota, *keys_tmp, *split, *unsafe, *csc_cnt, *indeg;
+    int2* rec;
+    void* sort_tmp;
+    size_t sort_bytes;
 };
 
 size_t carve_runs(PvsArena& a, int N, int E, int B, int max_graph_nodes, RunsWs* w) {
     const size_t e = (size_t)(E > 0 ? E : 1);
     RunsWs t;
-    t.row32 = a.take<int32_t>(e);
-    t.col32 = a.take<int32_t>(e);
-    t.iota = a.take<int32_t>(e);
-    t.keys_tmp = a.take<int32_t>(e);
-    t.etype_in = a.take<uint8_t>(e);
     t.split = a.take<int32_t>((size_t)B + 1);
-    t.start_a = a.take<int32_t>((size_t)N);
-    t.start_b = a.take<int32_t>((size_t)N);
-    t.cnt_a = a.take<int32_t>((size_t)N);
-    t.deg = a.take<int32_t>((size_t)N + 1);
-    t.sort_bytes = sort_temp_bytes(E > 0 ? E : 1, key_bits(N > 1 ? N : 2));
-    t.sort_tmp = a.take<char>(t.sort_bytes);
-    t.scan_bytes = 0;
-    hipcub::DeviceScan::ExclusiveSum(nullptr, t.scan_bytes, (const int32_t*)nullptr, (int32_t*)nullptr, N + 1, 0);
-    t.scan_tmp = a.take<char>(t.scan_bytes);
+    t.unsafe = a.take<int32_t>(1);
+    t.rec = a.take<int2>((size_t)N);
     t.csc_cnt = nullptr;
     t.indeg = nullptr;
+    t.iota = t.keys_tmp = nullptr;
+    t.sort_tmp = nullptr;
+    t.sort_bytes = 0;
     if (csc_counting_ok(max_graph_nodes)) {
         t.csc_cnt = a.take<int32_t>((size_t)B * csc_chunks_per_graph(B) * csc_stride(max_graph_nodes));
         t.indeg = a.take<int32_t>((size_t)N + 1);
     }
+    // (the by-column sort - graphs beyond the counting path, PVS_CSC_SORT=1 - is the only user of these)
+    t.iota = a.take<int32_t>(e);
+    t.keys_tmp = a.take<int32_t>(e);
+    t.sort_bytes = sort_temp_bytes(E > 0 ? E : 1, key_bits(N > 1 ? N : 2));
+    t.sort_tmp = a.take<char>(t.sort_bytes);
     if (w) *w = t;
     return a.off;
 }
 
 // indeg[n] = edges whose column is n (sum over the chunks of n's graph)
-// (status bit 4 - a broken layout contract, final since k_extract_runs: every in-degree is 0, so colptr is all zeros
+// (status bit 4 - a broken layout contract, final since k_place_stream: every in-degree is 0, so colptr is all zeros
 // and nothing downstream follows cedge; the host raises at its next poll of the status word)
 __global__ void k_csc_totals(const int32_t* __restrict__ cnt, int N, int n_graphs, const int32_t* __restrict__ node_ptr,
                              int cpg, int stride, int32_t* __restrict__ indeg, const int32_t* __restrict__ status) {
@@ -785,25 +876,25 @@ extern "C" int pvs_graph_prepare_runs(const int64_t* edge_index, const int64_t* 
     k_init_split<<<(n_graphs + T - 1) / T > 0 ? (n_graphs + T - 1) / T : 1, T, 0, stream>>>(n_graphs, edge_ptr, w.split, status);
     PVS_CHECK_LAUNCH();
     if (E > 0) {
-        const bool vec = (E & 1) == 0 && (((uintptr_t)edge_index | (uintptr_t)edge_attr) & 15) == 0;
-        const int pairs = (E + 1) / 2;
-        if (vec)
-            k_extract_runs<true><<<(pairs + T - 1) / T, T, 0, stream>>>(edge_index, edge_attr, n_edge_attr, N, E, n_graphs,
-                                                                        node_ptr, edge_ptr, w.row32, w.col32, w.etype_in,
-                                                                        w.split, status);
-        else
-            k_extract_runs<false><<<(pairs + T - 1) / T, T, 0, stream>>>(edge_index, edge_attr, n_edge_attr, N, E, n_graphs,
-                                                                         node_ptr, edge_ptr, w.row32, w.col32, w.etype_in,
-                                                                         w.split, status);
+        const int scan_edges = kPrepThreads * kScanEdges;
+        k_scan_rows<<<(E + scan_edges - 1) / scan_edges, kPrepThreads, 0, stream>>>(edge_index, N, E, n_graphs, node_ptr,
+                                                                                           edge_ptr, w.split, status);
         PVS_CHECK_LAUNCH();
     }
-    k_run_starts<<<(N + T - 1) / T, T, 0, stream>>>(w.row32, N, E, n_graphs, status, node_ptr, edge_ptr, w.split, w.start_a,
-                                                    w.start_b, w.cnt_a, rowptr, inv_deg);
+    k_run_starts<<<(N + T - 1) / T, T, 0, stream>>>(edge_index, N, E, n_graphs, status, node_ptr, edge_ptr, w.split, w.rec,
+                                                    w.unsafe, rowptr, inv_deg);
     PVS_CHECK_LAUNCH();
     if (E > 0) {
-        k_place_runs<<<(E + T - 1) / T, T, 0, stream>>>(w.row32, w.col32, w.etype_in, E, n_graphs, edge_ptr, w.split,
-                                                        rowptr, w.start_a, w.start_b, w.cnt_a, row, col,
-                                                        n_edge_attr ? etype : nullptr, perm, status);
+        // (16-byte loads of the one-hot words need a 16-byte aligned edge_attr; rows and columns go by 8-byte loads, one
+        // edge per lane, so an odd E or an offset edge_index changes nothing)
+        const bool vec = ((uintptr_t)edge_attr & 15) == 0;
+        const int place_edges = kPrepThreads * kPlaceEdges;
+        const int blocks = (E + place_edges - 1) / place_edges;
+        auto place = n_edge_attr <= 3 ? (vec ? k_place_stream<true, 3> : k_place_stream<false, 3>)
+                                      : (vec ? k_place_stream<true, 8> : k_place_stream<false, 8>);
+        place<<<blocks, kPrepThreads, 0, stream>>>(edge_index, edge_attr, n_edge_attr, N, E, n_graphs, node_ptr, edge_ptr,
+                                                   w.split, w.rec, w.unsafe, row, col, n_edge_attr ? etype : nullptr, perm,
+                                                   status);
         PVS_CHECK_LAUNCH();
     }
     if (!cedge) return 0;

@@ -10,7 +10,7 @@ for f in glob.glob(sys.argv[1] + '/**/*kernel_trace.csv', recursive=True):
     r = list(csv.DictReader(open(f)))
     if rows is None or len(r) > len(rows):
         rows = r
-anchor = sys.argv[2] if len(sys.argv) > 2 else 'k_extract_runs'
+anchor = sys.argv[2] if len(sys.argv) > 2 else 'k_scan_rows'
 rows.sort(key=lambda r: int(r['Start_Timestamp']))
 idx = [i for i, r in enumerate(rows) if anchor in r['Kernel_Name']]
 start = idx[-2] if len(idx) > 1 else idx[-1]
