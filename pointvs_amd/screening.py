@@ -229,17 +229,14 @@ class _ReceptorSideScreen:
                 torch.empty(lib.pvs_egnn_layer_workspace_bytes(C.byref(desc), ws_nodes, ws_edges, 2),
                             dtype=torch.uint8, device=dev))
         saved, ws = self._l1_ws
-        if att_out is None:
-            _lib.check(lib.pvs_egnn_layer_fwd_partial(
-                C.byref(desc), C.byref(g), C.byref(pstruct), _lib.ptr(h), _lib.ptr(x), _lib.ptr(base_magg),
+        args = [C.byref(desc), C.byref(g), C.byref(pstruct), _lib.ptr(h), _lib.ptr(x), _lib.ptr(base_magg),
                 _lib.ptr(base_xsum), _lib.ptr(base_deg), _lib.ptr(h_out), _lib.ptr(x_out), _lib.ptr(natt),
-                _lib.ptr(saved), _lib.ptr(ws), ws.numel(), _stream(dev)), 'pvs_egnn_layer_fwd_partial')
-        else:
-            _lib.check(lib.pvs_egnn_layer_fwd_partial_att(
-                C.byref(desc), C.byref(g), C.byref(pstruct), _lib.ptr(h), _lib.ptr(x), _lib.ptr(base_magg),
-                _lib.ptr(base_xsum), _lib.ptr(base_deg), _lib.ptr(h_out), _lib.ptr(x_out), _lib.ptr(natt),
-                _lib.ptr(att_out), _lib.ptr(saved), _lib.ptr(ws), ws.numel(), _stream(dev)),
-                'pvs_egnn_layer_fwd_partial_att')
+                _lib.ptr(saved), _lib.ptr(ws), ws.numel(), _stream(dev)]
+        name = 'pvs_egnn_layer_fwd_partial'
+        if att_out is not None:      # (the _att entry point takes att_out behind natt and is otherwise called alike)
+            args.insert(11, _lib.ptr(att_out))
+            name = 'pvs_egnn_layer_fwd_partial_att'
+        _lib.check(getattr(lib, name)(*args), name)
         return h_out, x_out
 
     def _tail(self, pg_full, h, x):
@@ -525,6 +522,17 @@ def leave_out_pair_plan(pair_counts, sizes, batch_size, ligand_atom=True, recept
             for k in range(0, len(copies), batch_size)]
 
 
+def slot_offsets(batch_sizes, batch_size):
+    """The slot offsets of batches of a LibraryScreen: batch_sizes, a list of per-batch lists of up to `batch_size`
+    atom counts, as an int32 table [len(batch_sizes), batch_size + 1] on the host - row b: the exclusive prefix sums
+    of batch b's sizes, the slots after its last one empty (they repeat the last offset). What load_packed takes as
+    lig_ptr, one row per batch. Pure host arithmetic."""
+    ptrs = torch.zeros((len(batch_sizes), int(batch_size) + 1), dtype=torch.int32)
+    for b, sizes in enumerate(batch_sizes):
+        ptrs[b, 1:len(sizes) + 1] = torch.tensor(sizes, dtype=torch.int32)
+    return ptrs.cumsum(1, dtype=torch.int32)
+
+
 class LibraryScreen(_ReceptorSideScreen):
     """Library screening: every one of the `batch_size` slots of a batch holds one pose of ANY ligand of up to
     `max_lig_atoms` (<= MAX_SCREEN_LIGAND_ATOMS = 1024) atoms against the one receptor, or nothing (the last batch of
@@ -615,28 +623,33 @@ class LibraryScreen(_ReceptorSideScreen):
                     f'LibraryScreen(contact_attention={contact_attention}): the contact-attention reduction runs in '
                     'the step of the first-layer reuse, which this model does not have (softmax attention, '
                     'edge_residual or a hidden size other than 32 / 64 take the plain forward)')
-            f32 = dict(dtype=torch.float32, device=dev)
-            rec_sum, rec_count, rec_max = PF.new_contact_accumulators(self.n_rec, dev)
-            self.contact = dict(lig_att=torch.full((self.l_cap,), float('nan'), **f32),
-                                slot_rec_att=torch.full((self.b, self.n_rec), float('nan'), **f32),
-                                rec_sum=rec_sum, rec_count=rec_count, rec_max=rec_max)
+            self.contact = self._value_buffers('lig_att', 'slot_rec_att')
         if self._cam_plan is not None:
-            f32 = dict(dtype=torch.float32, device=dev)
-            rec_sum, rec_count, rec_max = PF.new_contact_accumulators(self.n_rec, dev)
-            self.cam = dict(node_y=torch.zeros((self.n_cap, sum(self._cam_plan[1])), **f32),
-                            lig_val=torch.full((self.l_cap,), float('nan'), **f32),
-                            slot_rec_val=torch.full((self.b, self.n_rec), float('nan'), **f32),
-                            rec_sum=rec_sum, rec_count=rec_count, rec_max=rec_max)
+            self.cam = self._value_buffers('lig_val', 'slot_rec_val', node_width=sum(self._cam_plan[1]))
         if self.reuse:
             self._cache_receptor_sums()
 
+    def _value_buffers(self, lig_key, slot_key, node_width=None):
+        """The static buffers of `contact` / `cam`: the three accumulators, with node_width node_y [N_cap, node_width],
+        and the last step's values per packed ligand atom (`lig_key`) and per slot and receptor atom (`slot_key`)."""
+        f32 = dict(dtype=torch.float32, device=self.lig_pos.device)
+        rec_sum, rec_count, rec_max = PF.new_contact_accumulators(self.n_rec, f32['device'])
+        values = {} if node_width is None else dict(node_y=torch.zeros((self.n_cap, node_width), **f32))
+        values.update({lig_key: torch.full((self.l_cap,), float('nan'), **f32),
+                       slot_key: torch.full((self.b, self.n_rec), float('nan'), **f32)},
+                      rec_sum=rec_sum, rec_count=rec_count, rec_max=rec_max)
+        return values
+
+    def _reset_values(self, values, who, feature):
+        if values is None:
+            raise RuntimeError(f'{who}: the screen was built without {feature}')
+        values['rec_sum'].zero_()
+        values['rec_count'].zero_()
+        values['rec_max'].fill_(float('nan'))
+
     def reset_cam(self):
         """The accumulators of `cam` as before the first step: sums and counts zero, maxima NaN (none so far)."""
-        if self.cam is None:
-            raise RuntimeError('reset_cam: the screen was built without cam')
-        self.cam['rec_sum'].zero_()
-        self.cam['rec_count'].zero_()
-        self.cam['rec_max'].fill_(float('nan'))
+        self._reset_values(self.cam, 'reset_cam', 'cam')
 
     def _reduce_cam(self, h, node_ptr, lig_ptr):
         """The heads on every row of the final embedding h [n, H] into cam['node_y'][:n] - one launch (PF.node_heads)
@@ -658,11 +671,7 @@ class LibraryScreen(_ReceptorSideScreen):
 
     def reset_contact_attention(self):
         """The accumulators of `contact` as before the first step: sums and counts zero, maxima NaN (none so far)."""
-        if self.contact is None:
-            raise RuntimeError('reset_contact_attention: the screen was built without contact_attention')
-        self.contact['rec_sum'].zero_()
-        self.contact['rec_count'].zero_()
-        self.contact['rec_max'].fill_(float('nan'))
+        self._reset_values(self.contact, 'reset_contact_attention', 'contact_attention')
 
     def _reduce_contacts(self, f, tag, att):
         """PF.contact_attention over f's CSR `tag` ('_l': ligand-touching, '': full) with `att` in its edge order."""
@@ -678,13 +687,33 @@ class LibraryScreen(_ReceptorSideScreen):
             t.rec_magg, t.rec_xsum, t.rec_deg = (_lib.ptr(v) for v in (self.rec_magg, self.rec_xsum, self.rec_deg))
 
     # ---- inputs ----
+    def _checked_sizes(self, sizes):
+        """The slots' atom counts as a list of ints, or a ValueError for more slots or atoms than the screen holds."""
+        sizes = [int(n) for n in sizes]
+        if len(sizes) > self.b or any(not 0 <= n <= self.max_lig_atoms for n in sizes):
+            raise ValueError(f'a batch holds up to {self.b} slots of 0..{self.max_lig_atoms} atoms (got {sizes})')
+        return sizes
+
+    def _loaded(self, sizes, n_struck):
+        """The host's copies of what was loaded: the slots' atom counts, their sum, the slots that lack a receptor
+        atom."""
+        self._sizes = sizes + [0] * (self.b - len(sizes))
+        self.n_atoms = sum(sizes)
+        self._n_struck = int(n_struck)
+
+    def _packer_status(self):
+        """The status word of the leave-out packers, allocated at the first leave-out batch."""
+        if self._pack_status is None:
+            self._pack_status = torch.zeros(1, dtype=torch.int32, device=self.lig_pos.device)
+        return self._pack_status
+
     def _load_rec_drop(self, rec_drop, n_slots):
-        """The static rec_drop of a struck screen <- a host list (None: every slot has the whole receptor)."""
+        """The static rec_drop of a struck screen <- a host list (None: every slot has the whole receptor). Returns
+        how many slots lack a receptor atom."""
         if rec_drop is None:
             if self.struck:
                 self.rec_drop.fill_(-1)
-            self._n_struck = 0
-            return
+            return 0
         if not self.struck:
             raise ValueError('rec_drop: the screen was built without struck=True')
         drops = [int(r) for r in rec_drop]
@@ -692,25 +721,22 @@ class LibraryScreen(_ReceptorSideScreen):
             raise ValueError(f'rec_drop: one entry of -1..{self.n_rec - 1} per slot ({n_slots}; got {drops})')
         drops += [-1] * (self.b - len(drops))
         self.rec_drop.copy_(torch.tensor(drops, dtype=torch.int32))
-        self._n_struck = sum(r >= 0 for r in drops)
+        return sum(r >= 0 for r in drops)
 
     def load_packed(self, lig_pos, lig_feats, lig_ptr, sizes, rec_drop=None):
         """One batch from packed device (or pinned host) tensors: lig_pos [L,3], lig_feats [L,F] (L = sum of
         sizes), lig_ptr [batch_size+1] int32; `sizes`: the host's copy of the slots' atom counts. Three
         asynchronous copies into the step's static inputs. rec_drop (a struck screen): a host list, one entry per
         slot of `sizes`."""
-        sizes = [int(n) for n in sizes]
-        if len(sizes) > self.b or any(not 0 <= n <= self.max_lig_atoms for n in sizes):
-            raise ValueError(f'a batch holds up to {self.b} slots of 0..{self.max_lig_atoms} atoms (got {sizes})')
-        self._load_rec_drop(rec_drop, len(sizes))
+        sizes = self._checked_sizes(sizes)
+        n_struck = self._load_rec_drop(rec_drop, len(sizes))
         total = sum(sizes)
         if lig_pos.shape[0] != total or lig_feats.shape[0] != total or lig_ptr.numel() != self.b + 1:
             raise ValueError('packed ligand tensors do not match the slot sizes')
         self.lig_pos[:total].copy_(lig_pos, non_blocking=True)
         self.lig_feats[:total].copy_(lig_feats, non_blocking=True)
         self.lig_ptr.copy_(lig_ptr, non_blocking=True)
-        self._sizes = sizes + [0] * (self.b - len(sizes))
-        self.n_atoms = total
+        self._loaded(sizes, n_struck)
         return self
 
     def load(self, slots, rec_drop=None):
@@ -718,9 +744,7 @@ class LibraryScreen(_ReceptorSideScreen):
         tensors); the slots after them are empty. Host tensors are packed into pinned staging. rec_drop (a struck
         screen, hand-built batches): a host list with one entry per slot, -1 or the receptor atom the slot lacks."""
         slots = list(slots)
-        sizes = [int(pose.shape[0]) for _, pose in slots]
-        if len(sizes) > self.b or any(not 0 <= n <= self.max_lig_atoms for n in sizes):
-            raise ValueError(f'a batch holds up to {self.b} slots of 0..{self.max_lig_atoms} atoms (got {sizes})')
+        sizes = self._checked_sizes(pose.shape[0] for _, pose in slots)
         total = sum(sizes)
         if len(self._stage) < 2:      # two staging sets: the previous batch's copies may still be in flight
             self._stage.append(dict(
@@ -753,16 +777,10 @@ class LibraryScreen(_ReceptorSideScreen):
         device), packed by one launch straight into the step's static inputs. `sizes`: the host's copy of the slots'
         atom counts (a batch of `leave_out_plan`); nothing is copied back. `check_leave_out()` reads the packer's
         verdict on lig_ptr."""
-        sizes = [int(n) for n in sizes]
-        if len(sizes) > self.b or any(not 0 <= n <= self.max_lig_atoms for n in sizes):
-            raise ValueError(f'a batch holds up to {self.b} slots of 0..{self.max_lig_atoms} atoms (got {sizes})')
-        if self._pack_status is None:
-            self._pack_status = torch.zeros(1, dtype=torch.int32, device=self.lig_pos.device)
+        sizes = self._checked_sizes(sizes)
         PF.leave_out_ligand_pack(lig_pos, lig_feats, lig_ptr, first_copy, self.b, self.max_lig_atoms,
-                                 out=(self.lig_pos, self.lig_feats, self.lig_ptr, self._pack_status))
-        self._load_rec_drop(None, len(sizes))
-        self._sizes = sizes + [0] * (self.b - len(sizes))
-        self.n_atoms = sum(sizes)
+                                 out=(self.lig_pos, self.lig_feats, self.lig_ptr, self._packer_status()))
+        self._loaded(sizes, self._load_rec_drop(None, len(sizes)))
         return self
 
     def load_leave_out_pairs(self, lig_pos, lig_feats, lig_ptr, pairs, pair_ptr, sizes, n_struck, first_copy):
@@ -774,19 +792,13 @@ class LibraryScreen(_ReceptorSideScreen):
         packer's verdict on the tables."""
         if not self.struck:
             raise ValueError('load_leave_out_pairs: the screen was built without struck=True')
-        sizes = [int(n) for n in sizes]
-        if len(sizes) > self.b or any(not 0 <= n <= self.max_lig_atoms for n in sizes):
-            raise ValueError(f'a batch holds up to {self.b} slots of 0..{self.max_lig_atoms} atoms (got {sizes})')
+        sizes = self._checked_sizes(sizes)
         if not 0 <= int(n_struck) <= len(sizes):
             raise ValueError(f'n_struck: 0..{len(sizes)} of the batch\'s slots (got {n_struck})')
-        if self._pack_status is None:
-            self._pack_status = torch.zeros(1, dtype=torch.int32, device=self.lig_pos.device)
         PF.leave_out_pair_pack(lig_pos, lig_feats, lig_ptr, pairs, pair_ptr, self.n_rec, first_copy, self.b,
                                self.max_lig_atoms,
-                               out=(self.lig_pos, self.lig_feats, self.lig_ptr, self.rec_drop, self._pack_status))
-        self._sizes = sizes + [0] * (self.b - len(sizes))
-        self.n_atoms = sum(sizes)
-        self._n_struck = int(n_struck)
+                               out=(self.lig_pos, self.lig_feats, self.lig_ptr, self.rec_drop, self._packer_status()))
+        self._loaded(sizes, n_struck)
         return self
 
     def check_leave_out(self):
@@ -823,27 +835,20 @@ class LibraryScreen(_ReceptorSideScreen):
         return f
 
     def _launch_builder(self, f):
-        lib = _lib.lib()
-        if self.struck:
-            _lib.check(lib.pvs_screen_graph_build_struck(
-                _lib.ptr(self.lig_pos), _lib.ptr(self.lig_ptr), _lib.ptr(self.rec_drop), _lib.ptr(self._rec_pos),
+        """The builder of the loaded batch into f: pvs_screen_graph_build_ragged_cap, or for a struck screen
+        pvs_screen_graph_build_struck, which takes rec_drop behind lig_ptr and is otherwise called alike."""
+        args = [_lib.ptr(self.lig_pos), _lib.ptr(self.lig_ptr), _lib.ptr(self._rec_pos),
                 _lib.ptr(self._rr.t['rowptr']), _lib.ptr(self._rr.t['col']), self.b, self.l_cap, self.n_rec,
-                self.slot_cap, float(self.r_inter), float(self.r_intra),
-                f['cap'], f['cap_l'], _lib.ptr(f['rowptr']), _lib.ptr(f['row']), _lib.ptr(f['col']),
-                _lib.ptr(f['etype']), _lib.ptr(f['inv_deg']), _lib.ptr(f['rowptr_l']), _lib.ptr(f['row_l']),
-                _lib.ptr(f['col_l']), _lib.ptr(f['etype_l']), _lib.ptr(f['node_ptr']), _lib.ptr(f['node_graph']),
-                _lib.ptr(f['pos']), C.byref(f['tables']), _lib.ptr(f['status']), _lib.ptr(f['state']),
-                f['state'].numel(), _stream(self.lig_pos.device)), 'pvs_screen_graph_build_struck')
-            return
-        _lib.check(lib.pvs_screen_graph_build_ragged_cap(
-            _lib.ptr(self.lig_pos), _lib.ptr(self.lig_ptr), _lib.ptr(self._rec_pos), _lib.ptr(self._rr.t['rowptr']),
-            _lib.ptr(self._rr.t['col']), self.b, self.l_cap, self.n_rec, self.slot_cap, float(self.r_inter),
-            float(self.r_intra),
-            f['cap'], f['cap_l'], _lib.ptr(f['rowptr']), _lib.ptr(f['row']), _lib.ptr(f['col']), _lib.ptr(f['etype']),
-            _lib.ptr(f['inv_deg']), _lib.ptr(f['rowptr_l']), _lib.ptr(f['row_l']), _lib.ptr(f['col_l']),
-            _lib.ptr(f['etype_l']), _lib.ptr(f['node_ptr']), _lib.ptr(f['node_graph']), _lib.ptr(f['pos']),
-            C.byref(f['tables']), _lib.ptr(f['status']), _lib.ptr(f['state']), f['state'].numel(),
-            _stream(self.lig_pos.device)), 'pvs_screen_graph_build_ragged_cap')
+                self.slot_cap, float(self.r_inter), float(self.r_intra), f['cap'], f['cap_l']]
+        args += [_lib.ptr(f[key]) for key in ('rowptr', 'row', 'col', 'etype', 'inv_deg', 'rowptr_l', 'row_l', 'col_l',
+                                              'etype_l', 'node_ptr', 'node_graph', 'pos')]
+        args += [C.byref(f['tables']), _lib.ptr(f['status']), _lib.ptr(f['state']), f['state'].numel(),
+                 _stream(self.lig_pos.device)]
+        name = 'pvs_screen_graph_build_ragged_cap'
+        if self.struck:
+            args.insert(2, _lib.ptr(self.rec_drop))
+            name = 'pvs_screen_graph_build_struck'
+        _lib.check(getattr(_lib.lib(), name)(*args), name)
 
     def _probe_capacities(self):
         """One synchronous probe: the builder with no room for edges leaves both exact edge counts in its row
@@ -978,15 +983,6 @@ class LibraryScreen(_ReceptorSideScreen):
 
     def replay(self, slots=None):
         return self._replay(lambda: None if slots is None else self.load(slots))
-
-
-def _starts(counts):
-    """The exclusive prefix sums of a host list."""
-    out, at = [], 0
-    for k in counts:
-        out.append(at)
-        at += k
-    return out
 
 
 class _SweepSink:
@@ -1240,10 +1236,7 @@ class ScreeningSweep:
                 # the whole library packed once, in plan order: a batch is a contiguous range of it
                 all_pos = torch.cat([ligands[k][2].to(dev).float().reshape(-1, 3) for k in small], 0)
                 all_feats = torch.cat([ligands[k][1].to(dev).float().repeat(c, 1) for k, c in zip(small, counts)], 0)
-                ptrs = torch.zeros((len(plan), self.b + 1), dtype=torch.int32)
-                for b, batch in enumerate(plan):
-                    ptrs[b, 1:len(batch) + 1] = torch.tensor([sizes[lig] for lig, _ in batch], dtype=torch.int32)
-                ptrs = ptrs.cumsum(1, dtype=torch.int32)
+                ptrs = slot_offsets([[sizes[lig] for lig, _ in batch] for batch in plan], self.b)
                 ptrs_dev = ptrs.to(dev)
                 screen = self._library_screen(max(sizes))
             next_large, at = 0, 0
@@ -1298,27 +1291,7 @@ class ScreeningSweep:
             if best >= 0:
                 yield name, lig_feats, poses[best]
 
-    @staticmethod
-    def _checked_hits(items, who):
-        """(items as a list, names, atom counts) of an iterable of (name, lig_feats [n,F], pose [n,3]): unique names,
-        n <= MAX_SCREEN_LIGAND_ATOMS, one pose each - or a ValueError that begins with `who`."""
-        items = [(name, lig_feats, pose) for name, lig_feats, pose in items]
-        names = [name for name, _, _ in items]
-        if len(set(names)) != len(names):
-            raise ValueError(f'{who}: names must be unique (repeated: '
-                             f'{sorted({n for n in names if names.count(n) > 1})})')
-        ns = []
-        for name, lig_feats, pose in items:
-            n = int(pose.shape[0])
-            if n > MAX_SCREEN_LIGAND_ATOMS:
-                raise ValueError(f'{who}: ligand {name!r} has {n} atoms: a pose-batch slot holds up to '
-                                 f'{MAX_SCREEN_LIGAND_ATOMS}')
-            if pose.dim() != 2 or pose.shape[1] != 3 or lig_feats.dim() != 2 or int(lig_feats.shape[0]) != n:
-                raise ValueError(f'{who}: ligand {name!r}: lig_feats [n, F] and ONE pose [n, 3]')
-            ns.append(n)
-        return items, names, ns
-
-    @torch.no_grad()
+    # ---- attribution of hits: the bodies are in hit_attribution.py ----
     def ligand_atom_masking(self, items, scores_file=None, sigmoid=None, column=0):
         """Atom masking (the reference's attribution_fns.atom_masking, :365-431) of the LIGAND atoms of many complexes
         with this receptor: items = iterable of (name, lig_feats [n,F], pose [n,3]), n <= MAX_SCREEN_LIGAND_ATOMS,
@@ -1332,104 +1305,9 @@ class ScreeningSweep:
         sigmoid where a sweep applies it to that column (`sigmoid` as in `run`; False: raw differences);
         `self.atom_masking_raw[name]` keeps the raw rows [n + 1, C], whole ligand first. scores_file: one line per
         ligand atom, item order then atom order, '{score:.6f} | {receptor} {name}_atom{a}'."""
-        from .predictions import PredictionsWriter
-        items, names, ns = self._checked_hits(items, 'ligand_atom_masking')
-        self.atom_masking_raw = {}
-        if not items:
-            return {}
-        dev = self.rec_pos.device
-        screen = self._library_screen(max(max(ns), 1), 'masking')
-        if screen.reuse and screen._fast is None:
-            # a new screen sizes its edge buffers from its first batch, and the first leave-out batch may hold the
-            # copies of one small ligand: it is shown a batch of the largest whole ligands first (a copy has no more
-            # contacts per atom than its whole ligand)
-            big = sorted(range(len(items)), key=lambda i: -ns[i])[:self.b]
-            screen([(items[i][1], items[i][2]) for i in big])
-            self.batches_run += 1
-        all_pos = torch.cat([pose.to(dev).float() for _, _, pose in items], 0).contiguous()
-        all_feats = torch.cat([lig_feats.to(dev).float() for _, lig_feats, _ in items], 0).contiguous()
-        lig_ptr = torch.tensor([0] + ns).cumsum(0).to(device=dev, dtype=torch.int32)
-        plan = leave_out_plan(ns, self.b)
-        total = sum(ns) + len(ns)
-        firsts = (torch.arange(len(plan), dtype=torch.int32) * self.b).to(dev)     # batch k starts at copy k * b
-        kept = []
-        with self._sweeping(None, sigmoid, None) as sink:
-            for k, batch_sizes in enumerate(plan):
-                screen.load_leave_out(all_pos, all_feats, lig_ptr, batch_sizes, firsts[k:k + 1])
-                kept.append(self._library_step(screen))
-                self.batches_run += 1
-            screen.check()
-            screen.check_leave_out()
-            raw = torch.cat(kept, 0)[:total]
-            if not 0 <= int(column) < raw.shape[1]:
-                raise ValueError(f'ligand_atom_masking: column {column} of {raw.shape[1]} outputs')
-            scored = sink.scored(raw)[:, int(column)]
-        out, at = {}, 0
-        for name, n in zip(names, ns):
-            self.atom_masking_raw[name] = raw[at:at + n + 1]
-            out[name] = scored[at] - scored[at + 1:at + n + 1]
-            at += n + 1
-        if scores_file:
-            with PredictionsWriter(scores_file, 'atom_masking') as writer:
-                if sum(ns):
-                    writer.submit(torch.cat([out[name] for name in names], 0), None, [self.receptor_name] * sum(ns),
-                                  [f'{name}_atom{a}' for name, n in zip(names, ns) for a in range(n)])
-        return out
+        from . import hit_attribution
+        return hit_attribution.ligand_atom_masking(self, items, scores_file, sigmoid, column)
 
-    def _pair_copies(self, items, ns, pairs, counts, ligand_atom, sigmoid):
-        """Every hit's copies - the whole complex, then one per row of its pair table (pairs [K,2] int32 on the device:
-        ligand atom inside the hit or -1, receptor atom; counts: the host's rows per hit) - streamed through the one
-        struck LibraryScreen `self.struck` in dense batches (load_leave_out_pairs: one packer launch per batch, then
-        the one captured step). Returns (raw [K + hits, C], the same with the sweep's sigmoid)."""
-        dev = self.rec_pos.device
-        screen = self._library_screen(max(max(ns), 1), 'struck', struck=True)
-        if screen._fast is None:
-            # a new screen sizes its edge buffers from its first batch: the largest whole ligands (a copy has no more
-            # contacts per atom than its whole complex; the struck rows' room is the screen's own addition)
-            big = sorted(range(len(items)), key=lambda i: -ns[i])[:self.b]
-            screen([(items[i][1], items[i][2]) for i in big])
-            self.batches_run += 1
-        all_pos = torch.cat([pose.to(dev).float() for _, _, pose in items], 0).contiguous()
-        all_feats = torch.cat([lig_feats.to(dev).float() for _, lig_feats, _ in items], 0).contiguous()
-        lig_ptr = torch.tensor([0] + ns).cumsum(0).to(device=dev, dtype=torch.int32)
-        pair_ptr = torch.tensor([0] + list(counts)).cumsum(0).to(device=dev, dtype=torch.int32)
-        plan = leave_out_pair_plan(counts, ns, self.b, ligand_atom=ligand_atom)
-        total = sum(counts) + len(ns)
-        firsts = (torch.arange(len(plan), dtype=torch.int32) * self.b).to(dev)     # batch k starts at copy k * b
-        kept = []
-        with self._sweeping(None, sigmoid, None) as sink:
-            for k, (batch_sizes, n_struck) in enumerate(plan):
-                screen.load_leave_out_pairs(all_pos, all_feats, lig_ptr, pairs, pair_ptr, batch_sizes, n_struck,
-                                            firsts[k:k + 1])
-                kept.append(self._library_step(screen))
-                self.batches_run += 1
-            screen.check()
-            screen.check_leave_out()
-            raw = torch.cat(kept, 0)[:total]
-            return raw, sink.scored(raw)
-
-    @staticmethod
-    def _split_pair_scores(names, counts, raw, scored, column):
-        """({name: raw rows [K + 1, C]}, {name: s(whole) - s(copy k) [K]}) from the copies' rows in copy order."""
-        raws, out, at = {}, {}, 0
-        for name, k in zip(names, counts):
-            raws[name] = raw[at:at + k + 1]
-            out[name] = scored[at, column] - scored[at + 1:at + k + 1, column]
-            at += k + 1
-        return raws, out
-
-    def _hit_contacts(self, items):
-        """(pairs [K,2] int32 on the device, the host's pair counts per hit): PF.contact_pairs of the hits against the
-        receptor at the sweep's edge radius; the whole pair_ptr comes back in the method's one copy to the host."""
-        dev = self.rec_pos.device
-        ns = [int(pose.shape[0]) for _, _, pose in items]
-        all_pos = torch.cat([pose.to(dev).float() for _, _, pose in items], 0).contiguous()
-        lig_ptr = torch.tensor([0] + ns).cumsum(0).to(device=dev, dtype=torch.int32)
-        pairs, _, host_ptr = PF.contact_pairs(all_pos, lig_ptr, self.rec_pos.float().contiguous(), self.edge_radius,
-                                              host_ptr=True)
-        return pairs, [int(k) for k in (host_ptr[1:] - host_ptr[:-1]).tolist()]
-
-    @torch.no_grad()
     def contact_masking(self, items, scores_file=None, sigmoid=None, column=None):
         """Bond masking (the reference's attribution_fns.bond_masking, its default way to rank interactions) of the
         ligand-receptor contacts of many complexes with this receptor: items as for `ligand_atom_masking`. A contact is
@@ -1443,35 +1321,9 @@ class ScreeningSweep:
         (tasks='both': name it). One value per unordered pair (the reference lists a contact once per direction, with
         equal scores). `self.contact_masking_raw[name]`: the raw rows [K + 1, C]. scores_file: one line per contact,
         item order then pair order, '{score:.6f} | {receptor} {name}_atom{a} atom{r}'."""
-        from .predictions import PredictionsWriter
-        items, names, ns = self._checked_hits(items, 'contact_masking')
-        self.contact_masking_raw = {}
-        if column is None and self.tasks == 'both':
-            raise ValueError("contact_masking: with tasks='both' the column must be named (0: pose, 1..: affinity)")
-        if not items:
-            return {}
-        pairs, counts = self._hit_contacts(items)
-        raw, scored = self._pair_copies(items, ns, pairs, counts, True, sigmoid)
-        if column is None:
-            column = 1 if raw.shape[1] > 1 else 0
-        if not 0 <= int(column) < raw.shape[1]:
-            raise ValueError(f'contact_masking: column {column} of {raw.shape[1]} outputs')
-        self.contact_masking_raw, scores = self._split_pair_scores(names, counts, raw, scored, int(column))
-        out, at = {}, 0
-        for name, k in zip(names, counts):
-            out[name] = (pairs[at:at + k], scores[name])
-            at += k
-        if scores_file:
-            with PredictionsWriter(scores_file, 'atom_masking') as writer:
-                if sum(counts):
-                    host = pairs.cpu().tolist()
-                    labels = [f'{name}_atom{a} atom{r}' for name, k, lo in zip(names, counts, _starts(counts))
-                              for a, r in host[lo:lo + k]]
-                    writer.submit(torch.cat([scores[name] for name in names], 0), None,
-                                  [self.receptor_name] * len(labels), labels)
-        return out
+        from . import hit_attribution
+        return hit_attribution.contact_masking(self, items, scores_file, sigmoid, column)
 
-    @torch.no_grad()
     def receptor_atom_masking(self, items, atoms='contacts', scores_file=None, sigmoid=None, column=0):
         """Atom masking (the reference's attribution_fns.atom_masking) of RECEPTOR atoms of many complexes with this
         receptor, through the same struck screen as `contact_masking`: a copy keeps the whole ligand and lacks one
@@ -1480,49 +1332,9 @@ class ScreeningSweep:
         scores [M])} on the device, scores[m] = s(y_whole[column]) - s(y_without_atom_m[column]);
         `self.receptor_atom_masking_raw[name]`: the raw rows [M + 1, C]. scores_file: one line per atom, item order
         then atom order, '{score:.6f} | {receptor} {name} atom{r}'."""
-        from .predictions import PredictionsWriter
-        items, names, ns = self._checked_hits(items, 'receptor_atom_masking')
-        self.receptor_atom_masking_raw = {}
-        if not items:
-            return {}
-        dev, n_rec = self.rec_pos.device, int(self.rec_pos.shape[0])
-        if isinstance(atoms, str) and atoms == 'contacts':
-            pairs, counts = self._hit_contacts(items)
-            hit = torch.repeat_interleave(torch.arange(len(items), device=dev), torch.tensor(counts, device=dev))
-            keys = torch.unique(hit * n_rec + pairs[:, 1].long())         # ascending: by hit, then by receptor atom
-            which = (keys % n_rec).to(torch.int32)
-            counts = torch.bincount(keys // n_rec, minlength=len(items)).tolist()
-        elif isinstance(atoms, str) and atoms == 'all':
-            which = torch.arange(n_rec, dtype=torch.int32, device=dev).repeat(len(items))
-            counts = [n_rec] * len(items)
-        elif torch.is_tensor(atoms) and atoms.dim() == 1 and not atoms.is_floating_point():
-            host = [int(r) for r in atoms.tolist()]
-            if any(not 0 <= r < n_rec for r in host):
-                raise ValueError(f'receptor_atom_masking: atoms must be receptor atoms 0..{n_rec - 1}')
-            which = torch.tensor(host, dtype=torch.int32, device=dev).repeat(len(items))
-            counts = [len(host)] * len(items)
-        else:
-            raise ValueError(f"receptor_atom_masking: atoms={atoms!r}: 'contacts', 'all' or a 1-D index tensor")
-        table = torch.stack([torch.full_like(which, -1), which], 1).contiguous()
-        raw, scored = self._pair_copies(items, ns, table, counts, False, sigmoid)
-        if not 0 <= int(column) < raw.shape[1]:
-            raise ValueError(f'receptor_atom_masking: column {column} of {raw.shape[1]} outputs')
-        self.receptor_atom_masking_raw, scores = self._split_pair_scores(names, counts, raw, scored, int(column))
-        out, at = {}, 0
-        for name, k in zip(names, counts):
-            out[name] = (which[at:at + k], scores[name])
-            at += k
-        if scores_file:
-            with PredictionsWriter(scores_file, 'atom_masking') as writer:
-                if sum(counts):
-                    host = which.cpu().tolist()
-                    labels = [f'{name} atom{r}' for name, k, lo in zip(names, counts, _starts(counts))
-                              for r in host[lo:lo + k]]
-                    writer.submit(torch.cat([scores[name] for name in names], 0), None,
-                                  [self.receptor_name] * len(labels), labels)
-        return out
+        from . import hit_attribution
+        return hit_attribution.receptor_atom_masking(self, items, atoms, scores_file, sigmoid, column)
 
-    @torch.no_grad()
     def receptor_hotspots(self, items, gnn_layer=1, scores_file=None, per_hit=False, attribution='edge_attention',
                           column=None, ligand_scores_file=None):
         """Which receptor atoms the hits of a sweep bind to (the reference's attribution/hotspot.py with its default
@@ -1548,74 +1360,6 @@ class ScreeningSweep:
         (LibraryScreen(cam=...)), which needs neither an attention layer nor the first-layer reuse. Same keys.
         ligand_scores_file: one line per ligand atom of every hit, item order then atom order, '{value:.6f} |
         {receptor} {name}_atom{a}'."""
-        from pathlib import Path
-        from .predictions import PredictionsWriter
-        if attribution not in ('edge_attention', 'cam'):
-            raise ValueError(f"receptor_hotspots: attribution={attribution!r}: 'edge_attention' or 'cam'")
-        by_cam = attribution == 'cam'
-        if column is not None and not by_cam:
-            raise ValueError("receptor_hotspots: column selects a head output of attribution='cam'")
-        items, names, ns = self._checked_hits(items, 'receptor_hotspots')
-        dev, n_rec = self.rec_pos.device, int(self.rec_pos.shape[0])
-        ligand, hit_rows = {}, []
-        lig_key, slot_key = ('lig_val', 'slot_rec_val') if by_cam else ('lig_att', 'slot_rec_att')
-        if items:
-            if by_cam:
-                screen = self._library_screen(max(max(ns), 1), 'cam_screen', cam=True if column is None else int(column))
-            else:
-                screen = self._library_screen(max(max(ns), 1), 'hotspot', contact_attention=gnn_layer)
-            values = screen.cam if by_cam else screen.contact
-            if screen.reuse and screen._fast is None:
-                # (a new screen sizes its edge buffers from its first batch: the largest ligands, as ligand_atom_masking)
-                big = sorted(range(len(items)), key=lambda i: -ns[i])[:self.b]
-                screen([(items[i][1], items[i][2]) for i in big])
-                self.batches_run += 1
-            self._capture_if_wanted(screen)
-            # (behind the sizing batch and the capture's warm-up steps)
-            screen.reset_cam() if by_cam else screen.reset_contact_attention()
-            all_pos = torch.cat([pose.to(dev).float() for _, _, pose in items], 0).contiguous()
-            all_feats = torch.cat([lig_feats.to(dev).float() for _, lig_feats, _ in items], 0).contiguous()
-            n_batches = -(-len(items) // self.b)
-            ptrs = torch.zeros((n_batches, self.b + 1), dtype=torch.int32)
-            for k in range(n_batches):
-                batch_ns = ns[k * self.b:(k + 1) * self.b]
-                ptrs[k, 1:len(batch_ns) + 1] = torch.tensor(batch_ns, dtype=torch.int32)
-            ptrs = ptrs.cumsum(1, dtype=torch.int32)
-            ptrs_dev = ptrs.to(dev)
-            at, lig_rows = 0, []
-            for k in range(n_batches):
-                batch_ns = ns[k * self.b:(k + 1) * self.b]
-                total = sum(batch_ns)
-                screen.load_packed(all_pos[at:at + total], all_feats[at:at + total], ptrs_dev[k], batch_ns)
-                at += total
-                self._library_step(screen)
-                self.batches_run += 1
-                lig_rows.append(values[lig_key][:total].clone())
-                if per_hit:
-                    hit_rows.append(values[slot_key][:len(batch_ns)].clone())
-            screen.check()
-            rec_sum, count, top = (values[key].clone() for key in ('rec_sum', 'rec_count', 'rec_max'))
-            lig_rows, at = torch.cat(lig_rows, 0), 0
-            for name, n in zip(names, ns):
-                ligand[name] = lig_rows[at:at + n]
-                at += n
-        else:
-            rec_sum, count, top = PF.new_contact_accumulators(n_rec, dev)
-        out = dict(mean=rec_sum / count, count=count, max=top, ligand=ligand)      # (0 / 0: NaN)
-        if per_hit:
-            out['per_hit'] = torch.cat(hit_rows, 0) if hit_rows else torch.empty((0, n_rec), dtype=torch.float32,
-                                                                                 device=dev)
-        if scores_file:
-            packed = torch.stack([out['mean'], count.double()], 1).cpu().numpy()      # the one copy to the host
-            atoms = [j for j in range(n_rec) if packed[j, 1] > 0]
-            with PredictionsWriter(scores_file, 'hotspot') as writer:
-                if atoms:
-                    writer.submit(packed[atoms], None, [self.receptor_name] * len(atoms), [f'atom{j}' for j in atoms])
-            Path(scores_file).expanduser().touch()       # (no contact at all: an empty file)
-        if ligand_scores_file:
-            with PredictionsWriter(ligand_scores_file, 'atom_masking') as writer:
-                if sum(ns):
-                    writer.submit(torch.cat([ligand[name] for name in names], 0), None, [self.receptor_name] * sum(ns),
-                                  [f'{name}_atom{a}' for name, n in zip(names, ns) for a in range(n)])
-            Path(ligand_scores_file).expanduser().touch()
-        return out
+        from . import hit_attribution
+        return hit_attribution.receptor_hotspots(self, items, gnn_layer, scores_file, per_hit, attribution, column,
+                                                 ligand_scores_file)

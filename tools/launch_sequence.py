@@ -6,8 +6,9 @@ small two-graph batch. Under a kernel trace, once per library and once more with
     python tools/launch_sequence.py --parse DIR OUT.txt      # one line per launch: name, grid, workgroup, LDS
 Two libraries enqueue the same work when their OUT.txt files are equal (profiles/linear_job_refactor.txt).
 `--screening` traces instead one eager step of each screen (ReceptorScreen on the pose-batch builder and on the filter
-path, LibraryScreen) at a small shape (130-atom receptor, batch of 3): the record that a change of the screens'
-host code left every launch alone (profiles/screening_refactor.txt). `--fp64` runs the loop of the default mode with model
+path, LibraryScreen plain, with struck slots, with contact attention and with cam) at a small shape (130-atom receptor,
+batch of 3): the record that a change of the screens' host code left every launch alone
+(profiles/screening_refactor.txt, profiles/hit_attribution_refactor.txt). `--fp64` runs the loop of the default mode with model
 and batch in double (hidden 16 / 32 / 64, the per-layer path: there is no fp64 stack), for a change of the binding's
 fp64 side (profiles/functional_dtype_refactor.txt)."""
 import csv
@@ -72,10 +73,21 @@ def run_screening():
         screen = ReceptorScreen(model, rec, torch.cat([lig_feats[:n_lig], rec_feats], 0), n_lig, 3, 7.0)
         screen(random_poses(lig[:n_lig], 3, seed=5, max_shift=3.0).cuda())
         screen.check()
+    slots = [(lig_feats[:n].roll(k, 0).contiguous(), random_poses(lig[:n], 1, seed=90 + k, max_shift=3.0)[0])
+             for k, n in enumerate((7, 20, 3))]
     screen = LibraryScreen(model, rec, rec_feats, 3, 20, 7.0)
-    screen([(lig_feats[:n].roll(k, 0).contiguous(), random_poses(lig[:n], 1, seed=90 + k, max_shift=3.0)[0])
-            for k, n in enumerate((7, 20, 3))])
+    screen(slots)
     screen.check()
+    # the branches of the step that attribution adds: struck slots, the first layer's attention, per-node heads
+    torch.manual_seed(4)
+    attending = SartorrasEGNN(tempfile.mkdtemp(), 2e-3, 1e-4, silent=True, **dict(kw, edge_attention=True)).eval()
+    screen = LibraryScreen(model, rec, rec_feats, 3, 20, 7.0, struck=True)
+    screen.load(slots, rec_drop=[-1, 5, 77])()
+    screen.check()
+    for m, extra in ((attending, dict(contact_attention=1)), (model, dict(cam=True))):
+        screen = LibraryScreen(m, rec, rec_feats, 3, 20, 7.0, **extra)
+        screen(slots)
+        screen.check()
     torch.cuda.synchronize()
 
 
