@@ -996,6 +996,8 @@ def dropout_adj(edge_index, edge_attr=None, p=0.5, force_undirected=True, traini
     kept = int(pos[-1])
     out_index = torch.empty((2, 2 * kept), dtype=torch.int64, device=dev)
     out_attr = None if edge_attr is None else torch.empty((2 * kept, n_attr), dtype=torch.int64, device=dev)
+    if kept == 0:             # nothing survived: the empty outputs have no device pointer, which the fill refuses
+        return out_index, out_attr
     _lib.check(lib.pvs_dropout_adj_fill(_lib.ptr(edge_index), _lib.ptr(edge_attr), n_attr, n_edges, _lib.ptr(pos),
                                         kept, _lib.ptr(out_index), _lib.ptr(out_attr), stream),
                'pvs_dropout_adj_fill')

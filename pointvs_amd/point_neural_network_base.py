@@ -92,6 +92,11 @@ class _StepReplayer:
                             'optimisers (torch.optim.Adam bakes a float rate into the captured step)')
         if any(p.dtype == torch.float64 for p in model.parameters()):
             raise NotImplementedError('train_model(capture=True) is fp32 only (fp64 trains eagerly)')
+        if float(getattr(model, 'dropout_p', 0) or 0) > 0:
+            raise NotImplementedError('train_model(capture=True) does not cover edge dropout: the draw reads its survivor '
+                                      'count on the host (illegal inside a capture), and its (seed, step) are by-value '
+                                      'kernel arguments, so every replay would repeat the captured mask '
+                                      '(dropout > 0 trains eagerly)')
         self.model, self.max_graphs = model, max_graphs
         # one side stream per model, kept across calls (AccumulateGrad nodes remember the stream of their first backward)
         if getattr(model, '_capture_stream', None) is None:
@@ -334,7 +339,8 @@ class PointNeuralNetworkBase(nn.Module):
         profiles/r05_real_shape.txt); for BASELINE-size batches it buys nothing. Works with either optimiser the
         constructor builds (Adam, SGD) and under either scheduler (`use_1cycle`, `warm_restarts`): the fused optimisers
         read lr, betas / momentum from device memory, rewritten from the host's values before every replay, so the rates
-        of a captured run are the eager run's. Single process, fp32; anything else raises."""
+        of a captured run are the eager run's. Single process, fp32; anything else raises. Edge dropout (dropout > 0)
+        raises too: its draw reads the survivor count on the host and a replay would repeat the captured mask."""
         init_epoch, _ = self.training_setup(data_loader=data_loader, epochs=epochs)
         if capture:
             replayer = _StepReplayer(self)
