@@ -215,6 +215,21 @@ int pvs_dropout_adj_mark(const int64_t* edge_index, int32_t n_edges, float p, ui
 int pvs_dropout_adj_fill(const int64_t* edge_index, const int64_t* edge_attr, int32_t n_edge_attr,
                          int32_t n_edges, const int32_t* pos, int32_t n_kept, int64_t* out_index,
                          int64_t* out_attr, pvs_stream_t stream);
+/* The same draw for a captured training step: no host read, no by-value key.
+ * key_table: device uint64 [2] = {seed, step}; _key_write sets it from the host (one tiny launch, by value - issue
+ * it OUTSIDE a capture, before each replay). _mark_dev is _mark reading its key there (same flags, scan and stream).
+ * _fill_padded: out_index int64 [2][cap] (row stride cap), out_attr int64 [cap][A], cap even and
+ * >= 2 * #{e : row[e] <= col[e]} (an upper bound of 2K known on the host). With K = pos[E], read on the device:
+ * survivors in [0, K) in input order, their reverses in [K, 2K) - dropout_adj's list - and every slot j in [2K, cap)
+ * a padding edge: d = j - 2K, k = (d / 2) mod (n_pad / 2), a = n_nodes + 2k, b = a + 1; (a, b) for even d, (b, a)
+ * for odd d, attribute row one-hot class 0. n_pad even, >= 2: the padding nodes n_nodes .. n_nodes + n_pad - 1 are
+ * the caller's to provide. Nothing is written when 2K > cap (the bound was wrong; pos[E] tells). */
+int pvs_dropout_key_write(uint64_t* key_table, uint64_t seed, uint64_t step, pvs_stream_t stream);
+int pvs_dropout_adj_mark_dev(const int64_t* edge_index, int32_t n_edges, float p, const uint64_t* key_table,
+                             int32_t* pos, void* workspace, size_t workspace_bytes, pvs_stream_t stream);
+int pvs_dropout_adj_fill_padded(const int64_t* edge_index, const int64_t* edge_attr, int32_t n_edge_attr,
+                                int32_t n_edges, const int32_t* pos, int32_t cap, int32_t n_nodes, int32_t n_pad,
+                                int64_t* out_index, int64_t* out_attr, pvs_stream_t stream);
 
 /* dst[perm[e], :] = src[e, :]  (sorted -> input edge order), width floats per row.
  * Gives EGNNLayer.forward's 4th return value `edge_feat` and `att_val` in the reference's order. */

@@ -92,6 +92,11 @@ _PROTOTYPES = {
                                        C.c_void_p, C.c_size_t, C.c_void_p]),
     'pvs_dropout_adj_fill': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
                                        C.c_void_p, C.c_void_p, C.c_void_p]),
+    'pvs_dropout_key_write': (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
+    'pvs_dropout_adj_mark_dev': (C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_size_t, C.c_void_p]),
+    'pvs_dropout_adj_fill_padded': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                                              C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     'pvs_rows_to_input_order': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                           C.c_void_p]),
     'pvs_rows_to_sorted_order': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
@@ -219,7 +224,7 @@ _PROTOTYPES = {
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)
-MIN_VERSION = 110       # pvs_version() of the library these prototypes describe (110: struck slots, contact pairs)
+MIN_VERSION = 111       # pvs_version() of the library these prototypes describe (111: the captured edge dropout)
 _lib = None
 
 

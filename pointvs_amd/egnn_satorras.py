@@ -565,6 +565,13 @@ class SartorrasEGNN(PNNGeometricBase):
             return edges, edge_attributes
         if int(edges.shape[1]) == 0:          # nothing to draw from (and no device pointer to hand to the library)
             return edges, edge_attributes
+        seed, step = self.next_dropout_key()
+        return PF.dropout_adj(edges, edge_attributes, p, force_undirected=True, training=True, seed=seed, step=step)
+
+    def next_dropout_key(self):
+        """(seed, step) of the next draw, and the draw counted: pure host arithmetic, the one schedule of the eager
+        step, the static-shape step and the captured step (the replayer calls this before every replay and writes
+        the result to the device table the captured draw reads)."""
         # the step of the draw: epochs done (restored from a checkpoint) and optimiser steps taken in this run (+ the
         # calls since the last one, for several forwards per step), so that a resumed run does not replay the masks
         # of its first epoch; the rank goes into the seed, so that data-parallel ranks do not drop the same edge
@@ -580,8 +587,20 @@ class SartorrasEGNN(PNNGeometricBase):
         # (epochs, optimiser steps, calls) -> ONE 64-bit step by a mix, not by packing bit fields (with
         # fields, more than 255 forwards under one base - a loop that never bumps global_iter - carried into the next
         # base's range, and 2^24 optimiser steps into the epoch field: masks could repeat)
-        return PF.dropout_adj(edges, edge_attributes, p, force_undirected=True, training=True,
-                              seed=seed, step=_mix64(_mix64(int(base)) + self._dropout_calls))
+        return seed, _mix64(_mix64(int(base)) + self._dropout_calls)
+
+    def push_dropout_key(self, device):
+        """The next key of the schedule into the model's device table {seed, step}, on the current stream: what the
+        static-shape draw (PF.dropout_adj_padded) reads when it runs. A launch with by-value arguments, so outside any
+        capture. Returns (seed, step)."""
+        table = self.__dict__.get('_dropout_table')
+        if table is None or table.device != torch.device(device):
+            table = self.__dict__['_dropout_table'] = torch.zeros(2, dtype=torch.int64, device=device)
+        key = self.next_dropout_key()
+        PF.write_dropout_key(table, *key)
+        self.__dict__['_dropout_key'] = key
+        self.__dict__['_dropout_key_fresh'] = True      # (consumed by the one forward a replayer's step takes)
+        return key
 
     def embed_prepared(self, pg, feats, coords, need_messages=False, trace=None, need_coords=True):
         """Layer stack on a PreparedGraph. Edge messages stay in sorted order between layers and

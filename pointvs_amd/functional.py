@@ -4,6 +4,7 @@ PyTorch supplies device memory, the current stream and the autograd tape; every 
 of the path runs in libpvs_egnn.so.
 """
 import ctypes as C
+import math
 
 import torch
 
@@ -1002,3 +1003,82 @@ def dropout_adj(edge_index, edge_attr=None, p=0.5, force_undirected=True, traini
                                         kept, _lib.ptr(out_index), _lib.ptr(out_attr), stream),
                'pvs_dropout_adj_fill')
     return out_index, out_attr
+
+
+def static_dropout_plan(n_nodes, n_half, p):
+    """(cap, n_pad) of the fixed-shape dropped edge list of a batch with `n_nodes` nodes whose list has `n_half` edges
+    with row <= col (the candidates of the draw; a self-loop survives twice, as in dropout_adj). Pure host arithmetic.
+    cap = 2 * n_half holds every draw. n_pad = 2 * max(1, ceil(p * n_nodes / 2)) padding nodes: a draw leaves about
+    p * cap slots empty, which are spread over n_pad rows, so a padding row then has about the batch's mean degree
+    (cap / n_nodes) and balances like any other row - all dead slots on ONE pair of rows would serialise a launch on
+    one wave."""
+    n_nodes, n_half, p = int(n_nodes), int(n_half), float(p)
+    if n_nodes < 0 or n_half < 0 or not 0.0 <= p < 1.0:
+        raise ValueError(f'static_dropout_plan({n_nodes}, {n_half}, {p}): counts >= 0 and p in [0, 1)')
+    return 2 * n_half, 2 * max(1, math.ceil(p * n_nodes / 2))
+
+
+def dropout_key_table(device, seed=0, step=0):
+    """Device table {seed, step} (two 64-bit words, held as int64 bits) that dropout_adj_padded draws from."""
+    table = torch.zeros(2, dtype=torch.int64, device=device)
+    write_dropout_key(table, seed, step)
+    return table
+
+
+def write_dropout_key(key_table, seed, step):
+    """key_table <- (seed, step) on the current stream, by a launch with by-value arguments: NOT inside a capture (a
+    replay would write the captured key back)."""
+    _lib.require_hip(key_table)
+    if key_table.dtype != torch.int64 or key_table.numel() != 2:
+        raise ValueError('the dropout key table is an int64 tensor of two words')
+    _lib.check(_lib.lib().pvs_dropout_key_write(_lib.ptr(key_table), int(seed) & (2 ** 64 - 1),
+                                                int(step) & (2 ** 64 - 1), _lib.stream(key_table.device)),
+               'pvs_dropout_key_write')
+
+
+def dropout_adj_padded(edge_index, edge_attr, p, key_table, cap, n_nodes, n_pad, out=None):
+    """dropout_adj(force_undirected=True, training=True) with a fixed output shape, for a captured training step: no
+    host read, and the key (seed, step) comes from `key_table` (dropout_key_table / write_dropout_key) when the
+    kernels RUN. Returns (out_index [2, cap], out_attr [cap, A] or None, n_kept: device int32 scalar K). The first 2K
+    columns are dropout_adj's list for the table's key; every slot behind them is an edge between two of the `n_pad`
+    padding nodes n_nodes .. n_nodes + n_pad - 1, both directions in turn, attribute row one-hot class 0
+    (pvs_dropout_adj_fill_padded). cap: even, at least twice the number of row <= col edges (static_dropout_plan; 2 E
+    always suffices) - a smaller one leaves the outputs unwritten, and n_kept tells. out = (out_index, out_attr):
+    buffers of those shapes to write into."""
+    _lib.require_hip(edge_index, edge_attr, key_table)
+    if not 0.0 <= float(p) < 1.0:
+        raise ValueError(f'dropout probability {p} not in [0, 1)')
+    cap, n_nodes, n_pad = int(cap), int(n_nodes), int(n_pad)
+    if cap < 0 or cap % 2 or n_pad < 2 or n_pad % 2:
+        raise ValueError(f'cap={cap} must be even and >= 0, n_pad={n_pad} even and >= 2')
+    if key_table.dtype != torch.int64 or key_table.numel() != 2:
+        raise ValueError('the dropout key table is an int64 tensor of two words')
+    lib = _lib.lib()
+    edge_index = edge_index.long().contiguous()
+    n_edges = int(edge_index.shape[1])
+    dev = edge_index.device
+    n_attr = 0
+    if edge_attr is not None:
+        edge_attr = edge_attr.long().contiguous()
+        n_attr = int(edge_attr.shape[1])
+    if out is None:
+        out_index = torch.empty((2, cap), dtype=torch.int64, device=dev)
+        out_attr = None if edge_attr is None else torch.empty((cap, n_attr), dtype=torch.int64, device=dev)
+    else:
+        out_index, out_attr = out
+        if (out_index.dtype != torch.int64 or tuple(out_index.shape) != (2, cap) or (out_attr is None) != (edge_attr is None)
+                or (out_attr is not None and (out_attr.dtype != torch.int64 or tuple(out_attr.shape) != (cap, n_attr)))):
+            raise ValueError(f'out must be int64 buffers of shape (2, {cap}) and ({cap}, {n_attr})')
+        _lib.require_hip(out_index, out_attr)
+    stream = _lib.stream(dev)
+    pos = torch.empty(n_edges + 1, dtype=torch.int32, device=dev)
+    ws_bytes = lib.pvs_dropout_adj_workspace_bytes(n_edges)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    _lib.check(lib.pvs_dropout_adj_mark_dev(_lib.ptr(edge_index) if n_edges else None, n_edges, float(p),
+                                            _lib.ptr(key_table), _lib.ptr(pos), _lib.ptr(ws), ws_bytes, stream),
+               'pvs_dropout_adj_mark_dev')
+    _lib.check(lib.pvs_dropout_adj_fill_padded(
+        _lib.ptr(edge_index) if n_edges else None, _lib.ptr(edge_attr) if n_edges else None, n_attr, n_edges,
+        _lib.ptr(pos), cap, n_nodes, n_pad, _lib.ptr(out_index) if cap else None,
+        _lib.ptr(out_attr) if cap and out_attr is not None else None, stream), 'pvs_dropout_adj_fill_padded')
+    return out_index, out_attr, pos[n_edges]

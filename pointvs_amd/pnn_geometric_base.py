@@ -14,7 +14,7 @@ from torch import nn
 
 from . import functional as PF
 from .global_objects import DEVICE
-from .graph import prepared_for, runs_layout
+from .graph import prepare_graph, prepared_for, runs_layout
 from .point_neural_network_base import PointNeuralNetworkBase
 
 
@@ -42,9 +42,10 @@ class PNNGeometricBase(PointNeuralNetworkBase):
         w = getattr(getattr(embed, 'm', None), 'weight', None)
         return torch.float32 if w is None else w.dtype
 
-    def _embed_graph(self, graph):
+    def _graph_inputs(self, graph):
+        """The batch as the layer stack takes it: (feats, edges, coords, edge_attributes, n_graphs, graph_ptr: device
+        int32 node offsets, layout, pg: the PreparedGraph of a graph built on the GPU or None)."""
         feats, edges, coords, edge_attributes, batch = self.unpack_graph(graph)
-        n_nodes = feats.size(0)
         n_graphs = getattr(graph, 'num_graphs', None)
         if n_graphs is None:  # the reference syncs here too (torch.max(batch), :27)
             n_graphs = int(batch.max()) + 1
@@ -66,7 +67,15 @@ class PNNGeometricBase(PointNeuralNetworkBase):
                 if hasattr(graph, '__dict__'):
                     graph.__dict__['_pvs_ptr32'] = (ptr, ptr._version, graph_ptr)
         pg = getattr(graph, 'prepared', None)     # built on the GPU (radius_graph.attach_radius_graph)
+        return feats, edges, coords, edge_attributes, n_graphs, graph_ptr, layout, pg
+
+    def _embed_graph(self, graph):
+        feats, edges, coords, edge_attributes, n_graphs, graph_ptr, layout, pg = self._graph_inputs(graph)
+        n_nodes = feats.size(0)
         dropping = self.training and float(getattr(self, 'dropout_p', 0.0) or 0.0) > 0.0
+        if (dropping and getattr(self, 'static_dropout', None)
+                and (pg.n_edges if pg is not None else int(edges.shape[1])) > 0):
+            return self._embed_graph_static_dropout(graph, feats, edges, coords, edge_attributes, pg, graph_ptr, n_graphs)
         if dropping:      # edge dropout ahead of the layer stack (egnn_satorras.py:320-323): a new edge list
             if pg is not None:    # graph built on the GPU: its sorted list back as the COO the dropout draws from
                 e = pg.n_edges
@@ -82,11 +91,114 @@ class PNNGeometricBase(PointNeuralNetworkBase):
         feats, _, _ = self.embed_prepared(pg, feats, coords, need_coords=False)
         return feats, pg, graph_ptr, n_graphs
 
+    # ---- edge dropout with a fixed-shape edge list (model.static_dropout; captured training turns it on) ----
+    # None / False: the draw sizes its output by its result (one host read per step), today's path bit for bit.
+    # True, while training with dropout > 0: the dropped list always has cap = 2 * #{row <= col} columns; the slots a
+    # draw leaves empty hold edges between n_pad padding nodes appended behind the batch's own (features zero, the two
+    # nodes of a pair 1 A apart), which pooling and heads never see: feats[:N] goes on, autograd's slice hands the
+    # padding rows a zero gradient, so every padding edge contributes exact zeros to the weight gradients. Not for
+    # GraphNorm models (the statistics run over all rows of the batch, padding included): the step raises.
+    static_dropout = None
+
+    def plan_static_dropout(self, graph):
+        """static_dropout_state of a batch, ahead of the step that needs it (the replayer: _make_capturable). A batch
+        without edges has no plan (its step takes the eager path, which then draws nothing)."""
+        feats, edges, _, edge_attributes, n_graphs, graph_ptr, _, pg = self._graph_inputs(graph)
+        if (pg.n_edges if pg is not None else int(edges.shape[1])) == 0:
+            return None
+        return self.static_dropout_state(graph, feats, edges, edge_attributes, pg, graph_ptr, n_graphs)
+
+    def static_dropout_state(self, graph, feats, edges, edge_attributes, pg, graph_ptr, n_graphs):
+        """What the static-shape draw needs of one batch object, computed ONCE, outside any capture, and left on the
+        batch: the COO list the draw numbers (a graph built on the GPU: its sorted list), n_half = #{row <= col} (the
+        one host read), (cap, n_pad) = PF.static_dropout_plan, the static output buffers, the padding rows and the node
+        offsets extended by the padding block [..., N, N + n_pad] - a graph of its own for PvsGraph.graph_eptr, so
+        tiles of the fp16-split backward end before it - and, for a batch of one graph, the offsets [0, N] the pooling
+        shortcut reads (_whole_ptr). Whoever captures a step on these tensors keeps the state (the replayer does)."""
+        n_nodes, p = int(feats.size(0)), float(self.dropout_p)
+        source = pg if pg is not None else edges
+        key = (None if pg is not None else (edges.data_ptr(), edges._version, tuple(edges.shape)),
+               None if pg is not None or edge_attributes is None else (edge_attributes.data_ptr(), edge_attributes._version),
+               n_nodes, p, feats.dtype, feats.device, int(feats.size(1)), n_graphs)
+        holder = getattr(graph, '__dict__', None)
+        state = None if holder is None else holder.get('_pvs_static_dropout')
+        if state is not None and state['source'] is source and state['key'] == key:
+            return state
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('static edge dropout: the batch has no plan yet and counting its row <= col edges is a host '
+                               'read, which a capture cannot hold (visit the batch once outside the capture)')
+        if pg is not None:    # graph built on the GPU: its sorted list back as the COO the dropout draws from
+            e = pg.n_edges
+            edges = torch.stack([pg.t['row'][:e].long(), pg.t['col'][:e].long()])
+            edge_attributes = (None if pg.n_edge_attr == 0 else
+                               torch.nn.functional.one_hot(pg.t['etype'][:e].long(), pg.n_edge_attr))
+        edges = edges.long().contiguous()
+        if edge_attributes is not None:
+            edge_attributes = edge_attributes.long().contiguous()
+        n_half = int((edges[0] <= edges[1]).sum())
+        cap, n_pad = PF.static_dropout_plan(n_nodes, n_half, p)
+        dev = feats.device
+        pad_coords = torch.zeros((n_pad, 3), dtype=feats.dtype, device=dev)     # (unpack_graph: one dtype)
+        pad_coords[1::2, 0] = 1.0
+        node_ptr = torch.cat([graph_ptr.to(device=dev, dtype=torch.long),
+                              torch.tensor([n_nodes + n_pad], dtype=torch.long, device=dev)])
+        node_ptr._pvs_as_long = node_ptr
+        whole = None
+        if n_graphs == 1:
+            whole = torch.tensor([0, n_nodes], dtype=torch.int32, device=dev)
+            whole._pvs_whole = n_nodes
+        state = dict(
+            source=source, key=key, edges=edges, attrs=edge_attributes, n_half=n_half, cap=cap, n_pad=n_pad,
+            out_index=torch.empty((2, cap), dtype=torch.int64, device=dev),
+            out_attr=(None if edge_attributes is None else
+                      torch.empty((cap, int(edge_attributes.shape[1])), dtype=torch.int64, device=dev)),
+            pad_feats=torch.zeros((n_pad, int(feats.size(1))), dtype=feats.dtype, device=dev), pad_coords=pad_coords,
+            node_ptr=node_ptr, whole=whole)
+        if holder is not None:
+            holder['_pvs_static_dropout'] = state
+        return state
+
+    def _embed_graph_static_dropout(self, graph, feats, edges, coords, edge_attributes, pg, graph_ptr, n_graphs):
+        if any(getattr(layer, 'graphnorm', False) for layer in self.layers):
+            raise NotImplementedError('static_dropout does not cover a model with GraphNorm: the norm runs over every row '
+                                      'of the batch, so the padding rows of the fixed-shape edge dropout would enter its '
+                                      'statistics (leave static_dropout off: the eager draw has no padding)')
+        n_nodes = int(feats.size(0))
+        st = self.static_dropout_state(graph, feats, edges, edge_attributes, pg, graph_ptr, n_graphs)
+        if not self.__dict__.get('_dropout_key_external'):     # (a replayer writes the key itself, outside its captures)
+            self.push_dropout_key(feats.device)
+        elif not self.__dict__.pop('_dropout_key_fresh', False):
+            raise RuntimeError('static edge dropout under a replayer: a second training forward within one step would '
+                               'draw the first one\'s mask again (the replayer writes one key per step)')
+        seed, step = self._dropout_key
+        out_index, out_attr, n_kept = PF.dropout_adj_padded(
+            st['edges'], st['attrs'], float(self.dropout_p), self._dropout_table, st['cap'], n_nodes, st['n_pad'],
+            out=(st['out_index'], st['out_attr']))
+        # prepare_graph, never prepared_for's cache: the static buffers are written through raw pointers, their tensor
+        # _version never moves, and the cache would hand back the graph of an earlier draw
+        dropped = prepare_graph(out_index, out_attr, n_nodes + st['n_pad'])
+        dropped.poll_status()
+        dropped.set_graph_ptr(st['node_ptr'])
+        h, _, _ = self.embed_prepared(dropped, torch.cat([feats, st['pad_feats']]),
+                                      torch.cat([coords, st['pad_coords']]), need_coords=False)
+        self.last_dropout = dict(seed=seed, step=step, cap=st['cap'], n_pad=st['n_pad'], n_kept=n_kept,
+                                 out_index=out_index, out_attr=out_attr)
+        return h[:n_nodes], dropped, graph_ptr if st['whole'] is None else st['whole'], n_graphs
+
     @staticmethod
-    def _pool(feats, graph_ptr, n_graphs):
+    def _whole_ptr(feats, graph_ptr):
+        """[0, N] as device int32: the node offsets of a batch of one graph. The static-dropout path hands over the
+        tensor it keeps with the batch's plan (tagged with its N: static_dropout_state), so that a captured step reads
+        offsets that live as long as the batch does; every other caller gets a fresh tensor per call."""
+        if getattr(graph_ptr, '_pvs_whole', None) == feats.size(0) and graph_ptr.device == feats.device:
+            return graph_ptr
+        return torch.tensor([0, feats.size(0)], dtype=torch.int32, device=feats.device)
+
+    @classmethod
+    def _pool(cls, feats, graph_ptr, n_graphs):
         """global_mean_pool, or plain mean over nodes for a single graph (:29-33)."""
         if n_graphs == 1:
-            whole = torch.tensor([0, feats.size(0)], dtype=torch.int32, device=feats.device)
+            whole = cls._whole_ptr(feats, graph_ptr)
             return PF.mean_pool(feats, whole).reshape(-1)
         return PF.mean_pool(feats, graph_ptr)
 
@@ -107,7 +219,7 @@ class PNNGeometricBase(PointNeuralNetworkBase):
                 or os.environ.get('PVS_FUSED_HEAD') == '0'):       # (=0: the two ops apart, for A/B)
             return cls._run_head(head, cls._pool(feats, graph_ptr, n_graphs))
         if n_graphs == 1:
-            whole = torch.tensor([0, feats.size(0)], dtype=torch.int32, device=feats.device)
+            whole = cls._whole_ptr(feats, graph_ptr)
             out = PF.pool_head(feats, whole, mods[0].weight, mods[0].bias).reshape(-1)
         else:
             out = PF.pool_head(feats, graph_ptr, mods[0].weight, mods[0].bias)

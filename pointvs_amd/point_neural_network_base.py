@@ -76,7 +76,11 @@ class _StepReplayer:
     the fused optimisers' kernels read it from device memory, and step() has the groups' current values written there
     (`push_hyperparameters`, on the replayer's stream) before the capture and before every replay - an eager step does
     that itself. `scheduler.step()` stays on the host, after the optimiser step (_train_epochs): a captured run's
-    rates are the eager run's, double for double."""
+    rates are the eager run's, double for double.
+    Edge dropout is handled the same way: for the replayer's lifetime the model draws into an edge list of fixed shape
+    (`static_dropout`: PNNGeometricBase._embed_graph_static_dropout), keyed from a device table {seed, step} that step()
+    rewrites from the model's own schedule (`next_dropout_key`) before every step - a captured run draws the masks of the
+    same run taken eagerly with static_dropout on. Models with GraphNorm and dropout are refused."""
 
     def __init__(self, model, max_graphs=64):
         if not torch.cuda.is_available():
@@ -92,11 +96,13 @@ class _StepReplayer:
                             'optimisers (torch.optim.Adam bakes a float rate into the captured step)')
         if any(p.dtype == torch.float64 for p in model.parameters()):
             raise NotImplementedError('train_model(capture=True) is fp32 only (fp64 trains eagerly)')
-        if float(getattr(model, 'dropout_p', 0) or 0) > 0:
-            raise NotImplementedError('train_model(capture=True) does not cover edge dropout: the draw reads its survivor '
-                                      'count on the host (illegal inside a capture), and its (seed, step) are by-value '
-                                      'kernel arguments, so every replay would repeat the captured mask '
-                                      '(dropout > 0 trains eagerly)')
+        self._dropout = float(getattr(model, 'dropout_p', 0) or 0) > 0
+        if self._dropout and any(getattr(m, 'graphnorm', False) for m in model.modules()):
+            raise NotImplementedError('train_model(capture=True) does not cover edge dropout in a model with GraphNorm: a '
+                                      'captured step draws into an edge list of fixed shape whose unused slots join '
+                                      'padding nodes appended to the batch, and GraphNorm normalises over every row of the '
+                                      'batch, so the padding rows would enter its statistics (dropout > 0 with GraphNorm '
+                                      'trains eagerly; without GraphNorm it is captured)')
         self.model, self.max_graphs = model, max_graphs
         # one side stream per model, kept across calls (AccumulateGrad nodes remember the stream of their first backward)
         if getattr(model, '_capture_stream', None) is None:
@@ -121,10 +127,29 @@ class _StepReplayer:
         model.optimiser._fast = None
         if hasattr(model.optimiser, 'reserve_capture_tables'):
             model.optimiser.reserve_capture_tables(max_graphs)
+        # edge dropout: the static-shape draw for the replayer's lifetime (eager visits too: one arithmetic for every
+        # step of the run), keyed from the model's device table, which step() rewrites before every step
+        self._static_was = (model.__dict__.get('static_dropout', None), 'static_dropout' in model.__dict__)
+        if self._dropout:
+            model.static_dropout = True
+            model.__dict__['_dropout_key_external'] = True
+
+    def _push_dropout_key(self):
+        """The key the eager step would draw with now (the model's own schedule), into the device table the captured
+        draw reads: on the replayer's stream, outside the capture - as push_hyperparameters does for the rates."""
+        if self._dropout and self.model.training:
+            return self.model.push_dropout_key(next(self.model.parameters()).device)
+        return None
 
     def close(self):
         torch.cuda.current_stream(DEVICE).wait_stream(self.stream)
         self.graphs.clear()
+        if self._dropout:
+            self.model.__dict__.pop('_dropout_key_external', None)
+            if self._static_was[1]:
+                self.model.static_dropout = self._static_was[0]
+            else:
+                self.model.__dict__.pop('static_dropout', None)
         opt = self.model.optimiser
         if self._sgd_was is not None:
             opt.capturable = self._sgd_was
@@ -167,9 +192,11 @@ class _StepReplayer:
         return self.model.backprop(y_true, y_pred, sync=False)
 
     @staticmethod
-    def _make_capturable(graph):
+    def _make_capturable(graph, model=None):
         """What the forward would otherwise derive from the batch vector with data-dependent ops (a bincount, a
-        maximum read on the host): done once, outside any capture, and left on the batch object."""
+        maximum read on the host): done once, outside any capture, and left on the batch object. With a model that
+        draws its edge dropout into a fixed shape, the draw's plan as well (plan_static_dropout: its count of
+        row <= col edges is the one host read of that path)."""
         batch = getattr(graph, 'batch', None)
         if batch is None:
             return
@@ -178,22 +205,28 @@ class _StepReplayer:
         if getattr(graph, 'ptr', None) is None:
             counts = torch.bincount(batch, minlength=graph.num_graphs)
             graph.ptr = torch.cat([counts.new_zeros(1), counts.cumsum(0)])
+        if model is not None and model.training and getattr(model, 'static_dropout', None) \
+                and float(getattr(model, 'dropout_p', 0) or 0) > 0:
+            model.plan_static_dropout(graph)
 
     def step(self, graph):
         from . import graph as pgraph
         key = self._key(graph, self.model.model_task)
         hit = self.graphs.get(key) if key is not None else None
+        drawn = self._push_dropout_key()      # (every step of the run advances the schedule once, as the eager loop does)
         if hit is not None:
             if self._push is not None:
                 self._push()
             hit[0].replay()
             self.stats['replayed'] += 1
+            if hit[3] is not None and drawn is not None:      # the captured step's buffers, drawn with this step's key
+                self.model.last_dropout = dict(hit[3], seed=drawn[0], step=drawn[1])
             return hit[1].clone()
         visits = self.seen.get(key, 0) if key is not None else 0
         if key is None or visits == 0 or len(self.graphs) >= self.max_graphs:
             if key is not None:
                 self.seen[key] = visits + 1
-                self._make_capturable(graph)
+                self._make_capturable(graph, self.model)
             self.stats['eager'] += 1
             return self._eager(graph)
         # second visit: capture. The batch's CSR / CSC preparation is captured too (its tensors then live in the
@@ -204,11 +237,15 @@ class _StepReplayer:
             if self._push is not None:
                 self._push()                 # (outside the capture: what the replay just below runs at)
             hip_graph = torch.cuda.CUDAGraph()
+            self.model.__dict__.pop('last_dropout', None)
             with torch.cuda.graph(hip_graph, stream=self.stream):
                 static_loss = self._eager(graph)
         finally:
             pgraph.CACHE_ENABLED = cache_was
-        self.graphs[key] = (hip_graph, static_loss, graph)      # (holds the batch: its addresses stay unique)
+        # (holds the batch: its addresses stay unique; the captured draw's buffers, which every replay rewrites; and the
+        # batch's dropout plan, whose tensors the captured launches read - a plan replaced on the batch later stays alive)
+        self.graphs[key] = (hip_graph, static_loss, graph, self.model.__dict__.get('last_dropout') if self._dropout else None,
+                            getattr(graph, '__dict__', {}).get('_pvs_static_dropout') if self._dropout else None)
         hip_graph.replay()
         self.stats['captured'] += 1
         return static_loss.clone()
@@ -340,7 +377,10 @@ class PointNeuralNetworkBase(nn.Module):
         constructor builds (Adam, SGD) and under either scheduler (`use_1cycle`, `warm_restarts`): the fused optimisers
         read lr, betas / momentum from device memory, rewritten from the host's values before every replay, so the rates
         of a captured run are the eager run's. Single process, fp32; anything else raises. Edge dropout (dropout > 0)
-        raises too: its draw reads the survivor count on the host and a replay would repeat the captured mask."""
+        is captured with a fixed-shape draw (`static_dropout`, on for the duration: the dropped list padded to its
+        capacity with inert edges between padding nodes, the key read from a device table that is rewritten before every
+        replay - the masks are those of the same run with capture=False and static_dropout=True); a model with GraphNorm
+        and dropout raises, since the padding rows would enter the norm's statistics."""
         init_epoch, _ = self.training_setup(data_loader=data_loader, epochs=epochs)
         if capture:
             replayer = _StepReplayer(self)
