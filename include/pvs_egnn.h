@@ -88,7 +88,20 @@ typedef struct PvsGraph {
      * pvs_graph_prepare_runs (edge_ptr IS this table). */
     const int32_t* graph_eptr;
     int32_t n_graphs;
+    /* Optional DEVICE int32: the number of LEADING rows that enter GraphNorm's statistics when it is only known on the
+     * device (a padded, captured step: the real nodes in front, padding rows behind them). NULL: n_nodes. Read by the
+     * fp32 layer entry points under PVS_GRAPHNORM (pvs_egnn_layer_fwd / _fwd_partial / _fwd_partial_att / _bwd and
+     * pvs_egnn_stack_fwd / _bwd), ignored without that flag, refused by the *_f64 entry points. With n = the value
+     * clamped to [0, n_nodes]: mean and variance are those of rows [0, n) - bit for bit the statistics of a call on
+     * those n rows alone -, rows >= n are never read for them, ALL n_nodes rows are normalised with them, and the
+     * backward is the exact gradient of that (with zero upstream gradient on the rows >= n: the gradient of the n-row
+     * problem). n = 0: mean = var = 0, rstd = 1 / sqrt(eps); nothing is divided by n.
+     * ABI (pvs_version() >= 112): sizeof(PvsGraph) = 104, offsetof(PvsGraph, n_norm_rows_dev) = 96. */
+    const int32_t* n_norm_rows_dev;
 } PvsGraph;
+#if defined(__cplusplus)
+static_assert(sizeof(PvsGraph) == 104 && offsetof(PvsGraph, n_norm_rows_dev) == 96, "PvsGraph layout (pointvs_amd/_lib.py)");
+#endif
 
 /* Parameters of one EGNNLayer, torch nn.Linear layout W[out][in] (state_dict keys in comments). */
 typedef struct PvsLayerParams {
@@ -491,6 +504,17 @@ int pvs_egnn_stack_bwd(const PvsLayerDesc* descs, const PvsLayerParams* params, 
                        const float* h_mid, const float* x_mid, const float* att, const float* saved,
                        const float* g_h_out, const float* g_x_out, float* g_h0, float* g_x0,
                        const PvsLayerGrads* grads, void* workspace, size_t workspace_bytes, pvs_stream_t stream);
+
+/* GraphNorm's statistics as an operator (torch_geometric GraphNorm called without a batch vector, egnn_satorras.py:120):
+ * stats[0:H] = mean_c over the rows of y1 [n_rows_cap, H], stats[H:2H] = mean_c of (y1 - mean_scale * mean)^2.
+ * n_rows_dev NULL: over all n_rows_cap rows (>= 1), the launches a layer makes for a graph without
+ * PvsGraph.n_norm_rows_dev. Otherwise a DEVICE int32 n, clamped to [0, n_rows_cap]: over the first n rows, as described at
+ * that member (rows >= n never read, n = 0 gives zeros, n >= 1 the bits of the NULL call on n rows). H <= 256.
+ * No atomics; the same bits every call. */
+size_t pvs_graphnorm_stats_rows_workspace_bytes(int32_t n_rows_cap, int32_t H);
+int pvs_graphnorm_stats_rows(const float* y1, const float* mean_scale, int32_t n_rows_cap, int32_t H,
+                             const int32_t* n_rows_dev /* or NULL: n_rows_cap */, float* stats /* [2H] */,
+                             void* workspace, size_t workspace_bytes, pvs_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * The thin callers either side of the layer stack.

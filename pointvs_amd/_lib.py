@@ -28,7 +28,11 @@ class PvsGraph(C.Structure):
                 ('row', C.c_void_p), ('col', C.c_void_p), ('etype', C.c_void_p),
                 ('perm', C.c_void_p), ('colptr', C.c_void_p), ('cedge', C.c_void_p),
                 ('inv_deg', C.c_void_p), ('n_edges_dev', C.c_void_p), ('graph_eptr', C.c_void_p),
-                ('n_graphs', C.c_int32)]
+                ('n_graphs', C.c_int32), ('n_norm_rows_dev', C.c_void_p)]
+
+
+# sizeof(PvsGraph) and offsetof(PvsGraph, n_norm_rows_dev) as include/pvs_egnn.h states (and static_asserts) them
+PVS_GRAPH_SIZEOF, PVS_GRAPH_NORM_ROWS_OFFSET = 104, 96
 
 
 class PvsLayerParams(C.Structure):
@@ -156,6 +160,9 @@ _PROTOTYPES = {
     'pvs_egnn_stack_bwd': (C.c_int, [C.POINTER(PvsLayerDesc), C.POINTER(PvsLayerParams), C.c_int32, C.POINTER(PvsGraph),
                                      C.POINTER(PvsStackStrides)] + [C.c_void_p] * 10 +
                            [C.POINTER(PvsLayerGrads), C.c_void_p, C.c_size_t, C.c_void_p]),
+    'pvs_graphnorm_stats_rows_workspace_bytes': (C.c_size_t, [C.c_int32, C.c_int32]),
+    'pvs_graphnorm_stats_rows': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_size_t, C.c_void_p]),
     'pvs_linear_fwd': (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 3 + [C.c_void_p]),
     'pvs_linear_bwd_workspace_bytes': (C.c_size_t, [C.c_int32] * 3),
     'pvs_linear_bwd': (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 3 + [C.c_void_p, C.c_size_t,
@@ -224,7 +231,7 @@ _PROTOTYPES = {
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)
-MIN_VERSION = 111       # pvs_version() of the library these prototypes describe (111: the captured edge dropout)
+MIN_VERSION = 112       # pvs_version() of the library these prototypes describe (112: GraphNorm over a device row count)
 _lib = None
 
 

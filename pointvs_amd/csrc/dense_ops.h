@@ -100,6 +100,12 @@ enum { PVS_COL_SUM_A = 0, PVS_COL_SUM_AB = 1, PVS_COL_SUMSQ_SHIFT = 2 };
 int pvs_launch_colreduce(hipStream_t s, int mode, float* out, const float* A, int lda, const float* B,
                          int ldb, const float* shift, int N, int C, float scale, float* slabs,
                          bool accumulate);
+// out[c] = (1 / n) sum_{r < n} f(A[r*lda+c] | shift[c]) with n = clamp(*n_rows_dev, 0, n_cap) read on the DEVICE (a
+// captured, padded step knows its real row count only there). mode: PVS_COL_SUM_A or PVS_COL_SUMSQ_SHIFT; C <= 256.
+// For n >= 1 the bits of pvs_launch_colreduce(..., N = n, scale = 1.0f / (float)n): same row split, same slab order,
+// same quotient. Rows >= n are never read; n = 0 gives zeros. slabs: pvs_colreduce_blocks(n_cap) * C floats.
+int pvs_launch_colmean_rows(hipStream_t s, int mode, float* out, const float* A, int lda, const float* shift,
+                            int n_cap, const int32_t* n_rows_dev, int C, float* slabs);
 
 // out[map(o)] (=|+=) sum_g slabs[g*width + o], o < width; map(o) = (o / inner) * ldo + o % inner
 int pvs_launch_reduce_slabs(hipStream_t s, float* out, int ldo, int inner, const float* slabs,

@@ -96,10 +96,10 @@ k_tsgemm_tn(float* __restrict__ slabs, const float* __restrict__ A, int lda,
     }
 }
 
-__global__ void __launch_bounds__(kThreads)
-k_colreduce(int mode, float* __restrict__ slabs, const float* __restrict__ A, int lda,
-            const float* __restrict__ B, int ldb, const float* __restrict__ shift, int N, int C,
-            int rows_per_block) {
+__device__ __forceinline__ void
+colreduce_block(int mode, float* __restrict__ slabs, const float* __restrict__ A, int lda,
+                const float* __restrict__ B, int ldb, const float* __restrict__ shift, int N, int C,
+                int rows_per_block) {
     __shared__ float part[kThreads];
     const int tid = threadIdx.x;
     const int R = kThreads / C;          // row lanes per column (C <= 256)
@@ -176,6 +176,135 @@ k_colreduce4(int mode, float* __restrict__ slabs, const float* __restrict__ A, i
             s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
         }
         *reinterpret_cast<float4*>(slabs + (size_t)blockIdx.x * C + 4 * tid) = s;
+    }
+}
+
+
+// k_colreduce4's arithmetic for the device-count kernel below, statement for statement (same sums in the same order: same
+// bits). A copy and not a function both kernels inline: inlined, the compiler allocates k_colreduce4's registers and
+// schedules its loads differently, and the shipped kernel keeps its code.
+__device__ __forceinline__ void
+colreduce4_block(int mode, float* __restrict__ slabs, const float* __restrict__ A, int lda,
+                 const float* __restrict__ B, int ldb, const float* __restrict__ shift, int N, int C,
+                 int rows_per_block) {
+    __shared__ float4 part[kThreads];
+    const int tid = threadIdx.x;
+    const int QC = C / 4, R = kThreads / QC;
+    const int q = tid % QC, r = tid / QC;
+    const int r0 = blockIdx.x * rows_per_block;
+    const int r1 = min(N, r0 + rows_per_block);
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (r < R) {
+        const float4 sh = (mode == PVS_COL_SUMSQ_SHIFT) ? *reinterpret_cast<const float4*>(shift + 4 * q)
+                                                        : make_float4(0.f, 0.f, 0.f, 0.f);
+        constexpr int UN = 4;
+        for (int n0 = r0 + r; n0 < r1; n0 += UN * R) {
+            float4 a[UN], b[UN];
+#pragma unroll
+            for (int u = 0; u < UN; ++u) {
+                const int n = n0 + u * R;
+                const bool ok = n < r1;
+                a[u] = ok ? *reinterpret_cast<const float4*>(A + (size_t)n * lda + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
+                if (mode == PVS_COL_SUM_AB)
+                    b[u] = ok ? *reinterpret_cast<const float4*>(B + (size_t)n * ldb + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
+                else if (mode == PVS_COL_SUMSQ_SHIFT)
+                    a[u] = ok ? make_float4(a[u].x - sh.x, a[u].y - sh.y, a[u].z - sh.z, a[u].w - sh.w) : a[u];
+            }
+#pragma unroll
+            for (int u = 0; u < UN; ++u) {
+                if (mode == PVS_COL_SUM_A) { acc.x += a[u].x; acc.y += a[u].y; acc.z += a[u].z; acc.w += a[u].w; }
+                else if (mode == PVS_COL_SUM_AB) {
+                    acc.x = fmaf(a[u].x, b[u].x, acc.x); acc.y = fmaf(a[u].y, b[u].y, acc.y);
+                    acc.z = fmaf(a[u].z, b[u].z, acc.z); acc.w = fmaf(a[u].w, b[u].w, acc.w);
+                } else {
+                    acc.x = fmaf(a[u].x, a[u].x, acc.x); acc.y = fmaf(a[u].y, a[u].y, acc.y);
+                    acc.z = fmaf(a[u].z, a[u].z, acc.z); acc.w = fmaf(a[u].w, a[u].w, acc.w);
+                }
+            }
+        }
+    }
+    part[tid] = acc;
+    __syncthreads();
+    if (tid < QC) {
+        float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int rr = 0; rr < R; ++rr) {
+            const float4 v = part[rr * QC + tid];
+            s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+        }
+        *reinterpret_cast<float4*>(slabs + (size_t)blockIdx.x * C + 4 * tid) = s;
+    }
+}
+
+__global__ void __launch_bounds__(kThreads)
+k_colreduce(int mode, float* __restrict__ slabs, const float* __restrict__ A, int lda,
+            const float* __restrict__ B, int ldb, const float* __restrict__ shift, int N, int C,
+            int rows_per_block) {
+    colreduce_block(mode, slabs, A, lda, B, ldb, shift, N, C, rows_per_block);
+}
+
+// ---- column means over the leading n rows of A, n an int32 on the device (0 <= n <= n_cap after clamping) ------------
+// The row split is the one pvs_launch_colreduce makes on the host for N = n - blocks = clamp(ceil(n / 128), 1, 512),
+// rpb = ceil(n / blocks) -, formed here by every workgroup: the grid is launched for n_cap (blocks is monotone in N),
+// workgroups past blocks(n) leave, the others run the very code of k_colreduce / k_colreduce4 on their rows. Rows >= n
+// are never loaded. n = 0: one workgroup writes a slab of zeros.
+struct PvsRowSplit { int n, blocks, rpb; };
+
+__device__ __forceinline__ PvsRowSplit row_split_dev(const int* __restrict__ n_dev, int n_cap) {
+    PvsRowSplit r;
+    r.n = min(max(n_dev[0], 0), n_cap);
+    r.blocks = min(max((r.n + 127) / 128, 1), kMaxBlocks);
+    r.rpb = (r.n + r.blocks - 1) / r.blocks;
+    return r;
+}
+
+__global__ void __launch_bounds__(kThreads)
+k_colreduce_rows(int mode, float* __restrict__ slabs, const float* __restrict__ A, int lda,
+                 const float* __restrict__ shift, const int* __restrict__ n_dev, int n_cap, int C) {
+    const PvsRowSplit r = row_split_dev(n_dev, n_cap);
+    if ((int)blockIdx.x >= r.blocks) return;
+    colreduce_block(mode, slabs, A, lda, nullptr, 0, shift, r.n, C, r.rpb);
+}
+
+__global__ void __launch_bounds__(kThreads)
+k_colreduce4_rows(int mode, float* __restrict__ slabs, const float* __restrict__ A, int lda,
+                  const float* __restrict__ shift, const int* __restrict__ n_dev, int n_cap, int C) {
+    const PvsRowSplit r = row_split_dev(n_dev, n_cap);
+    if ((int)blockIdx.x >= r.blocks) return;
+    colreduce4_block(mode, slabs, A, lda, nullptr, 0, shift, r.n, C, r.rpb);
+}
+
+// out[o] = (1 / n) * sum_g slabs[g][o] over the blocks(n) slabs of the kernels above: the summation tree of
+// k_reduce_slabs (8 slab lanes, four partial sums each, combined in a fixed order) and its one multiplication by the
+// scale, which is the correctly rounded fp32 quotient 1 / n as the host forms `1.0f / (float)N`. n = 0: out = 0.
+__global__ void __launch_bounds__(kThreads)
+k_reduce_slabs_rows(float* __restrict__ out, const float* __restrict__ slabs, const int* __restrict__ n_dev,
+                    int n_cap, int width) {
+    __shared__ float part[8][33];
+    const PvsRowSplit r = row_split_dev(n_dev, n_cap);
+    const int n_slabs = r.blocks;
+    const float scale = r.n > 0 ? __fdiv_rn(1.0f, (float)r.n) : 0.f;
+    const int ol = threadIdx.x & 31, sl = threadIdx.x >> 5;
+    const int o = blockIdx.x * 32 + ol;
+    float s = 0.f;
+    if (o < width) {
+        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+        int gidx = sl;
+        for (; gidx + 24 < n_slabs; gidx += 32) {
+            a0 += slabs[(size_t)gidx * width + o];
+            a1 += slabs[(size_t)(gidx + 8) * width + o];
+            a2 += slabs[(size_t)(gidx + 16) * width + o];
+            a3 += slabs[(size_t)(gidx + 24) * width + o];
+        }
+        for (; gidx < n_slabs; gidx += 8) a0 += slabs[(size_t)gidx * width + o];
+        s = (a0 + a1) + (a2 + a3);
+    }
+    part[sl][ol] = s;
+    __syncthreads();
+    if (sl == 0 && o < width) {
+        float t = 0.f;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) t += part[k][ol];
+        out[o] = t * scale;
     }
 }
 
@@ -1376,6 +1505,23 @@ int pvs_launch_colreduce(hipStream_t s, int mode, float* out, const float* A, in
     PVS_CHECK_LAUNCH();
     k_reduce_slabs<<<(C + 31) / 32, kThreads, 0, s>>>(out, C, C, slabs, blocks, C, scale,
                                                       accumulate ? 1 : 0);
+    PVS_CHECK_LAUNCH();
+    return 0;
+}
+
+int pvs_launch_colmean_rows(hipStream_t s, int mode, float* out, const float* A, int lda, const float* shift,
+                            int n_cap, const int32_t* n_rows_dev, int C, float* slabs) {
+    PVS_REQUIRE(mode == PVS_COL_SUM_A || mode == PVS_COL_SUMSQ_SHIFT, "colmean_rows: mode %d unsupported", mode);
+    PVS_REQUIRE(C >= 1 && C <= kThreads, "colmean_rows: width %d unsupported (1..%d)", C, kThreads);
+    PVS_REQUIRE(n_cap >= 0 && n_rows_dev, "colmean_rows: needs a row capacity and a device row count");
+    const int blocks = pvs_colreduce_blocks(n_cap);
+    const bool vec4 = C % 4 == 0 && lda % 4 == 0 &&
+                      (((uintptr_t)A | (uintptr_t)shift | (uintptr_t)slabs) & 15) == 0;
+    PvsProfScope prof(s, vec4 ? PVS_PROF_COLREDUCE4_ROWS : PVS_PROF_COLREDUCE_ROWS);
+    if (vec4) k_colreduce4_rows<<<blocks, kThreads, 0, s>>>(mode, slabs, A, lda, shift, n_rows_dev, n_cap, C);
+    else k_colreduce_rows<<<blocks, kThreads, 0, s>>>(mode, slabs, A, lda, shift, n_rows_dev, n_cap, C);
+    PVS_CHECK_LAUNCH();
+    k_reduce_slabs_rows<<<(C + 31) / 32, kThreads, 0, s>>>(out, slabs, n_rows_dev, n_cap, C);
     PVS_CHECK_LAUNCH();
     return 0;
 }

@@ -218,10 +218,11 @@ int pvs_launch_edge_bwd_mfma(hipStream_t s, int H, PvsEdgeFamily fam, const PvsG
 // y1 = [h | Magg] Wn1^T + bn1 ; (graphnorm stats) ; u = SiLU(GN(y1)) ; o = u Wn2^T + bn2 ; h_out
 // = node_out(o, h). Without GraphNorm the SiLU rides on the first product's epilogue, and the plain
 // (un-gated, no node attention) output stage on the second's: two launches instead of four.
+// n_norm_rows_dev (PvsGraph.n_norm_rows_dev, read under GraphNorm only): the statistics run over that many leading rows.
 int node_mlp_forward(hipStream_t s, const Dims& m, const PvsLayerDesc* d, const PvsLayerParams* p,
                      const PvsNodeW& nw, const float* h, const float* Magg, float* y1, float* u,
                      float* o, float* stats, bool compute_stats, float* shift_tmp, float* slabs,
-                     float* h_out, float* node_att_out) {
+                     float* h_out, float* node_att_out, const int32_t* n_norm_rows_dev) {
     const int H = m.H;
     const uint32_t F = d->flags;
     PvsLinearJob first = pvs_linear_job(y1, H, pvs_operand(h, H, p->node_w1, 2 * H, H), m.N, H, p->node_b1);
@@ -250,7 +251,7 @@ int node_mlp_forward(hipStream_t s, const Dims& m, const PvsLayerDesc* d, const 
     first.epi = fuse_silu ? PVS_EPI_SILU_OUT : PVS_EPI_NONE;
     PVS_TRY(pvs_launch_linear(s, first));
     if ((F & PVS_GRAPHNORM) && compute_stats)
-        PVS_TRY(pvs_graphnorm_stats(s, y1, p->gn_mean_scale, m.N, H, stats, shift_tmp, slabs));
+        PVS_TRY(pvs_graphnorm_stats(s, y1, p->gn_mean_scale, m.N, H, stats, shift_tmp, slabs, n_norm_rows_dev));
     if (!fuse_silu) PVS_TRY(pvs_node_tail_fwd(s, y1, stats, nw, m.N, H, u));
     second.epi = !fuse_out ? PVS_EPI_NONE : (F & PVS_RESIDUAL) ? PVS_EPI_ADD_OUT : PVS_EPI_COPY_OUT;
     PVS_TRY(pvs_launch_linear(s, second));
@@ -351,7 +352,7 @@ extern "C" int pvs_egnn_layer_fwd(const PvsLayerDesc* d, const PvsGraph* g, cons
         PVS_CHECK_HIP(hipMemcpyAsync(x_out, x, sizeof(float) * 3 * (size_t)m.N,
                                      hipMemcpyDeviceToDevice, s));
     PVS_TRY(node_mlp_forward(s, m, d, p, nw, h, sv.Magg, sv.y1, sv.u, sv.o, sv.stats, true, w.shift, w.slabs, h_out,
-                             node_att_out));
+                             node_att_out, g->n_norm_rows_dev));
     return 0;
 }
 
@@ -455,7 +456,7 @@ extern "C" int pvs_egnn_layer_fwd_partial_att(const PvsLayerDesc* d, const PvsGr
                                                                    (d->flags & PVS_UPDATE_COORDS) ? 1 : 0);
     PVS_CHECK_LAUNCH();
     PVS_TRY(node_mlp_forward(s, m, d, p, nw, h, sv.Magg, sv.y1, sv.u, sv.o, sv.stats, true, w.shift, w.slabs, h_out,
-                             node_att_out));
+                             node_att_out, g->n_norm_rows_dev));
     return 0;
 }
 
@@ -563,9 +564,11 @@ extern "C" int pvs_egnn_layer_bwd(const PvsLayerDesc* d, const PvsGraph* g, cons
                                      w.dslabs, false));
         PVS_TRY(pvs_launch_colreduce(s, PVS_COL_SUM_AB, w.S2, w.g_u, H, sy1, H, nullptr, N, H, 1.f,
                                      w.dslabs, false));
+        // (g->n_norm_rows_dev: all N rows were normalised by the statistics of the first *n_norm_rows_dev; S1 / S2 stay
+        // sums over all N)
         PVS_TRY(pvs_graphnorm_bwd_coefs(s, w.S1, w.S2, stats, nw, N, H, gr.gn_weight, gr.gn_bias,
-                                        gr.gn_mean_scale, w.coefs));
-        PVS_TRY(pvs_node_tail_bwd2(s, w.g_u, sy1, stats, nw, w.coefs, N, H, w.g_u));
+                                        gr.gn_mean_scale, w.coefs, g->n_norm_rows_dev));
+        PVS_TRY(pvs_node_tail_bwd2(s, w.g_u, sy1, stats, nw, w.coefs, N, H, w.g_u, g->n_norm_rows_dev));
     }
     float* g_y1 = w.g_u;
     // y1 = h Wn1[:, :H]^T + Magg Wn1[:, H:]^T + bn1
@@ -805,4 +808,24 @@ extern "C" int pvs_egnn_stack_bwd(const PvsLayerDesc* descs, const PvsLayerParam
         gx = gx_in;
     }
     return 0;
+}
+
+// ---- GraphNorm's statistics as an operator (include/pvs_egnn.h: pvs_graphnorm_stats_rows) --------------------------------
+extern "C" size_t pvs_graphnorm_stats_rows_workspace_bytes(int32_t n_rows_cap, int32_t H) {
+    const size_t h = (size_t)(H > 0 ? H : 0);
+    return pvs_align_up(h * sizeof(float), 256) +
+           pvs_align_up((size_t)pvs_colreduce_blocks(n_rows_cap) * h * sizeof(float), 256) + 256;
+}
+
+extern "C" int pvs_graphnorm_stats_rows(const float* y1, const float* mean_scale, int32_t n_rows_cap, int32_t H,
+                                        const int32_t* n_rows_dev, float* stats, void* workspace, size_t workspace_bytes,
+                                        pvs_stream_t stream) {
+    PVS_REQUIRE(mean_scale && stats && H >= 1 && H <= 256, "pvs_graphnorm_stats_rows: needs mean_scale, stats and 1 <= H <= 256");
+    PVS_REQUIRE(n_rows_cap >= (n_rows_dev ? 0 : 1) && (y1 || n_rows_cap == 0),
+                "pvs_graphnorm_stats_rows: bad row count %d (the host-count route needs at least one row)", n_rows_cap);
+    PvsArena arena(workspace, workspace_bytes);
+    float* shift = arena.take<float>((size_t)H);
+    float* slabs = arena.take<float>((size_t)pvs_colreduce_blocks(n_rows_cap) * H);
+    PVS_REQUIRE(arena.ok(), "pvs_graphnorm_stats_rows: workspace too small (%zu < %zu)", workspace_bytes, arena.off);
+    return pvs_graphnorm_stats((hipStream_t)stream, y1, mean_scale, n_rows_cap, H, stats, shift, slabs, n_rows_dev);
 }

@@ -9,8 +9,11 @@ struct PvsNodeW {
 };
 
 // stats[0:H] = column mean of y1, stats[H:2H] = column mean of (y1 - mean*mean_scale)^2
+// n_rows_dev (optional DEVICE int32, PvsGraph.n_norm_rows_dev): the means run over the first n = clamp(*n_rows_dev, 0, N)
+// rows only, n read on the device; for n >= 1 the bits of the call with N = n and no count, n = 0 gives zeros. The
+// launchers below that take it normalise all N rows with those statistics and return the exact gradient of that.
 int pvs_graphnorm_stats(hipStream_t s, const float* y1, const float* gn_ms, int N, int H, float* stats,
-                        float* shift_tmp, float* slabs);
+                        float* shift_tmp, float* slabs, const int32_t* n_rows_dev = nullptr);
 // u = SiLU(GN(y1))  (GN skipped when w.gn_w == NULL)
 int pvs_node_tail_fwd(hipStream_t s, const float* y1, const float* stats, const PvsNodeW& w, int N,
                       int H, float* u);
@@ -29,10 +32,12 @@ int pvs_node_tail_bwd1(hipStream_t s, const float* g_u, const float* y1, const f
 // (coefs[3H..4H) = the gradient of the bias in front of the norm in closed form)
 int pvs_graphnorm_bwd_coefs(hipStream_t s, const float* S1, const float* S2, const float* stats,
                             const PvsNodeW& w, int N, int H, float* g_w, float* g_b, float* g_ms,
-                            float* coefs);
-// g_y1 = g_yn*coefA + (y1 - shift)*coefB + coefC   (in place on g_yn allowed)
+                            float* coefs, const int32_t* n_rows_dev = nullptr);
+// g_y1 = g_yn*coefA + (y1 - shift)*coefB + coefC   (in place on g_yn allowed); with n_rows_dev the last two terms go
+// to rows < n only
 int pvs_node_tail_bwd2(hipStream_t s, const float* g_yn, const float* y1, const float* stats,
-                       const PvsNodeW& w, const float* coefs, int N, int H, float* g_y1);
+                       const PvsNodeW& w, const float* coefs, int N, int H, float* g_y1,
+                       const int32_t* n_rows_dev = nullptr);
 // gxagg = g_x_out * inv_deg (if g_x_out), softD = rowdot(Magg, gM) (if softD)
 int pvs_prep_edge_bwd(hipStream_t s, const float* g_x_out, const float* inv_deg, const float* Magg,
                       const float* gM, int N, int H, float* gxagg, float* softD, float* zero_gPQ,

@@ -274,6 +274,39 @@ __global__ void k_gn_bwd_coefs(const float* S1, const float* S2raw, const float*
     coefs[3 * H + c] = sum_gc * (1.0f - ms);
 }
 
+// The same where ALL n_cap rows were normalised by the statistics of the first n = clamp(*n_rows_dev, 0, n_cap) of them:
+// S1 and S2 are sums over all rows (a row behind n depends on the statistics too), while var and mean are means over n
+// rows - sum_cc and the two / N coefficients take n, and k_node_tail_bwd2_rows hands their terms to rows < n only.
+// n = 0: mean = var = 0 are constants, nothing flows through them (no division by n).
+__global__ void k_gn_bwd_coefs_rows(const float* S1, const float* S2raw, const float* stats, PvsNodeW w,
+                                    const int* __restrict__ n_rows_dev, int n_cap, int H, float* g_w, float* g_b,
+                                    float* g_ms, float* coefs) {
+    int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= H) return;
+    const int n = min(max(n_rows_dev[0], 0), n_cap);
+    const float mean = stats[c], var = stats[H + c];
+    const float ms = w.gn_ms[c], gw = w.gn_w[c];
+    const float shift = mean * ms;
+    const float rstd = 1.0f / sqrtf(var + kGnEps);
+    const float s1 = S1[c];                  // sum g_yn over all n_cap rows
+    const float s2 = S2raw[c] - shift * s1;  // sum g_yn * cc over all n_cap rows
+    const float g_var = -0.5f * gw * rstd * rstd * rstd * s2;
+    const float inv_n = n > 0 ? 1.0f / (float)n : 0.f;
+    const float sum_cc = (float)n * (mean - shift);        // sum of cc over the n rows of the statistics
+    const float sum_gc = gw * rstd * s1 + g_var * 2.0f * sum_cc * inv_n;
+    const float g_shift = -sum_gc;
+    if (g_w) g_w[c] = s2 * rstd;
+    if (g_b) g_b[c] = s1;
+    if (g_ms) g_ms[c] = g_shift * mean;
+    const float g_mean = n > 0 ? g_shift * ms : 0.f;       // (n = 0: the mean is the constant 0, no row receives it)
+    coefs[c] = gw * rstd;
+    coefs[H + c] = 2.0f * g_var * inv_n;
+    coefs[2 * H + c] = g_mean * inv_n;
+    // node_mlp.0.bias = sum over ALL rows of g_y1 = gw rstd s1 + (2 g_var / n) sum_cc + g_mean = sum_gc (1 - ms), as above
+    // (n = 0: no row receives g_mean, the sum is sum_gc = gw rstd s1)
+    coefs[3 * H + c] = n > 0 ? sum_gc * (1.0f - ms) : sum_gc;
+}
+
 __global__ void k_copy_small(const float* __restrict__ src, float* __restrict__ dst, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) dst[i] = src[i];
@@ -289,6 +322,25 @@ __global__ void k_node_tail_bwd2(const float* __restrict__ g_yn, const float* __
         int c = (int)(i % H);
         const float shift = stats[c] * w.gn_ms[c];
         g_y1[i] = g_yn[i] * coefs[c] + (y1[i] - shift) * coefs[H + c] + coefs[2 * H + c];
+    }
+}
+
+// rows < n as above; rows >= n (normalised by the statistics, not part of them): g_yn * coefs[c] alone
+__global__ void k_node_tail_bwd2_rows(const float* __restrict__ g_yn, const float* __restrict__ y1,
+                                      const float* __restrict__ stats, PvsNodeW w,
+                                      const float* __restrict__ coefs, const int* __restrict__ n_rows_dev, int N, int H,
+                                      float* __restrict__ g_y1) {
+    const long long total = (long long)N * H;
+    const long long stat_end = (long long)min(max(n_rows_dev[0], 0), N) * H;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+         i += (long long)gridDim.x * blockDim.x) {
+        int c = (int)(i % H);
+        float g = g_yn[i] * coefs[c];
+        if (i < stat_end) {
+            const float shift = stats[c] * w.gn_ms[c];
+            g = g + (y1[i] - shift) * coefs[H + c] + coefs[2 * H + c];
+        }
+        g_y1[i] = g;
     }
 }
 
@@ -339,7 +391,14 @@ int ew_grid(long long total) {
 #include "dense_ops.h"
 
 int pvs_graphnorm_stats(hipStream_t s, const float* y1, const float* gn_ms, int N, int H, float* stats,
-                        float* shift_tmp, float* slabs) {
+                        float* shift_tmp, float* slabs, const int32_t* n_rows_dev) {
+    if (n_rows_dev) {
+        int rc = pvs_launch_colmean_rows(s, PVS_COL_SUM_A, stats, y1, H, nullptr, N, n_rows_dev, H, slabs);
+        if (rc) return rc;
+        k_gn_shift<<<(H + 63) / 64, 64, 0, s>>>(stats, gn_ms, H, shift_tmp);
+        PVS_CHECK_LAUNCH();
+        return pvs_launch_colmean_rows(s, PVS_COL_SUMSQ_SHIFT, stats + H, y1, H, shift_tmp, N, n_rows_dev, H, slabs);
+    }
     int rc = pvs_launch_colreduce(s, PVS_COL_SUM_A, stats, y1, H, nullptr, 0, nullptr, N, H,
                                   1.0f / (float)N, slabs, false);
     if (rc) return rc;
@@ -409,14 +468,26 @@ int pvs_node_tail_bwd1(hipStream_t s, const float* g_u, const float* y1, const f
 
 int pvs_graphnorm_bwd_coefs(hipStream_t s, const float* S1, const float* S2, const float* stats,
                             const PvsNodeW& w, int N, int H, float* g_w, float* g_b, float* g_ms,
-                            float* coefs) {
+                            float* coefs, const int32_t* n_rows_dev) {
+    if (n_rows_dev) {
+        PvsProfScope prof(s, PVS_PROF_NODE_TAIL_ROWS);
+        k_gn_bwd_coefs_rows<<<(H + 63) / 64, 64, 0, s>>>(S1, S2, stats, w, n_rows_dev, N, H, g_w, g_b, g_ms, coefs);
+        PVS_CHECK_LAUNCH();
+        return 0;
+    }
     k_gn_bwd_coefs<<<(H + 63) / 64, 64, 0, s>>>(S1, S2, stats, w, N, H, g_w, g_b, g_ms, coefs);
     PVS_CHECK_LAUNCH();
     return 0;
 }
 
 int pvs_node_tail_bwd2(hipStream_t s, const float* g_yn, const float* y1, const float* stats,
-                       const PvsNodeW& w, const float* coefs, int N, int H, float* g_y1) {
+                       const PvsNodeW& w, const float* coefs, int N, int H, float* g_y1, const int32_t* n_rows_dev) {
+    if (n_rows_dev) {
+        PvsProfScope prof(s, PVS_PROF_NODE_TAIL_ROWS);
+        k_node_tail_bwd2_rows<<<ew_grid((long long)N * H), 256, 0, s>>>(g_yn, y1, stats, w, coefs, n_rows_dev, N, H, g_y1);
+        PVS_CHECK_LAUNCH();
+        return 0;
+    }
     PvsProfScope prof(s, PVS_PROF_NODE_TAIL);
     k_node_tail_bwd2<<<ew_grid((long long)N * H), 256, 0, s>>>(g_yn, y1, stats, w, coefs, N, H, g_y1);
     PVS_CHECK_LAUNCH();

@@ -17,7 +17,10 @@ enum { PVS_PROF_EDGE_FWD = 0, PVS_PROF_EDGE_BWD = 1, PVS_PROF_COL_GATHER = 2, PV
        // of the two node routes a layer call took. Recorded like the dense routes, under their own mask bit only.
        PVS_PROF_NODE_MLP_FWD = 19, PVS_PROF_NODE_MLP_BWD = 20, PVS_PROF_NODE_OUT_FWD = 21, PVS_PROF_NODE_OUT_BWD = 22,
        PVS_PROF_NODE_TAIL = 23, PVS_PROF_NODE_WGRADS = 24,
-       PVS_PROF_COUNT = 25 };
+       // GraphNorm over a device row count (PvsGraph.n_norm_rows_dev): the column means over the leading rows, and the
+       // tail launchers that read the count (the coefficients and the row-bounded second backward pass)
+       PVS_PROF_COLREDUCE4_ROWS = 25, PVS_PROF_COLREDUCE_ROWS = 26, PVS_PROF_NODE_TAIL_ROWS = 27,
+       PVS_PROF_COUNT = 28 };
 static_assert(PVS_PROF_COUNT + 1 <= 32, "the profile mask is an unsigned with bit (id + 1) per category");
 
 // tag the edge forward launches of the calling thread carry (layer_api: full layer vs partial layer)

@@ -349,6 +349,12 @@ class EGNNLayer(nn.Module):
         node_model on the prepared graph's sorted edge list. Not fused (the [E, H] intermediates live in HBM and
         autograd keeps them), so it runs at a fraction of the fused layers' rate; same values as the reference
         (oracle-checked at k = 96 ... 1100)."""
+        if self.graphnorm and pg.c.n_norm_rows_dev:
+            raise NotImplementedError(
+                f'GraphNorm over a device row count (PreparedGraph.set_norm_rows) is built for hidden sizes up to 128: '
+                f'hidden_nf={self.hidden_nf} runs the decomposed layer, whose GraphNorm is a torch expression over all '
+                f'rows - a slice whose length lives on the device cannot be captured. Clear the count '
+                f'(set_norm_rows(None)) and run the exact node count.')
         e = pg.n_edges
         row, col = pg.t['row'][:e].long(), pg.t['col'][:e].long()
         edge_index = torch.stack([row, col])

@@ -444,6 +444,32 @@ def linear(x, weight, bias=None):
     return y.reshape(-1) if squeeze else y
 
 
+def graphnorm_stats(y1, mean_scale, n_rows=None, out=None):
+    """GraphNorm's statistics of y1 [N_cap, H] (fp32, H <= 256) as the layers compute them: a [2 H] tensor, the column
+    means in front, behind them the column means of (y1 - mean_scale * mean)^2. n_rows None: over all rows (N_cap >= 1).
+    n_rows a device int32 tensor with one element: over the first clamp(n_rows, 0, N_cap) rows, the count read on the
+    device (PvsGraph.n_norm_rows_dev: rows behind it are never read, 0 gives zeros, n >= 1 the bits of the call on
+    y1[:n]). No gradient: the layers' backward has its own kernels."""
+    if y1.dim() != 2 or y1.dtype != _F32:
+        raise TypeError(f'graphnorm_stats: y1 must be a float32 [N, H] tensor (got {y1.dtype}, {tuple(y1.shape)})')
+    y1, mean_scale = y1.contiguous(), _c(mean_scale, _F32)
+    _lib.require_hip(y1, mean_scale, n_rows)
+    n_cap, hidden = int(y1.shape[0]), int(y1.shape[1])
+    if mean_scale.numel() != hidden:
+        raise ValueError(f'graphnorm_stats: mean_scale has {mean_scale.numel()} entries, y1 {hidden} columns')
+    if n_rows is not None and not (n_rows.dtype == torch.int32 and n_rows.numel() == 1 and n_rows.is_contiguous()):
+        raise ValueError('graphnorm_stats: n_rows must be a device int32 tensor with one element')
+    lib = _lib.lib()
+    dev = y1.device
+    stats = torch.empty(2 * hidden, dtype=_F32, device=dev) if out is None else out
+    ws_bytes = lib.pvs_graphnorm_stats_rows_workspace_bytes(n_cap, hidden)
+    ws = _ws(ws_bytes, dev)
+    _lib.check(lib.pvs_graphnorm_stats_rows(_lib.ptr(y1), _lib.ptr(mean_scale), n_cap, hidden, _lib.ptr(n_rows),
+                                            _lib.ptr(stats), _lib.ptr(ws), ws_bytes, _stream(dev)),
+               'pvs_graphnorm_stats_rows')
+    return stats
+
+
 class _MeanPoolFn(torch.autograd.Function):
     """global_mean_pool over contiguous per-graph node ranges (pnn_geometric_base.py:29-33)."""
 

@@ -107,6 +107,24 @@ class PreparedGraph:
         self.c.graph_eptr = _lib.ptr(eptr)
         self.c.n_graphs = int(eptr.numel()) - 1
 
+    def set_norm_rows(self, count):
+        """count: a device int32 tensor with one element (or a one-element view of a longer one, e.g. the last entry
+        of a node offset table), the number of LEADING rows that enter GraphNorm's statistics
+        (PvsGraph.n_norm_rows_dev): a padded, captured step has its real node count only on the device. The layers
+        normalise every row with the statistics of those rows; forward and backward read the same word. The tensor is
+        kept alive in `self.t['norm_rows']`. None clears it (the statistics run over all n_nodes rows again)."""
+        if count is None:
+            self.t.pop('norm_rows', None)
+            self.c.n_norm_rows_dev = None
+            return
+        if not (torch.is_tensor(count) and count.is_cuda and count.dtype == torch.int32 and count.numel() == 1
+                and count.is_contiguous()):
+            raise ValueError('set_norm_rows needs a device int32 tensor with one element (or None)')
+        if count.device != self.t['rowptr'].device:
+            raise ValueError(f"set_norm_rows: the count is on {count.device}, the graph on {self.t['rowptr'].device}")
+        self.t['norm_rows'] = count
+        self.c.n_norm_rows_dev = count.data_ptr()
+
     def poll_status(self):
         """Asynchronous validation: the first call queues a D2H copy of the status word, later
         calls (or check_status) raise once it has landed. Never blocks the stream."""

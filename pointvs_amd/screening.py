@@ -549,7 +549,11 @@ class LibraryScreen(_ReceptorSideScreen):
     receptor); no host argument of a step depends on the batch's composition, so ONE captured step (`capture`) serves every batch. Models without graphnorm always run
     at the padded shape N_cap = batch_size * (max_lig_atoms + n_rec) (padding nodes have no edges and belong to no
     graph), eager and captured alike; graphnorm normalises over the batch's nodes, so such models run eager at the
-    exact node count. Models the first-layer reuse does not cover (edge_residual, softmax attention, hidden size not
+    exact node count - unless `padded_graphnorm=True` (opt-in, default False): they then run at N_cap like every other
+    model, eager and captured, with GraphNorm's statistics over the node_ptr[batch_size] real rows in front of the
+    padding, a count the layers read on the device (PvsGraph.n_norm_rows_dev). The copies of one batch still normalise
+    each other, as in every batched route. The keyword changes nothing for a model without graphnorm, nor for the
+    plain route below. Models the first-layer reuse does not cover (edge_residual, softmax attention, hidden size not
     32 / 64) take the plain forward on the same mixed batch. fp32 only. tasks: as for ReceptorScreen.
 
     cam: None, True or a column (`resolve_cam`): the class-activation map of every step - the heads the screen
@@ -576,9 +580,10 @@ class LibraryScreen(_ReceptorSideScreen):
     per slot). A screen without it launches exactly what it always launched."""
 
     def __init__(self, model, rec_pos, rec_feats, batch_size, max_lig_atoms, edge_radius, intra_radius=None,
-                 tasks=None, contact_attention=None, cam=None, struck=None):
+                 tasks=None, contact_attention=None, cam=None, struck=None, padded_graphnorm=False):
         super().__init__(model, edge_radius, intra_radius, tasks)
         self.struck = bool(struck)
+        self.padded_graphnorm = bool(padded_graphnorm)
         if self.struck and (cam is not None or contact_attention is not None):
             which = 'cam' if cam is not None else 'contact_attention'
             raise ValueError(f'LibraryScreen(struck=True, {which}=...): the {which} reduction assumes n_rec receptor '
@@ -592,6 +597,8 @@ class LibraryScreen(_ReceptorSideScreen):
         self.reuse = (first is not None and first.hidden_nf in (32, 64) and not first.softmax_attention
                       and not any(l.edge_residual for l in self.egnn))
         self.graphnorm = any(getattr(l, 'graphnorm', False) for l in self.egnn)
+        # a graphnorm model at the padded shape: the statistics over the node_ptr[batch_size] real rows, read on the device
+        self._gn_padded = self.padded_graphnorm and self.graphnorm and self.reuse
         dev = rec_pos.device
         self.b, self.max_lig_atoms = int(batch_size), int(max_lig_atoms)
         self.slot_cap = max(self.max_lig_atoms, 64)      # what the builder validates lig_ptr against
@@ -888,6 +895,10 @@ class LibraryScreen(_ReceptorSideScreen):
         pgs = self._fast['pgs']
         if n not in pgs:
             pgs[n] = _graph_pair(self._fast, n, self.n_cap)
+            if self._gn_padded:      # both graphs: the partial first layer's and the full one of the layers behind it
+                real_nodes = self._fast['node_ptr'][self.b:]
+                pgs[n][0].set_norm_rows(real_nodes)
+                pgs[n][1].n_norm_rows_dev = real_nodes.data_ptr()
         return pgs[n]
 
     def _build(self, capacities=None):
@@ -952,8 +963,10 @@ class LibraryScreen(_ReceptorSideScreen):
             return self._plain_forward()
         self._refresh_if_stale()
         f = self._build()
-        # graphnorm's statistics run over the batch's nodes: no padding rows there (the host knows the count)
-        n = self.n_atoms + self.b * self.n_rec - self._n_struck if self.graphnorm else self.n_cap
+        # graphnorm's statistics run over the batch's nodes: no padding rows there (the host knows the count) - or, with
+        # padded_graphnorm, the padded shape and the count where the builder left it (PvsGraph.n_norm_rows_dev)
+        exact = self.graphnorm and not self._gn_padded
+        n = self.n_atoms + self.b * self.n_rec - self._n_struck if exact else self.n_cap
         pg_full, g_lig = self._graphs(n)
         x = f['pos'][:n]
         h = self.embed.embed(f['x'][:n], x).contiguous()
@@ -974,7 +987,7 @@ class LibraryScreen(_ReceptorSideScreen):
         if not self.reuse:
             raise RuntimeError('capture needs the first-layer reuse (no edge_residual, no softmax attention, '
                                'hidden size 32 or 64)')
-        if self.graphnorm:
+        if self.graphnorm and not self._gn_padded:
             raise RuntimeError('a graphnorm model normalises over the batch\'s nodes and runs at the exact node '
                                'count: it cannot be captured at the padded shape; call the screen eagerly')
         if example_slots is not None:
@@ -1072,8 +1085,9 @@ class ScreeningSweep:
     """
 
     def __init__(self, model, rec_pos, rec_feats, edge_radius, batch_size=32, intra_radius=None, capture=True,
-                 receptor_name='receptor', tasks=None):
+                 receptor_name='receptor', tasks=None, padded_graphnorm=False):
         self.model, self.rec_pos, self.rec_feats = model, rec_pos, rec_feats
+        self.padded_graphnorm = bool(padded_graphnorm)      # handed to every LibraryScreen of the sweep
         self.tasks = _resolve_tasks(model, tasks)
         self.hits = {}
         self.atom_masking_raw = {}     # ligand_atom_masking: {name: raw rows [n + 1, C], whole ligand first}
@@ -1196,13 +1210,14 @@ class ScreeningSweep:
                 or screen.contact_attention != layer
                 or (type(screen.cam_request), screen.cam_request) != (type(cam), cam)):      # (True is not column 1)
             screen = LibraryScreen(self.model, self.rec_pos, self.rec_feats, self.b, max_atoms, self.edge_radius,
-                                   self.intra_radius, tasks=self.tasks, contact_attention=layer, cam=cam, struck=struck)
+                                   self.intra_radius, tasks=self.tasks, contact_attention=layer, cam=cam, struck=struck,
+                                   padded_graphnorm=self.padded_graphnorm)
             setattr(self, which, screen)
         return screen
 
     def _capture_if_wanted(self, screen):
         """Captures the step of `screen` on the batch loaded into it, where a captured step can be had."""
-        if self.capture and screen.reuse and not screen.graphnorm and not screen._captured:
+        if self.capture and screen.reuse and (not screen.graphnorm or screen._gn_padded) and not screen._captured:
             screen.capture()
 
     def _library_step(self, screen):
