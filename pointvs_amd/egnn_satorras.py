@@ -8,6 +8,7 @@ The nn.Sequential members only hold parameters under the reference's names (so r
 checkpoints load and seeds give the same init); they are never called. The arithmetic of
 forward/backward is `pvs_egnn_layer_fwd/bwd` in libpvs_egnn.so (include/pvs_egnn.h).
 """
+import contextlib
 import os
 
 import torch
@@ -574,39 +575,17 @@ class SartorrasEGNN(PNNGeometricBase):
         seed, step = self.next_dropout_key()
         return PF.dropout_adj(edges, edge_attributes, p, force_undirected=True, training=True, seed=seed, step=step)
 
+    @property
+    def dropout_keys(self):
+        """The model's DropoutKeys, made on first use. It lives in the instance's __dict__: no parameter, buffer or
+        sub-module, so `state_dict()` does not know it; deepcopy / pickle carry it like any plain attribute."""
+        return self.__dict__.setdefault('_dropout_keys', DropoutKeys())
+
     def next_dropout_key(self):
-        """(seed, step) of the next draw, and the draw counted: pure host arithmetic, the one schedule of the eager
-        step, the static-shape step and the captured step (the replayer calls this before every replay and writes
-        the result to the device table the captured draw reads)."""
-        # the step of the draw: epochs done (restored from a checkpoint) and optimiser steps taken in this run (+ the
-        # calls since the last one, for several forwards per step), so that a resumed run does not replay the masks
-        # of its first epoch; the rank goes into the seed, so that data-parallel ranks do not drop the same edge
-        # indices (ADVICE r03)
-        base = ((getattr(self, 'p_epoch', 0) + getattr(self, 'a_epoch', 0)) << 24) + getattr(self, 'global_iter', 0)
-        if base != getattr(self, '_dropout_base', None):
-            self._dropout_base, self._dropout_calls = base, 0
-        self._dropout_calls = getattr(self, '_dropout_calls', 0) + 1
-        rank = 0
-        if torch.distributed.is_available() and torch.distributed.is_initialized():
-            rank = torch.distributed.get_rank()
-        seed = (torch.initial_seed() + 0x9E3779B97F4A7C15 * rank) & (2 ** 64 - 1)
-        # (epochs, optimiser steps, calls) -> ONE 64-bit step by a mix, not by packing bit fields (ADVICE r04: with
-        # fields, more than 255 forwards under one base - a loop that never bumps global_iter - carried into the next
-        # base's range, and 2^24 optimiser steps into the epoch field: masks could repeat)
-        return seed, _mix64(_mix64(int(base)) + self._dropout_calls)
+        return self.dropout_keys.next(self)
 
     def push_dropout_key(self, device):
-        """The next key of the schedule into the model's device table {seed, step}, on the current stream: what the
-        static-shape draw (PF.dropout_adj_padded) reads when it runs. A launch with by-value arguments, so outside any
-        capture. Returns (seed, step)."""
-        table = self.__dict__.get('_dropout_table')
-        if table is None or table.device != torch.device(device):
-            table = self.__dict__['_dropout_table'] = torch.zeros(2, dtype=torch.int64, device=device)
-        key = self.next_dropout_key()
-        PF.write_dropout_key(table, *key)
-        self.__dict__['_dropout_key'] = key
-        self.__dict__['_dropout_key_fresh'] = True      # (consumed by the one forward a replayer's step takes)
-        return key
+        return self.dropout_keys.push(self, device)
 
     def embed_prepared(self, pg, feats, coords, need_messages=False, trace=None, need_coords=True):
         """Layer stack on a PreparedGraph. Edge messages stay in sorted order between layers and
@@ -739,6 +718,71 @@ def _mix64(x):
     x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & 0xFFFFFFFFFFFFFFFF
     x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & 0xFFFFFFFFFFFFFFFF
     return x ^ (x >> 31)
+
+
+class DropoutKeys:
+    """The (seed, step) schedule of a model's edge-dropout draws - the one schedule of the eager step, the static-shape
+    step and the captured step - and the device table {seed, step} that the static-shape draw reads its key from."""
+
+    base, calls = None, 0               # the schedule's counters: calls count the draws under one base
+    table = key = None                  # the device table and the (seed, step) last written to it
+    # is_external: a replayer pushes the keys, one per step, outside its captures; fresh: the pushed key has not served a
+    # forward yet
+    is_external = fresh = False
+
+    def next(self, model):
+        """(seed, step) of the model's next draw, and the draw counted: pure host arithmetic."""
+        # the step of the draw: epochs done (restored from a checkpoint) and optimiser steps taken in this run (+ the
+        # calls since the last one, for several forwards per step), so that a resumed run does not replay the masks
+        # of its first epoch; the rank goes into the seed, so that data-parallel ranks do not drop the same edge
+        # indices (ADVICE r03)
+        base = ((getattr(model, 'p_epoch', 0) + getattr(model, 'a_epoch', 0)) << 24) + getattr(model, 'global_iter', 0)
+        if base != self.base:
+            self.base, self.calls = base, 0
+        self.calls += 1
+        rank = 0
+        if torch.distributed.is_available() and torch.distributed.is_initialized():
+            rank = torch.distributed.get_rank()
+        seed = (torch.initial_seed() + 0x9E3779B97F4A7C15 * rank) & (2 ** 64 - 1)
+        # (epochs, optimiser steps, calls) -> ONE 64-bit step by a mix, not by packing bit fields (ADVICE r04: with
+        # fields, more than 255 forwards under one base - a loop that never bumps global_iter - carried into the next
+        # base's range, and 2^24 optimiser steps into the epoch field: masks could repeat)
+        return seed, _mix64(_mix64(int(base)) + self.calls)
+
+    def push(self, model, device):
+        """The next key of the schedule into the device table (re-made on another device), on the current stream. A
+        launch with by-value arguments, so outside any capture. Returns (seed, step)."""
+        if self.table is None or self.table.device != torch.device(device):
+            self.table = torch.zeros(2, dtype=torch.int64, device=device)
+        self.key = self.next(model)
+        PF.write_dropout_key(self.table, *self.key)
+        self.fresh = True
+        return self.key
+
+    def take(self, model, device):
+        """((seed, step), the table that holds them) for ONE static-shape forward: pushed here, unless keys are external -
+        then the key pushed for this step, which serves one forward."""
+        if not self.is_external:
+            self.push(model, device)
+        elif not self.fresh:
+            raise RuntimeError('static edge dropout under a replayer: a second training forward within one step would '
+                               'draw the first one\'s mask again (the replayer writes one key per step)')
+        self.fresh = False
+        return self.key, self.table
+
+    @contextlib.contextmanager
+    def external(self, model):
+        """A replayer's lifetime: keys are pushed from outside and the model draws into the fixed shape
+        (`static_dropout = True`). On exit - also when the body raised - both are as before, `static_dropout` unset
+        on the instance if it was."""
+        was = {k: v for k, v in vars(model).items() if k == 'static_dropout'}
+        model.static_dropout, self.is_external = True, True
+        try:
+            yield self
+        finally:
+            self.is_external = False
+            vars(model).pop('static_dropout', None)
+            vars(model).update(was)
 
 
 def unsorted_segment_sum(data, segment_ids, num_segments):

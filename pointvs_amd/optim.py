@@ -243,16 +243,7 @@ class FusedClipAdam(_PointerTables, torch.optim.Adam):
         back to exactly that), on the device as fp32 for a capturable one."""
         self._fast = None              # new state tensors, other step counts
         out = super().load_state_dict(state_dict)
-        for group in self.param_groups:
-            capturable = bool(group.get('capturable'))
-            for p in group['params']:
-                st = self.state.get(p)
-                if not st or not torch.is_tensor(st.get('step')):
-                    continue
-                if capturable and (not st['step'].is_cuda or st['step'].dtype != torch.float32):
-                    st['step'] = st['step'].to(device=p.device, dtype=torch.float32)
-                elif not capturable and (st['step'].is_cuda or st['step'].dtype != torch.float32):
-                    st['step'] = st['step'].detach().to(device='cpu', dtype=torch.float32)
+        _place_step_counters(self)
         return out
 
     @torch.no_grad()
@@ -467,3 +458,62 @@ class FusedClipSGD(_PointerTables, torch.optim.SGD):
             groups.append(works)
         self._fast = {'live': live, 'sig': self._signature(), 'groups': groups if fusable else [], 'fusable': fusable}
         return self._fast
+
+
+def _place_step_counters(optimiser):
+    """Adam's step counters where each group's `capturable` flag wants them: on the parameter's device for a capturable
+    group, as torch's capturable Adam keeps them, else on the host; fp32 either way."""
+    for group in optimiser.param_groups:
+        capturable = bool(group.get('capturable'))
+        for p in group['params']:
+            st = optimiser.state.get(p)
+            if st and torch.is_tensor(st.get('step')) and (st['step'].is_cuda != capturable
+                                                           or st['step'].dtype != torch.float32):
+                st['step'] = st['step'].detach().to(device=p.device if capturable else 'cpu', dtype=torch.float32)
+
+
+class capturable_window:
+    """`with capturable_window(optimiser, n_captures):` - FusedClipAdam, FusedClipSGD or plain torch.optim.Adam in its
+    capturable form for the duration, with pinned pointer tables for `n_captures` captured steps. SGD: its `capturable`
+    attribute (no group option, no state). Adam: every group's `capturable` option, and the step counters on the device
+    as fp32, as torch's capturable Adam keeps them (FusedClipAdam then forms the bias corrections in its kernel). The
+    work list is dropped either way. On exit - also when the body raised - flags and counters are as they were."""
+
+    def __init__(self, optimiser, n_captures):
+        self.optimiser, self.n_captures = optimiser, n_captures
+        self._sgd = isinstance(optimiser, FusedClipSGD)
+
+    def _set(self, form):
+        """form: SGD's attribute, or Adam's option group by group."""
+        if self._sgd:
+            self.optimiser.capturable = form
+        else:
+            for group, flag in zip(self.optimiser.param_groups, form):
+                group['capturable'] = flag
+            _place_step_counters(self.optimiser)
+        self.optimiser._fast = None
+
+    def __enter__(self):
+        self._was = (self.optimiser.capturable if self._sgd else
+                     [group.get('capturable', False) for group in self.optimiser.param_groups])
+        self._set(True if self._sgd else [True] * len(self._was))
+        if hasattr(self.optimiser, 'reserve_capture_tables'):
+            self.optimiser.reserve_capture_tables(self.n_captures)
+        return self
+
+    def __exit__(self, *exc):
+        self._set(self._was)
+
+    def checkpoint_state_dict(self):
+        """`optimiser.state_dict()` in the form the optimiser has OUTSIDE the window: a checkpoint written inside it
+        would otherwise carry capturable groups with device counters (a resumed run would silently be capturable -
+        another FusedClipAdam path, and torch's Adam asserts on CPU parameters). The groups get their own flags back
+        and the counters go to the host, as the reference's checkpoints hold them (:501-517)."""
+        sd = self.optimiser.state_dict()      # (its groups and its index -> state map are new dicts, the states the live ones)
+        for group, flag in zip(sd['param_groups'], [] if self._sgd else self._was):
+            group['capturable'] = flag
+            for idx in () if flag else group['params']:
+                st = sd['state'].get(idx)
+                if st is not None and torch.is_tensor(st.get('step')) and st['step'].is_cuda:
+                    sd['state'][idx] = dict(st, step=st['step'].detach().cpu())
+        return sd

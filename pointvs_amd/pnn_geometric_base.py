@@ -18,6 +18,20 @@ from .graph import prepare_graph, prepared_for, runs_layout
 from .point_neural_network_base import PointNeuralNetworkBase
 
 
+def batch_tables(graph, batch):
+    """(num_graphs, ptr: int64 node offsets) of a batch object: its own where it carries them, else derived from the
+    batch vector with data-dependent ops (a maximum read on the host - the reference syncs there too, torch.max(batch),
+    :27 - and a bincount). Whoever captures steps on the batch leaves them on it beforehand (StepReplayer)."""
+    n_graphs = getattr(graph, 'num_graphs', None)
+    if n_graphs is None:
+        n_graphs = int(batch.max()) + 1
+    ptr = getattr(graph, 'ptr', None)
+    if ptr is None:
+        counts = torch.bincount(batch, minlength=n_graphs)
+        ptr = torch.cat([counts.new_zeros(1), counts.cumsum(0)])
+    return n_graphs, ptr
+
+
 class PNNGeometricBase(PointNeuralNetworkBase):
     """Base class of the geometric point networks."""
 
@@ -46,13 +60,7 @@ class PNNGeometricBase(PointNeuralNetworkBase):
         """The batch as the layer stack takes it: (feats, edges, coords, edge_attributes, n_graphs, graph_ptr: device
         int32 node offsets, layout, pg: the PreparedGraph of a graph built on the GPU or None)."""
         feats, edges, coords, edge_attributes, batch = self.unpack_graph(graph)
-        n_graphs = getattr(graph, 'num_graphs', None)
-        if n_graphs is None:  # the reference syncs here too (torch.max(batch), :27)
-            n_graphs = int(batch.max()) + 1
-        ptr = getattr(graph, 'ptr', None)
-        if ptr is None:
-            counts = torch.bincount(batch, minlength=n_graphs)
-            ptr = torch.cat([counts.new_zeros(1), counts.cumsum(0)])
+        n_graphs, ptr = batch_tables(graph, batch)
         # (the node offsets as device int32: from the batch's cached layout tables where it has them, else converted
         # ONCE per batch object - two conversions and a gather per step were three launches of ~4 us each)
         layout = None if edges is None else runs_layout(graph, feats.device)
@@ -69,6 +77,13 @@ class PNNGeometricBase(PointNeuralNetworkBase):
         pg = getattr(graph, 'prepared', None)     # built on the GPU (radius_graph.attach_radius_graph)
         return feats, edges, coords, edge_attributes, n_graphs, graph_ptr, layout, pg
 
+    @staticmethod
+    def _coo_of(pg):
+        """A graph built on the GPU: its sorted list back as the COO (edges, one-hot attributes) the dropout draws from."""
+        e = pg.n_edges
+        return (torch.stack([pg.t['row'][:e].long(), pg.t['col'][:e].long()]),
+                None if pg.n_edge_attr == 0 else torch.nn.functional.one_hot(pg.t['etype'][:e].long(), pg.n_edge_attr))
+
     def _embed_graph(self, graph):
         feats, edges, coords, edge_attributes, n_graphs, graph_ptr, layout, pg = self._graph_inputs(graph)
         n_nodes = feats.size(0)
@@ -77,11 +92,8 @@ class PNNGeometricBase(PointNeuralNetworkBase):
                 and (pg.n_edges if pg is not None else int(edges.shape[1])) > 0):
             return self._embed_graph_static_dropout(graph, feats, edges, coords, edge_attributes, pg, graph_ptr, n_graphs)
         if dropping:      # edge dropout ahead of the layer stack (egnn_satorras.py:320-323): a new edge list
-            if pg is not None:    # graph built on the GPU: its sorted list back as the COO the dropout draws from
-                e = pg.n_edges
-                edges = torch.stack([pg.t['row'][:e].long(), pg.t['col'][:e].long()])
-                edge_attributes = (None if pg.n_edge_attr == 0 else
-                                   torch.nn.functional.one_hot(pg.t['etype'][:e].long(), pg.n_edge_attr))
+            if pg is not None:
+                edges, edge_attributes = self._coo_of(pg)
             edges, edge_attributes = self.edge_dropout(edges, edge_attributes)
             pg = prepared_for(edges, edge_attributes, n_nodes)
         elif pg is None:
@@ -127,11 +139,8 @@ class PNNGeometricBase(PointNeuralNetworkBase):
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError('static edge dropout: the batch has no plan yet and counting its row <= col edges is a host '
                                'read, which a capture cannot hold (visit the batch once outside the capture)')
-        if pg is not None:    # graph built on the GPU: its sorted list back as the COO the dropout draws from
-            e = pg.n_edges
-            edges = torch.stack([pg.t['row'][:e].long(), pg.t['col'][:e].long()])
-            edge_attributes = (None if pg.n_edge_attr == 0 else
-                               torch.nn.functional.one_hot(pg.t['etype'][:e].long(), pg.n_edge_attr))
+        if pg is not None:
+            edges, edge_attributes = self._coo_of(pg)
         edges = edges.long().contiguous()
         if edge_attributes is not None:
             edge_attributes = edge_attributes.long().contiguous()
@@ -165,14 +174,9 @@ class PNNGeometricBase(PointNeuralNetworkBase):
                                       'statistics (leave static_dropout off: the eager draw has no padding)')
         n_nodes = int(feats.size(0))
         st = self.static_dropout_state(graph, feats, edges, edge_attributes, pg, graph_ptr, n_graphs)
-        if not self.__dict__.get('_dropout_key_external'):     # (a replayer writes the key itself, outside its captures)
-            self.push_dropout_key(feats.device)
-        elif not self.__dict__.pop('_dropout_key_fresh', False):
-            raise RuntimeError('static edge dropout under a replayer: a second training forward within one step would '
-                               'draw the first one\'s mask again (the replayer writes one key per step)')
-        seed, step = self._dropout_key
+        (seed, step), key_table = self.dropout_keys.take(self, feats.device)
         out_index, out_attr, n_kept = PF.dropout_adj_padded(
-            st['edges'], st['attrs'], float(self.dropout_p), self._dropout_table, st['cap'], n_nodes, st['n_pad'],
+            st['edges'], st['attrs'], float(self.dropout_p), key_table, st['cap'], n_nodes, st['n_pad'],
             out=(st['out_index'], st['out_attr']))
         # prepare_graph, never prepared_for's cache: the static buffers are written through raw pointers, their tensor
         # _version never moves, and the cache would hand back the graph of an earlier draw

@@ -10,7 +10,6 @@ plain logging.
 """
 import contextlib
 import gc
-import itertools
 import math
 import os
 import re
@@ -26,7 +25,7 @@ from torch import nn
 
 from . import functional as PF
 from .global_objects import DEVICE
-from .optim import FusedClipAdam, FusedClipSGD
+from .optim import FusedClipAdam, FusedClipSGD, capturable_window
 
 
 def _rank_world():
@@ -62,193 +61,6 @@ def long_lived_heap_frozen():
 
 
 _FROZEN_DEPTH = 0
-
-class _StepReplayer:
-    """train_model(capture=True): whole training steps (graph preparation, forward, loss, backward, clip + optimiser) as
-    hipGraphs, one per batch that comes back with the same device tensors. A batch runs eagerly on its first visit
-    (which also warms up whatever its shapes need), is captured and replayed on its second, replayed from then on; at
-    most `max_graphs` batches are captured, the rest stay eager. Everything - eager steps too - runs on ONE side stream:
-    autograd's AccumulateGrad nodes remember the stream of their first backward, and a capture on another stream than
-    earlier eager steps faults in hipStreamEndCapture (ROCm 7.2 / torch 2.10; bench.py --graph 1 does the same).
-    The optimiser runs in its capturable form for the duration (Adam: step counters on the device, as torch's capturable
-    Adam keeps them; FusedClipAdam then forms the bias corrections in its kernel: optim.py) and is restored on close().
-    What a learning-rate scheduler changes between steps (lr; OneCycleLR: beta1 / momentum too) is no part of a capture:
-    the fused optimisers' kernels read it from device memory, and step() has the groups' current values written there
-    (`push_hyperparameters`, on the replayer's stream) before the capture and before every replay - an eager step does
-    that itself. `scheduler.step()` stays on the host, after the optimiser step (_train_epochs): a captured run's
-    rates are the eager run's, double for double.
-    Edge dropout is handled the same way: for the replayer's lifetime the model draws into an edge list of fixed shape
-    (`static_dropout`: PNNGeometricBase._embed_graph_static_dropout), keyed from a device table {seed, step} that step()
-    rewrites from the model's own schedule (`next_dropout_key`) before every step - a captured run draws the masks of the
-    same run taken eagerly with static_dropout on. Models with GraphNorm and dropout are refused."""
-
-    def __init__(self, model, max_graphs=64):
-        if not torch.cuda.is_available():
-            raise RuntimeError('train_model(capture=True) needs a GPU')
-        if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
-            raise NotImplementedError('train_model(capture=True) is single-process (the gradient exchange is not captured)')
-        if not isinstance(model.optimiser, (torch.optim.Adam, FusedClipSGD)):
-            raise TypeError(f'train_model(capture=True) replays FusedClipAdam, FusedClipSGD or torch.optim.Adam steps, '
-                            f'not {type(model.optimiser).__name__}')
-        self._push = getattr(model.optimiser, 'push_hyperparameters', None)
-        if model.scheduler is not None and self._push is None:
-            raise TypeError("train_model(capture=True) with a learning-rate scheduler needs one of the project's fused "
-                            'optimisers (torch.optim.Adam bakes a float rate into the captured step)')
-        if any(p.dtype == torch.float64 for p in model.parameters()):
-            raise NotImplementedError('train_model(capture=True) is fp32 only (fp64 trains eagerly)')
-        self._dropout = float(getattr(model, 'dropout_p', 0) or 0) > 0
-        if self._dropout and any(getattr(m, 'graphnorm', False) for m in model.modules()):
-            raise NotImplementedError('train_model(capture=True) does not cover edge dropout in a model with GraphNorm: a '
-                                      'captured step draws into an edge list of fixed shape whose unused slots join '
-                                      'padding nodes appended to the batch, and GraphNorm normalises over every row of the '
-                                      'batch, so the padding rows would enter its statistics (dropout > 0 with GraphNorm '
-                                      'trains eagerly; without GraphNorm it is captured)')
-        self.model, self.max_graphs = model, max_graphs
-        # one side stream per model, kept across calls (AccumulateGrad nodes remember the stream of their first backward)
-        if getattr(model, '_capture_stream', None) is None:
-            model._capture_stream = torch.cuda.Stream(DEVICE)
-        self.stream = model._capture_stream
-        self.seen, self.graphs = {}, {}
-        self.stats = {'eager': 0, 'captured': 0, 'replayed': 0}
-        model.last_capture_stats = self.stats
-        self._was, self._sgd_was = [], None
-        if isinstance(model.optimiser, FusedClipSGD):
-            # (a switch on the optimiser - no group option, no state: checkpoints written meanwhile need no care)
-            self._sgd_was, model.optimiser.capturable = model.optimiser.capturable, True
-        else:
-            model._capturable_was = self._was       # save() writes the optimiser's OWN form, not the replayer's
-            for group in model.optimiser.param_groups:
-                self._was.append(group.get('capturable', False))
-                group['capturable'] = True
-                for p in group['params']:
-                    st = model.optimiser.state.get(p)
-                    if st and isinstance(st.get('step'), torch.Tensor) and not st['step'].is_cuda:
-                        st['step'] = st['step'].to(device=p.device, dtype=torch.float32)
-        model.optimiser._fast = None
-        if hasattr(model.optimiser, 'reserve_capture_tables'):
-            model.optimiser.reserve_capture_tables(max_graphs)
-        # edge dropout: the static-shape draw for the replayer's lifetime (eager visits too: one arithmetic for every
-        # step of the run), keyed from the model's device table, which step() rewrites before every step
-        self._static_was = (model.__dict__.get('static_dropout', None), 'static_dropout' in model.__dict__)
-        if self._dropout:
-            model.static_dropout = True
-            model.__dict__['_dropout_key_external'] = True
-
-    def _push_dropout_key(self):
-        """The key the eager step would draw with now (the model's own schedule), into the device table the captured
-        draw reads: on the replayer's stream, outside the capture - as push_hyperparameters does for the rates."""
-        if self._dropout and self.model.training:
-            return self.model.push_dropout_key(next(self.model.parameters()).device)
-        return None
-
-    def close(self):
-        torch.cuda.current_stream(DEVICE).wait_stream(self.stream)
-        self.graphs.clear()
-        if self._dropout:
-            self.model.__dict__.pop('_dropout_key_external', None)
-            if self._static_was[1]:
-                self.model.static_dropout = self._static_was[0]
-            else:
-                self.model.__dict__.pop('static_dropout', None)
-        opt = self.model.optimiser
-        if self._sgd_was is not None:
-            opt.capturable = self._sgd_was
-        for group, was in zip(opt.param_groups, self._was):
-            group['capturable'] = was
-            if not was:
-                for p in group['params']:
-                    st = opt.state.get(p)
-                    if st and isinstance(st.get('step'), torch.Tensor) and st['step'].is_cuda:
-                        st['step'] = st['step'].cpu()
-        opt._fast = None
-        self.model._capturable_was = None
-
-    _batch_ids = itertools.count(1)
-
-    @classmethod
-    def _key(cls, graph, task):
-        """A batch is 'the same batch again' when it is the same OBJECT with the same device tensors at the same
-        versions: the object carries an id stamped on its first visit (a streaming loader that yields fresh batch
-        objects whose tensors happen to reuse freed addresses is never taken for a second visit)."""
-        try:
-            bid = graph.__dict__.get('_pvs_batch_id')
-            if bid is None:
-                bid = graph.__dict__['_pvs_batch_id'] = next(cls._batch_ids)
-        except AttributeError:
-            return None
-        key = [task, bid]
-        for name in ('x', 'pos', 'edge_index', 'edge_attr', 'batch', 'y'):
-            t = getattr(graph, name, None)
-            if t is None:
-                key.append(None)
-                continue
-            if not torch.is_tensor(t) or not t.is_cuda:
-                return None                  # host tensors are copied to new device tensors every step: nothing to replay
-            key.append((t.data_ptr(), t._version, tuple(t.shape)))
-        return tuple(key)
-
-    def _eager(self, graph):
-        y_pred, y_true, _, _ = self.model.unpack_input_data_and_predict(graph)
-        return self.model.backprop(y_true, y_pred, sync=False)
-
-    @staticmethod
-    def _make_capturable(graph, model=None):
-        """What the forward would otherwise derive from the batch vector with data-dependent ops (a bincount, a
-        maximum read on the host): done once, outside any capture, and left on the batch object. With a model that
-        draws its edge dropout into a fixed shape, the draw's plan as well (plan_static_dropout: its count of
-        row <= col edges is the one host read of that path)."""
-        batch = getattr(graph, 'batch', None)
-        if batch is None:
-            return
-        if getattr(graph, 'num_graphs', None) is None:
-            graph.num_graphs = int(batch.max()) + 1
-        if getattr(graph, 'ptr', None) is None:
-            counts = torch.bincount(batch, minlength=graph.num_graphs)
-            graph.ptr = torch.cat([counts.new_zeros(1), counts.cumsum(0)])
-        if model is not None and model.training and getattr(model, 'static_dropout', None) \
-                and float(getattr(model, 'dropout_p', 0) or 0) > 0:
-            model.plan_static_dropout(graph)
-
-    def step(self, graph):
-        from . import graph as pgraph
-        key = self._key(graph, self.model.model_task)
-        hit = self.graphs.get(key) if key is not None else None
-        drawn = self._push_dropout_key()      # (every step of the run advances the schedule once, as the eager loop does)
-        if hit is not None:
-            if self._push is not None:
-                self._push()
-            hit[0].replay()
-            self.stats['replayed'] += 1
-            if hit[3] is not None and drawn is not None:      # the captured step's buffers, drawn with this step's key
-                self.model.last_dropout = dict(hit[3], seed=drawn[0], step=drawn[1])
-            return hit[1].clone()
-        visits = self.seen.get(key, 0) if key is not None else 0
-        if key is None or visits == 0 or len(self.graphs) >= self.max_graphs:
-            if key is not None:
-                self.seen[key] = visits + 1
-                self._make_capturable(graph, self.model)
-            self.stats['eager'] += 1
-            return self._eager(graph)
-        # second visit: capture. The batch's CSR / CSC preparation is captured too (its tensors then live in the
-        # graph's private pool: a cached PreparedGraph could be evicted and freed under the captured launches).
-        cache_was, pgraph.CACHE_ENABLED = pgraph.CACHE_ENABLED, False
-        try:
-            self.stream.synchronize()
-            if self._push is not None:
-                self._push()                 # (outside the capture: what the replay just below runs at)
-            hip_graph = torch.cuda.CUDAGraph()
-            self.model.__dict__.pop('last_dropout', None)
-            with torch.cuda.graph(hip_graph, stream=self.stream):
-                static_loss = self._eager(graph)
-        finally:
-            pgraph.CACHE_ENABLED = cache_was
-        # (holds the batch: its addresses stay unique; the captured draw's buffers, which every replay rewrites; and the
-        # batch's dropout plan, whose tensors the captured launches read - a plan replaced on the batch later stays alive)
-        self.graphs[key] = (hip_graph, static_loss, graph, self.model.__dict__.get('last_dropout') if self._dropout else None,
-                            getattr(graph, '__dict__', {}).get('_pvs_static_dropout') if self._dropout else None)
-        hip_graph.replay()
-        self.stats['captured'] += 1
-        return static_loss.clone()
 
 
 class PointNeuralNetworkBase(nn.Module):
@@ -371,29 +183,42 @@ class PointNeuralNetworkBase(nn.Module):
         `log_interval` steps.
         capture=True (no reference counterpart, opt-in): batches that COME BACK - the same device tensors epoch after
         epoch, e.g. a list of pre-collated batches resident on the GPU - are replayed from a hipGraph of their whole
-        step from their third visit on (`_StepReplayer`). For small graphs the eager step is bound by the host
-        (~70 launches of a few microseconds: 16.8k -> 25.7k graphs/s at the reference's default shape,
-        profiles/r05_real_shape.txt); for BASELINE-size batches it buys nothing. Works with either optimiser the
-        constructor builds (Adam, SGD) and under either scheduler (`use_1cycle`, `warm_restarts`): the fused optimisers
-        read lr, betas / momentum from device memory, rewritten from the host's values before every replay, so the rates
-        of a captured run are the eager run's. Single process, fp32; anything else raises. Edge dropout (dropout > 0)
-        is captured with a fixed-shape draw (`static_dropout`, on for the duration: the dropped list padded to its
-        capacity with inert edges between padding nodes, the key read from a device table that is rewritten before every
-        replay - the masks are those of the same run with capture=False and static_dropout=True); a model with GraphNorm
-        and dropout raises, since the padding rows would enter the norm's statistics."""
+        step from their third visit on (captured_step.StepReplayer). For small graphs the eager step is bound by the
+        host (~70 launches of a few microseconds: 16.8k -> 25.7k graphs/s at the reference's default shape,
+        profiles/r05_real_shape.txt); for BASELINE-size batches it buys nothing. Either optimiser the constructor
+        builds, either scheduler: the rates of a captured run are the eager run's. With dropout > 0 the masks are those
+        of the same run with capture=False and static_dropout=True. Single process, fp32, no GraphNorm together with
+        dropout; anything else raises."""
         init_epoch, _ = self.training_setup(data_loader=data_loader, epochs=epochs)
-        if capture:
-            replayer = _StepReplayer(self)
-            try:
-                with torch.cuda.stream(replayer.stream), long_lived_heap_frozen():
-                    return self._train_epochs(data_loader, init_epoch, epochs, epoch_end_validation_set, top1_on_end,
-                                              replayer)
-            finally:
-                replayer.close()
-        with long_lived_heap_frozen():
-            return self._train_epochs(data_loader, init_epoch, epochs, epoch_end_validation_set, top1_on_end, None)
+        if not capture:
+            with long_lived_heap_frozen():
+                return self._train_epochs(data_loader, init_epoch, epochs, epoch_end_validation_set, top1_on_end,
+                                          self.training_step)
+        from .captured_step import StepReplayer
+        with StepReplayer(self) as replayer, torch.cuda.stream(replayer.stream), long_lived_heap_frozen():
+            return self._train_epochs(data_loader, init_epoch, epochs, epoch_end_validation_set, top1_on_end, replayer.step)
 
-    def _train_epochs(self, data_loader, init_epoch, epochs, epoch_end_validation_set, top1_on_end, replayer):
+    def training_step(self, graph):
+        """Predict + one optimisation step on one batch; the loss as a device tensor (backprop(sync=False))."""
+        y_pred, y_true, _, _ = self.unpack_input_data_and_predict(graph)
+        if hasattr(self.grad_sync, 'set_weight'):     # uneven shards: weight by local graphs
+            self.grad_sync.set_weight(float(y_pred.numel()))
+        return self.backprop(y_true, y_pred, sync=False)
+
+    # the optimiser's open capturable window (optim.capturable_window), None outside one: save() asks it for the
+    # optimiser's own form
+    optimiser_window = None
+
+    @contextlib.contextmanager
+    def optimiser_capturable(self, n_captures):
+        """The optimiser in its capturable form for the duration (captured training)."""
+        with capturable_window(self.optimiser, n_captures) as self.optimiser_window:
+            try:
+                yield self.optimiser_window
+            finally:
+                self.optimiser_window = None
+
+    def _train_epochs(self, data_loader, init_epoch, epochs, epoch_end_validation_set, top1_on_end, step):
         losses = []
         sampler = getattr(data_loader, 'sampler', None)
         for epoch in range(init_epoch, epochs):
@@ -402,13 +227,7 @@ class PointNeuralNetworkBase(nn.Module):
                 sampler.set_epoch(epoch)
             pending = []
             for self.batch, graph in enumerate(data_loader):
-                if replayer is not None:
-                    pending.append(replayer.step(graph))
-                else:
-                    y_pred, y_true, _, _ = self.unpack_input_data_and_predict(graph)
-                    if hasattr(self.grad_sync, 'set_weight'):     # uneven shards: weight by local graphs
-                        self.grad_sync.set_weight(float(y_pred.numel()))
-                    pending.append(self.backprop(y_true, y_pred, sync=False))
+                pending.append(step(graph))
                 if self.scheduler is not None:
                     self.scheduler.step()
                 self.global_iter += 1
@@ -491,33 +310,9 @@ class PointNeuralNetworkBase(nn.Module):
             'learning_rate': self.lr, 'weight_decay': self.weight_decay,
             'p_epoch': self.p_epoch, 'a_epoch': self.a_epoch,
             'model_state_dict': self.state_dict(),
-            'optimiser_state_dict': self._optimiser_state_for_checkpoint()}, save_path)
-
-    def _optimiser_state_for_checkpoint(self):
-        """`optimiser.state_dict()` in the form the optimiser has OUTSIDE train_model(capture=True): the replayer
-        flips every group to `capturable=True` with the step counters on the device for the duration of the call, and a
-        checkpoint written at an epoch end in between would carry that (a resumed run would silently be capturable -
-        another FusedClipAdam path, and torch's Adam asserts on CPU parameters). The groups get their own flags back
-        and the counters go to the host, as the reference's checkpoints hold them (:501-517)."""
-        sd = self.optimiser.state_dict()
-        was = getattr(self, '_capturable_was', None)
-        if not was:
-            return sd
-        groups = []
-        for group, flag in zip(sd['param_groups'], was):
-            group = dict(group)
-            group['capturable'] = flag
-            groups.append(group)
-            if flag:
-                continue
-            for idx in group['params']:
-                st = sd['state'].get(idx)
-                if st is not None and torch.is_tensor(st.get('step')) and st['step'].is_cuda:
-                    st = dict(st)
-                    st['step'] = st['step'].detach().cpu()
-                    sd['state'][idx] = st
-        sd['param_groups'] = groups
-        return sd
+            # (inside train_model(capture=True): the optimiser's own form, not the capturable one it is in meanwhile)
+            'optimiser_state_dict': (self.optimiser.state_dict() if self.optimiser_window is None else
+                                     self.optimiser_window.checkpoint_state_dict())}, save_path)
 
     @staticmethod
     def _transform_names(d):

@@ -92,11 +92,11 @@ def _schedule_owner(**counters):
 
 
 def test_the_key_function_is_the_eager_schedule(monkeypatch):
-    """next_dropout_key: seed = torch.initial_seed() (+ the rank's multiple of the golden ratio), step =
+    """DropoutKeys.next (model.next_dropout_key forwards to it): seed = torch.initial_seed() (+ the rank's multiple of the golden ratio), step =
     _mix64(_mix64(base) + calls) with base = (epochs << 24) + global_iter and calls counted from 1 under one base."""
-    from pointvs_amd.egnn_satorras import SartorrasEGNN, _mix64
+    from pointvs_amd.egnn_satorras import DropoutKeys, _mix64
     torch.manual_seed(77)
-    owner = _schedule_owner()
+    owner, keys = _schedule_owner(), DropoutKeys()
     got, want, calls, base_was = [], [], 0, None
     for bump in (None, None, None, 'global_iter', 'p_epoch', 'a_epoch', 'global_iter', None):
         if bump:
@@ -104,25 +104,24 @@ def test_the_key_function_is_the_eager_schedule(monkeypatch):
         base = ((owner.p_epoch + owner.a_epoch) << 24) + owner.global_iter
         calls = calls + 1 if base == base_was else 1
         base_was = base
-        got.append(SartorrasEGNN.next_dropout_key(owner))
+        got.append(keys.next(owner))
         want.append((77, _mix64(_mix64(base) + calls)))
     assert got == want and len({s for _, s in got}) == len(got)
-    assert (owner._dropout_base, owner._dropout_calls) == ((2 << 24) + 2, 2)
+    assert (keys.base, keys.calls) == ((2 << 24) + 2, 2)
     # a training loop: one draw per optimiser step
-    owner = _schedule_owner()
+    owner, keys = _schedule_owner(), DropoutKeys()
     loop = []
     for _ in range(4):
-        loop.append(SartorrasEGNN.next_dropout_key(owner))
+        loop.append(keys.next(owner))
         owner.global_iter += 1
     assert loop == [(77, _mix64(_mix64(it) + 1)) for it in range(4)]
     # the same counters give the same keys again; another torch seed another seed, the same steps
-    again = _schedule_owner()
-    assert SartorrasEGNN.next_dropout_key(again) == loop[0]
+    assert DropoutKeys().next(_schedule_owner()) == loop[0]
     torch.manual_seed(78)
-    assert SartorrasEGNN.next_dropout_key(_schedule_owner()) == (78, loop[0][1])
+    assert DropoutKeys().next(_schedule_owner()) == (78, loop[0][1])
     monkeypatch.setattr(torch.distributed, 'is_initialized', lambda: True)
     monkeypatch.setattr(torch.distributed, 'get_rank', lambda *a, **k: 3)
-    seed, step = SartorrasEGNN.next_dropout_key(_schedule_owner())
+    seed, step = DropoutKeys().next(_schedule_owner())
     assert seed == (78 + 3 * 0x9E3779B97F4A7C15) % 2 ** 64 and step == loop[0][1]
 
 

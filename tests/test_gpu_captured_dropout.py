@@ -327,7 +327,7 @@ def test_captured_training_with_edge_dropout_draws_the_eager_schedules_masks(tmp
         lists = [d[2] for d in loader.drawn if d[0] == id(batch)]
         assert len(lists) == 4 and len(set(lists)) == 4
     assert any(not torch.equal(p, before[n]) for n, p in model.named_parameters())
-    assert model.__dict__.get('static_dropout') is None and '_dropout_key_external' not in model.__dict__
+    assert model.__dict__.get('static_dropout') is None and not model.dropout_keys.is_external
     assert not torch.cuda.is_current_stream_capturing()
 
 
@@ -448,15 +448,15 @@ def test_the_switch_refuses_a_graphnorm_model_on_the_eager_path_too(tmp_path):
 def test_one_key_serves_one_forward_when_a_replayer_writes_the_keys(tmp_path):
     model, _ = _model(tmp_path, graphnorm=False)
     dev = _two_graphs().to('cuda')
-    model.static_dropout = True
-    model.__dict__['_dropout_key_external'] = True
     _restart(model, seed=21, global_iter=5)
-    model.push_dropout_key(dev.x.device)
-    _training_step(model, dev)
-    with pytest.raises(RuntimeError, match='second training forward'):
+    with model.dropout_keys.external(model):
+        assert model.static_dropout is True
+        model.push_dropout_key(dev.x.device)
         _training_step(model, dev)
-    model.push_dropout_key(dev.x.device)
-    _training_step(model, dev)
+        with pytest.raises(RuntimeError, match='second training forward'):
+            _training_step(model, dev)
+        model.push_dropout_key(dev.x.device)
+        _training_step(model, dev)
     from pointvs_amd.egnn_satorras import _mix64
     assert model.last_dropout['step'] == _mix64(_mix64(5) + 2)
 
@@ -467,12 +467,12 @@ def test_the_plan_is_made_ahead_of_the_step_and_lives_with_the_captured_graph(tm
     offsets there, the pooling shortcut reads THAT tensor, and the replayer's entry keeps the plan alive - nothing a
     captured step reads belongs to a cache that could drop it."""
     from pointvs_amd.pnn_geometric_base import PNNGeometricBase
-    from pointvs_amd.point_neural_network_base import _StepReplayer
+    from pointvs_amd.captured_step import StepReplayer
     model, _ = _model(tmp_path, graphnorm=False)
     two, one = _batches()
     model.static_dropout = True
-    _StepReplayer._make_capturable(two, model)
-    _StepReplayer._make_capturable(one, model)
+    StepReplayer._make_capturable(two, model)
+    StepReplayer._make_capturable(one, model)
     plan2, plan1 = two.__dict__['_pvs_static_dropout'], one.__dict__['_pvs_static_dropout']
     assert (plan2['n_half'], plan2['cap'], plan2['n_pad'], plan2['whole']) == (1235, 2470, 52, None)
     assert (plan1['n_half'], plan1['cap'], plan1['n_pad']) == (40, 80, 8) and plan1['whole'].tolist() == [0, 30]
@@ -484,16 +484,39 @@ def test_the_plan_is_made_ahead_of_the_step_and_lives_with_the_captured_graph(tm
     assert PNNGeometricBase._whole_ptr(feats[:20], plan1['whole']).tolist() == [0, 20]
     model.static_dropout = None
     _restart(model, seed=77)
-    replayer = _StepReplayer(model)
-    try:
-        with torch.cuda.stream(replayer.stream):
-            for _ in range(3):
-                for batch in (two, one):
-                    replayer.step(batch)
-                model.global_iter += 1
-            assert replayer.stats == {'eager': 2, 'captured': 2, 'replayed': 2}
-            entries = {id(e[2]): e for e in replayer.graphs.values()}
-            assert entries[id(one)][4] is plan1 and entries[id(two)][4] is plan2
-            assert one.__dict__['_pvs_static_dropout'] is plan1, 'the visits reuse the plan made ahead of them'
-    finally:
-        replayer.close()
+    with StepReplayer(model) as replayer, torch.cuda.stream(replayer.stream):
+        for _ in range(3):
+            for batch in (two, one):
+                replayer.step(batch)
+            model.global_iter += 1
+        assert replayer.stats == {'eager': 2, 'captured': 2, 'replayed': 2}
+        entries = {id(e.batch): e for e in replayer.graphs.values()}
+        assert entries[id(one)].plan is plan1 and entries[id(two)].plan is plan2
+        assert one.__dict__['_pvs_static_dropout'] is plan1, 'the visits reuse the plan made ahead of them'
+
+
+@needs_caching_allocator
+def test_a_step_that_raises_leaves_model_and_optimiser_as_before_the_run(tmp_path):
+    """The loader's fifth item is a batch without `y`: unpack_input_data_and_predict raises AttributeError on its first
+    line, before any launch, in the eager visit of a run that has two captured graphs. The replayer's windows close on
+    the way out, and the next captured run is an ordinary one."""
+    import copy
+    model, _ = _model(tmp_path, graphnorm=False)
+    good = _batches()
+    broken = copy.copy(good[0])
+    del broken.y
+    _restart(model, seed=77)
+    flags = [g.get('capturable', False) for g in model.optimiser.param_groups]
+    assert not any(flags) and model.optimiser_window is None
+    with pytest.raises(AttributeError, match="'y'"):
+        model.train_model(good * 2 + [broken], epochs=1, capture=True)
+    assert model.last_capture_stats == {'eager': 3, 'captured': 2, 'replayed': 0} and model.global_iter == 4
+    assert [g.get('capturable', False) for g in model.optimiser.param_groups] == flags
+    counters = [st['step'] for st in model.optimiser.state.values()]
+    assert counters and all(not c.is_cuda and c.dtype == torch.float32 and float(c) == 4.0 for c in counters)
+    assert 'static_dropout' not in model.__dict__ and not model.dropout_keys.is_external
+    assert model.optimiser_window is None
+    assert not torch.cuda.is_current_stream_capturing()
+    losses = model.train_model(good * 3, epochs=1, capture=True)
+    assert model.last_capture_stats == {'eager': 2, 'captured': 2, 'replayed': 2}
+    assert len(losses) == 6 and np.isfinite([float(v) for v in losses]).all()

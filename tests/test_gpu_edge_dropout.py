@@ -329,7 +329,7 @@ def _record_draws(monkeypatch):
 def _restart(model, seed, global_iter=0):
     torch.manual_seed(seed)
     model.global_iter, model.p_epoch, model.a_epoch = global_iter, 0, 0
-    model._dropout_base, model._dropout_calls = None, 0
+    model.dropout_keys.base, model.dropout_keys.calls = None, 0
 
 
 def _assert_call_equals_reference(call):

@@ -1117,10 +1117,10 @@ def test_model_with_edge_dropout_trains_and_is_the_plain_model_in_eval():
     assert np.array_equal(y_plain, y_eval)
     drop.train()
     torch.manual_seed(9)
-    drop._dropout_calls = 0
+    drop.dropout_keys.calls = 0
     y1, g1 = gpu_run(drop, g)
     y2, _ = gpu_run(drop, g)
-    drop._dropout_calls = 0
+    drop.dropout_keys.calls = 0
     y1b, _ = gpu_run(drop, g)
     assert np.array_equal(y1, y1b) and not np.array_equal(y1, y2) and not np.array_equal(y1, y_plain)
     assert all(np.isfinite(v).all() for v in g1.values() if v is not None)

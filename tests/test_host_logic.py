@@ -600,28 +600,35 @@ def test_layer_parameter_cache_is_validated_slot_by_slot_and_never_copied():
     assert '_pcache' not in again.__dict__ and [k for k, _ in again.named_parameters()] == [k for k, _ in layer.named_parameters()]
 
 
-def test_checkpoints_written_under_capture_hold_the_optimisers_own_form(tmp_path):
-    """while train_model(capture=True) runs, the replayer has every optimiser group flipped to capturable
-    with device step counters; a checkpoint written at an epoch end in between must carry the groups' OWN flags (and host
-    counters: tests/test_gpu_training_trajectory.py checks those on the device), like the reference's files."""
+def test_checkpoints_written_under_capture_hold_the_optimisers_own_form(tmp_path, monkeypatch):
+    """while train_model(capture=True) runs, the optimiser's capturable window is open: every group flipped
+    to capturable with device step counters; a checkpoint written at an epoch end in between must carry the groups' OWN
+    flags (and host counters: tests/test_gpu_training_trajectory.py checks those on the device), like the reference's
+    files. After the window everything is as before it."""
     from pointvs_amd.egnn_satorras import SartorrasEGNN
     from pointvs_amd.synthetic import CONFIGS
     model = SartorrasEGNN(tmp_path, 2e-3, 1e-4, silent=True, **CONFIGS['cfg2']['model'])
     for p in model.parameters():
         p.grad = torch.zeros_like(p)
     model.optimiser.step()
-    plain = model._optimiser_state_for_checkpoint()
+    def form():
+        return ([g.get('capturable') for g in model.optimiser.param_groups],
+                [(st['step'].device, st['step'].dtype) for st in model.optimiser.state.values()])
+    plain, before = model.optimiser.state_dict(), form()
+    assert model.optimiser_window is None and len(before[1]) == len(list(model.parameters()))
     assert not any(g.get('capturable') for g in plain['param_groups'])
-    model._capturable_was = [g.get('capturable', False) for g in model.optimiser.param_groups]       # what _StepReplayer does
-    for g in model.optimiser.param_groups:
-        g['capturable'] = True
-    under = model._optimiser_state_for_checkpoint()
-    assert not any(g.get('capturable') for g in under['param_groups'])
-    assert all(g['capturable'] for g in model.optimiser.param_groups)             # the live optimiser is untouched
-    assert under['state'].keys() == plain['state'].keys()
-    model.save(tmp_path / 'ck.pt')
-    ck = torch.load(tmp_path / 'ck.pt', weights_only=False)
-    assert not any(g.get('capturable') for g in ck['optimiser_state_dict']['param_groups'])
+    # (the window's pinned pointer tables need a GPU)
+    monkeypatch.setattr(type(model.optimiser), 'reserve_capture_tables', lambda self, k: None)
+    with model.optimiser_capturable(4) as window:       # what StepReplayer enters
+        assert model.optimiser_window is window
+        under = window.checkpoint_state_dict()
+        assert not any(g.get('capturable') for g in under['param_groups'])
+        assert all(g['capturable'] for g in model.optimiser.param_groups)             # the live optimiser is untouched
+        assert under['state'].keys() == plain['state'].keys()
+        model.save(tmp_path / 'ck.pt')
+        ck = torch.load(tmp_path / 'ck.pt', weights_only=False)
+        assert not any(g.get('capturable') for g in ck['optimiser_state_dict']['param_groups'])
+    assert model.optimiser_window is None and form() == before
 
 
 def test_stack_plan_lays_the_gradients_of_all_layers_out_in_one_buffer():
