@@ -438,6 +438,46 @@ int pvs_complex_edges(int32_t n_nodes, int32_t n_edges, int32_t n_graphs, const 
                       const int32_t* col, const uint8_t* etype, const int32_t* perm, int64_t* edge_index,
                       int64_t* edge_attr, int32_t* status, pvs_stream_t stream);
 
+/* Complex batches at fixed capacities (forward only): the node tables and the CSR of a batch whose sizes never reach the
+ * host, so that one captured step serves every batch of a types file. Every size below is a capacity chosen by the host;
+ * the launches depend on the capacities alone; no allocation, no host synchronisation, bitwise reproducible.
+ * pvs_complex_batch_build_cap = pvs_complex_batch_count + the running sum of its counts + pvs_complex_batch_fill, bit for
+ *   bit: pairs [B,3] as above (a static device buffer the caller rewrites), atoms_in_cap >= the batch's input atoms
+ *   (workspace: pvs_complex_batch_workspace_bytes(B, atoms_in_cap)). Outputs: counts [B,2], node_ptr [B+1] (device),
+ *   x [node_cap,F], pos [node_cap,3], pos_graph [node_cap,3] or NULL, bp [node_cap], node_graph [node_cap] int32 (the
+ *   sample of every row). Rows at or behind node_ptr[B] are padding: zeros, node_graph -1. Every row of every output is
+ *   written by every call. *status is reset, then bits 0-3 as for _count / _fill, and
+ *     PVS_CAP_NODE_OVERFLOW   more nodes than node_cap: the samples that end behind node_cap are left out whole (their
+ *                             rows are padding); node_ptr keeps the true offsets
+ *     PVS_CAP_EMPTY_SAMPLE    a sample with no atom left after crop and hydrogen filter
+ * pvs_radius_graph_build_cap = pvs_radius_graph_count + _fill over node_cap rows with graph_ptr = that device node_ptr:
+ *   rowptr [node_cap+1], row / col / etype [edge_cap], inv_deg [node_cap], in-row order as _fill (inter entries by
+ *   ascending column, then intra entries); no perm, no by-column lists. Rows at or behind graph_ptr[B] have degree 0,
+ *   inv_deg 1 and rowptr = E, so rowptr[node_cap] is the edge count. n_edges_fwd [1] (device) is the count to hand to a
+ *   forward (PvsGraph.n_edges_dev): E where row / col / etype were written, 0 on any of the three overflows below, whose
+ *   row / col / etype are an earlier call's and do not belong to this rowptr. state:
+ *   pvs_radius_graph_state_bytes(node_cap, n_graphs, graph_node_cap). *status is reset first when reset_status != 0
+ *   (0: the word of the node call goes on), then
+ *     PVS_CAP_NODE_OVERFLOW   graph_ptr is no offset table inside node_cap rows
+ *     PVS_CAP_GRAPH_OVERFLOW  a graph of more than graph_node_cap nodes (either: rowptr all 0, inv_deg all 1)
+ *     PVS_CAP_EDGE_OVERFLOW   more than edge_cap edges: rowptr and inv_deg hold the true counts
+ *   On any of the three nothing is written to row / col / etype. No access leaves a buffer whatever the tables hold. */
+#define PVS_CAP_NODE_OVERFLOW 32
+#define PVS_CAP_GRAPH_OVERFLOW 64
+#define PVS_CAP_EDGE_OVERFLOW 128
+#define PVS_CAP_EMPTY_SAMPLE 256
+int pvs_complex_batch_build_cap(const PvsComplexPool* pool, const int32_t* pairs, const double* lig_xform,
+                                const double* rot, int32_t n_samples, int32_t atoms_in_cap, int32_t node_cap,
+                                double radius, int32_t keep_hydrogens, int32_t use_atomic_numbers, int32_t n_features,
+                                int32_t compact, const int32_t* class_of_z, int32_t* counts, int32_t* node_ptr, float* x,
+                                float* pos, float* pos_graph, uint8_t* bp, int32_t* node_graph, int32_t* status,
+                                void* workspace, size_t workspace_bytes, pvs_stream_t stream);
+int pvs_radius_graph_build_cap(const float* pos, const uint8_t* bp, const int32_t* graph_ptr, int32_t n_graphs,
+                               int32_t node_cap, int32_t graph_node_cap, double inter_radius, double intra_radius,
+                               int32_t pair_filter, int32_t edge_cap, int32_t* rowptr, int32_t* row, int32_t* col,
+                               uint8_t* etype, float* inv_deg, int32_t* n_edges_fwd, int32_t* status,
+                               int32_t reset_status, void* state, size_t state_bytes, pvs_stream_t stream);
+
 /* Leave-out graph batch of masking attribution (the reference's atom_masking / bond_masking loops,
  * attribution/attribution_fns.py:39-115, 356-456, which rebuild one masked edge list per atom on the host).
  * `parent`: the prepared graph of ONE complex (rowptr / col / etype; host-side edge count); drop [n_masks, 2] int32:

@@ -268,20 +268,33 @@ def main(argv=None):
         from pointvs_amd.distributed import OverlappedGradAllReducer
         model.grad_sync = OverlappedGradAllReducer(list(model.parameters()))
 
+    def capture_val(loader):
+        """--capture_val: for the loaders that have a fixed-shape batch builder (parquet data roots); asked for
+        anything else it is an error, not a silent eager run."""
+        if loader is None or not getattr(args, 'capture_val', False):
+            return False
+        from pointvs_amd.parquet_data import ComplexLoader
+        if not isinstance(loader, ComplexLoader):
+            raise SystemExit('--capture_val scores parquet data roots (a types file over receptors/ and ligands/); '
+                             'this run validates on another kind of data')
+        return True
+
     if args.epochs_pose and train_pose is not None:
         model.set_task('classification')
         model.train_model(train_pose, epochs=args.epochs_pose, top1_on_end=args.top1,
-                          epoch_end_validation_set=test_pose if args.val_on_epoch_end else None)
+                          epoch_end_validation_set=test_pose if args.val_on_epoch_end else None,
+                          capture_val=capture_val(test_pose))
     if test_pose is not None:
         model.set_task('classification')
-        model.val(test_pose, top1_on_end=args.top1)
+        model.val(test_pose, top1_on_end=args.top1, capture=capture_val(test_pose))
     if args.epochs_affinity and train_aff is not None:
         model.set_task(regression_task)
         model.train_model(train_aff, epochs=args.epochs_affinity, top1_on_end=args.top1,
-                          epoch_end_validation_set=test_aff if args.val_on_epoch_end else None)
+                          epoch_end_validation_set=test_aff if args.val_on_epoch_end else None,
+                          capture_val=capture_val(test_aff))
     if test_aff is not None:
         model.set_task(regression_task)
-        model.val(test_aff, top1_on_end=args.top1)
+        model.val(test_aff, top1_on_end=args.top1, capture=capture_val(test_aff))
     if args.end_flag and rank == 0:
         (save_path / '_FINISHED').write_text('')
     if world > 1:

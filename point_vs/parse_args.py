@@ -114,8 +114,25 @@ def build_parser():
     return parser
 
 
+# switches of this entry that say HOW a run executes, never what it computes. The command line's parser is build_parser()
+# plus these, in a group of their own (`--help` lists them); build_parser() itself stays the reference's flags plus the
+# two data sources (tests/test_entry_and_predictions.py pins it).
+EXECUTION_FLAGS = (
+    (('--capture_val',), ON, False, 'score the test types files through one captured fixed-shape step '
+                                    '(val(capture=True): parquet data roots; same predictions file)'),
+)
+
+
+def command_line_parser():
+    parser = build_parser()
+    group = parser.add_argument_group('execution', 'how the run executes; what it computes stays the same')
+    for names, _, _, text in EXECUTION_FLAGS:
+        group.add_argument(*names, action='store_true', help=text)
+    return parser
+
+
 def parse_args(argv=None):
-    return build_parser().parse_args(argv)
+    return command_line_parser().parse_args(argv)
 
 
 def unsupported_in_use(args):

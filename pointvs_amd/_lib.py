@@ -66,6 +66,8 @@ class PvsHead(C.Structure):
 
 
 HEAD_NONE, HEAD_RELU, HEAD_SOFTPLUS = 0, 1, 2       # PVS_HEAD_* (pvs_egnn.h)
+# PVS_CAP_* (pvs_egnn.h): status bits of the capacity batch builders
+CAP_NODE_OVERFLOW, CAP_GRAPH_OVERFLOW, CAP_EDGE_OVERFLOW, CAP_EMPTY_SAMPLE = 32, 64, 128, 256
 MAX_POOL_HEADS = 4
 
 
@@ -139,6 +141,12 @@ _PROTOTYPES = {
     'pvs_complex_batch_fill': (C.c_int, [C.POINTER(PvsComplexPool), C.c_void_p, C.c_void_p, C.c_void_p] +
                                [C.c_int32] * 6 + [C.c_void_p] * 9 + [C.c_void_p, C.c_size_t, C.c_void_p]),
     'pvs_complex_edges': (C.c_int, [C.c_int32] * 3 + [C.c_void_p] * 12),
+    'pvs_complex_batch_build_cap': (C.c_int, [C.POINTER(PvsComplexPool), C.c_void_p, C.c_void_p, C.c_void_p] +
+                                    [C.c_int32] * 3 + [C.c_double] + [C.c_int32] * 4 + [C.c_void_p] * 9 +
+                                    [C.c_void_p, C.c_size_t, C.c_void_p]),
+    'pvs_radius_graph_build_cap': (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 3 + [C.c_double, C.c_double, C.c_int32,
+                                                                                  C.c_int32] + [C.c_void_p] * 7 +
+                                   [C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
     'pvs_graph_filter_workspace_bytes': (C.c_size_t, [C.c_int32]),
     'pvs_graph_filter_ligand_edges': (C.c_int, [C.POINTER(PvsGraph), C.c_void_p, C.c_int32] + [C.c_void_p] * 5 +
                                       [C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -26,7 +26,8 @@ constexpr int kWaves = kThreads / 64;
 constexpr int kMaxLig = 1024;      // ligand atoms held in LDS (24 KB as fp64)
 constexpr int kLutSize = 128;      // atomic numbers the class table covers; others fall into the overflow class
 
-enum : int { kBadPair = 1, kLigTooLarge = 2, kBadType = 4, kBadCounts = 8, kBadEdges = 16 };
+enum : int { kBadPair = 1, kLigTooLarge = 2, kBadType = 4, kBadCounts = 8, kBadEdges = 16,
+              kNodeOverflow = PVS_CAP_NODE_OVERFLOW, kNoAtomLeft = PVS_CAP_EMPTY_SAMPLE };
 
 // row vector times matrix, x' = x @ M, products and sums rounded one by one in this order (no contraction), so that a
 // host evaluation with element-wise fp64 operations gives the same bits
@@ -114,18 +115,23 @@ struct Encoding {
     int use_atomic_numbers, n_features, compact, feature_dim;
 };
 
+// BatchT: the graph id of a node as the loader's int64 batch vector, or as the int32 node_graph of the capacity builder.
+// kCap (pvs_complex_batch_build_cap): total_nodes is a capacity; a sample whose rows end behind it is left out whole
+// (the offset scan has set the overflow bit already), everything else is as without it.
+template <class BatchT, bool kCap>
 __global__ void __launch_bounds__(kThreads)
 k_complex_fill(PvsComplexPool pool, const int32_t* __restrict__ pairs, const double* __restrict__ lig_xform,
                const double* __restrict__ rot, Encoding enc, const int32_t* __restrict__ class_of_z, int flag_cap,
                const uint8_t* __restrict__ flags, const int32_t* __restrict__ counts,
                const int32_t* __restrict__ graph_ptr, int total_nodes, float* __restrict__ x,
                float* __restrict__ pos, float* __restrict__ pos_graph, uint8_t* __restrict__ bp,
-               int64_t* __restrict__ batch, int32_t* __restrict__ status) {
+               BatchT* __restrict__ batch, int32_t* __restrict__ status) {
     __shared__ int wave_n[kWaves];
     const int s = blockIdx.x;
     const Sample q = load_sample(pool, pairs, s, status);
     if (!q.ok || q.flag0 + q.n_lig + q.n_rec > flag_cap) return;
     const int n0 = graph_ptr[s], n1 = graph_ptr[s + 1];
+    if (kCap && n0 >= 0 && n1 >= n0 && n1 > total_nodes) return;
     if (n0 < 0 || n1 < n0 || n1 > total_nodes || n1 - n0 != counts[2 * s] + counts[2 * s + 1]) {
         if (threadIdx.x == 0) atomicOr(status, kBadCounts);
         return;
@@ -170,7 +176,7 @@ k_complex_fill(PvsComplexPool pool, const int32_t* __restrict__ pairs, const dou
         pos[3 * (size_t)node + 1] = (float)o[1];
         pos[3 * (size_t)node + 2] = (float)o[2];
         bp[node] = is_rec;
-        batch[node] = s;
+        batch[node] = (BatchT)s;
         // class of the atom (data_loaders.py:288-291, preprocessing.py:275): receptor classes sit n_features higher
         int cls;
         if (enc.use_atomic_numbers) {
@@ -231,6 +237,54 @@ __global__ void k_complex_edges(int n_nodes, int n_edges, int n_graphs, const in
     for (int k = 0; k < 3; ++k) edge_attr[3 * (size_t)dst + k] = k == ty;
 }
 
+// counts [B,2] -> node_ptr [B+1], their running sum, on the device (one wave; B is a few hundred at most). The sum is
+// carried in 64 bits and saturates at INT32_MAX, so an offset never wraps. Sets the two bits a capacity batch adds on
+// the node side: a sample without any atom left, more nodes than node_cap.
+__global__ void k_node_offsets(const int32_t* __restrict__ counts, int B, int node_cap, int32_t* __restrict__ node_ptr,
+                               int32_t* __restrict__ status) {
+    const int lane = threadIdx.x;
+    long long base = 0;
+    int bits = 0;
+    for (int g0 = 0; g0 < B; g0 += 64) {
+        const int g = g0 + lane;
+        const int n = g < B ? counts[2 * g] + counts[2 * g + 1] : 0;
+        if (g < B && n <= 0) bits |= kNoAtomLeft;
+        long long scan = n > 0 ? n : 0;
+        for (int o = 1; o < 64; o <<= 1) {
+            const long long t = __shfl_up(scan, o, 64);
+            if (lane >= o) scan += t;
+        }
+        const long long end = base + scan;
+        if (g < B) node_ptr[g + 1] = end > 0x7fffffffll ? 0x7fffffff : (int32_t)end;
+        base += __shfl(scan, 63, 64);
+    }
+    if (lane == 0) node_ptr[0] = 0;
+    if (base > node_cap) bits |= kNodeOverflow;
+    if (bits) atomicOr(status, bits);
+}
+
+// Every row of the node tables that no sample owns - behind node_ptr[B], or inside a sample that does not fit node_cap
+// and was therefore left out whole - is padding: zero features and coordinates, bp 0, node_graph -1. Together with
+// k_complex_fill this rewrites every row at every call.
+__global__ void k_pad_rows(const int32_t* __restrict__ node_ptr, int B, int node_cap, int feature_dim,
+                           float* __restrict__ x, float* __restrict__ pos, float* __restrict__ pos_graph,
+                           uint8_t* __restrict__ bp, int32_t* __restrict__ node_graph) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= node_cap) return;
+    if (i < node_ptr[B]) {
+        const int g = pvs_last_le(node_ptr, B, i);
+        if (node_ptr[g + 1] <= node_cap) return;      // a row k_complex_fill writes
+    }
+    float* row = x + (size_t)i * feature_dim;
+    for (int k = 0; k < feature_dim; ++k) row[k] = 0.0f;
+    for (int k = 0; k < 3; ++k) {
+        pos[3 * (size_t)i + k] = 0.0f;
+        if (pos_graph) pos_graph[3 * (size_t)i + k] = 0.0f;
+    }
+    bp[i] = 0;
+    node_graph[i] = -1;
+}
+
 bool pool_ok(const PvsComplexPool* pool) {
     return pool && pool->rec_xyz && pool->lig_xyz && pool->rec_types && pool->lig_types && pool->rec_z && pool->lig_z &&
            pool->rec_ptr && pool->lig_ptr && pool->n_rec > 0 && pool->n_lig > 0;
@@ -284,9 +338,50 @@ extern "C" int pvs_complex_batch_fill(const PvsComplexPool* pool, const int32_t*
     enc.n_features = n_features;
     enc.compact = compact;
     enc.feature_dim = compact ? n_features + 1 : 2 * n_features;
-    k_complex_fill<<<n_samples, kThreads, 0, s>>>(*pool, pairs, lig_xform, rot, enc, class_of_z, n_atoms_in,
-                                                  (const uint8_t*)workspace, counts, graph_ptr, total_nodes, x, pos,
-                                                  pos_graph, bp, batch, status);
+    k_complex_fill<int64_t, false><<<n_samples, kThreads, 0, s>>>(
+        *pool, pairs, lig_xform, rot, enc, class_of_z, n_atoms_in, (const uint8_t*)workspace, counts, graph_ptr,
+        total_nodes, x, pos, pos_graph, bp, batch, status);
+    PVS_CHECK_LAUNCH();
+    return 0;
+}
+
+// _count, the offsets and _fill in one call at host-chosen capacities: nothing about the batch's content reaches the
+// host, and the launch geometry depends on (n_samples, node_cap) alone, so the call can be captured.
+extern "C" int pvs_complex_batch_build_cap(const PvsComplexPool* pool, const int32_t* pairs, const double* lig_xform,
+                                           const double* rot, int32_t n_samples, int32_t atoms_in_cap, int32_t node_cap,
+                                           double radius, int32_t keep_hydrogens, int32_t use_atomic_numbers,
+                                           int32_t n_features, int32_t compact, const int32_t* class_of_z,
+                                           int32_t* counts, int32_t* node_ptr, float* x, float* pos, float* pos_graph,
+                                           uint8_t* bp, int32_t* node_graph, int32_t* status, void* workspace,
+                                           size_t workspace_bytes, pvs_stream_t stream_) {
+    hipStream_t s = (hipStream_t)stream_;
+    const char* who = "pvs_complex_batch_build_cap";
+    PVS_REQUIRE(pool_ok(pool) && pairs && counts && node_ptr && status && workspace, "%s: NULL argument or empty pool",
+                who);
+    PVS_REQUIRE(n_samples > 0 && atoms_in_cap >= 0 && node_cap > 0, "%s: bad sizes B=%d atoms=%d nodes=%d", who,
+                n_samples, atoms_in_cap, node_cap);
+    PVS_REQUIRE(n_features > 0 && (!use_atomic_numbers || class_of_z), "%s: bad feature encoding", who);
+    PVS_REQUIRE(x && pos && bp && node_graph, "%s: NULL output", who);
+    PVS_REQUIRE(workspace_bytes >= pvs_complex_batch_workspace_bytes(n_samples, atoms_in_cap),
+                "%s: workspace too small (%zu)", who, workspace_bytes);
+    PvsProfScope prof(s, PVS_PROF_PREPARE);
+    Encoding enc;
+    enc.use_atomic_numbers = use_atomic_numbers;
+    enc.n_features = n_features;
+    enc.compact = compact;
+    enc.feature_dim = compact ? n_features + 1 : 2 * n_features;
+    PVS_CHECK_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), s));
+    k_complex_count<<<n_samples, kThreads, 0, s>>>(*pool, pairs, lig_xform, make_radius(radius), keep_hydrogens,
+                                                   atoms_in_cap, (uint8_t*)workspace, counts, status);
+    PVS_CHECK_LAUNCH();
+    k_node_offsets<<<1, 64, 0, s>>>(counts, n_samples, node_cap, node_ptr, status);
+    PVS_CHECK_LAUNCH();
+    k_complex_fill<int32_t, true><<<n_samples, kThreads, 0, s>>>(
+        *pool, pairs, lig_xform, rot, enc, class_of_z, atoms_in_cap, (const uint8_t*)workspace, counts, node_ptr,
+        node_cap, x, pos, pos_graph, bp, node_graph, status);
+    PVS_CHECK_LAUNCH();
+    k_pad_rows<<<(node_cap + 255) / 256, 256, 0, s>>>(node_ptr, n_samples, node_cap, enc.feature_dim, x, pos, pos_graph,
+                                                      bp, node_graph);
     PVS_CHECK_LAUNCH();
     return 0;
 }

@@ -67,8 +67,15 @@ inline long long pvs_chunk_edges(long long dflt = 4096) {
 struct PvsEdgeGrid {
     int blocks, n_chunks;
 };
-inline PvsEdgeGrid pvs_edge_grid(long long E, int waves_per_block, int max_blocks, long long min_edges_per_wave,
-                                 long long chunk_edges) {
+// (also device code: a forward launch over a graph whose edge count lives on the device plans its chunks there, from the
+// count itself - pvs_edge_replan below - so that its sums do not depend on the room the caller gave the edge arrays)
+#ifdef __HIPCC__
+#define PVS_DISPATCH_FN __host__ __device__ inline
+#else
+#define PVS_DISPATCH_FN inline
+#endif
+PVS_DISPATCH_FN PvsEdgeGrid pvs_edge_grid(long long E, int waves_per_block, int max_blocks, long long min_edges_per_wave,
+                                          long long chunk_edges) {
     const long long per_block = waves_per_block * min_edges_per_wave;
     long long b = (E + per_block - 1) / per_block;
     if (b < 1) b = 1;
@@ -77,6 +84,21 @@ inline PvsEdgeGrid pvs_edge_grid(long long E, int waves_per_block, int max_block
     long long per_wave = (E + waves * chunk_edges - 1) / (waves * chunk_edges);
     if (per_wave < 1) per_wave = 1;
     return PvsEdgeGrid{(int)b, (int)(waves * per_wave)};
+}
+
+// What a launch planned on the host with a CAPACITY keeps, so that the kernel can plan again with the device-side count:
+// the chunk count of pvs_edge_grid for that count. The grid stays the capacity's (at least as many workgroups: the block
+// count grows with E), and the chunk loop strides over whatever number of chunks there is.
+struct PvsEdgePlan {
+    int waves_per_block, max_blocks, min_edges_per_wave, chunk_edges;
+};
+inline PvsEdgePlan pvs_edge_plan(int waves_per_block, int max_blocks, long long min_edges_per_wave, long long chunk_edges) {
+    const long long top = 0x7fffffffll;
+    return PvsEdgePlan{waves_per_block, max_blocks, (int)(min_edges_per_wave < top ? min_edges_per_wave : top),
+                       (int)(chunk_edges < top ? chunk_edges : top)};
+}
+PVS_DISPATCH_FN int pvs_edge_replan(const PvsEdgePlan& p, long long E) {
+    return pvs_edge_grid(E, p.waves_per_block, p.max_blocks, p.min_edges_per_wave, p.chunk_edges).n_chunks;
 }
 
 // Block caps (256 CUs). A backward workgroup leaves one weight-gradient slab, so the layer's workspace holds

@@ -34,11 +34,15 @@ namespace {
 template <int HB, int NT = kThreads, bool SOFT = false, bool F16X2 = false, int MODE = 0, bool SA32 = true>
 __global__ void __launch_bounds__(NT, (F16X2 && HB == 1) ? 4 : (F16X2 && NT == 768) ? 3 : 1)
 k_edge_fwd_mfma(PvsGraph g, PvsEdgeW w, uint32_t flags, int att_act, PvsEdgeFwdIO io, int n_chunks,
-                int e_lo, int e_hi) {
+                int e_lo, int e_hi, PvsEdgePlan plan) {
     constexpr int H = 32 * HB;
     static_assert(MODE == 0 || F16X2, "the two-launch form exists for the f16x2 kernels");
     constexpr int TS = H + 4;   // tile row stride (floats): conflict-free b128 writes / b32 reads
-    if (g.n_edges_dev) e_hi = min(e_hi, *g.n_edges_dev);   // edge count only known on the device
+    if (g.n_edges_dev) {        // edge count only known on the device: e_hi is the room of the edge arrays
+        e_hi = min(e_hi, *g.n_edges_dev);
+        // the chunks the host would have planned for this count: the room decides the grid, never a row's sums
+        n_chunks = __builtin_amdgcn_readfirstlane(pvs_edge_replan(plan, e_hi - e_lo));      // (uniform: keep it scalar)
+    }
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int NW = NT / 64;
     constexpr int kBlkWords = 4 * 64 * 4;      // one 32x32 block as f16x2: 4 KB
@@ -108,8 +112,11 @@ k_edge_fwd_mfma(PvsGraph g, PvsEdgeW w, uint32_t flags, int att_act, PvsEdgeFwdI
 
     const int total_waves = gridDim.x * NW;
     for (int chunk = pvs_xcd_block(blockIdx.x, gridDim.x) * NW + wv; chunk < n_chunks; chunk += total_waves) {
-        const int e_begin = chunk_begin(g, chunk, n_chunks, e_lo, e_hi);
-        const int e_end = chunk_begin(g, chunk + 1, n_chunks, e_lo, e_hi);
+        // (never past e_hi: the per-edge outputs are stored unclamped. A chunk end is rowptr[row[t]], which exceeds t only
+        // where rowptr and row are not of one graph - a builder that overflowed keeps the true counts in rowptr and an
+        // earlier call's rows; such a launch may compute nonsense, inside its buffers)
+        const int e_begin = min(chunk_begin(g, chunk, n_chunks, e_lo, e_hi), e_hi);
+        const int e_end = min(chunk_begin(g, chunk + 1, n_chunks, e_lo, e_hi), e_hi);
         int cur_row = -1;
         float4 acc = make_float4(0.f, 0.f, 0.f, 0.f), accx = acc;   // open row: lane = (row slot, quad)
         constexpr int QPR = H / 4;
@@ -380,12 +387,12 @@ __global__ void k_init_fwd(float* __restrict__ Magg, const float* __restrict__ x
 // One launch of k_edge_fwd_mfma<HB, NT, SOFT, F16X2, MODE, SA32>: the softmax form and the offset width picked at run time
 // (MODE 2, the coordinate branch alone, has no attention: only its SOFT = false form exists)
 template <int HB, int NT, bool F16X2, int MODE>
-int launch_fwd(hipStream_t s, bool soft, bool sa32, PvsEdgeGrid grid, size_t lds, const PvsGraph& g, const PvsEdgeW& w,
-               uint32_t flags, int att_act, const PvsEdgeFwdIO& io) {
+int launch_fwd(hipStream_t s, bool soft, bool sa32, PvsEdgeGrid grid, PvsEdgePlan plan, size_t lds, const PvsGraph& g,
+               const PvsEdgeW& w, uint32_t flags, int att_act, const PvsEdgeFwdIO& io) {
     return pvs_dispatch<MODE == 2 ? 1 : 2>(soft, sa32, [&](auto SF, auto SA) {
         auto kernel = k_edge_fwd_mfma<HB, NT, decltype(SF)::value != 0, F16X2, MODE, decltype(SA)::value>;
         if (set_lds(kernel, lds)) return -2;
-        kernel<<<grid.blocks, NT, lds, s>>>(g, w, flags, att_act, io, grid.n_chunks, 0, g.n_edges);
+        kernel<<<grid.blocks, NT, lds, s>>>(g, w, flags, att_act, io, grid.n_chunks, 0, g.n_edges, plan);
         PVS_CHECK_LAUNCH();
         return 0;
     });
@@ -423,13 +430,14 @@ int pvs_launch_edge_fwd_mfma(hipStream_t s, int H, PvsEdgeFamily fam, const PvsG
         const bool upd = flags & PVS_UPDATE_COORDS;
         PVS_REQUIRE(mbuf || !upd, "H = 128 edge forward needs m_out or the message scratch");
         const PvsEdgeGrid grid = pvs_edge_grid(g.n_edges, kWaves, kPvsFwdLargeMaxBlocks, pvs_edges_per_wave(), pvs_chunk_edges());
+        const PvsEdgePlan plan = pvs_edge_plan(kWaves, kPvsFwdLargeMaxBlocks, pvs_edges_per_wave(), pvs_chunk_edges());
         const size_t words = (size_t)16 * 4 * 64 * 4 + 4 + (5 + attr_rows) * H +
                              (size_t)kWaves * (kTile * (H + 4) + kTile * 4 + kTile);
         const size_t lds = words * sizeof(float);
         PvsEdgeFwdIO io1 = io;
         io1.m_out = upd ? mbuf : io.m_out;
-        PVS_TRY(launch_fwd<4, kThreads, true, 1>(s, soft, sa32, grid, lds, g, w, flags, att_act, io1));
-        if (upd) PVS_TRY(launch_fwd<4, kThreads, true, 2>(s, false, sa32, grid, lds, g, w, flags, att_act, io1));
+        PVS_TRY(launch_fwd<4, kThreads, true, 1>(s, soft, sa32, grid, plan, lds, g, w, flags, att_act, io1));
+        if (upd) PVS_TRY(launch_fwd<4, kThreads, true, 2>(s, false, sa32, grid, plan, lds, g, w, flags, att_act, io1));
     } else {
         // split (default): the two chain products as three-term fp16 products with tile scales ("f16x2", round 3);
         // exact: fp32 MFMAs - the cross-check family of the tests. (The six-term bf16 form of rounds 1-2 is gone from
@@ -440,15 +448,17 @@ int pvs_launch_edge_fwd_mfma(hipStream_t s, int H, PvsEdgeFamily fam, const PvsG
         const int nw = (HB == 2 && f16x2) ? (attr_rows <= 3 ? 12 : 8) : kWaves;
         const PvsEdgeGrid grid = pvs_edge_grid(g.n_edges, nw, nw >= 8 ? kPvsFwdLargeMaxBlocks : kPvsFwdMaxBlocks,
                                                pvs_edges_per_wave(), pvs_chunk_edges());
+        const PvsEdgePlan plan = pvs_edge_plan(nw, nw >= 8 ? kPvsFwdLargeMaxBlocks : kPvsFwdMaxBlocks, pvs_edges_per_wave(),
+                                               pvs_chunk_edges());
         const size_t words = (f16x2 ? (size_t)2 * HB * HB * 4 * 64 * 4 + 4 : (size_t)2 * H * H) +
                              (5 + attr_rows) * H +
                              (size_t)nw * (kTile * (H + 4) + kTile * 4 + kTile);
         const size_t lds = words * sizeof(float);
-        if (HB == 2 && f16x2 && nw == 12) PVS_TRY(launch_fwd<2, 768, true, 0>(s, soft, sa32, grid, lds, g, w, flags, att_act, io));
-        else if (HB == 2 && f16x2) PVS_TRY(launch_fwd<2, 512, true, 0>(s, soft, sa32, grid, lds, g, w, flags, att_act, io));
-        else if (HB == 1 && f16x2) PVS_TRY(launch_fwd<1, kThreads, true, 0>(s, soft, sa32, grid, lds, g, w, flags, att_act, io));
-        else if (HB == 1) PVS_TRY(launch_fwd<1, kThreads, false, 0>(s, soft, sa32, grid, lds, g, w, flags, att_act, io));
-        else PVS_TRY(launch_fwd<2, kThreads, false, 0>(s, soft, sa32, grid, lds, g, w, flags, att_act, io));
+        if (HB == 2 && f16x2 && nw == 12) PVS_TRY(launch_fwd<2, 768, true, 0>(s, soft, sa32, grid, plan, lds, g, w, flags, att_act, io));
+        else if (HB == 2 && f16x2) PVS_TRY(launch_fwd<2, 512, true, 0>(s, soft, sa32, grid, plan, lds, g, w, flags, att_act, io));
+        else if (HB == 1 && f16x2) PVS_TRY(launch_fwd<1, kThreads, true, 0>(s, soft, sa32, grid, plan, lds, g, w, flags, att_act, io));
+        else if (HB == 1) PVS_TRY(launch_fwd<1, kThreads, false, 0>(s, soft, sa32, grid, plan, lds, g, w, flags, att_act, io));
+        else PVS_TRY(launch_fwd<2, kThreads, false, 0>(s, soft, sa32, grid, plan, lds, g, w, flags, att_act, io));
     }
     // softmax attention: att_out holds the logits, the rows' maxima and sums are complete now
     if (soft) return pvs_launch_softmax_finalize(s, g, io.smax, io.ssum, io.att_out);

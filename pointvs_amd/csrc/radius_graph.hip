@@ -32,12 +32,17 @@ constexpr int kWaves = 4;
 constexpr int kRowsPerWave = 16;
 constexpr int kRowsPerBlock = kWaves * kRowsPerWave;
 
-// block -> (graph, first row) and the per-graph offset of its neighbour bit masks
+// block -> (graph, first row) and the per-graph offset of its neighbour bit masks. fits: NULL, or a device flag (the
+// capacity variant's k_cap_check): where it is 0 the offsets do not fit the tables, and there are no blocks.
 __global__ void k_block_table(const int32_t* __restrict__ gptr, int B, int32_t* __restrict__ blk_graph,
                               int32_t* __restrict__ blk_row0, int32_t* __restrict__ n_blocks_out,
-                              long long* __restrict__ mask_off) {
+                              long long* __restrict__ mask_off, const int32_t* __restrict__ fits) {
     // one wave: graph g's blocks start at the prefix sum of ceil(n_g / kRowsPerBlock)
     const int lane = threadIdx.x;
+    if (fits && !*fits) {
+        if (lane == 0) *n_blocks_out = 0;
+        return;
+    }
     int nb_base = 0;
     long long mo_base = 0;
     for (int g0 = 0; g0 < B; g0 += 64) {
@@ -164,6 +169,73 @@ k_radius_fill(const uint8_t* __restrict__ bp, const int32_t* __restrict__ gptr, 
     }
 }
 
+// ---- capacity variant (pvs_radius_graph_build_cap): node offsets that exist only on the device ----
+// The block table and the mask state are sized from two host capacities (node_cap rows, graphs of up to graph_node_cap
+// nodes); flags[0] says whether the batch fits them. Where it does not, no block runs (n_blocks = 0), every per-row
+// count stays zero and the status word says which capacity was short.
+__global__ void k_cap_check(const int32_t* __restrict__ gptr, int B, int node_cap, int graph_node_cap,
+                            int32_t* __restrict__ flags, int32_t* __restrict__ status) {
+    const int lane = threadIdx.x;
+    int bits = 0;
+    for (int g = lane; g < B; g += 64) {
+        const int n0 = gptr[g], n1 = gptr[g + 1];
+        if (n0 < 0 || n1 < n0) bits |= PVS_CAP_NODE_OVERFLOW;            // (not a table of offsets: nothing fits)
+        else if (n1 - n0 > graph_node_cap) bits |= PVS_CAP_GRAPH_OVERFLOW;
+    }
+    if (gptr[0] != 0 || gptr[B] > node_cap) bits |= PVS_CAP_NODE_OVERFLOW;
+    for (int o = 32; o > 0; o >>= 1) bits |= __shfl_xor(bits, o, 64);
+    if (lane == 0) {
+        flags[0] = bits == 0;
+        if (bits) atomicOr(status, bits);
+    }
+}
+
+// k_radius_fill without perm, over node_cap rows: a padding row (at or behind gptr[B]) gets inv_deg 1 and nothing else;
+// with more edges than edge_cap no row writes an entry (the row pointers keep the true counts) and the bit is set.
+// n_edges_fwd: the edge count a forward may use with row / col / etype as they now are: rowptr[node_cap] where every
+// entry was written, 0 on any overflow (the entries are then an earlier call's and do not match rowptr).
+__global__ void __launch_bounds__(kThreads)
+k_radius_fill_cap(const uint8_t* __restrict__ bp, const int32_t* __restrict__ gptr, int n_graphs,
+                  const int32_t* __restrict__ flags, const long long* __restrict__ mask_off,
+                  const unsigned long long* __restrict__ masks, const int32_t* __restrict__ rowptr,
+                  const int32_t* __restrict__ cnt_inter, int32_t* __restrict__ row, int32_t* __restrict__ col,
+                  uint8_t* __restrict__ etype, float* __restrict__ inv_deg, int32_t* __restrict__ n_edges_fwd,
+                  int node_cap, int edge_cap, int32_t* __restrict__ status) {
+    const int lane = threadIdx.x & 63;
+    const int i = (blockIdx.x * kThreads + threadIdx.x) >> 6;
+    if (i >= node_cap) return;
+    const bool fits = flags[0] != 0;
+    const int n_edges = rowptr[node_cap];
+    const bool room = n_edges >= 0 && n_edges <= edge_cap;
+    if (i == 0 && lane == 0) {
+        if (fits && !room) atomicOr(status, PVS_CAP_EDGE_OVERFLOW);
+        *n_edges_fwd = fits && room ? n_edges : 0;
+    }
+    if (!fits || i >= gptr[n_graphs]) {
+        if (lane == 0) inv_deg[i] = 1.0f;
+        return;
+    }
+    const int seg0 = rowptr[i], deg = rowptr[i + 1] - seg0;
+    if (lane == 0) inv_deg[i] = 1.0f / (float)(deg > 1 ? deg : 1);
+    if (!room) return;
+    const int g = pvs_last_le(gptr, n_graphs, i), n0 = gptr[g], n1 = gptr[g + 1];
+    const int n_chunks = (n1 - n0 + 63) / 64;
+    const unsigned long long* mrow = masks + 2 * mask_off[g] + (size_t)(i - n0) * 2 * n_chunks;
+    const int bpi = bp[i];
+    const int n_int = cnt_inter[i];
+    for (int kind = 0; kind < 2; ++kind) {
+        const int base = kind == 0 ? seg0 : seg0 + n_int;
+        pvs_expand_mask_row(mrow + (size_t)kind * n_chunks, n_chunks, lane, [&](int k, int b) {
+            const int p = base + k;
+            if (p >= seg0 + deg) return;      // (masks and counts come from one launch; never past the row's segment)
+            const int j = n0 + b;
+            row[p] = i;
+            col[p] = j;
+            etype[p] = kind == 0 ? 1 : ((bpi == 1 && bp[j] == 1) ? 2 : 0);
+        });
+    }
+}
+
 __global__ void k_sum_counts(const int32_t* __restrict__ a, const int32_t* __restrict__ b, int N,
                              int32_t* __restrict__ out) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -251,7 +323,7 @@ extern "C" int pvs_radius_graph_count(const float* pos, const uint8_t* bp, const
     PVS_REQUIRE(arena.ok(), "pvs_radius_graph_count: state too small (%zu < %zu)", state_bytes, arena.off);
     PvsProfScope prof(s, PVS_PROF_PREPARE);
     const int mb = max_blocks(N, n_graphs);
-    k_block_table<<<1, 64, 0, s>>>(graph_ptr, n_graphs, w.blk_graph, w.blk_row0, w.n_blocks, w.mask_off);
+    k_block_table<<<1, 64, 0, s>>>(graph_ptr, n_graphs, w.blk_graph, w.blk_row0, w.n_blocks, w.mask_off, nullptr);
     PVS_CHECK_LAUNCH();
     k_radius_masks<<<mb, kThreads, 0, s>>>(pos, bp, graph_ptr, w.blk_graph, w.blk_row0, w.n_blocks, w.mask_off,
                                            make_radius(inter_radius), make_radius(intra_radius),
@@ -295,6 +367,53 @@ extern "C" int pvs_radius_graph_fill(const uint8_t* bp, const int32_t* graph_ptr
     PVS_CHECK_LAUNCH();
     if (!cedge) return 0;     // forward-only use: the by-column lists are only read by the backward
     return pvs_build_csc(s, col, E, N, colptr, cedge, workspace, workspace_bytes);
+}
+
+// _count and _fill in one call over node_cap rows, for node offsets that exist only on the device (the node_ptr of
+// pvs_complex_batch_build_cap): forward-only arrays (no perm, no by-column lists), the same launches whatever the
+// batch holds. state: pvs_radius_graph_state_bytes(node_cap, n_graphs, graph_node_cap).
+extern "C" int pvs_radius_graph_build_cap(const float* pos, const uint8_t* bp, const int32_t* graph_ptr,
+                                          int32_t n_graphs, int32_t node_cap, int32_t graph_node_cap,
+                                          double inter_radius, double intra_radius, int32_t pair_filter,
+                                          int32_t edge_cap, int32_t* rowptr, int32_t* row, int32_t* col, uint8_t* etype,
+                                          float* inv_deg, int32_t* n_edges_fwd, int32_t* status, int32_t reset_status,
+                                          void* state,
+                                          size_t state_bytes, pvs_stream_t stream_) {
+    hipStream_t s = (hipStream_t)stream_;
+    const char* who = "pvs_radius_graph_build_cap";
+    PVS_REQUIRE(pos && bp && graph_ptr && rowptr && inv_deg && n_edges_fwd && status && state, "%s: NULL", who);
+    PVS_REQUIRE(node_cap > 0 && n_graphs > 0 && graph_node_cap > 0 && edge_cap >= 0, "%s: bad sizes N=%d B=%d", who,
+                node_cap, n_graphs);
+    PVS_REQUIRE(edge_cap == 0 || (row && col && etype), "%s: NULL edge arrays", who);
+    PvsArena arena(state, state_bytes);
+    RgState w;
+    carve_state(arena, node_cap, n_graphs, graph_node_cap, &w);
+    PVS_REQUIRE(arena.ok(), "%s: state too small (%zu < %zu)", who, state_bytes, arena.off);
+    PvsProfScope prof(s, PVS_PROF_PREPARE);
+    int32_t* fits = w.n_blocks + 1;
+    if (reset_status) {
+        PVS_CHECK_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), s));
+    }
+    k_cap_check<<<1, 64, 0, s>>>(graph_ptr, n_graphs, node_cap, graph_node_cap, fits, status);
+    PVS_CHECK_LAUNCH();
+    k_block_table<<<1, 64, 0, s>>>(graph_ptr, n_graphs, w.blk_graph, w.blk_row0, w.n_blocks, w.mask_off, fits);
+    PVS_CHECK_LAUNCH();
+    // rows behind the last graph, and every row of a batch that does not fit, are written by no block: zero first
+    PVS_CHECK_HIP(hipMemsetAsync(w.cnt_inter, 0, ((size_t)node_cap + 1) * sizeof(int32_t), s));
+    PVS_CHECK_HIP(hipMemsetAsync(w.cnt_intra, 0, ((size_t)node_cap + 1) * sizeof(int32_t), s));
+    k_radius_masks<<<max_blocks(node_cap, n_graphs), kThreads, 0, s>>>(
+        pos, bp, graph_ptr, w.blk_graph, w.blk_row0, w.n_blocks, w.mask_off, make_radius(inter_radius),
+        make_radius(intra_radius), make_radius(1e-7), pair_filter, w.masks, w.cnt_inter, w.cnt_intra);
+    PVS_CHECK_LAUNCH();
+    k_sum_counts<<<(node_cap + 1 + 255) / 256, 256, 0, s>>>(w.cnt_inter, w.cnt_intra, node_cap, w.deg);
+    PVS_CHECK_LAUNCH();
+    size_t sb = w.scan_bytes;
+    PVS_CHECK_HIP(hipcub::DeviceScan::ExclusiveSum(w.scan_tmp, sb, w.deg, rowptr, node_cap + 1, s));
+    k_radius_fill_cap<<<(node_cap + kWaves - 1) / kWaves, kThreads, 0, s>>>(
+        bp, graph_ptr, n_graphs, fits, w.mask_off, w.masks, rowptr, w.cnt_inter, row, col, etype, inv_deg, n_edges_fwd,
+        node_cap, edge_cap, status);
+    PVS_CHECK_LAUNCH();
+    return 0;
 }
 
 // labels [N] int32 (initialised to 0..N-1 by the caller), changed: device int32 set to 1 when any

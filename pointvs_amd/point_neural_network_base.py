@@ -177,7 +177,8 @@ class PointNeuralNetworkBase(nn.Module):
         init_epoch = self.a_epoch if 'regression' in self.model_task else self.p_epoch
         return init_epoch, time.time()
 
-    def train_model(self, data_loader, epochs=1, epoch_end_validation_set=None, top1_on_end=False, capture=False):
+    def train_model(self, data_loader, epochs=1, epoch_end_validation_set=None, top1_on_end=False, capture=False,
+                    capture_val=False):
         """Training loop (:136-205): per batch predict + backprop, per epoch checkpoint (+ optional
         validation, :470-490). No host synchronisation inside the loop: losses are drained every
         `log_interval` steps.
@@ -188,15 +189,17 @@ class PointNeuralNetworkBase(nn.Module):
         profiles/r05_real_shape.txt); for BASELINE-size batches it buys nothing. Either optimiser the constructor
         builds, either scheduler: the rates of a captured run are the eager run's. With dropout > 0 the masks are those
         of the same run with capture=False and static_dropout=True. Single process, fp32, no GraphNorm together with
-        dropout; anything else raises."""
+        dropout; anything else raises.
+        capture_val=True: the epoch-end validation runs as val(capture=True)."""
         init_epoch, _ = self.training_setup(data_loader=data_loader, epochs=epochs)
         if not capture:
             with long_lived_heap_frozen():
                 return self._train_epochs(data_loader, init_epoch, epochs, epoch_end_validation_set, top1_on_end,
-                                          self.training_step)
+                                          self.training_step, capture_val)
         from .captured_step import StepReplayer
         with StepReplayer(self) as replayer, torch.cuda.stream(replayer.stream), long_lived_heap_frozen():
-            return self._train_epochs(data_loader, init_epoch, epochs, epoch_end_validation_set, top1_on_end, replayer.step)
+            return self._train_epochs(data_loader, init_epoch, epochs, epoch_end_validation_set, top1_on_end, replayer.step,
+                                      capture_val)
 
     def training_step(self, graph):
         """Predict + one optimisation step on one batch; the loss as a device tensor (backprop(sync=False))."""
@@ -218,7 +221,8 @@ class PointNeuralNetworkBase(nn.Module):
             finally:
                 self.optimiser_window = None
 
-    def _train_epochs(self, data_loader, init_epoch, epochs, epoch_end_validation_set, top1_on_end, step):
+    def _train_epochs(self, data_loader, init_epoch, epochs, epoch_end_validation_set, top1_on_end, step,
+                      capture_val=False):
         losses = []
         sampler = getattr(data_loader, 'sampler', None)
         for epoch in range(init_epoch, epochs):
@@ -244,19 +248,28 @@ class PointNeuralNetworkBase(nn.Module):
             done = self.a_epoch if 'regression' in self.model_task else self.p_epoch
             if epoch_end_validation_set is not None and done < epochs:     # (:481: not after the last epoch)
                 fname = Path(self.predictions_file.parent, f'predictions_epoch_{done}.txt')
-                best = self.val(epoch_end_validation_set, predictions_file=fname, top1_on_end=top1_on_end)
+                best = self.val(epoch_end_validation_set, predictions_file=fname, top1_on_end=top1_on_end,
+                                capture=capture_val)
                 if self.only_save_best_models and best:
                     self.save()
         return losses
 
     @torch.no_grad()
-    def val(self, data_loader, predictions_file=None, top1_on_end=False, rich_ctx=None):
+    def val(self, data_loader, predictions_file=None, top1_on_end=False, rich_ctx=None, capture=False,
+            capture_options=None):
         """Inference loop (:208-360): writes `<save_path>/<pose|affinity>_<predictions file name>` in
         the reference's line format. The loop never waits for the host: scores leave the device
         through pinned buffers and a writer thread formats and appends them every `log_interval`
         batches, as the reference's write_predictions does (pointvs_amd/predictions.py).
         top1_on_end: the reference's model selection on the finished file (top-1 / Pearson); returns
-        False only when `only_save_best_models` is set and this epoch is not the best so far."""
+        False only when `only_save_best_models` is set and this epoch is not the best so far.
+        capture=True (no reference counterpart, opt-in; a parquet_data.ComplexLoader in val mode): the first
+        `probe_batches` batches are scored as always and size a captured_scoring.FixedShapeScorer; every further full
+        batch is one table upload and one replay of its captured step, written once its status word has arrived (one batch
+        late); a batch that overflows a capacity is rebuilt and scored by the eager route, in its place. The file has
+        the same lines in the same order. capture_options: probe_batches (4), headroom (1.5), capacities (a
+        captured_scoring.Capacities instead of the probe's). `last_val_stats` = batches {'eager', 'replayed',
+        'fallback'}. Models and datasets the fixed-shape step does not cover raise NotImplementedError."""
         from .predictions import PredictionsWriter, merge_rank_files, rank_part
         predictions_file = Path(predictions_file or self.predictions_file)
         predictions_file = (predictions_file.parent /
@@ -268,12 +281,15 @@ class PointNeuralNetworkBase(nn.Module):
         self.eval()
         self.val_iter = 0
         with PredictionsWriter(part, self.model_task, flush_every=self.log_interval) as writer, long_lived_heap_frozen():
-            for self.batch, graph in enumerate(data_loader):
-                self.val_iter += 1
-                y_pred, y_true, ligands, receptors = self.unpack_input_data_and_predict(graph)
-                if self.model_task == 'classification':
-                    y_pred = torch.sigmoid(y_pred)
-                writer.submit(y_pred, y_true, receptors, ligands)
+            if capture:
+                self.last_val_stats = self._val_captured(data_loader, writer, capture_options or {})
+            else:
+                for self.batch, graph in enumerate(data_loader):
+                    self.val_iter += 1
+                    y_pred, y_true, ligands, receptors = self.unpack_input_data_and_predict(graph)
+                    if self.model_task == 'classification':
+                        y_pred = torch.sigmoid(y_pred)
+                    writer.submit(y_pred, y_true, receptors, ligands)
         if world > 1:
             torch.distributed.barrier()         # every part is complete and closed
             if rank == 0:
@@ -295,6 +311,55 @@ class PointNeuralNetworkBase(nn.Module):
             self.test_metric = float(metric)
         self.last_validation_metric = float(metric)
         return bool(best or not self.only_save_best_models)
+
+    def _val_captured(self, data_loader, writer, options):
+        """val(capture=True): captured_scoring.score_batches over the loader's index order, this model's eager step and
+        a FixedShapeScorer sized by the probe batches."""
+        import numpy as np
+        from . import captured_scoring as cs
+        from .parquet_data import ComplexLoader, _check_late_status
+        unknown = set(options) - {'probe_batches', 'headroom', 'capacities'}
+        if unknown:
+            raise ValueError(f'capture_options: unknown keys {sorted(unknown)}')
+        if not isinstance(data_loader, ComplexLoader) or hasattr(data_loader.sampler, 'set_epoch'):
+            raise NotImplementedError('val(capture=True) scores a parquet_data.ComplexLoader in val mode (get_data_loader('
+                                      "mode='val')): other loaders have no fixed-shape batch builder")
+        ds, size = data_loader.dataset, data_loader.batch_size
+        why = cs.refusal(self, ds)
+        if why is not None:
+            raise NotImplementedError(f'val(capture=True): {why}')
+        order = list(data_loader.sampler) if data_loader.sampler is not None else list(range(len(ds)))
+        epoch = getattr(data_loader.sampler, 'epoch', ds.epoch)
+        batches = [order[k:k + size] for k in range(0, len(order), size)]
+        names = (lambda indices: ([Path(ds.receptor_fnames[i]) for i in indices],      # (as build_batch names them)
+                                  [Path(ds.ligand_fnames[i]) for i in indices]))
+
+        def finish(y_pred):
+            return torch.sigmoid(y_pred) if self.model_task == 'classification' else y_pred
+
+        def eager(indices):
+            self.val_iter += 1
+            graph = ds.build_batch(indices, epoch=epoch, device=data_loader.device)
+            y_pred, y_true, ligands, receptors = self.unpack_input_data_and_predict(graph)
+            return (finish(y_pred), y_true, receptors, ligands), cs.observed_sizes(graph)
+
+        def replayed(indices, scores):
+            self.val_iter += 1
+            labels = ds.host_draws(indices, epoch)[0]
+            y_true = torch.tensor(np.asarray(labels, dtype=np.float64).reshape(-1)).float()
+            receptors, ligands = names(indices)
+            return finish(scores.reshape(-1)), y_true, receptors, ligands
+
+        def make_scorer(observed, all_batches):
+            capacities = options.get('capacities') or cs.plan_capacities(
+                observed, cs.batch_input_atoms(ds, all_batches), options.get('headroom', cs.HEADROOM), batch_size=size)
+            full = next(b for b in all_batches[len(observed):] if len(b) == size)
+            return cs.FixedShapeScorer(self, ds, size, capacities, device=data_loader.device).capture(full)
+
+        stats = cs.score_batches(batches, size, eager, make_scorer, replayed, lambda payload: writer.submit(*payload),
+                                 probe_batches=options.get('probe_batches', cs.PROBE_BATCHES))
+        _check_late_status(wait=True)
+        return stats
 
     def save(self, save_path=None):
         """Checkpoint in the reference's format (:501-517). Data parallel: weights and optimiser state
