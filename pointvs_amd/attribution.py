@@ -144,11 +144,9 @@ def build_mask_batch(parent, drop, n_edges=None):
         _lib.ptr(t['inv_deg']), _lib.ptr(src_node), _lib.ptr(graph_ptr), _lib.ptr(t['graph_eptr']),
         _lib.ptr(t['status']), _lib.ptr(ws), ws_bytes, _lib.stream(dev)), 'pvs_mask_graph_build')
     t['_inputs'] = (drop_dev, ws, parent)        # alive until the kernels have run
-    pg = PreparedGraph(total_nodes, capacity, parent.n_edge_attr, t)
-    pg._status_checked = True                    # (the builder's own status word is read by the caller)
+    pg = PreparedGraph.over_buffers(total_nodes, capacity, t, t['rowptr'][total_nodes:] if n_edges is None else None,
+                                    parent.n_edge_attr)
     pg.c.graph_eptr, pg.c.n_graphs = _lib.ptr(t['graph_eptr']), n_masks
-    if n_edges is None:
-        pg.c.n_edges_dev = t['rowptr'][total_nodes:].data_ptr()
     return MaskBatch(pg, src_node[:total_nodes].long(), graph_ptr, t['graph_eptr'], t['status'], n_masks)
 
 

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from . import functional as PF
+from .nowait import LateQueue, StagingRing, capture_fixed_step, pinned
 from .parquet_data import MAX_LIGAND_ATOMS, _raise_for_status
 
 Capacities = collections.namedtuple('Capacities', 'node_cap graph_node_cap edge_cap atoms_in_cap')
@@ -173,8 +173,9 @@ class FixedShapeScorer:
         edge_radius = dataset.edge_radius if dataset.edge_radius and dataset.edge_radius > 0 else 4
         self.r_inter, self.r_intra = float(edge_radius), 2.0 if dataset.estimate_bonds else float(edge_radius)
         self._buffers()
-        self._graph, self._static_out, self._pending = None, None, collections.deque()
-        self._launched = 0
+        self._graph, self._static_out = None, None
+        self._late = LateQueue(ring=self.RING)      # the steps' status words, oldest first
+        self._launched = 0                          # steps of its own so far: capture() wants none
 
     def _probe(self):
         n, batches = len(self.dataset), []
@@ -199,15 +200,13 @@ class FixedShapeScorer:
             row=torch.zeros(cap.edge_cap, **i32), col=torch.zeros(cap.edge_cap, **i32),
             etype=torch.zeros(cap.edge_cap, **u8), inv_deg=torch.ones(cap.node_cap, **f32),
             n_edges_fwd=torch.zeros(1, **i32), status=torch.zeros(1, **i32), workspace=torch.empty(ws_bytes, **u8), state=torch.empty(st_bytes, **u8))
-        self._status_host = [torch.zeros(1, dtype=torch.int32).pin_memory() for _ in range(self.RING)]
-        self._stage = [(torch.zeros((self.b, 3), dtype=torch.int32).pin_memory(), None) for _ in range(self.RING)]
-        self._stage_at = 0
+        self._stage = StagingRing(self.RING, lambda: pinned((self.b, 3), torch.int32))
         from .graph import PreparedGraph
-        pg = PreparedGraph(cap.node_cap, cap.edge_cap, 3, {k: t[k] for k in ('rowptr', 'row', 'col', 'etype', 'inv_deg',
-                                                                              'status')})
-        pg._status_checked = True      # (the builders' own status word is read through check() / take_status())
-        # (not rowptr[node_cap]: on an edge overflow that is the true count, beside row / col / etype of an earlier batch)
-        pg.c.n_edges_dev = t['n_edges_fwd'].data_ptr()
+        # (the builders' own status word is read through check() / take_status(); the edge count is not
+        # rowptr[node_cap]: on an edge overflow that is the true count, beside row / col / etype of an earlier batch)
+        pg = PreparedGraph.over_buffers(
+            cap.node_cap, cap.edge_cap, {k: t[k] for k in ('rowptr', 'row', 'col', 'etype', 'inv_deg', 'status')},
+            t['n_edges_fwd'])
         if self.graphnorm:
             pg.set_norm_rows(t['node_ptr'][self.b:])
         self.pg = pg
@@ -228,15 +227,10 @@ class FixedShapeScorer:
         if int(flag_off[-1]) > self.capacities.atoms_in_cap:
             raise ValueError(f'the batch has {int(flag_off[-1])} input atoms, the scorer was built for '
                              f'{self.capacities.atoms_in_cap} (atoms_in_cap)')
-        host, event = self._stage[self._stage_at]
-        if event is not None:
-            event.synchronize()
+        host = self._stage.acquire()
         host.copy_(torch.from_numpy(np.stack([rec_id, lig_id, flag_off[:-1]], axis=1).astype(np.int32)))
         self.t['pairs'].copy_(host, non_blocking=True)
-        event = torch.cuda.Event()
-        event.record(torch.cuda.current_stream(self.device))
-        self._stage[self._stage_at] = (host, event)
-        self._stage_at = (self._stage_at + 1) % self.RING
+        self._stage.release(self.device)
         self.indices = [int(i) for i in indices]
 
     # ---- the step ----
@@ -266,9 +260,7 @@ class FixedShapeScorer:
             h, x, _ = layer.forward_prepared(self.pg, h, x, None, need_m=False, need_coords=layer is not self.egnn[-1])
         if self.head is None:
             return h
-        if self.b == 1:      # (one graph: the pooling still ends at node_ptr[1], not at the padded shape)
-            return model._run_head(self.head, PF.mean_pool(h, t['node_ptr']))
-        return model._pool_and_head(self.head, h, t['node_ptr'], self.b)
+        return model._pool_and_head_padded(self.head, h, t['node_ptr'], self.b)
 
     def __call__(self, indices=None):
         if self._graph is not None:
@@ -292,28 +284,21 @@ class FixedShapeScorer:
 
     # ---- the late status word ----
     def _queue_status(self):
-        """Queues the copy of the step's status word into a pinned host word of its own; with RING words in flight the
+        """Queues the copy of the step's status word into a pinned word of the ring; with RING words in flight the
         oldest is checked first (its word is the one about to be reused)."""
-        if len(self._pending) >= self.RING:
+        if len(self._late) >= self.RING:
             raise_for_status(self.take_status())
-        host = self._status_host[self._launched % self.RING]
         self._launched += 1
-        host.copy_(self.t['status'], non_blocking=True)
-        event = torch.cuda.Event()
-        event.record(torch.cuda.current_stream(self.device))
-        self._pending.append((event, host))
+        self._late.put(self.t['status'])
 
     def take_status(self):
         """The status word of the oldest step not yet asked about (waits for that step only), or 0 when there is none."""
-        if not self._pending:
-            return 0
-        event, host = self._pending.popleft()
-        event.synchronize()
-        return int(host.item())
+        taken = self._late.take()
+        return 0 if taken is None else taken[0]
 
     def check(self):
         """Raises for the status words of the steps launched so far (call once more after the last batch)."""
-        while self._pending:
+        while len(self._late):
             raise_for_status(self.take_status())
 
     # ---- capture / replay ----
@@ -325,20 +310,12 @@ class FixedShapeScorer:
                                'fresh scorer (see the class docstring)')
         if indices is not None:
             self.load(indices)
-        dev = self.device
-        stream = torch.cuda.Stream(dev)
-        stream.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(stream):
-            for _ in range(2):
-                self._run()                    # warm-up: lazy allocations, parameter structs
-            while self._pending:               # (a capacity overflow of the warm-up batch is its replay's to report)
+
+        def drain():      # (a capacity overflow of the warm-up batch is its replay's to report)
+            while len(self._late):
                 raise_for_status(self.take_status() & ~OVERFLOW_BITS)
-            torch.cuda.synchronize(dev)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph, stream=stream):
-                self._static_out = self._run()
-        self._graph = graph
-        torch.cuda.current_stream(dev).wait_stream(stream)
+
+        self._graph, self._static_out = capture_fixed_step(self._run, self.device, drain)
         return self
 
     def replay(self, indices=None, check=True):

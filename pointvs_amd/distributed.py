@@ -20,6 +20,8 @@ import contextlib
 import torch
 import torch.distributed as dist
 
+from .nowait import LateCopy
+
 
 def _refuse_fp64(params, group):
     """The flat buckets are fp32: fp64 gradients would be rounded on the way through. Refused with more than one rank."""
@@ -108,28 +110,20 @@ class GradAllReducer:
         self._live = live
 
     def _raise_if_flagged(self, flags):
-        """The summed flags are read ONE CALL LATE on a GPU (pinned copy + event, like
-        PreparedGraph.poll_status), so the step never waits for the host; every rank sees the same
-        sums at the same call and raises together. `check()` drains the pending read."""
+        """The summed flags are read ONE CALL LATE on a GPU (nowait.LateCopy), so the step never waits
+        for the host; every rank sees the same sums at the same call and raises together. `check()`
+        drains the pending read; a CPU total is read at once."""
         self.check()
         total = torch.stack([f.reshape(()) for f in flags]).sum()
+        self._pending = LateCopy(total)
         if not total.is_cuda:
-            self._pending = (None, total)
-            return self.check()
-        host = torch.empty((), dtype=torch.float32, pin_memory=True)
-        host.copy_(total, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(total.device))
-        self._pending = (ev, host)
+            self.check()
 
     def check(self):
         pending, self._pending = getattr(self, '_pending', None), None
         if pending is None:
             return
-        ev, host = pending
-        if ev is not None:
-            ev.synchronize()
-        if float(host) != 0.0:
+        if float(pending.wait()) != 0.0:
             raise RuntimeError('the set of parameters with gradients changed between steps (on at '
                                'least one rank; every rank raises this together)')
 

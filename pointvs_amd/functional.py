@@ -9,6 +9,7 @@ import math
 import torch
 
 from . import _lib
+from .nowait import LateQueue
 
 
 def _stream(dev):
@@ -904,40 +905,19 @@ def bce_with_logits_mean(y_pred, y_true):
     return _BceLogitsMeanFn.apply(y_pred, y_true)
 
 
-class _SegmentStatus:
-    """The status word of one pvs_segment_reduce_fwd call, read WITHOUT blocking the stream (as
-    graph.PreparedGraph.poll_status reads the graph preparation's): the call queues a copy into pinned memory and an
-    event; every later segment_reduce call raises for whichever earlier words have landed, and the call's own backward
-    waits for its word (it has long landed by then). The reference's scatter_add_ raises at once
-    (egnn_satorras.py:336); here the error surfaces one call late - or in the backward - but it does surface."""
-    pending = []
+# The status words of pvs_segment_reduce_fwd, read WITHOUT blocking the stream (as graph.PreparedGraph.poll_status reads
+# the graph preparation's): a call queues its word (nowait.LateQueue); every later segment_reduce call raises for
+# whichever earlier words have landed, and the call's own backward waits for its own word (it has long landed by then).
+# The reference's scatter_add_ raises at once (egnn_satorras.py:336); here the error surfaces one call late - or in the
+# backward - but it does surface.
+_SEGMENT_STATUS = LateQueue()
 
-    def __init__(self, status):
-        self.host = torch.empty(1, dtype=torch.int32, pin_memory=True)
-        self.host.copy_(status, non_blocking=True)
-        self.event = torch.cuda.Event()
-        self.event.record(torch.cuda.current_stream(status.device))
-        self.done = False
-        _SegmentStatus.pending.append(self)
 
-    def settle(self, wait):
-        if self.done:
-            return
-        if not self.event.query():
-            if not wait:
-                return
-            self.event.synchronize()
-        self.done = True
-        if self in _SegmentStatus.pending:
-            _SegmentStatus.pending.remove(self)
-        if int(self.host.item()) & 1:
-            raise IndexError('unsorted_segment_sum / unsorted_segment_mean: segment_ids contains values outside '
-                             '[0, num_segments)')
-
-    @classmethod
-    def poll(cls):
-        for st in list(cls.pending):
-            st.settle(wait=False)
+def _raise_for_segment_status(taken):
+    """taken: what the queue handed out, (status word, tag) or None."""
+    if taken is not None and taken[0] & 1:
+        raise IndexError('unsorted_segment_sum / unsorted_segment_mean: segment_ids contains values outside '
+                         '[0, num_segments)')
 
 
 class _SegmentReduceFn(torch.autograd.Function):
@@ -953,7 +933,8 @@ class _SegmentReduceFn(torch.autograd.Function):
         dev = data.device
         capturing = torch.cuda.is_current_stream_capturing()
         if not capturing:
-            _SegmentStatus.poll()           # an earlier call's out-of-range ids raise here
+            for taken in _SEGMENT_STATUS.landed():      # an earlier call's out-of-range ids raise here
+                _raise_for_segment_status(taken)
         out = torch.empty((num_segments, c), dtype=kind.dtype, device=dev)
         ptr = torch.empty(num_segments + 1, dtype=torch.int32, device=dev)
         status = torch.empty(1, dtype=torch.int32, device=dev)
@@ -962,7 +943,7 @@ class _SegmentReduceFn(torch.autograd.Function):
         kind.check(kind.segment_fwd(
             _lib.ptr(data), _lib.ptr(ids), e, c, num_segments, 1 if mean else 0, _lib.ptr(out),
             _lib.ptr(ptr), _lib.ptr(status), _lib.ptr(ws), ws_bytes, _stream(dev)), 'segment_fwd')
-        ctx.status = None if capturing else _SegmentStatus(status)      # (no host-visible validation inside a capture)
+        ctx.status = None if capturing else _SEGMENT_STATUS.put(status)      # (no host-visible validation under capture)
         ctx.save_for_backward(ids, ptr)
         ctx.mean, ctx.shape, ctx.n_segments, ctx.kind = mean, (e, c), num_segments, kind
         return out
@@ -971,7 +952,7 @@ class _SegmentReduceFn(torch.autograd.Function):
     def backward(ctx, g_out):
         ids, ptr = ctx.saved_tensors
         if ctx.status is not None and not torch.cuda.is_current_stream_capturing():
-            ctx.status.settle(wait=True)
+            _raise_for_segment_status(_SEGMENT_STATUS.take(ctx.status))
         e, c = ctx.shape
         kind = ctx.kind
         g_out = _c(g_out, kind.dtype)
@@ -988,8 +969,8 @@ def segment_reduce(data, segment_ids, num_segments, mean=False):
 
 def segment_status_check():
     """Wait for every pending status word of segment_reduce and raise for the first bad one (call where a sync is fine)."""
-    for st in list(_SegmentStatus.pending):
-        st.settle(wait=True)
+    while len(_SEGMENT_STATUS):
+        _raise_for_segment_status(_SEGMENT_STATUS.take())
 
 
 def dropout_adj(edge_index, edge_attr=None, p=0.5, force_undirected=True, training=True, seed=0, step=0):

@@ -13,6 +13,7 @@ import os
 import torch
 
 from . import _lib
+from .nowait import LateQueue
 
 
 class Data:
@@ -81,8 +82,18 @@ class PreparedGraph:
             setattr(g, name, _lib.ptr(tensors.get(name)))
         self.c = g
         self._status_checked = False
-        self._status_host = None
-        self._status_event = None
+        self._status_queued = False
+
+    @classmethod
+    def over_buffers(cls, n_nodes, edge_room, tensors, n_edges_word=None, n_edge_attr=3):
+        """The graph over buffers that a device-side builder fills: `tensors` (kept alive) with room for `edge_room`
+        edges, the batch's edge count in the device int32 word `n_edges_word` (a one-element view; None: edge_room is
+        the count). The builder's own status word is read by the caller, so there is nothing left to validate."""
+        pg = cls(n_nodes, edge_room, n_edge_attr, tensors)
+        pg._status_checked = True
+        if n_edges_word is not None:
+            pg.c.n_edges_dev = n_edges_word.data_ptr()
+        return pg
 
     @property
     def perm(self):
@@ -130,16 +141,11 @@ class PreparedGraph:
         calls (or check_status) raise once it has landed. Never blocks the stream."""
         if self._status_checked or torch.cuda.is_current_stream_capturing():
             return   # (no host-visible validation inside a captured step)
-        if self._status_event is None:
-            self._status_host = torch.empty(1, dtype=torch.int32, pin_memory=True)
-            self._status_host.copy_(self.t['status'], non_blocking=True)
-            self._status_event = torch.cuda.Event()
-            self._status_event.record(torch.cuda.current_stream(self.t['status'].device))
-            _PENDING.append(self)
-        for pg in list(_PENDING):
-            if pg._status_event.query():
-                _PENDING.remove(pg)
-                pg._raise_for(int(pg._status_host.item()))
+        if not self._status_queued:
+            self._status_queued = True
+            _PENDING.put(self.t['status'], tag=self)      # (the tag keeps the graph alive until its word is read)
+        for code, pg in _PENDING.landed():
+            pg._raise_for(code)
 
     def _raise_for(self, code):
         if code & 1:
@@ -159,7 +165,7 @@ class PreparedGraph:
             self._raise_for(int(self.t['status'].item()))
 
 
-_PENDING = []
+_PENDING = LateQueue()      # the status words of poll_status, each tagged with its graph
 
 
 def runs_layout(graph, device=None):

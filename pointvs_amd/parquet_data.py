@@ -27,6 +27,7 @@ import torch
 from . import _lib
 from .data_loaders import RankWeightedSampler, class_balance_weights
 from .graph import Batch
+from .nowait import LateQueue
 
 MAX_LIGAND_ATOMS = 1024     # csrc/complex_build.hip keeps a sample's ligand in LDS; the screening paths accept the
                             # same number (screening.MAX_SCREEN_LIGAND_ATOMS)
@@ -438,7 +439,7 @@ class PygPointCloudDataset:
             n, n_edges, n_b, _lib.ptr(graph_ptr), _lib.ptr(rowptr), _lib.ptr(inter_ptr), _lib.ptr(intra_ptr),
             _lib.ptr(row), _lib.ptr(col), _lib.ptr(etype), _lib.ptr(perm), _lib.ptr(edge_index), _lib.ptr(edge_attr),
             status_ptr, stream), 'pvs_complex_edges')
-        _queue_late_status(counts_status, device)
+        _LATE.put(counts_status[-1:], keep=counts_status)
 
         y = torch.tensor(np.asarray(labels, dtype=np.float64).reshape(-1))
         y = (y.long() if self.model_task == 'classification' else y.float()).to(device)
@@ -470,25 +471,15 @@ def _raise_for_status(code):
         raise ValueError('complex batch: ' + '; '.join(text for bit, text in _STATUS_TEXT if code & bit))
 
 
-_LATE = []      # status words of pvs_complex_edges, copied back without waiting and read at the next batch
-
-
-def _queue_late_status(counts_status, device):
-    host = torch.empty(1, dtype=torch.int32, pin_memory=True)
-    host.copy_(counts_status[-1:], non_blocking=True)
-    event = torch.cuda.Event()
-    event.record(torch.cuda.current_stream(device))
-    _LATE.append((host, event, counts_status))
+_LATE = LateQueue()      # status words of pvs_complex_edges, copied back without waiting and read at the next batch
 
 
 def _check_late_status(wait=False):
-    for entry in list(_LATE):
-        host, event, _ = entry
-        if wait:
-            event.synchronize()
-        if event.query():
-            _LATE.remove(entry)
-            _raise_for_status(int(host.item()))
+    """Raises for the words that have landed; wait=True: for every word still in flight, oldest first."""
+    while wait and len(_LATE):
+        _raise_for_status(_LATE.take()[0])
+    for code, _ in _LATE.landed():
+        _raise_for_status(code)
 
 
 class ComplexLoader:

@@ -229,6 +229,14 @@ class PNNGeometricBase(PointNeuralNetworkBase):
             out = PF.pool_head(feats, graph_ptr, mods[0].weight, mods[0].bias)
         return cls._run_head(mods[1:], out)
 
+    @classmethod
+    def _pool_and_head_padded(cls, head, feats, graph_ptr, n_graphs):
+        """_pool_and_head for the fixed-shape steps, whose feats end in padding rows: with one graph the pooling still
+        ends at graph_ptr[1] (a device word), not at feats' last row as _pool's plain mean would."""
+        if n_graphs == 1:
+            return cls._run_head(head, PF.mean_pool(feats, graph_ptr))
+        return cls._pool_and_head(head, feats, graph_ptr, n_graphs)
+
     @staticmethod
     def _fused_head(head):
         """(weight, bias, act) when `head` is a Linear followed by nothing, ReLU or a default Softplus - what

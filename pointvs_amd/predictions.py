@@ -22,6 +22,8 @@ from pathlib import Path
 import numpy as np
 import torch
 
+from .nowait import LateCopy
+
 _METRICS = ('pki', 'pkd', 'ic50')
 
 
@@ -142,18 +144,10 @@ class PredictionsWriter:
         self._thread = threading.Thread(target=self._run, name='pvs-predictions', daemon=True)
         self._thread.start()
 
-    def _stage(self, t):
-        """Device tensor -> (pinned host copy in flight, event); host data passes through."""
-        if t is None or not torch.is_tensor(t):
-            return t, None
-        t = t.detach()
-        if not t.is_cuda:
-            return t, None
-        host = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
-        host.copy_(t, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(t.device))
-        return host, ev
+    @staticmethod
+    def _stage(t):
+        """A tensor -> its LateCopy (a device tensor: the pinned host copy in flight); other host data passes through."""
+        return LateCopy(t.detach()) if torch.is_tensor(t) else t
 
     def submit(self, y_pred, y_true, receptors, ligands):
         """Enqueues one batch; returns immediately (blocks only when `ring` batches are already
@@ -161,9 +155,7 @@ class PredictionsWriter:
         if self._error is not None:
             raise self._error
         self._free.acquire()
-        pred, ev_p = self._stage(y_pred)
-        true, ev_t = self._stage(y_true)
-        self._q.put((pred, ev_p, true, ev_t, list(receptors), list(ligands)))
+        self._q.put((self._stage(y_pred), self._stage(y_true), list(receptors), list(ligands)))
 
     def _run(self):
         pending, batches = [], 0
@@ -172,12 +164,10 @@ class PredictionsWriter:
                 item = self._q.get()
                 if item is None:
                     break
-                pred, ev_p, true, ev_t, receptors, ligands = item
-                for ev in (ev_p, ev_t):
-                    if ev is not None:
-                        ev.synchronize()         # only this thread waits for the copy
-                pred = pred.numpy() if torch.is_tensor(pred) else np.asarray(pred)
-                true = None if true is None else (true.numpy() if torch.is_tensor(true) else np.asarray(true))
+                # only this thread waits for the copies
+                pred, true = (v.wait().numpy() if isinstance(v, LateCopy) else v for v in item[:2])
+                receptors, ligands = item[2:]
+                pred, true = np.asarray(pred), None if true is None else np.asarray(true)
                 pending += format_lines(self.task, pred, true, receptors, ligands)
                 self._free.release()
                 batches += 1

@@ -17,6 +17,7 @@ from torch import nn
 
 from . import _lib
 from . import functional as PF
+from .nowait import LateQueue, StagingRing, capture_fixed_step, pinned
 from .radius_graph import PoseBatcher, radius_graph
 
 
@@ -31,11 +32,10 @@ def _stream(dev):
 
 def _csr_buffers(dev, n_nodes, cap_l, cap=None, **extra):
     """Buffers of a device-built pose-batch graph over n_nodes nodes: the ligand-touching CSR (`*_l`, room for cap_l
-    edges) and, with `cap`, the full CSR and its inv_deg; the builder's status word and its pinned host copy; `ones`
-    (the ligand-touching graph's inv_deg). The builders read f['cap'] / f['cap_l'] at every launch."""
+    edges) and, with `cap`, the full CSR and its inv_deg; the builder's status word; `ones` (the ligand-touching
+    graph's inv_deg). The builders read f['cap'] / f['cap_l'] at every launch."""
     i32 = dict(dtype=torch.int32, device=dev)
-    f = dict(cap=cap, cap_l=cap_l, status=torch.zeros(1, **i32), host=torch.zeros(1, dtype=torch.int32).pin_memory(),
-             **extra)
+    f = dict(cap=cap, cap_l=cap_l, status=torch.zeros(1, **i32), **extra)
     for tag, c in (('', cap), ('_l', cap_l)):
         if c is not None:
             f['rowptr' + tag] = torch.empty(n_nodes + 1, **i32)
@@ -63,11 +63,8 @@ def _graph_pair(f, n_nodes, n_end):
     """(PreparedGraph of f's full CSR, PvsGraph of its ligand-touching CSR) over the first n_nodes nodes, both with
     device-side edge counts (rowptr[n_end])."""
     from .graph import PreparedGraph
-    pg = PreparedGraph(n_nodes, f['cap'], 3, dict(rowptr=f['rowptr'], row=f['row'], col=f['col'], etype=f['etype'],
-                                                   inv_deg=f['inv_deg'], status=f['status']))
-    pg._status_checked = True
-    pg.c.n_edges_dev = f['rowptr'][n_end:].data_ptr()
-    return pg, _ligand_csr(f, n_nodes, n_end)
+    csr = {k: f[k] for k in ('rowptr', 'row', 'col', 'etype', 'inv_deg', 'status')}
+    return PreparedGraph.over_buffers(n_nodes, f['cap'], csr, f['rowptr'][n_end:]), _ligand_csr(f, n_nodes, n_end)
 
 
 TASKS = ('pose', 'affinity', 'both')
@@ -143,7 +140,7 @@ class _ReceptorSideScreen:
     capture / replay scaffolding. A subclass provides `_cache_receptor_sums()` (where the sums are kept),
     `_raise_for(code)` (its status bits), `_head(h)` (pooling + head of a single-head model), `_pool_ptr()` (the
     batch's node offsets, for the heads of a two-headed model) and, once its builder has run, `_fast` (the live buffer
-    dict with `status` / `host`)."""
+    dict with `status`)."""
 
     def __init__(self, model, edge_radius, intra_radius, tasks=None):
         if any(p.dtype == torch.float64 for p in model.parameters()):
@@ -157,7 +154,8 @@ class _ReceptorSideScreen:
         # here (a captured step has them baked in) and never by changing model.model_task
         self.tasks = _resolve_tasks(model, tasks)
         self.heads = None if self.tasks is None else model.task_heads(self.tasks)
-        self._graph, self._captured, self._pending, self._l1_ws, self._fast = None, False, None, None, None
+        self._graph, self._captured, self._l1_ws, self._fast = None, False, None, None
+        self._late = LateQueue(ring=1)      # the one status word in flight: checked before the next builder launch
         self.cam, self._h_final = None, None      # (LibraryScreen(cam=...): per-node heads of the final embedding)
 
     def _weights_fingerprint(self):
@@ -270,35 +268,22 @@ class _ReceptorSideScreen:
             return feats if head is None else self.model._pool_and_head(head, feats, graph_ptr, n_graphs)
         return self._heads_out(feats, graph_ptr)
 
-    def _queue_status(self, status, host):
-        """Queues the copy of a builder's status word into its pinned host copy; check() reads it later."""
-        host.copy_(status, non_blocking=True)
-        event = torch.cuda.Event()
-        event.record(torch.cuda.current_stream(status.device))
-        self._pending = (event, host)
+    def _queue_status(self, status):
+        """Queues the copy of a builder's status word into the screen's pinned word; check() reads it later."""
+        self._late.put(status)
 
     def check(self):
         """Raises if the edge buffers of an earlier batch were too small (checked one batch late so that the loop
         never waits for the device; call once more after the last batch)."""
-        if self._pending is not None:
-            (event, host), self._pending = self._pending, None
-            event.synchronize()
-            self._raise_for(int(host.item()))
+        taken = self._late.take()
+        if taken is not None:
+            self._raise_for(taken[0])
 
     def _capture(self, step, dev):
-        """Captures step() (builder + layer stack + head) in a hipGraph on `dev` after two eager warm-up calls."""
-        stream = torch.cuda.Stream(dev)
-        stream.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(stream):
-            for _ in range(2):
-                step()                         # warm-up: probe, buffers, lazy allocations
-            self.check()
-            torch.cuda.synchronize(dev)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph, stream=stream):
-                self._static_out = step()
-        self._graph, self._captured = graph, True
-        torch.cuda.current_stream(dev).wait_stream(stream)
+        """Captures step() (builder + layer stack + head) in a hipGraph on `dev` after two eager warm-up calls (probe,
+        buffers, lazy allocations)."""
+        self._graph, self._static_out = capture_fixed_step(step, dev, self.check)
+        self._captured = True
         return self
 
     def _replay(self, load):
@@ -307,7 +292,7 @@ class _ReceptorSideScreen:
         self.check()
         load()
         self._graph.replay()
-        self._queue_status(self._fast['status'], self._fast['host'])
+        self._queue_status(self._fast['status'])
         return self._static_out
 
 
@@ -379,7 +364,7 @@ class ReceptorScreen(_ReceptorSideScreen):
             C.byref(full.c), _lib.ptr(b['bp']), b['cap_l'], _lib.ptr(b['rowptr_l']), _lib.ptr(b['row_l']),
             _lib.ptr(b['col_l']), _lib.ptr(b['etype_l']), _lib.ptr(b['status']), _lib.ptr(b['ws']), b['ws'].numel(),
             _stream(dev)), 'pvs_graph_filter_ligand_edges')
-        self._queue_status(b['status'], b['host'])
+        self._queue_status(b['status'])
         return b['gl']
 
     def _raise_for(self, code):
@@ -414,7 +399,7 @@ class ReceptorScreen(_ReceptorSideScreen):
             _lib.ptr(f['etype_l']), _lib.ptr(f['status']), _lib.ptr(f['state']), f['state'].numel(),
             _stream(dev)), 'pvs_screen_graph_build')
         if not capturing:
-            self._queue_status(f['status'], f['host'])
+            self._queue_status(f['status'])
         return f['pg'], f['gl']
 
     def capture(self, example_poses):
@@ -618,7 +603,11 @@ class LibraryScreen(_ReceptorSideScreen):
         self.lig_ptr = torch.zeros(self.b + 1, dtype=torch.int32, device=dev)
         self.n_atoms = 0             # host copies of what load() was given
         self._sizes = [0] * self.b
-        self._stage, self._stage_at = [], 0
+        # two pinned staging sets for load() - the previous batch's copies may still be in flight - pinned at its first
+        # call: a sweep that only calls load_packed needs none
+        self._stage = StagingRing(2, lambda: dict(
+            pos=pinned((self.l_cap, 3), torch.float32), feats=pinned((self.l_cap, n_feats), torch.float32),
+            ptr=pinned(self.b + 1, torch.int32)))
         self._pack_status = None     # load_leave_out's status word
         self.rec_drop = torch.full((self.b,), -1, dtype=torch.int32, device=dev) if self.struck else None
         self._n_struck = 0           # host copy: how many slots of the loaded batch lack a receptor atom
@@ -753,17 +742,7 @@ class LibraryScreen(_ReceptorSideScreen):
         slots = list(slots)
         sizes = self._checked_sizes(pose.shape[0] for _, pose in slots)
         total = sum(sizes)
-        if len(self._stage) < 2:      # two staging sets: the previous batch's copies may still be in flight
-            self._stage.append(dict(
-                pos=torch.zeros((self.l_cap, 3), dtype=torch.float32).pin_memory(),
-                feats=torch.zeros((self.l_cap, self.lig_feats.shape[1]), dtype=torch.float32).pin_memory(),
-                ptr=torch.zeros(self.b + 1, dtype=torch.int32).pin_memory(), event=None))
-            st = self._stage[-1]
-        else:
-            self._stage_at ^= 1
-            st = self._stage[self._stage_at]
-        if st['event'] is not None:
-            st['event'].synchronize()
+        st = self._stage.acquire()
         at = 0
         for k in range(self.b):
             st['ptr'][k] = at
@@ -774,8 +753,7 @@ class LibraryScreen(_ReceptorSideScreen):
                 at += sizes[k]
         st['ptr'][self.b] = at
         self.load_packed(st['pos'][:total], st['feats'][:total], st['ptr'], sizes, rec_drop)
-        st['event'] = torch.cuda.Event()
-        st['event'].record(torch.cuda.current_stream(self.lig_pos.device))
+        self._stage.release(self.lig_pos.device)
         return self
 
     def load_leave_out(self, lig_pos, lig_feats, lig_ptr, sizes, first_copy):
@@ -912,7 +890,7 @@ class LibraryScreen(_ReceptorSideScreen):
             self.check()
         self._launch_builder(f)
         if not capturing:
-            self._queue_status(f['status'], f['host'])
+            self._queue_status(f['status'])
         return f
 
     def _raise_for(self, code):
@@ -947,10 +925,7 @@ class LibraryScreen(_ReceptorSideScreen):
         return y
 
     def _head(self, h):
-        model, node_ptr = self.model, self._fast['node_ptr']
-        if self.b == 1:     # (one slot: the pooling still ends at node_ptr[1], not at the padded shape)
-            return model._run_head(model.feats_linear_layers, PF.mean_pool(h, node_ptr))
-        return model._pool_and_head(model.feats_linear_layers, h, node_ptr, self.b)
+        return self.model._pool_and_head_padded(self.model.feats_linear_layers, h, self._fast['node_ptr'], self.b)
 
     def _pool_ptr(self):
         return self._fast['node_ptr']

@@ -7,8 +7,9 @@ small two-graph batch. Under a kernel trace, once per library and once more with
 Two libraries enqueue the same work when their OUT.txt files are equal (profiles/linear_job_refactor.txt).
 `--screening` traces instead one eager step of each screen (ReceptorScreen on the pose-batch builder and on the filter
 path, LibraryScreen plain, with struck slots, with contact attention and with cam) at a small shape (130-atom receptor,
-batch of 3): the record that a change of the screens' host code left every launch alone
-(profiles/screening_refactor.txt, profiles/hit_attribution_refactor.txt). `--fp64` runs the loop of the default mode with model
+batch of 3) and one eager FixedShapeScorer step on two complexes of the cli_default golden root: the record that a
+change of the screens' host code left every launch alone (profiles/screening_refactor.txt,
+profiles/hit_attribution_refactor.txt, profiles/nowait_refactor.txt). `--fp64` runs the loop of the default mode with model
 and batch in double (hidden 16 / 32 / 64, the per-layer path: there is no fp64 stack), for a change of the binding's
 fp64 side (profiles/functional_dtype_refactor.txt)."""
 import csv
@@ -88,6 +89,15 @@ def run_screening():
         screen = LibraryScreen(m, rec, rec_feats, 3, 20, 7.0, **extra)
         screen(slots)
         screen.check()
+    # the data-root scorer: one eager fixed-shape step on two complexes of the cli_default golden root
+    from pointvs_amd.captured_scoring import FixedShapeScorer
+    from tests._fixed_shape_cases import generous_capacities
+    from tests.test_gpu_fixed_shape_scoring import make_model
+    from tests.test_gpu_parquet_dataset import setting
+    _, ds = setting('cli_default')
+    scorer = FixedShapeScorer(make_model(ds.feature_dim), ds, 2, generous_capacities(ds, [0, 1]), device='cuda')
+    scorer([0, 1])
+    scorer.check()
     torch.cuda.synchronize()
 
 
