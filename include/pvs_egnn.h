@@ -280,7 +280,8 @@ int pvs_egnn_layer_fwd(const PvsLayerDesc* desc, const PvsGraph* graph, const Pv
  *   pvs_egnn_layer_fwd_partial: EGNNLayer.forward where `graph` holds only part of every row's edges
  *     and the rest enters as base_magg [N,H], base_xsum [N,3], base_deg [N] (edge counts as floats):
  *     M = base_magg + sums over graph, x' = x + (base_xsum + sums) / max(base_deg + deg_graph, 1).
- * No edge_residual, no softmax attention, H = 32 or 64; no backward. Workspace:
+ * No edge_residual, no softmax attention, H = 32, 64 or 128 (the MFMA edge forward: the generic kernels of H = 16 and
+ * of PVS_EGNN_KERNELS=generic are refused); no backward. Workspace:
  * pvs_egnn_layer_workspace_bytes(desc, N, E, 2). */
 int pvs_egnn_layer_edge_sums(const PvsLayerDesc* desc, const PvsGraph* graph, const PvsLayerParams* params,
                              const float* h, const float* x, float* magg, float* xsum,

@@ -391,7 +391,7 @@ int partial_checks(const PvsLayerDesc* d, const PvsGraph* g, const PvsLayerParam
     PVS_TRY(check_desc(d, g, p, true));
     *fam = pvs_edge_family(d->hidden, d->flags, d->n_edge_attr, PVS_EDGE_FWD);
     PVS_REQUIRE(*fam != PVS_EDGE_GENERIC,
-                "partial-sum forward needs the MFMA edge kernel (H = 32 or 64)");
+                "partial-sum forward needs the MFMA edge kernel (H = 32, 64 or 128)");
     PVS_REQUIRE(!((d->flags & PVS_EDGE_ATTENTION) && (d->flags & PVS_SOFTMAX_ATT)),
                 "partial-sum forward: softmax attention is not supported (row sums of two edge sets do not add)");
     PVS_REQUIRE(!(d->flags & PVS_EDGE_RESIDUAL), "partial-sum forward: edge_residual layers are not supported");
