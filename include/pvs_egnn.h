@@ -90,8 +90,8 @@ typedef struct PvsGraph {
     int32_t n_graphs;
     /* Optional DEVICE int32: the number of LEADING rows that enter GraphNorm's statistics when it is only known on the
      * device (a padded, captured step: the real nodes in front, padding rows behind them). NULL: n_nodes. Read by the
-     * fp32 layer entry points under PVS_GRAPHNORM (pvs_egnn_layer_fwd / _fwd_partial / _fwd_partial_att / _bwd and
-     * pvs_egnn_stack_fwd / _bwd), ignored without that flag, refused by the *_f64 entry points. With n = the value
+     * fp32 layer entry points under PVS_GRAPHNORM (pvs_egnn_layer_fwd / _fwd_partial / _fwd_partial_att /
+     * _fwd_partial_softmax / _bwd and pvs_egnn_stack_fwd / _bwd), ignored without that flag, refused by the *_f64 entry points. With n = the value
      * clamped to [0, n_nodes]: mean and variance are those of rows [0, n) - bit for bit the statistics of a call on
      * those n rows alone -, rows >= n are never read for them, ALL n_nodes rows are normalised with them, and the
      * backward is the exact gradient of that (with zero upstream gradient on the rows >= n: the gradient of the n-row
@@ -299,6 +299,33 @@ int pvs_egnn_layer_fwd_partial_att(const PvsLayerDesc* desc, const PvsGraph* gra
                                    const float* base_deg, float* h_out, float* x_out, float* node_att_out,
                                    float* att_out, float* saved, void* workspace, size_t workspace_bytes,
                                    pvs_stream_t stream);
+
+/* The same reuse for layers with PVS_EDGE_ATTENTION | PVS_SOFTMAX_ATT (and only for them: every other layer is refused
+ * here, as softmax layers are refused by the three entries above). Row sums of two edge sets do not add under a softmax,
+ * but its statistics merge exactly. For a row i and an edge set T with logits l_e = w_a.m_e + b_a:
+ *   mu_T = max l_e,  S_T = sum exp(l_e - mu_T),  A_T = sum exp(l_e - mu_T) m_e / S_T      (S_T >= 1 for a set with an edge)
+ * and for the base set b and the set g of `graph`, with mu = max(mu_b, mu_g), a_b = S_b exp(mu_b - mu), a_g = S_g exp(mu_g - mu):
+ *   M_i = (a_b A_b + a_g A_g) / (a_b + a_g),   att_e = exp(l_e - mu_g) / S_g * a_g / (a_b + a_g)  for e in g.
+ * A set without an edge in row i contributes nothing; a row without any edge has M_i = 0. The coordinate sums are not
+ * attention weighted: base_xsum / base_deg are those of pvs_egnn_layer_edge_sums.
+ * A BASE ROW is H + 4 floats: A_b [H] | mu_b | S_b | 0 | 0; an all-zero row means "no base". base_rows [N, H + 4] is
+ * 16-byte aligned.
+ *   pvs_egnn_layer_edge_stats_softmax: base rows and xsum [N,3] (no 1/deg) over the edges of `graph`; rows without an
+ *     edge are all zero.
+ *   pvs_egnn_layer_fwd_partial_softmax: the contract of pvs_egnn_layer_fwd_partial_att (a device-side edge count and
+ *     n_norm_rows_dev are honoured, x_out must not alias x); att_out, or NULL, receives the attention of graph's edges
+ *     normalised over ALL edges of their rows (entries behind a device-side count are left as they are); h_out, x_out and
+ *     node_att_out have the same bits with and without it.
+ * H = 32, 64 or 128 on the MFMA edge forward, no edge_residual, no backward, the same bits on every run. Workspace of both:
+ * pvs_egnn_layer_workspace_bytes(desc, N, E, 3). */
+int pvs_egnn_layer_edge_stats_softmax(const PvsLayerDesc* desc, const PvsGraph* graph, const PvsLayerParams* params,
+                                      const float* h, const float* x, float* base_rows, float* xsum,
+                                      void* workspace, size_t workspace_bytes, pvs_stream_t stream);
+int pvs_egnn_layer_fwd_partial_softmax(const PvsLayerDesc* desc, const PvsGraph* graph, const PvsLayerParams* params,
+                                       const float* h, const float* x, const float* base_rows, const float* base_xsum,
+                                       const float* base_deg, float* h_out, float* x_out, float* node_att_out,
+                                       float* att_out, float* saved, void* workspace, size_t workspace_bytes,
+                                       pvs_stream_t stream);
 
 /* The edges of `full` that touch a ligand atom (bp == 0), as a CSR over the same nodes, without a
  * host round trip: rowptr_out [N+1] (its last entry = the edge count, pass it as

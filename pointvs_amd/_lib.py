@@ -159,6 +159,12 @@ _PROTOTYPES = {
     'pvs_egnn_layer_fwd_partial_att': (C.c_int, [C.POINTER(PvsLayerDesc), C.POINTER(PvsGraph),
                                                  C.POINTER(PvsLayerParams)] + [C.c_void_p] * 10 +
                                        [C.c_void_p, C.c_size_t, C.c_void_p]),
+    'pvs_egnn_layer_edge_stats_softmax': (C.c_int, [C.POINTER(PvsLayerDesc), C.POINTER(PvsGraph),
+                                                    C.POINTER(PvsLayerParams)] + [C.c_void_p] * 4 +
+                                          [C.c_void_p, C.c_size_t, C.c_void_p]),
+    'pvs_egnn_layer_fwd_partial_softmax': (C.c_int, [C.POINTER(PvsLayerDesc), C.POINTER(PvsGraph),
+                                                     C.POINTER(PvsLayerParams)] + [C.c_void_p] * 10 +
+                                           [C.c_void_p, C.c_size_t, C.c_void_p]),
     'pvs_egnn_layer_bwd':(C.c_int, [C.POINTER(PvsLayerDesc), C.POINTER(PvsGraph),
                                      C.POINTER(PvsLayerParams)] + [C.c_void_p] * 11 +
                            [C.POINTER(PvsLayerGrads), C.c_void_p, C.c_size_t, C.c_void_p]),

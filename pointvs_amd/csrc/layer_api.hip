@@ -313,6 +313,9 @@ extern "C" size_t pvs_egnn_layer_workspace_bytes(const PvsLayerDesc* d, int32_t 
     PvsArena a(nullptr, 0);
     if (backward == 2)   // pvs_egnn_layer_edge_sums / _fwd_partial: forward + a per-edge attention scratch
         return carve_fwd(a, m, nullptr) + pvs_align_up((size_t)(E > 0 ? E : 1) * sizeof(float), 256) + 512;
+    if (backward == 3)   // pvs_egnn_layer_edge_stats_softmax / _fwd_partial_softmax: mode 2 + the rows' attention factors
+        return carve_fwd(a, m, nullptr) + pvs_align_up((size_t)(E > 0 ? E : 1) * sizeof(float), 256) +
+               pvs_align_up((size_t)(N > 0 ? N : 1) * sizeof(float), 256) + 512;
     return (backward ? carve_bwd(a, m, nullptr) : carve_fwd(a, m, nullptr)) + 256;
 }
 
@@ -467,6 +470,186 @@ extern "C" int pvs_egnn_layer_fwd_partial(const PvsLayerDesc* d, const PvsGraph*
                                           size_t workspace_bytes, pvs_stream_t stream_) {
     return pvs_egnn_layer_fwd_partial_att(d, g, p, h, x, base_magg, base_xsum, base_deg, h_out, x_out, node_att_out,
                                           nullptr, saved, workspace, workspace_bytes, stream_);
+}
+
+// ---- the same for softmax attention: the softmax statistics of two edge sets merge exactly ----
+// For a row i and an edge set T with logits l_e: mu_T = max l_e, S_T = sum exp(l_e - mu_T), A_T = sum exp(l_e - mu_T) m_e
+// / S_T - what the softmax MFMA forward leaves in smax / ssum / Magg at every row it flushes. A BASE ROW is H + 4 floats:
+// A_b [H] | mu_b | S_b | 0 | 0; all zero: no base (S_b >= 1 for a set with an edge).
+namespace {
+
+constexpr int kBaseRowExtra = 4;      // mu, S and two zeros behind the H channels: rows stay 16-byte multiples
+
+// Magg / smax / ssum of the base launch -> base rows; rows without an edge (never flushed: their statistics are whatever
+// the workspace held) are decided from the degree and written as zeros
+__global__ void k_pack_base_rows(const float* __restrict__ Magg, const float* __restrict__ smax,
+                                 const float* __restrict__ ssum, const int32_t* __restrict__ rowptr,
+                                 float* __restrict__ base_rows, int N, int H) {
+    const int qpr = H / 4 + 1;
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    const int n = t / qpr, q = t - n * qpr;
+    if (n >= N) return;
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (rowptr[n + 1] > rowptr[n]) {
+        if (q < H / 4) v = *reinterpret_cast<const float4*>(Magg + (size_t)n * H + 4 * q);
+        else { v.x = smax[n]; v.y = ssum[n]; }
+    }
+    *reinterpret_cast<float4*>(base_rows + (size_t)n * (H + kBaseRowExtra) + 4 * q) = v;
+}
+
+// One thread per row and channel quad, like k_combine_partial: Magg (A_g, normalised over the graph's edges of the row)
+// becomes the mean over both sets, the coordinate update is k_combine_partial's, and the row's attention factor
+// a_g / (a_b + a_g) goes to fac. The larger maximum's weight is its S itself, the other's carries the one expf.
+__global__ void k_combine_partial_softmax(float* __restrict__ Magg, float* __restrict__ x_out, const float* __restrict__ x,
+                                          const float* __restrict__ base_rows, const float* __restrict__ base_xsum,
+                                          const float* __restrict__ base_deg, const int32_t* __restrict__ rowptr,
+                                          const float* __restrict__ smax, const float* __restrict__ ssum,
+                                          float* __restrict__ fac, int N, int H, int upd) {
+    const int qpr = H / 4;
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    const int n = t / qpr, q = t - n * qpr;
+    if (n >= N) return;
+    const float* brow = base_rows + (size_t)n * (H + kBaseRowExtra);
+    const float4 stat = *reinterpret_cast<const float4*>(brow + H);      // mu_b, S_b, 0, 0
+    const int deg_g = rowptr[n + 1] - rowptr[n];
+    const bool has_b = stat.y > 0.f, has_g = deg_g > 0;
+    float wb = has_b ? 1.f : 0.f, wg = has_g ? 1.f : 0.f;
+    if (has_b && has_g) {
+        const float mu_g = smax[n], S_g = ssum[n], d = stat.x - mu_g;
+        const float f = expf(-fabsf(d));
+        const float a_b = d >= 0.f ? stat.y : stat.y * f, a_g = d >= 0.f ? S_g * f : S_g;
+        const float inv = 1.0f / (a_b + a_g);
+        wb = a_b * inv;
+        wg = a_g * inv;
+    }
+    float4* mp = reinterpret_cast<float4*>(Magg + (size_t)n * H + 4 * q);
+    float4 m = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (has_g) {
+        const float4 a = *mp;
+        m.x = wg * a.x; m.y = wg * a.y; m.z = wg * a.z; m.w = wg * a.w;
+    }
+    if (has_b) {
+        const float4 b = *reinterpret_cast<const float4*>(brow + 4 * q);
+        m.x = fmaf(wb, b.x, m.x); m.y = fmaf(wb, b.y, m.y); m.z = fmaf(wb, b.z, m.z); m.w = fmaf(wb, b.w, m.w);
+    }
+    *mp = m;
+    if (q == 0) {
+        fac[n] = wg;
+        if (upd) {
+            const float deg = base_deg[n] + (float)deg_g;
+            const float inv = 1.0f / (deg > 1.f ? deg : 1.f);
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+                x_out[3 * n + c] = x[3 * n + c] + (base_xsum[3 * n + c] + x_out[3 * n + c]) * inv;
+        } else {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) x_out[3 * n + c] = x[3 * n + c];
+        }
+    }
+}
+
+// att[e] (normalised over the graph's edges of its row) -> normalised over both sets; entries behind a device-side count
+// stay as they are
+__global__ void k_scale_att_rows(PvsGraph g, const float* __restrict__ fac, float* __restrict__ att) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= g.n_edges || (g.n_edges_dev && e >= *g.n_edges_dev)) return;
+    att[e] *= fac[g.row[e]];
+}
+
+int softmax_partial_checks(const PvsLayerDesc* d, const PvsGraph* g, const PvsLayerParams* p, PvsEdgeFamily* fam) {
+    PVS_TRY(check_desc(d, g, p, true));
+    *fam = pvs_edge_family(d->hidden, d->flags, d->n_edge_attr, PVS_EDGE_FWD);
+    PVS_REQUIRE(*fam != PVS_EDGE_GENERIC,
+                "softmax partial forward needs the MFMA edge kernel (H = 32, 64 or 128)");
+    PVS_REQUIRE((d->flags & PVS_EDGE_ATTENTION) && (d->flags & PVS_SOFTMAX_ATT),
+                "softmax partial forward: for layers with edge attention and softmax attention only (the others: "
+                "pvs_egnn_layer_edge_sums / pvs_egnn_layer_fwd_partial)");
+    PVS_REQUIRE(!(d->flags & PVS_EDGE_RESIDUAL), "softmax partial forward: edge_residual layers are not supported");
+    return 0;
+}
+
+struct SoftPartialWs {
+    FwdWs w;
+    float *att, *fac;
+};
+
+// mode 3 of pvs_egnn_layer_workspace_bytes
+void carve_soft_partial(PvsArena& a, const Dims& m, SoftPartialWs* t) {
+    carve_fwd(a, m, &t->w);
+    t->att = a.take<float>((size_t)(m.E > 0 ? m.E : 1));
+    t->fac = a.take<float>((size_t)m.N);
+}
+
+}  // namespace
+
+extern "C" int pvs_egnn_layer_edge_stats_softmax(const PvsLayerDesc* d, const PvsGraph* g, const PvsLayerParams* p,
+                                                 const float* h, const float* x, float* base_rows, float* xsum,
+                                                 void* workspace, size_t workspace_bytes, pvs_stream_t stream_) {
+    hipStream_t s = (hipStream_t)stream_;
+    PvsEdgeFamily fam;
+    PVS_TRY(softmax_partial_checks(d, g, p, &fam));
+    PVS_REQUIRE(h && x && base_rows && xsum, "pvs_egnn_layer_edge_stats_softmax: NULL tensor");
+    PVS_REQUIRE(((uintptr_t)base_rows & 15) == 0, "pvs_egnn_layer_edge_stats_softmax: base_rows must be 16-byte aligned");
+    const Dims m = make_dims(d, g);
+    PvsArena arena(workspace, workspace_bytes);
+    SoftPartialWs t;
+    carve_soft_partial(arena, m, &t);
+    PVS_REQUIRE(arena.ok(), "pvs_egnn_layer_edge_stats_softmax: workspace too small (%zu < %zu)", workspace_bytes,
+                arena.off);
+    const PvsEdgeW ew = make_edge_w(m, p);
+    float* A_b = t.w.y1;       // [N, H] of the forward's workspace that this entry has no other use for
+    PvsEdgeFwdIO io = make_fwd_io(t.w, t.w.PQ, x, nullptr, A_b, xsum, nullptr, t.att);
+    PVS_TRY(node_pre_forward(s, m, p, h, t.w.PQ, &io, d->flags | kFwdRawXsum));
+    PVS_TRY(pvs_launch_edge_fwd_mfma(s, m.H, fam, *g, ew, d->flags | kFwdRawXsum, d->att_act, io));
+    if (!(d->flags & PVS_UPDATE_COORDS))
+        PVS_CHECK_HIP(hipMemsetAsync(xsum, 0, sizeof(float) * 3 * (size_t)m.N, s));
+    const long long threads = (long long)m.N * (m.H / 4 + 1);
+    k_pack_base_rows<<<(int)((threads + 255) / 256), 256, 0, s>>>(A_b, t.w.smax, t.w.ssum, g->rowptr, base_rows, m.N, m.H);
+    PVS_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int pvs_egnn_layer_fwd_partial_softmax(const PvsLayerDesc* d, const PvsGraph* g, const PvsLayerParams* p,
+                                                  const float* h, const float* x, const float* base_rows,
+                                                  const float* base_xsum, const float* base_deg, float* h_out,
+                                                  float* x_out, float* node_att_out, float* att_out, float* saved,
+                                                  void* workspace, size_t workspace_bytes, pvs_stream_t stream_) {
+    hipStream_t s = (hipStream_t)stream_;
+    PvsEdgeFamily fam;
+    PVS_TRY(softmax_partial_checks(d, g, p, &fam));
+    PVS_REQUIRE(h && x && base_rows && base_xsum && base_deg && h_out && x_out && saved,
+                "pvs_egnn_layer_fwd_partial_softmax: NULL tensor");
+    PVS_REQUIRE(x_out != x, "pvs_egnn_layer_fwd_partial_softmax: x_out must not alias x");
+    PVS_REQUIRE(((uintptr_t)base_rows & 15) == 0, "pvs_egnn_layer_fwd_partial_softmax: base_rows must be 16-byte aligned");
+    const Dims m = make_dims(d, g);
+    PvsArena arena(workspace, workspace_bytes);
+    SoftPartialWs t;
+    carve_soft_partial(arena, m, &t);
+    PVS_REQUIRE(arena.ok(), "pvs_egnn_layer_fwd_partial_softmax: workspace too small (%zu < %zu)", workspace_bytes,
+                arena.off);
+    float* att = att_out ? att_out : t.att;       // the caller keeps the layer's attention (CSR-sorted over g)
+    const int H = m.H;
+    const SavedLayout sv = saved_layout(saved, m.N, H);
+    const PvsEdgeW ew = make_edge_w(m, p);
+    const PvsNodeW nw = make_node_w(d, p);
+    PvsEdgeFwdIO io = make_fwd_io(t.w, sv.PQ, x, nullptr, sv.Magg, x_out, nullptr, att);
+    PVS_TRY(node_pre_forward(s, m, p, h, sv.PQ, &io, d->flags | kFwdRawXsum));
+    pvs_prof_set_fwd_tag(PVS_PROF_EDGE_FWD_PARTIAL);
+    const int rc_partial = pvs_launch_edge_fwd_mfma(s, H, fam, *g, ew, d->flags | kFwdRawXsum, d->att_act, io);
+    pvs_prof_set_fwd_tag(PVS_PROF_EDGE_FWD);
+    PVS_TRY(rc_partial);
+    const long long threads = (long long)m.N * (H / 4);
+    k_combine_partial_softmax<<<(int)((threads + 255) / 256), 256, 0, s>>>(
+        sv.Magg, x_out, x, base_rows, base_xsum, base_deg, g->rowptr, t.w.smax, t.w.ssum, t.fac, m.N, H,
+        (d->flags & PVS_UPDATE_COORDS) ? 1 : 0);
+    PVS_CHECK_LAUNCH();
+    if (att_out && g->n_edges > 0) {
+        k_scale_att_rows<<<(g->n_edges + 255) / 256, 256, 0, s>>>(*g, t.fac, att_out);
+        PVS_CHECK_LAUNCH();
+    }
+    PVS_TRY(node_mlp_forward(s, m, d, p, nw, h, sv.Magg, sv.y1, sv.u, sv.o, sv.stats, true, t.w.shift, t.w.slabs, h_out,
+                             node_att_out, g->n_norm_rows_dev));
+    return 0;
 }
 
 extern "C" int pvs_egnn_layer_bwd(const PvsLayerDesc* d, const PvsGraph* g, const PvsLayerParams* p,

@@ -7,7 +7,9 @@ receptor features and coordinates, so their per-node sums are computed once
 (`pvs_egnn_layer_edge_sums` on the receptor-only graph); per batch the first layer only runs over
 the edges that touch a ligand atom (`pvs_egnn_layer_fwd_partial`), the other layers over the full
 graph. Graphs are built on the GPU from the coordinates (radius_graph.py). Scores equal the plain
-`model(batch)` forward up to fp32 summation order.
+`model(batch)` forward up to fp32 summation order. A first layer with edge attention under softmax_attention has no
+sums that add; with `softmax_reuse=True` its receptor side is kept as softmax statistics instead, which merge exactly
+(`pvs_egnn_layer_edge_stats_softmax`, `pvs_egnn_layer_fwd_partial_softmax`).
 """
 import contextlib
 import ctypes as C
@@ -142,7 +144,7 @@ class _ReceptorSideScreen:
     batch's node offsets, for the heads of a two-headed model) and, once its builder has run, `_fast` (the live buffer
     dict with `status`)."""
 
-    def __init__(self, model, edge_radius, intra_radius, tasks=None):
+    def __init__(self, model, edge_radius, intra_radius, tasks=None, softmax_reuse=False):
         if any(p.dtype == torch.float64 for p in model.parameters()):
             raise NotImplementedError(f'{type(self).__name__} and its pose-batch builder are fp32 only (no fp64 '
                                       'screening kernels): score fp64 models through the model forward')
@@ -150,6 +152,11 @@ class _ReceptorSideScreen:
         self.model, self.embed, self.egnn = model, layers[0], layers[1:]
         self.r_inter = edge_radius
         self.r_intra = edge_radius if intra_radius is None else intra_radius
+        # opt-in: a first layer with edge attention under softmax_attention takes the first-layer reuse as well, its
+        # receptor side kept as softmax statistics (base rows of H + 4 floats) instead of sums
+        self.softmax_reuse = bool(softmax_reuse)
+        first = self.egnn[0] if self.egnn else None
+        self._soft = bool(self.softmax_reuse and first is not None and first.softmax_attention and first.edge_attention)
         # None: a single-head model, the path below as it always was; else the heads of a two-headed model, resolved
         # here (a captured step has them baked in) and never by changing model.model_task
         self.tasks = _resolve_tasks(model, tasks)
@@ -157,6 +164,13 @@ class _ReceptorSideScreen:
         self._graph, self._captured, self._l1_ws, self._fast = None, False, None, None
         self._late = LateQueue(ring=1)      # the one status word in flight: checked before the next builder launch
         self.cam, self._h_final = None, None      # (LibraryScreen(cam=...): per-node heads of the final embedding)
+
+    def _first_layer_reusable(self):
+        """The first layer's part in `reuse`: hidden size 32 or 64, and no softmax attention - unless the screen was
+        built with softmax_reuse and the layer has edge attention (a softmax flag without edge attention stays out)."""
+        first = self.egnn[0] if self.egnn else None
+        return (first is not None and first.hidden_nf in (32, 64)
+                and (not first.softmax_attention or self._soft))
 
     def _weights_fingerprint(self):
         """Version counters of everything the cached receptor-receptor sums were computed from (the
@@ -188,7 +202,9 @@ class _ReceptorSideScreen:
 
     def _receptor_sums(self, rec_feats, rec_pos):
         """Per-node sums of the first layer's receptor-receptor messages (pose and ligand independent):
-        (magg [n_rec,H], xsum [n_rec,3], deg [n_rec]). Keeps the receptor-receptor template CSR (`_rr`: rowptr /
+        (magg [n_rec,H], xsum [n_rec,3], deg [n_rec]); under softmax_reuse magg is the layer's base rows [n_rec,H+4]
+        (weighted mean | maximum logit | denominator | 0 | 0: pvs_egnn_layer_edge_stats_softmax). Keeps the
+        receptor-receptor template CSR (`_rr`: rowptr /
         col, receptor-local ids) and the fingerprint of the weights used."""
         lib = _lib.lib()
         dev, n_rec = rec_pos.device, rec_pos.shape[0]
@@ -198,14 +214,16 @@ class _ReceptorSideScreen:
             pg = radius_graph(rec_pos, torch.ones(n_rec, dtype=torch.uint8, device=dev), None,
                               self.r_inter, self.r_intra, need_backward=False)
             desc, params, pstruct = self._first_layer_args()
-            magg = torch.empty((n_rec, self.egnn[0].hidden_nf), dtype=torch.float32, device=dev)
+            width = self.egnn[0].hidden_nf + (4 if self._soft else 0)
+            name = 'pvs_egnn_layer_edge_stats_softmax' if self._soft else 'pvs_egnn_layer_edge_sums'
+            magg = torch.empty((n_rec, width), dtype=torch.float32, device=dev)
             xsum = torch.empty((n_rec, 3), dtype=torch.float32, device=dev)
-            ws_bytes = lib.pvs_egnn_layer_workspace_bytes(C.byref(desc), n_rec, pg.n_edges, 2)
+            ws_bytes = lib.pvs_egnn_layer_workspace_bytes(C.byref(desc), n_rec, pg.n_edges, 3 if self._soft else 2)
             ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            _lib.check(lib.pvs_egnn_layer_edge_sums(
+            _lib.check(getattr(lib, name)(
                 C.byref(desc), C.byref(pg.c), C.byref(pstruct), _lib.ptr(h_rec.contiguous()),
                 _lib.ptr(rec_pos.contiguous()), _lib.ptr(magg), _lib.ptr(xsum), _lib.ptr(ws), ws_bytes,
-                _stream(dev)), 'pvs_egnn_layer_edge_sums')
+                _stream(dev)), name)
             deg = (pg.t['rowptr'][1:] - pg.t['rowptr'][:-1]).float()
             self._rr = pg
             torch.cuda.current_stream(dev).synchronize()    # ws / params go out of scope
@@ -214,7 +232,9 @@ class _ReceptorSideScreen:
     def _partial_first_layer(self, g, h, x, base_magg, base_xsum, base_deg, ws_nodes, ws_edges, att_out=None):
         """First layer over the ligand-touching edges `g` on top of the receptor-receptor sums `base_*` (one row
         per node). ws_nodes / ws_edges size the saved / workspace pair, allocated at the first call. att_out
-        [>= g's edge room]: receives the layer's edge attention in g's edge order (pvs_egnn_layer_fwd_partial_att)."""
+        [>= g's edge room]: receives the layer's edge attention in g's edge order (pvs_egnn_layer_fwd_partial_att).
+        Under softmax_reuse base_magg holds base rows and the entry is pvs_egnn_layer_fwd_partial_softmax, whose
+        attention is normalised over all edges of a row."""
         lib = _lib.lib()
         dev = h.device
         desc, params, pstruct = self._first_layer_args()
@@ -224,14 +244,17 @@ class _ReceptorSideScreen:
             self._l1_ws = (
                 torch.empty(lib.pvs_egnn_layer_saved_floats(C.byref(desc), ws_nodes, ws_edges), dtype=torch.float32,
                             device=dev),
-                torch.empty(lib.pvs_egnn_layer_workspace_bytes(C.byref(desc), ws_nodes, ws_edges, 2),
+                torch.empty(lib.pvs_egnn_layer_workspace_bytes(C.byref(desc), ws_nodes, ws_edges, 3 if self._soft else 2),
                             dtype=torch.uint8, device=dev))
         saved, ws = self._l1_ws
         args = [C.byref(desc), C.byref(g), C.byref(pstruct), _lib.ptr(h), _lib.ptr(x), _lib.ptr(base_magg),
                 _lib.ptr(base_xsum), _lib.ptr(base_deg), _lib.ptr(h_out), _lib.ptr(x_out), _lib.ptr(natt),
                 _lib.ptr(saved), _lib.ptr(ws), ws.numel(), _stream(dev)]
         name = 'pvs_egnn_layer_fwd_partial'
-        if att_out is not None:      # (the _att entry point takes att_out behind natt and is otherwise called alike)
+        if self._soft:               # (att_out, or NULL, behind natt)
+            args.insert(11, _lib.ptr(att_out))
+            name = 'pvs_egnn_layer_fwd_partial_softmax'
+        elif att_out is not None:    # (the _att entry point takes att_out behind natt and is otherwise called alike)
             args.insert(11, _lib.ptr(att_out))
             name = 'pvs_egnn_layer_fwd_partial_att'
         _lib.check(getattr(lib, name)(*args), name)
@@ -302,13 +325,15 @@ class ReceptorScreen(_ReceptorSideScreen):
     feats [n_lig + n_rec, F]: ligand rows first, last column = bp (preprocessing.make_bit_vector);
     lig_poses [batch_size, n_lig, 3] on the device. Returns the model's raw outputs [batch_size, ...].
     tasks (two-headed models, `_resolve_tasks`): 'pose', 'affinity' or 'both' - [batch_size, 1 + A], pose logit first,
-    from one trunk pass."""
+    from one trunk pass.
+    softmax_reuse (opt-in, default False): a first layer with edge attention under softmax_attention takes the first-layer
+    reuse too (its receptor side as softmax statistics, merged per row with the ligand-touching edges'); without it such a
+    model runs the plain forward. The keyword changes nothing for any other model."""
 
-    def __init__(self, model, rec_pos, feats, n_lig, batch_size, edge_radius, intra_radius=None, tasks=None):
-        super().__init__(model, edge_radius, intra_radius, tasks)
-        first = self.egnn[0] if self.egnn else None
-        self.reuse = (first is not None and first.hidden_nf in (32, 64) and not first.softmax_attention
-                      and not first.edge_residual)
+    def __init__(self, model, rec_pos, feats, n_lig, batch_size, edge_radius, intra_radius=None, tasks=None,
+                 softmax_reuse=False):
+        super().__init__(model, edge_radius, intra_radius, tasks, softmax_reuse)
+        self.reuse = self._first_layer_reusable() and not self.egnn[0].edge_residual
         dev = rec_pos.device
         self.batcher = PoseBatcher(rec_pos, feats, n_lig, batch_size, edge_radius, intra_radius)
         self.n_lig, self.b = n_lig, batch_size
@@ -540,6 +565,10 @@ class LibraryScreen(_ReceptorSideScreen):
     each other, as in every batched route. The keyword changes nothing for a model without graphnorm, nor for the
     plain route below. Models the first-layer reuse does not cover (edge_residual, softmax attention, hidden size not
     32 / 64) take the plain forward on the same mixed batch. fp32 only. tasks: as for ReceptorScreen.
+    softmax_reuse (opt-in, default False): as for ReceptorScreen - a first layer with edge attention under
+    softmax_attention takes the reuse, and with it capture(), struck slots and contact_attention; the builder then expands
+    base rows of H + 4 floats (PvsRaggedNodeTables.hidden is a free row width), and contact_attention=1 reduces attention
+    values normalised over ALL edges of a row, the reference's att_val.
 
     cam: None, True or a column (`resolve_cam`): the class-activation map of every step - the heads the screen
     evaluates, applied to every node's final embedding (PF.node_heads) and gathered per slot (PF.slot_node_values),
@@ -565,8 +594,9 @@ class LibraryScreen(_ReceptorSideScreen):
     per slot). A screen without it launches exactly what it always launched."""
 
     def __init__(self, model, rec_pos, rec_feats, batch_size, max_lig_atoms, edge_radius, intra_radius=None,
-                 tasks=None, contact_attention=None, cam=None, struck=None, padded_graphnorm=False):
-        super().__init__(model, edge_radius, intra_radius, tasks)
+                 tasks=None, contact_attention=None, cam=None, struck=None, padded_graphnorm=False,
+                 softmax_reuse=False):
+        super().__init__(model, edge_radius, intra_radius, tasks, softmax_reuse)
         self.struck = bool(struck)
         self.padded_graphnorm = bool(padded_graphnorm)
         if self.struck and (cam is not None or contact_attention is not None):
@@ -578,9 +608,7 @@ class LibraryScreen(_ReceptorSideScreen):
         if not 1 <= int(max_lig_atoms) <= MAX_SCREEN_LIGAND_ATOMS:
             raise ValueError(f'max_lig_atoms must be 1..{MAX_SCREEN_LIGAND_ATOMS} (got {max_lig_atoms})')
         _lib.require_hip(rec_pos)
-        first = self.egnn[0] if self.egnn else None
-        self.reuse = (first is not None and first.hidden_nf in (32, 64) and not first.softmax_attention
-                      and not any(l.edge_residual for l in self.egnn))
+        self.reuse = self._first_layer_reusable() and not any(l.edge_residual for l in self.egnn)
         self.graphnorm = any(getattr(l, 'graphnorm', False) for l in self.egnn)
         # a graphnorm model at the padded shape: the statistics over the node_ptr[batch_size] real rows, read on the device
         self._gn_padded = self.padded_graphnorm and self.graphnorm and self.reuse
@@ -591,7 +619,8 @@ class LibraryScreen(_ReceptorSideScreen):
         if self.struck and not self.reuse:
             raise ValueError(
                 'LibraryScreen(struck=True): struck slots are built for the step of the first-layer reuse, which this '
-                'model does not have (softmax attention, edge_residual or a hidden size other than 32 / 64); mask it '
+                'model does not have (softmax attention without softmax_reuse=True, edge_residual or a hidden size other '
+                'than 32 / 64); mask it '
                 'one complex at a time with pointvs_amd.attribution.bond_masking / atom_masking')
         self.l_cap = self.b * self.max_lig_atoms
         self.n_cap = self.l_cap + self.b * self.n_rec
@@ -617,8 +646,8 @@ class LibraryScreen(_ReceptorSideScreen):
             if not self.reuse:
                 raise NotImplementedError(
                     f'LibraryScreen(contact_attention={contact_attention}): the contact-attention reduction runs in '
-                    'the step of the first-layer reuse, which this model does not have (softmax attention, '
-                    'edge_residual or a hidden size other than 32 / 64 take the plain forward)')
+                    'the step of the first-layer reuse, which this model does not have (softmax attention without '
+                    'softmax_reuse=True, edge_residual or a hidden size other than 32 / 64 take the plain forward)')
             self.contact = self._value_buffers('lig_att', 'slot_rec_att')
         if self._cam_plan is not None:
             self.cam = self._value_buffers('lig_val', 'slot_rec_val', node_width=sum(self._cam_plan[1]))
@@ -800,7 +829,7 @@ class LibraryScreen(_ReceptorSideScreen):
         dev, n_cap = self.lig_pos.device, self.n_cap
         i32 = dict(dtype=torch.int32, device=dev)
         f32 = dict(dtype=torch.float32, device=dev)
-        hid = self.egnn[0].hidden_nf
+        hid = self.rec_magg.shape[1]      # (the hidden size; under softmax_reuse the base rows' H + 4)
         f = _csr_buffers(
             dev, n_cap, cap_l, cap,
             state=torch.empty((lib.pvs_screen_graph_struck_state_bytes if self.struck else
@@ -960,8 +989,8 @@ class LibraryScreen(_ReceptorSideScreen):
         """Captures one whole step (builder + layer stack + head) in a hipGraph; `replay(slots)` then serves every
         batch of a library, whatever its composition."""
         if not self.reuse:
-            raise RuntimeError('capture needs the first-layer reuse (no edge_residual, no softmax attention, '
-                               'hidden size 32 or 64)')
+            raise RuntimeError('capture needs the first-layer reuse (no edge_residual, no softmax attention - or '
+                               'softmax_reuse=True -, hidden size 32 or 64)')
         if self.graphnorm and not self._gn_padded:
             raise RuntimeError('a graphnorm model normalises over the batch\'s nodes and runs at the exact node '
                                'count: it cannot be captured at the padded shape; call the screen eagerly')
@@ -1057,12 +1086,15 @@ class ScreeningSweep:
     `receptor_hotspots(best_poses(ligands))` says which receptor atoms the hits bind to: one layer's edge attention
     reduced per atom inside the screening step and averaged over the hits on the device - or, with attribution='cam',
     the class-activation map (the heads applied to every atom's final embedding), which needs no attention layer.
+    softmax_reuse (opt-in, default False): handed to every screen the sweep creates (LibraryScreen's docstring): models
+    with edge attention under softmax_attention then take the captured routes and the attribution methods above.
     """
 
     def __init__(self, model, rec_pos, rec_feats, edge_radius, batch_size=32, intra_radius=None, capture=True,
-                 receptor_name='receptor', tasks=None, padded_graphnorm=False):
+                 receptor_name='receptor', tasks=None, padded_graphnorm=False, softmax_reuse=False):
         self.model, self.rec_pos, self.rec_feats = model, rec_pos, rec_feats
         self.padded_graphnorm = bool(padded_graphnorm)      # handed to every LibraryScreen of the sweep
+        self.softmax_reuse = bool(softmax_reuse)            # handed to every screen of the sweep
         self.tasks = _resolve_tasks(model, tasks)
         self.hits = {}
         self.atom_masking_raw = {}     # ligand_atom_masking: {name: raw rows [n + 1, C], whole ligand first}
@@ -1087,7 +1119,7 @@ class ScreeningSweep:
         if screen is None:
             feats = torch.cat([lig_feats.to(self.rec_feats.device), self.rec_feats], 0)
             screen = ReceptorScreen(self.model, self.rec_pos, feats, n_lig, self.b, self.edge_radius, self.intra_radius,
-                                    tasks=self.tasks)
+                                    tasks=self.tasks, softmax_reuse=self.softmax_reuse)
             if self.capture and screen.fast_graph:
                 screen.capture(example_poses)
             self.buckets[n_lig] = screen
@@ -1186,7 +1218,7 @@ class ScreeningSweep:
                 or (type(screen.cam_request), screen.cam_request) != (type(cam), cam)):      # (True is not column 1)
             screen = LibraryScreen(self.model, self.rec_pos, self.rec_feats, self.b, max_atoms, self.edge_radius,
                                    self.intra_radius, tasks=self.tasks, contact_attention=layer, cam=cam, struck=struck,
-                                   padded_graphnorm=self.padded_graphnorm)
+                                   padded_graphnorm=self.padded_graphnorm, softmax_reuse=self.softmax_reuse)
             setattr(self, which, screen)
         return screen
 
