@@ -925,6 +925,10 @@ int pvs_profile_read(const char* kernel, double* total_ms, int64_t* launches);
  * the group, *launches = how many were recorded (bench.py: the launches of one step do different amounts of work - the
  * last layer's backward has no coordinate branch - and the line states the full-work average beside the overall one). */
 int pvs_profile_read_each(const char* kernel, double* ms, int64_t cap, int64_t* launches);
+/* Which edge-backward pair the last pvs_egnn_layer_bwd of the process launched (a layer of pvs_egnn_stack_bwd counts as
+ * one): -1 none yet, 0 the general pair, 1 the first-layer pair (g_x == NULL on a plain H = 32 layer with a coordinate
+ * update; PVS_EGNN_FIRST_LAYER_BWD=0 turns it off). For tests that must know which of two bit-identical routes ran. */
+int pvs_edge_bwd_last_variant(void);
 
 #ifdef __cplusplus
 }

@@ -127,6 +127,24 @@ inline PvsEdgeResidual pvs_edge_residual_kind(uint32_t flags, bool has_m_prev) {
     return (flags & PVS_GATED_RESIDUAL) ? PVS_ERES_GATED : PVS_ERES_SUM;
 }
 
+// ---- first-layer backward --------------------------------------------------------------------------------------------
+// A backward call whose caller asks no gradient of the layer's INPUT coordinates (g_x == NULL: the first layer of a model
+// whose positions need no gradient - training, scoring, the benchmark) takes the first-layer pair: an edge backward that
+// forms no per-edge coordinate gradient and leaves one word per edge (rho | type) instead of the 16-byte record
+// (edge_bwd_f16.hip: k_edge_bwd_f16_nogx), and a column gather that reads that word alone (edge_v0.hip:
+// k_node_gather_rho). The pair exists for the BASELINE instantiation of the H = 32 split family only: no edge residual, no
+// edge attention, coordinates updated with a live g_x_out. Every other call runs the general pair.
+//   PVS_EGNN_FIRST_LAYER_BWD=0   the general pair everywhere (A/B, and the tests' reference run; read at every call)
+// n_attr <= 3 is what the split family's backward holds (pvs_edge_family); it is restated because the gather variant sums
+// three classes.
+inline bool pvs_first_layer_bwd(int H, uint32_t flags, int n_attr, bool has_m_prev, bool has_g_x_out, bool wants_g_x) {
+    const char* sw = getenv("PVS_EGNN_FIRST_LAYER_BWD");
+    if (sw && sw[0] == '0') return false;
+    if (wants_g_x || !has_g_x_out || !(flags & PVS_UPDATE_COORDS)) return false;
+    if (H != 32 || n_attr > 3 || pvs_edge_family(H, flags, n_attr, PVS_EDGE_BWD) != PVS_EDGE_SPLIT) return false;
+    return !(flags & PVS_EDGE_ATTENTION) && pvs_edge_residual_kind(flags, has_m_prev) == PVS_ERES_NONE;
+}
+
 // ---- run-time (kind, switch) -> template arguments -------------------------------------------------------------------
 // Calls f(std::integral_constant<int, K>{}, std::bool_constant<B>{}) for kind == K in [0, NK) and b == B and returns its
 // result: exactly NK x 2 instantiations of what f launches.

@@ -48,8 +48,9 @@ struct PvsEdgeBwdIO {
     const float* g_m_out;  // [E,H] sorted or NULL
     float* gPQ;            // [N,2H]: row part written here (col part by the col gather)
     float* gz1;            // [E,H] sorted: grad wrt the first edge-MLP pre-activation
-    float* gd;             // [E,4] sorted: grad wrt (x_row - x_col), and rho in .w
-    float* gx_row;         // [N,3] row-side coordinate gradient
+    float* gd;             // [E,4] sorted: grad wrt (x_row - x_col), and rho | type in .w; first-layer form: [E] words rho | type
+    float* gx_row;         // [N,3] row-side coordinate gradient; NULL: the first-layer form (pvs_first_layer_bwd, H = 32 split
+                           // family only: nobody reads the input coordinates' gradient, the kernel forms none)
     float* g_m_prev;       // [E,H] sorted or NULL
     float* slabs;          // [blocks][slab_floats] per-block weight-gradient partials
     float* wpair;          // [2][H][H] scratch (H = 128: coord_mlp.0's weight and its transpose, staged per launch) or NULL
@@ -114,7 +115,8 @@ int pvs_launch_edge_fwd_v0(hipStream_t s, int H, const PvsGraph& g, const PvsEdg
 int pvs_launch_edge_bwd_v0(hipStream_t s, int H, const PvsGraph& g, const PvsEdgeW& w, uint32_t flags,
                            int att_act, const PvsEdgeBwdIO& io, int* n_slabs);
 // Column-side gather (see k_node_gather); with wsums also the g_wrho/g_wattr partial slabs
-// ([n_slabs][4H]: wrho, wattr0..2) that the MFMA backward leaves to this kernel.
+// ([n_slabs][4H]: wrho, wattr0..2) that the MFMA backward leaves to this kernel. gx_row == NULL: the first-layer form
+// (H = 32 with wsums, g_x == NULL): gd4 holds one rho | type word per edge, no coordinate sum is formed.
 int pvs_node_gather_blocks(int N);
 int pvs_launch_node_gather(hipStream_t s, int H, const PvsGraph& g, bool wsums, const float* gz1,
                            const float* gd4, const float* gx_row, const float* g_x_out, float* gPQ,

@@ -318,7 +318,9 @@ __device__ __forceinline__ int pvs_tile_quad_off(int row, int quad) {      // fl
     return row * H + 4 * (quad ^ (row & (H / 4 - 1)));
 }
 
-template <int HB, bool WSUM = false, bool ROWS = true, bool SWZ = false, class Flush, class RowStore>
+// XSUM = false (the first-layer backward: nobody reads the input coordinates' gradient): tx is not read and accx stays as
+// it is.
+template <int HB, bool WSUM = false, bool ROWS = true, bool SWZ = false, bool XSUM = true, class Flush, class RowStore>
 __device__ __forceinline__ void reduce_rows_tile(const float* __restrict__ T, const float* __restrict__ tx,
                                                  const int* __restrict__ rowbuf, unsigned bmask, int lane,
                                                  float4& acc, float4& accx, int& cur_row, Flush&& flush,
@@ -333,7 +335,7 @@ __device__ __forceinline__ void reduce_rows_tile(const float* __restrict__ T, co
         const int rl = k * RPI + rsub;
         if constexpr (ROWS) v[k] = *reinterpret_cast<const float4*>(T + (SWZ ? pvs_tile_quad_off<HB>(rl, quad) : rl * TS + 4 * quad));      // (!ROWS: only the
         else v[k] = make_float4(0.f, 0.f, 0.f, 0.f);                        // per-edge float4 of tx is reduced)
-        dx[k] = *reinterpret_cast<const float4*>(tx + rl * 4);
+        if constexpr (XSUM) dx[k] = *reinterpret_cast<const float4*>(tx + rl * 4);
         store_row(rl, quad, v[k]);
         const unsigned upto = rl == 31 ? 0xffffffffu : ((2u << rl) - 1u);
         seg[k] = __popc(bmask & upto);
@@ -348,7 +350,10 @@ __device__ __forceinline__ void reduce_rows_tile(const float* __restrict__ T, co
     };
     if (bmask == 0u) {
 #pragma unroll
-        for (int k = 0; k < NK; ++k) { add4(acc, v[k]); add4(accx, dx[k]); }
+        for (int k = 0; k < NK; ++k) {
+            add4(acc, v[k]);
+            if constexpr (XSUM) add4(accx, dx[k]);
+        }
         return;
     }
     unsigned bm = bmask;
@@ -358,9 +363,11 @@ __device__ __forceinline__ void reduce_rows_tile(const float* __restrict__ T, co
             const float m = seg[k] == s ? 1.f : 0.f;
             acc.x = fmaf(m, v[k].x, acc.x); acc.y = fmaf(m, v[k].y, acc.y);
             acc.z = fmaf(m, v[k].z, acc.z); acc.w = fmaf(m, v[k].w, acc.w);
-            accx.x = fmaf(m, dx[k].x, accx.x); accx.y = fmaf(m, dx[k].y, accx.y);
-            accx.z = fmaf(m, dx[k].z, accx.z);
-            if constexpr (WSUM) accx.w = fmaf(m, dx[k].w, accx.w);   // (softmax: the weights' sum)
+            if constexpr (XSUM) {
+                accx.x = fmaf(m, dx[k].x, accx.x); accx.y = fmaf(m, dx[k].y, accx.y);
+                accx.z = fmaf(m, dx[k].z, accx.z);
+                if constexpr (WSUM) accx.w = fmaf(m, dx[k].w, accx.w);   // (softmax: the weights' sum)
+            }
         }
         if (bm == 0u) break;            // the last segment stays open (carried to the next tile)
         flush(cur_row);

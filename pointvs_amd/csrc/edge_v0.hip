@@ -425,13 +425,18 @@ k_edge_bwd_v0(PvsGraph g, PvsEdgeW w, uint32_t flags, int att_act, PvsEdgeBwdIO 
 // slabs [4H] - the MFMA edge backward leaves those to this memory-bound kernel, whose VALU is idle.
 // Lane = (edge slot, 16-byte quad): one wave-instruction fetches 64/(H/4) whole rows; UN independent
 // batches in flight. Fixed order everywhere: bitwise reproducible.
+// RHO (the first-layer backward, pvs_first_layer_bwd: nobody reads the input coordinates' gradient): the per-edge record
+// is ONE word, rho | type, at gd4[e] (k_edge_bwd_f16_nogx wrote it); no coordinate sum, gx_row / g_x_out / g_x untouched.
+// The rows, the loop, the column map and every summation order are the general form's: gPQ and the weight sums come out
+// with the same bits. The body is shared; the kernels below are named wrappers, so that the general kernels keep their
+// symbols - and their code: PvsGraph comes BY VALUE (by reference the general instantiations compile to other
+// instructions, tools/device_code_diff.py), and the pointers carry their __restrict__ on the kernels' own arguments.
 constexpr int kNgMinBlocks = 5;   // workgroups per CU the register budget must allow: 20 waves per CU with UN = 6
-template <int H, bool WSUMS>
-__global__ void __launch_bounds__(kThreads, kNgMinBlocks)
-k_node_gather(PvsGraph g, const float* __restrict__ gz1, const float* __restrict__ gd4,
-              const float* __restrict__ gx_row, const float* __restrict__ g_x_out,
-              float* __restrict__ gPQ, float* __restrict__ g_x, float* __restrict__ slabs,
-              int n_lo, int n_hi) {
+template <int H, bool WSUMS, bool RHO>
+__device__ __forceinline__ void node_gather_columns(PvsGraph g, const float* gz1, const float* gd4, const float* gx_row,
+                                                    const float* g_x_out, float* gPQ, float* g_x, float* slabs, int n_lo,
+                                                    int n_hi) {
+    static_assert(!RHO || WSUMS, "the one-word record only feeds the weight sums");
     constexpr int QPR = H / 4;
     constexpr int EPW = 64 / QPR;
     // (8 at four waves per SIMD before round 4: the rate follows the waves in flight - five waves of six batches each:
@@ -483,8 +488,9 @@ k_node_gather(PvsGraph g, const float* __restrict__ gz1, const float* __restrict
                 const bool ok = idx[u] >= 0;
                 v[u] = ok ? *reinterpret_cast<const float4*>(gz1 + (size_t)idx[u] * H + 4 * quad)
                           : make_float4(0.f, 0.f, 0.f, 0.f);
-                d[u] = ok ? *reinterpret_cast<const float4*>(gd4 + (size_t)idx[u] * 4)
-                          : make_float4(0.f, 0.f, 0.f, 0.f);
+                if constexpr (RHO) d[u] = make_float4(0.f, 0.f, 0.f, ok ? gd4[idx[u]] : 0.f);
+                else d[u] = ok ? *reinterpret_cast<const float4*>(gd4 + (size_t)idx[u] * 4)
+                               : make_float4(0.f, 0.f, 0.f, 0.f);
                 ty[u] = -1;
                 if (WSUMS) {
                     int tt;
@@ -495,7 +501,7 @@ k_node_gather(PvsGraph g, const float* __restrict__ gz1, const float* __restrict
 #pragma unroll
             for (int u = 0; u < UN; ++u) {
                 add4(accc, v[u]);
-                axc += quad == 0 ? d[u].x : (quad == 1 ? d[u].y : (quad == 2 ? d[u].z : 0.f));
+                if constexpr (!RHO) axc += quad == 0 ? d[u].x : (quad == 1 ? d[u].y : (quad == 2 ? d[u].z : 0.f));
                 if (WSUMS) {
                     fma4(wrho, v[u], d[u].w);
                     fma4(wat0, v[u], ty[u] == 0 ? 1.f : 0.f);
@@ -508,11 +514,11 @@ k_node_gather(PvsGraph g, const float* __restrict__ gz1, const float* __restrict
         for (int o = QPR; o < 64; o <<= 1) {
             accc.x += __shfl_xor(accc.x, o, 64); accc.y += __shfl_xor(accc.y, o, 64);
             accc.z += __shfl_xor(accc.z, o, 64); accc.w += __shfl_xor(accc.w, o, 64);
-            axc += __shfl_xor(axc, o, 64);
+            if constexpr (!RHO) axc += __shfl_xor(axc, o, 64);
         }
         if (sub == 0) {
             *reinterpret_cast<float4*>(gPQ + (size_t)n * 2 * H + H + 4 * quad) = accc;
-            if (g_x && quad < 3) {
+            if (!RHO && g_x && quad < 3) {
                 const float base = g_x_out ? g_x_out[3 * n + quad] : 0.f;
                 g_x[3 * n + quad] = base + gx_row[3 * n + quad] - axc;
             }
@@ -541,6 +547,22 @@ k_node_gather(PvsGraph g, const float* __restrict__ gz1, const float* __restrict
             slabs[(size_t)blockIdx.x * 4 * H + i] = t;
         }
     }
+}
+
+template <int H, bool WSUMS>
+__global__ void __launch_bounds__(kThreads, kNgMinBlocks)
+k_node_gather(PvsGraph g, const float* __restrict__ gz1, const float* __restrict__ gd4,
+              const float* __restrict__ gx_row, const float* __restrict__ g_x_out,
+              float* __restrict__ gPQ, float* __restrict__ g_x, float* __restrict__ slabs,
+              int n_lo, int n_hi) {
+    node_gather_columns<H, WSUMS, false>(g, gz1, gd4, gx_row, g_x_out, gPQ, g_x, slabs, n_lo, n_hi);
+}
+
+// The first-layer form: H = 32 with the weight sums (its own name, as k_edge_bwd_f16_nogx has)
+__global__ void __launch_bounds__(kThreads, kNgMinBlocks)
+k_node_gather_rho(PvsGraph g, const float* __restrict__ gz1, const float* __restrict__ rho_type,
+                  float* __restrict__ gPQ, float* __restrict__ slabs, int n_lo, int n_hi) {
+    node_gather_columns<32, true, true>(g, gz1, rho_type, nullptr, nullptr, gPQ, nullptr, slabs, n_lo, n_hi);
 }
 
 template <typename K>
@@ -630,6 +652,12 @@ int pvs_launch_node_gather(hipStream_t s, int H, const PvsGraph& g, bool wsums, 
     const int blocks = wsums ? pvs_node_gather_blocks(n_hi - n_lo) : pvs_edge_v0_blocks(n_hi - n_lo);
     *n_slabs = wsums ? blocks : 0;
     PvsProfScope prof(s, PVS_PROF_COL_GATHER);
+    if (!gx_row) {       // the first-layer form (pvs_first_layer_bwd): gd4 holds one word per edge
+        PVS_REQUIRE(H == 32 && wsums && !g_x, "column gather: the first-layer form is built for H = 32 with the weight sums");
+        k_node_gather_rho<<<blocks, kThreads, 0, s>>>(g, gz1, gd4, gPQ, slabs, n_lo, n_hi);
+        PVS_CHECK_LAUNCH();
+        return 0;
+    }
     if (H == 128) {      // (the wide layer: only the column gather of this file is built at 128 channels)
         if (wsums)
             k_node_gather<128, true><<<blocks, kThreads, 0, s>>>(g, gz1, gd4, gx_row, g_x_out, gPQ, g_x, slabs, n_lo, n_hi);

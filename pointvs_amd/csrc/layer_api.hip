@@ -694,6 +694,12 @@ extern "C" int pvs_egnn_layer_bwd(const PvsLayerDesc* d, const PvsGraph* g, cons
     const bool split_small = getenv("PVS_EGNN_SPLIT_SMALL") != nullptr;     // (the launches apart, for A/B)
     const PvsEdgeFamily fam = pvs_edge_family(H, F, m.A, PVS_EDGE_BWD);
     const bool mfma_bwd = fam != PVS_EDGE_GENERIC;
+    // Nobody asks for the gradient of this layer's input coordinates (the first layer of a model, whichever entry point
+    // the call came through): the first-layer pair, which neither forms nor sums it (edge_dispatch.h). gx_row == NULL is
+    // how the two launchers are told.
+    const bool first_layer = pvs_first_layer_bwd(H, F, m.A, m_prev != nullptr, g_x_out != nullptr, g_x != nullptr);
+    float* const gx_row = first_layer ? nullptr : w.gx_row;
+    pvs_note_edge_bwd_variant(first_layer ? PVS_EDGE_BWD_FIRST_LAYER : PVS_EDGE_BWD_GENERAL);
     // Layers without GraphNorm and without rezero / gated residual: the output stage (node gate, residual), g_y1 and
     // [g_h | gM] as ONE launch that also carries the per-node preparation of the edge backward (dense_ops.hip:
     // k_node_mlp_bwd). Without a node gate g_o is g_h_out itself and nothing is written for it.
@@ -706,7 +712,7 @@ extern "C" int pvs_egnn_layer_bwd(const PvsLayerDesc* d, const PvsGraph* g, cons
         PVS_TRY(pvs_node_out_bwd(s, H, g_h_out, so, h, nw, F, d->att_act, N, w.g_o, g_h, w.gl, w.t1,
                                  w.tg));
     PvsLinearExt prep;
-    if (mfma_bwd) { prep.zero_rows = w.gPQ; prep.zero_w = H; prep.zero_ld = 2 * H; prep.zero3 = w.gx_row; }
+    if (mfma_bwd) { prep.zero_rows = w.gPQ; prep.zero_w = H; prep.zero_ld = 2 * H; prep.zero3 = gx_row; }
     if (coord_bwd) { prep.scale3_src = g_x_out; prep.scale3_by = g->inv_deg; prep.scale3_dst = w.gxagg; }
     if (chain_bwd)
         PVS_TRY(pvs_launch_node_mlp_bwd(s, H, N, g_h_out, so, sy1, p->node_w1, p->node_w2, (F & PVS_RESIDUAL) != 0,
@@ -797,19 +803,19 @@ extern "C" int pvs_egnn_layer_bwd(const PvsLayerDesc* d, const PvsGraph* g, cons
     else
         PVS_TRY(pvs_prep_edge_bwd(s, g_x_out, g->inv_deg, Magg, w.gM, N, H,
                                   coord_bwd ? w.gxagg : nullptr, (eatt && soft) ? w.softD : nullptr,
-                                  mfma_bwd ? w.gPQ : nullptr, mfma_bwd ? w.gx_row : nullptr));
+                                  mfma_bwd ? w.gPQ : nullptr, mfma_bwd ? gx_row : nullptr));
     PvsEdgeBwdIO io;
     io.PQ = sPQ; io.x = x; io.m_prev = m_prev; io.att = att; io.gM = w.gM;
     io.gxagg = coord_bwd ? w.gxagg : nullptr;
     io.softD = (eatt && soft) ? w.softD : nullptr;
-    io.g_m_out = g_m_out; io.gPQ = w.gPQ; io.gz1 = w.gz1; io.gd = w.gd; io.gx_row = w.gx_row;
+    io.g_m_out = g_m_out; io.gPQ = w.gPQ; io.gz1 = w.gz1; io.gd = w.gd; io.gx_row = gx_row;
     io.g_m_prev = eres ? g_m_prev : nullptr; io.slabs = w.eslabs; io.wpair = w.wpair;
     int n_slabs = 0;
     const PvsSlabLayout L = pvs_slab_layout(H);
     int n_nslabs = 0;
     if (mfma_bwd) {
         PVS_TRY(pvs_launch_edge_bwd_mfma(s, H, fam, *g, ew, F, d->att_act, io, 0, m.E, &n_slabs));
-        PVS_TRY(pvs_launch_node_gather(s, H, *g, true, w.gz1, w.gd, w.gx_row, g_x_out, w.gPQ, g_x,
+        PVS_TRY(pvs_launch_node_gather(s, H, *g, true, w.gz1, w.gd, gx_row, g_x_out, w.gPQ, g_x,
                                        w.nslabs, 0, N, &n_nslabs));
     } else {
         PVS_TRY(pvs_launch_edge_bwd_v0(s, H, *g, ew, F, d->att_act, io, &n_slabs));

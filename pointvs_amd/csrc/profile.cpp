@@ -1,3 +1,4 @@
+#include <atomic>
 #include <mutex>
 #include <string.h>
 #include <vector>
@@ -17,7 +18,11 @@ const char* kNames[PVS_PROF_COUNT] = {"edge_fwd", "edge_bwd", "col_gather", "gra
                                       "node_mlp_fwd", "node_mlp_bwd", "node_out_fwd", "node_out_bwd", "node_tail",
                                       "node_wgrads", "colreduce4_rows", "colreduce_rows", "node_tail_rows"};
 thread_local int t_fwd_tag = PVS_PROF_EDGE_FWD;
+std::atomic<int> g_edge_bwd_variant{PVS_EDGE_BWD_NONE};
 }  // namespace
+
+void pvs_note_edge_bwd_variant(int variant) { g_edge_bwd_variant.store(variant, std::memory_order_relaxed); }
+extern "C" int pvs_edge_bwd_last_variant(void) { return g_edge_bwd_variant.load(std::memory_order_relaxed); }
 
 void pvs_prof_set_fwd_tag(int id) { t_fwd_tag = id; }
 int pvs_prof_fwd_tag() { return t_fwd_tag; }

@@ -27,6 +27,10 @@ static_assert(PVS_PROF_COUNT + 1 <= 32, "the profile mask is an unsigned with bi
 void pvs_prof_set_fwd_tag(int id);
 int pvs_prof_fwd_tag();
 
+// which edge-backward pair the last pvs_egnn_layer_bwd of the process launched (pvs_edge_bwd_last_variant, pvs_egnn.h)
+enum { PVS_EDGE_BWD_NONE = -1, PVS_EDGE_BWD_GENERAL = 0, PVS_EDGE_BWD_FIRST_LAYER = 1 };
+void pvs_note_edge_bwd_variant(int variant);
+
 struct PvsProfScope {
     hipStream_t s;
     void* rec;
