@@ -73,8 +73,10 @@ typedef struct PvsGraph {
     const int32_t* cedge;    /* [E]   sorted positions of the edges grouped by col (stable)     */
     const float*   inv_deg;  /* [N]   1 / max(deg_row, 1)  (unsorted_segment_mean's clamp)      */
     /* Optional DEVICE int32: the true edge count when it is only known on the device (a graph made
-     * by pvs_graph_filter_ligand_edges); n_edges is then the capacity of the edge arrays. Only
-     * pvs_egnn_layer_edge_sums / _fwd_partial accept such a graph. */
+     * by pvs_graph_filter_ligand_edges); n_edges is then the capacity of the edge arrays. Forward only:
+     * pvs_egnn_layer_fwd (and pvs_egnn_stack_fwd through it) on the MFMA edge kernel with m_out == NULL, and
+     * pvs_egnn_layer_edge_sums / _edge_stats_softmax / _fwd_partial / _fwd_partial_att / _fwd_partial_softmax
+     * accept such a graph. */
     const int32_t* n_edges_dev;
     /* Optional DEVICE int32 [n_graphs + 1]: first sorted edge of every graph of the batch (graphs are
      * contiguous node ranges, so contiguous edge ranges of the CSR), last entry = E; NULL / 0 when unknown.
@@ -261,6 +263,10 @@ int pvs_rows_to_sorted_order(const float* src, float* dst, const int32_t* perm, 
  *   caller's business), m_out [E,H] sorted or NULL (skip materialising edge_feat),
  *   att_out [E] sorted (required when PVS_EDGE_ATTENTION: also consumed by the backward),
  *   node_att_out [N] or NULL, saved: pvs_egnn_layer_saved_floats() floats kept for the backward.
+ * pvs_egnn_layer_workspace_bytes(desc, N, E, backward): 0 for pvs_egnn_layer_fwd, 1 for pvs_egnn_layer_bwd, 2 and 3 for
+ * the first-layer reuse below: 2 is the forward's workspace plus a per-edge attention array (pvs_egnn_layer_edge_sums /
+ * _fwd_partial / _fwd_partial_att), 3 is mode 2 plus the per-row factor array [N] (_edge_stats_softmax /
+ * _fwd_partial_softmax).
  */
 size_t pvs_egnn_layer_saved_floats(const PvsLayerDesc* desc, int32_t n_nodes, int32_t n_edges);
 size_t pvs_egnn_layer_workspace_bytes(const PvsLayerDesc* desc, int32_t n_nodes, int32_t n_edges,

@@ -4,7 +4,7 @@
 #include "edge_dispatch.h"
 
 // Internal flag beside the PVS_* layer flags: the forward writes the raw coordinate sums (no x, no 1/deg) into x_out
-// (pvs_egnn_layer_edge_sums / _fwd_partial)
+// (pvs_egnn_layer_edge_sums / _edge_stats_softmax / _fwd_partial / _fwd_partial_att / _fwd_partial_softmax)
 constexpr uint32_t kFwdRawXsum = 1u << 23;
 
 // Pointers the edge kernels need, by value in the kernel arguments.

@@ -59,8 +59,9 @@ int check_desc(const PvsLayerDesc* d, const PvsGraph* g, const PvsLayerParams* p
     PVS_REQUIRE(!((d->flags & PVS_GATED_RESIDUAL) && (d->flags & PVS_REZERO)),
                 "gated_residual and rezero are incompatible");
     PVS_REQUIRE(g->n_nodes > 0 && g->n_edges >= 0, "bad graph sizes");
-    PVS_REQUIRE(allow_dev_count || !g->n_edges_dev, "a graph with a device-side edge count is only accepted by "
-                "pvs_egnn_layer_edge_sums / pvs_egnn_layer_fwd_partial");
+    PVS_REQUIRE(allow_dev_count || !g->n_edges_dev, "a graph with a device-side edge count is forward-only: accepted by "
+                "pvs_egnn_layer_fwd (MFMA edge kernel, m_out = NULL) and by pvs_egnn_layer_edge_sums / _edge_stats_softmax / "
+                "_fwd_partial / _fwd_partial_att / _fwd_partial_softmax");
     PVS_REQUIRE(d->n_edge_attr == 0 || g->etype, "graph has no edge types but layer expects %d",
                 d->n_edge_attr);
     PVS_REQUIRE(p->edge_w1 && p->edge_b1 && p->edge_w2 && p->edge_b2 && p->node_w1 && p->node_b1 &&
@@ -96,6 +97,28 @@ size_t carve_fwd(PvsArena& a, const Dims& m, FwdWs* w) {
     t.m_scratch = a.take<float>(m.H > 64 ? (size_t)(m.E > 0 ? m.E : 1) * m.H : 4);
     if (w) *w = t;
     return a.off;
+}
+
+// The first-layer reuse (the partial-layer entries below) in its two kinds: sums of the sigmoid / plain messages that add
+// over two edge sets, or softmax statistics that merge (soft = true).
+// Their workspace: the forward's, the edges' attention when the caller keeps none and, for softmax, the rows' factors.
+struct PartialWs {
+    FwdWs w;
+    float *att, *fac;      // [max(E, 1)] | [N] (soft only)
+};
+
+void carve_partial(PvsArena& a, const Dims& m, bool soft, PartialWs* t) {
+    carve_fwd(a, m, &t->w);
+    t->att = a.take<float>((size_t)(m.E > 0 ? m.E : 1));
+    t->fac = soft ? a.take<float>((size_t)m.N) : nullptr;
+}
+
+// Modes 2 and 3 of pvs_egnn_layer_workspace_bytes: never less than carve_partial needs, but not its dry run - the arena
+// aligns in front of a take, these sizes round att and fac up behind them and add slack, and callers hold such buffers.
+size_t partial_workspace_bytes(const Dims& m, bool soft) {
+    PvsArena a(nullptr, 0);
+    return carve_fwd(a, m, nullptr) + pvs_align_up((size_t)(m.E > 0 ? m.E : 1) * sizeof(float), 256) +
+           (soft ? pvs_align_up((size_t)(m.N > 0 ? m.N : 1) * sizeof(float), 256) : 0) + 512;
 }
 
 // What a layer's forward keeps for its backward in the caller's `saved` buffer: the node-level forward (N rows: small)
@@ -310,12 +333,9 @@ extern "C" size_t pvs_egnn_layer_workspace_bytes(const PvsLayerDesc* d, int32_t 
     PvsGraph g{};
     g.n_nodes = N; g.n_edges = E;
     Dims m = make_dims(d, &g);
+    // 2: pvs_egnn_layer_edge_sums / _fwd_partial / _fwd_partial_att; 3: _edge_stats_softmax / _fwd_partial_softmax
+    if (backward == 2 || backward == 3) return partial_workspace_bytes(m, backward == 3);
     PvsArena a(nullptr, 0);
-    if (backward == 2)   // pvs_egnn_layer_edge_sums / _fwd_partial: forward + a per-edge attention scratch
-        return carve_fwd(a, m, nullptr) + pvs_align_up((size_t)(E > 0 ? E : 1) * sizeof(float), 256) + 512;
-    if (backward == 3)   // pvs_egnn_layer_edge_stats_softmax / _fwd_partial_softmax: mode 2 + the rows' attention factors
-        return carve_fwd(a, m, nullptr) + pvs_align_up((size_t)(E > 0 ? E : 1) * sizeof(float), 256) +
-               pvs_align_up((size_t)(N > 0 ? N : 1) * sizeof(float), 256) + 512;
     return (backward ? carve_bwd(a, m, nullptr) : carve_fwd(a, m, nullptr)) + 256;
 }
 
@@ -361,7 +381,31 @@ extern "C" int pvs_egnn_layer_fwd(const PvsLayerDesc* d, const PvsGraph* g, cons
 
 // ---- forward with part of every row's edges given as precomputed sums (screening: the
 // receptor-receptor messages of the first layer do not depend on the ligand pose) ----
+// Two kinds (soft = false / true), one host path. Sums: the rows' sums of two edge sets add; for sigmoid attention or none.
+// Softmax attention: row sums of two edge sets do not add, but the softmax statistics merge exactly. For a
+// row i and an edge set T with logits l_e: mu_T = max l_e, S_T = sum exp(l_e - mu_T), A_T = sum exp(l_e - mu_T) m_e / S_T -
+// what the softmax MFMA forward leaves in smax / ssum / Magg at every row it flushes. A BASE ROW is H + 4 floats:
+// A_b [H] | mu_b | S_b | 0 | 0; all zero: no base (S_b >= 1 for a set with an edge).
 namespace {
+
+constexpr int kBaseRowExtra = 4;      // mu, S and two zeros behind the H channels: rows stay 16-byte multiples
+
+// Row n's coordinates, by the row's first thread of both combine kernels: x_out holds the raw sums over the graph's deg_g
+// edges of the row and becomes x + (base_xsum + x_out) / max(base_deg + deg_g, 1), or x where coordinates stay
+__device__ __forceinline__ void combine_partial_coords(float* __restrict__ x_out, const float* __restrict__ x,
+                                                       const float* __restrict__ base_xsum,
+                                                       const float* __restrict__ base_deg, int deg_g, int n, int upd) {
+    if (upd) {
+        const float deg = base_deg[n] + (float)deg_g;
+        const float inv = 1.0f / (deg > 1.f ? deg : 1.f);
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+            x_out[3 * n + c] = x[3 * n + c] + (base_xsum[3 * n + c] + x_out[3 * n + c]) * inv;
+    } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) x_out[3 * n + c] = x[3 * n + c];
+    }
+}
 
 __global__ void k_combine_partial(float* __restrict__ Magg, float* __restrict__ x_out, const float* __restrict__ x,
                                   const float* __restrict__ base_magg, const float* __restrict__ base_xsum,
@@ -376,109 +420,8 @@ __global__ void k_combine_partial(float* __restrict__ Magg, float* __restrict__ 
     float4 m = *mp;
     m.x += b.x; m.y += b.y; m.z += b.z; m.w += b.w;
     *mp = m;
-    if (q == 0) {
-        if (upd) {
-            const float deg = base_deg[n] + (float)(rowptr[n + 1] - rowptr[n]);
-            const float inv = 1.0f / (deg > 1.f ? deg : 1.f);
-#pragma unroll
-            for (int c = 0; c < 3; ++c)
-                x_out[3 * n + c] = x[3 * n + c] + (base_xsum[3 * n + c] + x_out[3 * n + c]) * inv;
-        } else {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) x_out[3 * n + c] = x[3 * n + c];
-        }
-    }
+    if (q == 0) combine_partial_coords(x_out, x, base_xsum, base_deg, rowptr[n + 1] - rowptr[n], n, upd);
 }
-
-int partial_checks(const PvsLayerDesc* d, const PvsGraph* g, const PvsLayerParams* p, PvsEdgeFamily* fam) {
-    PVS_TRY(check_desc(d, g, p, true));
-    *fam = pvs_edge_family(d->hidden, d->flags, d->n_edge_attr, PVS_EDGE_FWD);
-    PVS_REQUIRE(*fam != PVS_EDGE_GENERIC,
-                "partial-sum forward needs the MFMA edge kernel (H = 32, 64 or 128)");
-    PVS_REQUIRE(!((d->flags & PVS_EDGE_ATTENTION) && (d->flags & PVS_SOFTMAX_ATT)),
-                "partial-sum forward: softmax attention is not supported (row sums of two edge sets do not add)");
-    PVS_REQUIRE(!(d->flags & PVS_EDGE_RESIDUAL), "partial-sum forward: edge_residual layers are not supported");
-    return 0;
-}
-
-}  // namespace
-
-extern "C" int pvs_egnn_layer_edge_sums(const PvsLayerDesc* d, const PvsGraph* g, const PvsLayerParams* p,
-                                        const float* h, const float* x, float* magg, float* xsum,
-                                        void* workspace, size_t workspace_bytes, pvs_stream_t stream_) {
-    hipStream_t s = (hipStream_t)stream_;
-    PvsEdgeFamily fam;
-    PVS_TRY(partial_checks(d, g, p, &fam));
-    PVS_REQUIRE(h && x && magg && xsum, "pvs_egnn_layer_edge_sums: NULL tensor");
-    const Dims m = make_dims(d, g);
-    PvsArena arena(workspace, workspace_bytes);
-    FwdWs w;
-    carve_fwd(arena, m, &w);
-    float* att = arena.take<float>((size_t)(m.E > 0 ? m.E : 1));
-    PVS_REQUIRE(arena.ok(), "pvs_egnn_layer_edge_sums: workspace too small (%zu < %zu)", workspace_bytes, arena.off);
-    const PvsEdgeW ew = make_edge_w(m, p);
-    PvsEdgeFwdIO io = make_fwd_io(w, w.PQ, x, nullptr, magg, xsum, nullptr, att);
-    PVS_TRY(node_pre_forward(s, m, p, h, w.PQ, &io, d->flags | kFwdRawXsum));
-    PVS_TRY(pvs_launch_edge_fwd_mfma(s, m.H, fam, *g, ew, d->flags | kFwdRawXsum, d->att_act, io));
-    if (!(d->flags & PVS_UPDATE_COORDS))
-        PVS_CHECK_HIP(hipMemsetAsync(xsum, 0, sizeof(float) * 3 * (size_t)m.N, s));
-    return 0;
-}
-
-extern "C" int pvs_egnn_layer_fwd_partial_att(const PvsLayerDesc* d, const PvsGraph* g, const PvsLayerParams* p,
-                                              const float* h, const float* x, const float* base_magg,
-                                              const float* base_xsum, const float* base_deg, float* h_out,
-                                              float* x_out, float* node_att_out, float* att_out, float* saved,
-                                              void* workspace, size_t workspace_bytes, pvs_stream_t stream_) {
-    hipStream_t s = (hipStream_t)stream_;
-    PvsEdgeFamily fam;
-    PVS_TRY(partial_checks(d, g, p, &fam));
-    PVS_REQUIRE(h && x && base_magg && base_xsum && base_deg && h_out && x_out && saved,
-                "pvs_egnn_layer_fwd_partial: NULL tensor");
-    PVS_REQUIRE(x_out != x, "pvs_egnn_layer_fwd_partial: x_out must not alias x");
-    const Dims m = make_dims(d, g);
-    PvsArena arena(workspace, workspace_bytes);
-    FwdWs w;
-    carve_fwd(arena, m, &w);
-    float* att = arena.take<float>((size_t)(m.E > 0 ? m.E : 1));      // (carved either way: one workspace size)
-    PVS_REQUIRE(arena.ok(), "pvs_egnn_layer_fwd_partial: workspace too small (%zu < %zu)", workspace_bytes, arena.off);
-    if (att_out) att = att_out;       // the caller keeps the layer's attention (CSR-sorted over g)
-    const int H = m.H;
-    const SavedLayout sv = saved_layout(saved, m.N, H);
-    const PvsEdgeW ew = make_edge_w(m, p);
-    const PvsNodeW nw = make_node_w(d, p);
-    PvsEdgeFwdIO io = make_fwd_io(w, sv.PQ, x, nullptr, sv.Magg, x_out, nullptr, att);
-    PVS_TRY(node_pre_forward(s, m, p, h, sv.PQ, &io, d->flags | kFwdRawXsum));
-    pvs_prof_set_fwd_tag(PVS_PROF_EDGE_FWD_PARTIAL);      // timed apart from the full-graph layers (bench.py)
-    const int rc_partial = pvs_launch_edge_fwd_mfma(s, H, fam, *g, ew, d->flags | kFwdRawXsum, d->att_act, io);
-    pvs_prof_set_fwd_tag(PVS_PROF_EDGE_FWD);
-    PVS_TRY(rc_partial);
-    const long long threads = (long long)m.N * (H / 4);
-    k_combine_partial<<<(int)((threads + 255) / 256), 256, 0, s>>>(sv.Magg, x_out, x, base_magg, base_xsum, base_deg,
-                                                                   g->rowptr, m.N, H,
-                                                                   (d->flags & PVS_UPDATE_COORDS) ? 1 : 0);
-    PVS_CHECK_LAUNCH();
-    PVS_TRY(node_mlp_forward(s, m, d, p, nw, h, sv.Magg, sv.y1, sv.u, sv.o, sv.stats, true, w.shift, w.slabs, h_out,
-                             node_att_out, g->n_norm_rows_dev));
-    return 0;
-}
-
-extern "C" int pvs_egnn_layer_fwd_partial(const PvsLayerDesc* d, const PvsGraph* g, const PvsLayerParams* p,
-                                          const float* h, const float* x, const float* base_magg,
-                                          const float* base_xsum, const float* base_deg, float* h_out,
-                                          float* x_out, float* node_att_out, float* saved, void* workspace,
-                                          size_t workspace_bytes, pvs_stream_t stream_) {
-    return pvs_egnn_layer_fwd_partial_att(d, g, p, h, x, base_magg, base_xsum, base_deg, h_out, x_out, node_att_out,
-                                          nullptr, saved, workspace, workspace_bytes, stream_);
-}
-
-// ---- the same for softmax attention: the softmax statistics of two edge sets merge exactly ----
-// For a row i and an edge set T with logits l_e: mu_T = max l_e, S_T = sum exp(l_e - mu_T), A_T = sum exp(l_e - mu_T) m_e
-// / S_T - what the softmax MFMA forward leaves in smax / ssum / Magg at every row it flushes. A BASE ROW is H + 4 floats:
-// A_b [H] | mu_b | S_b | 0 | 0; all zero: no base (S_b >= 1 for a set with an edge).
-namespace {
-
-constexpr int kBaseRowExtra = 4;      // mu, S and two zeros behind the H channels: rows stay 16-byte multiples
 
 // Magg / smax / ssum of the base launch -> base rows; rows without an edge (never flushed: their statistics are whatever
 // the workspace held) are decided from the degree and written as zeros
@@ -535,16 +478,7 @@ __global__ void k_combine_partial_softmax(float* __restrict__ Magg, float* __res
     *mp = m;
     if (q == 0) {
         fac[n] = wg;
-        if (upd) {
-            const float deg = base_deg[n] + (float)deg_g;
-            const float inv = 1.0f / (deg > 1.f ? deg : 1.f);
-#pragma unroll
-            for (int c = 0; c < 3; ++c)
-                x_out[3 * n + c] = x[3 * n + c] + (base_xsum[3 * n + c] + x_out[3 * n + c]) * inv;
-        } else {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) x_out[3 * n + c] = x[3 * n + c];
-        }
+        combine_partial_coords(x_out, x, base_xsum, base_deg, deg_g, n, upd);
     }
 }
 
@@ -556,57 +490,135 @@ __global__ void k_scale_att_rows(PvsGraph g, const float* __restrict__ fac, floa
     att[e] *= fac[g.row[e]];
 }
 
-int softmax_partial_checks(const PvsLayerDesc* d, const PvsGraph* g, const PvsLayerParams* p, PvsEdgeFamily* fam) {
+struct PartialCall {      // what an accepted call works with
+    Dims m;
+    PvsEdgeFamily fam;
+    PartialWs ws;
+};
+
+// Every refusal of the five entries, in the order they have always come and all before the first HIP call: the layer and
+// its kind, then the entry's own arguments (tensors: none of them NULL; x_out: NULL for an entry without one; base_rows:
+// looked at for soft only), then the workspace. `entry`: the name the messages carry.
+int partial_checks(bool soft, const char* entry, const PvsLayerDesc* d, const PvsGraph* g, const PvsLayerParams* p,
+                   bool tensors, const float* x, const float* x_out, const float* base_rows, void* workspace,
+                   size_t workspace_bytes, PartialCall* c) {
+    const char* what = soft ? "softmax partial forward" : "partial-sum forward";
     PVS_TRY(check_desc(d, g, p, true));
-    *fam = pvs_edge_family(d->hidden, d->flags, d->n_edge_attr, PVS_EDGE_FWD);
-    PVS_REQUIRE(*fam != PVS_EDGE_GENERIC,
-                "softmax partial forward needs the MFMA edge kernel (H = 32, 64 or 128)");
-    PVS_REQUIRE((d->flags & PVS_EDGE_ATTENTION) && (d->flags & PVS_SOFTMAX_ATT),
-                "softmax partial forward: for layers with edge attention and softmax attention only (the others: "
-                "pvs_egnn_layer_edge_sums / pvs_egnn_layer_fwd_partial)");
-    PVS_REQUIRE(!(d->flags & PVS_EDGE_RESIDUAL), "softmax partial forward: edge_residual layers are not supported");
+    c->fam = pvs_edge_family(d->hidden, d->flags, d->n_edge_attr, PVS_EDGE_FWD);
+    PVS_REQUIRE(c->fam != PVS_EDGE_GENERIC, "%s needs the MFMA edge kernel (H = 32, 64 or 128)", what);
+    const bool soft_layer = (d->flags & PVS_EDGE_ATTENTION) && (d->flags & PVS_SOFTMAX_ATT);
+    PVS_REQUIRE(soft == soft_layer, "%s: %s", what,
+                soft ? "for layers with edge attention and softmax attention only (the others: pvs_egnn_layer_edge_sums / "
+                       "pvs_egnn_layer_fwd_partial)"
+                     : "softmax attention is not supported (row sums of two edge sets do not add)");
+    PVS_REQUIRE(!(d->flags & PVS_EDGE_RESIDUAL), "%s: edge_residual layers are not supported", what);
+    PVS_REQUIRE(tensors, "%s: NULL tensor", entry);
+    PVS_REQUIRE(x_out != x, "%s: x_out must not alias x", entry);
+    PVS_REQUIRE(!soft || ((uintptr_t)base_rows & 15) == 0, "%s: base_rows must be 16-byte aligned", entry);
+    c->m = make_dims(d, g);
+    PvsArena arena(workspace, workspace_bytes);
+    carve_partial(arena, c->m, soft, &c->ws);
+    PVS_REQUIRE(arena.ok(), "%s: workspace too small (%zu < %zu)", entry, workspace_bytes, arena.off);
     return 0;
 }
 
-struct SoftPartialWs {
-    FwdWs w;
-    float *att, *fac;
-};
+// P | Q into PQ with the clears, then the MFMA edge forward over g with the raw coordinate sums in x_out, timed as `tag`
+int partial_edge_forward(hipStream_t s, const PartialCall& c, const PvsLayerDesc* d, const PvsGraph* g,
+                         const PvsLayerParams* p, const float* h, const float* x, float* PQ, float* Magg, float* x_out,
+                         float* att, int tag) {
+    const PvsEdgeW ew = make_edge_w(c.m, p);
+    PvsEdgeFwdIO io = make_fwd_io(c.ws.w, PQ, x, nullptr, Magg, x_out, nullptr, att);
+    PVS_TRY(node_pre_forward(s, c.m, p, h, PQ, &io, d->flags | kFwdRawXsum));
+    pvs_prof_set_fwd_tag(tag);
+    const int rc = pvs_launch_edge_fwd_mfma(s, c.m.H, c.fam, *g, ew, d->flags | kFwdRawXsum, d->att_act, io);
+    pvs_prof_set_fwd_tag(PVS_PROF_EDGE_FWD);      // (back first: a failing launch's code goes out after it)
+    return rc;
+}
 
-// mode 3 of pvs_egnn_layer_workspace_bytes
-void carve_soft_partial(PvsArena& a, const Dims& m, SoftPartialWs* t) {
-    carve_fwd(a, m, &t->w);
-    t->att = a.take<float>((size_t)(m.E > 0 ? m.E : 1));
-    t->fac = a.take<float>((size_t)m.N);
+// The base of a set of edges, once per receptor. out: magg [N, H], or base rows [N, H + 4] for soft.
+int partial_base(bool soft, const char* entry, const PvsLayerDesc* d, const PvsGraph* g, const PvsLayerParams* p,
+                 const float* h, const float* x, float* out, float* xsum, void* workspace, size_t workspace_bytes,
+                 hipStream_t s) {
+    PartialCall c;
+    PVS_TRY(partial_checks(soft, entry, d, g, p, h && x && out && xsum, x, nullptr, out, workspace, workspace_bytes, &c));
+    const FwdWs& w = c.ws.w;
+    float* Magg = soft ? w.y1 : out;      // (A_b: [N, H] of the forward's workspace that a base has no other use for)
+    PVS_TRY(partial_edge_forward(s, c, d, g, p, h, x, w.PQ, Magg, xsum, c.ws.att, PVS_PROF_EDGE_FWD));
+    if (!(d->flags & PVS_UPDATE_COORDS))
+        PVS_CHECK_HIP(hipMemsetAsync(xsum, 0, sizeof(float) * 3 * (size_t)c.m.N, s));
+    if (soft) {
+        const long long threads = (long long)c.m.N * (c.m.H / 4 + 1);
+        k_pack_base_rows<<<(int)((threads + 255) / 256), 256, 0, s>>>(Magg, w.smax, w.ssum, g->rowptr, out, c.m.N, c.m.H);
+        PVS_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
+// EGNNLayer.forward over the edges of g on top of a base (base: base_magg, or base rows for soft), per batch. att_out: the
+// caller keeps the layer's attention (CSR-sorted over g), NULL: it stays in the workspace (carved either way: one size)
+int partial_forward(bool soft, const char* entry, const PvsLayerDesc* d, const PvsGraph* g, const PvsLayerParams* p,
+                    const float* h, const float* x, const float* base, const float* base_xsum, const float* base_deg,
+                    float* h_out, float* x_out, float* node_att_out, float* att_out, float* saved, void* workspace,
+                    size_t workspace_bytes, hipStream_t s) {
+    PartialCall c;
+    PVS_TRY(partial_checks(soft, entry, d, g, p, h && x && base && base_xsum && base_deg && h_out && x_out && saved, x,
+                           x_out, base, workspace, workspace_bytes, &c));
+    const Dims& m = c.m;
+    const FwdWs& w = c.ws.w;
+    const int H = m.H, upd = (d->flags & PVS_UPDATE_COORDS) ? 1 : 0;
+    const SavedLayout sv = saved_layout(saved, m.N, H);
+    // (the launch is timed apart from the full-graph layers: bench.py)
+    PVS_TRY(partial_edge_forward(s, c, d, g, p, h, x, sv.PQ, sv.Magg, x_out, att_out ? att_out : c.ws.att,
+                                 PVS_PROF_EDGE_FWD_PARTIAL));
+    const long long threads = (long long)m.N * (H / 4);
+    const int blocks = (int)((threads + 255) / 256);
+    if (soft)
+        k_combine_partial_softmax<<<blocks, 256, 0, s>>>(sv.Magg, x_out, x, base, base_xsum, base_deg, g->rowptr, w.smax,
+                                                         w.ssum, c.ws.fac, m.N, H, upd);
+    else
+        k_combine_partial<<<blocks, 256, 0, s>>>(sv.Magg, x_out, x, base, base_xsum, base_deg, g->rowptr, m.N, H, upd);
+    PVS_CHECK_LAUNCH();
+    if (soft && att_out && g->n_edges > 0) {
+        k_scale_att_rows<<<(g->n_edges + 255) / 256, 256, 0, s>>>(*g, c.ws.fac, att_out);
+        PVS_CHECK_LAUNCH();
+    }
+    return node_mlp_forward(s, m, d, p, make_node_w(d, p), h, sv.Magg, sv.y1, sv.u, sv.o, sv.stats, true, w.shift, w.slabs,
+                            h_out, node_att_out, g->n_norm_rows_dev);
 }
 
 }  // namespace
 
+extern "C" int pvs_egnn_layer_edge_sums(const PvsLayerDesc* d, const PvsGraph* g, const PvsLayerParams* p,
+                                        const float* h, const float* x, float* magg, float* xsum,
+                                        void* workspace, size_t workspace_bytes, pvs_stream_t stream_) {
+    return partial_base(false, "pvs_egnn_layer_edge_sums", d, g, p, h, x, magg, xsum, workspace, workspace_bytes,
+                        (hipStream_t)stream_);
+}
+
+// (reports itself as pvs_egnn_layer_fwd_partial, which it is with att_out = NULL)
+extern "C" int pvs_egnn_layer_fwd_partial_att(const PvsLayerDesc* d, const PvsGraph* g, const PvsLayerParams* p,
+                                              const float* h, const float* x, const float* base_magg,
+                                              const float* base_xsum, const float* base_deg, float* h_out,
+                                              float* x_out, float* node_att_out, float* att_out, float* saved,
+                                              void* workspace, size_t workspace_bytes, pvs_stream_t stream_) {
+    return partial_forward(false, "pvs_egnn_layer_fwd_partial", d, g, p, h, x, base_magg, base_xsum, base_deg, h_out,
+                           x_out, node_att_out, att_out, saved, workspace, workspace_bytes, (hipStream_t)stream_);
+}
+
+extern "C" int pvs_egnn_layer_fwd_partial(const PvsLayerDesc* d, const PvsGraph* g, const PvsLayerParams* p,
+                                          const float* h, const float* x, const float* base_magg,
+                                          const float* base_xsum, const float* base_deg, float* h_out,
+                                          float* x_out, float* node_att_out, float* saved, void* workspace,
+                                          size_t workspace_bytes, pvs_stream_t stream_) {
+    return pvs_egnn_layer_fwd_partial_att(d, g, p, h, x, base_magg, base_xsum, base_deg, h_out, x_out, node_att_out,
+                                          nullptr, saved, workspace, workspace_bytes, stream_);
+}
+
 extern "C" int pvs_egnn_layer_edge_stats_softmax(const PvsLayerDesc* d, const PvsGraph* g, const PvsLayerParams* p,
                                                  const float* h, const float* x, float* base_rows, float* xsum,
                                                  void* workspace, size_t workspace_bytes, pvs_stream_t stream_) {
-    hipStream_t s = (hipStream_t)stream_;
-    PvsEdgeFamily fam;
-    PVS_TRY(softmax_partial_checks(d, g, p, &fam));
-    PVS_REQUIRE(h && x && base_rows && xsum, "pvs_egnn_layer_edge_stats_softmax: NULL tensor");
-    PVS_REQUIRE(((uintptr_t)base_rows & 15) == 0, "pvs_egnn_layer_edge_stats_softmax: base_rows must be 16-byte aligned");
-    const Dims m = make_dims(d, g);
-    PvsArena arena(workspace, workspace_bytes);
-    SoftPartialWs t;
-    carve_soft_partial(arena, m, &t);
-    PVS_REQUIRE(arena.ok(), "pvs_egnn_layer_edge_stats_softmax: workspace too small (%zu < %zu)", workspace_bytes,
-                arena.off);
-    const PvsEdgeW ew = make_edge_w(m, p);
-    float* A_b = t.w.y1;       // [N, H] of the forward's workspace that this entry has no other use for
-    PvsEdgeFwdIO io = make_fwd_io(t.w, t.w.PQ, x, nullptr, A_b, xsum, nullptr, t.att);
-    PVS_TRY(node_pre_forward(s, m, p, h, t.w.PQ, &io, d->flags | kFwdRawXsum));
-    PVS_TRY(pvs_launch_edge_fwd_mfma(s, m.H, fam, *g, ew, d->flags | kFwdRawXsum, d->att_act, io));
-    if (!(d->flags & PVS_UPDATE_COORDS))
-        PVS_CHECK_HIP(hipMemsetAsync(xsum, 0, sizeof(float) * 3 * (size_t)m.N, s));
-    const long long threads = (long long)m.N * (m.H / 4 + 1);
-    k_pack_base_rows<<<(int)((threads + 255) / 256), 256, 0, s>>>(A_b, t.w.smax, t.w.ssum, g->rowptr, base_rows, m.N, m.H);
-    PVS_CHECK_LAUNCH();
-    return 0;
+    return partial_base(true, "pvs_egnn_layer_edge_stats_softmax", d, g, p, h, x, base_rows, xsum, workspace,
+                        workspace_bytes, (hipStream_t)stream_);
 }
 
 extern "C" int pvs_egnn_layer_fwd_partial_softmax(const PvsLayerDesc* d, const PvsGraph* g, const PvsLayerParams* p,
@@ -614,42 +626,8 @@ extern "C" int pvs_egnn_layer_fwd_partial_softmax(const PvsLayerDesc* d, const P
                                                   const float* base_xsum, const float* base_deg, float* h_out,
                                                   float* x_out, float* node_att_out, float* att_out, float* saved,
                                                   void* workspace, size_t workspace_bytes, pvs_stream_t stream_) {
-    hipStream_t s = (hipStream_t)stream_;
-    PvsEdgeFamily fam;
-    PVS_TRY(softmax_partial_checks(d, g, p, &fam));
-    PVS_REQUIRE(h && x && base_rows && base_xsum && base_deg && h_out && x_out && saved,
-                "pvs_egnn_layer_fwd_partial_softmax: NULL tensor");
-    PVS_REQUIRE(x_out != x, "pvs_egnn_layer_fwd_partial_softmax: x_out must not alias x");
-    PVS_REQUIRE(((uintptr_t)base_rows & 15) == 0, "pvs_egnn_layer_fwd_partial_softmax: base_rows must be 16-byte aligned");
-    const Dims m = make_dims(d, g);
-    PvsArena arena(workspace, workspace_bytes);
-    SoftPartialWs t;
-    carve_soft_partial(arena, m, &t);
-    PVS_REQUIRE(arena.ok(), "pvs_egnn_layer_fwd_partial_softmax: workspace too small (%zu < %zu)", workspace_bytes,
-                arena.off);
-    float* att = att_out ? att_out : t.att;       // the caller keeps the layer's attention (CSR-sorted over g)
-    const int H = m.H;
-    const SavedLayout sv = saved_layout(saved, m.N, H);
-    const PvsEdgeW ew = make_edge_w(m, p);
-    const PvsNodeW nw = make_node_w(d, p);
-    PvsEdgeFwdIO io = make_fwd_io(t.w, sv.PQ, x, nullptr, sv.Magg, x_out, nullptr, att);
-    PVS_TRY(node_pre_forward(s, m, p, h, sv.PQ, &io, d->flags | kFwdRawXsum));
-    pvs_prof_set_fwd_tag(PVS_PROF_EDGE_FWD_PARTIAL);
-    const int rc_partial = pvs_launch_edge_fwd_mfma(s, H, fam, *g, ew, d->flags | kFwdRawXsum, d->att_act, io);
-    pvs_prof_set_fwd_tag(PVS_PROF_EDGE_FWD);
-    PVS_TRY(rc_partial);
-    const long long threads = (long long)m.N * (H / 4);
-    k_combine_partial_softmax<<<(int)((threads + 255) / 256), 256, 0, s>>>(
-        sv.Magg, x_out, x, base_rows, base_xsum, base_deg, g->rowptr, t.w.smax, t.w.ssum, t.fac, m.N, H,
-        (d->flags & PVS_UPDATE_COORDS) ? 1 : 0);
-    PVS_CHECK_LAUNCH();
-    if (att_out && g->n_edges > 0) {
-        k_scale_att_rows<<<(g->n_edges + 255) / 256, 256, 0, s>>>(*g, t.fac, att_out);
-        PVS_CHECK_LAUNCH();
-    }
-    PVS_TRY(node_mlp_forward(s, m, d, p, nw, h, sv.Magg, sv.y1, sv.u, sv.o, sv.stats, true, t.w.shift, t.w.slabs, h_out,
-                             node_att_out, g->n_norm_rows_dev));
-    return 0;
+    return partial_forward(true, "pvs_egnn_layer_fwd_partial_softmax", d, g, p, h, x, base_rows, base_xsum, base_deg,
+                           h_out, x_out, node_att_out, att_out, saved, workspace, workspace_bytes, (hipStream_t)stream_);
 }
 
 extern "C" int pvs_egnn_layer_bwd(const PvsLayerDesc* d, const PvsGraph* g, const PvsLayerParams* p,

@@ -13,6 +13,7 @@ sums that add; with `softmax_reuse=True` its receptor side is kept as softmax st
 """
 import contextlib
 import ctypes as C
+from collections import namedtuple
 
 import torch
 from torch import nn
@@ -30,6 +31,15 @@ MAX_SCREEN_LIGAND_ATOMS = 1024
 
 def _stream(dev):
     return _lib.stream(dev)
+
+
+# The first-layer reuse of one kind of layer: the entry that makes a receptor's base, the entry that runs the layer on top
+# of it (the one that takes att_out, or NULL), the mode of pvs_egnn_layer_workspace_bytes and what a base row holds
+# behind its H channels. Sums that add (sigmoid attention or none; _att with NULL is pvs_egnn_layer_fwd_partial bit for
+# bit) | softmax statistics
+_ReuseKind = namedtuple('_ReuseKind', 'base_entry partial_entry ws_mode row_extra')
+_SUMS = _ReuseKind('pvs_egnn_layer_edge_sums', 'pvs_egnn_layer_fwd_partial_att', 2, 0)
+_SOFTMAX = _ReuseKind('pvs_egnn_layer_edge_stats_softmax', 'pvs_egnn_layer_fwd_partial_softmax', 3, 4)
 
 
 def _csr_buffers(dev, n_nodes, cap_l, cap=None, **extra):
@@ -157,6 +167,7 @@ class _ReceptorSideScreen:
         self.softmax_reuse = bool(softmax_reuse)
         first = self.egnn[0] if self.egnn else None
         self._soft = bool(self.softmax_reuse and first is not None and first.softmax_attention and first.edge_attention)
+        self._kind = _SOFTMAX if self._soft else _SUMS      # decided here, read by the base and the partial first layer
         # None: a single-head model, the path below as it always was; else the heads of a two-headed model, resolved
         # here (a captured step has them baked in) and never by changing model.model_task
         self.tasks = _resolve_tasks(model, tasks)
@@ -214,11 +225,10 @@ class _ReceptorSideScreen:
             pg = radius_graph(rec_pos, torch.ones(n_rec, dtype=torch.uint8, device=dev), None,
                               self.r_inter, self.r_intra, need_backward=False)
             desc, params, pstruct = self._first_layer_args()
-            width = self.egnn[0].hidden_nf + (4 if self._soft else 0)
-            name = 'pvs_egnn_layer_edge_stats_softmax' if self._soft else 'pvs_egnn_layer_edge_sums'
-            magg = torch.empty((n_rec, width), dtype=torch.float32, device=dev)
+            name = self._kind.base_entry
+            magg = torch.empty((n_rec, self.egnn[0].hidden_nf + self._kind.row_extra), dtype=torch.float32, device=dev)
             xsum = torch.empty((n_rec, 3), dtype=torch.float32, device=dev)
-            ws_bytes = lib.pvs_egnn_layer_workspace_bytes(C.byref(desc), n_rec, pg.n_edges, 3 if self._soft else 2)
+            ws_bytes = lib.pvs_egnn_layer_workspace_bytes(C.byref(desc), n_rec, pg.n_edges, self._kind.ws_mode)
             ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
             _lib.check(getattr(lib, name)(
                 C.byref(desc), C.byref(pg.c), C.byref(pstruct), _lib.ptr(h_rec.contiguous()),
@@ -232,7 +242,8 @@ class _ReceptorSideScreen:
     def _partial_first_layer(self, g, h, x, base_magg, base_xsum, base_deg, ws_nodes, ws_edges, att_out=None):
         """First layer over the ligand-touching edges `g` on top of the receptor-receptor sums `base_*` (one row
         per node). ws_nodes / ws_edges size the saved / workspace pair, allocated at the first call. att_out
-        [>= g's edge room]: receives the layer's edge attention in g's edge order (pvs_egnn_layer_fwd_partial_att).
+        [>= g's edge room]: receives the layer's edge attention in g's edge order; None: the entry gets NULL and keeps it
+        in its workspace (pvs_egnn_layer_fwd_partial_att, then pvs_egnn_layer_fwd_partial bit for bit).
         Under softmax_reuse base_magg holds base rows and the entry is pvs_egnn_layer_fwd_partial_softmax, whose
         attention is normalised over all edges of a row."""
         lib = _lib.lib()
@@ -244,20 +255,14 @@ class _ReceptorSideScreen:
             self._l1_ws = (
                 torch.empty(lib.pvs_egnn_layer_saved_floats(C.byref(desc), ws_nodes, ws_edges), dtype=torch.float32,
                             device=dev),
-                torch.empty(lib.pvs_egnn_layer_workspace_bytes(C.byref(desc), ws_nodes, ws_edges, 3 if self._soft else 2),
+                torch.empty(lib.pvs_egnn_layer_workspace_bytes(C.byref(desc), ws_nodes, ws_edges, self._kind.ws_mode),
                             dtype=torch.uint8, device=dev))
         saved, ws = self._l1_ws
-        args = [C.byref(desc), C.byref(g), C.byref(pstruct), _lib.ptr(h), _lib.ptr(x), _lib.ptr(base_magg),
-                _lib.ptr(base_xsum), _lib.ptr(base_deg), _lib.ptr(h_out), _lib.ptr(x_out), _lib.ptr(natt),
-                _lib.ptr(saved), _lib.ptr(ws), ws.numel(), _stream(dev)]
-        name = 'pvs_egnn_layer_fwd_partial'
-        if self._soft:               # (att_out, or NULL, behind natt)
-            args.insert(11, _lib.ptr(att_out))
-            name = 'pvs_egnn_layer_fwd_partial_softmax'
-        elif att_out is not None:    # (the _att entry point takes att_out behind natt and is otherwise called alike)
-            args.insert(11, _lib.ptr(att_out))
-            name = 'pvs_egnn_layer_fwd_partial_att'
-        _lib.check(getattr(lib, name)(*args), name)
+        name = self._kind.partial_entry
+        _lib.check(getattr(lib, name)(
+            C.byref(desc), C.byref(g), C.byref(pstruct), _lib.ptr(h), _lib.ptr(x), _lib.ptr(base_magg),
+            _lib.ptr(base_xsum), _lib.ptr(base_deg), _lib.ptr(h_out), _lib.ptr(x_out), _lib.ptr(natt), _lib.ptr(att_out),
+            _lib.ptr(saved), _lib.ptr(ws), ws.numel(), _stream(dev)), name)
         return h_out, x_out
 
     def _tail(self, pg_full, h, x):
@@ -829,7 +834,7 @@ class LibraryScreen(_ReceptorSideScreen):
         dev, n_cap = self.lig_pos.device, self.n_cap
         i32 = dict(dtype=torch.int32, device=dev)
         f32 = dict(dtype=torch.float32, device=dev)
-        hid = self.rec_magg.shape[1]      # (the hidden size; under softmax_reuse the base rows' H + 4)
+        hid = self.rec_magg.shape[1]      # (a base row's width: the hidden size + the reuse kind's row_extra)
         f = _csr_buffers(
             dev, n_cap, cap_l, cap,
             state=torch.empty((lib.pvs_screen_graph_struck_state_bytes if self.struck else
