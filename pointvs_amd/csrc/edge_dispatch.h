@@ -20,7 +20,7 @@ enum PvsEdgeDirection { PVS_EDGE_FWD, PVS_EDGE_BWD };
 //   PVS_EGNN_KERNELS=generic   the generic kernels everywhere (H = 128 has none: the layer calls refuse it)
 //   PVS_EGNN_BF16X3=0          exact fp32 MFMAs instead of the split products (the H = 128 forward has no exact form)
 //   PVS_EGNN_BF16X3_H64=0      the same for H = 64 only
-// Read at every call: the tests flip them inside one process (layer_api.hip, node_mlp_forward). No family depends on the
+// Read at every call: the tests flip them inside one process (layer_plan.h, pvs_layer_switches). No family depends on the
 // layer's flags today; they are part of the question all the same.
 inline PvsEdgeFamily pvs_edge_family(int H, uint32_t flags, int n_attr, PvsEdgeDirection dir) {
     (void)flags;

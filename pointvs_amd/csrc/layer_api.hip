@@ -3,6 +3,7 @@
 #include "common.h"
 #include "dense_ops.h"
 #include "edge_kernels.h"
+#include "layer_plan.h"
 #include "node_ops.h"
 #include "profile.h"
 
@@ -258,10 +259,8 @@ int node_mlp_forward(hipStream_t s, const Dims& m, const PvsLayerDesc* d, const 
     const bool fuse_silu = can_epi && !(F & PVS_GRAPHNORM);
     const bool gated = (F & PVS_RESIDUAL) && (F & (PVS_REZERO | PVS_GATED_RESIDUAL));
     const bool fuse_out = can_epi && !(F & PVS_NODE_ATTENTION) && !gated;
-    // (The A/B switches are read from the environment at EVERY call on purpose - ADVICE r03 suggested statics: the
-    // test suite and tools/abenv.py flip them inside one process, e.g. the exact-fp32 family against the split products
-    // on the same tensors. A getenv is ~0.2 us of host time; a layer call enqueues 6-9 launches of >= 3 us each.)
-    const bool split_small = getenv("PVS_EGNN_SPLIT_SMALL") != nullptr;     // (the launches apart, for A/B)
+    // (read at every call: layer_plan.h)
+    const bool split_small = pvs_layer_switches().split_small;     // (the launches apart, for A/B)
     if (fuse_silu && !gated && !split_small && p->node_b1 && p->node_b2 &&
         pvs_node_mlp_fused_supported(H, h, Magg, y1, h_out)) {
         // no GraphNorm, no rezero / gated residual: the whole chain y1 -> u -> o -> (node gate) -> h_out in one launch
@@ -290,7 +289,7 @@ int node_mlp_forward(hipStream_t s, const Dims& m, const PvsLayerDesc* d, const 
 int node_pre_forward(hipStream_t s, const Dims& m, const PvsLayerParams* p, const float* h,
                      float* PQ, PvsEdgeFwdIO* init = nullptr, uint32_t init_flags = 0) {
     const int H = m.H;
-    const bool split_small = getenv("PVS_EGNN_SPLIT_SMALL") != nullptr;     // (the launches apart, for A/B)
+    const bool split_small = pvs_layer_switches().split_small;     // (the launches apart, for A/B)
     PvsLinearExt e;
     if (init) {
         e.zero_rows = init->Magg; e.zero_w = H; e.zero_ld = H;
@@ -630,103 +629,109 @@ extern "C" int pvs_egnn_layer_fwd_partial_softmax(const PvsLayerDesc* d, const P
                            h_out, x_out, node_att_out, att_out, saved, workspace, workspace_bytes, (hipStream_t)stream_);
 }
 
-extern "C" int pvs_egnn_layer_bwd(const PvsLayerDesc* d, const PvsGraph* g, const PvsLayerParams* p,
-                                  const float* h, const float* x, const float* m_prev,
-                                  const float* att, const float* saved, const float* g_h_out,
-                                  const float* g_x_out, const float* g_m_out, float* g_h, float* g_x,
-                                  float* g_m_prev, const PvsLayerGrads* gr_, void* workspace,
-                                  size_t workspace_bytes, pvs_stream_t stream_) {
-    hipStream_t s = (hipStream_t)stream_;
-    PVS_TRY(check_desc(d, g, p));
-    PVS_REQUIRE(h && x && saved && g_h_out && g_h && gr_, "pvs_egnn_layer_bwd: NULL tensor");
-    PVS_REQUIRE(g->n_edges == 0 || (g->colptr && g->cedge),
-                "pvs_egnn_layer_bwd: graph was built without the by-column lists (forward-only)");
-    const uint32_t F = d->flags;
-    const bool eatt = F & PVS_EDGE_ATTENTION, soft = F & PVS_SOFTMAX_ATT;
-    const bool eres = (F & PVS_EDGE_RESIDUAL) && m_prev;
-    PVS_REQUIRE(!eatt || att, "pvs_egnn_layer_bwd: att required with edge attention");
-    PVS_REQUIRE(!eres || g_m_prev, "pvs_egnn_layer_bwd: g_m_prev required with edge residual");
-    const PvsLayerGrads gr = *gr_;
-    const Dims m = make_dims(d, g);
-    PvsArena arena(workspace, workspace_bytes);
-    BwdWs w;
-    carve_bwd(arena, m, &w);
-    PVS_REQUIRE(arena.ok(), "pvs_egnn_layer_bwd: workspace too small (%zu < %zu)", workspace_bytes,
-                arena.off);
-    const int H = m.H, N = m.N;
-    const SavedLayout sv = saved_layout(const_cast<float*>(saved), N, H);      // read-only here
-    const float *Magg = sv.Magg, *sPQ = sv.PQ, *sy1 = sv.y1, *so = sv.o, *su = sv.u;
-    float* stats = sv.stats;
-    const PvsEdgeW ew = make_edge_w(m, p);
-    const PvsNodeW nw = make_node_w(d, p);
-    const bool gn = F & PVS_GRAPHNORM, natt = F & PVS_NODE_ATTENTION;
-    const bool gates = (F & PVS_RESIDUAL) && (F & (PVS_REZERO | PVS_GATED_RESIDUAL));
-    const bool coord_bwd = (F & PVS_UPDATE_COORDS) && g_x_out;
-    // all node-level weight gradients in one pass at the end (H = 32, 64, the usual full set of grads)
-    const bool fused_wgrads = pvs_node_wgrads_supported(H) && gr.node_w2 && gr.node_w1 && gr.edge_w1 &&
-                              !getenv("PVS_EGNN_SPLIT_WGRADS");
+// ---- the backward as steps (pvs_egnn_layer_bwd below: checks, facts -> plan (layer_plan.h), these steps in order) --------
+// Every launch decision is a field of the plan; a step enqueues what the plan says and decides nothing.
+namespace {
 
-    // ---- node-level forward: PQ, y1, o and u = SiLU(GN(y1)) were kept by the forward ----
+// The call's tensors, and the pointers the plan settles for all steps
+struct BwdCall {
+    hipStream_t s;
+    const PvsLayerDesc* d;
+    const PvsGraph* g;
+    const PvsLayerParams* p;
+    Dims m;
+    const float *h, *x, *m_prev, *att, *g_h_out, *g_x_out, *g_m_out;
+    float *g_h, *g_x, *g_m_prev;
+    PvsLayerGrads gr;
+    PvsNodeW nw;
+    const float* g_o;       // w.g_o, or g_h_out itself (plan.g_o_is_g_h_out)
+    float* gx_row;          // w.gx_row, or NULL (plan.first_layer)
+    PvsLinearExt prep;      // the per-node preparation of the edge backward as row side jobs (plan.prep says of what)
+};
 
-    // ---- node_model backward ----
-    const bool split_small = getenv("PVS_EGNN_SPLIT_SMALL") != nullptr;     // (the launches apart, for A/B)
-    const PvsEdgeFamily fam = pvs_edge_family(H, F, m.A, PVS_EDGE_BWD);
-    const bool mfma_bwd = fam != PVS_EDGE_GENERIC;
-    // Nobody asks for the gradient of this layer's input coordinates (the first layer of a model, whichever entry point
-    // the call came through): the first-layer pair, which neither forms nor sums it (edge_dispatch.h). gx_row == NULL is
-    // how the two launchers are told.
-    const bool first_layer = pvs_first_layer_bwd(H, F, m.A, m_prev != nullptr, g_x_out != nullptr, g_x != nullptr);
-    float* const gx_row = first_layer ? nullptr : w.gx_row;
-    pvs_note_edge_bwd_variant(first_layer ? PVS_EDGE_BWD_FIRST_LAYER : PVS_EDGE_BWD_GENERAL);
-    // Layers without GraphNorm and without rezero / gated residual: the output stage (node gate, residual), g_y1 and
-    // [g_h | gM] as ONE launch that also carries the per-node preparation of the edge backward (dense_ops.hip:
-    // k_node_mlp_bwd). Without a node gate g_o is g_h_out itself and nothing is written for it.
-    const bool chain_bwd = !gn && !gates && !split_small && pvs_node_mlp_fused_supported(H, g_h_out, sy1, w.g_u, g_h) &&
-                           (((uintptr_t)w.gM | (uintptr_t)w.gPQ | (uintptr_t)so | (uintptr_t)w.g_o | (uintptr_t)w.t1) & 15) == 0;
-    // (no residual, no node gate: g_o = g_h_out and the residual's part of g_h is zero - nothing to launch either way)
-    const bool plain_out = !(F & PVS_RESIDUAL) && !natt && !split_small;
-    const float* g_o = (plain_out || (chain_bwd && !natt)) ? g_h_out : w.g_o;
-    if (!plain_out && !chain_bwd)
-        PVS_TRY(pvs_node_out_bwd(s, H, g_h_out, so, h, nw, F, d->att_act, N, w.g_o, g_h, w.gl, w.t1,
+// What the edge step leaves for the tail, and the tail for the finalize launch
+struct BwdTail {
+    PvsReduce2Args edge_red;
+    const float* node_gsum = nullptr;
+    PvsNodeWgradSlabs node_slabs;
+    PvsNodeWgradOut node_out{};
+};
+
+// o = u Wn2^T + bn2 backward: g_u = g_o Wn2 (g_o: the workspace's, or g_h_out)
+PvsLinearJob bwd_gu_job(const BwdCall& c, const BwdWs& w, const SavedLayout& sv, const float* g_o) {
+    const int H = c.m.H;
+    PvsLinearJob gu = pvs_linear_job(w.g_u, H, pvs_operand_t(g_o, H, c.p->node_w2, H, H), c.m.N, H);
+    gu.aux_in = sv.y1; gu.ld_in = H;
+    return gu;
+}
+// y1 = h Wn1[:, :H]^T + Magg Wn1[:, H:]^T + bn1 backward (g_y1 = w.g_u): g_h (+)= g_y1 Wn1[:, :H], gM = g_y1 Wn1[:, H:]
+PvsLinearJob bwd_gh1_job(const BwdCall& c, const BwdWs& w) {
+    const int H = c.m.H;
+    return pvs_linear_job(c.g_h, H, pvs_operand_t(w.g_u, H, c.p->node_w1, 2 * H, H), c.m.N, H);
+}
+PvsLinearJob bwd_gm_job(const BwdCall& c, const BwdWs& w) {
+    const int H = c.m.H;
+    return pvs_linear_job(w.gM, H, pvs_operand_t(w.g_u, H, c.p->node_w1 + H, 2 * H, H), c.m.N, H);
+}
+// both in one launch: 2H outputs over the two halves of node_mlp.0's weight, the second column block to gM (`ext`)
+PvsLinearJob bwd_both_job(const BwdCall& c, const BwdWs& w, const PvsLinearExt* ext) {
+    PvsLinearJob both = bwd_gh1_job(c, w);
+    both.C = 2 * c.m.H;
+    both.ext = ext;
+    return both;
+}
+
+// 1. output stage (node gate, residual) and the node-gate gradients. The chain kernel, where the plan takes it, is this
+// step's launch and does steps 2 and 3 as well.
+int bwd_output_stage(const PvsBwdPlan& plan, const BwdCall& c, const BwdWs& w, const SavedLayout& sv) {
+    hipStream_t s = c.s;
+    const int H = c.m.H, N = c.m.N;
+    const uint32_t F = c.d->flags;
+    const PvsLayerGrads& gr = c.gr;
+    if (plan.node_out_bwd)
+        PVS_TRY(pvs_node_out_bwd(s, H, c.g_h_out, sv.o, c.h, c.nw, F, c.d->att_act, N, w.g_o, c.g_h, w.gl, w.t1,
                                  w.tg));
-    PvsLinearExt prep;
-    if (mfma_bwd) { prep.zero_rows = w.gPQ; prep.zero_w = H; prep.zero_ld = 2 * H; prep.zero3 = gx_row; }
-    if (coord_bwd) { prep.scale3_src = g_x_out; prep.scale3_by = g->inv_deg; prep.scale3_dst = w.gxagg; }
-    if (chain_bwd)
-        PVS_TRY(pvs_launch_node_mlp_bwd(s, H, N, g_h_out, so, sy1, p->node_w1, p->node_w2, (F & PVS_RESIDUAL) != 0,
-                                        natt ? nw.natt_w : nullptr, natt ? nw.natt_b : nullptr, d->att_act, w.g_o, w.t1,
-                                        w.gl, w.g_u, g_h, w.gM, &prep));
-    // (the node gate's weight gradients - column sums of t1, sum of gl - ride on the fused weight-gradient pass when
-    // it runs: two column reductions and their slab reductions less per layer)
-    const bool gate_in_wgrads = natt && fused_wgrads && !split_small && gr.node_att_w && gr.node_att_b;
-    if (natt && !gate_in_wgrads) {
-        if (gr.node_att_w)
-            PVS_TRY(pvs_launch_colreduce(s, PVS_COL_SUM_A, gr.node_att_w, w.t1, H, nullptr, 0, nullptr,
-                                         N, H, 1.f, w.dslabs, false));
-        if (gr.node_att_b)
-            PVS_TRY(pvs_launch_colreduce(s, PVS_COL_SUM_A, gr.node_att_b, w.gl, 1, nullptr, 0, nullptr,
-                                         N, 1, 1.f, w.dslabs, false));
+    if (plan.gh_gm == PVS_BWD_GHGM_CHAIN) {
+        const bool natt = F & PVS_NODE_ATTENTION;
+        PVS_TRY(pvs_launch_node_mlp_bwd(s, H, N, c.g_h_out, sv.o, sv.y1, c.p->node_w1, c.p->node_w2, (F & PVS_RESIDUAL) != 0,
+                                        natt ? c.nw.natt_w : nullptr, natt ? c.nw.natt_b : nullptr, c.d->att_act, w.g_o, w.t1,
+                                        w.gl, w.g_u, c.g_h, w.gM, &c.prep));
     }
-    if (gates && gr.node_gate) {
+    if (plan.own_node_att_w)
+        PVS_TRY(pvs_launch_colreduce(s, PVS_COL_SUM_A, gr.node_att_w, w.t1, H, nullptr, 0, nullptr,
+                                     N, H, 1.f, w.dslabs, false));
+    if (plan.own_node_att_b)
+        PVS_TRY(pvs_launch_colreduce(s, PVS_COL_SUM_A, gr.node_att_b, w.gl, 1, nullptr, 0, nullptr,
+                                     N, 1, 1.f, w.dslabs, false));
+    if (plan.own_node_gate) {
         PVS_TRY(pvs_launch_colreduce(s, PVS_COL_SUM_A, w.gvec, w.tg, H, nullptr, 0, nullptr, N, H, 1.f,
                                      w.dslabs, false));
         PVS_TRY(pvs_sum_vec(s, w.gvec, H, gr.node_gate));
     }
-    // o = u Wn2^T + bn2
-    // (without GraphNorm g_y1 = g_u * SiLU'(y1) rides on this product's epilogue)
-    PvsLinearJob gu = pvs_linear_job(w.g_u, H, pvs_operand_t(g_o, H, p->node_w2, H, H), N, H);
-    gu.aux_in = sy1; gu.ld_in = H;
-    const bool fuse_tail_bwd = !gn && pvs_linear_epilogue_supported(gu) && ((uintptr_t)sy1 & 15) == 0;
-    gu.epi = fuse_tail_bwd ? PVS_EPI_MUL_SILU_GRAD : PVS_EPI_NONE;
-    if (!chain_bwd) PVS_TRY(pvs_launch_linear(s, gu));
-    if (gr.node_w2 && !fused_wgrads)
-        PVS_TRY(pvs_launch_tsgemm_tn(s, gr.node_w2, H, g_o, H, su, H, N, H, H, w.dslabs, false));
-    if (gr.node_b2 && !fused_wgrads)
-        PVS_TRY(pvs_launch_colreduce(s, PVS_COL_SUM_A, gr.node_b2, g_o, H, nullptr, 0, nullptr, N, H,
+    return 0;
+}
+
+// 2. node MLP backward up to g_y1 (w.g_u, in place), GraphNorm included
+int bwd_node_mlp_to_gy1(const PvsBwdPlan& plan, const BwdCall& c, const BwdWs& w, const SavedLayout& sv) {
+    hipStream_t s = c.s;
+    const int H = c.m.H, N = c.m.N;
+    const PvsLayerGrads& gr = c.gr;
+    const PvsGraph* g = c.g;
+    const PvsNodeW& nw = c.nw;
+    const float* sy1 = sv.y1;
+    float* stats = sv.stats;
+    if (plan.gu_product) {
+        PvsLinearJob gu = bwd_gu_job(c, w, sv, c.g_o);
+        gu.epi = plan.fuse_tail_bwd ? PVS_EPI_MUL_SILU_GRAD : PVS_EPI_NONE;
+        PVS_TRY(pvs_launch_linear(s, gu));
+    }
+    if (plan.own_node_w2)
+        PVS_TRY(pvs_launch_tsgemm_tn(s, gr.node_w2, H, c.g_o, H, sv.u, H, N, H, H, w.dslabs, false));
+    if (plan.own_node_b2)
+        PVS_TRY(pvs_launch_colreduce(s, PVS_COL_SUM_A, gr.node_b2, c.g_o, H, nullptr, 0, nullptr, N, H,
                                      1.f, w.dslabs, false));
-    // u = SiLU(GN(y1)) ; g_u becomes g_yn then g_y1 in place
-    if (!fuse_tail_bwd && !chain_bwd) PVS_TRY(pvs_node_tail_bwd1(s, w.g_u, sy1, stats, nw, N, H, w.g_u));
-    if (gn) {
+    if (plan.tail_bwd1) PVS_TRY(pvs_node_tail_bwd1(s, w.g_u, sy1, stats, nw, N, H, w.g_u));
+    if (plan.graphnorm) {
         PVS_TRY(pvs_launch_colreduce(s, PVS_COL_SUM_A, w.S1, w.g_u, H, nullptr, 0, nullptr, N, H, 1.f,
                                      w.dslabs, false));
         PVS_TRY(pvs_launch_colreduce(s, PVS_COL_SUM_AB, w.S2, w.g_u, H, sy1, H, nullptr, N, H, 1.f,
@@ -737,131 +742,196 @@ extern "C" int pvs_egnn_layer_bwd(const PvsLayerDesc* d, const PvsGraph* g, cons
                                         gr.gn_mean_scale, w.coefs, g->n_norm_rows_dev));
         PVS_TRY(pvs_node_tail_bwd2(s, w.g_u, sy1, stats, nw, w.coefs, N, H, w.g_u, g->n_norm_rows_dev));
     }
-    float* g_y1 = w.g_u;
-    // y1 = h Wn1[:, :H]^T + Magg Wn1[:, H:]^T + bn1
-    // The per-node preparation of the edge backward (clear the row part of gPQ and gx_row - rows without edges are
-    // never written by the MFMA edge backward -, g_x_out / deg) rides on these products as side jobs of the node rows
-    // where the MFMA linear takes the shape; the softmax row dots need the finished gM and keep their own launch.
-    PvsLinearJob gh1 = pvs_linear_job(g_h, H, pvs_operand_t(g_y1, H, p->node_w1, 2 * H, H), N, H);
-    gh1.accumulate = !plain_out;
-    PvsLinearJob gm = pvs_linear_job(w.gM, H, pvs_operand_t(g_y1, H, p->node_w1 + H, 2 * H, H), N, H);
-    const bool prep_side = !split_small && ((uintptr_t)w.gPQ & 15) == 0 && pvs_linear_epilogue_supported(gm);
-    // g_h (+)= and gM = in one launch: 64 outputs over the two halves of node_mlp.0's weight, the second column block
-    // to gM
-    PvsLinearJob both = gh1;
-    both.C = 2 * H;
-    both.ext = &prep;
-    bool prep_done = false;
-    if (chain_bwd) {
-        prep_done = true;       // (launched above)
-    } else if (H == 32 && prep_side && pvs_linear_epilogue_supported(both)) {
-        prep.y1 = w.gM; prep.ldy1 = H; prep.acc1 = 0;
+    return 0;
+}
+
+// 3. g_h / gM from g_y1 with the per-node preparation of the edge backward (plan.prep: layer_plan.h), and the unfused
+// weight gradients of node_mlp.0
+int bwd_gh_gm(const PvsBwdPlan& plan, const BwdCall& c, const BwdWs& w, const SavedLayout& sv) {
+    hipStream_t s = c.s;
+    const int H = c.m.H, N = c.m.N;
+    const PvsLayerGrads& gr = c.gr;
+    const float* g_y1 = w.g_u;
+    if (plan.gh_gm == PVS_BWD_GHGM_ONE_PRODUCT) {
+        PvsLinearExt ext = c.prep;
+        ext.y1 = w.gM; ext.ldy1 = H; ext.acc1 = 0;
+        PvsLinearJob both = bwd_both_job(c, w, &ext);
+        both.accumulate = plan.gh_accumulate;
         PVS_TRY(pvs_launch_linear(s, both));
-        prep_done = true;
-    } else {
+    } else if (plan.gh_gm == PVS_BWD_GHGM_TWO_PRODUCTS) {
+        PvsLinearJob gh1 = bwd_gh1_job(c, w);
+        gh1.accumulate = plan.gh_accumulate;
         PVS_TRY(pvs_launch_linear(s, gh1));
-        if (prep_side) gm.ext = &prep;
+        PvsLinearJob gm = bwd_gm_job(c, w);
+        if (plan.prep == PVS_BWD_PREP_SIDE_JOB) gm.ext = &c.prep;
         PVS_TRY(pvs_launch_linear(s, gm));
-        prep_done = prep_side;
     }
-    if (gr.node_w1 && !fused_wgrads) {
-        PVS_TRY(pvs_launch_tsgemm_tn(s, gr.node_w1, 2 * H, g_y1, H, h, H, N, H, H, w.dslabs, false));
-        PVS_TRY(pvs_launch_tsgemm_tn(s, gr.node_w1 + H, 2 * H, g_y1, H, Magg, H, N, H, H, w.dslabs,
+    if (plan.own_node_w1) {
+        PVS_TRY(pvs_launch_tsgemm_tn(s, gr.node_w1, 2 * H, g_y1, H, c.h, H, N, H, H, w.dslabs, false));
+        PVS_TRY(pvs_launch_tsgemm_tn(s, gr.node_w1 + H, 2 * H, g_y1, H, sv.Magg, H, N, H, H, w.dslabs,
                                      false));
     }
-    if (gr.node_b1 && !fused_wgrads)
+    if (plan.own_node_b1)
         PVS_TRY(pvs_launch_colreduce(s, PVS_COL_SUM_A, gr.node_b1, g_y1, H, nullptr, 0, nullptr, N, H,
                                      1.f, w.dslabs, false));
+    return 0;
+}
 
-    // ---- edge backward ----
-    // (MFMA path: rows without edges are never written by the edge kernel: cleared here, unless done above)
-    if (prep_done)
-        PVS_TRY(pvs_prep_edge_bwd(s, g_x_out, g->inv_deg, Magg, w.gM, N, H, nullptr,
-                                  (eatt && soft) ? w.softD : nullptr, nullptr, nullptr));
-    else
-        PVS_TRY(pvs_prep_edge_bwd(s, g_x_out, g->inv_deg, Magg, w.gM, N, H,
-                                  coord_bwd ? w.gxagg : nullptr, (eatt && soft) ? w.softD : nullptr,
-                                  mfma_bwd ? w.gPQ : nullptr, mfma_bwd ? gx_row : nullptr));
+// 4. edge backward and column gather; leaves the two-set slab reduction as a job (tail->edge_red) and runs it where the
+// plan gives it a launch of its own
+int bwd_edges(const PvsBwdPlan& plan, const BwdCall& c, const BwdWs& w, const SavedLayout& sv, BwdTail* tail) {
+    hipStream_t s = c.s;
+    const int H = c.m.H, N = c.m.N;
+    const PvsGraph* g = c.g;
+    // the softmax row dots, and the per-node preparation where no earlier launch carried it as side jobs
+    const PvsLinearExt none;
+    const PvsLinearExt& own = plan.prep == PVS_BWD_PREP_OWN_LAUNCH ? c.prep : none;
+    PVS_TRY(pvs_prep_edge_bwd(s, c.g_x_out, g->inv_deg, sv.Magg, w.gM, N, H, own.scale3_dst,
+                              plan.soft_dots ? w.softD : nullptr, own.zero_rows, own.zero3));
     PvsEdgeBwdIO io;
-    io.PQ = sPQ; io.x = x; io.m_prev = m_prev; io.att = att; io.gM = w.gM;
-    io.gxagg = coord_bwd ? w.gxagg : nullptr;
-    io.softD = (eatt && soft) ? w.softD : nullptr;
-    io.g_m_out = g_m_out; io.gPQ = w.gPQ; io.gz1 = w.gz1; io.gd = w.gd; io.gx_row = gx_row;
-    io.g_m_prev = eres ? g_m_prev : nullptr; io.slabs = w.eslabs; io.wpair = w.wpair;
-    int n_slabs = 0;
+    io.PQ = sv.PQ; io.x = c.x; io.m_prev = c.m_prev; io.att = c.att; io.gM = w.gM;
+    io.gxagg = plan.coord_bwd ? w.gxagg : nullptr;
+    io.softD = plan.soft_dots ? w.softD : nullptr;
+    io.g_m_out = c.g_m_out; io.gPQ = w.gPQ; io.gz1 = w.gz1; io.gd = w.gd; io.gx_row = c.gx_row;
+    io.g_m_prev = plan.edge_res ? c.g_m_prev : nullptr; io.slabs = w.eslabs; io.wpair = w.wpair;
+    const PvsEdgeW ew = make_edge_w(c.m, c.p);
+    int n_slabs = 0, n_nslabs = 0;
+    if (plan.mfma_bwd)
+        PVS_TRY(pvs_launch_edge_bwd_mfma(s, H, plan.fam, *g, ew, c.d->flags, c.d->att_act, io, 0, c.m.E, &n_slabs));
+    else
+        PVS_TRY(pvs_launch_edge_bwd_v0(s, H, *g, ew, c.d->flags, c.d->att_act, io, &n_slabs));
+    // (c.gx_row is w.gx_row whenever the generic family runs: the first-layer pair belongs to the split family)
+    PVS_TRY(pvs_launch_node_gather(s, H, *g, plan.mfma_bwd, w.gz1, w.gd, c.gx_row, c.g_x_out, w.gPQ, c.g_x,
+                                   w.nslabs, 0, N, &n_nslabs));
     const PvsSlabLayout L = pvs_slab_layout(H);
-    int n_nslabs = 0;
-    if (mfma_bwd) {
-        PVS_TRY(pvs_launch_edge_bwd_mfma(s, H, fam, *g, ew, F, d->att_act, io, 0, m.E, &n_slabs));
-        PVS_TRY(pvs_launch_node_gather(s, H, *g, true, w.gz1, w.gd, gx_row, g_x_out, w.gPQ, g_x,
-                                       w.nslabs, 0, N, &n_nslabs));
-    } else {
-        PVS_TRY(pvs_launch_edge_bwd_v0(s, H, *g, ew, F, d->att_act, io, &n_slabs));
-        PVS_TRY(pvs_launch_node_gather(s, H, *g, false, w.gz1, w.gd, w.gx_row, g_x_out, w.gPQ, g_x,
-                                       w.nslabs, 0, N, &n_nslabs));
-    }
-    // g_wrho / g_wattr come from the node gather: its slab layout [wrho | wattr0 | wattr1 | wattr2]
-    // == gsum[L.wrho .. L.wrho + 4H), which the edge slabs leave alone (one reduction for both). With the fused
-    // weight-gradient pass below that reduction rides on ITS launch as extra workgroups (independent work), and the
-    // pass's own slab reduction on the finalize launch: three launches at the end of a layer instead of five.
-    PvsReduce2Args edge_red;
-    edge_red.out_a = w.gsum; edge_red.slabs_a = w.eslabs; edge_red.n_a = n_slabs; edge_red.width_a = L.total;
-    edge_red.skip_lo = L.wrho; edge_red.skip_hi = L.wrho + 4 * H;
-    edge_red.out_b = w.gsum + L.wrho; edge_red.slabs_b = w.nslabs; edge_red.n_b = n_nslabs; edge_red.width_b = 4 * H;
-    const bool tail_folded = mfma_bwd && fused_wgrads && !split_small;
-    if (mfma_bwd && !tail_folded) {
-        PVS_TRY(pvs_launch_reduce_slabs2(s, w.gsum, w.eslabs, n_slabs, L.total, L.wrho, L.wrho + 4 * H,
-                                         w.gsum + L.wrho, w.nslabs, n_nslabs, 4 * H));
-    } else if (!mfma_bwd) {
+    PvsReduce2Args& r = tail->edge_red;
+    r.out_a = w.gsum; r.slabs_a = w.eslabs; r.n_a = n_slabs; r.width_a = L.total;
+    r.skip_lo = L.wrho; r.skip_hi = L.wrho + 4 * H;
+    r.out_b = w.gsum + L.wrho; r.slabs_b = w.nslabs; r.n_b = n_nslabs; r.width_b = 4 * H;
+    if (plan.slab_reduce == PVS_BWD_REDUCE_TWO_SETS)
+        PVS_TRY(pvs_launch_reduce_slabs2(s, r.out_a, r.slabs_a, r.n_a, r.width_a, r.skip_lo, r.skip_hi, r.out_b, r.slabs_b,
+                                         r.n_b, r.width_b));
+    else if (plan.slab_reduce == PVS_BWD_REDUCE_ONE_SET)
         PVS_TRY(pvs_launch_reduce_slabs(s, w.gsum, L.total, L.total, w.eslabs, n_slabs, L.total, false));
-    }
+    return 0;
+}
 
-    // ---- first edge-MLP layer at node level: P = W1a h + b1, Q = W1b h ----
-    // g_h += g_P W1a + g_Q W1b: one launch with the two (input, weight) pairs
-    // (with the folded tail it is a role of the weight-gradient launch below)
-    const bool gh_folded = tail_folded && (((uintptr_t)g_h | (uintptr_t)w.gPQ) & 15) == 0;
+// 5. first edge-MLP layer at node level (P = W1a h + b1, Q = W1b h): g_h += g_P W1a + g_Q W1b, and the weight-gradient
+// tail - the fused pass with the roles the plan folds into it, or the unfused products of edge_mlp.0
+int bwd_weight_tail(const PvsBwdPlan& plan, const BwdCall& c, const BwdWs& w, const SavedLayout& sv, BwdTail* tail) {
+    hipStream_t s = c.s;
+    const Dims& m = c.m;
+    const int H = m.H, N = m.N;
+    const PvsLayerGrads& gr = c.gr;
     PvsGhJob ghj;
-    ghj.g_h = g_h; ghj.gPQ = w.gPQ; ghj.W1 = p->edge_w1; ghj.ld1 = m.ld1; ghj.off_q = m.off_q;
-    if (!gh_folded) PVS_TRY(pvs_launch_linear(s, pvs_gh_linear_job(ghj, N, H)));
-    const float* node_gsum = nullptr;
-    PvsNodeWgradSlabs node_slabs;
-    PvsNodeWgradOut node_out{};
-    if (fused_wgrads) {
+    ghj.g_h = c.g_h; ghj.gPQ = w.gPQ; ghj.W1 = c.p->edge_w1; ghj.ld1 = m.ld1; ghj.off_q = m.off_q;
+    if (!plan.gh_folded) PVS_TRY(pvs_launch_linear(s, pvs_gh_linear_job(ghj, N, H)));
+    if (plan.fused_wgrads) {
         PvsNodeWgradIn wi;
-        wi.g_o = g_o; wi.g_y1 = g_y1; wi.gPQ = w.gPQ; wi.u = su; wi.h = h; wi.Magg = Magg;
+        wi.g_o = c.g_o; wi.g_y1 = w.g_u; wi.gPQ = w.gPQ; wi.u = sv.u; wi.h = c.h; wi.Magg = sv.Magg;
         PvsNodeWgradOut wo;
         wo.node_w2 = gr.node_w2; wo.node_w1 = gr.node_w1; wo.edge_w1 = gr.edge_w1;
         wo.node_b2 = gr.node_b2; wo.node_b1 = gr.node_b1; wo.edge_b1 = gr.edge_b1;
         wo.ld1 = m.ld1; wo.off_q = m.off_q; wo.perm = m.perm ? 1 : 0;
-        if (gate_in_wgrads) { wi.t1 = w.t1; wi.gl = w.gl; wo.natt_w = gr.node_att_w; wo.natt_b = gr.node_att_b; }
-        if (tail_folded)
-            PVS_TRY(pvs_launch_node_wgrads(s, H, N, wi, wo, w.wslabs, /*scatter=*/false, nullptr, &edge_red, &node_slabs,
-                                           gh_folded ? &ghj : nullptr));
+        if (plan.gate_in_wgrads) { wi.t1 = w.t1; wi.gl = w.gl; wo.natt_w = gr.node_att_w; wo.natt_b = gr.node_att_b; }
+        if (plan.tail_folded)
+            PVS_TRY(pvs_launch_node_wgrads(s, H, N, wi, wo, w.wslabs, /*scatter=*/false, nullptr, &tail->edge_red,
+                                           &tail->node_slabs, plan.gh_folded ? &ghj : nullptr));
         else
-            PVS_TRY(pvs_launch_node_wgrads(s, H, N, wi, wo, w.wslabs, /*scatter=*/false, &node_gsum));
-        node_out = wo;
+            PVS_TRY(pvs_launch_node_wgrads(s, H, N, wi, wo, w.wslabs, /*scatter=*/false, &tail->node_gsum));
+        tail->node_out = wo;
     }
-    if (gr.edge_w1 && !fused_wgrads) {
-        PVS_TRY(pvs_launch_tsgemm_tn(s, gr.edge_w1, m.ld1, w.gPQ, 2 * H, h, H, N, H, H, w.dslabs,
+    if (plan.own_edge_w1) {
+        PVS_TRY(pvs_launch_tsgemm_tn(s, gr.edge_w1, m.ld1, w.gPQ, 2 * H, c.h, H, N, H, H, w.dslabs,
                                      false));
-        PVS_TRY(pvs_launch_tsgemm_tn(s, gr.edge_w1 + m.off_q, m.ld1, w.gPQ + H, 2 * H, h, H, N, H, H,
+        PVS_TRY(pvs_launch_tsgemm_tn(s, gr.edge_w1 + m.off_q, m.ld1, w.gPQ + H, 2 * H, c.h, H, N, H, H,
                                      w.dslabs, m.perm));
     }
-    if (gr.edge_b1 && !fused_wgrads)
+    if (plan.own_edge_b1)
         PVS_TRY(pvs_launch_colreduce(s, PVS_COL_SUM_A, gr.edge_b1, w.gPQ, 2 * H, nullptr, 0, nullptr,
                                      N, H, 1.f, w.dslabs, false));
-    const int node_blocks = node_slabs.slabs ? (node_slabs.width + 31) / 32 : 0;
-    // (a graph without edges: the caller's [0, H] m_prev has no device pointer, yet the edge gate is a parameter of the
-    // layer and its gradient - the sum over no edges - is 0, not whatever the caller's buffer held)
-    const bool gate_grad = eres || ((F & PVS_EDGE_RESIDUAL) && m.E == 0);
-    k_finalize_edge_grads<<<node_blocks + (H * H / 256 > 4 ? H * H / 256 : 4), 256, 0, s>>>(
-        w.gsum, L, H, m.A, m.ld1, m.off_rho, gr, coord_bwd ? 1 : 0, eatt ? (soft ? 2 : 1) : 0,
-        (gate_grad && (F & (PVS_REZERO | PVS_GATED_RESIDUAL))) ? 1 : 0, node_gsum, node_out, node_slabs, node_blocks);
-    PVS_CHECK_LAUNCH();
-    // GraphNorm: node_mlp.0.bias from the closed form of k_gn_bwd_coefs instead of the column sum of g_y1
-    if (gn && gr.node_b1) PVS_TRY(pvs_copy_small(s, w.coefs + 3 * H, gr.node_b1, H));
     return 0;
 }
+
+// 6. scatter the reduced sums into the parameter gradients
+int bwd_finalize(const PvsBwdPlan& plan, const BwdCall& c, const BwdWs& w, const BwdTail& tail) {
+    hipStream_t s = c.s;
+    const Dims& m = c.m;
+    const int H = m.H;
+    const int node_blocks = tail.node_slabs.slabs ? (tail.node_slabs.width + 31) / 32 : 0;
+    k_finalize_edge_grads<<<node_blocks + (H * H / 256 > 4 ? H * H / 256 : 4), 256, 0, s>>>(
+        w.gsum, pvs_slab_layout(H), H, m.A, m.ld1, m.off_rho, c.gr, plan.coord_bwd ? 1 : 0, plan.has_att,
+        plan.has_gate ? 1 : 0, tail.node_gsum, tail.node_out, tail.node_slabs, node_blocks);
+    PVS_CHECK_LAUNCH();
+    if (plan.node_b1_from_coefs) PVS_TRY(pvs_copy_small(s, w.coefs + 3 * H, c.gr.node_b1, H));
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int pvs_egnn_layer_bwd(const PvsLayerDesc* d, const PvsGraph* g, const PvsLayerParams* p,
+                                  const float* h, const float* x, const float* m_prev,
+                                  const float* att, const float* saved, const float* g_h_out,
+                                  const float* g_x_out, const float* g_m_out, float* g_h, float* g_x,
+                                  float* g_m_prev, const PvsLayerGrads* gr_, void* workspace,
+                                  size_t workspace_bytes, pvs_stream_t stream_) {
+    PVS_TRY(check_desc(d, g, p));
+    PVS_REQUIRE(h && x && saved && g_h_out && g_h && gr_, "pvs_egnn_layer_bwd: NULL tensor");
+    PVS_REQUIRE(g->n_edges == 0 || (g->colptr && g->cedge),
+                "pvs_egnn_layer_bwd: graph was built without the by-column lists (forward-only)");
+    const uint32_t F = d->flags;
+    const bool eatt = F & PVS_EDGE_ATTENTION;
+    const bool eres = (F & PVS_EDGE_RESIDUAL) && m_prev;
+    PVS_REQUIRE(!eatt || att, "pvs_egnn_layer_bwd: att required with edge attention");
+    PVS_REQUIRE(!eres || g_m_prev, "pvs_egnn_layer_bwd: g_m_prev required with edge residual");
+    const Dims m = make_dims(d, g);
+    PvsArena arena(workspace, workspace_bytes);
+    BwdWs w;
+    carve_bwd(arena, m, &w);
+    PVS_REQUIRE(arena.ok(), "pvs_egnn_layer_bwd: workspace too small (%zu < %zu)", workspace_bytes,
+                arena.off);
+    const int H = m.H;
+    // (PQ, y1, o and u = SiLU(GN(y1)) were kept by the forward)
+    const SavedLayout sv = saved_layout(const_cast<float*>(saved), m.N, H);      // read-only here
+    BwdCall c{(hipStream_t)stream_, d, g, p, m, h, x, m_prev, att, g_h_out, g_x_out, g_m_out, g_h, g_x, g_m_prev, *gr_,
+              make_node_w(d, p), nullptr, nullptr, PvsLinearExt{}};
+    const PvsLayerGrads& gr = c.gr;
+
+    PvsBwdFacts f;
+    f.H = H; f.flags = F; f.n_attr = m.A;
+    f.has_m_prev = m_prev != nullptr; f.has_g_x_out = g_x_out != nullptr; f.has_g_x = g_x != nullptr;
+    f.no_edges = m.E == 0;
+    f.gr_node_w2 = gr.node_w2; f.gr_node_b2 = gr.node_b2; f.gr_node_w1 = gr.node_w1; f.gr_node_b1 = gr.node_b1;
+    f.gr_edge_w1 = gr.edge_w1; f.gr_edge_b1 = gr.edge_b1;
+    f.gr_node_att_w = gr.node_att_w; f.gr_node_att_b = gr.node_att_b; f.gr_node_gate = gr.node_gate;
+    f.wgrads_supported = pvs_node_wgrads_supported(H);
+    f.mlp_fused_ok = pvs_node_mlp_fused_supported(H, g_h_out, sv.y1, w.g_u, g_h);
+    f.chain_aligned = (((uintptr_t)w.gM | (uintptr_t)w.gPQ | (uintptr_t)sv.o | (uintptr_t)w.g_o | (uintptr_t)w.t1) & 15) == 0;
+    f.gu_epilogue_ok = pvs_linear_epilogue_supported(bwd_gu_job(c, w, sv, w.g_o));
+    f.gu_passthrough_epilogue_ok = pvs_linear_epilogue_supported(bwd_gu_job(c, w, sv, g_h_out));
+    f.gm_epilogue_ok = pvs_linear_epilogue_supported(bwd_gm_job(c, w));
+    f.both_epilogue_ok = pvs_linear_epilogue_supported(bwd_both_job(c, w, &c.prep));
+    f.sy1_aligned = ((uintptr_t)sv.y1 & 15) == 0;
+    f.gpq_aligned = ((uintptr_t)w.gPQ & 15) == 0;
+    f.gh_gpq_aligned = (((uintptr_t)g_h | (uintptr_t)w.gPQ) & 15) == 0;
+    f.sw = pvs_layer_switches();
+    const PvsBwdPlan plan = pvs_layer_bwd_plan(f);
+
+    c.g_o = plan.g_o_is_g_h_out ? g_h_out : w.g_o;
+    c.gx_row = plan.first_layer ? nullptr : w.gx_row;
+    pvs_note_edge_bwd_variant(plan.first_layer ? PVS_EDGE_BWD_FIRST_LAYER : PVS_EDGE_BWD_GENERAL);
+    if (plan.mfma_bwd) { c.prep.zero_rows = w.gPQ; c.prep.zero_w = H; c.prep.zero_ld = 2 * H; c.prep.zero3 = c.gx_row; }
+    if (plan.coord_bwd) { c.prep.scale3_src = g_x_out; c.prep.scale3_by = g->inv_deg; c.prep.scale3_dst = w.gxagg; }
+
+    BwdTail tail;
+    PVS_TRY(bwd_output_stage(plan, c, w, sv));
+    PVS_TRY(bwd_node_mlp_to_gy1(plan, c, w, sv));
+    PVS_TRY(bwd_gh_gm(plan, c, w, sv));
+    PVS_TRY(bwd_edges(plan, c, w, sv, &tail));
+    PVS_TRY(bwd_weight_tail(plan, c, w, sv, &tail));
+    return bwd_finalize(plan, c, w, tail);
+}
+
 
 // ---- the whole EGNNLayer stack as one call each way (include/pvs_egnn.h: pvs_egnn_stack_*) -------------------------------
 // SartorrasEGNN.get_embeddings loops `for layer in self.layers` (egnn_satorras.py:325-328); at the reference's default shape

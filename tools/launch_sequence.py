@@ -1,7 +1,10 @@
 """(GPU) The kernels a layer enqueues, in order, with their grids: the record that a host-side change left every launch alone.
 Runs one training step through the per-layer calls and one through the stack calls for each hidden size 16 / 32 / 64 /
-128 and four flag sets (plain; GraphNorm + both attentions + residual; gated residual; node attention + residual) on one
-small two-graph batch. Under a kernel trace, once per library and once more with PVS_EGNN_SPLIT_SMALL=1:
+128 and ten flag sets (plain; GraphNorm + both attentions + residual; gated residual; node attention + residual; softmax
+attention; edge residual plain and with rezero - the per-layer path both times; GraphNorm alone; no coordinate update)
+on one small two-graph batch, and the per-layer step once more with the input coordinates requiring a gradient (the
+first layer then takes the general backward pair). Under a kernel trace, once per library and once more under each of
+PVS_EGNN_SPLIT_SMALL=1 and PVS_EGNN_SPLIT_WGRADS=1 (profiles/layer_backward_plan.txt):
     PVS_EGNN_LIB=<library> rocprofv3 --kernel-trace --output-format csv -d DIR -- python tools/launch_sequence.py
     python tools/launch_sequence.py --parse DIR OUT.txt      # one line per launch: name, grid, workgroup, LDS
 Two libraries enqueue the same work when their OUT.txt files are equal (profiles/linear_job_refactor.txt).
@@ -25,6 +28,11 @@ FLAGS = {
     'attn_gn': dict(graphnorm=True, node_attention=True, edge_attention=True, residual=True),
     'gated': dict(residual=True, gated_residual=True),
     'natt_res': dict(node_attention=True, residual=True),
+    'softmax': dict(edge_attention=True, softmax_attention=True),
+    'eres': dict(edge_residual=True),
+    'eres_rezero': dict(edge_residual=True, rezero=True, residual=True),
+    'gn': dict(graphnorm=True),
+    'nocoords': dict(update_coords=False),
 }
 
 
@@ -50,8 +58,10 @@ def run(fp64=False):
             model.train()
             if fp64:
                 model.double()
-            for stack in ('0',) if fp64 else ('0', '1'):
-                os.environ['PVS_EGNN_STACK'] = stack
+            # ('0x': the per-layer calls with g_x asked of the first layer too)
+            for stack in ('0',) if fp64 else ('0', '1', '0x'):
+                os.environ['PVS_EGNN_STACK'] = stack[0]
+                g.pos = g.pos.detach().requires_grad_(stack == '0x')
                 model.optimiser.zero_grad()
                 y = model(g).reshape(-1)
                 model.get_loss(torch.ones_like(y), y).backward()
