@@ -426,6 +426,30 @@ int pvs_screen_graph_build_struck(const float* lig_pos, const int32_t* lig_ptr, 
                                   const PvsRaggedNodeTables* tables, int32_t* status, void* state, size_t state_bytes,
                                   pvs_stream_t stream);
 
+/* Cropped slots: pvs_screen_graph_build_ragged_cap where slot p keeps receptor atom j only if one of the slot's ligand
+ * atoms is closer to it than crop_radius (> 0) - the crop of the training loader (data_loaders.py: make_box with
+ * relative_to_ligand) per pose: fp64 on the fp32 coordinates, `<` strict and without a lower bound (a coincident atom is
+ * kept); an empty slot keeps nothing. keep [n_slots, ceil(n_rec / 64)] (uint64, DEVICE, an output): bit j % 64 of word
+ * j / 64 of row p is set for a kept atom. A slot owns its ligand atoms, then its kept receptor atoms in receptor order,
+ * compact: node_ptr[p + 1] = node_ptr[p] + n_lig_p + kept_p, padding from node_ptr[n_slots] up to N_cap = lig_cap +
+ * n_slots * n_rec as above. The slot's graph is generate_edges on the cropped complex: ligand-touching edges by
+ * distance, to kept atoms only (crop_radius may be below an edge radius); receptor-receptor edges from the template
+ * where both ends are kept, renumbered by rank in the mask, no distance evaluated. Written: the full CSR (rowptr, row,
+ * col, etype, inv_deg; edge count in rowptr[N_cap]), node_ptr, node_graph, pos, keep and tables->feats. NOT written:
+ * the ligand-touching CSR (rowptr_lig .. etype_lig and capacity_lig are ignored and may be NULL / 0) and the base_*
+ * tables (a row at the rim of the crop has lost template neighbours, so the receptor's first-layer sums are not its
+ * sums). `capacity` as for the uncropped call bounds the cropped graph, which is a subset. *status as above. No
+ * atomics: the same bits on every run. */
+size_t pvs_screen_graph_cropped_state_bytes(int32_t n_slots, int32_t lig_cap, int32_t n_rec, int32_t slot_cap);
+int pvs_screen_graph_build_cropped(const float* lig_pos, const int32_t* lig_ptr, const float* rec_pos,
+                                   const int32_t* rr_rowptr, const int32_t* rr_col, int32_t n_slots, int32_t lig_cap,
+                                   int32_t n_rec, int32_t slot_cap, double inter_radius, double intra_radius,
+                                   double crop_radius, int32_t capacity, int32_t capacity_lig, int32_t* rowptr,
+                                   int32_t* row, int32_t* col, uint8_t* etype, float* inv_deg, int32_t* rowptr_lig,
+                                   int32_t* row_lig, int32_t* col_lig, uint8_t* etype_lig, int32_t* node_ptr,
+                                   int32_t* node_graph, float* pos, uint64_t* keep, const PvsRaggedNodeTables* tables,
+                                   int32_t* status, void* state, size_t state_bytes, pvs_stream_t stream);
+
 /* Complex batches: the node tables of B protein-ligand complexes built from a device-resident pool of structure
  * files, as the reference loader builds one sample on the host (data_loaders.py:259-309: ligand then receptor, crop of
  * the receptor to the atoms closer than `radius` to some ligand atom - fp64, scipy's cdist decision -, hydrogen filter

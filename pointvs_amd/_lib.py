@@ -131,6 +131,11 @@ _PROTOTYPES = {
                                                                                      C.c_int32] +
                                       [C.c_void_p] * 12 + [C.POINTER(PvsRaggedNodeTables), C.c_void_p, C.c_void_p,
                                                            C.c_size_t, C.c_void_p]),
+    'pvs_screen_graph_cropped_state_bytes': (C.c_size_t, [C.c_int32] * 4),
+    'pvs_screen_graph_build_cropped': (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 4 + [C.c_double] * 3 +
+                                       [C.c_int32, C.c_int32] + [C.c_void_p] * 13 +
+                                       [C.POINTER(PvsRaggedNodeTables), C.c_void_p, C.c_void_p, C.c_size_t,
+                                        C.c_void_p]),
     'pvs_mask_graph_workspace_bytes': (C.c_size_t, [C.c_int32, C.c_int32]),
     'pvs_mask_graph_build': (C.c_int, [C.POINTER(PvsGraph), C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32] +
                              [C.c_void_p] * 9 + [C.c_void_p, C.c_size_t, C.c_void_p]),

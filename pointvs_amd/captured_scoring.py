@@ -102,8 +102,9 @@ def _kernel_width(hidden):
     return next((w for w in (16, 32, 64, 128) if w >= hidden), None)
 
 
-def refusal(model, dataset):
-    """Why the fixed-shape step cannot score `dataset` with `model`, or None. Host checks only."""
+def model_refusal(model):
+    """Why no step that leaves its edge count on the device can run `model`, or None: the model's part of `refusal`,
+    which the cropped library screen asks as well. Host checks only."""
     if any(p.dtype == torch.float64 for p in model.parameters()):
         return 'fp64 models (no fp64 layer takes a device-side edge count): score them without capture'
     layers = list(model.layers)[1:]
@@ -118,6 +119,14 @@ def refusal(model, dataset):
                 or (layer.hidden_nf > 64 and os.environ.get('PVS_WIDE') == 'decomposed')):
             return (f'hidden size {layer.hidden_nf} runs on the generic edge kernels, which need a host-known edge count '
                     '(the MFMA kernels cover 17..128 channels)')
+    return None
+
+
+def refusal(model, dataset):
+    """Why the fixed-shape step cannot score `dataset` with `model`, or None. Host checks only."""
+    why = model_refusal(model)
+    if why is not None:
+        return why
     if getattr(dataset, 'rot', False):
         return 'a dataset with rot=True (scoring loaders do not rotate)'
     if len(dataset) and dataset.is_augmented(len(dataset) - 1):

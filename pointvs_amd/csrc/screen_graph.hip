@@ -27,6 +27,9 @@ typedef unsigned long long u64;
 // Struck slots (PvsStruckSlots: a slot's receptor may lack one atom) run through the same kernels; what they do
 // differently is compiled only for that layout.
 template <class Slots> constexpr bool kStruck = std::is_same<Slots, PvsStruckSlots>::value;
+// Cropped slots (PvsCroppedSlots: a slot's receptor is the subset its keep mask names) likewise. Their builder writes
+// the full CSR only: what concerns the ligand-touching CSR is compiled out for that layout.
+template <class Slots> constexpr bool kCropped = std::is_same<Slots, PvsCroppedSlots>::value;
 
 // wave per packed ligand atom q: contact masks against the receptor (64 atoms per word) and the atom's own ligand
 // (W words per atom; trip w, lane l: the slot's atom 64 w + l)
@@ -60,7 +63,12 @@ k_contacts(const float* __restrict__ lig_pos, const float* __restrict__ rec_pos,
                 ea = below(s, r_intra);
             }
         }
-        const u64 bi = __ballot(ei), ba = __ballot(ea);
+        u64 bi = __ballot(ei), ba = __ballot(ea);
+        if constexpr (kCropped<Slots>) {                  // contacts with the slot's kept atoms only
+            const u64 kw = L.keep_word_of_atom(q, c);
+            bi &= kw;
+            ba &= kw;
+        }
         if (lane == 0) {
             m_inter[(size_t)q * n_chunks + c] = bi;
             m_intra[(size_t)q * n_chunks + c] = ba;
@@ -97,7 +105,11 @@ __global__ void k_degrees(const u64* __restrict__ m_inter, const u64* __restrict
     if (g > L.rows()) return;
     PvsSlotRow r = {};
     if (g < L.rows()) r = L.row(g);
-    if (!r.valid) { deg[g] = 0; deg_l[g] = 0; return; }
+    if (!r.valid) {
+        deg[g] = 0;
+        if constexpr (!kCropped<Slots>) deg_l[g] = 0;
+        return;
+    }
     const int n_chunks = (L.n_rec + 63) / 64;
     if (r.local < r.n_lig) {
         const size_t w = (size_t)r.a0 + r.local;
@@ -105,10 +117,11 @@ __global__ void k_degrees(const u64* __restrict__ m_inter, const u64* __restrict
         const int d = row_popc(m_inter + w * n_chunks, n_chunks) + row_popc(m_ll + w * W, W) +
                       row_popc(m_intra + w * n_chunks, n_chunks);
         deg[g] = d;
-        deg_l[g] = d;
+        if constexpr (!kCropped<Slots>) deg_l[g] = d;
     } else {
         int i = r.local - r.n_lig;
         if constexpr (kStruck<Slots>) i = pvs_struck_receptor(i, r.drop);
+        if constexpr (kCropped<Slots>) i = L.receptor(r.slot, i);
         const int c = i >> 6;
         const u64 bit = 1ull << (i & 63);
         int nl = 0;
@@ -123,7 +136,13 @@ __global__ void k_degrees(const u64* __restrict__ m_inter, const u64* __restrict
             touched = r.drop >= 0 && pvs_find_ascending(rr_col + rr_rowptr[i], rr, r.drop) >= 0;
             rr -= touched ? 1 : 0;
         }
-        deg_l[g] = touched ? nl + rr : nl;
+        if constexpr (kCropped<Slots>) {                  // the template neighbours that the slot keeps
+            const int r0 = rr_rowptr[i], n = rr;
+            rr = 0;
+            for (int k = 0; k < n; ++k) rr += L.kept(r.slot, rr_col[r0 + k]) ? 1 : 0;
+        } else {
+            deg_l[g] = touched ? nl + rr : nl;
+        }
         deg[g] = nl + rr;
     }
 }
@@ -145,7 +164,12 @@ k_fill(const u64* __restrict__ m_inter, const u64* __restrict__ m_intra, const u
     const int g = (blockIdx.x * 256 + threadIdx.x) >> 6;
     const int N = L.rows();
     if (g >= N) return;
-    if (full.rowptr[N] > full.capacity || lig.rowptr[N] > lig.capacity) {
+    if constexpr (kCropped<Slots>) {
+        if (full.rowptr[N] > full.capacity) {
+            if (g == 0 && lane == 0) *status |= 4;        // (the word's one writer in this launch)
+            return;
+        }
+    } else if (full.rowptr[N] > full.capacity || lig.rowptr[N] > lig.capacity) {
         if (g == 0 && lane == 0) atomicOr(status, 4);
         return;
     }
@@ -158,18 +182,22 @@ k_fill(const u64* __restrict__ m_inter, const u64* __restrict__ m_intra, const u
     const int n_chunks = (L.n_rec + 63) / 64, W = L.words();
     const int trips = pvs_slot_words(n_lig);               // the words that this slot's atoms reach (<= W)
     const u64 lower = (1ull << lane) - 1ull;
-    int pf = full.rowptr[g], pl = lig.rowptr[g];
+    int pf = full.rowptr[g], pl = 0;
+    if constexpr (!kCropped<Slots>) pl = lig.rowptr[g];
     if (lane == 0) {
         const int d = full.rowptr[g + 1] - pf;
         inv_deg[g] = 1.0f / (float)(d > 1 ? d : 1);
     }
     auto emit = [&](int off, int column, int cls, bool also_lig) {
         full.row[pf + off] = g; full.col[pf + off] = column; full.etype[pf + off] = (uint8_t)cls;
-        if (also_lig) { lig.row[pl + off] = g; lig.col[pl + off] = column; lig.etype[pl + off] = (uint8_t)cls; }
+        if constexpr (!kCropped<Slots>) {
+            if (also_lig) { lig.row[pl + off] = g; lig.col[pl + off] = column; lig.etype[pl + off] = (uint8_t)cls; }
+        }
     };
     auto expand_words = [&](const u64* __restrict__ m, int col0, int cls) {
         const int done = pvs_expand_mask_row(m, n_chunks, lane, [&](int k, int b) {
             if constexpr (kStruck<Slots>) b = pvs_struck_row(b, r.drop);
+            if constexpr (kCropped<Slots>) b = L.receptor_row(r.slot, b);     // (the masks hold kept atoms only)
             emit(k, col0 + b, cls, true);
         });
         pf += done;
@@ -190,6 +218,7 @@ k_fill(const u64* __restrict__ m_inter, const u64* __restrict__ m_intra, const u
     } else {
         int i = r.local - n_lig;
         if constexpr (kStruck<Slots>) i = pvs_struck_receptor(i, r.drop);
+        if constexpr (kCropped<Slots>) i = L.receptor(r.slot, i);
         const int c = i >> 6;
         const u64 bit = 1ull << (i & 63);
         for (int kind = 0; kind < 2; ++kind) {                                // inter block, then intra: ligand atoms
@@ -205,7 +234,17 @@ k_fill(const u64* __restrict__ m_inter, const u64* __restrict__ m_intra, const u
             pf += cnt; pl += cnt;
         }
         const int r0 = rr_rowptr[i], r1 = rr_rowptr[i + 1];                   // intra block: receptor atoms
-        if (!kStruck<Slots> || r.drop < 0) {
+        if constexpr (kCropped<Slots>) {   // the template neighbours that the slot keeps, renumbered by their rank
+            int cnt = 0;
+            for (int k0 = 0; k0 < r1 - r0; k0 += 64) {
+                const int k = k0 + lane;
+                const int j = k < r1 - r0 ? rr_col[r0 + k] : -1;
+                const bool on = j >= 0 && L.kept(r.slot, j);
+                const u64 b = __ballot(on);
+                if (on) emit(cnt + __popcll(b & lower), node0 + n_lig + L.receptor_row(r.slot, j), 2, false);
+                cnt += __popcll(b);
+            }
+        } else if (!kStruck<Slots> || r.drop < 0) {
             for (int k = lane; k < r1 - r0; k += 64) emit(k, node0 + n_lig + rr_col[r0 + k], 2, false);
         } else {                        // without the struck atom; a row that had it is written to both CSRs
             const int at = pvs_find_ascending(rr_col + r0, r1 - r0, r.drop);
@@ -219,15 +258,17 @@ k_fill(const u64* __restrict__ m_inter, const u64* __restrict__ m_intra, const u
 }
 
 // the builder's scratch: contact masks per packed atom (n_chunks receptor words each, `words` ligand words), degrees
-// per row; slot_of (atom -> slot) for the ragged layout
+// per row; slot_of (atom -> slot) for the ragged layout; keep_rank (crop_slots slots of n_chunks + 1 entries) for the
+// cropped layout, which has no second degree table
 struct ScreenState {
     u64 *m_inter, *m_intra, *m_ll;
-    int32_t *deg, *deg_l, *slot_of;
+    int32_t *deg, *deg_l, *slot_of, *keep_rank;
     void* scan_tmp;
     size_t scan_bytes;
 };
 
-size_t carve_screen(PvsArena& a, size_t atoms, int rows, int n_rec, int words, bool ragged, ScreenState* out) {
+size_t carve_screen(PvsArena& a, size_t atoms, int rows, int n_rec, int words, bool ragged, ScreenState* out,
+                    int crop_slots = 0) {
     ScreenState t;
     const size_t n_chunks = (size_t)(n_rec + 63) / 64;
     t.m_inter = a.take<u64>(atoms * n_chunks);
@@ -235,7 +276,8 @@ size_t carve_screen(PvsArena& a, size_t atoms, int rows, int n_rec, int words, b
     t.m_ll = a.take<u64>(atoms * (size_t)words);
     t.slot_of = ragged ? a.take<int32_t>(atoms) : nullptr;
     t.deg = a.take<int32_t>((size_t)rows + 1);
-    t.deg_l = a.take<int32_t>((size_t)rows + 1);
+    t.deg_l = crop_slots ? nullptr : a.take<int32_t>((size_t)rows + 1);
+    t.keep_rank = crop_slots ? a.take<int32_t>((size_t)crop_slots * (n_chunks + 1)) : nullptr;
     size_t sb = 0;
     (void)hipcub::DeviceScan::ExclusiveSum(nullptr, sb, (const int32_t*)nullptr, (int32_t*)nullptr, rows + 1);
     t.scan_bytes = sb;
@@ -260,8 +302,10 @@ int build_csrs(const Slots& L, const float* lig_pos, const float* rec_pos, const
     PVS_CHECK_LAUNCH();
     size_t sb = w.scan_bytes;
     PVS_CHECK_HIP(hipcub::DeviceScan::ExclusiveSum(w.scan_tmp, sb, w.deg, rowptr, N + 1, s));
-    sb = w.scan_bytes;
-    PVS_CHECK_HIP(hipcub::DeviceScan::ExclusiveSum(w.scan_tmp, sb, w.deg_l, rowptr_lig, N + 1, s));
+    if constexpr (!kCropped<Slots>) {
+        sb = w.scan_bytes;
+        PVS_CHECK_HIP(hipcub::DeviceScan::ExclusiveSum(w.scan_tmp, sb, w.deg_l, rowptr_lig, N + 1, s));
+    }
     k_fill<<<(N + 3) / 4, 256, 0, s>>>(w.m_inter, w.m_intra, w.m_ll, rr_rowptr, rr_col, L, full, lig, inv_deg, status);
     PVS_CHECK_LAUNCH();
     return 0;
@@ -385,6 +429,9 @@ k_node_tables_ragged(const float* __restrict__ lig_pos, const float* __restrict_
     int lig_row = -1, rec_row = -1;                        // padding: every table zero
     if (r.valid) {
         if (r.local < r.n_lig) lig_row = r.a0 + r.local; else rec_row = r.local - r.n_lig;
+    }
+    if constexpr (kCropped<Slots>) {                      // (the k-th kept atom; the cropped builder has no base tables)
+        if (rec_row >= 0) rec_row = L.receptor(r.slot, rec_row);
     }
     bool based = rec_row >= 0;                            // the row starts from the receptor's cached sums
     if constexpr (kStruck<Slots>) {
@@ -536,4 +583,137 @@ extern "C" int pvs_screen_graph_build_ragged(const float* lig_pos, const int32_t
                                              inter_radius, intra_radius, capacity, capacity_lig, rowptr, row, col,
                                              etype, inv_deg, rowptr_lig, row_lig, col_lig, etype_lig, node_ptr,
                                              node_graph, pos, tables, status, state, state_bytes, stream_);
+}
+
+// ---- cropped slots: pvs_screen_graph_build_ragged_cap where every slot keeps only the receptor atoms closer than
+// crop_radius to one of its ligand atoms (screen_slots.h: PvsCroppedSlots), as the training loader crops a complex
+// around its ligand. k_crop_keep decides the masks, k_crop_slots turns them into ranks and node offsets; the kernels
+// above then run on the layout: a ligand atom's contact masks are cut down to the kept atoms, a receptor row is the
+// k-th kept atom (select), a receptor column the rank of its atom, and the template's receptor-receptor edges go in
+// where both ends are kept - no distance is evaluated for them. Only the full CSR is written. No atomics anywhere:
+// every word has one writer, so a build gives the same bits on every run. ----
+namespace {
+
+// The slot's atoms lig_ptr[p] .. lig_ptr[p + 1], or none where the pair is no slot of a valid table.
+__device__ __forceinline__ bool crop_slot_ok(int a0, int a1, int L_cap, int slot_cap) {
+    return a0 >= 0 && a1 >= a0 && a1 - a0 <= slot_cap && a1 <= L_cap;
+}
+
+// block (p, y): the slot's ligand atoms staged in LDS; wave w of the block takes the mask word 4 y + w: lane l decides
+// receptor atom 64 (4 y + w) + l against every staged atom (fp64 on the fp32 coordinates, strict, no lower bound: a
+// coincident atom is kept), one ballot per word. An empty or invalid slot keeps nothing.
+__global__ void __launch_bounds__(256)
+k_crop_keep(const float* __restrict__ lig_pos, const int32_t* __restrict__ lig_ptr, const float* __restrict__ rec_pos,
+            int L_cap, int n_rec, int slot_cap, Radius r_crop, u64* __restrict__ keep) {
+    __shared__ float lig[3 * kPvsMaxSlotCap];
+    const int p = blockIdx.x, lane = threadIdx.x & 63;
+    const int W = pvs_rec_words(n_rec), c = 4 * blockIdx.y + (threadIdx.x >> 6);
+    const int a0 = lig_ptr[p], a1 = lig_ptr[p + 1];
+    const int n = crop_slot_ok(a0, a1, L_cap, slot_cap) ? a1 - a0 : 0;       // (<= slot_cap <= kPvsMaxSlotCap)
+    for (int t = threadIdx.x; t < 3 * n; t += 256) lig[t] = lig_pos[(size_t)a0 * 3 + t];
+    __syncthreads();
+    if (c >= W) return;
+    const int i = 64 * c + lane;
+    bool in = false;
+    if (i < n_rec) {
+        const double xr = rec_pos[3 * i], yr = rec_pos[3 * i + 1], zr = rec_pos[3 * i + 2];
+        for (int a = 0; a < n && !in; ++a)
+            in = below(pvs_sqdist((double)lig[3 * a], (double)lig[3 * a + 1], (double)lig[3 * a + 2], xr, yr, zr), r_crop);
+    }
+    const u64 b = __ballot(in);
+    if (lane == 0) keep[(size_t)p * W + c] = b;
+}
+
+// ONE block. First every slot's ranks (thread per slot: keep_rank[p, w] = the kept atoms before word w, entry W the
+// slot's count) and its verdict on lig_ptr; behind the barrier the node offsets (thread p adds the counts of the slots
+// before it: B is a batch size), the atom -> slot table and the status word, STORED as in k_slots. A table that is not
+// one: every offset 0 and kPvsBadTable, an edgeless batch of padding rows.
+__global__ void __launch_bounds__(256)
+k_crop_slots(const int32_t* __restrict__ lig_ptr, const u64* __restrict__ keep, int B, int L_cap, int n_rec,
+             int slot_cap, int32_t* __restrict__ keep_rank, int32_t* __restrict__ node_ptr,
+             int32_t* __restrict__ slot_of, int32_t* __restrict__ status) {
+    __shared__ int bad;
+    const int W = pvs_rec_words(n_rec);
+    if (threadIdx.x == 0) bad = lig_ptr[0] != 0 ? 1 : 0;
+    __syncthreads();
+    for (int p = threadIdx.x; p < B; p += 256) {
+        if (!crop_slot_ok(lig_ptr[p], lig_ptr[p + 1], L_cap, slot_cap)) bad = 1;     // (every writer stores the same 1)
+        int32_t* rank = keep_rank + (size_t)p * (W + 1);
+        int before = 0;
+        for (int w = 0; w < W; ++w) {
+            rank[w] = before;
+            before += __popcll(keep[(size_t)p * W + w]);
+        }
+        rank[W] = before;
+    }
+    __syncthreads();
+    const bool ok = !bad;
+    for (int p = threadIdx.x; p <= B; p += 256) {
+        int rows = 0;
+        if (ok) {
+            rows = lig_ptr[p];
+            for (int k = 0; k < p; ++k) rows += keep_rank[(size_t)k * (W + 1) + W];
+        }
+        node_ptr[p] = rows;
+        if (p == B) *status = ok ? 0 : kPvsBadTable;
+        else if (ok) for (int q = lig_ptr[p]; q < lig_ptr[p + 1]; ++q) slot_of[q] = p;
+    }
+}
+
+}  // namespace
+
+extern "C" size_t pvs_screen_graph_cropped_state_bytes(int32_t B, int32_t L_cap, int32_t n_rec, int32_t slot_cap) {
+    if (slot_cap < 1 || slot_cap > kPvsMaxSlotCap || B < 1) return 0;
+    PvsArena a(nullptr, 0);
+    return carve_screen(a, (size_t)L_cap, L_cap + B * n_rec, n_rec, pvs_slot_words(slot_cap), true, nullptr, B) + 256;
+}
+
+extern "C" int pvs_screen_graph_build_cropped(const float* lig_pos, const int32_t* lig_ptr, const float* rec_pos,
+                                              const int32_t* rr_rowptr, const int32_t* rr_col, int32_t B,
+                                              int32_t L_cap, int32_t n_rec, int32_t slot_cap, double inter_radius,
+                                              double intra_radius, double crop_radius, int32_t capacity,
+                                              int32_t capacity_lig, int32_t* rowptr, int32_t* row, int32_t* col,
+                                              uint8_t* etype, float* inv_deg, int32_t* rowptr_lig, int32_t* row_lig,
+                                              int32_t* col_lig, uint8_t* etype_lig, int32_t* node_ptr,
+                                              int32_t* node_graph, float* pos, uint64_t* keep,
+                                              const PvsRaggedNodeTables* tables, int32_t* status, void* state,
+                                              size_t state_bytes, pvs_stream_t stream_) {
+    const char* who = "pvs_screen_graph_build_cropped";
+    hipStream_t s = (hipStream_t)stream_;
+    (void)capacity_lig; (void)rowptr_lig; (void)row_lig; (void)col_lig; (void)etype_lig;      // (no ligand-touching CSR)
+    PVS_REQUIRE(lig_pos && lig_ptr && rec_pos && rr_rowptr && rr_col && rowptr && row && col && etype && inv_deg &&
+                node_ptr && node_graph && pos && keep && status && state, "%s: NULL", who);
+    PVS_REQUIRE(slot_cap >= 1 && slot_cap <= kPvsMaxSlotCap, "%s: slot_cap must be 1..%d (got %d)", who,
+                kPvsMaxSlotCap, slot_cap);
+    PVS_REQUIRE(B > 0 && L_cap > 0 && L_cap <= slot_cap * (int64_t)B && n_rec > 0, "%s: needs slots, 1..%d * slots "
+                "packed ligand atoms (got %d for %d) and a receptor", who, slot_cap, L_cap, B);
+    PVS_REQUIRE((int64_t)L_cap + (int64_t)B * n_rec < INT32_MAX, "%s: more than 2^31 nodes", who);
+    PVS_REQUIRE(crop_radius > 0.0, "%s: crop_radius must be positive (got %g)", who, crop_radius);
+    PvsRaggedNodeTables t = {};
+    if (tables) {
+        t = *tables;
+        PVS_REQUIRE(t.n_feats >= 0, "%s: negative table width", who);
+        PVS_REQUIRE(!t.feats || (t.lig_feats && t.rec_feats && t.n_feats > 0), "%s: feature table without sources", who);
+        t.base_magg = nullptr;          // (a cropped row has lost template neighbours: the receptor's sums are not its)
+    }
+    PvsArena arena(state, state_bytes);
+    ScreenState w;
+    carve_screen(arena, (size_t)L_cap, L_cap + B * n_rec, n_rec, pvs_slot_words(slot_cap), true, &w, B);
+    PVS_REQUIRE(arena.ok(), "%s: state too small (%zu < %zu)", who, state_bytes, arena.off);
+    PvsProfScope prof(s, PVS_PROF_PREPARE);
+    const int W = pvs_rec_words(n_rec), n_rows = L_cap + B * n_rec;
+    u64* keep_words = (u64*)keep;
+    k_crop_keep<<<dim3(B, (W + 3) / 4), 256, 0, s>>>(lig_pos, lig_ptr, rec_pos, L_cap, n_rec, slot_cap,
+                                                     make_radius(crop_radius), keep_words);
+    PVS_CHECK_LAUNCH();
+    k_crop_slots<<<1, 256, 0, s>>>(lig_ptr, keep_words, B, L_cap, n_rec, slot_cap, w.keep_rank, node_ptr, w.slot_of,
+                                   status);
+    PVS_CHECK_LAUNCH();
+    const PvsCroppedSlots L{lig_ptr, node_ptr, w.slot_of, status, keep_words, w.keep_rank, B, L_cap, n_rec, slot_cap};
+    const OutCsr full{rowptr, row, col, etype, capacity}, none{nullptr, nullptr, nullptr, nullptr, 0};
+    PVS_TRY(build_csrs(L, lig_pos, rec_pos, rr_rowptr, rr_col, inter_radius, intra_radius, rowptr, nullptr, full, none,
+                       inv_deg, status, false, w, s));
+    k_node_tables_ragged<<<(n_rows + 3) / 4, 256, 0, s>>>(lig_pos, rec_pos, L, rr_rowptr, rr_col, node_graph, pos, t);
+    PVS_CHECK_LAUNCH();
+    return 0;
 }

@@ -1,6 +1,6 @@
 // Where the slots of a pose batch live (screen_graph.hip), and the table bisection the graph builders share.
-// A slot holds one pose: its ligand atoms, then the receptor's n_rec atoms (struck slots, at the end of this file: all
-// but one of them). The layouts answer the same questions
+// A slot holds one pose: its ligand atoms, then the receptor's n_rec atoms (struck slots: all but one of them; cropped
+// slots, at the end of this file: any subset of them). The layouts answer the same questions
 // (how many packed ligand atoms and node rows there are; which slot a packed atom or a row belongs to), so that the
 // builder's kernels exist once: uniform (B poses of one n_lig-atom ligand, by arithmetic) and ragged (one pose of any
 // ligand of 0..slot_cap atoms per slot, from the device tables lig_ptr / node_ptr / slot_of). A ligand atom's contacts
@@ -8,6 +8,7 @@
 // k / 64); the word and bit arithmetic of those masks lives here too. No HIP header: the host compiler builds this
 // file alone (tests/test_screen_slots_host.py, tests/test_screen_words_host.py).
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __HIPCC__
@@ -135,5 +136,69 @@ struct PvsStruckSlots {
         if (g >= node_ptr[B] || (*status & kPvsBadTable)) return {false, -1, 0, 0, 0, 0};
         const int p = pvs_last_le(node_ptr, B, g), a0 = lig_ptr[p], node0 = node_ptr[p];
         return {true, p, a0, lig_ptr[p + 1] - a0, node0, g - node0, rec_drop[p]};
+    }
+};
+
+// ---- cropped slots: a slot's receptor is the subset of the receptor's atoms that a keep mask names ----
+// keep [B, W] 64-bit words, W = pvs_rec_words(n_rec): bit j % 64 of word j / 64 of slot p is set when receptor atom j is
+// one of the slot's rows (the bits from n_rec on are clear). The kept atoms keep their order, compact, behind the slot's
+// ligand atoms, so the slot owns n_lig + kept rows and node_ptr[p + 1] = node_ptr[p] + n_lig_p + kept_p. keep_rank
+// [B, W + 1]: per slot the kept atoms in the words before word w (entry W: the slot's kept count), which makes both
+// mappings between receptor rows and receptor atoms one table read and one word of bit arithmetic.
+
+PVS_SLOTS_FN int pvs_rec_words(int n_rec) { return (n_rec + 63) >> 6; }
+
+// The place of the n-th set bit of `word`, n = 0 .. popcount(word) - 1 (six halvings).
+PVS_SLOTS_FN int pvs_select64(unsigned long long word, int n) {
+    int at = 0;
+    for (int width = 32; width; width >>= 1) {
+        const int c = __builtin_popcountll((word >> at) & ((1ull << width) - 1ull));
+        if (n >= c) { n -= c; at += width; }
+    }
+    return at;
+}
+
+// The ragged layout with keep / keep_rank: the same questions (a row's `local` counts the slot's rows as they are,
+// compact), and the two mappings of a slot's receptor part. Not valid: as for PvsRaggedSlots.
+struct PvsCroppedSlots {
+    const int32_t *lig_ptr, *node_ptr, *slot_of, *status;
+    const unsigned long long* keep;
+    const int32_t* keep_rank;
+    int B, L_cap, n_rec;
+    int slot_cap = 64;
+    PVS_SLOTS_FN int words() const { return pvs_slot_words(slot_cap); }
+    PVS_SLOTS_FN int rec_words() const { return pvs_rec_words(n_rec); }
+    PVS_SLOTS_FN int atoms() const { return L_cap; }
+    PVS_SLOTS_FN int rows() const { return L_cap + B * n_rec; }       // (the room: a slot that keeps every atom)
+    PVS_SLOTS_FN PvsSlotAtom atom(int q) const {
+        if ((*status & kPvsBadTable) || q >= lig_ptr[B]) return {false, 0, 0};
+        const int p = slot_of[q], a0 = lig_ptr[p];
+        return {true, a0, lig_ptr[p + 1] - a0};
+    }
+    PVS_SLOTS_FN PvsSlotRow row(int g) const {
+        if (g >= node_ptr[B] || (*status & kPvsBadTable)) return {false, -1, 0, 0, 0, 0};
+        const int p = pvs_last_le(node_ptr, B, g), a0 = lig_ptr[p], node0 = node_ptr[p];
+        return {true, p, a0, lig_ptr[p + 1] - a0, node0, g - node0};
+    }
+    // word c of the keep mask of the slot that owns the (valid) packed atom q
+    PVS_SLOTS_FN unsigned long long keep_word_of_atom(int q, int c) const {
+        return keep[(size_t)slot_of[q] * rec_words() + c];
+    }
+    PVS_SLOTS_FN bool kept(int p, int j) const { return (keep[(size_t)p * rec_words() + (j >> 6)] >> (j & 63)) & 1ull; }
+    PVS_SLOTS_FN int kept_count(int p) const { return keep_rank[(size_t)p * (rec_words() + 1) + rec_words()]; }
+    // select: the receptor atom behind the k-th receptor row of slot p, k = 0 .. kept_count(p) - 1 (of words with
+    // equal ranks the last one wins: the one that is not empty)
+    PVS_SLOTS_FN int receptor(int p, int k) const {
+        const int W = rec_words();
+        const int32_t* rank = keep_rank + (size_t)p * (W + 1);
+        const int w = pvs_last_le(rank, W, k);
+        return 64 * w + pvs_select64(keep[(size_t)p * W + w], k - rank[w]);
+    }
+    // rank: the receptor row (0 .. kept_count(p) - 1) of the kept receptor atom j in slot p; for an atom that is not
+    // kept, the row the next kept atom has
+    PVS_SLOTS_FN int receptor_row(int p, int j) const {
+        const int W = rec_words(), w = j >> 6;
+        return keep_rank[(size_t)p * (W + 1) + w] +
+               __builtin_popcountll(keep[(size_t)p * W + w] & ((1ull << (j & 63)) - 1ull));
     }
 };

@@ -265,10 +265,20 @@ class _ReceptorSideScreen:
             _lib.ptr(saved), _lib.ptr(ws), ws.numel(), _stream(dev)), name)
         return h_out, x_out
 
-    def _tail(self, pg_full, h, x):
-        """The layers after the first over the full graph, then the head."""
+    def _receptor_template(self, rec_pos):
+        """The receptor-receptor template CSR alone (`_rr`), for a step that keeps no first-layer sums (a cropped
+        LibraryScreen); the weights fingerprint is taken as `_receptor_sums` takes it, so stale() and a captured step's
+        refusal after a weight change work alike."""
+        self._fingerprint = self._weights_fingerprint()
+        dev, n_rec = rec_pos.device, rec_pos.shape[0]
+        with torch.no_grad():
+            self._rr = radius_graph(rec_pos, torch.ones(n_rec, dtype=torch.uint8, device=dev), None, self.r_inter,
+                                    self.r_intra, need_backward=False)
+
+    def _tail(self, pg_full, h, x, layers=None):
+        """The layers after the first (or `layers`) over the full graph, then the head."""
         m_sorted = None
-        for layer in self.egnn[1:]:
+        for layer in self.egnn[1:] if layers is None else layers:
             h, x, m_sorted = layer.forward_prepared(pg_full, h, x, m_sorted, need_m=layer.edge_residual,
                                                     need_coords=layer is not self.egnn[-1])
         if self.cam is not None:
@@ -596,14 +606,32 @@ class LibraryScreen(_ReceptorSideScreen):
     neighbour take their whole first-layer row through the ligand-touching CSR with a zero base, every other row and
     every kernel is as without it. `load(slots, rec_drop=[...])` and `load_leave_out_pairs` fill it. Needs the
     first-layer reuse, and goes with neither `cam` nor `contact_attention` (their reductions assume n_rec receptor rows
-    per slot). A screen without it launches exactly what it always launched."""
+    per slot). A screen without it launches exactly what it always launched.
+
+    crop_radius: None, or the radius of the training loader's crop (the reference's make_box(...,
+    relative_to_ligand=True), the data-root path's `radius`; CLI default 10): every slot keeps only the receptor atoms
+    closer than it to one of the slot's ligand atoms (fp64 decision on the fp32 coordinates, strict, a coincident atom
+    is kept; an empty slot keeps nothing), in receptor order behind the ligand atoms, and the slot's graph is
+    generate_edges on that cropped complex - so a pose scores what `val()` gives the same pose, and the layers run
+    over the rows the model was trained on. The step is pvs_screen_graph_build_cropped, the embedding, then EVERY EGNN
+    layer through forward_prepared on the one full CSR (edge count on the device), pooling and heads by node_ptr: the
+    first-layer receptor sums are not used (a row at the rim of the crop has lost template neighbours). Shapes stay
+    padded to N_cap, so capture() / replay() and `tasks` work as above; `screen.keep` [batch_size, ceil(n_rec / 64)]
+    int64 holds the last step's masks (bit j % 64 of word j / 64), `screen._fast['node_ptr']` its offsets. Models as
+    captured_scoring.model_refusal accepts them (fp32, no edge_residual, 17..128 channels: NotImplementedError
+    otherwise); GraphNorm models need padded_graphnorm=True (the row count is only known on the device); struck, cam
+    and contact_attention do not go with it (their reductions assume n_rec rows per slot): ValueError. None: the screen
+    launches exactly what it launches without the keyword."""
 
     def __init__(self, model, rec_pos, rec_feats, batch_size, max_lig_atoms, edge_radius, intra_radius=None,
                  tasks=None, contact_attention=None, cam=None, struck=None, padded_graphnorm=False,
-                 softmax_reuse=False):
+                 softmax_reuse=False, crop_radius=None):
         super().__init__(model, edge_radius, intra_radius, tasks, softmax_reuse)
         self.struck = bool(struck)
         self.padded_graphnorm = bool(padded_graphnorm)
+        self.crop_radius = None if crop_radius is None else float(crop_radius)
+        if self.crop_radius is not None:
+            self._check_crop(model, contact_attention, cam)
         if self.struck and (cam is not None or contact_attention is not None):
             which = 'cam' if cam is not None else 'contact_attention'
             raise ValueError(f'LibraryScreen(struck=True, {which}=...): the {which} reduction assumes n_rec receptor '
@@ -613,8 +641,14 @@ class LibraryScreen(_ReceptorSideScreen):
         if not 1 <= int(max_lig_atoms) <= MAX_SCREEN_LIGAND_ATOMS:
             raise ValueError(f'max_lig_atoms must be 1..{MAX_SCREEN_LIGAND_ATOMS} (got {max_lig_atoms})')
         _lib.require_hip(rec_pos)
-        self.reuse = self._first_layer_reusable() and not any(l.edge_residual for l in self.egnn)
+        # (`reuse`: the screen runs its own fixed-shape step and not the plain forward - for a cropped screen every model
+        # that _check_crop let through)
+        self.reuse = (self.crop_radius is not None
+                      or (self._first_layer_reusable() and not any(l.edge_residual for l in self.egnn)))
         self.graphnorm = any(getattr(l, 'graphnorm', False) for l in self.egnn)
+        if self.crop_radius is not None and self.graphnorm and not self.padded_graphnorm:
+            raise ValueError('LibraryScreen(crop_radius=...): a GraphNorm model needs padded_graphnorm=True - the row '
+                             'count of a cropped batch is only known on the device, where the layers then read it')
         # a graphnorm model at the padded shape: the statistics over the node_ptr[batch_size] real rows, read on the device
         self._gn_padded = self.padded_graphnorm and self.graphnorm and self.reuse
         dev = rec_pos.device
@@ -658,6 +692,27 @@ class LibraryScreen(_ReceptorSideScreen):
             self.cam = self._value_buffers('lig_val', 'slot_rec_val', node_width=sum(self._cam_plan[1]))
         if self.reuse:
             self._cache_receptor_sums()
+
+    def _check_crop(self, model, contact_attention, cam):
+        """What a cropped screen refuses, before anything is allocated."""
+        from .captured_scoring import model_refusal
+        if not self.crop_radius > 0:
+            raise ValueError(f'crop_radius must be positive (got {self.crop_radius})')
+        for which, given in (('struck', self.struck), ('cam', cam is not None),
+                             ('contact_attention', contact_attention is not None)):
+            if given:
+                raise ValueError(f'LibraryScreen(crop_radius=..., {which}=...): the {which} path assumes n_rec receptor '
+                                 'rows in every slot, and a cropped slot has those inside the radius; use two screens')
+        why = model_refusal(model)
+        if why is not None:
+            raise NotImplementedError(f'LibraryScreen(crop_radius=...): {why}')
+
+    @property
+    def keep(self):
+        """The keep masks of the last step of a cropped screen, [batch_size, ceil(n_rec / 64)] int64 on the device."""
+        if self.crop_radius is None or self._fast is None:
+            raise RuntimeError('keep: the masks of a cropped screen (crop_radius=...) after its first step')
+        return self._fast['keep']
 
     def _value_buffers(self, lig_key, slot_key, node_width=None):
         """The static buffers of `contact` / `cam`: the three accumulators, with node_width node_y [N_cap, node_width],
@@ -711,6 +766,9 @@ class LibraryScreen(_ReceptorSideScreen):
 
     def _cache_receptor_sums(self):
         """The receptor sums kept once, [n_rec, .]; the builder's node-table struct points at them."""
+        if self.crop_radius is not None:      # (a cropped step keeps the template and no sums)
+            self._receptor_template(self._rec_pos)
+            return
         self.rec_magg, self.rec_xsum, self.rec_deg = self._receptor_sums(self._rec_feats, self._rec_pos)
         if self._fast is not None:
             t = self._fast['tables']
@@ -853,17 +911,60 @@ class LibraryScreen(_ReceptorSideScreen):
             _lib.ptr(f['base_xsum']), _lib.ptr(f['base_deg']))
         return f
 
+    def _cropped_buffers(self, cap):
+        """The buffers of a cropped screen: the full CSR alone, the node tables without base rows, the keep masks."""
+        lib = _lib.lib()
+        dev, n_cap = self.lig_pos.device, self.n_cap
+        i32 = dict(dtype=torch.int32, device=dev)
+        f32 = dict(dtype=torch.float32, device=dev)
+        f = _csr_buffers(
+            dev, n_cap, None, cap,
+            state=torch.empty(lib.pvs_screen_graph_cropped_state_bytes(self.b, self.l_cap, self.n_rec, self.slot_cap),
+                              dtype=torch.uint8, device=dev),
+            node_ptr=torch.zeros(self.b + 1, **i32), node_graph=torch.empty(n_cap, **i32),
+            pos=torch.empty((n_cap, 3), **f32), x=torch.empty((n_cap, self.lig_feats.shape[1]), **f32),
+            keep=torch.zeros((self.b, (self.n_rec + 63) // 64), dtype=torch.int64, device=dev))
+        f['tables'] = _lib.PvsRaggedNodeTables(f['x'].shape[1], 0, _lib.ptr(self.lig_feats), _lib.ptr(self._rec_feats),
+                                               None, None, None, _lib.ptr(f['x']), None, None, None)
+        from .graph import PreparedGraph
+        csr = {k: f[k] for k in ('rowptr', 'row', 'col', 'etype', 'inv_deg', 'status')}
+        f['pg'] = PreparedGraph.over_buffers(n_cap, cap, csr, f['rowptr'][n_cap:])
+        if self.graphnorm:
+            f['pg'].set_norm_rows(f['node_ptr'][self.b:])
+        return f
+
+    def _probe_buffers(self):
+        """What the probe of a cropped screen's capacities needs of the uncropped builder's buffers: row pointers, node
+        tables without feature or base rows, no room for edges."""
+        dev, n_cap = self.lig_pos.device, self.n_cap
+        i32 = dict(dtype=torch.int32, device=dev)
+        f = _csr_buffers(
+            dev, n_cap, 1, 1,
+            state=torch.empty(_lib.lib().pvs_screen_graph_ragged_cap_state_bytes(self.b, self.l_cap, self.n_rec,
+                                                                                 self.slot_cap),
+                              dtype=torch.uint8, device=dev),
+            node_ptr=torch.zeros(self.b + 1, **i32), node_graph=torch.empty(n_cap, **i32),
+            pos=torch.empty((n_cap, 3), dtype=torch.float32, device=dev))
+        f['tables'] = _lib.PvsRaggedNodeTables()
+        return f
+
     def _launch_builder(self, f):
         """The builder of the loaded batch into f: pvs_screen_graph_build_ragged_cap, or for a struck screen
-        pvs_screen_graph_build_struck, which takes rec_drop behind lig_ptr and is otherwise called alike."""
+        pvs_screen_graph_build_struck, which takes rec_drop behind lig_ptr and is otherwise called alike - as is
+        pvs_screen_graph_build_cropped where f has keep masks: crop_radius behind the edge radii, keep behind pos, and
+        no ligand-touching CSR (NULL, no room)."""
         args = [_lib.ptr(self.lig_pos), _lib.ptr(self.lig_ptr), _lib.ptr(self._rec_pos),
                 _lib.ptr(self._rr.t['rowptr']), _lib.ptr(self._rr.t['col']), self.b, self.l_cap, self.n_rec,
-                self.slot_cap, float(self.r_inter), float(self.r_intra), f['cap'], f['cap_l']]
-        args += [_lib.ptr(f[key]) for key in ('rowptr', 'row', 'col', 'etype', 'inv_deg', 'rowptr_l', 'row_l', 'col_l',
-                                              'etype_l', 'node_ptr', 'node_graph', 'pos')]
+                self.slot_cap, float(self.r_inter), float(self.r_intra), f['cap'], f['cap_l'] or 0]
+        args += [_lib.ptr(f.get(key)) for key in ('rowptr', 'row', 'col', 'etype', 'inv_deg', 'rowptr_l', 'row_l',
+                                                  'col_l', 'etype_l', 'node_ptr', 'node_graph', 'pos')]
         args += [C.byref(f['tables']), _lib.ptr(f['status']), _lib.ptr(f['state']), f['state'].numel(),
                  _stream(self.lig_pos.device)]
         name = 'pvs_screen_graph_build_ragged_cap'
+        if 'keep' in f:
+            args.insert(11, self.crop_radius)
+            args.insert(-5, _lib.ptr(f['keep']))
+            name = 'pvs_screen_graph_build_cropped'
         if self.struck:
             args.insert(2, _lib.ptr(self.rec_drop))
             name = 'pvs_screen_graph_build_struck'
@@ -875,7 +976,7 @@ class LibraryScreen(_ReceptorSideScreen):
         batch of L_cap atoms, at most what L_cap atoms can have (per atom: inter and intra contacts with the receptor,
         both directions, and the slot's other ligand atoms). A struck screen adds the whole rows of the receptor rows
         that the struck atom can touch (`_struck_room`) for every slot."""
-        probe = self._buffers(1, 1)
+        probe = self._buffers(1, 1) if self.crop_radius is None else self._probe_buffers()
         probe['cap'] = probe['cap_l'] = 0
         self._launch_builder(probe)
         n_lig_edges = int(probe['rowptr_l'][self.n_cap].item())
@@ -918,7 +1019,8 @@ class LibraryScreen(_ReceptorSideScreen):
         touching) edge room instead of the probe's."""
         capturing = torch.cuda.is_current_stream_capturing()
         if self._fast is None:
-            self._fast = self._buffers(*(capacities or self._probe_capacities()))
+            cap, cap_l = capacities or self._probe_capacities()
+            self._fast = self._buffers(cap, cap_l) if self.crop_radius is None else self._cropped_buffers(cap)
         f = self._fast
         if not capturing:
             self.check()
@@ -972,6 +1074,9 @@ class LibraryScreen(_ReceptorSideScreen):
             return self._plain_forward()
         self._refresh_if_stale()
         f = self._build()
+        if self.crop_radius is not None:      # every layer on the one full CSR of the cropped batch, padded shape
+            x = f['pos']
+            return self._tail(f['pg'], self.embed.embed(f['x'], x).contiguous(), x, layers=self.egnn)
         # graphnorm's statistics run over the batch's nodes: no padding rows there (the host knows the count) - or, with
         # padded_graphnorm, the padded shape and the count where the builder left it (PvsGraph.n_norm_rows_dev)
         exact = self.graphnorm and not self._gn_padded
@@ -1093,11 +1198,19 @@ class ScreeningSweep:
     the class-activation map (the heads applied to every atom's final embedding), which needs no attention layer.
     softmax_reuse (opt-in, default False): handed to every screen the sweep creates (LibraryScreen's docstring): models
     with edge attention under softmax_attention then take the captured routes and the attribution methods above.
+    crop_radius (opt-in, default None): every pose is scored on the complex cropped around it, as training and `val()`
+    see it (LibraryScreen's docstring). `run` and `run_library` then go through cropped LibraryScreens - `run` is
+    `run_library`, a ligand above max_lig_atoms gets a cropped screen of its own size (`self.crop_buckets`) - with
+    predictions, hits files, tasks and best_poses unchanged in form. The four attribution methods raise
+    NotImplementedError on such a sweep: the reference masks after cropping around the WHOLE ligand, so a copy must not
+    crop again around what is left of it.
     """
 
     def __init__(self, model, rec_pos, rec_feats, edge_radius, batch_size=32, intra_radius=None, capture=True,
-                 receptor_name='receptor', tasks=None, padded_graphnorm=False, softmax_reuse=False):
+                 receptor_name='receptor', tasks=None, padded_graphnorm=False, softmax_reuse=False, crop_radius=None):
         self.model, self.rec_pos, self.rec_feats = model, rec_pos, rec_feats
+        self.crop_radius = None if crop_radius is None else float(crop_radius)
+        self.crop_buckets = {}     # n_lig -> the cropped LibraryScreen of the ligands above run_library's max_lig_atoms
         self.padded_graphnorm = bool(padded_graphnorm)      # handed to every LibraryScreen of the sweep
         self.softmax_reuse = bool(softmax_reuse)            # handed to every screen of the sweep
         self.tasks = _resolve_tasks(model, tasks)
@@ -1136,8 +1249,38 @@ class ScreeningSweep:
         x = screen.batcher.batch.x
         x.view(screen.b, screen.batcher.n, -1)[:, :screen.n_lig] = lig_feats.to(x.device, x.dtype)
 
+    def _run_ligand_cropped(self, name, lig_feats, poses, sink):
+        """`_run_ligand` on a cropped sweep: the ligand's poses through a cropped LibraryScreen of its own size, up to
+        batch_size slots per step (the last step's other slots are empty); no padding poses."""
+        n_poses, n_lig = int(poses.shape[0]), int(poses.shape[1])
+        dev = self.rec_pos.device
+        screen = self.crop_buckets.get(n_lig)
+        if screen is None or screen.stale():
+            screen = LibraryScreen(self.model, self.rec_pos, self.rec_feats, self.b, n_lig, self.edge_radius,
+                                   self.intra_radius, tasks=self.tasks, padded_graphnorm=self.padded_graphnorm,
+                                   softmax_reuse=self.softmax_reuse, crop_radius=self.crop_radius)
+            self.crop_buckets[n_lig] = screen
+        feats = lig_feats.to(dev).float()
+        scores = []
+        for k in range(0, n_poses, self.b):
+            keep = min(self.b, n_poses - k)
+            ptr = slot_offsets([[n_lig] * keep], self.b)[0]
+            screen.load_packed(poses[k:k + keep].to(dev).float().reshape(-1, 3), feats.repeat(keep, 1), ptr.to(dev),
+                               [n_lig] * keep)
+            raw = self._library_step(screen)
+            y = sink.scored(raw)
+            scores.append(y[:keep])
+            sink.keep_raw(name, raw[:keep])
+            if sink.writers:
+                sink.write(y[:keep], [f'{name}_pose{k + i}' for i in range(keep)])
+            self.batches_run += 1
+        screen.check()
+        return torch.cat(scores, 0)
+
     def _run_ligand(self, name, lig_feats, poses, sink):
         """All poses of one ligand through its size bucket; returns its scores [P, ...]."""
+        if self.crop_radius is not None:
+            return self._run_ligand_cropped(name, lig_feats, poses, sink)
         n_poses, n_lig = int(poses.shape[0]), int(poses.shape[1])
         pad = (-n_poses) % self.b
         if pad:
@@ -1202,6 +1345,8 @@ class ScreeningSweep:
         Returns {name: scores [P, C] on the device} (raw model outputs; sigmoid-ed like `val` does for
         classification models when sigmoid is None/True - the pose column alone of a two-headed model).
         predictions_file, hits_file: optional paths (class docstring)."""
+        if self.crop_radius is not None:      # (cropped slots are library slots: one path for both)
+            return self.run_library(ligands, predictions_file, sigmoid, hits_file=hits_file)
         out, names = {}, []
         with self._sweeping(predictions_file, sigmoid, hits_file) as sink:
             for name, lig_feats, poses in ligands:
@@ -1223,7 +1368,8 @@ class ScreeningSweep:
                 or (type(screen.cam_request), screen.cam_request) != (type(cam), cam)):      # (True is not column 1)
             screen = LibraryScreen(self.model, self.rec_pos, self.rec_feats, self.b, max_atoms, self.edge_radius,
                                    self.intra_radius, tasks=self.tasks, contact_attention=layer, cam=cam, struck=struck,
-                                   padded_graphnorm=self.padded_graphnorm, softmax_reuse=self.softmax_reuse)
+                                   padded_graphnorm=self.padded_graphnorm, softmax_reuse=self.softmax_reuse,
+                                   crop_radius=self.crop_radius)
             setattr(self, which, screen)
         return screen
 
@@ -1319,6 +1465,13 @@ class ScreeningSweep:
                 yield name, lig_feats, poses[best]
 
     # ---- attribution of hits: the bodies are in hit_attribution.py ----
+    def _no_attribution_when_cropped(self, method):
+        if self.crop_radius is not None:
+            raise NotImplementedError(
+                f'ScreeningSweep(crop_radius=...).{method}: the reference masks after cropping around the WHOLE '
+                'ligand, so a copy must not be cropped again around what is left of it - and the attention and CAM '
+                'reductions assume n_rec receptor rows per slot. Not built yet: use a sweep without crop_radius')
+
     def ligand_atom_masking(self, items, scores_file=None, sigmoid=None, column=0):
         """Atom masking (the reference's attribution_fns.atom_masking, :365-431) of the LIGAND atoms of many complexes
         with this receptor: items = iterable of (name, lig_feats [n,F], pose [n,3]), n <= MAX_SCREEN_LIGAND_ATOMS,
@@ -1332,6 +1485,7 @@ class ScreeningSweep:
         sigmoid where a sweep applies it to that column (`sigmoid` as in `run`; False: raw differences);
         `self.atom_masking_raw[name]` keeps the raw rows [n + 1, C], whole ligand first. scores_file: one line per
         ligand atom, item order then atom order, '{score:.6f} | {receptor} {name}_atom{a}'."""
+        self._no_attribution_when_cropped('ligand_atom_masking')
         from . import hit_attribution
         return hit_attribution.ligand_atom_masking(self, items, scores_file, sigmoid, column)
 
@@ -1348,6 +1502,7 @@ class ScreeningSweep:
         (tasks='both': name it). One value per unordered pair (the reference lists a contact once per direction, with
         equal scores). `self.contact_masking_raw[name]`: the raw rows [K + 1, C]. scores_file: one line per contact,
         item order then pair order, '{score:.6f} | {receptor} {name}_atom{a} atom{r}'."""
+        self._no_attribution_when_cropped('contact_masking')
         from . import hit_attribution
         return hit_attribution.contact_masking(self, items, scores_file, sigmoid, column)
 
@@ -1359,6 +1514,7 @@ class ScreeningSweep:
         scores [M])} on the device, scores[m] = s(y_whole[column]) - s(y_without_atom_m[column]);
         `self.receptor_atom_masking_raw[name]`: the raw rows [M + 1, C]. scores_file: one line per atom, item order
         then atom order, '{score:.6f} | {receptor} {name} atom{r}'."""
+        self._no_attribution_when_cropped('receptor_atom_masking')
         from . import hit_attribution
         return hit_attribution.receptor_atom_masking(self, items, atoms, scores_file, sigmoid, column)
 
@@ -1387,6 +1543,7 @@ class ScreeningSweep:
         (LibraryScreen(cam=...)), which needs neither an attention layer nor the first-layer reuse. Same keys.
         ligand_scores_file: one line per ligand atom of every hit, item order then atom order, '{value:.6f} |
         {receptor} {name}_atom{a}'."""
+        self._no_attribution_when_cropped('receptor_hotspots')
         from . import hit_attribution
         return hit_attribution.receptor_hotspots(self, items, gnn_layer, scores_file, per_hit, attribution, column,
                                                  ligand_scores_file)

@@ -1,0 +1,428 @@
+"""Cropped library screening (LibraryScreen / ScreeningSweep with crop_radius=..., pvs_screen_graph_build_cropped):
+every slot keeps the receptor atoms closer than the radius to one of its ligand atoms, as the training loader crops a
+complex. The builder is checked exactly - masks against numpy (tests/_crop_ref.py), graphs against the oracle's
+generate_edges on the cropped complexes -, the scores against the plain forward on those complexes and against the
+data-root path. Receptor of 130 atoms: three 64-bit mask words, two bits in the last."""
+import tempfile
+
+import numpy as np
+import pytest
+import torch
+
+from tests import _crop_ref as ref
+from tests._golden import needs_caching_allocator
+
+pytestmark = pytest.mark.gpu
+
+N_REC = 130
+SIZES = (1, 64, 0, 7, 33, 20)
+KW = dict(dim_input=12, k=32, dim_output=1, num_layers=2, residual=False, edge_residual=False,
+          edge_attention=False, normalize=False, tanh=False, dropout=0.0, graphnorm=False, update_coords=True,
+          permutation_invariance=False, node_attention=False, gated_residual=False, rezero=False,
+          softmax_attention=False, model_task='classification')
+
+
+def _model(seed=0, **flags):
+    from pointvs_amd.egnn_satorras import SartorrasEGNN
+    torch.manual_seed(seed)
+    return SartorrasEGNN(tempfile.mkdtemp(), 2e-3, 1e-4, silent=True, **dict(KW, **flags)).eval()
+
+
+def _set(seed, n_lig=64):
+    """(ligand [n_lig,3], receptor [130,3], ligand feats, receptor feats): the 130 receptor atoms of a
+    screening_set nearest its centre."""
+    from pointvs_amd.synthetic import screening_set
+    lig, rec, feats = screening_set(seed=seed, n_nodes=n_lig + 400, n_lig=n_lig)
+    near = torch.argsort((rec - lig.mean(0)).norm(dim=1))[:N_REC].sort().values
+    return lig, rec[near].contiguous(), feats[:n_lig].contiguous(), feats[n_lig:][near].contiguous()
+
+
+def _slots(lig, lig_feats, sizes, seed, rec=None, special=True):
+    """One pose per slot: slot k holds the first sizes[k] ligand atoms (features rolled by k) in a random pose.
+    special: the first atom of the 7-atom ligand sits exactly on receptor atom 5 (d = 0: kept, and no edge), the
+    33-atom ligand is 100 A away (it keeps no receptor atom)."""
+    from pointvs_amd.synthetic import random_poses
+    slots = []
+    for k, n in enumerate(sizes):
+        if n == 0:
+            slots.append((lig_feats[:0], lig[:0]))
+            continue
+        pose = random_poses(lig[:n], 1, seed=seed + k, max_shift=3.0)[0].contiguous()
+        if special and n == 7:
+            pose[0] = rec[5]
+        if special and n == 33:
+            pose = pose + torch.tensor([100.0, 0.0, 0.0])
+        slots.append((lig_feats[:n].roll(k, 0).contiguous(), pose))
+    return slots
+
+
+def _cropped(slots, rec, rec_feats, radius):
+    """Per slot (x, pos, kept indices) of the cropped complex, as torch tensors (numpy reference)."""
+    out = []
+    for feats, pose in slots:
+        x, pos, kept = ref.cropped_complex(feats.numpy(), pose.numpy(), rec_feats.numpy(), rec.numpy(), radius)
+        out.append((torch.from_numpy(x), torch.from_numpy(pos).reshape(-1, 3), kept))
+    return out
+
+
+def _oracle_items(complexes, r_inter, r_intra):
+    """The cropped complexes as Data items with the oracle's edge lists (reference order); a complex without atoms
+    has no edges."""
+    from oracle.generate_edges_oracle import generate_edges as oracle_edges
+    from pointvs_amd.graph import Data
+    items = []
+    for x, pos, _ in complexes:
+        if x.shape[0]:
+            _, (rows, cols), attrs = oracle_edges(pos.numpy(), x[:, -1].numpy(), r_inter, r_intra, prune=False)
+        else:
+            rows = cols = attrs = np.zeros(0, dtype=np.int64)
+        items.append(Data(x=x, pos=pos, edge_index=torch.from_numpy(np.vstack([rows, cols])).long().reshape(2, -1),
+                          edge_attr=torch.nn.functional.one_hot(torch.from_numpy(np.asarray(attrs)).long(), 3),
+                          y=torch.tensor(0), lig_fname='l', rec_fname='r'))
+    return items
+
+
+def _keep_words(complexes, n_rec):
+    """[B, W] int64: the numpy masks of the slots as the builder's words."""
+    words = []
+    for _, _, kept in complexes:
+        mask = np.zeros(n_rec, dtype=bool)
+        mask[kept] = True
+        words.append(ref.mask_words(mask))
+    return torch.from_numpy(np.stack(words).view(np.int64))
+
+
+def _assert_exact(screen, f, slots, complexes, r_inter, r_intra):
+    """keep == the numpy masks; node_ptr, node_graph, pos and x == the gathers; per slot the CSR == the oracle's
+    generate_edges on the cropped complex, shifted (rows gathered stably: inter block before intra block inside a
+    row); padding rows are empty."""
+    n_cap, n_rec = screen.n_cap, screen.n_rec
+    sizes = [pose.shape[0] for _, pose in slots]
+    assert torch.equal(screen.keep.cpu(), _keep_words(complexes, n_rec))
+    node_ptr = np.concatenate([[0], np.cumsum([x.shape[0] for x, _, _ in complexes])])
+    assert [x.shape[0] for x, _, _ in complexes] == [n + len(kept) for n, (_, _, kept) in zip(sizes, complexes)]
+    n = int(node_ptr[-1])
+    assert f['node_ptr'].cpu().tolist() == node_ptr.tolist()
+    assert screen._fast['node_ptr'] is f['node_ptr']
+    graph_id = torch.arange(len(slots)).repeat_interleave(torch.from_numpy(np.diff(node_ptr)))
+    assert torch.equal(f['node_graph'][:n].cpu(), graph_id.int()) and bool((f['node_graph'][n:] == -1).all())
+    assert torch.equal(f['pos'][:n].cpu(), torch.cat([pos for _, pos, _ in complexes], 0))
+    assert torch.equal(f['x'][:n].cpu(), torch.cat([x for x, _, _ in complexes], 0))
+    assert bool((f['pos'][n:] == 0).all()) and bool((f['x'][n:] == 0).all())
+    rowptr, e = f['rowptr'].cpu().numpy(), int(f['rowptr'][n_cap])
+    row, col, etype = (f[k][:e].cpu().numpy() for k in ('row', 'col', 'etype'))
+    total = 0
+    for p, item in enumerate(_oracle_items(complexes, r_inter, r_inter if r_intra is None else r_intra)):
+        rows, cols = item.edge_index.numpy()
+        attrs = item.edge_attr.argmax(1).numpy() if len(rows) else np.zeros(0, dtype=np.int64)
+        order = np.argsort(rows, kind='stable')
+        lo, hi = rowptr[node_ptr[p]], rowptr[node_ptr[p + 1]]
+        assert hi - lo == len(rows), p
+        assert np.array_equal(row[lo:hi], rows[order] + node_ptr[p]), p
+        assert np.array_equal(col[lo:hi], cols[order] + node_ptr[p]), p
+        assert np.array_equal(etype[lo:hi], attrs[order]), p
+        total += len(rows)
+    assert e == total and bool((f['rowptr'][n:] == e).all())              # padding rows: degree 0 ...
+    degree = np.diff(rowptr[:n + 1])
+    assert np.array_equal(f['inv_deg'][:n].cpu().numpy(), (1.0 / np.maximum(degree, 1).astype(np.float32)))
+    assert bool((f['inv_deg'][n:] == 1).all())                            # ... and inv_deg 1
+
+
+@pytest.mark.parametrize('radii', [(7.0, None, 8.0), (6.0, 2.5, 8.0), (9.0, None, 6.0)])
+def test_cropped_builder_equals_the_reference_edge_lists_of_the_cropped_complexes(radii):
+    """(inter, intra, crop): a radius pair without and with intra_radius, and crop_radius below r_inter - an atom inside
+    the edge radius that the crop drops has no edge."""
+    from pointvs_amd.screening import LibraryScreen
+    r_inter, r_intra, crop = radii
+    lig, rec, lig_feats, rec_feats = _set(6001)
+    slots = _slots(lig, lig_feats, SIZES, seed=10, rec=rec)
+    complexes = _cropped(slots, rec, rec_feats, crop)
+    kept = [len(k) for _, _, k in complexes]
+    assert N_REC in kept and 0 in kept and any(0 < k < N_REC for k in kept), kept      # all, none and partial slots
+    assert kept[2] == 0 and kept[4] == 0 and 5 in complexes[3][2]     # empty slot; far ligand; the coincident atom
+    if crop < r_inter:      # the case is about atoms inside the edge radius and outside the crop: there are some
+        d = torch.cdist(slots[5][1].double(), rec.double())
+        assert bool(((d < r_inter).any(0) & ~(d < crop).any(0)).any())
+    screen = LibraryScreen(_model(), rec.cuda(), rec_feats, len(SIZES), 64, r_inter, r_intra, crop_radius=crop)
+    f = screen.load(slots)._build()
+    screen.check()
+    torch.cuda.synchronize()
+    assert screen.n_cap == len(SIZES) * (64 + N_REC) and 'rowptr_l' not in f and 'base_magg' not in f
+    _assert_exact(screen, f, slots, complexes, r_inter, r_intra)
+    again = {k: f[k].clone() for k in ('rowptr', 'row', 'col', 'etype', 'inv_deg', 'keep', 'node_ptr', 'pos', 'x')}
+    screen._build()                                       # no atomics: the same bits on every run
+    screen.check()
+    assert all(torch.equal(f[k], v) for k, v in again.items())
+
+
+def test_row_and_word_edges_on_a_line():
+    """Receptor atoms at (j, 0, 0), j = 0..129, crop radius 40, edge radius 2.5, ligands of one and two atoms on the
+    line at exactly representable places: kept counts 0, 1, 63, 64, 65, n_rec - 1 and n_rec, pairs at exactly the crop
+    radius (not kept), a kept run behind dropped atoms and two runs in different words."""
+    from pointvs_amd.screening import LibraryScreen
+    crop, r_edge = 40.0, 2.5
+    places = [(-40.0,), (-39.5,), (23.0,), (23.5,), (24.5,), (40.0, 90.0), (39.5, 90.0), (-30.0, 160.0), (100.0,)]
+    want = [0, 1, 63, 64, 65, N_REC - 1, N_REC, 19, 69]
+    rng = np.random.default_rng(5)
+    rec = torch.zeros((N_REC, 3))
+    rec[:, 0] = torch.arange(N_REC, dtype=torch.float32)
+    rec_feats = torch.from_numpy(rng.random((N_REC, 12)).astype(np.float32))
+    rec_feats[:, -1] = 1
+    slots = []
+    for xs in places:
+        pose = torch.zeros((len(xs), 3))
+        pose[:, 0] = torch.tensor(xs)
+        feats = torch.from_numpy(rng.random((len(xs), 12)).astype(np.float32))
+        feats[:, -1] = 0
+        slots.append((feats, pose))
+    complexes = _cropped(slots, rec, rec_feats, crop)
+    assert [len(k) for _, _, k in complexes] == want
+    masks = [ref.keep_mask(pose.numpy(), rec.numpy(), crop) for _, pose in slots]
+    assert not masks[0][0] and not masks[2][63] and not masks[5][0]                  # exactly 40 away: not kept
+    assert masks[2][62] and masks[3][63] and masks[4][64] and masks[6][0]
+    assert np.flatnonzero(masks[8])[0] == 61                                          # a run behind dropped atoms
+    assert np.flatnonzero(masks[7]).tolist() == list(range(10)) + list(range(121, 130))      # words 0 | 1 and 2
+    screen = LibraryScreen(_model(), rec.cuda(), rec_feats, len(slots), 2, r_edge, crop_radius=crop)
+    f = screen.load(slots)._build()
+    screen.check()
+    torch.cuda.synchronize()
+    _assert_exact(screen, f, slots, complexes, r_edge, None)
+
+
+def test_a_crop_that_drops_nothing_gives_the_uncropped_batch():
+    """crop_radius = 1e6: the full CSR and the node tables are the uncropped LibraryScreen's, array for array."""
+    from pointvs_amd.screening import LibraryScreen
+    lig, rec, lig_feats, rec_feats = _set(6002)
+    sizes = (1, 64, 12, 7, 33, 20)                        # (no empty slot: it keeps nothing, cropped)
+    slots = _slots(lig, lig_feats, sizes, seed=30, rec=rec)
+    model = _model()
+    for r_inter, r_intra in ((7.0, None), (6.0, 2.5)):
+        plain = LibraryScreen(model, rec.cuda(), rec_feats, len(sizes), 64, r_inter, r_intra).load(slots)
+        want = plain._build()
+        plain.check()
+        screen = LibraryScreen(model, rec.cuda(), rec_feats, len(sizes), 64, r_inter, r_intra, crop_radius=1e6)
+        f = screen.load(slots)._build()
+        screen.check()
+        e = int(want['rowptr'][screen.n_cap])
+        assert e > 0 and f['cap'] == want['cap']
+        for k in ('rowptr', 'inv_deg', 'node_ptr', 'node_graph', 'pos', 'x'):
+            assert torch.equal(f[k], want[k]), k
+        for k in ('row', 'col', 'etype'):
+            assert torch.equal(f[k][:e], want[k][:e]), k
+        full = torch.from_numpy(ref.mask_words(np.ones(N_REC, dtype=bool)).view(np.int64))
+        assert torch.equal(screen.keep.cpu(), full.expand(len(sizes), -1))
+
+
+FLAG_SETS = [dict(), dict(edge_attention=True, node_attention=True, tanh=True, residual=True),
+             dict(k=64, normalize=True, graphnorm=True), dict(edge_attention=True, softmax_attention=True)]
+
+
+@pytest.mark.parametrize('flags', FLAG_SETS)
+def test_cropped_screen_matches_the_plain_forward_on_the_cropped_complexes(flags):
+    """Two consecutive mixed batches == model(Batch) of the cropped complexes built from oracle edge lists (rel 1e-5,
+    the bound of the screening paths). The batches hold an empty slot and a ligand that keeps no receptor atom."""
+    from pointvs_amd.graph import Batch
+    from pointvs_amd.screening import LibraryScreen
+    crop = 8.0
+    lig, rec, lig_feats, rec_feats = _set(6003)
+    model = _model(1, num_layers=3, **flags)
+    screen = LibraryScreen(model, rec.cuda(), rec_feats, len(SIZES), 64, 7.0, crop_radius=crop,
+                           padded_graphnorm=bool(flags.get('graphnorm')))
+    for k, sizes in enumerate((SIZES, (20, 0, 64, 33, 1, 7))):
+        slots = _slots(lig, lig_feats, sizes, seed=40 + 10 * k, rec=rec)
+        complexes = _cropped(slots, rec, rec_feats, crop)
+        assert any(0 < len(kept) < N_REC for _, _, kept in complexes)
+        fast = screen(slots).reshape(-1)
+        assert fast.shape[0] == len(sizes)
+        with torch.no_grad():
+            slow = model(Batch.from_data_list(_oracle_items(complexes, 7.0, 7.0)).to('cuda')).reshape(-1)
+        err = float((fast - slow).abs().max() / slow.abs().max().clamp_min(1e-30))
+        print(f'{flags} batch {k}: max|fast-slow|/max|slow| = {err:.3e}')
+        assert err < 1e-5, err
+    screen.check()
+
+
+def test_cropped_screen_equals_the_data_root_path():
+    """Receptor 10498 of tests/golden/dataroot with its two ligands (38 and 20 atoms): features and coordinates from a
+    dataset whose radius keeps everything; the screen with crop_radius = 10 has the rows (x and pos, exactly) and the
+    edge lists of build_batch with radius = 10, and its scores within 1e-5. The data root crops in fp64 on its fp64
+    coordinates, the screen on the fp32 ones: the test first asserts that both keep the same atoms here."""
+    from pathlib import Path
+    from pointvs_amd.parquet_data import PygPointCloudDataset
+    from pointvs_amd.screening import LibraryScreen
+    root = Path(__file__).resolve().parent / 'golden' / 'dataroot'
+    kw = dict(types_fname=root / 'chembl6.types', edge_radius=4, estimate_bonds=False, use_atomic_numbers=True,
+              polar_hydrogens=True, compact=True, rot=False)
+    everything, cropped = PygPointCloudDataset(root, radius=1e6, **kw), PygPointCloudDataset(root, radius=10, **kw)
+    for item, n_lig, n_kept in ((0, 38, 372), (1, 20, 337)):      # host precondition: fp32 and fp64 keep sets agree
+        lig64, rec64 = cropped.ligand_coordinates(item), cropped.receptor_coordinates(item)
+        k64 = ref.keep_mask(lig64, rec64, 10)
+        k32 = ref.keep_mask(lig64.astype(np.float32), rec64.astype(np.float32), 10)
+        assert lig64.shape[0] == n_lig and rec64.shape[0] == 2061 and int(k64.sum()) == n_kept
+        assert np.array_equal(k64, k32)
+    whole = everything.build_batch([0, 1], device='cuda:0')
+    want = cropped.build_batch([0, 1], device='cuda:0')
+    assert whole.graph_node_counts == [38 + 2061, 20 + 2061] and want.graph_node_counts == [38 + 372, 20 + 337]
+    x, pos, ptr = whole.x.cpu(), whole.pos.cpu(), whole.ptr.tolist()
+    rec, rec_feats = pos[ptr[0] + 38:ptr[1]].contiguous(), x[ptr[0] + 38:ptr[1]].contiguous()
+    assert torch.equal(rec, pos[ptr[1] + 20:ptr[2]]) and torch.equal(rec_feats, x[ptr[1] + 20:ptr[2]])
+    assert bool((rec_feats[:, -1] == 1).all()) and bool((x[:38, -1] == 0).all())
+    slots = [(x[ptr[0]:ptr[0] + 38], pos[ptr[0]:ptr[0] + 38]), (x[ptr[1]:ptr[1] + 20], pos[ptr[1]:ptr[1] + 20])]
+    model = _model(4, num_layers=3, dim_input=int(x.shape[1]))
+    screen = LibraryScreen(model, rec.cuda(), rec_feats, 2, 38, 4.0, crop_radius=10.0)
+    fast = screen(slots).reshape(-1)
+    screen.check()
+    f, n = screen._fast, sum(want.graph_node_counts)
+    assert f['node_ptr'].cpu().tolist() == want.ptr.tolist()
+    assert torch.equal(f['x'][:n], want.x) and torch.equal(f['pos'][:n], want.pos)
+    e = int(f['rowptr'][screen.n_cap])
+    rows, cols = want.edge_index.cpu().numpy()
+    attrs = want.edge_attr.argmax(1).cpu().numpy()
+    order = np.argsort(rows, kind='stable')               # (graphs are consecutive: one stable gather for the batch)
+    assert e == len(rows)
+    assert np.array_equal(f['row'][:e].cpu().numpy(), rows[order])
+    assert np.array_equal(f['col'][:e].cpu().numpy(), cols[order])
+    assert np.array_equal(f['etype'][:e].cpu().numpy(), attrs[order])
+    with torch.no_grad():
+        slow = model(want).reshape(-1)
+    err = float((fast - slow).abs().max() / slow.abs().max().clamp_min(1e-30))
+    print(f'data root: max|fast-slow|/max|slow| = {err:.3e}')
+    assert err < 1e-5, err
+
+
+@needs_caching_allocator
+def test_captured_cropped_step_replays_across_compositions():
+    """ONE captured step, replayed on four compositions (other sizes, an empty trailing slot, sizes summing to L_cap)
+    == a second, eager cropped screen on the same batches, bit for bit."""
+    from pointvs_amd.screening import LibraryScreen
+    lig, rec, lig_feats, rec_feats = _set(6004)
+    model = _model(2, num_layers=3, residual=True, edge_attention=True, tanh=True)
+    comps = [(7, 20, 3), (5, 17, 1), (12, 9), (20, 20, 20)]           # B = 3, L_cap = 60
+    batches = [_slots(lig, lig_feats, sizes, seed=70 + 10 * k, special=False) for k, sizes in enumerate(comps)]
+    eager = LibraryScreen(model, rec.cuda(), rec_feats, 3, 20, 7.0, crop_radius=6.0)
+    want, masks = [], []
+    for slots in batches:                                             # (first batch first: the same probe)
+        want.append(eager(slots).reshape(-1).clone())
+        masks.append(eager.keep.clone())
+    eager.check()
+    assert any(0 < len(kept) < N_REC for _, _, kept in _cropped(batches[0], rec, rec_feats, 6.0))
+    graph = LibraryScreen(model, rec.cuda(), rec_feats, 3, 20, 7.0, crop_radius=6.0).capture(batches[0])
+    for k in (2, 3, 1, 0):
+        got = graph.replay(batches[k]).reshape(-1).clone()
+        assert torch.equal(got, want[k]), k
+        assert torch.equal(graph.keep, masks[k]), k
+    graph.check()
+
+
+def test_tasks_of_a_two_headed_model_on_a_cropped_screen():
+    """tasks='both' on a cropped screen: [B, 1 + A], pose logit first, == the model's own forward on the cropped
+    complexes under each of its tasks (rel 1e-5); 'pose' and 'affinity' are its columns bit for bit."""
+    from pointvs_amd.egnn_multitask import MultitaskSatorrasEGNN
+    from pointvs_amd.graph import Batch
+    from pointvs_amd.screening import LibraryScreen
+    crop = 8.0
+    torch.manual_seed(3)
+    model = MultitaskSatorrasEGNN(tempfile.mkdtemp(), 2e-3, 1e-4, silent=True,
+                                  **dict(KW, num_layers=3, dim_output=3, final_softplus=True)).eval()
+    lig, rec, lig_feats, rec_feats = _set(6003)
+    slots = _slots(lig, lig_feats, SIZES, seed=40, rec=rec)
+    screens = {t: LibraryScreen(model, rec.cuda(), rec_feats, len(SIZES), 64, 7.0, tasks=t, crop_radius=crop)
+               for t in ('both', 'pose', 'affinity')}
+    both = screens['both'](slots).clone()
+    assert both.shape == (len(SIZES), 4)
+    assert torch.equal(screens['pose'](slots), both[:, :1]) and torch.equal(screens['affinity'](slots), both[:, 1:])
+    items, out = _oracle_items(_cropped(slots, rec, rec_feats, crop), 7.0, 7.0), []
+    try:      # the model's own forward, once per task
+        for name in ('classification', 'regression'):
+            model.set_task(name)
+            with torch.no_grad():
+                out.append(model(Batch.from_data_list(items).to('cuda')).reshape(len(slots), -1))
+    finally:
+        model.set_task('classification')
+    slow = torch.cat(out, 1)
+    err = float((both - slow).abs().max() / slow.abs().max().clamp_min(1e-30))
+    print(f'tasks=both: max|fast-slow|/max|slow| = {err:.3e}')
+    assert err < 1e-5, err
+    for screen in screens.values():
+        screen.check()
+    assert model.model_task == 'classification'
+
+
+def test_what_a_cropped_screen_refuses():
+    from pointvs_amd.screening import LibraryScreen, ScreeningSweep
+    lig, rec, lig_feats, rec_feats = _set(6004)
+    args = (rec.cuda(), rec_feats, 3, 20, 7.0)
+    for extra in (dict(struck=True), dict(cam=True), dict(contact_attention=1)):
+        with pytest.raises(ValueError, match=next(iter(extra))):
+            LibraryScreen(_model(2, edge_attention=True), *args, crop_radius=6.0, **extra)
+    with pytest.raises(ValueError, match='padded_graphnorm=True'):
+        LibraryScreen(_model(2, graphnorm=True), *args, crop_radius=6.0)
+    with pytest.raises(NotImplementedError, match='edge_residual'):
+        LibraryScreen(_model(2, edge_residual=True), *args, crop_radius=6.0)
+    with pytest.raises(NotImplementedError, match='hidden size 16'):
+        LibraryScreen(_model(2, k=16), *args, crop_radius=6.0)
+    with pytest.raises(ValueError, match='positive'):
+        LibraryScreen(_model(2), *args, crop_radius=0.0)
+    sweep = ScreeningSweep(_model(2), rec.cuda(), rec_feats, edge_radius=6.0, batch_size=4, crop_radius=8.0)
+    item = [('ligA', lig_feats[:12], lig[:12])]
+    for method in (sweep.ligand_atom_masking, sweep.contact_masking, sweep.receptor_atom_masking,
+                   sweep.receptor_hotspots):
+        with pytest.raises(NotImplementedError, match='crop'):
+            method(item)
+
+
+@needs_caching_allocator
+def test_cropped_run_library_end_to_end(tmp_path):
+    """Five ligands (12, 9, 70, 12, 1 atoms; 7, 5, 3, 4, 2 poses), batch of 4, max_lig_atoms 64: the 70-atom ligand
+    takes a cropped screen of its own size, the others 5 dense mixed batches; predictions and hits lines == the scores
+    of an eager cropped screen on the same batches, in library order."""
+    from pointvs_amd.predictions import format_hit_lines
+    from pointvs_amd.screening import LibraryScreen, ScreeningSweep, plan_library
+    from pointvs_amd.synthetic import random_poses
+    crop = 8.0
+    lig, rec, lig_feats, rec_feats = _set(6005, n_lig=70)
+    model = _model(2, num_layers=3)
+    ligs = [('ligA', lig_feats[:12], lig[:12], 7), ('ligB', lig_feats[:9].roll(1, 0), lig[:9] * 0.9, 5),
+            ('ligC', lig_feats, lig, 3), ('ligD', lig_feats[:12].roll(3, 0), lig[:12].flip(0), 4),
+            ('ligE', lig_feats[5:6], lig[5:6], 2)]
+    work = [(name, f, random_poses(pos, n, seed=20 + k, max_shift=3.0).cuda())
+            for k, (name, f, pos, n) in enumerate(ligs)]
+    sweep = ScreeningSweep(model, rec.cuda(), rec_feats, edge_radius=6.0, batch_size=4, crop_radius=crop)
+    got = sweep.run_library(work, predictions_file=tmp_path / 'library.txt', hits_file=tmp_path / 'hits.txt')
+    assert sweep.buckets == {} and sorted(sweep.crop_buckets) == [70] and sweep.library.crop_radius == crop
+    assert sweep.batches_run == 1 + 5
+    assert list(got) == [name for name, _, _ in work]
+    # the same batches through eager cropped screens
+    small = [w for w in work if w[2].shape[1] <= 64]
+    plan = plan_library([w[2].shape[0] for w in small], [w[2].shape[1] for w in small], 4, 64)
+    screen = LibraryScreen(model, rec.cuda(), rec_feats, 4, 12, 6.0, crop_radius=crop)
+    raw = {name: [None] * poses.shape[0] for name, _, poses in work}
+    for batch in plan:
+        y = screen([(small[l][1], small[l][2][p].cpu()) for l, p in batch]).reshape(4, -1).clone()
+        for slot, (l, p) in enumerate(batch):
+            raw[small[l][0]][p] = y[slot]
+    screen.check()
+    big = LibraryScreen(model, rec.cuda(), rec_feats, 4, 70, 6.0, crop_radius=crop)
+    y = big([(work[2][1], pose.cpu()) for pose in work[2][2]]).reshape(4, -1).clone()
+    big.check()
+    raw['ligC'] = [y[p] for p in range(3)]
+    lines = (tmp_path / 'library.txt').read_text().splitlines()
+    assert len(lines) == 21
+    at, best, rows = 0, [], []
+    for name, _, poses in work:
+        want = torch.sigmoid(torch.stack(raw[name]))
+        assert torch.equal(got[name], want), name
+        for k in range(poses.shape[0]):
+            assert lines[at] == f'{float(want[k, 0]):.3f} | receptor {name}_pose{k}'
+            at += 1
+        top = int(torch.stack(raw[name])[:, 0].argmax())
+        best.append(top)
+        rows.append(want[top].cpu().numpy())
+        assert sweep.hits[name][0] == top
+    assert (tmp_path / 'hits.txt').read_text().splitlines() == format_hit_lines(
+        best, np.stack(rows), 'receptor', [name for name, _, _ in work])
+    assert [name for name, _, _ in sweep.best_poses(work)] == [name for name, _, _ in work]
+    # run() on a cropped sweep is the same path (other batch mates and edge room: fp32 summation order may differ)
+    again = ScreeningSweep(model, rec.cuda(), rec_feats, edge_radius=6.0, batch_size=4, crop_radius=crop).run(work[:2])
+    assert list(again) == ['ligA', 'ligB'] and again['ligA'].shape == got['ligA'].shape
+    assert float((again['ligA'] - got['ligA']).abs().max()) < 1e-5 * float(got['ligA'].abs().max())
