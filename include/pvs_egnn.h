@@ -360,51 +360,38 @@ int pvs_screen_graph_build(const float* lig_pos, const float* rec_pos, const int
                            int32_t* status, void* state, size_t state_bytes, pvs_stream_t stream);
 
 /* Library batches: the same graphs for a batch whose n_slots slots hold one pose each of DIFFERENT ligands
- * (0..64 atoms per slot, 0 = the receptor alone) against the one receptor. No host argument depends on the
- * batch's composition, so one captured step serves every batch of a library.
+ * (0..slot_cap atoms per slot, 0 = the receptor alone) against the one receptor, described by one job
+ * (PvsScreenSlotsJob below). No field depends on the batch's composition, so one captured step serves every batch of a
+ * library.
  *   lig_pos [lig_cap,3]: the ligand atoms of all slots, packed; lig_ptr [n_slots+1] (device, int32, lig_ptr[0] = 0):
- *     slot p holds the atoms lig_ptr[p] .. lig_ptr[p+1]; lig_ptr[n_slots] <= lig_cap <= 64 * n_slots.
+ *     slot p holds the atoms lig_ptr[p] .. lig_ptr[p+1]; lig_ptr[n_slots] <= lig_cap <= slot_cap * n_slots, slot_cap =
+ *     1..1024 (ceil(slot_cap / 64) ligand-ligand mask words per packed atom in the state).
  *   Node layout (compact): slot p owns the nodes node_ptr[p] .. node_ptr[p+1], node_ptr[p] = lig_ptr[p] + p * n_rec,
  *     its ligand atoms first, then the n_rec receptor atoms. The nodes from node_ptr[n_slots] up to
  *     N_cap = lig_cap + n_slots * n_rec are padding: degree 0, inv_deg 1, graph id -1, zero rows in every table.
- *   Outputs as the call above over N_cap nodes (rowptr / rowptr_lig [N_cap+1], inv_deg [N_cap]; edges, classes and
- *     in-row order per slot those of generate_edges; both edge counts on the device), plus the node tables of the layer
- *     stack: node_ptr [n_slots+1] (= the batch's graph ptr), node_graph [N_cap], pos [N_cap,3] and, where `tables` is
- *     given, feats [N_cap,n_feats] (ligand rows from lig_feats [lig_cap,n_feats], receptor rows from rec_feats
- *     [n_rec,n_feats]; feats may be NULL) and the first-layer receptor sums base_magg [N_cap,hidden], base_xsum
- *     [N_cap,3], base_deg [N_cap] expanded from rec_magg / rec_xsum / rec_deg [n_rec,.] with zeros on ligand and
- *     padding rows (base_magg may be NULL: none of the three is written).
+ *   Outputs as the call above over N_cap nodes (full.rowptr / lig.rowptr [N_cap+1], inv_deg [N_cap]; edges, classes and
+ *     in-row order per slot those of generate_edges; both edge counts on the device; `full` and `lig` have room for
+ *     their `capacity` edges), plus the node tables of the layer stack: node_ptr [n_slots+1] (= the batch's graph ptr),
+ *     node_graph [N_cap], pos [N_cap,3] and, from `tables`, feats [N_cap,n_feats] (ligand rows from lig_feats
+ *     [lig_cap,n_feats], receptor rows from rec_feats [n_rec,n_feats]; feats may be NULL) and the first-layer receptor
+ *     sums base_magg [N_cap,hidden], base_xsum [N_cap,3], base_deg [N_cap] expanded from rec_magg / rec_xsum / rec_deg
+ *     [n_rec,.] with zeros on ligand and padding rows (base_magg may be NULL: none of the three is written).
  *   *status: bit 2 = a capacity was too small (no edge is written then); bit 3 = lig_ptr is not such a table (the
- *     outputs then describe N_cap padding nodes and no edge).
- * The _cap pair is the same builder for slots of 0..slot_cap atoms, slot_cap = 1..1024 (lig_cap <= slot_cap * n_slots;
- * ceil(slot_cap / 64) ligand-ligand mask words per packed atom in the state); the pair without it is slot_cap = 64. */
+ *     outputs then describe N_cap padding nodes and no edge). */
 typedef struct {
     int32_t n_feats, hidden;
     const float *lig_feats, *rec_feats;
     const float *rec_magg, *rec_xsum, *rec_deg;
     float *feats, *base_magg, *base_xsum, *base_deg;
 } PvsRaggedNodeTables;
-size_t pvs_screen_graph_ragged_state_bytes(int32_t n_slots, int32_t lig_cap, int32_t n_rec);
-int pvs_screen_graph_build_ragged(const float* lig_pos, const int32_t* lig_ptr, const float* rec_pos,
-                                  const int32_t* rr_rowptr, const int32_t* rr_col, int32_t n_slots, int32_t lig_cap,
-                                  int32_t n_rec, double inter_radius, double intra_radius, int32_t capacity,
-                                  int32_t capacity_lig, int32_t* rowptr, int32_t* row, int32_t* col, uint8_t* etype,
-                                  float* inv_deg, int32_t* rowptr_lig, int32_t* row_lig, int32_t* col_lig,
-                                  uint8_t* etype_lig, int32_t* node_ptr, int32_t* node_graph, float* pos,
-                                  const PvsRaggedNodeTables* tables, int32_t* status, void* state,
-                                  size_t state_bytes, pvs_stream_t stream);
-size_t pvs_screen_graph_ragged_cap_state_bytes(int32_t n_slots, int32_t lig_cap, int32_t n_rec, int32_t slot_cap);
-int pvs_screen_graph_build_ragged_cap(const float* lig_pos, const int32_t* lig_ptr, const float* rec_pos,
-                                      const int32_t* rr_rowptr, const int32_t* rr_col, int32_t n_slots,
-                                      int32_t lig_cap, int32_t n_rec, int32_t slot_cap, double inter_radius,
-                                      double intra_radius, int32_t capacity, int32_t capacity_lig, int32_t* rowptr,
-                                      int32_t* row, int32_t* col, uint8_t* etype, float* inv_deg,
-                                      int32_t* rowptr_lig, int32_t* row_lig, int32_t* col_lig, uint8_t* etype_lig,
-                                      int32_t* node_ptr, int32_t* node_graph, float* pos,
-                                      const PvsRaggedNodeTables* tables, int32_t* status, void* state,
-                                      size_t state_bytes, pvs_stream_t stream);
 
-/* Struck slots: pvs_screen_graph_build_ragged_cap plus rec_drop [n_slots] (int32, DEVICE): -1, or the receptor atom
+/* One CSR a builder writes: rowptr [N_cap+1], row / col / etype with room for `capacity` edges. */
+typedef struct PvsCsrOut { int32_t *rowptr, *row, *col; uint8_t* etype; int32_t capacity; } PvsCsrOut;
+
+/* What a slot of the batch is. The layout is stated, never inferred from which pointers are set: a field that the
+ * stated layout does not take must be NULL / 0, and a field it needs must be there.
+ *
+ * PVS_SLOTS_STRUCK: PVS_SLOTS_RAGGED plus rec_drop [n_slots] (int32, DEVICE): -1, or the receptor atom
  * r in 0..n_rec-1 that the slot's receptor lacks (receptor-atom and contact masking of a sweep's hits:
  * attribution_fns.py atom_masking / bond_masking remove atoms together with their edges). A struck slot owns
  * n_lig + n_rec - 1 rows - its ligand atoms, then the receptor atoms in order without r - so node_ptr[p] = lig_ptr[p] +
@@ -413,20 +400,10 @@ int pvs_screen_graph_build_ragged_cap(const float* lig_pos, const int32_t* lig_p
  * the new degrees. A receptor row that had r in its template row cannot start from the cached receptor sums: its
  * base_magg / base_xsum / base_deg are zero and its row of the ligand-touching CSR is its WHOLE row (ligand entries,
  * then the class-2 entries that remain); every other row is as without rec_drop. With every entry -1 all outputs are
- * those of pvs_screen_graph_build_ragged_cap. *status as there; bit 3 also for an entry of rec_drop outside
- * -1..n_rec-1 (an edgeless batch). capacity_lig needs room for the whole rows of the touched receptor rows. */
-size_t pvs_screen_graph_struck_state_bytes(int32_t n_slots, int32_t lig_cap, int32_t n_rec, int32_t slot_cap);
-int pvs_screen_graph_build_struck(const float* lig_pos, const int32_t* lig_ptr, const int32_t* rec_drop,
-                                  const float* rec_pos, const int32_t* rr_rowptr, const int32_t* rr_col,
-                                  int32_t n_slots, int32_t lig_cap, int32_t n_rec, int32_t slot_cap,
-                                  double inter_radius, double intra_radius, int32_t capacity, int32_t capacity_lig,
-                                  int32_t* rowptr, int32_t* row, int32_t* col, uint8_t* etype, float* inv_deg,
-                                  int32_t* rowptr_lig, int32_t* row_lig, int32_t* col_lig, uint8_t* etype_lig,
-                                  int32_t* node_ptr, int32_t* node_graph, float* pos,
-                                  const PvsRaggedNodeTables* tables, int32_t* status, void* state, size_t state_bytes,
-                                  pvs_stream_t stream);
-
-/* Cropped slots: pvs_screen_graph_build_ragged_cap where slot p keeps receptor atom j only if one of the slot's ligand
+ * those of PVS_SLOTS_RAGGED. *status as there; bit 3 also for an entry of rec_drop outside
+ * -1..n_rec-1 (an edgeless batch). lig.capacity needs room for the whole rows of the touched receptor rows.
+ *
+ * PVS_SLOTS_CROPPED: PVS_SLOTS_RAGGED where slot p keeps receptor atom j only if one of the slot's ligand
  * atoms is closer to it than crop_radius (> 0) - the crop of the training loader (data_loaders.py: make_box with
  * relative_to_ligand) per pose: fp64 on the fp32 coordinates, `<` strict and without a lower bound (a coincident atom is
  * kept); an empty slot keeps nothing. keep [n_slots, ceil(n_rec / 64)] (uint64, DEVICE, an output): bit j % 64 of word
@@ -434,21 +411,29 @@ int pvs_screen_graph_build_struck(const float* lig_pos, const int32_t* lig_ptr, 
  * compact: node_ptr[p + 1] = node_ptr[p] + n_lig_p + kept_p, padding from node_ptr[n_slots] up to N_cap = lig_cap +
  * n_slots * n_rec as above. The slot's graph is generate_edges on the cropped complex: ligand-touching edges by
  * distance, to kept atoms only (crop_radius may be below an edge radius); receptor-receptor edges from the template
- * where both ends are kept, renumbered by rank in the mask, no distance evaluated. Written: the full CSR (rowptr, row,
- * col, etype, inv_deg; edge count in rowptr[N_cap]), node_ptr, node_graph, pos, keep and tables->feats. NOT written:
- * the ligand-touching CSR (rowptr_lig .. etype_lig and capacity_lig are ignored and may be NULL / 0) and the base_*
- * tables (a row at the rim of the crop has lost template neighbours, so the receptor's first-layer sums are not its
- * sums). `capacity` as for the uncropped call bounds the cropped graph, which is a subset. *status as above. No
+ * where both ends are kept, renumbered by rank in the mask, no distance evaluated. Written: the full CSR (full.rowptr,
+ * row, col, etype, inv_deg; edge count in full.rowptr[N_cap]), node_ptr, node_graph, pos, keep and tables.feats. NOT
+ * written: the ligand-touching CSR (`lig` is ignored and may be all zero) and the base_* tables (ignored, whatever they
+ * hold: a row at the rim of the crop has lost template neighbours, so the receptor's first-layer sums are not its
+ * sums). full.capacity as for the uncropped layouts bounds the cropped graph, which is a subset. *status as above. No
  * atomics: the same bits on every run. */
-size_t pvs_screen_graph_cropped_state_bytes(int32_t n_slots, int32_t lig_cap, int32_t n_rec, int32_t slot_cap);
-int pvs_screen_graph_build_cropped(const float* lig_pos, const int32_t* lig_ptr, const float* rec_pos,
-                                   const int32_t* rr_rowptr, const int32_t* rr_col, int32_t n_slots, int32_t lig_cap,
-                                   int32_t n_rec, int32_t slot_cap, double inter_radius, double intra_radius,
-                                   double crop_radius, int32_t capacity, int32_t capacity_lig, int32_t* rowptr,
-                                   int32_t* row, int32_t* col, uint8_t* etype, float* inv_deg, int32_t* rowptr_lig,
-                                   int32_t* row_lig, int32_t* col_lig, uint8_t* etype_lig, int32_t* node_ptr,
-                                   int32_t* node_graph, float* pos, uint64_t* keep, const PvsRaggedNodeTables* tables,
-                                   int32_t* status, void* state, size_t state_bytes, pvs_stream_t stream);
+enum { PVS_SLOTS_RAGGED = 0, PVS_SLOTS_STRUCK = 1, PVS_SLOTS_CROPPED = 2 };
+typedef struct PvsScreenSlotsJob {
+    int32_t layout;                 /* PVS_SLOTS_* */
+    const float* lig_pos; const int32_t* lig_ptr; const int32_t* rec_drop;   /* rec_drop: STRUCK only */
+    const float* rec_pos; const int32_t *rr_rowptr, *rr_col;    /* the template as for pvs_screen_graph_build */
+    int32_t n_slots, lig_cap, n_rec, slot_cap;
+    double inter_radius, intra_radius, crop_radius;                          /* crop_radius: CROPPED only */
+    PvsCsrOut full, lig;            /* lig: the ligand-touching CSR; ignored by CROPPED */
+    float* inv_deg; int32_t *node_ptr, *node_graph; float* pos;
+    uint64_t* keep;                 /* CROPPED only */
+    PvsRaggedNodeTables tables;     /* by value; all zero = none */
+    int32_t* status;
+} PvsScreenSlotsJob;
+/* The bytes of `state` for the job's layout and counts (no pointer of the job is read); 0 for counts or a layout that
+ * pvs_screen_slots_build refuses. Every refusal of the build happens on the host, before anything is launched. */
+size_t pvs_screen_slots_state_bytes(const PvsScreenSlotsJob* job);
+int pvs_screen_slots_build(const PvsScreenSlotsJob* job, void* state, size_t state_bytes, pvs_stream_t stream);
 
 /* Complex batches: the node tables of B protein-ligand complexes built from a device-resident pool of structure
  * files, as the reference loader builds one sample on the host (data_loaders.py:259-309: ligand then receptor, crop of
@@ -677,7 +662,7 @@ int pvs_segment_argmax(const float* scores, int32_t n_cols, int32_t column, cons
                        int32_t* best, float* best_rows, pvs_stream_t stream);
 
 /* Leave-one-atom-out copies of a set of ligands as the slots of a pose batch (atom masking of a sweep's hits through
- * pvs_screen_graph_build_ragged_cap: attribution_fns.py:365-431 removes an atom together with its edges, which is the
+ * pvs_screen_slots_build: attribution_fns.py:365-431 removes an atom together with its edges, which is the
  * radius graph of the atoms that remain). lig_pos [n_rows, 3], lig_feats [n_rows, n_feats], lig_ptr [n_ligands + 1]
  * (DEVICE): ligand s has n_s = lig_ptr[s + 1] - lig_ptr[s] atoms and owns n_s + 1 consecutive copies - the whole
  * ligand, then the ligand without atom 0, without atom 1, ... (the remaining rows keep their order). Its first copy is
@@ -711,7 +696,7 @@ int pvs_contact_pairs_fill(const float* lig_pos, const int32_t* lig_ptr, int32_t
                            int32_t n_pairs, int32_t* pairs, pvs_stream_t stream);
 
 /* pvs_leave_out_ligand_pack for copies that leave out one ligand-receptor pair, the slots of
- * pvs_screen_graph_build_struck (attribution_fns.py bond_masking; with a = -1 or r = -1 a single atom). Hit s owns the
+ * pvs_screen_slots_build (PVS_SLOTS_STRUCK) (attribution_fns.py bond_masking; with a = -1 or r = -1 a single atom). Hit s owns the
  * rows pair_ptr[s] .. pair_ptr[s + 1] of pairs [n_pairs, 2] (a: ligand atom counted inside the hit or -1; r: receptor
  * atom or -1) and one copy more than rows: the whole ligand, then one copy per row. Its first copy is number
  * pair_ptr[s] + s. Slot k holds copy first_copy[0] + k: the hit's rows without atom a in out_pos / out_feats, out_ptr as
@@ -729,7 +714,7 @@ int pvs_leave_out_pair_pack(const float* lig_pos, const float* lig_feats, const 
 /* Contact attention of a pose batch (the reference's attribution/hotspot.py over attribution_fns.edge_attention,
  * :278-295: per atom the largest attention value over its ligand-receptor edges, per receptor atom the mean of these
  * over the binding events in which it has a contact), reduced on the device over the compact pose-batch layout of
- * pvs_screen_graph_build_ragged_cap: slot p owns the rows node_ptr[p] .. node_ptr[p + 1] (node_ptr[p] = lig_ptr[p] +
+ * pvs_screen_slots_build: slot p owns the rows node_ptr[p] .. node_ptr[p + 1] (node_ptr[p] = lig_ptr[p] +
  * p * n_rec; node_ptr, lig_ptr: DEVICE, [n_slots + 1]), its lig_ptr[p + 1] - lig_ptr[p] ligand atoms first, then the
  * n_rec receptor atoms. rowptr [n_nodes + 1] / etype [n_edges] are either CSR of such a batch (the ligand-touching one
  * or the full one) and att [n_edges] one attention value per edge in THAT CSR's order. An edge counts when its class

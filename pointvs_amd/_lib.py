@@ -56,6 +56,26 @@ class PvsRaggedNodeTables(C.Structure):
         'lig_feats', 'rec_feats', 'rec_magg', 'rec_xsum', 'rec_deg', 'feats', 'base_magg', 'base_xsum', 'base_deg')]
 
 
+class PvsCsrOut(C.Structure):
+    _fields_ = [('rowptr', C.c_void_p), ('row', C.c_void_p), ('col', C.c_void_p), ('etype', C.c_void_p),
+                ('capacity', C.c_int32)]
+
+
+SLOTS_RAGGED, SLOTS_STRUCK, SLOTS_CROPPED = 0, 1, 2       # PVS_SLOTS_* (pvs_egnn.h)
+
+
+class PvsScreenSlotsJob(C.Structure):
+    """The pose-batch slot builders' job, field for field as pvs_egnn.h declares it (tests/test_screen_job_host.py
+    compares every offset with the C compiler's). Pointer fields take a device address (`ptr(tensor)`) or None."""
+    _fields_ = ([('layout', C.c_int32)] +
+                [(name, C.c_void_p) for name in ('lig_pos', 'lig_ptr', 'rec_drop', 'rec_pos', 'rr_rowptr', 'rr_col')] +
+                [(name, C.c_int32) for name in ('n_slots', 'lig_cap', 'n_rec', 'slot_cap')] +
+                [(name, C.c_double) for name in ('inter_radius', 'intra_radius', 'crop_radius')] +
+                [('full', PvsCsrOut), ('lig', PvsCsrOut)] +
+                [(name, C.c_void_p) for name in ('inv_deg', 'node_ptr', 'node_graph', 'pos', 'keep')] +
+                [('tables', PvsRaggedNodeTables), ('status', C.c_void_p)])
+
+
 class PvsComplexPool(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in ('rec_xyz', 'lig_xyz', 'rec_types', 'lig_types', 'rec_z', 'lig_z',
                                                 'rec_ptr', 'lig_ptr')] + [('n_rec', C.c_int32), ('n_lig', C.c_int32)]
@@ -117,25 +137,8 @@ _PROTOTYPES = {
     'pvs_screen_graph_build': (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 3 + [C.c_double, C.c_double, C.c_int32,
                                                                               C.c_int32] + [C.c_void_p] * 10 +
                                [C.c_void_p, C.c_size_t, C.c_void_p]),
-    'pvs_screen_graph_ragged_state_bytes': (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
-    'pvs_screen_graph_build_ragged': (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 3 + [C.c_double, C.c_double, C.c_int32,
-                                                                                     C.c_int32] + [C.c_void_p] * 12 +
-                                      [C.POINTER(PvsRaggedNodeTables), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    'pvs_screen_graph_ragged_cap_state_bytes': (C.c_size_t, [C.c_int32] * 4),
-    'pvs_screen_graph_build_ragged_cap': (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 4 + [C.c_double, C.c_double,
-                                                                                         C.c_int32, C.c_int32] +
-                                          [C.c_void_p] * 12 + [C.POINTER(PvsRaggedNodeTables), C.c_void_p, C.c_void_p,
-                                                               C.c_size_t, C.c_void_p]),
-    'pvs_screen_graph_struck_state_bytes': (C.c_size_t, [C.c_int32] * 4),
-    'pvs_screen_graph_build_struck': (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 4 + [C.c_double, C.c_double, C.c_int32,
-                                                                                     C.c_int32] +
-                                      [C.c_void_p] * 12 + [C.POINTER(PvsRaggedNodeTables), C.c_void_p, C.c_void_p,
-                                                           C.c_size_t, C.c_void_p]),
-    'pvs_screen_graph_cropped_state_bytes': (C.c_size_t, [C.c_int32] * 4),
-    'pvs_screen_graph_build_cropped': (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 4 + [C.c_double] * 3 +
-                                       [C.c_int32, C.c_int32] + [C.c_void_p] * 13 +
-                                       [C.POINTER(PvsRaggedNodeTables), C.c_void_p, C.c_void_p, C.c_size_t,
-                                        C.c_void_p]),
+    'pvs_screen_slots_state_bytes': (C.c_size_t, [C.POINTER(PvsScreenSlotsJob)]),
+    'pvs_screen_slots_build': (C.c_int, [C.POINTER(PvsScreenSlotsJob), C.c_void_p, C.c_size_t, C.c_void_p]),
     'pvs_mask_graph_workspace_bytes': (C.c_size_t, [C.c_int32, C.c_int32]),
     'pvs_mask_graph_build': (C.c_int, [C.POINTER(PvsGraph), C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32] +
                              [C.c_void_p] * 9 + [C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -251,7 +254,7 @@ _PROTOTYPES = {
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)
-MIN_VERSION = 112       # pvs_version() of the library these prototypes describe (112: GraphNorm over a device row count)
+MIN_VERSION = 113       # pvs_version() of the library these prototypes describe (113: the slot builders take one job)
 _lib = None
 
 

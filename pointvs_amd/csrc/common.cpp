@@ -12,4 +12,4 @@ void pvs_set_error(const char* fmt, ...) {
 }
 
 extern "C" const char* pvs_last_error(void) { return g_err; }
-extern "C" int pvs_version(void) { return 112; }
+extern "C" int pvs_version(void) { return 113; }

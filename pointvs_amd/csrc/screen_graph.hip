@@ -16,6 +16,7 @@
 #include "common.h"
 #include "profile.h"
 #include "radius_common.h"
+#include "screen_job.h"
 #include "screen_slots.h"
 #include <hipcub/hipcub.hpp>
 #include <type_traits>
@@ -343,8 +344,8 @@ extern "C" int pvs_screen_graph_build(const float* lig_pos, const float* rec_pos
 }
 
 // ---- library batches: every slot of the batch holds one pose of ANY ligand of 0..slot_cap atoms ----
-// pvs_screen_graph_build_ragged_cap (and pvs_screen_graph_build_ragged: the same with slot_cap = 64): the same graphs for a batch whose B slots hold poses of different
-// ligands (a docking library: thousands of ligands of 8-60 atoms with ~10 poses each). The ligand atoms
+// pvs_screen_slots_build (PvsScreenSlotsJob, layout PVS_SLOTS_RAGGED): the same graphs for a batch whose B slots hold
+// poses of different ligands (a docking library: thousands of ligands of 8-60 atoms with ~10 poses each). The ligand atoms
 // come packed, lig_pos [L_cap,3] with the device table lig_ptr [B+1]; slot p has lig_ptr[p+1]-lig_ptr[p]
 // atoms (0 = receptor only). Compact node layout: slot p owns nodes node_ptr[p] .. node_ptr[p+1],
 // node_ptr[p] = lig_ptr[p] + p * n_rec, ligand atoms first, then the receptor; the nodes from node_ptr[B]
@@ -384,9 +385,15 @@ __global__ void k_slots(const int32_t* __restrict__ lig_ptr, int B, int L_cap, i
     for (int q = a0; q < a1; ++q) slot_of[q] = p;
 }
 
-// k_slots for struck slots: the same with rec_drop [B]. A struck slot has one row less, so node_ptr[p] also counts the
+// k_slots for struck slots (PVS_SLOTS_STRUCK; screen_slots.h: PvsStruckSlots): the same with rec_drop [B], -1 or the
+// receptor atom that the slot's receptor lacks. A struck slot has one row less, so node_ptr[p] also counts the
 // struck slots before p (a walk over the table per thread: B is a batch size); an entry of rec_drop outside
-// -1..n_rec-1 makes the whole table bad.
+// -1..n_rec-1 makes the whole table bad: *status bit 3 and an edgeless batch, as for a bad lig_ptr. The slot's graph is
+// what the reference's masking leaves of the unstruck slot's graph: the atom and every edge that touches it are gone,
+// the ids above it move down by one, classes and in-row order stay. A receptor row that had the atom as a template
+// neighbour can no longer start from the receptor's cached first-layer sums: its base is zero and its WHOLE row (ligand
+// entries, then the class-2 entries that remain) is in the ligand-touching CSR, which is all
+// pvs_egnn_layer_fwd_partial needs.
 __global__ void k_slots_struck(const int32_t* __restrict__ lig_ptr, const int32_t* __restrict__ rec_drop, int B,
                                int L_cap, int n_rec, int slot_cap, int32_t* __restrict__ node_ptr,
                                int32_t* __restrict__ slot_of, int32_t* __restrict__ status) {
@@ -461,131 +468,7 @@ k_node_tables_ragged(const float* __restrict__ lig_pos, const float* __restrict_
 
 }  // namespace
 
-extern "C" size_t pvs_screen_graph_ragged_cap_state_bytes(int32_t B, int32_t L_cap, int32_t n_rec,
-                                                          int32_t slot_cap) {
-    if (slot_cap < 1 || slot_cap > kPvsMaxSlotCap) return 0;
-    PvsArena a(nullptr, 0);
-    return carve_screen(a, (size_t)L_cap, L_cap + B * n_rec, n_rec, pvs_slot_words(slot_cap), true, nullptr) + 256;
-}
-
-namespace {
-// the ragged builder; with rec_drop (a device table [B]) its slots are struck slots
-int build_ragged(const char* who, const float* lig_pos, const int32_t* lig_ptr, const int32_t* rec_drop,
-                 const float* rec_pos, const int32_t* rr_rowptr, const int32_t* rr_col, int32_t B, int32_t L_cap,
-                 int32_t n_rec, int32_t slot_cap, double inter_radius, double intra_radius, int32_t capacity,
-                 int32_t capacity_lig, int32_t* rowptr, int32_t* row, int32_t* col, uint8_t* etype, float* inv_deg,
-                 int32_t* rowptr_lig, int32_t* row_lig, int32_t* col_lig, uint8_t* etype_lig, int32_t* node_ptr,
-                 int32_t* node_graph, float* pos, const PvsRaggedNodeTables* tables, int32_t* status, void* state,
-                 size_t state_bytes, pvs_stream_t stream_) {
-    hipStream_t s = (hipStream_t)stream_;
-    PVS_REQUIRE(lig_pos && lig_ptr && rec_pos && rr_rowptr && rr_col && rowptr && row && col && etype && inv_deg &&
-                rowptr_lig && row_lig && col_lig && etype_lig && node_ptr && node_graph && pos && status && state,
-                "%s: NULL", who);
-    PVS_REQUIRE(slot_cap >= 1 && slot_cap <= kPvsMaxSlotCap, "%s: slot_cap must be 1..%d (got %d)", who,
-                kPvsMaxSlotCap, slot_cap);
-    PVS_REQUIRE(B > 0 && L_cap > 0 && L_cap <= slot_cap * (int64_t)B && n_rec > 0, "%s: needs slots, 1..%d * slots "
-                "packed ligand atoms (got %d for %d) and a receptor", who, slot_cap, L_cap, B);
-    PVS_REQUIRE((int64_t)L_cap + (int64_t)B * n_rec < INT32_MAX, "%s: more than 2^31 nodes", who);
-    PvsRaggedNodeTables t = {};
-    if (tables) {
-        t = *tables;
-        PVS_REQUIRE(t.n_feats >= 0 && t.hidden >= 0, "%s: negative table width", who);
-        PVS_REQUIRE(!t.feats || (t.lig_feats && t.rec_feats && t.n_feats > 0), "%s: feature table without sources", who);
-        PVS_REQUIRE(!t.base_magg || (t.rec_magg && t.rec_xsum && t.rec_deg && t.base_xsum && t.base_deg && t.hidden > 0),
-                    "%s: receptor sums incomplete", who);
-    }
-    PvsArena arena(state, state_bytes);
-    ScreenState w;
-    carve_screen(arena, (size_t)L_cap, L_cap + B * n_rec, n_rec, pvs_slot_words(slot_cap), true, &w);
-    PVS_REQUIRE(arena.ok(), "%s: state too small (%zu < %zu)", who, state_bytes, arena.off);
-    PvsProfScope prof(s, PVS_PROF_PREPARE);
-    const OutCsr full{rowptr, row, col, etype, capacity}, lig{rowptr_lig, row_lig, col_lig, etype_lig, capacity_lig};
-    const int n_rows = L_cap + B * n_rec;
-    if (rec_drop) {
-        const PvsStruckSlots L{lig_ptr, node_ptr, w.slot_of, status, rec_drop, B, L_cap, n_rec, slot_cap};
-        k_slots_struck<<<(B + 1 + 255) / 256, 256, 0, s>>>(lig_ptr, rec_drop, B, L_cap, n_rec, slot_cap, node_ptr,
-                                                           w.slot_of, status);
-        PVS_CHECK_LAUNCH();
-        PVS_TRY(build_csrs(L, lig_pos, rec_pos, rr_rowptr, rr_col, inter_radius, intra_radius, rowptr, rowptr_lig, full,
-                           lig, inv_deg, status, false, w, s));
-        k_node_tables_ragged<<<(n_rows + 3) / 4, 256, 0, s>>>(lig_pos, rec_pos, L, rr_rowptr, rr_col, node_graph, pos, t);
-    } else {
-        const PvsRaggedSlots L{lig_ptr, node_ptr, w.slot_of, status, B, L_cap, n_rec, slot_cap};
-        k_slots<<<(B + 1 + 255) / 256, 256, 0, s>>>(lig_ptr, B, L_cap, n_rec, slot_cap, node_ptr, w.slot_of, status);
-        PVS_CHECK_LAUNCH();
-        PVS_TRY(build_csrs(L, lig_pos, rec_pos, rr_rowptr, rr_col, inter_radius, intra_radius, rowptr, rowptr_lig, full,
-                           lig, inv_deg, status, false, w, s));
-        k_node_tables_ragged<<<(n_rows + 3) / 4, 256, 0, s>>>(lig_pos, rec_pos, L, rr_rowptr, rr_col, node_graph, pos, t);
-    }
-    PVS_CHECK_LAUNCH();
-    return 0;
-}
-}  // namespace
-
-extern "C" int pvs_screen_graph_build_ragged_cap(const float* lig_pos, const int32_t* lig_ptr, const float* rec_pos,
-                                                 const int32_t* rr_rowptr, const int32_t* rr_col, int32_t B,
-                                                 int32_t L_cap, int32_t n_rec, int32_t slot_cap, double inter_radius,
-                                                 double intra_radius, int32_t capacity, int32_t capacity_lig,
-                                                 int32_t* rowptr, int32_t* row, int32_t* col, uint8_t* etype,
-                                                 float* inv_deg, int32_t* rowptr_lig, int32_t* row_lig,
-                                                 int32_t* col_lig, uint8_t* etype_lig, int32_t* node_ptr,
-                                                 int32_t* node_graph, float* pos, const PvsRaggedNodeTables* tables,
-                                                 int32_t* status, void* state, size_t state_bytes,
-                                                 pvs_stream_t stream_) {
-    return build_ragged("pvs_screen_graph_build_ragged_cap", lig_pos, lig_ptr, nullptr, rec_pos, rr_rowptr, rr_col, B,
-                        L_cap, n_rec, slot_cap, inter_radius, intra_radius, capacity, capacity_lig, rowptr, row, col,
-                        etype, inv_deg, rowptr_lig, row_lig, col_lig, etype_lig, node_ptr, node_graph, pos, tables,
-                        status, state, state_bytes, stream_);
-}
-
-// ---- struck slots: pvs_screen_graph_build_ragged_cap plus rec_drop [B] (int32, on the device): -1, or the receptor
-// atom that the slot's receptor lacks (screen_slots.h: PvsStruckSlots). The slot's graph is what the reference's masking
-// leaves of the unstruck slot's graph: the atom and every edge that touches it are gone, the ids above it move down by
-// one, classes and in-row order stay. A receptor row that had the atom as a template neighbour can no longer start from
-// the receptor's cached first-layer sums: its base is zero and its WHOLE row (ligand entries, then the class-2 entries
-// that remain) is in the ligand-touching CSR, which is all pvs_egnn_layer_fwd_partial needs. An entry outside
-// -1..n_rec-1: *status bit 3 and an edgeless batch, as for a bad lig_ptr. ----
-extern "C" size_t pvs_screen_graph_struck_state_bytes(int32_t B, int32_t L_cap, int32_t n_rec, int32_t slot_cap) {
-    return pvs_screen_graph_ragged_cap_state_bytes(B, L_cap, n_rec, slot_cap);
-}
-
-extern "C" int pvs_screen_graph_build_struck(const float* lig_pos, const int32_t* lig_ptr, const int32_t* rec_drop,
-                                             const float* rec_pos, const int32_t* rr_rowptr, const int32_t* rr_col,
-                                             int32_t B, int32_t L_cap, int32_t n_rec, int32_t slot_cap,
-                                             double inter_radius, double intra_radius, int32_t capacity,
-                                             int32_t capacity_lig, int32_t* rowptr, int32_t* row, int32_t* col,
-                                             uint8_t* etype, float* inv_deg, int32_t* rowptr_lig, int32_t* row_lig,
-                                             int32_t* col_lig, uint8_t* etype_lig, int32_t* node_ptr,
-                                             int32_t* node_graph, float* pos, const PvsRaggedNodeTables* tables,
-                                             int32_t* status, void* state, size_t state_bytes, pvs_stream_t stream_) {
-    PVS_REQUIRE(rec_drop, "pvs_screen_graph_build_struck: NULL rec_drop");
-    return build_ragged("pvs_screen_graph_build_struck", lig_pos, lig_ptr, rec_drop, rec_pos, rr_rowptr, rr_col, B,
-                        L_cap, n_rec, slot_cap, inter_radius, intra_radius, capacity, capacity_lig, rowptr, row, col,
-                        etype, inv_deg, rowptr_lig, row_lig, col_lig, etype_lig, node_ptr, node_graph, pos, tables,
-                        status, state, state_bytes, stream_);
-}
-
-// the pair from before slots could be wider than one mask word: slots of 0..64 atoms
-extern "C" size_t pvs_screen_graph_ragged_state_bytes(int32_t B, int32_t L_cap, int32_t n_rec) {
-    return pvs_screen_graph_ragged_cap_state_bytes(B, L_cap, n_rec, 64);
-}
-
-extern "C" int pvs_screen_graph_build_ragged(const float* lig_pos, const int32_t* lig_ptr, const float* rec_pos,
-                                             const int32_t* rr_rowptr, const int32_t* rr_col, int32_t B,
-                                             int32_t L_cap, int32_t n_rec, double inter_radius, double intra_radius,
-                                             int32_t capacity, int32_t capacity_lig, int32_t* rowptr, int32_t* row,
-                                             int32_t* col, uint8_t* etype, float* inv_deg, int32_t* rowptr_lig,
-                                             int32_t* row_lig, int32_t* col_lig, uint8_t* etype_lig,
-                                             int32_t* node_ptr, int32_t* node_graph, float* pos,
-                                             const PvsRaggedNodeTables* tables, int32_t* status, void* state,
-                                             size_t state_bytes, pvs_stream_t stream_) {
-    return pvs_screen_graph_build_ragged_cap(lig_pos, lig_ptr, rec_pos, rr_rowptr, rr_col, B, L_cap, n_rec, 64,
-                                             inter_radius, intra_radius, capacity, capacity_lig, rowptr, row, col,
-                                             etype, inv_deg, rowptr_lig, row_lig, col_lig, etype_lig, node_ptr,
-                                             node_graph, pos, tables, status, state, state_bytes, stream_);
-}
-
-// ---- cropped slots: pvs_screen_graph_build_ragged_cap where every slot keeps only the receptor atoms closer than
+// ---- cropped slots (PVS_SLOTS_CROPPED): the ragged builder where every slot keeps only the receptor atoms closer than
 // crop_radius to one of its ligand atoms (screen_slots.h: PvsCroppedSlots), as the training loader crops a complex
 // around its ligand. k_crop_keep decides the masks, k_crop_slots turns them into ranks and node offsets; the kernels
 // above then run on the layout: a ligand atom's contact masks are cut down to the kept atoms, a receptor row is the
@@ -660,60 +543,86 @@ k_crop_slots(const int32_t* __restrict__ lig_ptr, const u64* __restrict__ keep, 
     }
 }
 
-}  // namespace
-
-extern "C" size_t pvs_screen_graph_cropped_state_bytes(int32_t B, int32_t L_cap, int32_t n_rec, int32_t slot_cap) {
-    if (slot_cap < 1 || slot_cap > kPvsMaxSlotCap || B < 1) return 0;
-    PvsArena a(nullptr, 0);
-    return carve_screen(a, (size_t)L_cap, L_cap + B * n_rec, n_rec, pvs_slot_words(slot_cap), true, nullptr, B) + 256;
+// ---- the host path of all three layouts: check (screen_job.h), carve, then the layout's own first launch(es) and the
+// shared sequence behind them ----
+size_t carve_job(PvsArena& a, const PvsScreenSlotsJob& j, ScreenState* out) {
+    return carve_screen(a, (size_t)j.lig_cap, j.lig_cap + j.n_slots * j.n_rec, j.n_rec, pvs_slot_words(j.slot_cap),
+                        true, out, j.layout == PVS_SLOTS_CROPPED ? j.n_slots : 0);
 }
 
-extern "C" int pvs_screen_graph_build_cropped(const float* lig_pos, const int32_t* lig_ptr, const float* rec_pos,
-                                              const int32_t* rr_rowptr, const int32_t* rr_col, int32_t B,
-                                              int32_t L_cap, int32_t n_rec, int32_t slot_cap, double inter_radius,
-                                              double intra_radius, double crop_radius, int32_t capacity,
-                                              int32_t capacity_lig, int32_t* rowptr, int32_t* row, int32_t* col,
-                                              uint8_t* etype, float* inv_deg, int32_t* rowptr_lig, int32_t* row_lig,
-                                              int32_t* col_lig, uint8_t* etype_lig, int32_t* node_ptr,
-                                              int32_t* node_graph, float* pos, uint64_t* keep,
-                                              const PvsRaggedNodeTables* tables, int32_t* status, void* state,
-                                              size_t state_bytes, pvs_stream_t stream_) {
-    const char* who = "pvs_screen_graph_build_cropped";
-    hipStream_t s = (hipStream_t)stream_;
-    (void)capacity_lig; (void)rowptr_lig; (void)row_lig; (void)col_lig; (void)etype_lig;      // (no ligand-touching CSR)
-    PVS_REQUIRE(lig_pos && lig_ptr && rec_pos && rr_rowptr && rr_col && rowptr && row && col && etype && inv_deg &&
-                node_ptr && node_graph && pos && keep && status && state, "%s: NULL", who);
-    PVS_REQUIRE(slot_cap >= 1 && slot_cap <= kPvsMaxSlotCap, "%s: slot_cap must be 1..%d (got %d)", who,
-                kPvsMaxSlotCap, slot_cap);
-    PVS_REQUIRE(B > 0 && L_cap > 0 && L_cap <= slot_cap * (int64_t)B && n_rec > 0, "%s: needs slots, 1..%d * slots "
-                "packed ligand atoms (got %d for %d) and a receptor", who, slot_cap, L_cap, B);
-    PVS_REQUIRE((int64_t)L_cap + (int64_t)B * n_rec < INT32_MAX, "%s: more than 2^31 nodes", who);
-    PVS_REQUIRE(crop_radius > 0.0, "%s: crop_radius must be positive (got %g)", who, crop_radius);
-    PvsRaggedNodeTables t = {};
-    if (tables) {
-        t = *tables;
-        PVS_REQUIRE(t.n_feats >= 0, "%s: negative table width", who);
-        PVS_REQUIRE(!t.feats || (t.lig_feats && t.rec_feats && t.n_feats > 0), "%s: feature table without sources", who);
-        t.base_magg = nullptr;          // (a cropped row has lost template neighbours: the receptor's sums are not its)
-    }
-    PvsArena arena(state, state_bytes);
-    ScreenState w;
-    carve_screen(arena, (size_t)L_cap, L_cap + B * n_rec, n_rec, pvs_slot_words(slot_cap), true, &w, B);
-    PVS_REQUIRE(arena.ok(), "%s: state too small (%zu < %zu)", who, state_bytes, arena.off);
-    PvsProfScope prof(s, PVS_PROF_PREPARE);
-    const int W = pvs_rec_words(n_rec), n_rows = L_cap + B * n_rec;
-    u64* keep_words = (u64*)keep;
-    k_crop_keep<<<dim3(B, (W + 3) / 4), 256, 0, s>>>(lig_pos, lig_ptr, rec_pos, L_cap, n_rec, slot_cap,
-                                                     make_radius(crop_radius), keep_words);
-    PVS_CHECK_LAUNCH();
-    k_crop_slots<<<1, 256, 0, s>>>(lig_ptr, keep_words, B, L_cap, n_rec, slot_cap, w.keep_rank, node_ptr, w.slot_of,
-                                   status);
-    PVS_CHECK_LAUNCH();
-    const PvsCroppedSlots L{lig_ptr, node_ptr, w.slot_of, status, keep_words, w.keep_rank, B, L_cap, n_rec, slot_cap};
-    const OutCsr full{rowptr, row, col, etype, capacity}, none{nullptr, nullptr, nullptr, nullptr, 0};
-    PVS_TRY(build_csrs(L, lig_pos, rec_pos, rr_rowptr, rr_col, inter_radius, intra_radius, rowptr, nullptr, full, none,
-                       inv_deg, status, false, w, s));
-    k_node_tables_ragged<<<(n_rows + 3) / 4, 256, 0, s>>>(lig_pos, rec_pos, L, rr_rowptr, rr_col, node_graph, pos, t);
+// The layout's first launch(es): they validate the slot table and write node_ptr, the atom -> slot table and the status
+// word, and leave in *L the layout that the kernels behind them read.
+int start_slots(const PvsScreenSlotsJob& j, const ScreenState& w, hipStream_t s, PvsRaggedSlots* L) {
+    *L = PvsRaggedSlots{j.lig_ptr, j.node_ptr, w.slot_of, j.status, j.n_slots, j.lig_cap, j.n_rec, j.slot_cap};
+    k_slots<<<(j.n_slots + 1 + 255) / 256, 256, 0, s>>>(j.lig_ptr, j.n_slots, j.lig_cap, j.n_rec, j.slot_cap,
+                                                         j.node_ptr, w.slot_of, j.status);
     PVS_CHECK_LAUNCH();
     return 0;
+}
+
+int start_slots(const PvsScreenSlotsJob& j, const ScreenState& w, hipStream_t s, PvsStruckSlots* L) {
+    *L = PvsStruckSlots{j.lig_ptr, j.node_ptr, w.slot_of, j.status, j.rec_drop, j.n_slots, j.lig_cap, j.n_rec,
+                        j.slot_cap};
+    k_slots_struck<<<(j.n_slots + 1 + 255) / 256, 256, 0, s>>>(j.lig_ptr, j.rec_drop, j.n_slots, j.lig_cap, j.n_rec,
+                                                                j.slot_cap, j.node_ptr, w.slot_of, j.status);
+    PVS_CHECK_LAUNCH();
+    return 0;
+}
+
+int start_slots(const PvsScreenSlotsJob& j, const ScreenState& w, hipStream_t s, PvsCroppedSlots* L) {
+    const int W = pvs_rec_words(j.n_rec);
+    u64* keep = (u64*)j.keep;
+    *L = PvsCroppedSlots{j.lig_ptr, j.node_ptr, w.slot_of, j.status, keep, w.keep_rank, j.n_slots, j.lig_cap, j.n_rec,
+                         j.slot_cap};
+    k_crop_keep<<<dim3(j.n_slots, (W + 3) / 4), 256, 0, s>>>(j.lig_pos, j.lig_ptr, j.rec_pos, j.lig_cap, j.n_rec,
+                                                              j.slot_cap, make_radius(j.crop_radius), keep);
+    PVS_CHECK_LAUNCH();
+    k_crop_slots<<<1, 256, 0, s>>>(j.lig_ptr, keep, j.n_slots, j.lig_cap, j.n_rec, j.slot_cap, w.keep_rank, j.node_ptr,
+                                   w.slot_of, j.status);
+    PVS_CHECK_LAUNCH();
+    return 0;
+}
+
+OutCsr out_csr(const PvsCsrOut& c) { return OutCsr{c.rowptr, c.row, c.col, c.etype, c.capacity}; }
+
+template <class Slots>
+int build_slots(const PvsScreenSlotsJob& j, const ScreenState& w, hipStream_t s) {
+    Slots L;
+    PVS_TRY(start_slots(j, w, s, &L));
+    const PvsCsrOut lig = kCropped<Slots> ? PvsCsrOut{} : j.lig;       // (cropped slots: no ligand-touching CSR)
+    PVS_TRY(build_csrs(L, j.lig_pos, j.rec_pos, j.rr_rowptr, j.rr_col, j.inter_radius, j.intra_radius, j.full.rowptr,
+                       lig.rowptr, out_csr(j.full), out_csr(lig), j.inv_deg, j.status, false, w, s));
+    const int n_rows = j.lig_cap + j.n_slots * j.n_rec;
+    k_node_tables_ragged<<<(n_rows + 3) / 4, 256, 0, s>>>(j.lig_pos, j.rec_pos, L, j.rr_rowptr, j.rr_col, j.node_graph,
+                                                          j.pos, pvs_screen_job_tables(j));
+    PVS_CHECK_LAUNCH();
+    return 0;
+}
+
+}  // namespace
+
+extern "C" size_t pvs_screen_slots_state_bytes(const PvsScreenSlotsJob* job) {
+    char why[256];
+    if (!job || pvs_screen_job_refusal(*job, true, why, sizeof(why))) return 0;
+    PvsArena a(nullptr, 0);
+    return carve_job(a, *job, nullptr) + 256;
+}
+
+extern "C" int pvs_screen_slots_build(const PvsScreenSlotsJob* job, void* state, size_t state_bytes,
+                                      pvs_stream_t stream_) {
+    const char* who = kPvsScreenJobWho;
+    hipStream_t s = (hipStream_t)stream_;
+    char why[256];
+    PVS_REQUIRE(job && state, "%s: NULL %s", who, job ? "state" : "job");
+    PVS_REQUIRE(!pvs_screen_job_refusal(*job, false, why, sizeof(why)), "%s", why);
+    PvsArena arena(state, state_bytes);
+    ScreenState w;
+    carve_job(arena, *job, &w);
+    PVS_REQUIRE(arena.ok(), "%s: state too small (%zu < %zu)", who, state_bytes, arena.off);
+    PvsProfScope prof(s, PVS_PROF_PREPARE);
+    switch (job->layout) {          // (one of the three: the refusal above)
+        case PVS_SLOTS_STRUCK: return build_slots<PvsStruckSlots>(*job, w, s);
+        case PVS_SLOTS_RAGGED: return build_slots<PvsRaggedSlots>(*job, w, s);
+        default: return build_slots<PvsCroppedSlots>(*job, w, s);
+    }
 }

@@ -569,7 +569,7 @@ class LibraryScreen(_ReceptorSideScreen):
     What ReceptorScreen reuses across the poses of one ligand is reused across ligands: the receptor-receptor
     template CSR and the first layer's receptor-receptor sums (kept once, [n_rec, .]), the ligand-touching first
     layer, device-side edge counts. The mixed batch's graph and node tables come from
-    pvs_screen_graph_build_ragged_cap (slot cap max(max_lig_atoms, 64): ceil(cap / 64) ligand-ligand mask words per
+    pvs_screen_slots_build (PVS_SLOTS_RAGGED; slot cap max(max_lig_atoms, 64): ceil(cap / 64) ligand-ligand words per
     atom, one word for a screen of up to 64 atoms) in a compact layout (slot p: its ligand atoms, then the
     receptor); no host argument of a step depends on the batch's composition, so ONE captured step (`capture`) serves every batch. Models without graphnorm always run
     at the padded shape N_cap = batch_size * (max_lig_atoms + n_rec) (padding nodes have no edges and belong to no
@@ -602,7 +602,7 @@ class LibraryScreen(_ReceptorSideScreen):
     struck: None, or True for a screen whose slots may lack one receptor atom each (receptor-atom and contact masking:
     the reference's atom_masking / bond_masking remove atoms together with their edges). The screen then owns a static
     `rec_drop [batch_size]` int32 (-1: the whole receptor; r: the slot's receptor is without atom r, so the slot has
-    n_rec - 1 receptor rows) and launches pvs_screen_graph_build_struck: the rows that had r as a receptor-receptor
+    n_rec - 1 receptor rows) and builds PVS_SLOTS_STRUCK slots: the rows that had r as a receptor-receptor
     neighbour take their whole first-layer row through the ligand-touching CSR with a zero base, every other row and
     every kernel is as without it. `load(slots, rec_drop=[...])` and `load_leave_out_pairs` fill it. Needs the
     first-layer reuse, and goes with neither `cam` nor `contact_attention` (their reductions assume n_rec receptor rows
@@ -613,9 +613,9 @@ class LibraryScreen(_ReceptorSideScreen):
     closer than it to one of the slot's ligand atoms (fp64 decision on the fp32 coordinates, strict, a coincident atom
     is kept; an empty slot keeps nothing), in receptor order behind the ligand atoms, and the slot's graph is
     generate_edges on that cropped complex - so a pose scores what `val()` gives the same pose, and the layers run
-    over the rows the model was trained on. The step is pvs_screen_graph_build_cropped, the embedding, then EVERY EGNN
-    layer through forward_prepared on the one full CSR (edge count on the device), pooling and heads by node_ptr: the
-    first-layer receptor sums are not used (a row at the rim of the crop has lost template neighbours). Shapes stay
+    over the rows the model was trained on. The step is pvs_screen_slots_build (PVS_SLOTS_CROPPED), the embedding, then
+    EVERY EGNN layer through forward_prepared on the one full CSR (edge count on the device), pooling and heads by
+    node_ptr: the first-layer receptor sums are not used (a row at the rim of the crop has lost template neighbours). Shapes stay
     padded to N_cap, so capture() / replay() and `tasks` work as above; `screen.keep` [batch_size, ceil(n_rec / 64)]
     int64 holds the last step's masks (bit j % 64 of word j / 64), `screen._fast['node_ptr']` its offsets. Models as
     captured_scoring.model_refusal accepts them (fp32, no edge_residual, 17..128 channels: NotImplementedError
@@ -765,14 +765,11 @@ class LibraryScreen(_ReceptorSideScreen):
                              out=(c['lig_att'], c['slot_rec_att'], c['rec_sum'], c['rec_count'], c['rec_max']))
 
     def _cache_receptor_sums(self):
-        """The receptor sums kept once, [n_rec, .]; the builder's node-table struct points at them."""
+        """The receptor sums kept once, [n_rec, .]; every builder launch reads them (and the template) anew (`_job`)."""
         if self.crop_radius is not None:      # (a cropped step keeps the template and no sums)
             self._receptor_template(self._rec_pos)
             return
         self.rec_magg, self.rec_xsum, self.rec_deg = self._receptor_sums(self._rec_feats, self._rec_pos)
-        if self._fast is not None:
-            t = self._fast['tables']
-            t.rec_magg, t.rec_xsum, t.rec_deg = (_lib.ptr(v) for v in (self.rec_magg, self.rec_xsum, self.rec_deg))
 
     # ---- inputs ----
     def _checked_sizes(self, sizes):
@@ -887,88 +884,87 @@ class LibraryScreen(_ReceptorSideScreen):
                              + (', or the pair table is not one of pairs inside them' if self.struck else ''))
 
     # ---- the graph and the node tables ----
-    def _buffers(self, cap, cap_l):
-        lib = _lib.lib()
+    def _buffers(self, cap, cap_l, feats=False, base=False, keep=False, att_l=False, pgs=False, pg=False):
+        """The builder's buffers over N_cap nodes: the full CSR with room for cap edges, node_ptr, node_graph, pos, and
+        what the use names - cap_l (not None): the ligand-touching CSR with room for cap_l edges; feats: the feature
+        rows x; base: the first-layer base rows; keep: the masks of cropped slots (and the state of that layout); att_l:
+        the first layer's attention in the ligand-touching CSR's order; pgs: the graph pairs of `_graphs`, by node
+        count; pg: the PreparedGraph of the full CSR over N_cap nodes."""
         dev, n_cap = self.lig_pos.device, self.n_cap
         i32 = dict(dtype=torch.int32, device=dev)
         f32 = dict(dtype=torch.float32, device=dev)
-        hid = self.rec_magg.shape[1]      # (a base row's width: the hidden size + the reuse kind's row_extra)
-        f = _csr_buffers(
-            dev, n_cap, cap_l, cap,
-            state=torch.empty((lib.pvs_screen_graph_struck_state_bytes if self.struck else
-                               lib.pvs_screen_graph_ragged_cap_state_bytes)(self.b, self.l_cap, self.n_rec,
-                                                                            self.slot_cap),
-                              dtype=torch.uint8, device=dev),
+        counts = _lib.PvsScreenSlotsJob(layout=self._layout(keep), n_slots=self.b, lig_cap=self.l_cap, n_rec=self.n_rec,
+                                        slot_cap=self.slot_cap)
+        own = dict(
+            state=torch.empty(_lib.lib().pvs_screen_slots_state_bytes(C.byref(counts)), dtype=torch.uint8, device=dev),
             node_ptr=torch.zeros(self.b + 1, **i32), node_graph=torch.empty(n_cap, **i32),
-            pos=torch.empty((n_cap, 3), **f32), x=torch.empty((n_cap, self.lig_feats.shape[1]), **f32),
-            base_magg=torch.empty((n_cap, hid), **f32), base_xsum=torch.empty((n_cap, 3), **f32),
-            base_deg=torch.empty(n_cap, **f32), pgs={})
-        if self.contact_attention == 1:      # the first EGNN layer's attention, in the ligand-touching CSR's order
+            pos=torch.empty((n_cap, 3), **f32))
+        if feats:
+            own['x'] = torch.empty((n_cap, self.lig_feats.shape[1]), **f32)
+        if base:        # (a base row's width: the hidden size + the reuse kind's row_extra)
+            own.update(base_magg=torch.empty((n_cap, self.rec_magg.shape[1]), **f32),
+                       base_xsum=torch.empty((n_cap, 3), **f32), base_deg=torch.empty(n_cap, **f32))
+        if keep:
+            own['keep'] = torch.zeros((self.b, (self.n_rec + 63) // 64), dtype=torch.int64, device=dev)
+        f = _csr_buffers(dev, n_cap, cap_l, cap, **own)
+        if att_l:
             f['att_l'] = torch.empty(max(cap_l, 1), **f32)
-        f['tables'] = _lib.PvsRaggedNodeTables(
-            f['x'].shape[1], hid, _lib.ptr(self.lig_feats), _lib.ptr(self._rec_feats), _lib.ptr(self.rec_magg),
-            _lib.ptr(self.rec_xsum), _lib.ptr(self.rec_deg), _lib.ptr(f['x']), _lib.ptr(f['base_magg']),
-            _lib.ptr(f['base_xsum']), _lib.ptr(f['base_deg']))
+        if pgs:
+            f['pgs'] = {}
+        if pg:
+            from .graph import PreparedGraph
+            csr = {k: f[k] for k in ('rowptr', 'row', 'col', 'etype', 'inv_deg', 'status')}
+            f['pg'] = PreparedGraph.over_buffers(n_cap, cap, csr, f['rowptr'][n_cap:])
+            if self.graphnorm:
+                f['pg'].set_norm_rows(f['node_ptr'][self.b:])
         return f
 
-    def _cropped_buffers(self, cap):
-        """The buffers of a cropped screen: the full CSR alone, the node tables without base rows, the keep masks."""
-        lib = _lib.lib()
-        dev, n_cap = self.lig_pos.device, self.n_cap
-        i32 = dict(dtype=torch.int32, device=dev)
-        f32 = dict(dtype=torch.float32, device=dev)
-        f = _csr_buffers(
-            dev, n_cap, None, cap,
-            state=torch.empty(lib.pvs_screen_graph_cropped_state_bytes(self.b, self.l_cap, self.n_rec, self.slot_cap),
-                              dtype=torch.uint8, device=dev),
-            node_ptr=torch.zeros(self.b + 1, **i32), node_graph=torch.empty(n_cap, **i32),
-            pos=torch.empty((n_cap, 3), **f32), x=torch.empty((n_cap, self.lig_feats.shape[1]), **f32),
-            keep=torch.zeros((self.b, (self.n_rec + 63) // 64), dtype=torch.int64, device=dev))
-        f['tables'] = _lib.PvsRaggedNodeTables(f['x'].shape[1], 0, _lib.ptr(self.lig_feats), _lib.ptr(self._rec_feats),
-                                               None, None, None, _lib.ptr(f['x']), None, None, None)
-        from .graph import PreparedGraph
-        csr = {k: f[k] for k in ('rowptr', 'row', 'col', 'etype', 'inv_deg', 'status')}
-        f['pg'] = PreparedGraph.over_buffers(n_cap, cap, csr, f['rowptr'][n_cap:])
-        if self.graphnorm:
-            f['pg'].set_norm_rows(f['node_ptr'][self.b:])
-        return f
+    def _step_buffers(self, cap, cap_l):
+        """The buffers of the screen's step. Cropped: the full CSR alone, the feature rows, the keep masks; else both
+        CSRs, feature and base rows and, for contact_attention=1, the first EGNN layer's attention."""
+        if self.crop_radius is not None:
+            return self._buffers(cap, None, feats=True, keep=True, pg=True)
+        return self._buffers(cap, cap_l, feats=True, base=True, att_l=self.contact_attention == 1, pgs=True)
 
-    def _probe_buffers(self):
-        """What the probe of a cropped screen's capacities needs of the uncropped builder's buffers: row pointers, node
-        tables without feature or base rows, no room for edges."""
-        dev, n_cap = self.lig_pos.device, self.n_cap
-        i32 = dict(dtype=torch.int32, device=dev)
-        f = _csr_buffers(
-            dev, n_cap, 1, 1,
-            state=torch.empty(_lib.lib().pvs_screen_graph_ragged_cap_state_bytes(self.b, self.l_cap, self.n_rec,
-                                                                                 self.slot_cap),
-                              dtype=torch.uint8, device=dev),
-            node_ptr=torch.zeros(self.b + 1, **i32), node_graph=torch.empty(n_cap, **i32),
-            pos=torch.empty((n_cap, 3), dtype=torch.float32, device=dev))
-        f['tables'] = _lib.PvsRaggedNodeTables()
-        return f
+    def _layout(self, cropped):
+        return _lib.SLOTS_CROPPED if cropped else _lib.SLOTS_STRUCK if self.struck else _lib.SLOTS_RAGGED
 
-    def _launch_builder(self, f):
-        """The builder of the loaded batch into f: pvs_screen_graph_build_ragged_cap, or for a struck screen
-        pvs_screen_graph_build_struck, which takes rec_drop behind lig_ptr and is otherwise called alike - as is
-        pvs_screen_graph_build_cropped where f has keep masks: crop_radius behind the edge radii, keep behind pos, and
-        no ligand-touching CSR (NULL, no room)."""
-        args = [_lib.ptr(self.lig_pos), _lib.ptr(self.lig_ptr), _lib.ptr(self._rec_pos),
-                _lib.ptr(self._rr.t['rowptr']), _lib.ptr(self._rr.t['col']), self.b, self.l_cap, self.n_rec,
-                self.slot_cap, float(self.r_inter), float(self.r_intra), f['cap'], f['cap_l'] or 0]
-        args += [_lib.ptr(f.get(key)) for key in ('rowptr', 'row', 'col', 'etype', 'inv_deg', 'rowptr_l', 'row_l',
-                                                  'col_l', 'etype_l', 'node_ptr', 'node_graph', 'pos')]
-        args += [C.byref(f['tables']), _lib.ptr(f['status']), _lib.ptr(f['state']), f['state'].numel(),
-                 _stream(self.lig_pos.device)]
-        name = 'pvs_screen_graph_build_ragged_cap'
-        if 'keep' in f:
-            args.insert(11, self.crop_radius)
-            args.insert(-5, _lib.ptr(f['keep']))
-            name = 'pvs_screen_graph_build_cropped'
-        if self.struck:
-            args.insert(2, _lib.ptr(self.rec_drop))
-            name = 'pvs_screen_graph_build_struck'
-        _lib.check(getattr(_lib.lib(), name)(*args), name)
+    def _job(self, f, probe=False):
+        """The PvsScreenSlotsJob of the loaded batch into f, filled at every launch from the screen's attributes and f
+        by name: nothing keeps a device address across steps, so whatever a refresh replaces (the template, the
+        receptor sums) is simply read again. The layout is PVS_SLOTS_CROPPED where f has keep masks, PVS_SLOTS_STRUCK
+        for a struck screen, else PVS_SLOTS_RAGGED. probe: no room for edges in either CSR."""
+        p = _lib.ptr
+        cropped = 'keep' in f
+        job = _lib.PvsScreenSlotsJob(
+            layout=self._layout(cropped), lig_pos=p(self.lig_pos), lig_ptr=p(self.lig_ptr), rec_drop=p(self.rec_drop),
+            rec_pos=p(self._rec_pos), rr_rowptr=p(self._rr.t['rowptr']), rr_col=p(self._rr.t['col']), n_slots=self.b,
+            lig_cap=self.l_cap, n_rec=self.n_rec, slot_cap=self.slot_cap, inter_radius=float(self.r_inter),
+            intra_radius=float(self.r_intra), crop_radius=self.crop_radius if cropped else 0.0,
+            inv_deg=p(f['inv_deg']), node_ptr=p(f['node_ptr']), node_graph=p(f['node_graph']), pos=p(f['pos']),
+            keep=p(f.get('keep')), status=p(f['status']))
+        full = job.full
+        full.rowptr, full.row, full.col, full.etype = p(f['rowptr']), p(f['row']), p(f['col']), p(f['etype'])
+        full.capacity = 0 if probe else f['cap']
+        if f['cap_l'] is not None:
+            lig = job.lig
+            lig.rowptr, lig.row, lig.col, lig.etype = p(f['rowptr_l']), p(f['row_l']), p(f['col_l']), p(f['etype_l'])
+            lig.capacity = 0 if probe else f['cap_l']
+        t = job.tables
+        if 'x' in f:
+            t.n_feats, t.feats = f['x'].shape[1], p(f['x'])
+            t.lig_feats, t.rec_feats = p(self.lig_feats), p(self._rec_feats)
+        if 'base_magg' in f:
+            t.hidden, t.rec_magg, t.rec_xsum, t.rec_deg = (f['base_magg'].shape[1], p(self.rec_magg), p(self.rec_xsum),
+                                                           p(self.rec_deg))
+            t.base_magg, t.base_xsum, t.base_deg = p(f['base_magg']), p(f['base_xsum']), p(f['base_deg'])
+        return job
+
+    def _launch_builder(self, f, probe=False):
+        """pvs_screen_slots_build of the loaded batch into f."""
+        job = self._job(f, probe)
+        _lib.check(_lib.lib().pvs_screen_slots_build(C.byref(job), _lib.ptr(f['state']), f['state'].numel(),
+                                                     _stream(self.lig_pos.device)), 'pvs_screen_slots_build')
 
     def _probe_capacities(self):
         """One synchronous probe: the builder with no room for edges leaves both exact edge counts in its row
@@ -976,9 +972,10 @@ class LibraryScreen(_ReceptorSideScreen):
         batch of L_cap atoms, at most what L_cap atoms can have (per atom: inter and intra contacts with the receptor,
         both directions, and the slot's other ligand atoms). A struck screen adds the whole rows of the receptor rows
         that the struck atom can touch (`_struck_room`) for every slot."""
-        probe = self._buffers(1, 1) if self.crop_radius is None else self._probe_buffers()
-        probe['cap'] = probe['cap_l'] = 0
-        self._launch_builder(probe)
+        # (an uncropped screen probes into a set like its step's, so that the step's buffers are then allocated as they
+        # always were; a cropped one needs of the uncropped builder no more than row pointers, node_ptr and pos)
+        probe = self._buffers(1, 1) if self.crop_radius is not None else self._step_buffers(1, 1)
+        self._launch_builder(probe, probe=True)
         n_lig_edges = int(probe['rowptr_l'][self.n_cap].item())
         per_atom = -(-n_lig_edges // max(self.n_atoms, 1))
         cap_l = min(self.l_cap * (4 * self.n_rec + self.slot_cap), 2 * per_atom * self.l_cap + 4096)
@@ -1015,12 +1012,12 @@ class LibraryScreen(_ReceptorSideScreen):
         return pgs[n]
 
     def _build(self, capacities=None):
-        """The loaded batch's graph and node tables (pvs_screen_graph_build_ragged_cap). capacities: (full, ligand-
+        """The loaded batch's graph and node tables (pvs_screen_slots_build). capacities: (full, ligand-
         touching) edge room instead of the probe's."""
         capturing = torch.cuda.is_current_stream_capturing()
         if self._fast is None:
             cap, cap_l = capacities or self._probe_capacities()
-            self._fast = self._buffers(cap, cap_l) if self.crop_radius is None else self._cropped_buffers(cap)
+            self._fast = self._step_buffers(cap, cap_l)
         f = self._fast
         if not capturing:
             self.check()

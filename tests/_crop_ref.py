@@ -1,4 +1,4 @@
-"""Numpy reference of the cropped pose-batch slots (pvs_screen_graph_build_cropped, LibraryScreen(crop_radius=...)):
+"""Numpy reference of the cropped pose-batch slots (pvs_screen_slots_build with PVS_SLOTS_CROPPED, LibraryScreen(crop_radius=...)):
 which receptor atoms a slot keeps, the keep mask's 64-bit words and their rank table, and the cropped complex that the
 slot's graph is generate_edges of. Pure host code; tests/test_screen_crop_host.py pins the keep decision against scipy's
 cdist."""

@@ -47,14 +47,38 @@ def test_exports_and_version():
     from pointvs_amd import _lib
     header = (ROOT / 'include' / 'pvs_egnn.h').read_text()
     declared = set(re.findall(r'\b(pvs_[a-z0-9_]+)\s*\(', header))
-    widths = {'pvs_screen_graph_struck_state_bytes': 4, 'pvs_screen_graph_build_struck': 31,
-              'pvs_contact_pairs_count': 9, 'pvs_contact_pairs_fill': 11, 'pvs_leave_out_pair_pack': 19}
+    widths = {'pvs_contact_pairs_count': 9, 'pvs_contact_pairs_fill': 11, 'pvs_leave_out_pair_pack': 19}
     for name, n_args in widths.items():
         assert name in declared and name in _lib.EXPORTED_SYMBOLS and hasattr(_lib.lib(), name), name
         assert len(_lib._PROTOTYPES[name][1]) == n_args, name
-    # the struck builder is the ragged one plus rec_drop
-    assert len(_lib._PROTOTYPES['pvs_screen_graph_build_ragged_cap'][1]) == 30
-    assert _lib.MIN_VERSION >= 110 and _lib.lib().pvs_version() >= 110
+    # the slot builders of every layout (struck: the ragged one plus rec_drop) are one entry pair on one job struct
+    # (its layout against the C compiler's: test_screen_job_host.py); the eight positional entries before it are gone
+    for name in ('pvs_screen_slots_state_bytes', 'pvs_screen_slots_build'):
+        assert name in declared and name in _lib.EXPORTED_SYMBOLS and hasattr(_lib.lib(), name), name
+    for layout in ('ragged', 'ragged_cap', 'struck', 'cropped'):
+        for name in (f'pvs_screen_graph_{layout}_state_bytes', f'pvs_screen_graph_build_{layout}'):
+            assert name not in declared and name not in _lib.EXPORTED_SYMBOLS and not hasattr(_lib.lib(), name), name
+    assert _lib.MIN_VERSION >= 113 and _lib.lib().pvs_version() >= 113
+
+
+def test_the_library_refuses_a_job_by_name_before_any_launch():
+    """Host checks return before any launch, so this runs without a GPU: pvs_last_error() names entry and cause."""
+    import ctypes as C
+    from pointvs_amd import _lib
+    lib = _lib.lib()
+    fake = 4096         # (an address that no refusal reads)
+    job = _lib.PvsScreenSlotsJob(
+        layout=_lib.SLOTS_STRUCK, n_slots=2, lig_cap=64, n_rec=65, slot_cap=64, inter_radius=4.0, intra_radius=2.0,
+        **{name: fake for name in ('lig_pos', 'lig_ptr', 'rec_pos', 'rr_rowptr', 'rr_col', 'inv_deg', 'node_ptr',
+                                   'node_graph', 'pos', 'status')})
+    for csr in (job.full, job.lig):
+        csr.rowptr = csr.row = csr.col = csr.etype = fake
+    assert lib.pvs_screen_slots_build(C.byref(job), fake, 1 << 20, None) != 0
+    assert lib.pvs_last_error() == b'pvs_screen_slots_build: NULL rec_drop'
+    job.layout, job.slot_cap = _lib.SLOTS_RAGGED, 1025
+    assert lib.pvs_screen_slots_build(C.byref(job), fake, 1 << 20, None) != 0
+    assert lib.pvs_last_error() == b'pvs_screen_slots_build: slot_cap must be 1..1024 (got 1025)'
+    assert lib.pvs_screen_slots_state_bytes(C.byref(job)) == 0
 
 
 # argv: K n_rec pair_ptr[...]. Prints the verdict on the table, every copy ("c <copy> <hit> <pair>") and two outside it.

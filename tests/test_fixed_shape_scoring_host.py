@@ -183,7 +183,7 @@ def test_new_entry_points_are_declared_and_bound():
         assert name in _lib._PROTOTYPES and name in _lib.EXPORTED_SYMBOLS
         declared = re.search(rf'\bint {name}\s*\(([^;]*)\);', header).group(1)
         assert len(declared.split(',')) == len(_lib._PROTOTYPES[name][1]), name     # one ctypes type per parameter
-    assert _lib.MIN_VERSION == 112
+    assert _lib.MIN_VERSION == 113
 
 
 def test_capture_val_flag_is_additive():

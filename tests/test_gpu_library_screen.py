@@ -1,5 +1,5 @@
 """Library screening (pointvs_amd/screening.py: LibraryScreen, ScreeningSweep.run_library): pose batches that mix
-ligands of different sizes, built by pvs_screen_graph_build_ragged. Receptor of 130 atoms everywhere: three 64-bit
+ligands of different sizes, built by pvs_screen_slots_build (PVS_SLOTS_RAGGED). Receptor of 130 atoms everywhere: three 64-bit
 contact-mask words, the last one partial."""
 import math
 import tempfile
@@ -375,7 +375,7 @@ BAD_LIG_PTR = [([1, 64, 64, 65, 129], 'first entry not 0'), ([0, 64, 60, 65, 129
 
 
 def test_a_lig_ptr_that_is_no_table_gives_an_empty_graph():
-    """Status bit 3 of pvs_screen_graph_build_ragged: a lig_ptr that is not a table of 0..64-atom slots inside L_cap
+    """Status bit 3 of pvs_screen_slots_build (PVS_SLOTS_RAGGED): a lig_ptr that is not a table of 0..64-atom slots inside L_cap
     (validated on the device) is reported as ValueError, the batch comes out as an empty graph of padding rows and
     no edge entry is written; the valid table afterwards reproduces the first build array for array."""
     from pointvs_amd.screening import LibraryScreen

@@ -1,4 +1,4 @@
-"""The three radius-graph builders (pvs_radius_graph_count/_fill, pvs_screen_graph_build, pvs_screen_graph_build_ragged)
+"""The three radius-graph builders (pvs_radius_graph_count/_fill, pvs_screen_graph_build, pvs_screen_slots_build with PVS_SLOTS_RAGGED)
 where random coordinates never take them (tests/_radius_cases.py): squared distances inside the +-2^-48 band around a
 radius and around the 1e-7 lower bound (the square-root path of radius_common.h), and graph sizes at the edges of the
 builders' tables (second trips of the 64-at-a-time loops, empty graphs, 1 / 63 / 64 / 65 nodes, no edge at all).
@@ -206,7 +206,7 @@ def test_pose_batch_builder_in_the_band(n_lig, n_rec, kind):
 
 @pytest.mark.parametrize('n_rec,kind', [(n_rec, kind) for n_rec in (64, 65, 130) for kind in ('inter', 'intra')])
 def test_ragged_pose_builder_in_the_band(n_rec, kind):
-    """pvs_screen_graph_build_ragged with slots of 64, 0, 1 and 64 ligand atoms: the same probes in slot 0."""
+    """pvs_screen_slots_build (PVS_SLOTS_RAGGED) with slots of 64, 0, 1 and 64 ligand atoms: the same probes in slot 0."""
     from pointvs_amd.screening import LibraryScreen
     lig, rec = rc.pose_case(64, n_rec)
     feats = _feats(64, n_rec)

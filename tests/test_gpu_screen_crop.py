@@ -1,4 +1,4 @@
-"""Cropped library screening (LibraryScreen / ScreeningSweep with crop_radius=..., pvs_screen_graph_build_cropped):
+"""Cropped library screening (LibraryScreen / ScreeningSweep with crop_radius=..., pvs_screen_slots_build with PVS_SLOTS_CROPPED):
 every slot keeps the receptor atoms closer than the radius to one of its ligand atoms, as the training loader crops a
 complex. The builder is checked exactly - masks against numpy (tests/_crop_ref.py), graphs against the oracle's
 generate_edges on the cropped complexes -, the scores against the plain forward on those complexes and against the

@@ -4,6 +4,7 @@ lane-per-ligand-atom step of csrc/screen_graph.hip runs as that many trips. The 
 is compared for equality with the numpy reference (tests/_radius_cases.py) and with radius_graph on the collated batch.
 Shapes: 65 atoms (one word and one bit; the coincident atoms 0 and 64 in different words), 128 (two full words), 130
 (the ligand-ligand probe 1-128 and the coincident atoms 0-129 both span words 0 and 2), 1,024 (the cap)."""
+import ctypes as C
 import math
 import tempfile
 
@@ -115,7 +116,7 @@ WIDE_SLOT_SIZES = (130, 0, 1, 65, 64, 128)
 
 @pytest.mark.parametrize('n_rec,kind', [(n_rec, kind) for n_rec in (65, 130) for kind in ('inter', 'intra')])
 def test_ragged_pose_builder_in_the_band_with_slots_of_up_to_130_atoms(n_rec, kind):
-    """pvs_screen_graph_build_ragged_cap at slot_cap = 130 (three ligand words), slots of 130, 0, 1, 65, 64 and 128
+    """pvs_screen_slots_build (PVS_SLOTS_RAGGED) at slot_cap = 130 (three ligand words), slots of 130, 0, 1, 65, 64 and 128
     atoms: the same probes in slot 0."""
     from pointvs_amd.screening import LibraryScreen
     lig, rec = rc.pose_case(130, n_rec)
@@ -238,9 +239,12 @@ def test_one_atom_above_the_cap_is_refused_by_name():
         assert code != 0
         message = lib.pvs_last_error().decode()
         assert 'n_lig' in message and '1..1024' in message and str(n_lig) in message, message
-    assert lib.pvs_screen_graph_ragged_cap_state_bytes(2, 64, 65, 1025) == 0
-    assert lib.pvs_screen_graph_ragged_cap_state_bytes(2, 64, 65, 1024) > \
-        lib.pvs_screen_graph_ragged_cap_state_bytes(2, 64, 65, 64) == lib.pvs_screen_graph_ragged_state_bytes(2, 64, 65)
+    def state_bytes(slot_cap):       # of the shape (2, 64, 65): n_slots, lig_cap, n_rec
+        job = _lib.PvsScreenSlotsJob(layout=_lib.SLOTS_RAGGED, n_slots=2, lig_cap=64, n_rec=65, slot_cap=slot_cap)
+        return lib.pvs_screen_slots_state_bytes(C.byref(job))
+    assert state_bytes(1025) == 0
+    # (5644: what the positional entries before the job struct gave on the MI355X for slots of 64 atoms at this shape)
+    assert state_bytes(1024) > state_bytes(64) == 5644
 
 
 # ---- d. bad tables at a cap that is not 64 ----

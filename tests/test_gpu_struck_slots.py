@@ -1,5 +1,5 @@
 """Struck slots, the device side: the pose-batch builder for slots whose receptor lacks one atom
-(pvs_screen_graph_build_struck, through LibraryScreen(struck=True)), the contact lister (PF.contact_pairs) and the pair
+(pvs_screen_slots_build with PVS_SLOTS_STRUCK, through LibraryScreen(struck=True)), the contact lister (PF.contact_pairs) and the pair
 packer (PF.leave_out_pair_pack). All three are integer work or copies: every array is compared for equality - the
 builder with the existing ragged builder's output for the same slots after the numpy masking of the reference
 (tests/_attribution_ref.masked_coo: drop the atom, drop its edges, shift the ids above it), the lister with the class-1

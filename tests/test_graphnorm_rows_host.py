@@ -82,7 +82,7 @@ def test_abi_graph_member_export_and_version():
     from pointvs_amd import functional as PF
     from pointvs_amd.graph import PreparedGraph
     header = (ROOT / 'include' / 'pvs_egnn.h').read_text()
-    assert _lib.MIN_VERSION == 112 and _lib.lib().pvs_version() == 112
+    assert _lib.MIN_VERSION == 113 and _lib.lib().pvs_version() == 113
     fields = [name for name, _ in _lib.PvsGraph._fields_]
     assert fields[-1] == 'n_norm_rows_dev' and fields[-3:-1] == ['graph_eptr', 'n_graphs']
     # the layout the header states (and static_asserts when compiled as C++)

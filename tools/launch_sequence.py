@@ -9,10 +9,10 @@ PVS_EGNN_SPLIT_SMALL=1 and PVS_EGNN_SPLIT_WGRADS=1 (profiles/layer_backward_plan
     python tools/launch_sequence.py --parse DIR OUT.txt      # one line per launch: name, grid, workgroup, LDS
 Two libraries enqueue the same work when their OUT.txt files are equal (profiles/linear_job_refactor.txt).
 `--screening` traces instead one eager step of each screen (ReceptorScreen on the pose-batch builder and on the filter
-path, LibraryScreen plain, with struck slots, with contact attention and with cam) at a small shape (130-atom receptor,
+path, LibraryScreen plain, with struck slots, with contact attention, with cam and cropped) at a small shape (130-atom receptor,
 batch of 3) and one eager FixedShapeScorer step on two complexes of the cli_default golden root: the record that a
 change of the screens' host code left every launch alone (profiles/screening_refactor.txt,
-profiles/hit_attribution_refactor.txt, profiles/nowait_refactor.txt). `--fp64` runs the loop of the default mode with model
+profiles/hit_attribution_refactor.txt, profiles/nowait_refactor.txt, profiles/slot_builder_job.txt). `--fp64` runs the loop of the default mode with model
 and batch in double (hidden 16 / 32 / 64, the per-layer path: there is no fp64 stack), for a change of the binding's
 fp64 side (profiles/functional_dtype_refactor.txt)."""
 import csv
@@ -95,7 +95,8 @@ def run_screening():
     screen = LibraryScreen(model, rec, rec_feats, 3, 20, 7.0, struck=True)
     screen.load(slots, rec_drop=[-1, 5, 77])()
     screen.check()
-    for m, extra in ((attending, dict(contact_attention=1)), (model, dict(cam=True))):
+    # ... and the cropped step: its own builder layout, every layer on the one full CSR
+    for m, extra in ((attending, dict(contact_attention=1)), (model, dict(cam=True)), (model, dict(crop_radius=6.0))):
         screen = LibraryScreen(m, rec, rec_feats, 3, 20, 7.0, **extra)
         screen(slots)
         screen.check()
