@@ -435,6 +435,45 @@ typedef struct PvsScreenSlotsJob {
 size_t pvs_screen_slots_state_bytes(const PvsScreenSlotsJob* job);
 int pvs_screen_slots_build(const PvsScreenSlotsJob* job, void* state, size_t state_bytes, pvs_stream_t stream);
 
+/* Cropped copies: PVS_SLOTS_CROPPED slots whose keep mask is decided from OTHER atoms than the slot's own - the
+ * leave-out copies of a hit on its cropped complex (the reference's attribution_fns.atom_masking / bond_masking get
+ * the loader's complex, cropped around the WHOLE ligand, and strike atoms out of that one; a copy is never cropped
+ * again around what is left of it). `slots` is a PVS_SLOTS_CROPPED job by value (its own rec_drop stays NULL; every
+ * refusal of pvs_screen_slots_build applies to it), beside it three tables:
+ *   crop_pos [crop_cap,3] / crop_ptr [n_slots+1] (DEVICE, int32, crop_ptr[0] = 0): the atoms that slot p is cropped
+ *     AROUND, packed like lig_pos / lig_ptr; a crop set has 0..1024 atoms, 1 <= crop_cap <= 1024 * n_slots.
+ *   rec_drop [n_slots] (DEVICE, int32; NULL = all -1): -1, or the receptor atom that the slot's receptor lacks.
+ * Slot p keeps receptor atom j iff some atom of crop_pos[crop_ptr[p] .. crop_ptr[p+1]) is closer to it than
+ * slots.crop_radius - the decision of PVS_SLOTS_CROPPED, made by the same kernel: fp64 on the fp32 coordinates, strict,
+ * no lower bound; an empty crop set keeps nothing - and j != rec_drop[p]. A rec_drop[p] that names an atom the crop does
+ * not keep changes nothing. Everything else is PVS_SLOTS_CROPPED: the slot's rows are its OWN ligand atoms (slots.lig_pos
+ * / lig_ptr), then the kept atoms in receptor order; ligand edges by distance to kept atoms only; template edges where
+ * both ends are kept; slots.keep is an output, only the full CSR is written, the base tables are ignored. With crop_pos /
+ * crop_ptr = the ligand table and no rec_drop every output is that of pvs_screen_slots_build on `slots`, bit for bit.
+ * *slots.status: as there; bit 3 (an edgeless batch of padding rows) also when crop_ptr is not an ascending table from 0
+ * inside crop_cap, a crop set has more than 1024 atoms or rec_drop has an entry outside -1..n_rec-1. The status word has
+ * one writer and no launch clears it; no atomics: the same bits on every run. The state is that of `slots`. Under
+ * GraphNorm the copies of one batch normalise each other, as in every batched route. */
+typedef struct PvsScreenCopiesJob {
+    PvsScreenSlotsJob slots;        /* by value; layout PVS_SLOTS_CROPPED, rec_drop NULL */
+    const float* crop_pos; const int32_t* crop_ptr;
+    const int32_t* rec_drop;        /* may be NULL */
+    int32_t crop_cap;
+} PvsScreenCopiesJob;
+size_t pvs_screen_copies_state_bytes(const PvsScreenCopiesJob* job);
+int pvs_screen_copies_build(const PvsScreenCopiesJob* job, void* state, size_t state_bytes, pvs_stream_t stream);
+
+/* The keep decision of PVS_SLOTS_CROPPED for packed hits, without building anything (which receptor atoms each hit's
+ * cropped complex has: receptor_atom_masking(atoms='all') of a cropped sweep). lig_pos [n_rows,3] / lig_ptr [n_hits+1]
+ * (DEVICE, int32; a hit has 0..1024 atoms) against rec_pos [n_rec,3]. keep [n_hits, ceil(n_rec / 64)] uint64: bit
+ * j % 64 of word j / 64 of row s is set when some atom of hit s is closer to receptor atom j than crop_radius (> 0);
+ * kept_ptr [n_hits+1] int32: the exclusive scan of the hits' kept counts (the host reads kept_ptr[n_hits], one copy
+ * back). A lig_ptr that does not ascend from 0 inside n_rows, or a hit of more than 1024 atoms: keep and kept_ptr all
+ * zero and kept_ptr[n_hits] = -1. Two launches (the builders' keep kernel, one scan), no atomics: the same bits every
+ * time. */
+int pvs_crop_keep(const float* lig_pos, const int32_t* lig_ptr, int32_t n_hits, int32_t n_rows, const float* rec_pos,
+                  int32_t n_rec, double crop_radius, uint64_t* keep, int32_t* kept_ptr, pvs_stream_t stream);
+
 /* Complex batches: the node tables of B protein-ligand complexes built from a device-resident pool of structure
  * files, as the reference loader builds one sample on the host (data_loaders.py:259-309: ligand then receptor, crop of
  * the receptor to the atoms closer than `radius` to some ligand atom - fp64, scipy's cdist decision -, hydrogen filter
@@ -710,6 +749,20 @@ int pvs_leave_out_pair_pack(const float* lig_pos, const float* lig_feats, const 
                             int32_t n_rec, const int32_t* first_copy, int32_t n_slots, int32_t slot_cap, float* out_pos,
                             float* out_feats, int32_t* out_ptr, int32_t* rec_drop, int32_t* status,
                             pvs_stream_t stream);
+
+/* The PARENTS' atoms for the slots of a leave-out batch: what the slots of pvs_screen_copies_build are cropped around
+ * (crop_pos / crop_ptr). lig_pos [n_rows,3] / lig_ptr [n_hits+1] as above; copy_ptr [n_hits+1] (DEVICE, int32): hit s
+ * owns the copies copy_ptr[s] + s .. copy_ptr[s+1] + s, both ends included - the numbering of both packers above:
+ * copy_ptr = lig_ptr for ligand-atom copies, copy_ptr = pair_ptr for pair copies. Slot k holds copy first_copy[0] + k
+ * and gets the WHOLE hit's atoms, whichever atom the copy itself leaves out: the rows [out_ptr[k], out_ptr[k+1]) of
+ * out_pos (room for n_slots * slot_cap rows; those from out_ptr[n_slots] on are left as they are). A slot whose copy
+ * number is no copy gets none.
+ *   *status is stored by every launch: 0, or bit 3 with out_ptr all zeros and no row written when lig_ptr does not
+ *   ascend from 0 to at most n_rows, a hit has more than slot_cap (1..1024) atoms or copy_ptr does not ascend from 0.
+ * One launch, no atomics, no workspace: the same bits every time. */
+int pvs_leave_out_parent_pack(const float* lig_pos, const int32_t* lig_ptr, const int32_t* copy_ptr, int32_t n_hits,
+                              int32_t n_rows, const int32_t* first_copy, int32_t n_slots, int32_t slot_cap,
+                              float* out_pos, int32_t* out_ptr, int32_t* status, pvs_stream_t stream);
 
 /* Contact attention of a pose batch (the reference's attribution/hotspot.py over attribution_fns.edge_attention,
  * :278-295: per atom the largest attention value over its ligand-receptor edges, per receptor atom the mean of these

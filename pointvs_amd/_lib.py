@@ -76,6 +76,14 @@ class PvsScreenSlotsJob(C.Structure):
                 [('tables', PvsRaggedNodeTables), ('status', C.c_void_p)])
 
 
+class PvsScreenCopiesJob(C.Structure):
+    """The cropped-copies builder's job (pvs_screen_copies_build), field for field as pvs_egnn.h declares it
+    (tests/test_crop_copies_host.py compares every offset with the C compiler's): a PVS_SLOTS_CROPPED job by value, then
+    the crop table and the copies' rec_drop."""
+    _fields_ = [('slots', PvsScreenSlotsJob), ('crop_pos', C.c_void_p), ('crop_ptr', C.c_void_p),
+                ('rec_drop', C.c_void_p), ('crop_cap', C.c_int32)]
+
+
 class PvsComplexPool(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in ('rec_xyz', 'lig_xyz', 'rec_types', 'lig_types', 'rec_z', 'lig_z',
                                                 'rec_ptr', 'lig_ptr')] + [('n_rec', C.c_int32), ('n_lig', C.c_int32)]
@@ -139,6 +147,10 @@ _PROTOTYPES = {
                                [C.c_void_p, C.c_size_t, C.c_void_p]),
     'pvs_screen_slots_state_bytes': (C.c_size_t, [C.POINTER(PvsScreenSlotsJob)]),
     'pvs_screen_slots_build': (C.c_int, [C.POINTER(PvsScreenSlotsJob), C.c_void_p, C.c_size_t, C.c_void_p]),
+    'pvs_screen_copies_state_bytes': (C.c_size_t, [C.POINTER(PvsScreenCopiesJob)]),
+    'pvs_screen_copies_build': (C.c_int, [C.POINTER(PvsScreenCopiesJob), C.c_void_p, C.c_size_t, C.c_void_p]),
+    'pvs_crop_keep': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_double,
+                                C.c_void_p, C.c_void_p, C.c_void_p]),
     'pvs_mask_graph_workspace_bytes': (C.c_size_t, [C.c_int32, C.c_int32]),
     'pvs_mask_graph_build': (C.c_int, [C.POINTER(PvsGraph), C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32] +
                              [C.c_void_p] * 9 + [C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -205,6 +217,8 @@ _PROTOTYPES = {
                                          C.c_double, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     'pvs_leave_out_pair_pack': (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 5 + [C.c_void_p, C.c_int32, C.c_int32] +
                                 [C.c_void_p] * 5 + [C.c_void_p]),
+    'pvs_leave_out_parent_pack': (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 2 + [C.c_void_p, C.c_int32, C.c_int32] +
+                                  [C.c_void_p] * 3 + [C.c_void_p]),
     'pvs_contact_attention': (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 2 + [C.c_void_p] * 2 + [C.c_int32] * 2 +
                               [C.c_void_p] * 5 + [C.c_void_p]),
     'pvs_node_heads_fwd': (C.c_int, [C.c_void_p, C.POINTER(PvsHead), C.c_int32, C.c_void_p] + [C.c_int32] * 3 +

@@ -142,6 +142,56 @@ k_leave_out_pair_pack(const float* __restrict__ lig_pos, const float* __restrict
     }
 }
 
+// The PARENTS of a leave-out batch's copies (what a cropped copy is cropped around): slot k <- the whole hit that owns
+// copy first_copy + k in the numbering of copy_ptr (lig_ptr for ligand-atom copies, pair_ptr for pair copies: hit s owns
+// copy_ptr[s] + s ..; pvs_pair_copy's bisection is that arithmetic). One workgroup per slot, as the packers above: every
+// workgroup checks both tables whole, sums the parents' sizes of the slots before its own, stores its entry of out_ptr
+// and copies its rows. No atomics, nothing shared between workgroups.
+__global__ void __launch_bounds__(kPackThreads)
+k_leave_out_parent_pack(const float* __restrict__ lig_pos, const int32_t* __restrict__ lig_ptr,
+                        const int32_t* __restrict__ copy_ptr, int S, int n_rows,
+                        const int32_t* __restrict__ first_copy, int n_slots, int slot_cap,
+                        float* __restrict__ out_pos, int32_t* __restrict__ out_ptr, int32_t* __restrict__ status) {
+    __shared__ int wave_sum[kPackThreads / PVS_WAVE];
+    const int k = blockIdx.x, tid = threadIdx.x;
+    const bool last = k == n_slots - 1;
+    int bad = 0;
+    for (int t = tid; t <= S; t += kPackThreads)
+        bad |= !pvs_leave_out_table_ok(lig_ptr, S, t, slot_cap, n_rows) || !pvs_pair_table_ok(copy_ptr, S, t, INT32_MAX);
+    if (__syncthreads_or(bad)) {
+        if (tid == 0) {
+            out_ptr[k] = 0;
+            if (last) out_ptr[n_slots] = 0;
+            if (k == 0) *status = kPvsBadTable;
+        }
+        return;
+    }
+    const long long c0 = first_copy[0];
+    auto parent_atoms = [&](long long copy) {
+        const int hit = pvs_pair_copy(copy_ptr, S, copy).hit;
+        return hit < 0 ? 0 : lig_ptr[hit + 1] - lig_ptr[hit];
+    };
+    int before = 0;
+    for (int t = tid; t < k; t += kPackThreads) before += parent_atoms(c0 + t);
+#pragma unroll
+    for (int o = 1; o < PVS_WAVE; o <<= 1) before += __shfl_xor(before, o, PVS_WAVE);
+    if (tid % PVS_WAVE == 0) wave_sum[tid / PVS_WAVE] = before;
+    __syncthreads();
+    int at = 0;
+#pragma unroll
+    for (int w = 0; w < kPackThreads / PVS_WAVE; ++w) at += wave_sum[w];
+    const int hit = pvs_pair_copy(copy_ptr, S, c0 + k).hit;
+    const int first = hit < 0 ? 0 : lig_ptr[hit], n = hit < 0 ? 0 : lig_ptr[hit + 1] - first;
+    if (tid == 0) {
+        out_ptr[k] = at;
+        if (last) out_ptr[n_slots] = at + n;
+        if (k == 0) *status = 0;
+    }
+    const float* src = lig_pos + (size_t)first * 3;
+    float* dst = out_pos + (size_t)at * 3;
+    for (int e = tid; e < n * 3; e += kPackThreads) dst[e] = src[e];
+}
+
 // ---- the contacts of packed hits with the receptor: the pairs the pose-batch builder gives a class-1 edge ----
 // Wave per hit; atom by atom and 64 receptor atoms per trip, so a ballot's set bits are the atom's contacts in
 // ascending receptor order and the hit's pairs come out sorted by (a, r). fp64 distances and compares as k_contacts.
@@ -304,6 +354,23 @@ extern "C" int pvs_leave_out_ligand_pack(const float* lig_pos, const float* lig_
     k_leave_out_pack<<<n_slots, kPackThreads, 0, (hipStream_t)stream>>>(lig_pos, lig_feats, lig_ptr, n_ligands, n_rows,
                                                                         n_feats, first_copy, n_slots, slot_cap, out_pos,
                                                                         out_feats, out_ptr, status);
+    PVS_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int pvs_leave_out_parent_pack(const float* lig_pos, const int32_t* lig_ptr, const int32_t* copy_ptr,
+                                         int32_t n_hits, int32_t n_rows, const int32_t* first_copy, int32_t n_slots,
+                                         int32_t slot_cap, float* out_pos, int32_t* out_ptr, int32_t* status,
+                                         pvs_stream_t stream) {
+    PVS_REQUIRE(n_hits >= 0 && n_rows >= 0, "leave_out_parent_pack: %d hits, %d rows", n_hits, n_rows);
+    PVS_REQUIRE(n_slots >= 1 && slot_cap >= 1 && slot_cap <= kPvsMaxSlotCap,
+                "leave_out_parent_pack: %d slots of up to %d atoms (1..%d)", n_slots, slot_cap, kPvsMaxSlotCap);
+    PVS_REQUIRE((long long)n_slots * slot_cap * 3 < (1ll << 31), "leave_out_parent_pack: %d slots x %d atoms pass 2^31",
+                n_slots, slot_cap);
+    PVS_REQUIRE(lig_ptr && copy_ptr && first_copy && out_pos && out_ptr && status && (n_rows == 0 || lig_pos),
+                "leave_out_parent_pack: NULL argument");
+    k_leave_out_parent_pack<<<n_slots, kPackThreads, 0, (hipStream_t)stream>>>(
+        lig_pos, lig_ptr, copy_ptr, n_hits, n_rows, first_copy, n_slots, slot_cap, out_pos, out_ptr, status);
     PVS_CHECK_LAUNCH();
     return 0;
 }

@@ -16,6 +16,7 @@
 #include "common.h"
 #include "profile.h"
 #include "radius_common.h"
+#include "screen_copies.h"
 #include "screen_job.h"
 #include "screen_slots.h"
 #include <hipcub/hipcub.hpp>
@@ -477,23 +478,34 @@ k_node_tables_ragged(const float* __restrict__ lig_pos, const float* __restrict_
 // every word has one writer, so a build gives the same bits on every run. ----
 namespace {
 
-// The slot's atoms lig_ptr[p] .. lig_ptr[p + 1], or none where the pair is no slot of a valid table.
-__device__ __forceinline__ bool crop_slot_ok(int a0, int a1, int L_cap, int slot_cap) {
-    return a0 >= 0 && a1 >= a0 && a1 - a0 <= slot_cap && a1 <= L_cap;
+// The atoms a0 .. a1 of a packed table of `cap` rows, or none where the pair is no set of at most set_cap atoms of a
+// valid table.
+__device__ __forceinline__ bool crop_slot_ok(int a0, int a1, int cap, int set_cap) {
+    return a0 >= 0 && a1 >= a0 && a1 - a0 <= set_cap && a1 <= cap;
 }
 
-// block (p, y): the slot's ligand atoms staged in LDS; wave w of the block takes the mask word 4 y + w: lane l decides
-// receptor atom 64 (4 y + w) + l against every staged atom (fp64 on the fp32 coordinates, strict, no lower bound: a
-// coincident atom is kept), one ballot per word. An empty or invalid slot keeps nothing.
+// Which atoms the slots are cropped AROUND: the rows ptr[p] .. ptr[p + 1] of pos [cap, 3], at most set_cap (<=
+// kPvsMaxSlotCap) per slot, and, with `drop`, the receptor atom drop[p] that slot p lacks whatever the crop says (-1:
+// none). pvs_screen_slots_build: the slot's own ligand atoms and no drop; pvs_screen_copies_build: the job's crop table
+// (a leave-out copy's parent) and its rec_drop; pvs_crop_keep: packed hits.
+struct CropSets {
+    const float* pos;
+    const int32_t *ptr, *drop;
+    int cap, set_cap;
+};
+
+// THE keep decision, its one copy. block (p, y): the slot's crop set staged in LDS; wave w of the block takes the mask
+// word 4 y + w: lane l decides receptor atom 64 (4 y + w) + l against every staged atom (fp64 on the fp32 coordinates,
+// strict, no lower bound: a coincident atom is kept), then the dropped bit, one ballot per word. An empty or invalid
+// set keeps nothing.
 __global__ void __launch_bounds__(256)
-k_crop_keep(const float* __restrict__ lig_pos, const int32_t* __restrict__ lig_ptr, const float* __restrict__ rec_pos,
-            int L_cap, int n_rec, int slot_cap, Radius r_crop, u64* __restrict__ keep) {
+k_crop_keep(CropSets from, const float* __restrict__ rec_pos, int n_rec, Radius r_crop, u64* __restrict__ keep) {
     __shared__ float lig[3 * kPvsMaxSlotCap];
     const int p = blockIdx.x, lane = threadIdx.x & 63;
     const int W = pvs_rec_words(n_rec), c = 4 * blockIdx.y + (threadIdx.x >> 6);
-    const int a0 = lig_ptr[p], a1 = lig_ptr[p + 1];
-    const int n = crop_slot_ok(a0, a1, L_cap, slot_cap) ? a1 - a0 : 0;       // (<= slot_cap <= kPvsMaxSlotCap)
-    for (int t = threadIdx.x; t < 3 * n; t += 256) lig[t] = lig_pos[(size_t)a0 * 3 + t];
+    const int a0 = from.ptr[p], a1 = from.ptr[p + 1];
+    const int n = crop_slot_ok(a0, a1, from.cap, from.set_cap) ? a1 - a0 : 0;       // (<= set_cap <= kPvsMaxSlotCap)
+    for (int t = threadIdx.x; t < 3 * n; t += 256) lig[t] = from.pos[(size_t)a0 * 3 + t];
     __syncthreads();
     if (c >= W) return;
     const int i = 64 * c + lane;
@@ -502,25 +514,29 @@ k_crop_keep(const float* __restrict__ lig_pos, const int32_t* __restrict__ lig_p
         const double xr = rec_pos[3 * i], yr = rec_pos[3 * i + 1], zr = rec_pos[3 * i + 2];
         for (int a = 0; a < n && !in; ++a)
             in = below(pvs_sqdist((double)lig[3 * a], (double)lig[3 * a + 1], (double)lig[3 * a + 2], xr, yr, zr), r_crop);
+        if (from.drop) in = in && i != from.drop[p];
     }
     const u64 b = __ballot(in);
     if (lane == 0) keep[(size_t)p * W + c] = b;
 }
 
 // ONE block. First every slot's ranks (thread per slot: keep_rank[p, w] = the kept atoms before word w, entry W the
-// slot's count) and its verdict on lig_ptr; behind the barrier the node offsets (thread p adds the counts of the slots
-// before it: B is a batch size), the atom -> slot table and the status word, STORED as in k_slots. A table that is not
-// one: every offset 0 and kPvsBadTable, an edgeless batch of padding rows.
+// slot's count) and its verdict on lig_ptr - and, for copies (crop.ptr set), on the crop table and rec_drop; behind the
+// barrier the node offsets (thread p adds the counts of the slots before it: B is a batch size), the atom -> slot table
+// and the status word, STORED as in k_slots: this kernel stays the word's one writer for copies too. A table that is
+// not one: every offset 0 and kPvsBadTable, an edgeless batch of padding rows.
 __global__ void __launch_bounds__(256)
-k_crop_slots(const int32_t* __restrict__ lig_ptr, const u64* __restrict__ keep, int B, int L_cap, int n_rec,
-             int slot_cap, int32_t* __restrict__ keep_rank, int32_t* __restrict__ node_ptr,
+k_crop_slots(const int32_t* __restrict__ lig_ptr, CropSets crop, const u64* __restrict__ keep, int B, int L_cap,
+             int n_rec, int slot_cap, int32_t* __restrict__ keep_rank, int32_t* __restrict__ node_ptr,
              int32_t* __restrict__ slot_of, int32_t* __restrict__ status) {
     __shared__ int bad;
     const int W = pvs_rec_words(n_rec);
-    if (threadIdx.x == 0) bad = lig_ptr[0] != 0 ? 1 : 0;
+    if (threadIdx.x == 0) bad = (lig_ptr[0] != 0 || (crop.ptr && crop.ptr[0] != 0)) ? 1 : 0;
     __syncthreads();
     for (int p = threadIdx.x; p < B; p += 256) {
         if (!crop_slot_ok(lig_ptr[p], lig_ptr[p + 1], L_cap, slot_cap)) bad = 1;     // (every writer stores the same 1)
+        if (crop.ptr && !crop_slot_ok(crop.ptr[p], crop.ptr[p + 1], crop.cap, crop.set_cap)) bad = 1;
+        if (crop.drop && !pvs_rec_drop_ok(crop.drop[p], n_rec)) bad = 1;
         int32_t* rank = keep_rank + (size_t)p * (W + 1);
         int before = 0;
         for (int w = 0; w < W; ++w) {
@@ -541,6 +557,39 @@ k_crop_slots(const int32_t* __restrict__ lig_ptr, const u64* __restrict__ keep, 
         if (p == B) *status = ok ? 0 : kPvsBadTable;
         else if (ok) for (int q = lig_ptr[p]; q < lig_ptr[p + 1]; ++q) slot_of[q] = p;
     }
+}
+
+// pvs_crop_keep's second launch, ONE block: kept_ptr [S + 1] <- the exclusive scan of the hits' kept counts (thread t
+// owns a contiguous run of hits, as k_contact_scan of leave_out.hip). A lig_ptr that is no table of hits of at most
+// kPvsMaxSlotCap atoms inside n_rows: keep and kept_ptr zero, kept_ptr[S] = -1.
+__global__ void __launch_bounds__(256)
+k_crop_keep_scan(const int32_t* __restrict__ lig_ptr, int S, int n_rows, int W, u64* __restrict__ keep,
+                 int32_t* __restrict__ kept_ptr) {
+    __shared__ long long part[256];
+    const int tid = threadIdx.x, per = (S + 255) / 256;
+    const int lo = min(S, tid * per), hi = min(S, lo + per);
+    int bad = tid == 0 && lig_ptr[0] != 0;
+    long long sum = 0;
+    for (int s = lo; s < hi; ++s) {
+        bad |= !crop_slot_ok(lig_ptr[s], lig_ptr[s + 1], n_rows, kPvsMaxSlotCap);
+        for (int w = 0; w < W; ++w) sum += __popcll(keep[(size_t)s * W + w]);
+    }
+    part[tid] = sum;
+    bad = __syncthreads_or(bad);
+    long long at = 0, total = 0;
+    for (int t = 0; t < 256; ++t) {
+        if (t < tid) at += part[t];
+        total += part[t];
+    }
+    bad = bad || total > 0x7fffffffll;
+    for (int s = lo; s < hi; ++s) {
+        kept_ptr[s] = bad ? 0 : (int32_t)at;
+        for (int w = 0; w < W; ++w) {
+            at += __popcll(keep[(size_t)s * W + w]);
+            if (bad) keep[(size_t)s * W + w] = 0;
+        }
+    }
+    if (tid == 0) kept_ptr[S] = bad ? -1 : (int32_t)total;
 }
 
 // ---- the host path of all three layouts: check (screen_job.h), carve, then the layout's own first launch(es) and the
@@ -569,26 +618,30 @@ int start_slots(const PvsScreenSlotsJob& j, const ScreenState& w, hipStream_t s,
     return 0;
 }
 
-int start_slots(const PvsScreenSlotsJob& j, const ScreenState& w, hipStream_t s, PvsCroppedSlots* L) {
+// Cropped slots. crop: nullptr for slots cropped around their own ligand atoms (pvs_screen_slots_build), else the
+// crop table and rec_drop of pvs_screen_copies_build - the same two launches either way.
+int start_slots(const PvsScreenSlotsJob& j, const ScreenState& w, hipStream_t s, PvsCroppedSlots* L,
+                const CropSets* crop = nullptr) {
     const int W = pvs_rec_words(j.n_rec);
     u64* keep = (u64*)j.keep;
     *L = PvsCroppedSlots{j.lig_ptr, j.node_ptr, w.slot_of, j.status, keep, w.keep_rank, j.n_slots, j.lig_cap, j.n_rec,
                          j.slot_cap};
-    k_crop_keep<<<dim3(j.n_slots, (W + 3) / 4), 256, 0, s>>>(j.lig_pos, j.lig_ptr, j.rec_pos, j.lig_cap, j.n_rec,
-                                                              j.slot_cap, make_radius(j.crop_radius), keep);
+    const CropSets own{j.lig_pos, j.lig_ptr, nullptr, j.lig_cap, j.slot_cap};
+    k_crop_keep<<<dim3(j.n_slots, (W + 3) / 4), 256, 0, s>>>(crop ? *crop : own, j.rec_pos, j.n_rec,
+                                                              make_radius(j.crop_radius), keep);
     PVS_CHECK_LAUNCH();
-    k_crop_slots<<<1, 256, 0, s>>>(j.lig_ptr, keep, j.n_slots, j.lig_cap, j.n_rec, j.slot_cap, w.keep_rank, j.node_ptr,
-                                   w.slot_of, j.status);
+    k_crop_slots<<<1, 256, 0, s>>>(j.lig_ptr, crop ? *crop : CropSets{}, keep, j.n_slots, j.lig_cap, j.n_rec, j.slot_cap,
+                                   w.keep_rank, j.node_ptr, w.slot_of, j.status);
     PVS_CHECK_LAUNCH();
     return 0;
 }
 
 OutCsr out_csr(const PvsCsrOut& c) { return OutCsr{c.rowptr, c.row, c.col, c.etype, c.capacity}; }
 
-template <class Slots>
-int build_slots(const PvsScreenSlotsJob& j, const ScreenState& w, hipStream_t s) {
+template <class Slots, class... Start>
+int build_slots(const PvsScreenSlotsJob& j, const ScreenState& w, hipStream_t s, Start... start) {
     Slots L;
-    PVS_TRY(start_slots(j, w, s, &L));
+    PVS_TRY(start_slots(j, w, s, &L, start...));
     const PvsCsrOut lig = kCropped<Slots> ? PvsCsrOut{} : j.lig;       // (cropped slots: no ligand-touching CSR)
     PVS_TRY(build_csrs(L, j.lig_pos, j.rec_pos, j.rr_rowptr, j.rr_col, j.inter_radius, j.intra_radius, j.full.rowptr,
                        lig.rowptr, out_csr(j.full), out_csr(lig), j.inv_deg, j.status, false, w, s));
@@ -625,4 +678,51 @@ extern "C" int pvs_screen_slots_build(const PvsScreenSlotsJob* job, void* state,
         case PVS_SLOTS_RAGGED: return build_slots<PvsRaggedSlots>(*job, w, s);
         default: return build_slots<PvsCroppedSlots>(*job, w, s);
     }
+}
+
+// ---- cropped copies (PvsScreenCopiesJob): cropped slots whose masks come from the job's crop table and rec_drop; the
+// checks are screen_copies.h, the state and every launch behind the first two those of the embedded job ----
+extern "C" size_t pvs_screen_copies_state_bytes(const PvsScreenCopiesJob* job) {
+    char why[256];
+    if (!job || pvs_screen_copies_refusal(*job, true, why, sizeof(why))) return 0;
+    PvsArena a(nullptr, 0);
+    return carve_job(a, job->slots, nullptr) + 256;
+}
+
+extern "C" int pvs_screen_copies_build(const PvsScreenCopiesJob* job, void* state, size_t state_bytes,
+                                       pvs_stream_t stream_) {
+    const char* who = kPvsScreenCopiesWho;
+    hipStream_t s = (hipStream_t)stream_;
+    char why[256];
+    PVS_REQUIRE(job && state, "%s: NULL %s", who, job ? "state" : "job");
+    PVS_REQUIRE(!pvs_screen_copies_refusal(*job, false, why, sizeof(why)), "%s", why);
+    PvsArena arena(state, state_bytes);
+    ScreenState w;
+    carve_job(arena, job->slots, &w);
+    PVS_REQUIRE(arena.ok(), "%s: state too small (%zu < %zu)", who, state_bytes, arena.off);
+    PvsProfScope prof(s, PVS_PROF_PREPARE);
+    const CropSets crop{job->crop_pos, job->crop_ptr, job->rec_drop, job->crop_cap, kPvsMaxSlotCap};
+    return build_slots<PvsCroppedSlots>(job->slots, w, s, &crop);
+}
+
+extern "C" int pvs_crop_keep(const float* lig_pos, const int32_t* lig_ptr, int32_t n_hits, int32_t n_rows,
+                             const float* rec_pos, int32_t n_rec, double crop_radius, uint64_t* keep,
+                             int32_t* kept_ptr, pvs_stream_t stream_) {
+    hipStream_t s = (hipStream_t)stream_;
+    PVS_REQUIRE(n_hits >= 0 && n_rows >= 0 && n_rec >= 1, "pvs_crop_keep: %d hits, %d rows, %d receptor atoms", n_hits,
+                n_rows, n_rec);
+    PVS_REQUIRE(crop_radius > 0.0, "pvs_crop_keep: crop_radius must be positive (got %g)", crop_radius);
+    PVS_REQUIRE(lig_ptr && rec_pos && kept_ptr && (n_rows == 0 || lig_pos) && (n_hits == 0 || keep),
+                "pvs_crop_keep: NULL argument");
+    const int W = pvs_rec_words(n_rec);
+    PVS_REQUIRE((W + 3) / 4 <= 65535, "pvs_crop_keep: %d receptor atoms are more than one launch takes", n_rec);
+    if (n_hits > 0) {
+        const CropSets hits{lig_pos, lig_ptr, nullptr, n_rows, kPvsMaxSlotCap};
+        k_crop_keep<<<dim3(n_hits, (W + 3) / 4), 256, 0, s>>>(hits, rec_pos, n_rec, make_radius(crop_radius),
+                                                               (u64*)keep);
+        PVS_CHECK_LAUNCH();
+    }
+    k_crop_keep_scan<<<1, 256, 0, s>>>(lig_ptr, n_hits, n_rows, W, (u64*)keep, kept_ptr);
+    PVS_CHECK_LAUNCH();
+    return 0;
 }

@@ -752,6 +752,108 @@ def leave_out_pair_pack(lig_pos, lig_feats, lig_ptr, pairs, pair_ptr, n_rec, fir
     return out_pos, out_feats, out_ptr, rec_drop, status
 
 
+def leave_out_parent_pack(lig_pos, lig_ptr, copy_ptr, first_copy, n_slots, slot_cap, out=None):
+    """The PARENTS' atoms for the slots of a leave-out batch (pvs_leave_out_parent_pack): what the slots of a cropped
+    copies batch are cropped around. lig_pos [L, 3] fp32, lig_ptr [S + 1] int32, copy_ptr [S + 1] int32 (hit s owns the
+    copies copy_ptr[s] + s .. copy_ptr[s + 1] + s: lig_ptr itself for leave_out_ligand_pack's copies, pair_ptr for
+    leave_out_pair_pack's), first_copy: one int32, all on the device. Slot k holds copy first_copy + k and gets the WHOLE
+    hit's atoms (nothing past the last copy). Returns (out_pos [n_slots * slot_cap, 3], out_ptr [n_slots + 1] int32,
+    status [1] int32); `out`: those three tensors to write into. status: 8 when lig_ptr or copy_ptr does not ascend from
+    0 (lig_ptr inside L) or a hit has more than slot_cap atoms (out_ptr all zeros, no row written). One launch, no
+    atomics, no host synchronisation."""
+    lig_pos = _c(lig_pos, _F32, _FP32_ONLY)
+    n_slots, slot_cap = int(n_slots), int(slot_cap)
+    if lig_pos.dim() != 2 or lig_pos.shape[1] != 3:
+        raise ValueError('leave_out_parent_pack: lig_pos [L, 3]')
+    if lig_ptr.dtype != torch.int32 or lig_ptr.dim() != 1 or lig_ptr.numel() < 1:
+        raise ValueError('leave_out_parent_pack: an int32 lig_ptr [S + 1]')
+    if copy_ptr.dtype != torch.int32 or copy_ptr.dim() != 1 or copy_ptr.numel() != lig_ptr.numel():
+        raise ValueError('leave_out_parent_pack: an int32 copy_ptr [S + 1], as long as lig_ptr')
+    if first_copy.dtype != torch.int32 or first_copy.numel() < 1:
+        raise ValueError('leave_out_parent_pack: first_copy is one int32 on the device')
+    if n_slots < 1 or slot_cap < 1:
+        raise ValueError(f'leave_out_parent_pack: {n_slots} slots of up to {slot_cap} atoms')
+    _lib.require_hip(lig_pos, lig_ptr, copy_ptr, first_copy)
+    dev, rows = lig_pos.device, n_slots * slot_cap
+    if out is None:
+        out = (torch.empty((rows, 3), dtype=torch.float32, device=dev),
+               torch.empty(n_slots + 1, dtype=torch.int32, device=dev), torch.empty(1, dtype=torch.int32, device=dev))
+    out_pos, out_ptr, status = out
+    _lib.require_hip(*out)
+    if (out_pos.dtype != torch.float32 or out_pos.dim() != 2 or out_pos.shape[0] < rows or out_pos.shape[1] != 3
+            or out_ptr.dtype != torch.int32 or out_ptr.numel() != n_slots + 1 or status.dtype != torch.int32
+            or status.numel() < 1):
+        raise ValueError(f'leave_out_parent_pack: out = (pos [>= {rows}, 3], int32 ptr [{n_slots + 1}], int32 status '
+                         '[1])')
+    _lib.check(_lib.lib().pvs_leave_out_parent_pack(
+        _lib.ptr(lig_pos), _lib.ptr(lig_ptr.contiguous()), _lib.ptr(copy_ptr.contiguous()), lig_ptr.numel() - 1,
+        lig_pos.shape[0], _lib.ptr(first_copy), n_slots, slot_cap, _lib.ptr(out_pos), _lib.ptr(out_ptr),
+        _lib.ptr(status), _stream(dev)), 'pvs_leave_out_parent_pack')
+    return out_pos, out_ptr, status
+
+
+def crop_keep(lig_pos, lig_ptr, rec_pos, crop_radius, host_ptr=False):
+    """Which receptor atoms the cropped complex of each packed hit keeps (pvs_crop_keep: the keep decision of the
+    cropped pose-batch builders, by the same kernel, without building anything). lig_pos [L, 3] fp32, lig_ptr [S + 1]
+    int32 (a hit has up to 1024 atoms), rec_pos [n_rec, 3] fp32, all on the device. Returns (keep [S, ceil(n_rec / 64)]
+    int64: bit j % 64 of word j / 64 of row s is set when some atom of hit s is closer to receptor atom j than
+    crop_radius; kept_ptr [S + 1] int32, the exclusive scan of the kept counts). kept_ptr[S] is read back once (the
+    call's one wait for the device); ValueError when lig_ptr is no such table inside L. host_ptr: that one copy brings
+    the whole kept_ptr, returned third (a host int32 tensor)."""
+    lig_pos, rec_pos = _c(lig_pos, _F32, _FP32_ONLY), _c(rec_pos, _F32, _FP32_ONLY)
+    if lig_pos.dim() != 2 or lig_pos.shape[1] != 3 or rec_pos.dim() != 2 or rec_pos.shape[1] != 3 or rec_pos.shape[0] < 1:
+        raise ValueError('crop_keep: lig_pos [L, 3] and rec_pos [n_rec >= 1, 3]')
+    if lig_ptr.dtype != torch.int32 or lig_ptr.dim() != 1 or lig_ptr.numel() < 1:
+        raise ValueError('crop_keep: an int32 lig_ptr [S + 1]')
+    if not float(crop_radius) > 0:
+        raise ValueError(f'crop_keep: crop_radius must be positive (got {crop_radius})')
+    _lib.require_hip(lig_pos, lig_ptr, rec_pos)
+    dev, n_hits, n_rec = lig_pos.device, lig_ptr.numel() - 1, rec_pos.shape[0]
+    keep = torch.empty((n_hits, (n_rec + 63) // 64), dtype=torch.int64, device=dev)
+    kept_ptr = torch.empty(n_hits + 1, dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().pvs_crop_keep(_lib.ptr(lig_pos), _lib.ptr(lig_ptr.contiguous()), n_hits, lig_pos.shape[0],
+                                        _lib.ptr(rec_pos), n_rec, float(crop_radius), _lib.ptr(keep), _lib.ptr(kept_ptr),
+                                        _stream(dev)), 'pvs_crop_keep')
+    on_host = kept_ptr.cpu() if host_ptr else kept_ptr[n_hits:].cpu()
+    if int(on_host[-1]) < 0:
+        raise ValueError('crop_keep: lig_ptr is not an ascending table from 0 of hits of up to 1024 atoms inside lig_pos')
+    return (keep, kept_ptr, on_host) if host_ptr else (keep, kept_ptr)
+
+
+def kept_atoms(keep, n_rec):
+    """The set bits of keep masks [S, ceil(n_rec / 64)] int64 as (hit [M] int64, receptor atom [M] int64), ascending by
+    hit, then by atom, made on the device."""
+    bits = torch.arange(64, device=keep.device, dtype=torch.int64)
+    on = ((keep.unsqueeze(2) >> bits) & 1).reshape(keep.shape[0], -1)[:, :int(n_rec)].bool()
+    hit, atom = on.nonzero(as_tuple=True)
+    return hit, atom
+
+
+def screen_copies_state_bytes(job):
+    """The bytes of state that pvs_screen_copies_build needs for `job` (a _lib.PvsScreenCopiesJob; only its layout and
+    counts are read); ValueError for counts or a layout that the build refuses."""
+    if not isinstance(job, _lib.PvsScreenCopiesJob):
+        raise ValueError('screen_copies_state_bytes: a _lib.PvsScreenCopiesJob')
+    n = int(_lib.lib().pvs_screen_copies_state_bytes(C.byref(job)))
+    if n == 0:
+        raise ValueError('screen_copies_state_bytes: the job is not PVS_SLOTS_CROPPED, or its counts (n_slots, lig_cap, '
+                         'n_rec, slot_cap, crop_cap) are ones that pvs_screen_copies_build refuses')
+    return n
+
+
+def screen_copies_build(job, state):
+    """pvs_screen_copies_build of `job` (a _lib.PvsScreenCopiesJob of device addresses) with the scratch `state` (a
+    uint8 tensor on the device, at least screen_copies_state_bytes(job)), on the current stream of the state's device.
+    Everything the entry refuses it refuses by name before any launch (RuntimeError with its words)."""
+    if not isinstance(job, _lib.PvsScreenCopiesJob):
+        raise ValueError('screen_copies_build: a _lib.PvsScreenCopiesJob')
+    if state.dtype != torch.uint8 or not state.is_contiguous():
+        raise ValueError('screen_copies_build: state is a contiguous uint8 tensor')
+    _lib.require_hip(state)
+    _lib.check(_lib.lib().pvs_screen_copies_build(C.byref(job), _lib.ptr(state), state.numel(), _stream(state.device)),
+               'pvs_screen_copies_build')
+
+
 def new_contact_accumulators(n_rec, device):
     """Fresh accumulators of `contact_attention`: (rec_sum [n_rec] float64 zeros, rec_count [n_rec] int32 zeros,
     rec_max [n_rec] float32 NaN: none so far)."""

@@ -113,6 +113,16 @@ def _ready_screen(sweep, hits, which, **kw):
     return screen
 
 
+def _copies_screen(sweep, hits, which, **kw):
+    """`_ready_screen` for a stream of leave-out copies: the sweep's screen `which` - on a cropped sweep
+    (cropped_attribution=True) the ONE LibraryScreen(crop_parents=True) of all three masking methods,
+    `sweep.cropped_copies`, whose slots are cropped around their parents; its sizing batch of whole ligands bounds every
+    copy's graph, a subgraph of its whole cropped complex."""
+    if sweep.crop_radius is not None:
+        return _ready_screen(sweep, hits, 'cropped_copies', crop_parents=True)
+    return _ready_screen(sweep, hits, which, **kw)
+
+
 def _leave_out_stream(sweep, screen, plan, total, load, sigmoid):
     """The batches of `plan` through `screen`: load(batch, first_copy [1] int32 on the device) lays a batch out (one
     packer launch), then the one captured step; the builder's status one batch late, the packer's verdict after the
@@ -137,7 +147,7 @@ def ligand_atom_masking(sweep, items, scores_file=None, sigmoid=None, column=0):
     sweep.atom_masking_raw = {}
     if not hits.items:
         return {}
-    screen = _ready_screen(sweep, hits, 'masking')
+    screen = _copies_screen(sweep, hits, 'masking')
     hits.pack(sweep.rec_pos.device)
     raw, scored = _leave_out_stream(
         sweep, screen, leave_out_plan(ns, sweep.b), sum(ns) + len(ns),
@@ -156,7 +166,7 @@ def _pair_copies(sweep, hits, pairs, counts, ligand_atom, sigmoid):
     struck LibraryScreen `sweep.struck` in dense batches (load_leave_out_pairs). Returns (raw [K + hits, C], the same
     with the sweep's sigmoid)."""
     dev = sweep.rec_pos.device
-    screen = _ready_screen(sweep, hits, 'struck', struck=True)
+    screen = _copies_screen(sweep, hits, 'struck', struck=True)
     hits.pack(dev)
     pair_ptr = torch.tensor([0] + list(counts)).cumsum(0).to(device=dev, dtype=torch.int32)
     return _leave_out_stream(
@@ -173,6 +183,12 @@ def _hit_contacts(sweep, hits):
     pairs, _, host_ptr = PF.contact_pairs(hits.pos, hits.lig_ptr, sweep.rec_pos.float().contiguous(),
                                           sweep.edge_radius, host_ptr=True)
     return pairs, [int(k) for k in (host_ptr[1:] - host_ptr[:-1]).tolist()]
+
+
+def _hit_keep(sweep, hits):
+    """PF.crop_keep of the hits at the sweep's crop radius: (keep masks [hits, words], kept_ptr, the host's kept_ptr)."""
+    hits.pack(sweep.rec_pos.device)
+    return PF.crop_keep(hits.pos, hits.lig_ptr, sweep.rec_pos.float().contiguous(), sweep.crop_radius, host_ptr=True)
 
 
 @torch.no_grad()
@@ -210,6 +226,11 @@ def receptor_atom_masking(sweep, items, atoms='contacts', scores_file=None, sigm
         keys = torch.unique(hit * n_rec + pairs[:, 1].long())         # ascending: by hit, then by receptor atom
         which = (keys % n_rec).to(torch.int32)
         counts = torch.bincount(keys // n_rec, minlength=n_hits).tolist()
+    elif isinstance(atoms, str) and atoms == 'all' and sweep.crop_radius is not None:
+        # every atom of each hit's cropped complex: the builders' keep decision, counts from its one copy back
+        keep, _, host_ptr = _hit_keep(sweep, hits)
+        which = PF.kept_atoms(keep, n_rec)[1].to(torch.int32)
+        counts = [int(k) for k in (host_ptr[1:] - host_ptr[:-1]).tolist()]
     elif isinstance(atoms, str) and atoms == 'all':
         which = torch.arange(n_rec, dtype=torch.int32, device=dev).repeat(n_hits)
         counts = [n_rec] * n_hits
@@ -219,6 +240,14 @@ def receptor_atom_masking(sweep, items, atoms='contacts', scores_file=None, sigm
             raise ValueError(f'receptor_atom_masking: atoms must be receptor atoms 0..{n_rec - 1}')
         which = torch.tensor(host, dtype=torch.int32, device=dev).repeat(n_hits)
         counts = [len(host)] * n_hits
+        if sweep.crop_radius is not None and host:
+            # an atom a hit's crop does not keep is no atom of that hit's complex: the list intersected with the kept
+            # atoms per hit, order kept
+            keep = _hit_keep(sweep, hits)[0]
+            at = which[:len(host)].long()
+            on = ((keep[:, at >> 6] >> (at & 63)) & 1).bool()      # [hits, atoms]
+            which = which[on.reshape(-1)]
+            counts = [int(k) for k in on.sum(1).tolist()]
     else:
         raise ValueError(f"receptor_atom_masking: atoms={atoms!r}: 'contacts', 'all' or a 1-D index tensor")
     table = torch.stack([torch.full_like(which, -1), which], 1).contiguous()

@@ -621,13 +621,30 @@ class LibraryScreen(_ReceptorSideScreen):
     captured_scoring.model_refusal accepts them (fp32, no edge_residual, 17..128 channels: NotImplementedError
     otherwise); GraphNorm models need padded_graphnorm=True (the row count is only known on the device); struck, cam
     and contact_attention do not go with it (their reductions assume n_rec rows per slot): ValueError. None: the screen
-    launches exactly what it launches without the keyword."""
+    launches exactly what it launches without the keyword.
+
+    crop_parents (opt-in, default False; needs crop_radius): the slots may be leave-out COPIES of hits on the hits'
+    cropped complexes - the reference's atom_masking / bond_masking get the loader's complex, cropped around the WHOLE
+    ligand, and strike atoms out of that one, so a copy must not be cropped again around what is left of it. The screen
+    then owns three more static tables - `crop_pos [batch_size * max_lig_atoms, 3]` / `crop_ptr [batch_size + 1]`: the
+    atoms every slot is cropped AROUND, and `rec_drop [batch_size]`: -1 or the receptor atom the slot lacks whatever the
+    crop says - and its step builds with pvs_screen_copies_build; everything behind the builder is the cropped step
+    above. A plain load (`screen(slots)`, `load_packed`) crops every slot around its own atoms - the ligand table is
+    copied into the crop table on the device, rec_drop is -1 - and gives the bits of a screen without the keyword.
+    `load_leave_out` and `load_leave_out_pairs` work on such a screen: the existing packer launch plus one
+    PF.leave_out_parent_pack launch that lays the copies' parents into the crop table, both outside the captured step;
+    the pair packer writes this screen's rec_drop. Under GraphNorm the copies of one batch normalise each other, as in
+    every batched route. False: the screen launches exactly what it launches without the keyword."""
 
     def __init__(self, model, rec_pos, rec_feats, batch_size, max_lig_atoms, edge_radius, intra_radius=None,
                  tasks=None, contact_attention=None, cam=None, struck=None, padded_graphnorm=False,
-                 softmax_reuse=False, crop_radius=None):
+                 softmax_reuse=False, crop_radius=None, crop_parents=False):
         super().__init__(model, edge_radius, intra_radius, tasks, softmax_reuse)
         self.struck = bool(struck)
+        self.crop_parents = bool(crop_parents)
+        if self.crop_parents and crop_radius is None:
+            raise ValueError('LibraryScreen(crop_parents=True) needs crop_radius: the parents\' atoms are what a cropped '
+                             'slot is cropped around')
         self.padded_graphnorm = bool(padded_graphnorm)
         self.crop_radius = None if crop_radius is None else float(crop_radius)
         if self.crop_radius is not None:
@@ -677,7 +694,11 @@ class LibraryScreen(_ReceptorSideScreen):
             pos=pinned((self.l_cap, 3), torch.float32), feats=pinned((self.l_cap, n_feats), torch.float32),
             ptr=pinned(self.b + 1, torch.int32)))
         self._pack_status = None     # load_leave_out's status word
-        self.rec_drop = torch.full((self.b,), -1, dtype=torch.int32, device=dev) if self.struck else None
+        self.rec_drop = (torch.full((self.b,), -1, dtype=torch.int32, device=dev)
+                         if self.struck or self.crop_parents else None)
+        if self.crop_parents:        # what every slot is cropped around (a plain load: its own atoms)
+            self.crop_pos = torch.zeros((self.l_cap, 3), dtype=torch.float32, device=dev)
+            self.crop_ptr = torch.zeros(self.b + 1, dtype=torch.int32, device=dev)
         self._n_struck = 0           # host copy: how many slots of the loaded batch lack a receptor atom
         self.contact_attention = resolve_attention_layer(model, contact_attention)       # (index into model.layers)
         self.contact = None
@@ -788,18 +809,32 @@ class LibraryScreen(_ReceptorSideScreen):
 
     def _packer_status(self):
         """The status word of the leave-out packers, allocated at the first leave-out batch."""
-        if self._pack_status is None:
-            self._pack_status = torch.zeros(1, dtype=torch.int32, device=self.lig_pos.device)
+        if self._pack_status is None:      # (crop_parents: a second word, the parent packer's)
+            self._pack_status = torch.zeros(2 if self.crop_parents else 1, dtype=torch.int32,
+                                            device=self.lig_pos.device)
         return self._pack_status
+
+    def _crop_around_own_atoms(self):
+        """crop_parents, a plain load: the crop table <- the ligand table, on the device."""
+        if self.crop_parents:
+            self.crop_pos.copy_(self.lig_pos)
+            self.crop_ptr.copy_(self.lig_ptr)
+
+    def _pack_parents(self, lig_pos, lig_ptr, copy_ptr, first_copy):
+        """crop_parents, a leave-out load: the crop table <- the whole hits behind the batch's copies
+        (PF.leave_out_parent_pack, one launch)."""
+        if self.crop_parents:
+            PF.leave_out_parent_pack(lig_pos, lig_ptr, copy_ptr, first_copy, self.b, self.max_lig_atoms,
+                                     out=(self.crop_pos, self.crop_ptr, self._packer_status()[1:]))
 
     def _load_rec_drop(self, rec_drop, n_slots):
         """The static rec_drop of a struck screen <- a host list (None: every slot has the whole receptor). Returns
         how many slots lack a receptor atom."""
         if rec_drop is None:
-            if self.struck:
+            if self.rec_drop is not None:
                 self.rec_drop.fill_(-1)
             return 0
-        if not self.struck:
+        if self.rec_drop is None:
             raise ValueError('rec_drop: the screen was built without struck=True')
         drops = [int(r) for r in rec_drop]
         if len(drops) > self.b or len(drops) != n_slots or any(not -1 <= r < self.n_rec for r in drops):
@@ -821,6 +856,7 @@ class LibraryScreen(_ReceptorSideScreen):
         self.lig_pos[:total].copy_(lig_pos, non_blocking=True)
         self.lig_feats[:total].copy_(lig_feats, non_blocking=True)
         self.lig_ptr.copy_(lig_ptr, non_blocking=True)
+        self._crop_around_own_atoms()
         self._loaded(sizes, n_struck)
         return self
 
@@ -853,7 +889,8 @@ class LibraryScreen(_ReceptorSideScreen):
         verdict on lig_ptr."""
         sizes = self._checked_sizes(sizes)
         PF.leave_out_ligand_pack(lig_pos, lig_feats, lig_ptr, first_copy, self.b, self.max_lig_atoms,
-                                 out=(self.lig_pos, self.lig_feats, self.lig_ptr, self._packer_status()))
+                                 out=(self.lig_pos, self.lig_feats, self.lig_ptr, self._packer_status()[:1]))
+        self._pack_parents(lig_pos, lig_ptr, lig_ptr, first_copy)
         self._loaded(sizes, self._load_rec_drop(None, len(sizes)))
         return self
 
@@ -864,24 +901,29 @@ class LibraryScreen(_ReceptorSideScreen):
         among them. `sizes`, `n_struck`: the host's copy of the slots' atom counts and of how many of them lack a
         receptor atom (a batch of `leave_out_pair_plan`); nothing is copied back. `check_leave_out()` reads the
         packer's verdict on the tables."""
-        if not self.struck:
-            raise ValueError('load_leave_out_pairs: the screen was built without struck=True')
+        if not self.struck and not self.crop_parents:
+            raise ValueError('load_leave_out_pairs: the screen was built without struck=True (or, cropped, without '
+                             'crop_parents=True): it has no rec_drop table')
         sizes = self._checked_sizes(sizes)
         if not 0 <= int(n_struck) <= len(sizes):
             raise ValueError(f'n_struck: 0..{len(sizes)} of the batch\'s slots (got {n_struck})')
         PF.leave_out_pair_pack(lig_pos, lig_feats, lig_ptr, pairs, pair_ptr, self.n_rec, first_copy, self.b,
                                self.max_lig_atoms,
-                               out=(self.lig_pos, self.lig_feats, self.lig_ptr, self.rec_drop, self._packer_status()))
+                               out=(self.lig_pos, self.lig_feats, self.lig_ptr, self.rec_drop,
+                                    self._packer_status()[:1]))
+        self._pack_parents(lig_pos, lig_ptr, pair_ptr, first_copy)
         self._loaded(sizes, n_struck)
         return self
 
     def check_leave_out(self):
         """Raises if the last load_leave_out() was given a lig_ptr that is no table of 0..max_lig_atoms-atom ligands
         (its batch was empty then). Waits for the device."""
-        if self._pack_status is not None and int(self._pack_status.item()) & 8:
+        # (crop_parents: the parent packer's word beside the packer's, one copy back for both)
+        if self._pack_status is not None and any(int(code) & 8 for code in self._pack_status.tolist()):
             raise ValueError(f'LibraryScreen.load_leave_out: lig_ptr is not a table of 0..{self.max_lig_atoms}-atom '
                              'ligands inside lig_pos'
-                             + (', or the pair table is not one of pairs inside them' if self.struck else ''))
+                             + (', or the pair table is not one of pairs inside them'
+                                if self.struck or self.crop_parents else ''))
 
     # ---- the graph and the node tables ----
     def _buffers(self, cap, cap_l, feats=False, base=False, keep=False, att_l=False, pgs=False, pg=False):
@@ -937,7 +979,8 @@ class LibraryScreen(_ReceptorSideScreen):
         p = _lib.ptr
         cropped = 'keep' in f
         job = _lib.PvsScreenSlotsJob(
-            layout=self._layout(cropped), lig_pos=p(self.lig_pos), lig_ptr=p(self.lig_ptr), rec_drop=p(self.rec_drop),
+            layout=self._layout(cropped), lig_pos=p(self.lig_pos), lig_ptr=p(self.lig_ptr),
+            rec_drop=p(self.rec_drop) if self.struck else None,
             rec_pos=p(self._rec_pos), rr_rowptr=p(self._rr.t['rowptr']), rr_col=p(self._rr.t['col']), n_slots=self.b,
             lig_cap=self.l_cap, n_rec=self.n_rec, slot_cap=self.slot_cap, inter_radius=float(self.r_inter),
             intra_radius=float(self.r_intra), crop_radius=self.crop_radius if cropped else 0.0,
@@ -961,8 +1004,14 @@ class LibraryScreen(_ReceptorSideScreen):
         return job
 
     def _launch_builder(self, f, probe=False):
-        """pvs_screen_slots_build of the loaded batch into f."""
+        """pvs_screen_slots_build of the loaded batch into f - pvs_screen_copies_build for the cropped step of a
+        crop_parents screen (its probe is the uncropped builder's, like every cropped screen's)."""
         job = self._job(f, probe)
+        if self.crop_parents and 'keep' in f:
+            p = _lib.ptr
+            PF.screen_copies_build(_lib.PvsScreenCopiesJob(slots=job, crop_pos=p(self.crop_pos), crop_ptr=p(self.crop_ptr),
+                                                           rec_drop=p(self.rec_drop), crop_cap=self.l_cap), f['state'])
+            return
         _lib.check(_lib.lib().pvs_screen_slots_build(C.byref(job), _lib.ptr(f['state']), f['state'].numel(),
                                                      _stream(self.lig_pos.device)), 'pvs_screen_slots_build')
 
@@ -1029,7 +1078,9 @@ class LibraryScreen(_ReceptorSideScreen):
     def _raise_for(self, code):
         if code & 8:
             raise ValueError(f'LibraryScreen: lig_ptr is not a table of 0..{self.slot_cap}-atom slots'
-                             + (f', or rec_drop has an entry outside -1..{self.n_rec - 1}' if self.struck else ''))
+                             + (f', or rec_drop has an entry outside -1..{self.n_rec - 1}'
+                                if self.struck or self.crop_parents else '')
+                             + (', or crop_ptr is no table of crop sets of up to 1024 atoms' if self.crop_parents else ''))
         if code & 4:
             raise RuntimeError('LibraryScreen: edge buffer overflow (more ligand contacts per atom than twice '
                                'the first batch); rebuild the screen with a denser first batch')
@@ -1201,12 +1252,32 @@ class ScreeningSweep:
     predictions, hits files, tasks and best_poses unchanged in form. The four attribution methods raise
     NotImplementedError on such a sweep: the reference masks after cropping around the WHOLE ligand, so a copy must not
     crop again around what is left of it.
+    cropped_attribution (opt-in, default False; needs crop_radius >= edge_radius, ValueError otherwise: below the edge
+    radius a listed contact's receptor atom may not be kept, at or above it every contact atom is): `ligand_atom_masking`,
+    `contact_masking` and `receptor_atom_masking` then work on the cropped sweep as the reference's masking does on the
+    loader's complex - every copy of a hit is cropped around the WHOLE hit and lacks what the copy leaves out - through
+    ONE LibraryScreen(crop_radius=..., crop_parents=True), `self.cropped_copies`; arguments, return values, `*_raw`,
+    score files, `column` and `sigmoid` as on an uncropped sweep. A receptor atom that a hit's crop does not keep is not
+    an atom of that hit's complex: atoms='all' means the kept atoms of each hit (PF.crop_keep), and an index tensor is
+    intersected with them per hit. Under GraphNorm the copies of one batch normalise each other, as in every batched
+    route. `receptor_hotspots` stays refused.
     """
 
     def __init__(self, model, rec_pos, rec_feats, edge_radius, batch_size=32, intra_radius=None, capture=True,
-                 receptor_name='receptor', tasks=None, padded_graphnorm=False, softmax_reuse=False, crop_radius=None):
+                 receptor_name='receptor', tasks=None, padded_graphnorm=False, softmax_reuse=False, crop_radius=None,
+                 cropped_attribution=False):
         self.model, self.rec_pos, self.rec_feats = model, rec_pos, rec_feats
         self.crop_radius = None if crop_radius is None else float(crop_radius)
+        self.cropped_attribution = bool(cropped_attribution)
+        if self.cropped_attribution and self.crop_radius is None:
+            raise ValueError('ScreeningSweep(cropped_attribution=True) needs crop_radius: without it the masking methods '
+                             'work on the whole receptor as they are')
+        if self.cropped_attribution and self.crop_radius < float(edge_radius):
+            raise ValueError(f'ScreeningSweep(cropped_attribution=True): crop_radius {self.crop_radius:g} is below the '
+                             f'edge radius {float(edge_radius):g} - a contact\'s receptor atom may then not be kept by '
+                             'the crop; mask at crop_radius >= edge_radius (training crops at 10 with edge radii of 4 to '
+                             '10)')
+        self.cropped_copies = None     # the LibraryScreen(crop_parents=True) of the masking methods of a cropped sweep
         self.crop_buckets = {}     # n_lig -> the cropped LibraryScreen of the ligands above run_library's max_lig_atoms
         self.padded_graphnorm = bool(padded_graphnorm)      # handed to every LibraryScreen of the sweep
         self.softmax_reuse = bool(softmax_reuse)            # handed to every screen of the sweep
@@ -1354,7 +1425,8 @@ class ScreeningSweep:
             self._pick_hits(names, sink, hits_file)
         return out
 
-    def _library_screen(self, max_atoms, which='library', contact_attention=None, cam=None, struck=None):
+    def _library_screen(self, max_atoms, which='library', contact_attention=None, cam=None, struck=None,
+                        crop_parents=False):
         """The sweep's LibraryScreen `which`, built anew when there is none, when the weights changed under it, when it
         is too narrow for `max_atoms`, when it reduces another layer's attention than `contact_attention` or maps
         another value than `cam`."""
@@ -1366,7 +1438,7 @@ class ScreeningSweep:
             screen = LibraryScreen(self.model, self.rec_pos, self.rec_feats, self.b, max_atoms, self.edge_radius,
                                    self.intra_radius, tasks=self.tasks, contact_attention=layer, cam=cam, struck=struck,
                                    padded_graphnorm=self.padded_graphnorm, softmax_reuse=self.softmax_reuse,
-                                   crop_radius=self.crop_radius)
+                                   crop_radius=self.crop_radius, crop_parents=crop_parents)
             setattr(self, which, screen)
         return screen
 
@@ -1463,6 +1535,8 @@ class ScreeningSweep:
 
     # ---- attribution of hits: the bodies are in hit_attribution.py ----
     def _no_attribution_when_cropped(self, method):
+        if self.cropped_attribution and method != 'receptor_hotspots':      # (the three masking methods: opted in)
+            return
         if self.crop_radius is not None:
             raise NotImplementedError(
                 f'ScreeningSweep(crop_radius=...).{method}: the reference masks after cropping around the WHOLE '
