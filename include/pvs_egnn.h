@@ -818,6 +818,39 @@ int pvs_slot_node_values(const float* y, int32_t ld_y, int32_t col, int32_t n_me
                          float* lig_val, float* slot_rec_val, double* rec_sum, int32_t* rec_count, float* rec_max,
                          pvs_stream_t stream);
 
+/* pvs_contact_attention and pvs_slot_node_values over the CROPPED pose-batch layout (PVS_SLOTS_CROPPED of
+ * pvs_screen_slots_build / pvs_screen_copies_build): slot p owns the rows node_ptr[p] .. node_ptr[p + 1], its
+ * lig_ptr[p + 1] - lig_ptr[p] ligand atoms first, then the receptor atoms whose bit is set in keep[p, :] (DEVICE,
+ * [n_slots, ceil(n_rec / 64)] words; atom j is bit j % 64 of word j / 64), in receptor order, compact: receptor atom j
+ * of slot p is row node_ptr[p] + n_lig_p + (the set bits of keep[p, :] below j). Outputs have the shapes and the
+ * meaning of the uncropped entries:
+ *   slot_rec_att / slot_rec_val [n_slots, n_rec]: for a KEPT atom the largest counted attention value of its row (NaN
+ *     without a contact) / its node value (a slot without ligand atoms: NaN, the uncropped rule); NaN for an atom that
+ *     is not kept - it is no atom of that slot's complex.
+ *   lig_att / lig_val [>= lig_ptr[n_slots]]: as uncropped (in a cropped CSR a ligand atom's class-1 edges reach kept
+ *     atoms only); the entries from lig_ptr[n_slots] on are left as they are. The caller provides lig_ptr[n_slots]
+ *     entries: no argument says how many there are, so a slot's ligand range is checked against the rows, not against
+ *     this array.
+ *   rec_sum / rec_count / rec_max [n_rec]: READ AND UPDATED by pvs_contact_attention's accumulation kernel itself, so
+ *     rec_count[j] grows by the slots that keep j and have a value for it.
+ * A slot is one iff 0 <= lig_ptr[p] <= lig_ptr[p + 1], it has at most 1024 ligand atoms, 0 <= node_ptr[p],
+ * node_ptr[p + 1] <= n_nodes, node_ptr[p + 1] - node_ptr[p] == its ligand atoms + the set bits of keep[p, :], and no
+ * bit at or beyond n_rec is set (csrc/contact_attention.h: pvs_cropped_slot); any other gets a row of NaN and no
+ * ligand write. A cropped batch may have fewer than n_slots * n_rec rows: that is not checked. NULL arguments, negative
+ * counts, columns outside ld_y and an n_mean other than 1 or 3 are refused before any launch; n_slots == 0 or
+ * n_rec == 0: returns 0 without a launch. One wavefront per (slot, mask word) counts the slot's words once and gives
+ * every lane its atom's row; every output element has one writer, no atomics: the same bits every time, whatever the
+ * launch geometry. Two launches each. */
+int pvs_contact_attention_cropped(const int32_t* rowptr, const uint8_t* etype, const float* att, int32_t n_nodes,
+                                  int32_t n_edges, const int32_t* node_ptr, const int32_t* lig_ptr,
+                                  const uint64_t* keep, int32_t n_slots, int32_t n_rec, float* lig_att,
+                                  float* slot_rec_att, double* rec_sum, int32_t* rec_count, float* rec_max,
+                                  pvs_stream_t stream);
+int pvs_slot_node_values_cropped(const float* y, int32_t ld_y, int32_t col, int32_t n_mean, int32_t n_nodes,
+                                 const int32_t* node_ptr, const int32_t* lig_ptr, const uint64_t* keep, int32_t n_slots,
+                                 int32_t n_rec, float* lig_val, float* slot_rec_val, double* rec_sum,
+                                 int32_t* rec_count, float* rec_max, pvs_stream_t stream);
+
 /* nn.BCEWithLogitsLoss() with its default mean reduction (point_neural_network_base.py:74, used at :365) over n logits:
  * loss[0] = mean(max(x, 0) - x t + log1p(exp(-|x|))), grad[i] = (sigmoid(x_i) - t_i) / n (what the backward scales by
  * the upstream gradient: pvs_scale_by_device_scalar, out[i] = a[i] * scalar[0] with the scalar in device memory). */

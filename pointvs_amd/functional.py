@@ -946,6 +946,88 @@ def slot_node_values(y, node_ptr, lig_ptr, n_rec, column=0, n_mean=1, out=None):
     return lig_val, slot_rec_val, rec_sum, rec_count, rec_max
 
 
+def _cropped_tables(who, node_ptr, lig_ptr, keep, n_rec):
+    """The slot tables of a cropped pose batch, checked: n_slots."""
+    if (node_ptr.dtype != torch.int32 or lig_ptr.dtype != torch.int32 or node_ptr.dim() != 1 or node_ptr.numel() < 1
+            or lig_ptr.shape != node_ptr.shape):
+        raise ValueError(f'{who}: int32 node_ptr and lig_ptr [n_slots + 1]')
+    n_slots = node_ptr.numel() - 1
+    if n_rec < 0:
+        raise ValueError(f'{who}: {n_rec} receptor atoms')
+    if keep.dtype != torch.int64 or keep.shape != (n_slots, (n_rec + 63) // 64) or not keep.is_contiguous():
+        raise ValueError(f'{who}: keep is a contiguous int64 tensor [{n_slots}, {(n_rec + 63) // 64}]: one mask of '
+                         f'{n_rec} receptor atoms per slot, atom j bit j % 64 of word j / 64')
+    return n_slots
+
+
+def _cropped_out(who, out, lig_room, n_slots, n_rec, dev, names):
+    """The five outputs of a cropped reduction: `out`, checked, or fresh ones with lig_room ligand rows of NaN."""
+    if out is None:
+        if lig_room is None:
+            raise ValueError(f'{who}: the ligand rows of a cropped batch are known on the device only - give lig_room '
+                             '(the ligand output then has that many rows, NaN-filled) or out')
+        out = (torch.full((int(lig_room),), float('nan'), dtype=torch.float32, device=dev),
+               torch.empty((n_slots, n_rec), dtype=torch.float32, device=dev)) + new_contact_accumulators(n_rec, dev)
+    lig, slot_rec, rec_sum, rec_count, rec_max = out
+    _lib.require_hip(*out)
+    if (lig.dtype != torch.float32 or slot_rec.dtype != torch.float32 or rec_sum.dtype != torch.float64
+            or rec_count.dtype != torch.int32 or rec_max.dtype != torch.float32 or lig.dim() != 1
+            or (lig_room is not None and lig.numel() < int(lig_room)) or slot_rec.shape != (n_slots, n_rec)
+            or rec_sum.shape != (n_rec,) or rec_count.shape != (n_rec,) or rec_max.shape != (n_rec,)
+            or not all(t.is_contiguous() for t in out)):
+        room = '>= lig_ptr[n_slots]' if lig_room is None else f'>= {int(lig_room)}'
+        raise ValueError(f'{who}: out = ({names[0]} [{room}], {names[1]} [{n_slots}, {n_rec}], float64 rec_sum [{n_rec}], '
+                         f'int32 rec_count [{n_rec}], rec_max [{n_rec}]), contiguous')
+    return out
+
+
+def contact_attention_cropped(rowptr, etype, att, node_ptr, lig_ptr, keep, n_rec, lig_room=None, out=None):
+    """`contact_attention` over a CROPPED pose batch (pvs_contact_attention_cropped): slot p owns the rows node_ptr[p] ..
+    node_ptr[p + 1], its lig_ptr[p + 1] - lig_ptr[p] ligand atoms, then the receptor atoms whose bit is set in keep[p]
+    (keep [n_slots, ceil(n_rec / 64)] int64 on the device, atom j bit j % 64 of word j / 64: LibraryScreen.keep), in
+    receptor order. Returns the five tensors of `contact_attention`; slot_rec_att[p, j] is NaN for an atom that slot p
+    does not keep, so rec_count[j] grows by the slots that keep j and in which it has a contact. The host does not know
+    how many ligand rows there are: without `out`, lig_att has `lig_room` rows (at least lig_ptr[n_slots]), NaN-filled;
+    with `out`, its lig_att holds at least lig_ptr[n_slots] (and lig_room, if given). Two launches, no atomics, no host
+    synchronisation: the same bits every time."""
+    who = 'contact_attention_cropped'
+    att = _c(att, _F32, _FP32_ONLY)
+    n_rec = int(n_rec)
+    if (rowptr.dtype != torch.int32 or rowptr.dim() != 1 or rowptr.numel() < 1 or etype.dtype != torch.uint8
+            or etype.dim() != 1 or att.dim() != 1 or att.numel() < etype.numel()):
+        raise ValueError(f'{who}: an int32 rowptr [N + 1], a uint8 etype [E] and att [>= E]')
+    n_slots = _cropped_tables(who, node_ptr, lig_ptr, keep, n_rec)
+    n_nodes, n_edges = rowptr.numel() - 1, etype.numel()
+    _lib.require_hip(rowptr, etype, att, node_ptr, lig_ptr, keep)
+    out = _cropped_out(who, out, lig_room, n_slots, n_rec, att.device, ('lig_att', 'slot_rec_att'))
+    _lib.check(_lib.lib().pvs_contact_attention_cropped(
+        _lib.ptr(rowptr), _lib.ptr(etype), _lib.ptr(att), n_nodes, n_edges, _lib.ptr(node_ptr), _lib.ptr(lig_ptr),
+        _lib.ptr(keep), n_slots, n_rec, *(_lib.ptr(t) for t in out), _stream(att.device)),
+        'pvs_contact_attention_cropped')
+    return out
+
+
+def slot_node_values_cropped(y, node_ptr, lig_ptr, keep, n_rec, column=0, n_mean=1, lig_room=None, out=None):
+    """`slot_node_values` over a CROPPED pose batch (pvs_slot_node_values_cropped; the layout and `keep` as for
+    `contact_attention_cropped`): slot_rec_val[p, j] is the node value of receptor atom j where slot p keeps it and has
+    ligand atoms, NaN otherwise, so rec_count[j] grows by the slots that keep j. lig_room / out as there."""
+    who = 'slot_node_values_cropped'
+    y = _c(y, _F32, _FP32_ONLY)
+    n_rec, column, n_mean = int(n_rec), int(column), int(n_mean)
+    if y.dim() != 2 or y.shape[1] < 1:
+        raise ValueError(f'{who}: y [N, C]')
+    if n_mean not in (1, 3) or not 0 <= column <= y.shape[1] - n_mean:
+        raise ValueError(f'{who}: column {column}, n_mean {n_mean}: one column or the mean of three, inside the '
+                         f'{y.shape[1]} of y')
+    n_slots = _cropped_tables(who, node_ptr, lig_ptr, keep, n_rec)
+    _lib.require_hip(y, node_ptr, lig_ptr, keep)
+    out = _cropped_out(who, out, lig_room, n_slots, n_rec, y.device, ('lig_val', 'slot_rec_val'))
+    _lib.check(_lib.lib().pvs_slot_node_values_cropped(
+        _lib.ptr(y), y.shape[1], column, n_mean, y.shape[0], _lib.ptr(node_ptr), _lib.ptr(lig_ptr), _lib.ptr(keep),
+        n_slots, n_rec, *(_lib.ptr(t) for t in out), _stream(y.device)), 'pvs_slot_node_values_cropped')
+    return out
+
+
 class _BceLogitsMeanFn(torch.autograd.Function):
     """nn.BCEWithLogitsLoss() (mean) as one launch forward (loss + the gradient factor), one backward."""
 

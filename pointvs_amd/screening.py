@@ -620,7 +620,17 @@ class LibraryScreen(_ReceptorSideScreen):
     int64 holds the last step's masks (bit j % 64 of word j / 64), `screen._fast['node_ptr']` its offsets. Models as
     captured_scoring.model_refusal accepts them (fp32, no edge_residual, 17..128 channels: NotImplementedError
     otherwise); GraphNorm models need padded_graphnorm=True (the row count is only known on the device); struck, cam
-    and contact_attention do not go with it (their reductions assume n_rec rows per slot): ValueError. None: the screen
+    and contact_attention do not go with it (their reductions assume n_rec rows per slot): ValueError - cam and
+    contact_attention unless `cropped_maps` is on. None: the screen launches exactly what it launches without the keyword.
+
+    cropped_maps (opt-in, default False; needs crop_radius, ValueError otherwise): `cam` and `contact_attention` on a
+    cropped screen - the maps of the complexes the scores are of. Behind the tail the step runs
+    PF.contact_attention_cropped / PF.slot_node_values_cropped, which find a receptor atom's row through the slot's keep
+    mask, into the same static buffers `screen.contact` / `screen.cam`, inside the captured step; an atom that a slot
+    does not keep has NaN in slot_rec_att / slot_rec_val and adds nothing to rec_count. contact_attention takes any layer
+    that has edge attention, 1 included: every layer of a cropped step runs on the one full CSR, so the values are the
+    layer's own (softmax attention: normalised over all edges of a row, nothing else needed). The models are those of a
+    cropped screen, not those of the first-layer reuse. struck stays refused. False, or True without a map: the screen
     launches exactly what it launches without the keyword.
 
     crop_parents (opt-in, default False; needs crop_radius): the slots may be leave-out COPIES of hits on the hits'
@@ -638,10 +648,14 @@ class LibraryScreen(_ReceptorSideScreen):
 
     def __init__(self, model, rec_pos, rec_feats, batch_size, max_lig_atoms, edge_radius, intra_radius=None,
                  tasks=None, contact_attention=None, cam=None, struck=None, padded_graphnorm=False,
-                 softmax_reuse=False, crop_radius=None, crop_parents=False):
+                 softmax_reuse=False, crop_radius=None, crop_parents=False, cropped_maps=False):
         super().__init__(model, edge_radius, intra_radius, tasks, softmax_reuse)
         self.struck = bool(struck)
         self.crop_parents = bool(crop_parents)
+        self.cropped_maps = bool(cropped_maps)
+        if self.cropped_maps and crop_radius is None:
+            raise ValueError('LibraryScreen(cropped_maps=True) needs crop_radius: without it cam and contact_attention '
+                             'reduce the whole receptor as they are')
         if self.crop_parents and crop_radius is None:
             raise ValueError('LibraryScreen(crop_parents=True) needs crop_radius: the parents\' atoms are what a cropped '
                              'slot is cropped around')
@@ -721,7 +735,7 @@ class LibraryScreen(_ReceptorSideScreen):
             raise ValueError(f'crop_radius must be positive (got {self.crop_radius})')
         for which, given in (('struck', self.struck), ('cam', cam is not None),
                              ('contact_attention', contact_attention is not None)):
-            if given:
+            if given and not (self.cropped_maps and which != 'struck'):      # (cropped_maps: the masked reductions)
                 raise ValueError(f'LibraryScreen(crop_radius=..., {which}=...): the {which} path assumes n_rec receptor '
                                  'rows in every slot, and a cropped slot has those inside the radius; use two screens')
         why = model_refusal(model)
@@ -757,10 +771,11 @@ class LibraryScreen(_ReceptorSideScreen):
         """The accumulators of `cam` as before the first step: sums and counts zero, maxima NaN (none so far)."""
         self._reset_values(self.cam, 'reset_cam', 'cam')
 
-    def _reduce_cam(self, h, node_ptr, lig_ptr):
+    def _reduce_cam(self, h, node_ptr, lig_ptr, keep=None):
         """The heads on every row of the final embedding h [n, H] into cam['node_y'][:n] - one launch (PF.node_heads)
         when every head is one that PF.pool_heads takes, else each head per node on the linear op - then the slots'
-        values and the accumulators (PF.slot_node_values)."""
+        values and the accumulators (PF.slot_node_values; keep: the masks of a cropped batch,
+        PF.slot_node_values_cropped)."""
         heads, widths, column, n_mean = self._cam_plan
         c, n = self.cam, h.shape[0]
         node_y = c['node_y'][:n]
@@ -772,8 +787,11 @@ class LibraryScreen(_ReceptorSideScreen):
             for head, width in zip(heads, widths):
                 node_y[:, at:at + width].copy_(self.model._run_head(head, h).reshape(n, width))
                 at += width
-        PF.slot_node_values(node_y, node_ptr, lig_ptr, self.n_rec, column, n_mean,
-                            out=(c['lig_val'], c['slot_rec_val'], c['rec_sum'], c['rec_count'], c['rec_max']))
+        out = (c['lig_val'], c['slot_rec_val'], c['rec_sum'], c['rec_count'], c['rec_max'])
+        if keep is not None:
+            PF.slot_node_values_cropped(node_y, node_ptr, lig_ptr, keep, self.n_rec, column, n_mean, out=out)
+            return
+        PF.slot_node_values(node_y, node_ptr, lig_ptr, self.n_rec, column, n_mean, out=out)
 
     def reset_contact_attention(self):
         """The accumulators of `contact` as before the first step: sums and counts zero, maxima NaN (none so far)."""
@@ -784,6 +802,19 @@ class LibraryScreen(_ReceptorSideScreen):
         c = self.contact
         PF.contact_attention(f['rowptr' + tag], f['etype' + tag], att, f['node_ptr'], self.lig_ptr, self.n_rec,
                              out=(c['lig_att'], c['slot_rec_att'], c['rec_sum'], c['rec_count'], c['rec_max']))
+
+    def _reduce_cropped_maps(self, f):
+        """The maps of a cropped step (cropped_maps=True), behind its tail: the attention that the layer's
+        forward_prepared left in the full CSR's order and / or the heads per node, each receptor atom found through the
+        slot's keep mask (PF.contact_attention_cropped, PF.slot_node_values_cropped)."""
+        if self.contact_attention is not None:
+            c = self.contact
+            PF.contact_attention_cropped(
+                f['rowptr'], f['etype'], self.model.layers[self.contact_attention]._att_sorted, f['node_ptr'],
+                self.lig_ptr, f['keep'], self.n_rec,
+                out=(c['lig_att'], c['slot_rec_att'], c['rec_sum'], c['rec_count'], c['rec_max']))
+        if self.cam is not None:
+            self._reduce_cam(self._h_final, f['node_ptr'], self.lig_ptr, f['keep'])
 
     def _cache_receptor_sums(self):
         """The receptor sums kept once, [n_rec, .]; every builder launch reads them (and the template) anew (`_job`)."""
@@ -1124,7 +1155,10 @@ class LibraryScreen(_ReceptorSideScreen):
         f = self._build()
         if self.crop_radius is not None:      # every layer on the one full CSR of the cropped batch, padded shape
             x = f['pos']
-            return self._tail(f['pg'], self.embed.embed(f['x'], x).contiguous(), x, layers=self.egnn)
+            y = self._tail(f['pg'], self.embed.embed(f['x'], x).contiguous(), x, layers=self.egnn)
+            if self.contact is not None or self.cam is not None:
+                self._reduce_cropped_maps(f)
+            return y
         # graphnorm's statistics run over the batch's nodes: no padding rows there (the host knows the count) - or, with
         # padded_graphnorm, the padded shape and the count where the builder left it (PvsGraph.n_norm_rows_dev)
         exact = self.graphnorm and not self._gn_padded
@@ -1250,8 +1284,8 @@ class ScreeningSweep:
     see it (LibraryScreen's docstring). `run` and `run_library` then go through cropped LibraryScreens - `run` is
     `run_library`, a ligand above max_lig_atoms gets a cropped screen of its own size (`self.crop_buckets`) - with
     predictions, hits files, tasks and best_poses unchanged in form. The four attribution methods raise
-    NotImplementedError on such a sweep: the reference masks after cropping around the WHOLE ligand, so a copy must not
-    crop again around what is left of it.
+    NotImplementedError on such a sweep unless one of the two keywords below opts them in: the reference masks after
+    cropping around the WHOLE ligand, so a copy must not crop again around what is left of it.
     cropped_attribution (opt-in, default False; needs crop_radius >= edge_radius, ValueError otherwise: below the edge
     radius a listed contact's receptor atom may not be kept, at or above it every contact atom is): `ligand_atom_masking`,
     `contact_masking` and `receptor_atom_masking` then work on the cropped sweep as the reference's masking does on the
@@ -1260,15 +1294,27 @@ class ScreeningSweep:
     score files, `column` and `sigmoid` as on an uncropped sweep. A receptor atom that a hit's crop does not keep is not
     an atom of that hit's complex: atoms='all' means the kept atoms of each hit (PF.crop_keep), and an index tensor is
     intersected with them per hit. Under GraphNorm the copies of one batch normalise each other, as in every batched
-    route. `receptor_hotspots` stays refused.
+    route. `receptor_hotspots` stays refused under this keyword; it runs under `cropped_hotspots`.
+    cropped_hotspots (opt-in, default False; needs crop_radius, ValueError otherwise; any crop radius - below the edge
+    radius a ligand atom's edges simply reach kept atoms only): `receptor_hotspots` then maps every hit on the complex
+    cropped around it, the one its score is of - the hits stream whole through LibraryScreen(crop_radius=...,
+    cropped_maps=True, contact_attention=gnn_layer | cam=...), still `self.hotspot` / `self.cam_screen`, in
+    ceil(hits / batch_size) steps; arguments, keys and score files as on an uncropped sweep. A receptor atom that a
+    hit's crop does not keep is no atom of that hit's complex: NaN in its per_hit row, nothing added to count - under
+    'cam' count[j] is the number of hits that keep j. A hit whose crop keeps nothing still has ligand values under
+    'cam'; under 'edge_attention' they are NaN.
     """
 
     def __init__(self, model, rec_pos, rec_feats, edge_radius, batch_size=32, intra_radius=None, capture=True,
                  receptor_name='receptor', tasks=None, padded_graphnorm=False, softmax_reuse=False, crop_radius=None,
-                 cropped_attribution=False):
+                 cropped_attribution=False, cropped_hotspots=False):
         self.model, self.rec_pos, self.rec_feats = model, rec_pos, rec_feats
         self.crop_radius = None if crop_radius is None else float(crop_radius)
         self.cropped_attribution = bool(cropped_attribution)
+        self.cropped_hotspots = bool(cropped_hotspots)
+        if self.cropped_hotspots and self.crop_radius is None:
+            raise ValueError('ScreeningSweep(cropped_hotspots=True) needs crop_radius: without it receptor_hotspots maps '
+                             'the whole receptor as it is')
         if self.cropped_attribution and self.crop_radius is None:
             raise ValueError('ScreeningSweep(cropped_attribution=True) needs crop_radius: without it the masking methods '
                              'work on the whole receptor as they are')
@@ -1438,7 +1484,8 @@ class ScreeningSweep:
             screen = LibraryScreen(self.model, self.rec_pos, self.rec_feats, self.b, max_atoms, self.edge_radius,
                                    self.intra_radius, tasks=self.tasks, contact_attention=layer, cam=cam, struck=struck,
                                    padded_graphnorm=self.padded_graphnorm, softmax_reuse=self.softmax_reuse,
-                                   crop_radius=self.crop_radius, crop_parents=crop_parents)
+                                   crop_radius=self.crop_radius, crop_parents=crop_parents,
+                                   cropped_maps=self.cropped_hotspots and (layer is not None or cam is not None))
             setattr(self, which, screen)
         return screen
 
@@ -1536,6 +1583,8 @@ class ScreeningSweep:
     # ---- attribution of hits: the bodies are in hit_attribution.py ----
     def _no_attribution_when_cropped(self, method):
         if self.cropped_attribution and method != 'receptor_hotspots':      # (the three masking methods: opted in)
+            return
+        if self.cropped_hotspots and method == 'receptor_hotspots':         # (the maps: opted in on their own)
             return
         if self.crop_radius is not None:
             raise NotImplementedError(
