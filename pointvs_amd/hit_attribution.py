@@ -103,7 +103,7 @@ def _ready_screen(sweep, hits, which, **kw):
     """The sweep's LibraryScreen `which` (ScreeningSweep._library_screen) wide enough for the hits, its edge buffers
     sized."""
     screen = sweep._library_screen(max(max(hits.ns), 1), which, **kw)
-    if screen.reuse and screen._fast is None:
+    if screen.needs_sizing_batch():
         # a new screen sizes its edge buffers from its first batch, and the first leave-out batch may hold the copies
         # of one small ligand: it is shown a batch of the largest whole ligands first (a copy has no more contacts per
         # atom than its whole complex; a struck screen, which always has the reuse, adds the struck rows' room itself)

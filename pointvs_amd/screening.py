@@ -20,6 +20,8 @@ from torch import nn
 
 from . import _lib
 from . import functional as PF
+from .library_steps import (STEPS, _PlainStep, _csr_buffers, _graph_pair, _ligand_csr, library_route,       # noqa: F401
+                            model_route)
 from .nowait import LateQueue, StagingRing, capture_fixed_step, pinned
 from .radius_graph import PoseBatcher, radius_graph
 
@@ -40,43 +42,6 @@ def _stream(dev):
 _ReuseKind = namedtuple('_ReuseKind', 'base_entry partial_entry ws_mode row_extra')
 _SUMS = _ReuseKind('pvs_egnn_layer_edge_sums', 'pvs_egnn_layer_fwd_partial_att', 2, 0)
 _SOFTMAX = _ReuseKind('pvs_egnn_layer_edge_stats_softmax', 'pvs_egnn_layer_fwd_partial_softmax', 3, 4)
-
-
-def _csr_buffers(dev, n_nodes, cap_l, cap=None, **extra):
-    """Buffers of a device-built pose-batch graph over n_nodes nodes: the ligand-touching CSR (`*_l`, room for cap_l
-    edges) and, with `cap`, the full CSR and its inv_deg; the builder's status word; `ones` (the ligand-touching
-    graph's inv_deg). The builders read f['cap'] / f['cap_l'] at every launch."""
-    i32 = dict(dtype=torch.int32, device=dev)
-    f = dict(cap=cap, cap_l=cap_l, status=torch.zeros(1, **i32), **extra)
-    for tag, c in (('', cap), ('_l', cap_l)):
-        if c is not None:
-            f['rowptr' + tag] = torch.empty(n_nodes + 1, **i32)
-            f['row' + tag] = torch.empty(c, **i32)
-            f['col' + tag] = torch.empty(c, **i32)
-            f['etype' + tag] = torch.empty(c, dtype=torch.uint8, device=dev)
-    if cap is not None:
-        f['inv_deg'] = torch.empty(n_nodes, dtype=torch.float32, device=dev)
-    f['ones'] = torch.ones(n_nodes, dtype=torch.float32, device=dev)
-    return f
-
-
-def _ligand_csr(f, n_nodes, n_end):
-    """PvsGraph of f's ligand-touching CSR over the first n_nodes nodes; its edge count stays on the device, in
-    rowptr_l[n_end] (the rows from n_nodes to n_end are padding, without edges)."""
-    gl = _lib.PvsGraph()
-    gl.n_nodes, gl.n_edges = n_nodes, f['cap_l']
-    gl.rowptr, gl.row, gl.col, gl.etype = (_lib.ptr(f[k + '_l']) for k in ('rowptr', 'row', 'col', 'etype'))
-    gl.inv_deg = _lib.ptr(f['ones'])
-    gl.n_edges_dev = f['rowptr_l'][n_end:].data_ptr()
-    return gl
-
-
-def _graph_pair(f, n_nodes, n_end):
-    """(PreparedGraph of f's full CSR, PvsGraph of its ligand-touching CSR) over the first n_nodes nodes, both with
-    device-side edge counts (rowptr[n_end])."""
-    from .graph import PreparedGraph
-    csr = {k: f[k] for k in ('rowptr', 'row', 'col', 'etype', 'inv_deg', 'status')}
-    return PreparedGraph.over_buffers(n_nodes, f['cap'], csr, f['rowptr'][n_end:]), _ligand_csr(f, n_nodes, n_end)
 
 
 TASKS = ('pose', 'affinity', 'both')
@@ -173,6 +138,7 @@ class _ReceptorSideScreen:
         self.tasks = _resolve_tasks(model, tasks)
         self.heads = None if self.tasks is None else model.task_heads(self.tasks)
         self._graph, self._captured, self._l1_ws, self._fast = None, False, None, None
+        self._fingerprint = None            # of the weights behind what is cached of the receptor; None: nothing is
         self._late = LateQueue(ring=1)      # the one status word in flight: checked before the next builder launch
         self.cam, self._h_final = None, None      # (LibraryScreen(cam=...): per-node heads of the final embedding)
 
@@ -192,7 +158,7 @@ class _ReceptorSideScreen:
     def stale(self):
         """True when the weights the cached receptor-receptor sums came from have changed since
         (load_weights(), an optimiser step): a captured step has those sums baked in."""
-        return self.reuse and self._fingerprint != self._weights_fingerprint()
+        return self._fingerprint is not None and self._fingerprint != self._weights_fingerprint()
 
     def _weights_changed(self):
         return RuntimeError(f'{type(self).__name__}: the model\'s weights changed after capture(); build a new screen')
@@ -566,85 +532,71 @@ class LibraryScreen(_ReceptorSideScreen):
         screen = LibraryScreen(model, rec_pos, rec_feats, batch_size, max_lig_atoms, edge_radius)
         scores = screen([(lig_feats [n,F], pose [n,3]), ...])        # [batch_size, ...] raw outputs
 
-    What ReceptorScreen reuses across the poses of one ligand is reused across ligands: the receptor-receptor
-    template CSR and the first layer's receptor-receptor sums (kept once, [n_rec, .]), the ligand-touching first
-    layer, device-side edge counts. The mixed batch's graph and node tables come from
-    pvs_screen_slots_build (PVS_SLOTS_RAGGED; slot cap max(max_lig_atoms, 64): ceil(cap / 64) ligand-ligand words per
-    atom, one word for a screen of up to 64 atoms) in a compact layout (slot p: its ligand atoms, then the
-    receptor); no host argument of a step depends on the batch's composition, so ONE captured step (`capture`) serves every batch. Models without graphnorm always run
-    at the padded shape N_cap = batch_size * (max_lig_atoms + n_rec) (padding nodes have no edges and belong to no
-    graph), eager and captured alike; graphnorm normalises over the batch's nodes, so such models run eager at the
-    exact node count - unless `padded_graphnorm=True` (opt-in, default False): they then run at N_cap like every other
-    model, eager and captured, with GraphNorm's statistics over the node_ptr[batch_size] real rows in front of the
+    A screen runs ONE of three steps, chosen once at construction (`library_steps.library_route`, kept in `self.route`;
+    each step's docstring in library_steps.py says what it builds and launches): `reuse`, the first-layer reuse, for
+    hidden size 32 / 64 without edge_residual and without softmax attention; `plain`, the model's own forward on the
+    same mixed batch, for every other model; `cropped` under crop_radius. The two builder steps run at the padded shape
+    N_cap = batch_size * (max_lig_atoms + n_rec) (padding nodes have no edges and belong to no graph), and no host
+    argument of theirs depends on the batch's composition, so ONE captured step (`capture`) serves every batch;
+    `self.reuse` says whether the screen has such a step. fp32 only. tasks: as for ReceptorScreen (every route).
+
+    padded_graphnorm (opt-in, default False; modifies reuse, required by cropped): GraphNorm normalises over the batch's
+    nodes, so such a model runs the reuse step eager at the exact node count; with the keyword it runs at N_cap like
+    every other model, eager and captured, with the statistics over the node_ptr[batch_size] real rows in front of the
     padding, a count the layers read on the device (PvsGraph.n_norm_rows_dev). The copies of one batch still normalise
-    each other, as in every batched route. The keyword changes nothing for a model without graphnorm, nor for the
-    plain route below. Models the first-layer reuse does not cover (edge_residual, softmax attention, hidden size not
-    32 / 64) take the plain forward on the same mixed batch. fp32 only. tasks: as for ReceptorScreen.
-    softmax_reuse (opt-in, default False): as for ReceptorScreen - a first layer with edge attention under
-    softmax_attention takes the reuse, and with it capture(), struck slots and contact_attention; the builder then expands
-    base rows of H + 4 floats (PvsRaggedNodeTables.hidden is a free row width), and contact_attention=1 reduces attention
-    values normalised over ALL edges of a row, the reference's att_val.
+    each other, as in every batched route. Changes nothing for a model without graphnorm, nor for the plain route.
 
-    cam: None, True or a column (`resolve_cam`): the class-activation map of every step - the heads the screen
-    evaluates, applied to every node's final embedding (PF.node_heads) and gathered per slot (PF.slot_node_values),
-    inside the captured step - in the static buffers `screen.cam`: node_y [N_cap, C] (the heads' raw outputs per node),
-    lig_val [batch_size * max_lig_atoms] (packed atom order of the loaded batch) and slot_rec_val [batch_size, n_rec]
-    (NaN for an empty slot) of the LAST step, and rec_sum / rec_count / rec_max [n_rec], accumulated over every step
-    since reset_cam(). Needs no attention layer and no first-layer reuse: the plain route runs it eagerly.
+    softmax_reuse (opt-in, default False; selects reuse): as for ReceptorScreen - a first layer with edge attention
+    under softmax_attention takes the reuse, and with it capture(), struck slots and contact_attention.
 
-    contact_attention: None, or a layer index into model.layers as the reference's attribution `--layer` (1: the first
-    EGNN layer; negative: from the end) whose edge attention every step reduces on the device (PF.contact_attention,
-    inside the captured step) into the static buffers `screen.contact`: lig_att [batch_size * max_lig_atoms] (packed
-    atom order of the loaded batch) and slot_rec_att [batch_size, n_rec] - the largest attention over each atom's
-    ligand-receptor edges, NaN without one - of the LAST step, and rec_sum / rec_count / rec_max [n_rec], accumulated
-    over every step since reset_contact_attention(). Needs the first-layer reuse.
+    cam (every route): None, True or a column (`resolve_cam`): the class-activation map of every step - the heads the
+    screen evaluates, applied to every node's final embedding (PF.node_heads) and gathered per slot
+    (PF.slot_node_values), inside the captured step - in the static buffers `screen.cam`: node_y [N_cap, C] (the heads'
+    raw outputs per node), lig_val [batch_size * max_lig_atoms] (packed atom order of the loaded batch) and slot_rec_val
+    [batch_size, n_rec] (NaN for an empty slot) of the LAST step, and rec_sum / rec_count / rec_max [n_rec], accumulated
+    over every step since reset_cam(). Needs no attention layer; the plain route runs it eagerly.
 
-    struck: None, or True for a screen whose slots may lack one receptor atom each (receptor-atom and contact masking:
-    the reference's atom_masking / bond_masking remove atoms together with their edges). The screen then owns a static
-    `rec_drop [batch_size]` int32 (-1: the whole receptor; r: the slot's receptor is without atom r, so the slot has
-    n_rec - 1 receptor rows) and builds PVS_SLOTS_STRUCK slots: the rows that had r as a receptor-receptor
-    neighbour take their whole first-layer row through the ligand-touching CSR with a zero base, every other row and
-    every kernel is as without it. `load(slots, rec_drop=[...])` and `load_leave_out_pairs` fill it. Needs the
-    first-layer reuse, and goes with neither `cam` nor `contact_attention` (their reductions assume n_rec receptor rows
-    per slot). A screen without it launches exactly what it always launched.
+    contact_attention (modifies reuse; cropped under cropped_maps; NotImplementedError on plain): None, or a layer index
+    into model.layers as the reference's attribution `--layer` (1: the first EGNN layer; negative: from the end) whose
+    edge attention every step reduces on the device (PF.contact_attention, inside the captured step) into the static
+    buffers `screen.contact`: lig_att [batch_size * max_lig_atoms] (packed atom order of the loaded batch) and
+    slot_rec_att [batch_size, n_rec] - the largest attention over each atom's ligand-receptor edges, NaN without one -
+    of the LAST step, and rec_sum / rec_count / rec_max [n_rec], accumulated since reset_contact_attention().
 
-    crop_radius: None, or the radius of the training loader's crop (the reference's make_box(...,
+    struck (modifies reuse; ValueError on plain and cropped): None, or True for a screen whose slots may lack one
+    receptor atom each (receptor-atom and contact masking: the reference's atom_masking / bond_masking remove atoms
+    together with their edges). The screen then owns a static `rec_drop [batch_size]` int32 (-1: the whole receptor; r:
+    the slot's receptor is without atom r, so the slot has n_rec - 1 receptor rows), which `load(slots, rec_drop=[...])`
+    and `load_leave_out_pairs` fill. Goes with neither `cam` nor `contact_attention` (their reductions assume n_rec
+    receptor rows per slot). A screen without it launches exactly what it always launched.
+
+    crop_radius (selects cropped): None, or the radius of the training loader's crop (the reference's make_box(...,
     relative_to_ligand=True), the data-root path's `radius`; CLI default 10): every slot keeps only the receptor atoms
-    closer than it to one of the slot's ligand atoms (fp64 decision on the fp32 coordinates, strict, a coincident atom
-    is kept; an empty slot keeps nothing), in receptor order behind the ligand atoms, and the slot's graph is
-    generate_edges on that cropped complex - so a pose scores what `val()` gives the same pose, and the layers run
-    over the rows the model was trained on. The step is pvs_screen_slots_build (PVS_SLOTS_CROPPED), the embedding, then
-    EVERY EGNN layer through forward_prepared on the one full CSR (edge count on the device), pooling and heads by
-    node_ptr: the first-layer receptor sums are not used (a row at the rim of the crop has lost template neighbours). Shapes stay
-    padded to N_cap, so capture() / replay() and `tasks` work as above; `screen.keep` [batch_size, ceil(n_rec / 64)]
-    int64 holds the last step's masks (bit j % 64 of word j / 64), `screen._fast['node_ptr']` its offsets. Models as
-    captured_scoring.model_refusal accepts them (fp32, no edge_residual, 17..128 channels: NotImplementedError
-    otherwise); GraphNorm models need padded_graphnorm=True (the row count is only known on the device); struck, cam
-    and contact_attention do not go with it (their reductions assume n_rec rows per slot): ValueError - cam and
-    contact_attention unless `cropped_maps` is on. None: the screen launches exactly what it launches without the keyword.
+    closer than it to one of the slot's ligand atoms, so a pose scores what `val()` gives the same pose, and the layers
+    run over the rows the model was trained on. capture() / replay() and `tasks` work as above; `screen.keep` holds the
+    last step's masks, `screen._fast['node_ptr']` its offsets. Models as captured_scoring.model_refusal accepts them
+    (fp32, no edge_residual, 17..128 channels: NotImplementedError otherwise); GraphNorm models need
+    padded_graphnorm=True (the row count is only known on the device); struck, cam and contact_attention do not go with
+    it (their reductions assume n_rec rows per slot): ValueError - cam and contact_attention unless `cropped_maps` is on.
+    None: the screen launches exactly what it launches without the keyword.
 
-    cropped_maps (opt-in, default False; needs crop_radius, ValueError otherwise): `cam` and `contact_attention` on a
-    cropped screen - the maps of the complexes the scores are of. Behind the tail the step runs
-    PF.contact_attention_cropped / PF.slot_node_values_cropped, which find a receptor atom's row through the slot's keep
-    mask, into the same static buffers `screen.contact` / `screen.cam`, inside the captured step; an atom that a slot
-    does not keep has NaN in slot_rec_att / slot_rec_val and adds nothing to rec_count. contact_attention takes any layer
-    that has edge attention, 1 included: every layer of a cropped step runs on the one full CSR, so the values are the
-    layer's own (softmax attention: normalised over all edges of a row, nothing else needed). The models are those of a
-    cropped screen, not those of the first-layer reuse. struck stays refused. False, or True without a map: the screen
-    launches exactly what it launches without the keyword.
+    cropped_maps (opt-in, default False; modifies cropped, ValueError without crop_radius): `cam` and
+    `contact_attention` on a cropped screen - the maps of the complexes the scores are of, into the same static buffers,
+    inside the captured step. contact_attention takes any layer that has edge attention, 1 included. The models are
+    those of a cropped screen, not those of the first-layer reuse. struck stays refused. False, or True without a map:
+    the screen launches exactly what it launches without the keyword.
 
-    crop_parents (opt-in, default False; needs crop_radius): the slots may be leave-out COPIES of hits on the hits'
-    cropped complexes - the reference's atom_masking / bond_masking get the loader's complex, cropped around the WHOLE
-    ligand, and strike atoms out of that one, so a copy must not be cropped again around what is left of it. The screen
-    then owns three more static tables - `crop_pos [batch_size * max_lig_atoms, 3]` / `crop_ptr [batch_size + 1]`: the
-    atoms every slot is cropped AROUND, and `rec_drop [batch_size]`: -1 or the receptor atom the slot lacks whatever the
-    crop says - and its step builds with pvs_screen_copies_build; everything behind the builder is the cropped step
-    above. A plain load (`screen(slots)`, `load_packed`) crops every slot around its own atoms - the ligand table is
-    copied into the crop table on the device, rec_drop is -1 - and gives the bits of a screen without the keyword.
-    `load_leave_out` and `load_leave_out_pairs` work on such a screen: the existing packer launch plus one
-    PF.leave_out_parent_pack launch that lays the copies' parents into the crop table, both outside the captured step;
-    the pair packer writes this screen's rec_drop. Under GraphNorm the copies of one batch normalise each other, as in
-    every batched route. False: the screen launches exactly what it launches without the keyword."""
+    crop_parents (opt-in, default False; modifies cropped, ValueError without crop_radius): the slots may be leave-out
+    COPIES of hits on the hits' cropped complexes - the reference's atom_masking / bond_masking get the loader's
+    complex, cropped around the WHOLE ligand, and strike atoms out of that one, so a copy must not be cropped again
+    around what is left of it. The screen then owns three more static tables - `crop_pos [batch_size * max_lig_atoms,
+    3]` / `crop_ptr [batch_size + 1]`: the atoms every slot is cropped AROUND, and `rec_drop [batch_size]`: -1 or the
+    receptor atom the slot lacks whatever the crop says. A plain load (`screen(slots)`, `load_packed`) crops every slot
+    around its own atoms - the ligand table is copied into the crop table on the device, rec_drop is -1 - and gives the
+    bits of a screen without the keyword. `load_leave_out` and `load_leave_out_pairs` work on such a screen: the
+    existing packer launch plus one PF.leave_out_parent_pack launch that lays the copies' parents into the crop table,
+    both outside the captured step; the pair packer writes this screen's rec_drop. False: the screen launches exactly
+    what it launches without the keyword."""
 
     def __init__(self, model, rec_pos, rec_feats, batch_size, max_lig_atoms, edge_radius, intra_radius=None,
                  tasks=None, contact_attention=None, cam=None, struck=None, padded_graphnorm=False,
@@ -672,26 +624,22 @@ class LibraryScreen(_ReceptorSideScreen):
         if not 1 <= int(max_lig_atoms) <= MAX_SCREEN_LIGAND_ATOMS:
             raise ValueError(f'max_lig_atoms must be 1..{MAX_SCREEN_LIGAND_ATOMS} (got {max_lig_atoms})')
         _lib.require_hip(rec_pos)
-        # (`reuse`: the screen runs its own fixed-shape step and not the plain forward - for a cropped screen every model
-        # that _check_crop let through)
-        self.reuse = (self.crop_radius is not None
-                      or (self._first_layer_reusable() and not any(l.edge_residual for l in self.egnn)))
         self.graphnorm = any(getattr(l, 'graphnorm', False) for l in self.egnn)
         if self.crop_radius is not None and self.graphnorm and not self.padded_graphnorm:
             raise ValueError('LibraryScreen(crop_radius=...): a GraphNorm model needs padded_graphnorm=True - the row '
                              'count of a cropped batch is only known on the device, where the layers then read it')
-        # a graphnorm model at the padded shape: the statistics over the node_ptr[batch_size] real rows, read on the device
-        self._gn_padded = self.padded_graphnorm and self.graphnorm and self.reuse
         dev = rec_pos.device
         self.b, self.max_lig_atoms = int(batch_size), int(max_lig_atoms)
         self.slot_cap = max(self.max_lig_atoms, 64)      # what the builder validates lig_ptr against
         self.n_rec = int(rec_pos.shape[0])
-        if self.struck and not self.reuse:
-            raise ValueError(
-                'LibraryScreen(struck=True): struck slots are built for the step of the first-layer reuse, which this '
-                'model does not have (softmax attention without softmax_reuse=True, edge_residual or a hidden size other '
-                'than 32 / 64); mask it '
-                'one complex at a time with pointvs_amd.attribution.bond_masking / atom_masking')
+        self._contact_request = contact_attention
+        self.contact_attention = resolve_attention_layer(model, contact_attention)       # (index into model.layers)
+        # the route is chosen here, once; its step says what it refuses (plain: struck slots, contact_attention)
+        self.route = model_route(model, self.softmax_reuse, self.crop_radius)
+        self._step = STEPS[self.route](self)
+        self.reuse = self._step.has_builder         # the screen runs its own fixed-shape step, not the plain forward
+        # a graphnorm model at the padded shape: the statistics over the node_ptr[batch_size] real rows, read on the device
+        self._gn_padded = self.padded_graphnorm and self.graphnorm and self._step.has_builder
         self.l_cap = self.b * self.max_lig_atoms
         self.n_cap = self.l_cap + self.b * self.n_rec
         self._rec_pos = rec_pos.float().contiguous()
@@ -714,19 +662,12 @@ class LibraryScreen(_ReceptorSideScreen):
             self.crop_pos = torch.zeros((self.l_cap, 3), dtype=torch.float32, device=dev)
             self.crop_ptr = torch.zeros(self.b + 1, dtype=torch.int32, device=dev)
         self._n_struck = 0           # host copy: how many slots of the loaded batch lack a receptor atom
-        self.contact_attention = resolve_attention_layer(model, contact_attention)       # (index into model.layers)
         self.contact = None
         if self.contact_attention is not None:
-            if not self.reuse:
-                raise NotImplementedError(
-                    f'LibraryScreen(contact_attention={contact_attention}): the contact-attention reduction runs in '
-                    'the step of the first-layer reuse, which this model does not have (softmax attention without '
-                    'softmax_reuse=True, edge_residual or a hidden size other than 32 / 64 take the plain forward)')
             self.contact = self._value_buffers('lig_att', 'slot_rec_att')
         if self._cam_plan is not None:
             self.cam = self._value_buffers('lig_val', 'slot_rec_val', node_width=sum(self._cam_plan[1]))
-        if self.reuse:
-            self._cache_receptor_sums()
+        self._cache_receptor_sums()
 
     def _check_crop(self, model, contact_attention, cam):
         """What a cropped screen refuses, before anything is allocated."""
@@ -745,9 +686,7 @@ class LibraryScreen(_ReceptorSideScreen):
     @property
     def keep(self):
         """The keep masks of the last step of a cropped screen, [batch_size, ceil(n_rec / 64)] int64 on the device."""
-        if self.crop_radius is None or self._fast is None:
-            raise RuntimeError('keep: the masks of a cropped screen (crop_radius=...) after its first step')
-        return self._fast['keep']
+        return self._step.keep()
 
     def _value_buffers(self, lig_key, slot_key, node_width=None):
         """The static buffers of `contact` / `cam`: the three accumulators, with node_width node_y [N_cap, node_width],
@@ -771,57 +710,14 @@ class LibraryScreen(_ReceptorSideScreen):
         """The accumulators of `cam` as before the first step: sums and counts zero, maxima NaN (none so far)."""
         self._reset_values(self.cam, 'reset_cam', 'cam')
 
-    def _reduce_cam(self, h, node_ptr, lig_ptr, keep=None):
-        """The heads on every row of the final embedding h [n, H] into cam['node_y'][:n] - one launch (PF.node_heads)
-        when every head is one that PF.pool_heads takes, else each head per node on the linear op - then the slots'
-        values and the accumulators (PF.slot_node_values; keep: the masks of a cropped batch,
-        PF.slot_node_values_cropped)."""
-        heads, widths, column, n_mean = self._cam_plan
-        c, n = self.cam, h.shape[0]
-        node_y = c['node_y'][:n]
-        fused = [self.model._fused_head(head) for head in heads]
-        if all(f is not None for f in fused) and len(fused) <= PF.MAX_POOL_HEADS and h.shape[1] <= PF.POOL_HEAD_MAX_WIDTH:
-            PF.node_heads(h, fused, out=node_y)
-        else:
-            at = 0
-            for head, width in zip(heads, widths):
-                node_y[:, at:at + width].copy_(self.model._run_head(head, h).reshape(n, width))
-                at += width
-        out = (c['lig_val'], c['slot_rec_val'], c['rec_sum'], c['rec_count'], c['rec_max'])
-        if keep is not None:
-            PF.slot_node_values_cropped(node_y, node_ptr, lig_ptr, keep, self.n_rec, column, n_mean, out=out)
-            return
-        PF.slot_node_values(node_y, node_ptr, lig_ptr, self.n_rec, column, n_mean, out=out)
-
     def reset_contact_attention(self):
         """The accumulators of `contact` as before the first step: sums and counts zero, maxima NaN (none so far)."""
         self._reset_values(self.contact, 'reset_contact_attention', 'contact_attention')
 
-    def _reduce_contacts(self, f, tag, att):
-        """PF.contact_attention over f's CSR `tag` ('_l': ligand-touching, '': full) with `att` in its edge order."""
-        c = self.contact
-        PF.contact_attention(f['rowptr' + tag], f['etype' + tag], att, f['node_ptr'], self.lig_ptr, self.n_rec,
-                             out=(c['lig_att'], c['slot_rec_att'], c['rec_sum'], c['rec_count'], c['rec_max']))
-
-    def _reduce_cropped_maps(self, f):
-        """The maps of a cropped step (cropped_maps=True), behind its tail: the attention that the layer's
-        forward_prepared left in the full CSR's order and / or the heads per node, each receptor atom found through the
-        slot's keep mask (PF.contact_attention_cropped, PF.slot_node_values_cropped)."""
-        if self.contact_attention is not None:
-            c = self.contact
-            PF.contact_attention_cropped(
-                f['rowptr'], f['etype'], self.model.layers[self.contact_attention]._att_sorted, f['node_ptr'],
-                self.lig_ptr, f['keep'], self.n_rec,
-                out=(c['lig_att'], c['slot_rec_att'], c['rec_sum'], c['rec_count'], c['rec_max']))
-        if self.cam is not None:
-            self._reduce_cam(self._h_final, f['node_ptr'], self.lig_ptr, f['keep'])
-
     def _cache_receptor_sums(self):
-        """The receptor sums kept once, [n_rec, .]; every builder launch reads them (and the template) anew (`_job`)."""
-        if self.crop_radius is not None:      # (a cropped step keeps the template and no sums)
-            self._receptor_template(self._rec_pos)
-            return
-        self.rec_magg, self.rec_xsum, self.rec_deg = self._receptor_sums(self._rec_feats, self._rec_pos)
+        """What the step keeps of the receptor, once: the first-layer sums and the template (reuse), the template alone
+        (cropped), nothing (plain)."""
+        self._step.cache_receptor()
 
     # ---- inputs ----
     def _checked_sizes(self, sizes):
@@ -957,104 +853,21 @@ class LibraryScreen(_ReceptorSideScreen):
                                 if self.struck or self.crop_parents else ''))
 
     # ---- the graph and the node tables ----
-    def _buffers(self, cap, cap_l, feats=False, base=False, keep=False, att_l=False, pgs=False, pg=False):
-        """The builder's buffers over N_cap nodes: the full CSR with room for cap edges, node_ptr, node_graph, pos, and
-        what the use names - cap_l (not None): the ligand-touching CSR with room for cap_l edges; feats: the feature
-        rows x; base: the first-layer base rows; keep: the masks of cropped slots (and the state of that layout); att_l:
-        the first layer's attention in the ligand-touching CSR's order; pgs: the graph pairs of `_graphs`, by node
-        count; pg: the PreparedGraph of the full CSR over N_cap nodes."""
-        dev, n_cap = self.lig_pos.device, self.n_cap
-        i32 = dict(dtype=torch.int32, device=dev)
-        f32 = dict(dtype=torch.float32, device=dev)
-        counts = _lib.PvsScreenSlotsJob(layout=self._layout(keep), n_slots=self.b, lig_cap=self.l_cap, n_rec=self.n_rec,
-                                        slot_cap=self.slot_cap)
-        own = dict(
-            state=torch.empty(_lib.lib().pvs_screen_slots_state_bytes(C.byref(counts)), dtype=torch.uint8, device=dev),
-            node_ptr=torch.zeros(self.b + 1, **i32), node_graph=torch.empty(n_cap, **i32),
-            pos=torch.empty((n_cap, 3), **f32))
-        if feats:
-            own['x'] = torch.empty((n_cap, self.lig_feats.shape[1]), **f32)
-        if base:        # (a base row's width: the hidden size + the reuse kind's row_extra)
-            own.update(base_magg=torch.empty((n_cap, self.rec_magg.shape[1]), **f32),
-                       base_xsum=torch.empty((n_cap, 3), **f32), base_deg=torch.empty(n_cap, **f32))
-        if keep:
-            own['keep'] = torch.zeros((self.b, (self.n_rec + 63) // 64), dtype=torch.int64, device=dev)
-        f = _csr_buffers(dev, n_cap, cap_l, cap, **own)
-        if att_l:
-            f['att_l'] = torch.empty(max(cap_l, 1), **f32)
-        if pgs:
-            f['pgs'] = {}
-        if pg:
-            from .graph import PreparedGraph
-            csr = {k: f[k] for k in ('rowptr', 'row', 'col', 'etype', 'inv_deg', 'status')}
-            f['pg'] = PreparedGraph.over_buffers(n_cap, cap, csr, f['rowptr'][n_cap:])
-            if self.graphnorm:
-                f['pg'].set_norm_rows(f['node_ptr'][self.b:])
-        return f
-
-    def _step_buffers(self, cap, cap_l):
-        """The buffers of the screen's step. Cropped: the full CSR alone, the feature rows, the keep masks; else both
-        CSRs, feature and base rows and, for contact_attention=1, the first EGNN layer's attention."""
-        if self.crop_radius is not None:
-            return self._buffers(cap, None, feats=True, keep=True, pg=True)
-        return self._buffers(cap, cap_l, feats=True, base=True, att_l=self.contact_attention == 1, pgs=True)
-
-    def _layout(self, cropped):
-        return _lib.SLOTS_CROPPED if cropped else _lib.SLOTS_STRUCK if self.struck else _lib.SLOTS_RAGGED
-
     def _job(self, f, probe=False):
-        """The PvsScreenSlotsJob of the loaded batch into f, filled at every launch from the screen's attributes and f
-        by name: nothing keeps a device address across steps, so whatever a refresh replaces (the template, the
-        receptor sums) is simply read again. The layout is PVS_SLOTS_CROPPED where f has keep masks, PVS_SLOTS_STRUCK
-        for a struck screen, else PVS_SLOTS_RAGGED. probe: no room for edges in either CSR."""
-        p = _lib.ptr
-        cropped = 'keep' in f
-        job = _lib.PvsScreenSlotsJob(
-            layout=self._layout(cropped), lig_pos=p(self.lig_pos), lig_ptr=p(self.lig_ptr),
-            rec_drop=p(self.rec_drop) if self.struck else None,
-            rec_pos=p(self._rec_pos), rr_rowptr=p(self._rr.t['rowptr']), rr_col=p(self._rr.t['col']), n_slots=self.b,
-            lig_cap=self.l_cap, n_rec=self.n_rec, slot_cap=self.slot_cap, inter_radius=float(self.r_inter),
-            intra_radius=float(self.r_intra), crop_radius=self.crop_radius if cropped else 0.0,
-            inv_deg=p(f['inv_deg']), node_ptr=p(f['node_ptr']), node_graph=p(f['node_graph']), pos=p(f['pos']),
-            keep=p(f.get('keep')), status=p(f['status']))
-        full = job.full
-        full.rowptr, full.row, full.col, full.etype = p(f['rowptr']), p(f['row']), p(f['col']), p(f['etype'])
-        full.capacity = 0 if probe else f['cap']
-        if f['cap_l'] is not None:
-            lig = job.lig
-            lig.rowptr, lig.row, lig.col, lig.etype = p(f['rowptr_l']), p(f['row_l']), p(f['col_l']), p(f['etype_l'])
-            lig.capacity = 0 if probe else f['cap_l']
-        t = job.tables
-        if 'x' in f:
-            t.n_feats, t.feats = f['x'].shape[1], p(f['x'])
-            t.lig_feats, t.rec_feats = p(self.lig_feats), p(self._rec_feats)
-        if 'base_magg' in f:
-            t.hidden, t.rec_magg, t.rec_xsum, t.rec_deg = (f['base_magg'].shape[1], p(self.rec_magg), p(self.rec_xsum),
-                                                           p(self.rec_deg))
-            t.base_magg, t.base_xsum, t.base_deg = p(f['base_magg']), p(f['base_xsum']), p(f['base_deg'])
-        return job
+        """The step's PvsScreenSlotsJob of the loaded batch into f (probe: into its probe's buffers, no room for edges)."""
+        return self._step.job(f, probe)
 
     def _launch_builder(self, f, probe=False):
-        """pvs_screen_slots_build of the loaded batch into f - pvs_screen_copies_build for the cropped step of a
-        crop_parents screen (its probe is the uncropped builder's, like every cropped screen's)."""
-        job = self._job(f, probe)
-        if self.crop_parents and 'keep' in f:
-            p = _lib.ptr
-            PF.screen_copies_build(_lib.PvsScreenCopiesJob(slots=job, crop_pos=p(self.crop_pos), crop_ptr=p(self.crop_ptr),
-                                                           rec_drop=p(self.rec_drop), crop_cap=self.l_cap), f['state'])
-            return
-        _lib.check(_lib.lib().pvs_screen_slots_build(C.byref(job), _lib.ptr(f['state']), f['state'].numel(),
-                                                     _stream(self.lig_pos.device)), 'pvs_screen_slots_build')
+        """The step's builder of the loaded batch into f."""
+        self._step.launch(f, probe)
 
     def _probe_capacities(self):
         """One synchronous probe: the builder with no room for edges leaves both exact edge counts in its row
         pointers. Room for the ligand-touching edges: twice the loaded batch's contacts per ligand atom at a full
         batch of L_cap atoms, at most what L_cap atoms can have (per atom: inter and intra contacts with the receptor,
         both directions, and the slot's other ligand atoms). A struck screen adds the whole rows of the receptor rows
-        that the struck atom can touch (`_struck_room`) for every slot."""
-        # (an uncropped screen probes into a set like its step's, so that the step's buffers are then allocated as they
-        # always were; a cropped one needs of the uncropped builder no more than row pointers, node_ptr and pos)
-        probe = self._buffers(1, 1) if self.crop_radius is not None else self._step_buffers(1, 1)
+        that the struck atom can touch (`_struck_room`) for every slot. The step says which buffers its probe needs."""
+        probe = self._step.probe_buffers()
         self._launch_builder(probe, probe=True)
         n_lig_edges = int(probe['rowptr_l'][self.n_cap].item())
         per_atom = -(-n_lig_edges // max(self.n_atoms, 1))
@@ -1079,25 +892,13 @@ class LibraryScreen(_ReceptorSideScreen):
         moved = torch.zeros(self.n_rec, dtype=torch.int64, device=deg.device).index_add_(0, rows, deg[col] - 1)
         return int(moved.max().item())
 
-    def _graphs(self, n):
-        """(PreparedGraph of the full CSR, PvsGraph of the ligand-touching CSR) over the first n nodes (the nodes
-        after n are padding, without edges: rowptr[n] == rowptr[N_cap] == the edge count)."""
-        pgs = self._fast['pgs']
-        if n not in pgs:
-            pgs[n] = _graph_pair(self._fast, n, self.n_cap)
-            if self._gn_padded:      # both graphs: the partial first layer's and the full one of the layers behind it
-                real_nodes = self._fast['node_ptr'][self.b:]
-                pgs[n][0].set_norm_rows(real_nodes)
-                pgs[n][1].n_norm_rows_dev = real_nodes.data_ptr()
-        return pgs[n]
-
     def _build(self, capacities=None):
-        """The loaded batch's graph and node tables (pvs_screen_slots_build). capacities: (full, ligand-
-        touching) edge room instead of the probe's."""
+        """The loaded batch's graph and node tables, into the step's buffers by the step's builder. capacities: (full,
+        ligand-touching) edge room instead of the probe's."""
         capturing = torch.cuda.is_current_stream_capturing()
         if self._fast is None:
             cap, cap_l = capacities or self._probe_capacities()
-            self._fast = self._step_buffers(cap, cap_l)
+            self._fast = self._step.buffers(cap, cap_l)
         f = self._fast
         if not capturing:
             self.check()
@@ -1118,26 +919,8 @@ class LibraryScreen(_ReceptorSideScreen):
 
     # ---- the step ----
     def _plain_forward(self):
-        """The models the first-layer reuse does not cover: the same mixed batch, graph from the general builder."""
-        from .graph import Batch
-        from .radius_graph import attach_radius_graph
-        dev = self.lig_pos.device
-        pos, x, counts, at = [], [], [], 0
-        for n in self._sizes:
-            pos += [self.lig_pos[at:at + n], self._rec_pos]
-            x += [self.lig_feats[at:at + n], self._rec_feats]
-            counts.append(n + self.n_rec)
-            at += n
-        ptr = torch.tensor([0] + counts, dtype=torch.int64).cumsum(0)
-        batch = Batch(x=torch.cat(x, 0), pos=torch.cat(pos, 0), edge_index=None, edge_attr=None,
-                      batch=torch.arange(self.b, device=dev).repeat_interleave(torch.tensor(counts, device=dev)),
-                      ptr=ptr, y=torch.zeros(self.b, device=dev), lig_fname=['pose'] * self.b,
-                      rec_fname=['receptor'] * self.b, num_graphs=self.b, graph_node_counts=counts)
-        y = self._plain(attach_radius_graph(batch, self.r_inter, self.r_intra))
-        if self.cam is not None:      # (eager: the offsets come from the host-known sizes)
-            lig_ptr = torch.tensor([0] + list(self._sizes), dtype=torch.int64).cumsum(0).to(device=dev, dtype=torch.int32)
-            self._reduce_cam(self._h_final.contiguous(), self._plain_ptr, lig_ptr)
-        return y
+        """The plain route's step on the loaded batch (it needs no buffers, so a screen of any route can run it)."""
+        return _PlainStep.run(self._step)
 
     def _head(self, h):
         return self.model._pool_and_head_padded(self.model.feats_linear_layers, h, self._fast['node_ptr'], self.b)
@@ -1149,43 +932,23 @@ class LibraryScreen(_ReceptorSideScreen):
     def __call__(self, slots=None):
         if slots is not None:
             self.load(slots)
-        if not self.reuse:
-            return self._plain_forward()
-        self._refresh_if_stale()
-        f = self._build()
-        if self.crop_radius is not None:      # every layer on the one full CSR of the cropped batch, padded shape
-            x = f['pos']
-            y = self._tail(f['pg'], self.embed.embed(f['x'], x).contiguous(), x, layers=self.egnn)
-            if self.contact is not None or self.cam is not None:
-                self._reduce_cropped_maps(f)
-            return y
-        # graphnorm's statistics run over the batch's nodes: no padding rows there (the host knows the count) - or, with
-        # padded_graphnorm, the padded shape and the count where the builder left it (PvsGraph.n_norm_rows_dev)
-        exact = self.graphnorm and not self._gn_padded
-        n = self.n_atoms + self.b * self.n_rec - self._n_struck if exact else self.n_cap
-        pg_full, g_lig = self._graphs(n)
-        x = f['pos'][:n]
-        h = self.embed.embed(f['x'][:n], x).contiguous()
-        h, x = self._partial_first_layer(g_lig, h, x, f['base_magg'], f['base_xsum'], f['base_deg'],
-                                         self.n_cap, f['cap_l'], f.get('att_l'))
-        y = self._tail(pg_full, h, x)
-        if self.contact_attention == 1:
-            self._reduce_contacts(f, '_l', f['att_l'])
-        elif self.contact_attention is not None:      # (a later layer: what its forward_prepared left, full CSR order)
-            self._reduce_contacts(f, '', self.model.layers[self.contact_attention]._att_sorted)
-        if self.cam is not None:
-            self._reduce_cam(self._h_final, f['node_ptr'], self.lig_ptr)
-        return y
+        return self._step.run()
+
+    def needs_sizing_batch(self):
+        """True while the step's edge buffers are still to be sized, from the first batch the screen is shown (the plain
+        route has none)."""
+        return self._step.has_builder and self._fast is None
+
+    def capture_refusal(self):
+        """Why capture() would refuse (the step's reason), or None."""
+        return self._step.capture_refusal()
 
     def capture(self, example_slots=None):
         """Captures one whole step (builder + layer stack + head) in a hipGraph; `replay(slots)` then serves every
         batch of a library, whatever its composition."""
-        if not self.reuse:
-            raise RuntimeError('capture needs the first-layer reuse (no edge_residual, no softmax attention - or '
-                               'softmax_reuse=True -, hidden size 32 or 64)')
-        if self.graphnorm and not self._gn_padded:
-            raise RuntimeError('a graphnorm model normalises over the batch\'s nodes and runs at the exact node '
-                               'count: it cannot be captured at the padded shape; call the screen eagerly')
+        why = self.capture_refusal()
+        if why is not None:
+            raise RuntimeError(why)
         if example_slots is not None:
             self.load(example_slots)
         return self._capture(lambda: self(), self.lig_pos.device)
@@ -1209,7 +972,7 @@ class _SweepSink:
         else:
             has_pose = tasks != 'affinity'
             self.sig_cols = 1 if has_pose and (sigmoid is None or sigmoid) else 0
-        self.receptor = sweep.receptor_name
+        self.sweep, self.receptor = sweep, sweep.receptor_name
         self.raw = {} if keep_raw else None
         self.writers = []          # (writer, first column, columns)
         if predictions_file:
@@ -1239,6 +1002,17 @@ class _SweepSink:
     def keep_raw(self, name, raw):
         if self.raw is not None:
             self.raw.setdefault(name, []).append(raw)
+
+    def take(self, raw, name, first_pose, keep):
+        """One batch of a ligand's poses, done: raw [batch_size, C], of which the first `keep` slots hold the poses
+        first_pose .. of ligand `name`. Scores them, keeps their raw rows, writes their predictions lines, counts the
+        batch; returns the kept slots' scores."""
+        y = self.scored(raw)[:keep]
+        self.keep_raw(name, raw[:keep])
+        if self.writers:
+            self.write(y, [f'{name}_pose{first_pose + i}' for i in range(keep)])
+        self.sweep.batches_run += 1
+        return y
 
     def close(self):
         error = None
@@ -1381,13 +1155,7 @@ class ScreeningSweep:
             ptr = slot_offsets([[n_lig] * keep], self.b)[0]
             screen.load_packed(poses[k:k + keep].to(dev).float().reshape(-1, 3), feats.repeat(keep, 1), ptr.to(dev),
                                [n_lig] * keep)
-            raw = self._library_step(screen)
-            y = sink.scored(raw)
-            scores.append(y[:keep])
-            sink.keep_raw(name, raw[:keep])
-            if sink.writers:
-                sink.write(y[:keep], [f'{name}_pose{k + i}' for i in range(keep)])
-            self.batches_run += 1
+            scores.append(sink.take(self._library_step(screen), name, k, keep))
         screen.check()
         return torch.cat(scores, 0)
 
@@ -1405,14 +1173,7 @@ class ScreeningSweep:
         for k in range(0, poses.shape[0], self.b):
             chunk = poses[k:k + self.b]
             y = screen.replay(chunk).clone() if screen._captured else screen(chunk.contiguous())
-            raw = y.reshape(self.b, -1)
-            y = sink.scored(raw)
-            keep = min(self.b, n_poses - k)
-            scores.append(y[:keep])
-            sink.keep_raw(name, raw[:keep])
-            if sink.writers:
-                sink.write(y[:keep], [f'{name}_pose{k + i}' for i in range(keep)])
-            self.batches_run += 1
+            scores.append(sink.take(y.reshape(self.b, -1), name, k, min(self.b, n_poses - k)))
         screen.check()
         return torch.cat(scores, 0)
 
@@ -1491,7 +1252,7 @@ class ScreeningSweep:
 
     def _capture_if_wanted(self, screen):
         """Captures the step of `screen` on the batch loaded into it, where a captured step can be had."""
-        if self.capture and screen.reuse and (not screen.graphnorm or screen._gn_padded) and not screen._captured:
+        if self.capture and not screen._captured and screen.capture_refusal() is None:
             screen.capture()
 
     def _library_step(self, screen):

@@ -9,10 +9,12 @@ PVS_EGNN_SPLIT_SMALL=1 and PVS_EGNN_SPLIT_WGRADS=1 (profiles/layer_backward_plan
     python tools/launch_sequence.py --parse DIR OUT.txt      # one line per launch: name, grid, workgroup, LDS
 Two libraries enqueue the same work when their OUT.txt files are equal (profiles/linear_job_refactor.txt).
 `--screening` traces instead one eager step of each screen (ReceptorScreen on the pose-batch builder and on the filter
-path, LibraryScreen plain, with struck slots, with contact attention, with cam and cropped) at a small shape (130-atom receptor,
-batch of 3) and one eager FixedShapeScorer step on two complexes of the cli_default golden root: the record that a
+path, LibraryScreen on the reuse route alone, with struck slots, with contact attention and with cam, cropped, on the
+plain route, cropped on leave-out copies and cropped with either map) at a small shape (130-atom receptor, batch of 3)
+and one eager FixedShapeScorer step on two complexes of the cli_default golden root: the record that a
 change of the screens' host code left every launch alone (profiles/screening_refactor.txt,
-profiles/hit_attribution_refactor.txt, profiles/nowait_refactor.txt, profiles/slot_builder_job.txt). `--fp64` runs the loop of the default mode with model
+profiles/hit_attribution_refactor.txt, profiles/nowait_refactor.txt, profiles/slot_builder_job.txt,
+profiles/library_steps_refactor.txt). `--fp64` runs the loop of the default mode with model
 and batch in double (hidden 16 / 32 / 64, the per-layer path: there is no fp64 stack), for a change of the binding's
 fp64 side (profiles/functional_dtype_refactor.txt)."""
 import csv
@@ -98,6 +100,27 @@ def run_screening():
     # ... and the cropped step: its own builder layout, every layer on the one full CSR
     for m, extra in ((attending, dict(contact_attention=1)), (model, dict(cam=True)), (model, dict(crop_radius=6.0))):
         screen = LibraryScreen(m, rec, rec_feats, 3, 20, 7.0, **extra)
+        screen(slots)
+        screen.check()
+    # the routes and variants not traced above: the plain route (hidden 16), a crop_parents screen on leave-one-atom-out
+    # copies of the three slots, and the masked map reductions of a cropped screen
+    torch.manual_seed(5)
+    narrow = SartorrasEGNN(tempfile.mkdtemp(), 2e-3, 1e-4, silent=True, **dict(kw, k=16)).eval()
+    screen = LibraryScreen(narrow, rec, rec_feats, 3, 20, 7.0)
+    screen(slots)
+    screen.check()
+    from pointvs_amd.screening import leave_out_plan
+    sizes = [int(pose.shape[0]) for _, pose in slots]
+    packed_pos = torch.cat([pose for _, pose in slots], 0).cuda()
+    packed_feats = torch.cat([f for f, _ in slots], 0).cuda().float()
+    packed_ptr = torch.tensor([0] + sizes).cumsum(0).to(device='cuda', dtype=torch.int32)
+    screen = LibraryScreen(model, rec, rec_feats, 3, 20, 7.0, crop_radius=6.0, crop_parents=True)
+    screen.load_leave_out(packed_pos, packed_feats, packed_ptr, leave_out_plan(sizes, 3)[0],
+                          torch.zeros(1, dtype=torch.int32, device='cuda'))()
+    screen.check()
+    screen.check_leave_out()
+    for m, extra in ((attending, dict(contact_attention=1)), (model, dict(cam=True))):
+        screen = LibraryScreen(m, rec, rec_feats, 3, 20, 7.0, crop_radius=6.0, cropped_maps=True, **extra)
         screen(slots)
         screen.check()
     # the data-root scorer: one eager fixed-shape step on two complexes of the cli_default golden root
