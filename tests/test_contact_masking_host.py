@@ -97,7 +97,7 @@ int main(int argc, char** argv) {
     printf("ok %d\n", ok);
     if (!ok) return 0;
     const long long total = (long long)ptr[S] + S;
-    for (long long c = -1; c <= total + 1; ++c) {
+    for (long long c = -2; c <= total + 2; ++c) {
         const PvsPairCopy v = pvs_pair_copy(ptr.data(), S, c);
         printf("c %lld %d %d\n", c, v.hit, v.pair);
     }
@@ -110,21 +110,58 @@ int main(int argc, char** argv) {
 '''
 
 
-@pytest.fixture(scope='module')
-def probe(tmp_path_factory):
+# The same for the ligand-atom copies. argv: slot_cap n_rows lig_ptr[...]. Prints the verdict on the table and every copy
+# ("c <copy> <first> <n> <skip>"), two on either side of them included.
+LIGAND_PROGRAM = r'''
+#include "leave_out.h"
+#include <stdio.h>
+#include <stdlib.h>
+#include <vector>
+int main(int argc, char** argv) {
+    const int slot_cap = atoi(argv[1]), n_rows = atoi(argv[2]);
+    std::vector<int32_t> ptr;
+    for (int i = 3; i < argc; ++i) ptr.push_back(atoi(argv[i]));
+    const int S = (int)ptr.size() - 1;
+    int ok = 1;
+    for (int t = 0; t <= S; ++t) ok &= pvs_leave_out_table_ok(ptr.data(), S, t, slot_cap, n_rows) ? 1 : 0;
+    printf("ok %d\n", ok);
+    if (!ok) return 0;
+    const long long total = (long long)ptr[S] + S;
+    for (long long c = -2; c <= total + 2; ++c) {
+        const PvsLeaveOutCopy v = pvs_leave_out_copy(ptr.data(), S, c);
+        printf("c %lld %d %d %d\n", c, v.first, v.n, v.skip);
+    }
+    return 0;
+}
+'''
+
+
+def _compiled(tmp_path_factory, name, program):
     assert CXX is not None, 'the copy enumeration is checked with the host C++ compiler; none found'
-    d = tmp_path_factory.mktemp('pair_copies')
-    (d / 'main.cpp').write_text(PROGRAM)
-    exe = d / 'pair_copy_probe'
+    d = tmp_path_factory.mktemp(name)
+    (d / 'main.cpp').write_text(program)
+    exe = d / f'{name}_probe'
     out = subprocess.run([CXX, '-std=c++17', '-O1', '-Wall', '-Werror', '-I', str(CSRC), str(d / 'main.cpp'), '-o', str(exe)],
                          capture_output=True, text=True)
     assert out.returncode == 0, out.stderr[-2000:]
 
-    def run(n_pairs, ptr):
-        res = subprocess.run([str(exe), str(n_pairs)] + [str(p) for p in ptr], capture_output=True, text=True)
+    def run(*args):
+        res = subprocess.run([str(exe)] + [str(a) for a in args], capture_output=True, text=True)
         assert res.returncode == 0, res.stderr
         return res.stdout.splitlines()
     return run
+
+
+@pytest.fixture(scope='module')
+def probe(tmp_path_factory):
+    run = _compiled(tmp_path_factory, 'pair_copy', PROGRAM)
+    return lambda n_pairs, ptr: run(n_pairs, *ptr)
+
+
+@pytest.fixture(scope='module')
+def ligand_probe(tmp_path_factory):
+    run = _compiled(tmp_path_factory, 'ligand_copy', LIGAND_PROGRAM)
+    return lambda slot_cap, n_rows, ptr: run(slot_cap, n_rows, *ptr)
 
 
 def _ptr(counts):
@@ -157,3 +194,29 @@ def test_pair_table_verdicts(probe):
     assert probe(9, [0, 5, 3, 9])[0] == 'ok 0'                  # descending
     assert probe(9, [1, 5, 9])[0] == 'ok 0'                     # does not start at 0
     assert probe(0, [0])[0] == 'ok 1' and probe(0, [0, 0])[0] == 'ok 1'
+
+
+@pytest.mark.parametrize('n_hits', [257, 513])
+def test_both_enumerations_over_257_and_513_hits(probe, ligand_probe, n_hits):
+    """The tables the packer tests of tests/test_gpu_many_slots.py use - empty hits at both ends, at 255 / 256 and every
+    50th, hits without pairs - bisected over 9 and 10 levels: every copy number in [-2, total + 2] of both numberings."""
+    from tests import _many_slots_cases as mc
+    sizes = mc.hit_sizes(n_hits)
+    counts = [len(hit) for hit in mc.hit_pairs(sizes, mc.N_REC)]
+    assert sizes[0] == sizes[255] == sizes[256] == sizes[-1] == sizes[100] == 0 and counts[0] == counts[-1] == 0
+    cases = [(probe(sum(counts), _ptr(counts)), counts,
+              [(s, -1 if j == 0 else _ptr(counts)[s] + j - 1) for s, k in enumerate(counts) for j in range(k + 1)], (-1, -1)),
+             (ligand_probe(9, sum(sizes), _ptr(sizes)), sizes,
+              [(_ptr(sizes)[s], n, -1) if j == 0 else (_ptr(sizes)[s], n - 1, j - 1)
+               for s, n in enumerate(sizes) for j in range(n + 1)], (0, 0, -1))]
+    for lines, table, want, nothing in cases:
+        assert lines[0] == 'ok 1'
+        got = {int(f[1]): tuple(map(int, f[2:])) for f in (line.split() for line in lines) if f[0] == 'c'}
+        total = sum(table) + n_hits
+        assert len(want) == total and sorted(got) == list(range(-2, total + 3))
+        for c in range(-2, total + 3):
+            assert got[c] == (want[c] if 0 <= c < total else nothing), (c, got[c])
+    assert ligand_probe(8, sum(sizes), _ptr(sizes))[0] == 'ok 0'            # (the 9-atom hit is wider than 8)
+    late = _ptr(sizes)
+    late[n_hits - 2] = late[n_hits - 3] - 1                                 # one descending pair, two entries from the end
+    assert ligand_probe(9, sum(sizes), late)[0] == 'ok 0'

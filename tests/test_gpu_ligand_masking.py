@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import _many_slots_cases as mc
 from tests._attribution_ref import AttrCase
 from tests._golden import needs_caching_allocator
 
@@ -29,37 +30,16 @@ F, N_SLOTS, SLOT_CAP, SENTINEL = 12, 7, 130, -7.0
 # ---------------------------------------------------------------- the packer
 
 def _ligands(sizes, n_feats=F):
-    """Distinct small integers as floats: every row of pos and feats names its source row."""
-    total = sum(sizes)
-    pos = np.arange(total * 3, dtype=np.float32).reshape(total, 3)
-    feats = 1000.0 + np.arange(total * n_feats, dtype=np.float32).reshape(total, n_feats)
-    return pos, feats, np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+    return mc.ligands(sizes, n_feats)
 
 
 def _copies(pos, feats, ptr):
     """Every copy in order: (pos rows, feats rows)."""
-    out = []
-    for s in range(len(ptr) - 1):
-        rows = np.arange(ptr[s], ptr[s + 1])
-        out.append((pos[rows], feats[rows]))
-        for a in range(len(rows)):
-            keep = np.delete(rows, a)
-            out.append((pos[keep], feats[keep]))
-    return out
+    return [c[:2] for c in mc.ligand_copies(pos, feats, ptr)]
 
 
 def _want(copies, first, n_slots, slot_cap, n_feats=F):
-    pos = np.full((n_slots * slot_cap, 3), SENTINEL, dtype=np.float32)
-    feats = np.full((n_slots * slot_cap, n_feats), SENTINEL, dtype=np.float32)
-    ptr = np.zeros(n_slots + 1, dtype=np.int32)
-    for k in range(n_slots):
-        at = ptr[k]
-        if 0 <= first + k < len(copies):
-            p, f = copies[first + k]
-            pos[at:at + len(p)], feats[at:at + len(p)] = p, f
-            at += len(p)
-        ptr[k + 1] = at
-    return pos, feats, ptr
+    return mc.packed_batch([c + (-1,) for c in copies], first, n_slots, slot_cap, n_feats, SENTINEL)[:3]
 
 
 def _pack(pos, feats, ptr, first, n_slots, slot_cap):

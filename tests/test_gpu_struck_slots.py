@@ -8,7 +8,8 @@ import numpy as np
 import pytest
 import torch
 
-from tests._attribution_ref import AttrCase, masked_coo
+from tests import _many_slots_cases as mc
+from tests._attribution_ref import AttrCase
 from tests.test_gpu_ligand_masking import N_REC, _set, _single_head
 
 pytestmark = pytest.mark.gpu
@@ -111,46 +112,8 @@ def _expected(radius, rec_drop):
     """What the struck builder must write, from the ragged builder's output and the reference's masking per slot."""
     g = _plain(radius)
     slots, rec, rec_feats, _ = _case()
-    rec, rec_feats = rec.numpy(), rec_feats.numpy()
-    magg, xsum, deg = g['sums']
-    n_cap = len(g['node_graph'])
-    rows, cols, ets, lig_keep = [], [], [], []
-    node_ptr, node_graph = [0], np.full(n_cap, -1, dtype=np.int32)
-    pos, x = np.zeros((n_cap, 3), np.float32), np.zeros((n_cap, rec_feats.shape[1]), np.float32)
-    base = [np.zeros((n_cap, magg.shape[1]), np.float32), np.zeros((n_cap, 3), np.float32), np.zeros(n_cap, np.float32)]
-    for p, (n, r) in enumerate(zip(SLOT_SIZES, rec_drop)):
-        ei, et = _slot_edges(g, p)
-        touched = np.zeros(N_REC, dtype=bool)
-        if r >= 0:
-            touched[ei[0][(ei[1] == n + r) & (et == 2)] - n] = True       # the rows that had r in their template row
-            ei, et, _ = masked_coo(ei, et, [n + r])
-        keep = np.array([i for i in range(N_REC) if i != r])
-        n0 = node_ptr[-1]
-        rows.append(ei[0] + n0)
-        cols.append(ei[1] + n0)
-        ets.append(et)
-        row_touched = np.concatenate([np.zeros(n, dtype=bool), touched[keep]])
-        lig_keep.append((ei[0] < n) | (ei[1] < n) | row_touched[ei[0]])
-        size = n + len(keep)
-        node_graph[n0:n0 + size] = p
-        pos[n0:n0 + n], pos[n0 + n:n0 + size] = slots[p][1].numpy(), rec[keep]
-        x[n0:n0 + n], x[n0 + n:n0 + size] = slots[p][0].numpy(), rec_feats[keep]
-        based = keep[~touched[keep]]
-        at = n0 + n + np.flatnonzero(~touched[keep])
-        base[0][at], base[1][at], base[2][at] = magg[based], xsum[based], deg[based]
-        node_ptr.append(n0 + size)
-    row, col, et = np.concatenate(rows), np.concatenate(cols), np.concatenate(ets)
-    keep_l = np.concatenate(lig_keep)
-    want = dict(node_ptr=np.array(node_ptr, np.int32), node_graph=node_graph, pos=pos, x=x, base_magg=base[0],
-                base_xsum=base[1], base_deg=base[2])
-    for tag, m in (('', np.ones(len(row), dtype=bool)), ('_l', keep_l)):
-        d = np.bincount(row[m], minlength=n_cap)
-        want['rowptr' + tag] = np.concatenate([[0], np.cumsum(d)]).astype(np.int32)
-        want['row' + tag], want['col' + tag] = row[m].astype(np.int32), col[m].astype(np.int32)
-        want['etype' + tag] = et[m].astype(np.uint8)
-        if not tag:
-            want['inv_deg'] = np.float32(1) / np.maximum(d, 1).astype(np.float32)
-    return want
+    return mc.slot_batch([_slot_edges(g, p) for p in range(B)], [(f.numpy(), pose.numpy()) for f, pose in slots], rec_drop,
+                         rec.numpy(), rec_feats.numpy(), g['sums'], len(g['node_graph']))
 
 
 def _struck_build(radius, rec_drop, capacities=None):
@@ -312,43 +275,14 @@ F, N_SLOTS, SLOT_CAP, SENTINEL = 12, 7, 130, -7.0
 
 
 def _ligands(sizes):
-    """Distinct small integers as floats: every row of pos and feats names its source row."""
-    total = sum(sizes)
-    pos = np.arange(total * 3, dtype=np.float32).reshape(total, 3)
-    feats = 1000.0 + np.arange(total * F, dtype=np.float32).reshape(total, F)
-    return pos, feats, np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+    return mc.ligands(sizes, F)
 
 
-def _pair_table(pairs):
-    flat = [p for hit in pairs for p in hit]
-    table = np.array(flat, dtype=np.int32).reshape(len(flat), 2)
-    return table, np.concatenate([[0], np.cumsum([len(hit) for hit in pairs])]).astype(np.int32)
-
-
-def _copies(pos, feats, ptr, pairs):
-    """Every copy in order: (pos rows, feats rows, rec_drop)."""
-    out = []
-    for s, hit in enumerate(pairs):
-        rows = np.arange(ptr[s], ptr[s + 1])
-        out.append((pos[rows], feats[rows], -1))
-        for a, r in hit:
-            keep = np.delete(rows, a) if a >= 0 else rows
-            out.append((pos[keep], feats[keep], r))
-    return out
+_pair_table, _copies = mc.pair_table, mc.pair_copies
 
 
 def _want(copies, first):
-    pos = np.full((N_SLOTS * SLOT_CAP, 3), SENTINEL, dtype=np.float32)
-    feats = np.full((N_SLOTS * SLOT_CAP, F), SENTINEL, dtype=np.float32)
-    ptr, drop = np.zeros(N_SLOTS + 1, dtype=np.int32), np.full(N_SLOTS, -1, dtype=np.int32)
-    for k in range(N_SLOTS):
-        at = ptr[k]
-        if 0 <= first + k < len(copies):
-            p, f, drop[k] = copies[first + k]
-            pos[at:at + len(p)], feats[at:at + len(p)] = p, f
-            at += len(p)
-        ptr[k + 1] = at
-    return pos, feats, ptr, drop
+    return mc.packed_batch(copies, first, N_SLOTS, SLOT_CAP, F, SENTINEL)
 
 
 def _pack(pos, feats, ptr, table, pair_ptr, first, n_slots=N_SLOTS, slot_cap=SLOT_CAP, n_rec=150):
