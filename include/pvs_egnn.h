@@ -851,6 +851,37 @@ int pvs_slot_node_values_cropped(const float* y, int32_t ld_y, int32_t col, int3
                                  int32_t n_rec, float* lig_val, float* slot_rec_val, double* rec_sum,
                                  int32_t* rec_count, float* rec_max, pvs_stream_t stream);
 
+/* pvs_contact_attention's accumulation kernel by itself, over rows [n_hits, n_rec] that came from elsewhere (the
+ * masking scores of ScreeningSweep.receptor_hotspots(attribution='atom_masking'), laid out as NaN-filled rows):
+ * rec_sum / rec_count / rec_max [n_rec] are READ AND UPDATED with the values of every column that are not NaN, in hit
+ * order, with the same order relation for the maximum. NULL arguments and negative counts are refused before the
+ * launch; n_hits == 0 or n_rec == 0: returns 0 without a launch. One launch, no atomics: the same bits every time. */
+int pvs_hit_rows_accumulate(const float* rows, int32_t n_hits, int32_t n_rec, double* rec_sum, int32_t* rec_count,
+                            float* rec_max, pvs_stream_t stream);
+
+/* Per-hit ranks (the reference's attribution/hotspot.py with use_rank, :183-191: an atom's value in a binding event is
+ * replaced by its position in that event's descending sort). rows [n_hits, n_rec]: the value of every receptor atom
+ * in every hit, NaN where it has none. lig_val, lig_ptr [n_hits + 1] (DEVICE) and lig_rank: all given or all NULL;
+ * given, the packed ligand values lig_val[lig_ptr[h] .. lig_ptr[h + 1]) of hit h are candidates too (the reference
+ * ranks over all atoms of the complex for cam and atom_masking, over protein atoms only for edge_attention). The
+ * candidates of hit h are its ligand values that are not NaN (position = packed order), then its row values that are
+ * not NaN (position = n_lig + j); u stands before v iff u > v, or u == v and u's position is lower (-0.0 == +0.0, the
+ * infinities are ordinary values); rank(c) = the number of candidates of the same hit that stand before c: the
+ * position in a descending STABLE sort, 0 = best (csrc/hit_ranks.h).
+ *   row_rank [n_hits, n_rec]: the rank as a float, NaN where rows is NaN.
+ *   lig_rank [>= lig_ptr[n_hits]]: the same, parallel to lig_val; the entries from lig_ptr[n_hits] on are left as they
+ *     are. The caller provides lig_val and lig_rank with lig_ptr[n_hits] entries: no argument says how many there are.
+ *   rank_sum / rank_count / rank_max [n_rec]: READ AND UPDATED from row_rank by pvs_contact_attention's accumulation
+ *     kernel itself (pvs_hit_rows_accumulate), in hit order.
+ * A hit whose ligand range descends, is negative or has more than 1024 atoms is no hit: a row of NaN, no ligand write,
+ * nothing accumulated. n_rec + 1024 >= 2^24 (a rank would not be exact in fp32), NULL rows / row_rank / accumulators
+ * and negative counts are refused before any launch; n_hits == 0 or n_rec == 0: returns 0 without a launch. A
+ * workgroup per (hit, 256 candidates) counts over the hit's candidates, staged through LDS; every output element has
+ * one writer, no atomics, no workspace: the same bits every time, whatever the launch geometry. Two launches. */
+int pvs_hit_value_ranks(const float* rows, int32_t n_hits, int32_t n_rec, const float* lig_val, const int32_t* lig_ptr,
+                        float* row_rank, float* lig_rank, double* rank_sum, int32_t* rank_count, float* rank_max,
+                        pvs_stream_t stream);
+
 /* nn.BCEWithLogitsLoss() with its default mean reduction (point_neural_network_base.py:74, used at :365) over n logits:
  * loss[0] = mean(max(x, 0) - x t + log1p(exp(-|x|))), grad[i] = (sigmoid(x_i) - t_i) / n (what the backward scales by
  * the upstream gradient: pvs_scale_by_device_scalar, out[i] = a[i] * scalar[0] with the scalar in device memory). */

@@ -229,6 +229,8 @@ _PROTOTYPES = {
                                       [C.c_int32] * 2 + [C.c_void_p] * 5 + [C.c_void_p]),
     'pvs_slot_node_values_cropped': (C.c_int, [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p] * 3 + [C.c_int32] * 2 +
                                      [C.c_void_p] * 5 + [C.c_void_p]),
+    'pvs_hit_rows_accumulate': (C.c_int, [C.c_void_p] + [C.c_int32] * 2 + [C.c_void_p] * 3 + [C.c_void_p]),
+    'pvs_hit_value_ranks': (C.c_int, [C.c_void_p] + [C.c_int32] * 2 + [C.c_void_p] * 7 + [C.c_void_p]),
     'pvs_bce_logits_fwd': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     'pvs_scale_by_device_scalar': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     'pvs_segment_workspace_bytes': (C.c_size_t, [C.c_int32, C.c_int32]),

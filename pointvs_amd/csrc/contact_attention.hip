@@ -220,6 +220,18 @@ k_cropped_node_values(const float* __restrict__ y, int ld_y, int col, int n_mean
 }
 }  // namespace
 
+// The accumulation kernel by itself, over rows that came from elsewhere (masking scores, ranks: hit_ranks.hip).
+extern "C" int pvs_hit_rows_accumulate(const float* rows, int32_t n_hits, int32_t n_rec, double* rec_sum,
+                                       int32_t* rec_count, float* rec_max, pvs_stream_t stream) {
+    PVS_REQUIRE(n_hits >= 0 && n_rec >= 0, "hit_rows_accumulate: %d hits, %d receptor atoms", n_hits, n_rec);
+    if (n_hits == 0 || n_rec == 0) return 0;
+    PVS_REQUIRE(rows && rec_sum && rec_count && rec_max, "hit_rows_accumulate: NULL argument");
+    k_contact_accumulate<<<(n_rec + kRowThreads - 1) / kRowThreads, kRowThreads, 0, (hipStream_t)stream>>>(
+        rows, n_hits, n_rec, rec_sum, rec_count, rec_max);
+    PVS_CHECK_LAUNCH();
+    return 0;
+}
+
 extern "C" int pvs_slot_node_values_cropped(const float* y, int32_t ld_y, int32_t col, int32_t n_mean, int32_t n_nodes,
                                             const int32_t* node_ptr, const int32_t* lig_ptr, const uint64_t* keep,
                                             int32_t n_slots, int32_t n_rec, float* lig_val, float* slot_rec_val,

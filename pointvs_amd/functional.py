@@ -1028,6 +1028,93 @@ def slot_node_values_cropped(y, node_ptr, lig_ptr, keep, n_rec, column=0, n_mean
     return out
 
 
+HIT_RANK_TILE = 1024        # csrc/hit_ranks.h: kPvsRankTile, the candidates one workgroup stages in LDS at a time
+HIT_RANK_MAX_LIGAND = 1024  # csrc/contact_attention.h: kPvsContactMaxLigand
+
+
+def _checked_accumulators(who, acc, n_rec):
+    """`acc`, a `new_contact_accumulators` triple over n_rec atoms on the device, checked."""
+    if acc is None or len(acc) != 3:
+        raise ValueError(f'{who}: acc = (float64 sum [{n_rec}], int32 count [{n_rec}], float32 max [{n_rec}]) - '
+                         'new_contact_accumulators')
+    rec_sum, rec_count, rec_max = acc
+    _lib.require_hip(*acc)
+    if (rec_sum.dtype != torch.float64 or rec_count.dtype != torch.int32 or rec_max.dtype != torch.float32
+            or rec_sum.shape != (n_rec,) or rec_count.shape != (n_rec,) or rec_max.shape != (n_rec,)
+            or not all(t.is_contiguous() for t in acc)):
+        raise ValueError(f'{who}: acc = (float64 sum [{n_rec}], int32 count [{n_rec}], float32 max [{n_rec}]), '
+                         'contiguous')
+    return acc
+
+
+def hit_rows_accumulate(rows, acc):
+    """`contact_attention`'s accumulation by itself (pvs_hit_rows_accumulate): rows [n_hits, n_rec] fp32 on the device,
+    NaN = no value; acc, a `new_contact_accumulators` triple, is UPDATED with every column's values that are not NaN,
+    in hit order, and returned. One launch, no atomics: the same bits every time."""
+    who = 'hit_rows_accumulate'
+    rows = _c(rows, _F32, _FP32_ONLY)
+    if rows.dim() != 2:
+        raise ValueError(f'{who}: rows [n_hits, n_rec]')
+    _lib.require_hip(rows)
+    n_hits, n_rec = rows.shape
+    acc = _checked_accumulators(who, acc, n_rec)
+    _lib.check(_lib.lib().pvs_hit_rows_accumulate(_lib.ptr(rows), n_hits, n_rec, *(_lib.ptr(t) for t in acc),
+                                                  _stream(rows.device)), 'pvs_hit_rows_accumulate')
+    return acc
+
+
+def hit_value_ranks(rows, lig_val=None, lig_ptr=None, out=None, acc=None):
+    """Per-hit ranks (pvs_hit_value_ranks; the reference's hotspot.py with use_rank): rows [n_hits, n_rec] fp32 on the
+    device holds every receptor atom's value in every hit, NaN = none. lig_val [>= lig_ptr[n_hits]] fp32 and lig_ptr
+    [n_hits + 1] int32, both or neither: the packed ligand values of the hits, candidates too. The candidates of a hit
+    are its ligand values, then its row values, NaN left out; u stands before v iff u > v, or u == v and u comes
+    earlier (-0.0 == +0.0); a candidate's rank is the number of candidates of its hit that stand before it - the
+    position in a descending stable sort, 0 = best. Returns (row_rank [n_hits, n_rec] - NaN where rows is -, lig_rank
+    (parallel to lig_val, entries from lig_ptr[n_hits] on not written; None without lig_val), rank_sum, rank_count,
+    rank_max): the last three are `acc` (fresh ones without: new_contact_accumulators), UPDATED with row_rank as
+    `contact_attention` updates its own. A hit whose ligand range descends, is negative or has more than 1024 atoms
+    gets a row of NaN, no ligand write and adds nothing. `out`: (row_rank, lig_rank) to write into. Two launches, no
+    atomics, no workspace, no allocation with out and acc: the same bits every time."""
+    who = 'hit_value_ranks'
+    rows = _c(rows, _F32, _FP32_ONLY)
+    if rows.dim() != 2:
+        raise ValueError(f'{who}: rows [n_hits, n_rec]')
+    n_hits, n_rec = rows.shape
+    if n_rec + HIT_RANK_MAX_LIGAND >= 1 << 24:
+        raise ValueError(f'{who}: {n_rec} receptor atoms: a rank is stored as a float and must be exact '
+                         f'(n_rec + {HIT_RANK_MAX_LIGAND} < 2^24)')
+    if (lig_val is None) != (lig_ptr is None):
+        raise ValueError(f'{who}: lig_val and lig_ptr are given together or not at all')
+    with_lig = lig_val is not None
+    if with_lig:
+        lig_val = _c(lig_val, _F32, _FP32_ONLY)
+        if (lig_val.dim() != 1 or lig_ptr.dtype != torch.int32 or lig_ptr.shape != (n_hits + 1,)
+                or not lig_ptr.is_contiguous()):
+            raise ValueError(f'{who}: lig_val [>= lig_ptr[n_hits]] and a contiguous int32 lig_ptr [{n_hits + 1}]')
+    _lib.require_hip(rows, lig_val, lig_ptr)
+    dev = rows.device
+    if out is None:
+        # (the ligand ranks start as NaN: what a hit that is none leaves behind)
+        out = (torch.empty_like(rows), torch.full_like(lig_val, float('nan')) if with_lig else None)
+    if len(out) != 2:
+        raise ValueError(f'{who}: out = (row_rank, lig_rank)')
+    row_rank, lig_rank = out
+    _lib.require_hip(row_rank, lig_rank)
+    if (row_rank.dtype != torch.float32 or row_rank.shape != rows.shape or not row_rank.is_contiguous()
+            or (lig_rank is None) == with_lig
+            or (with_lig and (lig_rank.dtype != torch.float32 or lig_rank.shape != lig_val.shape
+                              or not lig_rank.is_contiguous()))
+            or row_rank.data_ptr() == rows.data_ptr() and rows.numel()
+            or (with_lig and lig_rank.data_ptr() == lig_val.data_ptr() and lig_val.numel())):
+        raise ValueError(f'{who}: out = (row_rank [{n_hits}, {n_rec}], lig_rank like lig_val - None without it), '
+                         'contiguous fp32, not the inputs themselves')
+    acc = _checked_accumulators(who, new_contact_accumulators(n_rec, dev) if acc is None else acc, n_rec)
+    _lib.check(_lib.lib().pvs_hit_value_ranks(
+        _lib.ptr(rows), n_hits, n_rec, _lib.ptr(lig_val), _lib.ptr(lig_ptr), _lib.ptr(row_rank), _lib.ptr(lig_rank),
+        *(_lib.ptr(t) for t in acc), _stream(dev)), 'pvs_hit_value_ranks')
+    return (row_rank, lig_rank) + tuple(acc)
+
+
 class _BceLogitsMeanFn(torch.autograd.Function):
     """nn.BCEWithLogitsLoss() (mean) as one launch forward (loss + the gradient factor), one backward."""
 

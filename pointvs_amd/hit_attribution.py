@@ -260,20 +260,73 @@ def receptor_atom_masking(sweep, items, atoms='contacts', scores_file=None, sigm
     return _per_hit(names, counts, which, scores)
 
 
+ATTRIBUTIONS = ('edge_attention', 'cam', 'atom_masking')
+
+
+def _masking_rows(sweep, items, atoms, sigmoid, column):
+    """attribution='atom_masking': the sweep's own receptor_atom_masking and ligand_atom_masking of the hits, the
+    receptor scores laid out as NaN-filled rows. Returns (rows [hits, n_rec], {name: ligand scores [n]})."""
+    dev, n_rec = sweep.rec_pos.device, int(sweep.rec_pos.shape[0])
+    if torch.is_tensor(atoms) and atoms.dim() == 1 and not atoms.is_floating_point():
+        listed = atoms.tolist()
+        if len(set(listed)) != len(listed):
+            raise ValueError('receptor_hotspots: atoms lists a receptor atom more than once '
+                             f'({sorted({r for r in listed if listed.count(r) > 1})}): a hit has one score per atom')
+    by_hit = sweep.receptor_atom_masking(items, atoms=atoms, sigmoid=sigmoid, column=column)
+    ligand = sweep.ligand_atom_masking(items, sigmoid=sigmoid, column=column)
+    rows = torch.full((len(items), n_rec), float('nan'), dtype=torch.float32, device=dev)
+    counts = [int(by_hit[name][0].shape[0]) for name, _, _ in items]
+    if sum(counts):
+        # (one indexed write: a hit lists an atom once)
+        hit = torch.repeat_interleave(torch.arange(len(items), device=dev), torch.tensor(counts, device=dev))
+        which = torch.cat([by_hit[name][0] for name, _, _ in items], 0).long()
+        rows[hit, which] = torch.cat([by_hit[name][1] for name, _, _ in items], 0).float()
+    return rows, {name: ligand[name].float() for name, _, _ in items}
+
+
+def _hotspot_order(out, use_rank, top):
+    """The receptor atoms with count > 0, best first - by rank_mean ascending under use_rank, else by mean descending
+    (the reference's final sort), ties to the lower atom - cut to the first `top` (its --cutoff)."""
+    key = out['rank_mean'] if use_rank else -out['mean']
+    have = torch.nonzero(out['count'] > 0).reshape(-1)
+    order = have[torch.sort(key[have], stable=True).indices]       # (have ascends: a stable sort leaves ties to the lower atom)
+    return order if top is None else order[:top]
+
+
 @torch.no_grad()
 def receptor_hotspots(sweep, items, gnn_layer=1, scores_file=None, per_hit=False, attribution='edge_attention',
-                      column=None, ligand_scores_file=None):
-    if attribution not in ('edge_attention', 'cam'):
-        raise ValueError(f"receptor_hotspots: attribution={attribution!r}: 'edge_attention' or 'cam'")
-    by_cam = attribution == 'cam'
-    if column is not None and not by_cam:
-        raise ValueError("receptor_hotspots: column selects a head output of attribution='cam'")
-    hits = Hits(items, 'receptor_hotspots')
+                      column=None, ligand_scores_file=None, atoms='contacts', sigmoid=None, use_rank=False, top=None):
+    if attribution not in ATTRIBUTIONS:
+        raise ValueError(f"receptor_hotspots: attribution={attribution!r}: 'edge_attention', 'cam' or 'atom_masking'")
+    by_cam, by_masking = attribution == 'cam', attribution == 'atom_masking'
+    if column is not None and not (by_cam or by_masking):
+        raise ValueError("receptor_hotspots: column selects a head output of attribution='cam' or 'atom_masking'")
+    if not by_masking and (sigmoid is not None or not (isinstance(atoms, str) and atoms == 'contacts')):
+        raise ValueError("receptor_hotspots: atoms and sigmoid belong to attribution='atom_masking'")
+    if top is not None:
+        top = int(top)
+        if top < 0:
+            raise ValueError(f'receptor_hotspots: top={top}: the number of atoms to keep in order, or None')
+    hits = Hits(items, 'receptor_hotspots')            # (materialises `items`, once)
     names, ns = hits.names, hits.ns
     dev, n_rec = sweep.rec_pos.device, int(sweep.rec_pos.shape[0])
     ligand, hit_rows = {}, []
+    # use_rank: the ranks of every batch's values (PF.hit_value_ranks, behind the step and outside its capture)
+    # accumulate into a second triple; edge_attention ranks the receptor atoms alone, the other two the whole complex
+    ranks = PF.new_contact_accumulators(n_rec, dev) if use_rank else None
+    rank_rows, lig_ranks = [], []
     lig_key, slot_key = ('lig_val', 'slot_rec_val') if by_cam else ('lig_att', 'slot_rec_att')
-    if hits.items:
+    if by_masking:
+        rows, ligand = _masking_rows(sweep, hits.items, atoms, sigmoid, 0 if column is None else column)
+        rec_sum, count, high = PF.hit_rows_accumulate(rows, PF.new_contact_accumulators(n_rec, dev))
+        if use_rank and hits.items:
+            lig_ptr = torch.tensor([0] + ns).cumsum(0).to(device=dev, dtype=torch.int32)
+            got = PF.hit_value_ranks(rows, torch.cat([ligand[name] for name in names], 0), lig_ptr, acc=ranks)
+            rank_rows.append(got[0])
+            lig_ranks.append(got[1])
+        if per_hit:
+            hit_rows.append(rows)
+    elif hits.items:
         kw = dict(cam=True if column is None else int(column)) if by_cam else dict(contact_attention=gnn_layer)
         screen = _ready_screen(sweep, hits, 'cam_screen' if by_cam else 'hotspot', **kw)
         values = screen.cam if by_cam else screen.contact
@@ -293,18 +346,36 @@ def receptor_hotspots(sweep, items, gnn_layer=1, scores_file=None, per_hit=False
             lig_rows.append(values[lig_key][:total].clone())
             if per_hit:
                 hit_rows.append(values[slot_key][:len(batch_ns)].clone())
+            if use_rank:
+                with_lig = (lig_rows[-1], ptrs_dev[k, :len(batch_ns) + 1]) if by_cam else ()
+                got = PF.hit_value_ranks(values[slot_key][:len(batch_ns)], *with_lig, acc=ranks)
+                if per_hit:
+                    rank_rows.append(got[0])
+                if by_cam:
+                    lig_ranks.append(got[1])
         screen.check()
-        rec_sum, count, top = (values[key].clone() for key in ('rec_sum', 'rec_count', 'rec_max'))
+        rec_sum, count, high = (values[key].clone() for key in ('rec_sum', 'rec_count', 'rec_max'))
         lig_rows = torch.cat(lig_rows, 0)
         ligand = {name: lig_rows[lo:lo + n] for name, n, lo in zip(names, ns, _starts(ns))}
     else:
-        rec_sum, count, top = PF.new_contact_accumulators(n_rec, dev)
-    out = dict(mean=rec_sum / count, count=count, max=top, ligand=ligand)      # (0 / 0: NaN)
+        rec_sum, count, high = PF.new_contact_accumulators(n_rec, dev)
+    out = dict(mean=rec_sum / count, count=count, max=high, ligand=ligand)      # (0 / 0: NaN)
     if per_hit:
         out['per_hit'] = torch.cat(hit_rows, 0) if hit_rows else torch.empty((0, n_rec), dtype=torch.float32,
                                                                              device=dev)
+    if use_rank:
+        out['rank_mean'] = ranks[0] / ranks[1]
+        if by_cam or by_masking:
+            packed = torch.cat(lig_ranks, 0) if lig_ranks else torch.empty(0, dtype=torch.float32, device=dev)
+            out['ligand_rank'] = {name: packed[lo:lo + n] for name, n, lo in zip(names, ns, _starts(ns))}
+        if per_hit:
+            out['per_hit_rank'] = torch.cat(rank_rows, 0) if rank_rows else torch.empty((0, n_rec), dtype=torch.float32,
+                                                                                       device=dev)
+    if use_rank or top is not None:
+        out['order'] = _hotspot_order(out, use_rank, top)
     if scores_file:
-        packed = torch.stack([out['mean'], count.double()], 1).cpu().numpy()      # the one copy to the host
+        # the one copy to the host (under use_rank the file carries rank_mean)
+        packed = torch.stack([out['rank_mean' if use_rank else 'mean'], count.double()], 1).cpu().numpy()
         atoms = [j for j in range(n_rec) if packed[j, 1] > 0]
         # (touch: no contact at all gives an empty file)
         _write_scores(sweep, scores_file, 'hotspot', packed[atoms], [f'atom{j}' for j in atoms], touch=True)

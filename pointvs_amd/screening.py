@@ -1068,7 +1068,8 @@ class ScreeningSweep:
     score files, `column` and `sigmoid` as on an uncropped sweep. A receptor atom that a hit's crop does not keep is not
     an atom of that hit's complex: atoms='all' means the kept atoms of each hit (PF.crop_keep), and an index tensor is
     intersected with them per hit. Under GraphNorm the copies of one batch normalise each other, as in every batched
-    route. `receptor_hotspots` stays refused under this keyword; it runs under `cropped_hotspots`.
+    route. `receptor_hotspots` stays refused under this keyword; it runs under `cropped_hotspots` - but for its
+    attribution='atom_masking', which IS these masking methods and is opted in here.
     cropped_hotspots (opt-in, default False; needs crop_radius, ValueError otherwise; any crop radius - below the edge
     radius a ligand atom's edges simply reach kept atoms only): `receptor_hotspots` then maps every hit on the complex
     cropped around it, the one its score is of - the hits stream whole through LibraryScreen(crop_radius=...,
@@ -1400,7 +1401,7 @@ class ScreeningSweep:
         return hit_attribution.receptor_atom_masking(self, items, atoms, scores_file, sigmoid, column)
 
     def receptor_hotspots(self, items, gnn_layer=1, scores_file=None, per_hit=False, attribution='edge_attention',
-                          column=None, ligand_scores_file=None):
+                          column=None, ligand_scores_file=None, atoms='contacts', sigmoid=None, use_rank=False, top=None):
         """Which receptor atoms the hits of a sweep bind to (the reference's attribution/hotspot.py with its default
         attribution, edge_attention): items as for `ligand_atom_masking` - (name, lig_feats [n,F], pose [n,3]), unique
         names, e.g. `best_poses(ligands)` - are the binding events; per event every atom gets the largest attention
@@ -1423,8 +1424,31 @@ class ScreeningSweep:
         atom, and scores_file gets a line for each; `gnn_layer` is ignored. The hits stream through `self.cam_screen`
         (LibraryScreen(cam=...)), which needs neither an attention layer nor the first-layer reuse. Same keys.
         ligand_scores_file: one line per ligand atom of every hit, item order then atom order, '{value:.6f} |
-        {receptor} {name}_atom{a}'."""
-        self._no_attribution_when_cropped('receptor_hotspots')
+        {receptor} {name}_atom{a}'.
+        attribution='atom_masking' (the reference's `--scoring_method atom_masking`): the value of an atom in a hit is
+        its masking score - this sweep's own `receptor_atom_masking(items, atoms=atoms, sigmoid=sigmoid, column=column
+        or 0)` and `ligand_atom_masking(items, sigmoid=sigmoid, column=column or 0)`, whose `*_raw` attributes stay
+        filled as those calls leave them - laid out as NaN-filled rows [hits, n_rec] and reduced over the hits on the
+        device (PF.hit_rows_accumulate). Same keys: count[j] is the number of hits that list atom j. atoms: 'contacts'
+        (default: per hit the receptor atoms in a contact), 'all' - on an uncropped sweep n_rec copies of every hit
+        through the struck screen, n_rec * len(items) / batch_size steps; on a cropped sweep every hit's kept atoms,
+        the reference's complex exactly - or a 1-D index tensor without repeats (ValueError otherwise). `atoms` and
+        `sigmoid` with another attribution: ValueError; `gnn_layer` is ignored. On a sweep with crop_radius this
+        attribution is opted in by cropped_attribution=True, the masking keyword, not by cropped_hotspots.
+        use_rank=True (the reference's `--use_rank`): beside the values, every hit's values are replaced by their
+        ranks within the hit - the position in a descending stable sort, 0 = best, ties to the earlier atom, the
+        ligand atoms before the receptor's (PF.hit_value_ranks, once per batch behind the step, outside its capture);
+        'edge_attention' ranks the receptor atoms among themselves, 'cam' and 'atom_masking' all atoms of the complex.
+        Added keys: rank_mean [n_rec] float64 (the mean rank over the hits in which the atom has a value, NaN without
+        one), ligand_rank {name: [n]} ('cam' and 'atom_masking'), per_hit_rank [len(items), n_rec] with per_hit;
+        scores_file then carries rank_mean in place of mean. The value keys are what they are without use_rank.
+        With use_rank or top: order, the receptor atoms with count > 0, best first - by mean descending, under
+        use_rank by rank_mean ascending (the reference's final sort), ties to the lower atom - cut to the first `top`
+        (the reference's `--cutoff`; top < 0: ValueError)."""
+        if attribution == 'atom_masking':       # (gated as the masking methods it calls: cropped_attribution)
+            self._no_attribution_when_cropped('receptor_atom_masking')
+        else:
+            self._no_attribution_when_cropped('receptor_hotspots')
         from . import hit_attribution
         return hit_attribution.receptor_hotspots(self, items, gnn_layer, scores_file, per_hit, attribution, column,
-                                                 ligand_scores_file)
+                                                 ligand_scores_file, atoms, sigmoid, use_rank, top)
