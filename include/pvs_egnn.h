@@ -44,7 +44,22 @@ enum {
     PVS_NODE_ATTENTION  = 1u << 8,
     PVS_GATED_RESIDUAL  = 1u << 9,
     PVS_REZERO          = 1u << 10,
-    PVS_SOFTMAX_ATT     = 1u << 11
+    PVS_SOFTMAX_ATT     = 1u << 11,
+    /* GraphNorm per node segment, forward only, fp32: valid only together with PVS_GRAPHNORM. The graph's
+     * n_norm_rows_dev then points at a DEVICE int32 table [n_graphs + 1] (the first row of every segment, as the batch
+     * builders leave node_ptr / graph_ptr; n_graphs >= 1, <= n_nodes; graph_eptr may stay NULL) instead of a single
+     * count. Every entry is clamped to [0, n_nodes]; segment s = rows [table[s], table[s + 1]), length
+     * max(0, table[s + 1] - table[s]); the table is expected non-decreasing and is read when the kernels run (a captured
+     * forward follows what is written into it). Each segment's mean and variance are bit for bit those of a call on its
+     * rows alone (pvs_graphnorm_stats_segments below), each row is normalised with its own segment's pair, and rows in
+     * front of table[0] or at / behind table[n_graphs] (padding) with mean = var = 0 - finite whenever the input is. A
+     * segment of length 0 has mean = var = 0; nothing is divided by 0. No atomics: the same bits every call.
+     * Honoured by pvs_egnn_layer_fwd, pvs_egnn_stack_fwd and pvs_egnn_layer_fwd_partial / _fwd_partial_att /
+     * _fwd_partial_softmax; pvs_egnn_layer_workspace_bytes grows under it (statistics and slabs for up to n_nodes
+     * segments) and the [2H] statistics slot of `saved` is unspecified. Refused, by name, by pvs_egnn_layer_bwd,
+     * pvs_egnn_stack_bwd and every *_f64 entry, without PVS_GRAPHNORM, with a NULL table and with n_graphs < 1. Without
+     * the flag nothing changes. */
+    PVS_GRAPHNORM_SEGMENTS = 1u << 12
 };
 
 /* attention_activation_fn (egnn_satorras.py:66-71); IDENTITY is what softmax_attention selects */
@@ -98,6 +113,8 @@ typedef struct PvsGraph {
      * those n rows alone -, rows >= n are never read for them, ALL n_nodes rows are normalised with them, and the
      * backward is the exact gradient of that (with zero upstream gradient on the rows >= n: the gradient of the n-row
      * problem). n = 0: mean = var = 0, rstd = 1 / sqrt(eps); nothing is divided by n.
+     * Under the layer flag PVS_GRAPHNORM_SEGMENTS (forward only) this member is instead a DEVICE int32 table
+     * [n_graphs + 1] of segment starts and every segment of rows is normalised by its own statistics: see the flag.
      * ABI (pvs_version() >= 112): sizeof(PvsGraph) = 104, offsetof(PvsGraph, n_norm_rows_dev) = 96. */
     const int32_t* n_norm_rows_dev;
 } PvsGraph;
@@ -637,6 +654,18 @@ size_t pvs_graphnorm_stats_rows_workspace_bytes(int32_t n_rows_cap, int32_t H);
 int pvs_graphnorm_stats_rows(const float* y1, const float* mean_scale, int32_t n_rows_cap, int32_t H,
                              const int32_t* n_rows_dev /* or NULL: n_rows_cap */, float* stats /* [2H] */,
                              void* workspace, size_t workspace_bytes, pvs_stream_t stream);
+
+/* The same per node segment (what a layer computes under PVS_GRAPHNORM_SEGMENTS): stats [n_segments, 2H], row s = the pair of
+ * the rows [seg_ptr[s], seg_ptr[s + 1]) of y1 [n_rows_cap, H] - bit for bit pvs_graphnorm_stats_rows on those rows alone.
+ * seg_ptr: DEVICE int32 [n_segments + 1], read when the kernels run, every entry clamped to [0, n_rows_cap], a segment's
+ * length max(0, seg_ptr[s + 1] - seg_ptr[s]); expected non-decreasing (a table that is not stays within the workspace, but
+ * segments that overlap may then get each other's sums). Length 0: mean = var = 0. Rows outside every segment are never
+ * read. n_segments >= 1, H <= 256. No atomics; the same bits every call. */
+size_t pvs_graphnorm_stats_segments_workspace_bytes(int32_t n_rows_cap, int32_t n_segments, int32_t H);
+int pvs_graphnorm_stats_segments(const float* y1, const float* mean_scale, int32_t n_rows_cap, int32_t H,
+                                 const int32_t* seg_ptr /* [n_segments + 1] */, int32_t n_segments,
+                                 float* stats /* [n_segments, 2H] */, void* workspace, size_t workspace_bytes,
+                                 pvs_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * The thin callers either side of the layer stack.

@@ -10,6 +10,8 @@ LIB_PATH = Path(os.environ.get('PVS_EGNN_LIB', _HERE / 'libpvs_egnn.so'))
 RESIDUAL, EDGE_RESIDUAL, EDGE_ATTENTION, NORMALIZE = 1 << 0, 1 << 1, 1 << 2, 1 << 3
 TANH, GRAPHNORM, UPDATE_COORDS, PERM_INVARIANT = 1 << 4, 1 << 5, 1 << 6, 1 << 7
 NODE_ATTENTION, GATED_RESIDUAL, REZERO, SOFTMAX_ATT = 1 << 8, 1 << 9, 1 << 10, 1 << 11
+# forward only, with GRAPHNORM: PvsGraph.n_norm_rows_dev is a segment table [n_graphs + 1], GraphNorm runs per segment
+GRAPHNORM_SEGMENTS = 1 << 12
 ACT_CODES = {'sigmoid': 0, 'tanh': 1, 'relu': 2, 'silu': 3, 'identity': 4}
 
 PARAM_FIELDS = (
@@ -197,6 +199,9 @@ _PROTOTYPES = {
     'pvs_graphnorm_stats_rows_workspace_bytes': (C.c_size_t, [C.c_int32, C.c_int32]),
     'pvs_graphnorm_stats_rows': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_size_t, C.c_void_p]),
+    'pvs_graphnorm_stats_segments_workspace_bytes': (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    'pvs_graphnorm_stats_segments': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                                               C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     'pvs_linear_fwd': (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 3 + [C.c_void_p]),
     'pvs_linear_bwd_workspace_bytes': (C.c_size_t, [C.c_int32] * 3),
     'pvs_linear_bwd': (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 3 + [C.c_void_p, C.c_size_t,

@@ -198,10 +198,26 @@ class _Eval:
         self.model.train(self.was_training)
 
 
-def masked_outputs(model, p, v, drop, bs=32, edge_indices=None, edge_attrs=None):
+def segments_refusal(model):
+    """Why the model's GraphNorm layers cannot normalise per node segment (fp64, more than 128 channels): a string, or
+    None. Autograd is not looked at: the callers run under no_grad."""
+    with torch.no_grad():
+        for layer in model.layers:
+            if getattr(layer, 'graphnorm', False):
+                why = layer.norm_segments_refusal()
+                if why is not None:
+                    return why
+    return None
+
+
+def masked_outputs(model, p, v, drop, bs=32, edge_indices=None, edge_attrs=None, per_graph_norm=False):
     """Raw model outputs of the unmasked complex and of every leave-out graph of the mask table `drop` (host int
     [M, 2], second slot -1: one atom): (original as the model returns it for one graph, masked [M, dim_output]), both
-    device tensors in the model's dtype. This is what atom_masking / bond_masking reduce to scores."""
+    device tensors in the model's dtype. This is what atom_masking / bond_masking reduce to scores.
+    per_graph_norm (default False): a model with GraphNorm (`couples_graphs`) is scored `chunk_size(...)` copies per
+    forward like any other model, every copy normalised by its own statistics (PreparedGraph.set_norm_segments on the
+    leave-out batch: the values of one copy per forward). Where the layers cannot take segments (fp64, more than 128
+    channels) the call keeps one copy per forward. Nothing changes for a model without GraphNorm."""
     if not isinstance(model, PNNGeometricBase):
         raise TypeError('pointvs_amd.attribution scores the geometric (EGNN) models only')
     x, pos, edge_indices, edge_attrs = _single_graph(model, p, v, edge_indices, edge_attrs)
@@ -219,11 +235,14 @@ def masked_outputs(model, p, v, drop, bs=32, edge_indices=None, edge_attrs=None)
         parent.check_status()
         original = model(_whole_graph(x, pos, edge_indices, edge_attrs, prepared=parent))
         step = chunk_size(bs, len(drop), n, parent.n_edges)
-        if couples_graphs(model):
+        segments = bool(per_graph_norm) and couples_graphs(model) and segments_refusal(model) is None
+        if couples_graphs(model) and not segments:
             step = 1
         outs, status = [], []
         for k in range(0, len(drop), step):
             mb = build_mask_batch(parent, drop[k:k + step], n_edges=int(counts[k:k + step].sum()))
+            if segments:
+                mb.prepared.set_norm_segments(mb.graph_ptr)
             total = mb.prepared.n_nodes
             batch = torch.searchsorted(mb.graph_ptr[1:].long(), torch.arange(total, device=x.device), right=True)
             g = Data(x=x.index_select(0, mb.src_node), pos=pos.index_select(0, mb.src_node), batch=batch,
@@ -262,13 +281,15 @@ def atom_masking(model, p, v, m=None, bs=32, edge_indices=None, edge_attrs=None,
 
     p [1, n, 3] positions, v [1, n, d] features, edge_indices [2, E] COO, edge_attrs [E, 3] one-hot. bs: leave-out
     graphs per forward (the reference ignores it for the EGNN models and runs one graph per forward; a model with
-    graphnorm is scored one graph per forward here too: couples_graphs). m and resis are
+    graphnorm is scored one graph per forward here too - couples_graphs - unless per_graph_norm=True: then `bs` copies
+    per forward, each normalised by its own statistics, masked_outputs). m and resis are
     accepted for the reference's signature and unused, as there. With SIGMOID the scores are differences of sigmoids."""
     if kwargs.get('synthpharm', False):
         p, v = p.reshape(1, *p.shape), v.reshape(1, *v.shape)
     n_atoms = int(p.shape[-2])
     drop = np.stack([np.arange(n_atoms), np.full(n_atoms, -1)], axis=1)
-    original, masked = masked_outputs(model, p, v, drop, bs, edge_indices, edge_attrs)
+    original, masked = masked_outputs(model, p, v, drop, bs, edge_indices, edge_attrs,
+                                      per_graph_norm=kwargs.get('per_graph_norm', False))
     regression = original.dim() == 2 and original.shape[1] == 3
     if SIGMOID and not regression:
         original, masked = torch.sigmoid(original), torch.sigmoid(masked)
@@ -281,14 +302,15 @@ def bond_masking(model, p, v, m=None, bs=32, edge_indices=None, edge_attrs=None,
 
     A model with several outputs is scored by output 1, as in the reference. For a SINGLE-output model the reference
     raises (`len()` of a 0-d array); here the one output is the score. A type-1 self loop (which generate_edges never
-    emits) removes its one atom. bs: leave-out graphs per forward."""
+    emits) removes its one atom. bs: leave-out graphs per forward. per_graph_norm: as in atom_masking."""
     if edge_indices is None or edge_attrs is None:
         raise ValueError('bond_masking needs edge_indices and edge_attrs')
     ei, ea = to_numpy(torch.as_tensor(edge_indices)), to_numpy(torch.as_tensor(edge_attrs))
     if ea.ndim != 2 or ea.shape[0] != ei.shape[1] or ea.shape[1] < 2:
         raise ValueError(f'edge_attrs must be [E, A >= 2] with E = {ei.shape[1]}, got {ea.shape}')
     visited, drop = bond_mask_table(ei, ea)
-    original, masked = masked_outputs(model, p, v, drop, bs, edge_indices, edge_attrs)
+    original, masked = masked_outputs(model, p, v, drop, bs, edge_indices, edge_attrs,
+                                      per_graph_norm=kwargs.get('per_graph_norm', False))
     if SIGMOID:
         original, masked = torch.sigmoid(original), torch.sigmoid(masked)
     scores = np.zeros(ei.shape[1], dtype=np.float64)

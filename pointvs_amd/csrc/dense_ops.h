@@ -106,6 +106,15 @@ int pvs_launch_colreduce(hipStream_t s, int mode, float* out, const float* A, in
 // same quotient. Rows >= n are never read; n = 0 gives zeros. slabs: pvs_colreduce_blocks(n_cap) * C floats.
 int pvs_launch_colmean_rows(hipStream_t s, int mode, float* out, const float* A, int lda, const float* shift,
                             int n_cap, const int32_t* n_rows_dev, int C, float* slabs);
+// The same per row segment: stats [n_segs, 2C]; segment s = rows [seg_ptr[s], seg_ptr[s + 1]) of A, the table (DEVICE int32
+// [n_segs + 1], every entry clamped to [0, n_cap], length max(0, end - start)) read when the kernels run.
+// PVS_COL_SUM_A writes stats[s][0:C] = the segment's column means; PVS_COL_SUMSQ_SHIFT writes stats[s][C:2C] = its means of
+// (A - stats[s][0:C] * ms)^2. Per segment the bits of pvs_launch_colmean_rows on the segment's rows alone; length 0 gives
+// zeros; rows outside every segment are never read. No atomics. slabs: pvs_colmean_segments_slabs(n_cap, n_segs) * C floats
+// (a table that is not non-decreasing stays inside them; segments that overlap may then get each other's sums).
+size_t pvs_colmean_segments_slabs(int n_cap, int n_segs);
+int pvs_launch_colmean_segments(hipStream_t s, int mode, float* stats, const float* A, int lda, const float* ms,
+                                int n_cap, const int32_t* seg_ptr, int n_segs, int C, float* slabs);
 
 // out[map(o)] (=|+=) sum_g slabs[g*width + o], o < width; map(o) = (o / inner) * ldo + o % inner
 int pvs_launch_reduce_slabs(hipStream_t s, float* out, int ldo, int inner, const float* slabs,

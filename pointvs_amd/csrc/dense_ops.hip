@@ -308,6 +308,163 @@ k_reduce_slabs_rows(float* __restrict__ out, const float* __restrict__ slabs, co
     }
 }
 
+// ---- column means per row segment: segment s = rows [seg_ptr[s], seg_ptr[s + 1]) of A, the table on the device ---------
+// Every entry is clamped to [0, n_cap], a segment's length is n = max(0, end - start). Per segment the split is
+// row_split_dev's for n, its workgroups run the block code of k_colreduce / k_colreduce4 on the segment's rows (block b of
+// the split by workgroup y = b mod gridDim.y: the grid is sized from host-known numbers and stays right for any length up
+// to n_cap), and the slabs are summed by k_reduce_slabs_rows' tree: the bits of a call on the segment's rows alone.
+// Slabs: segment s writes its blocks(n) slabs from slab s + start / 128 on. For a non-decreasing table these ranges are
+// disjoint (start / 128 + ceil(n / 128) <= (start + n) / 128 + 1), and for any table they end in front of slab
+// S + n_cap / 128 + 1 (pvs_colmean_segments_slabs): segments of a table that runs backwards may share slabs - their
+// statistics are then unspecified - but nothing is written out of bounds. A segment of length 0 writes no slab and gets
+// zeros from the reduction. Rows outside every segment are never read.
+// mode PVS_COL_SUMSQ_SHIFT: the shift of segment s is stats[s][0:C] * ms (the mean the first pass left there times
+// GraphNorm's mean_scale, rounded once like k_gn_shift's product, never contracted into the subtraction).
+struct PvsSegSplit { int start, n, blocks, rpb, slab0; };
+
+__device__ __forceinline__ PvsSegSplit seg_split_dev(const int* __restrict__ seg_ptr, int seg, int n_cap) {
+    PvsSegSplit r;
+    r.start = min(max(seg_ptr[seg], 0), n_cap);
+    const int end = min(max(seg_ptr[seg + 1], 0), n_cap);
+    r.n = max(end - r.start, 0);
+    r.blocks = min(max((r.n + 127) / 128, 1), kMaxBlocks);
+    r.rpb = (r.n + r.blocks - 1) / r.blocks;
+    r.slab0 = seg + r.start / 128;
+    return r;
+}
+
+// colreduce_block's arithmetic (modes PVS_COL_SUM_A / PVS_COL_SUMSQ_SHIFT), statement for statement, per block of a segment
+__global__ void __launch_bounds__(kThreads)
+k_colreduce_segs(int mode, float* __restrict__ slabs, const float* __restrict__ A, int lda,
+                 const float* __restrict__ stats, const float* __restrict__ ms, const int* __restrict__ seg_ptr,
+                 int n_cap, int C) {
+    __shared__ float part[kThreads];
+    const int seg = blockIdx.x;
+    const PvsSegSplit g = seg_split_dev(seg_ptr, seg, n_cap);
+    if (g.n == 0) return;
+    const float* __restrict__ As = A + (size_t)g.start * lda;
+    const int tid = threadIdx.x;
+    const int R = kThreads / C;
+    const int c = tid % C, r = tid / C;
+    const float sh = (mode == PVS_COL_SUMSQ_SHIFT && r < R) ? __fmul_rn(stats[(size_t)seg * 2 * C + c], ms[c]) : 0.f;
+    for (int b = blockIdx.y; b < g.blocks; b += gridDim.y) {
+        const int r0 = b * g.rpb;
+        const int r1 = min(g.n, r0 + g.rpb);
+        float acc = 0.f;
+        if (r < R) {
+            for (int n = r0 + r; n < r1; n += R) {
+                float a = As[(size_t)n * lda + c];
+                if (mode == PVS_COL_SUM_A) acc += a;
+                else { float d = a - sh; acc = fmaf(d, d, acc); }
+            }
+        }
+        part[tid] = acc;
+        __syncthreads();
+        if (tid < C) {
+            float s = 0.f;
+            for (int rr = 0; rr < R; ++rr) s += part[rr * C + tid];
+            slabs[(size_t)(g.slab0 + b) * C + tid] = s;
+        }
+        __syncthreads();
+    }
+}
+
+// k_colreduce4's arithmetic likewise (C % 4 == 0, 16-byte aligned rows and slabs)
+__global__ void __launch_bounds__(kThreads)
+k_colreduce4_segs(int mode, float* __restrict__ slabs, const float* __restrict__ A, int lda,
+                  const float* __restrict__ stats, const float* __restrict__ ms, const int* __restrict__ seg_ptr,
+                  int n_cap, int C) {
+    __shared__ float4 part[kThreads];
+    const int seg = blockIdx.x;
+    const PvsSegSplit g = seg_split_dev(seg_ptr, seg, n_cap);
+    if (g.n == 0) return;
+    const float* __restrict__ As = A + (size_t)g.start * lda;
+    const int tid = threadIdx.x;
+    const int QC = C / 4, R = kThreads / QC;
+    const int q = tid % QC, r = tid / QC;
+    float4 sh = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (mode == PVS_COL_SUMSQ_SHIFT && r < R) {
+        const float* mean = stats + (size_t)seg * 2 * C + 4 * q;
+        sh = make_float4(__fmul_rn(mean[0], ms[4 * q]), __fmul_rn(mean[1], ms[4 * q + 1]),
+                         __fmul_rn(mean[2], ms[4 * q + 2]), __fmul_rn(mean[3], ms[4 * q + 3]));
+    }
+    for (int b = blockIdx.y; b < g.blocks; b += gridDim.y) {
+        const int r0 = b * g.rpb;
+        const int r1 = min(g.n, r0 + g.rpb);
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (r < R) {
+            constexpr int UN = 4;
+            for (int n0 = r0 + r; n0 < r1; n0 += UN * R) {
+                float4 a[UN];
+#pragma unroll
+                for (int u = 0; u < UN; ++u) {
+                    const int n = n0 + u * R;
+                    const bool ok = n < r1;
+                    a[u] = ok ? *reinterpret_cast<const float4*>(As + (size_t)n * lda + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
+                    if (mode == PVS_COL_SUMSQ_SHIFT)
+                        a[u] = ok ? make_float4(a[u].x - sh.x, a[u].y - sh.y, a[u].z - sh.z, a[u].w - sh.w) : a[u];
+                }
+#pragma unroll
+                for (int u = 0; u < UN; ++u) {
+                    if (mode == PVS_COL_SUM_A) { acc.x += a[u].x; acc.y += a[u].y; acc.z += a[u].z; acc.w += a[u].w; }
+                    else {
+                        acc.x = fmaf(a[u].x, a[u].x, acc.x); acc.y = fmaf(a[u].y, a[u].y, acc.y);
+                        acc.z = fmaf(a[u].z, a[u].z, acc.z); acc.w = fmaf(a[u].w, a[u].w, acc.w);
+                    }
+                }
+            }
+        }
+        part[tid] = acc;
+        __syncthreads();
+        if (tid < QC) {
+            float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+            for (int rr = 0; rr < R; ++rr) {
+                const float4 v = part[rr * QC + tid];
+                s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+            }
+            *reinterpret_cast<float4*>(slabs + (size_t)(g.slab0 + b) * C + 4 * tid) = s;
+        }
+        __syncthreads();
+    }
+}
+
+// stats[seg][col0 + o] = (1 / n) * sum of the segment's slabs: k_reduce_slabs_rows per segment (workgroup = segment x
+// 32 outputs). n = 0: zeros.
+__global__ void __launch_bounds__(kThreads)
+k_reduce_slabs_segs(float* __restrict__ stats, int col0, const float* __restrict__ slabs,
+                    const int* __restrict__ seg_ptr, int n_cap, int width) {
+    __shared__ float part[8][33];
+    const int chunks = (width + 31) / 32;
+    const int seg = blockIdx.x / chunks, chunk = blockIdx.x - seg * chunks;
+    const PvsSegSplit g = seg_split_dev(seg_ptr, seg, n_cap);
+    const int n_slabs = g.n > 0 ? g.blocks : 0;
+    const float scale = g.n > 0 ? __fdiv_rn(1.0f, (float)g.n) : 0.f;
+    const float* __restrict__ sl0 = slabs + (size_t)g.slab0 * width;
+    const int ol = threadIdx.x & 31, sl = threadIdx.x >> 5;
+    const int o = chunk * 32 + ol;
+    float s = 0.f;
+    if (o < width) {
+        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+        int gidx = sl;
+        for (; gidx + 24 < n_slabs; gidx += 32) {
+            a0 += sl0[(size_t)gidx * width + o];
+            a1 += sl0[(size_t)(gidx + 8) * width + o];
+            a2 += sl0[(size_t)(gidx + 16) * width + o];
+            a3 += sl0[(size_t)(gidx + 24) * width + o];
+        }
+        for (; gidx < n_slabs; gidx += 8) a0 += sl0[(size_t)gidx * width + o];
+        s = (a0 + a1) + (a2 + a3);
+    }
+    part[sl][ol] = s;
+    __syncthreads();
+    if (sl == 0 && o < width) {
+        float t = 0.f;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) t += part[k][ol];
+        stats[(size_t)seg * 2 * width + col0 + o] = t * scale;
+    }
+}
+
 // out[map(o)] (=|+=) scale * sum_g slabs[g][o].  One block per 32 outputs: 8 slab lanes x 32
 // outputs; each slab lane sums its slabs g = lane, lane+8, ... in order, then the 8 partials are
 // added in lane order: a fixed summation tree, so the result is reproducible.
@@ -1522,6 +1679,32 @@ int pvs_launch_colmean_rows(hipStream_t s, int mode, float* out, const float* A,
     else k_colreduce_rows<<<blocks, kThreads, 0, s>>>(mode, slabs, A, lda, shift, n_rows_dev, n_cap, C);
     PVS_CHECK_LAUNCH();
     k_reduce_slabs_rows<<<(C + 31) / 32, kThreads, 0, s>>>(out, slabs, n_rows_dev, n_cap, C);
+    PVS_CHECK_LAUNCH();
+    return 0;
+}
+
+size_t pvs_colmean_segments_slabs(int n_cap, int n_segs) {
+    return (size_t)(n_segs > 0 ? n_segs : 0) + (size_t)(n_cap > 0 ? n_cap : 0) / 128 + 1;
+}
+
+int pvs_launch_colmean_segments(hipStream_t s, int mode, float* stats, const float* A, int lda, const float* ms,
+                                int n_cap, const int32_t* seg_ptr, int n_segs, int C, float* slabs) {
+    PVS_REQUIRE(mode == PVS_COL_SUM_A || mode == PVS_COL_SUMSQ_SHIFT, "colmean_segments: mode %d unsupported", mode);
+    PVS_REQUIRE(C >= 1 && C <= kThreads, "colmean_segments: width %d unsupported (1..%d)", C, kThreads);
+    PVS_REQUIRE(n_cap >= 0 && n_segs >= 1 && seg_ptr && ms, "colmean_segments: needs a row capacity, a segment table and mean_scale");
+    // block lanes per segment: enough workgroups for one long segment, few where there are many segments
+    int lanes = 1024 / n_segs;
+    if (lanes < 8) lanes = 8;
+    if (lanes > pvs_colreduce_blocks(n_cap)) lanes = pvs_colreduce_blocks(n_cap);
+    const bool vec4 = C % 4 == 0 && lda % 4 == 0 && (((uintptr_t)A | (uintptr_t)slabs) & 15) == 0;
+    const long long blocks = (long long)n_segs * ((C + 31) / 32);
+    PVS_REQUIRE(blocks <= 0x7fffffffLL, "colmean_segments: %d segments of width %d exceed the grid", n_segs, C);
+    PvsProfScope prof(s, vec4 ? PVS_PROF_COLREDUCE4_SEGS : PVS_PROF_COLREDUCE_SEGS);
+    if (vec4) k_colreduce4_segs<<<dim3(n_segs, lanes), kThreads, 0, s>>>(mode, slabs, A, lda, stats, ms, seg_ptr, n_cap, C);
+    else k_colreduce_segs<<<dim3(n_segs, lanes), kThreads, 0, s>>>(mode, slabs, A, lda, stats, ms, seg_ptr, n_cap, C);
+    PVS_CHECK_LAUNCH();
+    k_reduce_slabs_segs<<<(unsigned)blocks, kThreads, 0, s>>>(stats, mode == PVS_COL_SUMSQ_SHIFT ? C : 0, slabs, seg_ptr,
+                                                             n_cap, C);
     PVS_CHECK_LAUNCH();
     return 0;
 }

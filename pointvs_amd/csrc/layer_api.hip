@@ -14,12 +14,14 @@ namespace {
 struct Dims {
     int N, E, H, A, ld1, off_rho, off_q;
     bool perm;
+    bool segs;      // PVS_GRAPHNORM_SEGMENTS: GraphNorm per node segment (the table: PvsGraph.n_norm_rows_dev, n_graphs entries + 1)
 };
 
 Dims make_dims(const PvsLayerDesc* d, const PvsGraph* g) {
     Dims m;
     m.N = g->n_nodes; m.E = g->n_edges; m.H = d->hidden; m.A = d->n_edge_attr;
     m.perm = d->flags & PVS_PERM_INVARIANT;
+    m.segs = d->flags & PVS_GRAPHNORM_SEGMENTS;
     m.off_rho = m.perm ? m.H : 2 * m.H;
     m.off_q = m.perm ? 0 : m.H;
     m.ld1 = m.off_rho + 1 + m.A;
@@ -49,6 +51,15 @@ PvsNodeW make_node_w(const PvsLayerDesc* d, const PvsLayerParams* p) {
 
 int check_desc(const PvsLayerDesc* d, const PvsGraph* g, const PvsLayerParams* p, bool allow_dev_count = false) {
     PVS_REQUIRE(d && g && p, "NULL descriptor/graph/params");
+    if (d->flags & PVS_GRAPHNORM_SEGMENTS) {      // (forward entries pass allow_dev_count: the same set takes the flag)
+        PVS_REQUIRE(allow_dev_count, "PVS_GRAPHNORM_SEGMENTS is forward-only: accepted by pvs_egnn_layer_fwd, pvs_egnn_stack_fwd "
+                    "and pvs_egnn_layer_fwd_partial / _fwd_partial_att / _fwd_partial_softmax, refused by the backward");
+        PVS_REQUIRE(d->flags & PVS_GRAPHNORM, "PVS_GRAPHNORM_SEGMENTS is valid only together with PVS_GRAPHNORM");
+        PVS_REQUIRE(g->n_norm_rows_dev, "PVS_GRAPHNORM_SEGMENTS: PvsGraph.n_norm_rows_dev must point at the segment table "
+                    "[n_graphs + 1] (it is NULL)");
+        PVS_REQUIRE(g->n_graphs >= 1 && g->n_graphs <= g->n_nodes, "PVS_GRAPHNORM_SEGMENTS: PvsGraph.n_graphs = %d segments "
+                    "(1..n_nodes = %d)", g->n_graphs, g->n_nodes);
+    }
     // 16 / 32 / 64: every kernel family; 128 (the wide layer: 64 < hidden <= 128 zero-padded by the caller): the MFMA
     // edge kernels only (up to 3 edge classes, no PVS_EGNN_KERNELS=generic)
     PVS_REQUIRE(pvs_edge_v0_supported(d->hidden) ||
@@ -81,6 +92,7 @@ int check_desc(const PvsLayerDesc* d, const PvsGraph* g, const PvsLayerParams* p
 
 struct FwdWs {
     float *PQ, *y1, *u, *o, *smax, *ssum, *shift, *slabs, *m_scratch;
+    float *seg_stats, *seg_slabs;      // PVS_GRAPHNORM_SEGMENTS only (else NULL): [S, 2H] and the segments' slabs, for S <= N
 };
 
 size_t carve_fwd(PvsArena& a, const Dims& m, FwdWs* w) {
@@ -96,6 +108,8 @@ size_t carve_fwd(PvsArena& a, const Dims& m, FwdWs* w) {
     t.slabs = a.take<float>((size_t)pvs_colreduce_blocks(m.N) * m.H);
     // H = 128: the edge forward is two launches that hand the messages over through memory
     t.m_scratch = a.take<float>(m.H > 64 ? (size_t)(m.E > 0 ? m.E : 1) * m.H : 4);
+    t.seg_stats = m.segs ? a.take<float>(2 * NH) : nullptr;
+    t.seg_slabs = m.segs ? a.take<float>(pvs_colmean_segments_slabs(m.N, m.N) * m.H) : nullptr;
     if (w) *w = t;
     return a.off;
 }
@@ -243,10 +257,13 @@ int pvs_launch_edge_bwd_mfma(hipStream_t s, int H, PvsEdgeFamily fam, const PvsG
 // = node_out(o, h). Without GraphNorm the SiLU rides on the first product's epilogue, and the plain
 // (un-gated, no node attention) output stage on the second's: two launches instead of four.
 // n_norm_rows_dev (PvsGraph.n_norm_rows_dev, read under GraphNorm only): the statistics run over that many leading rows.
+// n_segs > 0 (PVS_GRAPHNORM_SEGMENTS): n_norm_rows_dev is the segment table [n_segs + 1] instead, every segment's pair goes
+// to seg_stats [n_segs, 2H] (slabs: seg_slabs), each row is normalised with its own; `stats` is not written.
 int node_mlp_forward(hipStream_t s, const Dims& m, const PvsLayerDesc* d, const PvsLayerParams* p,
                      const PvsNodeW& nw, const float* h, const float* Magg, float* y1, float* u,
                      float* o, float* stats, bool compute_stats, float* shift_tmp, float* slabs,
-                     float* h_out, float* node_att_out, const int32_t* n_norm_rows_dev) {
+                     float* h_out, float* node_att_out, const int32_t* n_norm_rows_dev, int n_segs = 0,
+                     float* seg_stats = nullptr, float* seg_slabs = nullptr) {
     const int H = m.H;
     const uint32_t F = d->flags;
     PvsLinearJob first = pvs_linear_job(y1, H, pvs_operand(h, H, p->node_w1, 2 * H, H), m.N, H, p->node_b1);
@@ -272,9 +289,15 @@ int node_mlp_forward(hipStream_t s, const Dims& m, const PvsLayerDesc* d, const 
     }
     first.epi = fuse_silu ? PVS_EPI_SILU_OUT : PVS_EPI_NONE;
     PVS_TRY(pvs_launch_linear(s, first));
-    if ((F & PVS_GRAPHNORM) && compute_stats)
-        PVS_TRY(pvs_graphnorm_stats(s, y1, p->gn_mean_scale, m.N, H, stats, shift_tmp, slabs, n_norm_rows_dev));
-    if (!fuse_silu) PVS_TRY(pvs_node_tail_fwd(s, y1, stats, nw, m.N, H, u));
+    if (n_segs > 0) {
+        PVS_TRY(pvs_graphnorm_stats_segments_launch(s, y1, p->gn_mean_scale, m.N, H, n_norm_rows_dev, n_segs, seg_stats,
+                                                    seg_slabs));
+        PVS_TRY(pvs_node_tail_fwd_segments(s, y1, seg_stats, n_norm_rows_dev, n_segs, nw, m.N, H, u));
+    } else {
+        if ((F & PVS_GRAPHNORM) && compute_stats)
+            PVS_TRY(pvs_graphnorm_stats(s, y1, p->gn_mean_scale, m.N, H, stats, shift_tmp, slabs, n_norm_rows_dev));
+        if (!fuse_silu) PVS_TRY(pvs_node_tail_fwd(s, y1, stats, nw, m.N, H, u));
+    }
     second.epi = !fuse_out ? PVS_EPI_NONE : (F & PVS_RESIDUAL) ? PVS_EPI_ADD_OUT : PVS_EPI_COPY_OUT;
     PVS_TRY(pvs_launch_linear(s, second));
     if (!fuse_out) PVS_TRY(pvs_node_out_fwd(s, H, o, h, nw, F, d->att_act, m.N, h_out, node_att_out));
@@ -374,7 +397,7 @@ extern "C" int pvs_egnn_layer_fwd(const PvsLayerDesc* d, const PvsGraph* g, cons
         PVS_CHECK_HIP(hipMemcpyAsync(x_out, x, sizeof(float) * 3 * (size_t)m.N,
                                      hipMemcpyDeviceToDevice, s));
     PVS_TRY(node_mlp_forward(s, m, d, p, nw, h, sv.Magg, sv.y1, sv.u, sv.o, sv.stats, true, w.shift, w.slabs, h_out,
-                             node_att_out, g->n_norm_rows_dev));
+                             node_att_out, g->n_norm_rows_dev, m.segs ? g->n_graphs : 0, w.seg_stats, w.seg_slabs));
     return 0;
 }
 
@@ -582,7 +605,7 @@ int partial_forward(bool soft, const char* entry, const PvsLayerDesc* d, const P
         PVS_CHECK_LAUNCH();
     }
     return node_mlp_forward(s, m, d, p, make_node_w(d, p), h, sv.Magg, sv.y1, sv.u, sv.o, sv.stats, true, w.shift, w.slabs,
-                            h_out, node_att_out, g->n_norm_rows_dev);
+                            h_out, node_att_out, g->n_norm_rows_dev, m.segs ? g->n_graphs : 0, w.seg_stats, w.seg_slabs);
 }
 
 }  // namespace
@@ -1023,6 +1046,9 @@ extern "C" int pvs_egnn_stack_bwd(const PvsLayerDesc* descs, const PvsLayerParam
                                   const PvsLayerGrads* grads, void* workspace, size_t workspace_bytes,
                                   pvs_stream_t stream) {
     PVS_TRY(check_stack(descs, params, n_layers, g, st, "pvs_egnn_stack_bwd"));
+    for (int l = 0; l < n_layers; ++l)
+        PVS_REQUIRE(!(descs[l].flags & PVS_GRAPHNORM_SEGMENTS),
+                    "pvs_egnn_stack_bwd: PVS_GRAPHNORM_SEGMENTS is forward-only (layer %d carries it)", l);
     PVS_REQUIRE(h0 && x0 && saved && g_h_out && g_h0 && grads && (n_layers == 1 || (h_mid && x_mid)),
                 "pvs_egnn_stack_bwd: NULL tensor");
     PvsArena arena(workspace, workspace_bytes);
@@ -1065,4 +1091,24 @@ extern "C" int pvs_graphnorm_stats_rows(const float* y1, const float* mean_scale
     float* slabs = arena.take<float>((size_t)pvs_colreduce_blocks(n_rows_cap) * H);
     PVS_REQUIRE(arena.ok(), "pvs_graphnorm_stats_rows: workspace too small (%zu < %zu)", workspace_bytes, arena.off);
     return pvs_graphnorm_stats((hipStream_t)stream, y1, mean_scale, n_rows_cap, H, stats, shift, slabs, n_rows_dev);
+}
+
+// ---- GraphNorm's statistics per node segment as an operator (include/pvs_egnn.h: pvs_graphnorm_stats_segments) ----------
+extern "C" size_t pvs_graphnorm_stats_segments_workspace_bytes(int32_t n_rows_cap, int32_t n_segments, int32_t H) {
+    const size_t h = (size_t)(H > 0 ? H : 0);
+    return pvs_align_up(pvs_colmean_segments_slabs(n_rows_cap, n_segments) * h * sizeof(float), 256) + 256;
+}
+
+extern "C" int pvs_graphnorm_stats_segments(const float* y1, const float* mean_scale, int32_t n_rows_cap, int32_t H,
+                                            const int32_t* seg_ptr, int32_t n_segments, float* stats, void* workspace,
+                                            size_t workspace_bytes, pvs_stream_t stream) {
+    PVS_REQUIRE(mean_scale && stats && H >= 1 && H <= 256,
+                "pvs_graphnorm_stats_segments: needs mean_scale, stats and 1 <= H <= 256");
+    PVS_REQUIRE(seg_ptr && n_segments >= 1, "pvs_graphnorm_stats_segments: needs a segment table with at least one segment");
+    PVS_REQUIRE(n_rows_cap >= 0 && (y1 || n_rows_cap == 0), "pvs_graphnorm_stats_segments: bad row capacity %d", n_rows_cap);
+    PvsArena arena(workspace, workspace_bytes);
+    float* slabs = arena.take<float>(pvs_colmean_segments_slabs(n_rows_cap, n_segments) * (size_t)H);
+    PVS_REQUIRE(arena.ok(), "pvs_graphnorm_stats_segments: workspace too small (%zu < %zu)", workspace_bytes, arena.off);
+    return pvs_graphnorm_stats_segments_launch((hipStream_t)stream, y1, mean_scale, n_rows_cap, H, seg_ptr, n_segments, stats,
+                                               slabs);
 }

@@ -589,6 +589,7 @@ int check_desc(const PvsLayerDesc* d, const PvsGraph* g, const char* who) {
     PVS_REQUIRE(d->n_edge_attr >= 0 && d->n_edge_attr <= 3, "%s: n_edge_attr=%d (0..3 built)", who, d->n_edge_attr);
     PVS_REQUIRE(g->n_nodes > 0 && g->n_edges >= 0, "%s: graph with %d nodes / %d edges", who, g->n_nodes, g->n_edges);
     PVS_REQUIRE(!g->n_edges_dev, "%s: a graph with a device-side edge count is forward-only fp32", who);
+    PVS_REQUIRE(!(d->flags & PVS_GRAPHNORM_SEGMENTS), "%s: PVS_GRAPHNORM_SEGMENTS (GraphNorm per node segment) is fp32 only", who);
     PVS_REQUIRE(!g->n_norm_rows_dev, "%s: a graph with a device-side GraphNorm row count (n_norm_rows_dev) is fp32 only",
                 who);
     PVS_REQUIRE(g->rowptr && (g->n_edges == 0 || g->col), "%s: graph without CSR arrays", who);

@@ -14,6 +14,13 @@ struct PvsNodeW {
 // launchers below that take it normalise all N rows with those statistics and return the exact gradient of that.
 int pvs_graphnorm_stats(hipStream_t s, const float* y1, const float* gn_ms, int N, int H, float* stats,
                         float* shift_tmp, float* slabs, const int32_t* n_rows_dev = nullptr);
+// GraphNorm per node segment (PVS_GRAPHNORM_SEGMENTS): stats [n_segs, 2H], per segment s = rows [seg_ptr[s], seg_ptr[s + 1])
+// the pair pvs_graphnorm_stats gives on those rows alone, bit for bit (dense_ops.h: pvs_launch_colmean_segments; slabs as
+// sized there). The tail normalises every row with its own segment's pair, rows of no segment with mean = var = 0.
+int pvs_graphnorm_stats_segments_launch(hipStream_t s, const float* y1, const float* gn_ms, int N, int H,
+                                        const int32_t* seg_ptr, int n_segs, float* stats, float* slabs);
+int pvs_node_tail_fwd_segments(hipStream_t s, const float* y1, const float* stats, const int32_t* seg_ptr, int n_segs,
+                               const PvsNodeW& w, int N, int H, float* u);
 // u = SiLU(GN(y1))  (GN skipped when w.gn_w == NULL)
 int pvs_node_tail_fwd(hipStream_t s, const float* y1, const float* stats, const PvsNodeW& w, int N,
                       int H, float* u);

@@ -379,6 +379,47 @@ __global__ void k_sum_vec(const float* v, int n, float* out) {
     }
 }
 
+// u = SiLU(GN(y1)) with each row's own segment statistics (stats [S, 2H], PVS_GRAPHNORM_SEGMENTS). The row's segment: the
+// last s with clamp(seg_ptr[s]) <= row, by bisection over the table as the statistics kernels clamp it (non-decreasing,
+// like a node offset table; an empty segment shares its start with the next one and is never picked). Rows in front of
+// seg_ptr[0] and rows at / behind seg_ptr[S] belong to no segment: mean = var = 0, the n = 0 contract of n_norm_rows_dev
+// (rstd = 1 / sqrt(eps): finite whenever y1 is). One thread per row and group of V channels (V = 4: 16-byte accesses).
+template <int V>
+__global__ void __launch_bounds__(256)
+k_node_tail_fwd_segs(const float* __restrict__ y1, const float* __restrict__ stats, const int* __restrict__ seg_ptr,
+                     int S, PvsNodeW w, int N, int H, float* __restrict__ u) {
+    const int gpr = H / V;
+    const long long total = (long long)N * gpr;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+         i += (long long)gridDim.x * blockDim.x) {
+        const int n = (int)(i / gpr), c0 = (int)(i - (long long)n * gpr) * V;
+        int lo = -1, hi = S;      // invariant: clamp(seg_ptr[lo]) <= n (lo = -1: none yet), clamp(seg_ptr[hi + 1]) > n (hi = S: none)
+        while (lo < hi) {
+            const int mid = lo + (hi - lo + 1) / 2;
+            if (min(max(seg_ptr[mid], 0), N) <= n) lo = mid; else hi = mid - 1;
+        }
+        const bool owned = lo >= 0 && lo < S;
+        const float* __restrict__ st = stats + (size_t)(owned ? lo : 0) * 2 * H;
+        float y[V], o[V];
+        if (V == 4) {
+            const float4 t = *reinterpret_cast<const float4*>(y1 + (size_t)n * H + c0);
+            y[0] = t.x; y[1 % V] = t.y; y[2 % V] = t.z; y[3 % V] = t.w;
+        } else {
+            y[0] = y1[(size_t)n * H + c0];
+        }
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            const int c = c0 + k;
+            const float mean = owned ? st[c] : 0.f, var = owned ? st[H + c] : 0.f;
+            const float shift = mean * w.gn_ms[c];
+            const float rstd = 1.0f / sqrtf(var + kGnEps);
+            o[k] = pvs_silu(w.gn_w[c] * (y[k] - shift) * rstd + w.gn_b[c]);
+        }
+        if (V == 4) *reinterpret_cast<float4*>(u + (size_t)n * H + c0) = make_float4(o[0], o[1 % V], o[2 % V], o[3 % V]);
+        else u[(size_t)n * H + c0] = o[0];
+    }
+}
+
 int ew_grid(long long total) {
     long long b = (total + 255) / 256;
     if (b < 1) b = 1;
@@ -406,6 +447,24 @@ int pvs_graphnorm_stats(hipStream_t s, const float* y1, const float* gn_ms, int 
     PVS_CHECK_LAUNCH();
     return pvs_launch_colreduce(s, PVS_COL_SUMSQ_SHIFT, stats + H, y1, H, nullptr, 0, shift_tmp, N, H,
                                 1.0f / (float)N, slabs, false);
+}
+
+int pvs_graphnorm_stats_segments_launch(hipStream_t s, const float* y1, const float* gn_ms, int N, int H,
+                                        const int32_t* seg_ptr, int n_segs, float* stats, float* slabs) {
+    int rc = pvs_launch_colmean_segments(s, PVS_COL_SUM_A, stats, y1, H, gn_ms, N, seg_ptr, n_segs, H, slabs);
+    if (rc) return rc;
+    return pvs_launch_colmean_segments(s, PVS_COL_SUMSQ_SHIFT, stats, y1, H, gn_ms, N, seg_ptr, n_segs, H, slabs);
+}
+
+int pvs_node_tail_fwd_segments(hipStream_t s, const float* y1, const float* stats, const int32_t* seg_ptr, int n_segs,
+                               const PvsNodeW& w, int N, int H, float* u) {
+    PVS_REQUIRE(w.gn_w && w.gn_b && w.gn_ms && seg_ptr && n_segs >= 1, "node_tail_fwd_segments: needs GraphNorm and a segment table");
+    PvsProfScope prof(s, PVS_PROF_NODE_TAIL_SEGS);
+    const bool vec4 = H % 4 == 0 && (((uintptr_t)y1 | (uintptr_t)u) & 15) == 0;
+    if (vec4) k_node_tail_fwd_segs<4><<<ew_grid((long long)N * (H / 4)), 256, 0, s>>>(y1, stats, seg_ptr, n_segs, w, N, H, u);
+    else k_node_tail_fwd_segs<1><<<ew_grid((long long)N * H), 256, 0, s>>>(y1, stats, seg_ptr, n_segs, w, N, H, u);
+    PVS_CHECK_LAUNCH();
+    return 0;
 }
 
 int pvs_node_tail_fwd(hipStream_t s, const float* y1, const float* stats, const PvsNodeW& w, int N,

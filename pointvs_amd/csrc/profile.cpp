@@ -16,7 +16,8 @@ const char* kNames[PVS_PROF_COUNT] = {"edge_fwd", "edge_bwd", "col_gather", "gra
                                       "tsgemm_mfma", "tsgemm_wide", "tsgemm_colchunk", "tsgemm_narrow", "tsgemm_tn8",
                                       "tsgemm_tn32", "colreduce4", "colreduce", "colreduce_chunk",
                                       "node_mlp_fwd", "node_mlp_bwd", "node_out_fwd", "node_out_bwd", "node_tail",
-                                      "node_wgrads", "colreduce4_rows", "colreduce_rows", "node_tail_rows"};
+                                      "node_wgrads", "colreduce4_rows", "colreduce_rows", "node_tail_rows",
+                                      "colreduce4_segments", "colreduce_segments", "node_tail_segments"};
 thread_local int t_fwd_tag = PVS_PROF_EDGE_FWD;
 std::atomic<int> g_edge_bwd_variant{PVS_EDGE_BWD_NONE};
 }  // namespace

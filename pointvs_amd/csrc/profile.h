@@ -20,7 +20,10 @@ enum { PVS_PROF_EDGE_FWD = 0, PVS_PROF_EDGE_BWD = 1, PVS_PROF_COL_GATHER = 2, PV
        // GraphNorm over a device row count (PvsGraph.n_norm_rows_dev): the column means over the leading rows, and the
        // tail launchers that read the count (the coefficients and the row-bounded second backward pass)
        PVS_PROF_COLREDUCE4_ROWS = 25, PVS_PROF_COLREDUCE_ROWS = 26, PVS_PROF_NODE_TAIL_ROWS = 27,
-       PVS_PROF_COUNT = 28 };
+       // GraphNorm per node segment (PVS_GRAPHNORM_SEGMENTS): the column means of every segment, and the tail that picks
+       // each row's pair
+       PVS_PROF_COLREDUCE4_SEGS = 28, PVS_PROF_COLREDUCE_SEGS = 29, PVS_PROF_NODE_TAIL_SEGS = 30,
+       PVS_PROF_COUNT = 31 };
 static_assert(PVS_PROF_COUNT + 1 <= 32, "the profile mask is an unsigned with bit (id + 1) per category");
 
 // tag the edge forward launches of the calling thread carry (layer_api: full layer vs partial layer)

@@ -317,6 +317,8 @@ class EGNNLayer(nn.Module):
         desc = self._desc()
         if skip_coords:
             desc = (desc[0], desc[1], desc[2] & ~_lib.UPDATE_COORDS, desc[3])
+        if self.graphnorm and pg.norm_segments is not None:
+            desc = self._desc_with_norm_segments(desc, h, coord)
         if not self._fused_width_ok():
             # wider than the fused kernels are built for: the layer as the composition of its public
             # sub-methods (dense products and segment reductions through the C ABI, per-edge glue as torch
@@ -343,6 +345,27 @@ class EGNNLayer(nn.Module):
         elif self.use_coords:
             d['_coords_src'] = lambda: x_out.detach()
         return h_out, x_out, m_sorted
+
+    def norm_segments_refusal(self, h=None, coord=None):
+        """Why this layer cannot normalise per node segment (PreparedGraph.set_norm_segments): a string, or None. The
+        segment kernels are forward-only fp32 kernels of the fused layer."""
+        if self.edge_mlp[0].weight.dtype == torch.float64 or (h is not None and h.dtype == torch.float64):
+            return 'the layer is fp64 (the fp64 kernels have no segment route)'
+        if not self._fused_width_ok():
+            return (f'hidden_nf={self.hidden_nf} runs the decomposed layer, whose GraphNorm is a torch expression over all '
+                    f'rows (the segment kernels are built for hidden sizes up to 128)')
+        if torch.is_grad_enabled() and (any(p.requires_grad for p in self.parameters())
+                                        or any(t is not None and t.requires_grad for t in (h, coord))):
+            return 'autograd is recording and the segment kernels have no backward (run under torch.no_grad())'
+        return None
+
+    def _desc_with_norm_segments(self, desc, h, coord):
+        why = self.norm_segments_refusal(h, coord)
+        if why is not None:
+            raise NotImplementedError(
+                f'GraphNorm per node segment (PreparedGraph.set_norm_segments) is forward-only, fp32 and built for hidden '
+                f'sizes up to 128: {why}. Clear the table (set_norm_segments(None)) and run one graph per forward.')
+        return (desc[0], desc[1], desc[2] | _lib.GRAPHNORM_SEGMENTS, desc[3])
 
     def _decomposed_call(self, pg, h, coord, m_prev_sorted, skip_coords):
         """EGNNLayer.forward (egnn_satorras.py:189-206) for hidden sizes above the fused kernels' 128 channels (any
@@ -651,6 +674,9 @@ class SartorrasEGNN(PNNGeometricBase):
         if skip_coords:
             d = descs[-1]
             descs[-1] = (d[0], d[1], d[2] & ~_lib.UPDATE_COORDS, d[3])
+        if pg.norm_segments is not None:      # (part of the descriptors: a plan is cached per flag set)
+            descs = [layer._desc_with_norm_segments(d, None, None) if layer.graphnorm else d
+                     for layer, d in zip(egnn_layers, descs)]
         if cached is not None and cached[0] == skip_coords and len(cached[1].pstructs) == len(pstructs) \
                 and all(a is b for a, b in zip(cached[1].pstructs, pstructs)) and cached[1].desc_tuples == tuple(descs):
             return cached[1]

@@ -471,6 +471,36 @@ def graphnorm_stats(y1, mean_scale, n_rows=None, out=None):
     return stats
 
 
+def graphnorm_stats_segments(y1, mean_scale, seg_ptr, out=None):
+    """GraphNorm's statistics of every row segment of y1 [N_cap, H] (fp32, H <= 256) as the layers compute them under
+    `_lib.GRAPHNORM_SEGMENTS`: a [S, 2 H] tensor, row s the pair `graphnorm_stats` gives on y1[seg_ptr[s]:seg_ptr[s + 1]]
+    alone, bit for bit. seg_ptr: a device int32 tensor [S + 1] (a node offset table), read on the device when the kernels
+    run; every entry is clamped to [0, N_cap], a segment that ends in front of its start has length 0, and a segment of
+    length 0 gives zeros. Rows outside every segment are never read. No gradient."""
+    if y1.dim() != 2 or y1.dtype != _F32:
+        raise TypeError(f'graphnorm_stats_segments: y1 must be a float32 [N, H] tensor (got {y1.dtype}, {tuple(y1.shape)})')
+    y1, mean_scale = y1.contiguous(), _c(mean_scale, _F32)
+    _lib.require_hip(y1, mean_scale, seg_ptr)
+    n_cap, hidden = int(y1.shape[0]), int(y1.shape[1])
+    if mean_scale.numel() != hidden:
+        raise ValueError(f'graphnorm_stats_segments: mean_scale has {mean_scale.numel()} entries, y1 {hidden} columns')
+    if not (torch.is_tensor(seg_ptr) and seg_ptr.dtype == torch.int32 and seg_ptr.dim() == 1 and seg_ptr.numel() >= 2
+            and seg_ptr.is_contiguous()):
+        raise ValueError('graphnorm_stats_segments: seg_ptr must be a contiguous device int32 tensor [S + 1], S >= 1')
+    n_segs = int(seg_ptr.numel()) - 1
+    lib = _lib.lib()
+    dev = y1.device
+    stats = torch.empty((n_segs, 2 * hidden), dtype=_F32, device=dev) if out is None else out
+    if stats.shape != (n_segs, 2 * hidden) or stats.dtype != _F32 or not stats.is_contiguous() or stats.device != dev:
+        raise ValueError(f'graphnorm_stats_segments: out must be a contiguous float32 [{n_segs}, {2 * hidden}] tensor on {dev}')
+    ws_bytes = lib.pvs_graphnorm_stats_segments_workspace_bytes(n_cap, n_segs, hidden)
+    ws = _ws(ws_bytes, dev)
+    _lib.check(lib.pvs_graphnorm_stats_segments(_lib.ptr(y1), _lib.ptr(mean_scale), n_cap, hidden, _lib.ptr(seg_ptr), n_segs,
+                                                _lib.ptr(stats), _lib.ptr(ws), ws_bytes, _stream(dev)),
+               'pvs_graphnorm_stats_segments')
+    return stats
+
+
 class _MeanPoolFn(torch.autograd.Function):
     """global_mean_pool over contiguous per-graph node ranges (pnn_geometric_base.py:29-33)."""
 

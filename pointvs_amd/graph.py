@@ -124,9 +124,8 @@ class PreparedGraph:
         (PvsGraph.n_norm_rows_dev): a padded, captured step has its real node count only on the device. The layers
         normalise every row with the statistics of those rows; forward and backward read the same word. The tensor is
         kept alive in `self.t['norm_rows']`. None clears it (the statistics run over all n_nodes rows again)."""
+        self._clear_norm()      # (exclusive with set_norm_segments: the later call replaces the earlier one)
         if count is None:
-            self.t.pop('norm_rows', None)
-            self.c.n_norm_rows_dev = None
             return
         if not (torch.is_tensor(count) and count.is_cuda and count.dtype == torch.int32 and count.numel() == 1
                 and count.is_contiguous()):
@@ -135,6 +134,42 @@ class PreparedGraph:
             raise ValueError(f"set_norm_rows: the count is on {count.device}, the graph on {self.t['rowptr'].device}")
         self.t['norm_rows'] = count
         self.c.n_norm_rows_dev = count.data_ptr()
+
+    def _clear_norm(self):
+        if self.t.pop('norm_segments', None) is not None:
+            self.c.n_graphs = int(self.t['graph_eptr'].numel()) - 1 if self.c.graph_eptr else 0
+        self.t.pop('norm_rows', None)
+        self.c.n_norm_rows_dev = None
+
+    @property
+    def norm_segments(self):
+        """The table given to `set_norm_segments`, or None."""
+        return self.t.get('norm_segments')
+
+    def set_norm_segments(self, node_ptr):
+        """node_ptr: a device int32 tensor [S + 1] on the graph's device, the first row of every node segment (a batch's
+        node offsets, as the batch builders leave `node_ptr` / `graph_ptr`), read on the device at every layer call.
+        GraphNorm layers then normalise every segment by its own statistics - each graph of a batch as if it ran alone,
+        the reference's semantics for one graph per forward - and rows of no segment (padding) with mean = var = 0
+        (`_lib.GRAPHNORM_SEGMENTS`; forward only, fp32, hidden sizes up to 128: the layers raise NotImplementedError
+        otherwise). Exclusive with `set_norm_rows`: the later call replaces the earlier one. The tensor is kept alive in
+        `self.t['norm_segments']`. None clears it."""
+        self._clear_norm()
+        if node_ptr is None:
+            return
+        if not (torch.is_tensor(node_ptr) and node_ptr.is_cuda and node_ptr.dtype == torch.int32 and node_ptr.dim() == 1
+                and node_ptr.numel() >= 2 and node_ptr.is_contiguous()):
+            raise ValueError('set_norm_segments needs a contiguous device int32 tensor [S + 1] with S >= 1 (or None)')
+        if node_ptr.device != self.t['rowptr'].device:
+            raise ValueError(f"set_norm_segments: the table is on {node_ptr.device}, the graph on {self.t['rowptr'].device}")
+        if node_ptr.numel() - 1 > self.n_nodes:
+            raise ValueError(f'set_norm_segments: {node_ptr.numel() - 1} segments over {self.n_nodes} nodes')
+        if self.c.graph_eptr and int(self.t['graph_eptr'].numel()) != int(node_ptr.numel()):
+            raise ValueError(f"set_norm_segments: the graph already knows {int(self.t['graph_eptr'].numel()) - 1} graphs "
+                             f'(set_graph_ptr), the table has {node_ptr.numel() - 1} segments: PvsGraph has one n_graphs')
+        self.t['norm_segments'] = node_ptr
+        self.c.n_norm_rows_dev = node_ptr.data_ptr()
+        self.c.n_graphs = int(node_ptr.numel()) - 1
 
     def poll_status(self):
         """Asynchronous validation: the first call queues a D2H copy of the status word, later

@@ -242,7 +242,8 @@ class _ReuseStep(_Step):
     rows x and the base rows base_magg / base_xsum / base_deg, which the builder expands from the receptor's. The step:
     the embedding, the partial first layer over the ligand-touching CSR on top of the base rows, the other layers over the
     full CSR, pooling and heads by node_ptr. It runs at the padded shape N_cap - a GraphNorm model at the exact node
-    count instead, eager only, unless padded_graphnorm is on (`_graphs`, by node count).
+    count instead, eager only, unless padded_graphnorm is on (`_graphs`, by node count); under slot_graphnorm every slot
+    is normalised by its own rows (the slots' node_ptr as the layers' segment table).
     Variants: softmax_reuse - the base rows are H + 4 floats (PvsRaggedNodeTables.hidden is a free row width) and the
     attention is normalised over ALL edges of a row; struck - PVS_SLOTS_STRUCK slots read `screen.rec_drop`: the rows that
     had the struck atom r as a receptor-receptor neighbour take their whole first-layer row through the ligand-touching
@@ -298,7 +299,11 @@ class _ReuseStep(_Step):
         pgs = s._fast['pgs']
         if n not in pgs:
             pgs[n] = _graph_pair(s._fast, n, s.n_cap)
-            if s._gn_padded:      # both graphs: the partial first layer's and the full one of the layers behind it
+            if s._gn_slots:       # slot_graphnorm: every slot by its own rows, the slots' node_ptr as the segment table
+                node_ptr = s._fast['node_ptr']
+                pgs[n][0].set_norm_segments(node_ptr)
+                pgs[n][1].n_norm_rows_dev, pgs[n][1].n_graphs = node_ptr.data_ptr(), s.b
+            elif s._gn_padded:    # both graphs: the partial first layer's and the full one of the layers behind it
                 real_nodes = s._fast['node_ptr'][s.b:]
                 pgs[n][0].set_norm_rows(real_nodes)
                 pgs[n][1].n_norm_rows_dev = real_nodes.data_ptr()
@@ -364,7 +369,9 @@ class _CroppedStep(_Step):
         own['keep'] = torch.zeros((s.b, (s.n_rec + 63) // 64), dtype=torch.int64, device=dev)
         f = _csr_buffers(dev, s.n_cap, None, cap, **own)
         f['pg'] = _full_graph(f, s.n_cap, s.n_cap)
-        if s.graphnorm:
+        if s._gn_slots:
+            f['pg'].set_norm_segments(f['node_ptr'])
+        elif s.graphnorm:
             f['pg'].set_norm_rows(f['node_ptr'][s.b:])
         return f
 

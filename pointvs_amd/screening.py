@@ -215,6 +215,8 @@ class _ReceptorSideScreen:
         lib = _lib.lib()
         dev = h.device
         desc, params, pstruct = self._first_layer_args()
+        if getattr(self, '_gn_slots', False) and self.egnn[0].graphnorm:
+            desc.flags |= _lib.GRAPHNORM_SEGMENTS      # (g carries the slots' node_ptr: library_steps._ReuseStep._graphs)
         h_out, x_out = torch.empty_like(h), torch.empty_like(x)
         natt = torch.empty(h.shape[0], dtype=torch.float32, device=dev) if self.egnn[0].node_attention else None
         if self._l1_ws is None:
@@ -544,7 +546,17 @@ class LibraryScreen(_ReceptorSideScreen):
     nodes, so such a model runs the reuse step eager at the exact node count; with the keyword it runs at N_cap like
     every other model, eager and captured, with the statistics over the node_ptr[batch_size] real rows in front of the
     padding, a count the layers read on the device (PvsGraph.n_norm_rows_dev). The copies of one batch still normalise
-    each other, as in every batched route. Changes nothing for a model without graphnorm, nor for the plain route.
+    each other, as in every batched route, unless `slot_graphnorm=True`. Changes nothing for a model without graphnorm,
+    nor for the plain route.
+
+    slot_graphnorm (opt-in, default False; implies padded_graphnorm, giving both is fine): every slot of a GraphNorm
+    model's batch is normalised by its own rows - the reference's semantics for one complex per forward - so a pose's
+    score no longer depends on what shares its batch and equals the batch_size=1 score, at the padded shape in the one
+    captured step: both graphs of the reuse step and the cropped step's graph carry the slots' node_ptr as a segment
+    table (PreparedGraph.set_norm_segments, `_lib.GRAPHNORM_SEGMENTS`) instead of the real-row count. An empty slot is
+    a segment of length 0, a struck or cropped slot a shorter one. Covers what padded_graphnorm covers. A GraphNorm
+    model on the plain route raises NotImplementedError (fp64 models are refused as always); on a cropped screen it
+    stands in for padded_graphnorm=True. Changes nothing for a model without graphnorm: same launches, same bits.
 
     softmax_reuse (opt-in, default False; selects reuse): as for ReceptorScreen - a first layer with edge attention
     under softmax_attention takes the reuse, and with it capture(), struck slots and contact_attention.
@@ -600,8 +612,9 @@ class LibraryScreen(_ReceptorSideScreen):
 
     def __init__(self, model, rec_pos, rec_feats, batch_size, max_lig_atoms, edge_radius, intra_radius=None,
                  tasks=None, contact_attention=None, cam=None, struck=None, padded_graphnorm=False,
-                 softmax_reuse=False, crop_radius=None, crop_parents=False, cropped_maps=False):
+                 softmax_reuse=False, crop_radius=None, crop_parents=False, cropped_maps=False, slot_graphnorm=False):
         super().__init__(model, edge_radius, intra_radius, tasks, softmax_reuse)
+        self.slot_graphnorm = bool(slot_graphnorm)
         self.struck = bool(struck)
         self.crop_parents = bool(crop_parents)
         self.cropped_maps = bool(cropped_maps)
@@ -625,9 +638,10 @@ class LibraryScreen(_ReceptorSideScreen):
             raise ValueError(f'max_lig_atoms must be 1..{MAX_SCREEN_LIGAND_ATOMS} (got {max_lig_atoms})')
         _lib.require_hip(rec_pos)
         self.graphnorm = any(getattr(l, 'graphnorm', False) for l in self.egnn)
-        if self.crop_radius is not None and self.graphnorm and not self.padded_graphnorm:
+        if self.crop_radius is not None and self.graphnorm and not (self.padded_graphnorm or self.slot_graphnorm):
             raise ValueError('LibraryScreen(crop_radius=...): a GraphNorm model needs padded_graphnorm=True - the row '
-                             'count of a cropped batch is only known on the device, where the layers then read it')
+                             'count of a cropped batch is only known on the device, where the layers then read it - or '
+                             'slot_graphnorm=True')
         dev = rec_pos.device
         self.b, self.max_lig_atoms = int(batch_size), int(max_lig_atoms)
         self.slot_cap = max(self.max_lig_atoms, 64)      # what the builder validates lig_ptr against
@@ -639,7 +653,14 @@ class LibraryScreen(_ReceptorSideScreen):
         self._step = STEPS[self.route](self)
         self.reuse = self._step.has_builder         # the screen runs its own fixed-shape step, not the plain forward
         # a graphnorm model at the padded shape: the statistics over the node_ptr[batch_size] real rows, read on the device
-        self._gn_padded = self.padded_graphnorm and self.graphnorm and self._step.has_builder
+        self._gn_padded = (self.padded_graphnorm or self.slot_graphnorm) and self.graphnorm and self._step.has_builder
+        # ... and every slot by its own rows: the slots' node_ptr as the layers' segment table
+        self._gn_slots = self.slot_graphnorm and self.graphnorm
+        if self._gn_slots and not self._step.has_builder:
+            raise NotImplementedError(
+                'LibraryScreen(slot_graphnorm=True): per-slot GraphNorm runs in the fixed-shape steps (the first-layer '
+                'reuse or a cropped screen), which this model does not have - ' + self._step.capture_refusal() +
+                '; score it at batch_size=1, or mask it one complex at a time with pointvs_amd.attribution')
         self.l_cap = self.b * self.max_lig_atoms
         self.n_cap = self.l_cap + self.b * self.n_rec
         self._rec_pos = rec_pos.float().contiguous()
@@ -1068,7 +1089,7 @@ class ScreeningSweep:
     score files, `column` and `sigmoid` as on an uncropped sweep. A receptor atom that a hit's crop does not keep is not
     an atom of that hit's complex: atoms='all' means the kept atoms of each hit (PF.crop_keep), and an index tensor is
     intersected with them per hit. Under GraphNorm the copies of one batch normalise each other, as in every batched
-    route. `receptor_hotspots` stays refused under this keyword; it runs under `cropped_hotspots` - but for its
+    route, unless `slot_graphnorm=True`. `receptor_hotspots` stays refused under this keyword; it runs under `cropped_hotspots` - but for its
     attribution='atom_masking', which IS these masking methods and is opted in here.
     cropped_hotspots (opt-in, default False; needs crop_radius, ValueError otherwise; any crop radius - below the edge
     radius a ligand atom's edges simply reach kept atoms only): `receptor_hotspots` then maps every hit on the complex
@@ -1082,7 +1103,7 @@ class ScreeningSweep:
 
     def __init__(self, model, rec_pos, rec_feats, edge_radius, batch_size=32, intra_radius=None, capture=True,
                  receptor_name='receptor', tasks=None, padded_graphnorm=False, softmax_reuse=False, crop_radius=None,
-                 cropped_attribution=False, cropped_hotspots=False):
+                 cropped_attribution=False, cropped_hotspots=False, slot_graphnorm=False):
         self.model, self.rec_pos, self.rec_feats = model, rec_pos, rec_feats
         self.crop_radius = None if crop_radius is None else float(crop_radius)
         self.cropped_attribution = bool(cropped_attribution)
@@ -1101,6 +1122,9 @@ class ScreeningSweep:
         self.cropped_copies = None     # the LibraryScreen(crop_parents=True) of the masking methods of a cropped sweep
         self.crop_buckets = {}     # n_lig -> the cropped LibraryScreen of the ligands above run_library's max_lig_atoms
         self.padded_graphnorm = bool(padded_graphnorm)      # handed to every LibraryScreen of the sweep
+        self.slot_graphnorm = bool(slot_graphnorm)          # likewise
+        # (what the per-ligand ReceptorScreen route cannot give: its batches normalise over all poses)
+        self._gn_slots = self.slot_graphnorm and any(getattr(l, 'graphnorm', False) for l in list(model.layers)[1:])
         self.softmax_reuse = bool(softmax_reuse)            # handed to every screen of the sweep
         self.tasks = _resolve_tasks(model, tasks)
         self.hits = {}
@@ -1147,7 +1171,8 @@ class ScreeningSweep:
         if screen is None or screen.stale():
             screen = LibraryScreen(self.model, self.rec_pos, self.rec_feats, self.b, n_lig, self.edge_radius,
                                    self.intra_radius, tasks=self.tasks, padded_graphnorm=self.padded_graphnorm,
-                                   softmax_reuse=self.softmax_reuse, crop_radius=self.crop_radius)
+                                   softmax_reuse=self.softmax_reuse, crop_radius=self.crop_radius,
+                                   slot_graphnorm=self.slot_graphnorm)
             self.crop_buckets[n_lig] = screen
         feats = lig_feats.to(dev).float()
         scores = []
@@ -1165,6 +1190,10 @@ class ScreeningSweep:
         if self.crop_radius is not None:
             return self._run_ligand_cropped(name, lig_feats, poses, sink)
         n_poses, n_lig = int(poses.shape[0]), int(poses.shape[1])
+        if self._gn_slots:
+            raise ValueError(f'ScreeningSweep(slot_graphnorm=True): ligand {name!r} ({n_lig} atoms) would go through the '
+                             'per-ligand ReceptorScreen route, whose poses normalise each other; use run_library with '
+                             'max_lig_atoms at least the largest ligand')
         pad = (-n_poses) % self.b
         if pad:
             poses = torch.cat([poses, poses[-1:].expand(pad, -1, -1)], 0)
@@ -1223,6 +1252,10 @@ class ScreeningSweep:
         predictions_file, hits_file: optional paths (class docstring)."""
         if self.crop_radius is not None:      # (cropped slots are library slots: one path for both)
             return self.run_library(ligands, predictions_file, sigmoid, hits_file=hits_file)
+        if self._gn_slots:
+            raise ValueError('ScreeningSweep(slot_graphnorm=True).run: the per-ligand ReceptorScreen route normalises a '
+                             'GraphNorm model over all poses of a batch; use run_library (LibraryScreen slots are '
+                             'normalised one by one)')
         out, names = {}, []
         with self._sweeping(predictions_file, sigmoid, hits_file) as sink:
             for name, lig_feats, poses in ligands:
@@ -1246,6 +1279,7 @@ class ScreeningSweep:
             screen = LibraryScreen(self.model, self.rec_pos, self.rec_feats, self.b, max_atoms, self.edge_radius,
                                    self.intra_radius, tasks=self.tasks, contact_attention=layer, cam=cam, struck=struck,
                                    padded_graphnorm=self.padded_graphnorm, softmax_reuse=self.softmax_reuse,
+                                   slot_graphnorm=self.slot_graphnorm,
                                    crop_radius=self.crop_radius, crop_parents=crop_parents,
                                    cropped_maps=self.cropped_hotspots and (layer is not None or cam is not None))
             setattr(self, which, screen)
